@@ -15,19 +15,25 @@ Steps are counted like the reference: n_tables x step calls, finished tables inc
 inside the timed region and are not counted.  The roll-out enqueues a 5-step chunk as ONE launch
 (pulse_poker_rollout: state in registers across the steps, every step's observation / reward / done / action stored).
 
-`--steps K --warmup W`: W untimed steps, then blocks of EXACTLY K steps: barrier, synchronize, clock, K steps, synchronize,
-clock -- the closing barrier comes AFTER the clock is read (an 8-rank barrier is an all-reduce + host sync, tens of
-microseconds: inside a 0.2 ms block it would be a "scaling loss" made by the stopwatch); the block's time is the MAX
-over the ranks.  A 20-step block is ~0.2 ms, so the block is repeated (`config.repeats`) until the blocks sum to >= 1 s
-of GPU time and span >= 8 episodes; `ms_per_step` / `value` come from the MEDIAN block, the mean and the spread are in
-`config.blocks`.  Two workloads are timed: `active_players` sampled 2..10 per episode as the
-reference's trainer does (`value`), and forced to 10 (`active_players_10`, with its own roofline).
+`--steps K --warmup W`: W untimed steps, then ONE timed window of exactly K steps: barrier, synchronize, clock, K steps,
+synchronize, clock -- the closing barrier comes AFTER the clock is read (an 8-rank barrier is an all-reduce + host sync,
+tens of microseconds: inside a 0.2 ms window it would be a "scaling loss" made by the stopwatch); the window's time is the
+MAX over the ranks, `ms_per_step` is that time over K and `value` = tables of the job x K over it.  `--dump-outputs DIR`
+then writes what the timed window left to its caller (dump_outputs) as DIR/<name>.npy.
+
+A plain run measures only that: the `active_players`-sampled workload (2..10 per episode, as the reference's trainer
+does).  `--full` adds everything else, each part after the headline window:
+  * blocks of K steps repeated (`config.repeats`) until they sum to >= --min-timed-ms and span >= --min-episodes
+    episodes, the kernel timer on: the median, mean and spread of the blocks are in `config.blocks`;
+  * the workload with `active_players` forced to 10 (`active_players_10`, with its own roofline; SURVEY.md 8d, config 2);
+  * `roofline`, `cpu_baseline`, `trainer_loop`, `other_envs` and `finished_tables` (below).
+An explicit `--trainer-loop on` / `--other-envs on` / `--census on` / `--active-players both` runs that part without --full.
 
 Launching: `python bench.py --gpus N` spawns N rank processes itself (this parent never touches the GPU);
 under torchrun (WORLD_SIZE set) the process is a rank.  Rank 0 prints ONE JSON line.  `roofline` prices the chunk
 kernel: algorithmic bytes per launch (453 B per table-step x tables x steps in the launch) over
 its mean duration from HIP event pairs recorded on the launch stream around every launch of every 4th EPISODE of the
-timed blocks (whole episodes: a launch costs 0.55-1x the mean depending on the phase of the episode it falls in).
+repeated blocks (whole episodes: a launch costs 0.55-1x the mean depending on the phase of the episode it falls in).
 `cpu_baseline` (N = 1 only) times the oracle (oracle/poker_oracle.c, the CPU restatement of the same policy + step +
 reset + shuffle, same seeds => the same games; tests/test_poker_gpu_parity.py holds the two legs to the same episode
 lengths, done counts and reward sums) in a short-lived child process of its own, so that no OpenMP pool ever
@@ -47,6 +53,7 @@ import socket
 import statistics
 import subprocess
 import sys
+import tempfile
 import time
 from pathlib import Path
 
@@ -69,31 +76,48 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3000)
     ap.add_argument("--warmup", type=int, default=300)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline window: repeated blocks, roofline, the active_players 10 "
+                         "workload, cpu_baseline, trainer_loop, other_envs, finished_tables")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed window computed (its last step's outputs) as DIR/<name>.npy")
     ap.add_argument("--tables", type=int, default=65536, help="tables per GPU (weak scaling)")
-    ap.add_argument("--active-players", choices=["both", "sampled", "10"], default="both",
+    ap.add_argument("--active-players", choices=["auto", "both", "sampled", "10"], default="auto",
                     help="sampled: 2..10 per episode like the reference's trainer (= `value`); 10: every seat in every hand "
-                         "(the P = 10 case the 453 B/step figure prices); both: `value` from sampled, a sub-record for 10")
+                         "(the P = 10 case the 453 B/step figure prices); both: `value` from sampled, a sub-record for 10; "
+                         "auto: both with --full, else sampled")
     ap.add_argument("--stop-rule", choices=["lagged", "sync"], default="lagged")
     ap.add_argument("--max-episode-steps", type=int, default=40,
                     help="episode cap: the reference's close-on-aggressor rule livelocks tables whose last ACTIVE seat "
                          "keeps calling against all-ins (SURVEY.md A.3), so >20 %% of tables may never finish; its "
                          "published runs average 31-35 steps per episode (results/PokerGPU/runs/run_2..8.yaml)")
-    ap.add_argument("--min-timed-ms", type=float, default=2000.0, help="repeat the K-step block until the blocks sum to this")
+    ap.add_argument("--min-timed-ms", type=float, default=2000.0, help="--full: repeat the K-step block until the blocks sum to this")
     ap.add_argument("--min-episodes", type=int, default=8, help="... and span at least this many episodes")
     ap.add_argument("--max-repeats", type=int, default=20000)
     ap.add_argument("--per-step-launches", action="store_true", help="one launch per step instead of one per chunk (A/B)")
     ap.add_argument("--stop-exchange", choices=["auto", "host", "shm", "rccl"], default="auto",
                     help="how the ranks exchange the stop rule's counts (auto: shared memory with the nccl backend, torch.distributed with gloo)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline child")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU time of the cpu_baseline sample")
-    ap.add_argument("--trainer-loop", choices=["auto", "on", "off"], default="auto", help="auto = on (N > 1: data-parallel learner, the per-GPU size only)")
+    ap.add_argument("--trainer-loop", choices=["auto", "on", "off"], default="auto",
+                    help="auto = on with --full (N > 1: data-parallel learner, the per-GPU size only)")
     ap.add_argument("--trainer-episodes", type=int, default=12)
     ap.add_argument("--trainer-tables-large", type=int, default=2000000, help="second trainer-loop size (the reference's published N_GAMES); 0 = skip")
-    ap.add_argument("--other-envs", choices=["auto", "on", "off"], default="auto", help="2048 / Q-learning / Particle2D / Blackjack records; auto: at N = 1")
-    ap.add_argument("--census", choices=["auto", "on", "off"], default="auto", help="share of table-steps on finished tables; auto: at N = 1")
+    ap.add_argument("--other-envs", choices=["auto", "on", "off"], default="auto", help="2048 / Q-learning / Particle2D / Blackjack records; auto: at N = 1 with --full")
+    ap.add_argument("--census", choices=["auto", "on", "off"], default="auto", help="share of table-steps on finished tables; auto: at N = 1 with --full")
     ap.add_argument("--role", choices=["launcher", "rank", "cpu"], default="launcher", help=argparse.SUPPRESS)
     ap.add_argument("--inproc", action="store_true", help="measure in this process (what a profiler wraps); same as --role rank")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def headline_modes(args):
+    """The `active_players` workloads to time, the headline's first."""
+    if args.active_players == "auto":
+        return ["sampled", "10"] if args.full else ["sampled"]
+    return ["sampled", "10"] if args.active_players == "both" else [args.active_players]
 
 
 _TYPES_CACHE = {}
@@ -424,6 +448,38 @@ def finished_tables_census(args, device, episodes=8):
                     "a step on a finished table still writes its observation, reward (0) and done flag"}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT_BYTES = 64_000_000       # all ranks' files together
+
+
+def dump_outputs(out_dir, env, actions, episode_stats, rank, world):
+    """What the timed window left to a caller of the roll-out, per table: the observation, the last step's reward and done
+    flag, the action buffer and the seats' stacks (float32: every value is exact there), plus the job's cumulative episode
+    sums (float64).  Where the window ended on an episode boundary, observation / done / stacks are the next episode's reset
+    state, as the caller receives them.  A batch whose files would pass DUMP_LIMIT_BYTES is written as a fixed sample of its
+    tables (seeded: the same tables on every run); `table_id.npy` (float64) names the tables written.  With N > 1 ranks the
+    names carry `_rank<r>`."""
+    import numpy as np
+    import torch
+    arrays = {"obs": env.obs, "reward": env._rewards[1 - env._pp], "done": env.is_done, "action": actions, "stacks": env.stacks}
+    n = env.n_games
+    per_table = 8 + 4 * sum(t[0].numel() for t in arrays.values())
+    rows = min(n, (DUMP_LIMIT_BYTES // world - 4096) // per_table)
+    table_id = np.arange(n, dtype=np.int64)
+    if rows < n:
+        table_id = np.sort(np.random.default_rng(SEED).choice(n, rows, replace=False))
+        sel = torch.from_numpy(table_id).to(env.device)
+        arrays = {k: t.index_select(0, sel) for k, t in arrays.items()}
+    out = {k: t.to(torch.float32).cpu().numpy() for k, t in arrays.items()}
+    out["table_id"] = (table_id + env.table_id0).astype(np.float64)
+    out["episode_stats"] = np.asarray([episode_stats["last_step_reward_sum"], episode_stats["tables_done_at_episode_end"]], dtype=np.float64)
+    path = Path(out_dir)
+    path.mkdir(parents=True, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for k, a in out.items():
+        np.save(path / f"{k}{suffix}.npy", a)
+
+
 # ------------------------------------------------------------------------------------------------ one rank
 def _sha_of_kernel_sources():
     import hashlib
@@ -564,71 +620,88 @@ def main_rank(args):
     rule = LaggedDoneCount(device, N, TERMINATION_THRESHOLD, lag=0 if args.stop_rule == "sync" else 1, n_global=N * world,
                            exchange=None if args.stop_exchange == "auto" else args.stop_exchange)
     actions = torch.zeros(N, dtype=torch.long, device=device)
-    timer = RolloutTimer()
+    timer = RolloutTimer() if args.full else None
 
-    def measure(mode):
-        """Warm-up, then blocks of exactly args.steps steps: barrier -> sync -> t0 -> steps -> sync -> dt; the MAX over
-        the ranks of dt is the block's time.  No collective and no barrier between the two clock reads."""
+    def measure(mode, dump_dir=None):
+        """Warm-up, then ONE window of exactly args.steps steps: barrier -> sync -> t0 -> steps -> sync -> dt; the MAX over
+        the ranks of dt is the window's time (`value`, `ms_per_step`).  No collective and no barrier between the two clock
+        reads.  `dump_dir`: the window's outputs are written there right after it.  --full: then the blocks of args.steps
+        steps, repeated with the kernel timer on (`blocks`, `rank_spread`, `roofline`)."""
         stats = EpisodeStatsReducer(env, device, world)
         loop = EpisodeLoop(env, rule, actions, args.max_episode_steps, on_episode_end=stats, active_players=mode)
         if rank == 0:
             _log(f"active_players {mode}: warm-up {args.warmup} steps ...")
         barrier()                              # the ranks start together (a rank seconds behind would stall every other rank's launches)
         loop.run_steps(args.warmup)
-        torch.cuda.synchronize()
-        timer.collect()
         if rank == 0:
-            _log(f"active_players {mode}: timing blocks of {args.steps} steps ...")
-        blocks, fastest, own, episodes0 = [], [], [], loop.episode
-        while True:
+            _log(f"active_players {mode}: timing {args.steps} steps ...")
+        episodes0 = loop.episode
+
+        def timed_block(tm=None):
             barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            ran = loop.run_steps(args.steps, timer=timer, time_every=TIME_EVERY)
+            ran = loop.run_steps(args.steps, timer=tm, time_every=TIME_EVERY if tm is not None else 0)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0              # read BEFORE anything collective
             assert ran == args.steps
-            hi, lo = max_min_over_ranks(dt)
-            blocks.append(hi); fastest.append(lo); own.append(dt)      # (hi is identical on every rank: so is the decision below)
-            enough = sum(blocks) * 1e3 >= args.min_timed_ms and loop.episode - episodes0 >= args.min_episodes
-            if enough or len(blocks) >= args.max_repeats:
-                break
-        sum_ms, n_launches, n_steps_timed = timer.collect()
-        med = statistics.median(blocks)
+            return dt
+
+        window = max_over_ranks(timed_block())
         total_tables = N * world
         rec = {"active_players": "sampled 2..10 per episode (host RNG seeded 0)" if mode == "sampled" else "10 in every episode",
-               "value": total_tables * args.steps / med, "ms_per_step": med / args.steps * 1e3,
-               "repeats": len(blocks), "episodes_timed": loop.episode - episodes0,
-               "blocks": {"median_ms": med * 1e3, "mean_ms": statistics.fmean(blocks) * 1e3, "min_ms": min(blocks) * 1e3,
-                          "max_ms": max(blocks) * 1e3, "sum_ms": sum(blocks) * 1e3,
-                          "value_from_mean": total_tables * args.steps / statistics.fmean(blocks)},
-               "episode_stats": stats.totals(),
-               # a straggling host shows here: per block the slowest and the fastest rank's time, and every rank's own sum
-               "rank_spread": {"slowest_over_fastest_mean": statistics.fmean(h / max(l, 1e-12) for h, l in zip(blocks, fastest)),
-                               "slowest_over_fastest_max": max(h / max(l, 1e-12) for h, l in zip(blocks, fastest)),
-                               "per_rank_sum_ms": [v * 1e3 for v in gather_over_ranks(sum(own))]},
-               "stop_rule": rule.stats() if hasattr(rule, "stats") else None,
-               "roofline": roofline_record(args, N, sum_ms, n_launches, n_steps_timed, mode) if rank == 0 else None}
+               "value": total_tables * args.steps / window, "ms_per_step": window / args.steps * 1e3,
+               "episodes_timed": loop.episode - episodes0}
+        if dump_dir is not None:
+            dump_outputs(dump_dir, env, actions, stats.totals(), rank, world)
+        if args.full:
+            torch.cuda.synchronize()
+            timer.collect()
+            blocks, fastest, own, episodes1 = [], [], [], loop.episode
+            while True:
+                dt = timed_block(timer)
+                hi, lo = max_min_over_ranks(dt)
+                blocks.append(hi); fastest.append(lo); own.append(dt)      # (hi is identical on every rank: so is the decision below)
+                enough = sum(blocks) * 1e3 >= args.min_timed_ms and loop.episode - episodes1 >= args.min_episodes
+                if enough or len(blocks) >= args.max_repeats:
+                    break
+            sum_ms, n_launches, n_steps_timed = timer.collect()
+            med = statistics.median(blocks)
+            rec.update({
+                "repeats": len(blocks),
+                "blocks": {"median_ms": med * 1e3, "mean_ms": statistics.fmean(blocks) * 1e3, "min_ms": min(blocks) * 1e3,
+                           "max_ms": max(blocks) * 1e3, "sum_ms": sum(blocks) * 1e3, "episodes": loop.episode - episodes1,
+                           "value_from_median": total_tables * args.steps / med,
+                           "value_from_mean": total_tables * args.steps / statistics.fmean(blocks)},
+                # a straggling host shows here: per block the slowest and the fastest rank's time, and every rank's own sum
+                "rank_spread": {"slowest_over_fastest_mean": statistics.fmean(h / max(l, 1e-12) for h, l in zip(blocks, fastest)),
+                                "slowest_over_fastest_max": max(h / max(l, 1e-12) for h, l in zip(blocks, fastest)),
+                                "per_rank_sum_ms": [v * 1e3 for v in gather_over_ranks(sum(own))]},
+                "roofline": roofline_record(args, N, sum_ms, n_launches, n_steps_timed, mode) if rank == 0 else None})
+            if rank == 0:
+                _log(f"active_players {mode}: {len(blocks)} blocks, {sum(blocks) * 1e3:.1f} ms, {rec['blocks']['value_from_median']:.4g} env-steps/s")
+        rec["episode_stats"] = stats.totals()
+        rec["stop_rule"] = rule.stats() if hasattr(rule, "stats") else None
         if rank == 0:
-            _log(f"active_players {mode}: {len(blocks)} blocks, {sum(blocks) * 1e3:.1f} ms, {rec['value']:.4g} env-steps/s")
+            _log(f"active_players {mode}: {args.steps} steps in {window * 1e3:.1f} ms, {rec['value']:.4g} env-steps/s")
         if world > 1:                                        # every rank: a rehearsal's log shows that the ranks stayed in step
-            _log(f"rank {rank}/{world} active_players {mode}: episodes {loop.episode}, blocks {len(blocks)}, own time {sum(own) * 1e3:.1f} ms, "
+            _log(f"rank {rank}/{world} active_players {mode}: episodes {loop.episode}, blocks {rec.get('repeats', 0)}, "
                  f"job totals {rec['episode_stats']}, stop rule {rec['stop_rule']}")
         return rec
 
     if rank == 0:
         _log(f"environment ready ({N} tables/GPU x {world}, stop-rule exchange: {rule.exchange})")
-    modes = ["sampled", "10"] if args.active_players == "both" else [args.active_players]
-    records = {m: measure(m) for m in modes}
+    modes = headline_modes(args)
+    records = {m: measure(m, args.dump_outputs if m == modes[0] else None) for m in modes}
     main = records[modes[0]]
 
     trainer = census = other = None
     solo = world == 1
-    if args.census == "on" or (args.census == "auto" and solo):
+    if args.census == "on" or (args.census == "auto" and solo and args.full):
         if rank == 0:
             _log("finished-tables census ...")
             census = finished_tables_census(args, device)
-    if args.trainer_loop in ("on", "auto"):                  # auto: at every N (N > 1: the data-parallel learner, per-GPU size only)
+    if args.trainer_loop == "on" or (args.trainer_loop == "auto" and args.full):      # at every N (N > 1: the data-parallel learner, per-GPU size only)
         rule.close()
         del env
         torch.cuda.empty_cache()
@@ -644,7 +717,7 @@ def main_rank(args):
                 t = trainer[-1]
                 _log(f"rank {rank}/{world} trainer loop: episodes {t['episodes']}, steps {t['steps']}, first episode reward sums (job-wide) "
                      f"{[round(x, 3) for x in t['episode_reward_sums']]}, weights equal on all ranks: {t['weights_equal_on_all_ranks']}")
-    if (args.other_envs == "on" or (args.other_envs == "auto" and solo)) and rank == 0:
+    if (args.other_envs == "on" or (args.other_envs == "auto" and solo and args.full)) and rank == 0:
         _log("other environments ...")
         from tools.bench_envs import gpu_records
         other = gpu_records(device)
@@ -660,17 +733,17 @@ def main_rank(args):
             "config": {"workload": workload(modes[0]),
                        "tables_per_gpu": N, "n_players": 10, "stop_rule": args.stop_rule, "stop_rule_exchange": rule.exchange,
                        "max_episode_steps": args.max_episode_steps, "steps_per_launch": CHECK_INTERVAL if not args.per_step_launches else 1,
-                       "repeats": main["repeats"], "episodes_timed": main["episodes_timed"], "blocks": main["blocks"],
+                       "repeats": main.get("repeats"), "episodes_timed": main["episodes_timed"], "blocks": main.get("blocks"),
                        "episode_stats": main["episode_stats"], "min_timed_ms": args.min_timed_ms,
                        # two check intervals per launch unless the rule fell back: a launch that waited in vain for its
                        # host's verdict (a stalled rank) is counted here and the run goes on with one check interval per launch
                        "paired_launches": bool(main["stop_rule"]["pairs"]) if main.get("stop_rule") else False,
                        "verdict_timeouts": int(main["stop_rule"]["verdict_timeouts"]) if main.get("stop_rule") else 0,
-                       "rank_spread": main["rank_spread"],
+                       "rank_spread": main.get("rank_spread"),
                        "timed_window": "barrier, sync, t0, K steps, sync, dt (no barrier or collective between the clock reads); MAX over ranks",
                        "parallelism": f"tables sharded x{world}, no data-path collective; stop-rule count exchanged per check point, episode "
                                       f"statistics all-reduced every {REPORT_EVERY}th episode and at the end"},
-            "roofline": main["roofline"], "trainer_loop": trainer, "finished_tables": census, "other_envs": other,
+            "full": args.full, "roofline": main.get("roofline"), "trainer_loop": trainer, "finished_tables": census, "other_envs": other,
         }
         if len(modes) > 1:
             sub = dict(records[modes[1]])
@@ -729,72 +802,60 @@ def run_cpu_child(args, argv):
 
 
 def launcher(args, argv):
-    """This process never touches the GPU: it runs the CPU baseline in one child, then N rank children
+    """This process never touches the GPU: with --full it runs the CPU baseline in one child, then N rank children
     (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, one GPU each), and prints rank 0's JSON line.  A rank set that
-    produces no line within the limit is killed, its stderr (with the watchdog's stack dump) is kept under
-    gpurun_out/bench_wedge_<time>.log, and the measurement is repeated ONCE; the line says so (`attempts`)."""
+    produces no line within the limit is killed and the run fails with every rank's stderr (the watchdog's stack dump in
+    it); it is not started again: a rank that hung or faulted the device would meet the same state."""
     cpu = None
-    if args.gpus == 1 and not args.no_cpu_baseline:
+    if args.gpus == 1 and args.full and not args.no_cpu_baseline:
         cpu = run_cpu_child(args, argv)
     limit = int(os.environ.get("PULSE_BENCH_ATTEMPT_S", "420"))
     base = _passthrough_args(argv)
-    for attempt in (1, 2):
-        port = _free_port()
-        procs, errs = [], []
-        for r in range(args.gpus):
-            # a clean rendezvous of our own: nothing of an enclosing torchrun worker's (TORCHELASTIC_USE_AGENT_STORE would
-            # make rank 0 look for the agent's store on OUR port and wait for ever)
-            env = {k: v for k, v in os.environ.items() if not k.startswith(("TORCHELASTIC_", "TORCH_NCCL_ASYNC")) and k not in ("GROUP_RANK", "ROLE_RANK", "ROLE_NAME", "LOCAL_WORLD_SIZE", "GROUP_WORLD_SIZE", "ROLE_WORLD_SIZE")}
-            env.update(RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(args.gpus), MASTER_ADDR="127.0.0.1",
-                       MASTER_PORT=str(port), PULSE_BENCH_WATCHDOG_S=str(max(30, limit - 30)))
-            err = open(f"/tmp/pulse_bench_{os.getpid()}_a{attempt}_r{r}.err", "w+")
-            errs.append(err)
-            procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__), *base, "--role", "rank"],
-                                          stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, stderr=err, text=True, env=env))
-        out, timed_out = "", False
-        try:
-            out, _ = procs[0].communicate(timeout=limit)
-            for p in procs[1:]:
-                p.wait(timeout=60)
-        except subprocess.TimeoutExpired:
-            timed_out = True
-            for p in procs:
-                if p.poll() is None:
-                    p.kill()
-            for p in procs:
-                try:
-                    p.wait(timeout=20)
-                except subprocess.TimeoutExpired:
-                    pass
-        logs = []
-        for r, err in enumerate(errs):
-            err.seek(0)
-            logs.append(f"==== rank {r} (exit {procs[r].returncode}) ====\n{err.read()}")
-            err.close()
-            os.unlink(err.name)
-        sys.stderr.write("\n".join(logs) + "\n")
-        lines = [ln for ln in out.splitlines() if ln.startswith("{")]
-        ok = not timed_out and all(p.returncode == 0 for p in procs) and lines
-        if ok:
-            line = json.loads(lines[-1])
-            if cpu and cpu.get("other_envs") is not None:           # the child's per-environment CPU samples join their GPU records
-                per_env = cpu.pop("other_envs")
-                for rec in line.get("other_envs") or []:
-                    rec["cpu_baseline"] = per_env.get(rec.get("name"))
-            line["cpu_baseline"] = cpu
-            line["attempts"] = attempt
-            print(json.dumps(line), flush=True)
-            return 0
-        wedge = ROOT / "gpurun_out" / f"bench_wedge_{time.strftime('%Y%m%d_%H%M%S')}_a{attempt}.log"
-        try:
-            wedge.parent.mkdir(exist_ok=True)
-            wedge.write_text(f"attempt {attempt}: timed_out={timed_out}, exits={[p.returncode for p in procs]}\n" + "\n".join(logs) + "\nstdout:\n" + out)
-            _log(f"attempt {attempt} failed (timed out: {timed_out}); record kept in {wedge}")
-        except OSError:
-            _log(f"attempt {attempt} failed (timed out: {timed_out})")
-        if any(p.returncode == 2 for p in procs):                    # argparse / usage error: repeating will not help
-            return 2
-    return 1
+    port = _free_port()
+    procs, errs = [], []
+    for r in range(args.gpus):
+        # a clean rendezvous of our own: nothing of an enclosing torchrun worker's (TORCHELASTIC_USE_AGENT_STORE would
+        # make rank 0 look for the agent's store on OUR port and wait for ever)
+        env = {k: v for k, v in os.environ.items() if not k.startswith(("TORCHELASTIC_", "TORCH_NCCL_ASYNC")) and k not in ("GROUP_RANK", "ROLE_RANK", "ROLE_NAME", "LOCAL_WORLD_SIZE", "GROUP_WORLD_SIZE", "ROLE_WORLD_SIZE")}
+        env.update(RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(args.gpus), MASTER_ADDR="127.0.0.1",
+                   MASTER_PORT=str(port), PULSE_BENCH_WATCHDOG_S=str(max(30, limit - 30)))
+        err = tempfile.TemporaryFile("w+")
+        errs.append(err)
+        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__), *base, "--role", "rank"],
+                                      stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, stderr=err, text=True, env=env))
+    out, timed_out = "", False
+    try:
+        out, _ = procs[0].communicate(timeout=limit)
+        for p in procs[1:]:
+            p.wait(timeout=60)
+    except subprocess.TimeoutExpired:
+        timed_out = True
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+        for p in procs:
+            try:
+                p.wait(timeout=20)
+            except subprocess.TimeoutExpired:
+                pass
+    logs = []
+    for r, err in enumerate(errs):
+        err.seek(0)
+        logs.append(f"==== rank {r} (exit {procs[r].returncode}) ====\n{err.read()}")
+        err.close()
+    sys.stderr.write("\n".join(logs) + "\n")
+    lines = [ln for ln in out.splitlines() if ln.startswith("{")]
+    if timed_out or not all(p.returncode == 0 for p in procs) or not lines:
+        _log(f"rank set failed (timed out: {timed_out}, exits {[p.returncode for p in procs]})")
+        return 2 if any(p.returncode == 2 for p in procs) else 1          # 2: argparse / usage error
+    line = json.loads(lines[-1])
+    if cpu and cpu.get("other_envs") is not None:           # the child's per-environment CPU samples join their GPU records
+        per_env = cpu.pop("other_envs")
+        for rec in line.get("other_envs") or []:
+            rec["cpu_baseline"] = per_env.get(rec.get("name"))
+    line["cpu_baseline"] = cpu
+    print(json.dumps(line), flush=True)
+    return 0
 
 
 if __name__ == "__main__":

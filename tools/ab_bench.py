@@ -13,7 +13,7 @@ extra = [a for a in sys.argv[1:] if not a.endswith(".so")]
 for rnd in range(2):
     for lib in libs:
         env = dict(os.environ, PULSE_LIB=os.path.abspath(lib))
-        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--inproc", "--no-cpu-baseline", "--trainer-loop", "off", "--other-envs", "off",
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--inproc", "--no-cpu-baseline", "--trainer-loop", "off", "--other-envs", "off",
                             "--census", "off", "--active-players", "sampled", "--min-timed-ms", "600", *extra], env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
         lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
         if p.returncode != 0 or not lines:

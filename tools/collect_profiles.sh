@@ -12,7 +12,7 @@ PARTS=${2:-"poker envs trainer harness bench rehearsal"}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-B="python bench.py --inproc --no-cpu-baseline --trainer-loop off --other-envs off --census off --min-timed-ms 50"
+B="python bench.py --full --inproc --no-cpu-baseline --trainer-loop off --other-envs off --census off --min-timed-ms 50"
 P="rocprofv3 --kernel-trace --output-format csv"
 if [[ $PARTS == *poker* ]]; then
 # ... and at 65,536 tables once more in the DRIVER's form (--steps 20 --warmup 5: blocks of 20 steps cut some launches to one
@@ -45,8 +45,8 @@ fi
 if [[ $PARTS == *trainer* ]]; then
   # the bench's own trainer_loop leg (same tool, episodes and warm-up as the number in the bench line) under the kernel trace
   rm -rf $OUT/trainer
-  echo "[collect] $(date +%T) trainer loop"; $T $P --stats -d $OUT/trainer -- python bench.py --inproc --no-cpu-baseline --trainer-loop on --trainer-tables-large 0 --other-envs off --census off --active-players sampled --steps 200 --warmup 40 --min-timed-ms 10 > $OUT/trainer_trace.log 2>&1
-  $T python bench.py --inproc --no-cpu-baseline --trainer-loop on --other-envs off --census off --active-players sampled --steps 200 --warmup 40 --min-timed-ms 10 > $OUT/trainer_plain.log 2> $OUT/trainer_plain.err
+  echo "[collect] $(date +%T) trainer loop"; $T $P --stats -d $OUT/trainer -- python bench.py --full --inproc --no-cpu-baseline --trainer-loop on --trainer-tables-large 0 --other-envs off --census off --active-players sampled --steps 200 --warmup 40 --min-timed-ms 10 > $OUT/trainer_trace.log 2>&1
+  $T python bench.py --full --inproc --no-cpu-baseline --trainer-loop on --other-envs off --census off --active-players sampled --steps 200 --warmup 40 --min-timed-ms 10 > $OUT/trainer_plain.log 2> $OUT/trainer_plain.err
 fi
 if [[ $PARTS == *trainer* ]]; then
   # ... and the same loop at the reference's published size, with the SQ counters of its kernels (tools/trainer_profile_at.sh)
@@ -69,14 +69,14 @@ if [[ $PARTS == *harness* ]]; then
   done
 fi
 if [[ $PARTS == *bench* ]]; then
-  echo "[collect] $(date +%T) default bench (the driver's line)"; $T python bench.py > $OUT/bench_default.log 2> $OUT/bench_default.err
-  $T python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_style.log 2> $OUT/bench_driver_style.err
+  echo "[collect] $(date +%T) full bench line, default and 20-step blocks"; $T python bench.py --full > $OUT/bench_default.log 2> $OUT/bench_default.err
+  $T python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_style.log 2> $OUT/bench_driver_style.err
 fi
 if [[ $PARTS == *rehearsal* ]]; then
   # several ranks on ONE device (gloo): what a one-GPU box can rehearse of --gpus N
   for R in "2 host" "2 shm" "3 shm"; do set -- $R
     echo "[collect] $(date +%T) rehearsal: $1 ranks, $2 exchange"
-    PULSE_BENCH_ONE_DEVICE=1 $T python bench.py --gpus $1 --steps 600 --warmup 100 --min-timed-ms 100 --stop-exchange $2 > $OUT/rehearsal_${1}ranks_$2.log 2> $OUT/rehearsal_${1}ranks_$2.err || echo "rehearsal $R failed"
+    PULSE_BENCH_ONE_DEVICE=1 $T python bench.py --full --gpus $1 --steps 600 --warmup 100 --min-timed-ms 100 --stop-exchange $2 > $OUT/rehearsal_${1}ranks_$2.log 2> $OUT/rehearsal_${1}ranks_$2.err || echo "rehearsal $R failed"
   done
 fi
 python tools/summarize_profiles.py $TAG

@@ -31,7 +31,7 @@ while done < episodes:
 p = torch.cat([x.detach().reshape(-1) for x in q.network.parameters()])
 assert bool(torch.isfinite(p).all()), "parameters went non-finite"
 print("[soak] trainer ok; env-only loop ...", flush=True)
-r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--inproc", "--no-cpu-baseline", "--trainer-loop", "off", "--other-envs", "off", "--census", "off",
+r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--inproc", "--no-cpu-baseline", "--trainer-loop", "off", "--other-envs", "off", "--census", "off",
                     "--min-timed-ms", str(env_seconds * 1000)], capture_output=True, text=True, timeout=env_seconds * 4 + 300)
 print(r.stderr[-600:])
 assert r.returncode == 0, "bench failed"

@@ -4,7 +4,7 @@
 OUT=gpurun_out/${1:-trainer_trace}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf $OUT
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv --stats -d $OUT -- python bench.py --inproc --no-cpu-baseline --trainer-loop on --trainer-tables-large 0 --other-envs off --census off --active-players sampled --steps 200 --warmup 40 --min-timed-ms 10 > $OUT.log 2>&1 || exit 1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv --stats -d $OUT -- python bench.py --full --inproc --no-cpu-baseline --trainer-loop on --trainer-tables-large 0 --other-envs off --census off --active-players sampled --steps 200 --warmup 40 --min-timed-ms 10 > $OUT.log 2>&1 || exit 1
 f=$(ls $OUT/*/*kernel_stats.csv | head -1)
 python - "$f" <<PY
 import csv, sys
