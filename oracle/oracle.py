@@ -26,7 +26,7 @@ ACTIVE, FOLDED, ALLIN, SITOUT = 0, 1, 2, 3
 
 def build(force: bool = False) -> Path:
     so = _HERE / "liboracle.so"
-    srcs = [_HERE / "handranks_oracle.c", _HERE / "poker_oracle.c", _HERE / "envs_oracle.c"]
+    srcs = [_HERE / "handranks_oracle.c", _HERE / "poker_oracle.c", _HERE / "envs_oracle.c", _HERE / "qnet_oracle.c"]
     if force or not so.exists() or any(s.stat().st_mtime > so.stat().st_mtime for s in srcs):
         subprocess.check_call(["make", "-C", str(_HERE), "-B", "liboracle.so"], stdout=subprocess.DEVNULL)
     return so
@@ -348,6 +348,16 @@ def qnet_adamw(params, target, grad, m, v, count: int, t: int, lr, wd, beta1=0.9
                     grad.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), C.c_int(count),
                     C.c_long(t), C.c_float(lr), C.c_float(wd), C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
                     C.c_float(max_norm), C.c_int(update_freq)))
+
+
+def qnet_keep_masks(seed: int, step: int, table_ids, drop_p: float = 0.1) -> np.ndarray:
+    """oracle/qnet_oracle.c: the training forward's dropout keep masks -> bool[len(table_ids), 192] (columns 0..127: the
+    dropout after layer 2, 128..191: after layer 3) for the rows of the given global table ids at `step`."""
+    ids = np.ascontiguousarray(table_ids, dtype=np.uint64).ravel()
+    keep = np.zeros((ids.size, 192), dtype=np.uint8)
+    lib().oracle_qnet_keep_masks(C.c_uint64(seed), C.c_uint64(step), ids.ctypes.data_as(C.c_void_p), C.c_int(ids.size),
+                                 C.c_float(drop_p), keep.ctypes.data_as(C.c_void_p))
+    return keep.astype(bool)
 
 
 def philox4x32(seed: int, subseq: int, offset: int) -> np.ndarray:

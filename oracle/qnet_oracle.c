@@ -83,6 +83,15 @@ static int drop_keep(uint64_t seed, uint64_t g, uint64_t step, int u, uint32_t t
     return u16 >= thr;
 }
 
+/* The dropout keep masks of oracle_qnet_train_grads for a list of rows: keep[i * 192 + u] = 1 when hidden unit u
+ * (0..127 layer 2, 128..191 layer 3) of global table ids[i] is kept at `step` (the draw of drop_keep above). */
+void oracle_qnet_keep_masks(uint64_t seed, uint64_t step, const uint64_t* ids, int n, float drop_p, uint8_t* keep) {
+    const uint32_t thr = (uint32_t)(drop_p * 65536.0f);
+    #pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; i++)
+        for (int u = 0; u < 192; u++) keep[(size_t)i * 192 + u] = (uint8_t)drop_keep(seed, ids[i], step, u, thr);
+}
+
 int oracle_qnet_train_grads(int state_dim, int n_actions, const float* const* w, const float* const* b,
                             const float* const* tw, const float* const* tb, const float* states, long stride,
                             const int64_t* actions, const float* rewards, const float* next_states, long next_stride,

@@ -327,17 +327,22 @@ class PokerQNetwork(nn.Module):
     def train_step(self, states, actions, rewards, next_states, dones):
         """Player.py:255-294 -- the reference's signature.  On the GPU the update runs on the native kernels
         (`train_step_native` with every passed row a candidate; the filter on the seat status, :261, is the kernel's):
-        no boolean indexing, no `.any()` sync, no autograd graph.  Returns the MSE loss as a 0-d DEVICE tensor
-        (`float(loss)` works and only then waits for the GPU; 0 when no row was valid, as the reference's early return).
+        no boolean indexing, no autograd graph.  Like the reference (:261-262) it asks the host whether any row is valid (one
+        sync) and returns 0 before the update and the step count when none is.  Returns the MSE loss as a 0-d DEVICE tensor
+        of its own (`float(loss)` waits for the GPU; the report buffer it is copied from is shared by every call).
         Moments and step count of this path live in its own buffers (`train_step_native`), not in `self.optimizer`;
         dropout draws are Philox (a documented deviation).  `train_step_torch` is the same update on PyTorch autograd
         with the reference's own op sequence -- what the reference-fixture test compares (and the path of a CPU module)."""
         if self._flat is None or not (torch.is_tensor(states) and states.is_cuda):
             return self.train_step_torch(states, actions, rewards, next_states, dones)
+        valid = (states[:, 12] == 0) | (states[:, 12] == 2)                        # seat status ACTIVE or ALLIN (:261)
+        if states.shape[0] == 0 or not bool(valid.any()):                          # :262: return before the update and the step count
+            return torch.zeros((), dtype=torch.float32, device=states.device)
         report = self.train_step_native(states, actions, rewards, next_states, dones, None)
+        loss = report[1].clone()                   # the report buffer is shared by every call: the caller keeps its own loss
         if self.step_count % 1000 == 0:                                            # Player.py:281-287 (the Q / reward means are not kept)
-            print(f"Step {self.step_count} | Avg Loss: {float(report[1]):.2f} | Epsilon: {self.epsilon:.4f}")
-        return report[1]
+            print(f"Step {self.step_count} | Avg Loss: {float(loss):.2f} | Epsilon: {self.epsilon:.4f}")
+        return loss
 
     def check_native_report(self, report_host=None, wait=True):
         """Raises if a native update was called off inside its launch (report[3] = -1, pulse_env.h: PulseQNetTrain).
