@@ -474,7 +474,22 @@ typedef struct PulseQNetTrain {
     int64_t meet_wait_ticks;        /* how long a workgroup waits at that meeting, in ticks of the 100 MHz clock; 0 = 5 s */
     int32_t debug_meet_extra;       /* test hook: arrivals the meeting expects beyond the grid's own (> 0: it never comes about) */
     int32_t reserved0;
+    float* stability;               /* NULL: off (the launches are exactly those without it); else device fp32[16], below */
 } PulseQNetTrain;
+/* Training-stability metrics (PulseQNetTrain.stability; the reference's utils/stability.py), taken inside the launches above:
+ * the training launch totals |td| and Q(s, a) (the train-mode, dropout value) over the rows next to the loss terms, the
+ * reduce / AdamW launch writes
+ *   per-call block, every call that launches:  [0] rows, [1] mean |td|, [2] mean Q(s, a), [3] min Q(s, a), [4] max Q(s, a),
+ *                  [5] gradient norm before clipping, [6] clipped (1 if [5] > max_grad_norm, else 0), [7] loss;
+ *                  all 0 when rows is 0 or the meeting was called off (report[3] = -1)
+ *   accumulator, added to only by calls with rows > 0:  [8] measured steps, [9] sum of [1], [10] sum of [2], [11] min of [3],
+ *                  [12] max of [4], [13] sum of [6], [14] sum of [7], [15] 0.
+ * Cleared state of the accumulator: [11] = +inf, [12] = -inf, everything else 0 (PokerQNetwork.clear_stability_metrics); the
+ * per-call block needs no clearing.  An episode's values are then td_error = [9] / [8], q_mean = [10] / [8] (the mean of the
+ * per-step means, not over rows), q_min = [11], q_max = [12], clip_rate = [13] / [8] (0 everywhere while [8] == 0).
+ * pulse_qnet_train_grads (data-parallel) leaves the UNNORMALISED totals of its rows in [0..4] = {rows, sum |td|, sum Q,
+ * min Q, max Q}; the caller all-reduces [0..2] with SUM, [3] with MIN and [4] with MAX (one MAX all-reduce of {-[3], [4]} does
+ * both), then pulse_qnet_train_apply normalises them and accumulates: the metrics of the job-wide batch, as the gradient. */
 int pulse_qnet_param_count(int32_t state_dim, int32_t n_actions);
 int pulse_qnet_slice_floats(void);
 /* How many reduce + AdamW launches of this process have called their meeting off so far (a count in pinned host memory the

@@ -67,7 +67,8 @@ class QNetTrain(C.Structure):
         "params", "target_params", "grad", "exp_avg", "exp_avg_sq", "step", "stats", "report", "partials")] + [(n, C.c_float) for n in (
             "lr", "weight_decay", "beta1", "beta2", "eps", "max_grad_norm", "gamma", "dropout_p")] + [
         ("update_freq", C.c_int32), ("max_blocks", C.c_int32), ("select_scratch", C.c_void_p), ("select_words", C.c_int64), ("select_from_act", C.c_int32),
-        ("separate_apply", C.c_int32), ("meet_wait_ticks", C.c_int64), ("debug_meet_extra", C.c_int32), ("reserved0", C.c_int32)]
+        ("separate_apply", C.c_int32), ("meet_wait_ticks", C.c_int64), ("debug_meet_extra", C.c_int32), ("reserved0", C.c_int32),
+        ("stability", C.c_void_p)]
 
 
 class QNetAct(C.Structure):

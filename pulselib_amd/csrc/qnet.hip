@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256, 3) void qnet_act_rows_kernel(const QNetArgs a)
 constexpr int kMeetUsed = 400;                 // meet[400]: how many of the training launch's workgroups wrote a slice (workgroups 0 .. that - 1)
 struct TrainArgs {
     FlatNet net, tgt;
-    float* partials;                          // [gridDim.x][kSlicePitch]: gradient blocks, biases, then {rows, sum td^2, -, used}
+    float* partials;                          // [gridDim.x][kSlicePitch]: gradient blocks, biases, then the 8 statistics (kSliceStats)
     float* scal;                              // scal[0] = squared gradient norm of the reduce launch: cleared here for it
     int n_params;
     const float* states; long long stride;
@@ -183,12 +183,14 @@ __global__ __launch_bounds__(256) void qnet_select_kernel(const SelectArgs a) {
 
 // A workgroup's gradient slice is private scratch, so its layout is the accumulators' own: 35 blocks of 32x32 (layer 1:
 // 4x2, layer 2: 4x4, layer 3: 2x4, layer 4: 1x2, layer 5: 1x1 -- padded rows / columns included), each stored as
-// [lane][16 registers], then the five bias vectors, then 4 statistics.  A wavefront then writes a block with four
+// [lane][16 registers], then the five bias vectors, then 8 statistics.  A wavefront then writes a block with four
 // 16-byte stores per lane instead of sixteen 4-byte ones (global stores are issue-bound: the dword form made the
 // weight-gradient blocks 4x slower than their MFMAs); qnet_grad_reduce_kernel maps parameters to this layout.
+// Statistics: {rows, sum td^2, reward, used}, then -- written by the STAB instances only (PulseQNetTrain.stability) --
+// {sum |td|, sum Q(s, a), min Q(s, a), max Q(s, a)} over the workgroup's rows (+inf / -inf for a workgroup without rows).
 constexpr int kSliceBlk1 = 0, kSliceBlk2 = 8, kSliceBlk3 = 24, kSliceBlk4 = 32, kSliceBlk5 = 34, kSliceBlocks = 35;
 constexpr int kSliceBias = kSliceBlocks * 1024;                 // b1 @+0, b2 @+128, b3 @+256, b4 @+320, b5 @+352 (32 slots)
-constexpr int kSliceStats = kSliceBias + 384, kSlicePitch = kSliceStats + 4;
+constexpr int kSliceStats = kSliceBias + 384, kSlicePitch = kSliceStats + 8;
 
 // block `blk` (= dW rows [32 ot, +32) x columns [32 it, +32) of its layer) += delta . a^T for this tile (`first`: nothing
 // accumulated yet); delta in D, a_{l-1} in Ap; bsum: this tile's db rows of tile ot
@@ -269,7 +271,9 @@ __device__ __forceinline__ void back_mul(const float (&wa)[KU / 2], int it, cons
     for (int r = 0; r < 16; ++r) Dn[(32 * it + rho(r) + 4 * h) * kLd + c] = acc[r] * gv[r];
 }
 
-template <bool VEC, int NK1>
+// STAB (PulseQNetTrain.stability set): the rows' |td| and Q(s, a) are totalled into statistics 4..7 of the slice as well;
+// the instances without it are the code they were before those statistics existed.
+template <bool VEC, int NK1, bool STAB>
 __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
     extern __shared__ float lds[];
     const FlatNet& n = a.net;
@@ -285,6 +289,7 @@ __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
     // this wavefront's rows of db, live across every tile of the launch (its blocks of dW accumulate in the slice)
     float b5 = 0.0f, b4 = 0.0f, b3 = 0.0f, b2 = 0.0f, b1 = 0.0f;
     float rows_sum = 0.0f, sq_sum = 0.0f;                        // wavefront 0, lane-replicated after the reductions
+    float st_td = 0.0f, st_q = 0.0f, st_min = INFINITY, st_max = -INFINITY;   // STAB, wavefront 0: per lane until the end
     bool used = false;
     float* part = a.partials + (size_t)blockIdx.x * kSlicePitch;
 
@@ -394,6 +399,7 @@ __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
 #pragma unroll
                     for (int off = 32; off >= 1; off >>= 1) { sq += __shfl_xor(sq, off); cnt += __shfl_xor(cnt, off); }
                     rows_sum += cnt; sq_sum += sq;
+                    if (STAB && h == 0 && live) { st_td += fabsf(td); st_q += qa; st_min = fminf(st_min, qa); st_max = fmaxf(st_max, qa); }
                 }
             }
             lds_barrier();
@@ -452,6 +458,14 @@ __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
     lds_barrier();
     if (lane == 0) wave_reward[wv] = reward_sum;
     lds_barrier();
+    if (STAB && wv == 0) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            st_td += __shfl_xor(st_td, off); st_q += __shfl_xor(st_q, off);
+            st_min = fminf(st_min, __shfl_xor(st_min, off)); st_max = fmaxf(st_max, __shfl_xor(st_max, off));
+        }
+        if (lane == 0) *reinterpret_cast<float4*>(part + kSliceStats + 4) = make_float4(st_td, st_q, st_min, st_max);
+    }
     if (wv == 0 && lane == 0) {
         float* ps = part + kSliceStats;
         ps[0] = rows_sum; ps[1] = sq_sum; ps[2] = (wave_reward[0] + wave_reward[1]) + (wave_reward[2] + wave_reward[3]);
@@ -467,7 +481,7 @@ __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
 // four do, the epilogues of layers 3 and 4 split between them); the backward phases deal their 16 + 4 products per layer to
 // all eight (delta tiles on 0-3, the weight-gradient blocks on 4-7, equal MFMA counts).  Same tiles, same LDS image, same
 // slice layout; a block of the slice is still owned by one wavefront for the whole launch.
-template <bool VEC, int NK1>
+template <bool VEC, int NK1, bool STAB>
 __global__ __launch_bounds__(512) void qnet_train8_kernel(const TrainArgs a) {
     extern __shared__ float lds[];
     const FlatNet& n = a.net;
@@ -482,6 +496,7 @@ __global__ __launch_bounds__(512) void qnet_train8_kernel(const TrainArgs a) {
 
     float b5 = 0.0f, b4 = 0.0f, b3 = 0.0f, b2 = 0.0f, b1 = 0.0f;  // this wavefront's rows of db (see the stores at the end)
     float rows_sum = 0.0f, sq_sum = 0.0f;                        // wavefront 4
+    float st_td = 0.0f, st_q = 0.0f, st_min = INFINITY, st_max = -INFINITY;   // STAB, wavefront 4: per lane until the end
     bool used = false;
     float* part = a.partials + (size_t)blockIdx.x * kSlicePitch;
     if (blockIdx.x == 0 && threadIdx.x < 8) a.meet[threadIdx.x] = 0u;
@@ -598,6 +613,7 @@ __global__ __launch_bounds__(512) void qnet_train8_kernel(const TrainArgs a) {
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) { sq += __shfl_xor(sq, off); cnt += __shfl_xor(cnt, off); }
             rows_sum += cnt; sq_sum += sq;
+            if (STAB && h == 0 && live) { st_td += fabsf(td); st_q += qa; st_min = fminf(st_min, qa); st_max = fmaxf(st_max, qa); }
         }
         lds_barrier();
         QSTAMP(3);
@@ -664,6 +680,14 @@ __global__ __launch_bounds__(512) void qnet_train8_kernel(const TrainArgs a) {
     lds_barrier();
     if (lane == 0) wave_reward[wv] = reward_sum;
     if (wv == 4 && lane == 0) { wave_reward[8] = rows_sum; wave_reward[9] = sq_sum; }
+    if (STAB && wv == 4) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            st_td += __shfl_xor(st_td, off); st_q += __shfl_xor(st_q, off);
+            st_min = fminf(st_min, __shfl_xor(st_min, off)); st_max = fmaxf(st_max, __shfl_xor(st_max, off));
+        }
+        if (lane == 0) *reinterpret_cast<float4*>(part + kSliceStats + 4) = make_float4(st_td, st_q, st_min, st_max);
+    }
     lds_barrier();
     if (wv == 0 && lane == 0) {
         float* ps = part + kSliceStats;
@@ -685,13 +709,30 @@ struct ReduceArgs {
     long long wait_ticks;                     // fused form: how long a workgroup waits at the meeting (100 MHz ticks)
     unsigned extra_arrivals;                  // fused form, test hook: arrivals counter 0 expects beyond the grid's (never met)
     long long* gave_up;                       // fused form: pinned host word, += 1 by a launch whose meeting was called off
+    float* stab;                              // PulseQNetTrain.stability or nullptr; two-launch form: [0..4] = the unnormalised totals
 };
 constexpr unsigned kMeetOff = 0x80000000u;     // an arrival counter with this bit set: the meeting was called off
 
 struct AdamArgs {
     float* params; float* target; const float* grad; float* m; float* v; const long long* step; float* scal; float* report;
     int n_params; float lr, wd, beta1, beta2, eps, max_norm; int update_freq;
+    float* stab;                              // PulseQNetTrain.stability or nullptr
 };
+
+// PulseQNetTrain.stability (pulse_env.h): the per-call block from the call's totals over `rows` rows (0: a call without rows,
+// or whose meeting was called off -- the block is zero and the accumulator is not touched), added to the episode accumulator
+__device__ __forceinline__ void stability_finish(float* s, float rows, float td_sum, float q_sum, float q_min, float q_max, float norm,
+                                                 float max_norm, float loss) {
+    const bool any = rows > 0.0f;
+    const float inv = any ? 1.0f / rows : 0.0f;
+    const float td = td_sum * inv, qm = q_sum * inv, clipped = (any && norm > max_norm) ? 1.0f : 0.0f;
+    s[0] = rows; s[1] = td; s[2] = qm; s[3] = any ? q_min : 0.0f; s[4] = any ? q_max : 0.0f;
+    s[5] = any ? norm : 0.0f; s[6] = clipped; s[7] = any ? loss : 0.0f;
+    if (any) {
+        s[8] += 1.0f; s[9] += td; s[10] += qm; s[11] = fminf(s[11], q_min); s[12] = fmaxf(s[12], q_max);
+        s[13] += clipped; s[14] += loss;
+    }
+}
 
 // the AdamW update of parameter i (torch semantics: decoupled decay, bias-corrected moments) from the gradient SUM g over
 // `count` rows, `ss` = squared norm of the summed gradient, t = optimizer step of this update
@@ -784,18 +825,32 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(const ReduceArgs 
         }
     }
     float rows = 0.0f, sq = 0.0f; double rew = 0.0;
+    float st_td = 0.0f, st_q = 0.0f, st_min = INFINITY, st_max = -INFINITY;     // stability totals (workgroup 0)
+    const bool stab = a.stab != nullptr && blockIdx.x == 0;
     if ((FUSED || blockIdx.x == 0) && threadIdx.x < 64) {        // fused: every workgroup totals the row count itself
         for (int b = threadIdx.x; b < a.n_blocks; b += 64) {
             const float* ps = a.partials + b * pitch + kSliceStats;
             rows += ps[0]; sq += ps[1]; rew += (double)ps[2];
+            if (stab) {
+                const float4 s4 = *reinterpret_cast<const float4*>(ps + 4);
+                st_td += s4.x; st_q += s4.y; st_min = fminf(st_min, s4.z); st_max = fmaxf(st_max, s4.w);
+            }
         }
         if (blockIdx.x == 0 && a.reward_sum) for (int wdw = threadIdx.x; wdw < a.n_windows; wdw += 64) rew += (double)a.win_reward[wdw];
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) { rows += __shfl_xor(rows, off); sq += __shfl_xor(sq, off); rew += __shfl_xor(rew, off); }
+        if (stab) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                st_td += __shfl_xor(st_td, off); st_q += __shfl_xor(st_q, off);
+                st_min = fminf(st_min, __shfl_xor(st_min, off)); st_max = fmaxf(st_max, __shfl_xor(st_max, off));
+            }
+        }
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             a.scal[1] = rows; a.scal[2] = sq;
             if (!FUSED && rows > 0.0f && a.step) *a.step += 1;
             if (a.reward_sum) *a.reward_sum += rew;
+            if (!FUSED && stab) { a.stab[0] = rows; a.stab[1] = st_td; a.stab[2] = st_q; a.stab[3] = st_min; a.stab[4] = st_max; }
         }
     }
     if (FUSED) {
@@ -845,6 +900,7 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(const ReduceArgs 
             a.scal[0] = total_ss;
             const float inv = count > 0.0f ? 1.0f / count : 0.0f;
             w.report[0] = count; w.report[1] = sq * inv; w.report[2] = sqrtf(total_ss) * inv;
+            if (stab) stability_finish(a.stab, count, st_td, st_q, st_min, st_max, w.report[2], w.max_norm, w.report[1]);
         }
     }
 }
@@ -859,7 +915,11 @@ __global__ __launch_bounds__(256) void qnet_adamw_kernel(const AdamArgs a) {
     const float count = a.scal[1], sq = a.scal[2], ss = a.scal[0];
     const float inv = count > 0.0f ? 1.0f / count : 0.0f;
     if (count > 0.0f && i < a.n_params) adamw_one(a, i, a.grad[i], count, ss, *a.step);   // (step already advanced by the reduce launch)
-    if (i == 0) { a.report[0] = count; a.report[1] = count > 0.0f ? sq * inv : 0.0f; a.report[2] = sqrtf(ss) * inv; }
+    if (i == 0) {
+        a.report[0] = count; a.report[1] = count > 0.0f ? sq * inv : 0.0f; a.report[2] = sqrtf(ss) * inv;
+        // the reduce launch (or, data-parallel, the caller's all-reduce) left the unnormalised totals in stab[0..4]
+        if (a.stab) stability_finish(a.stab, count, a.stab[1], a.stab[2], a.stab[3], a.stab[4], a.report[2], a.max_norm, a.report[1]);
+    }
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
@@ -1066,7 +1126,7 @@ AdamArgs adam_args(const PulseQNetTrain* t, int np) {
     AdamArgs b{};
     b.params = t->params; b.target = t->target_params; b.grad = t->grad; b.m = t->exp_avg; b.v = t->exp_avg_sq; b.step = (const long long*)t->step;
     b.scal = t->stats; b.report = t->report; b.n_params = np; b.lr = t->lr; b.wd = t->weight_decay; b.beta1 = t->beta1; b.beta2 = t->beta2;
-    b.eps = t->eps; b.max_norm = t->max_grad_norm; b.update_freq = t->update_freq;
+    b.eps = t->eps; b.max_norm = t->max_grad_norm; b.update_freq = t->update_freq; b.stab = t->stability;
     return b;
 }
 
@@ -1141,13 +1201,16 @@ int train_launches(const PulseQNetTrain* t, const float* states, int64_t row_str
             hipLaunchKernelGGL(qnet_select_kernel, dim3((unsigned)nw), dim3(256), 0, st, sa);
         }
         const bool vec = n.state_dim % 8 == 0 && row_stride % 4 == 0 && next_stride % 4 == 0 && aligned16(states) && aligned16(next_states);
-        // instances: layer-1 steps 5 (16-byte rows of <= 40 inputs) or 8; four or eight wavefronts per tile
+        // instances: layer-1 steps 5 (16-byte rows of <= 40 inputs) or 8; four or eight wavefronts per tile; stability totals or not
         static const bool four = [] { const char* e = getenv("PULSE_TRAIN_WAVES"); return e && e[0] == '4'; }();
-        const void* fns[6] = {reinterpret_cast<const void*>(&qnet_train_kernel<false, 8>), reinterpret_cast<const void*>(&qnet_train_kernel<true, 8>),
-                              reinterpret_cast<const void*>(&qnet_train_kernel<true, 5>), reinterpret_cast<const void*>(&qnet_train8_kernel<false, 8>),
-                              reinterpret_cast<const void*>(&qnet_train8_kernel<true, 8>), reinterpret_cast<const void*>(&qnet_train8_kernel<true, 5>)};
-        const int slot = (vec ? (n.state_dim <= 40 ? 2 : 1) : 0) + (four ? 0 : 3);
-        static const void* attr_set[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        const void* fns[12] = {reinterpret_cast<const void*>(&qnet_train_kernel<false, 8, false>), reinterpret_cast<const void*>(&qnet_train_kernel<true, 8, false>),
+                               reinterpret_cast<const void*>(&qnet_train_kernel<true, 5, false>), reinterpret_cast<const void*>(&qnet_train8_kernel<false, 8, false>),
+                               reinterpret_cast<const void*>(&qnet_train8_kernel<true, 8, false>), reinterpret_cast<const void*>(&qnet_train8_kernel<true, 5, false>),
+                               reinterpret_cast<const void*>(&qnet_train_kernel<false, 8, true>), reinterpret_cast<const void*>(&qnet_train_kernel<true, 8, true>),
+                               reinterpret_cast<const void*>(&qnet_train_kernel<true, 5, true>), reinterpret_cast<const void*>(&qnet_train8_kernel<false, 8, true>),
+                               reinterpret_cast<const void*>(&qnet_train8_kernel<true, 8, true>), reinterpret_cast<const void*>(&qnet_train8_kernel<true, 5, true>)};
+        const int slot = (vec ? (n.state_dim <= 40 ? 2 : 1) : 0) + (four ? 0 : 3) + (t->stability ? 6 : 0);
+        static const void* attr_set[12] = {};
         if (attr_set[slot] != fns[slot]) {
             const hipError_t e = hipFuncSetAttribute(fns[slot], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTrainLdsBytes);
             if (e != hipSuccess) return pulse::fail_hip((int)e, "pulse_qnet_train_step: LDS size attribute");
@@ -1170,6 +1233,7 @@ int train_launches(const PulseQNetTrain* t, const float* states, int64_t row_str
     r.wait_ticks = t->meet_wait_ticks > 0 ? (long long)t->meet_wait_ticks : 500000000ll;     // 5 s of the 100 MHz clock
     r.extra_arrivals = t->debug_meet_extra > 0 ? (unsigned)t->debug_meet_extra : 0u;
     r.gave_up = g_meet_gave_up;
+    r.stab = t->stability;
     if (fused) hipLaunchKernelGGL(qnet_grad_reduce_kernel<true>, dim3(rg), dim3(256), 0, st, r, b);
     else hipLaunchKernelGGL(qnet_grad_reduce_kernel<false>, dim3(rg), dim3(256), 0, st, r, b);
     }

@@ -79,6 +79,7 @@ class PokerQNetwork(nn.Module):
         # the reduce launch applies AdamW itself behind a meeting of its workgroups (qnet.hip); True = AdamW as its own launch
         self.separate_apply = False
         self.meet_wait_ticks = 0             # 0: the library's 5 s (ticks of the 100 MHz clock)
+        self.max_grad_norm = 1.0             # clip_grad_norm_ (Player.py:280) of the native update
         self._meetings_called_off = int(_native.lib().pulse_qnet_called_off_meetings()) if torch.device(device).type == "cuda" else 0
 
     # ------------------------------------------------------------------ torch side
@@ -229,6 +230,7 @@ class PokerQNetwork(nn.Module):
             t.lr, t.weight_decay, t.gamma, t.update_freq = self.lr, self.wd, float(self.gamma), int(self.update_freq)
             t.dropout_p = float(self.network[4].p) if self.network.training else 0.0
             t.separate_apply, t.meet_wait_ticks = int(self.separate_apply), int(self.meet_wait_ticks)
+            t.max_grad_norm = float(self.max_grad_norm)
             return t
         t = self._struct_cache["train"] = _native.QNetTrain()
         t.net, t.target = self._net_struct(self.network), self._net_struct(self.target_network)
@@ -238,11 +240,43 @@ class PokerQNetwork(nn.Module):
         t.partials, t.max_blocks = nat["partials"].data_ptr(), TRAIN_BLOCKS
         t.select_scratch, t.select_words = nat["select"].data_ptr(), nat["select"].numel()
         t.lr, t.weight_decay, t.beta1, t.beta2, t.eps = self.lr, self.wd, 0.9, 0.999, 1e-8       # torch.optim.AdamW defaults (:296)
-        t.max_grad_norm, t.gamma = 1.0, float(self.gamma)                                      # clip_grad_norm_ (:280)
+        t.max_grad_norm, t.gamma = float(self.max_grad_norm), float(self.gamma)                # clip_grad_norm_ (:280)
         t.dropout_p = float(self.network[4].p) if self.network.training else 0.0
         t.update_freq = int(self.update_freq)
         t.separate_apply, t.meet_wait_ticks, t.debug_meet_extra = int(self.separate_apply), int(self.meet_wait_ticks), 0
+        stab = nat.get("stability")
+        t.stability = None if stab is None else stab.data_ptr()
         return t
+
+    # ------------------------------------------------------------------ training-stability metrics (utils/stability.py)
+    def enable_stability_metrics(self) -> torch.Tensor:
+        """From now on every native update also writes the training-stability metrics of pulse_env.h (PulseQNetTrain.stability)
+        into a device fp32[16] of this module -- inside its own launches: no launch more, no sync.  Returns that buffer (the
+        accumulator starts cleared).  Without this call the updates run exactly the launches they ran before."""
+        self._native_state()
+        nat = self._native
+        if nat.get("stability") is None:
+            dev = self._flat.device
+            nat["stability"] = torch.zeros(16, dtype=torch.float32, device=dev)
+            nat["stability_cleared"] = torch.tensor([0.0, 0.0, 0.0, float("inf"), float("-inf"), 0.0, 0.0, 0.0], dtype=torch.float32,
+                                                    device=dev)
+            self.clear_stability_metrics()
+        self._struct_cache["train"].stability = nat["stability"].data_ptr()
+        return nat["stability"]
+
+    def clear_stability_metrics(self) -> None:
+        """Clears the per-episode accumulator (stability[8..15]) on the stream: one device-to-device copy, no sync."""
+        nat = self._native
+        nat["stability"][8:].copy_(nat["stability_cleared"])
+
+    def stability_step(self) -> torch.Tensor:
+        """Device view of the last call's block: [rows, mean |td|, mean Q(s, a), min Q, max Q, grad norm, clipped, loss]."""
+        return self._native["stability"][:8]
+
+    def stability_episode(self) -> torch.Tensor:
+        """Device view of the accumulator: [measured steps, sum td_error, sum q_mean, min q_min, max q_max, sum clipped,
+        sum loss, 0] over the calls with rows since the last clear."""
+        return self._native["stability"][8:]
 
     def train_step_native(self, states, actions, rewards, next_states, dones, row_mask=None, step_counter=None, terminated=None,
                           reward_sum=None):
@@ -297,12 +331,23 @@ class PokerQNetwork(nn.Module):
             _native.check(lib.pulse_qnet_train_grads(*args), "pulse_qnet_train_grads")
             nat = self._native
             grad, stats = nat["grad"], nat["stats"]
+            stab = nat.get("stability")
+            # stability totals (pulse_env.h): {rows, sum |td|, sum Q} with SUM, {-min Q, max Q} with MAX
+            spread = None if stab is None else torch.stack([-stab[3], stab[4]])
             if dist.get_backend() == "gloo":          # one-GPU rehearsal / CPU-side reduction
                 g, s2 = grad.cpu(), stats[1:3].cpu()
                 dist.all_reduce(g); dist.all_reduce(s2)
                 grad.copy_(g); stats[1:3].copy_(s2)
+                if stab is not None:
+                    s3, mm = stab[0:3].cpu(), spread.cpu()
+                    dist.all_reduce(s3); dist.all_reduce(mm, op=dist.ReduceOp.MAX)
+                    stab[0:3].copy_(s3); spread.copy_(mm)
             else:
                 dist.all_reduce(grad); dist.all_reduce(stats[1:3])
+                if stab is not None:
+                    dist.all_reduce(stab[0:3]); dist.all_reduce(spread, op=dist.ReduceOp.MAX)
+            if stab is not None:
+                stab[3:5].copy_(torch.stack([-spread[0], spread[1]]))
             stats[0:1].copy_(grad.square().sum().reshape(1))
             nat["step"] += (stats[1:2] > 0).to(torch.int64)
             _native.check(lib.pulse_qnet_train_apply(C.byref(t), stream), "pulse_qnet_train_apply")
@@ -340,7 +385,7 @@ class PokerQNetwork(nn.Module):
             return torch.zeros((), dtype=torch.float32, device=states.device)
         report = self.train_step_native(states, actions, rewards, next_states, dones, None)
         loss = report[1].clone()                   # the report buffer is shared by every call: the caller keeps its own loss
-        if self.step_count % 1000 == 0:                                            # Player.py:281-287 (the Q / reward means are not kept)
+        if self.step_count % 1000 == 0:                                            # Player.py:281-287 (Q means: enable_stability_metrics)
             print(f"Step {self.step_count} | Avg Loss: {float(loss):.2f} | Epsilon: {self.epsilon:.4f}")
         return loss
 

@@ -93,7 +93,8 @@ def train_agent(env, agents, agent_types, episodes, n_games, device, results_dir
 
 def train_agent_fused(env, agents, agent_types, episodes, n_games, device, results_dir=None, config=None, plotter=None,
                       benchmarker=None, max_episode_steps=None, reduce_stats=True, stop_rule="lagged", host_seed=0,
-                      step_hook=None, learner="native", hand_metrics=None, prefixed_decks=None, fuse_act_step=False):
+                      step_hook=None, learner="native", hand_metrics=None, prefixed_decks=None, fuse_act_step=False,
+                      stability_metrics=None):
     """train_agent with nothing in the step waiting on the host: the loop contract above (rotation, masks evaluated
     before `terminated |= dones`, stop cadence, step accounting) on four launches-groups per step --
       learner's actions (pulse_qnet_act, masked by seat) -> scripted opponents + env step (pulse_poker_policy_step) ->
@@ -106,7 +107,9 @@ def train_agent_fused(env, agents, agent_types, episodes, n_games, device, resul
     check (lag 0), `"steps"` runs every episode to `max_episode_steps`.  Needs a learner with `act_into` /
     `train_step_masked` (qnetwork.py).
     `hand_metrics` (utils.performance.HandMetrics) adds the BB/100 side-channel of trainGPU_performance.py:192-206 as
-    one more launch per step; its per-episode summaries come back under "hand_metrics"."""
+    one more launch per step; its per-episode summaries come back under "hand_metrics".
+    `stability_metrics` (utils.stability.StabilityMetrics, native learner) adds the metrics of trainGPU_stability.py, taken
+    inside the learner's own launches (no launch more) and read back once per episode: "stability" in the summary."""
     import random
 
     from ..environments.Poker.utils import native_types
@@ -117,6 +120,8 @@ def train_agent_fused(env, agents, agent_types, episodes, n_games, device, resul
     if not (hasattr(q_agent, "act_into") and hasattr(q_agent, "train_step_masked") and hasattr(q_agent, "train_step_native")):
         raise TypeError("train_agent_fused needs a learner with act_into / train_step_native (PokerQNetwork)")
     native = learner == "native"
+    if stability_metrics is not None and not native:
+        raise ValueError("stability_metrics needs learner='native' (the metrics are taken inside the native update's launches)")
     host_rng = random.Random(host_seed)
     if stop_rule not in ("lagged", "sync", "steps"):
         raise ValueError(f"stop_rule must be 'lagged', 'sync' or 'steps', got {stop_rule!r}")
@@ -138,7 +143,7 @@ def train_agent_fused(env, agents, agent_types, episodes, n_games, device, resul
     episode_reward = torch.zeros((), dtype=torch.float64, device=device)
     stats = EpisodeStats(device)
     total_steps, global_step = 0, 0
-    scores, reward_scores, episode_metrics = [], [], []
+    scores, reward_scores, episode_metrics, stability_episodes = [], [], [], []
     pending = []
 
     def drain_pending():
@@ -162,6 +167,8 @@ def train_agent_fused(env, agents, agent_types, episodes, n_games, device, resul
         done_count.drain()
         if hand_metrics is not None:
             hand_metrics.begin_episode(env, q_seat)
+        if stability_metrics is not None:
+            stability_metrics.begin_episode()
         idx = 0
         while True:
             seat_idx = info["seat_idx"]
@@ -226,6 +233,8 @@ def train_agent_fused(env, agents, agent_types, episodes, n_games, device, resul
             drain_pending()
         if hand_metrics is not None:
             episode_metrics.append(hand_metrics.end_episode())
+        if stability_metrics is not None:
+            stability_episodes.append(stability_metrics.end_episode(episode_reward))
         total_steps += done_count.n_global * idx                                      # :108 (the tables of the whole job: every rank steps in lock step)
 
     drain_pending()
@@ -242,6 +251,9 @@ def train_agent_fused(env, agents, agent_types, episodes, n_games, device, resul
                "episode_rewards": reward_scores, "episode_profits": scores, "config": dict(config), "env_step_calls": global_step}
     if hand_metrics is not None:
         summary["hand_metrics"] = {"episodes": episode_metrics, "final": hand_metrics.summary()}
+    if stability_metrics is not None:
+        from ..utils.stability import metric_values
+        summary["stability"] = {"episodes": stability_episodes, "final": metric_values(stability_metrics.summary(elapsed))}
     if plotter is not None and results_dir is not None:
         plotter.plot_learning_curve(scores=reward_scores, file_path=str(Path(results_dir) / "rewards_learning_curve"), window_size=10,
                                     title="Poker Q-Learning - Total Reward per Episode Batch")

@@ -5,7 +5,8 @@ reference's way (n_tables x steps per episode / wall time, scripts/Poker/trainGP
     python tools/bench_trainer.py [--tables 65536] [--episodes 20] [--warmup 3] [--loop fused|reference]
 
 `--loop reference` runs train_agent, the loop with the reference's host syncs (boolean-mask indexing, blocking stop
-rule), on the same kernels for comparison.  Prints one JSON line."""
+rule), on the same kernels for comparison.  `--stability` adds the training-stability metrics (utils/stability.py).  Prints one
+JSON line."""
 import argparse
 import json
 import os
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--learner", choices=["native", "torch"], default="native", help="fused loop only")
     ap.add_argument("--max-episode-steps", type=int, default=40)
     ap.add_argument("--fuse-act-step", action="store_true", help="act + env step as ONE launch (PokerGPU.act_policy_step)")
+    ap.add_argument("--stability", action="store_true", help="training-stability metrics on (utils.stability.StabilityMetrics, native learner)")
     args = ap.parse_args()
     from pulselib_amd.environments.Poker import PokerGPU, PokerQNetwork, load_gpu_agents
     from pulselib_amd.environments.Poker.utils import PokerAgentType
@@ -56,6 +58,9 @@ def main():
     if args.loop == "fused":
         kw["learner"] = args.learner
         kw["fuse_act_step"] = args.fuse_act_step
+        if args.stability:
+            from pulselib_amd.utils.stability import StabilityMetrics
+            kw["stability_metrics"] = StabilityMetrics(q)
     run(env, agents, types, args.warmup, args.tables, device, **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -72,7 +77,7 @@ def main():
         print(json.dumps({"metric": "trainer-loop env-steps/sec, Poker batched tables (learner acting and learning every step)",
                       "value": out["total_steps"] / elapsed, "unit": "env-steps/sec", "n_gpus": world, "loop": args.loop, "learner": args.learner if args.loop == "fused" else "torch",
                       "tables": args.tables, "episodes": args.episodes, "step_calls_counted": steps,
-                      "ms_per_step": elapsed / max(steps, 1) * 1e3, "learner_calls": q.step_count,
+                      "ms_per_step": elapsed / max(steps, 1) * 1e3, "learner_calls": q.step_count, "stability": args.stability,
                       "mean_episode_reward": sum(out["episode_rewards"]) / max(len(out["episode_rewards"]), 1)}), flush=True)
     if world > 1:
         import torch.distributed as dist
