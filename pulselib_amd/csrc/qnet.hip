@@ -24,7 +24,6 @@
 #include <cstdlib>
 
 #include "pulse_internal.h"
-#include "pulse_internal.h"
 
 // In-kernel timeline of the training kernel (diagnostic build only, -DPULSE_STAMPS=1 -> libpulse_hip_stamps.so,
 // tools/qnet_stamp_timeline.py): lane 0 of wavefront 0 stores the clock at phase boundaries of its first tile.
@@ -41,6 +40,7 @@ __device__ unsigned long long* g_qstamp_buf = nullptr;
 
 #include "qnet_device.h"
 #include "qnet_rows16.h"
+#include "qnet_train_device.h"
 
 namespace {
 
@@ -62,40 +62,17 @@ __global__ __launch_bounds__(256, 3) void qnet_act_rows_kernel(const QNetArgs a)
     extern __shared__ float lds[];
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
     const int n_windows = (a.n_rows + WIN - 1) / WIN, per = (n_windows + 255) / 256;
-    int* chunk = reinterpret_cast<int*>(lds + ActLds::List);     // [256] first position of thread t's windows; [257..260] wavefront totals
-    int T;
-    {
-        int mine = 0;
-        for (int j = 0; j < per; ++j) { const int w = threadIdx.x * per + j; mine += w < n_windows ? a.asel_counts[w] : 0; }
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off); incl += lane >= off ? o : 0; }
-        int* wtot = chunk + 257;
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        int base = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) base += i < wv ? wtot[i] : 0;
-        chunk[threadIdx.x] = base + incl - mine;
-        T = (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
-        __syncthreads();
-    }
+    int* chunk = reinterpret_cast<int*>(lds + ActLds::List);
+    const int T = list_positions<256>(chunk, a.asel_counts, n_windows, per, wv, lane);
     const int n_tiles = (T + 31) / 32;
     if ((int)blockIdx.x >= n_tiles) return;
     const int K1 = a.net.state_dim, K1r = (K1 + 7) & ~7;
     float w1r[NK1][4];
     load_layer<VEC, NK1>(w1r, a.net, 0, 32 * wv + c, h, 0, K1r);
     for (int ti = blockIdx.x; ti < n_tiles; ti += gridDim.x) {
-        int rowc = -1;
         const int p = 32 * ti + c;
-        if (p < T) {                                             // its window by bisection of the threads' first positions, then along that thread's windows
-            int t = 0;
-#pragma unroll
-            for (int s = 128; s >= 1; s >>= 1) t += (chunk[t + s] <= p) ? s : 0;
-            int w = t * per, acc = chunk[t], cnt = a.asel_counts[w];
-            while (p >= acc + cnt) { acc += cnt; ++w; cnt = a.asel_counts[w]; }
-            rowc = a.asel_rows[(size_t)w * WIN + (p - acc)];
-        }
+        static_assert(WIN == 128, "list_row: windows of 1 << 7 rows");
+        const int rowc = p < T ? list_row<256>(chunk, a.asel_counts, a.asel_rows, per, 7, p) : -1;
         lds_barrier();                                                        // previous tile's readers are done
         coop_load_rows<VEC>(lds + ActLds::R0, a.states, a.row_stride, K1, rowc, wv, c, h);
         const f32x16 qv = group_forward<false, NK1>(w1r, a.net, lds + ActLds::R0, lds + ActLds::R1, lds + ActLds::R0, lds + ActLds::R1, lds + ActLds::R0,
@@ -123,25 +100,7 @@ __global__ __launch_bounds__(256, 3) void qnet_act_rows_kernel(const QNetArgs a)
 // Launch 2 (qnet_grad_reduce_kernel) sums the slices into the flat gradient and its squared norm and, on one GPU, applies
 // mean / clip_grad_norm_ / AdamW / target sync to the parameters it holds the sums of (qnet_adamw_kernel: the same as a
 // launch of its own, for data-parallel training where an all-reduce comes between the two).
-constexpr int kMeetUsed = 400;                 // meet[400]: how many of the training launch's workgroups wrote a slice (workgroups 0 .. that - 1)
-struct TrainArgs {
-    FlatNet net, tgt;
-    float* partials;                          // [gridDim.x][kSlicePitch]: gradient blocks, biases, then the 8 statistics (kSliceStats)
-    float* scal;                              // scal[0] = squared gradient norm of the reduce launch: cleared here for it
-    int n_params;
-    const float* states; long long stride;
-    const int64_t* actions; const float* rewards;
-    const float* next_states; long long next_stride;
-    const uint8_t* dones;
-    const int32_t* sel_rows; const int32_t* sel_counts;   // the row lists: sel_rows[(w << win_shift) + i], i < sel_counts[w]
-    int win_shift;                                        // 8: the select launch's windows; 7: the act launch's
-    const uint8_t* row_mask; uint8_t* terminated; int book; // book: the per-candidate bookkeeping is done here (lists from act)
-    unsigned* meet;
-    int n_rows;
-    uint64_t seed, step, table_id0;
-    float gamma, drop_p;
-};
-
+//
 // Launch 0 (qnet_select_kernel; not needed after pulse_qnet_act_select), one workgroup per window of 256 candidate rows: everything train_step and the trainer do
 // per CANDIDATE row -- the reference's filters (row_mask, seat status ACTIVE / ALLIN, Player.py:258-261) compacted into
 // the window's list of selected rows, `terminated |= dones` (trainGPU.py:86), the window's reward sum over the row_mask
@@ -181,96 +140,6 @@ __global__ __launch_bounds__(256) void qnet_select_kernel(const SelectArgs a) {
     }
 }
 
-// A workgroup's gradient slice is private scratch, so its layout is the accumulators' own: 35 blocks of 32x32 (layer 1:
-// 4x2, layer 2: 4x4, layer 3: 2x4, layer 4: 1x2, layer 5: 1x1 -- padded rows / columns included), each stored as
-// [lane][16 registers], then the five bias vectors, then 8 statistics.  A wavefront then writes a block with four
-// 16-byte stores per lane instead of sixteen 4-byte ones (global stores are issue-bound: the dword form made the
-// weight-gradient blocks 4x slower than their MFMAs); qnet_grad_reduce_kernel maps parameters to this layout.
-// Statistics: {rows, sum td^2, reward, used}, then -- written by the STAB instances only (PulseQNetTrain.stability) --
-// {sum |td|, sum Q(s, a), min Q(s, a), max Q(s, a)} over the workgroup's rows (+inf / -inf for a workgroup without rows).
-constexpr int kSliceBlk1 = 0, kSliceBlk2 = 8, kSliceBlk3 = 24, kSliceBlk4 = 32, kSliceBlk5 = 34, kSliceBlocks = 35;
-constexpr int kSliceBias = kSliceBlocks * 1024;                 // b1 @+0, b2 @+128, b3 @+256, b4 @+320, b5 @+352 (32 slots)
-constexpr int kSliceStats = kSliceBias + 384, kSlicePitch = kSliceStats + 8;
-
-// block `blk` (= dW rows [32 ot, +32) x columns [32 it, +32) of its layer) += delta . a^T for this tile (`first`: nothing
-// accumulated yet); delta in D, a_{l-1} in Ap; bsum: this tile's db rows of tile ot
-__device__ __forceinline__ void dw_accum(const float* __restrict__ D, const float* __restrict__ Ap, float* __restrict__ slice, int blk,
-                                         int ot, int it, int c, int h, bool first, float* bsum) {
-    // registers 4q .. 4q+3 of all 64 lanes form one contiguous KB of the slice: a store instruction writes whole lines.  The
-    // block's old values are asked for FIRST (not after the MFMAs, where every call waited out their round trip: with ~20 tiles
-    // per workgroup at 2,000,000 tables the slices live in the Infinity Cache, not in L2)
-    float4* dst = reinterpret_cast<float4*>(slice + (size_t)blk * 1024) + (c + 32 * h);
-    float4 old[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { old[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); if (!first) old[q] = dst[64 * q]; }
-    float ad[16], ap[16]; float bs = 0.0f;
-#pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2) { ad[s2] = D[(32 * ot + c) * kLd + 2 * s2 + h]; ap[s2] = Ap[(32 * it + c) * kLd + 2 * s2 + h]; }
-    __builtin_amdgcn_sched_barrier(0);                            // (all 32 LDS reads ahead of the MFMAs, as in mfma_w)
-#pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2) bs += ad[s2];
-    if (bsum) *bsum += bs + __shfl_xor(bs, 32);
-    f32x16 acc = zero16();
-#pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ad[s2], ap[s2], acc, 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        dst[64 * q] = make_float4(acc[4 * q] + old[q].x, acc[4 * q + 1] + old[q].y, acc[4 * q + 2] + old[q].z, acc[4 * q + 3] + old[q].w);
-}
-
-// flat parameter index (order w1,b1,...,w5,b5) of slice element j, or -1 for a padding element
-__device__ __forceinline__ int slice_param(int j, int K1, int A) {
-    const int n_out[5] = {128, 128, 64, 32, A}, n_in[5] = {K1, 128, 128, 64, 32};
-    const int blk0[6] = {kSliceBlk1, kSliceBlk2, kSliceBlk3, kSliceBlk4, kSliceBlk5, kSliceBlocks}, its[5] = {2, 4, 4, 2, 1};
-    const int bias0[6] = {0, 128, 256, 320, 352, 384};
-    int base[5], bbase[5], acc = 0;
-#pragma unroll
-    for (int l = 0; l < 5; ++l) { base[l] = acc; acc += n_out[l] * n_in[l]; bbase[l] = acc; acc += n_out[l]; }
-    if (j >= kSliceBias) {
-        const int u = j - kSliceBias;
-#pragma unroll
-        for (int l = 0; l < 5; ++l)
-            if (u >= bias0[l] && u < bias0[l + 1]) return (u - bias0[l]) < n_out[l] ? bbase[l] + (u - bias0[l]) : -1;
-        return -1;
-    }
-    const int blk = j >> 10, lane = (j >> 2) & 63, r = 4 * ((j >> 8) & 3) + (j & 3), c = lane & 31, h = lane >> 5;   // [block][q][lane][4]
-#pragma unroll
-    for (int l = 0; l < 5; ++l) {
-        if (blk >= blk0[l] && blk < blk0[l + 1]) {
-            const int b = blk - blk0[l], ot = b / its[l], it = b - ot * its[l];
-            const int o = 32 * ot + rho(r) + 4 * h, in = 32 * it + c;
-            return (o < n_out[l] && in < n_in[l]) ? base[l] + o * n_in[l] + in : -1;
-        }
-    }
-    return -1;
-}
-
-// tile `it` of delta_{l-1} = (W^T . delta_l) * g_{l-1} -> Dn[32 it ..]; W is n_out x n_in, delta_l = units [0, KU) of D.
-// back_load: the KU / 2 weights (one per MFMA, down a column of W: coalesced), issued a phase ahead by the caller.
-template <int KU>
-__device__ __forceinline__ void back_load(float (&wa)[KU / 2], const float* __restrict__ w, int n_out, int n_in, int it, int c, int h) {
-#pragma unroll
-    for (int i = 0; i < KU / 2; ++i) {
-        const int k = 2 * i + h;
-        wa[i] = k < n_out ? w[(size_t)k * n_in + 32 * it + c] : 0.0f;
-    }
-}
-template <int KU>
-__device__ __forceinline__ void back_mul(const float (&wa)[KU / 2], int it, const float* __restrict__ D, const float* __restrict__ G,
-                                         float* __restrict__ Dn, int c, int h) {
-    float dv[KU / 2], gv[16];
-#pragma unroll
-    for (int i = 0; i < KU / 2; ++i) dv[i] = D[(2 * i + h) * kLd + c];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) gv[r] = G[(32 * it + rho(r) + 4 * h) * kLd + c];
-    __builtin_amdgcn_sched_barrier(0);                            // (LDS reads ahead of the MFMAs)
-    f32x16 acc = zero16();
-#pragma unroll
-    for (int i = 0; i < KU / 2; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[i], dv[i], acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) Dn[(32 * it + rho(r) + 4 * h) * kLd + c] = acc[r] * gv[r];
-}
-
 // STAB (PulseQNetTrain.stability set): the rows' |td| and Q(s, a) are totalled into statistics 4..7 of the slice as well;
 // the instances without it are the code they were before those statistics existed.
 template <bool VEC, int NK1, bool STAB>
@@ -279,60 +148,28 @@ __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
     const FlatNet& n = a.net;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, c0 = lane & 31, h0 = lane >> 5;
     const int K1 = n.state_dim, A = n.n_actions;
+    // (plain pointers: gathered in one struct they cost the kernel 14 registers)
     float* Xs = lds + CoopLds::Xs; float* A1 = lds + CoopLds::A1; float* A2 = lds + CoopLds::A2; float* A3 = lds + CoopLds::A3;
     float* A4 = lds + CoopLds::A4;
     float* G1 = lds + CoopLds::G1; float* G2 = lds + CoopLds::G2; float* G3 = lds + CoopLds::G3; float* G4 = lds + CoopLds::G4;
-    float* Da = lds + CoopLds::Da; float* Db = lds + CoopLds::Db;
+    float* Da = lds + CoopLds::Da; float* Db = lds + CoopLds::Db; float* Tg = lds + CoopLds::Tgt;
+    int* chunk = reinterpret_cast<int*>(lds + CoopLds::List);
     const uint32_t thr = (uint32_t)(a.drop_p * 65536.0f);
     const float scale = 1.0f / (1.0f - a.drop_p);
 
     // this wavefront's rows of db, live across every tile of the launch (its blocks of dW accumulate in the slice)
     float b5 = 0.0f, b4 = 0.0f, b3 = 0.0f, b2 = 0.0f, b1 = 0.0f;
     float rows_sum = 0.0f, sq_sum = 0.0f;                        // wavefront 0, lane-replicated after the reductions
-    float st_td = 0.0f, st_q = 0.0f, st_min = INFINITY, st_max = -INFINITY;   // STAB, wavefront 0: per lane until the end
+    StabTotals st;                                               // STAB, wavefront 0: per lane until the end
     bool used = false;
     float* part = a.partials + (size_t)blockIdx.x * kSlicePitch;
-
-    // scal[0] is read by every workgroup of the previous step's AdamW launch and accumulated by this step's reduce
-    // launch: this kernel sits between the two on the stream, so its first thread clears it
-    if (blockIdx.x == 0 && threadIdx.x < 8) a.meet[threadIdx.x] = 0u;          // the fused reduce launch's arrival counters
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.scal[0] = 0.0f;
-    QSTAMP(0);
-    // The selected rows of the whole batch, in window order, are positions [0, T); every workgroup computes the same
-    // exclusive sums of the windows' counts (thread t: windows [t per, (t + 1) per)) and takes the tiles ti = blockIdx.x,
-    // + gridDim.x, ... of an even split of [0, T) into n_tiles <= 32-row pieces.
-    float reward_sum = 0.0f;
-    if (a.book) {                                                // what the select launch does per candidate row, when act made the lists
-        for (int win = blockIdx.x; win * 256 < a.n_rows; win += gridDim.x) {
-            const int row = win * 256 + threadIdx.x;
-            const bool cand = row < a.n_rows && (a.row_mask == nullptr || a.row_mask[row] != 0);
-            float rew = cand ? a.rewards[row] : 0.0f;            // episode reward: rows of row_mask, before the status filter (trainGPU.py:96)
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) rew += __shfl_xor(rew, off);
-            reward_sum += rew;
-            if (a.terminated && row < a.n_rows && a.dones[row]) a.terminated[row] = 1;      // trainGPU.py:86
-        }
-    }
+    train_prologue(a);
+    const float reward_sum = a.book ? book_candidates<256>(a) : 0.0f;
+    // The selected rows of the whole batch, in window order, are positions [0, T); the workgroup takes the tiles
+    // ti = blockIdx.x, + gridDim.x, ... of an even split of [0, T) into n_tiles <= 32-row pieces.
     const int W = 1 << a.win_shift;
     const int n_windows = (a.n_rows + W - 1) >> a.win_shift, per = (n_windows + 255) / 256;
-    int* chunk = reinterpret_cast<int*>(lds + CoopLds::List);    // [256] first position of thread t's windows, [256] = T
-    int T;
-    {
-        int mine = 0;
-        for (int j = 0; j < per; ++j) { const int w = threadIdx.x * per + j; mine += w < n_windows ? a.sel_counts[w] : 0; }
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off); incl += lane >= off ? o : 0; }
-        int* wtot = chunk + 257;
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        int base = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) base += i < wv ? wtot[i] : 0;
-        chunk[threadIdx.x] = base + incl - mine;
-        T = (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
-        __syncthreads();
-    }
+    const int T = list_positions<256>(chunk, a.sel_counts, n_windows, per, wv, lane);
     const int G = (int)gridDim.x;
     // full tiles: fewer slices to reduce than with T rows spread over all the workgroups (a tile costs the same with 25 rows
     // as with 32), and every workgroup at most one more tile than any other
@@ -349,19 +186,7 @@ __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
             float* part_t = part + opaque;
             int c = c0, h = h0;
             asm volatile("" : "+v"(c), "+v"(h));
-            // column c = position lo + c of the batch's selected rows: its window by bisection of the threads' first
-            // positions (the last t with chunk[t] <= p has a non-empty range holding p), then along that thread's windows
-            const int lo = (int)((long long)ti * T / n_tiles), hi = (int)((long long)(ti + 1) * T / n_tiles);
-            int rowc = -1;
-            if (lo + c < hi) {
-                const int p = lo + c;
-                int t = 0;
-#pragma unroll
-                for (int s = 128; s >= 1; s >>= 1) t += (chunk[t + s] <= p) ? s : 0;
-                int w = t * per, acc = chunk[t], cnt = a.sel_counts[w];
-                while (p >= acc + cnt) { acc += cnt; ++w; cnt = a.sel_counts[w]; }
-                rowc = a.sel_rows[((size_t)w << a.win_shift) + (p - acc)];
-            }
+            const int rowc = tile_row<256>(chunk, a, per, T, n_tiles, ti, c);
             const bool live = rowc >= 0;
             const int rw = max(rowc, 0);
             const uint64_t gid = a.table_id0 + (uint64_t)rw;
@@ -371,8 +196,8 @@ __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
             float w1t[NK1][4], w1c[NK1][4];
             load_layer<VEC, NK1>(w1t, a.tgt, 0, 32 * wv + c, h, 0, (K1 + 7) & ~7);
             load_layer<VEC, NK1>(w1c, n, 0, 32 * wv + c, h, 0, (K1 + 7) & ~7);
-            coop_load_rows<VEC>(lds + CoopLds::Db, a.next_states, a.next_stride, K1, rowc, wv, c, h);
-            coop_load_rows<VEC>(lds + CoopLds::Xs, a.states, a.stride, K1, rowc, wv, c, h);
+            coop_load_rows<VEC>(Db, a.next_states, a.next_stride, K1, rowc, wv, c, h);
+            coop_load_rows<VEC>(Xs, a.states, a.stride, K1, rowc, wv, c, h);
             float wb5[16];
             if (wv == 1) back_load<32>(wb5, net_w(n, 4), A, 32, 0, c, h);
             // the row's transition, ahead of the forwards that need it last
@@ -382,25 +207,8 @@ __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
                 f32x16 qn, qv;
                 coop_forward_pair<VEC, NK1>(w1t, w1c, a.tgt, n, lds, wv, c, h, a.seed, gid, a.step, thr, scale, qn, qv);
                 QSTAMP(2);
-                if (wv == 0) {                                                // delta_5 and the loss terms (:270-279)
-                    float best = -INFINITY;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) if (rho(r) + 4 * h < A) best = fmaxf(best, qn[r]);
-                    best = fmaxf(best, __shfl_xor(best, 32));
-                    const float target = row_reward + a.gamma * best * (1.0f - row_done);
-                    float qa = 0.0f;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) qa += (rho(r) + 4 * h == act) ? qv[r] : 0.0f;
-                    qa += __shfl_xor(qa, 32);
-                    const float td = live ? qa - target : 0.0f;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) Da[(rho(r) + 4 * h) * kLd + c] = (rho(r) + 4 * h == act) ? 2.0f * td : 0.0f;
-                    float sq = (h == 0) ? td * td : 0.0f, cnt = (h == 0 && live) ? 1.0f : 0.0f;
-#pragma unroll
-                    for (int off = 32; off >= 1; off >>= 1) { sq += __shfl_xor(sq, off); cnt += __shfl_xor(cnt, off); }
-                    rows_sum += cnt; sq_sum += sq;
-                    if (STAB && h == 0 && live) { st_td += fabsf(td); st_q += qa; st_min = fminf(st_min, qa); st_max = fmaxf(st_max, qa); }
-                }
+                if (wv == 0)                                                  // delta_5 and the loss terms (:270-279)
+                    td_head<STAB>(qv, max_q_target(qn, A, h), a.gamma, row_reward, row_done, act, live, Da, c, h, rows_sum, sq_sum, st);
             }
             lds_barrier();
             QSTAMP(3);
@@ -444,7 +252,7 @@ __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
     }
 
     QSTAMP(8);
-    if (used && K1 <= 32) {                                       // (no tile for this workgroup: the reduce launch skips its slice)                                        // the second column tile of layer 1 was never touched
+    if (used && K1 <= 32) {                                       // the second column tile of layer 1 was never touched
         for (int i = threadIdx.x; i < 4 * 1024; i += 256) part[(size_t)(kSliceBlk1 + 2 * (i >> 10) + 1) * 1024 + (i & 1023)] = 0.0f;
     }
     // db rows: every bias is written by exactly one wavefront
@@ -454,17 +262,13 @@ __global__ __launch_bounds__(256) void qnet_train_kernel(const TrainArgs a) {
         part[kSliceBias + 128 + 32 * wv + c0] = b2;
         part[kSliceBias + 32 * wv + c0] = b1;
     }
-    float* wave_reward = lds + CoopLds::Tgt;                      // (32 spare words)
+    float* wave_reward = Tg;                                      // (32 spare words)
     lds_barrier();
     if (lane == 0) wave_reward[wv] = reward_sum;
     lds_barrier();
     if (STAB && wv == 0) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            st_td += __shfl_xor(st_td, off); st_q += __shfl_xor(st_q, off);
-            st_min = fminf(st_min, __shfl_xor(st_min, off)); st_max = fmaxf(st_max, __shfl_xor(st_max, off));
-        }
-        if (lane == 0) *reinterpret_cast<float4*>(part + kSliceStats + 4) = make_float4(st_td, st_q, st_min, st_max);
+        st.reduce();
+        if (lane == 0) st.store(part + kSliceStats + 4);
     }
     if (wv == 0 && lane == 0) {
         float* ps = part + kSliceStats;
@@ -491,76 +295,32 @@ __global__ __launch_bounds__(512) void qnet_train8_kernel(const TrainArgs a) {
     float* A4 = lds + CoopLds::A4; float* P = lds + CoopLds::P;
     float* G1 = lds + CoopLds::G1; float* G2 = lds + CoopLds::G2; float* G3 = lds + CoopLds::G3; float* G4 = lds + CoopLds::G4;
     float* Da = lds + CoopLds::Da; float* Db = lds + CoopLds::Db; float* Tg = lds + CoopLds::Tgt;
+    int* chunk = reinterpret_cast<int*>(lds + CoopLds::List);
     const uint32_t thr = (uint32_t)(a.drop_p * 65536.0f);
     const float scale = 1.0f / (1.0f - a.drop_p);
 
     float b5 = 0.0f, b4 = 0.0f, b3 = 0.0f, b2 = 0.0f, b1 = 0.0f;  // this wavefront's rows of db (see the stores at the end)
     float rows_sum = 0.0f, sq_sum = 0.0f;                        // wavefront 4
-    float st_td = 0.0f, st_q = 0.0f, st_min = INFINITY, st_max = -INFINITY;   // STAB, wavefront 4: per lane until the end
+    StabTotals st;                                               // STAB, wavefront 4: per lane until the end
     bool used = false;
     float* part = a.partials + (size_t)blockIdx.x * kSlicePitch;
-    if (blockIdx.x == 0 && threadIdx.x < 8) a.meet[threadIdx.x] = 0u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) a.scal[0] = 0.0f;
-    QSTAMP(0);
-    float reward_sum = 0.0f;
-    if (a.book) {
-        for (int win = blockIdx.x; win * 512 < a.n_rows; win += gridDim.x) {
-            const int row = win * 512 + threadIdx.x;
-            const bool cand = row < a.n_rows && (a.row_mask == nullptr || a.row_mask[row] != 0);
-            float rew = cand ? a.rewards[row] : 0.0f;
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) rew += __shfl_xor(rew, off);
-            reward_sum += rew;
-            if (a.terminated && row < a.n_rows && a.dones[row]) a.terminated[row] = 1;
-        }
-    }
+    train_prologue(a);
+    const float reward_sum = a.book ? book_candidates<512>(a) : 0.0f;
     const int W = 1 << a.win_shift;
     // (512 first positions, one per thread: a column's walk along its thread's windows below is half as long as with 256 -- at
     // 2,000,000 tables 31 windows instead of 62, a dependent load each)
     const int n_windows = (a.n_rows + W - 1) >> a.win_shift, per = (n_windows + 511) / 512;
-    int* chunk = reinterpret_cast<int*>(lds + CoopLds::List);
-    int T;
-    {
-        int mine = 0;
-        for (int j = 0; j < per; ++j) { const int w = threadIdx.x * per + j; mine += w < n_windows ? a.sel_counts[w] : 0; }
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off); incl += lane >= off ? o : 0; }
-        int* wtot = chunk + 512;
-        if (lane == 63) wtot[wv] = incl;
-        __syncthreads();
-        int base = 0; T = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const int n = wtot[i]; base += i < wv ? n : 0; T += n; }
-        chunk[threadIdx.x] = base + incl - mine;
-        __syncthreads();
-    }
+    const int T = list_positions<512>(chunk, a.sel_counts, n_windows, per, wv, lane);
     const int G = (int)gridDim.x;
     // full tiles: fewer slices to reduce than with T rows spread over all the workgroups (a tile costs the same with 25 rows
     // as with 32), and every workgroup at most one more tile than any other
     const int n_tiles = (T + 31) / 32;
     if (blockIdx.x == 0 && threadIdx.x == 0) a.meet[kMeetUsed] = (unsigned)min(n_tiles, G);      // workgroups 0 .. n_tiles - 1 hold a gradient slice (the reduce launch sums exactly those)
-    // column c of tile ti = position lo + c of the batch's listed rows: its thread's first position by bisection, then along that
-    // thread's windows (a dependent load each)
-    auto tile_row = [&](int ti, int c) -> int {
-        const int lo = (int)((long long)ti * T / n_tiles), hi = (int)((long long)(ti + 1) * T / n_tiles);
-        int rowc = -1;
-        if (lo + c < hi) {
-            const int p = lo + c;
-            int t = 0;
-#pragma unroll
-            for (int s = 256; s >= 1; s >>= 1) t += (chunk[t + s] <= p) ? s : 0;
-            int w = t * per, acc = chunk[t], cnt = a.sel_counts[w];
-            while (p >= acc + cnt) { acc += cnt; ++w; cnt = a.sel_counts[w]; }
-            rowc = a.sel_rows[((size_t)w << a.win_shift) + (p - acc)];
-        }
-        return rowc;
-    };
     // The NEXT tile's rows are looked up by wavefront 7 while it has nothing to do (the layer-5 backward phase runs on two
     // wavefronts) and their observation rows are asked for by everybody in the layer-4 phase: with ~20 tiles per workgroup the
     // walk and the gather's round trip were 5 % of a tile, in front of its first layer.
     int* const next_rows = reinterpret_cast<int*>(Tg);           // (free between delta_5 and the next tile's max Q_target)
-    int rowc_next = blockIdx.x < n_tiles ? tile_row((int)blockIdx.x, c0) : -1;
+    int rowc_next = blockIdx.x < n_tiles ? tile_row<512>(chunk, a, per, T, n_tiles, (int)blockIdx.x, c0) : -1;
     float xpre[8];
     bool have_pre = false;
     for (int ti = blockIdx.x; ti < n_tiles; ti += G) {
@@ -592,29 +352,9 @@ __global__ __launch_bounds__(512) void qnet_train8_kernel(const TrainArgs a) {
         if (grp) qv = group_forward<true, NK1>(w1r, n, Xs, A1, A2, A3, A4, G1, G2, G3, G4, P + 3 * 16 * 64, wq, c, h, a.seed, gid, a.step, thr, scale);
         else qv = group_forward<false, NK1>(w1r, a.tgt, Db, Da, Db, Da, Db, nullptr, nullptr, nullptr, nullptr, P, wq, c, h, 0, 0, 0, 0, 1.0f);
         QSTAMP(2);
-        if (wv == 0) {                                            // max_a' Q_target(s', a') per row -> Tg
-            float best = -INFINITY;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) if (rho(r) + 4 * h < A) best = fmaxf(best, qv[r]);
-            best = fmaxf(best, __shfl_xor(best, 32));
-            if (h == 0) Tg[c] = best;
-        }
+        if (wv == 0) { const float best = max_q_target(qv, A, h); if (h == 0) Tg[c] = best; }     // max_a' Q_target(s', a') per row -> Tg
         lds_barrier();
-        if (wv == 4) {                                            // delta_5 and the loss terms (:270-279)
-            const float target = row_reward + a.gamma * Tg[c] * (1.0f - row_done);
-            float qa = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) qa += (rho(r) + 4 * h == act) ? qv[r] : 0.0f;
-            qa += __shfl_xor(qa, 32);
-            const float td = live ? qa - target : 0.0f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Da[(rho(r) + 4 * h) * kLd + c] = (rho(r) + 4 * h == act) ? 2.0f * td : 0.0f;
-            float sq = (h == 0) ? td * td : 0.0f, cnt = (h == 0 && live) ? 1.0f : 0.0f;
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) { sq += __shfl_xor(sq, off); cnt += __shfl_xor(cnt, off); }
-            rows_sum += cnt; sq_sum += sq;
-            if (STAB && h == 0 && live) { st_td += fabsf(td); st_q += qa; st_min = fminf(st_min, qa); st_max = fmaxf(st_max, qa); }
-        }
+        if (wv == 4) td_head<STAB>(qv, Tg[c], a.gamma, row_reward, row_done, act, live, Da, c, h, rows_sum, sq_sum, st);   // delta_5 and the loss terms (:270-279)
         lds_barrier();
         QSTAMP(3);
         // layer 5 (delta_5 in Da): dW5 on wavefront 0 | delta_4 -> Db on wavefront 1
@@ -623,7 +363,7 @@ __global__ __launch_bounds__(512) void qnet_train8_kernel(const TrainArgs a) {
         if (wv == 0) dw_accum(Da, A4, part_t, kSliceBlk5, 0, 0, c, h, first, &b5);
         if (wv == 1) { float wb5[16]; back_load<32>(wb5, net_w(n, 4), A, 32, 0, c, h); back_mul<32>(wb5, 0, Da, G4, Db, c, h); }
         const bool more = ti + G < n_tiles;
-        if (wv == 7 && more) { const int r = tile_row(ti + G, c); if (h == 0) next_rows[c] = r; }
+        if (wv == 7 && more) { const int r = tile_row<512>(chunk, a, per, T, n_tiles, ti + G, c); if (h == 0) next_rows[c] = r; }
         lds_barrier();
         QSTAMP(4);
         rowc_next = more ? next_rows[c] : -1;
@@ -681,12 +421,8 @@ __global__ __launch_bounds__(512) void qnet_train8_kernel(const TrainArgs a) {
     if (lane == 0) wave_reward[wv] = reward_sum;
     if (wv == 4 && lane == 0) { wave_reward[8] = rows_sum; wave_reward[9] = sq_sum; }
     if (STAB && wv == 4) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            st_td += __shfl_xor(st_td, off); st_q += __shfl_xor(st_q, off);
-            st_min = fminf(st_min, __shfl_xor(st_min, off)); st_max = fmaxf(st_max, __shfl_xor(st_max, off));
-        }
-        if (lane == 0) *reinterpret_cast<float4*>(part + kSliceStats + 4) = make_float4(st_td, st_q, st_min, st_max);
+        st.reduce();
+        if (lane == 0) st.store(part + kSliceStats + 4);
     }
     lds_barrier();
     if (wv == 0 && lane == 0) {
@@ -825,32 +561,23 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(const ReduceArgs 
         }
     }
     float rows = 0.0f, sq = 0.0f; double rew = 0.0;
-    float st_td = 0.0f, st_q = 0.0f, st_min = INFINITY, st_max = -INFINITY;     // stability totals (workgroup 0)
+    StabTotals st;                                               // stability totals (workgroup 0)
     const bool stab = a.stab != nullptr && blockIdx.x == 0;
     if ((FUSED || blockIdx.x == 0) && threadIdx.x < 64) {        // fused: every workgroup totals the row count itself
         for (int b = threadIdx.x; b < a.n_blocks; b += 64) {
             const float* ps = a.partials + b * pitch + kSliceStats;
             rows += ps[0]; sq += ps[1]; rew += (double)ps[2];
-            if (stab) {
-                const float4 s4 = *reinterpret_cast<const float4*>(ps + 4);
-                st_td += s4.x; st_q += s4.y; st_min = fminf(st_min, s4.z); st_max = fmaxf(st_max, s4.w);
-            }
+            if (stab) st.add(StabTotals::load(ps + 4));
         }
         if (blockIdx.x == 0 && a.reward_sum) for (int wdw = threadIdx.x; wdw < a.n_windows; wdw += 64) rew += (double)a.win_reward[wdw];
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) { rows += __shfl_xor(rows, off); sq += __shfl_xor(sq, off); rew += __shfl_xor(rew, off); }
-        if (stab) {
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                st_td += __shfl_xor(st_td, off); st_q += __shfl_xor(st_q, off);
-                st_min = fminf(st_min, __shfl_xor(st_min, off)); st_max = fmaxf(st_max, __shfl_xor(st_max, off));
-            }
-        }
+        if (stab) st.reduce();
         if (blockIdx.x == 0 && threadIdx.x == 0) {
             a.scal[1] = rows; a.scal[2] = sq;
             if (!FUSED && rows > 0.0f && a.step) *a.step += 1;
             if (a.reward_sum) *a.reward_sum += rew;
-            if (!FUSED && stab) { a.stab[0] = rows; a.stab[1] = st_td; a.stab[2] = st_q; a.stab[3] = st_min; a.stab[4] = st_max; }
+            if (!FUSED && stab) { a.stab[0] = rows; a.stab[1] = st.td; a.stab[2] = st.q; a.stab[3] = st.qmin; a.stab[4] = st.qmax; }
         }
     }
     if (FUSED) {
@@ -900,7 +627,7 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(const ReduceArgs 
             a.scal[0] = total_ss;
             const float inv = count > 0.0f ? 1.0f / count : 0.0f;
             w.report[0] = count; w.report[1] = sq * inv; w.report[2] = sqrtf(total_ss) * inv;
-            if (stab) stability_finish(a.stab, count, st_td, st_q, st_min, st_max, w.report[2], w.max_norm, w.report[1]);
+            if (stab) stability_finish(a.stab, count, st.td, st.q, st.qmin, st.qmax, w.report[2], w.max_norm, w.report[1]);
         }
     }
 }
@@ -971,6 +698,40 @@ bool fused_apply_fits(unsigned grid) {
     return resident[dev] >= (int)grid;
 }
 
+// Launches a kernel that needs more dynamic LDS than the default limit: the limit of `fn` is raised the first time `fn` is
+// launched.  `attr`: what raising it answered (the launch is not tried after a refusal), `launch`: what the launch answered.
+struct LdsLaunch { hipError_t attr, launch; };
+LdsLaunch launch_lds(const void* fn, unsigned grid, unsigned block, void* args, size_t lds_bytes, hipStream_t st) {
+    static const void* raised[32] = {};                            // (this file has 22 such kernel instances)
+    int i = 0;
+    while (i < 32 && raised[i] && raised[i] != fn) ++i;
+    if (i == 32 || !raised[i]) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return {e, hipSuccess};
+        if (i < 32) raised[i] = fn;
+    }
+    void* params[1] = {args};
+    return {hipSuccess, hipLaunchKernel(fn, dim3(grid), dim3(block), params, lds_bytes, st)};
+}
+
+// PulseQNetTrain.select_scratch / pulse_qnet_act_select's select_scratch (int32 words, pulse_env.h), nw = ceil(n_rows / 256):
+// [0, 256 nw) the training row lists; [256 nw, 258 nw) their window counts (256-row windows from the select launch, 128-row
+// windows from pulse_qnet_act_select); [258 nw, 259 nw) window reward sums; [259 nw, +512) the fused reduce launch's meeting
+// words; then, for the two-launch act form, [.., + 256 nw) the learner's rows per window and [.., + 2 nw) their counts.
+struct SelectScratch {
+    int32_t* base; int64_t words; size_t nw;
+    SelectScratch(int32_t* p, int64_t n_words, int n_rows) : base(p), words(n_words), nw((size_t)((n_rows + 255) / 256)) {}
+    static constexpr size_t kTrainPer = 256 + 2 + 1, kActPer = kTrainPer + 256 + 2, kMeetWords = 512;    // 259 and 517 words per 256 rows
+    int32_t* rows() const { return base; }
+    int32_t* counts() const { return base + nw * 256; }
+    float* win_reward() const { return reinterpret_cast<float*>(base + nw * 258); }
+    unsigned* meet() const { return reinterpret_cast<unsigned*>(base + nw * kTrainPer); }
+    int32_t* asel_rows() const { return base + nw * kTrainPer + kMeetWords; }
+    int32_t* asel_counts() const { return asel_rows() + nw * 256; }
+    bool holds_train_lists() const { return base && words >= (int64_t)(nw * kTrainPer + kMeetWords); }
+    bool holds_act_lists() const { return base && words >= (int64_t)(nw * kActPer + kMeetWords); }
+};
+
 int launch(const QNetArgs& a, void* stream) {
     const PulseQNet& n = a.net;
     if (a.n_rows < 0) return pulse::fail(PULSE_EINVAL, "pulse_qnet: n_rows < 0");
@@ -986,64 +747,191 @@ int launch(const QNetArgs& a, void* stream) {
     const bool select = a.seat_idx != nullptr;
     const unsigned grid = select ? (unsigned)((a.n_rows + 63) / 64) : (unsigned)((a.n_rows + 31) / 32);
     hipStream_t st = (hipStream_t)stream;
+    void* args = const_cast<QNetArgs*>(&a);
     if (select && act_rows16_ok(a)) {
         const int cus = device_cus();
         const bool wide = a.n_rows >= 1024 * cus;                 // large batches: windows of 1,024 candidates (~11 tiles for the 16 wavefronts)
-        const int slot = (n.state_dim <= 48 ? 0 : 1) + (wide ? 2 : 0);
-        const void* fns[4] = {reinterpret_cast<const void*>(&qnet_act_r16_kernel<3, 256>), reinterpret_cast<const void*>(&qnet_act_r16_kernel<4, 256>),
-                              reinterpret_cast<const void*>(&qnet_act_r16_kernel<3, 1024>), reinterpret_cast<const void*>(&qnet_act_r16_kernel<4, 1024>)};
-        const size_t lds_sizes[4] = {R16Lds<3, 256>::bytes, R16Lds<4, 256>::bytes, R16Lds<3, 1024>::bytes, R16Lds<4, 1024>::bytes};
-        static const void* attr_set[4] = {nullptr, nullptr, nullptr, nullptr};
-        if (attr_set[slot] != fns[slot]) {
-            const hipError_t e = hipFuncSetAttribute(fns[slot], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sizes[slot]);
-            if (e != hipSuccess) {                           // a device (partition) without that much LDS per workgroup: the tile kernels
-                (void)hipGetLastError();
-                g_rows16_unavailable = true;
-                return launch(a, stream);
-            }
-            attr_set[slot] = fns[slot];
-        }
+        const bool k3 = n.state_dim <= 48;
+        const void* fn = wide ? (k3 ? reinterpret_cast<const void*>(&qnet_act_r16_kernel<3, 1024>) : reinterpret_cast<const void*>(&qnet_act_r16_kernel<4, 1024>))
+                              : (k3 ? reinterpret_cast<const void*>(&qnet_act_r16_kernel<3, 256>) : reinterpret_cast<const void*>(&qnet_act_r16_kernel<4, 256>));
+        const size_t lds_bytes = wide ? (k3 ? R16Lds<3, 1024>::bytes : R16Lds<4, 1024>::bytes) : (k3 ? R16Lds<3, 256>::bytes : R16Lds<4, 256>::bytes);
         const int win = wide ? 1024 : 256;
         const unsigned n_win = (unsigned)((a.n_rows + win - 1) / win);
-        void* params[1] = {const_cast<QNetArgs*>(&a)};
-        const hipError_t le = hipLaunchKernel(fns[slot], dim3(std::min(n_win, (unsigned)cus)), dim3(kR16Threads), params, lds_sizes[slot], st);
-        if (le != hipSuccess) return pulse::fail_hip((int)le, "pulse_qnet_act (sixteen rows per wavefront) launch");
+        const LdsLaunch r = launch_lds(fn, std::min(n_win, (unsigned)cus), kR16Threads, args, lds_bytes, st);
+        if (r.attr != hipSuccess) {                          // a device (partition) without that much LDS per workgroup: the tile kernels
+            (void)hipGetLastError();
+            g_rows16_unavailable = true;
+            return launch(a, stream);
+        }
+        if (r.launch != hipSuccess) return pulse::fail_hip((int)r.launch, "pulse_qnet_act (sixteen rows per wavefront) launch");
     } else if (select && n.state_dim > 64) {        // wider inputs than the cooperative tile's LDS image: one wavefront per tile
         if (vec) hipLaunchKernelGGL((qnet_kernel<true, true>), dim3(grid), dim3(64), 0, st, a); else hipLaunchKernelGGL((qnet_kernel<true, false>), dim3(grid), dim3(64), 0, st, a);
     } else if (select) {
-        const int slot = vec ? (n.state_dim <= 40 ? 0 : 1) : 2;
-        const void* fns[3] = {reinterpret_cast<const void*>(&qnet_act4_kernel<true, kActWin, 5>),
-                              reinterpret_cast<const void*>(&qnet_act4_kernel<true, kActWin, 8>),
-                              reinterpret_cast<const void*>(&qnet_act4_kernel<false, kActWin, 8>)};
-        const void* fn = fns[slot];
-        static const void* attr_set[3] = {nullptr, nullptr, nullptr};
-        if (attr_set[slot] != fn) {
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kActLdsBytes);
-            if (e != hipSuccess) return pulse::fail_hip((int)e, "pulse_qnet_act: LDS size attribute");
-            attr_set[slot] = fn;
-        }
-        const unsigned g4 = (unsigned)((a.n_rows + kActWin - 1) / kActWin);
-        void* params[1] = {const_cast<QNetArgs*>(&a)};
-        const hipError_t le = hipLaunchKernel(fn, dim3(g4), dim3(256), params, kActLdsBytes, st);
-        if (le != hipSuccess) return pulse::fail_hip((int)le, "pulse_qnet_act launch");
+        const bool k5 = vec && n.state_dim <= 40;
+        const void* fn = !vec ? reinterpret_cast<const void*>(&qnet_act4_kernel<false, kActWin, 8>)
+                         : k5 ? reinterpret_cast<const void*>(&qnet_act4_kernel<true, kActWin, 5>) : reinterpret_cast<const void*>(&qnet_act4_kernel<true, kActWin, 8>);
+        const LdsLaunch r = launch_lds(fn, (unsigned)((a.n_rows + kActWin - 1) / kActWin), 256, args, kActLdsBytes, st);
+        if (r.attr != hipSuccess) return pulse::fail_hip((int)r.attr, "pulse_qnet_act: LDS size attribute");
+        if (r.launch != hipSuccess) return pulse::fail_hip((int)r.launch, "pulse_qnet_act launch");
         if (a.asel_counts) {                                 // two-launch form: the window launch listed the rows, this one runs them in full tiles
-            const void* fns2[3] = {reinterpret_cast<const void*>(&qnet_act_rows_kernel<true, kActWin, 5>),
-                                   reinterpret_cast<const void*>(&qnet_act_rows_kernel<true, kActWin, 8>),
-                                   reinterpret_cast<const void*>(&qnet_act_rows_kernel<false, kActWin, 8>)};
-            static const void* attr_set2[3] = {nullptr, nullptr, nullptr};
-            if (attr_set2[slot] != fns2[slot]) {
-                const hipError_t e2 = hipFuncSetAttribute(fns2[slot], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kActLdsBytes);
-                if (e2 != hipSuccess) return pulse::fail_hip((int)e2, "pulse_qnet_act: LDS size attribute");
-                attr_set2[slot] = fns2[slot];
-            }
+            const void* fn2 = !vec ? reinterpret_cast<const void*>(&qnet_act_rows_kernel<false, kActWin, 8>)
+                              : k5 ? reinterpret_cast<const void*>(&qnet_act_rows_kernel<true, kActWin, 5>) : reinterpret_cast<const void*>(&qnet_act_rows_kernel<true, kActWin, 8>);
             const unsigned tiles_at_most = (unsigned)((a.n_rows + 31) / 32);
-            const hipError_t l2 = hipLaunchKernel(fns2[slot], dim3(std::min(tiles_at_most, 768u)), dim3(256), params, kActLdsBytes, st);   // three workgroups per CU
-            if (l2 != hipSuccess) return pulse::fail_hip((int)l2, "pulse_qnet_act (rows) launch");
+            const LdsLaunch r2 = launch_lds(fn2, std::min(tiles_at_most, 768u), 256, args, kActLdsBytes, st);   // three workgroups per CU
+            if (r2.attr != hipSuccess) return pulse::fail_hip((int)r2.attr, "pulse_qnet_act: LDS size attribute");
+            if (r2.launch != hipSuccess) return pulse::fail_hip((int)r2.launch, "pulse_qnet_act (rows) launch");
         }
     }
     else { if (vec) hipLaunchKernelGGL((qnet_kernel<false, true>), dim3(grid), dim3(64), 0, st, a); else hipLaunchKernelGGL((qnet_kernel<false, false>), dim3(grid), dim3(64), 0, st, a); }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : pulse::fail_hip((int)e, "pulse_qnet launch");
+}
+
+int act_call(const PulseQNet* net, const float* states, int64_t row_stride, int32_t n_rows, const int32_t* seat_idx,
+             int32_t q_seat, float epsilon, uint64_t seed, uint64_t step, uint64_t table_id0, int64_t* actions,
+             float* q_out, const uint8_t* terminated, uint8_t* row_mask_out, int32_t* select_scratch, int64_t select_words, void* stream) {
+    if (!net || !actions) return pulse::fail(PULSE_EINVAL, "pulse_qnet_act: null argument");
+    if (row_mask_out && (!seat_idx || net->state_dim > 64))
+        return pulse::fail(PULSE_EINVAL, "pulse_qnet_act: row_mask_out needs seat_idx and state_dim <= 64");
+    QNetArgs a{};
+    a.net = *net; a.states = states; a.row_stride = row_stride; a.n_rows = n_rows; a.seat_idx = seat_idx; a.q_seat = q_seat;
+    a.epsilon = epsilon; a.seed = seed; a.step = step; a.table_id0 = table_id0; a.actions = actions; a.q_out = q_out;
+    a.terminated = terminated; a.row_mask_out = row_mask_out;
+    if (select_scratch) {
+        const SelectScratch sc(select_scratch, select_words, n_rows);
+        a.tsel_rows = sc.rows(); a.tsel_counts = sc.counts();
+        // large batches, scratch permitting: list the learner's rows per window, then run them in full tiles (qnet_act_rows_kernel)
+        if (!act_rows16_ok(a) && n_rows >= kActTwoLaunchRows && sc.holds_act_lists() && net->state_dim <= 64) {
+            a.asel_rows = sc.asel_rows(); a.asel_counts = sc.asel_counts();
+        }
+    }
+    return launch(a, stream);
+}
+
+AdamArgs adam_args(const PulseQNetTrain* t, int np) {
+    AdamArgs b{};
+    b.params = t->params; b.target = t->target_params; b.grad = t->grad; b.m = t->exp_avg; b.v = t->exp_avg_sq; b.step = (const long long*)t->step;
+    b.scal = t->stats; b.report = t->report; b.n_params = np; b.lr = t->lr; b.wd = t->weight_decay; b.beta1 = t->beta1; b.beta2 = t->beta2;
+    b.eps = t->eps; b.max_norm = t->max_grad_norm; b.update_freq = t->update_freq; b.stab = t->stability;
+    return b;
+}
+
+// the transitions of one pulse_qnet_train_step / pulse_qnet_train_grads call
+struct TrainBatch {
+    const float* states; int64_t row_stride; const int64_t* actions; const float* rewards; const float* next_states; int64_t next_stride;
+    const uint8_t* dones; const uint8_t* row_mask; int32_t n_rows; uint64_t seed, step_counter, table_id0; uint8_t* terminated; double* reward_sum;
+};
+
+// What every training entry point checks, in one order; `b`: the call's transitions, nullptr for pulse_qnet_train_apply (which
+// has none).  Last, once: the report of an earlier launch whose meeting was called off (see fused_apply_fits).
+int train_validate(const PulseQNetTrain* t, const TrainBatch* b) {
+    if (!t || (b && (!b->states || !b->actions || !b->rewards || !b->next_states || !b->dones)))
+        return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: null argument");
+    const PulseQNet& n = t->net;
+    if (n.state_dim < 13 || n.state_dim > 64 || n.n_actions < 1 || n.n_actions > 32)
+        return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: state_dim must be 13..64 (column 12 is the seat status) and n_actions 1..32");
+    if (t->target.state_dim != n.state_dim || t->target.n_actions != n.n_actions)
+        return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: target network shape differs");
+    if (!t->params || !t->target_params || !t->grad || !t->exp_avg || !t->exp_avg_sq || !t->step || !t->stats || !t->report || !t->partials)
+        return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: null optimizer buffer");
+    if (t->max_blocks < 1) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: max_blocks < 1");
+    // the ten tensors of each network must be the views of the flat buffers in the documented order
+    const NetShape shape = net_shape(n.state_dim, n.n_actions);
+    const float* got[10] = {n.w1, n.b1, n.w2, n.b2, n.w3, n.b3, n.w4, n.b4, n.w5, n.b5};
+    const float* got_t[10] = {t->target.w1, t->target.b1, t->target.w2, t->target.b2, t->target.w3, t->target.b3, t->target.w4, t->target.b4,
+                              t->target.w5, t->target.b5};
+    for (int l = 0; l < 5; ++l) {
+        if (got[2 * l] != t->params + shape.w[l] || got[2 * l + 1] != t->params + shape.b[l] ||
+            got_t[2 * l] != t->target_params + shape.w[l] || got_t[2 * l + 1] != t->target_params + shape.b[l])
+            return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: network tensors are not the views of the flat parameter buffers");
+    }
+    if (b && (b->row_stride < n.state_dim || b->next_stride < n.state_dim)) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: row stride < state_dim");
+    if (!aligned16(t->params) || !aligned16(t->target_params))
+        return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: flat parameter buffers must be 16-byte aligned");
+    if (!(t->dropout_p >= 0.0f && t->dropout_p < 1.0f)) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: dropout_p outside [0, 1)");
+    if (b && b->n_rows < 0) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: n_rows < 0");
+    if (g_meet_gave_up) {
+        const long long gave_up = __atomic_load_n(g_meet_gave_up, __ATOMIC_ACQUIRE);
+        if (gave_up != g_meet_gave_up_seen) {
+            g_meet_gave_up_seen = gave_up;
+            return pulse::fail(PULSE_EINTERNAL, "pulse_qnet_train_step: an earlier reduce + AdamW launch could not gather its workgroups within its wait "
+                                                "(another process or stream holds the GPU's compute units?) and applied NO update (report[3] = -1); "
+                                                "set PulseQNetTrain.separate_apply to run AdamW as a launch of its own");
+        }
+    }
+    return 0;
+}
+
+int launched() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : pulse::fail_hip((int)e, "pulse_qnet_train_step launch");
+}
+
+// the training instance: layer-1 steps 5 (16-byte rows of <= 40 inputs) or 8; four or eight wavefronts per tile; stability totals or not
+template <bool VEC, int NK1, bool STAB>
+const void* train_kernel(bool four) {
+    return four ? reinterpret_cast<const void*>(&qnet_train_kernel<VEC, NK1, STAB>) : reinterpret_cast<const void*>(&qnet_train8_kernel<VEC, NK1, STAB>);
+}
+template <bool STAB>
+const void* train_kernel(bool vec, int state_dim, bool four) {
+    return !vec ? train_kernel<false, 8, STAB>(four) : state_dim <= 40 ? train_kernel<true, 5, STAB>(four) : train_kernel<true, 8, STAB>(four);
+}
+
+// select (unless pulse_qnet_act_select listed the rows) + training + reduce launches for a call with rows; `apply`: AdamW rides
+// in the reduce launch where the device can hold that launch's whole grid at once (*fused says whether it did)
+int train_grads(const PulseQNetTrain* t, const TrainBatch& b, bool apply, bool* fused, hipStream_t st) {
+    const PulseQNet& n = t->net;
+    const int np = net_shape(n.state_dim, n.n_actions).count;
+    const SelectScratch sc(t->select_scratch, t->select_words, b.n_rows);
+    if (!sc.holds_train_lists()) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: select_scratch must hold 259 words per 256 rows + 512");
+    TrainArgs a{};
+    a.net = FlatNet{t->params, n.state_dim, n.n_actions}; a.tgt = FlatNet{t->target_params, n.state_dim, n.n_actions};
+    a.partials = t->partials; a.scal = t->stats; a.n_params = np; a.states = b.states; a.stride = b.row_stride;
+    a.actions = b.actions; a.rewards = b.rewards; a.next_states = b.next_states; a.next_stride = b.next_stride; a.dones = b.dones;
+    a.n_rows = b.n_rows; a.seed = b.seed; a.step = b.step_counter; a.table_id0 = b.table_id0;
+    a.gamma = t->gamma; a.drop_p = t->dropout_p;
+    a.sel_rows = sc.rows(); a.sel_counts = sc.counts(); a.meet = sc.meet();
+    int n_windows = 0;                                             // (windows with a reward sum: the select launch's)
+    if (t->select_from_act) {                                      // the lists are pulse_qnet_act_select's, on this observation
+        a.win_shift = 7; a.book = 1; a.row_mask = b.row_mask; a.terminated = b.terminated;
+    } else {
+        a.win_shift = 8; a.book = 0;
+        n_windows = (int)sc.nw;
+        SelectArgs sa{};
+        sa.states = b.states; sa.stride = b.row_stride; sa.rewards = b.rewards; sa.dones = b.dones; sa.row_mask = b.row_mask; sa.terminated = b.terminated;
+        sa.n_rows = b.n_rows; sa.sel_rows = sc.rows(); sa.sel_counts = sc.counts(); sa.win_reward = sc.win_reward();
+        hipLaunchKernelGGL(qnet_select_kernel, dim3((unsigned)sc.nw), dim3(256), 0, st, sa);
+    }
+    const bool vec = n.state_dim % 8 == 0 && b.row_stride % 4 == 0 && b.next_stride % 4 == 0 && aligned16(b.states) && aligned16(b.next_states);
+    static const bool four = [] { const char* e = getenv("PULSE_TRAIN_WAVES"); return e && e[0] == '4'; }();
+    const void* fn = t->stability ? train_kernel<true>(vec, n.state_dim, four) : train_kernel<false>(vec, n.state_dim, four);
+    // persistent workgroups (157 KB of LDS: one per CU), one per possible tile of 32 rows at most
+    const int grid = std::min((b.n_rows + 31) / 32, (int)t->max_blocks);
+    const LdsLaunch tl = launch_lds(fn, (unsigned)grid, four ? 256 : 512, &a, kTrainLdsBytes, st);
+    if (tl.attr != hipSuccess) return pulse::fail_hip((int)tl.attr, "pulse_qnet_train_step: LDS size attribute");
+    if (tl.launch != hipSuccess) return pulse::fail_hip((int)tl.launch, "pulse_qnet_train_step launch");
+    ReduceArgs r{};
+    r.partials = t->partials; r.n_blocks = grid; r.n_params = np; r.state_dim = n.state_dim; r.n_actions = n.n_actions;
+    r.grad = t->grad; r.scal = t->stats;
+    r.step = apply ? (long long*)t->step : nullptr;               // gradients only: the caller advances the step after its all-reduce
+    r.reward_sum = b.reward_sum; r.win_reward = sc.win_reward(); r.n_windows = n_windows; r.meet = a.meet;
+    const AdamArgs w = adam_args(t, np);
+    const unsigned rg = (unsigned)((kSliceStats + 127) / 128);
+    *fused = apply && !t->separate_apply && fused_apply_fits(rg);
+    r.wait_ticks = t->meet_wait_ticks > 0 ? (long long)t->meet_wait_ticks : 500000000ll;     // 5 s of the 100 MHz clock
+    r.extra_arrivals = t->debug_meet_extra > 0 ? (unsigned)t->debug_meet_extra : 0u;
+    r.gave_up = g_meet_gave_up;
+    r.stab = t->stability;
+    if (*fused) hipLaunchKernelGGL(qnet_grad_reduce_kernel<true>, dim3(rg), dim3(256), 0, st, r, w);
+    else hipLaunchKernelGGL(qnet_grad_reduce_kernel<false>, dim3(rg), dim3(256), 0, st, r, w);
+    return launched();
+}
+
+// AdamW as a launch of its own, on the gradient and the totals the reduce launch (or the caller's all-reduce) left
+int train_adamw(const PulseQNetTrain* t, hipStream_t st) {
+    const int np = net_shape(t->net.state_dim, t->net.n_actions).count;
+    hipLaunchKernelGGL(qnet_adamw_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, adam_args(t, np));
+    return launched();
 }
 
 }  // namespace
@@ -1055,12 +943,6 @@ int pulse_qnet_forward(const PulseQNet* net, const float* states, int64_t row_st
     QNetArgs a{};
     a.net = *net; a.states = states; a.row_stride = row_stride; a.n_rows = n_rows; a.q_out = q_out;
     return launch(a, stream);
-}
-
-namespace {
-int act_call(const PulseQNet* net, const float* states, int64_t row_stride, int32_t n_rows, const int32_t* seat_idx,
-             int32_t q_seat, float epsilon, uint64_t seed, uint64_t step, uint64_t table_id0, int64_t* actions,
-             float* q_out, const uint8_t* terminated, uint8_t* row_mask_out, int32_t* select_scratch, int64_t select_words, void* stream);
 }
 
 int pulse_qnet_act(const PulseQNet* net, const float* states, int64_t row_stride, int32_t n_rows, const int32_t* seat_idx,
@@ -1075,35 +957,11 @@ int pulse_qnet_act_select(const PulseQNet* net, const float* states, int64_t row
                           const uint8_t* terminated, uint8_t* row_mask_out, int32_t* select_scratch, int64_t select_words, void* stream) {
     if (!select_scratch || !seat_idx || !row_mask_out || !net || net->state_dim < 13 || net->state_dim > 64)
         return pulse::fail(PULSE_EINVAL, "pulse_qnet_act_select: needs seat_idx, row_mask_out, select_scratch and state_dim 13..64");
-    if (select_words < (int64_t)((n_rows + 255) / 256) * 259 + 512)
+    if (!SelectScratch(select_scratch, select_words, n_rows).holds_train_lists())
         return pulse::fail(PULSE_EINVAL, "pulse_qnet_act_select: select_scratch must hold 259 words per 256 rows + 512");
     return act_call(net, states, row_stride, n_rows, seat_idx, q_seat, epsilon, seed, step, table_id0, actions, nullptr, terminated, row_mask_out,
                     select_scratch, select_words, stream);
 }
-
-namespace {
-int act_call(const PulseQNet* net, const float* states, int64_t row_stride, int32_t n_rows, const int32_t* seat_idx,
-             int32_t q_seat, float epsilon, uint64_t seed, uint64_t step, uint64_t table_id0, int64_t* actions,
-             float* q_out, const uint8_t* terminated, uint8_t* row_mask_out, int32_t* select_scratch, int64_t select_words, void* stream) {
-    if (!net || !actions) return pulse::fail(PULSE_EINVAL, "pulse_qnet_act: null argument");
-    if (row_mask_out && (!seat_idx || net->state_dim > 64))
-        return pulse::fail(PULSE_EINVAL, "pulse_qnet_act: row_mask_out needs seat_idx and state_dim <= 64");
-    QNetArgs a{};
-    a.net = *net; a.states = states; a.row_stride = row_stride; a.n_rows = n_rows; a.seat_idx = seat_idx; a.q_seat = q_seat;
-    a.epsilon = epsilon; a.seed = seed; a.step = step; a.table_id0 = table_id0; a.actions = actions; a.q_out = q_out;
-    a.terminated = terminated; a.row_mask_out = row_mask_out;
-    if (select_scratch) {
-        const size_t nw = (size_t)((n_rows + 255) / 256);
-        a.tsel_rows = select_scratch; a.tsel_counts = select_scratch + nw * 256;
-        // large batches, scratch permitting: list the learner's rows per window, then run them in full tiles (qnet_act_rows_kernel)
-        if (!act_rows16_ok(a) && n_rows >= kActTwoLaunchRows && select_words >= (int64_t)(nw * 517 + 512) && net->state_dim <= 64) {
-            a.asel_rows = select_scratch + nw * 259 + 512; a.asel_counts = a.asel_rows + nw * 256;
-        }
-    }
-    return launch(a, stream);
-}
-}  // namespace
-
 
 #if PULSE_STAMPS
 int pulse_debug_set_qnet_stamp_buffer(unsigned long long* buf) {
@@ -1118,153 +976,34 @@ int64_t pulse_qnet_called_off_meetings(void) { return g_meet_gave_up ? (int64_t)
 
 int pulse_qnet_param_count(int32_t state_dim, int32_t n_actions) {
     if (state_dim < 1 || n_actions < 1 || n_actions > 32) return pulse::fail(PULSE_EINVAL, "pulse_qnet_param_count: bad dimensions");
-    return 128 * state_dim + 128 + 128 * 128 + 128 + 64 * 128 + 64 + 32 * 64 + 32 + 32 * n_actions + n_actions;
+    return net_shape(state_dim, n_actions).count;
 }
-
-namespace {
-AdamArgs adam_args(const PulseQNetTrain* t, int np) {
-    AdamArgs b{};
-    b.params = t->params; b.target = t->target_params; b.grad = t->grad; b.m = t->exp_avg; b.v = t->exp_avg_sq; b.step = (const long long*)t->step;
-    b.scal = t->stats; b.report = t->report; b.n_params = np; b.lr = t->lr; b.wd = t->weight_decay; b.beta1 = t->beta1; b.beta2 = t->beta2;
-    b.eps = t->eps; b.max_norm = t->max_grad_norm; b.update_freq = t->update_freq; b.stab = t->stability;
-    return b;
-}
-
-int train_launches(const PulseQNetTrain* t, const float* states, int64_t row_stride, const int64_t* actions,
-                   const float* rewards, const float* next_states, int64_t next_stride, const uint8_t* dones,
-                   const uint8_t* row_mask, int32_t n_rows, uint64_t seed, uint64_t step_counter, uint64_t table_id0,
-                   uint8_t* terminated, double* reward_sum, bool grads, bool apply, void* stream) {
-    if (!t || !states || !actions || !rewards || !next_states || !dones)
-        return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: null argument");
-    const PulseQNet& n = t->net;
-    if (n.state_dim < 13 || n.state_dim > 64 || n.n_actions < 1 || n.n_actions > 32)
-        return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: state_dim must be 13..64 (column 12 is the seat status) and n_actions 1..32");
-    if (t->target.state_dim != n.state_dim || t->target.n_actions != n.n_actions)
-        return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: target network shape differs");
-    if (!t->params || !t->target_params || !t->grad || !t->exp_avg || !t->exp_avg_sq || !t->step || !t->stats || !t->report || !t->partials)
-        return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: null optimizer buffer");
-    if (t->max_blocks < 1) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: max_blocks < 1");
-    const int np = pulse_qnet_param_count(n.state_dim, n.n_actions);
-    // the ten tensors of each network must be the views of the flat buffers in the documented order
-    const float* expect = t->params; const float* expect_t = t->target_params;
-    const float* got[10] = {n.w1, n.b1, n.w2, n.b2, n.w3, n.b3, n.w4, n.b4, n.w5, n.b5};
-    const float* got_t[10] = {t->target.w1, t->target.b1, t->target.w2, t->target.b2, t->target.w3, t->target.b3, t->target.w4, t->target.b4,
-                              t->target.w5, t->target.b5};
-    const int sizes[10] = {128 * n.state_dim, 128, 128 * 128, 128, 64 * 128, 64, 32 * 64, 32, 32 * n.n_actions, n.n_actions};
-    for (int i = 0; i < 10; ++i) {
-        if (got[i] != expect || got_t[i] != expect_t)
-            return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: network tensors are not the views of the flat parameter buffers");
-        expect += sizes[i]; expect_t += sizes[i];
-    }
-    if (row_stride < n.state_dim || next_stride < n.state_dim) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: row stride < state_dim");
-    if (!aligned16(t->params) || !aligned16(t->target_params))
-        return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: flat parameter buffers must be 16-byte aligned");
-    if (!(t->dropout_p >= 0.0f && t->dropout_p < 1.0f)) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: dropout_p outside [0, 1)");
-    if (n_rows < 0) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: n_rows < 0");
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned eg = (unsigned)((np + 255) / 256);
-    bool fused = false;
-    if (g_meet_gave_up) {
-        const long long n = __atomic_load_n(g_meet_gave_up, __ATOMIC_ACQUIRE);
-        if (n != g_meet_gave_up_seen) {
-            g_meet_gave_up_seen = n;
-            return pulse::fail(PULSE_EINTERNAL, "pulse_qnet_train_step: an earlier reduce + AdamW launch could not gather its workgroups within its wait "
-                                                "(another process or stream holds the GPU's compute units?) and applied NO update (report[3] = -1); "
-                                                "set PulseQNetTrain.separate_apply to run AdamW as a launch of its own");
-        }
-    }
-    if (grads && n_rows > 0) {
-        TrainArgs a{};
-        a.net = FlatNet{t->params, n.state_dim, n.n_actions}; a.tgt = FlatNet{t->target_params, n.state_dim, n.n_actions}; a.partials = t->partials; a.scal = t->stats; a.n_params = np; a.states = states; a.stride = row_stride;
-        a.actions = actions; a.rewards = rewards; a.next_states = next_states; a.next_stride = next_stride; a.dones = dones;
-        a.n_rows = n_rows; a.seed = seed; a.step = step_counter; a.table_id0 = table_id0;
-        a.gamma = t->gamma; a.drop_p = t->dropout_p;
-        // select_scratch (int32 words), nw = ceil(n_rows / 256): [0, 256 nw) row lists; [256 nw, 258 nw) window counts (256-row
-        // windows from the select launch, 128-row windows from pulse_qnet_act_select); [258 nw, 259 nw) window reward sums;
-        // [259 nw, +512) the fused reduce launch's meeting words
-        const int nw = (n_rows + 255) / 256;
-        if (!t->select_scratch || t->select_words < (int64_t)nw * 259 + 512)
-            return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: select_scratch must hold 259 words per 256 rows + 512");
-        int32_t* sel_rows = t->select_scratch; int32_t* sel_counts = t->select_scratch + (size_t)nw * 256;
-        float* win_reward = reinterpret_cast<float*>(t->select_scratch + (size_t)nw * 258);
-        a.sel_rows = sel_rows; a.sel_counts = sel_counts;
-        a.meet = reinterpret_cast<unsigned*>(t->select_scratch + (size_t)nw * 259);
-        int n_windows = 0;                                         // (windows with a reward sum: the select launch's)
-        if (t->select_from_act) {                                  // the lists are pulse_qnet_act_select's, on this observation
-            a.win_shift = 7; a.book = 1; a.row_mask = row_mask; a.terminated = terminated;
-        } else {
-            a.win_shift = 8; a.book = 0;
-            n_windows = nw;
-            SelectArgs sa{};
-            sa.states = states; sa.stride = row_stride; sa.rewards = rewards; sa.dones = dones; sa.row_mask = row_mask; sa.terminated = terminated;
-            sa.n_rows = n_rows; sa.sel_rows = sel_rows; sa.sel_counts = sel_counts; sa.win_reward = win_reward;
-            hipLaunchKernelGGL(qnet_select_kernel, dim3((unsigned)nw), dim3(256), 0, st, sa);
-        }
-        const bool vec = n.state_dim % 8 == 0 && row_stride % 4 == 0 && next_stride % 4 == 0 && aligned16(states) && aligned16(next_states);
-        // instances: layer-1 steps 5 (16-byte rows of <= 40 inputs) or 8; four or eight wavefronts per tile; stability totals or not
-        static const bool four = [] { const char* e = getenv("PULSE_TRAIN_WAVES"); return e && e[0] == '4'; }();
-        const void* fns[12] = {reinterpret_cast<const void*>(&qnet_train_kernel<false, 8, false>), reinterpret_cast<const void*>(&qnet_train_kernel<true, 8, false>),
-                               reinterpret_cast<const void*>(&qnet_train_kernel<true, 5, false>), reinterpret_cast<const void*>(&qnet_train8_kernel<false, 8, false>),
-                               reinterpret_cast<const void*>(&qnet_train8_kernel<true, 8, false>), reinterpret_cast<const void*>(&qnet_train8_kernel<true, 5, false>),
-                               reinterpret_cast<const void*>(&qnet_train_kernel<false, 8, true>), reinterpret_cast<const void*>(&qnet_train_kernel<true, 8, true>),
-                               reinterpret_cast<const void*>(&qnet_train_kernel<true, 5, true>), reinterpret_cast<const void*>(&qnet_train8_kernel<false, 8, true>),
-                               reinterpret_cast<const void*>(&qnet_train8_kernel<true, 8, true>), reinterpret_cast<const void*>(&qnet_train8_kernel<true, 5, true>)};
-        const int slot = (vec ? (n.state_dim <= 40 ? 2 : 1) : 0) + (four ? 0 : 3) + (t->stability ? 6 : 0);
-        static const void* attr_set[12] = {};
-        if (attr_set[slot] != fns[slot]) {
-            const hipError_t e = hipFuncSetAttribute(fns[slot], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kTrainLdsBytes);
-            if (e != hipSuccess) return pulse::fail_hip((int)e, "pulse_qnet_train_step: LDS size attribute");
-            attr_set[slot] = fns[slot];
-        }
-        // persistent workgroups (157 KB of LDS: one per CU), one per possible tile of 32 rows at most
-        const int grid = std::min((n_rows + 31) / 32, (int)t->max_blocks);
-        void* params[1] = {&a};
-        const hipError_t le = hipLaunchKernel(fns[slot], dim3((unsigned)grid), dim3(four ? 256 : 512), params, kTrainLdsBytes, st);
-        if (le != hipSuccess) return pulse::fail_hip((int)le, "pulse_qnet_train_step launch");
-    ReduceArgs r{};
-    r.partials = t->partials; r.n_blocks = grid; r.n_params = np; r.state_dim = n.state_dim; r.n_actions = n.n_actions;
-    r.grad = t->grad; r.scal = t->stats;
-    r.step = apply ? (long long*)t->step : nullptr;        // gradients only: the caller advances the step after its all-reduce
-    r.reward_sum = reward_sum; r.win_reward = win_reward; r.n_windows = n_windows; r.meet = a.meet;
-    AdamArgs b = adam_args(t, np);
-    const unsigned rg = (unsigned)((kSliceStats + 127) / 128);
-    // one GPU: AdamW rides in the reduce launch -- where the whole grid fits the device at once
-    fused = apply && !t->separate_apply && fused_apply_fits(rg);
-    r.wait_ticks = t->meet_wait_ticks > 0 ? (long long)t->meet_wait_ticks : 500000000ll;     // 5 s of the 100 MHz clock
-    r.extra_arrivals = t->debug_meet_extra > 0 ? (unsigned)t->debug_meet_extra : 0u;
-    r.gave_up = g_meet_gave_up;
-    r.stab = t->stability;
-    if (fused) hipLaunchKernelGGL(qnet_grad_reduce_kernel<true>, dim3(rg), dim3(256), 0, st, r, b);
-    else hipLaunchKernelGGL(qnet_grad_reduce_kernel<false>, dim3(rg), dim3(256), 0, st, r, b);
-    }
-    if (apply && !fused && (n_rows > 0 || !grads)) {
-        const AdamArgs b = adam_args(t, np);
-        hipLaunchKernelGGL(qnet_adamw_kernel, dim3(eg), dim3(256), 0, st, b);
-    }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : pulse::fail_hip((int)e, "pulse_qnet_train_step launch");
-}
-}  // namespace
 
 int pulse_qnet_train_step(const PulseQNetTrain* t, const float* states, int64_t row_stride, const int64_t* actions,
                           const float* rewards, const float* next_states, int64_t next_stride, const uint8_t* dones,
                           const uint8_t* row_mask, int32_t n_rows, uint64_t seed, uint64_t step_counter, uint64_t table_id0,
                           uint8_t* terminated, double* reward_sum, void* stream) {
-    return train_launches(t, states, row_stride, actions, rewards, next_states, next_stride, dones, row_mask, n_rows, seed, step_counter,
-                          table_id0, terminated, reward_sum, true, true, stream);
+    const TrainBatch b{states, row_stride, actions, rewards, next_states, next_stride, dones, row_mask, n_rows, seed, step_counter, table_id0, terminated, reward_sum};
+    if (const int err = train_validate(t, &b)) return err;
+    if (n_rows == 0) return 0;                                     // (the reference returns before the optimizer, Player.py:262)
+    bool fused = false;
+    if (const int err = train_grads(t, b, true, &fused, (hipStream_t)stream)) return err;
+    return fused ? 0 : train_adamw(t, (hipStream_t)stream);
 }
 
 int pulse_qnet_train_grads(const PulseQNetTrain* t, const float* states, int64_t row_stride, const int64_t* actions,
                            const float* rewards, const float* next_states, int64_t next_stride, const uint8_t* dones,
                            const uint8_t* row_mask, int32_t n_rows, uint64_t seed, uint64_t step_counter, uint64_t table_id0,
                            uint8_t* terminated, double* reward_sum, void* stream) {
-    return train_launches(t, states, row_stride, actions, rewards, next_states, next_stride, dones, row_mask, n_rows, seed, step_counter,
-                          table_id0, terminated, reward_sum, true, false, stream);
+    const TrainBatch b{states, row_stride, actions, rewards, next_states, next_stride, dones, row_mask, n_rows, seed, step_counter, table_id0, terminated, reward_sum};
+    if (const int err = train_validate(t, &b)) return err;
+    bool fused = false;
+    return n_rows == 0 ? 0 : train_grads(t, b, false, &fused, (hipStream_t)stream);
 }
 
 int pulse_qnet_train_apply(const PulseQNetTrain* t, void* stream) {
-    static const float dummy_f = 0.0f; static const int64_t dummy_a = 0; static const uint8_t dummy_d = 0;
-    return train_launches(t, &dummy_f, 64, &dummy_a, &dummy_f, &dummy_f, 64, &dummy_d, nullptr, 0, 0, 0, 0, nullptr, nullptr, false, true, stream);
+    if (const int err = train_validate(t, nullptr)) return err;
+    return train_adamw(t, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -360,20 +360,30 @@ __device__ __forceinline__ f32x16 mfma_w(const float (&wa)[NK8][4], int c, int h
 // the critical path).
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// The network's shape, once (host and device): layer l is n_out x n_in; in the flat buffer w1,b1,...,w5,b5 its W starts at
+// w[l] and its b at b[l] (`count` parameters in all); in a training workgroup's gradient slice (qnet_train_device.h) dW_l is
+// the 32x32 blocks [blk[l], blk[l + 1]), row tile by row tile of `col_tiles[l]` blocks (padded rows / columns included:
+// n_actions <= 32, state_dim <= 64), and db_l the words [bias[l], bias[l + 1]) behind the blocks.
+struct NetShape { int n_out[5], n_in[5], w[5], b[5], count, col_tiles[5], blk[6], bias[6]; };
+__host__ __device__ __forceinline__ constexpr NetShape net_shape(int K1, int A) {
+    NetShape s{{128, 128, 64, 32, A}, {K1, 128, 128, 64, 32}, {}, {}, 0, {2, 4, 4, 2, 1}, {}, {}};
+#pragma unroll
+    for (int l = 0; l < 5; ++l) {
+        s.w[l] = s.count; s.count += s.n_out[l] * s.n_in[l];
+        s.b[l] = s.count; s.count += s.n_out[l];
+        const int row_tiles = l == 4 ? 1 : s.n_out[l] / 32;
+        s.blk[l + 1] = s.blk[l] + row_tiles * s.col_tiles[l];
+        s.bias[l + 1] = s.bias[l] + 32 * row_tiles;
+    }
+    return s;
+}
+
 // A network as the training kernels see it: ONE base pointer into the flat w1,b1,...,w5,b5 buffer (pulse_env.h:
 // PulseQNetTrain -- the host checks that the ten tensors are those views).  Twenty pointers per network in scalar registers
 // were most of the 200 scalar spills of these kernels (a v_readlane per use).
 struct FlatNet { const float* base; int32_t state_dim, n_actions; };
-__device__ __forceinline__ int layer_base(int layer, int K1) {
-    const int base[5] = {0, 128 * K1 + 128, 128 * K1 + 128 + 128 * 128 + 128, 128 * K1 + 128 + 128 * 128 + 128 + 64 * 128 + 64,
-                         128 * K1 + 128 + 128 * 128 + 128 + 64 * 128 + 64 + 32 * 64 + 32};
-    return base[layer];
-}
-__device__ __forceinline__ const float* net_w(const FlatNet& n, int layer) { return n.base + layer_base(layer, n.state_dim); }
-__device__ __forceinline__ const float* net_b(const FlatNet& n, int layer) {
-    const int nw[5] = {128 * n.state_dim, 128 * 128, 64 * 128, 32 * 64, 32 * n.n_actions};
-    return n.base + layer_base(layer, n.state_dim) + nw[layer];
-}
+__device__ __forceinline__ const float* net_w(const FlatNet& n, int layer) { return n.base + net_shape(n.state_dim, n.n_actions).w[layer]; }
+__device__ __forceinline__ const float* net_b(const FlatNet& n, int layer) { return n.base + net_shape(n.state_dim, n.n_actions).b[layer]; }
 __device__ __forceinline__ const float* net_w(const PulseQNet& n, int layer) {
     return layer == 0 ? n.w1 : layer == 1 ? n.w2 : layer == 2 ? n.w3 : layer == 3 ? n.w4 : n.w5;
 }
@@ -387,45 +397,31 @@ __device__ __forceinline__ const float* net_b(const PulseQNet& n, int layer) {
 // the weights arrive)
 template <bool VEC, int NK8, class Net>
 __device__ __forceinline__ void load_layer(float (&wa)[NK8][4], const Net& n, int layer, int out_row, int h, int k0, int k1) {
-    const int n_in = layer == 0 ? n.state_dim : layer == 1 ? 128 : layer == 2 ? 128 : layer == 3 ? 64 : 32;
-    load_w<VEC, NK8>(wa, net_w(n, layer), n_in, out_row, h, k0, k1);
+    load_w<VEC, NK8>(wa, net_w(n, layer), net_shape(n.state_dim, n.n_actions).n_in[layer], out_row, h, k0, k1);
 }
 
-// hidden layer epilogue: z = acc + bias -> a = gelu(z) * m to As; TRAIN also g = gelu'(z) * m to Gs (m = dropout keep * scale)
 // the 16 biases of this lane's accumulator rows (units unit0 + rho(r) + 4h); `bias` global or LDS
 __device__ __forceinline__ void load_bias16(float (&bz)[16], const float* __restrict__ bias, int unit0, int h) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) bz[r] = bias[unit0 + rho(r) + 4 * h];
 }
 
-template <bool TRAIN>
-__device__ __forceinline__ void coop_epilogue(const f32x16& acc, const float (&bz)[16], int unit0, int c, int h, uint32_t keep,
-                                              float scale, float* __restrict__ As, float* __restrict__ Gs) {
+// hidden layer epilogue: z = v + bias -> a = gelu(z) * m to As; TRAIN also g = gelu'(z) * m to Gs (m = dropout keep * scale).
+// NR values `v` (an accumulator tile, or the registers of one that a wavefront finishes) standing for units unit0 + rho(r) + 4h;
+// no dropout: keep = 0xFFFF, scale = 1
+template <bool TRAIN, int NR, class V>
+__device__ __forceinline__ void coop_epilogue(const V& v, const float (&bz)[NR], int unit0, int c, int h, uint32_t keep, float scale,
+                                              float* __restrict__ As, float* __restrict__ Gs) {
 #pragma unroll
-    for (int r = 0; r < 16; r += 2) {                             // registers r, r + 1 are units u, u + 1
+    for (int r = 0; r < NR; r += 2) {                             // values r, r + 1 are units u, u + 1
         const int u = unit0 + rho(r) + 4 * h;
-        const f32x2 z = {acc[r] + bz[r], acc[r + 1] + bz[r + 1]};
+        const f32x2 z = {v[r] + bz[r], v[r + 1] + bz[r + 1]};
         const f32x2 m = {((keep >> r) & 1u) ? scale : 0.0f, ((keep >> (r + 1)) & 1u) ? scale : 0.0f};
         f32x2 y, dy;
         if (PULSE_QABL & 2) { y = z; dy = z; } else gelu_pair2(z, y, dy);
         y = y * m;
         As[u * kLd + c] = y.x; As[(u + 1) * kLd + c] = y.y;
         if (TRAIN) { dy = dy * m; Gs[u * kLd + c] = dy.x; Gs[(u + 1) * kLd + c] = dy.y; }
-    }
-}
-
-// the same for accumulator registers 0..7 of `acc` standing for units unit0 + rho(i) + 4h (no dropout)
-template <bool TRAIN>
-__device__ __forceinline__ void coop_epilogue8(const f32x16& acc, const float (&bz)[8], int unit0, int c, int h, float* __restrict__ As,
-                                               float* __restrict__ Gs) {
-#pragma unroll
-    for (int r = 0; r < 8; r += 2) {
-        const int u = unit0 + rho(r) + 4 * h;
-        const f32x2 z = {acc[r] + bz[r], acc[r + 1] + bz[r + 1]};
-        f32x2 y, dy;
-        if (PULSE_QABL & 2) { y = z; dy = z; } else gelu_pair2(z, y, dy);
-        As[u * kLd + c] = y.x; As[(u + 1) * kLd + c] = y.y;
-        if (TRAIN) { Gs[u * kLd + c] = dy.x; Gs[(u + 1) * kLd + c] = dy.y; }
     }
 }
 
@@ -484,8 +480,8 @@ __device__ __forceinline__ void coop_forward_pair(const float (&w1t)[NK1][4], co
         const f32x16 ac = mfma_w<NK1>(w1c, c, h, Xs, 0);
         load_layer<true, 16>(w2t, nt, 1, 32 * wv + c, h, 0, 128);
         load_layer<true, 16>(w2c, n, 1, 32 * wv + c, h, 0, 128);
-        coop_epilogue<false>(at, bt, 32 * wv, c, h, 0xFFFFu, 1.0f, T1, nullptr);
-        coop_epilogue<true>(ac, bo, 32 * wv, c, h, 0xFFFFu, 1.0f, A1, G1);
+        coop_epilogue<false, 16>(at, bt, 32 * wv, c, h, 0xFFFFu, 1.0f, T1, nullptr);
+        coop_epilogue<true, 16>(ac, bo, 32 * wv, c, h, 0xFFFFu, 1.0f, A1, G1);
     }
     lds_barrier();
     float w3t[8][4], w3c[8][4];
@@ -496,8 +492,8 @@ __device__ __forceinline__ void coop_forward_pair(const float (&w1t)[NK1][4], co
         const f32x16 ac = mfma_w<16>(w2c, c, h, A1, 0);
         load_layer<true, 8>(w3t, nt, 2, 32 * ot + c, h, 64 * half, 64 * half + 64);
         load_layer<true, 8>(w3c, n, 2, 32 * ot + c, h, 64 * half, 64 * half + 64);
-        coop_epilogue<false>(at, bt, 32 * wv, c, h, 0xFFFFu, 1.0f, T2, nullptr);
-        coop_epilogue<true>(ac, bo, 32 * wv, c, h, dropout_keep_bits(seed, gid, step, wv, h, thr), scale, A2, G2);
+        coop_epilogue<false, 16>(at, bt, 32 * wv, c, h, 0xFFFFu, 1.0f, T2, nullptr);
+        coop_epilogue<true, 16>(ac, bo, 32 * wv, c, h, dropout_keep_bits(seed, gid, step, wv, h, thr), scale, A2, G2);
     }
     lds_barrier();
     float w4t[2][4], w4c[2][4];
@@ -520,11 +516,11 @@ __device__ __forceinline__ void coop_forward_pair(const float (&w1t)[NK1][4], co
         if (half == 0) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) at[r] += P[(ot * 16 + r) * 64 + lane];
-            coop_epilogue<false>(at, bz, 32 * ot, c, h, 0xFFFFu, 1.0f, T3, nullptr);
+            coop_epilogue<false, 16>(at, bz, 32 * ot, c, h, 0xFFFFu, 1.0f, T3, nullptr);
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) ac[r] = P2[(ot * 16 + r) * 64 + lane] + ac[r];
-            coop_epilogue<true>(ac, bz, 32 * ot, c, h, dropout_keep_bits(seed, gid, step, 4 + ot, h, thr), scale, A3, G3);
+            coop_epilogue<true, 16>(ac, bz, 32 * ot, c, h, dropout_keep_bits(seed, gid, step, 4 + ot, h, thr), scale, A3, G3);
         }
     }
     lds_barrier();
@@ -548,14 +544,14 @@ __device__ __forceinline__ void coop_forward_pair(const float (&w1t)[NK1][4], co
             }
         }
         lds_barrier();
-        f32x16 fin = zero16();                                     // registers 0..7: this wavefront's group
+        float fin[8];                                              // this wavefront's group
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const float own = own_net ? (rb ? ac[8 + i] : ac[i]) : (rb ? at[8 + i] : at[i]);
             fin[i] = own + ((P[((wv * 3 + 0) * 8 + i) * 64 + lane] + P[((wv * 3 + 1) * 8 + i) * 64 + lane]) + P[((wv * 3 + 2) * 8 + i) * 64 + lane]);
         }
-        if (own_net) coop_epilogue8<true>(fin, bz8, 2 * rb, c, h, A4, G4);
-        else coop_epilogue8<false>(fin, bz8, 2 * rb, c, h, T4, nullptr);
+        if (own_net) coop_epilogue<true, 8>(fin, bz8, 2 * rb, c, h, 0xFFFFu, 1.0f, A4, G4);
+        else coop_epilogue<false, 8>(fin, bz8, 2 * rb, c, h, 0xFFFFu, 1.0f, T4, nullptr);
     }
     lds_barrier();
     q_tgt = zero16(); q = zero16();
@@ -564,22 +560,6 @@ __device__ __forceinline__ void coop_forward_pair(const float (&w1t)[NK1][4], co
         bias_act<false>(q_tgt, net_b(nt, 4), 0, n.n_actions, h);
         q = mfma_w<4>(w5c, c, h, A4, 0);
         bias_act<false>(q, net_b(n, 4), 0, n.n_actions, h);
-    }
-}
-
-template <bool TRAIN, int NR>
-__device__ __forceinline__ void coop_epilogue_n(const float (&v)[NR], const float (&bz)[NR], int unit0, int c, int h, uint32_t keep, float scale,
-                                                float* __restrict__ As, float* __restrict__ Gs) {
-#pragma unroll
-    for (int r = 0; r < NR; r += 2) {                             // values r, r + 1 are units u, u + 1 (rho(i) = i below 4)
-        const int u = unit0 + rho(r) + 4 * h;
-        const f32x2 z = {v[r] + bz[r], v[r + 1] + bz[r + 1]};
-        const f32x2 m = {((keep >> r) & 1u) ? scale : 0.0f, ((keep >> (r + 1)) & 1u) ? scale : 0.0f};
-        f32x2 y, dy;
-        if (PULSE_QABL & 2) { y = z; dy = z; } else gelu_pair2(z, y, dy);
-        y = y * m;
-        As[u * kLd + c] = y.x; As[(u + 1) * kLd + c] = y.y;
-        if (TRAIN) { dy = dy * m; Gs[u * kLd + c] = dy.x; Gs[(u + 1) * kLd + c] = dy.y; }
     }
 }
 
@@ -599,7 +579,7 @@ __device__ __forceinline__ f32x16 group_forward(const float (&w1r)[NK1][4], cons
         load_bias16(bz, net_b(n, 0), 32 * wq, h);
         const f32x16 acc = mfma_w<NK1>(w1r, c, h, X, 0);
         load_layer<true, 16>(w2r, n, 1, 32 * wq + c, h, 0, 128);
-        coop_epilogue<TRAIN>(acc, bz, 32 * wq, c, h, 0xFFFFu, 1.0f, B1, G1);
+        coop_epilogue<TRAIN, 16>(acc, bz, 32 * wq, c, h, 0xFFFFu, 1.0f, B1, G1);
     }
     lds_barrier();
     float w3r[8][4];
@@ -608,7 +588,7 @@ __device__ __forceinline__ f32x16 group_forward(const float (&w1r)[NK1][4], cons
         load_bias16(bz, net_b(n, 1), 32 * wq, h);
         const f32x16 acc = mfma_w<16>(w2r, c, h, B1, 0);
         load_layer<true, 8>(w3r, n, 2, 32 * ot + c, h, 64 * half, 64 * half + 64);
-        coop_epilogue<TRAIN>(acc, bz, 32 * wq, c, h, TRAIN ? dropout_keep_bits(seed, gid, step, wq, h, thr) : 0xFFFFu, TRAIN ? scale : 1.0f, B2, G2);
+        coop_epilogue<TRAIN, 16>(acc, bz, 32 * wq, c, h, TRAIN ? dropout_keep_bits(seed, gid, step, wq, h, thr) : 0xFFFFu, TRAIN ? scale : 1.0f, B2, G2);
     }
     lds_barrier();
     float w4r[2][4];
@@ -624,7 +604,7 @@ __device__ __forceinline__ f32x16 group_forward(const float (&w1r)[NK1][4], cons
 #pragma unroll
         for (int i = 0; i < 8; ++i) own[i] = (half ? acc[8 + i] : acc[i]) + P[((ot * 2 + half) * 8 + i) * 64 + lane];
         const uint32_t keep = TRAIN ? (dropout_keep_bits(seed, gid, step, 4 + ot, h, thr) >> (8 * half)) : 0xFFFFu;
-        coop_epilogue_n<TRAIN, 8>(own, bz8, 32 * ot + 16 * half, c, h, keep, TRAIN ? scale : 1.0f, B3, G3);
+        coop_epilogue<TRAIN, 8>(own, bz8, 32 * ot + 16 * half, c, h, keep, TRAIN ? scale : 1.0f, B3, G3);
     }
     lds_barrier();
     float w5r[4][4];
@@ -648,7 +628,7 @@ __device__ __forceinline__ f32x16 group_forward(const float (&w1r)[NK1][4], cons
             const float mine = wq == 0 ? acc[i] : wq == 1 ? acc[4 + i] : wq == 2 ? acc[8 + i] : acc[12 + i];
             own[i] = mine + ((P[((wq * 3 + 0) * 4 + i) * 64 + lane] + P[((wq * 3 + 1) * 4 + i) * 64 + lane]) + P[((wq * 3 + 2) * 4 + i) * 64 + lane]);
         }
-        coop_epilogue_n<TRAIN, 4>(own, bz4, 8 * wq, c, h, 0xFFFFu, 1.0f, B4, G4);
+        coop_epilogue<TRAIN, 4>(own, bz4, 8 * wq, c, h, 0xFFFFu, 1.0f, B4, G4);
     }
     lds_barrier();
     f32x16 qv = zero16();
