@@ -23,6 +23,24 @@ int fail_hip(int hip_error, const char* what) {
     return (e == hipErrorNoDevice || e == hipErrorInvalidDevice || e == hipErrorNotInitialized) ? PULSE_ENODEVICE : PULSE_ELAUNCH;
 }
 
+LdsLaunch launch_lds(const void* fn, unsigned grid, unsigned block, void** params, size_t lds_bytes, ihipStream_t* stream, bool launch_if_refused) {
+    hipError_t attr = hipSuccess;
+    if (lds_bytes > 48 * 1024) {
+        // Assumes what the three tables this one replaces assumed: one launching thread (no lock) and one device per process
+        // (the limit is a property of the function on a device; the table is keyed by function alone).
+        static struct { const void* fn; size_t bytes; } raised[64] = {};     // (the library has some thirty such kernel instances)
+        int i = 0;
+        while (i < 64 && raised[i].fn && raised[i].fn != fn) ++i;
+        if (i == 64 || raised[i].bytes < lds_bytes) {
+            attr = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            if (attr == hipSuccess && i < 64) { raised[i].fn = fn; raised[i].bytes = lds_bytes; }
+        }
+    }
+    if (attr != hipSuccess && !launch_if_refused) return {(int)attr, (int)hipSuccess};
+    if (attr != hipSuccess) (void)hipGetLastError();      // the launch below reports what is wrong, not the attribute call's sticky error
+    return {(int)attr, (int)hipLaunchKernel(fn, dim3(grid), dim3(block), params, lds_bytes, stream)};
+}
+
 }  // namespace pulse
 
 extern "C" {

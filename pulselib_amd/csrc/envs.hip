@@ -14,6 +14,7 @@
 
 #include <mutex>
 
+#include "poker_device.h"
 #include "pulse_internal.h"
 #include "tfe_device.h"
 
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void tfe_step4_kernel(int32_t* __restrict__
             mine[64 * j + lane] = (uint16_t)row;
         }
         fast = !__any(bad != 0u);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        pulse_dev::wave_sync();
         if (fast) {
             const uint2 w = *reinterpret_cast<const uint2*>(mine + 4 * lane);           // (a wavefront's LDS operations retire in order)
             pb.lo = w.x; pb.hi = w.y;
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(kBlock) void tfe_step4_kernel(int32_t* __restrict__
         const int empty_before = tfe_spawn_packed(pb, rnd.x, rnd.y);                   // TFE.py:182 (always)
         const bool over = tfe_over_packed(pb, empty_before);                           // TFE.py:48-67
         *reinterpret_cast<uint2*>(mine + 4 * lane) = make_uint2(pb.lo, pb.hi);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        pulse_dev::wave_sync();
         total_score[g] = ts + score;                                                    // TFE.py:168
         rewards[g] = score > 0 ? 31 - __clz(score) : 0;                                 // TFE.py:185-187
         dones[g] = over;

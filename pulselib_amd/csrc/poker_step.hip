@@ -18,12 +18,16 @@
 // n single launches leave behind), and the changed state words are written once at the end.  The 130 MB hand-rank
 // table is only touched when a poked state misses the evaluation cache the reset kernel fills.
 #include <algorithm>
+#include <cstddef>
 #include <type_traits>
 
 #include "poker_device.h"
+#include "poker_launch.h"
 #include "qnet_device.h"
 
 using namespace pulse_dev;
+using pulse::ChunkArgs;
+using pulse::PolicyArgs;
 
 namespace {
 
@@ -42,31 +46,18 @@ constexpr int kStepBlock = PULSE_STEP_BLOCK;
 // a word with the rank: 5 instead of 7 dwords per seat, which is what lets three two-lane wavefronts per SIMD fit the LDS at large batches.
 __host__ __device__ constexpr int chunk_lds_dwords(int obs_size, int seats, int tables, bool slim) { return (tables * (obs_size + seats * (slim ? 5 : 7) + 8) + 3) & ~3; }
 
-struct PolicyArgs {
-    uint64_t types_packed, seed, step_counter, table_id0;
-    uint32_t* wave_done;                   // nullptr, or one word per wavefront of the launch: tables done after the last step
-    // the PREVIOUS check point's wavefront counts, summed and published to the host by workgroup 0 of this launch, before its own tables
-    const uint32_t* carry_partials; int carry_n; long long* carry_host; long long carry_seq;
-    // paired launches (pulse_internal.h: StopRulePair): a second carried check point, the counts after the launch's first
-    // chunk, and the verdict word {launch id << 8 | skip_all | stop_mid << 1 | error << 7} the host answers the carries with
-    const uint32_t* carry2_partials; int carry2_n; long long* carry2_host; long long carry2_seq;
-    uint32_t* wave_done_mid; int mid_step;
-    const long long* verdict_host; long long* verdict_dev; long long verdict_id;
-    long long* verdict_err;                // pinned: set by a launch that gave up waiting for its verdict (the host then runs its steps unpaired)
-    long long verdict_ticks;               // ticks of the 100 MHz wall clock thread 0 waits for the word: a launch never waits for a dead host for ever
-};
 constexpr int kVerdictStride = 16;                          // long longs between the 64 copies of a relayed verdict word (one 128-byte line each)
-struct ChunkArgs {                         // MULTI only: the odd steps' output buffers and the number of steps
-    float* obs_odd;
-    float* rewards_odd;
-    int n_steps;
-};
 
 // The kernel-argument segment as the kernel below receives it.  Values needed once inside (or after) the long step loop
 // are re-read from it through a constant-address-space pointer (scalar loads) instead of being kept in scalar
 // registers across the loop, where they were spilled to vector lanes.
 struct StepKernargs { PulsePokerView v; int64_t* actions; const int32_t* actor_idx_in; float* rewards; PolicyArgs pa; ChunkArgs ca; };
 typedef const __attribute__((address_space(4))) StepKernargs* StepKernargsPtr;
+static_assert(offsetof(StepKernargs, v) == 0 && offsetof(StepKernargs, actions) == sizeof(PulsePokerView), "the view is the first kernel argument");
+static_assert(offsetof(StepKernargs, pa) == sizeof(PulsePokerView) + 24 && offsetof(StepKernargs, ca) == offsetof(StepKernargs, pa) + sizeof(PolicyArgs), "kernel arguments");
+// (PolicyArgs' two carried check points are pulse::StopRuleCarry records: the same words, in the same places, as when they were eight loose fields)
+static_assert(sizeof(pulse::StopRuleCarry) == 32 && offsetof(PolicyArgs, wave_done) == 32 && offsetof(PolicyArgs, carry) == 40 &&
+              offsetof(PolicyArgs, wave_done_mid) == 104 && offsetof(PolicyArgs, verdict_host) == 120 && sizeof(PolicyArgs) == 160, "PolicyArgs layout");
 
 // In-kernel timeline (diagnostic build only, -DPULSE_STAMPS=1 -> libpulse_hip_stamps.so; no stamp executes
 // in the product): lane 0 of every wavefront stores s_memtime at phase boundaries into a buffer of its own.
@@ -141,13 +132,13 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
     static_assert(!MULTI || (POLICY && PH == PULSE_PH_STEP), "a chunk is fused policy + full step");
     static_assert(!ACT || (MULTI == 1 && LPT == 2), "the act + step launch is a one-step chunk at two lanes per table");
     extern __shared__ int4 smem4[];
-    if (POLICY && pa.carry_n > 0 && blockIdx.x == 0) {
+    if (POLICY && pa.carry[0].n > 0 && blockIdx.x == 0) {
         // The stop rule's previous check point: workgroup 0 sums its per-wavefront counts and publishes the total to
         // the host BEFORE its own tables.  (A separate last workgroup did this in the first version; at 65,536 tables
         // the grid fills the chip exactly, so that workgroup only got a slot when the first one retired and the host
         // learned the count ~35 us later than it could -- too late to keep the queue fed at an episode boundary.)
-        sum_and_publish<BLK>(pa.carry_partials, pa.carry_n, nullptr, pa.carry_host, pa.carry_seq);
-        if (pa.carry2_n > 0) { __syncthreads(); sum_and_publish<BLK>(pa.carry2_partials, pa.carry2_n, nullptr, pa.carry2_host, pa.carry2_seq); }
+        sum_and_publish<BLK>(pa.carry[0].partials, pa.carry[0].n, nullptr, pa.carry[0].host, pa.carry[0].seq);
+        if (pa.carry[1].n > 0) { __syncthreads(); sum_and_publish<BLK>(pa.carry[1].partials, pa.carry[1].n, nullptr, pa.carry[1].host, pa.carry[1].seq); }
     }
     if (ACT) {
         // the learner's actions of this workgroup's 128 tables first (the act window owns the workgroup's whole LDS block; the
@@ -158,8 +149,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
     }
     const int gt = blockIdx.x * BLK + threadIdx.x;
     const int t = gt / LPT;
-    const int j_lane = gt % LPT;
-    const int j = j_lane;
+    const int j = gt % LPT;
     if (!ACT && t >= v.n_games) return;   // the lanes of a table leave together (ACT: the host launches whole windows only -- every thread meets the barriers)
     STAMP(0);
     const int P = v.n_players, A = v.active_players;
@@ -260,7 +250,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
         for (int k = 0; k < SPL; ++k) {
             const int seat = SEAT(k);
             *reinterpret_cast<int2*>(l_hands + (q * P_ + seat) * 2) = make_int2(h0[k], h1[k]);
-            seat_hit[k] = ((uint32_t)ph_[k] & (kPreHandsValid * 2u - 1u)) == pack_hand(h0[k], h1[k]) && card_ok(h0[k]) && card_ok(h1[k]);   // hole cards are fixed for the episode
+            seat_hit[k] = PULSE_CACHE_HIT((uint32_t)ph_[k], h0[k], h1[k]);   // hole cards are fixed for the episode
             uint32_t cls = (uint32_t)ph_[k] >> kClsShift;                    // the reset kernel classified the cards the tag names
             if (POLICY && !seat_hit[k]) {          // seats outside the hand hold (-1, -1): a constant; anything else (no cache, poked cards) is classified here
                 const bool empty = h0[k] == -1 && h1[k] == -1;
@@ -278,9 +268,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
             const int at = dpos0 + DPL * j + e;
             l_deck[q * 8 + DPL * j + e] = (uint32_t)at < 52u ? dk[at] : 0;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
     }
     // Paired launch: the host answers the carried counts with this launch's verdict word; thread 0 of the launch relays
     // it from pinned memory into device memory (one poller on PCIe), everybody reads it there before the first step --
@@ -345,9 +333,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 #pragma unroll
             for (int e = 0; e < DPL; ++e) l_deck[q * 8 + DPL * j + e] = c[e];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
         }
         return l_deck[q * 8 + (at - dwin0)];
     };
@@ -403,7 +389,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
         // In a chunk, everything derived from the lane's position in its table (seat numbers, `seat < A` masks, ...)
         // is re-derived inside the step: hoisted out of the loop those lane masks filled the scalar registers and were
         // spilled (~200 v_readlane per step to fetch them back); a compare is cheaper than its reload.
-        int j = j_lane;
+        int j = gt % LPT;
         if (MULTI) asm volatile("" : "+v"(j));
 
         // ---- capture (PokerGPU.py:530-539)
@@ -467,7 +453,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                             } else {
                                 const uint32_t ph = (uint32_t)ldo(v.pre_hands, ROW_OFF(k));
                                 const float pe = ldo(v.pre_eq, (__umul24(ut, 3u * (uint32_t)P) + __umul24((uint32_t)(stage - 1), (uint32_t)P) + (uint32_t)seat) * 4u);
-                                hit = (ph & (kPreHandsValid * 2u - 1u)) == pack_hand(h0[k], h1[k]) && card_ok(h0[k]) && card_ok(h1[k]);
+                                hit = PULSE_CACHE_HIT(ph, h0[k], h1[k]);
                                 e = pe;
                             }
                         }
@@ -614,7 +600,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                                 rank[k] = SLIM ? l_prerank[q * P_ + seat] & 0xFFFF : l_prerank[q * P_ + seat];
                             } else {
                                 const uint32_t ph = (uint32_t)ldo(v.pre_hands, ROW_OFF(k));
-                                hit = (ph & (kPreHandsValid * 2u - 1u)) == pack_hand(h0[k], h1[k]) && card_ok(h0[k]) && card_ok(h1[k]);
+                                hit = PULSE_CACHE_HIT(ph, h0[k], h1[k]);
                                 rank[k] = ldo(v.pre_rank, ROW_OFF(k));
                             }
                         }
@@ -724,9 +710,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                 }
             }
             if (WOBS) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_sync();
                 const int n4 = TPW / 4 * v.obs_size;                             // int4 per wavefront block
                 const int tw0 = (int)((blockIdx.x * BLK + threadIdx.x) >> 6) * TPW;  // first table of this wavefront
                 const uint32_t blk0 = __umul24((uint32_t)tw0, (uint32_t)v.obs_size) * 4u;      // byte offset of the wavefront's block
@@ -743,16 +727,9 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                 } else
                     for (int e = wlane; e < n4; e += 64) sto_in_loop(reinterpret_cast<int4*>(obs_dst), blk0 + (uint32_t)e * 16u, src[e]);
                 if (MULTI) {       // the next step's values must not overtake these reads of the slice
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_sync();
                 }
             }
-        } else if (MULTI) {
-            // (not reachable: a chunk always has PULSE_PH_OBS) keep the carried actor consistent anyway
-            const int seat_i = idx & 15;
-            a_status = SEAT_PICK(status, seat_i); a_stack = SEAT_PICK(stack, seat_i); a_bet = SEAT_PICK(bet, seat_i);
-            a_cls = next_cls;
         }
         STAMP(9);   // observation stores issued
         if ((PH & PULSE_PH_ADVANCE) && j == 0) sto_in_loop(done_dst, ut, (uint8_t)(done ? 1 : 0));      // ping-pong buffer: always written
@@ -775,10 +752,9 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
     // The pointer stays in the constant address space (scalar loads of the array pointers, lgkmcnt only -- as a generic
     // pointer they became vector loads waited for with vmcnt(0), i.e. behind every store in flight), and the stores go
     // out as global stores (stg).
-    typedef const __attribute__((address_space(4))) PulsePokerView* ViewInKernarg;
-    ViewInKernarg vk = (ViewInKernarg)__builtin_amdgcn_kernarg_segment_ptr();       // the view is the first kernel argument
-    if (MULTI) asm volatile("" : "+s"(vk));
-#define VS(field) (MULTI ? vk->field : v.field)
+    StepKernargsPtr ka = (StepKernargsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    if (MULTI) asm volatile("" : "+s"(ka));
+#define VS(field) (MULTI ? ka->v.field : v.field)
 #pragma unroll
     for (int k = 0; k < SPL; ++k) {
         const int seat = SEAT(k);
@@ -793,7 +769,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
 #pragma unroll
         for (int k = 0; k < SPL; ++k) if (SEAT(k) < A) stg(VS(equities), (eq0 + (uint32_t)SEAT(k)) * 4u, eq[k]);
     }
-    if (POLICY && act_dirty && j == 0) stg(MULTI ? *(int64_t* const __attribute__((address_space(4)))*)((const __attribute__((address_space(4))) char*)vk + sizeof(PulsePokerView)) : actions, ut * 8u, (int64_t)act64);
+    if (POLICY && act_dirty && j == 0) stg(MULTI ? ka->actions : actions, ut * 8u, (int64_t)act64);
     if (PH & (PULSE_PH_ADVANCE | PULSE_PH_SHOWDOWN)) {
         if (board_dirty) {
             static_assert(LPT == 4 || LPT == 2, "board store");
@@ -855,6 +831,8 @@ __global__ __launch_bounds__(256, 2) void poker_act_step_kernel(const PulsePoker
     poker_step_body<PULSE_PH_STEP, true, 2, 5, WOBS, 1, true>(v, actions, actor_idx_in, rewards, pa, ca, &qa);
 }
 
+}  // namespace
+
 // ---------------------------------------------------------------- host side
 // Lanes per table.  Single-step launches: four.  Chunk launches: two where a lane can hold the table's seats in five
 // (max_players <= 10; PULSE_VIEW_FOUR_LANES asks for four), four otherwise.  Two lanes per table replicate the table's
@@ -864,7 +842,10 @@ __global__ __launch_bounds__(256, 2) void poker_act_step_kernel(const PulsePoker
 // size, 46.9 vs 43.6 us and 553 vs 463 us: what it saves is exactly the replicated table-level work those changes cut.
 // Tables of 12 / 16 seats at six / eight seats per lane were measured too and lose: 42.7 vs 42.5 and 72.6 vs 59.2 us at
 // 65,536 tables, 277 vs 233 and 391 vs 317 us at 524,288 -- registers (168 / 187) and LDS per wavefront grow with the seats.)
-inline int lanes_for(const PulsePokerView& v, bool chunk) { return chunk && v.max_players <= 10 && !(v.flags & PULSE_VIEW_FOUR_LANES) ? 2 : 4; }
+int pulse::lanes_for(const PulsePokerView& v, bool chunk) { return chunk && v.max_players <= 10 && !(v.flags & PULSE_VIEW_FOUR_LANES) ? 2 : 4; }
+
+namespace {
+
 inline dim3 step_grid(const PulsePokerView& v, int lpt) { return dim3((unsigned)(((long long)v.n_games * lpt + kStepBlock - 1) / kStepBlock)); }
 inline bool obs_staging(const PulsePokerView& v, const float* obs_odd, int lpt) {
     return !(v.flags & PULSE_VIEW_NO_OBS_STAGING) && (v.n_games % (64 / lpt)) == 0 && ((uintptr_t)v.obs & 15u) == 0 && ((uintptr_t)obs_odd & 15u) == 0;
@@ -873,24 +854,14 @@ inline bool obs_staging(const PulsePokerView& v, const float* obs_odd, int lpt) 
 template <uint32_t PH, bool POLICY, int LPT, int SPL, int MULTI>
 void launch_one(const PulsePokerView& v, int64_t* actions, const int32_t* actor_idx, float* rewards, const PolicyArgs& pa, const ChunkArgs& ca,
                 hipStream_t st) {
-    dim3 grid = step_grid(v, LPT);
-    const dim3 block(kStepBlock);
     constexpr int TPW = 64 / LPT;
     const bool wobs = (PH & PULSE_PH_OBS) && (MULTI || PH == PULSE_PH_STEP) && obs_staging(v, MULTI ? ca.obs_odd : nullptr, LPT);
     const size_t lds = MULTI ? sizeof(int32_t) * (size_t)(kStepBlock / 64) * (size_t)chunk_lds_dwords(v.obs_size, LPT * SPL, TPW, MULTI == 2)
                              : (wobs ? sizeof(float) * (size_t)(kStepBlock / 64) * TPW * (size_t)v.obs_size : 0);
     constexpr bool W = PH == PULSE_PH_STEP;          // only the full step is instantiated with observation staging
-    if (lds > 48 * 1024) {                           // beyond the default dynamic-LDS limit: raise it (to what this launch needs)
-        static size_t raised[2] = {0, 0};
-        if (raised[wobs ? 1 : 0] < lds) {
-            const void* fn = wobs ? reinterpret_cast<const void*>(&poker_step_kernel<PH, POLICY, LPT, SPL, W, MULTI>)
-                                  : reinterpret_cast<const void*>(&poker_step_kernel<PH, POLICY, LPT, SPL, false, MULTI>);
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess) raised[wobs ? 1 : 0] = lds;
-            else (void)hipGetLastError();            // the launch below reports what is wrong, not this call's sticky error
-        }
-    }
-    if (wobs) hipLaunchKernelGGL((poker_step_kernel<PH, POLICY, LPT, SPL, W, MULTI>), grid, block, lds, st, v, actions, actor_idx, rewards, pa, ca);
-    else hipLaunchKernelGGL((poker_step_kernel<PH, POLICY, LPT, SPL, false, MULTI>), grid, block, lds, st, v, actions, actor_idx, rewards, pa, ca);
+    const auto fn = wobs ? &poker_step_kernel<PH, POLICY, LPT, SPL, W, MULTI> : &poker_step_kernel<PH, POLICY, LPT, SPL, false, MULTI>;
+    // after a refusal to raise the LDS limit the launch is tried all the same, and it is the launch that reports (finish_launch)
+    pulse::launch_lds(fn, step_grid(v, LPT).x, kStepBlock, lds, st, true, v, actions, actor_idx, rewards, pa, ca);
 }
 
 template <uint32_t PH, bool POLICY, int MULTI>
@@ -901,12 +872,18 @@ void launch_any(const PulsePokerView& v, int64_t* actions, const int32_t* actor_
     else launch_one<PH, POLICY, 4, 4, MULTI>(v, actions, actor_idx, rewards, pa, ca, st);
 }
 
-template <uint32_t PH, bool POLICY>
-void launch_step(const PulsePokerView& v, int64_t* actions, const int32_t* actor_idx, float* rewards, const PolicyArgs& pa, hipStream_t st) {
-    launch_any<PH, POLICY, 0>(v, actions, actor_idx, rewards, pa, ChunkArgs{nullptr, nullptr, 1}, st);
+template <uint32_t PH>
+void launch_phase(const PulsePokerView& v, int64_t* actions, const int32_t* actor_idx, float* rewards, hipStream_t st) {
+    launch_any<PH, false, 0>(v, actions, actor_idx, rewards, PolicyArgs{}, ChunkArgs{}, st);
 }
 
-void launch_chunk(const PulsePokerView& v, int64_t* actions, float* rewards_even, const PolicyArgs& pa, const ChunkArgs& ca, hipStream_t st) {
+}  // namespace
+
+void pulse::launch_policy_step(const PulsePokerView& v, int64_t* actions, float* rewards, const PolicyArgs& pa, hipStream_t st) {
+    launch_any<PULSE_PH_STEP, true, 0>(v, actions, nullptr, rewards, pa, ChunkArgs{}, st);
+}
+
+void pulse::launch_chunk(const PulsePokerView& v, int64_t* actions, float* rewards_even, const PolicyArgs& pa, const ChunkArgs& ca, hipStream_t st) {
     if (lanes_for(v, true) == 2) {
         // The full LDS image lets 10 two-lane wavefronts live on a CU (2.5 per SIMD = 81,920 tables on the 256 CUs of an
         // MI355X), the slim one 12.  Batches with more wavefronts than that take the slim image -- 67.0 vs 68.9 us per chunk
@@ -916,45 +893,6 @@ void launch_chunk(const PulsePokerView& v, int64_t* actions, float* rewards_even
         else launch_one<PULSE_PH_STEP, true, 2, 5, 1>(v, actions, nullptr, rewards_even, pa, ca, st);
     } else launch_any<PULSE_PH_STEP, true, 1>(v, actions, nullptr, rewards_even, pa, ca, st);
 }
-
-template <uint32_t PH>
-void launch_phase(const PulsePokerView& v, int64_t* actions, const int32_t* actor_idx, float* rewards, hipStream_t st) {
-    launch_step<PH, false>(v, actions, actor_idx, rewards, PolicyArgs{0, 0, 0, 0, nullptr, nullptr, 0, nullptr, 0}, st);
-}
-
-}  // namespace
-
-// HIP-event timer owned by the caller: brackets whole roll-out calls on their launch stream
-struct PulseTimer {
-    static constexpr int kMax = 4096;
-    hipEvent_t start[kMax], stop[kMax];
-    int launches[kMax], steps[kMax];
-    int created = 0, used = 0;
-    long long calls = 0;                  // chunks seen by pulse_poker_rollout_until (a bracket opens every time_every-th)
-    bool open = false;                    // a bracket is open: start recorded, stop not yet
-    int open_launches = 0, open_steps = 0;
-};
-
-namespace {
-constexpr int kTimedSpan = 8;             // consecutive chunks per event pair (an episode has at most eight): the pair's own queue time is shared
-int timer_begin(PulseTimer* tm, hipStream_t st) {
-    if (tm->used >= PulseTimer::kMax) return 0;
-    if (tm->used >= tm->created) {
-        if (hipEventCreate(&tm->start[tm->created]) != hipSuccess || hipEventCreate(&tm->stop[tm->created]) != hipSuccess)
-            return pulse::fail(PULSE_ENODEVICE, "roll-out timer: hipEventCreate failed");
-        ++tm->created;
-    }
-    const hipError_t e = hipEventRecord(tm->start[tm->used], st);
-    if (e != hipSuccess) return pulse::fail_hip((int)e, "roll-out timer: hipEventRecord");
-    tm->open = true; tm->open_launches = 0; tm->open_steps = 0;
-    return 0;
-}
-void timer_end(PulseTimer* tm, hipStream_t st) {
-    (void)hipEventRecord(tm->stop[tm->used], st);
-    tm->launches[tm->used] = tm->open_launches; tm->steps[tm->used] = tm->open_steps; ++tm->used;
-    tm->open = false;
-}
-}  // namespace
 
 extern "C" {
 
@@ -971,8 +909,7 @@ int pulse_poker_policy_step(const PulsePokerView* v, const uint8_t* agent_types,
     if (int rc = pulse::check_view(v, "pulse_poker_policy_step")) return rc;
     if (!actions || !rewards || !agent_types) return pulse::fail(PULSE_EINVAL, "pulse_poker_policy_step: null argument");
     if (v->n_games == 0) return 0;
-    const PolicyArgs pa{pulse::pack_types(agent_types, v->n_players), seed, step_counter, table_id0, nullptr, nullptr, 0, nullptr, 0};
-    launch_step<PULSE_PH_STEP, true>(*v, actions, nullptr, rewards, pa, (hipStream_t)stream);
+    pulse::launch_policy_step(*v, actions, rewards, PolicyArgs(pulse::pack_types(agent_types, v->n_players), seed, step_counter, table_id0), (hipStream_t)stream);
     return pulse::finish_launch("pulse_poker_policy_step");
 }
 
@@ -1009,10 +946,10 @@ int pulse_poker_ablate(const PulsePokerView* v, uint32_t phases, int64_t* action
     if (int rc = pulse::check_view(v, "pulse_poker_ablate")) return rc;
     if (v->max_players > 12) return pulse::fail(PULSE_EINVAL, "pulse_poker_ablate: max_players <= 12");
     const dim3 grid = step_grid(*v, 4), block(kStepBlock);
-    const PolicyArgs pa{types_packed, 1, step_counter, 0, nullptr, nullptr, 0, nullptr, 0};
-    const ChunkArgs ca{nullptr, nullptr, 1};
+    const PolicyArgs pa(types_packed, 1, step_counter, 0);
+    const ChunkArgs ca{};
     hipStream_t st = (hipStream_t)stream;
-#define PULSE_ABL(MASK) case (MASK): hipLaunchKernelGGL((poker_step_kernel<(MASK), true, 4, 3, false, false>), grid, block, 0, st, *v, actions, (const int32_t*)nullptr, rewards, pa, ca); break;
+#define PULSE_ABL(MASK) case (MASK): hipLaunchKernelGGL((poker_step_kernel<(MASK), true, 4, 3, false, 0>), grid, block, 0, st, *v, actions, (const int32_t*)nullptr, rewards, pa, ca); break;
     switch (phases) {
     PULSE_ABL(PULSE_PH_STEP)
     PULSE_ABL(PULSE_PH_STEP & ~PULSE_PH_EQUITY)
@@ -1035,98 +972,6 @@ int pulse_debug_set_stamp_buffer(unsigned long long* buf) {
     return e == hipSuccess ? 0 : pulse::fail_hip((int)e, "pulse_debug_set_stamp_buffer");
 }
 #endif
-
-/* ---- roll-out: n_steps fused policy+step transitions enqueued by one native call --------------------------- */
-int pulse_timer_create(void** out) {
-    if (!out) return pulse::fail(PULSE_EINVAL, "pulse_timer_create: null argument");
-    *out = new PulseTimer();
-    return 0;
-}
-
-int pulse_timer_destroy(void* timer) {
-    PulseTimer* tm = static_cast<PulseTimer*>(timer);
-    if (!tm) return 0;
-    for (int i = 0; i < tm->created; ++i) { (void)hipEventDestroy(tm->start[i]); (void)hipEventDestroy(tm->stop[i]); }
-    delete tm;
-    return 0;
-}
-
-int pulse_timer_collect(void* timer, float* sum_ms, int32_t* n_launches, int64_t* n_steps) {
-    PulseTimer* tm = static_cast<PulseTimer*>(timer);
-    if (!tm || !sum_ms || !n_launches || !n_steps) return pulse::fail(PULSE_EINVAL, "pulse_timer_collect: null argument");
-    float total = 0.0f; int launches = 0; long long steps = 0;
-    for (int i = 0; i < tm->used; ++i) {
-        float ms = 0.0f;
-        const hipError_t e = hipEventElapsedTime(&ms, tm->start[i], tm->stop[i]);
-        if (e != hipSuccess) return pulse::fail_hip((int)e, "pulse_timer_collect (call it after a stream sync)");
-        total += ms; launches += tm->launches[i]; steps += tm->steps[i];
-    }
-    *sum_ms = total; *n_launches = launches; *n_steps = steps;
-    tm->used = 0;
-    return 0;
-}
-
-namespace {
-// one chunk launch of a paired sequence (pulse_internal.h: StopRulePair)
-void launch_pair(const PulsePokerView& v_even, const PulsePokerView& v_odd, uint64_t packed, uint64_t seed, uint64_t step_counter0,
-                 uint64_t table_id0, int64_t* actions, float* rewards_even, float* rewards_odd, int n_steps, int chunk_steps,
-                 const pulse::StopRulePair& plan, hipStream_t st) {
-    PolicyArgs pa{packed, seed, step_counter0, table_id0, plan.wave_done_fin, plan.carry[0].partials, plan.carry[0].n, plan.carry[0].host, plan.carry[0].seq};
-    pa.carry2_partials = plan.carry[1].partials; pa.carry2_n = plan.carry[1].n; pa.carry2_host = plan.carry[1].host; pa.carry2_seq = plan.carry[1].seq;
-    if (pa.carry_n == 0 && pa.carry2_n > 0) {        // (cannot happen: carries are filled in order; kept for safety)
-        pa.carry_partials = pa.carry2_partials; pa.carry_n = pa.carry2_n; pa.carry_host = pa.carry2_host; pa.carry_seq = pa.carry2_seq; pa.carry2_n = 0;
-    }
-    pa.wave_done_mid = plan.wave_done_mid; pa.mid_step = plan.n_chunks == 2 ? chunk_steps : 0;
-    pa.verdict_host = plan.verdict_host; pa.verdict_dev = plan.verdict_dev; pa.verdict_id = plan.launch_id; pa.verdict_err = plan.verdict_err;
-    pa.verdict_ticks = plan.wait_ticks;
-    const ChunkArgs ca{v_odd.obs, rewards_odd, n_steps};
-    launch_chunk(v_even, actions, rewards_even, pa, ca, st);
-}
-}  // namespace
-
-int pulse_poker_rollout(const PulsePokerView* v_even, const PulsePokerView* v_odd, const uint8_t* agent_types,
-                        uint64_t seed, uint64_t step_counter0, uint64_t table_id0, int64_t* actions, float* rewards_even,
-                        float* rewards_odd, int32_t n_steps, void* timer, void* stoprule, void* stream) {
-    if (int rc = pulse::check_view(v_even, "pulse_poker_rollout")) return rc;
-    if (int rc = pulse::check_view(v_odd, "pulse_poker_rollout")) return rc;
-    if (!actions || !rewards_even || !rewards_odd || !agent_types || n_steps < 0)
-        return pulse::fail(PULSE_EINVAL, "pulse_poker_rollout: bad argument");
-    if (v_even->is_done != v_odd->is_done_out || v_even->is_done_out != v_odd->is_done || v_even->n_games != v_odd->n_games)
-        return pulse::fail(PULSE_EINVAL, "pulse_poker_rollout: v_odd must be v_even with is_done / is_done_out swapped");
-    if (v_even->n_games == 0 || n_steps == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    const uint64_t packed = pulse::pack_types(agent_types, v_even->n_players);
-    // one step is what the single-step kernel is for (15.4 vs 18.1 us at 65,536 tables: no LDS staging to amortise)
-    const bool chunk = !(v_even->flags & PULSE_VIEW_NO_CHUNK) && n_steps > 1;
-    PulseTimer* tm = static_cast<PulseTimer*>(timer);
-    const bool timed = tm && !tm->open && tm->used < PulseTimer::kMax;
-    if (timed) if (int rc = timer_begin(tm, st)) return rc;
-    PulseStopRule* rule = static_cast<PulseStopRule*>(stoprule);
-    const int n_waves = (int)(((long long)v_even->n_games * lanes_for(*v_even, chunk) + 63) / 64);
-    uint32_t* wave_done = nullptr;
-    pulse::StopRuleCarry carry{nullptr, 0, nullptr, 0};
-    if (rule) if (int rc = pulse::stoprule_claim(rule, n_waves, &wave_done, &carry)) return rc;
-    if (chunk) {
-        const PolicyArgs pa{packed, seed, step_counter0, table_id0, wave_done, carry.partials, carry.n, carry.host, carry.seq};
-        ChunkArgs ca{v_odd->obs, rewards_odd, n_steps};
-        // (streaming, non-temporal observation stores were measured: -1 % per chunk up to 262,144 tables, +4 % at 1 M --
-        // and +50 % fabric write traffic, since ordinary stores to the two ping-pong blocks are largely absorbed by the
-        // caches.  Not used.)
-        launch_chunk(*v_even, actions, rewards_even, pa, ca, st);
-    } else {
-        for (int i = 0; i < n_steps; ++i) {
-            const PulsePokerView& v = (i & 1) ? *v_odd : *v_even;
-            float* rw = (i & 1) ? rewards_odd : rewards_even;
-            PolicyArgs pa{packed, seed, step_counter0 + (uint64_t)i, table_id0, i == n_steps - 1 ? wave_done : nullptr, nullptr, 0, nullptr, 0};
-            if (i == 0) { pa.carry_partials = carry.partials; pa.carry_n = carry.n; pa.carry_host = carry.host; pa.carry_seq = carry.seq; }
-            launch_step<PULSE_PH_STEP, true>(v, actions, nullptr, rw, pa, st);
-        }
-    }
-    if (timed) { tm->open_launches = chunk ? 1 : n_steps; tm->open_steps = n_steps; timer_end(tm, st); }
-    if (int rc = pulse::finish_launch("pulse_poker_rollout")) return rc;
-    if (rule) return pulse::stoprule_commit(rule, n_waves, st);
-    return 0;
-}
 
 /* The trainer's step with the learner in it, first half, as ONE launch: pulse_qnet_act_select on the
  * observation `act->states` followed by pulse_poker_policy_step on `v` -- same results, word for word (the workgroup that
@@ -1154,104 +999,17 @@ int pulse_poker_act_policy_step(const PulsePokerView* v, const uint8_t* agent_ty
     qa.terminated = act->terminated; qa.row_mask_out = act->row_mask_out;
     qa.tsel_rows = act->select_scratch; qa.tsel_counts = act->select_scratch + (size_t)((n + 255) / 256) * 256;
     PulseStopRule* rule = static_cast<PulseStopRule*>(stoprule);
-    const int n_waves = n * 2 / 64;
-    uint32_t* wave_done = nullptr;
-    pulse::StopRuleCarry carry{nullptr, 0, nullptr, 0};
-    if (rule) if (int rc = pulse::stoprule_claim(rule, n_waves, &wave_done, &carry)) return rc;
-    const PolicyArgs pa{pulse::pack_types(agent_types, v->n_players), seed, step_counter, table_id0, wave_done, carry.partials, carry.n, carry.host, carry.seq};
-    const ChunkArgs ca{v->obs, rewards, 1};
+    const int n_waves = pulse::launch_waves(n, 2);
+    PolicyArgs pa(pulse::pack_types(agent_types, v->n_players), seed, step_counter, table_id0);
+    if (rule) if (int rc = pulse::stoprule_claim(rule, n_waves, &pa.wave_done, &pa.carry[0])) return rc;
+    ChunkArgs ca{v->obs, rewards, 1};
     const bool wobs = obs_staging(*v, v->obs, 2);
     const size_t lds = std::max(pulse_qnet::kActLdsBytes, sizeof(int32_t) * 4 * (size_t)chunk_lds_dwords(v->obs_size, 10, 32, false));
-    const void* fn = wobs ? reinterpret_cast<const void*>(&poker_act_step_kernel<true>) : reinterpret_cast<const void*>(&poker_act_step_kernel<false>);
-    static size_t raised[2] = {0, 0};
-    if (raised[wobs ? 1 : 0] < lds) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return pulse::fail_hip((int)e, "pulse_poker_act_policy_step: LDS size attribute");
-        raised[wobs ? 1 : 0] = lds;
-    }
-    const dim3 grid((unsigned)(n / 128)), block(256);
-    if (wobs) hipLaunchKernelGGL(poker_act_step_kernel<true>, grid, block, lds, st, *v, actions, (const int32_t*)nullptr, rewards, pa, ca, qa);
-    else hipLaunchKernelGGL(poker_act_step_kernel<false>, grid, block, lds, st, *v, actions, (const int32_t*)nullptr, rewards, pa, ca, qa);
+    const auto fn = wobs ? &poker_act_step_kernel<true> : &poker_act_step_kernel<false>;
+    const pulse::LdsLaunch r = pulse::launch_lds(fn, (unsigned)(n / 128), 256, lds, st, false, *v, actions, nullptr, rewards, pa, ca, qa);
+    if (r.attr != hipSuccess) return pulse::fail_hip(r.attr, "pulse_poker_act_policy_step: LDS size attribute");
     if (int rc = pulse::finish_launch("pulse_poker_act_policy_step")) return rc;
     if (rule) return pulse::stoprule_commit(rule, n_waves, st);
-    return 0;
-}
-
-int pulse_poker_rollout_until(const PulsePokerView* v_even, const PulsePokerView* v_odd, const uint8_t* agent_types,
-                              uint64_t seed, uint64_t step_counter0, uint64_t table_id0, int64_t* actions, float* rewards_even,
-                              float* rewards_odd, int32_t chunk_steps, int32_t max_steps, void* timer, int32_t time_every,
-                              void* stoprule, void* stream, int32_t* steps_done, int32_t* over) {
-    if (!steps_done || !over || chunk_steps <= 0 || max_steps < 0 || !stoprule)
-        return pulse::fail(PULSE_EINVAL, "pulse_poker_rollout_until: bad argument");
-    if (int rc = pulse::check_view(v_even, "pulse_poker_rollout_until")) return rc;
-    if (int rc = pulse::check_view(v_odd, "pulse_poker_rollout_until")) return rc;
-    if (!actions || !rewards_even || !rewards_odd || !agent_types) return pulse::fail(PULSE_EINVAL, "pulse_poker_rollout_until: null argument");
-    PulseTimer* tm = static_cast<PulseTimer*>(timer);
-    hipStream_t st = (hipStream_t)stream;
-    const bool per_step = (v_even->flags & PULSE_VIEW_NO_CHUNK) != 0;
-    PulseStopRule* rule = static_cast<PulseStopRule*>(stoprule);
-    int done = 0, parity = 0, verdict = 0;
-    bool fell_back = false;
-    // ---- paired launches: with the lag-1 rule ONE launch runs up to two check intervals and takes the rule's verdicts on
-    // the two check points before them itself (pulse_internal.h: StopRulePair) -- half as many state load bursts and
-    // store tails per episode, the same episodes step for step.  (PULSE_VIEW_NO_PAIRS / lag 0 / lag 2 / RCCL: one check
-    // interval per launch, below.)
-    const int n_waves_chunk = (int)(((long long)v_even->n_games * lanes_for(*v_even, true) + 63) / 64);
-    const bool pairs = !per_step && !(v_even->flags & PULSE_VIEW_NO_PAIRS) && chunk_steps > 1 && v_even->n_games > 0 &&
-                       pulse::stoprule_pairs_supported(rule, n_waves_chunk);
-    if (pairs) {
-        const uint64_t packed = pulse::pack_types(agent_types, v_even->n_players);
-        while (done < max_steps && !verdict) {
-            const int left = max_steps - done;
-            const int k = left >= 2 * chunk_steps ? 2 : 1;
-            const int n = k == 2 ? 2 * chunk_steps : (left < chunk_steps ? left : chunk_steps);
-            pulse::StopRulePair plan;
-            const int c = pulse::stoprule_pair_claim(rule, n_waves_chunk, k, &plan);
-            if (c < 0) return c;
-            if (c == 1) { verdict = 1; break; }
-            if (tm && time_every > 0 && !tm->open && (tm->calls % time_every) == 0) if (int rc = timer_begin(tm, st)) return rc;
-            if (tm) ++tm->calls;
-            launch_pair(parity ? *v_odd : *v_even, parity ? *v_even : *v_odd, packed, seed, step_counter0 + (uint64_t)done, table_id0, actions,
-                        parity ? rewards_odd : rewards_even, parity ? rewards_even : rewards_odd, n, chunk_steps, plan, st);
-            if (int rc = pulse::finish_launch("pulse_poker_rollout_until")) return rc;
-            if (int rc = pulse::stoprule_pair_commit(rule, &plan, n_waves_chunk, st)) return rc;
-            int chunks_run = 0, gave_up = 0;
-            if (int rc = pulse::stoprule_pair_verdict(rule, &plan, &chunks_run, &verdict, &gave_up)) return rc;
-            if (gave_up) {                  // the host was too late for this launch: it ran nothing; the rule pairs no more
-                fell_back = !verdict;       // (unless the episode had ended before it anyway) its steps run below, one check interval per launch
-                break;
-            }
-            const int ran = chunks_run == k ? n : chunks_run * chunk_steps;
-            done += ran; parity ^= ran & 1;
-            if (tm && tm->open) {
-                tm->open_launches += 1; tm->open_steps += ran;
-                if (tm->open_launches >= kTimedSpan) timer_end(tm, st);
-            }
-        }
-        if (!fell_back) {
-            if (tm && tm->open) timer_end(tm, st);
-            *steps_done = done; *over = verdict;
-            return 0;
-        }
-    }
-    while (done < max_steps && !verdict) {
-        const int n = chunk_steps < max_steps - done ? chunk_steps : max_steps - done;
-        // an event pair brackets kTimedSpan consecutive chunks, every time_every-th chunk opens one
-        if (tm && time_every > 0 && !tm->open && (tm->calls % time_every) == 0) if (int rc = timer_begin(tm, st)) return rc;
-        if (tm) ++tm->calls;
-        // after an odd number of steps the roles of the two views (and reward buffers) are swapped
-        if (int rc = pulse_poker_rollout(parity ? v_odd : v_even, parity ? v_even : v_odd, agent_types, seed, step_counter0 + (uint64_t)done,
-                                         table_id0, actions, parity ? rewards_odd : rewards_even, parity ? rewards_even : rewards_odd, n,
-                                         nullptr, stoprule, stream)) return rc;
-        done += n; parity ^= n & 1;
-        if (tm && tm->open) {
-            tm->open_launches += per_step ? n : 1; tm->open_steps += n;
-            if (tm->open_launches >= (per_step ? kTimedSpan * chunk_steps : kTimedSpan)) timer_end(tm, st);
-        }
-        if (int rc = pulse_stoprule_decide(stoprule, &verdict)) return rc;
-    }
-    if (tm && tm->open) timer_end(tm, st);            // the episode ended inside a bracket: it covers what ran
-    *steps_done = done; *over = verdict;
     return 0;
 }
 

@@ -1,5 +1,6 @@
 // pulse_internal.h -- shared by the translation units of libpulse_hip.so (not part of the ABI).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/pulse_env.h"
@@ -12,6 +13,22 @@ namespace pulse {
 // Records a thread-local error message and returns `code` (so callers can `return fail(...)`).
 int fail(int code, const char* msg);
 int fail_hip(int hip_error, const char* what);
+
+// abi.hip: launches `fn` with `lds_bytes` of dynamic LDS.  Beyond the default limit of 48 KiB the limit of `fn` is raised first --
+// the first time, and again when a later launch of the same function needs more (the step kernel's size follows obs_size);
+// within it no attribute call is made.  `attr`: what raising the limit answered, `launch`: what the launch answered (both
+// hipError_t values); after a refusal the launch is tried only with `launch_if_refused`, and then the refusal's sticky error is
+// cleared first, so that hipGetLastError() afterwards tells what the LAUNCH answered.
+struct LdsLaunch { int attr, launch; };
+LdsLaunch launch_lds(const void* fn, unsigned grid, unsigned block, void** params, size_t lds_bytes, ihipStream_t* stream, bool launch_if_refused = false);
+// the same for a kernel known by its type: the arguments are checked against its parameters, as a <<< >>> launch checks them
+template <class T> struct LdsArg { using type = T; };
+template <class... P>
+LdsLaunch launch_lds(void (*kernel)(P...), unsigned grid, unsigned block, size_t lds_bytes, ihipStream_t* stream, bool launch_if_refused,
+                     typename LdsArg<P>::type... args) {
+    void* params[] = {const_cast<void*>(static_cast<const void*>(&args))...};
+    return launch_lds(reinterpret_cast<const void*>(kernel), grid, block, params, lds_bytes, stream, launch_if_refused);
+}
 
 // envs.hip: the current device's row table of the packed 2048 move (tfe_device.h), built on first use
 int tfe_row_lut(const uint32_t** out);

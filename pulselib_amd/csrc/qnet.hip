@@ -698,22 +698,6 @@ bool fused_apply_fits(unsigned grid) {
     return resident[dev] >= (int)grid;
 }
 
-// Launches a kernel that needs more dynamic LDS than the default limit: the limit of `fn` is raised the first time `fn` is
-// launched.  `attr`: what raising it answered (the launch is not tried after a refusal), `launch`: what the launch answered.
-struct LdsLaunch { hipError_t attr, launch; };
-LdsLaunch launch_lds(const void* fn, unsigned grid, unsigned block, void* args, size_t lds_bytes, hipStream_t st) {
-    static const void* raised[32] = {};                            // (this file has 22 such kernel instances)
-    int i = 0;
-    while (i < 32 && raised[i] && raised[i] != fn) ++i;
-    if (i == 32 || !raised[i]) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return {e, hipSuccess};
-        if (i < 32) raised[i] = fn;
-    }
-    void* params[1] = {args};
-    return {hipSuccess, hipLaunchKernel(fn, dim3(grid), dim3(block), params, lds_bytes, st)};
-}
-
 // PulseQNetTrain.select_scratch / pulse_qnet_act_select's select_scratch (int32 words, pulse_env.h), nw = ceil(n_rows / 256):
 // [0, 256 nw) the training row lists; [256 nw, 258 nw) their window counts (256-row windows from the select launch, 128-row
 // windows from pulse_qnet_act_select); [258 nw, 259 nw) window reward sums; [259 nw, +512) the fused reduce launch's meeting
@@ -747,7 +731,7 @@ int launch(const QNetArgs& a, void* stream) {
     const bool select = a.seat_idx != nullptr;
     const unsigned grid = select ? (unsigned)((a.n_rows + 63) / 64) : (unsigned)((a.n_rows + 31) / 32);
     hipStream_t st = (hipStream_t)stream;
-    void* args = const_cast<QNetArgs*>(&a);
+    void* args[] = {const_cast<QNetArgs*>(&a)};
     if (select && act_rows16_ok(a)) {
         const int cus = device_cus();
         const bool wide = a.n_rows >= 1024 * cus;                 // large batches: windows of 1,024 candidates (~11 tiles for the 16 wavefronts)
@@ -757,7 +741,7 @@ int launch(const QNetArgs& a, void* stream) {
         const size_t lds_bytes = wide ? (k3 ? R16Lds<3, 1024>::bytes : R16Lds<4, 1024>::bytes) : (k3 ? R16Lds<3, 256>::bytes : R16Lds<4, 256>::bytes);
         const int win = wide ? 1024 : 256;
         const unsigned n_win = (unsigned)((a.n_rows + win - 1) / win);
-        const LdsLaunch r = launch_lds(fn, std::min(n_win, (unsigned)cus), kR16Threads, args, lds_bytes, st);
+        const pulse::LdsLaunch r = pulse::launch_lds(fn, std::min(n_win, (unsigned)cus), kR16Threads, args, lds_bytes, st);
         if (r.attr != hipSuccess) {                          // a device (partition) without that much LDS per workgroup: the tile kernels
             (void)hipGetLastError();
             g_rows16_unavailable = true;
@@ -770,14 +754,14 @@ int launch(const QNetArgs& a, void* stream) {
         const bool k5 = vec && n.state_dim <= 40;
         const void* fn = !vec ? reinterpret_cast<const void*>(&qnet_act4_kernel<false, kActWin, 8>)
                          : k5 ? reinterpret_cast<const void*>(&qnet_act4_kernel<true, kActWin, 5>) : reinterpret_cast<const void*>(&qnet_act4_kernel<true, kActWin, 8>);
-        const LdsLaunch r = launch_lds(fn, (unsigned)((a.n_rows + kActWin - 1) / kActWin), 256, args, kActLdsBytes, st);
+        const pulse::LdsLaunch r = pulse::launch_lds(fn, (unsigned)((a.n_rows + kActWin - 1) / kActWin), 256, args, kActLdsBytes, st);
         if (r.attr != hipSuccess) return pulse::fail_hip((int)r.attr, "pulse_qnet_act: LDS size attribute");
         if (r.launch != hipSuccess) return pulse::fail_hip((int)r.launch, "pulse_qnet_act launch");
         if (a.asel_counts) {                                 // two-launch form: the window launch listed the rows, this one runs them in full tiles
             const void* fn2 = !vec ? reinterpret_cast<const void*>(&qnet_act_rows_kernel<false, kActWin, 8>)
                               : k5 ? reinterpret_cast<const void*>(&qnet_act_rows_kernel<true, kActWin, 5>) : reinterpret_cast<const void*>(&qnet_act_rows_kernel<true, kActWin, 8>);
             const unsigned tiles_at_most = (unsigned)((a.n_rows + 31) / 32);
-            const LdsLaunch r2 = launch_lds(fn2, std::min(tiles_at_most, 768u), 256, args, kActLdsBytes, st);   // three workgroups per CU
+            const pulse::LdsLaunch r2 = pulse::launch_lds(fn2, std::min(tiles_at_most, 768u), 256, args, kActLdsBytes, st);   // three workgroups per CU
             if (r2.attr != hipSuccess) return pulse::fail_hip((int)r2.attr, "pulse_qnet_act: LDS size attribute");
             if (r2.launch != hipSuccess) return pulse::fail_hip((int)r2.launch, "pulse_qnet_act (rows) launch");
         }
@@ -907,7 +891,8 @@ int train_grads(const PulseQNetTrain* t, const TrainBatch& b, bool apply, bool* 
     const void* fn = t->stability ? train_kernel<true>(vec, n.state_dim, four) : train_kernel<false>(vec, n.state_dim, four);
     // persistent workgroups (157 KB of LDS: one per CU), one per possible tile of 32 rows at most
     const int grid = std::min((b.n_rows + 31) / 32, (int)t->max_blocks);
-    const LdsLaunch tl = launch_lds(fn, (unsigned)grid, four ? 256 : 512, &a, kTrainLdsBytes, st);
+    void* train_args[] = {&a};
+    const pulse::LdsLaunch tl = pulse::launch_lds(fn, (unsigned)grid, four ? 256 : 512, train_args, kTrainLdsBytes, st);
     if (tl.attr != hipSuccess) return pulse::fail_hip((int)tl.attr, "pulse_qnet_train_step: LDS size attribute");
     if (tl.launch != hipSuccess) return pulse::fail_hip((int)tl.launch, "pulse_qnet_train_step launch");
     ReduceArgs r{};

@@ -279,6 +279,32 @@ class PokerGPU(_EnvBase):
             raise ValueError(f"actions must have shape ({self.n_games},), got {tuple(actions.shape)}")
         return actions
 
+    def _types(self, agent_types):
+        """The per-seat PULSE_AGENT_* bytes as the C array the entry points take (one array per distinct tuple)."""
+        key = tuple(int(x) for x in agent_types)
+        types = self._types_cache.get(key)
+        if types is None:
+            if len(key) != self.n_players:
+                raise ValueError(f"agent_types must have {self.n_players} entries, got {len(key)}")
+            types = self._types_cache[key] = (C.c_uint8 * self.n_players)(*key)
+        return types
+
+    @property
+    def _seed64(self):
+        return self.seed & (2**64 - 1)
+
+    def _advance(self, n_steps):
+        """After `n_steps` transitions were enqueued from ping-pong side `_pp`: show the side the last one wrote (without
+        dirtying the views) and return what step() returns; the rewards are the buffer of the last step."""
+        pp = self._pp
+        rewards = self._rewards[pp ^ ((n_steps - 1) & 1) if n_steps > 0 else pp]
+        if n_steps > 0 and n_steps & 1:
+            pp = 1 - pp
+            object.__setattr__(self, "_pp", pp)
+            object.__setattr__(self, "is_done", self._done_bufs[pp])
+            object.__setattr__(self, "obs", self._obs_bufs[pp])
+        return self.obs, rewards, self.is_done, self.is_truncated, self.get_info()
+
     # ------------------------------------------------------------------ reset (PokerGPU.py:73-157)
     def reset(self, seed=None, options=None, rotation=0):
         super().reset(seed=seed)
@@ -328,7 +354,7 @@ class PokerGPU(_EnvBase):
         o.first = 0 if self._has_episode else 1
         o.starting_bbs, o.max_bbs = int(self.starting_bbs), int(self.max_bbs)
         o.rotation = int(options.get('rotation', rotation)) if self._has_episode else 0
-        o.seed, o.episode, o.table_id0 = self.seed & (2**64 - 1), self.episode, self.table_id0
+        o.seed, o.episode, o.table_id0 = self._seed64, self.episode, self.table_id0
         o.prefixed_decks = deck_tensor.data_ptr() if deck_tensor is not None else None
         o.decks_out = self.decks.data_ptr()
         o.shuffle_key_bits = int(getattr(self, "_shuffle_key_bits", 0))      # test hook (pulse_env.h)
@@ -371,33 +397,20 @@ class PokerGPU(_EnvBase):
         with self._on_device():
             _native.check(self._lib.pulse_poker_step(C.byref(v), actions.data_ptr(), rewards.data_ptr(), self._stream()),
                           "pulse_poker_step")
-        pp = 1 - self._pp
-        object.__setattr__(self, "_pp", pp)
-        object.__setattr__(self, "is_done", self._done_bufs[pp])
-        object.__setattr__(self, "obs", self._obs_bufs[pp])
-        return self.obs, rewards, self.is_done, self.is_truncated, self.get_info()
+        return self._advance(1)
 
     def policy_step(self, agent_types, actions, step_counter):
         """Scripted-opponent policy (build_actions) fused with step() in one launch.  `agent_types`:
         bytes/uint8 sequence of PULSE_AGENT_* per seat; EXTERNAL seats take their action from `actions`."""
         actions = self._actions(actions)
-        key = tuple(int(x) for x in agent_types)
-        types = self._types_cache.get(key)
-        if types is None:
-            if len(key) != self.n_players:
-                raise ValueError(f"agent_types must have {self.n_players} entries, got {len(key)}")
-            types = self._types_cache[key] = (C.c_uint8 * self.n_players)(*key)
+        types = self._types(agent_types)
         v = self._view()
         rewards = self._rewards[self._pp]
         with self._on_device():
-            _native.check(self._lib.pulse_poker_policy_step(C.byref(v), types, self.seed & (2**64 - 1), int(step_counter),
+            _native.check(self._lib.pulse_poker_policy_step(C.byref(v), types, self._seed64, int(step_counter),
                                                             self.table_id0, actions.data_ptr(), rewards.data_ptr(),
                                                             self._stream()), "pulse_poker_policy_step")
-        pp = 1 - self._pp
-        object.__setattr__(self, "_pp", pp)
-        object.__setattr__(self, "is_done", self._done_bufs[pp])
-        object.__setattr__(self, "obs", self._obs_bufs[pp])
-        return self.obs, rewards, self.is_done, self.is_truncated, self.get_info()
+        return self._advance(1)
 
     def act_policy_step(self, learner, q_seat, agent_types, actions, step_counter, states, seat_idx, terminated, row_mask_out, stop_rule=None):
         """`learner.act_into(states, seat_idx, q_seat, actions, step_counter=step_counter, terminated=terminated,
@@ -420,12 +433,7 @@ class PokerGPU(_EnvBase):
             if stop_rule is not None:
                 stop_rule.submit(terminated | out[2] if terminated is not None else out[2])
             return out
-        key = tuple(int(x) for x in agent_types)
-        types = self._types_cache.get(key)
-        if types is None:
-            if len(key) != self.n_players:
-                raise ValueError(f"agent_types must have {self.n_players} entries, got {len(key)}")
-            types = self._types_cache[key] = (C.c_uint8 * self.n_players)(*key)
+        types = self._types(agent_types)
         v = self._view()
         if v.obs == states.data_ptr():
             raise ValueError("act_policy_step: `states` is the buffer this step writes its observation into")
@@ -440,13 +448,9 @@ class PokerGPU(_EnvBase):
         act.row_mask_out, act.select_scratch, act.select_words = row_mask_out.data_ptr(), scratch.data_ptr(), scratch.numel()
         with self._on_device():
             _native.check(self._lib.pulse_poker_act_policy_step(
-                C.byref(v), types, self.seed & (2**64 - 1), int(step_counter), self.table_id0, actions.data_ptr(), rewards.data_ptr(),
+                C.byref(v), types, self._seed64, int(step_counter), self.table_id0, actions.data_ptr(), rewards.data_ptr(),
                 C.byref(net), C.byref(act), None if stop_rule is None else stop_rule.handle, self._stream()), "pulse_poker_act_policy_step")
-        pp = 1 - self._pp
-        object.__setattr__(self, "_pp", pp)
-        object.__setattr__(self, "is_done", self._done_bufs[pp])
-        object.__setattr__(self, "obs", self._obs_bufs[pp])
-        return self.obs, rewards, self.is_done, self.is_truncated, self.get_info()
+        return self._advance(1)
 
     def rollout(self, agent_types, actions, n_steps, step_counter0, timer=None, stop_rule=None):
         """`n_steps` fused policy+step transitions in ONE native call and (chunked_rollout) ONE launch: the
@@ -456,31 +460,19 @@ class PokerGPU(_EnvBase):
         returned.  `stop_rule` (stoprule.LaggedDoneCount): the done-count of the final state is submitted as one
         check point by the same call; `timer` (stoprule.RolloutTimer): the call is bracketed by HIP events."""
         actions = self._actions(actions)
-        key = tuple(int(x) for x in agent_types)
-        types = self._types_cache.get(key)
-        if types is None:
-            if len(key) != self.n_players:
-                raise ValueError(f"agent_types must have {self.n_players} entries, got {len(key)}")
-            types = self._types_cache[key] = (C.c_uint8 * self.n_players)(*key)
+        types = self._types(agent_types)
         if self._view_dirty:
             self._build_views()
         pp = self._pp
         with self._on_device():
             _native.check(self._lib.pulse_poker_rollout(C.byref(self._views[pp]), C.byref(self._views[1 - pp]), types,
-                                                        self.seed & (2**64 - 1), int(step_counter0), self.table_id0,
+                                                        self._seed64, int(step_counter0), self.table_id0,
                                                         actions.data_ptr(), self._rewards[pp].data_ptr(),
                                                         self._rewards[1 - pp].data_ptr(), int(n_steps),
                                                         None if timer is None else timer.handle,
                                                         None if stop_rule is None else stop_rule.handle,
                                                         self._stream()), "pulse_poker_rollout")
-        if n_steps <= 0:
-            return self.obs, self._rewards[pp], self.is_done, self.is_truncated, self.get_info()
-        last = pp if (n_steps - 1) % 2 == 0 else 1 - pp
-        new_pp = pp if n_steps % 2 == 0 else 1 - pp
-        object.__setattr__(self, "_pp", new_pp)
-        object.__setattr__(self, "is_done", self._done_bufs[new_pp])
-        object.__setattr__(self, "obs", self._obs_bufs[new_pp])
-        return self.obs, self._rewards[last], self.is_done, self.is_truncated, self.get_info()
+        return self._advance(int(n_steps))
 
     def rollout_until(self, agent_types, actions, chunk_steps, max_steps, step_counter0, stop_rule, timer=None, time_every=0):
         """The trainer's inner loop for scripted tables without the interpreter in it (pulse_poker_rollout_until): chunks
@@ -491,28 +483,19 @@ class PokerGPU(_EnvBase):
         if stop_rule is None or getattr(stop_rule, "handle", None) is None or stop_rule.exchange == "host":
             raise ValueError("rollout_until needs a stop rule that decides natively (exchange 'local' or 'rccl')")
         actions = self._actions(actions)
-        key = tuple(int(x) for x in agent_types)
-        types = self._types_cache.get(key)
-        if types is None:
-            if len(key) != self.n_players:
-                raise ValueError(f"agent_types must have {self.n_players} entries, got {len(key)}")
-            types = self._types_cache[key] = (C.c_uint8 * self.n_players)(*key)
+        types = self._types(agent_types)
         if self._view_dirty:
             self._build_views()
         pp = self._pp
         done, over = C.c_int32(0), C.c_int32(0)
         with self._on_device():
             _native.check(self._lib.pulse_poker_rollout_until(
-                C.byref(self._views[pp]), C.byref(self._views[1 - pp]), types, self.seed & (2**64 - 1), int(step_counter0), self.table_id0,
+                C.byref(self._views[pp]), C.byref(self._views[1 - pp]), types, self._seed64, int(step_counter0), self.table_id0,
                 actions.data_ptr(), self._rewards[pp].data_ptr(), self._rewards[1 - pp].data_ptr(), int(chunk_steps), int(max_steps),
                 None if timer is None else timer.handle, int(time_every), stop_rule.handle, self._stream(), C.byref(done), C.byref(over)),
                 "pulse_poker_rollout_until")
         stop_rule.decisions += -(-done.value // max(int(chunk_steps), 1))
-        if done.value % 2:
-            new_pp = 1 - pp
-            object.__setattr__(self, "_pp", new_pp)
-            object.__setattr__(self, "is_done", self._done_bufs[new_pp])
-            object.__setattr__(self, "obs", self._obs_bufs[new_pp])
+        self._advance(done.value)
         return done.value, bool(over.value)
 
     # ------------------------------------------------------------------ white-box methods

@@ -9,7 +9,7 @@ import sys
 f = glob.glob(sys.argv[1] + "/*/*counter_collection.csv")[0]
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for r in csv.DictReader(open(f)):
-    m = re.search(r"poker_step_kernel<(\d+)u, true, 4, 3, false, false>", r["Kernel_Name"])
+    m = re.search(r"poker_step_kernel<(\d+)u, true, 4, 3, false, 0>", r["Kernel_Name"])
     if m:
         acc[int(m.group(1))][r["Counter_Name"]].append(float(r["Counter_Value"]))
 names = {0x1FF: "full", 0x1FD: "-equity", 0x1DF: "-showdown", 0x1DD: "-equity-showdown", 0x17F: "-reward", 0x0FF: "-obs", 0x15D: "-eq-sd-reward",
