@@ -331,6 +331,51 @@ int pulse_blackjack_reset(const PulseBlackjackView* v, const int32_t* decks_src,
                           uint64_t seed, uint64_t episode, void* stream);
 int pulse_blackjack_step(const PulseBlackjackView* v, const int64_t* actions, void* stream);   /* :113-186 */
 
+/* ---- Blackjack: first-visit Monte-Carlo value estimation in one launch (agents/MonteCarlo/FirstVisitMonteCarlo.py:5-31 and the
+ * reset / step / per-game learn() loop that feeds it).  One lane plays one game from the shuffle to the terminal step, n_episodes
+ * episodes of n_games games per launch; the env's decks, card rows and per-game state are never written.  Game g of episode e is
+ * the game pulse_blackjack_reset(seed, episode + e) + pulse_blackjack_step play: the same Fisher-Yates shuffle on
+ * Philox4x32-10(seed, g, (episode + e) * 16 + (q >> 2)), the same deal / hit / stand / dealer rules.
+ * The reward is 0 before the terminal step and +-1 at it, so the first-visit return of the state seen k steps before the terminal
+ * step is r * gamma^k, and the launch COUNTS: acc[PULSE_BJ_MC_CELL(state, k, r < 0)] += 1 for the first visit of every state of
+ * every game, with state = PULSE_BJ_MC_STATE_INDEX(player's sum, usable ace, dealer's upcard) -- the observation
+ * (blackjack.py:103-108).  Integer adds only: the result is the same bit for bit whatever the order of the atomics.  The sum of
+ * returns of a state follows on the host as sum over k of (acc[.., k, 0] - acc[.., k, 1]) * gamma^k, its count as the sum of both.
+ *   acc      : device int64[PULSE_BJ_MC_ACC_LEN], 8-byte aligned, ADDED to, never cleared: the caller zeroes it when a new
+ *              estimate starts (the convention of pulse_poker_hand_metrics).
+ *   stats    : device int64[4], 8-byte aligned, added to: {games played, games won, actions taken, games capped}.
+ *   hit_prob : device fp32[PULSE_BJ_MC_STATES], the policy: the probability of hitting in each state.  <= 0 (or NaN) = stand,
+ *              >= 1 = hit, between = hit iff u < p with u = (w >> 8) * 2^-24, w = word (t & 3) of
+ *              Philox4x32-10(seed ^ 0xB1AC7AC4D3A1E5, g, (episode + e) * 4 + (t >> 2)) for action t of the game -- the policy's
+ *              own stream, keyed apart from the shuffle's; a word is only drawn where the table holds such a probability.
+ *   decks_src: NULL = device shuffle, else device int32[n_episodes * n_games, 52], row e * n_games + g, used as it is (any
+ *              int32, as pulse_blackjack_reset takes them).
+ *   trace    : NULL, or device int8[n_episodes * n_games, PULSE_BJ_MC_MAX_ACTIONS], 16-byte aligned: row e * n_games + g holds
+ *              the actions of that game (0 = hit, 1 = stand), then -1.  For tests and diagnostics; with NULL nothing is stored
+ *              per game.
+ *   max_blocks: 0 = two persistent workgroups per CU, else the largest grid (each workgroup loops over games and adds its
+ *              histogram to acc once, at the end of the launch).
+ * A game is capped at PULSE_BJ_MC_MAX_ACTIONS actions: one that has not ended by then records nothing and counts in stats[3]
+ * (and in stats[0], not in stats[1..2]).  Cards 0..51 cannot get there; an injected deck of arbitrary values can.  Such values can
+ * also lead to a state outside the layout below (a sum outside 0..31): the policy stands in it and its visit is not counted.
+ * n_games * n_episodes < 2^32 per launch.  Zero-initialise the struct; reserved0 != 0 is PULSE_EINVAL. */
+#define PULSE_BJ_MC_MAX_ACTIONS 16
+#define PULSE_BJ_MC_STATES      1024       /* 32 sums x 2 x 16 upcards */
+#define PULSE_BJ_MC_STATE_INDEX(sum, has_ace, upcard) ((((sum) * 2 + (has_ace)) * 16) + (upcard))   /* sum 0..31, upcard 0..15 */
+#define PULSE_BJ_MC_CELL(state, k, negative) ((((state) * PULSE_BJ_MC_MAX_ACTIONS + (k)) * 2) + (negative))
+#define PULSE_BJ_MC_ACC_LEN     (PULSE_BJ_MC_STATES * PULSE_BJ_MC_MAX_ACTIONS * 2)
+typedef struct PulseBlackjackMC {
+    int32_t n_games, n_episodes;
+    uint64_t seed, episode;
+    const float* hit_prob;
+    const int32_t* decks_src;
+    int64_t* acc;
+    int64_t* stats;
+    int8_t* trace;
+    int32_t max_blocks, reserved0;
+} PulseBlackjackMC;
+int pulse_blackjack_mc_rollout(const PulseBlackjackMC* o, void* stream);
+
 /* ---- 2048 (environments/2048/TFE.py), batched: boards device int32[B,n,n], n = 2..8 ------------
  * 4 x 4 (config/tfe.yaml) with 16-byte aligned boards runs packed: the board as 64 bits of 4-bit log2 tiles, the move as four
  * lookups in a 65,536-entry row table the library builds on the device at the first call (256 KB of static device memory, one

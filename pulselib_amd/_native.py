@@ -93,6 +93,17 @@ class BlackjackView(C.Structure):
         "terminated", "has_ace", "dealer_has_ace", "rewards", "obs")]
 
 
+# pulse_blackjack_mc_rollout's accumulator layout (include/pulse_env.h)
+BJ_MC_MAX_ACTIONS, BJ_MC_STATES = 16, 1024
+BJ_MC_ACC_LEN = BJ_MC_STATES * BJ_MC_MAX_ACTIONS * 2
+
+
+class BlackjackMC(C.Structure):
+    _fields_ = [("n_games", C.c_int32), ("n_episodes", C.c_int32), ("seed", C.c_uint64), ("episode", C.c_uint64),
+                ("hit_prob", C.c_void_p), ("decks_src", C.c_void_p), ("acc", C.c_void_p), ("stats", C.c_void_p), ("trace", C.c_void_p),
+                ("max_blocks", C.c_int32), ("reserved0", C.c_int32)]
+
+
 # every symbol include/pulse_env.h declares: (restype, argtypes)
 _P, _I32, _U32, _U64, _F32, _I64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_float, C.c_int64
 SYMBOLS = {
@@ -139,6 +150,7 @@ SYMBOLS = {
     "pulse_poker_hand_metrics": (C.c_int, [_P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P, _P]),
     "pulse_blackjack_reset": (C.c_int, [_P, _P, _P, _U64, _U64, _P]),
     "pulse_blackjack_step": (C.c_int, [_P, _P, _P]),
+    "pulse_blackjack_mc_rollout": (C.c_int, [_P, _P]),
     "pulse_tfe_reset": (C.c_int, [_P, _P, _I32, _I32, _U64, _U64, _P]),
     "pulse_tfe_step": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _U64, _U64, _U64, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),

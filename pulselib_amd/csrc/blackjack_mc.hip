@@ -1,0 +1,202 @@
+// blackjack_mc.hip -- first-visit Monte-Carlo value estimation for Blackjack as ONE launch (pulse_blackjack_mc_rollout).
+//
+//   agents/MonteCarlo/FirstVisitMonteCarlo.py:5-31 fed by environments/blackjack/blackjack.py:23-186: the reference resets the
+//   env, steps it until every game is over, builds one episode list per game on the host and calls learn() per game.
+//
+// Here one lane plays one game from the shuffle to the terminal step in registers and LDS (blackjack_device.h: the env kernels'
+// own shuffle and card arithmetic, so game (seed, g, episode) IS the game BlackJack.reset() + step() plays) and none of the
+// env's state ever reaches memory.  The reward is 0 before the terminal step and +-1 at it, so the first-visit return of the state
+// seen k steps before the end is r * gamma^k: learning is counting the visits per (state, k, sign of r) -- integer adds, which
+// commute, so the result does not depend on the order of the atomics -- and gamma enters on the host only.
+// Every workgroup is persistent: it loops over games, counts into a histogram in its LDS (32-bit LDS atomics, plain: they are 8 % of the
+// launch) and adds its non-zero cells to the caller's int64 accumulator once, at the end.
+#include <hip/hip_runtime.h>
+
+#include "blackjack_device.h"
+#include "pulse_internal.h"
+
+// Diagnostic twin builds only (`make bjmc-ablate ABL=n`, tools/bench_blackjack_mc.py): bit 0 = no histogram adds (the games are still
+// played: the counters need them), bit 1 = a two-instruction hash instead of Philox in the shuffle.  The product is built with 0.
+#ifndef PULSE_BJMC_ABL
+#define PULSE_BJMC_ABL 0
+#endif
+
+namespace {
+
+using namespace pulse_bj;
+
+// 512 lanes share one histogram: 46 KB of counts + 27 KB of decks + 4 KB of policy = 77 KB of LDS per workgroup, two workgroups =
+// sixteen wavefronts per CU.  (256 lanes per histogram: 64 KB per workgroup, eight wavefronts per CU, 1.39 x the time per game:
+// the shuffle is a chain of dependent LDS byte swaps, so the wavefronts in flight set the rate -- DESIGN.md section 11.)
+constexpr int kBlock = 512;
+constexpr int kMaxActions = PULSE_BJ_MC_MAX_ACTIONS;
+// The LDS histogram covers the states a deck of cards 0..51 can reach: player's sum 4..21 x usable ace x upcard 2..11.
+constexpr int kSumLo = 4, kSums = 18, kUpLo = 2, kUps = 10;
+constexpr int kCompactStates = kSums * 2 * kUps;                       // 360
+constexpr int kCellsPerState = kMaxActions * 2;                        // k x sign
+constexpr int kCompactCells = kCompactStates * kCellsPerState;         // 11,520 cells = 46,080 bytes
+// The policy's draws are keyed apart from the shuffle's (which uses the caller's seed as it is).
+constexpr uint64_t kPolicyKey = 0xB1AC7AC4D3A1E5ull;
+
+constexpr size_t kProbAt = (size_t)kCompactCells * 4, kStatsAt = kProbAt + PULSE_BJ_MC_STATES * 4, kDeckAt = kStatsAt + 32;
+constexpr size_t kLdsBytes = kDeckAt + (size_t)kBlock * 53;            // 77,344
+
+// PULSE_BJ_MC_STATE_INDEX, or -1 for a state outside the public layout (only cards outside 0..51 lead there)
+__device__ __forceinline__ int state_index(int sum, bool has, int up) {
+    return ((uint32_t)sum < 32u && (uint32_t)up < 16u) ? (sum * 2 + (int)has) * 16 + up : -1;
+}
+
+__global__ __launch_bounds__(kBlock) void blackjack_mc_kernel(const PulseBlackjackMC o) {
+    extern __shared__ __align__(16) uint8_t lds[];       // kLdsBytes: beyond the 64 KB a static allocation may have
+    uint32_t* hist = reinterpret_cast<uint32_t*>(lds);
+    float* prob = reinterpret_cast<float*>(lds + kProbAt);
+    unsigned long long* wg_stats = reinterpret_cast<unsigned long long*>(lds + kStatsAt);
+    uint8_t (*deck)[53] = reinterpret_cast<uint8_t (*)[53]>(lds + kDeckAt);     // 53: odd stride, as in the reset kernel
+    for (int i = threadIdx.x; i < kCompactCells; i += kBlock) hist[i] = 0u;
+    for (int i = threadIdx.x; i < PULSE_BJ_MC_STATES; i += kBlock) prob[i] = o.hit_prob[i];
+    if (threadIdx.x < 4) wg_stats[threadIdx.x] = 0ull;
+    __syncthreads();
+
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(o.acc);
+    const uint32_t n_games = (uint32_t)o.n_games;
+    const uint32_t total = n_games * (uint32_t)o.n_episodes;          // (< 2^32: checked by the host)
+    const uint32_t stride = gridDim.x * kBlock;
+    uint8_t* d = deck[threadIdx.x];
+    uint32_t n_played = 0, n_won = 0, n_actions = 0, n_capped = 0;
+
+    for (uint64_t it = (uint64_t)blockIdx.x * kBlock + threadIdx.x; it < total; it += stride) {
+        const uint32_t item = (uint32_t)it;               // (the counter itself is 64 bits wide: item + stride may pass 2^32)
+        const uint32_t e = item / n_games, g = item - e * n_games;
+        const uint64_t episode = o.episode + e;
+        const int32_t* src = o.decks_src ? o.decks_src + (size_t)item * 52 : nullptr;
+        int c0, c1, c2, c3;
+        if (src) { c0 = src[0]; c1 = src[1]; c2 = src[2]; c3 = src[3]; }
+        else { bj_shuffle<(PULSE_BJMC_ABL & 2) != 0>(d, o.seed, (uint64_t)g, episode); c0 = d[0]; c1 = d[1]; c2 = d[2]; c3 = d[3]; }
+        auto card = [&](int pos) -> int { return (uint32_t)pos < 52u ? (src ? src[pos] : (int)d[pos]) : 0; };   // as the step kernel reads it
+        const BjDeal deal = bj_deal(c0, c1, c2, c3);
+        int ps = deal.ps, ds = deal.ds, pos = 4;
+        bool has = deal.has, dhas = deal.dhas;
+        const int up = deal.d1;
+
+        int st[kMaxActions];                              // the state before action t (statically indexed: the loops are unrolled)
+        int T = 0, rew = 0;
+        uint32_t stands = 0;                              // bit t: action t was a stand
+        bool done = false;
+        U4 draw{0u, 0u, 0u, 0u};
+        int draw_call = -1;
+#pragma unroll
+        for (int t = 0; t < kMaxActions; ++t) {
+            if (!done) {
+                const int s = state_index(ps, has, up);
+                st[t] = s;
+                const float p = s >= 0 ? prob[s] : 0.0f;   // a state outside the table stands
+                bool hit = p >= 1.0f;
+                if (!hit && p > 0.0f) {                    // one 24-bit uniform per action, drawn only where the table asks for one
+                    if (draw_call != (t >> 2)) { draw = philox4x32(o.seed ^ kPolicyKey, (uint64_t)g, episode * 4 + (uint64_t)(t >> 2)); draw_call = t >> 2; }
+                    hit = (float)(u4_word(draw, t & 3) >> 8) * (1.0f / 16777216.0f) < p;
+                }
+                T = t + 1;
+                if (hit) {                                                              // blackjack.py:118-135, :166-168
+                    bj_draw(card(pos), ps, has); pos += 1;
+                    if (ps > 21) { rew = -1; done = true; }
+                } else {                                                                // :139-160, :171-177
+                    stands |= 1u << t;
+                    bool active = ds < 17;
+                    while (active) { bj_draw(card(pos), ds, dhas); pos += 1; active = bj_dealer_active(ds, pos); }
+                    rew = bj_stand_reward(ps, ds); done = true;
+                }
+            } else {
+                st[t] = -1;
+            }
+        }
+        n_played += 1;
+        if (o.trace) {                                    // actions taken (0 = hit, 1 = stand), then -1
+            uint32_t w[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                w[q] = 0u;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const int t = 4 * q + b;
+                    w[q] |= (t < T ? ((stands >> t) & 1u) : 0xFFu) << (8 * b);
+                }
+            }
+            reinterpret_cast<uint4*>(o.trace)[item] = make_uint4(w[0], w[1], w[2], w[3]);
+        }
+        if (!done) { n_capped += 1; continue; }           // the cap: nothing is learnt from a game that did not end
+        n_won += rew > 0; n_actions += (uint32_t)T;
+        const int sign = rew < 0;
+#pragma unroll
+        for (int t = 0; t < kMaxActions; ++t) {
+            if (t < T) {
+                const int s = st[t];
+                bool first = s >= 0;
+#pragma unroll
+                for (int j = 0; j < t; ++j) first = first && st[j] != s;                // first visit (FirstVisitMonteCarlo.py:24-31)
+                if (first && !(PULSE_BJMC_ABL & 1)) {
+                    const int cell = (T - 1 - t) * 2 + sign;
+                    const int sum = s >> 5, ace = (s >> 4) & 1, u = s & 15;
+                    if ((uint32_t)(sum - kSumLo) < (uint32_t)kSums && (uint32_t)(u - kUpLo) < (uint32_t)kUps)
+                        atomicAdd(&hist[(((sum - kSumLo) * 2 + ace) * kUps + (u - kUpLo)) * kCellsPerState + cell], 1u);
+                    else
+                        atomicAdd(&acc[(size_t)s * kCellsPerState + cell], 1ull);
+                }
+            }
+        }
+    }
+
+    atomicAdd(&wg_stats[0], (unsigned long long)n_played); atomicAdd(&wg_stats[1], (unsigned long long)n_won);
+    atomicAdd(&wg_stats[2], (unsigned long long)n_actions); atomicAdd(&wg_stats[3], (unsigned long long)n_capped);
+    __syncthreads();
+    for (int i = threadIdx.x; i < kCompactCells; i += kBlock) {
+        const uint32_t n = hist[i];
+        if (n) {
+            const int c = i / kCellsPerState, cell = i % kCellsPerState;
+            const int sum = c / (2 * kUps) + kSumLo, ace = (c / kUps) & 1, u = c % kUps + kUpLo;
+            atomicAdd(&acc[(size_t)PULSE_BJ_MC_STATE_INDEX(sum, ace, u) * kCellsPerState + cell], (unsigned long long)n);
+        }
+    }
+    if (threadIdx.x < 4 && wg_stats[threadIdx.x])
+        atomicAdd(reinterpret_cast<unsigned long long*>(o.stats) + threadIdx.x, wg_stats[threadIdx.x]);
+}
+
+int device_cus() {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 256; }
+    if (cus[dev] == 0) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus[dev] = prop.multiProcessorCount;
+        else { (void)hipGetLastError(); cus[dev] = 256; }
+    }
+    return cus[dev];
+}
+
+}  // namespace
+
+extern "C" int pulse_blackjack_mc_rollout(const PulseBlackjackMC* o, void* stream) {
+    if (!o) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: options are null");
+    if (!o->acc) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: acc is null");
+    if (!o->stats) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: stats is null");
+    if (!o->hit_prob) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: hit_prob is null");
+    if (o->n_games <= 0) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: n_games must be positive");
+    if (o->n_episodes <= 0) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: n_episodes must be positive");
+    if ((uint64_t)o->n_games * (uint64_t)o->n_episodes > 0xFFFFFFFFull)
+        return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: n_games * n_episodes must be below 2^32 per launch");
+    if (((uintptr_t)o->acc & 7u) || ((uintptr_t)o->stats & 7u))
+        return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: acc / stats must be 8-byte aligned");
+    if (((uintptr_t)o->hit_prob & 3u) || ((uintptr_t)o->decks_src & 3u))
+        return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: hit_prob / decks_src must be 4-byte aligned");
+    if ((uintptr_t)o->trace & 15u) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: trace must be 16-byte aligned (one row per store)");
+    if (o->max_blocks < 0) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: max_blocks must be >= 0 (0 = two workgroups per CU)");
+    if (o->reserved0 != 0) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: reserved0 must be 0 (zero-initialise the struct)");
+    const uint64_t total = (uint64_t)o->n_games * (uint64_t)o->n_episodes;
+    const uint64_t needed = (total + kBlock - 1) / kBlock;
+    // persistent workgroups, two per CU (their LDS); the flush of a workgroup's histogram is paid once per launch
+    const uint64_t cap = o->max_blocks > 0 ? (uint64_t)o->max_blocks : 2ull * (uint64_t)device_cus();
+    const unsigned grid = (unsigned)(needed < cap ? needed : cap);
+    const pulse::LdsLaunch r = pulse::launch_lds(blackjack_mc_kernel, grid, kBlock, kLdsBytes, (hipStream_t)stream, false, *o);
+    if (r.attr != hipSuccess) return pulse::fail_hip(r.attr, "pulse_blackjack_mc_rollout: LDS size attribute");
+    if (r.launch != hipSuccess) return pulse::fail_hip(r.launch, "pulse_blackjack_mc_rollout launch");
+    return 0;
+}

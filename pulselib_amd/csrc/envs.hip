@@ -14,6 +14,7 @@
 
 #include <mutex>
 
+#include "blackjack_device.h"
 #include "poker_device.h"
 #include "pulse_internal.h"
 #include "tfe_device.h"
@@ -21,27 +22,12 @@
 namespace {
 
 using namespace pulse_tfe;
+using namespace pulse_bj;
 
 constexpr int kBlock = 256;
 
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32(uint64_t seed, uint64_t subseq, uint64_t offset) {
-    uint32_t c0 = (uint32_t)offset, c1 = (uint32_t)(offset >> 32), c2 = (uint32_t)subseq, c3 = (uint32_t)(subseq >> 32);
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        // one 32 x 32 -> 64 multiply per word pair (v_mad_u64_u32): 32-bit integer multiplies are the slow vector instructions here
-        const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0, p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
-        const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0, h1 = (uint32_t)(p1 >> 32), l1 = (uint32_t)p1;
-        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{c0, c1, c2, c3};
-}
-
 // ------------------------------------------------------------------------------------ Blackjack
-__device__ __forceinline__ int bj_rank(int card) { const int r = card % 13 + 1; return r > 10 ? 10 : r; }
+// (Philox, the shuffle and the card arithmetic: blackjack_device.h, shared with blackjack_mc.hip)
 
 // One lane per game.  The deck lives in the workgroup's LDS while it is shuffled (52 bytes per game: cards are 0..51)
 // and leaves as coalesced dwords -- consecutive lanes write consecutive words of the block's 256 x 52 deck region,
@@ -61,25 +47,13 @@ __global__ __launch_bounds__(kBlock) void blackjack_reset_kernel(const PulseBlac
             const int32_t* src = decks_src + (size_t)g * 52;
             c0 = src[0]; c1 = src[1]; c2 = src[2]; c3 = src[3];
         } else {
-            // Fisher-Yates with Philox draws (replaces argsort(rand), blackjack.py:24-29)
-            for (int c = 0; c < 52; ++c) d[c] = (uint8_t)c;
-            for (int i = 51, q = 0; i > 0; --i, ++q) {
-                const U4 r = philox4x32(seed, (uint64_t)g, episode * 16 + (uint64_t)(q >> 2));
-                const uint32_t w = (q & 3) == 0 ? r.x : (q & 3) == 1 ? r.y : (q & 3) == 2 ? r.z : r.w;
-                const int j = (int)__umulhi(w, (uint32_t)(i + 1));
-                const uint8_t tmp = d[i]; d[i] = d[j]; d[j] = tmp;
-            }
+            bj_shuffle(d, seed, (uint64_t)g, episode);       // Fisher-Yates with Philox draws (replaces argsort(rand), blackjack.py:24-29)
             c0 = d[0]; c1 = d[1]; c2 = d[2]; c3 = d[3];
         }
-        int r1 = bj_rank(c0); const bool a1 = r1 == 1; if (a1) r1 = 11;                   // :53-59
-        int d1 = bj_rank(c1); const bool da1 = d1 == 1; if (da1) d1 = 11;                 // :62-69
-        int r2 = bj_rank(c2); const bool a2 = r2 == 1; if (a2) r2 = 11;                   // :72-78
-        int d2 = bj_rank(c3); const bool dfirst = !da1 && d2 == 1; if (d2 == 1) d2 = 11;  // :81-87
+        const BjDeal o = bj_deal(c0, c1, c2, c3);            // :53-101
+        const int r1 = o.r1, r2 = o.r2, d1 = o.d1, d2 = o.d2, ps = o.ps, ds = o.ds;
+        const bool has = o.has, dhas = o.dhas;
         first[threadIdx.x][0] = r1; first[threadIdx.x][1] = r2; first[threadIdx.x][2] = d1; first[threadIdx.x][3] = d2;
-        bool has = a1 || a2, dhas = da1 || dfirst;
-        int ps = r1 + r2, ds = d1 + d2;
-        if (ps > 21 && has) { ps -= 10; has = false; }                                    // :93-95
-        if (ds > 21 && dhas) { ds -= 10; dhas = false; }                                  // :99-101
         v.players_card_idx[g] = 2; v.dealer_card_idx[g] = 2; v.deck_positions[g] = 4;
         v.dealer_upcard[g] = d1; v.player_card_sums[g] = ps; v.dealer_card_sums[g] = ds;
         v.has_ace[g] = has; v.dealer_has_ace[g] = dhas; v.terminated[g] = 0; v.rewards[g] = 0;
@@ -110,36 +84,27 @@ __global__ __launch_bounds__(kBlock) void blackjack_step_kernel(const PulseBlack
     int ps = v.player_card_sums[g], ds = v.dealer_card_sums[g];
     bool has = v.has_ace[g] != 0, dhas = v.dealer_has_ace[g] != 0;
     if (hit) {                                                                          // :118-135
-        int rank = bj_rank((uint32_t)pos < 52u ? d[pos] : 0);
-        const bool ace = rank == 1;
-        if (ace && !has) rank = 11;
+        const int rank = bj_draw((uint32_t)pos < 52u ? d[pos] : 0, ps, has);
         const int ci = v.players_card_idx[g];
         if ((uint32_t)ci < 20u) v.players_cards[(size_t)g * 20 + ci] = rank;
         v.players_card_idx[g] = ci + 1;
-        has = has || ace;   // (ace & ~already) | already
-        ps += rank; pos += 1;
-        if (ps > 21 && has) { ps -= 10; has = false; }
+        pos += 1;
     }
     if (stand) {                                                                        // :139-160
         int ci = v.dealer_card_idx[g];
         bool active = ds < 17;
         while (active) {
-            int rank = bj_rank((uint32_t)pos < 52u ? d[pos] : 0);
-            const bool ace = rank == 1;
-            if (ace && !dhas) rank = 11;
+            const int rank = bj_draw((uint32_t)pos < 52u ? d[pos] : 0, ds, dhas);
             if ((uint32_t)ci < 20u) v.dealer_cards[(size_t)g * 20 + ci] = rank;
             ci += 1;
-            dhas = dhas || ace;
-            ds += rank;
-            if (ds > 21 && dhas) { ds -= 10; dhas = false; }
             pos += 1;
-            active = ds < 17 && ds <= 21 && pos < 52;
+            active = bj_dealer_active(ds, pos);
         }
         v.dealer_card_idx[g] = ci;
     }
     int rew = 0;                                                                        // :183
     if (hit && ps > 21) { rew = -1; term = true; }                                      // :166-168
-    if (stand) { rew = (ds > 21 || ps >= ds) ? 1 : -1; term = true; }                   // :171-177
+    if (stand) { rew = bj_stand_reward(ps, ds); term = true; }                          // :171-177
     v.deck_positions[g] = pos; v.player_card_sums[g] = ps; v.dealer_card_sums[g] = ds;
     v.has_ace[g] = has; v.dealer_has_ace[g] = dhas; v.terminated[g] = term; v.rewards[g] = rew;
     v.obs[g * 3 + 0] = ps; v.obs[g * 3 + 1] = has; v.obs[g * 3 + 2] = v.dealer_upcard[g];

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import torch
 
-from ..agents import FirstVisitMonteCarlo
+from ..agents import FirstVisitMonteCarlo, FirstVisitMonteCarloGPU
 from ..environments.blackjack import BlackJack
 
 
@@ -33,7 +33,23 @@ def run(device, batches=5, batch_size=1000, gamma=0.9, seed=1, hit_below=17):
     return agent, n_episodes
 
 
+def run_device(device, batches=5, batch_size=1000, gamma=0.9, seed=1, hit_below=17, episodes_per_launch=1, agent=None):
+    """The same estimate with the learner on the device: every batch is ONE launch that shuffles, plays and counts
+    (agents/first_visit_mc_gpu.py); with episodes_per_launch = 1 the games are those `run` plays.  Nothing is read back before
+    `agent.returns`.  agent: continue this agent's estimate instead of starting one."""
+    if agent is None:
+        agent = FirstVisitMonteCarloGPU(device, gamma, seed=seed)
+    policy = agent.threshold_policy(hit_below)
+    for _ in range(batches):
+        agent.learn_batch(batch_size, policy, n_episodes=episodes_per_launch)
+    return agent, batches * batch_size * episodes_per_launch
+
+
 if __name__ == "__main__":
-    agent, n = run(torch.device("cuda"))
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--device-learner", action="store_true", help="play and learn in one launch per batch (run_device)")
+    args = ap.parse_args()
+    agent, n = (run_device if args.device_learner else run)(torch.device("cuda"))
     best = sorted(agent.values.items(), key=lambda kv: -kv[1])[:5]
     print(f"{n} episodes, {len(agent.values)} states; best states {best}")
