@@ -376,6 +376,54 @@ typedef struct PulseBlackjackMC {
 } PulseBlackjackMC;
 int pulse_blackjack_mc_rollout(const PulseBlackjackMC* o, void* stream);
 
+/* ---- Blackjack: on-policy first-visit Monte-Carlo CONTROL on the device (agents/MonteCarlo/OnPolicyFirstVisit.py:6-71): the
+ * roll-out above counting first visits of (state, action) PAIRS, and the policy improvement as a launch of its own, so that
+ * roll-out -> improve -> roll-out runs without a host round trip.
+ * pulse_blackjack_mc_control_rollout plays the games pulse_blackjack_mc_rollout plays -- same shuffle, same policy stream, same
+ * cap, trace and stats, same fields with the same meanings and checks -- and counts action t at state s iff no earlier action of
+ * that game was the same action at the same state.  A stand ends the game, so it is only ever seen k = 0 steps before the
+ * terminal reward: a state has the 32 cells (k, sign) of its hits and 2 cells (sign) of its stands,
+ *   acc[PULSE_BJ_MCC_CELL_HIT(state, k, r < 0)] += 1   /   acc[PULSE_BJ_MCC_CELL_STAND(state, r < 0)] += 1,
+ * acc: device int64[PULSE_BJ_MCC_ACC_LEN], added to.  Summed over the actions the cells are pulse_blackjack_mc_rollout's wherever no
+ * state repeats within a game (cards 0..51).  The launch holds two workgroups per CU; where the device cannot, it is an error.
+ *
+ * pulse_blackjack_mc_improve: one lane per state, float64.  pow[0] = 1, pow[k] = gamma * pow[k - 1]; for each action n_a = the
+ * sum of its cells, sum_a = the sum over ascending k of (double)(acc[.., k, 0] - acc[.., k, 1]) * pow[k] (stand: k = 0 only),
+ * q_a = n_a ? sum_a / n_a : 0.0 (an unseen pair reads 0, as the reference's defaultdict).  A state with n_hit + n_stand = 0 keeps
+ * its hit_prob.  Otherwise the greedy action is stand if q_stand > q_hit, hit if q_stand < q_hit, and on equality stand iff bit 0
+ * of word 0 of Philox4x32-10(seed ^ PULSE_BJ_MCC_TIE_KEY, state, round) is set -- a third stream, keyed apart from the shuffle's
+ * (the seed itself) and the policy's (seed ^ 0xB1AC7AC4D3A1E5) -- and hit_prob[state] = (float)(1 - epsilon + epsilon / 2) where
+ * hit is greedy, (float)(epsilon / 2) where stand is: computed in double, rounded once.
+ *   acc      : device int64[PULSE_BJ_MCC_ACC_LEN], 8-byte aligned, read only.
+ *   q        : NULL, or device float64[PULSE_BJ_MC_STATES][2], (hit, stand), 8-byte aligned: written for every state.
+ *   hit_prob : device fp32[PULSE_BJ_MC_STATES], 4-byte aligned, updated in place.
+ * epsilon outside [0, 1], a gamma that is not finite and non-zero reserved fields are PULSE_EINVAL. */
+#define PULSE_BJ_MCC_CELLS      34         /* hit x k 0..15 x sign, then stand x sign */
+#define PULSE_BJ_MCC_CELL_HIT(state, k, negative) (((state) * PULSE_BJ_MCC_CELLS) + ((k) * 2) + (negative))
+#define PULSE_BJ_MCC_CELL_STAND(state, negative) (((state) * PULSE_BJ_MCC_CELLS) + (PULSE_BJ_MC_MAX_ACTIONS * 2) + (negative))
+#define PULSE_BJ_MCC_ACC_LEN    (PULSE_BJ_MC_STATES * PULSE_BJ_MCC_CELLS)
+#define PULSE_BJ_MCC_TIE_KEY    0x7C01F11B5EEDull
+typedef struct PulseBlackjackMCControl {
+    int32_t n_games, n_episodes;
+    uint64_t seed, episode;
+    const float* hit_prob;
+    const int32_t* decks_src;
+    int64_t* acc;                       /* int64[PULSE_BJ_MCC_ACC_LEN] */
+    int64_t* stats;
+    int8_t* trace;
+    int32_t max_blocks, reserved0;
+} PulseBlackjackMCControl;
+int pulse_blackjack_mc_control_rollout(const PulseBlackjackMCControl* o, void* stream);
+typedef struct PulseBlackjackMCImprove {
+    const int64_t* acc;
+    double gamma, epsilon;
+    uint64_t seed, round;
+    double* q;
+    float* hit_prob;
+    int32_t reserved0, reserved1;
+} PulseBlackjackMCImprove;
+int pulse_blackjack_mc_improve(const PulseBlackjackMCImprove* o, void* stream);
+
 /* ---- 2048 (environments/2048/TFE.py), batched: boards device int32[B,n,n], n = 2..8 ------------
  * 4 x 4 (config/tfe.yaml) with 16-byte aligned boards runs packed: the board as 64 bits of 4-bit log2 tiles, the move as four
  * lookups in a 65,536-entry row table the library builds on the device at the first call (256 KB of static device memory, one

@@ -104,6 +104,21 @@ class BlackjackMC(C.Structure):
                 ("max_blocks", C.c_int32), ("reserved0", C.c_int32)]
 
 
+# pulse_blackjack_mc_control_rollout's accumulator layout: per state the hits' (k, sign) cells, then the stand's two
+BJ_MCC_CELLS = BJ_MC_MAX_ACTIONS * 2 + 2
+BJ_MCC_ACC_LEN = BJ_MC_STATES * BJ_MCC_CELLS
+BJ_MCC_TIE_KEY = 0x7C01F11B5EED
+
+
+class BlackjackMCControl(C.Structure):
+    _fields_ = BlackjackMC._fields_
+
+
+class BlackjackMCImprove(C.Structure):
+    _fields_ = [("acc", C.c_void_p), ("gamma", C.c_double), ("epsilon", C.c_double), ("seed", C.c_uint64), ("round", C.c_uint64),
+                ("q", C.c_void_p), ("hit_prob", C.c_void_p), ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
+
+
 # every symbol include/pulse_env.h declares: (restype, argtypes)
 _P, _I32, _U32, _U64, _F32, _I64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_float, C.c_int64
 SYMBOLS = {
@@ -151,6 +166,8 @@ SYMBOLS = {
     "pulse_blackjack_reset": (C.c_int, [_P, _P, _P, _U64, _U64, _P]),
     "pulse_blackjack_step": (C.c_int, [_P, _P, _P]),
     "pulse_blackjack_mc_rollout": (C.c_int, [_P, _P]),
+    "pulse_blackjack_mc_control_rollout": (C.c_int, [_P, _P]),
+    "pulse_blackjack_mc_improve": (C.c_int, [_P, _P]),
     "pulse_tfe_reset": (C.c_int, [_P, _P, _I32, _I32, _U64, _U64, _P]),
     "pulse_tfe_step": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _U64, _U64, _U64, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),

@@ -1,5 +1,7 @@
 from .first_visit_mc import FirstVisitMonteCarlo
 from .first_visit_mc_gpu import FirstVisitMonteCarloGPU
+from .on_policy_first_visit_mc import OnPolicyFirstVisitMC
+from .on_policy_first_visit_mc_gpu import OnPolicyFirstVisitMCGPU
 from .qlearning import QLearningBatch
 
-__all__ = ["FirstVisitMonteCarlo", "FirstVisitMonteCarloGPU", "QLearningBatch"]
+__all__ = ["FirstVisitMonteCarlo", "FirstVisitMonteCarloGPU", "OnPolicyFirstVisitMC", "OnPolicyFirstVisitMCGPU", "QLearningBatch"]

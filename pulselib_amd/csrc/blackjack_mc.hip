@@ -10,7 +10,15 @@
 // commute, so the result does not depend on the order of the atomics -- and gamma enters on the host only.
 // Every workgroup is persistent: it loops over games, counts into a histogram in its LDS (32-bit LDS atomics, plain: they are 8 % of the
 // launch) and adds its non-zero cells to the caller's int64 accumulator once, at the end.
+//
+// The same kernel, instantiated with CONTROL, counts first visits of (state, ACTION) pairs for on-policy Monte-Carlo control
+// (agents/MonteCarlo/OnPolicyFirstVisit.py:24-49, pulse_blackjack_mc_control_rollout): a stand ends the game, so it is only ever
+// seen at k = 0, and 2 cells per state beside the 32 of the hits hold it.  pulse_blackjack_mc_improve turns that histogram into
+// the next epsilon-soft policy table on the device (:51-71), so roll-out -> improve -> roll-out needs no host round trip.
 #include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
 
 #include "blackjack_device.h"
 #include "pulse_internal.h"
@@ -33,20 +41,30 @@ constexpr int kMaxActions = PULSE_BJ_MC_MAX_ACTIONS;
 // The LDS histogram covers the states a deck of cards 0..51 can reach: player's sum 4..21 x usable ace x upcard 2..11.
 constexpr int kSumLo = 4, kSums = 18, kUpLo = 2, kUps = 10;
 constexpr int kCompactStates = kSums * 2 * kUps;                       // 360
-constexpr int kCellsPerState = kMaxActions * 2;                        // k x sign
-constexpr int kCompactCells = kCompactStates * kCellsPerState;         // 11,520 cells = 46,080 bytes
-// The policy's draws are keyed apart from the shuffle's (which uses the caller's seed as it is).
+// The policy's draws are keyed apart from the shuffle's (which uses the caller's seed as it is), the tie coins of the policy
+// improvement apart from both (PULSE_BJ_MCC_TIE_KEY).
 constexpr uint64_t kPolicyKey = 0xB1AC7AC4D3A1E5ull;
+constexpr uint64_t kTieKey = PULSE_BJ_MCC_TIE_KEY;
 
-constexpr size_t kProbAt = (size_t)kCompactCells * 4, kStatsAt = kProbAt + PULSE_BJ_MC_STATES * 4, kDeckAt = kStatsAt + 32;
-constexpr size_t kLdsBytes = kDeckAt + (size_t)kBlock * 53;            // 77,344
+// Value estimation: hit and stand share the k x sign cells of a state.  Control: the hits' k x sign cells, then the stand's two.
+template <bool CONTROL> struct Layout {
+    static constexpr int kCellsPerState = CONTROL ? PULSE_BJ_MCC_CELLS : kMaxActions * 2;
+    static constexpr int kCompactCells = kCompactStates * kCellsPerState;       // 11,520 cells = 46,080 bytes | 12,240 = 48,960
+    static constexpr size_t kProbAt = (size_t)kCompactCells * 4, kStatsAt = kProbAt + PULSE_BJ_MC_STATES * 4, kDeckAt = kStatsAt + 32;
+    static constexpr size_t kLdsBytes = kDeckAt + (size_t)kBlock * 53;          // 77,344 | 80,224
+};
+static_assert(Layout<false>::kLdsBytes == 77344 && Layout<true>::kLdsBytes == 80224, "LDS budget (DESIGN.md section 11)");
+static_assert(2 * Layout<true>::kLdsBytes <= 160 * 1024 && Layout<true>::kLdsBytes <= 81920, "two workgroups per CU");
 
 // PULSE_BJ_MC_STATE_INDEX, or -1 for a state outside the public layout (only cards outside 0..51 lead there)
 __device__ __forceinline__ int state_index(int sum, bool has, int up) {
     return ((uint32_t)sum < 32u && (uint32_t)up < 16u) ? (sum * 2 + (int)has) * 16 + up : -1;
 }
 
+template <bool CONTROL>
 __global__ __launch_bounds__(kBlock) void blackjack_mc_kernel(const PulseBlackjackMC o) {
+    constexpr int kCellsPerState = Layout<CONTROL>::kCellsPerState, kCompactCells = Layout<CONTROL>::kCompactCells;
+    constexpr size_t kProbAt = Layout<CONTROL>::kProbAt, kStatsAt = Layout<CONTROL>::kStatsAt, kDeckAt = Layout<CONTROL>::kDeckAt;
     extern __shared__ __align__(16) uint8_t lds[];       // kLdsBytes: beyond the 64 KB a static allocation may have
     uint32_t* hist = reinterpret_cast<uint32_t*>(lds);
     float* prob = reinterpret_cast<float*>(lds + kProbAt);
@@ -133,8 +151,14 @@ __global__ __launch_bounds__(kBlock) void blackjack_mc_kernel(const PulseBlackja
                 bool first = s >= 0;
 #pragma unroll
                 for (int j = 0; j < t; ++j) first = first && st[j] != s;                // first visit (FirstVisitMonteCarlo.py:24-31)
+                int cell = (T - 1 - t) * 2 + sign;
+                if constexpr (CONTROL) {                  // first visit of the PAIR (OnPolicyFirstVisit.py:30-36): every action before
+                    if ((stands >> t) & 1u) {             // a stand was a hit, so the stand -- the last action, k = 0 -- is always one
+                        first = s >= 0;
+                        cell = kMaxActions * 2 + sign;
+                    }
+                }
                 if (first && !(PULSE_BJMC_ABL & 1)) {
-                    const int cell = (T - 1 - t) * 2 + sign;
                     const int sum = s >> 5, ace = (s >> 4) & 1, u = s & 15;
                     if ((uint32_t)(sum - kSumLo) < (uint32_t)kSums && (uint32_t)(u - kUpLo) < (uint32_t)kUps)
                         atomicAdd(&hist[(((sum - kSumLo) * 2 + ace) * kUps + (u - kUpLo)) * kCellsPerState + cell], 1u);
@@ -172,31 +196,116 @@ int device_cus() {
     return cus[dev];
 }
 
-}  // namespace
+int fail_named(const char* name, const char* msg) {
+    char text[256];
+    std::snprintf(text, sizeof text, "%s: %s", name, msg);
+    return pulse::fail(PULSE_EINVAL, text);
+}
 
-extern "C" int pulse_blackjack_mc_rollout(const PulseBlackjackMC* o, void* stream) {
-    if (!o) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: options are null");
-    if (!o->acc) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: acc is null");
-    if (!o->stats) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: stats is null");
-    if (!o->hit_prob) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: hit_prob is null");
-    if (o->n_games <= 0) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: n_games must be positive");
-    if (o->n_episodes <= 0) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: n_episodes must be positive");
-    if ((uint64_t)o->n_games * (uint64_t)o->n_episodes > 0xFFFFFFFFull)
-        return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: n_games * n_episodes must be below 2^32 per launch");
-    if (((uintptr_t)o->acc & 7u) || ((uintptr_t)o->stats & 7u))
-        return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: acc / stats must be 8-byte aligned");
-    if (((uintptr_t)o->hit_prob & 3u) || ((uintptr_t)o->decks_src & 3u))
-        return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: hit_prob / decks_src must be 4-byte aligned");
-    if ((uintptr_t)o->trace & 15u) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: trace must be 16-byte aligned (one row per store)");
-    if (o->max_blocks < 0) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: max_blocks must be >= 0 (0 = two workgroups per CU)");
-    if (o->reserved0 != 0) return pulse::fail(PULSE_EINVAL, "pulse_blackjack_mc_rollout: reserved0 must be 0 (zero-initialise the struct)");
+// Both roll-out entry points: the checks, the grid and the launch.  (PulseBlackjackMCControl has PulseBlackjackMC's fields.)
+template <bool CONTROL>
+int rollout(const PulseBlackjackMC* o, void* stream, const char* name) {
+    if (!o) return fail_named(name, "options are null");
+    if (!o->acc) return fail_named(name, "acc is null");
+    if (!o->stats) return fail_named(name, "stats is null");
+    if (!o->hit_prob) return fail_named(name, "hit_prob is null");
+    if (o->n_games <= 0) return fail_named(name, "n_games must be positive");
+    if (o->n_episodes <= 0) return fail_named(name, "n_episodes must be positive");
+    if ((uint64_t)o->n_games * (uint64_t)o->n_episodes > 0xFFFFFFFFull) return fail_named(name, "n_games * n_episodes must be below 2^32 per launch");
+    if (((uintptr_t)o->acc & 7u) || ((uintptr_t)o->stats & 7u)) return fail_named(name, "acc / stats must be 8-byte aligned");
+    if (((uintptr_t)o->hit_prob & 3u) || ((uintptr_t)o->decks_src & 3u)) return fail_named(name, "hit_prob / decks_src must be 4-byte aligned");
+    if ((uintptr_t)o->trace & 15u) return fail_named(name, "trace must be 16-byte aligned (one row per store)");
+    if (o->max_blocks < 0) return fail_named(name, "max_blocks must be >= 0 (0 = two workgroups per CU)");
+    if (o->reserved0 != 0) return fail_named(name, "reserved0 must be 0 (zero-initialise the struct)");
+    char what[96];
+    if constexpr (CONTROL) {
+        // Two workgroups per CU are what the kernel's time per game rests on (one: 1.39 x): a device or a build that cannot hold
+        // them is an error, not a slower run.
+        static int resident[64] = {0};
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
+        if (e == hipSuccess && resident[dev] == 0) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(blackjack_mc_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)Layout<true>::kLdsBytes);
+            int n = 0;
+            if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, blackjack_mc_kernel<true>, kBlock, Layout<true>::kLdsBytes);
+            if (e == hipSuccess) resident[dev] = n > 0 ? n : -1;
+        }
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            std::snprintf(what, sizeof what, "%s: occupancy query", name);
+            return pulse::fail_hip(e, what);
+        }
+        if (resident[dev] < 2) {
+            char text[256];
+            std::snprintf(text, sizeof text, "%s: %d workgroup(s) of %d lanes and %zu bytes of LDS fit on a CU, 2 are needed", name,
+                          resident[dev] < 0 ? 0 : resident[dev], kBlock, Layout<true>::kLdsBytes);
+            return pulse::fail(PULSE_ELAUNCH, text);
+        }
+    }
     const uint64_t total = (uint64_t)o->n_games * (uint64_t)o->n_episodes;
     const uint64_t needed = (total + kBlock - 1) / kBlock;
     // persistent workgroups, two per CU (their LDS); the flush of a workgroup's histogram is paid once per launch
     const uint64_t cap = o->max_blocks > 0 ? (uint64_t)o->max_blocks : 2ull * (uint64_t)device_cus();
     const unsigned grid = (unsigned)(needed < cap ? needed : cap);
-    const pulse::LdsLaunch r = pulse::launch_lds(blackjack_mc_kernel, grid, kBlock, kLdsBytes, (hipStream_t)stream, false, *o);
-    if (r.attr != hipSuccess) return pulse::fail_hip(r.attr, "pulse_blackjack_mc_rollout: LDS size attribute");
-    if (r.launch != hipSuccess) return pulse::fail_hip(r.launch, "pulse_blackjack_mc_rollout launch");
+    const pulse::LdsLaunch r = pulse::launch_lds(blackjack_mc_kernel<CONTROL>, grid, kBlock, Layout<CONTROL>::kLdsBytes, (hipStream_t)stream, false, *o);
+    if (r.attr != hipSuccess) { std::snprintf(what, sizeof what, "%s: LDS size attribute", name); return pulse::fail_hip(r.attr, what); }
+    if (r.launch != hipSuccess) { std::snprintf(what, sizeof what, "%s launch", name); return pulse::fail_hip(r.launch, what); }
+    return 0;
+}
+
+// Policy improvement (OnPolicyFirstVisit.py:51-71) for all states at once, one lane per state: q(s, a) from the control
+// histogram in float64 -- gamma^k by repeated multiplication, the sum over ascending k, as the host's returns_from_histogram
+// forms them (no contraction: the library is built with -ffp-contract=off) -- then the epsilon-soft table the next roll-out reads.
+__global__ __launch_bounds__(256) void blackjack_mc_improve_kernel(const PulseBlackjackMCImprove o) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= PULSE_BJ_MC_STATES) return;
+    const int64_t* cells = o.acc + (size_t)s * PULSE_BJ_MCC_CELLS;
+    int64_t n_hit = 0;
+    double sum_hit = 0.0, pow_k = 1.0;
+    for (int k = 0; k < kMaxActions; ++k) {
+        const int64_t pos = cells[2 * k], neg = cells[2 * k + 1];
+        n_hit += pos + neg;
+        sum_hit += (double)(pos - neg) * pow_k;
+        pow_k = o.gamma * pow_k;
+    }
+    const int64_t pos = cells[2 * kMaxActions], neg = cells[2 * kMaxActions + 1];
+    const int64_t n_stand = pos + neg;
+    const double sum_stand = (double)(pos - neg);                          // k = 0 only
+    const double q_hit = n_hit ? sum_hit / (double)n_hit : 0.0;            // an unseen pair reads 0.0, as the reference's defaultdict(float)
+    const double q_stand = n_stand ? sum_stand / (double)n_stand : 0.0;
+    if (o.q) { o.q[2 * s] = q_hit; o.q[2 * s + 1] = q_stand; }
+    if (n_hit + n_stand == 0) return;                                      // a state never visited keeps its probability
+    bool stand = q_stand > q_hit;                                          // :52-62, the actions in the order hit, stand
+    if (q_stand == q_hit) stand = (philox4x32(o.seed ^ kTieKey, (uint64_t)s, o.round).x & 1u) != 0u;
+    const double explore = o.epsilon / 2.0;
+    o.hit_prob[s] = (float)(stand ? explore : 1.0 - o.epsilon + explore);  // :65-71
+}
+
+}  // namespace
+
+extern "C" int pulse_blackjack_mc_rollout(const PulseBlackjackMC* o, void* stream) {
+    return rollout<false>(o, stream, "pulse_blackjack_mc_rollout");
+}
+
+extern "C" int pulse_blackjack_mc_control_rollout(const PulseBlackjackMCControl* o, void* stream) {
+    static_assert(sizeof(PulseBlackjackMCControl) == sizeof(PulseBlackjackMC), "the two structs share one layout");
+    return rollout<true>(reinterpret_cast<const PulseBlackjackMC*>(o), stream, "pulse_blackjack_mc_control_rollout");
+}
+
+extern "C" int pulse_blackjack_mc_improve(const PulseBlackjackMCImprove* o, void* stream) {
+    const char* name = "pulse_blackjack_mc_improve";
+    if (!o) return fail_named(name, "options are null");
+    if (!o->acc) return fail_named(name, "acc is null");
+    if (!o->hit_prob) return fail_named(name, "hit_prob is null");
+    if (((uintptr_t)o->acc & 7u) || ((uintptr_t)o->q & 7u)) return fail_named(name, "acc / q must be 8-byte aligned");
+    if ((uintptr_t)o->hit_prob & 3u) return fail_named(name, "hit_prob must be 4-byte aligned");
+    if (!(o->epsilon >= 0.0 && o->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
+    if (!std::isfinite(o->gamma)) return fail_named(name, "gamma must be finite");
+    if (o->reserved0 != 0 || o->reserved1 != 0) return fail_named(name, "reserved0 / reserved1 must be 0 (zero-initialise the struct)");
+    blackjack_mc_improve_kernel<<<PULSE_BJ_MC_STATES / 256, 256, 0, (hipStream_t)stream>>>(*o);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return pulse::fail_hip(e, "pulse_blackjack_mc_improve launch");
     return 0;
 }

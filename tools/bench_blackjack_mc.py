@@ -7,6 +7,13 @@
   (c) env_floor      : BlackJack.reset() + 12 step() launches at 1,048,576 games with a fixed action tensor and NO learner: what any
       env-stepped learner pays before it has learnt anything.  HIP events.
 --device-only: (a) alone; --seconds S: the length of (a)'s timed run (1.0; shorter under a counter pass).
+--control: instead, ONE JSON line on the Monte-Carlo control launches (csrc/blackjack_mc.hip, agents/on_policy_first_visit_mc_gpu.py)
+at the same 1,048,576 games x 16 episodes per launch, in one process, HIP events around --launches L (200) back-to-back launches
+after a warm-up, --repeats R (7) times, the three taking turns within every repeat:
+  value_rollout   : pulse_blackjack_mc_rollout under the threshold-17 table -- the baseline, (a) above;
+  control_rollout : pulse_blackjack_mc_control_rollout under the same table: the same games, 34 instead of 32 cells per state;
+  control_train   : OnPolicyFirstVisitMCGPU.train -- roll-out under the agent's own epsilon-soft table + improve per batch.
+control_rollout is accepted at median <= value_rollout's median x (1 + value_rollout's (max - min) / median + 0.05).
 PULSE_LIB=<a twin from `make -C pulselib_amd/csrc bjmc-ablate ABL=n`> prices parts of (a)."""
 import json
 import math
@@ -81,9 +88,58 @@ def env_floor(dev, reps=20):
             "launches_per_episode": 13}
 
 
+def control(dev, launches=200, repeats=7):
+    import statistics
+    import torch
+    from pulselib_amd.agents import FirstVisitMonteCarloGPU, OnPolicyFirstVisitMCGPU
+    value = FirstVisitMonteCarloGPU(dev, 0.9, seed=1)
+    rollout = OnPolicyFirstVisitMCGPU(dev, 0.9, 0.1, seed=1)
+    train = OnPolicyFirstVisitMCGPU(dev, 0.9, 0.1, seed=1)
+    table = value._table(value.threshold_policy(17))
+    runs = {"value_rollout": lambda: value.learn_batch(GAMES, table, n_episodes=EPISODES_PER_LAUNCH),
+            "control_rollout": lambda: rollout.learn_batch(GAMES, n_episodes=EPISODES_PER_LAUNCH, policy=table),
+            "control_train": lambda: train.train(1, GAMES, EPISODES_PER_LAUNCH)}
+    for fn in runs.values():                                       # module load, and a policy that has left the uniform start
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name in runs}
+    for _ in range(repeats):
+        for name, fn in runs.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(launches):
+                fn()
+            b.record()
+            b.synchronize()
+            us[name].append(a.elapsed_time(b) * 1e3 / launches)
+    n = (3 + repeats * launches) * GAMES * EPISODES_PER_LAUNCH
+    stats = {"value_rollout": value.stats(), "control_rollout": rollout.stats(), "control_train": train.stats()}
+    assert all(st["games"] == n and st["capped"] == 0 for st in stats.values())
+    assert stats["value_rollout"] == stats["control_rollout"]      # the same games under the same table
+    out = {}
+    for name, t in us.items():
+        med = statistics.median(t)
+        out[name] = {"us_per_launch": med, "min": min(t), "max": max(t), "spread": (max(t) - min(t)) / med, "repeats_us": t,
+                     "ns_per_game": med * 1e3 / (GAMES * EPISODES_PER_LAUNCH), "episodes_per_sec": GAMES * EPISODES_PER_LAUNCH / (med * 1e-6),
+                     "actions_per_game": stats[name]["actions"] / stats[name]["games"], "win_rate": stats[name]["wins"] / stats[name]["games"]}
+    bound = out["value_rollout"]["us_per_launch"] * (1.0 + out["value_rollout"]["spread"] + 0.05)
+    out.update(launches=launches, repeats=repeats, games_per_launch=GAMES, episodes_per_launch=EPISODES_PER_LAUNCH,
+               control_over_value=out["control_rollout"]["us_per_launch"] / out["value_rollout"]["us_per_launch"],
+               train_over_value=out["control_train"]["us_per_launch"] / out["value_rollout"]["us_per_launch"],
+               bound_us=bound, control_within_bound=out["control_rollout"]["us_per_launch"] <= bound)
+    return out
+
+
 def main():
     import torch
     dev = torch.device("cuda", 0)
+    if "--control" in sys.argv:
+        arg = lambda flag, default: int(sys.argv[sys.argv.index(flag) + 1]) if flag in sys.argv else default
+        out = {"name": "blackjack_mc_control", "device": torch.cuda.get_device_name(0), "lib": os.environ.get("PULSE_LIB", "libpulse_hip.so")}
+        out.update(control(dev, max(20, arg("--launches", 200)), max(5, arg("--repeats", 7))))
+        print(json.dumps(out), flush=True)
+        return
     out = {"name": "blackjack_first_visit_mc", "device": torch.cuda.get_device_name(0), "lib": os.environ.get("PULSE_LIB", "libpulse_hip.so")}
     seconds = float(sys.argv[sys.argv.index("--seconds") + 1]) if "--seconds" in sys.argv else 1.0      # (short runs: under a counter pass)
     out["device_learner"] = device_learner(dev, seconds)
