@@ -492,6 +492,72 @@ int pulse_qtable_rollout_step(const PulseQTable* q, const PulseQTableScratch* sc
                               uint64_t agent_seed, uint64_t agent_step, uint64_t env_seed, uint64_t env_step, uint64_t board_id0,
                               int64_t* actions, int32_t* rewards, uint8_t* dones, int64_t* slots_io, void* stream);
 
+/* ---- 2048: on-policy first-visit Monte-Carlo control on the device (agents/MonteCarlo/OnPolicyFirstVisit.py:6-71 on the
+ * games of scripts/TFE/mctrain.py): whole games against a table policy in one launch, the backward first-visit pass into
+ * that table in a second one.  Stream-ordered: a round needs no host synchronisation.
+ *
+ * The table is an open-addressing hash table (linear probing) of 128-byte ENTRIES in HBM, 128-byte aligned, zeroed by the
+ * caller, capacity a power of two:
+ *   entry = { uint64 key (the board as 4-bit log2 tiles, pulse_qtable's key; 0 = free), int64 cnt[4], int64 sum[4], 56 spare bytes }
+ * sum[a] = the fixed-point sum of the first-visit returns of (state, a), llrint(G * 2^frac_bits) each; cnt[a] = their number;
+ *   q(s, a) = cnt[a] > 0 ? (double)sum[a] / (double)cnt[a] * 2^-frac_bits : 0.0   (the reference's defaultdict(float)).
+ * Integer adds only: the table read as a map key -> {cnt, sum} does not depend on scheduling (the slots' positions do).
+ * frac_bits: 0 .. the largest value <= 30 with G_max * 2^frac_bits * 2^32 < 2^62, G_max = 17 * min(max_steps, 1 / (1 - gamma))
+ * (17 bounds the reward of a step for n <= 4): room for 2^32 adds per cell.  gamma .9: 22.
+ *
+ * pulse_tfe_mc_rollout: one lane per game, from reset to the terminal step or to max_steps moves.  The games are the
+ * environment's own: reset and spawns draw from Philox4x32-10(env_seed, board_id0 + g, env_step), env_step 0 at reset and t + 1
+ * at move t, as pulse_tfe_reset / pulse_tfe_step.  The table is only READ (a lookup never inserts; at most
+ * PULSE_TFE_MC_MAX_PROBE slots are examined): the policy of a round is fixed.  The action at move t, from {x, y, ..} =
+ * Philox4x32-10(agent_seed, board_id0 + g, t):
+ *   no entry for the state, or (x >> 8) < floor(epsilon * 2^24)   ->   y >> 30;
+ *   otherwise the greedy action of the entry: a = 0..3 in order, a larger q replaces the best, an equal q replaces it iff bit
+ *   31 of word a - 1 of Philox4x32-10(tie_seed, key, round) is set (float64, IEEE division).
+ * Output, step-major: keys[t * n_games + g] = the state before move t, steps[t * n_games + g] = action | reward << 2 | first << 7,
+ * first = the action was not yet taken in the current run of identical boards (equal states of a game are consecutive: the
+ * tile sum rises at every step that changes the board or spawns).  Rows t >= lengths[g] are not written.  Per game: lengths
+ * (moves played), total_score (TFE.py:168), episode_reward (the sum of the rewards).  stats: device int64[8], added to:
+ * [0] moves played, [3] games cut at max_steps (this call); [1] first visits added, [2] first visits dropped (learn).
+ *
+ * pulse_tfe_mc_learn: one lane per game, t = lengths[g] - 1 .. 0, G = gamma * G + reward in float64 (from 0 at the end, also of
+ * a game that was cut); at a step with `first` set the entry is found or inserted (compare-and-swap on the key) and
+ * sum[a] += llrint(ldexp(G, frac_bits)), cnt[a] += 1.  A state with no room (PULSE_TFE_MC_MAX_PROBE slots, or all of them, taken)
+ * counts in stats[2] and is not learnt.
+ *
+ * PULSE_EINVAL, before anything is launched: n outside 2..4, epsilon or gamma outside [0, 1], a capacity that is no power of two,
+ * entries not 128-byte aligned, a null or misaligned buffer, n_games < 1, max_steps outside 1..65,535, frac_bits outside its
+ * bound, non-zero reserved fields. */
+#define PULSE_TFE_MC_ENTRY_BYTES 128
+#define PULSE_TFE_MC_MAX_PROBE   512
+#define PULSE_TFE_MC_R_MAX       17
+typedef struct PulseTfeMCRollout {
+    void* entries;
+    uint64_t capacity;
+    int32_t n_games, n, max_steps, frac_bits;
+    double gamma, epsilon;
+    uint64_t env_seed, agent_seed, tie_seed, board_id0, round;
+    uint64_t* keys;                     /* uint64[max_steps * n_games] */
+    uint8_t* steps;                     /* uint8[max_steps * n_games] */
+    int32_t* lengths;                   /* int32[n_games] */
+    int64_t* total_score;               /* int64[n_games] */
+    int32_t* episode_reward;            /* int32[n_games] */
+    int64_t* stats;                     /* int64[8] */
+    int64_t reserved0;
+} PulseTfeMCRollout;
+int pulse_tfe_mc_rollout(const PulseTfeMCRollout* o, void* stream);
+typedef struct PulseTfeMCLearn {
+    void* entries;
+    uint64_t capacity;
+    int32_t n_games, n, max_steps, frac_bits;
+    double gamma, epsilon;
+    const uint64_t* keys;
+    const uint8_t* steps;
+    const int32_t* lengths;
+    int64_t* stats;
+    int64_t reserved0;
+} PulseTfeMCLearn;
+int pulse_tfe_mc_learn(const PulseTfeMCLearn* o, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

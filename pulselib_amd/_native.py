@@ -119,6 +119,21 @@ class BlackjackMCImprove(C.Structure):
                 ("q", C.c_void_p), ("hit_prob", C.c_void_p), ("reserved0", C.c_int32), ("reserved1", C.c_int32)]
 
 
+# the 2048 Monte-Carlo table (include/pulse_env.h): 128-byte entries {uint64 key, int64 cnt[4], int64 sum[4], 56 spare bytes}
+TFE_MC_ENTRY_BYTES, TFE_MC_MAX_PROBE, TFE_MC_R_MAX = 128, 512, 17
+_TFE_MC_HEAD = [("entries", C.c_void_p), ("capacity", C.c_uint64), ("n_games", C.c_int32), ("n", C.c_int32), ("max_steps", C.c_int32),
+                ("frac_bits", C.c_int32), ("gamma", C.c_double), ("epsilon", C.c_double)]
+
+
+class TfeMCRollout(C.Structure):
+    _fields_ = _TFE_MC_HEAD + [(n, C.c_uint64) for n in ("env_seed", "agent_seed", "tie_seed", "board_id0", "round")] + [
+        (n, C.c_void_p) for n in ("keys", "steps", "lengths", "total_score", "episode_reward", "stats")] + [("reserved0", C.c_int64)]
+
+
+class TfeMCLearn(C.Structure):
+    _fields_ = _TFE_MC_HEAD + [(n, C.c_void_p) for n in ("keys", "steps", "lengths", "stats")] + [("reserved0", C.c_int64)]
+
+
 # every symbol include/pulse_env.h declares: (restype, argtypes)
 _P, _I32, _U32, _U64, _F32, _I64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_float, C.c_int64
 SYMBOLS = {
@@ -170,6 +185,8 @@ SYMBOLS = {
     "pulse_blackjack_mc_improve": (C.c_int, [_P, _P]),
     "pulse_tfe_reset": (C.c_int, [_P, _P, _I32, _I32, _U64, _U64, _P]),
     "pulse_tfe_step": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _U64, _U64, _U64, _P]),
+    "pulse_tfe_mc_rollout": (C.c_int, [_P, _P]),
+    "pulse_tfe_mc_learn": (C.c_int, [_P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

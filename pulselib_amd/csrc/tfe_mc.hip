@@ -1,0 +1,271 @@
+// tfe_mc.hip -- on-policy first-visit Monte-Carlo control for 2048 (agents/MonteCarlo/OnPolicyFirstVisit.py:6-71 on the games of
+// scripts/TFE/mctrain.py) as two launches per batch of games: pulse_tfe_mc_rollout and pulse_tfe_mc_learn.
+//
+// The reference steps one board through the interpreter, keeps the episode in a list and the pairs it has seen in a set.  Here one
+// lane plays one game from reset to the terminal step with the board in registers (tfe_device.h: the env kernels' own move, spawn
+// and game-over test, drawing from the env's own Philox stream, so game (env_seed, board id) IS the game pulse_tfe_reset +
+// pulse_tfe_step play under the same actions) against a policy read from a hash table of states in HBM, and writes one key and one
+// byte per move, step-major (a wavefront's stores of a step are one run of 512 + 64 bytes).  The table is read-only in that launch.
+// A second launch walks every game backwards and adds the first-visit returns into the table as fixed-point integers: the adds
+// commute, so the table as a map does not depend on the order of the atomics.
+//
+// First visits without a per-game set: a merge keeps the tile sum and a spawn adds to it, so the sum rises at every step unless the
+// board is full and the move changes nothing -- equal states of a game are consecutive, and "first visit of (s, a)" is "a was not
+// yet taken in the current run of identical boards": four bits per lane.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdio>
+
+#include "blackjack_device.h"
+#include "pulse_internal.h"
+#include "tfe_device.h"
+
+namespace {
+
+using namespace pulse_tfe;
+using pulse_bj::philox4x32;          // the one Philox4x32-10 of the env kernels (envs.hip takes it from the same header)
+using pulse_bj::U4;
+
+constexpr int kBlock = 256;
+constexpr uint64_t kMaxProbe = PULSE_TFE_MC_MAX_PROBE;
+
+// one table entry = one 128-byte line
+struct alignas(128) Entry { unsigned long long key; long long cnt[4]; long long sum[4]; unsigned long long spare[7]; };
+static_assert(sizeof(Entry) == PULSE_TFE_MC_ENTRY_BYTES, "entry layout is part of the ABI");
+
+// board -> key: 4 bits of log2(tile) per cell (0 = empty), row-major, cell 0 in the low nibble (qtable.hip's key)
+template <int NB>
+__device__ __forceinline__ uint64_t pack_cells(const int (&b)[NB * NB]) {
+    uint64_t key = 0;
+#pragma unroll
+    for (int i = 0; i < NB * NB; ++i) {
+        const int v = b[i];
+        const uint64_t e = v > 0 ? (uint64_t)min(31 - __clz(v), 15) : 0ull;
+        key |= e << (4 * i);
+    }
+    return key;
+}
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
+    return x;
+}
+
+// Slot of `key`, or -1: absent.  Never inserts.  At most kMaxProbe slots are examined -- the limit find_or_insert places under, so
+// whatever it placed is found.
+__device__ __forceinline__ long long find(const Entry* table, uint64_t slots, uint64_t key) {
+    const uint64_t h = mix64(key) & (slots - 1);
+    const uint64_t limit = slots < kMaxProbe ? slots : kMaxProbe;
+    for (uint64_t probe = 0; probe < limit; ++probe) {
+        const uint64_t s = (h + probe) & (slots - 1);
+        const unsigned long long cur = table[s].key;
+        if (cur == key) return (long long)s;
+        if (cur == 0ull) return -1;
+    }
+    return -1;
+}
+// Slot of `key`, inserted (counts and sums already zero) if absent.  -1 = no room within the probe limit.
+__device__ __forceinline__ long long find_or_insert(Entry* table, uint64_t slots, uint64_t key) {
+    const uint64_t h = mix64(key) & (slots - 1);
+    const uint64_t limit = slots < kMaxProbe ? slots : kMaxProbe;
+    for (uint64_t probe = 0; probe < limit; ++probe) {
+        const uint64_t s = (h + probe) & (slots - 1);
+        unsigned long long cur = table[s].key;
+        if (cur == key) return (long long)s;
+        if (cur == 0ull) {
+            cur = atomicCAS(&table[s].key, 0ull, (unsigned long long)key);
+            if (cur == 0ull || cur == key) return (long long)s;
+        }
+    }
+    return -1;
+}
+
+// The greedy action of an entry (OnPolicyFirstVisit.py:52-62): the actions in order, a larger q replaces the best, an equal q
+// replaces it on the coin of that action.  The coins are constant per (state, round); they are drawn only where two q are equal.
+__device__ __forceinline__ int greedy_action(const Entry& e, uint64_t key, uint64_t tie_seed, uint64_t round, double inv_scale) {
+    double q[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const long long n = e.cnt[a];
+        q[a] = n > 0 ? __dmul_rn(__ddiv_rn((double)e.sum[a], (double)n), inv_scale) : 0.0;   // an unseen pair reads 0.0 (defaultdict(float))
+    }
+    const bool any_tie = q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3];
+    U4 coins{0u, 0u, 0u, 0u};
+    if (any_tie) coins = philox4x32(tie_seed, key, round);
+    const uint32_t coin[3] = {coins.x >> 31, coins.y >> 31, coins.z >> 31};
+    int best = 0;
+    double best_q = q[0];
+#pragma unroll
+    for (int a = 1; a < 4; ++a) {
+        const bool take = q[a] > best_q || (q[a] == best_q && coin[a - 1] != 0u);
+        best = take ? a : best;
+        best_q = q[a] > best_q ? q[a] : best_q;
+    }
+    return best;
+}
+
+// Per-workgroup counters, added to the caller's stats once per workgroup.  Called by every thread of the workgroup.
+__device__ __forceinline__ void add_stats(unsigned long long* wg, int64_t* stats, int at0, unsigned long long v0, int at1, unsigned long long v1) {
+    if (v0) atomicAdd(&wg[0], v0);                        // LDS
+    if (v1) atomicAdd(&wg[1], v1);
+    __syncthreads();
+    if (threadIdx.x == 0 && wg[0]) atomicAdd(reinterpret_cast<unsigned long long*>(stats) + at0, wg[0]);
+    if (threadIdx.x == 1 && wg[1]) atomicAdd(reinterpret_cast<unsigned long long*>(stats) + at1, wg[1]);
+}
+
+template <int NB>
+__global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMCRollout o, uint32_t eps_q24, double inv_scale) {
+    __shared__ unsigned long long wg[2];
+    if (threadIdx.x < 2) wg[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int g = blockIdx.x * kBlock + threadIdx.x;
+    const size_t B = (size_t)o.n_games;
+    unsigned long long n_moves = 0ull, n_cut = 0ull;
+    if (g < o.n_games) {
+        const Entry* table = static_cast<const Entry*>(o.entries);
+        const uint64_t id = o.board_id0 + (uint64_t)g;
+        int b[NB * NB];
+#pragma unroll
+        for (int i = 0; i < NB * NB; ++i) b[i] = 0;
+        {                                                                               // TFE.py:143-149, as pulse_tfe_reset
+            const U4 rnd = philox4x32(o.env_seed, id, 0ull);
+            tfe_spawn<NB>(b, rnd.x, rnd.y);
+            tfe_spawn<NB>(b, rnd.z, rnd.w);
+        }
+        int64_t total = 0;
+        int ep_reward = 0, length = 0;
+        uint32_t taken = 0u;                              // bit a: action a was taken in the current run of identical boards
+        uint64_t prev_key = 0ull;                         // (no live board packs to 0)
+        bool over = false;
+        for (int t = 0; t < o.max_steps && !over; ++t) {
+            const uint64_t key = pack_cells<NB>(b);
+            taken = key == prev_key ? taken : 0u;
+            prev_key = key;
+            const U4 r = philox4x32(o.agent_seed, id, (uint64_t)t);
+            const long long s = find(table, o.capacity, key);
+            int a = (int)(r.y >> 30);                     // no entry: the reference's uniform default policy; or the epsilon branch
+            if (s >= 0 && (r.x >> 8) >= eps_q24) a = greedy_action(table[s], key, o.tie_seed, o.round, inv_scale);
+            const int score = tfe_move<NB>(b, a);                                      // TFE.py:154-178
+            const U4 rnd = philox4x32(o.env_seed, id, (uint64_t)t + 1ull);
+            tfe_spawn<NB>(b, rnd.x, rnd.y);                                            // TFE.py:182 (always)
+            over = tfe_over<NB>(b);                                                    // TFE.py:48-67
+            const int reward = score > 0 ? 31 - __clz(score) : 0;                      // TFE.py:185-187 (<= 17 for n <= 4: five bits)
+            const uint32_t first = ((taken >> a) & 1u) ^ 1u;
+            taken |= 1u << a;
+            o.keys[(size_t)t * B + (size_t)g] = key;
+            o.steps[(size_t)t * B + (size_t)g] = (uint8_t)((uint32_t)a | ((uint32_t)reward & 31u) << 2 | first << 7);
+            total += score; ep_reward += reward;
+            length = t + 1;
+        }
+        o.lengths[g] = length;
+        o.total_score[g] = total;
+        o.episode_reward[g] = ep_reward;
+        n_moves = (unsigned long long)length;
+        n_cut = over ? 0ull : 1ull;
+    }
+    add_stats(wg, o.stats, 0, n_moves, 3, n_cut);
+}
+
+__global__ __launch_bounds__(kBlock) void tfe_mc_learn_kernel(const PulseTfeMCLearn o) {
+    __shared__ unsigned long long wg[2];
+    if (threadIdx.x < 2) wg[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int g = blockIdx.x * kBlock + threadIdx.x;
+    const size_t B = (size_t)o.n_games;
+    unsigned long long n_added = 0ull, n_dropped = 0ull;
+    if (g < o.n_games) {
+        Entry* table = static_cast<Entry*>(o.entries);
+        int length = o.lengths[g];
+        length = length < 0 ? 0 : (length > o.max_steps ? o.max_steps : length);       // (the buffers hold max_steps rows)
+        double G = 0.0;
+        for (int t = length - 1; t >= 0; --t) {
+            const uint32_t st = o.steps[(size_t)t * B + (size_t)g];
+            G = __dadd_rn(__dmul_rn(o.gamma, G), (double)((st >> 2) & 31u));           // OnPolicyFirstVisit.py:28: G = gamma * G + reward
+            if (st & 0x80u) {
+                const uint64_t key = o.keys[(size_t)t * B + (size_t)g];
+                const long long s = key ? find_or_insert(table, o.capacity, key) : -1;
+                if (s >= 0) {
+                    const int a = (int)(st & 3u);
+                    atomicAdd(reinterpret_cast<unsigned long long*>(&table[s].sum[a]), (unsigned long long)llrint(ldexp(G, o.frac_bits)));
+                    atomicAdd(reinterpret_cast<unsigned long long*>(&table[s].cnt[a]), 1ull);
+                    n_added += 1ull;
+                } else {
+                    n_dropped += 1ull;
+                }
+            }
+        }
+    }
+    add_stats(wg, o.stats, 1, n_added, 2, n_dropped);
+}
+
+int fail_named(const char* name, const char* msg) {
+    char text[256];
+    std::snprintf(text, sizeof text, "%s: %s", name, msg);
+    return pulse::fail(PULSE_EINVAL, text);
+}
+
+// The largest frac_bits <= 30 with G_max * 2^frac_bits * 2^32 < 2^62, G_max = r_max * min(max_steps, 1 / (1 - gamma)); -1 = none.
+int max_frac_bits(double gamma, int max_steps) {
+    const double horizon = 1.0 / (1.0 - gamma);                                        // (gamma = 1: inf)
+    const double g_max = (double)PULSE_TFE_MC_R_MAX * (horizon < (double)max_steps ? horizon : (double)max_steps);
+    for (int f = 30; f >= 0; --f)
+        if (std::ldexp(g_max, f) < 1073741824.0) return f;                             // 2^30
+    return -1;
+}
+
+// The checks both entry points share: their structs begin with the same fields.
+template <class O>
+int check_common(const O* o, const char* name) {
+    if (!o) return fail_named(name, "options are null");
+    if (!o->entries) return fail_named(name, "entries is null");
+    if ((uintptr_t)o->entries & (PULSE_TFE_MC_ENTRY_BYTES - 1)) return fail_named(name, "entries must be 128-byte aligned");
+    if (o->capacity == 0 || (o->capacity & (o->capacity - 1))) return fail_named(name, "capacity must be a power of two");
+    if (o->n < 2 || o->n > 4) return fail_named(name, "board side must be 2..4 (64-bit state key)");
+    if (o->n_games < 1) return fail_named(name, "n_games must be positive");
+    if (o->max_steps < 1 || o->max_steps > 65535) return fail_named(name, "max_steps must be in 1..65535");
+    if (!(o->gamma >= 0.0 && o->gamma <= 1.0)) return fail_named(name, "gamma must be in [0, 1]");
+    if (!(o->epsilon >= 0.0 && o->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
+    if (o->frac_bits < 0 || o->frac_bits > max_frac_bits(o->gamma, o->max_steps))
+        return fail_named(name, "frac_bits outside 0 .. the largest value with 17 * min(max_steps, 1 / (1 - gamma)) * 2^frac_bits < 2^30");
+    if (!o->keys) return fail_named(name, "keys is null");
+    if (!o->steps) return fail_named(name, "steps is null");
+    if (!o->lengths) return fail_named(name, "lengths is null");
+    if (!o->stats) return fail_named(name, "stats is null");
+    if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->stats & 7u)) return fail_named(name, "keys / stats must be 8-byte aligned");
+    if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
+    if (o->reserved0 != 0) return fail_named(name, "reserved0 must be 0 (zero-initialise the struct)");
+    return 0;
+}
+
+int finish_launch(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return pulse::fail_hip((int)e, what);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int pulse_tfe_mc_rollout(const PulseTfeMCRollout* o, void* stream) {
+    const char* name = "pulse_tfe_mc_rollout";
+    if (int rc = check_common(o, name)) return rc;
+    if (!o->total_score) return fail_named(name, "total_score is null");
+    if (!o->episode_reward) return fail_named(name, "episode_reward is null");
+    if ((uintptr_t)o->total_score & 7u) return fail_named(name, "total_score must be 8-byte aligned");
+    if ((uintptr_t)o->episode_reward & 3u) return fail_named(name, "episode_reward must be 4-byte aligned");
+    const uint32_t eps_q24 = (uint32_t)std::floor(o->epsilon * 16777216.0);            // once, here: the kernel compares integers
+    const double inv_scale = std::ldexp(1.0, -o->frac_bits);
+    const dim3 grid((unsigned)((o->n_games + kBlock - 1) / kBlock)), block(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+    switch (o->n) {
+    case 2: hipLaunchKernelGGL(tfe_mc_rollout_kernel<2>, grid, block, 0, st, *o, eps_q24, inv_scale); break;
+    case 3: hipLaunchKernelGGL(tfe_mc_rollout_kernel<3>, grid, block, 0, st, *o, eps_q24, inv_scale); break;
+    default: hipLaunchKernelGGL(tfe_mc_rollout_kernel<4>, grid, block, 0, st, *o, eps_q24, inv_scale);
+    }
+    return finish_launch("pulse_tfe_mc_rollout launch");
+}
+
+extern "C" int pulse_tfe_mc_learn(const PulseTfeMCLearn* o, void* stream) {
+    if (int rc = check_common(o, "pulse_tfe_mc_learn")) return rc;
+    hipLaunchKernelGGL(tfe_mc_learn_kernel, dim3((unsigned)((o->n_games + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, *o);
+    return finish_launch("pulse_tfe_mc_learn launch");
+}

@@ -1,0 +1,56 @@
+"""On-policy first-visit Monte-Carlo control on 2048 with the whole loop on the device (agents/tfe_on_policy_mc_gpu.py): every
+round is a roll-out launch of `--tables` whole games against the table's policy and a learn launch into that table.  Defaults:
+GAMMA 0.9, EPSILON 0.1, NUM_EPISODES 1,000,000 on a 3 x 3 board (the reference's scripts/TFE/mctrain.py with
+config/on_policy_first_visit_monte_carlo.yaml, which `--config PATH` reads as it is).  Per logging interval it prints what
+mctrain.py:54 prints: the average episode reward, the final score and the steps per second -- here of the rounds since the last
+line, each line costing one synchronisation."""
+from __future__ import annotations
+
+import argparse
+import time
+
+import torch
+
+from ..agents import OnPolicyFirstVisitMCTFEGPU
+
+
+def run(device, rounds, tables=65536, board=3, gamma=0.9, epsilon=0.1, seed=0, capacity=1 << 22, max_steps=1024, log_every=1, out=print):
+    agent = OnPolicyFirstVisitMCTFEGPU(device, tables, board_size=board, gamma=gamma, epsilon=epsilon, capacity=capacity, max_steps=max_steps,
+                                       seed=seed)
+    steps_before, t0 = 0, time.perf_counter()
+    for r in range(rounds):
+        agent.learn_batch()
+        if (r + 1) % log_every == 0 or r + 1 == rounds:
+            reward = agent.episode_reward.double().mean().item()            # (synchronises)
+            score, best = agent.total_score.double().mean().item(), int(agent.total_score.max().item())
+            st, now = agent.stats(), time.perf_counter()
+            out(f"Round {r}: episodes {(r + 1) * tables}, Avg episode reward: {reward:.2f}, Avg final score: {score:.2f}, Highest: {best}, "
+                f"Steps/sec: {(st['steps'] - steps_before) / (now - t0):.0f}, dropped {st['dropped']}, truncated {st['truncated']}")
+            steps_before, t0 = st["steps"], now
+    return agent
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--config", help="a YAML file with GAMMA, EPSILON and NUM_EPISODES (the reference's own file can be passed)")
+    ap.add_argument("--tables", type=int, default=65536, help="games per round (one policy improvement per round)")
+    ap.add_argument("--board", type=int, default=3, help="board side, 2..4")
+    ap.add_argument("--rounds", type=int, help="default: NUM_EPISODES / tables, rounded up")
+    ap.add_argument("--capacity", type=int, default=1 << 22, help="table slots, a power of two (128 bytes each)")
+    ap.add_argument("--max-steps", type=int, default=1024)
+    ap.add_argument("--log-every", type=int, default=1, help="rounds per printed line")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    gamma, epsilon, episodes = 0.9, 0.1, 1_000_000
+    if args.config:
+        import yaml
+        with open(args.config) as fh:
+            cfg = yaml.safe_load(fh)
+        gamma, epsilon, episodes = float(cfg.get("GAMMA", gamma)), float(cfg.get("EPSILON", epsilon)), int(cfg.get("NUM_EPISODES", episodes))
+    rounds = args.rounds if args.rounds is not None else max(1, -(-episodes // args.tables))
+    agent = run(torch.device("cuda"), rounds, args.tables, args.board, gamma, epsilon, args.seed, args.capacity, args.max_steps, args.log_every)
+    print(f"{rounds * args.tables} games in {agent.round} rounds, gamma {gamma}, epsilon {epsilon}: {len(agent.table())} states stored")
+
+
+if __name__ == "__main__":
+    main()
