@@ -243,6 +243,17 @@ def check(rc: int, what: str = "") -> None:
         raise PulseError(f"{what}: {msg} (code {rc})")
 
 
+def gpu_device(device, who: str):
+    """`device` as a torch.device with its index filled in; `who` (a class of the package) refuses anything but a 'cuda' device."""
+    import torch
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"pulselib_amd.{who} runs on an MI355X ('cuda' device); got '{device}'. No CPU fallback.")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
 def current_stream(device) -> int:
     import torch
     return torch.cuda.current_stream(device).cuda_stream

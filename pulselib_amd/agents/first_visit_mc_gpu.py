@@ -62,22 +62,15 @@ class HitPolicy:
         self.key, self.table = key, np.ascontiguousarray(table, dtype=np.float32)
 
 
-class FirstVisitMonteCarloGPU:
-    """`learn_batch` plays n_games x n_episodes games under a fixed policy and adds their first visits to the device
-    histogram; `returns` / `values` read it back in the shapes of the CPU class (agents/first_visit_mc.py)."""
+class _BlackjackMCAgent:
+    """What the two Blackjack Monte-Carlo agents share: the env's counters, the launch's buffers, the policy tables and the
+    roll-out launch itself.  A subclass owns `acc`, its histogram."""
 
-    def __init__(self, device, gamma: float, seed: int = 0):
+    def __init__(self, device, seed: int):
         import torch
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"pulselib_amd.FirstVisitMonteCarloGPU runs on an MI355X ('cuda' device); got '{device}'. No CPU fallback.")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = device = _native.gpu_device(device, type(self).__name__)
         self._lib = _native.lib()
-        self.device = device
-        self.gamma = float(gamma)
         self.seed, self.episode = int(seed), 0            # the env's counters: episode e is BlackJack(seed).reset() number e
-        self.acc = torch.zeros(ACC_LEN, dtype=torch.int64, device=device)
         self.counters = torch.zeros(4, dtype=torch.int64, device=device)
         self.last_trace = None                            # int8[n_episodes * n_games, 16] of the last learn_batch(trace=True)
         self._policies = {}
@@ -106,15 +99,13 @@ class FirstVisitMonteCarloGPU:
         return policy
 
     # ------------------------------------------------------------------ the launch
-    def learn_batch(self, n_games: int, policy, n_episodes: int = 1, decks=None, trace: bool = False, max_blocks: int = 0):
-        """One launch, no host sync.  policy: a device fp32[N_STATES] table, threshold_policy(n) or uniform_policy().
-        decks: None = the env's device shuffle, else int32[n_episodes * n_games, 52] used as they are."""
+    def _rollout(self, struct_type, symbol: str, table, n_games: int, n_episodes: int, decks, trace: bool, max_blocks: int):
+        """One launch of `symbol` under the device table `table`, no host sync; its first visits are added to `acc`."""
         import torch
-        policy = self._table(policy)
         n_games, n_episodes = int(n_games), int(n_episodes)
-        o = _native.BlackjackMC()
+        o = struct_type()
         o.n_games, o.n_episodes, o.seed, o.episode = n_games, n_episodes, self.seed, self.episode
-        o.hit_prob, o.acc, o.stats, o.max_blocks = policy.data_ptr(), self.acc.data_ptr(), self.counters.data_ptr(), int(max_blocks)
+        o.hit_prob, o.acc, o.stats, o.max_blocks = table.data_ptr(), self.acc.data_ptr(), self.counters.data_ptr(), int(max_blocks)
         src = None
         if decks is not None:
             src = torch.as_tensor(decks).to(device=self.device, dtype=torch.int32).contiguous()
@@ -124,9 +115,29 @@ class FirstVisitMonteCarloGPU:
         if trace:
             self.last_trace = torch.empty((max(n_games * n_episodes, 0), MAX_ACTIONS), dtype=torch.int8, device=self.device)
             o.trace = self.last_trace.data_ptr()
-        _native.check(self._lib.pulse_blackjack_mc_rollout(C.byref(o), _native.current_stream(self.device)), "pulse_blackjack_mc_rollout")
+        _native.check(getattr(self._lib, symbol)(C.byref(o), _native.current_stream(self.device)), symbol)
         self.episode += n_episodes
         return self
+
+    def stats(self) -> dict:
+        games, wins, actions, capped = self.counters.cpu().tolist()
+        return {"games": games, "wins": wins, "actions": actions, "capped": capped}
+
+
+class FirstVisitMonteCarloGPU(_BlackjackMCAgent):
+    """`learn_batch` plays n_games x n_episodes games under a fixed policy and adds their first visits to the device
+    histogram; `returns` / `values` read it back in the shapes of the CPU class (agents/first_visit_mc.py)."""
+
+    def __init__(self, device, gamma: float, seed: int = 0):
+        import torch
+        super().__init__(device, seed)
+        self.gamma = float(gamma)
+        self.acc = torch.zeros(ACC_LEN, dtype=torch.int64, device=self.device)
+
+    def learn_batch(self, n_games: int, policy, n_episodes: int = 1, decks=None, trace: bool = False, max_blocks: int = 0):
+        """One launch, no host sync.  policy: a device fp32[N_STATES] table, threshold_policy(n) or uniform_policy().
+        decks: None = the env's device shuffle, else int32[n_episodes * n_games, 52] used as they are."""
+        return self._rollout(_native.BlackjackMC, "pulse_blackjack_mc_rollout", self._table(policy), n_games, n_episodes, decks, trace, max_blocks)
 
     # ------------------------------------------------------------------ read-back (the only syncs)
     def histogram(self) -> np.ndarray:
@@ -139,10 +150,6 @@ class FirstVisitMonteCarloGPU:
     @property
     def values(self) -> dict:
         return {s: total / count for s, (total, count) in self.returns.items()}
-
-    def stats(self) -> dict:
-        games, wins, actions, capped = self.counters.cpu().tolist()
-        return {"games": games, "wins": wins, "actions": actions, "capped": capped}
 
     def clear(self):
         self.acc.zero_()

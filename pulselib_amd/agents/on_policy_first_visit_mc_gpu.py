@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _native
-from .first_visit_mc_gpu import MAX_ACTIONS, N_STATES, HitPolicy, FirstVisitMonteCarloGPU, state_from_index, state_index  # noqa: F401
+from .first_visit_mc_gpu import MAX_ACTIONS, N_STATES, HitPolicy, FirstVisitMonteCarloGPU, _BlackjackMCAgent, state_from_index, state_index  # noqa: F401
 
 CELLS = _native.BJ_MCC_CELLS                              # per state: hit x k 0..15 x sign, then stand x sign
 ACC_LEN = _native.BJ_MCC_ACC_LEN
@@ -72,55 +72,25 @@ def improve_on_host(hist, gamma: float, epsilon: float, hit_prob, tie_stand):
     return q, out
 
 
-class OnPolicyFirstVisitMCGPU:
+class OnPolicyFirstVisitMCGPU(_BlackjackMCAgent):
     """`learn_batch` plays n_games x n_episodes games under the agent's table and adds their pair first visits to the device
     histogram; `improve` makes the table epsilon-soft around the greedy actions of that histogram; `train` alternates the two."""
 
     def __init__(self, device, gamma: float, epsilon: float, seed: int = 0):
         import torch
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"pulselib_amd.OnPolicyFirstVisitMCGPU runs on an MI355X ('cuda' device); got '{device}'. No CPU fallback.")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        self._lib = _native.lib()
-        self.device = device
+        super().__init__(device, seed)
         self.gamma, self.epsilon = float(gamma), float(epsilon)
-        self.seed, self.episode, self.round = int(seed), 0, 0              # round: the number of improvements so far
-        self.acc = torch.zeros(ACC_LEN, dtype=torch.int64, device=device)
-        self.counters = torch.zeros(4, dtype=torch.int64, device=device)
-        self.hit_prob = torch.full((N_STATES,), 0.5, dtype=torch.float32, device=device)   # the reference's uniform default
-        self.q_table = torch.zeros((N_STATES, 2), dtype=torch.float64, device=device)      # written by improve()
-        self.last_trace = None
-        self._policies = {}
-
-    threshold_policy = staticmethod(FirstVisitMonteCarloGPU.threshold_policy)
-    uniform_policy = staticmethod(FirstVisitMonteCarloGPU.uniform_policy)
-    _table = FirstVisitMonteCarloGPU._table
+        self.round = 0                                                     # the number of improvements so far
+        self.acc = torch.zeros(ACC_LEN, dtype=torch.int64, device=self.device)
+        self.hit_prob = torch.full((N_STATES,), 0.5, dtype=torch.float32, device=self.device)   # the reference's uniform default
+        self.q_table = torch.zeros((N_STATES, 2), dtype=torch.float64, device=self.device)      # written by improve()
 
     # ------------------------------------------------------------------ the launches
     def learn_batch(self, n_games: int, n_episodes: int = 1, decks=None, trace: bool = False, max_blocks: int = 0, policy=None):
         """One roll-out launch, no host sync, under the agent's own table -- or under `policy` (a device fp32[N_STATES] table,
         threshold_policy(n) or uniform_policy()).  decks: None = the env's device shuffle, else int32[n_episodes * n_games, 52]."""
-        import torch
         table = self.hit_prob if policy is None else self._table(policy)
-        n_games, n_episodes = int(n_games), int(n_episodes)
-        o = _native.BlackjackMCControl()
-        o.n_games, o.n_episodes, o.seed, o.episode = n_games, n_episodes, self.seed, self.episode
-        o.hit_prob, o.acc, o.stats, o.max_blocks = table.data_ptr(), self.acc.data_ptr(), self.counters.data_ptr(), int(max_blocks)
-        src = None
-        if decks is not None:
-            src = torch.as_tensor(decks).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(src.shape) != (n_games * n_episodes, 52):
-                raise ValueError(f"decks must have shape {(n_games * n_episodes, 52)}, got {tuple(src.shape)}")
-            o.decks_src = src.data_ptr()
-        if trace:
-            self.last_trace = torch.empty((max(n_games * n_episodes, 0), MAX_ACTIONS), dtype=torch.int8, device=self.device)
-            o.trace = self.last_trace.data_ptr()
-        _native.check(self._lib.pulse_blackjack_mc_control_rollout(C.byref(o), _native.current_stream(self.device)),
-                      "pulse_blackjack_mc_control_rollout")
-        self.episode += n_episodes
-        return self
+        return self._rollout(_native.BlackjackMCControl, "pulse_blackjack_mc_control_rollout", table, n_games, n_episodes, decks, trace, max_blocks)
 
     def improve(self):
         """One launch: q(s, a) of the histogram so far into `q_table`, and `hit_prob` epsilon-soft around its greedy actions."""
@@ -167,10 +137,6 @@ class OnPolicyFirstVisitMCGPU:
     def greedy_policy(self) -> dict:
         """{state: HIT or STAND} of every state visited: the action the table favours."""
         return {s: HIT if p[0] > p[1] else STAND for s, p in self.policy.items()}
-
-    def stats(self) -> dict:
-        games, wins, actions, capped = self.counters.cpu().tolist()
-        return {"games": games, "wins": wins, "actions": actions, "capped": capped}
 
     def clear(self):
         """A new estimate: histogram, counters and q emptied, the table uniform again, round 0."""

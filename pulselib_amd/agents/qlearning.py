@@ -23,11 +23,7 @@ ENTRY_WORDS = 8          # int64 words per 64-byte entry: key, q[0..3] (as float
 
 class QLearningBatch:
     def __init__(self, device, batch_size, board_size=4, config=None, private_tables=False, slots=None, seed=0, board_id0=0):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"pulselib_amd.QLearningBatch runs on an MI355X ('cuda' device); got '{device}'. No CPU fallback.")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _native.gpu_device(device, "QLearningBatch")
         config = config or {}
         self.alpha = float(config.get("ALPHA", 0.1))          # config/qlearning.yaml:6-8
         self.gamma = float(config.get("GAMMA", 0.99))

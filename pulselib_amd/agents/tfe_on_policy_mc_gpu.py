@@ -131,11 +131,7 @@ class OnPolicyFirstVisitMCTFEGPU:
 
     def __init__(self, device, n_games, board_size=3, gamma=.9, epsilon=.1, capacity=1 << 22, max_steps=1024, seed=0, board_id0=0):
         import torch
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"pulselib_amd.OnPolicyFirstVisitMCTFEGPU runs on an MI355X ('cuda' device); got '{device}'. No CPU fallback.")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _native.gpu_device(device, "OnPolicyFirstVisitMCTFEGPU")
         if not 2 <= int(board_size) <= 4:
             raise ValueError("board_size must be 2..4 (the state key holds 16 cells)")
         if int(capacity) < 1 or int(capacity) & (int(capacity) - 1):

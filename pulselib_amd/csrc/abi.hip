@@ -1,4 +1,4 @@
-// abi.hip -- error reporting and version of libpulse_hip.so (include/pulse_env.h).
+// abi.hip -- error reporting, the launch helpers every unit shares, and version of libpulse_hip.so (include/pulse_env.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -42,6 +42,31 @@ LdsLaunch launch_lds(const void* fn, unsigned grid, unsigned block, void** param
 }
 
 }  // namespace pulse
+
+// ---- the tail of an entry point, one copy for every unit (pulse_internal.h)
+int pulse::fail_named(const char* name, const char* msg) {
+    char text[256];
+    std::snprintf(text, sizeof text, "%s: %s", name, msg);
+    return fail(PULSE_EINVAL, text);
+}
+
+int pulse::finish_launch(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail_hip((int)e, what);
+    return 0;
+}
+
+int pulse::device_cus() {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 256; }
+    if (cus[dev] == 0) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus[dev] = prop.multiProcessorCount;
+        else { (void)hipGetLastError(); cus[dev] = 256; }
+    }
+    return cus[dev];
+}
 
 extern "C" {
 

@@ -1,5 +1,5 @@
 // blackjack_device.h -- device code shared by the Blackjack env kernels (envs.hip) and the fused first-visit Monte-Carlo
-// roll-out (blackjack_mc.hip): the Philox4x32-10 generator, the deck shuffle and the card arithmetic of
+// roll-out (blackjack_mc.hip): the deck shuffle (on the library's Philox4x32-10, philox_device.h) and the card arithmetic of
 // environments/blackjack/blackjack.py (cited as :line).  Both translation units play the same game from the same
 // (seed, game, episode) because they run these functions, not restatements of them.
 #pragma once
@@ -7,24 +7,13 @@
 
 #include <cstdint>
 
+#include "philox_device.h"
+
 namespace pulse_bj {
 
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32(uint64_t seed, uint64_t subseq, uint64_t offset) {
-    uint32_t c0 = (uint32_t)offset, c1 = (uint32_t)(offset >> 32), c2 = (uint32_t)subseq, c3 = (uint32_t)(subseq >> 32);
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        // one 32 x 32 -> 64 multiply per word pair (v_mad_u64_u32): 32-bit integer multiplies are the slow vector instructions here
-        const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0, p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
-        const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0, h1 = (uint32_t)(p1 >> 32), l1 = (uint32_t)p1;
-        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{c0, c1, c2, c3};
-}
-__device__ __forceinline__ uint32_t u4_word(const U4& r, int i) { return i == 0 ? r.x : i == 1 ? r.y : i == 2 ? r.z : r.w; }
+using pulse_philox::U4;
+using pulse_philox::philox4x32;
+using pulse_philox::u4_word;
 
 __device__ __forceinline__ int bj_rank(int card) { const int r = card % 13 + 1; return r > 10 ? 10 : r; }
 

@@ -184,23 +184,8 @@ __global__ __launch_bounds__(kBlock) void blackjack_mc_kernel(const PulseBlackja
         atomicAdd(reinterpret_cast<unsigned long long*>(o.stats) + threadIdx.x, wg_stats[threadIdx.x]);
 }
 
-int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return 256; }
-    if (cus[dev] == 0) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus[dev] = prop.multiProcessorCount;
-        else { (void)hipGetLastError(); cus[dev] = 256; }
-    }
-    return cus[dev];
-}
-
-int fail_named(const char* name, const char* msg) {
-    char text[256];
-    std::snprintf(text, sizeof text, "%s: %s", name, msg);
-    return pulse::fail(PULSE_EINVAL, text);
-}
+using pulse::device_cus;
+using pulse::fail_named;
 
 // Both roll-out entry points: the checks, the grid and the launch.  (PulseBlackjackMCControl has PulseBlackjackMC's fields.)
 template <bool CONTROL>
@@ -305,7 +290,5 @@ extern "C" int pulse_blackjack_mc_improve(const PulseBlackjackMCImprove* o, void
     if (!std::isfinite(o->gamma)) return fail_named(name, "gamma must be finite");
     if (o->reserved0 != 0 || o->reserved1 != 0) return fail_named(name, "reserved0 / reserved1 must be 0 (zero-initialise the struct)");
     blackjack_mc_improve_kernel<<<PULSE_BJ_MC_STATES / 256, 256, 0, (hipStream_t)stream>>>(*o);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pulse::fail_hip(e, "pulse_blackjack_mc_improve launch");
-    return 0;
+    return pulse::finish_launch("pulse_blackjack_mc_improve launch");
 }

@@ -327,11 +327,7 @@ __global__ __launch_bounds__(kBlock) void particle2d_step_kernel(float4* __restr
     terminated[i] = (dist < 0.1f) || (st >= max_steps);                                 // :29
 }
 
-int finish_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pulse::fail_hip((int)e, what);
-    return 0;
-}
+using pulse::finish_launch;
 inline dim3 grid1(int n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
 int check_bj(const PulseBlackjackView* v) {

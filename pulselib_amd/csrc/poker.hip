@@ -439,12 +439,6 @@ int check_view(const PulsePokerView* v, const char* who) {
     return 0;
 }
 
-int finish_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip((int)e, what);
-    return 0;
-}
-
 uint64_t pack_types(const uint8_t* agent_types, int n_players) {
     uint64_t packed = 0;
     for (int i = 0; i < n_players && i < 16; ++i) packed |= (uint64_t)(agent_types[i] & 15u) << (4 * i);

@@ -6,6 +6,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "philox_device.h"
 #include "pulse_internal.h"
 
 namespace pulse_dev {
@@ -60,24 +61,11 @@ __device__ __forceinline__ bool board_matches(uint32_t tag, int n_cards, int b0,
     return (tag & kPreBoardValid) && in_range && ((pack_board(b0, b1, b2, b3, b4) ^ tag) & mask) == 0;
 }
 
-// ---------------------------------------------------------------- Philox4x32-10
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32(uint64_t seed, uint64_t subseq, uint64_t offset) {
-    uint32_t c0 = (uint32_t)offset, c1 = (uint32_t)(offset >> 32), c2 = (uint32_t)subseq, c3 = (uint32_t)(subseq >> 32);
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        // one 32x32 -> 64 multiply per word pair (v_mad_u64_u32): 32-bit integer multiplies are the slow VALU ops here
-        const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0, p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
-        const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0, h1 = (uint32_t)(p1 >> 32), l1 = (uint32_t)p1;
-        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{c0, c1, c2, c3};
-}
-__device__ __forceinline__ int rand_below(uint32_t r, int n) { return (int)__umulhi(r, (uint32_t)n); }
-__device__ __forceinline__ float rand_unit(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
+// ---------------------------------------------------------------- Philox4x32-10 (philox_device.h)
+using pulse_philox::U4;
+using pulse_philox::philox4x32;
+using pulse_philox::rand_below;
+using pulse_philox::rand_unit;
 
 // The scripted opponents' draw for (table, step): one Philox call serves two consecutive steps --
 // call = Philox4x32-10(seed, table id, step >> 1); an even step takes words (x, y), an odd step (z, w).
@@ -278,6 +266,5 @@ __device__ __forceinline__ void sum_and_publish(const uint32_t* __restrict__ par
 // host-side helpers shared by the translation units
 namespace pulse {
 int check_view(const PulsePokerView* v, const char* who);
-int finish_launch(const char* what);
 uint64_t pack_types(const uint8_t* agent_types, int n_players);
 }  // namespace pulse

@@ -13,6 +13,12 @@ namespace pulse {
 // Records a thread-local error message and returns `code` (so callers can `return fail(...)`).
 int fail(int code, const char* msg);
 int fail_hip(int hip_error, const char* what);
+// fail(PULSE_EINVAL, "<name>: <msg>"): the argument checks of an entry point that reports under its own name
+int fail_named(const char* name, const char* msg);
+// After a launch: 0, or fail_hip(hipGetLastError(), what).
+int finish_launch(const char* what);
+// Compute units of the current device (asked once per device); 256 where the device cannot be asked, with the sticky error cleared.
+int device_cus();
 
 // abi.hip: launches `fn` with `lds_bytes` of dynamic LDS.  Beyond the default limit of 48 KiB the limit of `fn` is raised first --
 // the first time, and again when a later launch of the same function needs more (the step kernel's size follows obs_size);

@@ -661,17 +661,7 @@ bool act_rows16_ok(const QNetArgs& a) {
     return !tiles_forced && a.seat_idx && a.actions && n.state_dim % 4 == 0 && n.state_dim >= 13 && n.state_dim <= 64 && n.n_actions <= 16 &&
            a.row_stride % 4 == 0 && aligned16(a.states) && aligned16(n.w1);
 }
-int device_cus() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cus[dev] == 0) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus[dev] = prop.multiProcessorCount;
-        else { (void)hipGetLastError(); cus[dev] = 256; }
-    }
-    return cus[dev];
-}
+using pulse::device_cus;
 constexpr int kActTwoLaunchRows = 262144;       // from here on the masked action selection lists first and runs full tiles second
 
 // The fused reduce + AdamW launch is a meeting of all its workgroups inside one ordinary launch: it is only taken where the
@@ -767,8 +757,7 @@ int launch(const QNetArgs& a, void* stream) {
         }
     }
     else { if (vec) hipLaunchKernelGGL((qnet_kernel<false, true>), dim3(grid), dim3(64), 0, st, a); else hipLaunchKernelGGL((qnet_kernel<false, false>), dim3(grid), dim3(64), 0, st, a); }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : pulse::fail_hip((int)e, "pulse_qnet launch");
+    return pulse::finish_launch("pulse_qnet launch");
 }
 
 int act_call(const PulseQNet* net, const float* states, int64_t row_stride, int32_t n_rows, const int32_t* seat_idx,
@@ -846,11 +835,6 @@ int train_validate(const PulseQNetTrain* t, const TrainBatch* b) {
     return 0;
 }
 
-int launched() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : pulse::fail_hip((int)e, "pulse_qnet_train_step launch");
-}
-
 // the training instance: layer-1 steps 5 (16-byte rows of <= 40 inputs) or 8; four or eight wavefronts per tile; stability totals or not
 template <bool VEC, int NK1, bool STAB>
 const void* train_kernel(bool four) {
@@ -909,14 +893,14 @@ int train_grads(const PulseQNetTrain* t, const TrainBatch& b, bool apply, bool* 
     r.stab = t->stability;
     if (*fused) hipLaunchKernelGGL(qnet_grad_reduce_kernel<true>, dim3(rg), dim3(256), 0, st, r, w);
     else hipLaunchKernelGGL(qnet_grad_reduce_kernel<false>, dim3(rg), dim3(256), 0, st, r, w);
-    return launched();
+    return pulse::finish_launch("pulse_qnet_train_step launch");
 }
 
 // AdamW as a launch of its own, on the gradient and the totals the reduce launch (or the caller's all-reduce) left
 int train_adamw(const PulseQNetTrain* t, hipStream_t st) {
     const int np = net_shape(t->net.state_dim, t->net.n_actions).count;
     hipLaunchKernelGGL(qnet_adamw_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, adam_args(t, np));
-    return launched();
+    return pulse::finish_launch("pulse_qnet_train_step launch");
 }
 
 }  // namespace

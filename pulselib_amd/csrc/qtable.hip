@@ -23,79 +23,27 @@
 // -- the k transitions applied one after another with the mean of their targets (k = 1: the reference's formula itself).
 #include <hip/hip_runtime.h>
 
+#include "philox_device.h"
 #include "pulse_internal.h"
 #include "tfe_device.h"
+#include "tfe_table_device.h"
 
 namespace {
 
 constexpr int kBlock = 256;
 
-struct U4 { uint32_t x, y, z, w; };
-__device__ __forceinline__ U4 philox4x32(uint64_t seed, uint64_t subseq, uint64_t offset) {
-    uint32_t c0 = (uint32_t)offset, c1 = (uint32_t)(offset >> 32), c2 = (uint32_t)subseq, c3 = (uint32_t)(subseq >> 32);
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0, p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;   // (v_mad_u64_u32)
-        const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0, h1 = (uint32_t)(p1 >> 32), l1 = (uint32_t)p1;
-        const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-        c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{c0, c1, c2, c3};
-}
+using pulse_philox::U4;
+using pulse_philox::philox4x32;
 
 // one table entry = one 64-byte line
 struct alignas(64) Entry { unsigned long long key; double q[4]; unsigned long long spare[3]; };
 static_assert(sizeof(Entry) == PULSE_QTABLE_ENTRY_BYTES, "entry layout is part of the ABI");
 
-// board -> key: 4 bits of log2(tile) per cell (0 = empty), row-major, cell 0 in the low nibble.
-__device__ __forceinline__ uint64_t pack_cells(const int* b, int cells) {
-    uint64_t key = 0;
-    for (int i = 0; i < cells; ++i) {
-        const int v = b[i];
-        const uint64_t e = v > 0 ? (uint64_t)min(31 - __clz(v), 15) : 0ull;
-        key |= e << (4 * i);
-    }
-    return key;
-}
-__device__ __forceinline__ uint64_t pack_board(const int32_t* __restrict__ b, int cells) {
-    uint64_t key = 0;
-    for (int i = 0; i < cells; ++i) {
-        const int v = b[i];
-        const uint64_t e = v > 0 ? (uint64_t)min(31 - __clz(v), 15) : 0ull;
-        key |= e << (4 * i);
-    }
-    return key;
-}
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return x;
-}
-
-// Slot of `key` inside [base, base + slots): inserted (value row already zero) if absent.  -1 = no room.
-// At most kMaxProbe slots are examined: a table filled to the brim would otherwise turn every lookup of every
-// thread into a walk over the whole table (262,144 threads x 2^24 slots: a launch that never ends); past the
-// limit the state counts as "no room" like a full region.
-constexpr uint64_t kMaxProbe = 4096;
-// (Tried and dropped, DESIGN.md section 3.4: a "shared by several boards" hint kept in the entry's spare words by plain loads
-// and stores at the lookup of the state a move led to, so that the next launch sends the updates of a hot entry straight to the
-// combine path instead of racing for a compare-and-swap -- 233 -> 140 us at the second step after a reset, but +8 us at EVERY
-// step for dirtying the looked-up line, and the racy visitor count rarely passed 8 across the eight L2s.)
-__device__ __forceinline__ long long find_or_insert(Entry* table, uint64_t base, uint64_t slots, uint64_t key) {
-    uint64_t h = mix64(key) & (slots - 1);
-    const uint64_t limit = slots < kMaxProbe ? slots : kMaxProbe;
-    for (uint64_t probe = 0; probe < limit; ++probe) {
-        const uint64_t s = base + ((h + probe) & (slots - 1));
-        unsigned long long cur = table[s].key;
-        if (cur == key) return (long long)s;
-        if (cur == 0ull) {
-            cur = atomicCAS(&table[s].key, 0ull, (unsigned long long)key);
-            if (cur == 0ull || cur == key) return (long long)s;
-        }
-    }
-    return -1;
-}
+using pulse_tfe::pack_cells;
+using pulse_tfe::mix64;
+using pulse_tfe::find_or_insert;
+using pulse::finish_launch;
+constexpr uint64_t kMaxProbe = 4096;      // slots a lookup examines at most (tfe_table_device.h)
 
 // epsilon-greedy (numba.py:5-21): p from words x, y of the board's Philox call, the random action from word z
 __device__ __forceinline__ int choose_action(const U4& r, double epsilon, const double* q, bool have_row) {
@@ -303,9 +251,9 @@ __global__ __launch_bounds__(kBlock) void qtable_select_kernel(Entry* table, uin
                                                               int64_t* __restrict__ actions, int64_t* __restrict__ slots_out) {
     const int g = blockIdx.x * kBlock + threadIdx.x;
     if (g >= n_boards) return;
-    const uint64_t key = pack_board(boards + (size_t)g * cells, cells);
+    const uint64_t key = pack_cells(boards + (size_t)g * cells, cells);
     const uint64_t base = region_slots ? (uint64_t)g * region_slots : 0, slots = region_slots ? region_slots : capacity;
-    const long long s = find_or_insert(table, base, slots, key);
+    const long long s = find_or_insert<kMaxProbe>(table, base, slots, key);
     slots_out[g] = s;
     const U4 r = philox4x32(seed, board_id0 + (uint64_t)g, step_counter);
     double q[4] = {0.0, 0.0, 0.0, 0.0};
@@ -328,7 +276,7 @@ __global__ __launch_bounds__(kBlock) void qtable_update_kernel(Entry* table, uin
     if (live) {
         const uint64_t base = region_slots ? (uint64_t)g * region_slots : 0, slots = region_slots ? region_slots : capacity;
         // QLearningNumba.py:28-37 touches q[next_state] even for terminal transitions (defaultdict insert)
-        const long long sn = find_or_insert(table, base, slots, pack_board(next_boards + (size_t)g * cells, cells));
+        const long long sn = find_or_insert<kMaxProbe>(table, base, slots, pack_cells(next_boards + (size_t)g * cells, cells));
         double mx = 0.0;
         if (sn >= 0) {
             mx = table[sn].q[0];
@@ -372,7 +320,7 @@ __global__ __launch_bounds__(kBlock) void qtable_rollout_step_kernel(Entry* tabl
     PackedBoard pb{0u, 0u};
     bool fast = false;
     if (NB == 4 && lut) { const bool ok = tfe_pack4(reinterpret_cast<const int (&)[16]>(b), pb); fast = !__any(!ok); }
-    if (s == -2) s = find_or_insert(table, base, slots, fast ? ((uint64_t)pb.hi << 32 | pb.lo) : pack_cells(b, NB * NB));
+    if (s == -2) s = find_or_insert<kMaxProbe>(table, base, slots, fast ? ((uint64_t)pb.hi << 32 | pb.lo) : pack_cells(b, NB * NB));
     double q[4] = {0.0, 0.0, 0.0, 0.0};
     if (s >= 0) { q[0] = table[s].q[0]; q[1] = table[s].q[1]; q[2] = table[s].q[2]; q[3] = table[s].q[3]; }
     const int a = choose_action(philox4x32(agent_seed, board_id0 + (uint64_t)g, agent_step), epsilon, q, s >= 0);
@@ -395,7 +343,7 @@ __global__ __launch_bounds__(kBlock) void qtable_rollout_step_kernel(Entry* tabl
     for (int i = 0; i < NB * NB; ++i) bp[i] = b[i];
     total_score[g] += score;
     actions[g] = a; rewards[g] = reward; dones[g] = over;
-    const long long sn = (d.ablate & 4) ? (long long)(base + (mix64(key_next) & (slots - 1))) : find_or_insert(table, base, slots, key_next);
+    const long long sn = (d.ablate & 4) ? (long long)(base + (mix64(key_next) & (slots - 1))) : find_or_insert<kMaxProbe>(table, base, slots, key_next);
     slots_io[g] = sn;
     double mx = 0.0;                                                                    // (s < 0: no room for the state: acted at random, learns nothing)
     if (s >= 0 && sn >= 0) {
@@ -405,12 +353,6 @@ __global__ __launch_bounds__(kBlock) void qtable_rollout_step_kernel(Entry* tabl
     const double target = over ? (double)reward : __dadd_rn((double)reward, __dmul_rn(gamma, mx));
     apply_update(table, s >= 0, s, a, target, alpha, region_slots == 0, d, &wg_n);
     finish_deferred(d, &wg_n);
-}
-
-int finish_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pulse::fail_hip((int)e, what);
-    return 0;
 }
 
 int check_table(const PulseQTable* q, int32_t n_boards, int32_t n) {

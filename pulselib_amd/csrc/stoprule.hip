@@ -298,8 +298,7 @@ int flush(PulseStopRule* h, long long c) {
     const int slot = (int)(c % kSlots);
     hipLaunchKernelGGL(stoprule_sum_kernel, dim3(1), dim3(kBlock), 0, h->last_stream, h->partials_dev + (size_t)slot * h->max_partials,
                        h->n_partials[slot], h->pair_dev + 2 * slot, h->host + slot, c + 1);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pulse::fail_hip((int)e, "stop rule: flush");
+    if (int rc = pulse::finish_launch("stop rule: flush")) return rc;
     h->scheduled = c + 1;
     return 0;
 }

@@ -15,17 +15,19 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdio>
 
-#include "blackjack_device.h"
+#include "philox_device.h"
 #include "pulse_internal.h"
 #include "tfe_device.h"
+#include "tfe_table_device.h"
 
 namespace {
 
 using namespace pulse_tfe;
-using pulse_bj::philox4x32;          // the one Philox4x32-10 of the env kernels (envs.hip takes it from the same header)
-using pulse_bj::U4;
+using pulse_philox::philox4x32;
+using pulse_philox::U4;
+using pulse::fail_named;
+using pulse::finish_launch;
 
 constexpr int kBlock = 256;
 constexpr uint64_t kMaxProbe = PULSE_TFE_MC_MAX_PROBE;
@@ -33,52 +35,6 @@ constexpr uint64_t kMaxProbe = PULSE_TFE_MC_MAX_PROBE;
 // one table entry = one 128-byte line
 struct alignas(128) Entry { unsigned long long key; long long cnt[4]; long long sum[4]; unsigned long long spare[7]; };
 static_assert(sizeof(Entry) == PULSE_TFE_MC_ENTRY_BYTES, "entry layout is part of the ABI");
-
-// board -> key: 4 bits of log2(tile) per cell (0 = empty), row-major, cell 0 in the low nibble (qtable.hip's key)
-template <int NB>
-__device__ __forceinline__ uint64_t pack_cells(const int (&b)[NB * NB]) {
-    uint64_t key = 0;
-#pragma unroll
-    for (int i = 0; i < NB * NB; ++i) {
-        const int v = b[i];
-        const uint64_t e = v > 0 ? (uint64_t)min(31 - __clz(v), 15) : 0ull;
-        key |= e << (4 * i);
-    }
-    return key;
-}
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return x;
-}
-
-// Slot of `key`, or -1: absent.  Never inserts.  At most kMaxProbe slots are examined -- the limit find_or_insert places under, so
-// whatever it placed is found.
-__device__ __forceinline__ long long find(const Entry* table, uint64_t slots, uint64_t key) {
-    const uint64_t h = mix64(key) & (slots - 1);
-    const uint64_t limit = slots < kMaxProbe ? slots : kMaxProbe;
-    for (uint64_t probe = 0; probe < limit; ++probe) {
-        const uint64_t s = (h + probe) & (slots - 1);
-        const unsigned long long cur = table[s].key;
-        if (cur == key) return (long long)s;
-        if (cur == 0ull) return -1;
-    }
-    return -1;
-}
-// Slot of `key`, inserted (counts and sums already zero) if absent.  -1 = no room within the probe limit.
-__device__ __forceinline__ long long find_or_insert(Entry* table, uint64_t slots, uint64_t key) {
-    const uint64_t h = mix64(key) & (slots - 1);
-    const uint64_t limit = slots < kMaxProbe ? slots : kMaxProbe;
-    for (uint64_t probe = 0; probe < limit; ++probe) {
-        const uint64_t s = (h + probe) & (slots - 1);
-        unsigned long long cur = table[s].key;
-        if (cur == key) return (long long)s;
-        if (cur == 0ull) {
-            cur = atomicCAS(&table[s].key, 0ull, (unsigned long long)key);
-            if (cur == 0ull || cur == key) return (long long)s;
-        }
-    }
-    return -1;
-}
 
 // The greedy action of an entry (OnPolicyFirstVisit.py:52-62): the actions in order, a larger q replaces the best, an equal q
 // replaces it on the coin of that action.  The coins are constant per (state, round); they are drawn only where two q are equal.
@@ -138,11 +94,11 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMC
         uint64_t prev_key = 0ull;                         // (no live board packs to 0)
         bool over = false;
         for (int t = 0; t < o.max_steps && !over; ++t) {
-            const uint64_t key = pack_cells<NB>(b);
+            const uint64_t key = pack_cells<NB * NB>(b);
             taken = key == prev_key ? taken : 0u;
             prev_key = key;
             const U4 r = philox4x32(o.agent_seed, id, (uint64_t)t);
-            const long long s = find(table, o.capacity, key);
+            const long long s = find<kMaxProbe>(table, 0, o.capacity, key);
             int a = (int)(r.y >> 30);                     // no entry: the reference's uniform default policy; or the epsilon branch
             if (s >= 0 && (r.x >> 8) >= eps_q24) a = greedy_action(table[s], key, o.tie_seed, o.round, inv_scale);
             const int score = tfe_move<NB>(b, a);                                      // TFE.py:154-178
@@ -183,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_learn_kernel(const PulseTfeMCLe
             G = __dadd_rn(__dmul_rn(o.gamma, G), (double)((st >> 2) & 31u));           // OnPolicyFirstVisit.py:28: G = gamma * G + reward
             if (st & 0x80u) {
                 const uint64_t key = o.keys[(size_t)t * B + (size_t)g];
-                const long long s = key ? find_or_insert(table, o.capacity, key) : -1;
+                const long long s = key ? find_or_insert<kMaxProbe>(table, 0, o.capacity, key) : -1;
                 if (s >= 0) {
                     const int a = (int)(st & 3u);
                     atomicAdd(reinterpret_cast<unsigned long long*>(&table[s].sum[a]), (unsigned long long)llrint(ldexp(G, o.frac_bits)));
@@ -196,12 +152,6 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_learn_kernel(const PulseTfeMCLe
         }
     }
     add_stats(wg, o.stats, 1, n_added, 2, n_dropped);
-}
-
-int fail_named(const char* name, const char* msg) {
-    char text[256];
-    std::snprintf(text, sizeof text, "%s: %s", name, msg);
-    return pulse::fail(PULSE_EINVAL, text);
 }
 
 // The largest frac_bits <= 30 with G_max * 2^frac_bits * 2^32 < 2^62, G_max = r_max * min(max_steps, 1 / (1 - gamma)); -1 = none.
@@ -234,12 +184,6 @@ int check_common(const O* o, const char* name) {
     if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->stats & 7u)) return fail_named(name, "keys / stats must be 8-byte aligned");
     if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
     if (o->reserved0 != 0) return fail_named(name, "reserved0 must be 0 (zero-initialise the struct)");
-    return 0;
-}
-
-int finish_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pulse::fail_hip((int)e, what);
     return 0;
 }
 

@@ -27,11 +27,7 @@ class Particle2D(_EnvBase):
 
     def __init__(self, device, batch_size, dt=0.1, max_steps=200):
         super().__init__()
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"pulselib_amd.Particle2D runs on an MI355X ('cuda' device); got '{device}'. No CPU fallback.")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _native.gpu_device(device, "Particle2D")
         self._lib = _native.lib()
         self.device, self.batch_size, self.dt, self.max_steps = device, batch_size, dt, max_steps
         if spaces is not None:

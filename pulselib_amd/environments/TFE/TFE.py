@@ -28,11 +28,7 @@ class TFEBatch:
     """B independent n x n boards (n in 2..8) on the GPU."""
 
     def __init__(self, device, batch_size, board_size=4, seed=0, board_id0=0):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"pulselib_amd.TFEBatch runs on an MI355X ('cuda' device); got '{device}'. No CPU fallback.")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _native.gpu_device(device, "TFEBatch")
         if not 2 <= board_size <= 8:
             raise ValueError("board_size must be 2..8")
         self._lib = _native.lib()

@@ -33,11 +33,7 @@ class BlackJack(_EnvBase):
 
     def __init__(self, device, batch_size, seed=0):
         super().__init__()
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError(f"pulselib_amd.BlackJack runs on an MI355X ('cuda' device); got '{device}'. No CPU fallback.")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _native.gpu_device(device, "BlackJack")
         self._lib = _native.lib()
         self.device = device
         self.batch_size = batch_size

@@ -63,6 +63,16 @@ def test_product_classes_refuse_cpu_devices():
             make()
 
 
+@pytest.mark.parametrize("text", ["0xD2511F53", "0xff51afd7ed558ccd", "int finish_launch("],
+                         ids=["philox-multiplier", "mix64-constant", "finish_launch"])
+def test_shared_pieces_are_written_once(text):
+    """Philox4x32-10 (philox_device.h), the 2048 tables' hash (tfe_table_device.h) and the launch tail (pulse_internal.h, defined
+    in abi.hip as pulse::finish_launch) each stand in ONE file of csrc: the bit-for-bit tests rest on every unit running the same
+    text, so the next kernel takes the shared one instead of a copy."""
+    holders = sorted(p.name for p in (ROOT / "pulselib_amd" / "csrc").iterdir() if p.is_file() and text.lower() in p.read_text().lower())     # (either letter case of the hex digits)
+    assert len(holders) == 1, f"{text!r} occurs in {holders}"
+
+
 def test_product_package_never_imports_the_oracle():
     """oracle/ is test infrastructure: nothing under pulselib_amd/ may import, include or link it."""
     for path in (ROOT / "pulselib_amd").rglob("*.py"):

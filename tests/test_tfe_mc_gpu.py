@@ -201,6 +201,12 @@ def test_a_full_table_drops_and_ends():
     assert stats["first_visits"] == sum(sum(c) for c, _ in table.values()) and stats["first_visits"] + stats["dropped"] == total
     want = _host_rollout(a, table)                                         # the roll-out against a table without a free slot
     _assert_rollout(_rollout(a), want, 1)
+    # ... and one that is sure to meet its entries.  Which 16 keys were placed is a race among the learner's lanes -- each wavefront
+    # starts at its games' last moves -- and round 1's boards pass through few such states (on the host: no lookup of theirs hits
+    # under most outcomes of the race).  Round 0's own games do: the game that placed a key plays as before up to the first entry met.
+    a.round = 0
+    want = _host_rollout(a, table)
+    _assert_rollout(_rollout(a), want, 2)
     assert want["present"] > 0
     _guards_intact(a)
 
