@@ -558,6 +558,45 @@ typedef struct PulseTfeMCLearn {
 } PulseTfeMCLearn;
 int pulse_tfe_mc_learn(const PulseTfeMCLearn* o, void* stream);
 
+/* ---- 2048 Monte-Carlo control: the eight symmetries of the square as one state, and an evaluation launch.
+ *
+ * T_0 .. T_7: T_j rotates the board j & 3 times by the environment's rotation (TFE.py:38-44: out[r][c] = in[c][n - 1 - r]), for
+ * j >= 4 after a transpose.  canon(board) = (key_c, j*): key_c = the smallest of the eight images' keys as uint64, j* = the smallest
+ * j whose image has it.  amap[j][a] = the action with T_j(move(B, a)) == move(T_j(B), amap[j][a]) and the same merge score:
+ *   amap = {0,1,2,3}, {3,0,1,2}, {2,3,0,1}, {1,2,3,0}, {1,0,3,2}, {0,3,2,1}, {3,2,1,0}, {2,1,0,3}   (0 left, 1 up, 2 right, 3 down).
+ *
+ * pulse_tfe_mc_rollout_canon: pulse_tfe_mc_rollout (same struct, same checks, same game of the environment, same draws) on the
+ * table of canonical states.  Per move key_c is looked up.  No entry, or the epsilon branch: the board moves by a = y >> 30 as
+ * there, so on an empty table the two entry points play the same games.  Otherwise a_c = the greedy action of the entry with the
+ * tie coins of Philox4x32-10(tie_seed, key_c, round), and the board moves by the a with amap[j*][a] = a_c.  Recorded:
+ * keys[t * n_games + g] = key_c, steps = a_c | reward << 2 | first << 7 with a_c = amap[j*][a], first = a_c was not yet taken in
+ * the current run of equal key_c (equal key_c: equal tile sums: the same run of one unchanged board: the same j*).
+ * pulse_tfe_mc_learn takes these as it takes the plain ones.
+ *
+ * pulse_tfe_mc_evaluate: the games pulse_tfe_mc_rollout (canonical = 0) or pulse_tfe_mc_rollout_canon (canonical = 1) plays for
+ * equal env_seed, agent_seed, tie_seed, board_id0, round, epsilon and table, without a trajectory.  The table is only read.
+ * summary, device int64[8], ADDED TO: [0] games, [1] moves, [2] sum of total_score, [3] sum of total_score^2, [4] the largest
+ * total_score (atomic max), [5] games cut at max_steps, [6] moves whose state had an entry, [7] moves decided greedily (an entry
+ * and not the epsilon branch).  max_tile_hist, device int64[16], added to: bin = log2 of the largest tile of the final board.
+ * total_score int64[n_games] / lengths int32[n_games]: per game, or NULL.  One launch: the counters are reduced in the workgroup
+ * and added with one atomic per workgroup and non-zero bin.  frac_bits: the table's, 0..30 (the scale of q does not change an
+ * order).  PULSE_EINVAL as above, and for canonical outside {0, 1}, a null summary or max_tile_hist, non-zero reserved fields. */
+int pulse_tfe_mc_rollout_canon(const PulseTfeMCRollout* o, void* stream);
+typedef struct PulseTfeMCEval {
+    const void* entries;
+    uint64_t capacity;
+    int32_t n_games, n, max_steps, frac_bits;
+    double epsilon;
+    uint64_t env_seed, agent_seed, tie_seed, board_id0, round;
+    int32_t canonical, reserved0;
+    int64_t* summary;                   /* int64[8] */
+    int64_t* max_tile_hist;             /* int64[16] */
+    int64_t* total_score;               /* int64[n_games] or NULL */
+    int32_t* lengths;                   /* int32[n_games] or NULL */
+    int64_t reserved1;
+} PulseTfeMCEval;
+int pulse_tfe_mc_evaluate(const PulseTfeMCEval* o, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

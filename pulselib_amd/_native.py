@@ -134,6 +134,13 @@ class TfeMCLearn(C.Structure):
     _fields_ = _TFE_MC_HEAD + [(n, C.c_void_p) for n in ("keys", "steps", "lengths", "stats")] + [("reserved0", C.c_int64)]
 
 
+class TfeMCEval(C.Structure):
+    _fields_ = [("entries", C.c_void_p), ("capacity", C.c_uint64), ("n_games", C.c_int32), ("n", C.c_int32), ("max_steps", C.c_int32),
+                ("frac_bits", C.c_int32), ("epsilon", C.c_double)] + [
+        (n, C.c_uint64) for n in ("env_seed", "agent_seed", "tie_seed", "board_id0", "round")] + [("canonical", C.c_int32), ("reserved0", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("summary", "max_tile_hist", "total_score", "lengths")] + [("reserved1", C.c_int64)]
+
+
 # every symbol include/pulse_env.h declares: (restype, argtypes)
 _P, _I32, _U32, _U64, _F32, _I64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_float, C.c_int64
 SYMBOLS = {
@@ -187,6 +194,8 @@ SYMBOLS = {
     "pulse_tfe_step": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _U64, _U64, _U64, _P]),
     "pulse_tfe_mc_rollout": (C.c_int, [_P, _P]),
     "pulse_tfe_mc_learn": (C.c_int, [_P, _P]),
+    "pulse_tfe_mc_rollout_canon": (C.c_int, [_P, _P]),
+    "pulse_tfe_mc_evaluate": (C.c_int, [_P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

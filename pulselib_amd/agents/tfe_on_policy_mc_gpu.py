@@ -10,8 +10,13 @@ Against the reference: the policy improves once per BATCH
 breaks a tie between equal q is drawn per (state, round), not per look; actions and spawns come from Philox streams; a game is cut
 at `max_steps` moves.  Round r plays the boards board_id0 + r * n_games + g, so no two rounds replay the same spawns.
 
+`symmetric=True` keeps a board's eight images under the symmetries of the square as one state:
+`pulse_tfe_mc_rollout_canon` looks up the smallest of the eight keys, takes the greedy action in that image's frame and moves the
+board by the action mapped back; the learner is the same.  `evaluate()` (`pulse_tfe_mc_evaluate`) plays games under the table without
+recording them and returns score statistics reduced in the launch.
+
 `learn_on_host`, `greedy_on_host`, `first_visit_flags_on_host` and `run_mask_flags_on_host` are the host's statement of the same
-arithmetic, in numpy and pure Python."""
+arithmetic, in numpy and pure Python; `transforms_on_host`, `canon_on_host`, `ACTION_MAP` and `fold_table_on_host` that of the symmetries."""
 from __future__ import annotations
 
 import ctypes as C
@@ -25,6 +30,8 @@ ENTRY_BYTES, MAX_PROBE, R_MAX = _native.TFE_MC_ENTRY_BYTES, _native.TFE_MC_MAX_P
 AGENT_KEY = 0x2048AC7105EED                     # the agent's draws are keyed apart from the environment's (the seed itself) ...
 TIE_KEY = 0x20487C01F11B5                       # ... and the tie coins apart from both
 STATS = ("steps", "first_visits", "dropped", "truncated")
+EVAL_SUMMARY = ("games", "moves", "score_sum", "score_sq_sum", "max_score", "truncated", "moves_with_entry", "moves_greedy")
+EVAL_BINS = 16                                  # bin = log2 of the largest tile of the final board
 
 
 def frac_bits_for(gamma: float, max_steps: int) -> int:
@@ -55,6 +62,60 @@ def pack_board(board) -> int:
     for i, v in enumerate(np.asarray(board).ravel().tolist()):
         key |= (min(int(v).bit_length() - 1, 15) if v > 0 else 0) << (4 * i)
     return key
+
+
+def unpack_key(key: int, n: int) -> list:
+    """The n * n log2 tiles of a state key, row-major."""
+    return [(int(key) >> (4 * i)) & 15 for i in range(n * n)]
+
+
+# The eight symmetries of the square (DESIGN.md section 12.1).  T_0..T_3 rotate the board 0..3 times by the environment's own
+# rotation (TFE.py:38-44: out[r][c] = in[c][n - 1 - r]); T_4..T_7 do the same to the transposed board.  ACTION_MAP[j][a] is the
+# action with T_j(move(B, a)) == move(T_j(B), ACTION_MAP[j][a]): the moves are 0 left, 1 up, 2 right, 3 down, a rotation turns
+# them by one, the transpose swaps left with up and right with down.  (tests/test_tfe_mc_sym_cpu.py establishes the table against
+# the environment's move; the device holds the same 32 numbers, two bits each, in one 64-bit constant.)
+ACTION_MAP = ((0, 1, 2, 3), (3, 0, 1, 2), (2, 3, 0, 1), (1, 2, 3, 0), (1, 0, 3, 2), (0, 3, 2, 1), (3, 2, 1, 0), (2, 1, 0, 3))
+ACTION_UNMAP = tuple(tuple(row.index(a) for a in range(4)) for row in ACTION_MAP)      # ACTION_UNMAP[j][ACTION_MAP[j][a]] == a
+
+
+def transforms_on_host(n: int) -> np.ndarray:
+    """int64[8, n * n]: T_j(B).ravel() == B.ravel()[transforms_on_host(n)[j]]."""
+    out = np.zeros((8, n * n), dtype=np.int64)
+    for j in range(8):
+        for r in range(n):
+            for c in range(n):
+                rr, cc = r, c
+                for _ in range(j & 3):                                     # rot_src of csrc/tfe_device.h
+                    rr, cc = cc, n - 1 - rr
+                out[j, r * n + c] = cc * n + rr if j >= 4 else rr * n + cc
+    return out
+
+
+def canon_key_on_host(key: int, n: int):
+    """(key_c, j*) of a state key: the smallest of the keys of its eight images and the smallest j whose image has it."""
+    cells = unpack_key(key, n)
+    images = [sum(cells[s] << (4 * i) for i, s in enumerate(src)) for src in transforms_on_host(n).tolist()]
+    key_c = min(images)
+    return key_c, images.index(key_c)
+
+
+def canon_on_host(board):
+    """(key_c, j*) of an n x n board of tiles."""
+    board = np.asarray(board)
+    return canon_key_on_host(pack_board(board), board.shape[-1])
+
+
+def fold_table_on_host(table: dict, n: int) -> dict:
+    """A plain table {key: (cnt[4], sum[4])} as the table of canonical states: every entry goes to its canonical key with cnt / sum
+    permuted by ACTION_MAP[j*], and entries that meet are added.  (n: the board side the keys were packed for.)"""
+    out = {}
+    for key, (cnt, total) in table.items():
+        key_c, j = canon_key_on_host(key, n)
+        c, s = out.setdefault(key_c, ([0] * 4, [0] * 4))
+        for a in range(4):
+            c[ACTION_MAP[j][a]] += int(cnt[a])
+            s[ACTION_MAP[j][a]] += int(total[a])
+    return out
 
 
 def unpack_steps(steps):
@@ -125,11 +186,26 @@ def learn_on_host(keys, steps, lengths, gamma: float, frac_bits: int, table: dic
     return table
 
 
+def eval_summary_on_host(words) -> dict:
+    """pulse_tfe_mc_evaluate's 8 + 16 counters as a dict: the words by name, the histogram, and mean / std (sample standard deviation,
+    from the exact integer sums) / max of the final score, the mean length and the share of moves whose state had a table entry."""
+    w = [int(x) for x in words]
+    out = dict(zip(EVAL_SUMMARY, w[:len(EVAL_SUMMARY)]))
+    n, s, ss = out["games"], out["score_sum"], out["score_sq_sum"]
+    out["max_tile_hist"] = w[len(EVAL_SUMMARY):len(EVAL_SUMMARY) + EVAL_BINS]
+    out["mean_score"] = s / n if n else 0.0
+    out["std_score"] = math.sqrt((n * ss - s * s) / (n * (n - 1))) if n > 1 else 0.0          # exact integers under the root
+    out["mean_length"] = out["moves"] / n if n else 0.0
+    out["coverage"] = out["moves_with_entry"] / out["moves"] if out["moves"] else 0.0
+    return out
+
+
 class OnPolicyFirstVisitMCTFEGPU:
     """`learn_batch` = `rollout` + `learn` + `round += 1`, two launches and no synchronisation.  Everything that reads back
     (`table`, `q`, `greedy`, `stats`, `trajectory`, the per-game arrays' `.cpu()`) synchronises."""
 
-    def __init__(self, device, n_games, board_size=3, gamma=.9, epsilon=.1, capacity=1 << 22, max_steps=1024, seed=0, board_id0=0):
+    def __init__(self, device, n_games, board_size=3, gamma=.9, epsilon=.1, capacity=1 << 22, max_steps=1024, seed=0, board_id0=0,
+                 symmetric=False):
         import torch
         device = _native.gpu_device(device, "OnPolicyFirstVisitMCTFEGPU")
         if not 2 <= int(board_size) <= 4:
@@ -145,7 +221,7 @@ class OnPolicyFirstVisitMCTFEGPU:
         self.n_games, self.n, self.capacity, self.max_steps = int(n_games), int(board_size), int(capacity), int(max_steps)
         self.gamma, self.epsilon = float(gamma), float(epsilon)
         self.frac_bits = frac_bits_for(self.gamma, self.max_steps)
-        self.seed, self.board_id0, self.round = int(seed), int(board_id0), 0
+        self.seed, self.board_id0, self.round, self.symmetric = int(seed), int(board_id0), 0, bool(symmetric)
         self.env_seed, self.agent_seed, self.tie_seed = self.seed, self.seed ^ AGENT_KEY, self.seed ^ TIE_KEY
         words = ENTRY_BYTES // 8
         self._storage = torch.zeros(self.capacity * words + words, dtype=torch.int64, device=device)
@@ -157,6 +233,7 @@ class OnPolicyFirstVisitMCTFEGPU:
         self.total_score = torch.zeros(self.n_games, dtype=torch.int64, device=device)
         self.episode_reward = torch.zeros(self.n_games, dtype=torch.int32, device=device)
         self.counters = torch.zeros(8, dtype=torch.int64, device=device)
+        self._eval = torch.zeros(len(EVAL_SUMMARY) + EVAL_BINS, dtype=torch.int64, device=device)     # evaluate(): summary, then the histogram
 
     # ------------------------------------------------------------------ the launches
     def _head(self, o):
@@ -170,11 +247,13 @@ class OnPolicyFirstVisitMCTFEGPU:
         return self.board_id0 + (self.round if round is None else int(round)) * self.n_games
 
     def rollout(self):
-        """One launch: n_games games under the table as it stands (round `self.round`), into keys / steps / lengths / scores."""
+        """One launch: n_games games under the table as it stands (round `self.round`), into keys / steps / lengths / scores.
+        With `symmetric` the recorded keys and actions are those of the canonical frame (pulse_tfe_mc_rollout_canon)."""
         o = self._head(_native.TfeMCRollout())
         o.env_seed, o.agent_seed, o.tie_seed, o.board_id0, o.round = self.env_seed, self.agent_seed, self.tie_seed, self.round_board_id0(), self.round
         o.total_score, o.episode_reward = self.total_score.data_ptr(), self.episode_reward.data_ptr()
-        _native.check(self._lib.pulse_tfe_mc_rollout(C.byref(o), _native.current_stream(self.device)), "pulse_tfe_mc_rollout")
+        name = "pulse_tfe_mc_rollout_canon" if self.symmetric else "pulse_tfe_mc_rollout"
+        _native.check(getattr(self._lib, name)(C.byref(o), _native.current_stream(self.device)), name)
         return self
 
     def learn(self):
@@ -201,9 +280,58 @@ class OnPolicyFirstVisitMCTFEGPU:
         return {(k, a): v for k, e in self.table().items() for a, v in enumerate(q_of_entry(e, self.frac_bits))}
 
     def greedy(self, keys, round=None) -> list:
-        """The greedy action the roll-out of `round` takes in each of `keys`, or None where the table has no entry."""
+        """The greedy action the roll-out of `round` takes in each of `keys` (the keys of boards as they lie), or None where the table
+        has no entry.  With `symmetric` a key is looked up as its canonical state and the action comes back in the board's own frame."""
         table, r = self.table(), self.round if round is None else int(round)
-        return [greedy_on_host(table[int(k)], int(k), self.tie_seed, r) if int(k) in table else None for k in keys]
+        out = []
+        for k in keys:
+            k, j = canon_key_on_host(int(k), self.n) if self.symmetric else (int(k), 0)
+            out.append(ACTION_UNMAP[j][greedy_on_host(table[k], k, self.tie_seed, r)] if k in table else None)
+        return out
+
+    def eval_board_id0(self) -> int:
+        """evaluate()'s default boards: board_id0 + 2^62 + g.  Round r trains on board_id0 + r * n_games + g, so training meets them
+        only after 2^62 / n_games rounds; every call with the default replays the same spawns (scores of two tables are paired)."""
+        return (self.board_id0 + (1 << 62)) & 0xFFFFFFFFFFFFFFFF
+
+    def evaluate_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False):
+        """The launch of evaluate() alone (pulse_tfe_mc_evaluate): ADDS to the counters of `eval_counters` and reads nothing back.
+        Returns the per-game device tensors (total_score int64[B], lengths int32[B]) with per_game, else None."""
+        import torch
+        B = self.n_games if n_games is None else int(n_games)
+        o = _native.TfeMCEval()
+        o.entries, o.capacity, o.n_games, o.n, o.max_steps, o.frac_bits = self.entries.data_ptr(), self.capacity, B, self.n, self.max_steps, self.frac_bits
+        o.epsilon, o.env_seed, o.agent_seed, o.tie_seed, o.round = float(epsilon), self.env_seed, self.agent_seed, self.tie_seed, self.round
+        o.board_id0 = self.eval_board_id0() if board_id0 is None else int(board_id0)
+        o.canonical = int(self.symmetric)
+        o.summary, o.max_tile_hist = self._eval.data_ptr(), self._eval[len(EVAL_SUMMARY):].data_ptr()
+        arrays = None
+        if per_game:
+            arrays = (torch.zeros(B, dtype=torch.int64, device=self.device), torch.zeros(B, dtype=torch.int32, device=self.device))
+            o.total_score, o.lengths = arrays[0].data_ptr(), arrays[1].data_ptr()
+        _native.check(self._lib.pulse_tfe_mc_evaluate(C.byref(o), _native.current_stream(self.device)), "pulse_tfe_mc_evaluate")
+        return arrays
+
+    def eval_counters(self, clear=False) -> dict:
+        """What the evaluation launches since the last clear added up to (eval_summary_on_host; synchronises), or, with clear, nothing:
+        the counters are zeroed."""
+        if clear:
+            self._eval.zero_()
+            return {}
+        return eval_summary_on_host(self._eval.cpu().tolist())
+
+    def evaluate(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False) -> dict:
+        """One launch and one read-back: `n_games` games (default: the agent's) under the table as it stands and `epsilon` (default 0:
+        the greedy policy; a state without an entry still plays the uniform default), no trajectory.  With equal seeds, round, epsilon
+        and board_id0 they are the games rollout() plays.  Returns the counters by name, the histogram of the largest tile, mean /
+        standard deviation / maximum of the final score, the mean length, the games cut at max_steps and the share of moves whose
+        state had an entry; per_game adds the arrays total_score / lengths."""
+        self.eval_counters(clear=True)
+        arrays = self.evaluate_launch(n_games, epsilon, board_id0, per_game)
+        out = self.eval_counters()
+        if per_game:
+            out["total_score"], out["lengths"] = arrays[0].cpu().numpy(), arrays[1].cpu().numpy()
+        return out
 
     def stats(self) -> dict:
         return dict(zip(STATS, self.counters.cpu().tolist()[:4]))

@@ -12,6 +12,11 @@
 // First visits without a per-game set: a merge keeps the tile sum and a spawn adds to it, so the sum rises at every step unless the
 // board is full and the move changes nothing -- equal states of a game are consecutive, and "first visit of (s, a)" is "a was not
 // yet taken in the current run of identical boards": four bits per lane.
+//
+// The same game loop has two more instantiations.  Canon: the state is the smallest key among the board's
+// eight images under the symmetries of the square, the greedy action is taken in that image's frame and mapped back
+// (pulse_tfe_mc_rollout_canon).  Not Record: no trajectory is written and the scores are reduced in the launch
+// (pulse_tfe_mc_evaluate).  The table is only read by all of them.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -69,10 +74,63 @@ __device__ __forceinline__ void add_stats(unsigned long long* wg, int64_t* stats
     if (threadIdx.x == 1 && wg[1]) atomicAdd(reinterpret_cast<unsigned long long*>(stats) + at1, wg[1]);
 }
 
+// The eight symmetries of the square, T_0 .. T_7: T_j rotates the board j & 3 times by the move's own rotation (rot_src), for
+// j >= 4 after a transpose.  sym_src = the cell of the board that cell (r, c) of T_j(board) shows.
 template <int NB>
-__global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMCRollout o, uint32_t eps_q24, double inv_scale) {
-    __shared__ unsigned long long wg[2];
-    if (threadIdx.x < 2) wg[threadIdx.x] = 0ull;
+__device__ __forceinline__ int sym_src(int j, int r, int c) {
+    const int i = rot_src<NB>(j & 3, r, c);
+    return j >= 4 ? (i % NB) * NB + i / NB : i;
+}
+// kActionMap >> (8 j + 2 a) & 3 = the action with T_j(move(B, a)) == move(T_j(B), that action); kActionUnmap is its inverse per j.
+// (ACTION_MAP / ACTION_UNMAP of agents/tfe_on_policy_mc_gpu.py, which a test holds to the environment's move.)
+constexpr uint64_t kActionMap = 0xc61b6cb1394e93e4ull, kActionUnmap = 0xc61b6cb1934e39e4ull;
+__device__ __forceinline__ int map_action(uint64_t map, int j, int a) { return (int)((map >> (8 * j + 2 * a)) & 3ull); }
+
+// (key_c, j*) of a board: the smallest of the keys of its eight images and the smallest j whose image has it.  The cells' nibbles
+// are taken once; every image is NB * NB shift-ors of them at constant positions -- registers only.
+template <int NB>
+__device__ __forceinline__ uint64_t canon_key(const int (&b)[NB * NB], int& j_min) {
+    uint32_t e[NB * NB];
+#pragma unroll
+    for (int i = 0; i < NB * NB; ++i) e[i] = b[i] > 0 ? (uint32_t)min(31 - __clz(b[i]), 15) : 0u;         // pack_cells' nibble
+    uint64_t best = 0ull;
+    j_min = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        uint32_t lo = 0u, hi = 0u;
+#pragma unroll
+        for (int r = 0; r < NB; ++r)
+#pragma unroll
+            for (int c = 0; c < NB; ++c) {
+                const int i = r * NB + c;
+                const uint32_t v = e[sym_src<NB>(j, r, c)] << (4 * (i & 7));
+                if (i < 8) lo |= v; else hi |= v;
+            }
+        const uint64_t key = (uint64_t)hi << 32 | lo;
+        const bool less = j > 0 && key < best;
+        j_min = less ? j : j_min;
+        best = j == 0 || less ? key : best;
+    }
+    return best;
+}
+
+// pulse_tfe_mc_evaluate's counters: summary[8] then max_tile_hist[16], reduced in LDS and added once per workgroup and non-zero bin.
+constexpr int kEvalSummary = 8, kEvalBins = kEvalSummary + 16, kEvalMax = 4;
+__device__ __forceinline__ void flush_bins(unsigned long long* wg, int64_t* summary, int64_t* hist) {
+    __syncthreads();
+    const int i = (int)threadIdx.x;
+    if (i < kEvalBins && wg[i]) {
+        unsigned long long* dst = reinterpret_cast<unsigned long long*>(i < kEvalSummary ? summary + i : hist + (i - kEvalSummary));
+        if (i == kEvalMax) atomicMax(dst, wg[i]); else atomicAdd(dst, wg[i]);          // (scores are not negative)
+    }
+}
+
+// The game loop.  <NB, false, true> is pulse_tfe_mc_rollout; Canon plays in the canonical frame; without Record nothing is written
+// per move, lengths / total_score are optional, o.stats is the evaluation's summary[8] and `hist` its max_tile_hist[16].
+template <int NB, bool Canon, bool Record>
+__global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMCRollout o, uint32_t eps_q24, double inv_scale, int64_t* hist) {
+    __shared__ unsigned long long wg[Record ? 2 : kEvalBins];
+    if (threadIdx.x < (Record ? 2 : kEvalBins)) wg[threadIdx.x] = 0ull;
     __syncthreads();
     const int g = blockIdx.x * kBlock + threadIdx.x;
     const size_t B = (size_t)o.n_games;
@@ -93,33 +151,57 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMC
         uint32_t taken = 0u;                              // bit a: action a was taken in the current run of identical boards
         uint64_t prev_key = 0ull;                         // (no live board packs to 0)
         bool over = false;
+        unsigned long long n_present = 0ull, n_greedy = 0ull;
         for (int t = 0; t < o.max_steps && !over; ++t) {
-            const uint64_t key = pack_cells<NB * NB>(b);
+            int j = 0;                                    // the board shows its canonical state under T_j
+            uint64_t key;
+            if constexpr (Canon) key = canon_key<NB>(b, j); else key = pack_cells<NB * NB>(b);
             taken = key == prev_key ? taken : 0u;
             prev_key = key;
             const U4 r = philox4x32(o.agent_seed, id, (uint64_t)t);
             const long long s = find<kMaxProbe>(table, 0, o.capacity, key);
             int a = (int)(r.y >> 30);                     // no entry: the reference's uniform default policy; or the epsilon branch
+            if constexpr (Canon) a = map_action(kActionMap, j, a);                     // a: the action in the frame of `key`
             if (s >= 0 && (r.x >> 8) >= eps_q24) a = greedy_action(table[s], key, o.tie_seed, o.round, inv_scale);
-            const int score = tfe_move<NB>(b, a);                                      // TFE.py:154-178
+            if constexpr (!Record) { n_present += s >= 0; n_greedy += s >= 0 && (r.x >> 8) >= eps_q24; }
+            int a_board = a;                                                           // ... and as the board lies
+            if constexpr (Canon) a_board = map_action(kActionUnmap, j, a);
+            const int score = tfe_move<NB>(b, a_board);                                // TFE.py:154-178
             const U4 rnd = philox4x32(o.env_seed, id, (uint64_t)t + 1ull);
             tfe_spawn<NB>(b, rnd.x, rnd.y);                                            // TFE.py:182 (always)
             over = tfe_over<NB>(b);                                                    // TFE.py:48-67
             const int reward = score > 0 ? 31 - __clz(score) : 0;                      // TFE.py:185-187 (<= 17 for n <= 4: five bits)
             const uint32_t first = ((taken >> a) & 1u) ^ 1u;
             taken |= 1u << a;
-            o.keys[(size_t)t * B + (size_t)g] = key;
-            o.steps[(size_t)t * B + (size_t)g] = (uint8_t)((uint32_t)a | ((uint32_t)reward & 31u) << 2 | first << 7);
+            if constexpr (Record) {
+                o.keys[(size_t)t * B + (size_t)g] = key;
+                o.steps[(size_t)t * B + (size_t)g] = (uint8_t)((uint32_t)a | ((uint32_t)reward & 31u) << 2 | first << 7);
+            }
             total += score; ep_reward += reward;
             length = t + 1;
         }
-        o.lengths[g] = length;
-        o.total_score[g] = total;
-        o.episode_reward[g] = ep_reward;
         n_moves = (unsigned long long)length;
         n_cut = over ? 0ull : 1ull;
+        if constexpr (Record) {
+            o.lengths[g] = length;
+            o.total_score[g] = total;
+            o.episode_reward[g] = ep_reward;
+        } else {
+            if (o.lengths) o.lengths[g] = length;
+            if (o.total_score) o.total_score[g] = total;
+            int top = 0;
+#pragma unroll
+            for (int i = 0; i < NB * NB; ++i) top = max(top, b[i]);
+            const unsigned long long sc = (unsigned long long)total;
+            const unsigned long long v[kEvalSummary] = {1ull, n_moves, sc, sc * sc, sc, n_cut, n_present, n_greedy};
+#pragma unroll
+            for (int i = 0; i < kEvalSummary; ++i)
+                if (v[i]) { if (i == kEvalMax) atomicMax(&wg[i], v[i]); else atomicAdd(&wg[i], v[i]); }       // LDS
+            atomicAdd(&wg[kEvalSummary + min(31 - __clz(top | 1), 15)], 1ull);
+        }
     }
-    add_stats(wg, o.stats, 0, n_moves, 3, n_cut);
+    if constexpr (Record) add_stats(wg, o.stats, 0, n_moves, 3, n_cut);
+    else flush_bins(wg, o.stats, hist);
 }
 
 __global__ __launch_bounds__(kBlock) void tfe_mc_learn_kernel(const PulseTfeMCLearn o) {
@@ -163,9 +245,9 @@ int max_frac_bits(double gamma, int max_steps) {
     return -1;
 }
 
-// The checks both entry points share: their structs begin with the same fields.
+// The checks every entry point shares: the table and the shape of the batch ...
 template <class O>
-int check_common(const O* o, const char* name) {
+int check_table(const O* o, const char* name) {
     if (!o) return fail_named(name, "options are null");
     if (!o->entries) return fail_named(name, "entries is null");
     if ((uintptr_t)o->entries & (PULSE_TFE_MC_ENTRY_BYTES - 1)) return fail_named(name, "entries must be 128-byte aligned");
@@ -173,6 +255,12 @@ int check_common(const O* o, const char* name) {
     if (o->n < 2 || o->n > 4) return fail_named(name, "board side must be 2..4 (64-bit state key)");
     if (o->n_games < 1) return fail_named(name, "n_games must be positive");
     if (o->max_steps < 1 || o->max_steps > 65535) return fail_named(name, "max_steps must be in 1..65535");
+    return 0;
+}
+// ... and those of the roll-outs and the learner: their structs begin with the same fields.
+template <class O>
+int check_common(const O* o, const char* name) {
+    if (int rc = check_table(o, name)) return rc;
     if (!(o->gamma >= 0.0 && o->gamma <= 1.0)) return fail_named(name, "gamma must be in [0, 1]");
     if (!(o->epsilon >= 0.0 && o->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
     if (o->frac_bits < 0 || o->frac_bits > max_frac_bits(o->gamma, o->max_steps))
@@ -187,25 +275,62 @@ int check_common(const O* o, const char* name) {
     return 0;
 }
 
-}  // namespace
+// The three launches of the game loop.  `o` is the caller's struct, or pulse_tfe_mc_evaluate's outputs in its shape.
+template <bool Canon, bool Record>
+void launch_games(const PulseTfeMCRollout& o, int64_t* hist, void* stream) {
+    const uint32_t eps_q24 = (uint32_t)std::floor(o.epsilon * 16777216.0);             // once, here: the kernel compares integers
+    const double inv_scale = std::ldexp(1.0, -o.frac_bits);
+    const dim3 grid((unsigned)((o.n_games + kBlock - 1) / kBlock)), block(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+    switch (o.n) {
+    case 2: hipLaunchKernelGGL((tfe_mc_rollout_kernel<2, Canon, Record>), grid, block, 0, st, o, eps_q24, inv_scale, hist); break;
+    case 3: hipLaunchKernelGGL((tfe_mc_rollout_kernel<3, Canon, Record>), grid, block, 0, st, o, eps_q24, inv_scale, hist); break;
+    default: hipLaunchKernelGGL((tfe_mc_rollout_kernel<4, Canon, Record>), grid, block, 0, st, o, eps_q24, inv_scale, hist);
+    }
+}
 
-extern "C" int pulse_tfe_mc_rollout(const PulseTfeMCRollout* o, void* stream) {
-    const char* name = "pulse_tfe_mc_rollout";
+int rollout(const PulseTfeMCRollout* o, void* stream, bool canon, const char* name) {
     if (int rc = check_common(o, name)) return rc;
     if (!o->total_score) return fail_named(name, "total_score is null");
     if (!o->episode_reward) return fail_named(name, "episode_reward is null");
     if ((uintptr_t)o->total_score & 7u) return fail_named(name, "total_score must be 8-byte aligned");
     if ((uintptr_t)o->episode_reward & 3u) return fail_named(name, "episode_reward must be 4-byte aligned");
-    const uint32_t eps_q24 = (uint32_t)std::floor(o->epsilon * 16777216.0);            // once, here: the kernel compares integers
-    const double inv_scale = std::ldexp(1.0, -o->frac_bits);
-    const dim3 grid((unsigned)((o->n_games + kBlock - 1) / kBlock)), block(kBlock);
-    hipStream_t st = (hipStream_t)stream;
-    switch (o->n) {
-    case 2: hipLaunchKernelGGL(tfe_mc_rollout_kernel<2>, grid, block, 0, st, *o, eps_q24, inv_scale); break;
-    case 3: hipLaunchKernelGGL(tfe_mc_rollout_kernel<3>, grid, block, 0, st, *o, eps_q24, inv_scale); break;
-    default: hipLaunchKernelGGL(tfe_mc_rollout_kernel<4>, grid, block, 0, st, *o, eps_q24, inv_scale);
-    }
+    if (canon) launch_games<true, true>(*o, nullptr, stream); else launch_games<false, true>(*o, nullptr, stream);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int pulse_tfe_mc_rollout(const PulseTfeMCRollout* o, void* stream) {
+    if (int rc = rollout(o, stream, false, "pulse_tfe_mc_rollout")) return rc;
     return finish_launch("pulse_tfe_mc_rollout launch");
+}
+
+extern "C" int pulse_tfe_mc_rollout_canon(const PulseTfeMCRollout* o, void* stream) {
+    if (int rc = rollout(o, stream, true, "pulse_tfe_mc_rollout_canon")) return rc;
+    return finish_launch("pulse_tfe_mc_rollout_canon launch");
+}
+
+extern "C" int pulse_tfe_mc_evaluate(const PulseTfeMCEval* e, void* stream) {
+    const char* name = "pulse_tfe_mc_evaluate";
+    if (int rc = check_table(e, name)) return rc;
+    if (!(e->epsilon >= 0.0 && e->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
+    if (e->frac_bits < 0 || e->frac_bits > 30) return fail_named(name, "frac_bits must be in 0..30");
+    if (e->canonical != 0 && e->canonical != 1) return fail_named(name, "canonical must be 0 or 1");
+    if (!e->summary) return fail_named(name, "summary is null");
+    if (!e->max_tile_hist) return fail_named(name, "max_tile_hist is null");
+    if (((uintptr_t)e->summary & 7u) || ((uintptr_t)e->max_tile_hist & 7u)) return fail_named(name, "summary / max_tile_hist must be 8-byte aligned");
+    if ((uintptr_t)e->total_score & 7u) return fail_named(name, "total_score must be 8-byte aligned");
+    if ((uintptr_t)e->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
+    if (e->reserved0 != 0 || e->reserved1 != 0) return fail_named(name, "reserved0 / reserved1 must be 0 (zero-initialise the struct)");
+    PulseTfeMCRollout o{};                                                             // keys / steps / episode_reward stay null: not Record
+    o.entries = const_cast<void*>(e->entries); o.capacity = e->capacity;
+    o.n_games = e->n_games; o.n = e->n; o.max_steps = e->max_steps; o.frac_bits = e->frac_bits;
+    o.epsilon = e->epsilon;
+    o.env_seed = e->env_seed; o.agent_seed = e->agent_seed; o.tie_seed = e->tie_seed; o.board_id0 = e->board_id0; o.round = e->round;
+    o.lengths = e->lengths; o.total_score = e->total_score; o.stats = e->summary;
+    if (e->canonical) launch_games<true, false>(o, e->max_tile_hist, stream); else launch_games<false, false>(o, e->max_tile_hist, stream);
+    return finish_launch("pulse_tfe_mc_evaluate launch");
 }
 
 extern "C" int pulse_tfe_mc_learn(const PulseTfeMCLearn* o, void* stream) {

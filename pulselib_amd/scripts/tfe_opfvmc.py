@@ -3,7 +3,9 @@ round is a roll-out launch of `--tables` whole games against the table's policy 
 GAMMA 0.9, EPSILON 0.1, NUM_EPISODES 1,000,000 on a 3 x 3 board (the reference's scripts/TFE/mctrain.py with
 config/on_policy_first_visit_monte_carlo.yaml, which `--config PATH` reads as it is).  Per logging interval it prints what
 mctrain.py:54 prints: the average episode reward, the final score and the steps per second -- here of the rounds since the last
-line, each line costing one synchronisation."""
+line, each line costing one synchronisation.  `--symmetric` keeps a board's eight images under the symmetries of the square as one
+state; `--eval-every K --eval-games M` prints, every K rounds, the scores of M games under the greedy policy
+of the table as it stands (one evaluation launch, no trajectory; the same boards at every check)."""
 from __future__ import annotations
 
 import argparse
@@ -14,9 +16,10 @@ import torch
 from ..agents import OnPolicyFirstVisitMCTFEGPU
 
 
-def run(device, rounds, tables=65536, board=3, gamma=0.9, epsilon=0.1, seed=0, capacity=1 << 22, max_steps=1024, log_every=1, out=print):
+def run(device, rounds, tables=65536, board=3, gamma=0.9, epsilon=0.1, seed=0, capacity=1 << 22, max_steps=1024, log_every=1, out=print,
+        symmetric=False, eval_every=0, eval_games=None):
     agent = OnPolicyFirstVisitMCTFEGPU(device, tables, board_size=board, gamma=gamma, epsilon=epsilon, capacity=capacity, max_steps=max_steps,
-                                       seed=seed)
+                                       seed=seed, symmetric=symmetric)
     steps_before, t0 = 0, time.perf_counter()
     for r in range(rounds):
         agent.learn_batch()
@@ -27,6 +30,11 @@ def run(device, rounds, tables=65536, board=3, gamma=0.9, epsilon=0.1, seed=0, c
             out(f"Round {r}: episodes {(r + 1) * tables}, Avg episode reward: {reward:.2f}, Avg final score: {score:.2f}, Highest: {best}, "
                 f"Steps/sec: {(st['steps'] - steps_before) / (now - t0):.0f}, dropped {st['dropped']}, truncated {st['truncated']}")
             steps_before, t0 = st["steps"], now
+        if eval_every and (r + 1) % eval_every == 0:
+            e = agent.evaluate(n_games=eval_games)                          # (synchronises)
+            out(f"Round {r}: greedy policy over {e['games']} games: Avg final score: {e['mean_score']:.2f} +- {e['std_score'] / e['games'] ** .5:.2f}, "
+                f"Highest: {e['max_score']}, Avg length: {e['mean_length']:.1f}, truncated {e['truncated']}, moves with a table entry: "
+                f"{100 * e['coverage']:.1f} %, largest tile 2^k: {e['max_tile_hist']}")
     return agent
 
 
@@ -40,6 +48,9 @@ def main(argv=None):
     ap.add_argument("--max-steps", type=int, default=1024)
     ap.add_argument("--log-every", type=int, default=1, help="rounds per printed line")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--symmetric", action="store_true", help="one state per board up to rotation and reflection")
+    ap.add_argument("--eval-every", type=int, default=0, help="rounds between evaluations of the greedy policy (0: never)")
+    ap.add_argument("--eval-games", type=int, help="games per evaluation (default: --tables)")
     args = ap.parse_args(argv)
     gamma, epsilon, episodes = 0.9, 0.1, 1_000_000
     if args.config:
@@ -48,7 +59,8 @@ def main(argv=None):
             cfg = yaml.safe_load(fh)
         gamma, epsilon, episodes = float(cfg.get("GAMMA", gamma)), float(cfg.get("EPSILON", epsilon)), int(cfg.get("NUM_EPISODES", episodes))
     rounds = args.rounds if args.rounds is not None else max(1, -(-episodes // args.tables))
-    agent = run(torch.device("cuda"), rounds, args.tables, args.board, gamma, epsilon, args.seed, args.capacity, args.max_steps, args.log_every)
+    agent = run(torch.device("cuda"), rounds, args.tables, args.board, gamma, epsilon, args.seed, args.capacity, args.max_steps, args.log_every,
+                symmetric=args.symmetric, eval_every=args.eval_every, eval_games=args.eval_games)
     print(f"{rounds * args.tables} games in {agent.round} rounds, gamma {gamma}, epsilon {epsilon}: {len(agent.table())} states stored")
 
 

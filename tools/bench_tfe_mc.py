@@ -8,6 +8,10 @@ JSON line per batch size B (65,536 and 1,048,576 games per round by default):
   host    : the path it replaces, on the code of the parent commit: --host-games G (1,024) of the same games stepped through
             TFEBatch.step, every board copied to the host every step, the reference's OnPolicyFirstVisitMC choosing per board and
             learning per game.  Wall clock around a loop that synchronises itself.  A rate (board-steps/s): the number to beat.
+  evaluate: the evaluation launch (pulse_tfe_mc_evaluate, epsilon 0, B games, no trajectory) on the table the warm rounds left, --repeats
+            times between its own pair of HIP events after one untimed call: median and (min, max), games/s and board-steps/s from the
+            moves the launch counts.  (A greedy game that repeats a move which changes nothing on a full board runs to max_steps.)
+--symmetric runs everything on the table of canonical states (pulse_tfe_mc_rollout_canon).
 max_steps is 256 here (the longest game met while learning for 12 rounds of 4,096 games was 222 moves; cut games are counted in
 the line): the per-move buffers are B x max_steps x 9 bytes.  Nothing is asserted about the rates."""
 import argparse
@@ -37,10 +41,20 @@ def _spread(xs):
     return {"median": statistics.median(xs), "min": min(xs), "max": max(xs)}
 
 
-def device_rounds(dev, games, warmup, repeats, max_steps, capacity):
+def _timed_evaluate(agent, torch):
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    agent.eval_counters(clear=True)
+    ev[0].record()
+    agent.evaluate_launch()
+    ev[1].record()
+    ev[1].synchronize()
+    return ev[0].elapsed_time(ev[1]) * 1e-3, agent.eval_counters()
+
+
+def device_rounds(dev, games, warmup, repeats, max_steps, capacity, symmetric=False):
     import torch
     from pulselib_amd.agents import OnPolicyFirstVisitMCTFEGPU
-    kw = dict(board_size=3, gamma=.9, epsilon=.1, capacity=capacity, max_steps=max_steps, seed=0)
+    kw = dict(board_size=3, gamma=.9, epsilon=.1, capacity=capacity, max_steps=max_steps, seed=0, symmetric=symmetric)
     OnPolicyFirstVisitMCTFEGPU(dev, games, **kw).learn_batch()              # untimed: code objects, allocator
     torch.cuda.synchronize()
     agent = OnPolicyFirstVisitMCTFEGPU(dev, games, **kw)
@@ -53,13 +67,19 @@ def device_rounds(dev, games, warmup, repeats, max_steps, capacity):
     after = agent.stats()
     steps = (after["steps"] - before["steps"]) / repeats
     rnd = _spread([a + b for a, b in times])
-    return {"games": games, "board": 3, "max_steps": max_steps, "capacity": capacity, "warmup": warmup, "repeats": repeats,
+    states, mean_final_score = int((agent.entries[:, 0] != 0).sum().item()), agent.total_score.double().mean().item()
+    agent.evaluate()                                                        # untimed: the evaluation kernel's code object
+    evals = [_timed_evaluate(agent, torch) for _ in range(repeats)]
+    ev_s, e = _spread([s for s, _ in evals]), evals[-1][1]
+    return {"games": games, "board": 3, "symmetric": symmetric, "max_steps": max_steps, "capacity": capacity, "warmup": warmup, "repeats": repeats,
             "cold": {"rollout_s": cold[0], "learn_s": cold[1], "steps": cold_steps, "episodes_per_s": games / sum(cold),
                      "board_steps_per_s": cold_steps / sum(cold)},
             "warm": {"rollout_s": _spread([a for a, _ in times]), "learn_s": _spread([b for _, b in times]), "round_s": rnd,
                      "steps_per_round": steps, "episodes_per_s": games / rnd["median"], "board_steps_per_s": steps / rnd["median"]},
-            "states_stored": int((agent.entries[:, 0] != 0).sum().item()), "dropped": after["dropped"], "truncated": after["truncated"],
-            "mean_final_score": agent.total_score.double().mean().item()}
+            "evaluate": {"seconds": ev_s, "moves": e["moves"], "games_per_s": games / ev_s["median"], "board_steps_per_s": e["moves"] / ev_s["median"],
+                         "mean_score": e["mean_score"], "std_score": e["std_score"], "mean_length": e["mean_length"], "truncated": e["truncated"],
+                         "coverage": e["coverage"]},
+            "states_stored": states, "dropped": after["dropped"], "truncated": after["truncated"], "mean_final_score": mean_final_score}
 
 
 def host_rounds(dev, games, rounds=2):
@@ -102,6 +122,7 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--max-steps", type=int, default=256)
     ap.add_argument("--host-games", type=int, default=1024, help="0: skip the host path")
+    ap.add_argument("--symmetric", action="store_true", help="the table of canonical states")
     args = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
@@ -110,7 +131,7 @@ def main(argv=None):
     for games in args.games:
         # 128 slots per game, 2^25 (4 GB) at the most: a first round of 4,096 games stores ~19 states per game, later ones fewer; `dropped` tells if it was too few
         capacity = 1 << max(16, (games * 128 - 1).bit_length())
-        print(json.dumps(device_rounds(dev, games, args.warmup, args.repeats, args.max_steps, min(capacity, 1 << 25))), flush=True)
+        print(json.dumps(device_rounds(dev, games, args.warmup, args.repeats, args.max_steps, min(capacity, 1 << 25), args.symmetric)), flush=True)
     if args.host_games:
         print(json.dumps(host_rounds(dev, args.host_games)), flush=True)
 
