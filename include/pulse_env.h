@@ -597,6 +597,38 @@ typedef struct PulseTfeMCEval {
 } PulseTfeMCEval;
 int pulse_tfe_mc_evaluate(const PulseTfeMCEval* o, void* stream);
 
+/* ---- 2048 Monte-Carlo table: dst += src over entries, one launch.  Growing a table (src = the old table, dst = a larger zeroed
+ * one), folding a plain table into a symmetric one (canonical = 1), adding the tables of two agents and loading a checkpoint
+ * (src = a dense array of entries) are all this call.
+ *
+ * src: src_entries entries of PULSE_TFE_MC_ENTRY_BYTES in the table's layout, 128-byte aligned.  It is only SCANNED, one lane per
+ * slot, never probed: a hash table with holes or a dense array of ANY length >= 1; an entry with key 0 is skipped.  dst: a
+ * pulse_tfe_mc table (capacity a power of two, caller-owned).  Per live source entry: with canonical = 1 the key's n * n nibbles are
+ * unpacked, (key_c, j*) = canon of that board, and the eight values go to cnt[amap[j*][a]] / sum[amap[j*][a]]; with canonical = 0 key and
+ * values go as they are.  The key is found or inserted in dst by the learner's bounded probe (at most PULSE_TFE_MC_MAX_PROBE slots)
+ * and cnt[a], sum[a] are added there with 64-bit integer atomics for every action whose cnt | sum is non-zero.  Integer adds: dst read
+ * as a map key -> {cnt, sum} does not depend on scheduling.  An entry with no room adds NOTHING of itself and counts in stats[2].
+ * stats, device int64[4], ADDED TO: [0] live source entries, [1] entries placed, [2] entries dropped, [3] not written.  One
+ * launch, counters reduced per workgroup, no wait between workgroups, no loop whose end depends on table content.
+ *
+ * Limits.  (1) dst is NOT zeroed by the call: a new table is the caller's to zero.  (2) The room the fixed-point rule leaves -- 2^32
+ * adds per cell -- now covers the SUM of the merged tables' counts per cell.  (3) frac_bits, gamma and the board side of the two
+ * tables must agree; the kernel cannot see that (the Python layer refuses).  (4) With canonical = 1 only the low n * n nibbles of
+ * a source key are read: a key with bits above them is folded as the state of its low nibbles, and nothing counts that.
+ * PULSE_EINVAL, before anything is launched: src or dst null or not 128-byte aligned, src_entries < 1 (or 2^32 and more: one lane
+ * per slot in one launch), dst_capacity no power of two, overlapping byte ranges, canonical outside {0, 1}, n outside 2..4 (also when it is not
+ * used), stats null or not 8-byte aligned, non-zero reserved0. */
+typedef struct PulseTfeMCMerge {
+    const void* src;
+    uint64_t src_entries;
+    void* dst;
+    uint64_t dst_capacity;
+    int32_t n, canonical;
+    int64_t* stats;                     /* int64[4] */
+    int64_t reserved0;
+} PulseTfeMCMerge;
+int pulse_tfe_mc_table_merge(const PulseTfeMCMerge* o, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

@@ -141,6 +141,11 @@ class TfeMCEval(C.Structure):
         (n, C.c_void_p) for n in ("summary", "max_tile_hist", "total_score", "lengths")] + [("reserved1", C.c_int64)]
 
 
+class TfeMCMerge(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("src_entries", C.c_uint64), ("dst", C.c_void_p), ("dst_capacity", C.c_uint64),
+                ("n", C.c_int32), ("canonical", C.c_int32), ("stats", C.c_void_p), ("reserved0", C.c_int64)]
+
+
 # every symbol include/pulse_env.h declares: (restype, argtypes)
 _P, _I32, _U32, _U64, _F32, _I64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_float, C.c_int64
 SYMBOLS = {
@@ -196,6 +201,7 @@ SYMBOLS = {
     "pulse_tfe_mc_learn": (C.c_int, [_P, _P]),
     "pulse_tfe_mc_rollout_canon": (C.c_int, [_P, _P]),
     "pulse_tfe_mc_evaluate": (C.c_int, [_P, _P]),
+    "pulse_tfe_mc_table_merge": (C.c_int, [_P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

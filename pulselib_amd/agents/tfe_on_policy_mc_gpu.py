@@ -16,7 +16,11 @@ board by the action mapped back; the learner is the same.  `evaluate()` (`pulse_
 recording them and returns score statistics reduced in the launch.
 
 `learn_on_host`, `greedy_on_host`, `first_visit_flags_on_host` and `run_mask_flags_on_host` are the host's statement of the same
-arithmetic, in numpy and pure Python; `transforms_on_host`, `canon_on_host`, `ACTION_MAP` and `fold_table_on_host` that of the symmetries."""
+arithmetic, in numpy and pure Python; `transforms_on_host`, `canon_on_host`, `ACTION_MAP` and `fold_table_on_host` that of the symmetries.
+
+The table as a whole goes through one more launch, `pulse_tfe_mc_table_merge`: dst += src over entries by key.
+`merge_from` adds another agent's table (folding a plain one into a symmetric one), `grow` re-inserts the table into a larger one,
+`to_symmetric` folds it, `save` / `load` write and read an .npz of the live rows; `merge_tables_on_host` is the host's statement."""
 from __future__ import annotations
 
 import ctypes as C
@@ -32,6 +36,7 @@ TIE_KEY = 0x20487C01F11B5                       # ... and the tie coins apart fr
 STATS = ("steps", "first_visits", "dropped", "truncated")
 EVAL_SUMMARY = ("games", "moves", "score_sum", "score_sq_sum", "max_score", "truncated", "moves_with_entry", "moves_greedy")
 EVAL_BINS = 16                                  # bin = log2 of the largest tile of the final board
+MERGE_STATS = ("live", "placed", "dropped")     # pulse_tfe_mc_table_merge's counters
 
 
 def frac_bits_for(gamma: float, max_steps: int) -> int:
@@ -115,6 +120,69 @@ def fold_table_on_host(table: dict, n: int) -> dict:
         for a in range(4):
             c[ACTION_MAP[j][a]] += int(cnt[a])
             s[ACTION_MAP[j][a]] += int(total[a])
+    return out
+
+
+def merge_tables_on_host(dst: dict, src: dict, n=None, canonical=False) -> dict:
+    """pulse_tfe_mc_table_merge on the host: dst += src over entries, in place and returned.  Every entry of `src` goes to its key -- with
+    `canonical` to its canonical key, cnt / sum permuted by ACTION_MAP[j*] (n: the board side the keys were packed for) -- and is added
+    to what `dst` holds there; `dst`'s own keys stay as they are.  `src` is not changed."""
+    if canonical and n is None:
+        raise ValueError("canonical=True needs the board side n")
+    for key, (cnt, total) in src.items():
+        key_c, j = canon_key_on_host(key, n) if canonical else (int(key), 0)
+        c, s = dst.setdefault(key_c, ([0] * 4, [0] * 4))
+        for a in range(4):
+            c[ACTION_MAP[j][a]] += int(cnt[a])
+            s[ACTION_MAP[j][a]] += int(total[a])
+    return dst
+
+
+# ------------------------------------------------------------------ the checkpoint file (save / load)
+CHECKPOINT_VERSION = 1
+CHECKPOINT_SCALARS = ("n", "gamma", "epsilon", "frac_bits", "max_steps", "seed", "board_id0", "round", "symmetric", "n_games")
+_CHECKPOINT_DTYPES = dict(gamma=np.float64, epsilon=np.float64, seed=np.uint64, board_id0=np.uint64)         # the others: int64
+
+
+def write_checkpoint(path, keys, cnt, total, **scalars) -> None:
+    """The table as an .npz of plain arrays (np.savez, no pickles): keys uint64[m] sorted ascending, cnt int64[m, 4], sum int64[m, 4],
+    the scalars of CHECKPOINT_SCALARS as 0-d arrays and `version`.  Rows are sorted here, so equal tables give equal arrays whatever
+    slots their entries had.  `path` is written as given (no suffix is appended)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    cnt, total = np.asarray(cnt, dtype=np.int64).reshape(-1, 4), np.asarray(total, dtype=np.int64).reshape(-1, 4)
+    if not len(keys) == len(cnt) == len(total):
+        raise ValueError("keys, cnt and sum must have one row per entry")
+    if sorted(scalars) != sorted(CHECKPOINT_SCALARS):
+        raise ValueError(f"a checkpoint holds exactly the scalars {CHECKPOINT_SCALARS}")
+    order = np.argsort(keys, kind="stable")
+    arrays = {k: np.array(scalars[k], dtype=_CHECKPOINT_DTYPES.get(k, np.int64)) for k in CHECKPOINT_SCALARS}
+    with open(path, "wb") as fh:
+        np.savez(fh, version=np.array(CHECKPOINT_VERSION, dtype=np.int64), keys=keys[order], cnt=cnt[order], sum=total[order], **arrays)
+
+
+def read_checkpoint(path, n=None) -> dict:
+    """What write_checkpoint wrote (np.load with allow_pickle=False): the three arrays and the scalars as Python numbers.  ValueError
+    for another format version, a missing or misshapen array, keys that are not strictly ascending from above 0 or do not fit n * n
+    cells, and, where `n` is given, a file of another board side."""
+    with np.load(path, allow_pickle=False) as f:
+        missing = [k for k in ("version", "keys", "cnt", "sum") + CHECKPOINT_SCALARS if k not in f.files]
+        if missing:
+            raise ValueError(f"{path}: not a 2048 Monte-Carlo checkpoint (no {missing})")
+        if int(f["version"]) != CHECKPOINT_VERSION:
+            raise ValueError(f"{path}: format version {int(f['version'])}, this package reads {CHECKPOINT_VERSION}")
+        out = {k: f[k] for k in ("keys", "cnt", "sum")}
+        for k in CHECKPOINT_SCALARS:
+            if f[k].shape != ():
+                raise ValueError(f"{path}: {k} is not a scalar")
+            out[k] = float(f[k]) if k in ("gamma", "epsilon") else int(f[k])
+    out["symmetric"] = bool(out["symmetric"])
+    keys, m = out["keys"], len(out["keys"])
+    if keys.dtype != np.uint64 or keys.ndim != 1 or any(out[k].dtype != np.int64 or out[k].shape != (m, 4) for k in ("cnt", "sum")):
+        raise ValueError(f"{path}: keys must be uint64[m], cnt and sum int64[m, 4]")
+    if not 2 <= out["n"] <= 4 or (n is not None and out["n"] != int(n)):
+        raise ValueError(f"{path}: board side {out['n']}" + (f", expected {int(n)}" if n is not None else " outside 2..4"))
+    if m and (int(keys[0]) == 0 or not bool((keys[1:] > keys[:-1]).all()) or int(keys[-1]) >> (4 * out["n"] ** 2)):
+        raise ValueError(f"{path}: keys must be strictly ascending, non-zero and fit the {out['n']} x {out['n']} cells")
     return out
 
 
@@ -223,10 +291,7 @@ class OnPolicyFirstVisitMCTFEGPU:
         self.frac_bits = frac_bits_for(self.gamma, self.max_steps)
         self.seed, self.board_id0, self.round, self.symmetric = int(seed), int(board_id0), 0, bool(symmetric)
         self.env_seed, self.agent_seed, self.tie_seed = self.seed, self.seed ^ AGENT_KEY, self.seed ^ TIE_KEY
-        words = ENTRY_BYTES // 8
-        self._storage = torch.zeros(self.capacity * words + words, dtype=torch.int64, device=device)
-        skip = (-self._storage.data_ptr() % ENTRY_BYTES) // 8
-        self.entries = self._storage[skip:skip + self.capacity * words].view(self.capacity, words)   # 128-byte aligned
+        self.entries = self._new_table(self.capacity)
         self.keys = torch.zeros((self.max_steps, self.n_games), dtype=torch.int64, device=device)    # (uint64 words)
         self.steps = torch.zeros((self.max_steps, self.n_games), dtype=torch.uint8, device=device)
         self.lengths = torch.zeros(self.n_games, dtype=torch.int32, device=device)
@@ -234,6 +299,15 @@ class OnPolicyFirstVisitMCTFEGPU:
         self.episode_reward = torch.zeros(self.n_games, dtype=torch.int32, device=device)
         self.counters = torch.zeros(8, dtype=torch.int64, device=device)
         self._eval = torch.zeros(len(EVAL_SUMMARY) + EVAL_BINS, dtype=torch.int64, device=device)     # evaluate(): summary, then the histogram
+        self._merge = torch.zeros(4, dtype=torch.int64, device=device)                                # merge_from(): live, placed, dropped
+
+    def _new_table(self, rows):
+        """int64[rows, 16] on the device, zeroed and 128-byte aligned: a table of `rows` slots, or a dense array of entries."""
+        import torch
+        words = ENTRY_BYTES // 8
+        storage = torch.zeros(rows * words + words, dtype=torch.int64, device=self.device)
+        skip = (-storage.data_ptr() % ENTRY_BYTES) // 8
+        return storage[skip:skip + rows * words].view(rows, words)
 
     # ------------------------------------------------------------------ the launches
     def _head(self, o):
@@ -267,6 +341,130 @@ class OnPolicyFirstVisitMCTFEGPU:
         self.learn()
         self.round += 1
         return self
+
+    # ------------------------------------------------------------------ the table as a whole
+    def _merge_launch(self, src, dst, canonical, stats):
+        """pulse_tfe_mc_table_merge: dst += src over entries, both int64[rows, 16] device tensors; the three counters are added to `stats`."""
+        o = _native.TfeMCMerge()
+        o.src, o.src_entries, o.dst, o.dst_capacity = src.data_ptr(), src.shape[0], dst.data_ptr(), dst.shape[0]
+        o.n, o.canonical, o.stats = self.n, int(canonical), stats.data_ptr()
+        _native.check(self._lib.pulse_tfe_mc_table_merge(C.byref(o), _native.current_stream(self.device)), "pulse_tfe_mc_table_merge")
+
+    def dense_entries(self, keys, cnt, total):
+        """keys uint64[m], cnt / sum int64[m, 4] of the host as a dense array of entries on the device (int64[m, 16], 128-byte aligned):
+        what merge_from takes and a checkpoint load uploads."""
+        import torch
+        rows = np.zeros((len(keys), ENTRY_BYTES // 8), dtype=np.int64)
+        rows[:, 0] = np.asarray(keys, dtype=np.uint64).view(np.int64)
+        rows[:, 1:5], rows[:, 5:9] = cnt, total
+        dense = self._new_table(len(keys))
+        dense.copy_(torch.from_numpy(rows))
+        return dense
+
+    def merge_from(self, other, canonical=None):
+        """This table += `other`: another agent's table, or an int64[m, 16] device tensor of entries (a dense array or a table with holes;
+        key 0 = skip).  One launch, no synchronisation; merge_stats() tells what it placed.  The two tables must share n, gamma and
+        frac_bits (ValueError otherwise: the sums would be on different scales).  A plain agent's table into a symmetric one is folded
+        on the way; a symmetric one into a plain one is refused.  For a tensor `canonical` says whether its keys are to be folded
+        (default: no; only a symmetric agent may ask for it)."""
+        import torch
+        if other is self:
+            raise ValueError("merge_from: an agent cannot be merged into itself (source and destination overlap)")
+        if isinstance(other, OnPolicyFirstVisitMCTFEGPU):
+            for name in ("n", "gamma", "frac_bits"):
+                if getattr(other, name) != getattr(self, name):
+                    raise ValueError(f"merge_from: {name} differs ({getattr(other, name)} against {getattr(self, name)})")
+            if other.symmetric and not self.symmetric:
+                raise ValueError("merge_from: a table of canonical states cannot be merged into a plain one")
+            if canonical is not None:
+                raise ValueError("merge_from: `canonical` is for a tensor of entries; between agents it follows from `symmetric`")
+            src, canonical = other.entries, self.symmetric and not other.symmetric
+        else:
+            src, canonical = other, bool(canonical)
+            if not (isinstance(src, torch.Tensor) and src.dtype == torch.int64 and src.dim() == 2 and src.shape[1] == ENTRY_BYTES // 8
+                    and src.shape[0] >= 1 and src.is_contiguous()):
+                raise ValueError("merge_from takes an agent or a contiguous int64[m, 16] tensor of entries, m >= 1")
+            if canonical and not self.symmetric:
+                raise ValueError("merge_from: canonical=True needs a symmetric destination")
+        if src.device != self.entries.device:
+            raise ValueError(f"merge_from: the source is on {src.device}, the table on {self.entries.device}")
+        self._merge_launch(src, self.entries, canonical, self._merge)
+        return self
+
+    def merge_stats(self, clear=False) -> dict:
+        """What the merge_from launches since the last clear added up to: live source entries, entries placed, entries dropped for want
+        of room (nothing of a dropped entry is added).  Synchronises; with clear the counters are zeroed afterwards."""
+        out = dict(zip(MERGE_STATS, self._merge.cpu().tolist()[:3]))
+        if clear:
+            self._merge.zero_()
+        return out
+
+    def occupancy(self) -> int:
+        """The number of live slots (synchronises)."""
+        return int((self.entries[:, 0] != 0).sum().item())
+
+    def grow(self, capacity):
+        """The same map in a new zeroed table of `capacity` slots (a power of two; smaller is allowed): one merge launch and one read-back.
+        If an entry finds no room there, RuntimeError, and the agent keeps the table it had.  Round, seeds, trajectory buffers and
+        counters are untouched; the roll-out reads the table only by key, so the games to come are those of an agent that had
+        this capacity from the start."""
+        import torch
+        capacity = int(capacity)
+        if capacity < 1 or capacity & (capacity - 1):
+            raise ValueError("capacity must be a power of two")
+        table, stats = self._new_table(capacity), torch.zeros(4, dtype=torch.int64, device=self.device)
+        self._merge_launch(self.entries, table, False, stats)
+        live, placed, dropped = stats.cpu().tolist()[:3]
+        if dropped or placed != live:
+            raise RuntimeError(f"grow({capacity}): {dropped} of {live} entries found no room; the table of {self.capacity} slots is kept")
+        self.entries, self.capacity = table, capacity
+        return self
+
+    def _like(self, n_games=None, capacity=None, symmetric=None):
+        return type(self)(self.device, self.n_games if n_games is None else n_games, board_size=self.n, gamma=self.gamma, epsilon=self.epsilon,
+                          capacity=self.capacity if capacity is None else capacity, max_steps=self.max_steps, seed=self.seed,
+                          board_id0=self.board_id0, symmetric=self.symmetric if symmetric is None else symmetric)
+
+    def to_symmetric(self, capacity=None):
+        """A new agent with symmetric=True that holds the fold of this plain table (fold_table_on_host, as one launch), with this agent's
+        seeds, round and shapes; `capacity` defaults to this one's.  RuntimeError if an entry found no room."""
+        if self.symmetric:
+            raise ValueError("to_symmetric: the table already holds canonical states")
+        out = self._like(capacity=capacity, symmetric=True)
+        out.round = self.round
+        st = out.merge_from(self).merge_stats()
+        if st["dropped"]:
+            raise RuntimeError(f"to_symmetric: {st['dropped']} of {st['live']} entries found no room in {out.capacity} slots")
+        return out
+
+    def save(self, path):
+        """The table and what a continued run needs as an .npz (write_checkpoint).  The live rows are compacted on the device; only
+        they cross to the host."""
+        e = self.entries
+        rows = e[e[:, 0] != 0].cpu().numpy()
+        write_checkpoint(path, np.ascontiguousarray(rows[:, 0]).view(np.uint64), rows[:, 1:5], rows[:, 5:9], n=self.n, gamma=self.gamma,
+                         epsilon=self.epsilon, frac_bits=self.frac_bits, max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0,
+                         round=self.round, symmetric=int(self.symmetric), n_games=self.n_games)
+
+    @classmethod
+    def load(cls, path, device, capacity=None, n_games=None):
+        """The agent save() wrote: the rows are uploaded as a dense array of entries and merged into a zeroed table of `capacity` slots
+        (default: the smallest power of two >= 4 m and >= 2^12), round and seeds restored.  With the saved n_games it continues the
+        run the saved agent would have continued (another n_games plays other boards: round r starts at board_id0 + r * n_games)."""
+        f = read_checkpoint(path)
+        m = len(f["keys"])
+        if capacity is None:
+            capacity = max(1 << 12, 1 << max(4 * m - 1, 0).bit_length())
+        agent = cls(device, f["n_games"] if n_games is None else n_games, board_size=f["n"], gamma=f["gamma"], epsilon=f["epsilon"],
+                    capacity=capacity, max_steps=f["max_steps"], seed=f["seed"], board_id0=f["board_id0"], symmetric=f["symmetric"])
+        if agent.frac_bits != f["frac_bits"]:
+            raise ValueError(f"{path}: frac_bits {f['frac_bits']}, but gamma {f['gamma']} and max_steps {f['max_steps']} give {agent.frac_bits}")
+        if m:
+            st = agent.merge_from(agent.dense_entries(f["keys"], f["cnt"], f["sum"])).merge_stats()
+            if st["dropped"] or st["placed"] != m:
+                raise RuntimeError(f"{path}: {st['dropped']} of {m} entries found no room in {agent.capacity} slots")
+        agent.round = f["round"]
+        return agent
 
     # ------------------------------------------------------------------ read-back (the only syncs)
     def table(self) -> dict:
@@ -353,5 +551,6 @@ class OnPolicyFirstVisitMCTFEGPU:
         """An empty table, zeroed counters, round 0."""
         self.entries.zero_()
         self.counters.zero_()
+        self._merge.zero_()
         self.round = 0
         return self

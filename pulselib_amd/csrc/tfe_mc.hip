@@ -17,6 +17,9 @@
 // eight images under the symmetries of the square, the greedy action is taken in that image's frame and mapped back
 // (pulse_tfe_mc_rollout_canon).  Not Record: no trajectory is written and the scores are reduced in the launch
 // (pulse_tfe_mc_evaluate).  The table is only read by all of them.
+//
+// pulse_tfe_mc_table_merge adds one array of entries into a table by key: growing, folding a plain table
+// into a symmetric one, adding two agents' tables and loading a checkpoint are that one launch.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -87,12 +90,9 @@ constexpr uint64_t kActionMap = 0xc61b6cb1394e93e4ull, kActionUnmap = 0xc61b6cb1
 __device__ __forceinline__ int map_action(uint64_t map, int j, int a) { return (int)((map >> (8 * j + 2 * a)) & 3ull); }
 
 // (key_c, j*) of a board: the smallest of the keys of its eight images and the smallest j whose image has it.  The cells' nibbles
-// are taken once; every image is NB * NB shift-ors of them at constant positions -- registers only.
+// (e) are taken once; every image is NB * NB shift-ors of them at constant positions -- registers only.
 template <int NB>
-__device__ __forceinline__ uint64_t canon_key(const int (&b)[NB * NB], int& j_min) {
-    uint32_t e[NB * NB];
-#pragma unroll
-    for (int i = 0; i < NB * NB; ++i) e[i] = b[i] > 0 ? (uint32_t)min(31 - __clz(b[i]), 15) : 0u;         // pack_cells' nibble
+__device__ __forceinline__ uint64_t canon_nibbles(const uint32_t (&e)[NB * NB], int& j_min) {
     uint64_t best = 0ull;
     j_min = 0;
 #pragma unroll
@@ -112,6 +112,21 @@ __device__ __forceinline__ uint64_t canon_key(const int (&b)[NB * NB], int& j_mi
         best = j == 0 || less ? key : best;
     }
     return best;
+}
+// ... of a board of tiles (the roll-outs), and of a state key (the merge launch): one text of the images above for both
+template <int NB>
+__device__ __forceinline__ uint64_t canon_key(const int (&b)[NB * NB], int& j_min) {
+    uint32_t e[NB * NB];
+#pragma unroll
+    for (int i = 0; i < NB * NB; ++i) e[i] = b[i] > 0 ? (uint32_t)min(31 - __clz(b[i]), 15) : 0u;         // pack_cells' nibble
+    return canon_nibbles<NB>(e, j_min);
+}
+template <int NB>
+__device__ __forceinline__ uint64_t canon_of_key(uint64_t key, int& j_min) {
+    uint32_t e[NB * NB];
+#pragma unroll
+    for (int i = 0; i < NB * NB; ++i) e[i] = (uint32_t)(key >> (4 * i)) & 15u;
+    return canon_nibbles<NB>(e, j_min);
 }
 
 // pulse_tfe_mc_evaluate's counters: summary[8] then max_tile_hist[16], reduced in LDS and added once per workgroup and non-zero bin.
@@ -236,6 +251,46 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_learn_kernel(const PulseTfeMCLe
     add_stats(wg, o.stats, 1, n_added, 2, n_dropped);
 }
 
+// dst += src over entries (pulse_tfe_mc_table_merge).  One lane per SOURCE slot: the source is scanned, not
+// probed, and an empty slot costs its one line whatever the mapping, so lanes per entry would save no traffic.  NB = 0: keys as they
+// are; NB = 2..4: every key goes to its canonical key with the eight values permuted by amap[j*] (the fold).  The adds are the
+// learner's integer atomics, so dst as a map does not depend on the order; an entry with no room adds nothing of itself.
+template <int NB>
+__global__ __launch_bounds__(kBlock) void tfe_mc_merge_kernel(const PulseTfeMCMerge o) {
+    __shared__ unsigned long long wg[2];
+    if (threadIdx.x < 2) wg[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    unsigned long long n_live = 0ull, n_dropped = 0ull;
+    if (i < o.src_entries) {
+        const Entry& e = static_cast<const Entry*>(o.src)[i];
+        uint64_t key = e.key;
+        if (key) {
+            n_live = 1ull;
+            long long cnt[4], sum[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) { cnt[a] = e.cnt[a]; sum[a] = e.sum[a]; }
+            int j = 0;
+            if constexpr (NB > 0) key = canon_of_key<NB>(key, j);
+            Entry* table = static_cast<Entry*>(o.dst);
+            const long long s = find_or_insert<kMaxProbe>(table, 0, o.dst_capacity, key);
+            if (s >= 0) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+                    if (cnt[a] | sum[a]) {
+                        const int at = NB > 0 ? map_action(kActionMap, j, a) : a;      // (an address, not a register index)
+                        atomicAdd(reinterpret_cast<unsigned long long*>(&table[s].sum[at]), (unsigned long long)sum[a]);
+                        atomicAdd(reinterpret_cast<unsigned long long*>(&table[s].cnt[at]), (unsigned long long)cnt[a]);
+                    }
+            } else {
+                n_dropped = 1ull;
+            }
+        }
+    }
+    add_stats(wg, o.stats, 0, n_live, 2, n_dropped);                                   // (ends behind a barrier: wg is final)
+    if (threadIdx.x == 2 && wg[0] != wg[1]) atomicAdd(reinterpret_cast<unsigned long long*>(o.stats) + 1, wg[0] - wg[1]);   // placed
+}
+
 // The largest frac_bits <= 30 with G_max * 2^frac_bits * 2^32 < 2^62, G_max = r_max * min(max_steps, 1 / (1 - gamma)); -1 = none.
 int max_frac_bits(double gamma, int max_steps) {
     const double horizon = 1.0 / (1.0 - gamma);                                        // (gamma = 1: inf)
@@ -331,6 +386,39 @@ extern "C" int pulse_tfe_mc_evaluate(const PulseTfeMCEval* e, void* stream) {
     o.lengths = e->lengths; o.total_score = e->total_score; o.stats = e->summary;
     if (e->canonical) launch_games<true, false>(o, e->max_tile_hist, stream); else launch_games<false, false>(o, e->max_tile_hist, stream);
     return finish_launch("pulse_tfe_mc_evaluate launch");
+}
+
+extern "C" int pulse_tfe_mc_table_merge(const PulseTfeMCMerge* o, void* stream) {
+    const char* name = "pulse_tfe_mc_table_merge";
+    constexpr uint64_t kLine = PULSE_TFE_MC_ENTRY_BYTES;
+    if (!o) return fail_named(name, "options are null");
+    if (!o->src) return fail_named(name, "src is null");
+    if (!o->dst) return fail_named(name, "dst is null");
+    if ((uintptr_t)o->src & (kLine - 1)) return fail_named(name, "src must be 128-byte aligned");
+    if ((uintptr_t)o->dst & (kLine - 1)) return fail_named(name, "dst must be 128-byte aligned");
+    if (o->src_entries < 1) return fail_named(name, "src_entries must be positive");
+    if (o->src_entries > 0xFFFFFFFFull) return fail_named(name, "src_entries must be below 2^32 (one lane per slot, one launch)");
+    if (o->dst_capacity == 0 || (o->dst_capacity & (o->dst_capacity - 1)) || o->dst_capacity > (UINT64_MAX >> 8))
+        return fail_named(name, "dst_capacity must be a power of two");
+    {
+        const uint64_t s0 = (uint64_t)(uintptr_t)o->src, s1 = s0 + o->src_entries * kLine;
+        const uint64_t d0 = (uint64_t)(uintptr_t)o->dst, d1 = d0 + o->dst_capacity * kLine;
+        if (s0 < d1 && d0 < s1) return fail_named(name, "src and dst overlap");
+    }
+    if (o->canonical != 0 && o->canonical != 1) return fail_named(name, "canonical must be 0 or 1");
+    if (o->n < 2 || o->n > 4) return fail_named(name, "board side n must be 2..4 (64-bit state key)");
+    if (!o->stats) return fail_named(name, "stats is null");
+    if ((uintptr_t)o->stats & 7u) return fail_named(name, "stats must be 8-byte aligned");
+    if (o->reserved0 != 0) return fail_named(name, "reserved0 must be 0 (zero-initialise the struct)");
+    const dim3 grid((unsigned)((o->src_entries + kBlock - 1) / kBlock)), block(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+    switch (o->canonical ? o->n : 0) {
+    case 0: hipLaunchKernelGGL(tfe_mc_merge_kernel<0>, grid, block, 0, st, *o); break;
+    case 2: hipLaunchKernelGGL(tfe_mc_merge_kernel<2>, grid, block, 0, st, *o); break;
+    case 3: hipLaunchKernelGGL(tfe_mc_merge_kernel<3>, grid, block, 0, st, *o); break;
+    default: hipLaunchKernelGGL(tfe_mc_merge_kernel<4>, grid, block, 0, st, *o);
+    }
+    return finish_launch("pulse_tfe_mc_table_merge launch");
 }
 
 extern "C" int pulse_tfe_mc_learn(const PulseTfeMCLearn* o, void* stream) {

@@ -11,6 +11,12 @@ JSON line per batch size B (65,536 and 1,048,576 games per round by default):
   evaluate: the evaluation launch (pulse_tfe_mc_evaluate, epsilon 0, B games, no trajectory) on the table the warm rounds left, --repeats
             times between its own pair of HIP events after one untimed call: median and (min, max), games/s and board-steps/s from the
             moves the launch counts.  (A greedy game that repeats a move which changes nothing on a full board runs to max_steps.)
+--table-ops times pulse_tfe_mc_table_merge instead, on the plain table that one cold and --warmup rounds of
+--table-games G (65,536) games leave in 2^22 slots, each launch between its own pair of HIP events, --table-untimed U (3) untimed and
+--repeats timed repetitions into a freshly zeroed destination: grow (the 2^22 slots into 2^23), fold (the 2^23 slots into a symmetric table of 2^23)
+and load (the live rows as a dense array into 2^23).  Per launch: live entries, ms (median, min, max) and source bytes scanned per
+second; and, measured in the same run on a 3 x 3 table, the host path the fold replaces: table(), then fold_table_on_host.  One
+JSON line per launch, also appended to profiles/tfe_mc/bench_tfe_mc_table.jsonl.
 --symmetric runs everything on the table of canonical states (pulse_tfe_mc_rollout_canon).
 max_steps is 256 here (the longest game met while learning for 12 rounds of 4,096 games was 222 moves; cut games are counted in
 the line): the per-move buffers are B x max_steps x 9 bytes.  Nothing is asserted about the rates."""
@@ -82,6 +88,66 @@ def device_rounds(dev, games, warmup, repeats, max_steps, capacity, symmetric=Fa
             "states_stored": states, "dropped": after["dropped"], "truncated": after["truncated"], "mean_final_score": mean_final_score}
 
 
+def _timed_merge(agent, torch, src, capacity, canonical, untimed=3, repeats=5):
+    """(seconds per repetition, the counters of the last one): src merged into a zeroed table of `capacity` slots, every time a new one"""
+    stats = torch.zeros(4, dtype=torch.int64, device=agent.device)
+    dst = agent._new_table(capacity)
+    times = []
+    for i in range(untimed + repeats):
+        dst.zero_()
+        stats.zero_()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        agent._merge_launch(src, dst, canonical, stats)
+        ev[1].record()
+        ev[1].synchronize()
+        if i >= untimed:
+            times.append(ev[0].elapsed_time(ev[1]) * 1e-3)
+    return times, dict(zip(("live", "placed", "dropped"), stats.cpu().tolist())), dst
+
+
+def table_ops(dev, games, warmup, untimed, repeats, max_steps, path):
+    import torch
+    from pulselib_amd.agents import OnPolicyFirstVisitMCTFEGPU
+    from pulselib_amd.agents.tfe_on_policy_mc_gpu import ENTRY_BYTES, fold_table_on_host
+    agent = OnPolicyFirstVisitMCTFEGPU(dev, games, board_size=3, gamma=.9, epsilon=.1, capacity=1 << 22, max_steps=max_steps, seed=0)
+    for _ in range(1 + warmup):
+        agent.learn_batch()
+    dropped = agent.stats()["dropped"]
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+
+    def emit(entry):
+        print(json.dumps(entry), flush=True)
+        with open(path, "a") as fh:
+            fh.write(json.dumps(entry) + "\n")
+
+    def line(op, src, times, st, **more):
+        s = _spread(times)
+        emit({"op": op, "board": 3, "games": games, "rounds": 1 + warmup, "untimed": untimed, "repeats": repeats, "src_entries": src.shape[0],
+              "live": st["live"], "placed": st["placed"], "dropped": st["dropped"], "ms": {k: v * 1e3 for k, v in s.items()},
+              "src_bytes_per_s": src.shape[0] * ENTRY_BYTES / s["median"], "learn_dropped": dropped, **more})
+
+    times, st, grown = _timed_merge(agent, torch, agent.entries, 1 << 23, False, untimed, repeats)
+    line("grow 2^22 -> 2^23", agent.entries, times, st, dst_capacity=1 << 23)
+    times, st, sym = _timed_merge(agent, torch, grown, 1 << 23, True, untimed, repeats)
+    line("fold 2^23 -> symmetric 2^23", grown, times, st, dst_capacity=1 << 23)
+    folded = int((sym[:, 0] != 0).sum().item())                              # the canonical states the fold left: the host's count below
+    live = grown[grown[:, 0] != 0]
+    dense = agent._new_table(live.shape[0])                                  # (128-byte aligned)
+    dense.copy_(live)
+    del grown, sym, live
+    times, st, _ = _timed_merge(agent, torch, dense, 1 << 23, False, untimed, repeats)
+    line("load dense -> 2^23", dense, times, st, dst_capacity=1 << 23)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    table = agent.table()
+    t1 = time.perf_counter()
+    host = fold_table_on_host(table, 3)
+    t2 = time.perf_counter()
+    emit({"op": "host: table(), then fold_table_on_host", "board": 3, "games": games, "live": len(table), "canonical": len(host), "table_s": t1 - t0,
+          "fold_s": t2 - t1, "canonical_states_on_device": folded})
+
+
 def host_rounds(dev, games, rounds=2):
     """The interpreter's loop: one TFEBatch.step per move, a host copy of every board, a Python dict per game."""
     import torch
@@ -123,11 +189,18 @@ def main(argv=None):
     ap.add_argument("--max-steps", type=int, default=256)
     ap.add_argument("--host-games", type=int, default=1024, help="0: skip the host path")
     ap.add_argument("--symmetric", action="store_true", help="the table of canonical states")
+    ap.add_argument("--table-ops", action="store_true", help="time the table-merge launch (grow, fold, dense load) instead of the rounds")
+    ap.add_argument("--table-games", type=int, default=65536, help="games per round that fill the table for --table-ops")
+    ap.add_argument("--table-untimed", type=int, default=3, help="untimed repetitions of each merge launch for --table-ops")
+    ap.add_argument("--table-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "tfe_mc", "bench_tfe_mc_table.jsonl"))
     args = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_tfe_mc needs the MI355X: no timing is taken on a CPU")
     dev = torch.device("cuda:0")
+    if args.table_ops:
+        table_ops(dev, args.table_games, args.warmup, args.table_untimed, args.repeats, args.max_steps, args.table_out)
+        return
     for games in args.games:
         # 128 slots per game, 2^25 (4 GB) at the most: a first round of 4,096 games stores ~19 states per game, later ones fewer; `dropped` tells if it was too few
         capacity = 1 << max(16, (games * 128 - 1).bit_length())
