@@ -629,6 +629,48 @@ typedef struct PulseTfeMCMerge {
 } PulseTfeMCMerge;
 int pulse_tfe_mc_table_merge(const PulseTfeMCMerge* o, void* stream);
 
+/* ---- 2048 Monte-Carlo control on AFTERSTATES: the table holds V(board after the move, before the spawn), not Q(state, action).
+ * Five entry points on the structs above, with the checks of their namesakes (messages carry the new names); the plain ones are
+ * unchanged.
+ *
+ * The table is the same table.  The key is the afterstate's key; cnt[0] / sum[0] hold the count and the fixed-point sum of the returns
+ * that FOLLOWED the afterstate, cnt[1..3] and sum[1..3] stay 0:
+ *   v(key) = cnt[0] > 0 ? (double)sum[0] / (double)cnt[0] * 2^-frac_bits : 0.0.
+ * frac_bits obeys the same bound (the stored return is bounded by the same G_max).  pulse_tfe_mc_table_merge with canonical = 0
+ * (grow, add, load) works on such a table as it is; with canonical = 1 it would permute the slots, so the fold is a call of its own.
+ *
+ * pulse_tfe_mc_rollout_after / pulse_tfe_mc_rollout_after_canon: the games of pulse_tfe_mc_rollout (same reset, spawns and agent
+ * draws {x, y, ..} = Philox4x32-10(agent_seed, board_id0 + g, t)).  At move t on board B, for a = 0..3: (B_a, score_a) = the move of B
+ * by a without a spawn, r_a = the environment's reward of score_a (bit length - 1, 0 for 0), key_a = the key of B_a (_canon: the
+ * smallest key of its eight images; a value has no action, so nothing is mapped), v_a = v(entry of key_a) by a read-only lookup of at
+ * most PULSE_TFE_MC_MAX_PROBE slots, 0.0 without an entry, q_a = r_a + gamma * v_a in float64 (one rounding per operation, IEEE
+ * division).  A move that changes nothing is a candidate like any other: the environment accepts it and spawns after it.
+ *   none of the four keys has an entry, or (x >> 8) < floor(epsilon * 2^24)   ->   a = y >> 30;
+ *   otherwise a = 0..3 in order, a larger q replaces the best, an equal q replaces it iff bit 31 of word a - 1 of
+ *   Philox4x32-10(tie_seed, key of B, round) is set -- the plain key of the state before the move, in both forms.
+ * Recorded: keys[t * n_games + g] = key_a of the action taken, steps = a | r_a << 2 | first << 7 with a the BOARD's action (a replay
+ * through pulse_tfe_step works in both forms), first = key_a differs from the key recorded at t - 1 (1 at t = 0).  Equal
+ * afterstates of a game are consecutive: a move keeps the tile sum and the sum rises from one distinct state to the next, so equal
+ * afterstates come from one run of an unchanged full board, where every unchanged move has the board itself as its afterstate and
+ * the move that ends the run merges tiles -- its afterstate has an empty cell.  lengths, total_score, episode_reward and stats as
+ * pulse_tfe_mc_rollout.
+ *
+ * pulse_tfe_mc_learn_after: t = lengths[g] - 1 .. 0; at a step with `first` set the key is found or inserted and
+ * sum[0] += llrint(ldexp(G, frac_bits)), cnt[0] += 1 with G as it stands; THEN G = gamma * G + reward.  So an afterstate collects the
+ * return that follows it, and r_a + gamma * v_a above is the reference's G_t.  Counters as pulse_tfe_mc_learn.
+ *
+ * pulse_tfe_mc_evaluate_after: the games of the two roll-outs above (by `canonical`) without a trajectory; summary and histogram as
+ * pulse_tfe_mc_evaluate, summary[6] = moves where at least one of the four keys had an entry.  gamma: the policy's (PulseTfeMCEval
+ * holds none); PULSE_EINVAL outside [0, 1].
+ *
+ * pulse_tfe_mc_table_fold_after: pulse_tfe_mc_table_merge's checks and launch for the fold of a value table -- every key goes to its
+ * canonical key, cnt[a] / sum[a] go to slot a as they are.  canonical must be 1. */
+int pulse_tfe_mc_rollout_after(const PulseTfeMCRollout* o, void* stream);
+int pulse_tfe_mc_rollout_after_canon(const PulseTfeMCRollout* o, void* stream);
+int pulse_tfe_mc_learn_after(const PulseTfeMCLearn* o, void* stream);
+int pulse_tfe_mc_evaluate_after(const PulseTfeMCEval* o, double gamma, void* stream);
+int pulse_tfe_mc_table_fold_after(const PulseTfeMCMerge* o, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

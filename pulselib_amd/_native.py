@@ -202,6 +202,11 @@ SYMBOLS = {
     "pulse_tfe_mc_rollout_canon": (C.c_int, [_P, _P]),
     "pulse_tfe_mc_evaluate": (C.c_int, [_P, _P]),
     "pulse_tfe_mc_table_merge": (C.c_int, [_P, _P]),
+    "pulse_tfe_mc_rollout_after": (C.c_int, [_P, _P]),
+    "pulse_tfe_mc_rollout_after_canon": (C.c_int, [_P, _P]),
+    "pulse_tfe_mc_learn_after": (C.c_int, [_P, _P]),
+    "pulse_tfe_mc_evaluate_after": (C.c_int, [_P, C.c_double, _P]),
+    "pulse_tfe_mc_table_fold_after": (C.c_int, [_P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

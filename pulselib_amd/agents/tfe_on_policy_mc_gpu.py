@@ -20,10 +20,17 @@ arithmetic, in numpy and pure Python; `transforms_on_host`, `canon_on_host`, `AC
 
 The table as a whole goes through one more launch, `pulse_tfe_mc_table_merge`: dst += src over entries by key.
 `merge_from` adds another agent's table (folding a plain one into a symmetric one), `grow` re-inserts the table into a larger one,
-`to_symmetric` folds it, `save` / `load` write and read an .npz of the live rows; `merge_tables_on_host` is the host's statement."""
+`to_symmetric` folds it, `save` / `load` write and read an .npz of the live rows; `merge_tables_on_host` is the host's statement.
+
+`afterstate=True` learns V(afterstate) instead of Q(state, action): the key is the board after the move and
+before the spawn, cnt[0] / sum[0] of its entry hold the returns that followed it, and the policy takes the largest
+reward + gamma * v among the board's four afterstates (`pulse_tfe_mc_rollout_after`, `_after_canon`, `pulse_tfe_mc_learn_after`,
+`pulse_tfe_mc_evaluate_after`, `pulse_tfe_mc_table_fold_after`).  `move_on_host`, `afterstates_on_host`, `greedy_after_on_host`,
+`learn_after_on_host` and `fold_values_on_host` are the host's statement of it."""
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -138,24 +145,38 @@ def merge_tables_on_host(dst: dict, src: dict, n=None, canonical=False) -> dict:
     return dst
 
 
+def fold_values_on_host(table: dict, n: int) -> dict:
+    """A plain VALUE table {key: (cnt[4], sum[4])} as the table of canonical afterstates: every entry goes to its canonical key with
+    cnt / sum in the slots they have (a value has no action to map), and entries that meet are added."""
+    out = {}
+    for key, (cnt, total) in table.items():
+        c, s = out.setdefault(canon_key_on_host(key, n)[0], ([0] * 4, [0] * 4))
+        for a in range(4):
+            c[a] += int(cnt[a])
+            s[a] += int(total[a])
+    return out
+
+
 # ------------------------------------------------------------------ the checkpoint file (save / load)
 CHECKPOINT_VERSION = 1
 CHECKPOINT_SCALARS = ("n", "gamma", "epsilon", "frac_bits", "max_steps", "seed", "board_id0", "round", "symmetric", "n_games")
+CHECKPOINT_OPTIONAL = ("afterstate",)           # written by save(); a file without it holds a Q(state, action) table
 _CHECKPOINT_DTYPES = dict(gamma=np.float64, epsilon=np.float64, seed=np.uint64, board_id0=np.uint64)         # the others: int64
 
 
 def write_checkpoint(path, keys, cnt, total, **scalars) -> None:
     """The table as an .npz of plain arrays (np.savez, no pickles): keys uint64[m] sorted ascending, cnt int64[m, 4], sum int64[m, 4],
     the scalars of CHECKPOINT_SCALARS as 0-d arrays and `version`.  Rows are sorted here, so equal tables give equal arrays whatever
-    slots their entries had.  `path` is written as given (no suffix is appended)."""
+    slots their entries had.  `path` is written as given (no suffix is appended).  `afterstate=` (optional, 0 or 1) is written as one
+    more scalar: the kind of the table."""
     keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
     cnt, total = np.asarray(cnt, dtype=np.int64).reshape(-1, 4), np.asarray(total, dtype=np.int64).reshape(-1, 4)
     if not len(keys) == len(cnt) == len(total):
         raise ValueError("keys, cnt and sum must have one row per entry")
-    if sorted(scalars) != sorted(CHECKPOINT_SCALARS):
+    if sorted(k for k in scalars if k not in CHECKPOINT_OPTIONAL) != sorted(CHECKPOINT_SCALARS):
         raise ValueError(f"a checkpoint holds exactly the scalars {CHECKPOINT_SCALARS}")
     order = np.argsort(keys, kind="stable")
-    arrays = {k: np.array(scalars[k], dtype=_CHECKPOINT_DTYPES.get(k, np.int64)) for k in CHECKPOINT_SCALARS}
+    arrays = {k: np.array(scalars[k], dtype=_CHECKPOINT_DTYPES.get(k, np.int64)) for k in CHECKPOINT_SCALARS + CHECKPOINT_OPTIONAL if k in scalars}
     with open(path, "wb") as fh:
         np.savez(fh, version=np.array(CHECKPOINT_VERSION, dtype=np.int64), keys=keys[order], cnt=cnt[order], sum=total[order], **arrays)
 
@@ -163,7 +184,7 @@ def write_checkpoint(path, keys, cnt, total, **scalars) -> None:
 def read_checkpoint(path, n=None) -> dict:
     """What write_checkpoint wrote (np.load with allow_pickle=False): the three arrays and the scalars as Python numbers.  ValueError
     for another format version, a missing or misshapen array, keys that are not strictly ascending from above 0 or do not fit n * n
-    cells, and, where `n` is given, a file of another board side."""
+    cells, and, where `n` is given, a file of another board side.  `afterstate` is False for a file without that scalar."""
     with np.load(path, allow_pickle=False) as f:
         missing = [k for k in ("version", "keys", "cnt", "sum") + CHECKPOINT_SCALARS if k not in f.files]
         if missing:
@@ -175,6 +196,7 @@ def read_checkpoint(path, n=None) -> dict:
             if f[k].shape != ():
                 raise ValueError(f"{path}: {k} is not a scalar")
             out[k] = float(f[k]) if k in ("gamma", "epsilon") else int(f[k])
+        out["afterstate"] = "afterstate" in f.files and bool(int(f["afterstate"]))
     out["symmetric"] = bool(out["symmetric"])
     keys, m = out["keys"], len(out["keys"])
     if keys.dtype != np.uint64 or keys.ndim != 1 or any(out[k].dtype != np.int64 or out[k].shape != (m, 4) for k in ("cnt", "sum")):
@@ -254,6 +276,107 @@ def learn_on_host(keys, steps, lengths, gamma: float, frac_bits: int, table: dic
     return table
 
 
+# ------------------------------------------------------------------ afterstates
+@functools.lru_cache(maxsize=None)
+def _transform_lists(n: int) -> tuple:
+    return tuple(tuple(row) for row in transforms_on_host(n).tolist())
+
+
+def move_cells_on_host(cells, n: int, a: int):
+    """(cells, merge score) of move `a` WITHOUT the spawn on the n * n tiles of a board as a list (TFE.py:154-178): the board rotated
+    `a` times, every row squashed to the left -- a tile merges with an equal neighbour once --, rotated back."""
+    src = _transform_lists(n)[a]
+    out, score = [0] * (n * n), 0
+    for r in range(0, n * n, n):
+        res, w, merged = [0] * n, 0, False
+        for c in range(n):
+            val = cells[src[r + c]]
+            if val == 0:
+                continue
+            if res[w] == 0:
+                res[w] = val
+            elif res[w] == val and not merged:
+                res[w], score, merged = 2 * val, score + 2 * val, True
+            else:
+                w, merged = w + 1, False
+                res[w] = val
+        for c in range(n):
+            out[src[r + c]] = res[c]
+    return out, score
+
+
+def move_on_host(board, a):
+    """(board, merge score) of move `a` without the spawn: int[n, n] in, a new int64[n, n] out (move_cells_on_host)."""
+    board = np.asarray(board, dtype=np.int64)
+    n = board.shape[-1]
+    cells, score = move_cells_on_host(board.reshape(-1).tolist(), n, int(a))
+    return np.array(cells, dtype=np.int64).reshape(n, n), score
+
+
+def reward_of_score(score: int) -> int:
+    """TFE.py:185-187: bit length - 1 of the merge score of a move, 0 for 0."""
+    return int(score).bit_length() - 1 if score > 0 else 0
+
+
+def afterstates_on_host(board, symmetric=False):
+    """(keys[4], rewards[4]) of the four moves of a board: the afterstate's key (its canonical key with `symmetric`) and the reward."""
+    board = np.asarray(board)
+    n, cells = board.shape[-1], board.reshape(-1).tolist()
+    keys, rewards = [], []
+    for a in range(4):
+        after, score = move_cells_on_host(cells, n, a)
+        logs = [min(v.bit_length() - 1, 15) if v > 0 else 0 for v in after]
+        images = _transform_lists(n) if symmetric else _transform_lists(n)[:1]
+        keys.append(min(sum(logs[s] << (4 * i) for i, s in enumerate(src)) for src in images))
+        rewards.append(reward_of_score(score))
+    return keys, rewards
+
+
+def v_of_entry(entry, frac_bits: int) -> float:
+    cnt, total = entry
+    return float(int(total[0])) / float(int(cnt[0])) * 2.0 ** -frac_bits if cnt[0] > 0 else 0.0
+
+
+def greedy_after_on_host(board, table: dict, gamma: float, frac_bits: int, tie_seed: int, round: int, symmetric=False, philox=philox4x32):
+    """The afterstate roll-out's greedy rule on one board: (action or None, keys[4], rewards[4]).  q_a = r_a + gamma * v(key_a) in
+    float64, 0.0 for a key without an entry; a = 0..3 in order, a larger q replaces the best, an equal q replaces it iff bit 31 of
+    word a - 1 of philox(tie_seed, plain key of the board, round) is set.  None: none of the four keys has an entry."""
+    keys, rewards = afterstates_on_host(board, symmetric)
+    if not any(k in table for k in keys):
+        return None, keys, rewards
+    q = [float(r) + gamma * (v_of_entry(table[k], frac_bits) if k in table else 0.0) for k, r in zip(keys, rewards)]
+    coins = None
+    best, best_q = 0, q[0]
+    for a in (1, 2, 3):
+        if q[a] > best_q:
+            best, best_q = a, q[a]
+        elif q[a] == best_q:
+            if coins is None:
+                coins = [int(w) for w in philox(tie_seed, pack_board(board), round)]
+            if coins[a - 1] >> 31:
+                best = a
+    return best, keys, rewards
+
+
+def learn_after_on_host(keys, steps, lengths, gamma: float, frac_bits: int, table: dict) -> dict:
+    """pulse_tfe_mc_learn_after on the host, in learn_on_host's shapes.  Per game t = length - 1 .. 0: at a flagged step
+    sum[0] += round-half-even(G * 2^frac_bits), cnt[0] += 1 with G as it stands, THEN G = gamma * G + reward -- an afterstate
+    collects the return that follows it."""
+    keys, steps = np.asarray(keys, dtype=np.uint64), np.asarray(steps, dtype=np.uint8)
+    if keys.ndim == 1:
+        keys, steps = keys[:, None], steps[:, None]
+    for g, length in enumerate(np.asarray(lengths).reshape(-1).tolist()):
+        tail = 0.0
+        for t in range(int(length) - 1, -1, -1):
+            s = int(steps[t, g])
+            if s & 0x80:
+                cnt, total = table.setdefault(int(keys[t, g]), ([0] * 4, [0] * 4))
+                total[0] += round(math.ldexp(tail, frac_bits))
+                cnt[0] += 1
+            tail = gamma * tail + float((s >> 2) & 31)
+    return table
+
+
 def eval_summary_on_host(words) -> dict:
     """pulse_tfe_mc_evaluate's 8 + 16 counters as a dict: the words by name, the histogram, and mean / std (sample standard deviation,
     from the exact integer sums) / max of the final score, the mean length and the share of moves whose state had a table entry."""
@@ -273,7 +396,7 @@ class OnPolicyFirstVisitMCTFEGPU:
     (`table`, `q`, `greedy`, `stats`, `trajectory`, the per-game arrays' `.cpu()`) synchronises."""
 
     def __init__(self, device, n_games, board_size=3, gamma=.9, epsilon=.1, capacity=1 << 22, max_steps=1024, seed=0, board_id0=0,
-                 symmetric=False):
+                 symmetric=False, afterstate=False):
         import torch
         device = _native.gpu_device(device, "OnPolicyFirstVisitMCTFEGPU")
         if not 2 <= int(board_size) <= 4:
@@ -290,6 +413,7 @@ class OnPolicyFirstVisitMCTFEGPU:
         self.gamma, self.epsilon = float(gamma), float(epsilon)
         self.frac_bits = frac_bits_for(self.gamma, self.max_steps)
         self.seed, self.board_id0, self.round, self.symmetric = int(seed), int(board_id0), 0, bool(symmetric)
+        self.afterstate = bool(afterstate)              # the table holds V(afterstate) in cnt[0] / sum[0]
         self.env_seed, self.agent_seed, self.tie_seed = self.seed, self.seed ^ AGENT_KEY, self.seed ^ TIE_KEY
         self.entries = self._new_table(self.capacity)
         self.keys = torch.zeros((self.max_steps, self.n_games), dtype=torch.int64, device=device)    # (uint64 words)
@@ -322,18 +446,20 @@ class OnPolicyFirstVisitMCTFEGPU:
 
     def rollout(self):
         """One launch: n_games games under the table as it stands (round `self.round`), into keys / steps / lengths / scores.
-        With `symmetric` the recorded keys and actions are those of the canonical frame (pulse_tfe_mc_rollout_canon)."""
+        With `symmetric` the recorded keys and actions are those of the canonical frame (pulse_tfe_mc_rollout_canon).  With
+        `afterstate` the keys are those of the boards after the moves and the actions the board's own (pulse_tfe_mc_rollout_after*)."""
         o = self._head(_native.TfeMCRollout())
         o.env_seed, o.agent_seed, o.tie_seed, o.board_id0, o.round = self.env_seed, self.agent_seed, self.tie_seed, self.round_board_id0(), self.round
         o.total_score, o.episode_reward = self.total_score.data_ptr(), self.episode_reward.data_ptr()
-        name = "pulse_tfe_mc_rollout_canon" if self.symmetric else "pulse_tfe_mc_rollout"
+        name = "pulse_tfe_mc_rollout" + ("_after" if self.afterstate else "") + ("_canon" if self.symmetric else "")
         _native.check(getattr(self._lib, name)(C.byref(o), _native.current_stream(self.device)), name)
         return self
 
     def learn(self):
         """One launch: the first-visit returns of the games last played, into the table."""
         o = self._head(_native.TfeMCLearn())
-        _native.check(self._lib.pulse_tfe_mc_learn(C.byref(o), _native.current_stream(self.device)), "pulse_tfe_mc_learn")
+        name = "pulse_tfe_mc_learn_after" if self.afterstate else "pulse_tfe_mc_learn"
+        _native.check(getattr(self._lib, name)(C.byref(o), _native.current_stream(self.device)), name)
         return self
 
     def learn_batch(self):
@@ -344,11 +470,13 @@ class OnPolicyFirstVisitMCTFEGPU:
 
     # ------------------------------------------------------------------ the table as a whole
     def _merge_launch(self, src, dst, canonical, stats):
-        """pulse_tfe_mc_table_merge: dst += src over entries, both int64[rows, 16] device tensors; the three counters are added to `stats`."""
+        """pulse_tfe_mc_table_merge: dst += src over entries, both int64[rows, 16] device tensors; the three counters are added to `stats`.
+        The fold of a value table (`afterstate` and canonical) is pulse_tfe_mc_table_fold_after: the slots stay where they are."""
         o = _native.TfeMCMerge()
         o.src, o.src_entries, o.dst, o.dst_capacity = src.data_ptr(), src.shape[0], dst.data_ptr(), dst.shape[0]
         o.n, o.canonical, o.stats = self.n, int(canonical), stats.data_ptr()
-        _native.check(self._lib.pulse_tfe_mc_table_merge(C.byref(o), _native.current_stream(self.device)), "pulse_tfe_mc_table_merge")
+        name = "pulse_tfe_mc_table_fold_after" if self.afterstate and canonical else "pulse_tfe_mc_table_merge"
+        _native.check(getattr(self._lib, name)(C.byref(o), _native.current_stream(self.device)), name)
 
     def dense_entries(self, keys, cnt, total):
         """keys uint64[m], cnt / sum int64[m, 4] of the host as a dense array of entries on the device (int64[m, 16], 128-byte aligned):
@@ -366,7 +494,8 @@ class OnPolicyFirstVisitMCTFEGPU:
         key 0 = skip).  One launch, no synchronisation; merge_stats() tells what it placed.  The two tables must share n, gamma and
         frac_bits (ValueError otherwise: the sums would be on different scales).  A plain agent's table into a symmetric one is folded
         on the way; a symmetric one into a plain one is refused.  For a tensor `canonical` says whether its keys are to be folded
-        (default: no; only a symmetric agent may ask for it)."""
+        (default: no; only a symmetric agent may ask for it).  A Q(state, action) table and a table of afterstate values do not mix:
+        an agent of the other kind is refused (a tensor is taken as entries of this agent's kind)."""
         import torch
         if other is self:
             raise ValueError("merge_from: an agent cannot be merged into itself (source and destination overlap)")
@@ -374,6 +503,9 @@ class OnPolicyFirstVisitMCTFEGPU:
             for name in ("n", "gamma", "frac_bits"):
                 if getattr(other, name) != getattr(self, name):
                     raise ValueError(f"merge_from: {name} differs ({getattr(other, name)} against {getattr(self, name)})")
+            if other.afterstate != self.afterstate:
+                kinds = ("Q(state, action)", "afterstate values")
+                raise ValueError(f"merge_from: the source holds {kinds[other.afterstate]}, this table {kinds[self.afterstate]}")
             if other.symmetric and not self.symmetric:
                 raise ValueError("merge_from: a table of canonical states cannot be merged into a plain one")
             if canonical is not None:
@@ -423,10 +555,11 @@ class OnPolicyFirstVisitMCTFEGPU:
     def _like(self, n_games=None, capacity=None, symmetric=None):
         return type(self)(self.device, self.n_games if n_games is None else n_games, board_size=self.n, gamma=self.gamma, epsilon=self.epsilon,
                           capacity=self.capacity if capacity is None else capacity, max_steps=self.max_steps, seed=self.seed,
-                          board_id0=self.board_id0, symmetric=self.symmetric if symmetric is None else symmetric)
+                          board_id0=self.board_id0, symmetric=self.symmetric if symmetric is None else symmetric, afterstate=self.afterstate)
 
     def to_symmetric(self, capacity=None):
-        """A new agent with symmetric=True that holds the fold of this plain table (fold_table_on_host, as one launch), with this agent's
+        """A new agent with symmetric=True that holds the fold of this plain table (fold_table_on_host, with `afterstate`
+        fold_values_on_host, as one launch), with this agent's
         seeds, round and shapes; `capacity` defaults to this one's.  RuntimeError if an entry found no room."""
         if self.symmetric:
             raise ValueError("to_symmetric: the table already holds canonical states")
@@ -444,19 +577,24 @@ class OnPolicyFirstVisitMCTFEGPU:
         rows = e[e[:, 0] != 0].cpu().numpy()
         write_checkpoint(path, np.ascontiguousarray(rows[:, 0]).view(np.uint64), rows[:, 1:5], rows[:, 5:9], n=self.n, gamma=self.gamma,
                          epsilon=self.epsilon, frac_bits=self.frac_bits, max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0,
-                         round=self.round, symmetric=int(self.symmetric), n_games=self.n_games)
+                         round=self.round, symmetric=int(self.symmetric), n_games=self.n_games, afterstate=int(self.afterstate))
 
     @classmethod
-    def load(cls, path, device, capacity=None, n_games=None):
-        """The agent save() wrote: the rows are uploaded as a dense array of entries and merged into a zeroed table of `capacity` slots
+    def load(cls, path, device, capacity=None, n_games=None, afterstate=None):
+        """The agent save() wrote, of the kind it had (a file without an `afterstate` scalar holds a Q table; `afterstate`, where
+        given, is the kind the caller expects: ValueError for a file of the other kind): the rows are uploaded as a dense array of entries and merged into a zeroed table of `capacity` slots
         (default: the smallest power of two >= 4 m and >= 2^12), round and seeds restored.  With the saved n_games it continues the
         run the saved agent would have continued (another n_games plays other boards: round r starts at board_id0 + r * n_games)."""
         f = read_checkpoint(path)
+        if afterstate is not None and bool(afterstate) != f["afterstate"]:
+            kinds = ("Q(state, action)", "afterstate values")
+            raise ValueError(f"{path}: the checkpoint holds {kinds[f['afterstate']]}, not {kinds[bool(afterstate)]}")
         m = len(f["keys"])
         if capacity is None:
             capacity = max(1 << 12, 1 << max(4 * m - 1, 0).bit_length())
         agent = cls(device, f["n_games"] if n_games is None else n_games, board_size=f["n"], gamma=f["gamma"], epsilon=f["epsilon"],
-                    capacity=capacity, max_steps=f["max_steps"], seed=f["seed"], board_id0=f["board_id0"], symmetric=f["symmetric"])
+                    capacity=capacity, max_steps=f["max_steps"], seed=f["seed"], board_id0=f["board_id0"], symmetric=f["symmetric"],
+                    afterstate=f["afterstate"])
         if agent.frac_bits != f["frac_bits"]:
             raise ValueError(f"{path}: frac_bits {f['frac_bits']}, but gamma {f['gamma']} and max_steps {f['max_steps']} give {agent.frac_bits}")
         if m:
@@ -474,13 +612,25 @@ class OnPolicyFirstVisitMCTFEGPU:
         return {int(k): (r[1:5].tolist(), r[5:9].tolist()) for k, r in zip(rows[:, 0].view(np.uint64).tolist(), rows)}
 
     def q(self) -> dict:
-        """{(key, a): q} for the four actions of every stored state; a pair never seen reads 0.0."""
+        """{(key, a): q} for the four actions of every stored state; a pair never seen reads 0.0.  ValueError on an afterstate agent."""
+        if self.afterstate:
+            raise ValueError("q(): this table holds afterstate values; read v()")
         return {(k, a): v for k, e in self.table().items() for a, v in enumerate(q_of_entry(e, self.frac_bits))}
+
+    def v(self) -> dict:
+        """{key: v} for every stored afterstate.  ValueError on a Q(state, action) agent."""
+        if not self.afterstate:
+            raise ValueError("v(): this table holds Q(state, action); read q()")
+        return {k: v_of_entry(e, self.frac_bits) for k, e in self.table().items()}
 
     def greedy(self, keys, round=None) -> list:
         """The greedy action the roll-out of `round` takes in each of `keys` (the keys of boards as they lie), or None where the table
-        has no entry.  With `symmetric` a key is looked up as its canonical state and the action comes back in the board's own frame."""
+        has no entry.  With `symmetric` a key is looked up as its canonical state and the action comes back in the board's own frame.
+        On an afterstate agent `keys` are BOARDS (n x n tiles): the rule needs their four moves (greedy_after_on_host); None where
+        none of the four afterstates has an entry."""
         table, r = self.table(), self.round if round is None else int(round)
+        if getattr(self, "afterstate", False):
+            return [greedy_after_on_host(b, table, self.gamma, self.frac_bits, self.tie_seed, r, self.symmetric)[0] for b in keys]
         out = []
         for k in keys:
             k, j = canon_key_on_host(int(k), self.n) if self.symmetric else (int(k), 0)
@@ -493,7 +643,7 @@ class OnPolicyFirstVisitMCTFEGPU:
         return (self.board_id0 + (1 << 62)) & 0xFFFFFFFFFFFFFFFF
 
     def evaluate_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False):
-        """The launch of evaluate() alone (pulse_tfe_mc_evaluate): ADDS to the counters of `eval_counters` and reads nothing back.
+        """The launch of evaluate() alone (pulse_tfe_mc_evaluate, with `afterstate` pulse_tfe_mc_evaluate_after): ADDS to the counters of `eval_counters` and reads nothing back.
         Returns the per-game device tensors (total_score int64[B], lengths int32[B]) with per_game, else None."""
         import torch
         B = self.n_games if n_games is None else int(n_games)
@@ -507,7 +657,11 @@ class OnPolicyFirstVisitMCTFEGPU:
         if per_game:
             arrays = (torch.zeros(B, dtype=torch.int64, device=self.device), torch.zeros(B, dtype=torch.int32, device=self.device))
             o.total_score, o.lengths = arrays[0].data_ptr(), arrays[1].data_ptr()
-        _native.check(self._lib.pulse_tfe_mc_evaluate(C.byref(o), _native.current_stream(self.device)), "pulse_tfe_mc_evaluate")
+        stream = _native.current_stream(self.device)
+        if self.afterstate:
+            _native.check(self._lib.pulse_tfe_mc_evaluate_after(C.byref(o), self.gamma, stream), "pulse_tfe_mc_evaluate_after")
+        else:
+            _native.check(self._lib.pulse_tfe_mc_evaluate(C.byref(o), stream), "pulse_tfe_mc_evaluate")
         return arrays
 
     def eval_counters(self, clear=False) -> dict:

@@ -20,6 +20,11 @@
 //
 // pulse_tfe_mc_table_merge adds one array of entries into a table by key: growing, folding a plain table
 // into a symmetric one, adding two agents' tables and loading a checkpoint are that one launch.
+//
+// After: the table holds V(afterstate) -- the board after the move and before the spawn -- in cnt[0] / sum[0]
+// of the afterstate's key.  The game loop looks up the four afterstates of a board and takes the largest reward + gamma * v
+// (pulse_tfe_mc_rollout_after, _after_canon, pulse_tfe_mc_evaluate_after), the learner adds the return that FOLLOWS a step
+// (pulse_tfe_mc_learn_after), and the fold keeps the slots where they are (pulse_tfe_mc_table_fold_after).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -129,6 +134,83 @@ __device__ __forceinline__ uint64_t canon_of_key(uint64_t key, int& j_min) {
     return canon_nibbles<NB>(e, j_min);
 }
 
+// A value table's entry of `key`: find() with the first slot's key, cnt[0] and sum[0] already loaded by the
+// caller -- the four afterstates of a move load theirs before any of them is compared, so the four lines are in flight together.
+// The same slots in the same order as find(): the first was examined by the caller, probes 1 .. limit - 1 follow here.
+struct Value { long long cnt, sum; bool hit; };
+__device__ __forceinline__ Value value_after_first(const Entry* table, uint64_t slots, uint64_t key, uint64_t h, unsigned long long key0, long long cnt0, long long sum0) {
+    if (key0 == key) return Value{cnt0, sum0, true};
+    if (key0 == 0ull) return Value{0, 0, false};
+    const uint64_t limit = slots < kMaxProbe ? slots : kMaxProbe;
+    for (uint64_t probe = 1; probe < limit; ++probe) {
+        const Entry& e = table[(h + probe) & (slots - 1)];
+        const unsigned long long cur = e.key;
+        if (cur == key) return Value{e.cnt[0], e.sum[0], true};
+        if (cur == 0ull) break;
+    }
+    return Value{0, 0, false};
+}
+
+// The action of the afterstate policy on board b, a = 0..3 as the board lies (a value has no frame), and the key of the afterstate it
+// leads to.  any: one of the four keys had an entry; greedy: and it was not the epsilon branch.  r = this move's agent draw.
+template <int NB, bool Canon>
+__device__ __forceinline__ int afterstate_action(const int (&b)[NB * NB], const Entry* table, const PulseTfeMCRollout& o, uint32_t eps_q24,
+                                                 double inv_scale, const U4& r, uint64_t& key, bool& any, bool& greedy) {
+    // The four afterstates: keys and rewards only -- the caller moves the board itself again by the action returned.  One move at
+    // a time (not unrolled): the moved board is dead once its key is formed, and the kernel holds one text of the move for the four.
+    uint64_t ka[4] = {0ull, 0ull, 0ull, 0ull};
+    int ra[4] = {0, 0, 0, 0};
+#pragma unroll 1
+    for (int i = 0; i < 4; ++i) {
+        int c[NB * NB];
+#pragma unroll
+        for (int x = 0; x < NB * NB; ++x) c[x] = b[x];
+        const int sc = tfe_move<NB>(c, i);
+        const int rw = sc > 0 ? 31 - __clz(sc) : 0;
+        int jc = 0;
+        uint64_t k;
+        if constexpr (Canon) k = canon_key<NB>(c, jc); else k = pack_cells<NB * NB>(c);
+#pragma unroll
+        for (int x = 0; x < 4; ++x) { ka[x] = x == i ? k : ka[x]; ra[x] = x == i ? rw : ra[x]; }      // (selects, not addresses)
+    }
+    uint64_t h[4];
+    unsigned long long k0[4];
+    long long c0[4], s0[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) h[i] = mix64(ka[i]) & (o.capacity - 1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { k0[i] = table[h[i]].key; c0[i] = table[h[i]].cnt[0]; s0[i] = table[h[i]].sum[0]; }
+    double q[4];
+    any = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const Value v = value_after_first(table, o.capacity, ka[i], h[i], k0[i], c0[i], s0[i]);
+        any = any || v.hit;
+        const double val = v.cnt > 0 ? __dmul_rn(__ddiv_rn((double)v.sum, (double)v.cnt), inv_scale) : 0.0;
+        q[i] = __dadd_rn((double)ra[i], __dmul_rn(o.gamma, val));
+    }
+    greedy = any && (r.x >> 8) >= eps_q24;
+    int a = (int)(r.y >> 30);                             // no entry among the four, or the epsilon branch
+    if (greedy) {
+        const bool any_tie = q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3];
+        U4 coins{0u, 0u, 0u, 0u};
+        if (any_tie) coins = philox4x32(o.tie_seed, pack_cells<NB * NB>(b), o.round);      // the plain key of the state, in both forms
+        const uint32_t coin[3] = {coins.x >> 31, coins.y >> 31, coins.z >> 31};
+        a = 0;
+        double best_q = q[0];
+#pragma unroll
+        for (int i = 1; i < 4; ++i) {
+            const bool take = q[i] > best_q || (q[i] == best_q && coin[i - 1] != 0u);
+            a = take ? i : a;
+            best_q = q[i] > best_q ? q[i] : best_q;
+        }
+    }
+    key = ka[0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i) key = a == i ? ka[i] : key;
+    return a;
+}
+
 // pulse_tfe_mc_evaluate's counters: summary[8] then max_tile_hist[16], reduced in LDS and added once per workgroup and non-zero bin.
 constexpr int kEvalSummary = 8, kEvalBins = kEvalSummary + 16, kEvalMax = 4;
 __device__ __forceinline__ void flush_bins(unsigned long long* wg, int64_t* summary, int64_t* hist) {
@@ -140,9 +222,10 @@ __device__ __forceinline__ void flush_bins(unsigned long long* wg, int64_t* summ
     }
 }
 
-// The game loop.  <NB, false, true> is pulse_tfe_mc_rollout; Canon plays in the canonical frame; without Record nothing is written
-// per move, lengths / total_score are optional, o.stats is the evaluation's summary[8] and `hist` its max_tile_hist[16].
-template <int NB, bool Canon, bool Record>
+// The game loop.  <NB, false, true, false> is pulse_tfe_mc_rollout; Canon plays in the canonical frame; without Record nothing is
+// written per move, lengths / total_score are optional, o.stats is the evaluation's summary[8] and `hist` its max_tile_hist[16].
+// After: the policy reads the values of the board's four afterstates and the afterstate of the move taken is what is recorded.
+template <int NB, bool Canon, bool Record, bool After>
 __global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMCRollout o, uint32_t eps_q24, double inv_scale, int64_t* hist) {
     __shared__ unsigned long long wg[Record ? 2 : kEvalBins];
     if (threadIdx.x < (Record ? 2 : kEvalBins)) wg[threadIdx.x] = 0ull;
@@ -168,26 +251,37 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMC
         bool over = false;
         unsigned long long n_present = 0ull, n_greedy = 0ull;
         for (int t = 0; t < o.max_steps && !over; ++t) {
-            int j = 0;                                    // the board shows its canonical state under T_j
+            int a, score;                                 // a: the action in the frame of `key`
             uint64_t key;
-            if constexpr (Canon) key = canon_key<NB>(b, j); else key = pack_cells<NB * NB>(b);
-            taken = key == prev_key ? taken : 0u;
-            prev_key = key;
+            uint32_t first;
             const U4 r = philox4x32(o.agent_seed, id, (uint64_t)t);
-            const long long s = find<kMaxProbe>(table, 0, o.capacity, key);
-            int a = (int)(r.y >> 30);                     // no entry: the reference's uniform default policy; or the epsilon branch
-            if constexpr (Canon) a = map_action(kActionMap, j, a);                     // a: the action in the frame of `key`
-            if (s >= 0 && (r.x >> 8) >= eps_q24) a = greedy_action(table[s], key, o.tie_seed, o.round, inv_scale);
-            if constexpr (!Record) { n_present += s >= 0; n_greedy += s >= 0 && (r.x >> 8) >= eps_q24; }
-            int a_board = a;                                                           // ... and as the board lies
-            if constexpr (Canon) a_board = map_action(kActionUnmap, j, a);
-            const int score = tfe_move<NB>(b, a_board);                                // TFE.py:154-178
+            if constexpr (After) {
+                bool any, greedy;
+                a = afterstate_action<NB, Canon>(b, table, o, eps_q24, inv_scale, r, key, any, greedy);
+                if constexpr (!Record) { n_present += any; n_greedy += greedy; }
+                first = key != prev_key ? 1u : 0u;        // equal afterstates of a game are consecutive
+                prev_key = key;
+                score = tfe_move<NB>(b, a);               // the board moves again, so the four moved boards were never kept
+            } else {
+                int j = 0;                                // the board shows its canonical state under T_j
+                if constexpr (Canon) key = canon_key<NB>(b, j); else key = pack_cells<NB * NB>(b);
+                taken = key == prev_key ? taken : 0u;
+                prev_key = key;
+                const long long s = find<kMaxProbe>(table, 0, o.capacity, key);
+                a = (int)(r.y >> 30);                     // no entry: the reference's uniform default policy; or the epsilon branch
+                if constexpr (Canon) a = map_action(kActionMap, j, a);                     // a: the action in the frame of `key`
+                if (s >= 0 && (r.x >> 8) >= eps_q24) a = greedy_action(table[s], key, o.tie_seed, o.round, inv_scale);
+                if constexpr (!Record) { n_present += s >= 0; n_greedy += s >= 0 && (r.x >> 8) >= eps_q24; }
+                int a_board = a;                                                           // ... and as the board lies
+                if constexpr (Canon) a_board = map_action(kActionUnmap, j, a);
+                score = tfe_move<NB>(b, a_board);                                          // TFE.py:154-178
+                first = ((taken >> a) & 1u) ^ 1u;
+                taken |= 1u << a;
+            }
             const U4 rnd = philox4x32(o.env_seed, id, (uint64_t)t + 1ull);
             tfe_spawn<NB>(b, rnd.x, rnd.y);                                            // TFE.py:182 (always)
             over = tfe_over<NB>(b);                                                    // TFE.py:48-67
             const int reward = score > 0 ? 31 - __clz(score) : 0;                      // TFE.py:185-187 (<= 17 for n <= 4: five bits)
-            const uint32_t first = ((taken >> a) & 1u) ^ 1u;
-            taken |= 1u << a;
             if constexpr (Record) {
                 o.keys[(size_t)t * B + (size_t)g] = key;
                 o.steps[(size_t)t * B + (size_t)g] = (uint8_t)((uint32_t)a | ((uint32_t)reward & 31u) << 2 | first << 7);
@@ -219,6 +313,8 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMC
     else flush_bins(wg, o.stats, hist);
 }
 
+// After: a flagged step adds the return that FOLLOWS it (G before this step's reward enters) to cnt[0] / sum[0] of its key.
+template <bool After>
 __global__ __launch_bounds__(kBlock) void tfe_mc_learn_kernel(const PulseTfeMCLearn o) {
     __shared__ unsigned long long wg[2];
     if (threadIdx.x < 2) wg[threadIdx.x] = 0ull;
@@ -233,12 +329,12 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_learn_kernel(const PulseTfeMCLe
         double G = 0.0;
         for (int t = length - 1; t >= 0; --t) {
             const uint32_t st = o.steps[(size_t)t * B + (size_t)g];
-            G = __dadd_rn(__dmul_rn(o.gamma, G), (double)((st >> 2) & 31u));           // OnPolicyFirstVisit.py:28: G = gamma * G + reward
+            if constexpr (!After) G = __dadd_rn(__dmul_rn(o.gamma, G), (double)((st >> 2) & 31u));    // OnPolicyFirstVisit.py:28: G = gamma * G + reward
             if (st & 0x80u) {
                 const uint64_t key = o.keys[(size_t)t * B + (size_t)g];
                 const long long s = key ? find_or_insert<kMaxProbe>(table, 0, o.capacity, key) : -1;
                 if (s >= 0) {
-                    const int a = (int)(st & 3u);
+                    const int a = After ? 0 : (int)(st & 3u);
                     atomicAdd(reinterpret_cast<unsigned long long*>(&table[s].sum[a]), (unsigned long long)llrint(ldexp(G, o.frac_bits)));
                     atomicAdd(reinterpret_cast<unsigned long long*>(&table[s].cnt[a]), 1ull);
                     n_added += 1ull;
@@ -246,6 +342,7 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_learn_kernel(const PulseTfeMCLe
                     n_dropped += 1ull;
                 }
             }
+            if constexpr (After) G = __dadd_rn(__dmul_rn(o.gamma, G), (double)((st >> 2) & 31u));
         }
     }
     add_stats(wg, o.stats, 1, n_added, 2, n_dropped);
@@ -255,7 +352,8 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_learn_kernel(const PulseTfeMCLe
 // probed, and an empty slot costs its one line whatever the mapping, so lanes per entry would save no traffic.  NB = 0: keys as they
 // are; NB = 2..4: every key goes to its canonical key with the eight values permuted by amap[j*] (the fold).  The adds are the
 // learner's integer atomics, so dst as a map does not depend on the order; an entry with no room adds nothing of itself.
-template <int NB>
+// Values: the fold of a value table (pulse_tfe_mc_table_fold_after) -- the key goes to its canonical key, the slots stay where they are.
+template <int NB, bool Values>
 __global__ __launch_bounds__(kBlock) void tfe_mc_merge_kernel(const PulseTfeMCMerge o) {
     __shared__ unsigned long long wg[2];
     if (threadIdx.x < 2) wg[threadIdx.x] = 0ull;
@@ -278,7 +376,7 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_merge_kernel(const PulseTfeMCMe
 #pragma unroll
                 for (int a = 0; a < 4; ++a)
                     if (cnt[a] | sum[a]) {
-                        const int at = NB > 0 ? map_action(kActionMap, j, a) : a;      // (an address, not a register index)
+                        const int at = NB > 0 && !Values ? map_action(kActionMap, j, a) : a;      // (an address, not a register index)
                         atomicAdd(reinterpret_cast<unsigned long long*>(&table[s].sum[at]), (unsigned long long)sum[a]);
                         atomicAdd(reinterpret_cast<unsigned long long*>(&table[s].cnt[at]), (unsigned long long)cnt[a]);
                     }
@@ -330,46 +428,40 @@ int check_common(const O* o, const char* name) {
     return 0;
 }
 
-// The three launches of the game loop.  `o` is the caller's struct, or pulse_tfe_mc_evaluate's outputs in its shape.
-template <bool Canon, bool Record>
+// The launches of the game loop.  `o` is the caller's struct, or pulse_tfe_mc_evaluate's outputs in its shape.
+template <bool Canon, bool Record, bool After>
 void launch_games(const PulseTfeMCRollout& o, int64_t* hist, void* stream) {
     const uint32_t eps_q24 = (uint32_t)std::floor(o.epsilon * 16777216.0);             // once, here: the kernel compares integers
     const double inv_scale = std::ldexp(1.0, -o.frac_bits);
     const dim3 grid((unsigned)((o.n_games + kBlock - 1) / kBlock)), block(kBlock);
     hipStream_t st = (hipStream_t)stream;
     switch (o.n) {
-    case 2: hipLaunchKernelGGL((tfe_mc_rollout_kernel<2, Canon, Record>), grid, block, 0, st, o, eps_q24, inv_scale, hist); break;
-    case 3: hipLaunchKernelGGL((tfe_mc_rollout_kernel<3, Canon, Record>), grid, block, 0, st, o, eps_q24, inv_scale, hist); break;
-    default: hipLaunchKernelGGL((tfe_mc_rollout_kernel<4, Canon, Record>), grid, block, 0, st, o, eps_q24, inv_scale, hist);
+    case 2: hipLaunchKernelGGL((tfe_mc_rollout_kernel<2, Canon, Record, After>), grid, block, 0, st, o, eps_q24, inv_scale, hist); break;
+    case 3: hipLaunchKernelGGL((tfe_mc_rollout_kernel<3, Canon, Record, After>), grid, block, 0, st, o, eps_q24, inv_scale, hist); break;
+    default: hipLaunchKernelGGL((tfe_mc_rollout_kernel<4, Canon, Record, After>), grid, block, 0, st, o, eps_q24, inv_scale, hist);
     }
 }
 
-int rollout(const PulseTfeMCRollout* o, void* stream, bool canon, const char* name) {
+template <bool Record, bool After>
+void launch_games(const PulseTfeMCRollout& o, int64_t* hist, void* stream, bool canon) {
+    if (canon) launch_games<true, Record, After>(o, hist, stream); else launch_games<false, Record, After>(o, hist, stream);
+}
+
+int rollout(const PulseTfeMCRollout* o, void* stream, bool canon, bool after, const char* name) {
     if (int rc = check_common(o, name)) return rc;
     if (!o->total_score) return fail_named(name, "total_score is null");
     if (!o->episode_reward) return fail_named(name, "episode_reward is null");
     if ((uintptr_t)o->total_score & 7u) return fail_named(name, "total_score must be 8-byte aligned");
     if ((uintptr_t)o->episode_reward & 3u) return fail_named(name, "episode_reward must be 4-byte aligned");
-    if (canon) launch_games<true, true>(*o, nullptr, stream); else launch_games<false, true>(*o, nullptr, stream);
+    if (after) launch_games<true, true>(*o, nullptr, stream, canon); else launch_games<true, false>(*o, nullptr, stream, canon);
     return 0;
 }
 
-}  // namespace
-
-extern "C" int pulse_tfe_mc_rollout(const PulseTfeMCRollout* o, void* stream) {
-    if (int rc = rollout(o, stream, false, "pulse_tfe_mc_rollout")) return rc;
-    return finish_launch("pulse_tfe_mc_rollout launch");
-}
-
-extern "C" int pulse_tfe_mc_rollout_canon(const PulseTfeMCRollout* o, void* stream) {
-    if (int rc = rollout(o, stream, true, "pulse_tfe_mc_rollout_canon")) return rc;
-    return finish_launch("pulse_tfe_mc_rollout_canon launch");
-}
-
-extern "C" int pulse_tfe_mc_evaluate(const PulseTfeMCEval* e, void* stream) {
-    const char* name = "pulse_tfe_mc_evaluate";
+// pulse_tfe_mc_evaluate and pulse_tfe_mc_evaluate_after (gamma: the latter's, which its policy needs and the struct does not hold)
+int evaluate(const PulseTfeMCEval* e, double gamma, void* stream, bool after, const char* name) {
     if (int rc = check_table(e, name)) return rc;
     if (!(e->epsilon >= 0.0 && e->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
+    if (!(gamma >= 0.0 && gamma <= 1.0)) return fail_named(name, "gamma must be in [0, 1]");
     if (e->frac_bits < 0 || e->frac_bits > 30) return fail_named(name, "frac_bits must be in 0..30");
     if (e->canonical != 0 && e->canonical != 1) return fail_named(name, "canonical must be 0 or 1");
     if (!e->summary) return fail_named(name, "summary is null");
@@ -381,15 +473,16 @@ extern "C" int pulse_tfe_mc_evaluate(const PulseTfeMCEval* e, void* stream) {
     PulseTfeMCRollout o{};                                                             // keys / steps / episode_reward stay null: not Record
     o.entries = const_cast<void*>(e->entries); o.capacity = e->capacity;
     o.n_games = e->n_games; o.n = e->n; o.max_steps = e->max_steps; o.frac_bits = e->frac_bits;
-    o.epsilon = e->epsilon;
+    o.gamma = gamma; o.epsilon = e->epsilon;
     o.env_seed = e->env_seed; o.agent_seed = e->agent_seed; o.tie_seed = e->tie_seed; o.board_id0 = e->board_id0; o.round = e->round;
     o.lengths = e->lengths; o.total_score = e->total_score; o.stats = e->summary;
-    if (e->canonical) launch_games<true, false>(o, e->max_tile_hist, stream); else launch_games<false, false>(o, e->max_tile_hist, stream);
-    return finish_launch("pulse_tfe_mc_evaluate launch");
+    if (after) launch_games<false, true>(o, e->max_tile_hist, stream, e->canonical != 0);
+    else launch_games<false, false>(o, e->max_tile_hist, stream, e->canonical != 0);
+    return 0;
 }
 
-extern "C" int pulse_tfe_mc_table_merge(const PulseTfeMCMerge* o, void* stream) {
-    const char* name = "pulse_tfe_mc_table_merge";
+// pulse_tfe_mc_table_merge, and pulse_tfe_mc_table_fold_after (values): the fold of a value table
+int merge(const PulseTfeMCMerge* o, void* stream, bool values, const char* name) {
     constexpr uint64_t kLine = PULSE_TFE_MC_ENTRY_BYTES;
     if (!o) return fail_named(name, "options are null");
     if (!o->src) return fail_named(name, "src is null");
@@ -406,23 +499,76 @@ extern "C" int pulse_tfe_mc_table_merge(const PulseTfeMCMerge* o, void* stream) 
         if (s0 < d1 && d0 < s1) return fail_named(name, "src and dst overlap");
     }
     if (o->canonical != 0 && o->canonical != 1) return fail_named(name, "canonical must be 0 or 1");
+    if (values && o->canonical != 1) return fail_named(name, "canonical must be 1 (the plain merge of a value table is pulse_tfe_mc_table_merge)");
     if (o->n < 2 || o->n > 4) return fail_named(name, "board side n must be 2..4 (64-bit state key)");
     if (!o->stats) return fail_named(name, "stats is null");
     if ((uintptr_t)o->stats & 7u) return fail_named(name, "stats must be 8-byte aligned");
     if (o->reserved0 != 0) return fail_named(name, "reserved0 must be 0 (zero-initialise the struct)");
     const dim3 grid((unsigned)((o->src_entries + kBlock - 1) / kBlock)), block(kBlock);
     hipStream_t st = (hipStream_t)stream;
-    switch (o->canonical ? o->n : 0) {
-    case 0: hipLaunchKernelGGL(tfe_mc_merge_kernel<0>, grid, block, 0, st, *o); break;
-    case 2: hipLaunchKernelGGL(tfe_mc_merge_kernel<2>, grid, block, 0, st, *o); break;
-    case 3: hipLaunchKernelGGL(tfe_mc_merge_kernel<3>, grid, block, 0, st, *o); break;
-    default: hipLaunchKernelGGL(tfe_mc_merge_kernel<4>, grid, block, 0, st, *o);
+    switch ((o->canonical ? o->n : 0) + (values ? 8 : 0)) {
+    case 0: hipLaunchKernelGGL((tfe_mc_merge_kernel<0, false>), grid, block, 0, st, *o); break;
+    case 2: hipLaunchKernelGGL((tfe_mc_merge_kernel<2, false>), grid, block, 0, st, *o); break;
+    case 3: hipLaunchKernelGGL((tfe_mc_merge_kernel<3, false>), grid, block, 0, st, *o); break;
+    case 4: hipLaunchKernelGGL((tfe_mc_merge_kernel<4, false>), grid, block, 0, st, *o); break;
+    case 10: hipLaunchKernelGGL((tfe_mc_merge_kernel<2, true>), grid, block, 0, st, *o); break;
+    case 11: hipLaunchKernelGGL((tfe_mc_merge_kernel<3, true>), grid, block, 0, st, *o); break;
+    default: hipLaunchKernelGGL((tfe_mc_merge_kernel<4, true>), grid, block, 0, st, *o);
     }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int pulse_tfe_mc_rollout(const PulseTfeMCRollout* o, void* stream) {
+    if (int rc = rollout(o, stream, false, false, "pulse_tfe_mc_rollout")) return rc;
+    return finish_launch("pulse_tfe_mc_rollout launch");
+}
+
+extern "C" int pulse_tfe_mc_rollout_canon(const PulseTfeMCRollout* o, void* stream) {
+    if (int rc = rollout(o, stream, true, false, "pulse_tfe_mc_rollout_canon")) return rc;
+    return finish_launch("pulse_tfe_mc_rollout_canon launch");
+}
+
+extern "C" int pulse_tfe_mc_evaluate(const PulseTfeMCEval* e, void* stream) {
+    if (int rc = evaluate(e, 0.0, stream, false, "pulse_tfe_mc_evaluate")) return rc;
+    return finish_launch("pulse_tfe_mc_evaluate launch");
+}
+
+extern "C" int pulse_tfe_mc_table_merge(const PulseTfeMCMerge* o, void* stream) {
+    if (int rc = merge(o, stream, false, "pulse_tfe_mc_table_merge")) return rc;
     return finish_launch("pulse_tfe_mc_table_merge launch");
 }
 
 extern "C" int pulse_tfe_mc_learn(const PulseTfeMCLearn* o, void* stream) {
     if (int rc = check_common(o, "pulse_tfe_mc_learn")) return rc;
-    hipLaunchKernelGGL(tfe_mc_learn_kernel, dim3((unsigned)((o->n_games + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, *o);
+    hipLaunchKernelGGL(tfe_mc_learn_kernel<false>, dim3((unsigned)((o->n_games + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, *o);
     return finish_launch("pulse_tfe_mc_learn launch");
+}
+
+// ---- the afterstate mode: the same structs and checks, V(board after the move) in cnt[0] / sum[0]
+extern "C" int pulse_tfe_mc_rollout_after(const PulseTfeMCRollout* o, void* stream) {
+    if (int rc = rollout(o, stream, false, true, "pulse_tfe_mc_rollout_after")) return rc;
+    return finish_launch("pulse_tfe_mc_rollout_after launch");
+}
+
+extern "C" int pulse_tfe_mc_rollout_after_canon(const PulseTfeMCRollout* o, void* stream) {
+    if (int rc = rollout(o, stream, true, true, "pulse_tfe_mc_rollout_after_canon")) return rc;
+    return finish_launch("pulse_tfe_mc_rollout_after_canon launch");
+}
+
+extern "C" int pulse_tfe_mc_learn_after(const PulseTfeMCLearn* o, void* stream) {
+    if (int rc = check_common(o, "pulse_tfe_mc_learn_after")) return rc;
+    hipLaunchKernelGGL(tfe_mc_learn_kernel<true>, dim3((unsigned)((o->n_games + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream, *o);
+    return finish_launch("pulse_tfe_mc_learn_after launch");
+}
+
+extern "C" int pulse_tfe_mc_evaluate_after(const PulseTfeMCEval* e, double gamma, void* stream) {
+    if (int rc = evaluate(e, gamma, stream, true, "pulse_tfe_mc_evaluate_after")) return rc;
+    return finish_launch("pulse_tfe_mc_evaluate_after launch");
+}
+
+extern "C" int pulse_tfe_mc_table_fold_after(const PulseTfeMCMerge* o, void* stream) {
+    if (int rc = merge(o, stream, true, "pulse_tfe_mc_table_fold_after")) return rc;
+    return finish_launch("pulse_tfe_mc_table_fold_after launch");
 }

@@ -8,7 +8,8 @@ state; `--eval-every K --eval-games M` prints, every K 
 of the table as it stands (one evaluation launch, no trajectory; the same boards at every check).  `--grow-at LOAD` doubles the table
 at a printed line while it holds LOAD x capacity states or more, or once after first visits were dropped since the last line (the
 line then also prints the occupancy); `--save PATH` writes the table and the run's state at the end, `--resume PATH` continues such
-a run for `--rounds` more rounds."""
+a run for `--rounds` more rounds.  `--afterstate` learns the value of the board after the move instead of
+Q(state, action); it works with all of the above, and `--resume` refuses a checkpoint of the other kind."""
 from __future__ import annotations
 
 import argparse
@@ -20,16 +21,16 @@ from ..agents import OnPolicyFirstVisitMCTFEGPU
 
 
 def run(device, rounds, tables=65536, board=3, gamma=0.9, epsilon=0.1, seed=0, capacity=None, max_steps=1024, log_every=1, out=print,
-        symmetric=False, eval_every=0, eval_games=None, grow_at=0.0, save=None, resume=None):
+        symmetric=False, eval_every=0, eval_games=None, grow_at=0.0, save=None, resume=None, afterstate=False):
     if resume:                                                              # capacity None: what load() takes for the saved rows
-        agent = OnPolicyFirstVisitMCTFEGPU.load(resume, device, capacity=capacity)
+        agent = OnPolicyFirstVisitMCTFEGPU.load(resume, device, capacity=capacity, afterstate=afterstate)
         want = dict(n_games=tables, n=board, gamma=float(gamma), epsilon=float(epsilon), max_steps=max_steps, seed=seed, symmetric=bool(symmetric))
         differ = {k: (getattr(agent, k), v) for k, v in want.items() if getattr(agent, k) != v}
         if differ:
             raise ValueError(f"{resume} continues another run: (saved, asked) {differ}")
     else:
         agent = OnPolicyFirstVisitMCTFEGPU(device, tables, board_size=board, gamma=gamma, epsilon=epsilon, capacity=capacity or 1 << 22,
-                                           max_steps=max_steps, seed=seed, symmetric=symmetric)
+                                           max_steps=max_steps, seed=seed, symmetric=symmetric, afterstate=afterstate)
     first, dropped_before = agent.round, 0
     steps_before, t0 = 0, time.perf_counter()
     for r in range(first, first + rounds):
@@ -71,12 +72,13 @@ def main(argv=None):
     ap.add_argument("--log-every", type=int, default=1, help="rounds per printed line")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--symmetric", action="store_true", help="one state per board up to rotation and reflection")
+    ap.add_argument("--afterstate", action="store_true", help="learn V(board after the move) instead of Q(state, action)")
     ap.add_argument("--eval-every", type=int, default=0, help="rounds between evaluations of the greedy policy (0: never)")
     ap.add_argument("--eval-games", type=int, help="games per evaluation (default: --tables)")
     ap.add_argument("--grow-at", type=float, default=0.0, metavar="LOAD",
                     help="double the table at a printed line while occupancy >= LOAD * capacity, or after drops since the last line (0: never)")
     ap.add_argument("--save", metavar="PATH", help="write the table and the run's state to this .npz at the end")
-    ap.add_argument("--resume", metavar="PATH", help="continue the run saved there (the same --tables, --board, --max-steps, --seed, --symmetric) for --rounds more rounds")
+    ap.add_argument("--resume", metavar="PATH", help="continue the run saved there (the same --tables, --board, --max-steps, --seed, --symmetric, --afterstate) for --rounds more rounds")
     args = ap.parse_args(argv)
     gamma, epsilon, episodes = 0.9, 0.1, 1_000_000
     if args.config:
@@ -86,7 +88,8 @@ def main(argv=None):
         gamma, epsilon, episodes = float(cfg.get("GAMMA", gamma)), float(cfg.get("EPSILON", epsilon)), int(cfg.get("NUM_EPISODES", episodes))
     rounds = args.rounds if args.rounds is not None else max(1, -(-episodes // args.tables))
     agent = run(torch.device("cuda"), rounds, args.tables, args.board, gamma, epsilon, args.seed, args.capacity, args.max_steps, args.log_every,
-                symmetric=args.symmetric, eval_every=args.eval_every, eval_games=args.eval_games, grow_at=args.grow_at, save=args.save, resume=args.resume)
+                symmetric=args.symmetric, eval_every=args.eval_every, eval_games=args.eval_games, grow_at=args.grow_at, save=args.save, resume=args.resume,
+                afterstate=args.afterstate)
     print(f"{agent.round * args.tables} games in {agent.round} rounds, gamma {gamma}, epsilon {epsilon}: {len(agent.table())} states stored")
 
 

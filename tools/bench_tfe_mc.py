@@ -17,6 +17,11 @@ JSON line per batch size B (65,536 and 1,048,576 games per round by default):
 and load (the live rows as a dense array into 2^23).  Per launch: live entries, ms (median, min, max) and source bytes scanned per
 second; and, measured in the same run on a 3 x 3 table, the host path the fold replaces: table(), then fold_table_on_host.  One
 JSON line per launch, also appended to profiles/tfe_mc/bench_tfe_mc_table.jsonl.
+--afterstate times the afterstate mode (pulse_tfe_mc_rollout_after, pulse_tfe_mc_learn_after,
+pulse_tfe_mc_evaluate_after, pulse_tfe_mc_table_fold_after) BESIDE the default agent of the same run, shape and seeds: per batch size the
+two agents' lines as above under "plain" and "afterstate", the fold of the afterstate table the warm rounds left into a zeroed table
+of the same capacity, and per launch the time per move and its ratio to the plain agent's (afterstate games get longer as the policy
+improves, so launches are compared per move).  One JSON line per batch size, also appended to profiles/tfe_mc/bench_tfe_mc_after.jsonl.
 --symmetric runs everything on the table of canonical states (pulse_tfe_mc_rollout_canon).
 max_steps is 256 here (the longest game met while learning for 12 rounds of 4,096 games was 222 moves; cut games are counted in
 the line): the per-move buffers are B x max_steps x 9 bytes.  Nothing is asserted about the rates."""
@@ -57,10 +62,10 @@ def _timed_evaluate(agent, torch):
     return ev[0].elapsed_time(ev[1]) * 1e-3, agent.eval_counters()
 
 
-def device_rounds(dev, games, warmup, repeats, max_steps, capacity, symmetric=False):
+def device_rounds(dev, games, warmup, repeats, max_steps, capacity, symmetric=False, afterstate=False, keep_agent=False):
     import torch
     from pulselib_amd.agents import OnPolicyFirstVisitMCTFEGPU
-    kw = dict(board_size=3, gamma=.9, epsilon=.1, capacity=capacity, max_steps=max_steps, seed=0, symmetric=symmetric)
+    kw = dict(board_size=3, gamma=.9, epsilon=.1, capacity=capacity, max_steps=max_steps, seed=0, symmetric=symmetric, afterstate=afterstate)
     OnPolicyFirstVisitMCTFEGPU(dev, games, **kw).learn_batch()              # untimed: code objects, allocator
     torch.cuda.synchronize()
     agent = OnPolicyFirstVisitMCTFEGPU(dev, games, **kw)
@@ -77,7 +82,7 @@ def device_rounds(dev, games, warmup, repeats, max_steps, capacity, symmetric=Fa
     agent.evaluate()                                                        # untimed: the evaluation kernel's code object
     evals = [_timed_evaluate(agent, torch) for _ in range(repeats)]
     ev_s, e = _spread([s for s, _ in evals]), evals[-1][1]
-    return {"games": games, "board": 3, "symmetric": symmetric, "max_steps": max_steps, "capacity": capacity, "warmup": warmup, "repeats": repeats,
+    line = {"games": games, "board": 3, "symmetric": symmetric, "afterstate": afterstate, "max_steps": max_steps, "capacity": capacity, "warmup": warmup, "repeats": repeats,
             "cold": {"rollout_s": cold[0], "learn_s": cold[1], "steps": cold_steps, "episodes_per_s": games / sum(cold),
                      "board_steps_per_s": cold_steps / sum(cold)},
             "warm": {"rollout_s": _spread([a for a, _ in times]), "learn_s": _spread([b for _, b in times]), "round_s": rnd,
@@ -86,6 +91,33 @@ def device_rounds(dev, games, warmup, repeats, max_steps, capacity, symmetric=Fa
                          "mean_score": e["mean_score"], "std_score": e["std_score"], "mean_length": e["mean_length"], "truncated": e["truncated"],
                          "coverage": e["coverage"]},
             "states_stored": states, "dropped": after["dropped"], "truncated": after["truncated"], "mean_final_score": mean_final_score}
+    return (line, agent) if keep_agent else line
+
+
+def after_rounds(dev, games, warmup, repeats, max_steps, capacity, symmetric, path):
+    """The default agent and the afterstate agent, one after the other in this process, and the afterstate table's fold."""
+    import torch
+    plain = device_rounds(dev, games, warmup, repeats, max_steps, capacity, symmetric)
+    torch.cuda.empty_cache()
+    after, agent = device_rounds(dev, games, warmup, repeats, max_steps, capacity, symmetric, afterstate=True, keep_agent=True)
+    out = {"games": games, "board": 3, "symmetric": symmetric, "max_steps": max_steps, "capacity": capacity, "plain": plain, "afterstate": after}
+    if not symmetric:                                                       # (a table of canonical states has no fold)
+        sym = agent._like(n_games=1, capacity=1, symmetric=True)            # its _merge_launch is the fold; its own table is not used
+        times, st, _ = _timed_merge(sym, torch, agent.entries, capacity, True, 3, repeats)
+        out["fold"] = {"seconds": _spread(times), "src_entries": capacity, **st, "src_bytes_per_s": capacity * 128 / statistics.median(times)}
+
+    def per_move(line, launch):
+        if launch == "evaluate":
+            return line["evaluate"]["seconds"]["median"] / line["evaluate"]["moves"]
+        if launch.startswith("cold"):
+            return line["cold"][launch[5:] + "_s"] / line["cold"]["steps"]
+        return line["warm"][launch + "_s"]["median"] / line["warm"]["steps_per_round"]
+    out["per_move"] = {k: {"plain_ns": per_move(plain, k) * 1e9, "afterstate_ns": per_move(after, k) * 1e9, "ratio": per_move(after, k) / per_move(plain, k)}
+                       for k in ("cold_rollout", "cold_learn", "rollout", "learn", "evaluate")}
+    print(json.dumps(out), flush=True)
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "a") as fh:
+        fh.write(json.dumps(out) + "\n")
 
 
 def _timed_merge(agent, torch, src, capacity, canonical, untimed=3, repeats=5):
@@ -189,6 +221,8 @@ def main(argv=None):
     ap.add_argument("--max-steps", type=int, default=256)
     ap.add_argument("--host-games", type=int, default=1024, help="0: skip the host path")
     ap.add_argument("--symmetric", action="store_true", help="the table of canonical states")
+    ap.add_argument("--afterstate", action="store_true", help="the afterstate mode beside the default agent (DESIGN.md section 12.3)")
+    ap.add_argument("--after-out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "tfe_mc", "bench_tfe_mc_after.jsonl"))
     ap.add_argument("--table-ops", action="store_true", help="time the table-merge launch (grow, fold, dense load) instead of the rounds")
     ap.add_argument("--table-games", type=int, default=65536, help="games per round that fill the table for --table-ops")
     ap.add_argument("--table-untimed", type=int, default=3, help="untimed repetitions of each merge launch for --table-ops")
@@ -204,8 +238,11 @@ def main(argv=None):
     for games in args.games:
         # 128 slots per game, 2^25 (4 GB) at the most: a first round of 4,096 games stores ~19 states per game, later ones fewer; `dropped` tells if it was too few
         capacity = 1 << max(16, (games * 128 - 1).bit_length())
+        if args.afterstate:
+            after_rounds(dev, games, args.warmup, args.repeats, args.max_steps, min(capacity, 1 << 25), args.symmetric, args.after_out)
+            continue
         print(json.dumps(device_rounds(dev, games, args.warmup, args.repeats, args.max_steps, min(capacity, 1 << 25), args.symmetric)), flush=True)
-    if args.host_games:
+    if args.host_games and not args.afterstate:
         print(json.dumps(host_rounds(dev, args.host_games)), flush=True)
 
 
