@@ -671,6 +671,123 @@ int pulse_tfe_mc_learn_after(const PulseTfeMCLearn* o, void* stream);
 int pulse_tfe_mc_evaluate_after(const PulseTfeMCEval* o, double gamma, void* stream);
 int pulse_tfe_mc_table_fold_after(const PulseTfeMCMerge* o, void* stream);
 
+/* ---- 2048 on 4 x 4: an n-tuple network trained by batch TD(0) on afterstates.  Four launches, stream-ordered, no host
+ * synchronisation between them: whole games under the network, the temporal differences of every recorded move into integer
+ * accumulators, the accumulators into the weights, and an evaluation.  n = 4 only; the board is the packed 64-bit key for the whole game.
+ *
+ * The network (PulseTfeNtNet, the first member of the four structs).  n_tuples = 1..8 tuples; tuple t is tuple_len[t] = 1..6 distinct
+ * cells (0..15, row-major) in cells[t][0 .. len - 1] (the other bytes of cells[t] are not read) with its own table of 16^len weights:
+ *   float weights[n_weights], n_weights = the sum of 16^len over the tuples, tuple t's table at the sum of the earlier tables' sizes;
+ *   4-byte aligned, caller-owned, zeroed = the empty network.
+ * The index of a tuple on a board = the sum over i of nibble(cell_i) << 4 i, the nibble being the key's (log2 of the tile, 0 = empty).
+ * symmetric = 1: every tuple is read on the eight images T_0 .. T_7 of the board (the eight symmetries above) -- image j reads the
+ * cells T_j shows at the tuple's positions -- and all eight read the tuple's one table; F = 8 n_tuples features (n_tuples with
+ * symmetric = 0, where only T_0, the board as it lies, is read).  The library derives the images' cells from T_j; the caller passes
+ * the tuples only.
+ *   V(board) = the sum over the features of (double)weights[index], in float64, tuple-major and image j = 0..7 within a tuple, from
+ *   0.0, one rounding per add.
+ * Accumulators: int64 acc[n_weights][2] = {sum, cnt}, 16-byte aligned, caller-owned, zeroed once by the caller (the apply launch
+ * zeroes what it reads).  sum holds temporal differences as llrint(delta * 2^PULSE_TFE_NT_FRAC_BITS), |delta| clamped to
+ * PULSE_TFE_NT_DELTA_MAX: 8192 * 2^16 * 2^32 < 2^62, room for 2^32 adds per cell (the bound of the Monte-Carlo table's frac_bits).
+ * stats, device int64[8], ADDED TO: [0] moves played, [3] games cut (roll-out); [1] moves learnt, [2] moves skipped, [4] temporal
+ * differences clamped (learn); [5..7] not written.
+ *
+ * pulse_tfe_nt_rollout: one lane per game, from reset to the terminal step or to max_steps moves; the environment's own games,
+ * exactly as pulse_tfe_mc_rollout draws them (Philox4x32-10(env_seed, board_id0 + g, env_step), env_step 0 at reset and t + 1 at move
+ * t; the agent's draw {x, y, ..} = Philox4x32-10(agent_seed, board_id0 + g, t)).  The weights are only read.  At move t on board B,
+ * for a = 0..3: (B_a, score_a) = the move of B by a without a spawn, r_a = the environment's reward (bit length of score_a - 1, 0 for
+ * 0), q_a = r_a + gamma * V(B_a) in float64, one rounding per operation.  The CANDIDATES are the moves with B_a != B (a board that is
+ * not over has one) -- unlike pulse_tfe_mc_rollout_after: a move that changes nothing on a full board has a temporal difference of 0
+ * at gamma = 1, which TD would never unlearn.
+ *   (x >> 8) < floor(epsilon * 2^24)   ->   a = y >> 30 (uniform over the four; the environment accepts a move that changes nothing);
+ *   otherwise the candidates in the order a = 0..3: the first is the best so far, a larger q replaces it, an equal q replaces it iff
+ *   bit 31 of word a - 1 of Philox4x32-10(tie_seed, key of B, round) is set.  On zero weights: greedy on the reward.
+ * Recorded, step-major: keys[t * n_games + g] = the key of the afterstate B_a taken, values[...] = V(B_a) as float64,
+ * steps[...] = a | r_a << 2 | terminal << 7, terminal = the game was over after this move's spawn.  Rows t >= lengths[g] are not
+ * written.  Per game: lengths, total_score, episode_reward.  A game whose board comes to hold nibble 15 (a 32,768 tile: the row
+ * table cannot merge two of them) stops there; a game that stopped without being over -- at max_steps or at that tile -- is CUT.
+ *
+ * pulse_tfe_nt_learn: one lane per recorded move (t, g), t < lengths[g]; no weight is read.  The last move of a game has target 0
+ * if its terminal bit is set and is SKIPPED otherwise (a cut game's last afterstate has no known successor); any other move has
+ * target = reward(steps[t + 1]) + gamma * values[t + 1].  delta = target - values[t], clamped to +-PULSE_TFE_NT_DELTA_MAX (counted),
+ * d = llrint(ldexp(delta, PULSE_TFE_NT_FRAC_BITS)); for every feature of keys[t]: acc[index].sum += d, acc[index].cnt += 1 (64-bit
+ * integer atomics without a returned value; two images that land on one weight add twice).  Integer adds: acc does not depend on
+ * scheduling.
+ *
+ * pulse_tfe_nt_apply: one lane per weight; where cnt > 0,
+ *   weights[i] = (float)((double)weights[i] + step * (((double)sum / (double)cnt) * 2^-16))   (one rounding per operation, IEEE
+ *   division), and both accumulator words become 0.  A weight with cnt = 0 keeps its bits.  step = alpha / F: each weight moves
+ *   by alpha / F of the MEAN temporal difference of its visits in the round, whatever the number of games.
+ *
+ * pulse_tfe_nt_evaluate: the roll-out's games for equal seeds, ids, round, gamma, epsilon and weights, without a trajectory.
+ * summary, device int64[8], ADDED TO: [0] games, [1] moves, [2] sum of total_score, [3] sum of total_score^2, [4] the largest
+ * total_score (atomic max), [5] games cut, [6] moves decided greedily (not the epsilon branch), [7] games stopped at the 32,768 tile
+ * (counted in [5] too unless the game was over as well).  max_tile_hist, device int64[16], added to: bin = the largest nibble of
+ * the final board.  total_score int64[n_games] / lengths int32[n_games]: per game, or NULL.  Reduced in the workgroup: one atomic per
+ * workgroup and non-zero bin.
+ *
+ * PULSE_EINVAL, before anything is launched: n != 4, n_tuples outside 1..8, a length outside 1..6, a cell above 15 or repeated within
+ * a tuple, n_weights != the sum of 16^len, symmetric outside {0, 1}, gamma or epsilon outside [0, 1], step outside (0, 1], max_steps
+ * outside 1..65,535, n_games < 1, a null or misaligned buffer the call needs (learn needs no weights), non-zero reserved fields. */
+#define PULSE_TFE_NT_MAX_TUPLES 8
+#define PULSE_TFE_NT_MAX_LEN    6
+#define PULSE_TFE_NT_FRAC_BITS  16
+#define PULSE_TFE_NT_DELTA_MAX  8192.0
+typedef struct PulseTfeNtNet {
+    int32_t n, n_tuples, symmetric, reserved0;
+    uint8_t tuple_len[PULSE_TFE_NT_MAX_TUPLES];
+    uint8_t cells[PULSE_TFE_NT_MAX_TUPLES][8];
+    uint64_t n_weights;
+    float* weights;                     /* float[n_weights] */
+} PulseTfeNtNet;
+typedef struct PulseTfeNtRollout {
+    PulseTfeNtNet net;
+    int32_t n_games, max_steps;
+    double gamma, epsilon;
+    uint64_t env_seed, agent_seed, tie_seed, board_id0, round;
+    uint64_t* keys;                     /* uint64[max_steps * n_games] */
+    double* values;                     /* float64[max_steps * n_games] */
+    uint8_t* steps;                     /* uint8[max_steps * n_games] */
+    int32_t* lengths;                   /* int32[n_games] */
+    int64_t* total_score;               /* int64[n_games] */
+    int32_t* episode_reward;            /* int32[n_games] */
+    int64_t* stats;                     /* int64[8] */
+    int64_t reserved0;
+} PulseTfeNtRollout;
+int pulse_tfe_nt_rollout(const PulseTfeNtRollout* o, void* stream);
+typedef struct PulseTfeNtLearn {
+    PulseTfeNtNet net;                  /* weights may be NULL */
+    int32_t n_games, max_steps;
+    double gamma;
+    const uint64_t* keys;
+    const double* values;
+    const uint8_t* steps;
+    const int32_t* lengths;
+    int64_t* acc;                       /* int64[n_weights][2] */
+    int64_t* stats;                     /* int64[8] */
+    int64_t reserved0;
+} PulseTfeNtLearn;
+int pulse_tfe_nt_learn(const PulseTfeNtLearn* o, void* stream);
+typedef struct PulseTfeNtApply {
+    PulseTfeNtNet net;
+    double step;                        /* alpha / F */
+    int64_t* acc;                       /* int64[n_weights][2] */
+    int64_t reserved0;
+} PulseTfeNtApply;
+int pulse_tfe_nt_apply(const PulseTfeNtApply* o, void* stream);
+typedef struct PulseTfeNtEval {
+    PulseTfeNtNet net;
+    int32_t n_games, max_steps;
+    double gamma, epsilon;
+    uint64_t env_seed, agent_seed, tie_seed, board_id0, round;
+    int64_t* summary;                   /* int64[8] */
+    int64_t* max_tile_hist;             /* int64[16] */
+    int64_t* total_score;               /* int64[n_games] or NULL */
+    int32_t* lengths;                   /* int32[n_games] or NULL */
+    int64_t reserved0;
+} PulseTfeNtEval;
+int pulse_tfe_nt_evaluate(const PulseTfeNtEval* o, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

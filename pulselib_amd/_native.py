@@ -146,6 +146,35 @@ class TfeMCMerge(C.Structure):
                 ("n", C.c_int32), ("canonical", C.c_int32), ("stats", C.c_void_p), ("reserved0", C.c_int64)]
 
 
+# the 2048 n-tuple network (include/pulse_env.h): the network heads the four structs
+TFE_NT_MAX_TUPLES, TFE_NT_MAX_LEN, TFE_NT_FRAC_BITS, TFE_NT_DELTA_MAX = 8, 6, 16, 8192.0
+_TFE_NT_SEEDS = [(n, C.c_uint64) for n in ("env_seed", "agent_seed", "tie_seed", "board_id0", "round")]
+
+
+class TfeNtNet(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n", "n_tuples", "symmetric", "reserved0")] + [
+        ("tuple_len", C.c_uint8 * TFE_NT_MAX_TUPLES), ("cells", (C.c_uint8 * 8) * TFE_NT_MAX_TUPLES), ("n_weights", C.c_uint64), ("weights", C.c_void_p)]
+
+
+class TfeNtRollout(C.Structure):
+    _fields_ = [("net", TfeNtNet), ("n_games", C.c_int32), ("max_steps", C.c_int32), ("gamma", C.c_double), ("epsilon", C.c_double)] + _TFE_NT_SEEDS + [
+        (n, C.c_void_p) for n in ("keys", "values", "steps", "lengths", "total_score", "episode_reward", "stats")] + [("reserved0", C.c_int64)]
+
+
+class TfeNtLearn(C.Structure):
+    _fields_ = [("net", TfeNtNet), ("n_games", C.c_int32), ("max_steps", C.c_int32), ("gamma", C.c_double)] + [
+        (n, C.c_void_p) for n in ("keys", "values", "steps", "lengths", "acc", "stats")] + [("reserved0", C.c_int64)]
+
+
+class TfeNtApply(C.Structure):
+    _fields_ = [("net", TfeNtNet), ("step", C.c_double), ("acc", C.c_void_p), ("reserved0", C.c_int64)]
+
+
+class TfeNtEval(C.Structure):
+    _fields_ = [("net", TfeNtNet), ("n_games", C.c_int32), ("max_steps", C.c_int32), ("gamma", C.c_double), ("epsilon", C.c_double)] + _TFE_NT_SEEDS + [
+        (n, C.c_void_p) for n in ("summary", "max_tile_hist", "total_score", "lengths")] + [("reserved0", C.c_int64)]
+
+
 # every symbol include/pulse_env.h declares: (restype, argtypes)
 _P, _I32, _U32, _U64, _F32, _I64 = C.c_void_p, C.c_int32, C.c_uint32, C.c_uint64, C.c_float, C.c_int64
 SYMBOLS = {
@@ -207,6 +236,10 @@ SYMBOLS = {
     "pulse_tfe_mc_learn_after": (C.c_int, [_P, _P]),
     "pulse_tfe_mc_evaluate_after": (C.c_int, [_P, C.c_double, _P]),
     "pulse_tfe_mc_table_fold_after": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_rollout": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_learn": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_apply": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_evaluate": (C.c_int, [_P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

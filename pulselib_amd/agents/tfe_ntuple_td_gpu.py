@@ -1,0 +1,437 @@
+"""2048 on 4 x 4: an n-tuple network trained by batch TD(0) on afterstates, on the device (csrc/tfe_ntuple.hip).
+
+The value of an afterstate -- the board after the move and before the spawn -- is the sum of a few lookup tables.  Each table is
+indexed by the tiles (4-bit log2, the state key's nibbles) on a fixed set of cells, read on the board's eight images under the
+symmetries of the square, which share the table.  A round is three launches and nothing read back in between:
+`pulse_tfe_nt_rollout` plays `n_games` whole games, one lane each, greedily (or epsilon-greedily) on reward + gamma * V among the
+moves that change the board, and records per move the afterstate's key, its V and one byte; `pulse_tfe_nt_learn` runs one lane per
+recorded move and adds the temporal difference reward' + gamma * V' - V (0 - V at a terminal move) as a fixed-point integer into
+{sum, cnt} of every weight the afterstate reads; `pulse_tfe_nt_apply` moves every visited weight by alpha / F of the MEAN of its
+adds and zeroes the accumulators.  `pulse_tfe_nt_evaluate` plays games without a trajectory and reduces the scores in the launch.
+
+The policy of a round is frozen (the weights are only read by the roll-out) and the adds are integers, so a round's result does not
+depend on scheduling: `feature_cells_on_host`, `value_on_host`, `greedy_nt_on_host`, `learn_nt_on_host` and `apply_nt_on_host` are
+the host's statement of the same arithmetic in numpy, vectorised over boards, and the device is held to them word for word."""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+import math
+
+import numpy as np
+
+from .. import _native
+from .tfe_on_policy_mc_gpu import AGENT_KEY, EVAL_BINS, TIE_KEY, transforms_on_host
+
+MAX_TUPLES, MAX_LEN, FRAC_BITS, DELTA_MAX = _native.TFE_NT_MAX_TUPLES, _native.TFE_NT_MAX_LEN, _native.TFE_NT_FRAC_BITS, _native.TFE_NT_DELTA_MAX
+DEFAULT_TUPLES = ((0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))       # two rows and two 2 x 3 rectangles
+STATS = ("moves", "learnt", "skipped", "truncated", "clamped")                                # words 0..4 of the stats buffer
+EVAL_SUMMARY = ("games", "moves", "score_sum", "score_sq_sum", "max_score", "truncated", "moves_greedy", "tile_capped")
+CHECKPOINT_VERSION = 1
+CHECKPOINT_SCALARS = ("symmetric", "gamma", "epsilon", "alpha", "max_steps", "seed", "board_id0", "round", "n_games")
+_U64, _M32 = np.uint64, np.uint64(0xFFFFFFFF)
+
+
+# ------------------------------------------------------------------ the network's shape
+def check_tuples(tuples) -> tuple:
+    """The tuples as a tuple of tuples of ints, after the library's own checks (ValueError)."""
+    tuples = tuple(tuple(int(c) for c in t) for t in tuples)
+    if not 1 <= len(tuples) <= MAX_TUPLES:
+        raise ValueError(f"n_tuples must be in 1..{MAX_TUPLES}")
+    for t in tuples:
+        if not 1 <= len(t) <= MAX_LEN:
+            raise ValueError(f"a tuple's length must be in 1..{MAX_LEN}")
+        if any(not 0 <= c <= 15 for c in t) or len(set(t)) != len(t):
+            raise ValueError("a tuple's cells must be distinct and in 0..15")
+    return tuples
+
+
+def tuple_offsets(tuples):
+    """(offsets, n_weights): tuple t's table of 16^len weights starts at the sum of the earlier tables' sizes."""
+    sizes = [16 ** len(t) for t in tuples]
+    return [sum(sizes[:i]) for i in range(len(sizes))], sum(sizes)
+
+
+def feature_cells_on_host(tuples, symmetric=True) -> list:
+    """Per tuple int64[images, len]: the board cells that feature (tuple, image j) reads, in the tuple's order.  Image j reads the
+    cells T_j(board) shows at the tuple's positions: transforms_on_host(4)[j][cell].  images = 8, or 1 (T_0) without `symmetric`."""
+    tf = transforms_on_host(4)[:8 if symmetric else 1]
+    return [tf[:, list(t)] for t in tuples]
+
+
+def feature_indices_on_host(keys, tuples, symmetric=True) -> np.ndarray:
+    """int64[len(keys), F]: the weights an afterstate reads, tuple-major and image j within a tuple (the order V is summed in)."""
+    keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
+    nib = np.stack([(keys >> _U64(4 * c)) & _U64(15) for c in range(16)], axis=1).astype(np.int64)
+    offsets, _ = tuple_offsets(tuples)
+    cols = []
+    for off, cells in zip(offsets, feature_cells_on_host(tuples, symmetric)):
+        for image in cells:
+            cols.append(off + sum(nib[:, int(c)] << (4 * i) for i, c in enumerate(image)))
+    return np.stack(cols, axis=1)
+
+
+def value_on_host(keys, weights, tuples, symmetric=True) -> np.ndarray:
+    """float64[len(keys)]: V = the sum of (double)weights[index] over the features, from 0.0 in the order of feature_indices_on_host,
+    one rounding per add."""
+    w = np.asarray(weights, dtype=np.float32)[feature_indices_on_host(keys, tuples, symmetric)].astype(np.float64)
+    v = np.zeros(w.shape[0], dtype=np.float64)
+    for f in range(w.shape[1]):
+        v = v + w[:, f]
+    return v
+
+
+# ------------------------------------------------------------------ the environment's move and Philox, over many boards
+def philox_many_on_host(seed: int, subseq, offset) -> np.ndarray:
+    """uint32[N, 4]: Philox4x32-10 with the device's layout (csrc/philox_device.h) -- counter {offset, subseq}, key = seed -- for
+    arrays (or scalars) of subseq and offset."""
+    subseq, offset = np.broadcast_arrays(np.asarray(subseq, dtype=_U64).reshape(-1), np.asarray(offset, dtype=_U64).reshape(-1))
+    c0, c1, c2, c3 = offset & _M32, offset >> _U64(32), subseq & _M32, subseq >> _U64(32)
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = _U64(0xD2511F53) * c0, _U64(0xCD9E8D57) * c2                  # 32 x 32 -> 64 bits: no overflow
+        c0, c1, c2, c3 = (p1 >> _U64(32)) ^ c1 ^ _U64(k0), p1 & _M32, (p0 >> _U64(32)) ^ c3 ^ _U64(k1), p0 & _M32
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return np.stack([c0, c1, c2, c3], axis=1).astype(np.uint32)
+
+
+@functools.lru_cache(maxsize=None)
+def row_table_on_host():
+    """(row after the squash to the left uint16[65536], merge score int64[65536]) of every row of four nibbles (TFE.py:85-101: a
+    tile merges with an equal neighbour once): the host's copy of the device's row table (csrc/tfe_device.h)."""
+    rows, ar = np.arange(65536, dtype=np.int64), np.arange(65536)
+    res, w = np.zeros((65536, 4), dtype=np.int64), np.zeros(65536, dtype=np.int64)
+    merged, score = np.zeros(65536, dtype=bool), np.zeros(65536, dtype=np.int64)
+    for c in range(4):
+        val = (rows >> (4 * c)) & 15
+        cur = res[ar, w]
+        put = (val != 0) & (cur == 0)
+        mrg = (val != 0) & (cur != 0) & (cur == val) & ~merged
+        adv = (val != 0) & (cur != 0) & ~mrg
+        res[ar[put], w[put]] = val[put]
+        res[ar[mrg], w[mrg]] = np.minimum(val[mrg] + 1, 15)
+        score[mrg] += np.int64(2) << val[mrg]
+        merged[mrg] = True
+        w[adv] += 1
+        res[ar[adv], w[adv]] = val[adv]
+        merged[adv] = False
+    return (res[:, 0] | res[:, 1] << 4 | res[:, 2] << 8 | res[:, 3] << 12).astype(np.uint16), score
+
+
+def moves_on_host(keys):
+    """(afterstate keys uint64[N, 4], merge scores int64[N, 4]) of the four moves of packed 4 x 4 boards, without the spawn
+    (TFE.py:154-178: the board rotated `a` times, every row squashed to the left, rotated back)."""
+    keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
+    nib = np.stack([(keys >> _U64(4 * c)) & _U64(15) for c in range(16)], axis=1).astype(np.int64)
+    table, table_score = row_table_on_host()
+    after, score = np.zeros((len(keys), 4), dtype=_U64), np.zeros((len(keys), 4), dtype=np.int64)
+    for a, src in enumerate(transforms_on_host(4)[:4].tolist()):
+        for r in range(0, 16, 4):
+            row = nib[:, src[r]] | nib[:, src[r + 1]] << 4 | nib[:, src[r + 2]] << 8 | nib[:, src[r + 3]] << 12
+            out = table[row].astype(np.int64)
+            score[:, a] += table_score[row]
+            for c in range(4):
+                after[:, a] |= ((out >> (4 * c)) & 15).astype(_U64) << _U64(4 * src[r + c])
+    return after, score
+
+
+def rewards_of_scores(scores) -> np.ndarray:
+    """TFE.py:185-187 over an array: bit length - 1 of a merge score, 0 for 0 (scores are sums of powers of two below 2^18: exact)."""
+    s = np.asarray(scores, dtype=np.int64)
+    return np.where(s > 0, np.floor(np.log2(np.maximum(s, 1))).astype(np.int64), 0)
+
+
+def greedy_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: int, round: int) -> dict:
+    """The roll-out's greedy rule on packed boards: q_a = r_a + gamma * V(B_a) in float64 for the four moves; the candidates are the
+    moves with B_a != B, scanned in the order a = 0..3 -- the first is the best so far, a larger q replaces it, an equal q replaces
+    it iff bit 31 of word a - 1 of Philox(tie_seed, key of B, round) is set.  Returns action int64[N] (-1: no candidate: the board is
+    over), after uint64[N, 4], scores / rewards int64[N, 4], values / q float64[N, 4]."""
+    keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
+    after, scores = moves_on_host(keys)
+    rewards = rewards_of_scores(scores)
+    values = value_on_host(after.reshape(-1), weights, tuples, symmetric).reshape(-1, 4)
+    q = rewards.astype(np.float64) + float(gamma) * values
+    coins = philox_many_on_host(tie_seed, keys, int(round)) >> np.uint32(31)
+    best, best_q = np.full(len(keys), -1, dtype=np.int64), np.zeros(len(keys), dtype=np.float64)
+    for a in range(4):
+        cand = after[:, a] != keys
+        take = cand & ((best < 0) | (q[:, a] > best_q))
+        if a:
+            take |= cand & (best >= 0) & (q[:, a] == best_q) & (coins[:, a - 1] != 0)
+        best, best_q = np.where(take, a, best), np.where(take, q[:, a], best_q)
+    return dict(action=best, after=after, scores=scores, rewards=rewards, values=values, q=q)
+
+
+# ------------------------------------------------------------------ the learner and the apply launch
+def unpack_steps(steps):
+    """(action, reward, terminal) of the per-move bytes."""
+    s = np.asarray(steps, dtype=np.uint8)
+    return s & 3, (s >> 2) & 31, (s >> 7).astype(bool)
+
+
+def learn_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, acc):
+    """pulse_tfe_nt_learn on the host.  keys uint64[T, B], values float64[T, B], steps uint8[T, B], lengths int[B]; acc int64[W, 2] =
+    {sum, cnt}, added to in place.  Move (t, g), t < lengths[g]: the last move of a game has target 0 with its terminal bit and is
+    skipped without; any other has target = reward(steps[t + 1]) + gamma * values[t + 1]; delta = target - values[t] clamped to
+    +-DELTA_MAX, d = round-half-even(delta * 2^16); sum += d, cnt += 1 at every feature of keys[t] (a weight two images meet gets
+    both).  Returns dict(learnt, skipped, clamped)."""
+    keys, values, steps = np.asarray(keys, dtype=_U64), np.asarray(values, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    T = keys.shape[0]
+    t = np.arange(T, dtype=np.int64)[:, None]
+    played, last = t < lengths[None, :], t == lengths[None, :] - 1
+    skipped = played & last & (steps >> 7 == 0)
+    learn = played & ~skipped
+    nxt_r, nxt_v = np.zeros_like(values), np.zeros_like(values)
+    nxt_r[:-1], nxt_v[:-1] = ((steps[1:] >> 2) & 31).astype(np.float64), values[1:]
+    target = np.where(last, 0.0, nxt_r + float(gamma) * nxt_v)
+    delta = (target - values)[learn]
+    clamped = np.abs(delta) > DELTA_MAX
+    d = np.rint(np.ldexp(np.clip(delta, -DELTA_MAX, DELTA_MAX), FRAC_BITS)).astype(np.int64)
+    idx = feature_indices_on_host(keys[learn], tuples, symmetric)
+    np.add.at(acc[:, 0], idx.reshape(-1), np.repeat(d, idx.shape[1]))
+    np.add.at(acc[:, 1], idx.reshape(-1), 1)
+    return dict(learnt=int(learn.sum()), skipped=int(skipped.sum()), clamped=int(clamped.sum()))
+
+
+def apply_nt_on_host(weights, acc, step: float) -> int:
+    """pulse_tfe_nt_apply on the host, in place: where cnt > 0, w = float32(float64(w) + step * ((sum / cnt) * 2^-16)), one rounding per
+    operation, and the two accumulator words become 0.  Returns the number of weights moved."""
+    at = np.flatnonzero(acc[:, 1] > 0)
+    mean = acc[at, 0].astype(np.float64) / acc[at, 1].astype(np.float64) * 2.0 ** -FRAC_BITS
+    weights[at] = (weights[at].astype(np.float64) + float(step) * mean).astype(np.float32)
+    acc[at] = 0
+    return len(at)
+
+
+def eval_summary_on_host(words) -> dict:
+    """pulse_tfe_nt_evaluate's 8 + 16 counters as a dict: the words by name, the histogram of the largest tile (bin = its log2), and
+    mean / std (sample standard deviation, from the exact integer sums) of the final score and the mean length."""
+    w = [int(x) for x in words]
+    out = dict(zip(EVAL_SUMMARY, w[:len(EVAL_SUMMARY)]))
+    n, s, ss = out["games"], out["score_sum"], out["score_sq_sum"]
+    out["max_tile_hist"] = w[len(EVAL_SUMMARY):len(EVAL_SUMMARY) + EVAL_BINS]
+    out["mean_score"] = s / n if n else 0.0
+    out["std_score"] = math.sqrt((n * ss - s * s) / (n * (n - 1))) if n > 1 else 0.0              # exact integers under the root
+    out["mean_length"] = out["moves"] / n if n else 0.0
+    return out
+
+
+# ------------------------------------------------------------------ the checkpoint file
+def write_checkpoint(path, weights, tuples, **scalars) -> None:
+    """The network as an .npz of plain arrays (np.savez, no pickles): the non-zero weights as index int64[m] (ascending) and value
+    float32[m], the tuples as tuple_len int64[n_tuples] and tuple_cells int64[n_tuples, 6] (-1 beyond a tuple's length), the scalars of
+    CHECKPOINT_SCALARS as 0-d arrays and `version`.  `path` is written as given."""
+    if sorted(scalars) != sorted(CHECKPOINT_SCALARS):
+        raise ValueError(f"a checkpoint holds exactly the scalars {CHECKPOINT_SCALARS}")
+    weights = np.asarray(weights, dtype=np.float32).reshape(-1)
+    index = np.flatnonzero(weights.view(np.uint32) != 0)                   # by bit pattern: what is not +0.0 is kept
+    cells = np.full((len(tuples), MAX_LEN), -1, dtype=np.int64)
+    for i, t in enumerate(tuples):
+        cells[i, :len(t)] = t
+    dtypes = dict(gamma=np.float64, epsilon=np.float64, alpha=np.float64, seed=np.uint64, board_id0=np.uint64)
+    arrays = {k: np.array(scalars[k], dtype=dtypes.get(k, np.int64)) for k in CHECKPOINT_SCALARS}
+    with open(path, "wb") as fh:
+        np.savez(fh, version=np.array(CHECKPOINT_VERSION, dtype=np.int64), index=index.astype(np.int64), value=weights[index],
+                 tuple_len=np.array([len(t) for t in tuples], dtype=np.int64), tuple_cells=cells, **arrays)
+
+
+def read_checkpoint(path) -> dict:
+    """What write_checkpoint wrote (np.load with allow_pickle=False): `tuples`, `index`, `value`, `n_weights` and the scalars as
+    Python numbers.  ValueError for another format version, a missing array, tuples the library would refuse or an index outside
+    the network."""
+    with np.load(path, allow_pickle=False) as f:
+        missing = [k for k in ("version", "index", "value", "tuple_len", "tuple_cells") + CHECKPOINT_SCALARS if k not in f.files]
+        if missing:
+            raise ValueError(f"{path}: not an n-tuple network checkpoint (no {missing})")
+        if int(f["version"]) != CHECKPOINT_VERSION:
+            raise ValueError(f"{path}: format version {int(f['version'])}, this package reads {CHECKPOINT_VERSION}")
+        out = {k: (float(f[k]) if k in ("gamma", "epsilon", "alpha") else int(f[k])) for k in CHECKPOINT_SCALARS}
+        index, value, lens, cells = f["index"], f["value"], f["tuple_len"], f["tuple_cells"]
+    out["symmetric"] = bool(out["symmetric"])
+    out["tuples"] = check_tuples([cells[i, :int(n)].tolist() for i, n in enumerate(lens.tolist())])
+    out["n_weights"] = tuple_offsets(out["tuples"])[1]
+    if index.dtype != np.int64 or value.dtype != np.float32 or index.shape != value.shape or index.ndim != 1:
+        raise ValueError(f"{path}: index must be int64[m] and value float32[m]")
+    if len(index) and (int(index[0]) < 0 or int(index[-1]) >= out["n_weights"] or not bool((index[1:] > index[:-1]).all())):
+        raise ValueError(f"{path}: index must be strictly ascending inside the network's {out['n_weights']} weights")
+    out["index"], out["value"] = index, value
+    return out
+
+
+def weights_of_checkpoint(f: dict) -> np.ndarray:
+    """float32[n_weights] of a read_checkpoint dict."""
+    w = np.zeros(f["n_weights"], dtype=np.float32)
+    w[f["index"]] = f["value"]
+    return w
+
+
+# ------------------------------------------------------------------ the device agent
+class NTupleTDAfterstateTFEGPU:
+    """`learn_batch` = `rollout` + `learn` + `apply` + `round += 1`: three launches and no synchronisation.  Everything that reads
+    back (`weights`, `stats`, `trajectory`, `evaluate`, the per-game arrays' `.cpu()`) synchronises.  Round r plays the boards
+    board_id0 + r * n_games + g, so no two rounds replay the same spawns."""
+
+    def __init__(self, device, n_games, tuples=DEFAULT_TUPLES, symmetric=True, gamma=1.0, epsilon=0.0, alpha=1.0, max_steps=4096, seed=0,
+                 board_id0=0):
+        import torch
+        device = _native.gpu_device(device, "NTupleTDAfterstateTFEGPU")
+        self.tuples = check_tuples(tuples)
+        if int(n_games) < 1 or not 1 <= int(max_steps) <= 65535:
+            raise ValueError("n_games must be positive and max_steps in 1..65535")
+        if not (0.0 <= gamma <= 1.0 and 0.0 <= epsilon <= 1.0):
+            raise ValueError("gamma and epsilon must be in [0, 1]")
+        self._lib = _native.lib()
+        self.device = device
+        self.n, self.n_games, self.max_steps, self.symmetric = 4, int(n_games), int(max_steps), bool(symmetric)
+        self.gamma, self.epsilon, self.alpha = float(gamma), float(epsilon), float(alpha)
+        self.n_features = len(self.tuples) * (8 if self.symmetric else 1)
+        if not 0.0 < self.alpha <= self.n_features:
+            raise ValueError("alpha must be in (0, F]: the apply launch takes step = alpha / F in (0, 1]")
+        self.offsets, self.n_weights = tuple_offsets(self.tuples)
+        self.seed, self.board_id0, self.round = int(seed), int(board_id0), 0
+        self.env_seed, self.agent_seed, self.tie_seed = self.seed, self.seed ^ AGENT_KEY, self.seed ^ TIE_KEY
+        self.weights_dev = torch.zeros(self.n_weights, dtype=torch.float32, device=device)
+        self.acc = torch.zeros((self.n_weights, 2), dtype=torch.int64, device=device)                 # {sum, cnt}; torch allocations are 16-byte aligned
+        self.keys = torch.zeros((self.max_steps, self.n_games), dtype=torch.int64, device=device)     # (uint64 words)
+        self.values = torch.zeros((self.max_steps, self.n_games), dtype=torch.float64, device=device)
+        self.steps = torch.zeros((self.max_steps, self.n_games), dtype=torch.uint8, device=device)
+        self.lengths = torch.zeros(self.n_games, dtype=torch.int32, device=device)
+        self.total_score = torch.zeros(self.n_games, dtype=torch.int64, device=device)
+        self.episode_reward = torch.zeros(self.n_games, dtype=torch.int32, device=device)
+        self.counters = torch.zeros(8, dtype=torch.int64, device=device)
+        self._eval = torch.zeros(len(EVAL_SUMMARY) + EVAL_BINS, dtype=torch.int64, device=device)     # evaluate(): summary, then the histogram
+
+    # ------------------------------------------------------------------ the launches
+    def _net(self, net):
+        net.n, net.n_tuples, net.symmetric = self.n, len(self.tuples), int(self.symmetric)
+        for t, cells in enumerate(self.tuples):
+            net.tuple_len[t] = len(cells)
+            for i, c in enumerate(cells):
+                net.cells[t][i] = c
+        net.n_weights, net.weights = self.n_weights, self.weights_dev.data_ptr()
+
+    def _launch(self, name, o):
+        _native.check(getattr(self._lib, name)(C.byref(o), _native.current_stream(self.device)), name)
+        return self
+
+    def round_board_id0(self, round=None) -> int:
+        return self.board_id0 + (self.round if round is None else int(round)) * self.n_games
+
+    def rollout(self):
+        """One launch: n_games games under the weights as they stand (round `self.round`), into keys / values / steps / lengths /
+        scores."""
+        o = _native.TfeNtRollout()
+        self._net(o.net)
+        o.n_games, o.max_steps, o.gamma, o.epsilon = self.n_games, self.max_steps, self.gamma, self.epsilon
+        o.env_seed, o.agent_seed, o.tie_seed, o.board_id0, o.round = self.env_seed, self.agent_seed, self.tie_seed, self.round_board_id0(), self.round
+        o.keys, o.values, o.steps, o.lengths = self.keys.data_ptr(), self.values.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr()
+        o.total_score, o.episode_reward, o.stats = self.total_score.data_ptr(), self.episode_reward.data_ptr(), self.counters.data_ptr()
+        return self._launch("pulse_tfe_nt_rollout", o)
+
+    def learn(self):
+        """One launch: the temporal differences of the games last played, into the accumulators."""
+        o = _native.TfeNtLearn()
+        self._net(o.net)
+        o.n_games, o.max_steps, o.gamma = self.n_games, self.max_steps, self.gamma
+        o.keys, o.values, o.steps, o.lengths = self.keys.data_ptr(), self.values.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr()
+        o.acc, o.stats = self.acc.data_ptr(), self.counters.data_ptr()
+        return self._launch("pulse_tfe_nt_learn", o)
+
+    def apply(self):
+        """One launch: every visited weight moves by alpha / F of the mean of its adds; the accumulators are zero afterwards."""
+        o = _native.TfeNtApply()
+        self._net(o.net)
+        o.step, o.acc = self.alpha / self.n_features, self.acc.data_ptr()
+        return self._launch("pulse_tfe_nt_apply", o)
+
+    def learn_batch(self):
+        self.rollout()
+        self.learn()
+        self.apply()
+        self.round += 1
+        return self
+
+    # ------------------------------------------------------------------ evaluation
+    def eval_board_id0(self) -> int:
+        """evaluate()'s default boards: board_id0 + 2^62 + g, which training meets only after 2^62 / n_games rounds; every call with
+        the default replays the same spawns (scores under two networks are paired)."""
+        return (self.board_id0 + (1 << 62)) & 0xFFFFFFFFFFFFFFFF
+
+    def evaluate_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False):
+        """The launch of evaluate() alone: ADDS to the counters of `eval_counters` and reads nothing back.  Returns the per-game device
+        tensors (total_score int64[B], lengths int32[B]) with per_game, else None."""
+        import torch
+        B = self.n_games if n_games is None else int(n_games)
+        o = _native.TfeNtEval()
+        self._net(o.net)
+        o.n_games, o.max_steps, o.gamma, o.epsilon = B, self.max_steps, self.gamma, float(epsilon)
+        o.env_seed, o.agent_seed, o.tie_seed, o.round = self.env_seed, self.agent_seed, self.tie_seed, self.round
+        o.board_id0 = self.eval_board_id0() if board_id0 is None else int(board_id0)
+        o.summary, o.max_tile_hist = self._eval.data_ptr(), self._eval[len(EVAL_SUMMARY):].data_ptr()
+        arrays = None
+        if per_game:
+            arrays = (torch.zeros(B, dtype=torch.int64, device=self.device), torch.zeros(B, dtype=torch.int32, device=self.device))
+            o.total_score, o.lengths = arrays[0].data_ptr(), arrays[1].data_ptr()
+        self._launch("pulse_tfe_nt_evaluate", o)
+        return arrays
+
+    def eval_counters(self, clear=False) -> dict:
+        """What the evaluation launches since the last clear added up to (eval_summary_on_host; synchronises), or, with clear,
+        nothing: the counters are zeroed."""
+        if clear:
+            self._eval.zero_()
+            return {}
+        return eval_summary_on_host(self._eval.cpu().tolist())
+
+    def evaluate(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False) -> dict:
+        """One launch and one read-back: `n_games` games (default: the agent's) under the weights as they stand and `epsilon` (default 0:
+        the greedy policy), no trajectory.  With equal seeds, round, epsilon and board_id0 they are the games rollout() plays.  Returns
+        the counters by name, the histogram of the largest tile, mean / standard deviation of the final score and the mean length;
+        per_game adds the arrays total_score / lengths."""
+        self.eval_counters(clear=True)
+        arrays = self.evaluate_launch(n_games, epsilon, board_id0, per_game)
+        out = self.eval_counters()
+        if per_game:
+            out["total_score"], out["lengths"] = arrays[0].cpu().numpy(), arrays[1].cpu().numpy()
+        return out
+
+    # ------------------------------------------------------------------ read-back (the only syncs) and the checkpoint
+    def weights(self) -> np.ndarray:
+        """float32[n_weights] on the host."""
+        return self.weights_dev.cpu().numpy()
+
+    def stats(self) -> dict:
+        return dict(zip(STATS, self.counters.cpu().tolist()[:len(STATS)]))
+
+    def trajectory(self):
+        """(keys uint64[T, B], values float64[T, B], steps uint8[T, B], lengths int32[B]) of the last batch, T = the longest game; rows
+        at and beyond a game's length hold whatever the buffers held before."""
+        lengths = self.lengths.cpu().numpy()
+        T = int(lengths.max()) if lengths.size else 0
+        return self.keys[:T].cpu().numpy().view(np.uint64), self.values[:T].cpu().numpy(), self.steps[:T].cpu().numpy(), lengths
+
+    def save(self, path):
+        """The non-zero weights and what a continued run needs as an .npz (write_checkpoint)."""
+        write_checkpoint(path, self.weights(), self.tuples, symmetric=int(self.symmetric), gamma=self.gamma, epsilon=self.epsilon, alpha=self.alpha,
+                         max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games)
+
+    @classmethod
+    def load(cls, path, device, n_games=None):
+        """The agent save() wrote: weights, round and seeds restored.  With the saved n_games it continues the run the saved agent would
+        have continued (another n_games plays other boards: round r starts at board_id0 + r * n_games)."""
+        import torch
+        f = read_checkpoint(path)
+        agent = cls(device, f["n_games"] if n_games is None else n_games, tuples=f["tuples"], symmetric=f["symmetric"], gamma=f["gamma"],
+                    epsilon=f["epsilon"], alpha=f["alpha"], max_steps=f["max_steps"], seed=f["seed"], board_id0=f["board_id0"])
+        agent.weights_dev.copy_(torch.from_numpy(weights_of_checkpoint(f)))
+        agent.round = f["round"]
+        return agent
+
+    def clear(self):
+        """The empty network, zeroed accumulators and counters, round 0."""
+        self.weights_dev.zero_()
+        self.acc.zero_()
+        self.counters.zero_()
+        self.round = 0
+        return self

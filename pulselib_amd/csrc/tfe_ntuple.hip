@@ -1,0 +1,414 @@
+// tfe_ntuple.hip -- 2048 on 4 x 4: an n-tuple network trained by batch TD(0) on afterstates, four launches:
+// pulse_tfe_nt_rollout, pulse_tfe_nt_learn, pulse_tfe_nt_apply, pulse_tfe_nt_evaluate (include/pulse_env.h).
+//
+// V(afterstate) = the sum of a few lookup tables, each indexed by the nibbles on a fixed set of cells, read on the board's eight
+// images.  One lane plays one game with the board as the packed 64-bit key in two registers (tfe_device.h: the row-table move, the
+// spawn and the game-over test of the step kernel, on the environment's own Philox stream); a move is four row-table moves, 4 F
+// gathers from the weights and one comparison.  Which cell a feature reads is the same for every lane: the host derives the images'
+// cells and hands the kernels 6 shift counts per feature in one 64-bit word, by value, so a nibble is a shift by a scalar and no lane
+// indexes an array.  The learner runs one lane per recorded move and adds temporal differences as fixed-point integers, so the
+// accumulators do not depend on scheduling; the apply launch moves each weight by step * the mean of its adds.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "philox_device.h"
+#include "pulse_internal.h"
+#include "tfe_device.h"
+
+namespace {
+
+using namespace pulse_tfe;
+using pulse_philox::philox4x32;
+using pulse_philox::U4;
+using pulse::fail_named;
+using pulse::finish_launch;
+
+constexpr int kBlock = 256;
+constexpr int kMaxTuples = PULSE_TFE_NT_MAX_TUPLES, kMaxLen = PULSE_TFE_NT_MAX_LEN;
+static_assert(sizeof(PulseTfeNtNet) == 104 && sizeof(PulseTfeNtRollout) == 232 && sizeof(PulseTfeNtLearn) == 176 && sizeof(PulseTfeNtApply) == 128 &&
+              sizeof(PulseTfeNtEval) == 208, "struct layouts are part of the ABI");
+
+// The network as the kernels take it (by value: every word is read at a wavefront-uniform position).  Feature f = t * images + j:
+// byte i of shifts[f] = 4 * (the board cell that image j shows at cell i of tuple t), 0 at and beyond the tuple's length -- those
+// nibbles are masked off again by mask[t] = 16^len - 1.
+struct NtDev {
+    uint64_t shifts[kMaxTuples * 8];
+    uint32_t offset[kMaxTuples], mask[kMaxTuples];
+    int32_t n_tuples;
+};
+
+__device__ __forceinline__ uint32_t feature_index(uint64_t key, uint64_t sh, uint32_t mask, uint32_t offset) {
+    uint32_t idx = 0u;
+#pragma unroll
+    for (int i = 0; i < kMaxLen; ++i) idx |= ((uint32_t)(key >> ((sh >> (8 * i)) & 63ull)) & 15u) << (4 * i);
+    return (idx & mask) + offset;
+}
+
+// V of the four afterstates of a move at once: per tuple the 4 * IMG indices are formed first and their loads issued with nothing
+// dependent between them (32 lines in flight per lane), then added in the order of the definition: tuple-major, image j = 0..7.
+template <int IMG>
+__device__ __forceinline__ void values4(const NtDev& net, const float* __restrict__ w, const uint64_t (&ka)[4], double (&v)[4]) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) v[a] = 0.0;
+#pragma unroll 1
+    for (int t = 0; t < net.n_tuples; ++t) {
+        const uint32_t mask = net.mask[t], offset = net.offset[t];
+        uint32_t idx[4][IMG];
+#pragma unroll
+        for (int j = 0; j < IMG; ++j) {
+            const uint64_t sh = net.shifts[t * IMG + j];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) idx[a][j] = feature_index(ka[a], sh, mask, offset);
+        }
+        float x[4][IMG];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int j = 0; j < IMG; ++j) x[a][j] = w[idx[a][j]];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int j = 0; j < IMG; ++j) v[a] = __dadd_rn(v[a], (double)x[a][j]);
+    }
+}
+
+__device__ __forceinline__ bool has_nibble15(const PackedBoard p) {
+    const uint32_t l = p.lo & (p.lo >> 1) & (p.lo >> 2) & (p.lo >> 3), h = p.hi & (p.hi >> 1) & (p.hi >> 2) & (p.hi >> 3);
+    return ((l | h) & 0x11111111u) != 0u;
+}
+
+// what the game loops get: pulse_tfe_nt_rollout's struct, or pulse_tfe_nt_evaluate's outputs in its shape (stats = summary)
+struct Games {
+    const float* weights;
+    int32_t n_games, max_steps;
+    double gamma;
+    uint32_t eps_q24;
+    uint64_t env_seed, agent_seed, tie_seed, board_id0, round;
+    uint64_t* keys; double* values; uint8_t* steps;
+    int32_t* lengths; int64_t* total_score; int32_t* episode_reward;
+    int64_t* stats; int64_t* hist;
+    const uint32_t* lut;
+};
+
+// the evaluation's counters: summary[8] then max_tile_hist[16], reduced in LDS and added once per workgroup and non-zero bin
+constexpr int kEvalSummary = 8, kEvalBins = kEvalSummary + 16, kEvalMax = 4;
+
+// IMG = 8 (symmetric) or 1.  Record: pulse_tfe_nt_rollout; otherwise pulse_tfe_nt_evaluate.
+template <int IMG, bool Record>
+__global__ __launch_bounds__(kBlock) void tfe_nt_games_kernel(const Games o, const NtDev net) {
+    __shared__ unsigned long long wg[Record ? 2 : kEvalBins];
+    if (threadIdx.x < (Record ? 2 : kEvalBins)) wg[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int g = blockIdx.x * kBlock + threadIdx.x;
+    const size_t B = (size_t)o.n_games;
+    if (g < o.n_games) {
+        const uint64_t id = o.board_id0 + (uint64_t)g;
+        PackedBoard p{0u, 0u};
+        {                                                                               // TFE.py:143-149, as pulse_tfe_reset
+            const U4 rnd = philox4x32(o.env_seed, id, 0ull);
+            tfe_spawn_packed(p, rnd.x, rnd.y);
+            tfe_spawn_packed(p, rnd.z, rnd.w);
+        }
+        int64_t total = 0;
+        int ep_reward = 0, length = 0;
+        bool over = false, capped = false;
+        unsigned long long n_greedy = 0ull;
+        for (int t = 0; t < o.max_steps && !over && !capped; ++t) {
+            const U4 r = philox4x32(o.agent_seed, id, (uint64_t)t);
+            const uint64_t key_b = (uint64_t)p.hi << 32 | p.lo;
+            uint64_t ka[4];
+            int sc[4];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                PackedBoard m = p;
+                sc[a] = tfe_move_packed(m, a, o.lut);
+                ka[a] = (uint64_t)m.hi << 32 | m.lo;
+            }
+            double v[4], q[4];
+            values4<IMG>(net, o.weights, ka, v);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) q[a] = __dadd_rn((double)(sc[a] > 0 ? 31 - __clz(sc[a]) : 0), __dmul_rn(o.gamma, v[a]));
+            const bool greedy = (r.x >> 8) >= o.eps_q24;
+            int act = (int)(r.y >> 30);
+            if (greedy) {
+                const bool any_tie = q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3];
+                U4 coins{0u, 0u, 0u, 0u};
+                if (any_tie) coins = philox4x32(o.tie_seed, key_b, o.round);
+                const uint32_t coin[4] = {0u, coins.x >> 31, coins.y >> 31, coins.z >> 31};
+                int best = -1;
+                double best_q = 0.0;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    const bool cand = ka[a] != key_b;
+                    const bool take = cand && (best < 0 || q[a] > best_q || (q[a] == best_q && coin[a] != 0u));
+                    best_q = take ? q[a] : best_q;
+                    best = take ? a : best;
+                }
+                act = best < 0 ? act : best;                                            // (a live board has a candidate)
+                n_greedy += 1ull;
+            }
+            uint64_t key = ka[0];
+            double val = v[0];
+            int score = sc[0];
+#pragma unroll
+            for (int a = 1; a < 4; ++a) { key = act == a ? ka[a] : key; val = act == a ? v[a] : val; score = act == a ? sc[a] : score; }
+            p.lo = (uint32_t)key; p.hi = (uint32_t)(key >> 32);                         // the afterstate's key IS the moved board
+            const U4 rnd = philox4x32(o.env_seed, id, (uint64_t)t + 1ull);
+            const int empty_before = tfe_spawn_packed(p, rnd.x, rnd.y);                // TFE.py:182 (always)
+            over = tfe_over_packed(p, empty_before);                                   // TFE.py:48-67
+            capped = has_nibble15(p);
+            const int reward = score > 0 ? 31 - __clz(score) : 0;                      // TFE.py:185-187 (<= 16: five bits)
+            if constexpr (Record) {
+                const size_t at = (size_t)t * B + (size_t)g;
+                o.keys[at] = key;
+                o.values[at] = val;
+                o.steps[at] = (uint8_t)((uint32_t)act | ((uint32_t)reward & 31u) << 2 | (over ? 0x80u : 0u));
+            }
+            total += score; ep_reward += reward;
+            length = t + 1;
+        }
+        const unsigned long long n_moves = (unsigned long long)length, n_cut = over ? 0ull : 1ull;
+        if constexpr (Record) {
+            o.lengths[g] = length;
+            o.total_score[g] = total;
+            o.episode_reward[g] = ep_reward;
+            atomicAdd(&wg[0], n_moves);                                                 // LDS
+            if (n_cut) atomicAdd(&wg[1], n_cut);
+        } else {
+            if (o.lengths) o.lengths[g] = length;
+            if (o.total_score) o.total_score[g] = total;
+            uint32_t top = 0u;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) top = max(top, max((p.lo >> (4 * i)) & 15u, (p.hi >> (4 * i)) & 15u));
+            const unsigned long long s = (unsigned long long)total;
+            const unsigned long long x[kEvalSummary] = {1ull, n_moves, s, s * s, s, n_cut, n_greedy, capped ? 1ull : 0ull};
+#pragma unroll
+            for (int i = 0; i < kEvalSummary; ++i)
+                if (x[i]) { if (i == kEvalMax) atomicMax(&wg[i], x[i]); else atomicAdd(&wg[i], x[i]); }       // LDS
+            atomicAdd(&wg[kEvalSummary + top], 1ull);
+        }
+    }
+    __syncthreads();
+    const int i = (int)threadIdx.x;
+    if constexpr (Record) {
+        if (i < 2 && wg[i]) atomicAdd(reinterpret_cast<unsigned long long*>(o.stats) + (i == 0 ? 0 : 3), wg[i]);
+    } else {
+        if (i < kEvalBins && wg[i]) {
+            unsigned long long* dst = reinterpret_cast<unsigned long long*>(i < kEvalSummary ? o.stats + i : o.hist + (i - kEvalSummary));
+            if (i == kEvalMax) atomicMax(dst, wg[i]); else atomicAdd(dst, wg[i]);       // (scores are not negative)
+        }
+    }
+}
+
+// One lane per recorded move: blockIdx.y = t, blockIdx.x * kBlock + threadIdx.x = g.
+template <int IMG>
+__global__ __launch_bounds__(kBlock) void tfe_nt_learn_kernel(const PulseTfeNtLearn o, const NtDev net) {
+    __shared__ unsigned long long wg[3];
+    if (threadIdx.x < 3) wg[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int g = blockIdx.x * kBlock + threadIdx.x, t = (int)blockIdx.y;
+    const size_t B = (size_t)o.n_games;
+    if (g < o.n_games) {
+        int length = o.lengths[g];
+        length = length > o.max_steps ? o.max_steps : length;                          // (the buffers hold max_steps rows)
+        if (t < length) {
+            const size_t at = (size_t)t * B + (size_t)g;
+            const bool last = t == length - 1;
+            const bool skip = last && (o.steps[at] & 0x80u) == 0u;
+            if (skip) {
+                atomicAdd(&wg[1], 1ull);                                                // LDS
+            } else {
+                double target = 0.0;
+                if (!last) target = __dadd_rn((double)((o.steps[at + B] >> 2) & 31u), __dmul_rn(o.gamma, o.values[at + B]));
+                double delta = __dsub_rn(target, o.values[at]);
+                const bool clamp = delta > PULSE_TFE_NT_DELTA_MAX || delta < -PULSE_TFE_NT_DELTA_MAX;
+                delta = delta > PULSE_TFE_NT_DELTA_MAX ? PULSE_TFE_NT_DELTA_MAX : (delta < -PULSE_TFE_NT_DELTA_MAX ? -PULSE_TFE_NT_DELTA_MAX : delta);
+                const unsigned long long d = (unsigned long long)llrint(ldexp(delta, PULSE_TFE_NT_FRAC_BITS));
+                const uint64_t key = o.keys[at];
+                unsigned long long* acc = reinterpret_cast<unsigned long long*>(o.acc);
+#pragma unroll 1
+                for (int tu = 0; tu < net.n_tuples; ++tu) {
+                    const uint32_t mask = net.mask[tu], offset = net.offset[tu];
+#pragma unroll
+                    for (int j = 0; j < IMG; ++j) {
+                        const size_t idx = (size_t)feature_index(key, net.shifts[tu * IMG + j], mask, offset);
+                        atomicAdd(acc + 2 * idx, d);
+                        atomicAdd(acc + 2 * idx + 1, 1ull);
+                    }
+                }
+                atomicAdd(&wg[0], 1ull);
+                if (clamp) atomicAdd(&wg[2], 1ull);
+            }
+        }
+    }
+    __syncthreads();
+    const int i = (int)threadIdx.x;
+    if (i < 3 && wg[i]) atomicAdd(reinterpret_cast<unsigned long long*>(o.stats) + (i == 0 ? 1 : i == 1 ? 2 : 4), wg[i]);
+}
+
+__global__ __launch_bounds__(kBlock) void tfe_nt_apply_kernel(float* __restrict__ weights, longlong2* __restrict__ acc, uint64_t n_weights, double step) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_weights) return;
+    const longlong2 a = acc[i];                                                         // {sum, cnt}
+    if (a.y > 0) {
+        const double mean = __dmul_rn(__ddiv_rn((double)a.x, (double)a.y), 1.0 / (double)(1 << PULSE_TFE_NT_FRAC_BITS));
+        weights[i] = (float)__dadd_rn((double)weights[i], __dmul_rn(step, mean));
+        acc[i] = make_longlong2(0, 0);
+    }
+}
+
+// The cell of the board that cell `cell` of T_j(board) shows (include/pulse_env.h, "eight symmetries"): j & 3 rotations by the
+// environment's rotation (out[r][c] = in[c][3 - r]), for j >= 4 after a transpose.
+int image_cell(int j, int cell) {
+    int r = cell / 4, c = cell % 4;
+    for (int q = 0; q < (j & 3); ++q) { const int nr = c, nc = 3 - r; r = nr; c = nc; }
+    return j >= 4 ? c * 4 + r : r * 4 + c;
+}
+
+// The checks of the network, shared by the four entry points; fills the kernels' form of it.
+int check_net(const PulseTfeNtNet& n, bool need_weights, const char* name, NtDev* dev) {
+    if (n.n != 4) return fail_named(name, "board side n must be 4 (the n-tuple network plays the packed 4 x 4 board)");
+    if (n.n_tuples < 1 || n.n_tuples > kMaxTuples) return fail_named(name, "n_tuples must be in 1..8");
+    if (n.symmetric != 0 && n.symmetric != 1) return fail_named(name, "symmetric must be 0 or 1");
+    if (n.reserved0 != 0) return fail_named(name, "net.reserved0 must be 0 (zero-initialise the struct)");
+    *dev = NtDev{};
+    dev->n_tuples = n.n_tuples;
+    const int images = n.symmetric ? 8 : 1;
+    uint64_t total = 0;
+    for (int t = 0; t < n.n_tuples; ++t) {
+        const int len = n.tuple_len[t];
+        if (len < 1 || len > kMaxLen) return fail_named(name, "a tuple's length must be in 1..6");
+        uint32_t seen = 0u;
+        for (int i = 0; i < len; ++i) {
+            const int cell = n.cells[t][i];
+            if (cell > 15) return fail_named(name, "a tuple's cell must be in 0..15");
+            if (seen >> cell & 1u) return fail_named(name, "a cell is repeated within a tuple");
+            seen |= 1u << cell;
+            for (int j = 0; j < images; ++j) dev->shifts[t * images + j] |= (uint64_t)(4 * image_cell(j, cell)) << (8 * i);
+        }
+        dev->offset[t] = (uint32_t)total;
+        dev->mask[t] = (uint32_t)((1ull << (4 * len)) - 1ull);
+        total += 1ull << (4 * len);
+    }
+    if (n.n_weights != total) return fail_named(name, "n_weights must be the sum of 16^len over the tuples");
+    if (need_weights && !n.weights) return fail_named(name, "weights is null");
+    if ((uintptr_t)n.weights & 3u) return fail_named(name, "weights must be 4-byte aligned");
+    return 0;
+}
+
+// ... and those of a batch of games (the roll-out's, the learner's and the evaluation's structs name these fields alike)
+template <class O>
+int check_batch(const O* o, const char* name) {
+    if (o->n_games < 1) return fail_named(name, "n_games must be positive");
+    if (o->max_steps < 1 || o->max_steps > 65535) return fail_named(name, "max_steps must be in 1..65535");
+    if (!(o->gamma >= 0.0 && o->gamma <= 1.0)) return fail_named(name, "gamma must be in [0, 1]");
+    if (o->reserved0 != 0) return fail_named(name, "reserved0 must be 0 (zero-initialise the struct)");
+    return 0;
+}
+
+int check_acc(const int64_t* acc, const char* name) {
+    if (!acc) return fail_named(name, "acc is null");
+    if ((uintptr_t)acc & 15u) return fail_named(name, "acc must be 16-byte aligned");
+    return 0;
+}
+
+int launch_games(Games& g, const NtDev& dev, bool symmetric, bool record, void* stream) {
+    if (int rc = pulse::tfe_row_lut(&g.lut)) return rc;
+    const dim3 grid((unsigned)((g.n_games + kBlock - 1) / kBlock)), block(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+    if (record) {
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_games_kernel<8, true>), grid, block, 0, st, g, dev);
+        else hipLaunchKernelGGL((tfe_nt_games_kernel<1, true>), grid, block, 0, st, g, dev);
+    } else {
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_games_kernel<8, false>), grid, block, 0, st, g, dev);
+        else hipLaunchKernelGGL((tfe_nt_games_kernel<1, false>), grid, block, 0, st, g, dev);
+    }
+    return 0;
+}
+
+template <class O>
+Games games_of(const O* o) {
+    Games g{};
+    g.weights = o->net.weights; g.n_games = o->n_games; g.max_steps = o->max_steps; g.gamma = o->gamma;
+    g.eps_q24 = (uint32_t)std::floor(o->epsilon * 16777216.0);                         // once, here: the kernel compares integers
+    g.env_seed = o->env_seed; g.agent_seed = o->agent_seed; g.tie_seed = o->tie_seed; g.board_id0 = o->board_id0; g.round = o->round;
+    return g;
+}
+
+}  // namespace
+
+extern "C" int pulse_tfe_nt_rollout(const PulseTfeNtRollout* o, void* stream) {
+    const char* name = "pulse_tfe_nt_rollout";
+    if (!o) return fail_named(name, "options are null");
+    NtDev dev;
+    if (int rc = check_net(o->net, true, name, &dev)) return rc;
+    if (int rc = check_batch(o, name)) return rc;
+    if (!(o->epsilon >= 0.0 && o->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
+    if (!o->keys) return fail_named(name, "keys is null");
+    if (!o->values) return fail_named(name, "values is null");
+    if (!o->steps) return fail_named(name, "steps is null");
+    if (!o->lengths) return fail_named(name, "lengths is null");
+    if (!o->total_score) return fail_named(name, "total_score is null");
+    if (!o->episode_reward) return fail_named(name, "episode_reward is null");
+    if (!o->stats) return fail_named(name, "stats is null");
+    if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->values & 7u) || ((uintptr_t)o->total_score & 7u) || ((uintptr_t)o->stats & 7u))
+        return fail_named(name, "keys / values / total_score / stats must be 8-byte aligned");
+    if (((uintptr_t)o->lengths & 3u) || ((uintptr_t)o->episode_reward & 3u)) return fail_named(name, "lengths / episode_reward must be 4-byte aligned");
+    Games g = games_of(o);
+    g.keys = o->keys; g.values = o->values; g.steps = o->steps; g.lengths = o->lengths; g.total_score = o->total_score;
+    g.episode_reward = o->episode_reward; g.stats = o->stats;
+    if (int rc = launch_games(g, dev, o->net.symmetric != 0, true, stream)) return rc;
+    return finish_launch("pulse_tfe_nt_rollout launch");
+}
+
+extern "C" int pulse_tfe_nt_evaluate(const PulseTfeNtEval* o, void* stream) {
+    const char* name = "pulse_tfe_nt_evaluate";
+    if (!o) return fail_named(name, "options are null");
+    NtDev dev;
+    if (int rc = check_net(o->net, true, name, &dev)) return rc;
+    if (int rc = check_batch(o, name)) return rc;
+    if (!(o->epsilon >= 0.0 && o->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
+    if (!o->summary) return fail_named(name, "summary is null");
+    if (!o->max_tile_hist) return fail_named(name, "max_tile_hist is null");
+    if (((uintptr_t)o->summary & 7u) || ((uintptr_t)o->max_tile_hist & 7u)) return fail_named(name, "summary / max_tile_hist must be 8-byte aligned");
+    if ((uintptr_t)o->total_score & 7u) return fail_named(name, "total_score must be 8-byte aligned");
+    if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
+    Games g = games_of(o);
+    g.lengths = o->lengths; g.total_score = o->total_score; g.stats = o->summary; g.hist = o->max_tile_hist;
+    if (int rc = launch_games(g, dev, o->net.symmetric != 0, false, stream)) return rc;
+    return finish_launch("pulse_tfe_nt_evaluate launch");
+}
+
+extern "C" int pulse_tfe_nt_learn(const PulseTfeNtLearn* o, void* stream) {
+    const char* name = "pulse_tfe_nt_learn";
+    if (!o) return fail_named(name, "options are null");
+    NtDev dev;
+    if (int rc = check_net(o->net, false, name, &dev)) return rc;
+    if (int rc = check_batch(o, name)) return rc;
+    if (!o->keys) return fail_named(name, "keys is null");
+    if (!o->values) return fail_named(name, "values is null");
+    if (!o->steps) return fail_named(name, "steps is null");
+    if (!o->lengths) return fail_named(name, "lengths is null");
+    if (int rc = check_acc(o->acc, name)) return rc;
+    if (!o->stats) return fail_named(name, "stats is null");
+    if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->values & 7u) || ((uintptr_t)o->stats & 7u)) return fail_named(name, "keys / values / stats must be 8-byte aligned");
+    if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
+    const dim3 grid((unsigned)((o->n_games + kBlock - 1) / kBlock), (unsigned)o->max_steps), block(kBlock);
+    if (o->net.symmetric) hipLaunchKernelGGL(tfe_nt_learn_kernel<8>, grid, block, 0, (hipStream_t)stream, *o, dev);
+    else hipLaunchKernelGGL(tfe_nt_learn_kernel<1>, grid, block, 0, (hipStream_t)stream, *o, dev);
+    return finish_launch("pulse_tfe_nt_learn launch");
+}
+
+extern "C" int pulse_tfe_nt_apply(const PulseTfeNtApply* o, void* stream) {
+    const char* name = "pulse_tfe_nt_apply";
+    if (!o) return fail_named(name, "options are null");
+    NtDev dev;
+    if (int rc = check_net(o->net, true, name, &dev)) return rc;
+    if (!(o->step > 0.0 && o->step <= 1.0)) return fail_named(name, "step must be in (0, 1]");
+    if (int rc = check_acc(o->acc, name)) return rc;
+    if (o->reserved0 != 0) return fail_named(name, "reserved0 must be 0 (zero-initialise the struct)");
+    const dim3 grid((unsigned)((o->net.n_weights + kBlock - 1) / kBlock)), block(kBlock);
+    hipLaunchKernelGGL(tfe_nt_apply_kernel, grid, block, 0, (hipStream_t)stream, o->net.weights, reinterpret_cast<longlong2*>(o->acc), o->net.n_weights, o->step);
+    return finish_launch("pulse_tfe_nt_apply launch");
+}

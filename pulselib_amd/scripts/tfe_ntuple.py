@@ -1,0 +1,66 @@
+"""An n-tuple network for 2048 on the 4 x 4 board, trained by batch TD(0) on afterstates with the whole loop on the device
+(agents/tfe_ntuple_td_gpu.py): every round is a roll-out launch of `--tables` whole games under the network,
+a learn launch of one lane per recorded move and an apply launch over the weights.  Defaults: the network of two rows and two 2 x 3
+rectangles over the board's eight images, gamma 1, epsilon 0, alpha 1.  Every `--eval-every` rounds (default: every round) it
+prints, from ONE evaluation launch of `--eval-games` games under the greedy policy on the same boards every time: the mean final
+score and its standard error, the mean length and the histogram of the largest tile.  `--save PATH` writes the non-zero weights and
+the run's state at the end, `--resume PATH` continues such a run for `--rounds` more rounds."""
+from __future__ import annotations
+
+import argparse
+import time
+
+import torch
+
+from ..agents import NTupleTDAfterstateTFEGPU
+
+
+def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
+        resume=None, out=print):
+    if resume:
+        agent = NTupleTDAfterstateTFEGPU.load(resume, device)
+        want = dict(n_games=tables, alpha=float(alpha), epsilon=float(epsilon), gamma=float(gamma), max_steps=max_steps, seed=seed)
+        differ = {k: (getattr(agent, k), v) for k, v in want.items() if getattr(agent, k) != v}
+        if differ:
+            raise ValueError(f"{resume} continues another run: (saved, asked) {differ}")
+    else:
+        agent = NTupleTDAfterstateTFEGPU(device, tables, gamma=gamma, epsilon=epsilon, alpha=alpha, max_steps=max_steps, seed=seed)
+    first, moves_before, t0 = agent.round, agent.stats()["moves"], time.perf_counter()
+    for r in range(first, first + rounds):
+        agent.learn_batch()
+        if eval_every and ((r + 1) % eval_every == 0 or r + 1 == first + rounds):
+            e = agent.evaluate(n_games=eval_games)                          # (synchronises)
+            st, now = agent.stats(), time.perf_counter()
+            out(f"Round {r}: greedy policy over {e['games']} games: Avg final score: {e['mean_score']:.1f} +- {e['std_score'] / e['games'] ** .5:.1f}, "
+                f"Highest: {e['max_score']}, Avg length: {e['mean_length']:.1f}, cut {e['truncated']}, largest tile 2^k: {e['max_tile_hist']}; "
+                f"training: Avg final score {agent.total_score.double().mean().item():.1f}, moves/sec {(st['moves'] - moves_before) / (now - t0):.0f}, "
+                f"skipped {st['skipped']}, clamped {st['clamped']}")
+            moves_before, t0 = st["moves"], time.perf_counter()
+    if save:
+        agent.save(save)
+    return agent
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--tables", type=int, default=65536, help="games per round (one update of the weights per round)")
+    ap.add_argument("--rounds", type=int, default=16)
+    ap.add_argument("--alpha", type=float, default=1.0, help="a weight moves by alpha / F of the mean temporal difference of its visits")
+    ap.add_argument("--epsilon", type=float, default=0.0)
+    ap.add_argument("--gamma", type=float, default=1.0)
+    ap.add_argument("--max-steps", type=int, default=4096)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--eval-every", type=int, default=1, help="rounds between evaluations of the greedy policy (0: never)")
+    ap.add_argument("--eval-games", type=int, help="games per evaluation (default: --tables)")
+    ap.add_argument("--save", metavar="PATH", help="write the non-zero weights and the run's state to this .npz at the end")
+    ap.add_argument("--resume", metavar="PATH", help="continue the run saved there (the same --tables, --alpha, --epsilon, --gamma, --max-steps, --seed)")
+    args = ap.parse_args(argv)
+    agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
+                args.eval_games, args.save, args.resume)
+    st = agent.stats()
+    print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
+          f"{int((agent.weights_dev != 0).sum().item())} of {agent.n_weights} weights are not zero")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,114 @@
+"""Launch times of the 2048 n-tuple network (csrc/tfe_ntuple.hip, agents/tfe_ntuple_td_gpu.py), ONE JSON line
+per batch size B (65,536 and 1,048,576 games per round by default; a size whose buffers do not fit the free device memory is
+skipped and says so) and state of the weights:
+  zero    : every timed round starts from ZERO weights (the weights are cleared before it, untimed): greedy on the reward, short
+            games, every lane of a wavefront on the same few hot weights.
+  trained : --trained-rounds T (8) untimed rounds first, then the timed rounds go on learning: longer games, spread indices.
+Per state --warmup W (2) untimed rounds, then --repeats R (5) timed ones; the roll-out, the learn and the apply launch each sit between
+their own pair of HIP events; min / median / max of each, the moves per round beside them, moves/s of the roll-out and of the learn
+launch, 16-byte accumulator atomics/s of the learn launch (2 F per move) and bytes/s of the apply launch (20 bytes per weight read,
+20 written where touched: only the read side is counted).  Then the evaluation launch on the weights the rounds left, --repeats
+times after one untimed call.  max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes).  Lines are also
+appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _spread(xs):
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs)}
+
+
+def _timed_round(agent, torch):
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    ev[0].record()
+    agent.rollout()
+    ev[1].record()
+    agent.learn()
+    ev[2].record()
+    agent.apply()
+    ev[3].record()
+    agent.round += 1
+    ev[3].synchronize()
+    return [ev[i].elapsed_time(ev[i + 1]) * 1e-3 for i in range(3)]
+
+
+def _timed_evaluate(agent, torch):
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    agent.eval_counters(clear=True)
+    ev[0].record()
+    agent.evaluate_launch()
+    ev[1].record()
+    ev[1].synchronize()
+    return ev[0].elapsed_time(ev[1]) * 1e-3, agent.eval_counters()
+
+
+def state_line(agent, torch, state, trained_rounds, warmup, repeats):
+    agent.clear()
+    for _ in range(trained_rounds if state == "trained" else 0):
+        agent.learn_batch()
+    times, moves = [], []
+    for i in range(warmup + repeats):
+        if state == "zero":
+            agent.weights_dev.zero_()
+        before = agent.stats()["moves"]                                     # (synchronises: outside the events)
+        t = _timed_round(agent, torch)
+        if i >= warmup:
+            times.append(t)
+            moves.append(agent.stats()["moves"] - before)
+    ro, le, ap = (_spread([t[i] for t in times]) for i in range(3))
+    m, F, W = statistics.mean(moves), agent.n_features, agent.n_weights
+    agent.evaluate()                                                        # untimed: the evaluation kernel's code object
+    evals = [_timed_evaluate(agent, torch) for _ in range(repeats)]
+    ev_s, e = _spread([s for s, _ in evals]), evals[-1][1]
+    st = agent.stats()
+    return {"games": agent.n_games, "state": state, "tuples": [list(t) for t in agent.tuples], "features": F, "weights": W, "max_steps": agent.max_steps,
+            "trained_rounds": trained_rounds if state == "trained" else 0, "warmup": warmup, "repeats": repeats,
+            "rollout_s": ro, "learn_s": le, "apply_s": ap, "round_s": _spread([sum(t) for t in times]), "moves_per_round": m,
+            "rollout_moves_per_s": m / ro["median"], "learn_moves_per_s": m / le["median"], "learn_atomics_per_s": 2 * F * m / le["median"],
+            "apply_read_bytes_per_s": 20 * W / ap["median"], "mean_final_score_last_round": agent.total_score.double().mean().item(),
+            "skipped": st["skipped"], "clamped": st["clamped"], "truncated": st["truncated"],
+            "evaluate": {"seconds": ev_s, "moves": e["moves"], "moves_per_s": e["moves"] / ev_s["median"], "mean_score": e["mean_score"],
+                         "std_score": e["std_score"], "mean_length": e["mean_length"], "truncated": e["truncated"]}}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--games", type=int, nargs="+", default=[65536, 1048576])
+    ap.add_argument("--states", nargs="+", default=["zero", "trained"], choices=["zero", "trained"])
+    ap.add_argument("--trained-rounds", type=int, default=8)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--max-steps", type=int, default=4096)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
+    args = ap.parse_args(argv)
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_tfe_ntuple needs the MI355X: no timing is taken on a CPU")
+    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
+    from pulselib_amd.agents.tfe_ntuple_td_gpu import DEFAULT_TUPLES, tuple_offsets
+    dev = torch.device("cuda:0")
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    for games in args.games:
+        need = 20 * tuple_offsets(DEFAULT_TUPLES)[1] + 17 * games * args.max_steps + 64 * games
+        free = torch.cuda.mem_get_info(dev)[0]
+        if need > 0.9 * free:
+            lines = [{"games": games, "skipped": f"needs {need} bytes of device memory, {free} are free"}]
+        else:
+            agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=args.max_steps, seed=0)
+            lines = [state_line(agent, torch, s, args.trained_rounds, args.warmup, args.repeats) for s in args.states]
+            del agent
+            torch.cuda.empty_cache()
+        for line in lines:
+            print(json.dumps(line), flush=True)
+            with open(args.out, "a") as fh:
+                fh.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
