@@ -14,14 +14,14 @@ depend on scheduling: `feature_cells_on_host`, `value_on_host`, `greedy_nt_on_ho
 the host's statement of the same arithmetic in numpy, vectorised over boards, and the device is held to them word for word."""
 from __future__ import annotations
 
-import ctypes as C
 import functools
-import math
 
 import numpy as np
 
 from .. import _native
-from .tfe_on_policy_mc_gpu import AGENT_KEY, EVAL_BINS, TIE_KEY, transforms_on_host
+from .tfe_common import (AGENT_KEY, EVAL_BINS, TIE_KEY, _TFEGamesGPU, greedy_scan_many_on_host, philox_many_on_host,  # noqa: F401 (re-exported)
+                         rewards_of_scores, transforms_on_host, unpack_steps)
+from .tfe_common import eval_summary_on_host as _eval_summary_on_host
 
 MAX_TUPLES, MAX_LEN, FRAC_BITS, DELTA_MAX = _native.TFE_NT_MAX_TUPLES, _native.TFE_NT_MAX_LEN, _native.TFE_NT_FRAC_BITS, _native.TFE_NT_DELTA_MAX
 DEFAULT_TUPLES = ((0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))       # two rows and two 2 x 3 rectangles
@@ -29,7 +29,7 @@ STATS = ("moves", "learnt", "skipped", "truncated", "clamped")                  
 EVAL_SUMMARY = ("games", "moves", "score_sum", "score_sq_sum", "max_score", "truncated", "moves_greedy", "tile_capped")
 CHECKPOINT_VERSION = 1
 CHECKPOINT_SCALARS = ("symmetric", "gamma", "epsilon", "alpha", "max_steps", "seed", "board_id0", "round", "n_games")
-_U64, _M32 = np.uint64, np.uint64(0xFFFFFFFF)
+_U64 = np.uint64
 
 
 # ------------------------------------------------------------------ the network's shape
@@ -81,20 +81,7 @@ def value_on_host(keys, weights, tuples, symmetric=True) -> np.ndarray:
     return v
 
 
-# ------------------------------------------------------------------ the environment's move and Philox, over many boards
-def philox_many_on_host(seed: int, subseq, offset) -> np.ndarray:
-    """uint32[N, 4]: Philox4x32-10 with the device's layout (csrc/philox_device.h) -- counter {offset, subseq}, key = seed -- for
-    arrays (or scalars) of subseq and offset."""
-    subseq, offset = np.broadcast_arrays(np.asarray(subseq, dtype=_U64).reshape(-1), np.asarray(offset, dtype=_U64).reshape(-1))
-    c0, c1, c2, c3 = offset & _M32, offset >> _U64(32), subseq & _M32, subseq >> _U64(32)
-    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
-    for _ in range(10):
-        p0, p1 = _U64(0xD2511F53) * c0, _U64(0xCD9E8D57) * c2                  # 32 x 32 -> 64 bits: no overflow
-        c0, c1, c2, c3 = (p1 >> _U64(32)) ^ c1 ^ _U64(k0), p1 & _M32, (p0 >> _U64(32)) ^ c3 ^ _U64(k1), p0 & _M32
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return np.stack([c0, c1, c2, c3], axis=1).astype(np.uint32)
-
-
+# ------------------------------------------------------------------ the environment's move, over many boards
 @functools.lru_cache(maxsize=None)
 def row_table_on_host():
     """(row after the squash to the left uint16[65536], merge score int64[65536]) of every row of four nibbles (TFE.py:85-101: a
@@ -135,12 +122,6 @@ def moves_on_host(keys):
     return after, score
 
 
-def rewards_of_scores(scores) -> np.ndarray:
-    """TFE.py:185-187 over an array: bit length - 1 of a merge score, 0 for 0 (scores are sums of powers of two below 2^18: exact)."""
-    s = np.asarray(scores, dtype=np.int64)
-    return np.where(s > 0, np.floor(np.log2(np.maximum(s, 1))).astype(np.int64), 0)
-
-
 def greedy_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: int, round: int) -> dict:
     """The roll-out's greedy rule on packed boards: q_a = r_a + gamma * V(B_a) in float64 for the four moves; the candidates are the
     moves with B_a != B, scanned in the order a = 0..3 -- the first is the best so far, a larger q replaces it, an equal q replaces
@@ -151,24 +132,11 @@ def greedy_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
     rewards = rewards_of_scores(scores)
     values = value_on_host(after.reshape(-1), weights, tuples, symmetric).reshape(-1, 4)
     q = rewards.astype(np.float64) + float(gamma) * values
-    coins = philox_many_on_host(tie_seed, keys, int(round)) >> np.uint32(31)
-    best, best_q = np.full(len(keys), -1, dtype=np.int64), np.zeros(len(keys), dtype=np.float64)
-    for a in range(4):
-        cand = after[:, a] != keys
-        take = cand & ((best < 0) | (q[:, a] > best_q))
-        if a:
-            take |= cand & (best >= 0) & (q[:, a] == best_q) & (coins[:, a - 1] != 0)
-        best, best_q = np.where(take, a, best), np.where(take, q[:, a], best_q)
+    best = greedy_scan_many_on_host(q, philox_many_on_host(tie_seed, keys, int(round)), after != keys[:, None])
     return dict(action=best, after=after, scores=scores, rewards=rewards, values=values, q=q)
 
 
 # ------------------------------------------------------------------ the learner and the apply launch
-def unpack_steps(steps):
-    """(action, reward, terminal) of the per-move bytes."""
-    s = np.asarray(steps, dtype=np.uint8)
-    return s & 3, (s >> 2) & 31, (s >> 7).astype(bool)
-
-
 def learn_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, acc):
     """pulse_tfe_nt_learn on the host.  keys uint64[T, B], values float64[T, B], steps uint8[T, B], lengths int[B]; acc int64[W, 2] =
     {sum, cnt}, added to in place.  Move (t, g), t < lengths[g]: the last move of a game has target 0 with its terminal bit and is
@@ -205,16 +173,8 @@ def apply_nt_on_host(weights, acc, step: float) -> int:
 
 
 def eval_summary_on_host(words) -> dict:
-    """pulse_tfe_nt_evaluate's 8 + 16 counters as a dict: the words by name, the histogram of the largest tile (bin = its log2), and
-    mean / std (sample standard deviation, from the exact integer sums) of the final score and the mean length."""
-    w = [int(x) for x in words]
-    out = dict(zip(EVAL_SUMMARY, w[:len(EVAL_SUMMARY)]))
-    n, s, ss = out["games"], out["score_sum"], out["score_sq_sum"]
-    out["max_tile_hist"] = w[len(EVAL_SUMMARY):len(EVAL_SUMMARY) + EVAL_BINS]
-    out["mean_score"] = s / n if n else 0.0
-    out["std_score"] = math.sqrt((n * ss - s * s) / (n * (n - 1))) if n > 1 else 0.0              # exact integers under the root
-    out["mean_length"] = out["moves"] / n if n else 0.0
-    return out
+    """pulse_tfe_nt_evaluate's 8 + 16 counters as a dict (tfe_common.eval_summary_on_host with this agent's EVAL_SUMMARY)."""
+    return _eval_summary_on_host(words, EVAL_SUMMARY)
 
 
 # ------------------------------------------------------------------ the checkpoint file
@@ -267,40 +227,24 @@ def weights_of_checkpoint(f: dict) -> np.ndarray:
 
 
 # ------------------------------------------------------------------ the device agent
-class NTupleTDAfterstateTFEGPU:
+class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     """`learn_batch` = `rollout` + `learn` + `apply` + `round += 1`: three launches and no synchronisation.  Everything that reads
     back (`weights`, `stats`, `trajectory`, `evaluate`, the per-game arrays' `.cpu()`) synchronises.  Round r plays the boards
     board_id0 + r * n_games + g, so no two rounds replay the same spawns."""
+    STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
 
     def __init__(self, device, n_games, tuples=DEFAULT_TUPLES, symmetric=True, gamma=1.0, epsilon=0.0, alpha=1.0, max_steps=4096, seed=0,
                  board_id0=0):
         import torch
-        device = _native.gpu_device(device, "NTupleTDAfterstateTFEGPU")
-        self.tuples = check_tuples(tuples)
-        if int(n_games) < 1 or not 1 <= int(max_steps) <= 65535:
-            raise ValueError("n_games must be positive and max_steps in 1..65535")
-        if not (0.0 <= gamma <= 1.0 and 0.0 <= epsilon <= 1.0):
-            raise ValueError("gamma and epsilon must be in [0, 1]")
-        self._lib = _native.lib()
-        self.device = device
-        self.n, self.n_games, self.max_steps, self.symmetric = 4, int(n_games), int(max_steps), bool(symmetric)
-        self.gamma, self.epsilon, self.alpha = float(gamma), float(epsilon), float(alpha)
+        super().__init__(device, n_games, 4, max_steps, gamma, epsilon, seed, board_id0)
+        self.tuples, self.symmetric, self.alpha = check_tuples(tuples), bool(symmetric), float(alpha)
         self.n_features = len(self.tuples) * (8 if self.symmetric else 1)
         if not 0.0 < self.alpha <= self.n_features:
             raise ValueError("alpha must be in (0, F]: the apply launch takes step = alpha / F in (0, 1]")
         self.offsets, self.n_weights = tuple_offsets(self.tuples)
-        self.seed, self.board_id0, self.round = int(seed), int(board_id0), 0
-        self.env_seed, self.agent_seed, self.tie_seed = self.seed, self.seed ^ AGENT_KEY, self.seed ^ TIE_KEY
-        self.weights_dev = torch.zeros(self.n_weights, dtype=torch.float32, device=device)
-        self.acc = torch.zeros((self.n_weights, 2), dtype=torch.int64, device=device)                 # {sum, cnt}; torch allocations are 16-byte aligned
-        self.keys = torch.zeros((self.max_steps, self.n_games), dtype=torch.int64, device=device)     # (uint64 words)
-        self.values = torch.zeros((self.max_steps, self.n_games), dtype=torch.float64, device=device)
-        self.steps = torch.zeros((self.max_steps, self.n_games), dtype=torch.uint8, device=device)
-        self.lengths = torch.zeros(self.n_games, dtype=torch.int32, device=device)
-        self.total_score = torch.zeros(self.n_games, dtype=torch.int64, device=device)
-        self.episode_reward = torch.zeros(self.n_games, dtype=torch.int32, device=device)
-        self.counters = torch.zeros(8, dtype=torch.int64, device=device)
-        self._eval = torch.zeros(len(EVAL_SUMMARY) + EVAL_BINS, dtype=torch.int64, device=device)     # evaluate(): summary, then the histogram
+        self.weights_dev = torch.zeros(self.n_weights, dtype=torch.float32, device=self.device)
+        self.acc = torch.zeros((self.n_weights, 2), dtype=torch.int64, device=self.device)            # {sum, cnt}; torch allocations are 16-byte aligned
+        self.values = torch.zeros((self.max_steps, self.n_games), dtype=torch.float64, device=self.device)
 
     # ------------------------------------------------------------------ the launches
     def _net(self, net):
@@ -311,20 +255,12 @@ class NTupleTDAfterstateTFEGPU:
                 net.cells[t][i] = c
         net.n_weights, net.weights = self.n_weights, self.weights_dev.data_ptr()
 
-    def _launch(self, name, o):
-        _native.check(getattr(self._lib, name)(C.byref(o), _native.current_stream(self.device)), name)
-        return self
-
-    def round_board_id0(self, round=None) -> int:
-        return self.board_id0 + (self.round if round is None else int(round)) * self.n_games
-
     def rollout(self):
         """One launch: n_games games under the weights as they stand (round `self.round`), into keys / values / steps / lengths /
         scores."""
-        o = _native.TfeNtRollout()
+        o = self._draws(_native.TfeNtRollout(), self.round_board_id0())
         self._net(o.net)
         o.n_games, o.max_steps, o.gamma, o.epsilon = self.n_games, self.max_steps, self.gamma, self.epsilon
-        o.env_seed, o.agent_seed, o.tie_seed, o.board_id0, o.round = self.env_seed, self.agent_seed, self.tie_seed, self.round_board_id0(), self.round
         o.keys, o.values, o.steps, o.lengths = self.keys.data_ptr(), self.values.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr()
         o.total_score, o.episode_reward, o.stats = self.total_score.data_ptr(), self.episode_reward.data_ptr(), self.counters.data_ptr()
         return self._launch("pulse_tfe_nt_rollout", o)
@@ -353,62 +289,24 @@ class NTupleTDAfterstateTFEGPU:
         return self
 
     # ------------------------------------------------------------------ evaluation
-    def eval_board_id0(self) -> int:
-        """evaluate()'s default boards: board_id0 + 2^62 + g, which training meets only after 2^62 / n_games rounds; every call with
-        the default replays the same spawns (scores under two networks are paired)."""
-        return (self.board_id0 + (1 << 62)) & 0xFFFFFFFFFFFFFFFF
-
-    def evaluate_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False):
-        """The launch of evaluate() alone: ADDS to the counters of `eval_counters` and reads nothing back.  Returns the per-game device
-        tensors (total_score int64[B], lengths int32[B]) with per_game, else None."""
-        import torch
-        B = self.n_games if n_games is None else int(n_games)
+    def _eval_struct(self):
         o = _native.TfeNtEval()
         self._net(o.net)
-        o.n_games, o.max_steps, o.gamma, o.epsilon = B, self.max_steps, self.gamma, float(epsilon)
-        o.env_seed, o.agent_seed, o.tie_seed, o.round = self.env_seed, self.agent_seed, self.tie_seed, self.round
-        o.board_id0 = self.eval_board_id0() if board_id0 is None else int(board_id0)
-        o.summary, o.max_tile_hist = self._eval.data_ptr(), self._eval[len(EVAL_SUMMARY):].data_ptr()
-        arrays = None
-        if per_game:
-            arrays = (torch.zeros(B, dtype=torch.int64, device=self.device), torch.zeros(B, dtype=torch.int32, device=self.device))
-            o.total_score, o.lengths = arrays[0].data_ptr(), arrays[1].data_ptr()
+        o.gamma = self.gamma
+        return o
+
+    def _eval_launch(self, o):
         self._launch("pulse_tfe_nt_evaluate", o)
-        return arrays
-
-    def eval_counters(self, clear=False) -> dict:
-        """What the evaluation launches since the last clear added up to (eval_summary_on_host; synchronises), or, with clear,
-        nothing: the counters are zeroed."""
-        if clear:
-            self._eval.zero_()
-            return {}
-        return eval_summary_on_host(self._eval.cpu().tolist())
-
-    def evaluate(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False) -> dict:
-        """One launch and one read-back: `n_games` games (default: the agent's) under the weights as they stand and `epsilon` (default 0:
-        the greedy policy), no trajectory.  With equal seeds, round, epsilon and board_id0 they are the games rollout() plays.  Returns
-        the counters by name, the histogram of the largest tile, mean / standard deviation of the final score and the mean length;
-        per_game adds the arrays total_score / lengths."""
-        self.eval_counters(clear=True)
-        arrays = self.evaluate_launch(n_games, epsilon, board_id0, per_game)
-        out = self.eval_counters()
-        if per_game:
-            out["total_score"], out["lengths"] = arrays[0].cpu().numpy(), arrays[1].cpu().numpy()
-        return out
 
     # ------------------------------------------------------------------ read-back (the only syncs) and the checkpoint
     def weights(self) -> np.ndarray:
         """float32[n_weights] on the host."""
         return self.weights_dev.cpu().numpy()
 
-    def stats(self) -> dict:
-        return dict(zip(STATS, self.counters.cpu().tolist()[:len(STATS)]))
-
     def trajectory(self):
         """(keys uint64[T, B], values float64[T, B], steps uint8[T, B], lengths int32[B]) of the last batch, T = the longest game; rows
         at and beyond a game's length hold whatever the buffers held before."""
-        lengths = self.lengths.cpu().numpy()
-        T = int(lengths.max()) if lengths.size else 0
+        T, lengths = self._played()
         return self.keys[:T].cpu().numpy().view(np.uint64), self.values[:T].cpu().numpy(), self.steps[:T].cpu().numpy(), lengths
 
     def save(self, path):

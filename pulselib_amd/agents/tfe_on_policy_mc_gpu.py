@@ -17,6 +17,8 @@ recording them and returns score statistics reduced in the launch.
 
 `learn_on_host`, `greedy_on_host`, `first_visit_flags_on_host` and `run_mask_flags_on_host` are the host's statement of the same
 arithmetic, in numpy and pure Python; `transforms_on_host`, `canon_on_host`, `ACTION_MAP` and `fold_table_on_host` that of the symmetries.
+What the n-tuple agent shares with this one (Philox, the state key, the greedy scan, the evaluation counters, the agents' base class)
+is in tfe_common.py and re-exported here.
 
 The table as a whole goes through one more launch, `pulse_tfe_mc_table_merge`: dst += src over entries by key.
 `merge_from` adds another agent's table (folding a plain one into a symmetric one), `grow` re-inserts the table into a larger one,
@@ -29,20 +31,19 @@ reward + gamma * v among the board's four afterstates (`pulse_tfe_mc_rollout_aft
 `learn_after_on_host` and `fold_values_on_host` are the host's statement of it."""
 from __future__ import annotations
 
-import ctypes as C
 import functools
 import math
 
 import numpy as np
 
 from .. import _native
+from .tfe_common import (AGENT_KEY, EVAL_BINS, TIE_KEY, _TFEGamesGPU, greedy_scan_on_host, pack_board, philox4x32,  # noqa: F401 (re-exported)
+                         reward_of_score, transforms_on_host, unpack_key, unpack_steps)
+from .tfe_common import eval_summary_on_host as _eval_summary_on_host
 
 ENTRY_BYTES, MAX_PROBE, R_MAX = _native.TFE_MC_ENTRY_BYTES, _native.TFE_MC_MAX_PROBE, _native.TFE_MC_R_MAX
-AGENT_KEY = 0x2048AC7105EED                     # the agent's draws are keyed apart from the environment's (the seed itself) ...
-TIE_KEY = 0x20487C01F11B5                       # ... and the tie coins apart from both
 STATS = ("steps", "first_visits", "dropped", "truncated")
 EVAL_SUMMARY = ("games", "moves", "score_sum", "score_sq_sum", "max_score", "truncated", "moves_with_entry", "moves_greedy")
-EVAL_BINS = 16                                  # bin = log2 of the largest tile of the final board
 MERGE_STATS = ("live", "placed", "dropped")     # pulse_tfe_mc_table_merge's counters
 
 
@@ -57,30 +58,6 @@ def frac_bits_for(gamma: float, max_steps: int) -> int:
     raise ValueError("no frac_bits fits")
 
 
-def philox4x32(seed: int, subseq: int, offset: int):
-    """Philox4x32-10 with the device's layout (csrc/blackjack_device.h): counter {offset, subseq}, key = seed.  Four uint32 as ints."""
-    c0, c1, c2, c3 = offset & 0xFFFFFFFF, (offset >> 32) & 0xFFFFFFFF, subseq & 0xFFFFFFFF, (subseq >> 32) & 0xFFFFFFFF
-    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
-        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & 0xFFFFFFFF, (p0 >> 32) ^ c3 ^ k1, p0 & 0xFFFFFFFF
-        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
-    return [c0, c1, c2, c3]
-
-
-def pack_board(board) -> int:
-    """The state key: 4 bits of log2(tile) per cell (0 = empty), row-major, cell 0 in the low nibble."""
-    key = 0
-    for i, v in enumerate(np.asarray(board).ravel().tolist()):
-        key |= (min(int(v).bit_length() - 1, 15) if v > 0 else 0) << (4 * i)
-    return key
-
-
-def unpack_key(key: int, n: int) -> list:
-    """The n * n log2 tiles of a state key, row-major."""
-    return [(int(key) >> (4 * i)) & 15 for i in range(n * n)]
-
-
 # The eight symmetries of the square (DESIGN.md section 12.1).  T_0..T_3 rotate the board 0..3 times by the environment's own
 # rotation (TFE.py:38-44: out[r][c] = in[c][n - 1 - r]); T_4..T_7 do the same to the transposed board.  ACTION_MAP[j][a] is the
 # action with T_j(move(B, a)) == move(T_j(B), ACTION_MAP[j][a]): the moves are 0 left, 1 up, 2 right, 3 down, a rotation turns
@@ -88,19 +65,6 @@ def unpack_key(key: int, n: int) -> list:
 # the environment's move; the device holds the same 32 numbers, two bits each, in one 64-bit constant.)
 ACTION_MAP = ((0, 1, 2, 3), (3, 0, 1, 2), (2, 3, 0, 1), (1, 2, 3, 0), (1, 0, 3, 2), (0, 3, 2, 1), (3, 2, 1, 0), (2, 1, 0, 3))
 ACTION_UNMAP = tuple(tuple(row.index(a) for a in range(4)) for row in ACTION_MAP)      # ACTION_UNMAP[j][ACTION_MAP[j][a]] == a
-
-
-def transforms_on_host(n: int) -> np.ndarray:
-    """int64[8, n * n]: T_j(B).ravel() == B.ravel()[transforms_on_host(n)[j]]."""
-    out = np.zeros((8, n * n), dtype=np.int64)
-    for j in range(8):
-        for r in range(n):
-            for c in range(n):
-                rr, cc = r, c
-                for _ in range(j & 3):                                     # rot_src of csrc/tfe_device.h
-                    rr, cc = cc, n - 1 - rr
-                out[j, r * n + c] = cc * n + rr if j >= 4 else rr * n + cc
-    return out
 
 
 def canon_key_on_host(key: int, n: int):
@@ -117,44 +81,33 @@ def canon_on_host(board):
     return canon_key_on_host(pack_board(board), board.shape[-1])
 
 
-def fold_table_on_host(table: dict, n: int) -> dict:
-    """A plain table {key: (cnt[4], sum[4])} as the table of canonical states: every entry goes to its canonical key with cnt / sum
-    permuted by ACTION_MAP[j*], and entries that meet are added.  (n: the board side the keys were packed for.)"""
-    out = {}
-    for key, (cnt, total) in table.items():
-        key_c, j = canon_key_on_host(key, n)
-        c, s = out.setdefault(key_c, ([0] * 4, [0] * 4))
-        for a in range(4):
-            c[ACTION_MAP[j][a]] += int(cnt[a])
-            s[ACTION_MAP[j][a]] += int(total[a])
-    return out
-
-
-def merge_tables_on_host(dst: dict, src: dict, n=None, canonical=False) -> dict:
+def merge_tables_on_host(dst: dict, src: dict, n=None, canonical=False, keep_slots=False) -> dict:
     """pulse_tfe_mc_table_merge on the host: dst += src over entries, in place and returned.  Every entry of `src` goes to its key -- with
     `canonical` to its canonical key, cnt / sum permuted by ACTION_MAP[j*] (n: the board side the keys were packed for) -- and is added
-    to what `dst` holds there; `dst`'s own keys stay as they are.  `src` is not changed."""
+    to what `dst` holds there; `dst`'s own keys stay as they are.  `src` is not changed.  `keep_slots`: cnt / sum stay in the slots
+    they have (pulse_tfe_mc_table_fold_after: a value has no action to map)."""
     if canonical and n is None:
         raise ValueError("canonical=True needs the board side n")
     for key, (cnt, total) in src.items():
         key_c, j = canon_key_on_host(key, n) if canonical else (int(key), 0)
         c, s = dst.setdefault(key_c, ([0] * 4, [0] * 4))
+        amap = ACTION_MAP[0 if keep_slots else j]
         for a in range(4):
-            c[ACTION_MAP[j][a]] += int(cnt[a])
-            s[ACTION_MAP[j][a]] += int(total[a])
+            c[amap[a]] += int(cnt[a])
+            s[amap[a]] += int(total[a])
     return dst
+
+
+def fold_table_on_host(table: dict, n: int) -> dict:
+    """A plain table {key: (cnt[4], sum[4])} as the table of canonical states: every entry goes to its canonical key with cnt / sum
+    permuted by ACTION_MAP[j*], and entries that meet are added.  (n: the board side the keys were packed for.)"""
+    return merge_tables_on_host({}, table, n, canonical=True)
 
 
 def fold_values_on_host(table: dict, n: int) -> dict:
     """A plain VALUE table {key: (cnt[4], sum[4])} as the table of canonical afterstates: every entry goes to its canonical key with
     cnt / sum in the slots they have (a value has no action to map), and entries that meet are added."""
-    out = {}
-    for key, (cnt, total) in table.items():
-        c, s = out.setdefault(canon_key_on_host(key, n)[0], ([0] * 4, [0] * 4))
-        for a in range(4):
-            c[a] += int(cnt[a])
-            s[a] += int(total[a])
-    return out
+    return merge_tables_on_host({}, table, n, canonical=True, keep_slots=True)
 
 
 # ------------------------------------------------------------------ the checkpoint file (save / load)
@@ -208,12 +161,6 @@ def read_checkpoint(path, n=None) -> dict:
     return out
 
 
-def unpack_steps(steps):
-    """(action, reward, first) of the per-move bytes."""
-    s = np.asarray(steps, dtype=np.uint8)
-    return s & 3, (s >> 2) & 31, (s >> 7).astype(bool)
-
-
 def first_visit_flags_on_host(keys, actions) -> np.ndarray:
     """One game: True where (state, action) occurs for the first time -- the dict rule of OnPolicyFirstVisit.py:30-36."""
     seen, out = set(), []
@@ -243,24 +190,13 @@ def greedy_on_host(entry, key: int, tie_seed: int, round: int, philox=philox4x32
     """The greedy action of a table entry (cnt[4], sum[4]) as the roll-out takes it (OnPolicyFirstVisit.py:52-62): the actions in
     order, a larger q replaces the best, an equal q replaces it iff bit 31 of word a - 1 of philox(tie_seed, key, round) is set.
     (The factor 2^-frac_bits is exact and the same for the four q: it does not enter a comparison.)"""
-    q = q_of_entry(entry, 0)
-    coins = None
-    best, best_q = 0, q[0]
-    for a in (1, 2, 3):
-        if q[a] > best_q:
-            best, best_q = a, q[a]
-        elif q[a] == best_q:
-            if coins is None:
-                coins = [int(w) for w in philox(tie_seed, key, round)]
-            if coins[a - 1] >> 31:
-                best = a
-    return best
+    return greedy_scan_on_host(q_of_entry(entry, 0), lambda: philox(tie_seed, key, round))
 
 
-def learn_on_host(keys, steps, lengths, gamma: float, frac_bits: int, table: dict) -> dict:
-    """pulse_tfe_mc_learn on the host.  keys uint64[T, B], steps uint8[T, B], lengths int[B]; table {key: (cnt[4], sum[4])} of Python
-    ints, added to in place and returned.  Per game t = length - 1 .. 0, G = gamma * G + reward in float64; at a flagged step
-    sum[a] += round-half-even(G * 2^frac_bits), cnt[a] += 1."""
+def _learn_on_host(keys, steps, lengths, gamma: float, frac_bits: int, table: dict, after: bool) -> dict:
+    """The backward pass of both learners: per game t = length - 1 .. 0, G = gamma * G + reward in float64, one rounding per
+    operation; a flagged step adds round-half-even(G * 2^frac_bits) to sum[a] and 1 to cnt[a] of its key.  Without `after` a is the
+    step's action and G includes the step's reward; with it a = 0 and G is taken BEFORE the step's reward enters."""
     keys, steps = np.asarray(keys, dtype=np.uint64), np.asarray(steps, dtype=np.uint8)
     if keys.ndim == 1:
         keys, steps = keys[:, None], steps[:, None]
@@ -268,12 +204,23 @@ def learn_on_host(keys, steps, lengths, gamma: float, frac_bits: int, table: dic
         tail = 0.0
         for t in range(int(length) - 1, -1, -1):
             s = int(steps[t, g])
-            tail = gamma * tail + float((s >> 2) & 31)
+            if not after:
+                tail = gamma * tail + float((s >> 2) & 31)
             if s & 0x80:
+                a = 0 if after else s & 3
                 cnt, total = table.setdefault(int(keys[t, g]), ([0] * 4, [0] * 4))
-                total[s & 3] += round(math.ldexp(tail, frac_bits))
-                cnt[s & 3] += 1
+                total[a] += round(math.ldexp(tail, frac_bits))
+                cnt[a] += 1
+            if after:
+                tail = gamma * tail + float((s >> 2) & 31)
     return table
+
+
+def learn_on_host(keys, steps, lengths, gamma: float, frac_bits: int, table: dict) -> dict:
+    """pulse_tfe_mc_learn on the host.  keys uint64[T, B], steps uint8[T, B], lengths int[B]; table {key: (cnt[4], sum[4])} of Python
+    ints, added to in place and returned.  Per game t = length - 1 .. 0, G = gamma * G + reward in float64; at a flagged step
+    sum[a] += round-half-even(G * 2^frac_bits), cnt[a] += 1."""
+    return _learn_on_host(keys, steps, lengths, gamma, frac_bits, table, False)
 
 
 # ------------------------------------------------------------------ afterstates (DESIGN.md section 12.3)
@@ -313,11 +260,6 @@ def move_on_host(board, a):
     return np.array(cells, dtype=np.int64).reshape(n, n), score
 
 
-def reward_of_score(score: int) -> int:
-    """TFE.py:185-187: bit length - 1 of the merge score of a move, 0 for 0."""
-    return int(score).bit_length() - 1 if score > 0 else 0
-
-
 def afterstates_on_host(board, symmetric=False):
     """(keys[4], rewards[4]) of the four moves of a board: the afterstate's key (its canonical key with `symmetric`) and the reward."""
     board = np.asarray(board)
@@ -345,85 +287,39 @@ def greedy_after_on_host(board, table: dict, gamma: float, frac_bits: int, tie_s
     if not any(k in table for k in keys):
         return None, keys, rewards
     q = [float(r) + gamma * (v_of_entry(table[k], frac_bits) if k in table else 0.0) for k, r in zip(keys, rewards)]
-    coins = None
-    best, best_q = 0, q[0]
-    for a in (1, 2, 3):
-        if q[a] > best_q:
-            best, best_q = a, q[a]
-        elif q[a] == best_q:
-            if coins is None:
-                coins = [int(w) for w in philox(tie_seed, pack_board(board), round)]
-            if coins[a - 1] >> 31:
-                best = a
-    return best, keys, rewards
+    return greedy_scan_on_host(q, lambda: philox(tie_seed, pack_board(board), round)), keys, rewards
 
 
 def learn_after_on_host(keys, steps, lengths, gamma: float, frac_bits: int, table: dict) -> dict:
     """pulse_tfe_mc_learn_after on the host, in learn_on_host's shapes.  Per game t = length - 1 .. 0: at a flagged step
     sum[0] += round-half-even(G * 2^frac_bits), cnt[0] += 1 with G as it stands, THEN G = gamma * G + reward -- an afterstate
     collects the return that follows it."""
-    keys, steps = np.asarray(keys, dtype=np.uint64), np.asarray(steps, dtype=np.uint8)
-    if keys.ndim == 1:
-        keys, steps = keys[:, None], steps[:, None]
-    for g, length in enumerate(np.asarray(lengths).reshape(-1).tolist()):
-        tail = 0.0
-        for t in range(int(length) - 1, -1, -1):
-            s = int(steps[t, g])
-            if s & 0x80:
-                cnt, total = table.setdefault(int(keys[t, g]), ([0] * 4, [0] * 4))
-                total[0] += round(math.ldexp(tail, frac_bits))
-                cnt[0] += 1
-            tail = gamma * tail + float((s >> 2) & 31)
-    return table
+    return _learn_on_host(keys, steps, lengths, gamma, frac_bits, table, True)
 
 
 def eval_summary_on_host(words) -> dict:
-    """pulse_tfe_mc_evaluate's 8 + 16 counters as a dict: the words by name, the histogram, and mean / std (sample standard deviation,
-    from the exact integer sums) / max of the final score, the mean length and the share of moves whose state had a table entry."""
-    w = [int(x) for x in words]
-    out = dict(zip(EVAL_SUMMARY, w[:len(EVAL_SUMMARY)]))
-    n, s, ss = out["games"], out["score_sum"], out["score_sq_sum"]
-    out["max_tile_hist"] = w[len(EVAL_SUMMARY):len(EVAL_SUMMARY) + EVAL_BINS]
-    out["mean_score"] = s / n if n else 0.0
-    out["std_score"] = math.sqrt((n * ss - s * s) / (n * (n - 1))) if n > 1 else 0.0          # exact integers under the root
-    out["mean_length"] = out["moves"] / n if n else 0.0
-    out["coverage"] = out["moves_with_entry"] / out["moves"] if out["moves"] else 0.0
-    return out
+    """pulse_tfe_mc_evaluate's 8 + 16 counters as a dict (tfe_common.eval_summary_on_host with this agent's EVAL_SUMMARY)."""
+    return _eval_summary_on_host(words, EVAL_SUMMARY)
 
 
-class OnPolicyFirstVisitMCTFEGPU:
+class OnPolicyFirstVisitMCTFEGPU(_TFEGamesGPU):
     """`learn_batch` = `rollout` + `learn` + `round += 1`, two launches and no synchronisation.  Everything that reads back
     (`table`, `q`, `greedy`, `stats`, `trajectory`, the per-game arrays' `.cpu()`) synchronises."""
+    STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
 
     def __init__(self, device, n_games, board_size=3, gamma=.9, epsilon=.1, capacity=1 << 22, max_steps=1024, seed=0, board_id0=0,
                  symmetric=False, afterstate=False):
         import torch
-        device = _native.gpu_device(device, "OnPolicyFirstVisitMCTFEGPU")
+        super().__init__(device, n_games, board_size, max_steps, gamma, epsilon, seed, board_id0)
         if not 2 <= int(board_size) <= 4:
             raise ValueError("board_size must be 2..4 (the state key holds 16 cells)")
         if int(capacity) < 1 or int(capacity) & (int(capacity) - 1):
             raise ValueError("capacity must be a power of two")
-        if int(n_games) < 1 or not 1 <= int(max_steps) <= 65535:
-            raise ValueError("n_games must be positive and max_steps in 1..65535")
-        if not (0.0 <= gamma <= 1.0 and 0.0 <= epsilon <= 1.0):
-            raise ValueError("gamma and epsilon must be in [0, 1]")
-        self._lib = _native.lib()
-        self.device = device
-        self.n_games, self.n, self.capacity, self.max_steps = int(n_games), int(board_size), int(capacity), int(max_steps)
-        self.gamma, self.epsilon = float(gamma), float(epsilon)
+        self.capacity, self.symmetric = int(capacity), bool(symmetric)
         self.frac_bits = frac_bits_for(self.gamma, self.max_steps)
-        self.seed, self.board_id0, self.round, self.symmetric = int(seed), int(board_id0), 0, bool(symmetric)
         self.afterstate = bool(afterstate)              # the table holds V(afterstate) in cnt[0] / sum[0] (DESIGN.md section 12.3)
-        self.env_seed, self.agent_seed, self.tie_seed = self.seed, self.seed ^ AGENT_KEY, self.seed ^ TIE_KEY
         self.entries = self._new_table(self.capacity)
-        self.keys = torch.zeros((self.max_steps, self.n_games), dtype=torch.int64, device=device)    # (uint64 words)
-        self.steps = torch.zeros((self.max_steps, self.n_games), dtype=torch.uint8, device=device)
-        self.lengths = torch.zeros(self.n_games, dtype=torch.int32, device=device)
-        self.total_score = torch.zeros(self.n_games, dtype=torch.int64, device=device)
-        self.episode_reward = torch.zeros(self.n_games, dtype=torch.int32, device=device)
-        self.counters = torch.zeros(8, dtype=torch.int64, device=device)
-        self._eval = torch.zeros(len(EVAL_SUMMARY) + EVAL_BINS, dtype=torch.int64, device=device)     # evaluate(): summary, then the histogram
-        self._merge = torch.zeros(4, dtype=torch.int64, device=device)                                # merge_from(): live, placed, dropped
+        self._merge = torch.zeros(4, dtype=torch.int64, device=self.device)                           # merge_from(): live, placed, dropped
 
     def _new_table(self, rows):
         """int64[rows, 16] on the device, zeroed and 128-byte aligned: a table of `rows` slots, or a dense array of entries."""
@@ -441,26 +337,17 @@ class OnPolicyFirstVisitMCTFEGPU:
         o.keys, o.steps, o.lengths, o.stats = self.keys.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr(), self.counters.data_ptr()
         return o
 
-    def round_board_id0(self, round=None) -> int:
-        return self.board_id0 + (self.round if round is None else int(round)) * self.n_games
-
     def rollout(self):
         """One launch: n_games games under the table as it stands (round `self.round`), into keys / steps / lengths / scores.
         With `symmetric` the recorded keys and actions are those of the canonical frame (pulse_tfe_mc_rollout_canon).  With
         `afterstate` the keys are those of the boards after the moves and the actions the board's own (pulse_tfe_mc_rollout_after*)."""
-        o = self._head(_native.TfeMCRollout())
-        o.env_seed, o.agent_seed, o.tie_seed, o.board_id0, o.round = self.env_seed, self.agent_seed, self.tie_seed, self.round_board_id0(), self.round
+        o = self._draws(self._head(_native.TfeMCRollout()), self.round_board_id0())
         o.total_score, o.episode_reward = self.total_score.data_ptr(), self.episode_reward.data_ptr()
-        name = "pulse_tfe_mc_rollout" + ("_after" if self.afterstate else "") + ("_canon" if self.symmetric else "")
-        _native.check(getattr(self._lib, name)(C.byref(o), _native.current_stream(self.device)), name)
-        return self
+        return self._launch("pulse_tfe_mc_rollout" + ("_after" if self.afterstate else "") + ("_canon" if self.symmetric else ""), o)
 
     def learn(self):
         """One launch: the first-visit returns of the games last played, into the table."""
-        o = self._head(_native.TfeMCLearn())
-        name = "pulse_tfe_mc_learn_after" if self.afterstate else "pulse_tfe_mc_learn"
-        _native.check(getattr(self._lib, name)(C.byref(o), _native.current_stream(self.device)), name)
-        return self
+        return self._launch("pulse_tfe_mc_learn_after" if self.afterstate else "pulse_tfe_mc_learn", self._head(_native.TfeMCLearn()))
 
     def learn_batch(self):
         self.rollout()
@@ -475,8 +362,7 @@ class OnPolicyFirstVisitMCTFEGPU:
         o = _native.TfeMCMerge()
         o.src, o.src_entries, o.dst, o.dst_capacity = src.data_ptr(), src.shape[0], dst.data_ptr(), dst.shape[0]
         o.n, o.canonical, o.stats = self.n, int(canonical), stats.data_ptr()
-        name = "pulse_tfe_mc_table_fold_after" if self.afterstate and canonical else "pulse_tfe_mc_table_merge"
-        _native.check(getattr(self._lib, name)(C.byref(o), _native.current_stream(self.device)), name)
+        self._launch("pulse_tfe_mc_table_fold_after" if self.afterstate and canonical else "pulse_tfe_mc_table_merge", o)
 
     def dense_entries(self, keys, cnt, total):
         """keys uint64[m], cnt / sum int64[m, 4] of the host as a dense array of entries on the device (int64[m, 16], 128-byte aligned):
@@ -637,62 +523,23 @@ class OnPolicyFirstVisitMCTFEGPU:
             out.append(ACTION_UNMAP[j][greedy_on_host(table[k], k, self.tie_seed, r)] if k in table else None)
         return out
 
-    def eval_board_id0(self) -> int:
-        """evaluate()'s default boards: board_id0 + 2^62 + g.  Round r trains on board_id0 + r * n_games + g, so training meets them
-        only after 2^62 / n_games rounds; every call with the default replays the same spawns (scores of two tables are paired)."""
-        return (self.board_id0 + (1 << 62)) & 0xFFFFFFFFFFFFFFFF
-
-    def evaluate_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False):
-        """The launch of evaluate() alone (pulse_tfe_mc_evaluate, with `afterstate` pulse_tfe_mc_evaluate_after): ADDS to the counters of `eval_counters` and reads nothing back.
-        Returns the per-game device tensors (total_score int64[B], lengths int32[B]) with per_game, else None."""
-        import torch
-        B = self.n_games if n_games is None else int(n_games)
+    # evaluate() (tfe_common.py): pulse_tfe_mc_evaluate, with `afterstate` pulse_tfe_mc_evaluate_after; a state without an entry still
+    # plays the uniform default, and `coverage` is the share of moves whose state had an entry
+    def _eval_struct(self):
         o = _native.TfeMCEval()
-        o.entries, o.capacity, o.n_games, o.n, o.max_steps, o.frac_bits = self.entries.data_ptr(), self.capacity, B, self.n, self.max_steps, self.frac_bits
-        o.epsilon, o.env_seed, o.agent_seed, o.tie_seed, o.round = float(epsilon), self.env_seed, self.agent_seed, self.tie_seed, self.round
-        o.board_id0 = self.eval_board_id0() if board_id0 is None else int(board_id0)
-        o.canonical = int(self.symmetric)
-        o.summary, o.max_tile_hist = self._eval.data_ptr(), self._eval[len(EVAL_SUMMARY):].data_ptr()
-        arrays = None
-        if per_game:
-            arrays = (torch.zeros(B, dtype=torch.int64, device=self.device), torch.zeros(B, dtype=torch.int32, device=self.device))
-            o.total_score, o.lengths = arrays[0].data_ptr(), arrays[1].data_ptr()
-        stream = _native.current_stream(self.device)
+        o.entries, o.capacity, o.n, o.frac_bits, o.canonical = self.entries.data_ptr(), self.capacity, self.n, self.frac_bits, int(self.symmetric)
+        return o
+
+    def _eval_launch(self, o):
         if self.afterstate:
-            _native.check(self._lib.pulse_tfe_mc_evaluate_after(C.byref(o), self.gamma, stream), "pulse_tfe_mc_evaluate_after")
+            self._launch("pulse_tfe_mc_evaluate_after", o, self.gamma)
         else:
-            _native.check(self._lib.pulse_tfe_mc_evaluate(C.byref(o), stream), "pulse_tfe_mc_evaluate")
-        return arrays
-
-    def eval_counters(self, clear=False) -> dict:
-        """What the evaluation launches since the last clear added up to (eval_summary_on_host; synchronises), or, with clear, nothing:
-        the counters are zeroed."""
-        if clear:
-            self._eval.zero_()
-            return {}
-        return eval_summary_on_host(self._eval.cpu().tolist())
-
-    def evaluate(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False) -> dict:
-        """One launch and one read-back: `n_games` games (default: the agent's) under the table as it stands and `epsilon` (default 0:
-        the greedy policy; a state without an entry still plays the uniform default), no trajectory.  With equal seeds, round, epsilon
-        and board_id0 they are the games rollout() plays.  Returns the counters by name, the histogram of the largest tile, mean /
-        standard deviation / maximum of the final score, the mean length, the games cut at max_steps and the share of moves whose
-        state had an entry; per_game adds the arrays total_score / lengths."""
-        self.eval_counters(clear=True)
-        arrays = self.evaluate_launch(n_games, epsilon, board_id0, per_game)
-        out = self.eval_counters()
-        if per_game:
-            out["total_score"], out["lengths"] = arrays[0].cpu().numpy(), arrays[1].cpu().numpy()
-        return out
-
-    def stats(self) -> dict:
-        return dict(zip(STATS, self.counters.cpu().tolist()[:4]))
+            self._launch("pulse_tfe_mc_evaluate", o)
 
     def trajectory(self):
         """(keys uint64[T, B], steps uint8[T, B], lengths int32[B]) of the last batch, T = the longest game; rows at and beyond a
         game's length hold whatever the buffers held before."""
-        lengths = self.lengths.cpu().numpy()
-        T = int(lengths.max()) if lengths.size else 0
+        T, lengths = self._played()
         return self.keys[:T].cpu().numpy().view(np.uint64), self.steps[:T].cpu().numpy(), lengths
 
     def episodes(self):

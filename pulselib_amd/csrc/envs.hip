@@ -17,6 +17,7 @@
 #include "blackjack_device.h"
 #include "poker_device.h"
 #include "pulse_internal.h"
+#include "tfe_agent_device.h"
 #include "tfe_device.h"
 
 namespace {
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(kBlock) void tfe_step4_kernel(int32_t* __restrict__
         *reinterpret_cast<uint2*>(mine + 4 * lane) = make_uint2(pb.lo, pb.hi);
         pulse_dev::wave_sync();
         total_score[g] = ts + score;                                                    // TFE.py:168
-        rewards[g] = score > 0 ? 31 - __clz(score) : 0;                                 // TFE.py:185-187
+        rewards[g] = tfe_reward(score);                                 // TFE.py:185-187
         dones[g] = over;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(kBlock) void tfe_step4_kernel(int32_t* __restrict__
     const int score = tfe_move<4>(b, (int)(actions[g] & 3));
     tfe_spawn<4>(b, rnd.x, rnd.y);
     total_score[g] += score;
-    rewards[g] = score > 0 ? 31 - __clz(score) : 0;
+    rewards[g] = tfe_reward(score);
     dones[g] = tfe_over<4>(b);
 #pragma unroll
     for (int q = 0; q < 4; ++q) p4[q] = make_int4(b[4 * q], b[4 * q + 1], b[4 * q + 2], b[4 * q + 3]);
@@ -233,7 +234,7 @@ __global__ __launch_bounds__(kBlock) void tfe_step_kernel(int32_t* __restrict__ 
         const int score = tfe_move<NB>(b, k);
         total_score[g] += score;                                                        // TFE.py:168
         tfe_spawn<NB>(b, rnd.x, rnd.y);                                                 // TFE.py:182 (always)
-        rewards[g] = score > 0 ? 31 - __clz(score) : 0;                                 // TFE.py:185-187
+        rewards[g] = tfe_reward(score);                                 // TFE.py:185-187
     }
     const bool over = tfe_over<NB>(b);                                                  // TFE.py:48-67
     if (!is_reset) dones[g] = over;
@@ -296,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void tfe_step_any_kernel(int32_t* __restric
         }
         total_score[g] += score;                                                        // TFE.py:168
         spawn(rnd.x, rnd.y);                                                            // TFE.py:182 (always)
-        rewards[g] = score > 0 ? 31 - __clz(score) : 0;                                 // TFE.py:185-187
+        rewards[g] = tfe_reward(score);                                 // TFE.py:185-187
         bool over = true;                                                               // TFE.py:48-67
         for (int i = 0; i < cells; ++i) over = over && x[i] != 0;
         for (int r = 0; r < n; ++r) for (int c = 0; c + 1 < n; ++c) over = over && x[r * n + c] != x[r * n + c + 1];

@@ -25,6 +25,7 @@
 
 #include "philox_device.h"
 #include "pulse_internal.h"
+#include "tfe_agent_device.h"
 #include "tfe_device.h"
 #include "tfe_table_device.h"
 
@@ -338,7 +339,7 @@ __global__ __launch_bounds__(kBlock) void qtable_rollout_step_kernel(Entry* tabl
         over = tfe_over<NB>(b);
         key_next = pack_cells(b, NB * NB);
     }
-    const int reward = score > 0 ? 31 - __clz(score) : 0;                                // TFE.py:185-187
+    const int reward = tfe_reward(score);                                // TFE.py:185-187
 #pragma unroll
     for (int i = 0; i < NB * NB; ++i) bp[i] = b[i];
     total_score[g] += score;

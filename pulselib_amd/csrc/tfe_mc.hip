@@ -31,6 +31,7 @@
 
 #include "philox_device.h"
 #include "pulse_internal.h"
+#include "tfe_agent_device.h"
 #include "tfe_device.h"
 #include "tfe_table_device.h"
 
@@ -49,8 +50,7 @@ constexpr uint64_t kMaxProbe = PULSE_TFE_MC_MAX_PROBE;
 struct alignas(128) Entry { unsigned long long key; long long cnt[4]; long long sum[4]; unsigned long long spare[7]; };
 static_assert(sizeof(Entry) == PULSE_TFE_MC_ENTRY_BYTES, "entry layout is part of the ABI");
 
-// The greedy action of an entry (OnPolicyFirstVisit.py:52-62): the actions in order, a larger q replaces the best, an equal q
-// replaces it on the coin of that action.  The coins are constant per (state, round); they are drawn only where two q are equal.
+// The greedy action of an entry (greedy_scan over its four q; the coins' key is the key of the entry).
 __device__ __forceinline__ int greedy_action(const Entry& e, uint64_t key, uint64_t tie_seed, uint64_t round, double inv_scale) {
     double q[4];
 #pragma unroll
@@ -58,28 +58,9 @@ __device__ __forceinline__ int greedy_action(const Entry& e, uint64_t key, uint6
         const long long n = e.cnt[a];
         q[a] = n > 0 ? __dmul_rn(__ddiv_rn((double)e.sum[a], (double)n), inv_scale) : 0.0;   // an unseen pair reads 0.0 (defaultdict(float))
     }
-    const bool any_tie = q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3];
     U4 coins{0u, 0u, 0u, 0u};
-    if (any_tie) coins = philox4x32(tie_seed, key, round);
-    const uint32_t coin[3] = {coins.x >> 31, coins.y >> 31, coins.z >> 31};
-    int best = 0;
-    double best_q = q[0];
-#pragma unroll
-    for (int a = 1; a < 4; ++a) {
-        const bool take = q[a] > best_q || (q[a] == best_q && coin[a - 1] != 0u);
-        best = take ? a : best;
-        best_q = q[a] > best_q ? q[a] : best_q;
-    }
-    return best;
-}
-
-// Per-workgroup counters, added to the caller's stats once per workgroup.  Called by every thread of the workgroup.
-__device__ __forceinline__ void add_stats(unsigned long long* wg, int64_t* stats, int at0, unsigned long long v0, int at1, unsigned long long v1) {
-    if (v0) atomicAdd(&wg[0], v0);                        // LDS
-    if (v1) atomicAdd(&wg[1], v1);
-    __syncthreads();
-    if (threadIdx.x == 0 && wg[0]) atomicAdd(reinterpret_cast<unsigned long long*>(stats) + at0, wg[0]);
-    if (threadIdx.x == 1 && wg[1]) atomicAdd(reinterpret_cast<unsigned long long*>(stats) + at1, wg[1]);
+    if (any_two_equal(q)) coins = philox4x32(tie_seed, key, round);
+    return greedy_scan(q, coins);
 }
 
 // The eight symmetries of the square, T_0 .. T_7: T_j rotates the board j & 3 times by the move's own rotation (rot_src), for
@@ -166,7 +147,7 @@ __device__ __forceinline__ int afterstate_action(const int (&b)[NB * NB], const 
 #pragma unroll
         for (int x = 0; x < NB * NB; ++x) c[x] = b[x];
         const int sc = tfe_move<NB>(c, i);
-        const int rw = sc > 0 ? 31 - __clz(sc) : 0;
+        const int rw = tfe_reward(sc);
         int jc = 0;
         uint64_t k;
         if constexpr (Canon) k = canon_key<NB>(c, jc); else k = pack_cells<NB * NB>(c);
@@ -192,34 +173,14 @@ __device__ __forceinline__ int afterstate_action(const int (&b)[NB * NB], const 
     greedy = any && (r.x >> 8) >= eps_q24;
     int a = (int)(r.y >> 30);                             // no entry among the four, or the epsilon branch
     if (greedy) {
-        const bool any_tie = q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3];
         U4 coins{0u, 0u, 0u, 0u};
-        if (any_tie) coins = philox4x32(o.tie_seed, pack_cells<NB * NB>(b), o.round);      // the plain key of the state, in both forms
-        const uint32_t coin[3] = {coins.x >> 31, coins.y >> 31, coins.z >> 31};
-        a = 0;
-        double best_q = q[0];
-#pragma unroll
-        for (int i = 1; i < 4; ++i) {
-            const bool take = q[i] > best_q || (q[i] == best_q && coin[i - 1] != 0u);
-            a = take ? i : a;
-            best_q = q[i] > best_q ? q[i] : best_q;
-        }
+        if (any_two_equal(q)) coins = philox4x32(o.tie_seed, pack_cells<NB * NB>(b), o.round);     // the plain key of the state, in both forms
+        a = greedy_scan(q, coins);
     }
     key = ka[0];
 #pragma unroll
     for (int i = 1; i < 4; ++i) key = a == i ? ka[i] : key;
     return a;
-}
-
-// pulse_tfe_mc_evaluate's counters: summary[8] then max_tile_hist[16], reduced in LDS and added once per workgroup and non-zero bin.
-constexpr int kEvalSummary = 8, kEvalBins = kEvalSummary + 16, kEvalMax = 4;
-__device__ __forceinline__ void flush_bins(unsigned long long* wg, int64_t* summary, int64_t* hist) {
-    __syncthreads();
-    const int i = (int)threadIdx.x;
-    if (i < kEvalBins && wg[i]) {
-        unsigned long long* dst = reinterpret_cast<unsigned long long*>(i < kEvalSummary ? summary + i : hist + (i - kEvalSummary));
-        if (i == kEvalMax) atomicMax(dst, wg[i]); else atomicAdd(dst, wg[i]);          // (scores are not negative)
-    }
 }
 
 // The game loop.  <NB, false, true, false> is pulse_tfe_mc_rollout; Canon plays in the canonical frame; without Record nothing is
@@ -237,13 +198,7 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMC
         const Entry* table = static_cast<const Entry*>(o.entries);
         const uint64_t id = o.board_id0 + (uint64_t)g;
         int b[NB * NB];
-#pragma unroll
-        for (int i = 0; i < NB * NB; ++i) b[i] = 0;
-        {                                                                               // TFE.py:143-149, as pulse_tfe_reset
-            const U4 rnd = philox4x32(o.env_seed, id, 0ull);
-            tfe_spawn<NB>(b, rnd.x, rnd.y);
-            tfe_spawn<NB>(b, rnd.z, rnd.w);
-        }
+        tfe_reset<NB>(b, o.env_seed, id);
         int64_t total = 0;
         int ep_reward = 0, length = 0;
         uint32_t taken = 0u;                              // bit a: action a was taken in the current run of identical boards
@@ -281,10 +236,10 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMC
             const U4 rnd = philox4x32(o.env_seed, id, (uint64_t)t + 1ull);
             tfe_spawn<NB>(b, rnd.x, rnd.y);                                            // TFE.py:182 (always)
             over = tfe_over<NB>(b);                                                    // TFE.py:48-67
-            const int reward = score > 0 ? 31 - __clz(score) : 0;                      // TFE.py:185-187 (<= 17 for n <= 4: five bits)
+            const int reward = tfe_reward(score);
             if constexpr (Record) {
                 o.keys[(size_t)t * B + (size_t)g] = key;
-                o.steps[(size_t)t * B + (size_t)g] = (uint8_t)((uint32_t)a | ((uint32_t)reward & 31u) << 2 | first << 7);
+                o.steps[(size_t)t * B + (size_t)g] = tfe_step_byte(a, reward, first);
             }
             total += score; ep_reward += reward;
             length = t + 1;
@@ -302,11 +257,7 @@ __global__ __launch_bounds__(kBlock) void tfe_mc_rollout_kernel(const PulseTfeMC
 #pragma unroll
             for (int i = 0; i < NB * NB; ++i) top = max(top, b[i]);
             const unsigned long long sc = (unsigned long long)total;
-            const unsigned long long v[kEvalSummary] = {1ull, n_moves, sc, sc * sc, sc, n_cut, n_present, n_greedy};
-#pragma unroll
-            for (int i = 0; i < kEvalSummary; ++i)
-                if (v[i]) { if (i == kEvalMax) atomicMax(&wg[i], v[i]); else atomicAdd(&wg[i], v[i]); }       // LDS
-            atomicAdd(&wg[kEvalSummary + min(31 - __clz(top | 1), 15)], 1ull);
+            add_game(wg, {1ull, n_moves, sc, sc * sc, sc, n_cut, n_present, n_greedy}, min(31 - __clz(top | 1), 15));
         }
     }
     if constexpr (Record) add_stats(wg, o.stats, 0, n_moves, 3, n_cut);

@@ -14,6 +14,7 @@
 
 #include "philox_device.h"
 #include "pulse_internal.h"
+#include "tfe_agent_device.h"
 #include "tfe_device.h"
 
 namespace {
@@ -91,9 +92,6 @@ struct Games {
     const uint32_t* lut;
 };
 
-// the evaluation's counters: summary[8] then max_tile_hist[16], reduced in LDS and added once per workgroup and non-zero bin
-constexpr int kEvalSummary = 8, kEvalBins = kEvalSummary + 16, kEvalMax = 4;
-
 // IMG = 8 (symmetric) or 1.  Record: pulse_tfe_nt_rollout; otherwise pulse_tfe_nt_evaluate.
 template <int IMG, bool Record>
 __global__ __launch_bounds__(kBlock) void tfe_nt_games_kernel(const Games o, const NtDev net) {
@@ -102,14 +100,10 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_games_kernel(const Games o, con
     __syncthreads();
     const int g = blockIdx.x * kBlock + threadIdx.x;
     const size_t B = (size_t)o.n_games;
+    unsigned long long n_moves = 0ull, n_cut = 0ull;
     if (g < o.n_games) {
         const uint64_t id = o.board_id0 + (uint64_t)g;
-        PackedBoard p{0u, 0u};
-        {                                                                               // TFE.py:143-149, as pulse_tfe_reset
-            const U4 rnd = philox4x32(o.env_seed, id, 0ull);
-            tfe_spawn_packed(p, rnd.x, rnd.y);
-            tfe_spawn_packed(p, rnd.z, rnd.w);
-        }
+        PackedBoard p = tfe_reset_packed(o.env_seed, id);
         int64_t total = 0;
         int ep_reward = 0, length = 0;
         bool over = false, capped = false;
@@ -128,23 +122,14 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_games_kernel(const Games o, con
             double v[4], q[4];
             values4<IMG>(net, o.weights, ka, v);
 #pragma unroll
-            for (int a = 0; a < 4; ++a) q[a] = __dadd_rn((double)(sc[a] > 0 ? 31 - __clz(sc[a]) : 0), __dmul_rn(o.gamma, v[a]));
+            for (int a = 0; a < 4; ++a) q[a] = __dadd_rn((double)tfe_reward(sc[a]), __dmul_rn(o.gamma, v[a]));
             const bool greedy = (r.x >> 8) >= o.eps_q24;
             int act = (int)(r.y >> 30);
             if (greedy) {
-                const bool any_tie = q[0] == q[1] || q[0] == q[2] || q[0] == q[3] || q[1] == q[2] || q[1] == q[3] || q[2] == q[3];
                 U4 coins{0u, 0u, 0u, 0u};
-                if (any_tie) coins = philox4x32(o.tie_seed, key_b, o.round);
-                const uint32_t coin[4] = {0u, coins.x >> 31, coins.y >> 31, coins.z >> 31};
-                int best = -1;
-                double best_q = 0.0;
-#pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const bool cand = ka[a] != key_b;
-                    const bool take = cand && (best < 0 || q[a] > best_q || (q[a] == best_q && coin[a] != 0u));
-                    best_q = take ? q[a] : best_q;
-                    best = take ? a : best;
-                }
+                if (any_two_equal(q)) coins = philox4x32(o.tie_seed, key_b, o.round);
+                const bool cand[4] = {ka[0] != key_b, ka[1] != key_b, ka[2] != key_b, ka[3] != key_b};        // the moves that change the board
+                const int best = greedy_scan<false>(q, coins, cand);
                 act = best < 0 ? act : best;                                            // (a live board has a candidate)
                 n_greedy += 1ull;
             }
@@ -158,23 +143,22 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_games_kernel(const Games o, con
             const int empty_before = tfe_spawn_packed(p, rnd.x, rnd.y);                // TFE.py:182 (always)
             over = tfe_over_packed(p, empty_before);                                   // TFE.py:48-67
             capped = has_nibble15(p);
-            const int reward = score > 0 ? 31 - __clz(score) : 0;                      // TFE.py:185-187 (<= 16: five bits)
+            const int reward = tfe_reward(score);
             if constexpr (Record) {
                 const size_t at = (size_t)t * B + (size_t)g;
                 o.keys[at] = key;
                 o.values[at] = val;
-                o.steps[at] = (uint8_t)((uint32_t)act | ((uint32_t)reward & 31u) << 2 | (over ? 0x80u : 0u));
+                o.steps[at] = tfe_step_byte(act, reward, over ? 1u : 0u);
             }
             total += score; ep_reward += reward;
             length = t + 1;
         }
-        const unsigned long long n_moves = (unsigned long long)length, n_cut = over ? 0ull : 1ull;
+        n_moves = (unsigned long long)length;
+        n_cut = over ? 0ull : 1ull;
         if constexpr (Record) {
             o.lengths[g] = length;
             o.total_score[g] = total;
             o.episode_reward[g] = ep_reward;
-            atomicAdd(&wg[0], n_moves);                                                 // LDS
-            if (n_cut) atomicAdd(&wg[1], n_cut);
         } else {
             if (o.lengths) o.lengths[g] = length;
             if (o.total_score) o.total_score[g] = total;
@@ -182,23 +166,11 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_games_kernel(const Games o, con
 #pragma unroll
             for (int i = 0; i < 8; ++i) top = max(top, max((p.lo >> (4 * i)) & 15u, (p.hi >> (4 * i)) & 15u));
             const unsigned long long s = (unsigned long long)total;
-            const unsigned long long x[kEvalSummary] = {1ull, n_moves, s, s * s, s, n_cut, n_greedy, capped ? 1ull : 0ull};
-#pragma unroll
-            for (int i = 0; i < kEvalSummary; ++i)
-                if (x[i]) { if (i == kEvalMax) atomicMax(&wg[i], x[i]); else atomicAdd(&wg[i], x[i]); }       // LDS
-            atomicAdd(&wg[kEvalSummary + top], 1ull);
+            add_game(wg, {1ull, n_moves, s, s * s, s, n_cut, n_greedy, capped ? 1ull : 0ull}, (int)top);
         }
     }
-    __syncthreads();
-    const int i = (int)threadIdx.x;
-    if constexpr (Record) {
-        if (i < 2 && wg[i]) atomicAdd(reinterpret_cast<unsigned long long*>(o.stats) + (i == 0 ? 0 : 3), wg[i]);
-    } else {
-        if (i < kEvalBins && wg[i]) {
-            unsigned long long* dst = reinterpret_cast<unsigned long long*>(i < kEvalSummary ? o.stats + i : o.hist + (i - kEvalSummary));
-            if (i == kEvalMax) atomicMax(dst, wg[i]); else atomicAdd(dst, wg[i]);       // (scores are not negative)
-        }
-    }
+    if constexpr (Record) add_stats(wg, o.stats, 0, n_moves, 3, n_cut);
+    else flush_bins(wg, o.stats, o.hist);
 }
 
 // One lane per recorded move: blockIdx.y = t, blockIdx.x * kBlock + threadIdx.x = g.
