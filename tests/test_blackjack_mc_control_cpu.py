@@ -11,6 +11,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from tests.native_args import assert_refusals, opts
+
 ROOT = Path(__file__).resolve().parent.parent
 GOLDEN = np.load(ROOT / "tests" / "golden" / "opfvmc.npz")
 
@@ -132,54 +134,35 @@ def test_improve_on_host(epsilon):
         assert hit_p == stand_p == np.float32(0.5)
 
 
-def _opts(struct, **kw):
-    o = struct()                                                           # (zero-initialised)
-    for k, v in kw.items():
-        setattr(o, k, v)
-    return o
-
-
 def test_control_rollout_argument_checks_without_gpu():
     from pulselib_amd import _native
     lib = _native.lib()
-    fn = lib.pulse_blackjack_mc_control_rollout
     base = dict(n_games=64, n_episodes=1, hit_prob=0x10000, acc=0x20000, stats=0x30000)   # never dereferenced: every case fails its check first
-    assert fn(None, None) == -1 and lib.pulse_last_error() == b"pulse_blackjack_mc_control_rollout: options are null"
-    for kw, msg in [(dict(acc=None), b"acc is null"), (dict(hit_prob=None), b"hit_prob is null"), (dict(stats=None), b"stats is null"),
-                    (dict(n_games=0), b"n_games must be positive"), (dict(n_games=-5), b"n_games must be positive"),
-                    (dict(n_episodes=0), b"n_episodes must be positive"), (dict(n_episodes=-1), b"n_episodes must be positive"),
-                    (dict(n_games=1 << 20, n_episodes=1 << 12), b"below 2^32"),
-                    (dict(acc=0x20004), b"8-byte aligned"), (dict(stats=0x30004), b"8-byte aligned"),
-                    (dict(hit_prob=0x10002), b"4-byte aligned"), (dict(decks_src=0x40001), b"4-byte aligned"),
-                    (dict(trace=0x50008), b"16-byte aligned"), (dict(max_blocks=-1), b"max_blocks"),
-                    (dict(reserved0=1), b"reserved0 must be 0")]:
-        o = _opts(_native.BlackjackMCControl, **{**base, **kw})
-        assert fn(C.byref(o), None) == -1, kw
-        err = lib.pulse_last_error()
-        assert err.startswith(b"pulse_blackjack_mc_control_rollout: ") and msg in err, (kw, err)
-        v = _opts(_native.BlackjackMC, **{**base, **kw})                   # the value entry point: the same message under its own name
-        assert lib.pulse_blackjack_mc_rollout(C.byref(v), None) == -1
-        assert lib.pulse_last_error() == err.replace(b"pulse_blackjack_mc_control_rollout", b"pulse_blackjack_mc_rollout")
-    with pytest.raises(ValueError, match="acc is null"):
-        _native.check(fn(C.byref(_opts(_native.BlackjackMCControl, **{**base, "acc": None})), None), "pulse_blackjack_mc_control_rollout")
+    cases = [(dict(acc=None), b"acc is null"), (dict(hit_prob=None), b"hit_prob is null"), (dict(stats=None), b"stats is null"),
+             (dict(n_games=0), b"n_games must be positive"), (dict(n_games=-5), b"n_games must be positive"),
+             (dict(n_episodes=0), b"n_episodes must be positive"), (dict(n_episodes=-1), b"n_episodes must be positive"),
+             (dict(n_games=1 << 20, n_episodes=1 << 12), b"below 2^32"),
+             (dict(acc=0x20004), b"8-byte aligned"), (dict(stats=0x30004), b"8-byte aligned"),
+             (dict(hit_prob=0x10002), b"4-byte aligned"), (dict(decks_src=0x40001), b"4-byte aligned"),
+             (dict(trace=0x50008), b"16-byte aligned"), (dict(max_blocks=-1), b"max_blocks"),
+             (dict(reserved0=1), b"reserved0 must be 0")]
+    control = assert_refusals(lib, "pulse_blackjack_mc_control_rollout", lambda **kw: opts(_native.BlackjackMCControl, **{**base, **kw}), cases)
+    value = assert_refusals(lib, "pulse_blackjack_mc_rollout", lambda **kw: opts(_native.BlackjackMC, **{**base, **kw}), cases)
+    # the value entry point: the same message under its own name
+    assert value == [err.replace(b"pulse_blackjack_mc_control_rollout", b"pulse_blackjack_mc_rollout") for err in control]
 
 
 def test_improve_argument_checks_without_gpu():
     from pulselib_amd import _native
     lib = _native.lib()
-    fn = lib.pulse_blackjack_mc_improve
     base = dict(acc=0x20000, hit_prob=0x10000, q=0x30000, gamma=0.9, epsilon=0.1)
-    assert fn(None, None) == -1 and lib.pulse_last_error() == b"pulse_blackjack_mc_improve: options are null"
-    for kw, msg in [(dict(acc=None), b"acc is null"), (dict(hit_prob=None), b"hit_prob is null"),
-                    (dict(acc=0x20004), b"8-byte aligned"), (dict(q=0x30004), b"8-byte aligned"), (dict(hit_prob=0x10002), b"4-byte aligned"),
-                    (dict(epsilon=-0.01), b"epsilon must be in [0, 1]"), (dict(epsilon=1.5), b"epsilon must be in [0, 1]"),
-                    (dict(epsilon=math.nan), b"epsilon must be in [0, 1]"),
-                    (dict(gamma=math.inf), b"gamma must be finite"), (dict(gamma=math.nan), b"gamma must be finite"),
-                    (dict(reserved0=1), b"reserved0 / reserved1 must be 0"), (dict(reserved1=-1), b"reserved0 / reserved1 must be 0")]:
-        o = _opts(_native.BlackjackMCImprove, **{**base, **kw})
-        assert fn(C.byref(o), None) == -1, kw
-        err = lib.pulse_last_error()
-        assert err.startswith(b"pulse_blackjack_mc_improve: ") and msg in err, (kw, err)
+    cases = [(dict(acc=None), b"acc is null"), (dict(hit_prob=None), b"hit_prob is null"),
+             (dict(acc=0x20004), b"8-byte aligned"), (dict(q=0x30004), b"8-byte aligned"), (dict(hit_prob=0x10002), b"4-byte aligned"),
+             (dict(epsilon=-0.01), b"epsilon must be in [0, 1]"), (dict(epsilon=1.5), b"epsilon must be in [0, 1]"),
+             (dict(epsilon=math.nan), b"epsilon must be in [0, 1]"),
+             (dict(gamma=math.inf), b"gamma must be finite"), (dict(gamma=math.nan), b"gamma must be finite"),
+             (dict(reserved0=1), b"reserved0 / reserved1 must be 0"), (dict(reserved1=-1), b"reserved0 / reserved1 must be 0")]
+    assert_refusals(lib, "pulse_blackjack_mc_improve", lambda **kw: opts(_native.BlackjackMCImprove, **{**base, **kw}), cases)
 
 
 def test_header_macros_agree_with_the_binding():

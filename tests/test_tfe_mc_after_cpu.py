@@ -13,7 +13,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from tests.test_tfe_mc_cpu import BASE, COMMON, ROLLOUT_ONLY, _opts
+from tests.native_args import assert_refusals, opts
+from tests.test_tfe_mc_cpu import BASE, COMMON, ROLLOUT_ONLY
 from tests.test_tfe_mc_sym_cpu import BASE as EVAL_BASE, EVAL, TABLE
 from tests.test_tfe_mc_table_cpu import BASE as MERGE_BASE, CASES as MERGE_CASES
 
@@ -54,7 +55,7 @@ def test_move_on_host_against_the_oracles_step(n, n_games):
 def _host_games(n, n_games, canonical=False, rounds=2):
     """Host-played games: round 0 on an empty table, round 1 on the table learnt from it.  Per round (roll-out, table after it)."""
     from pulselib_amd.agents import tfe_on_policy_mc_gpu as mc
-    from tests.tfe_mc_after_host import rollout_after_on_host
+    from tests.tfe_host import rollout_after_on_host
     seed, fb, table, out = 11 + n, mc.frac_bits_for(0.9, 256), {}, []
     for r in range(rounds):
         o = rollout_after_on_host(n_games, n, 256, 0.1, 0.9, fb, table, seed, seed ^ mc.AGENT_KEY, seed ^ mc.TIE_KEY, 100 + r * n_games, r, canonical)
@@ -165,33 +166,15 @@ def test_argument_checks_without_gpu():
     for name, struct, cases in (("pulse_tfe_mc_rollout_after", _native.TfeMCRollout, COMMON + ROLLOUT_ONLY),
                                 ("pulse_tfe_mc_rollout_after_canon", _native.TfeMCRollout, COMMON + ROLLOUT_ONLY),
                                 ("pulse_tfe_mc_learn_after", _native.TfeMCLearn, COMMON)):
-        fn = getattr(lib, name)
-        assert fn(None, None) == -1 and lib.pulse_last_error() == name.encode() + b": options are null"
-        for kw, msg in cases:
-            o = _opts(struct, **{**BASE, **kw})
-            assert fn(C.byref(o), None) == -1, (name, kw)
-            err = lib.pulse_last_error()
-            assert err.startswith(name.encode() + b": ") and msg in err, (name, kw, err)
-    name = b"pulse_tfe_mc_evaluate_after"
-    assert lib.pulse_tfe_mc_evaluate_after(None, 0.9, None) == -1 and lib.pulse_last_error() == name + b": options are null"
-    for kw, msg in TABLE + EVAL:
-        assert lib.pulse_tfe_mc_evaluate_after(C.byref(_opts(_native.TfeMCEval, **{**EVAL_BASE, **kw})), 0.9, None) == -1, kw
-        err = lib.pulse_last_error()
-        assert err.startswith(name + b": ") and msg in err, (kw, err)
+        assert_refusals(lib, name, lambda **kw: opts(struct, **{**BASE, **kw}), cases)
+    assert_refusals(lib, "pulse_tfe_mc_evaluate_after", lambda **kw: opts(_native.TfeMCEval, **{**EVAL_BASE, **kw}), TABLE + EVAL, 0.9)
     for gamma in (-0.01, 1.01, math.nan):
-        assert lib.pulse_tfe_mc_evaluate_after(C.byref(_opts(_native.TfeMCEval, **EVAL_BASE)), gamma, None) == -1
-        assert lib.pulse_last_error() == name + b": gamma must be in [0, 1]"
-    name = b"pulse_tfe_mc_table_fold_after"
-    assert lib.pulse_tfe_mc_table_fold_after(None, None) == -1 and lib.pulse_last_error() == name + b": options are null"
-    for kw, msg in MERGE_CASES:
-        o = _opts(_native.TfeMCMerge, **{**MERGE_BASE, "canonical": 1, **kw})
-        assert lib.pulse_tfe_mc_table_fold_after(C.byref(o), None) == -1, kw
-        err = lib.pulse_last_error()
-        assert err.startswith(name + b": ") and msg in err, (kw, err)
-    assert lib.pulse_tfe_mc_table_fold_after(C.byref(_opts(_native.TfeMCMerge, **{**MERGE_BASE, "canonical": 0})), None) == -1
-    assert lib.pulse_last_error() == name + b": canonical must be 1 (the plain merge of a value table is pulse_tfe_mc_table_merge)"
-    with pytest.raises(ValueError, match="entries is null"):
-        _native.check(lib.pulse_tfe_mc_learn_after(C.byref(_opts(_native.TfeMCLearn, **{**BASE, "entries": None})), None), "pulse_tfe_mc_learn_after")
+        assert lib.pulse_tfe_mc_evaluate_after(C.byref(opts(_native.TfeMCEval, **EVAL_BASE)), gamma, None) == -1
+        assert lib.pulse_last_error() == b"pulse_tfe_mc_evaluate_after: gamma must be in [0, 1]"
+    name = "pulse_tfe_mc_table_fold_after"
+    assert_refusals(lib, name, lambda **kw: opts(_native.TfeMCMerge, **{**MERGE_BASE, "canonical": 1, **kw}), MERGE_CASES)
+    assert lib.pulse_tfe_mc_table_fold_after(C.byref(opts(_native.TfeMCMerge, **{**MERGE_BASE, "canonical": 0})), None) == -1
+    assert lib.pulse_last_error() == name.encode() + b": canonical must be 1 (the plain merge of a value table is pulse_tfe_mc_table_merge)"
 
 
 def test_header_agrees_with_the_binding():

@@ -1,6 +1,6 @@
 """2048 Monte-Carlo control on afterstates on the device (csrc/tfe_mc.hip: pulse_tfe_mc_rollout_after,
 _after_canon, pulse_tfe_mc_learn_after, pulse_tfe_mc_evaluate_after, pulse_tfe_mc_table_fold_after) against the host's statement of
-it (tests/tfe_mc_after_host.py: the oracle's environment and Philox under greedy_after_on_host; learn_after_on_host,
+it (tests/tfe_host.py: the oracle's environment and Philox under greedy_after_on_host; learn_after_on_host,
 fold_values_on_host) and the environment's own kernels.  Every comparison is exact.  Every buffer a launch is handed sits between
 guard words, and the rows of keys / steps at and beyond a game's length must keep what they held.
 
@@ -14,15 +14,16 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_tfe_mc_gpu import _agent, _assert_rollout, _guards_intact, _rollout
+from tests.tfe_gpu_support import PATTERNS, assert_rollout, guard, guards_intact, replay, rollout
 
 pytestmark = pytest.mark.gpu
 
 GAMES, MAX_STEPS, ROOMY, TIGHT, ROUNDS = 257, 128, 1 << 14, 1 << 8, 3
+BUFFERS = ("entries", "keys", "steps", "lengths", "total_score", "episode_reward", "counters")
 
 
 def _host_rollout(a, table, **kw):
-    from tests.tfe_mc_after_host import rollout_after_on_host
+    from tests.tfe_host import rollout_after_on_host
     return rollout_after_on_host(a.n_games, a.n, a.max_steps, a.epsilon, a.gamma, a.frac_bits, table, a.env_seed, a.agent_seed, a.tie_seed,
                                  a.round_board_id0(), a.round, canonical=a.symmetric, **kw)
 
@@ -30,20 +31,24 @@ def _host_rollout(a, table, **kw):
 @functools.lru_cache(maxsize=None)
 def _rounds(n, symmetric=False, capacity=ROOMY):
     """Three rounds on the device and on the host, once per shape: (the agent after them, per round a record)."""
+    import torch
+    from pulselib_amd.agents import OnPolicyFirstVisitMCTFEGPU
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import learn_after_on_host
-    a = _agent(GAMES, n, afterstate=True, symmetric=symmetric, capacity=capacity, max_steps=MAX_STEPS, seed=100 * n + 57, board_id0=7)
+    a = guard(OnPolicyFirstVisitMCTFEGPU(torch.device("cuda:0"), GAMES, board_size=n, afterstate=True, symmetric=symmetric, capacity=capacity,
+                                         max_steps=MAX_STEPS, seed=100 * n + 57, board_id0=7), BUFFERS, **PATTERNS)
+    assert a.entries.data_ptr() % 128 == 0
     host, out, flags = {}, [], 0
     for _ in range(ROUNDS):
         policy = a.table()
-        want = _host_rollout(a, policy, keep_boards=True)
-        got = _rollout(a)
+        want = _host_rollout(a, policy, keep_boards="before")
+        got = rollout(a)
         a.learn()
         learn_after_on_host(want["keys"], want["steps"], want["lengths"], a.gamma, a.frac_bits, host)
         flags += int((want["steps"] >> 7).sum())
         out.append(dict(got=got, want=want, policy=policy, table=a.table(), host={k: (list(c), list(s)) for k, (c, s) in host.items()},
                         stats=a.stats(), flags=flags, board_id0=a.round_board_id0()))
         a.round += 1
-    _guards_intact(a)
+    guards_intact(a)
     return a, out
 
 
@@ -54,7 +59,7 @@ def test_rollout_after_equals_the_host_word_for_word(n, symmetric):
     _, rounds = _rounds(n, symmetric)
     moves = 0
     for r, rec in enumerate(rounds):
-        _assert_rollout(rec["got"], rec["want"], (n, symmetric, r))
+        assert_rollout(rec["got"], rec["want"], (n, symmetric, r))
         moves += int(rec["want"]["lengths"].sum())
         assert rec["stats"]["steps"] == moves
     assert rounds[0]["want"]["present"] == 0 and rounds[0]["policy"] == {}
@@ -68,28 +73,17 @@ def test_rollout_after_equals_the_host_word_for_word(n, symmetric):
 def test_recorded_actions_replay_through_the_environment(symmetric):
     """TFEBatch (pulse_tfe_reset / pulse_tfe_step) with the same seed and board ids, stepped by the recorded actions, meets the boards
     whose move_on_host images pack to the recorded keys (to their canonical keys with `symmetric`), with the recorded rewards."""
-    import torch
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import afterstates_on_host, unpack_steps
-    from pulselib_amd.environments.TFE.TFE import TFEBatch
     a, rounds = _rounds(3, symmetric)
-    rec = rounds[2]
-    got, L = rec["got"], rec["got"]["lengths"]
-    actions, rewards, _ = unpack_steps(got["steps"])
-    env = TFEBatch(a.device, GAMES, 3, seed=a.env_seed, board_id0=rec["board_id0"])
-    boards, _ = env.reset()
-    final = np.zeros(GAMES, dtype=np.int64)
-    for t in range(int(L.max())):
-        live, now = L > t, boards.cpu().numpy()
+    got = rounds[2]["got"]
+    rewards = unpack_steps(got["steps"])[1]
+
+    def recorded_afterstate(t, live, boards, actions):
         for g in np.nonzero(live)[0].tolist():
-            keys, rs = afterstates_on_host(now[g], symmetric)
-            assert keys[actions[t, g]] == int(got["keys"][t, g]) and rs[actions[t, g]] == int(rewards[t, g]), (t, g)
-        act = np.where(live, actions[t], 0).astype(np.int64)
-        boards, rew, dones, _, info = env.step(torch.from_numpy(act).to(a.device))
-        assert np.array_equal(rew.cpu().numpy()[live], rewards[t][live].astype(np.int32)), t
-        ends = L == t + 1
-        assert not dones.cpu().numpy()[live & ~ends].any(), t
-        final[ends] = info["score"].cpu().numpy()[ends]
-    assert np.array_equal(final, got["total_score"])
+            keys, rs = afterstates_on_host(boards[g], symmetric)
+            assert keys[actions[g]] == int(got["keys"][t, g]) and rs[actions[g]] == int(rewards[t, g]), (t, g)
+        return actions
+    replay(a, got, recorded_afterstate, rounds[2]["board_id0"])
 
 
 @pytest.mark.parametrize("n,symmetric,capacity", [(3, False, ROOMY), (3, True, ROOMY), (2, False, ROOMY), (4, False, ROOMY), (3, False, TIGHT),
@@ -100,7 +94,7 @@ def test_learn_after_equals_the_host_as_a_map(n, symmetric, capacity):
     2^14 slots n = 2 stores 331 afterstates in three rounds and n = 3 canonical 10,180, n = 3 plain 11,816 in two (15,995 in three: a
     load of .98, where a probe may run past its limit), so those rounds must drop nothing; n = 4 meets 25,507 in round 0 alone, and
     2^8 slots fill in round 0."""
-    from tests.tfe_mc_after_host import values_of
+    from tests.tfe_host import values_of
     _, rounds = _rounds(n, symmetric, capacity)
     for r, rec in enumerate(rounds):
         table, host, st = rec["table"], rec["host"], rec["stats"]
@@ -121,18 +115,18 @@ def _evaluation(symmetric):
     """round 3 of the shape's agent, rolled out and evaluated with equal seeds, round, epsilon and table; and the host's mirror of it"""
     a, _ = _rounds(3, symmetric)
     want = _host_rollout(a, a.table())
-    got = _rollout(a)
+    got = rollout(a)
     ev = a.evaluate(epsilon=a.epsilon, board_id0=a.round_board_id0(), per_game=True)
-    _guards_intact(a)
+    guards_intact(a)
     return a, got, want, ev
 
 
 @pytest.mark.parametrize("symmetric", [False, True], ids=["plain", "canonical"])
 def test_evaluate_after_plays_the_rollouts_games(symmetric):
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import EVAL_BINS, EVAL_SUMMARY
-    from tests.tfe_mc_sym_host import eval_words
+    from tests.tfe_host import eval_words
     a, got, want, ev = _evaluation(symmetric)
-    _assert_rollout(got, want, symmetric)
+    assert_rollout(got, want, symmetric)
     assert np.array_equal(ev["total_score"], got["total_score"]) and np.array_equal(ev["lengths"], got["lengths"])
     words = eval_words(want["total_score"], want["lengths"], want["final_boards"], want["truncated"], want["present"], want["greedy"])
     assert [ev[k] for k in EVAL_SUMMARY] + ev["max_tile_hist"] == words and len(words) == len(EVAL_SUMMARY) + EVAL_BINS

@@ -11,13 +11,15 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from tests.native_args import assert_refusals, opts
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
 def _uniform_games(n, n_games, seed):
     """oracle-played games under the uniform policy (an empty table), per game (keys, actions, rewards, flags)"""
     from pulselib_amd.agents import tfe_on_policy_mc_gpu as mc
-    from tests.tfe_mc_host import rollout_on_host
+    from tests.tfe_host import rollout_on_host
     o = rollout_on_host(n_games, n, 256, 0.1, {}, seed, seed ^ mc.AGENT_KEY, seed ^ mc.TIE_KEY, 100, 0)
     assert o["truncated"] == 0
     a, r, f = mc.unpack_steps(o["steps"])
@@ -113,18 +115,10 @@ def test_frac_bits_rule(gamma, max_steps, want):
     assert g_max * 2.0 ** want * 2.0 ** 32 < 2.0 ** 62 <= g_max * 2.0 ** (want + 1) * 2.0 ** 32
     lib = _native.lib()
     for fn, struct in ((lib.pulse_tfe_mc_rollout, _native.TfeMCRollout), (lib.pulse_tfe_mc_learn, _native.TfeMCLearn)):
-        o = _opts(struct, **{**BASE, "gamma": gamma, "max_steps": max_steps, "frac_bits": want + 1})
+        o = opts(struct, **{**BASE, "gamma": gamma, "max_steps": max_steps, "frac_bits": want + 1})
         assert fn(C.byref(o), None) == -1 and b"frac_bits" in lib.pulse_last_error()
-        o = _opts(struct, **{**BASE, "gamma": gamma, "max_steps": max_steps, "frac_bits": want, "keys": None})
+        o = opts(struct, **{**BASE, "gamma": gamma, "max_steps": max_steps, "frac_bits": want, "keys": None})
         assert fn(C.byref(o), None) == -1 and b"keys is null" in lib.pulse_last_error()      # past the frac_bits check
-
-
-def _opts(struct, **kw):
-    o = struct()                                                           # (zero-initialised)
-    for k, v in kw.items():
-        if hasattr(o, k):
-            setattr(o, k, v)
-    return o
 
 
 # never dereferenced: every case fails its check first
@@ -151,15 +145,7 @@ def test_argument_checks_without_gpu():
     from pulselib_amd import _native
     lib = _native.lib()
     for name, struct, cases in (("pulse_tfe_mc_rollout", _native.TfeMCRollout, COMMON + ROLLOUT_ONLY), ("pulse_tfe_mc_learn", _native.TfeMCLearn, COMMON)):
-        fn = getattr(lib, name)
-        assert fn(None, None) == -1 and lib.pulse_last_error() == name.encode() + b": options are null"
-        for kw, msg in cases:
-            o = _opts(struct, **{**BASE, **kw})
-            assert fn(C.byref(o), None) == -1, (name, kw)
-            err = lib.pulse_last_error()
-            assert err.startswith(name.encode() + b": ") and msg in err, (name, kw, err)
-    with pytest.raises(ValueError, match="entries is null"):
-        _native.check(lib.pulse_tfe_mc_learn(C.byref(_opts(_native.TfeMCLearn, **{**BASE, "entries": None})), None), "pulse_tfe_mc_learn")
+        assert_refusals(lib, name, lambda **kw: opts(struct, **{**BASE, **kw}), cases)
 
 
 def test_header_agrees_with_the_binding():

@@ -1,5 +1,5 @@
 """On-policy first-visit Monte-Carlo control for 2048 on the device (csrc/tfe_mc.hip, agents/tfe_on_policy_mc_gpu.py) against the
-host's statement of it (tests/tfe_mc_host.py: the oracle's environment and Philox under the kernel's policy rule;
+host's statement of it (tests/tfe_host.py: the oracle's environment and Philox under the kernel's policy rule;
 learn_on_host / greedy_on_host) and against the reference's dict-based class.  Every buffer the launches are handed sits between
 guard words, and the rows of keys / steps at and beyond a game's length must keep what they held."""
 import functools
@@ -8,10 +8,11 @@ import random
 import numpy as np
 import pytest
 
+from tests.tfe_gpu_support import PATTERNS, assert_rollout, guard, guards_intact, read, replay, rollout
+
 pytestmark = pytest.mark.gpu
 
-GUARD_BYTES = 256                    # a multiple of the table's 128-byte alignment
-KEY_FILL, STEP_FILL, GUARD_FILL = 0x5A5A5A5A5A5A5A5A, 0xEE, 0x77
+BUFFERS = ("entries", "keys", "steps", "lengths", "total_score", "episode_reward", "counters")
 BATCHES = (1, 63, 64, 65, 257)       # one lane, a wavefront less one, a whole one, one more, more than one workgroup and ragged
 
 
@@ -21,58 +22,14 @@ def _agent(n_games, n=3, **kw):
     from pulselib_amd.agents import OnPolicyFirstVisitMCTFEGPU
     kw.setdefault("capacity", 1 << 16)
     kw.setdefault("max_steps", 256)
-    a = OnPolicyFirstVisitMCTFEGPU(torch.device("cuda:0"), n_games, board_size=n, **kw)
-    a._guards = []
-    for name, fill in (("entries", 0), ("keys", KEY_FILL), ("steps", STEP_FILL), ("lengths", 0), ("total_score", 0), ("episode_reward", 0),
-                       ("counters", 0)):
-        t = getattr(a, name)
-        g = GUARD_BYTES // t.element_size()
-        flat = torch.empty(t.numel() + 2 * g, dtype=t.dtype, device=t.device)
-        flat.view(torch.uint8).fill_(GUARD_FILL)
-        inner = flat[g:g + t.numel()].view(t.shape)
-        inner.fill_(fill)
-        setattr(a, name, inner)
-        a._guards.append((name, flat, g))
+    a = guard(OnPolicyFirstVisitMCTFEGPU(torch.device("cuda:0"), n_games, board_size=n, **kw), BUFFERS, **PATTERNS)
     assert a.entries.data_ptr() % 128 == 0
     return a
 
 
-def _guards_intact(a):
-    for name, flat, g in a._guards:
-        import torch
-        b = flat.view(torch.uint8)
-        gb = g * flat.element_size()
-        assert bool((b[:gb] == GUARD_FILL).all()) and bool((b[-gb:] == GUARD_FILL).all()), f"guard words of {name} were written"
-
-
-def _read(a):
-    """the last roll-out's buffers in full (not trimmed to the longest game)"""
-    return dict(keys=a.keys.cpu().numpy().view(np.uint64), steps=a.steps.cpu().numpy(), lengths=a.lengths.cpu().numpy(),
-                total_score=a.total_score.cpu().numpy(), episode_reward=a.episode_reward.cpu().numpy())
-
-
-def _rollout(a):
-    """one roll-out launch; the read-back carries what keys / steps held before it (the pattern, or an earlier round's rows)"""
-    before = _read(a)
-    a.rollout()
-    return dict(_read(a), keys_before=before["keys"], steps_before=before["steps"])
-
-
 def _host_rollout(a, table, **kw):
-    from tests.tfe_mc_host import rollout_on_host
+    from tests.tfe_host import rollout_on_host
     return rollout_on_host(a.n_games, a.n, a.max_steps, a.epsilon, table, a.env_seed, a.agent_seed, a.tie_seed, a.round_board_id0(), a.round, **kw)
-
-
-def _assert_rollout(got, want, where):
-    """word for word; at and beyond a game's length the rows hold what they held before the launch"""
-    L = want["lengths"]
-    assert np.array_equal(got["lengths"], L), where
-    played = np.arange(got["keys"].shape[0])[:, None] < L[None, :]
-    assert np.array_equal(got["keys"][played], want["keys"][played]), where
-    assert np.array_equal(got["steps"][played], want["steps"][played]), where
-    assert np.array_equal(got["keys"][~played], got["keys_before"][~played]), where
-    assert np.array_equal(got["steps"][~played], got["steps_before"][~played]), where
-    assert np.array_equal(got["total_score"], want["total_score"]) and np.array_equal(got["episode_reward"], want["episode_reward"]), where
 
 
 @functools.lru_cache(maxsize=None)
@@ -82,7 +39,7 @@ def _four_rounds(n, n_games):
     table, rounds, steps = {}, [], 0
     for _ in range(4):
         want = _host_rollout(a, table)
-        got = _rollout(a)
+        got = rollout(a)
         a.learn()
         from pulselib_amd.agents.tfe_on_policy_mc_gpu import learn_on_host
         learn_on_host(want["keys"], want["steps"], want["lengths"], a.gamma, a.frac_bits, table)
@@ -90,7 +47,7 @@ def _four_rounds(n, n_games):
         rounds.append(dict(got=got, want=want, table=a.table(), host_table={k: (list(c), list(s)) for k, (c, s) in table.items()},
                            stats=a.stats(), steps=steps))
         a.round += 1
-    _guards_intact(a)
+    guards_intact(a)
     return rounds
 
 
@@ -100,7 +57,7 @@ def test_rollout_equals_the_host_word_for_word(n, n_games):
     """Round 0 runs on an empty table (the uniform default policy); round 3 on the table of three earlier rounds."""
     rounds = _four_rounds(n, n_games)
     for r, rec in enumerate(rounds):
-        _assert_rollout(rec["got"], rec["want"], (n, n_games, r))
+        assert_rollout(rec["got"], rec["want"], (n, n_games, r))
         assert rec["stats"]["steps"] == rec["steps"] and rec["stats"]["truncated"] == 0
     assert rounds[0]["want"]["present"] == 0
     if n_games >= 63:                                                      # the present-entry and the tie paths ran
@@ -119,29 +76,17 @@ def test_learn_equals_the_host_as_a_map(n, n_games):
 
 def test_games_are_the_environments_own():
     """TFEBatch (pulse_tfe_reset / pulse_tfe_step) replayed with the recorded actions visits the recorded states"""
-    import torch
-    from pulselib_amd.agents.tfe_on_policy_mc_gpu import unpack_steps
-    from pulselib_amd.environments.TFE.TFE import TFEBatch
-    from tests.tfe_mc_host import pack_boards
+    from tests.tfe_host import pack_boards
     a = _agent(65, 3, seed=21, board_id0=1000)
     a.learn_batch().learn_batch()                                          # the second round's games: under a table, other board ids
     a.round -= 1
-    got = _read(a)
-    env = TFEBatch(a.device, 65, 3, seed=a.env_seed, board_id0=a.round_board_id0())
-    boards, _ = env.reset()
-    L = got["lengths"]
-    actions, rewards, _ = unpack_steps(got["steps"])
-    final = np.zeros(65, dtype=np.int64)
-    for t in range(int(L.max())):
-        live = L > t
-        assert np.array_equal(pack_boards(boards.cpu().numpy())[live], got["keys"][t][live]), t
-        act = np.where(live, actions[t], 0).astype(np.int64)
-        boards, rew, dones, _, info = env.step(torch.from_numpy(act).to(a.device))
-        assert np.array_equal(rew.cpu().numpy()[live], rewards[t][live].astype(np.int32)), t
-        assert np.array_equal(dones.cpu().numpy()[live], (L == t + 1)[live]), t
-        final[L == t + 1] = info["score"].cpu().numpy()[L == t + 1]
-    assert np.array_equal(final, got["total_score"])
-    _guards_intact(a)
+    got = read(a)
+
+    def recorded_state(t, live, boards, actions):
+        assert np.array_equal(pack_boards(boards)[live], got["keys"][t][live]), t
+        return actions
+    assert replay(a, got, recorded_state)[2].all()                         # every game ends where the environment says
+    guards_intact(a)
 
 
 def test_one_game_per_round_against_the_cpu_class():
@@ -161,7 +106,7 @@ def test_one_game_per_round_against_the_cpu_class():
         assert table[k][0][act] == count
         assert abs(q[(k, act)] - cpu.q[(k, act)]) <= 2.0 ** -a.frac_bits, (k, act)
     assert a.stats()["truncated"] == 0 and a.stats()["dropped"] == 0
-    _guards_intact(a)
+    guards_intact(a)
 
 
 def test_truncation_at_max_steps():
@@ -172,8 +117,8 @@ def test_truncation_at_max_steps():
     table, cut = {}, 0
     for r in range(2):
         want = _host_rollout(a, table)
-        got = _rollout(a)
-        _assert_rollout(got, want, r)
+        got = rollout(a)
+        assert_rollout(got, want, r)
         cut += want["truncated"]
         assert got["keys"].shape[0] == 8 and got["lengths"].max() == 8 and want["truncated"] > 100
         a.learn()
@@ -181,7 +126,7 @@ def test_truncation_at_max_steps():
         assert a.table() == table
         a.round += 1
         assert a.stats()["truncated"] == cut
-    _guards_intact(a)
+    guards_intact(a)
 
 
 def test_a_full_table_drops_and_ends():
@@ -190,7 +135,7 @@ def test_a_full_table_drops_and_ends():
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import learn_on_host
     a = _agent(257, 3, seed=6, capacity=16)
     want = _host_rollout(a, {})
-    _assert_rollout(_rollout(a), want, 0)
+    assert_rollout(rollout(a), want, 0)
     a.learn()
     a.round += 1
     host = learn_on_host(want["keys"], want["steps"], want["lengths"], a.gamma, a.frac_bits, {})
@@ -200,15 +145,15 @@ def test_a_full_table_drops_and_ends():
     total = sum(sum(c) for c, _ in host.values())
     assert stats["first_visits"] == sum(sum(c) for c, _ in table.values()) and stats["first_visits"] + stats["dropped"] == total
     want = _host_rollout(a, table)                                         # the roll-out against a table without a free slot
-    _assert_rollout(_rollout(a), want, 1)
+    assert_rollout(rollout(a), want, 1)
     # ... and one that is sure to meet its entries.  Which 16 keys were placed is a race among the learner's lanes -- each wavefront
     # starts at its games' last moves -- and round 1's boards pass through few such states (on the host: no lookup of theirs hits
     # under most outcomes of the race).  Round 0's own games do: the game that placed a key plays as before up to the first entry met.
     a.round = 0
     want = _host_rollout(a, table)
-    _assert_rollout(_rollout(a), want, 2)
+    assert_rollout(rollout(a), want, 2)
     assert want["present"] > 0
-    _guards_intact(a)
+    guards_intact(a)
 
 
 def test_same_seeds_same_result_and_clear():
@@ -218,7 +163,7 @@ def test_same_seeds_same_result_and_clear():
         out = []
         for _ in range(3):
             a.learn_batch()
-            got = _read(a)
+            got = read(a)
             played = np.arange(a.max_steps)[:, None] < got["lengths"][None, :]
             out.append((got["keys"][played].tobytes(), got["steps"][played].tobytes(), got["lengths"].tobytes(), got["total_score"].tobytes()))
         return out, a.table(), a.stats()
@@ -227,7 +172,7 @@ def test_same_seeds_same_result_and_clear():
     a.clear()
     assert a.table() == {} and a.round == 0 and set(a.stats().values()) == {0}
     assert first == three_rounds() and len(first[1]) > 1000
-    _guards_intact(a)
+    guards_intact(a)
 
 
 def test_four_by_four_smoke():
@@ -236,13 +181,13 @@ def test_four_by_four_smoke():
     table = {}
     for r in range(2):
         want = _host_rollout(a, table)
-        _assert_rollout(_rollout(a), want, r)
+        assert_rollout(rollout(a), want, r)
         a.learn()
         learn_on_host(want["keys"], want["steps"], want["lengths"], a.gamma, a.frac_bits, table)
         assert a.table() == table
         a.round += 1
     assert a.stats()["truncated"] > 0 and max(table) >= 1 << 36               # cut games; keys that use the upper cells
-    _guards_intact(a)
+    guards_intact(a)
 
 
 def test_it_learns():

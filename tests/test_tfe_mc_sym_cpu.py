@@ -10,6 +10,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from tests.native_args import assert_refusals, opts
+
 ROOT = Path(__file__).resolve().parent.parent
 SIDES = (2, 3, 4)
 
@@ -53,9 +55,9 @@ def test_transforms_are_the_eight_symmetries(n):
 @pytest.mark.parametrize("n", SIDES)
 def test_action_map_commutes_with_the_oracles_move(n):
     """T_j(move(B, a)) == move(T_j(B), ACTION_MAP[j][a]) with the same merge score, for 200 boards, every j and every a; the move is
-    the oracle's step with its spawn taken out (tests/tfe_mc_sym_host.move_on_host)."""
+    the oracle's step with its spawn taken out (tests/tfe_host.move_on_host)."""
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import ACTION_MAP, ACTION_UNMAP, transforms_on_host
-    from tests.tfe_mc_sym_host import move_on_host
+    from tests.tfe_host import move_on_host
     T = transforms_on_host(n)
     assert all(sorted(row) == [0, 1, 2, 3] for row in ACTION_MAP) and len(ACTION_MAP) == 8
     assert all(ACTION_UNMAP[j][ACTION_MAP[j][a]] == a for j in range(8) for a in range(4))
@@ -92,7 +94,7 @@ def test_canon_is_constant_over_the_images_and_greedy_is_equivalent(n):
     """canon_on_host of a board's eight images is one key, the smallest of the eight, with the smallest j that reaches it; and the
     greedy action of that key's entry, mapped back to each image's frame, leads the images to images of one board with one score."""
     from pulselib_amd.agents import tfe_on_policy_mc_gpu as mc
-    from tests.tfe_mc_sym_host import canon_many, move_on_host
+    from tests.tfe_host import canon_many, move_on_host
     T = mc.transforms_on_host(n)
     rng = np.random.default_rng(n)
     symmetric = 0
@@ -149,7 +151,7 @@ def test_run_mask_on_canonical_pairs_is_the_dict_rule(n, n_games):
     """Equal canonical keys: equal tile sums: one run of one unchanged board: one j* (DESIGN.md section 12.1).  Host-played games in
     the canonical frame, round 0 on an empty table and round 1 on the table learnt from it; at n = 2 repeats are common."""
     from pulselib_amd.agents import tfe_on_policy_mc_gpu as mc
-    from tests.tfe_mc_sym_host import rollout_on_host
+    from tests.tfe_host import rollout_on_host
     seed, table, repeats = 31 + n, {}, 0
     for r in range(2):
         o = rollout_on_host(n_games, n, 256, 0.1, table, seed, seed ^ mc.AGENT_KEY, seed ^ mc.TIE_KEY, 50 + r * n_games, r, canonical=True)
@@ -170,12 +172,9 @@ def test_run_mask_on_canonical_pairs_is_the_dict_rule(n, n_games):
 def test_canonical_rollout_on_an_empty_table_plays_the_plain_games(n):
     """no entry: the board moves by y >> 30 in either frame; the recorded pairs are the plain ones, canonicalised"""
     from pulselib_amd.agents import tfe_on_policy_mc_gpu as mc
-    from tests.tfe_mc_host import rollout_on_host as plain_rollout
-    from tests.tfe_mc_sym_host import rollout_on_host
+    from tests.tfe_host import rollout_on_host
     args = (40, n, 128, 0.1, {}, 8, 8 ^ mc.AGENT_KEY, 8 ^ mc.TIE_KEY, 3, 0)
-    want, plain, canon = plain_rollout(*args), rollout_on_host(*args), rollout_on_host(*args, canonical=True)
-    for name in ("keys", "steps", "lengths", "total_score", "episode_reward"):
-        assert np.array_equal(plain[name], want[name]), name                # the helper's plain frame is the existing host roll-out
+    plain, canon = rollout_on_host(*args), rollout_on_host(*args, canonical=True)
     for name in ("lengths", "total_score", "episode_reward", "moved", "final_boards"):
         assert np.array_equal(canon[name], plain[name]), name
     a_c, r_c, _ = mc.unpack_steps(canon["steps"])
@@ -191,7 +190,7 @@ def test_fold_table(n):
     """folding is idempotent, every key of a folded table is its own canonical key, nothing is lost, and the fold of the table learnt
     from plain games on an empty table is the table learnt from the same games recorded in the canonical frame"""
     from pulselib_amd.agents import tfe_on_policy_mc_gpu as mc
-    from tests.tfe_mc_sym_host import rollout_on_host
+    from tests.tfe_host import rollout_on_host
     args = (120, n, 128, 0.1, {}, 9, 9 ^ mc.AGENT_KEY, 9 ^ mc.TIE_KEY, 0, 0)
     fb = mc.frac_bits_for(0.9, 128)
     plain, canon = rollout_on_host(*args), rollout_on_host(*args, canonical=True)
@@ -217,14 +216,6 @@ def test_eval_summary_on_host():
 
 
 # ------------------------------------------------------------------ the entry points' argument checks (as tests/test_tfe_mc_cpu.py)
-def _opts(struct, **kw):
-    o = struct()                                                           # (zero-initialised)
-    for k, v in kw.items():
-        if hasattr(o, k):
-            setattr(o, k, v)
-    return o
-
-
 # never dereferenced: every case fails its check first
 BASE = dict(entries=0x100000, capacity=1 << 10, n_games=64, n=3, max_steps=128, frac_bits=22, gamma=0.9, epsilon=0.1,
             keys=0x200000, steps=0x300000, lengths=0x400000, total_score=0x500000, episode_reward=0x600000, stats=0x700000,
@@ -252,15 +243,7 @@ def test_argument_checks_without_gpu():
     from pulselib_amd import _native
     lib = _native.lib()
     for name, struct, cases in (("pulse_tfe_mc_rollout_canon", _native.TfeMCRollout, TABLE + ROLLOUT), ("pulse_tfe_mc_evaluate", _native.TfeMCEval, TABLE + EVAL)):
-        fn = getattr(lib, name)
-        assert fn(None, None) == -1 and lib.pulse_last_error() == name.encode() + b": options are null"
-        for kw, msg in cases:
-            o = _opts(struct, **{**BASE, **kw})
-            assert fn(C.byref(o), None) == -1, (name, kw)
-            err = lib.pulse_last_error()
-            assert err.startswith(name.encode() + b": ") and msg in err, (name, kw, err)
-    with pytest.raises(ValueError, match="summary is null"):
-        _native.check(lib.pulse_tfe_mc_evaluate(C.byref(_opts(_native.TfeMCEval, **{**BASE, "summary": None})), None), "pulse_tfe_mc_evaluate")
+        assert_refusals(lib, name, lambda **kw: opts(struct, **{**BASE, **kw}), cases)
 
 
 def test_header_agrees_with_the_binding():

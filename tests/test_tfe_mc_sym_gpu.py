@@ -1,5 +1,5 @@
 """The 2048 Monte-Carlo symmetries and evaluation launch on the device (csrc/tfe_mc.hip: pulse_tfe_mc_rollout_canon,
-pulse_tfe_mc_evaluate) against the plain roll-out, the host mirror (tests/tfe_mc_sym_host.py) and the
+pulse_tfe_mc_evaluate) against the plain roll-out, the host mirror (tests/tfe_host.py) and the
 environment's own kernels.  Every buffer a launch is handed sits between guard words.
 
 Shapes: 300 games (two workgroups, the second partial) at n = 2 and n = 3 with max_steps = 64, 70 games at n = 4 with max_steps = 48,
@@ -12,9 +12,11 @@ every table must equal the host's exactly, as n = 2 must at 2^12."""
 import numpy as np
 import pytest
 
+from tests.tfe_gpu_support import guard, guarded, guards_intact, read, replay
+
 pytestmark = pytest.mark.gpu
 
-GUARD_BYTES, GUARD_FILL = 256, 0x77
+BUFFERS = ("entries", "keys", "steps", "lengths", "total_score", "episode_reward", "counters", "_eval")
 #         n, games, max_steps, capacity
 SHAPES = [(2, 300, 64, 1 << 12), (3, 300, 64, 1 << 12), (4, 70, 48, 1 << 12)]
 ROOMY = [(3, 300, 64, 1 << 16), (4, 70, 48, 1 << 16)]
@@ -24,80 +26,42 @@ def _fits(shape):
     return shape[0] == 2 or shape[3] >= 1 << 16
 
 
-def _guarded(t, fill=0):
-    """(the tensor re-seated between guard words, the whole allocation, the guard's length in elements)"""
-    import torch
-    g = GUARD_BYTES // t.element_size()
-    flat = torch.empty(t.numel() + 2 * g, dtype=t.dtype, device=t.device)
-    flat.view(torch.uint8).fill_(GUARD_FILL)
-    inner = flat[g:g + t.numel()].view(t.shape)
-    inner.fill_(fill)
-    return inner, flat, g
-
-
 def _agent(shape, symmetric, seed=None, **kw):
     import torch
     from pulselib_amd.agents import OnPolicyFirstVisitMCTFEGPU
     n, n_games, max_steps, capacity = shape
-    a = OnPolicyFirstVisitMCTFEGPU(torch.device("cuda:0"), n_games, board_size=n, capacity=capacity, max_steps=max_steps,
-                                   seed=10 * n + 1 if seed is None else seed, board_id0=7, symmetric=symmetric, **kw)
-    a._guards = []
-    for name in ("entries", "keys", "steps", "lengths", "total_score", "episode_reward", "counters", "_eval"):
-        inner, flat, g = _guarded(getattr(a, name))
-        setattr(a, name, inner)
-        a._guards.append((name, flat, g))
+    a = guard(OnPolicyFirstVisitMCTFEGPU(torch.device("cuda:0"), n_games, board_size=n, capacity=capacity, max_steps=max_steps,
+                                         seed=10 * n + 1 if seed is None else seed, board_id0=7, symmetric=symmetric, **kw), BUFFERS)
     assert a.entries.data_ptr() % 128 == 0
     return a
-
-
-def _guards_intact(guards):
-    import torch
-    for name, flat, g in guards:
-        b, gb = flat.view(torch.uint8), g * flat.element_size()
-        assert bool((b[:gb] == GUARD_FILL).all()) and bool((b[-gb:] == GUARD_FILL).all()), f"guard words of {name} were written"
 
 
 def _read(a):
     """the last roll-out: keys / actions / rewards / first [T, B] over the moves played (`played`), and the per-game arrays"""
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import unpack_steps
-    lengths = a.lengths.cpu().numpy()
-    act, rew, first = unpack_steps(a.steps.cpu().numpy())
-    return dict(keys=a.keys.cpu().numpy().view(np.uint64), steps=a.steps.cpu().numpy(), actions=act.astype(np.int64), rewards=rew, first=first,
-                lengths=lengths, played=np.arange(a.max_steps)[:, None] < lengths[None, :], total_score=a.total_score.cpu().numpy(),
-                episode_reward=a.episode_reward.cpu().numpy())
+    got = read(a)
+    act, rew, first = unpack_steps(got["steps"])
+    return dict(got, actions=act.astype(np.int64), rewards=rew, first=first, played=np.arange(a.max_steps)[:, None] < got["lengths"][None, :])
 
 
 def _replay(a, got):
     """The recorded games through TFEBatch (pulse_tfe_reset / pulse_tfe_step): the environment meets the recorded states (after
     canonicalisation for a symmetric agent) under the actions mapped back to the board's frame.  Returns the final boards."""
-    import torch
-    from pulselib_amd.environments.TFE.TFE import TFEBatch
-    from tests.tfe_mc_host import pack_boards
-    from tests.tfe_mc_sym_host import ACTION_UNMAP, canon_many
-    B, L = a.n_games, got["lengths"]
-    env = TFEBatch(a.device, B, a.n, seed=a.env_seed, board_id0=a.round_board_id0())
-    boards, _ = env.reset()
-    final, score = np.zeros((B, a.n, a.n), dtype=np.int32), np.zeros(B, dtype=np.int64)
-    for t in range(int(L.max())):
-        live, now = L > t, boards.cpu().numpy()
-        keys, j = canon_many(now) if a.symmetric else (pack_boards(now), np.zeros(B, dtype=np.int64))
+    from tests.tfe_host import ACTION_UNMAP, canon_many, pack_boards
+
+    def recorded_state(t, live, boards, actions):
+        keys, j = canon_many(boards) if a.symmetric else (pack_boards(boards), np.zeros(a.n_games, dtype=np.int64))
         assert np.array_equal(keys[live], got["keys"][t][live]), t
-        moved = np.where(live, ACTION_UNMAP[j, got["actions"][t]], 0).astype(np.int64)
-        boards, rew, dones, _, info = env.step(torch.from_numpy(moved).to(a.device))
-        assert np.array_equal(rew.cpu().numpy()[live], got["rewards"][t][live].astype(np.int32)), t
-        ends = L == t + 1
-        assert np.array_equal(dones.cpu().numpy()[live & ~ends], np.zeros(int((live & ~ends).sum()), dtype=bool)), t
-        final[ends], score[ends] = boards.cpu().numpy()[ends], info["score"].cpu().numpy()[ends]
-        cut = ends & ~dones.cpu().numpy()
-        assert not cut.any() or t + 1 == a.max_steps                       # a game ends where the environment says, or at max_steps
-    assert np.array_equal(score, got["total_score"])
+        return ACTION_UNMAP[j, actions]
+    final, _, done = replay(a, got, recorded_state)
+    assert (done | (got["lengths"] == a.max_steps)).all()                  # a game ends where the environment says, or at max_steps
     return final
 
 
 def _branches(a, got, table, epsilon):
     """(present, greedy) bool[T, B] of the recorded moves: the state had an entry; and the draw was not the epsilon branch's --
     recomputed from Philox (agent_seed, board id, t) on the host"""
-    from tests.tfe_mc_host import philox_many
+    from tests.tfe_host import philox_many
     eps_q24 = int(np.floor(epsilon * 2.0 ** 24))
     ids = [a.round_board_id0() + g for g in range(a.n_games)]
     present = np.isin(got["keys"], np.array(sorted(table), dtype=np.uint64)) & got["played"]
@@ -112,7 +76,7 @@ def _branches(a, got, table, epsilon):
 @pytest.mark.parametrize("shape", SHAPES, ids=str)
 def test_empty_table_plays_the_plain_games(shape):
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import first_visit_flags_on_host
-    from tests.tfe_mc_sym_host import ACTION_MAP, canon_keys
+    from tests.tfe_host import ACTION_MAP, canon_keys
     plain, sym = _agent(shape, False), _agent(shape, True)
     p, s = _read(plain.rollout()), _read(sym.rollout())
     for name in ("lengths", "total_score", "episode_reward"):
@@ -132,7 +96,7 @@ def test_empty_table_plays_the_plain_games(shape):
         assert sym.stats()["truncated"] > 0                                # rehearsed: 5 of 300 at n = 3, 70 of 70 at n = 4
     if shape[0] <= 3:
         assert sym.stats()["truncated"] < shape[1] // 2                    # ... and games that finish
-    _guards_intact(plain._guards + sym._guards)
+    guards_intact(plain, sym)
 
 
 # ------------------------------------------------------------------ 2. the fold
@@ -161,14 +125,14 @@ def test_one_round_learns_the_folded_table(shape):
     else:                                                                   # which keys found room is a race; what is stored is whole
         assert table == {k: host[k] for k in table}
         assert plain.table() == {k: host_plain[k] for k in plain.table()}
-    _guards_intact(plain._guards + sym._guards)
+    guards_intact(plain, sym)
 
 
 # ------------------------------------------------------------------ 3. a warm table
 @pytest.mark.parametrize("shape", SHAPES + ROOMY, ids=str)
 def test_three_symmetric_rounds(shape):
     from pulselib_amd.agents import tfe_on_policy_mc_gpu as mc
-    from tests.tfe_mc_sym_host import rollout_on_host
+    from tests.tfe_host import rollout_on_host
     a = _agent(shape, True)
     n = shape[0]
     host, mirror, ties, greedy_moves = {}, {}, 0, 0
@@ -210,7 +174,7 @@ def test_three_symmetric_rounds(shape):
             assert table == {k: host[k] for k in table}
     print(shape, "greedy moves", greedy_moves, "tie draws", ties, "states", len(table), "dropped", stats["dropped"], "truncated", stats["truncated"])
     assert greedy_moves > 40 and ties > 0
-    _guards_intact(a._guards)
+    guards_intact(a)
 
 
 # ------------------------------------------------------------------ 4. evaluate against the roll-out
@@ -219,8 +183,8 @@ def _evaluate(a, epsilon, zero=True):
     import ctypes as C
     import torch
     from pulselib_amd import _native
-    score, f1, g1 = _guarded(torch.zeros(a.n_games, dtype=torch.int64, device=a.device), -1)
-    lengths, f2, g2 = _guarded(torch.zeros(a.n_games, dtype=torch.int32, device=a.device), -1)
+    score, f1, g1 = guarded(torch.zeros(a.n_games, dtype=torch.int64, device=a.device), -1)
+    lengths, f2, g2 = guarded(torch.zeros(a.n_games, dtype=torch.int32, device=a.device), -1)
     o = _native.TfeMCEval()
     o.entries, o.capacity, o.n_games, o.n, o.max_steps, o.frac_bits = a.entries.data_ptr(), a.capacity, a.n_games, a.n, a.max_steps, a.frac_bits
     o.epsilon, o.env_seed, o.agent_seed, o.tie_seed, o.round = epsilon, a.env_seed, a.agent_seed, a.tie_seed, a.round
@@ -230,7 +194,7 @@ def _evaluate(a, epsilon, zero=True):
     o.summary, o.max_tile_hist, o.total_score, o.lengths = a._eval.data_ptr(), a._eval[8:].data_ptr(), score.data_ptr(), lengths.data_ptr()
     _native.check(a._lib.pulse_tfe_mc_evaluate(C.byref(o), _native.current_stream(a.device)), "pulse_tfe_mc_evaluate")
     words = a._eval.cpu().tolist()
-    _guards_intact([("eval total_score", f1, g1), ("eval lengths", f2, g2)])
+    guards_intact([("eval total_score", f1, g1), ("eval lengths", f2, g2)])
     return words, score.cpu().numpy(), lengths.cpu().numpy()
 
 
@@ -238,7 +202,7 @@ def _evaluate(a, epsilon, zero=True):
 @pytest.mark.parametrize("shape", SHAPES, ids=str)
 def test_evaluate_plays_the_rollouts_games(shape, symmetric):
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import EVAL_SUMMARY, eval_summary_on_host
-    from tests.tfe_mc_sym_host import eval_words
+    from tests.tfe_host import eval_words
     a = _agent(shape, symmetric)
     a.learn_batch().learn_batch()                                          # a table to play against (at 2^12 slots: whatever found room)
     table, raw = a.table(), a.entries.cpu().numpy().copy()
@@ -265,14 +229,14 @@ def test_evaluate_plays_the_rollouts_games(shape, symmetric):
         assert a.evaluate(n_games=65, epsilon=epsilon, board_id0=a.round_board_id0())["score_sum"] == int(score[:65].sum())
     assert np.array_equal(a.entries.cpu().numpy(), raw)                     # the table's bytes: only read
     assert a.evaluate()["games"] == shape[1] and a.eval_board_id0() == 7 + (1 << 62)
-    _guards_intact(a._guards)
+    guards_intact(a)
 
 
 # ------------------------------------------------------------------ 5. it learns
 def test_it_learns_with_symmetry():
     """tests/test_tfe_mc_gpu.py::test_it_learns under symmetric=True, the scores taken from evaluate(epsilon=0) on the table before
     each round (boards board_id0 + 2^62 + g, the same for every call): 4,096 games of 3 x 3 per round, gamma .9, epsilon .1, seed 0.
-    Rehearsed on the CPU with the host mirror (tests/tfe_mc_sym_host.py): mean final score 172.18 +- 1.47 before round 0 (the uniform
+    Rehearsed on the CPU with the host mirror (tests/tfe_host.py): mean final score 172.18 +- 1.47 before round 0 (the uniform
     policy), 235.80 +- 1.71, 249.21 +- 1.69 and 266.22 +- 1.76 before round 3 (1,178 of the 4,096 greedy games repeat a move that
     changes nothing on a full board and are cut at 1,024 moves with the score they had): a difference of 94.0 = 41 standard errors
     of the difference (2.29).  Without symmetry the same rehearsal gives 172.18, 187.86, 187.18, 196.67 (DESIGN.md section 12.1;

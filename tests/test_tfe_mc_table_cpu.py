@@ -3,7 +3,7 @@ pulse_tfe_mc_table_merge): merge_tables_on_host on host-played games, the entry 
 checkpoint file's writer and reader.  Nothing here launches a kernel.
 
 Shapes: those of tests/test_tfe_mc_sym_gpu.py -- (n, games, max_steps) = (2, 300, 64), (3, 300, 64), (4, 70, 48), seed 10 n + 1,
-board_id0 7 -- round 0, played by tests/tfe_mc_sym_host.rollout_on_host and learnt by learn_on_host."""
+board_id0 7 -- round 0, played by tests/tfe_host.rollout_on_host and learnt by learn_on_host."""
 import ctypes as C
 import copy
 import re
@@ -11,6 +11,8 @@ from pathlib import Path
 
 import numpy as np
 import pytest
+
+from tests.native_args import assert_refusals, opts
 
 ROOT = Path(__file__).resolve().parent.parent
 SHAPES = [(2, 300, 64), (3, 300, 64), (4, 70, 48)]
@@ -20,7 +22,7 @@ BOARD_ID0 = 7
 
 def _learnt(n, games, max_steps, board_id0, canonical=False):
     from pulselib_amd.agents import tfe_on_policy_mc_gpu as mc
-    from tests.tfe_mc_sym_host import rollout_on_host
+    from tests.tfe_host import rollout_on_host
     seed = 10 * n + 1
     o = rollout_on_host(games, n, max_steps, 0.1, {}, seed, seed ^ mc.AGENT_KEY, seed ^ mc.TIE_KEY, board_id0, 0, canonical=canonical)
     return mc.learn_on_host(o["keys"], o["steps"], o["lengths"], 0.9, mc.frac_bits_for(0.9, max_steps), {})
@@ -98,25 +100,9 @@ CASES = [(dict(src=None), b"src is null"), (dict(dst=None), b"dst is null"), (di
          (dict(stats=0x700004), b"stats must be 8-byte aligned"), (dict(reserved0=1), b"reserved0 must be 0")]
 
 
-def _opts(**kw):
-    from pulselib_amd import _native
-    o = _native.TfeMCMerge()                                               # (zero-initialised)
-    for k, v in kw.items():
-        setattr(o, k, v)
-    return o
-
-
 def test_argument_checks_without_gpu():
     from pulselib_amd import _native
-    lib = _native.lib()
-    name = b"pulse_tfe_mc_table_merge"
-    assert lib.pulse_tfe_mc_table_merge(None, None) == -1 and lib.pulse_last_error() == name + b": options are null"
-    for kw, msg in CASES:
-        assert lib.pulse_tfe_mc_table_merge(C.byref(_opts(**{**BASE, **kw})), None) == -1, kw
-        err = lib.pulse_last_error()
-        assert err.startswith(name + b": ") and msg in err, (kw, err)
-    with pytest.raises(ValueError, match="stats is null"):
-        _native.check(lib.pulse_tfe_mc_table_merge(C.byref(_opts(**{**BASE, "stats": None})), None), "pulse_tfe_mc_table_merge")
+    assert_refusals(_native.lib(), "pulse_tfe_mc_table_merge", lambda **kw: opts(_native.TfeMCMerge, **{**BASE, **kw}), CASES)
 
 
 def test_header_agrees_with_the_binding():

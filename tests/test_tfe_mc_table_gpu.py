@@ -13,25 +13,15 @@ import re
 import numpy as np
 import pytest
 
+from tests.tfe_gpu_support import guard, guarded, guards_intact
+
 pytestmark = pytest.mark.gpu
 
-GUARD_BYTES, GUARD_FILL = 256, 0x77
 #         n, games, max_steps
 SHAPES = [(2, 300, 64), (3, 300, 64), (4, 70, 48)]
 CAPACITY = {2: 1 << 12, 3: 1 << 16, 4: 1 << 16}
 SPLIT = {300: 153, 70: 38}
 BUFFERS = ("keys", "steps", "lengths", "total_score", "episode_reward", "counters", "_eval", "_merge")
-
-
-def _guarded(t):
-    """(a copy of the tensor between guard words, the whole allocation, the guard's length in elements)"""
-    import torch
-    g = GUARD_BYTES // t.element_size()
-    flat = torch.empty(t.numel() + 2 * g, dtype=t.dtype, device=t.device)
-    flat.view(torch.uint8).fill_(GUARD_FILL)
-    inner = flat[g:g + t.numel()].view(t.shape)
-    inner.copy_(t)
-    return inner, flat, g
 
 
 @pytest.fixture(autouse=True)
@@ -42,7 +32,7 @@ def guarded_tables(monkeypatch):
     from pulselib_amd.agents import OnPolicyFirstVisitMCTFEGPU
 
     def new_table(self, rows):
-        inner, flat, g = _guarded(torch.zeros((rows, 16), dtype=torch.int64, device=self.device))
+        inner, flat, g = guarded(torch.zeros((rows, 16), dtype=torch.int64, device=self.device))
         assert inner.data_ptr() % 128 == 0
         self.__dict__.setdefault("_guards", []).append((f"table of {rows}", flat, g))
         return inner
@@ -51,11 +41,7 @@ def guarded_tables(monkeypatch):
 
 def _guard(a):
     """the per-game buffers and counters of an agent re-seated between guard words (contents kept)"""
-    for name in BUFFERS:
-        inner, flat, g = _guarded(getattr(a, name))
-        setattr(a, name, inner)
-        a._guards.append((name, flat, g))
-    return a
+    return guard(a, BUFFERS, fill=None)
 
 
 def _agent(shape, symmetric=False, capacity=None, n_games=None, board_id0=7, **kw):
@@ -66,14 +52,6 @@ def _agent(shape, symmetric=False, capacity=None, n_games=None, board_id0=7, **k
     return _guard(OnPolicyFirstVisitMCTFEGPU(torch.device("cuda:0"), games if n_games is None else n_games, board_size=n,
                                              capacity=CAPACITY[n] if capacity is None else capacity, seed=10 * n + 1, board_id0=board_id0,
                                              symmetric=symmetric, **kw))
-
-
-def _guards_intact(*agents):
-    import torch
-    for a in agents:
-        for name, flat, g in a._guards:
-            b, gb = flat.view(torch.uint8), g * flat.element_size()
-            assert bool((b[:gb] == GUARD_FILL).all()) and bool((b[-gb:] == GUARD_FILL).all()), f"guard words of {name} were written"
 
 
 def _raw(a):
@@ -116,7 +94,7 @@ def test_merge_of_two_agents_is_the_whole_batch(shape, symmetric):
     assert len(got) < len(ty) + len(tz)                                     # entries met
     assert np.array_equal(_raw(z), z_raw)                                   # the source: only read
     assert y.merge_stats(clear=True) == st and y.merge_stats() == dict(live=0, placed=0, dropped=0)
-    _guards_intact(x, y, z)
+    guards_intact(x, y, z)
 
 
 # ------------------------------------------------------------------ 2. growing keeps the map and the games to come
@@ -142,7 +120,7 @@ def test_grow_keeps_the_map_and_the_future(shape, symmetric):
     assert a.capacity == large // 2 and a.table() == b.table()
     with pytest.raises(ValueError, match="power of two"):
         a.grow(3000)
-    _guards_intact(a, b)
+    guards_intact(a, b)
 
 
 # ------------------------------------------------------------------ 3. no room: counted, never half-learnt
@@ -164,7 +142,7 @@ def test_no_room_is_counted_and_nothing_is_half_added():
     assert src.entries is entries and src.capacity == 1 << 16 and np.array_equal(_raw(src), raw) and src.table() == table
     with pytest.raises(RuntimeError, match="found no room"):
         src.to_symmetric(capacity=1 << 12)
-    _guards_intact(src, dst)
+    guards_intact(src, dst)
 
 
 # ------------------------------------------------------------------ 4. the fold on the device
@@ -197,7 +175,7 @@ def test_fold_on_the_device(shape):
     assert sym.merge_stats() == dict(live=len(t3), placed=len(t3), dropped=0)
     with pytest.raises(ValueError, match="already"):
         sym.to_symmetric()
-    _guards_intact(plain, sym, folded)
+    guards_intact(plain, sym, folded)
 
 
 # ------------------------------------------------------------------ 5. dense sources
@@ -236,7 +214,7 @@ def test_dense_sources():
     for bad in (dense[:, :8], dense.to(torch.int32), dense[:0], dense.cpu()):
         with pytest.raises(ValueError):
             dst.merge_from(bad)
-    _guards_intact(src, dst, one, twice, sym)
+    guards_intact(src, dst, one, twice, sym)
 
 
 # ------------------------------------------------------------------ 6. save, load, continue
@@ -269,7 +247,7 @@ def test_save_load_continue(shape, symmetric, tmp_path):
     b.learn_batch()
     _same_last_round(a, b)
     assert a.table() == b.table() and a.round == b.round == 3 and b.stats()["dropped"] == 0
-    _guards_intact(a, b, c)
+    guards_intact(a, b, c)
 
 
 # ------------------------------------------------------------------ 7. what the Python layer refuses
@@ -307,7 +285,7 @@ def test_script_grows_saves_and_resumes(tmp_path):
         slots = int(grown.group(1)) if grown else slots
         assert occupancy < 0.5 * slots
     assert agent.capacity == slots >= 1 << 15 and agent.occupancy() == len(agent.table()) == seen[-1][0]
-    _guards_intact(agent)
+    guards_intact(agent)
     plain_lines = []
     whole = run(dev, 3, capacity=1 << 16, out=plain_lines.append, **kw)   # without --grow-at the line is the one it was
     assert len(plain_lines) == 3 and not any("occupancy" in line or "grown" in line for line in plain_lines)
@@ -322,4 +300,4 @@ def test_script_grows_saves_and_resumes(tmp_path):
     assert auto.capacity == max(1 << 12, 1 << (4 * saved - 1).bit_length()) and auto.table() == whole.table()
     with pytest.raises(ValueError, match="continues another run"):
         run(dev, 1, capacity=1 << 16, out=lines.append, resume=path, **{**kw, "tables": 200})
-    _guards_intact(whole, head, tail, auto)
+    guards_intact(whole, head, tail, auto)

@@ -10,6 +10,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from tests.native_args import assert_refusals
+
 ROOT = Path(__file__).resolve().parent.parent
 NAMES = ("pulse_tfe_nt_rollout", "pulse_tfe_nt_learn", "pulse_tfe_nt_apply", "pulse_tfe_nt_evaluate")
 
@@ -106,17 +108,10 @@ def test_argument_checks_without_gpu(name):
     is asked for or anything is launched (there is no device here to ask)"""
     from pulselib_amd import _native
     lib = _native.lib()
-    fn = getattr(lib, name)
-    assert fn(None, None) == -1 and lib.pulse_last_error() == name.encode() + b": options are null"
-    for kw, msg in CASES[name]:
-        assert fn(C.byref(_opts(name, **kw)), None) == -1, (name, kw)
-        err = lib.pulse_last_error()
-        assert err.startswith(name.encode() + b": ") and msg in err, (name, kw, err)
+    assert_refusals(lib, name, lambda **kw: _opts(name, **kw), CASES[name])
     if name == "pulse_tfe_nt_learn":                                       # the learner reads no weight
         o = _opts(name, net_weights=None, n_games=0)
-        assert fn(C.byref(o), None) == -1 and b"n_games must be positive" in lib.pulse_last_error()
-    with pytest.raises(ValueError, match="board side n must be 4"):
-        _native.check(fn(C.byref(_opts(name, net_n=2)), None), name)
+        assert getattr(lib, name)(C.byref(o), None) == -1 and b"n_games must be positive" in lib.pulse_last_error()
 
 
 def test_python_layer_refuses():
@@ -174,8 +169,7 @@ def test_value_is_the_same_on_the_eight_images():
 def test_host_philox_and_moves_are_the_oracles():
     from oracle import oracle as orc
     from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-    from tests.tfe_mc_host import pack_boards
-    from tests.tfe_mc_sym_host import move_on_host
+    from tests.tfe_host import move_on_host, pack_boards
     for seed, subseq, offset in ((1, 2, 3), (2 ** 63 + 5, 2 ** 64 - 1, 77), (0x2048AC7105EED, 12345678901234, 0)):
         assert nt.philox_many_on_host(seed, [subseq], offset)[0].tolist() == [int(x) for x in orc.philox4x32(seed, subseq, offset)]
     rng = np.random.default_rng(5)
@@ -240,7 +234,7 @@ def test_learn_and_apply_on_a_hand_worked_case():
 # ------------------------------------------------------------------ games on the host
 def _round(weights, tuples, r, n_games=256, epsilon=0.0, max_steps=4096, seed=0, **kw):
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import AGENT_KEY, TIE_KEY
-    from tests.tfe_nt_host import rollout_nt_on_host
+    from tests.tfe_host import rollout_nt_on_host
     return rollout_nt_on_host(n_games, max_steps, epsilon, 1.0, weights, tuples, True, seed, seed ^ AGENT_KEY, seed ^ TIE_KEY, r * n_games, r, **kw)
 
 

@@ -1,5 +1,5 @@
 """The 2048 n-tuple network on the device (csrc/tfe_ntuple.hip: pulse_tfe_nt_rollout, pulse_tfe_nt_learn,
-pulse_tfe_nt_apply, pulse_tfe_nt_evaluate) against the host's statement of it (tests/tfe_nt_host.py: the oracle's environment under
+pulse_tfe_nt_apply, pulse_tfe_nt_evaluate) against the host's statement of it (tests/tfe_host.py: the oracle's environment under
 greedy_nt_on_host; learn_nt_on_host, apply_nt_on_host) and the environment's own kernels.  Every comparison is exact: keys, bytes and
 integers word for word, values and weights as bit patterns.  Every buffer a launch is handed sits between guard words, and the rows of
 keys / values / steps at and beyond a game's length must keep what they held.
@@ -14,13 +14,15 @@ import functools
 import numpy as np
 import pytest
 
+from tests.tfe_gpu_support import PATTERNS, assert_rollout, guard, guards_intact, replay, rollout
+
 pytestmark = pytest.mark.gpu
 
-GUARD_BYTES, GUARD_FILL = 256, 0x77
-KEY_FILL, STEP_FILL, VALUE_FILL = 0x5A5A5A5A5A5A5A5A, 0xEE, -12345.678
 GAMES, MAX_STEPS, ROUNDS, EPSILON = 257, 256, 3, .25
 TUPLES = ((0, 1, 2, 3), (4, 5, 6, 8, 9, 10))
 SEED, BOARD_ID0 = 457, 3000
+BUFFERS = ("weights_dev", "acc", "keys", "values", "steps", "lengths", "total_score", "episode_reward", "counters", "_eval")
+PER_MOVE = ("keys", "values", "steps")
 
 
 def _agent(n_games=GAMES, **kw):
@@ -28,60 +30,16 @@ def _agent(n_games=GAMES, **kw):
     import torch
     from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
     kw = dict(dict(tuples=TUPLES, epsilon=EPSILON, max_steps=MAX_STEPS, seed=SEED, board_id0=BOARD_ID0), **kw)
-    a = NTupleTDAfterstateTFEGPU(torch.device("cuda:0"), n_games, **kw)
-    a._guards = []
-    for name, fill in (("weights_dev", 0), ("acc", 0), ("keys", KEY_FILL), ("values", VALUE_FILL), ("steps", STEP_FILL), ("lengths", 0),
-                       ("total_score", 0), ("episode_reward", 0), ("counters", 0), ("_eval", 0)):
-        t = getattr(a, name)
-        g = GUARD_BYTES // t.element_size()
-        flat = torch.empty(t.numel() + 2 * g, dtype=t.dtype, device=t.device)
-        flat.view(torch.uint8).fill_(GUARD_FILL)
-        inner = flat[g:g + t.numel()].view(t.shape)
-        inner.fill_(fill)
-        setattr(a, name, inner)
-        a._guards.append((name, flat, g))
+    a = guard(NTupleTDAfterstateTFEGPU(torch.device("cuda:0"), n_games, **kw), BUFFERS, **PATTERNS)
     assert a.acc.data_ptr() % 16 == 0
     return a
 
 
-def _guards_intact(a):
-    import torch
-    for name, flat, g in a._guards:
-        b = flat.view(torch.uint8)
-        gb = g * flat.element_size()
-        assert bool((b[:gb] == GUARD_FILL).all()) and bool((b[-gb:] == GUARD_FILL).all()), f"guard words of {name} were written"
-
-
-def _read(a):
-    """the last roll-out's buffers in full (not trimmed to the longest game); values as bit patterns"""
-    return dict(keys=a.keys.cpu().numpy().view(np.uint64), values=a.values.cpu().numpy().view(np.uint64), steps=a.steps.cpu().numpy(),
-                lengths=a.lengths.cpu().numpy(), total_score=a.total_score.cpu().numpy(), episode_reward=a.episode_reward.cpu().numpy())
-
-
-def _rollout(a):
-    before = _read(a)
-    a.rollout()
-    return dict(_read(a), **{k + "_before": before[k] for k in ("keys", "values", "steps")})
-
-
 def _host_rollout(a, weights, **kw):
-    from tests.tfe_nt_host import rollout_nt_on_host
+    from tests.tfe_host import rollout_nt_on_host
     kw = dict(dict(epsilon=a.epsilon, board_id0=a.round_board_id0()), **kw)
     return rollout_nt_on_host(a.n_games, a.max_steps, kw["epsilon"], a.gamma, weights, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
                               kw["board_id0"], a.round)
-
-
-def _assert_rollout(got, want, where):
-    """word for word; at and beyond a game's length the rows hold what they held before the launch"""
-    L = want["lengths"]
-    assert np.array_equal(got["lengths"], L), where
-    played = np.arange(got["keys"].shape[0])[:, None] < L[None, :]
-    assert np.array_equal(got["keys"][played], want["keys"][played]), where
-    assert np.array_equal(got["values"][played], want["values"].view(np.uint64)[played]), where
-    assert np.array_equal(got["steps"][played], want["steps"][played]), where
-    for k in ("keys", "values", "steps"):
-        assert np.array_equal(got[k][~played], got[k + "_before"][~played]), (where, k)
-    assert np.array_equal(got["total_score"], want["total_score"]) and np.array_equal(got["episode_reward"], want["episode_reward"]), where
 
 
 def _play_rounds(symmetric, rounds):
@@ -93,7 +51,7 @@ def _play_rounds(symmetric, rounds):
     for _ in range(rounds):
         policy = a.weights()
         want = _host_rollout(a, policy)
-        got = _rollout(a)
+        got = rollout(a, PER_MOVE)
         a.learn()
         acc = a.acc.cpu().numpy()
         host_acc = np.zeros_like(acc)
@@ -112,7 +70,7 @@ def _play_rounds(symmetric, rounds):
                    weights_changed=int((weights.view(np.uint32) != policy.view(np.uint32)).sum()), max_index=int(np.flatnonzero(~untouched).max()))
         out.append(rec)
         a.round += 1
-    _guards_intact(a)
+    guards_intact(a)
     return a, out
 
 
@@ -133,7 +91,7 @@ def test_rollout_equals_the_host_word_for_word():
     a, rounds = _rounds()
     cut = 0
     for r, rec in enumerate(rounds):
-        _assert_rollout(rec["got"], rec["want"], r)
+        assert_rollout(rec["got"], rec["want"], r, PER_MOVE)
         cut += rec["want"]["truncated"]
         assert rec["stats_learn"]["moves"] == rec["moves"] and rec["stats_learn"]["truncated"] == cut
     assert not rounds[0]["want"]["values"].any() and rounds[2]["want"]["values"].any()
@@ -144,7 +102,7 @@ def test_rollout_without_symmetry():
     """symmetric = 0: one feature per tuple; the second round runs on weights the first one learnt"""
     _, rounds = _play_rounds(False, 2)
     for r, rec in enumerate(rounds):
-        _assert_rollout(rec["got"], rec["want"], r)
+        assert_rollout(rec["got"], rec["want"], r, PER_MOVE)
         assert rec["acc_equal"] and rec["weights_equal"] and rec["acc_zero"] and rec["acc_adds"] == 2 * rec["host"]["learnt"], r
     assert rounds[1]["want"]["values"].any()
 
@@ -152,29 +110,20 @@ def test_rollout_without_symmetry():
 def test_recorded_actions_replay_through_the_environment():
     """TFEBatch (pulse_tfe_reset / pulse_tfe_step) with the same seed and board ids, stepped by the recorded actions, meets the boards
     whose moved images pack to the recorded keys, with the recorded rewards, terminal bits and final scores."""
-    import torch
     from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-    from pulselib_amd.environments.TFE.TFE import TFEBatch
-    from tests.tfe_mc_host import pack_boards
+    from tests.tfe_host import pack_boards
     a, rounds = _rounds()
-    rec = rounds[2]
-    got, L = rec["got"], rec["got"]["lengths"]
-    actions, rewards, terminal = nt.unpack_steps(got["steps"])
-    env = TFEBatch(a.device, GAMES, 4, seed=a.env_seed, board_id0=rec["board_id0"])
-    boards, _ = env.reset()
-    final, rows = np.zeros(GAMES, dtype=np.int64), np.arange(GAMES)
-    for t in range(int(L.max())):
-        live = L > t
-        after, scores = nt.moves_on_host(pack_boards(boards.cpu().numpy()))
-        act = np.where(live, actions[t], 0).astype(np.int64)
-        assert np.array_equal(after[rows, act][live], got["keys"][t][live]), t
-        assert np.array_equal(nt.rewards_of_scores(scores[rows, act])[live], rewards[t][live]), t
-        boards, rew, dones, _, info = env.step(torch.from_numpy(act).to(a.device))
-        assert np.array_equal(rew.cpu().numpy()[live], rewards[t][live].astype(np.int32)), t
-        assert np.array_equal(dones.cpu().numpy()[live] != 0, terminal[t][live]), t
-        ends = L == t + 1
-        final[ends] = info["score"].cpu().numpy()[ends]
-    assert np.array_equal(final, got["total_score"])
+    got, L, rows = rounds[2]["got"], rounds[2]["got"]["lengths"], np.arange(GAMES)
+    _, rewards, terminal = nt.unpack_steps(got["steps"])
+
+    def recorded_afterstate(t, live, boards, actions):
+        after, scores = nt.moves_on_host(pack_boards(boards))
+        assert np.array_equal(after[rows, actions][live], got["keys"][t][live]), t
+        assert np.array_equal(nt.rewards_of_scores(scores[rows, actions])[live], rewards[t][live]), t
+        return actions
+    _, _, done = replay(a, got, recorded_afterstate, rounds[2]["board_id0"])
+    played = np.arange(MAX_STEPS)[:, None] < L[None, :]                    # the terminal bit: the game's last move, where the environment ended it
+    assert np.array_equal(terminal[played], ((np.arange(MAX_STEPS)[:, None] == L[None, :] - 1) & done[None, :])[played])
 
 
 def test_learn_equals_the_host_word_for_word():
@@ -200,21 +149,22 @@ def test_apply_equals_the_host_bit_for_bit():
 def test_evaluate_plays_the_rollouts_games(epsilon):
     """the 24 counters and the per-game arrays against the host's games under the weights of three rounds"""
     from pulselib_amd.agents.tfe_ntuple_td_gpu import EVAL_SUMMARY
-    from tests.tfe_nt_host import eval_words
+    from tests.tfe_host import eval_words
     a, _ = _rounds()
     want = _host_rollout(a, a.weights(), epsilon=epsilon)
     ev = a.evaluate(epsilon=epsilon, board_id0=a.round_board_id0(), per_game=True)
     assert np.array_equal(ev["total_score"], want["total_score"]) and np.array_equal(ev["lengths"], want["lengths"])
-    assert [ev[k] for k in EVAL_SUMMARY] + ev["max_tile_hist"] == eval_words(want)
+    words = eval_words(want["total_score"], want["lengths"], want["final_boards"], want["truncated"], want["greedy"], want["capped"])
+    assert [ev[k] for k in EVAL_SUMMARY] + ev["max_tile_hist"] == words
     assert ev["games"] == GAMES and (ev["moves_greedy"] == ev["moves"]) == (epsilon == 0.0) and sum(ev["max_tile_hist"]) == GAMES
     if epsilon:
         a.epsilon, keep = epsilon, a.epsilon                               # ... and they are the games the roll-out records
-        got = _rollout(a)
+        got = rollout(a, PER_MOVE)
         a.epsilon = keep
         assert np.array_equal(got["total_score"], ev["total_score"]) and np.array_equal(got["lengths"], ev["lengths"])
     small = a.evaluate(n_games=64)                                         # the defaults: epsilon 0, other boards, no arrays
     assert small["games"] == 64 and "total_score" not in small
-    _guards_intact(a)
+    guards_intact(a)
 
 
 def test_save_and_load_on_the_device(tmp_path):
