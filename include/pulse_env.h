@@ -788,6 +788,42 @@ typedef struct PulseTfeNtEval {
 } PulseTfeNtEval;
 int pulse_tfe_nt_evaluate(const PulseTfeNtEval* o, void* stream);
 
+/* ---- the n-tuple network under expectimax search, one chance layer deep: the same network asked about the boards AFTER the random
+ * tile.  Everything is float64, one rounding per operation.  For a board B and a = 0..3, (B_a, score_a), r_a, V and "candidate"
+ * (B_a != B) are pulse_tfe_nt_rollout's.  For a candidate a the CHANCE BOARDS of B_a are C(c, k) = B_a with nibble k at the empty cell
+ * c, k = 1 (a 2-tile) or 2 (a 4-tile), in slot s = 2 c + (k - 1), s = 0..31.  The tile odds are the environment's own:
+ * P_1 = 15099495 * 2^-24 and P_2 = 1677721 * 2^-24 (exact doubles); the cell is uniform over the n_empty(B_a) empty cells.
+ *   m(C)   = the maximum over the candidates a' of C of r_a' + gamma * V(C_a'), 0.0 where C has none (the game is over there); a chance
+ *            board is valued like any board (the 32,768-tile cut is a rule of real games only);
+ *   term_s = P_k * m(C(c, k)), +0.0 at a slot whose cell is filled;
+ *   S      = the pairwise tree over the 32 terms in slot order: level 0 adds slots s and s ^ 1, level 1 s and s ^ 2, .. up to 16;
+ *   E_a    = S / n_empty(B_a),  q_a = r_a + gamma * E_a;  q_a = +0.0 for a move that is no candidate.
+ * The action: pulse_tfe_nt_rollout's rule on these q -- the epsilon branch, the scan over the candidates in the order a = 0..3, the
+ * tie coins Philox4x32-10(tie_seed, key of B, round).  At gamma = 0 this is the one-ply policy.  32 lanes play one board.
+ * (A row of four nibbles 15 has a merge score the row table cannot hold, as in the roll-out: q of a board whose move or chance board
+ * squashes such a row is not defined.)
+ *
+ * pulse_tfe_nt_search: for boards[g], g < n_boards (any packed boards, device uint64): q[g][0..3], action[g] = the greedy action
+ * (-1: no candidate: the board is over), candidates[g] = bit a set where B_a != B.  The weights are only read.
+ *
+ * pulse_tfe_nt_evaluate_search: pulse_tfe_nt_evaluate's games, streams, counters and per-game arrays under the search policy.
+ *
+ * PULSE_EINVAL, before anything is launched: the network's checks; n_boards < 1; gamma outside [0, 1]; a null buffer; boards or q not
+ * 8-byte aligned; non-zero reserved fields; pulse_tfe_nt_evaluate's own for pulse_tfe_nt_evaluate_search. */
+typedef struct PulseTfeNtSearch {
+    PulseTfeNtNet net;
+    int32_t n_boards, reserved0;
+    double gamma;
+    uint64_t tie_seed, round;
+    const uint64_t* boards;             /* uint64[n_boards] */
+    double* q;                          /* float64[n_boards][4] */
+    int8_t* action;                     /* int8[n_boards] */
+    uint8_t* candidates;                /* uint8[n_boards] */
+    int64_t reserved1;
+} PulseTfeNtSearch;
+int pulse_tfe_nt_search(const PulseTfeNtSearch* o, void* stream);
+int pulse_tfe_nt_evaluate_search(const PulseTfeNtEval* o, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

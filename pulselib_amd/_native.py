@@ -146,7 +146,7 @@ class TfeMCMerge(C.Structure):
                 ("n", C.c_int32), ("canonical", C.c_int32), ("stats", C.c_void_p), ("reserved0", C.c_int64)]
 
 
-# the 2048 n-tuple network (include/pulse_env.h): the network heads the four structs
+# the 2048 n-tuple network (include/pulse_env.h): the network heads the structs
 TFE_NT_MAX_TUPLES, TFE_NT_MAX_LEN, TFE_NT_FRAC_BITS, TFE_NT_DELTA_MAX = 8, 6, 16, 8192.0
 _TFE_NT_SEEDS = [(n, C.c_uint64) for n in ("env_seed", "agent_seed", "tie_seed", "board_id0", "round")]
 
@@ -173,6 +173,11 @@ class TfeNtApply(C.Structure):
 class TfeNtEval(C.Structure):
     _fields_ = [("net", TfeNtNet), ("n_games", C.c_int32), ("max_steps", C.c_int32), ("gamma", C.c_double), ("epsilon", C.c_double)] + _TFE_NT_SEEDS + [
         (n, C.c_void_p) for n in ("summary", "max_tile_hist", "total_score", "lengths")] + [("reserved0", C.c_int64)]
+
+
+class TfeNtSearch(C.Structure):
+    _fields_ = [("net", TfeNtNet), ("n_boards", C.c_int32), ("reserved0", C.c_int32), ("gamma", C.c_double), ("tie_seed", C.c_uint64),
+                ("round", C.c_uint64)] + [(n, C.c_void_p) for n in ("boards", "q", "action", "candidates")] + [("reserved1", C.c_int64)]
 
 
 # every symbol include/pulse_env.h declares: (restype, argtypes)
@@ -240,6 +245,8 @@ SYMBOLS = {
     "pulse_tfe_nt_learn": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_apply": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_evaluate": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_search": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_evaluate_search": (C.c_int, [_P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

@@ -7,10 +7,11 @@ symmetries of the square, which share the table.  A round is three launches and 
 moves that change the board, and records per move the afterstate's key, its V and one byte; `pulse_tfe_nt_learn` runs one lane per
 recorded move and adds the temporal difference reward' + gamma * V' - V (0 - V at a terminal move) as a fixed-point integer into
 {sum, cnt} of every weight the afterstate reads; `pulse_tfe_nt_apply` moves every visited weight by alpha / F of the MEAN of its
-adds and zeroes the accumulators.  `pulse_tfe_nt_evaluate` plays games without a trajectory and reduces the scores in the launch.
+adds and zeroes the accumulators.  `pulse_tfe_nt_evaluate` plays games without a trajectory and reduces the scores in the launch; `pulse_tfe_nt_search` and
+`pulse_tfe_nt_evaluate_search` play under expectimax search one chance layer deep (section 13.1), 32 lanes per board.
 
 The policy of a round is frozen (the weights are only read by the roll-out) and the adds are integers, so a round's result does not
-depend on scheduling: `feature_cells_on_host`, `value_on_host`, `greedy_nt_on_host`, `learn_nt_on_host` and `apply_nt_on_host` are
+depend on scheduling: `feature_cells_on_host`, `value_on_host`, `greedy_nt_on_host`, `search_nt_on_host`, `learn_nt_on_host` and `apply_nt_on_host` are
 the host's statement of the same arithmetic in numpy, vectorised over boards, and the device is held to them word for word."""
 from __future__ import annotations
 
@@ -134,6 +135,49 @@ def greedy_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
     q = rewards.astype(np.float64) + float(gamma) * values
     best = greedy_scan_many_on_host(q, philox_many_on_host(tie_seed, keys, int(round)), after != keys[:, None])
     return dict(action=best, after=after, scores=scores, rewards=rewards, values=values, q=q)
+
+
+# ------------------------------------------------------------------ expectimax search, one chance layer deep
+TILE_ODDS = (15099495.0 / 16777216.0, 1677721.0 / 16777216.0)                                 # a 2-tile, a 4-tile (csrc/tfe_device.h: tfe_spawn_packed)
+
+
+def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: int, round: int) -> dict:
+    """pulse_tfe_nt_search on the host, word for word.  For a candidate move a of board B (B_a != B) the chance boards of B_a are B_a
+    with nibble k = 1, 2 at an empty cell c, slot s = 2 c + (k - 1); m = the best r + gamma * V over the candidate moves of a chance board
+    (scanned in the order 0..3, a larger one replaces; 0.0 without a candidate); term_s = P_k * m, +0.0 at a filled cell; S = the pairwise
+    tree over the 32 terms (x[0::2] + x[1::2], five times); E_a = S / n_empty(B_a); q_a = r_a + gamma * E_a, +0.0 for a move that is no
+    candidate.  The action is greedy_nt_on_host's scan on these q.  Returns q float64[N, 4], action int64[N] (-1: no candidate),
+    candidates uint8[N] (bit a), E float64[N, 4] (0.0 for a non-candidate), terms float64[N, 4, 32], and the moves themselves: after
+    uint64[N, 4], rewards int64[N, 4]."""
+    keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
+    gamma = float(gamma)
+    after, scores = moves_on_host(keys)
+    cand = after != keys[:, None]
+    slot = np.arange(32)
+    shift, tile = (_U64(4) * (slot >> 1).astype(_U64)), ((slot & 1) + 1).astype(_U64)
+    empty = ((after[:, :, None] >> shift) & _U64(15)) == 0                                     # [N, 4, 32]: the slot's cell is empty in B_a
+    live = cand[:, :, None] & empty
+    chance = (after[:, :, None] | (tile << shift))[live]
+    terms = np.zeros(live.shape, dtype=np.float64)
+    if len(chance):
+        after2, scores2 = moves_on_host(chance)
+        x = rewards_of_scores(scores2).astype(np.float64) + gamma * value_on_host(after2.reshape(-1), weights, tuples, symmetric).reshape(-1, 4)
+        cand2 = after2 != chance[:, None]
+        m, found = np.zeros(len(chance), dtype=np.float64), np.zeros(len(chance), dtype=bool)
+        for a in range(4):
+            take = cand2[:, a] & (~found | (x[:, a] > m))
+            m, found = np.where(take, x[:, a], m), found | cand2[:, a]
+        terms[live] = np.broadcast_to(np.array(TILE_ODDS, dtype=np.float64)[slot & 1], live.shape)[live] * m
+    total = terms
+    for _ in range(5):
+        total = total[..., 0::2] + total[..., 1::2]
+    n_empty = empty[:, :, 0::2].sum(axis=2)
+    E = np.where(cand, total[..., 0] / np.maximum(n_empty, 1), 0.0)
+    rewards = rewards_of_scores(scores)
+    q = np.where(cand, rewards.astype(np.float64) + gamma * E, 0.0)
+    action = greedy_scan_many_on_host(q, philox_many_on_host(tie_seed, keys, int(round)), cand)
+    return dict(q=q, action=action, candidates=(cand << np.arange(4)).sum(axis=1).astype(np.uint8), E=E, terms=terms, after=after,
+                rewards=rewards)
 
 
 # ------------------------------------------------------------------ the learner and the apply launch
@@ -296,7 +340,46 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         return o
 
     def _eval_launch(self, o):
-        self._launch("pulse_tfe_nt_evaluate", o)
+        self._launch(self._eval_entry, o)
+
+    # ------------------------------------------------------------------ expectimax search
+    _eval_entry = "pulse_tfe_nt_evaluate"
+
+    def _under_search(self, call, *args):
+        self._eval_entry = "pulse_tfe_nt_evaluate_search"
+        try:
+            return call(*args)
+        finally:
+            del self._eval_entry
+
+    def search_launch(self, boards, q, action, candidates):
+        """The launch of search() alone on device tensors: boards int64[N] (the keys' words), q float64[N, 4], action int8[N],
+        candidates uint8[N]."""
+        o = _native.TfeNtSearch()
+        self._net(o.net)
+        o.n_boards, o.gamma, o.tie_seed, o.round = boards.numel(), self.gamma, self.tie_seed, self.round
+        o.boards, o.q, o.action, o.candidates = boards.data_ptr(), q.data_ptr(), action.data_ptr(), candidates.data_ptr()
+        return self._launch("pulse_tfe_nt_search", o)
+
+    def search(self, keys) -> dict:
+        """One launch and one read-back: q float64[N, 4] of the packed boards `keys` under one chance layer of search, the greedy action
+        int8[N] (-1: the board is over) and the candidates uint8[N] (bit a: move a changes the board); search_nt_on_host on the device."""
+        import torch
+        keys = np.array(keys, dtype=_U64).reshape(-1)                       # (a copy: torch takes no read-only array)
+        boards = torch.from_numpy(keys.view(np.int64)).to(self.device)
+        q = torch.zeros((len(keys), 4), dtype=torch.float64, device=self.device)
+        action, candidates = torch.zeros(len(keys), dtype=torch.int8, device=self.device), torch.zeros(len(keys), dtype=torch.uint8, device=self.device)
+        self.search_launch(boards, q, action, candidates)
+        return dict(q=q.cpu().numpy(), action=action.cpu().numpy(), candidates=candidates.cpu().numpy())
+
+    def evaluate_search_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False):
+        """evaluate_launch() under the search policy."""
+        return self._under_search(self.evaluate_launch, n_games, epsilon, board_id0, per_game)
+
+    def evaluate_search(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False) -> dict:
+        """evaluate() under the search policy: the same default boards, so the two policies are paired on the spawns each game starts
+        from."""
+        return self._under_search(self.evaluate, n_games, epsilon, board_id0, per_game)
 
     # ------------------------------------------------------------------ read-back (the only syncs) and the checkpoint
     def weights(self) -> np.ndarray:

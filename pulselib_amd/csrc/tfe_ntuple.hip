@@ -16,6 +16,7 @@
 #include "pulse_internal.h"
 #include "tfe_agent_device.h"
 #include "tfe_device.h"
+#include "tfe_ntuple_device.h"
 
 namespace {
 
@@ -26,71 +27,8 @@ using pulse::fail_named;
 using pulse::finish_launch;
 
 constexpr int kBlock = 256;
-constexpr int kMaxTuples = PULSE_TFE_NT_MAX_TUPLES, kMaxLen = PULSE_TFE_NT_MAX_LEN;
 static_assert(sizeof(PulseTfeNtNet) == 104 && sizeof(PulseTfeNtRollout) == 232 && sizeof(PulseTfeNtLearn) == 176 && sizeof(PulseTfeNtApply) == 128 &&
               sizeof(PulseTfeNtEval) == 208, "struct layouts are part of the ABI");
-
-// The network as the kernels take it (by value: every word is read at a wavefront-uniform position).  Feature f = t * images + j:
-// byte i of shifts[f] = 4 * (the board cell that image j shows at cell i of tuple t), 0 at and beyond the tuple's length -- those
-// nibbles are masked off again by mask[t] = 16^len - 1.
-struct NtDev {
-    uint64_t shifts[kMaxTuples * 8];
-    uint32_t offset[kMaxTuples], mask[kMaxTuples];
-    int32_t n_tuples;
-};
-
-__device__ __forceinline__ uint32_t feature_index(uint64_t key, uint64_t sh, uint32_t mask, uint32_t offset) {
-    uint32_t idx = 0u;
-#pragma unroll
-    for (int i = 0; i < kMaxLen; ++i) idx |= ((uint32_t)(key >> ((sh >> (8 * i)) & 63ull)) & 15u) << (4 * i);
-    return (idx & mask) + offset;
-}
-
-// V of the four afterstates of a move at once: per tuple the 4 * IMG indices are formed first and their loads issued with nothing
-// dependent between them (32 lines in flight per lane), then added in the order of the definition: tuple-major, image j = 0..7.
-template <int IMG>
-__device__ __forceinline__ void values4(const NtDev& net, const float* __restrict__ w, const uint64_t (&ka)[4], double (&v)[4]) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a) v[a] = 0.0;
-#pragma unroll 1
-    for (int t = 0; t < net.n_tuples; ++t) {
-        const uint32_t mask = net.mask[t], offset = net.offset[t];
-        uint32_t idx[4][IMG];
-#pragma unroll
-        for (int j = 0; j < IMG; ++j) {
-            const uint64_t sh = net.shifts[t * IMG + j];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) idx[a][j] = feature_index(ka[a], sh, mask, offset);
-        }
-        float x[4][IMG];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int j = 0; j < IMG; ++j) x[a][j] = w[idx[a][j]];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int j = 0; j < IMG; ++j) v[a] = __dadd_rn(v[a], (double)x[a][j]);
-    }
-}
-
-__device__ __forceinline__ bool has_nibble15(const PackedBoard p) {
-    const uint32_t l = p.lo & (p.lo >> 1) & (p.lo >> 2) & (p.lo >> 3), h = p.hi & (p.hi >> 1) & (p.hi >> 2) & (p.hi >> 3);
-    return ((l | h) & 0x11111111u) != 0u;
-}
-
-// what the game loops get: pulse_tfe_nt_rollout's struct, or pulse_tfe_nt_evaluate's outputs in its shape (stats = summary)
-struct Games {
-    const float* weights;
-    int32_t n_games, max_steps;
-    double gamma;
-    uint32_t eps_q24;
-    uint64_t env_seed, agent_seed, tie_seed, board_id0, round;
-    uint64_t* keys; double* values; uint8_t* steps;
-    int32_t* lengths; int64_t* total_score; int32_t* episode_reward;
-    int64_t* stats; int64_t* hist;
-    const uint32_t* lut;
-};
 
 // IMG = 8 (symmetric) or 1.  Record: pulse_tfe_nt_rollout; otherwise pulse_tfe_nt_evaluate.
 template <int IMG, bool Record>
@@ -230,6 +168,30 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_apply_kernel(float* __restrict_
     }
 }
 
+int check_acc(const int64_t* acc, const char* name) {
+    if (!acc) return fail_named(name, "acc is null");
+    if ((uintptr_t)acc & 15u) return fail_named(name, "acc must be 16-byte aligned");
+    return 0;
+}
+
+int launch_games(Games& g, const NtDev& dev, bool symmetric, bool record, void* stream) {
+    if (int rc = pulse::tfe_row_lut(&g.lut)) return rc;
+    const dim3 grid((unsigned)((g.n_games + kBlock - 1) / kBlock)), block(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+    if (record) {
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_games_kernel<8, true>), grid, block, 0, st, g, dev);
+        else hipLaunchKernelGGL((tfe_nt_games_kernel<1, true>), grid, block, 0, st, g, dev);
+    } else {
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_games_kernel<8, false>), grid, block, 0, st, g, dev);
+        else hipLaunchKernelGGL((tfe_nt_games_kernel<1, false>), grid, block, 0, st, g, dev);
+    }
+    return 0;
+}
+
+}  // namespace
+
+namespace pulse_tfe {
+
 // The cell of the board that cell `cell` of T_j(board) shows (include/pulse_env.h, "eight symmetries"): j & 3 rotations by the
 // environment's rotation (out[r][c] = in[c][3 - r]), for j >= 4 after a transpose.
 int image_cell(int j, int cell) {
@@ -238,7 +200,7 @@ int image_cell(int j, int cell) {
     return j >= 4 ? c * 4 + r : r * 4 + c;
 }
 
-// The checks of the network, shared by the four entry points; fills the kernels' form of it.
+// The checks of the network, shared by the entry points; fills the kernels' form of it.
 int check_net(const PulseTfeNtNet& n, bool need_weights, const char* name, NtDev* dev) {
     if (n.n != 4) return fail_named(name, "board side n must be 4 (the n-tuple network plays the packed 4 x 4 board)");
     if (n.n_tuples < 1 || n.n_tuples > kMaxTuples) return fail_named(name, "n_tuples must be in 1..8");
@@ -269,46 +231,22 @@ int check_net(const PulseTfeNtNet& n, bool need_weights, const char* name, NtDev
     return 0;
 }
 
-// ... and those of a batch of games (the roll-out's, the learner's and the evaluation's structs name these fields alike)
-template <class O>
-int check_batch(const O* o, const char* name) {
-    if (o->n_games < 1) return fail_named(name, "n_games must be positive");
-    if (o->max_steps < 1 || o->max_steps > 65535) return fail_named(name, "max_steps must be in 1..65535");
-    if (!(o->gamma >= 0.0 && o->gamma <= 1.0)) return fail_named(name, "gamma must be in [0, 1]");
-    if (o->reserved0 != 0) return fail_named(name, "reserved0 must be 0 (zero-initialise the struct)");
+int check_eval(const PulseTfeNtEval* o, const char* name, NtDev* dev, Games* g) {
+    if (!o) return fail_named(name, "options are null");
+    if (int rc = check_net(o->net, true, name, dev)) return rc;
+    if (int rc = check_batch(o, name)) return rc;
+    if (!(o->epsilon >= 0.0 && o->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
+    if (!o->summary) return fail_named(name, "summary is null");
+    if (!o->max_tile_hist) return fail_named(name, "max_tile_hist is null");
+    if (((uintptr_t)o->summary & 7u) || ((uintptr_t)o->max_tile_hist & 7u)) return fail_named(name, "summary / max_tile_hist must be 8-byte aligned");
+    if ((uintptr_t)o->total_score & 7u) return fail_named(name, "total_score must be 8-byte aligned");
+    if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
+    *g = games_of(o);
+    g->lengths = o->lengths; g->total_score = o->total_score; g->stats = o->summary; g->hist = o->max_tile_hist;
     return 0;
 }
 
-int check_acc(const int64_t* acc, const char* name) {
-    if (!acc) return fail_named(name, "acc is null");
-    if ((uintptr_t)acc & 15u) return fail_named(name, "acc must be 16-byte aligned");
-    return 0;
-}
-
-int launch_games(Games& g, const NtDev& dev, bool symmetric, bool record, void* stream) {
-    if (int rc = pulse::tfe_row_lut(&g.lut)) return rc;
-    const dim3 grid((unsigned)((g.n_games + kBlock - 1) / kBlock)), block(kBlock);
-    hipStream_t st = (hipStream_t)stream;
-    if (record) {
-        if (symmetric) hipLaunchKernelGGL((tfe_nt_games_kernel<8, true>), grid, block, 0, st, g, dev);
-        else hipLaunchKernelGGL((tfe_nt_games_kernel<1, true>), grid, block, 0, st, g, dev);
-    } else {
-        if (symmetric) hipLaunchKernelGGL((tfe_nt_games_kernel<8, false>), grid, block, 0, st, g, dev);
-        else hipLaunchKernelGGL((tfe_nt_games_kernel<1, false>), grid, block, 0, st, g, dev);
-    }
-    return 0;
-}
-
-template <class O>
-Games games_of(const O* o) {
-    Games g{};
-    g.weights = o->net.weights; g.n_games = o->n_games; g.max_steps = o->max_steps; g.gamma = o->gamma;
-    g.eps_q24 = (uint32_t)std::floor(o->epsilon * 16777216.0);                         // once, here: the kernel compares integers
-    g.env_seed = o->env_seed; g.agent_seed = o->agent_seed; g.tie_seed = o->tie_seed; g.board_id0 = o->board_id0; g.round = o->round;
-    return g;
-}
-
-}  // namespace
+}  // namespace pulse_tfe
 
 extern "C" int pulse_tfe_nt_rollout(const PulseTfeNtRollout* o, void* stream) {
     const char* name = "pulse_tfe_nt_rollout";
@@ -335,19 +273,9 @@ extern "C" int pulse_tfe_nt_rollout(const PulseTfeNtRollout* o, void* stream) {
 }
 
 extern "C" int pulse_tfe_nt_evaluate(const PulseTfeNtEval* o, void* stream) {
-    const char* name = "pulse_tfe_nt_evaluate";
-    if (!o) return fail_named(name, "options are null");
     NtDev dev;
-    if (int rc = check_net(o->net, true, name, &dev)) return rc;
-    if (int rc = check_batch(o, name)) return rc;
-    if (!(o->epsilon >= 0.0 && o->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
-    if (!o->summary) return fail_named(name, "summary is null");
-    if (!o->max_tile_hist) return fail_named(name, "max_tile_hist is null");
-    if (((uintptr_t)o->summary & 7u) || ((uintptr_t)o->max_tile_hist & 7u)) return fail_named(name, "summary / max_tile_hist must be 8-byte aligned");
-    if ((uintptr_t)o->total_score & 7u) return fail_named(name, "total_score must be 8-byte aligned");
-    if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
-    Games g = games_of(o);
-    g.lengths = o->lengths; g.total_score = o->total_score; g.stats = o->summary; g.hist = o->max_tile_hist;
+    Games g;
+    if (int rc = check_eval(o, "pulse_tfe_nt_evaluate", &dev, &g)) return rc;
     if (int rc = launch_games(g, dev, o->net.symmetric != 0, false, stream)) return rc;
     return finish_launch("pulse_tfe_nt_evaluate launch");
 }

@@ -4,7 +4,9 @@ a learn launch of one lane per recorded move and an apply launch over the weight
 rectangles over the board's eight images, gamma 1, epsilon 0, alpha 1.  Every `--eval-every` rounds (default: every round) it
 prints, from ONE evaluation launch of `--eval-games` games under the greedy policy on the same boards every time: the mean final
 score and its standard error, the mean length and the histogram of the largest tile.  `--save PATH` writes the non-zero weights and
-the run's state at the end, `--resume PATH` continues such a run for `--rounds` more rounds."""
+the run's state at the end, `--resume PATH` continues such a run for `--rounds` more rounds.  `--search`: every evaluation also runs
+under expectimax search one chance layer deep (section 13.1) on the same boards, and both means are printed; `--resume PATH --rounds 0
+--search` plays a saved network."""
 from __future__ import annotations
 
 import argparse
@@ -16,7 +18,7 @@ from ..agents import NTupleTDAfterstateTFEGPU
 
 
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
-        resume=None, out=print):
+        resume=None, out=print, search=False):
     if resume:
         agent = NTupleTDAfterstateTFEGPU.load(resume, device)
         want = dict(n_games=tables, alpha=float(alpha), epsilon=float(epsilon), gamma=float(gamma), max_steps=max_steps, seed=seed)
@@ -26,15 +28,29 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
     else:
         agent = NTupleTDAfterstateTFEGPU(device, tables, gamma=gamma, epsilon=epsilon, alpha=alpha, max_steps=max_steps, seed=seed)
     first, moves_before, t0 = agent.round, agent.stats()["moves"], time.perf_counter()
+
+    def under_search():
+        if not search:
+            return ""
+        e = agent.evaluate_search(n_games=eval_games)
+        return (f"; under search: Avg final score: {e['mean_score']:.1f} +- {e['std_score'] / e['games'] ** .5:.1f}, Highest: {e['max_score']}, "
+                f"Avg length: {e['mean_length']:.1f}, cut {e['truncated']}, largest tile 2^k: {e['max_tile_hist']}")
+
+    def evaluation():
+        e = agent.evaluate(n_games=eval_games)                              # (synchronises)
+        return (f"greedy policy over {e['games']} games: Avg final score: {e['mean_score']:.1f} +- {e['std_score'] / e['games'] ** .5:.1f}, "
+                f"Highest: {e['max_score']}, Avg length: {e['mean_length']:.1f}, cut {e['truncated']}, largest tile 2^k: {e['max_tile_hist']}")
+
+    if not rounds and search:
+        out(f"After {agent.round} rounds: {evaluation()}{under_search()}")
     for r in range(first, first + rounds):
         agent.learn_batch()
         if eval_every and ((r + 1) % eval_every == 0 or r + 1 == first + rounds):
-            e = agent.evaluate(n_games=eval_games)                          # (synchronises)
+            line = evaluation()
             st, now = agent.stats(), time.perf_counter()
-            out(f"Round {r}: greedy policy over {e['games']} games: Avg final score: {e['mean_score']:.1f} +- {e['std_score'] / e['games'] ** .5:.1f}, "
-                f"Highest: {e['max_score']}, Avg length: {e['mean_length']:.1f}, cut {e['truncated']}, largest tile 2^k: {e['max_tile_hist']}; "
+            out(f"Round {r}: {line}; "
                 f"training: Avg final score {agent.total_score.double().mean().item():.1f}, moves/sec {(st['moves'] - moves_before) / (now - t0):.0f}, "
-                f"skipped {st['skipped']}, clamped {st['clamped']}")
+                f"skipped {st['skipped']}, clamped {st['clamped']}{under_search()}")
             moves_before, t0 = st["moves"], time.perf_counter()
     if save:
         agent.save(save)
@@ -54,9 +70,10 @@ def main(argv=None):
     ap.add_argument("--eval-games", type=int, help="games per evaluation (default: --tables)")
     ap.add_argument("--save", metavar="PATH", help="write the non-zero weights and the run's state to this .npz at the end")
     ap.add_argument("--resume", metavar="PATH", help="continue the run saved there (the same --tables, --alpha, --epsilon, --gamma, --max-steps, --seed)")
+    ap.add_argument("--search", action="store_true", help="every evaluation also under expectimax search, one chance layer deep")
     args = ap.parse_args(argv)
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
-                args.eval_games, args.save, args.resume)
+                args.eval_games, args.save, args.resume, search=args.search)
     st = agent.stats()
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
           f"{int((agent.weights_dev != 0).sum().item())} of {agent.n_weights} weights are not zero")

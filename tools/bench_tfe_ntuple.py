@@ -8,7 +8,11 @@ Per state --warmup W (2) untimed rounds, then --repeats R (5) timed ones; the ro
 their own pair of HIP events; min / median / max of each, the moves per round beside them, moves/s of the roll-out and of the learn
 launch, 16-byte accumulator atomics/s of the learn launch (2 F per move) and bytes/s of the apply launch (20 bytes per weight read,
 20 written where touched: only the read side is counted).  Then the evaluation launch on the weights the rounds left, --repeats
-times after one untimed call.  max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes).  Lines are also
+times after one untimed call.  --search: per B and per --search-games G (1,024: few wavefronts, the time of the longest game; 65,536: every compute unit busy) one more
+line, {"search": ...}: G games on the weights the rounds left
+from the default evaluation boards under the one-ply policy and under expectimax search one chance layer deep (DESIGN.md section
+13.1), each launch between its own HIP events in the same process, --repeats times after one untimed call: seconds, moves, seconds
+per move (a move = one move of one game; the launch's time over all the moves it played) and the ratio of the two.  max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes).  Lines are also
 appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
 import argparse
 import json
@@ -48,6 +52,30 @@ def _timed_evaluate(agent, torch):
     return ev[0].elapsed_time(ev[1]) * 1e-3, agent.eval_counters()
 
 
+def search_line(agent, torch, games, repeats):
+    """the evaluation launch under both policies on the same weights and boards"""
+    out = {}
+    for name, launch in (("one_ply", agent.evaluate_launch), ("search", agent.evaluate_search_launch)):
+        agent.eval_counters(clear=True)
+        launch(games)                                                       # untimed: the kernel's code object
+        torch.cuda.synchronize()
+        seconds = []
+        for _ in range(repeats):
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            agent.eval_counters(clear=True)
+            ev[0].record()
+            launch(games)
+            ev[1].record()
+            ev[1].synchronize()
+            seconds.append(ev[0].elapsed_time(ev[1]) * 1e-3)
+        e, s = agent.eval_counters(), _spread(seconds)
+        out[name] = {"seconds": s, "moves": e["moves"], "seconds_per_move": s["median"] / e["moves"], "mean_score": e["mean_score"],
+                     "std_score": e["std_score"], "mean_length": e["mean_length"], "truncated": e["truncated"]}
+    return {"search": {"games": games, "trained_rounds": agent.round, "train_games": agent.n_games, "max_steps": agent.max_steps, "repeats": repeats, **out,
+                       "seconds_per_move_ratio": out["search"]["seconds_per_move"] / out["one_ply"]["seconds_per_move"],
+                       "seconds_ratio": out["search"]["seconds"]["median"] / out["one_ply"]["seconds"]["median"]}}
+
+
 def state_line(agent, torch, state, trained_rounds, warmup, repeats):
     agent.clear()
     for _ in range(trained_rounds if state == "trained" else 0):
@@ -85,6 +113,8 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--max-steps", type=int, default=4096)
+    ap.add_argument("--search", action="store_true", help="one more line per B: the evaluation under search beside the one-ply one")
+    ap.add_argument("--search-games", type=int, nargs="+", default=[1024, 65536])
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
     args = ap.parse_args(argv)
     import torch
@@ -102,6 +132,8 @@ def main(argv=None):
         else:
             agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=args.max_steps, seed=0)
             lines = [state_line(agent, torch, s, args.trained_rounds, args.warmup, args.repeats) for s in args.states]
+            if args.search:                                                 # on the weights the last state left
+                lines += [search_line(agent, torch, g, args.repeats) for g in args.search_games]
             del agent
             torch.cuda.empty_cache()
         for line in lines:
