@@ -788,6 +788,38 @@ typedef struct PulseTfeNtEval {
 } PulseTfeNtEval;
 int pulse_tfe_nt_evaluate(const PulseTfeNtEval* o, void* stream);
 
+/* ---- the n-tuple network's TD(lambda) learner: pulse_tfe_nt_learn with lambda-differences in place of one-step differences, on the
+ * same recorded games and into the same accumulators; pulse_tfe_nt_apply follows as it does there.  Everything is float64, one
+ * rounding per operation.  For game g let L = min(lengths[g], max_steps), moves t = 0 .. L - 1.
+ *   delta_t  = pulse_tfe_nt_learn's one-step difference, unclamped: 0 - V_t at the last move with its terminal bit,
+ *              (r_{t+1} + gamma * V_{t+1}) - V_t at any other; the last move without its terminal bit is SKIPPED as it is there
+ *              (it adds nothing, is counted in stats[2]) and its lambda-difference is +0.0;
+ *   gl       = gamma * lambda, one multiply, formed once;
+ *   D_{L-1}  = delta_{L-1}, or +0.0 if that move is skipped;   D_t = delta_t + gl * D_{t+1}, one multiply and one add.
+ * The recurrence carries the UNCLAMPED D.  Where a move is added, D_t is clamped to +-PULSE_TFE_NT_DELTA_MAX (counted in stats[4]),
+ * d = llrint(ldexp(D_t, PULSE_TFE_NT_FRAC_BITS)), and for every feature of keys[t]: acc[index].sum += d, acc[index].cnt += 1, the
+ * adds and the counters stats[1], [2], [4] of pulse_tfe_nt_learn.  At lambda = 0 acc is pulse_tfe_nt_learn's.
+ * Two launches on the stream: one lane per game walks t downwards and writes deltas[t * n_games + g] = D_t for t < L (rows at and
+ * beyond L are not written); one lane per recorded move then adds.  deltas: device float64[max_steps * n_games], step-major like
+ * values, caller-owned scratch that holds the round's D afterwards.
+ *
+ * PULSE_EINVAL, before anything is launched: pulse_tfe_nt_learn's refusals; lambda outside [0, 1] (NaN included); deltas null or not
+ * 8-byte aligned. */
+typedef struct PulseTfeNtLearnLambda {
+    PulseTfeNtNet net;                  /* weights may be NULL */
+    int32_t n_games, max_steps;
+    double gamma, lambda;
+    const uint64_t* keys;
+    const double* values;
+    const uint8_t* steps;
+    const int32_t* lengths;
+    double* deltas;                     /* float64[max_steps * n_games] */
+    int64_t* acc;                       /* int64[n_weights][2] */
+    int64_t* stats;                     /* int64[8] */
+    int64_t reserved0;
+} PulseTfeNtLearnLambda;
+int pulse_tfe_nt_learn_lambda(const PulseTfeNtLearnLambda* o, void* stream);
+
 /* ---- the n-tuple network under expectimax search, one chance layer deep: the same network asked about the boards AFTER the random
  * tile.  Everything is float64, one rounding per operation.  For a board B and a = 0..3, (B_a, score_a), r_a, V and "candidate"
  * (B_a != B) are pulse_tfe_nt_rollout's.  For a candidate a the CHANCE BOARDS of B_a are C(c, k) = B_a with nibble k at the empty cell

@@ -166,6 +166,11 @@ class TfeNtLearn(C.Structure):
         (n, C.c_void_p) for n in ("keys", "values", "steps", "lengths", "acc", "stats")] + [("reserved0", C.c_int64)]
 
 
+class TfeNtLearnLambda(C.Structure):
+    _fields_ = [("net", TfeNtNet), ("n_games", C.c_int32), ("max_steps", C.c_int32), ("gamma", C.c_double), ("lam", C.c_double)] + [
+        (n, C.c_void_p) for n in ("keys", "values", "steps", "lengths", "deltas", "acc", "stats")] + [("reserved0", C.c_int64)]
+
+
 class TfeNtApply(C.Structure):
     _fields_ = [("net", TfeNtNet), ("step", C.c_double), ("acc", C.c_void_p), ("reserved0", C.c_int64)]
 
@@ -243,6 +248,7 @@ SYMBOLS = {
     "pulse_tfe_mc_table_fold_after": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_rollout": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_learn": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_learn_lambda": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_apply": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_evaluate": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_search": (C.c_int, [_P, _P]),

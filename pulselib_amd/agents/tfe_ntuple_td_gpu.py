@@ -1,4 +1,5 @@
-"""2048 on 4 x 4: an n-tuple network trained by batch TD(0) on afterstates, on the device (csrc/tfe_ntuple.hip).
+"""2048 on 4 x 4: an n-tuple network trained by batch TD(0) -- or, with `lam`, TD(lambda) -- on afterstates, on the device (DESIGN.md
+sections 13 and 13.2; csrc/tfe_ntuple.hip, csrc/tfe_ntuple_lambda.hip).
 
 The value of an afterstate -- the board after the move and before the spawn -- is the sum of a few lookup tables.  Each table is
 indexed by the tiles (4-bit log2, the state key's nibbles) on a fixed set of cells, read on the board's eight images under the
@@ -8,11 +9,13 @@ moves that change the board, and records per move the afterstate's key, its V an
 recorded move and adds the temporal difference reward' + gamma * V' - V (0 - V at a terminal move) as a fixed-point integer into
 {sum, cnt} of every weight the afterstate reads; `pulse_tfe_nt_apply` moves every visited weight by alpha / F of the MEAN of its
 adds and zeroes the accumulators.  `pulse_tfe_nt_evaluate` plays games without a trajectory and reduces the scores in the launch; `pulse_tfe_nt_search` and
-`pulse_tfe_nt_evaluate_search` play under expectimax search one chance layer deep (section 13.1), 32 lanes per board.
+`pulse_tfe_nt_evaluate_search` play under expectimax search one chance layer deep (section 13.1), 32 lanes per board.  With `lam > 0`
+the learn launch is `pulse_tfe_nt_learn_lambda` (section 13.2): one lane per game walks the recorded game backwards and leaves the
+lambda-differences D_t = delta_t + gamma * lam * D_{t+1} in `deltas`, and the same one-lane-per-move adds follow with D_t for delta_t.
 
 The policy of a round is frozen (the weights are only read by the roll-out) and the adds are integers, so a round's result does not
-depend on scheduling: `feature_cells_on_host`, `value_on_host`, `greedy_nt_on_host`, `search_nt_on_host`, `learn_nt_on_host` and `apply_nt_on_host` are
-the host's statement of the same arithmetic in numpy, vectorised over boards, and the device is held to them word for word."""
+depend on scheduling: `feature_cells_on_host`, `value_on_host`, `greedy_nt_on_host`, `search_nt_on_host`, `learn_nt_on_host`,
+`lambda_deltas_on_host`, `learn_lambda_nt_on_host` and `apply_nt_on_host` are the host's statement of the same arithmetic in numpy, vectorised over boards, and the device is held to them word for word."""
 from __future__ import annotations
 
 import functools
@@ -28,7 +31,8 @@ MAX_TUPLES, MAX_LEN, FRAC_BITS, DELTA_MAX = _native.TFE_NT_MAX_TUPLES, _native.T
 DEFAULT_TUPLES = ((0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))       # two rows and two 2 x 3 rectangles
 STATS = ("moves", "learnt", "skipped", "truncated", "clamped")                                # words 0..4 of the stats buffer
 EVAL_SUMMARY = ("games", "moves", "score_sum", "score_sq_sum", "max_score", "truncated", "moves_greedy", "tile_capped")
-CHECKPOINT_VERSION = 1
+CHECKPOINT_VERSION = 1                                                                        # what an agent with lam == 0 writes
+CHECKPOINT_VERSION_LAMBDA = 2                                                                 # ... and with lam != 0: version 1's arrays and `lam`
 CHECKPOINT_SCALARS = ("symmetric", "gamma", "epsilon", "alpha", "max_steps", "seed", "board_id0", "round", "n_games")
 _U64 = np.uint64
 
@@ -45,6 +49,14 @@ def check_tuples(tuples) -> tuple:
         if any(not 0 <= c <= 15 for c in t) or len(set(t)) != len(t):
             raise ValueError("a tuple's cells must be distinct and in 0..15")
     return tuples
+
+
+def check_lam(lam) -> float:
+    """lambda as a float, after the library's own check (ValueError outside [0, 1]; NaN is outside)."""
+    lam = float(lam)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError("lam must be in [0, 1]")
+    return lam
 
 
 def tuple_offsets(tuples):
@@ -206,6 +218,50 @@ def learn_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: flo
     return dict(learnt=int(learn.sum()), skipped=int(skipped.sum()), clamped=int(clamped.sum()))
 
 
+def lambda_deltas_on_host(values, steps, lengths, gamma: float, lam: float) -> np.ndarray:
+    """float64[T, B]: the lambda-differences pulse_tfe_nt_learn_lambda writes, operation for operation.  values float64[T, B], steps
+    uint8[T, B], lengths int[B] (a game has min(lengths[g], T) moves).  gl = gamma * lam (one multiply); at a game's last move
+    D = 0 - values[t] with its terminal bit and +0.0 without (the move is skipped); at any other D_t = ((reward(steps[t + 1]) + gamma *
+    values[t + 1]) - values[t]) + gl * D_{t+1}, unclamped.  Rows at or beyond a game's length are returned as 0 (the device does
+    not write them: they keep what `deltas` held)."""
+    values, steps = np.asarray(values, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
+    T = values.shape[0]
+    L = np.minimum(np.asarray(lengths, dtype=np.int64).reshape(-1), T)
+    gamma, gl = np.float64(gamma), np.float64(gamma) * np.float64(lam)
+    out, carried = np.zeros(values.shape, dtype=np.float64), np.zeros(values.shape[1], dtype=np.float64)
+    for t in range(int(L.max()) - 1 if L.size else -1, -1, -1):
+        last, played = t == L - 1, t < L
+        nxt = t + 1 if t + 1 < T else t                                    # (row T does not exist; a move at T - 1 is a last move)
+        target = np.where(last, 0.0, ((steps[nxt] >> 2) & 31).astype(np.float64) + gamma * values[nxt])
+        delta = target - values[t]
+        with np.errstate(all="ignore"):                                    # (what a lane computes on rows beyond its game is not used)
+            through = delta + gl * carried
+        carried = np.where(last, np.where(steps[t] >> 7 != 0, delta, 0.0), through)
+        carried = np.where(played, carried, 0.0)
+        out[t] = carried
+    return out
+
+
+def learn_lambda_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, lam: float, acc) -> dict:
+    """pulse_tfe_nt_learn_lambda on the host: learn_nt_on_host with lambda_deltas_on_host's D_t in place of the one-step difference.
+    The skipped moves, the clamp to +-DELTA_MAX (applied to the add only: the recurrence carries the unclamped D), d and the adds are
+    learn_nt_on_host's.  Returns dict(learnt, skipped, clamped, deltas float64[T, B])."""
+    keys, values, steps = np.asarray(keys, dtype=_U64), np.asarray(values, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    deltas = lambda_deltas_on_host(values, steps, lengths, gamma, lam)
+    t = np.arange(keys.shape[0], dtype=np.int64)[:, None]
+    played, last = t < lengths[None, :], t == np.minimum(lengths, keys.shape[0])[None, :] - 1
+    skipped = played & last & (steps >> 7 == 0)
+    learn = played & ~skipped
+    delta = deltas[learn]
+    clamped = np.abs(delta) > DELTA_MAX
+    d = np.rint(np.ldexp(np.clip(delta, -DELTA_MAX, DELTA_MAX), FRAC_BITS)).astype(np.int64)
+    idx = feature_indices_on_host(keys[learn], tuples, symmetric)
+    np.add.at(acc[:, 0], idx.reshape(-1), np.repeat(d, idx.shape[1]))
+    np.add.at(acc[:, 1], idx.reshape(-1), 1)
+    return dict(learnt=int(learn.sum()), skipped=int(skipped.sum()), clamped=int(clamped.sum()), deltas=deltas)
+
+
 def apply_nt_on_host(weights, acc, step: float) -> int:
     """pulse_tfe_nt_apply on the host, in place: where cnt > 0, w = float32(float64(w) + step * ((sum / cnt) * 2^-16)), one rounding per
     operation, and the two accumulator words become 0.  Returns the number of weights moved."""
@@ -222,10 +278,11 @@ def eval_summary_on_host(words) -> dict:
 
 
 # ------------------------------------------------------------------ the checkpoint file
-def write_checkpoint(path, weights, tuples, **scalars) -> None:
+def write_checkpoint(path, weights, tuples, lam=0.0, **scalars) -> None:
     """The network as an .npz of plain arrays (np.savez, no pickles): the non-zero weights as index int64[m] (ascending) and value
     float32[m], the tuples as tuple_len int64[n_tuples] and tuple_cells int64[n_tuples, 6] (-1 beyond a tuple's length), the scalars of
-    CHECKPOINT_SCALARS as 0-d arrays and `version`.  `path` is written as given."""
+    CHECKPOINT_SCALARS as 0-d arrays and `version`.  lam == 0 writes exactly that, as version 1; any other `lam` adds a 0-d float64
+    `lam` and writes version 2.  `path` is written as given."""
     if sorted(scalars) != sorted(CHECKPOINT_SCALARS):
         raise ValueError(f"a checkpoint holds exactly the scalars {CHECKPOINT_SCALARS}")
     weights = np.asarray(weights, dtype=np.float32).reshape(-1)
@@ -235,22 +292,29 @@ def write_checkpoint(path, weights, tuples, **scalars) -> None:
         cells[i, :len(t)] = t
     dtypes = dict(gamma=np.float64, epsilon=np.float64, alpha=np.float64, seed=np.uint64, board_id0=np.uint64)
     arrays = {k: np.array(scalars[k], dtype=dtypes.get(k, np.int64)) for k in CHECKPOINT_SCALARS}
+    version = CHECKPOINT_VERSION
+    if float(lam) != 0.0:
+        arrays["lam"], version = np.array(lam, dtype=np.float64), CHECKPOINT_VERSION_LAMBDA
     with open(path, "wb") as fh:
-        np.savez(fh, version=np.array(CHECKPOINT_VERSION, dtype=np.int64), index=index.astype(np.int64), value=weights[index],
+        np.savez(fh, version=np.array(version, dtype=np.int64), index=index.astype(np.int64), value=weights[index],
                  tuple_len=np.array([len(t) for t in tuples], dtype=np.int64), tuple_cells=cells, **arrays)
 
 
 def read_checkpoint(path) -> dict:
-    """What write_checkpoint wrote (np.load with allow_pickle=False): `tuples`, `index`, `value`, `n_weights` and the scalars as
-    Python numbers.  ValueError for another format version, a missing array, tuples the library would refuse or an index outside
+    """What write_checkpoint wrote (np.load with allow_pickle=False), version 1 or 2: `tuples`, `index`, `value`, `n_weights`, the
+    scalars as Python numbers and `lam` (0.0 for version 1).  ValueError for another format version, a missing array, tuples the library would refuse or an index outside
     the network."""
     with np.load(path, allow_pickle=False) as f:
         missing = [k for k in ("version", "index", "value", "tuple_len", "tuple_cells") + CHECKPOINT_SCALARS if k not in f.files]
         if missing:
             raise ValueError(f"{path}: not an n-tuple network checkpoint (no {missing})")
-        if int(f["version"]) != CHECKPOINT_VERSION:
-            raise ValueError(f"{path}: format version {int(f['version'])}, this package reads {CHECKPOINT_VERSION}")
+        version = int(f["version"])
+        if version not in (CHECKPOINT_VERSION, CHECKPOINT_VERSION_LAMBDA):
+            raise ValueError(f"{path}: format version {version}, this package reads {CHECKPOINT_VERSION} and {CHECKPOINT_VERSION_LAMBDA}")
+        if version == CHECKPOINT_VERSION_LAMBDA and "lam" not in f.files:
+            raise ValueError(f"{path}: not an n-tuple network checkpoint (no ['lam'])")
         out = {k: (float(f[k]) if k in ("gamma", "epsilon", "alpha") else int(f[k])) for k in CHECKPOINT_SCALARS}
+        out["lam"] = float(f["lam"]) if version == CHECKPOINT_VERSION_LAMBDA else 0.0
         index, value, lens, cells = f["index"], f["value"], f["tuple_len"], f["tuple_cells"]
     out["symmetric"] = bool(out["symmetric"])
     out["tuples"] = check_tuples([cells[i, :int(n)].tolist() for i, n in enumerate(lens.tolist())])
@@ -274,12 +338,14 @@ def weights_of_checkpoint(f: dict) -> np.ndarray:
 class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     """`learn_batch` = `rollout` + `learn` + `apply` + `round += 1`: three launches and no synchronisation.  Everything that reads
     back (`weights`, `stats`, `trajectory`, `evaluate`, the per-game arrays' `.cpu()`) synchronises.  Round r plays the boards
-    board_id0 + r * n_games + g, so no two rounds replay the same spawns."""
+    board_id0 + r * n_games + g, so no two rounds replay the same spawns.  `lam` > 0: `learn` is the TD(lambda) launch and the agent
+    holds `deltas`, float64 in the shape of `values`; `lam` = 0 (the default) allocates nothing more and learns by TD(0)."""
     STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
 
     def __init__(self, device, n_games, tuples=DEFAULT_TUPLES, symmetric=True, gamma=1.0, epsilon=0.0, alpha=1.0, max_steps=4096, seed=0,
-                 board_id0=0):
+                 board_id0=0, lam=0.0):
         import torch
+        self.lam = check_lam(lam)
         super().__init__(device, n_games, 4, max_steps, gamma, epsilon, seed, board_id0)
         self.tuples, self.symmetric, self.alpha = check_tuples(tuples), bool(symmetric), float(alpha)
         self.n_features = len(self.tuples) * (8 if self.symmetric else 1)
@@ -289,6 +355,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         self.weights_dev = torch.zeros(self.n_weights, dtype=torch.float32, device=self.device)
         self.acc = torch.zeros((self.n_weights, 2), dtype=torch.int64, device=self.device)            # {sum, cnt}; torch allocations are 16-byte aligned
         self.values = torch.zeros((self.max_steps, self.n_games), dtype=torch.float64, device=self.device)
+        self.deltas = torch.zeros_like(self.values) if self.lam > 0.0 else None
 
     # ------------------------------------------------------------------ the launches
     def _net(self, net):
@@ -310,13 +377,30 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         return self._launch("pulse_tfe_nt_rollout", o)
 
     def learn(self):
-        """One launch: the temporal differences of the games last played, into the accumulators."""
+        """The temporal differences of the games last played, into the accumulators: one launch, or with lam > 0
+        learn_lambda_launch's two."""
+        if self.lam > 0.0:
+            return self.learn_lambda_launch(self.lam)
         o = _native.TfeNtLearn()
         self._net(o.net)
         o.n_games, o.max_steps, o.gamma = self.n_games, self.max_steps, self.gamma
         o.keys, o.values, o.steps, o.lengths = self.keys.data_ptr(), self.values.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr()
         o.acc, o.stats = self.acc.data_ptr(), self.counters.data_ptr()
         return self._launch("pulse_tfe_nt_learn", o)
+
+    def learn_lambda_launch(self, lam):
+        """pulse_tfe_nt_learn_lambda on the games last played, whatever the agent's own `lam`: the backward walk into `deltas`
+        (allocated here if the agent has none) and the adds of the lambda-differences into the accumulators."""
+        import torch
+        lam = check_lam(lam)
+        if self.deltas is None:
+            self.deltas = torch.zeros_like(self.values)
+        o = _native.TfeNtLearnLambda()
+        self._net(o.net)
+        o.n_games, o.max_steps, o.gamma, o.lam = self.n_games, self.max_steps, self.gamma, lam
+        o.keys, o.values, o.steps, o.lengths = self.keys.data_ptr(), self.values.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr()
+        o.deltas, o.acc, o.stats = self.deltas.data_ptr(), self.acc.data_ptr(), self.counters.data_ptr()
+        return self._launch("pulse_tfe_nt_learn_lambda", o)
 
     def apply(self):
         """One launch: every visited weight moves by alpha / F of the mean of its adds; the accumulators are zero afterwards."""
@@ -392,19 +476,27 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         T, lengths = self._played()
         return self.keys[:T].cpu().numpy().view(np.uint64), self.values[:T].cpu().numpy(), self.steps[:T].cpu().numpy(), lengths
 
+    def trajectory_deltas(self) -> np.ndarray:
+        """float64[T, B]: the lambda-differences of the last TD(lambda) learn launch, T = the longest game; rows at and beyond a game's
+        length hold whatever `deltas` held before."""
+        if self.deltas is None:
+            raise ValueError("no TD(lambda) launch has run: the agent holds no deltas")
+        T, _ = self._played()
+        return self.deltas[:T].cpu().numpy()
+
     def save(self, path):
         """The non-zero weights and what a continued run needs as an .npz (write_checkpoint)."""
         write_checkpoint(path, self.weights(), self.tuples, symmetric=int(self.symmetric), gamma=self.gamma, epsilon=self.epsilon, alpha=self.alpha,
-                         max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games)
+                         max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games, lam=self.lam)
 
     @classmethod
     def load(cls, path, device, n_games=None):
-        """The agent save() wrote: weights, round and seeds restored.  With the saved n_games it continues the run the saved agent would
+        """The agent save() wrote: weights, round, seeds and lam restored.  With the saved n_games it continues the run the saved agent would
         have continued (another n_games plays other boards: round r starts at board_id0 + r * n_games)."""
         import torch
         f = read_checkpoint(path)
         agent = cls(device, f["n_games"] if n_games is None else n_games, tuples=f["tuples"], symmetric=f["symmetric"], gamma=f["gamma"],
-                    epsilon=f["epsilon"], alpha=f["alpha"], max_steps=f["max_steps"], seed=f["seed"], board_id0=f["board_id0"])
+                    epsilon=f["epsilon"], alpha=f["alpha"], max_steps=f["max_steps"], seed=f["seed"], board_id0=f["board_id0"], lam=f["lam"])
         agent.weights_dev.copy_(torch.from_numpy(weights_of_checkpoint(f)))
         agent.round = f["round"]
         return agent

@@ -130,23 +130,10 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_learn_kernel(const PulseTfeNtLe
                 atomicAdd(&wg[1], 1ull);                                                // LDS
             } else {
                 double target = 0.0;
-                if (!last) target = __dadd_rn((double)((o.steps[at + B] >> 2) & 31u), __dmul_rn(o.gamma, o.values[at + B]));
-                double delta = __dsub_rn(target, o.values[at]);
-                const bool clamp = delta > PULSE_TFE_NT_DELTA_MAX || delta < -PULSE_TFE_NT_DELTA_MAX;
-                delta = delta > PULSE_TFE_NT_DELTA_MAX ? PULSE_TFE_NT_DELTA_MAX : (delta < -PULSE_TFE_NT_DELTA_MAX ? -PULSE_TFE_NT_DELTA_MAX : delta);
-                const unsigned long long d = (unsigned long long)llrint(ldexp(delta, PULSE_TFE_NT_FRAC_BITS));
-                const uint64_t key = o.keys[at];
-                unsigned long long* acc = reinterpret_cast<unsigned long long*>(o.acc);
-#pragma unroll 1
-                for (int tu = 0; tu < net.n_tuples; ++tu) {
-                    const uint32_t mask = net.mask[tu], offset = net.offset[tu];
-#pragma unroll
-                    for (int j = 0; j < IMG; ++j) {
-                        const size_t idx = (size_t)feature_index(key, net.shifts[tu * IMG + j], mask, offset);
-                        atomicAdd(acc + 2 * idx, d);
-                        atomicAdd(acc + 2 * idx + 1, 1ull);
-                    }
-                }
+                if (!last) target = td_target(o.steps[at + B], o.values[at + B], o.gamma);
+                bool clamp;
+                const unsigned long long d = td_fixed(__dsub_rn(target, o.values[at]), clamp);
+                add_features<IMG>(net, reinterpret_cast<unsigned long long*>(o.acc), o.keys[at], d);
                 atomicAdd(&wg[0], 1ull);
                 if (clamp) atomicAdd(&wg[2], 1ull);
             }
@@ -166,12 +153,6 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_apply_kernel(float* __restrict_
         weights[i] = (float)__dadd_rn((double)weights[i], __dmul_rn(step, mean));
         acc[i] = make_longlong2(0, 0);
     }
-}
-
-int check_acc(const int64_t* acc, const char* name) {
-    if (!acc) return fail_named(name, "acc is null");
-    if ((uintptr_t)acc & 15u) return fail_named(name, "acc must be 16-byte aligned");
-    return 0;
 }
 
 int launch_games(Games& g, const NtDev& dev, bool symmetric, bool record, void* stream) {

@@ -1,6 +1,7 @@
 // tfe_ntuple_device.h -- what the units of the 2048 n-tuple network share (tfe_ntuple.hip: the learner's four launches; tfe_ntuple_search.hip:
-// expectimax play): the network as the kernels take it, a feature's index, V of four afterstates at once, the 32,768-tile test, the
-// game loops' parameters and the host's checks of the network and of a batch of games.  One copy each.  Not part of the ABI.
+// expectimax play; tfe_ntuple_lambda.hip: the TD(lambda) learner): the network as the kernels take it, a feature's index, V of four
+// afterstates at once, the learners' target, fixed-point difference and adds, the 32,768-tile test, the game loops' parameters and
+// the host's checks of the network, of the accumulators and of a batch of games.  One copy each.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,6 +61,34 @@ __device__ __forceinline__ void values4(const NtDev& net, const float* __restric
     }
 }
 
+// What the learners share (tfe_ntuple.hip: batch TD(0); tfe_ntuple_lambda.hip: TD(lambda)).  The one-step target of a move that is
+// not its game's last, from the next move's byte and value ...
+__device__ __forceinline__ double td_target(const uint32_t next_step, const double next_value, const double gamma) {
+    return __dadd_rn((double)((next_step >> 2) & 31u), __dmul_rn(gamma, next_value));
+}
+
+// ... a difference clamped to +-PULSE_TFE_NT_DELTA_MAX (`clamp`: it was outside) as the fixed-point integer the accumulators hold ...
+__device__ __forceinline__ unsigned long long td_fixed(double delta, bool& clamp) {
+    clamp = delta > PULSE_TFE_NT_DELTA_MAX || delta < -PULSE_TFE_NT_DELTA_MAX;
+    delta = delta > PULSE_TFE_NT_DELTA_MAX ? PULSE_TFE_NT_DELTA_MAX : (delta < -PULSE_TFE_NT_DELTA_MAX ? -PULSE_TFE_NT_DELTA_MAX : delta);
+    return (unsigned long long)llrint(ldexp(delta, PULSE_TFE_NT_FRAC_BITS));
+}
+
+// ... and its adds: sum += d, cnt += 1 at every feature of `key`
+template <int IMG>
+__device__ __forceinline__ void add_features(const NtDev& net, unsigned long long* acc, const uint64_t key, const unsigned long long d) {
+#pragma unroll 1
+    for (int tu = 0; tu < net.n_tuples; ++tu) {
+        const uint32_t mask = net.mask[tu], offset = net.offset[tu];
+#pragma unroll
+        for (int j = 0; j < IMG; ++j) {
+            const size_t idx = (size_t)feature_index(key, net.shifts[tu * IMG + j], mask, offset);
+            atomicAdd(acc + 2 * idx, d);
+            atomicAdd(acc + 2 * idx + 1, 1ull);
+        }
+    }
+}
+
 __device__ __forceinline__ bool has_nibble15(const PackedBoard p) {
     const uint32_t l = p.lo & (p.lo >> 1) & (p.lo >> 2) & (p.lo >> 3), h = p.hi & (p.hi >> 1) & (p.hi >> 2) & (p.hi >> 3);
     return ((l | h) & 0x11111111u) != 0u;
@@ -97,6 +126,13 @@ int check_batch(const O* o, const char* name) {
     if (o->max_steps < 1 || o->max_steps > 65535) return fail_named(name, "max_steps must be in 1..65535");
     if (!(o->gamma >= 0.0 && o->gamma <= 1.0)) return fail_named(name, "gamma must be in [0, 1]");
     if (o->reserved0 != 0) return fail_named(name, "reserved0 must be 0 (zero-initialise the struct)");
+    return 0;
+}
+
+// ... and of the accumulators
+inline int check_acc(const int64_t* acc, const char* name) {
+    if (!acc) return fail_named(name, "acc is null");
+    if ((uintptr_t)acc & 15u) return fail_named(name, "acc must be 16-byte aligned");
     return 0;
 }
 

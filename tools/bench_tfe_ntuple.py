@@ -12,7 +12,10 @@ times after one untimed call.  --search: per B and per --search-games G (1,024: 
 line, {"search": ...}: G games on the weights the rounds left
 from the default evaluation boards under the one-ply policy and under expectimax search one chance layer deep (DESIGN.md section
 13.1), each launch between its own HIP events in the same process, --repeats times after one untimed call: seconds, moves, seconds
-per move (a move = one move of one game; the launch's time over all the moves it played) and the ratio of the two.  max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes).  Lines are also
+per move (a move = one move of one game; the launch's time over all the moves it played) and the ratio of the two.  --lambda L: per B one more line, {"lambda": ...}: on the games of the last timed round, in the same
+process and back to back, the TD(0) learn launch (pulse_tfe_nt_learn) and the TD(lambda) launch (pulse_tfe_nt_learn_lambda: the backward
+walk and the adds) each between its own pair of HIP events, --warmup untimed pairs and then --repeats timed ones, alternating; the
+accumulators are zeroed, untimed, before every launch, so both add the same moves into empty cells.  max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes).  Lines are also
 appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
 import argparse
 import json
@@ -76,6 +79,30 @@ def search_line(agent, torch, games, repeats):
                        "seconds_ratio": out["search"]["seconds"]["median"] / out["one_ply"]["seconds"]["median"]}}
 
 
+def lambda_line(agent, torch, lam, warmup, repeats):
+    """the two learn launches on the games the agent last recorded (the agent's own lam is 0: learn() is the TD(0) launch)"""
+    launches = (("learn", agent.learn), ("learn_lambda", lambda: agent.learn_lambda_launch(lam)))
+    seconds = {name: [] for name, _ in launches}
+    before = agent.stats()
+    for i in range(warmup + repeats):
+        for name, launch in launches:
+            agent.acc.zero_()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            launch()
+            ev[1].record()
+            ev[1].synchronize()
+            if i >= warmup:
+                seconds[name].append(ev[0].elapsed_time(ev[1]) * 1e-3)
+    agent.acc.zero_()
+    moves = (agent.stats()["learnt"] - before["learnt"]) // (2 * (warmup + repeats))
+    td0, tdl = _spread(seconds["learn"]), _spread(seconds["learn_lambda"])
+    return {"lambda": {"games": agent.n_games, "lambda": lam, "gamma": agent.gamma, "trained_rounds": agent.round, "max_steps": agent.max_steps,
+                       "warmup": warmup, "repeats": repeats, "moves_learnt": moves, "learn_s": td0, "learn_lambda_s": tdl,
+                       "overhead_s": tdl["median"] - td0["median"], "ratio": tdl["median"] / td0["median"], "walk_bytes": 17 * moves,
+                       "atomics": 2 * agent.n_features * moves}}
+
+
 def state_line(agent, torch, state, trained_rounds, warmup, repeats):
     agent.clear()
     for _ in range(trained_rounds if state == "trained" else 0):
@@ -115,6 +142,7 @@ def main(argv=None):
     ap.add_argument("--max-steps", type=int, default=4096)
     ap.add_argument("--search", action="store_true", help="one more line per B: the evaluation under search beside the one-ply one")
     ap.add_argument("--search-games", type=int, nargs="+", default=[1024, 65536])
+    ap.add_argument("--lambda", dest="lam", type=float, help="one more line per B: the TD(lambda) learn launch beside the TD(0) one, on the same games")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
     args = ap.parse_args(argv)
     import torch
@@ -125,7 +153,7 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     for games in args.games:
-        need = 20 * tuple_offsets(DEFAULT_TUPLES)[1] + 17 * games * args.max_steps + 64 * games
+        need = 20 * tuple_offsets(DEFAULT_TUPLES)[1] + (17 if args.lam is None else 25) * games * args.max_steps + 64 * games
         free = torch.cuda.mem_get_info(dev)[0]
         if need > 0.9 * free:
             lines = [{"games": games, "skipped": f"needs {need} bytes of device memory, {free} are free"}]
@@ -134,6 +162,8 @@ def main(argv=None):
             lines = [state_line(agent, torch, s, args.trained_rounds, args.warmup, args.repeats) for s in args.states]
             if args.search:                                                 # on the weights the last state left
                 lines += [search_line(agent, torch, g, args.repeats) for g in args.search_games]
+            if args.lam is not None:                                        # on the games the last timed round recorded
+                lines.append(lambda_line(agent, torch, args.lam, args.warmup, args.repeats))
             del agent
             torch.cuda.empty_cache()
         for line in lines:
