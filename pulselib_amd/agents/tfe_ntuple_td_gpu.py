@@ -193,29 +193,36 @@ def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
 
 
 # ------------------------------------------------------------------ the learner and the apply launch
-def learn_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, acc):
-    """pulse_tfe_nt_learn on the host.  keys uint64[T, B], values float64[T, B], steps uint8[T, B], lengths int[B]; acc int64[W, 2] =
-    {sum, cnt}, added to in place.  Move (t, g), t < lengths[g]: the last move of a game has target 0 with its terminal bit and is
-    skipped without; any other has target = reward(steps[t + 1]) + gamma * values[t + 1]; delta = target - values[t] clamped to
-    +-DELTA_MAX, d = round-half-even(delta * 2^16); sum += d, cnt += 1 at every feature of keys[t] (a weight two images meet gets
-    both).  Returns dict(learnt, skipped, clamped)."""
-    keys, values, steps = np.asarray(keys, dtype=_U64), np.asarray(values, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
-    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
-    T = keys.shape[0]
-    t = np.arange(T, dtype=np.int64)[:, None]
-    played, last = t < lengths[None, :], t == lengths[None, :] - 1
-    skipped = played & last & (steps >> 7 == 0)
+def _add_moves_on_host(keys, steps, lengths, deltas, tuples, symmetric, acc) -> dict:
+    """The learners' tail.  A game has L = min(lengths[g], T) moves; its last is skipped without its terminal bit; any other move (t, g),
+    t < L, has deltas[t, g] clamped to +-DELTA_MAX, d = round-half-even(that * 2^16), and sum += d, cnt += 1 at every feature of
+    keys[t, g] (a weight two images meet gets both).  acc int64[W, 2] = {sum, cnt}, in place.  Returns dict(learnt, skipped, clamped)."""
+    L = np.minimum(np.asarray(lengths, dtype=np.int64).reshape(-1), keys.shape[0])
+    t = np.arange(keys.shape[0], dtype=np.int64)[:, None]
+    played = t < L[None, :]
+    skipped = played & (t == L[None, :] - 1) & (steps >> 7 == 0)
     learn = played & ~skipped
-    nxt_r, nxt_v = np.zeros_like(values), np.zeros_like(values)
-    nxt_r[:-1], nxt_v[:-1] = ((steps[1:] >> 2) & 31).astype(np.float64), values[1:]
-    target = np.where(last, 0.0, nxt_r + float(gamma) * nxt_v)
-    delta = (target - values)[learn]
+    delta = deltas[learn]
     clamped = np.abs(delta) > DELTA_MAX
     d = np.rint(np.ldexp(np.clip(delta, -DELTA_MAX, DELTA_MAX), FRAC_BITS)).astype(np.int64)
     idx = feature_indices_on_host(keys[learn], tuples, symmetric)
     np.add.at(acc[:, 0], idx.reshape(-1), np.repeat(d, idx.shape[1]))
     np.add.at(acc[:, 1], idx.reshape(-1), 1)
     return dict(learnt=int(learn.sum()), skipped=int(skipped.sum()), clamped=int(clamped.sum()))
+
+
+def learn_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, acc):
+    """pulse_tfe_nt_learn on the host.  keys uint64[T, B], values float64[T, B], steps uint8[T, B], lengths int[B] (a game has
+    min(lengths[g], T) moves); acc int64[W, 2] = {sum, cnt}, added to in place.  The last move of a game has target 0; any other has
+    target = reward(steps[t + 1]) + gamma * values[t + 1]; delta = target - values[t], added by _add_moves_on_host.  Returns
+    dict(learnt, skipped, clamped)."""
+    keys, values, steps = np.asarray(keys, dtype=_U64), np.asarray(values, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
+    T = keys.shape[0]
+    last = np.arange(T, dtype=np.int64)[:, None] == np.minimum(np.asarray(lengths, dtype=np.int64).reshape(-1), T)[None, :] - 1
+    nxt_r, nxt_v = np.zeros_like(values), np.zeros_like(values)
+    nxt_r[:-1], nxt_v[:-1] = ((steps[1:] >> 2) & 31).astype(np.float64), values[1:]
+    target = np.where(last, 0.0, nxt_r + float(gamma) * nxt_v)
+    return _add_moves_on_host(keys, steps, lengths, target - values, tuples, symmetric, acc)
 
 
 def lambda_deltas_on_host(values, steps, lengths, gamma: float, lam: float) -> np.ndarray:
@@ -245,21 +252,10 @@ def lambda_deltas_on_host(values, steps, lengths, gamma: float, lam: float) -> n
 def learn_lambda_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, lam: float, acc) -> dict:
     """pulse_tfe_nt_learn_lambda on the host: learn_nt_on_host with lambda_deltas_on_host's D_t in place of the one-step difference.
     The skipped moves, the clamp to +-DELTA_MAX (applied to the add only: the recurrence carries the unclamped D), d and the adds are
-    learn_nt_on_host's.  Returns dict(learnt, skipped, clamped, deltas float64[T, B])."""
+    _add_moves_on_host's.  Returns dict(learnt, skipped, clamped, deltas float64[T, B])."""
     keys, values, steps = np.asarray(keys, dtype=_U64), np.asarray(values, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
-    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
     deltas = lambda_deltas_on_host(values, steps, lengths, gamma, lam)
-    t = np.arange(keys.shape[0], dtype=np.int64)[:, None]
-    played, last = t < lengths[None, :], t == np.minimum(lengths, keys.shape[0])[None, :] - 1
-    skipped = played & last & (steps >> 7 == 0)
-    learn = played & ~skipped
-    delta = deltas[learn]
-    clamped = np.abs(delta) > DELTA_MAX
-    d = np.rint(np.ldexp(np.clip(delta, -DELTA_MAX, DELTA_MAX), FRAC_BITS)).astype(np.int64)
-    idx = feature_indices_on_host(keys[learn], tuples, symmetric)
-    np.add.at(acc[:, 0], idx.reshape(-1), np.repeat(d, idx.shape[1]))
-    np.add.at(acc[:, 1], idx.reshape(-1), 1)
-    return dict(learnt=int(learn.sum()), skipped=int(skipped.sum()), clamped=int(clamped.sum()), deltas=deltas)
+    return dict(_add_moves_on_host(keys, steps, lengths, deltas, tuples, symmetric, acc), deltas=deltas)
 
 
 def apply_nt_on_host(weights, acc, step: float) -> int:
@@ -376,17 +372,20 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         o.total_score, o.episode_reward, o.stats = self.total_score.data_ptr(), self.episode_reward.data_ptr(), self.counters.data_ptr()
         return self._launch("pulse_tfe_nt_rollout", o)
 
+    def _moves(self, o):
+        """The network and the fields the two learners' structs share."""
+        self._net(o.net)
+        o.n_games, o.max_steps, o.gamma = self.n_games, self.max_steps, self.gamma
+        o.keys, o.values, o.steps, o.lengths = self.keys.data_ptr(), self.values.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr()
+        o.acc, o.stats = self.acc.data_ptr(), self.counters.data_ptr()
+        return o
+
     def learn(self):
         """The temporal differences of the games last played, into the accumulators: one launch, or with lam > 0
         learn_lambda_launch's two."""
         if self.lam > 0.0:
             return self.learn_lambda_launch(self.lam)
-        o = _native.TfeNtLearn()
-        self._net(o.net)
-        o.n_games, o.max_steps, o.gamma = self.n_games, self.max_steps, self.gamma
-        o.keys, o.values, o.steps, o.lengths = self.keys.data_ptr(), self.values.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr()
-        o.acc, o.stats = self.acc.data_ptr(), self.counters.data_ptr()
-        return self._launch("pulse_tfe_nt_learn", o)
+        return self._launch("pulse_tfe_nt_learn", self._moves(_native.TfeNtLearn()))
 
     def learn_lambda_launch(self, lam):
         """pulse_tfe_nt_learn_lambda on the games last played, whatever the agent's own `lam`: the backward walk into `deltas`
@@ -395,11 +394,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         lam = check_lam(lam)
         if self.deltas is None:
             self.deltas = torch.zeros_like(self.values)
-        o = _native.TfeNtLearnLambda()
-        self._net(o.net)
-        o.n_games, o.max_steps, o.gamma, o.lam = self.n_games, self.max_steps, self.gamma, lam
-        o.keys, o.values, o.steps, o.lengths = self.keys.data_ptr(), self.values.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr()
-        o.deltas, o.acc, o.stats = self.deltas.data_ptr(), self.acc.data_ptr(), self.counters.data_ptr()
+        o = self._moves(_native.TfeNtLearnLambda())
+        o.lam, o.deltas = lam, self.deltas.data_ptr()
         return self._launch("pulse_tfe_nt_learn_lambda", o)
 
     def apply(self):

@@ -8,21 +8,19 @@
 // cells and hands the kernels 6 shift counts per feature in one 64-bit word, by value, so a nibble is a shift by a scalar and no lane
 // indexes an array.  The learner runs one lane per recorded move and adds temporal differences as fixed-point integers, so the
 // accumulators do not depend on scheduling; the apply launch moves each weight by step * the mean of its adds.
+// The game loop (play_game) is tfe_ntuple_device.h's, shared with tfe_ntuple_search.hip; the learner's kernel (tfe_nt_scatter_kernel,
+// launch_scatter) also makes the adds of tfe_ntuple_lambda.hip's TD(lambda) learner.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 
-#include "philox_device.h"
 #include "pulse_internal.h"
-#include "tfe_agent_device.h"
 #include "tfe_device.h"
 #include "tfe_ntuple_device.h"
 
 namespace {
 
 using namespace pulse_tfe;
-using pulse_philox::philox4x32;
-using pulse_philox::U4;
 using pulse::fail_named;
 using pulse::finish_launch;
 
@@ -30,90 +28,24 @@ constexpr int kBlock = 256;
 static_assert(sizeof(PulseTfeNtNet) == 104 && sizeof(PulseTfeNtRollout) == 232 && sizeof(PulseTfeNtLearn) == 176 && sizeof(PulseTfeNtApply) == 128 &&
               sizeof(PulseTfeNtEval) == 208, "struct layouts are part of the ABI");
 
-// IMG = 8 (symmetric) or 1.  Record: pulse_tfe_nt_rollout; otherwise pulse_tfe_nt_evaluate.
+// IMG = 8 (symmetric) or 1.  Record: pulse_tfe_nt_rollout; otherwise pulse_tfe_nt_evaluate.  One lane plays one game: q = r + gamma * V.
 template <int IMG, bool Record>
 __global__ __launch_bounds__(kBlock) void tfe_nt_games_kernel(const Games o, const NtDev net) {
     __shared__ unsigned long long wg[Record ? 2 : kEvalBins];
     if (threadIdx.x < (Record ? 2 : kEvalBins)) wg[threadIdx.x] = 0ull;
     __syncthreads();
-    const int g = blockIdx.x * kBlock + threadIdx.x;
-    const size_t B = (size_t)o.n_games;
-    unsigned long long n_moves = 0ull, n_cut = 0ull;
-    if (g < o.n_games) {
-        const uint64_t id = o.board_id0 + (uint64_t)g;
-        PackedBoard p = tfe_reset_packed(o.env_seed, id);
-        int64_t total = 0;
-        int ep_reward = 0, length = 0;
-        bool over = false, capped = false;
-        unsigned long long n_greedy = 0ull;
-        for (int t = 0; t < o.max_steps && !over && !capped; ++t) {
-            const U4 r = philox4x32(o.agent_seed, id, (uint64_t)t);
-            const uint64_t key_b = (uint64_t)p.hi << 32 | p.lo;
-            uint64_t ka[4];
-            int sc[4];
+    play_game<Record>(o, wg, blockIdx.x * kBlock + threadIdx.x, true,
+                      [&](const uint64_t, const uint64_t (&ka)[4], const int (&sc)[4], double (&v)[4], double (&q)[4]) {
+                          values4<IMG>(net, o.weights, ka, v);
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                PackedBoard m = p;
-                sc[a] = tfe_move_packed(m, a, o.lut);
-                ka[a] = (uint64_t)m.hi << 32 | m.lo;
-            }
-            double v[4], q[4];
-            values4<IMG>(net, o.weights, ka, v);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) q[a] = __dadd_rn((double)tfe_reward(sc[a]), __dmul_rn(o.gamma, v[a]));
-            const bool greedy = (r.x >> 8) >= o.eps_q24;
-            int act = (int)(r.y >> 30);
-            if (greedy) {
-                U4 coins{0u, 0u, 0u, 0u};
-                if (any_two_equal(q)) coins = philox4x32(o.tie_seed, key_b, o.round);
-                const bool cand[4] = {ka[0] != key_b, ka[1] != key_b, ka[2] != key_b, ka[3] != key_b};        // the moves that change the board
-                const int best = greedy_scan<false>(q, coins, cand);
-                act = best < 0 ? act : best;                                            // (a live board has a candidate)
-                n_greedy += 1ull;
-            }
-            uint64_t key = ka[0];
-            double val = v[0];
-            int score = sc[0];
-#pragma unroll
-            for (int a = 1; a < 4; ++a) { key = act == a ? ka[a] : key; val = act == a ? v[a] : val; score = act == a ? sc[a] : score; }
-            p.lo = (uint32_t)key; p.hi = (uint32_t)(key >> 32);                         // the afterstate's key IS the moved board
-            const U4 rnd = philox4x32(o.env_seed, id, (uint64_t)t + 1ull);
-            const int empty_before = tfe_spawn_packed(p, rnd.x, rnd.y);                // TFE.py:182 (always)
-            over = tfe_over_packed(p, empty_before);                                   // TFE.py:48-67
-            capped = has_nibble15(p);
-            const int reward = tfe_reward(score);
-            if constexpr (Record) {
-                const size_t at = (size_t)t * B + (size_t)g;
-                o.keys[at] = key;
-                o.values[at] = val;
-                o.steps[at] = tfe_step_byte(act, reward, over ? 1u : 0u);
-            }
-            total += score; ep_reward += reward;
-            length = t + 1;
-        }
-        n_moves = (unsigned long long)length;
-        n_cut = over ? 0ull : 1ull;
-        if constexpr (Record) {
-            o.lengths[g] = length;
-            o.total_score[g] = total;
-            o.episode_reward[g] = ep_reward;
-        } else {
-            if (o.lengths) o.lengths[g] = length;
-            if (o.total_score) o.total_score[g] = total;
-            uint32_t top = 0u;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) top = max(top, max((p.lo >> (4 * i)) & 15u, (p.hi >> (4 * i)) & 15u));
-            const unsigned long long s = (unsigned long long)total;
-            add_game(wg, {1ull, n_moves, s, s * s, s, n_cut, n_greedy, capped ? 1ull : 0ull}, (int)top);
-        }
-    }
-    if constexpr (Record) add_stats(wg, o.stats, 0, n_moves, 3, n_cut);
-    else flush_bins(wg, o.stats, o.hist);
+                          for (int a = 0; a < 4; ++a) q[a] = __dadd_rn((double)tfe_reward(sc[a]), __dmul_rn(o.gamma, v[a]));
+                      });
 }
 
-// One lane per recorded move: blockIdx.y = t, blockIdx.x * kBlock + threadIdx.x = g.
-template <int IMG>
-__global__ __launch_bounds__(kBlock) void tfe_nt_learn_kernel(const PulseTfeNtLearn o, const NtDev net) {
+// The learners' adds, one lane per recorded move: blockIdx.y = t, blockIdx.x * kBlock + threadIdx.x = g.  Given: the move's difference
+// is o.deltas' (pulse_tfe_nt_learn_lambda, after its walk); otherwise it is the one-step difference, formed here (pulse_tfe_nt_learn).
+template <int IMG, bool Given>
+__global__ __launch_bounds__(kBlock) void tfe_nt_scatter_kernel(const Moves o, const NtDev net) {
     __shared__ unsigned long long wg[3];
     if (threadIdx.x < 3) wg[threadIdx.x] = 0ull;
     __syncthreads();
@@ -129,10 +61,16 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_learn_kernel(const PulseTfeNtLe
             if (skip) {
                 atomicAdd(&wg[1], 1ull);                                                // LDS
             } else {
-                double target = 0.0;
-                if (!last) target = td_target(o.steps[at + B], o.values[at + B], o.gamma);
+                double delta;
+                if constexpr (Given) {
+                    delta = o.deltas[at];
+                } else {
+                    double target = 0.0;
+                    if (!last) target = td_target(o.steps[at + B], o.values[at + B], o.gamma);
+                    delta = __dsub_rn(target, o.values[at]);
+                }
                 bool clamp;
-                const unsigned long long d = td_fixed(__dsub_rn(target, o.values[at]), clamp);
+                const unsigned long long d = td_fixed(delta, clamp);
                 add_features<IMG>(net, reinterpret_cast<unsigned long long*>(o.acc), o.keys[at], d);
                 atomicAdd(&wg[0], 1ull);
                 if (clamp) atomicAdd(&wg[2], 1ull);
@@ -212,6 +150,18 @@ int check_net(const PulseTfeNtNet& n, bool need_weights, const char* name, NtDev
     return 0;
 }
 
+void launch_scatter(const Moves& m, const NtDev& dev, bool symmetric, void* stream) {
+    const dim3 grid((unsigned)((m.n_games + kBlock - 1) / kBlock), (unsigned)m.max_steps), block(kBlock);
+    hipStream_t st = (hipStream_t)stream;
+    if (m.deltas) {
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, true>), grid, block, 0, st, m, dev);
+        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, true>), grid, block, 0, st, m, dev);
+    } else {
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, false>), grid, block, 0, st, m, dev);
+        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, false>), grid, block, 0, st, m, dev);
+    }
+}
+
 int check_eval(const PulseTfeNtEval* o, const char* name, NtDev* dev, Games* g) {
     if (!o) return fail_named(name, "options are null");
     if (int rc = check_net(o->net, true, name, dev)) return rc;
@@ -263,21 +213,12 @@ extern "C" int pulse_tfe_nt_evaluate(const PulseTfeNtEval* o, void* stream) {
 
 extern "C" int pulse_tfe_nt_learn(const PulseTfeNtLearn* o, void* stream) {
     const char* name = "pulse_tfe_nt_learn";
-    if (!o) return fail_named(name, "options are null");
     NtDev dev;
-    if (int rc = check_net(o->net, false, name, &dev)) return rc;
-    if (int rc = check_batch(o, name)) return rc;
-    if (!o->keys) return fail_named(name, "keys is null");
-    if (!o->values) return fail_named(name, "values is null");
-    if (!o->steps) return fail_named(name, "steps is null");
-    if (!o->lengths) return fail_named(name, "lengths is null");
-    if (int rc = check_acc(o->acc, name)) return rc;
-    if (!o->stats) return fail_named(name, "stats is null");
+    Moves m;
+    if (int rc = check_moves(o, name, &dev, &m)) return rc;
     if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->values & 7u) || ((uintptr_t)o->stats & 7u)) return fail_named(name, "keys / values / stats must be 8-byte aligned");
     if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
-    const dim3 grid((unsigned)((o->n_games + kBlock - 1) / kBlock), (unsigned)o->max_steps), block(kBlock);
-    if (o->net.symmetric) hipLaunchKernelGGL(tfe_nt_learn_kernel<8>, grid, block, 0, (hipStream_t)stream, *o, dev);
-    else hipLaunchKernelGGL(tfe_nt_learn_kernel<1>, grid, block, 0, (hipStream_t)stream, *o, dev);
+    launch_scatter(m, dev, o->net.symmetric != 0, stream);
     return finish_launch("pulse_tfe_nt_learn launch");
 }
 

@@ -1,14 +1,17 @@
 // tfe_ntuple_device.h -- what the units of the 2048 n-tuple network share (tfe_ntuple.hip: the learner's four launches; tfe_ntuple_search.hip:
-// expectimax play; tfe_ntuple_lambda.hip: the TD(lambda) learner): the network as the kernels take it, a feature's index, V of four
-// afterstates at once, the learners' target, fixed-point difference and adds, the 32,768-tile test, the game loops' parameters and
-// the host's checks of the network, of the accumulators and of a batch of games.  One copy each.  Not part of the ABI.
+// expectimax play; tfe_ntuple_lambda.hip: the TD(lambda) walk): the network as the kernels take it, a feature's index, V of four
+// afterstates at once, the learners' target, fixed-point difference and adds, their parameters (Moves), shared refusals
+// (check_moves) and scatter launch, the four moves of a board, the greedy action, the game loop (play_game) with its parameters
+// (Games) and the host's checks of the network, of the accumulators and of a batch of games.  One copy each.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
+#include "philox_device.h"
 #include "pulse_internal.h"
+#include "tfe_agent_device.h"
 #include "tfe_device.h"
 
 namespace pulse_tfe {
@@ -136,8 +139,134 @@ inline int check_acc(const int64_t* acc, const char* name) {
     return 0;
 }
 
+// The learners' counterpart of Games: what pulse_tfe_nt_learn and pulse_tfe_nt_learn_lambda hand the scatter (deltas: null for TD(0))
+struct Moves {
+    int32_t n_games, max_steps;
+    double gamma;
+    const uint64_t* keys; const double* values; const uint8_t* steps;
+    const int32_t* lengths;
+    const double* deltas;
+    int64_t* acc; int64_t* stats;
+};
+
+// ... what both learners refuse, and the scatter's parameters of their struct (deltas left null)
+template <class O>
+int check_moves(const O* o, const char* name, NtDev* dev, Moves* m) {
+    if (!o) return fail_named(name, "options are null");
+    if (int rc = check_net(o->net, false, name, dev)) return rc;
+    if (int rc = check_batch(o, name)) return rc;
+    if (!o->keys) return fail_named(name, "keys is null");
+    if (!o->values) return fail_named(name, "values is null");
+    if (!o->steps) return fail_named(name, "steps is null");
+    if (!o->lengths) return fail_named(name, "lengths is null");
+    if (int rc = check_acc(o->acc, name)) return rc;
+    if (!o->stats) return fail_named(name, "stats is null");
+    *m = Moves{o->n_games, o->max_steps, o->gamma, o->keys, o->values, o->steps, o->lengths, nullptr, o->acc, o->stats};
+    return 0;
+}
+
+// ... and their adds, one lane per recorded move: the difference is m.deltas' where it is set and the one-step difference otherwise
+// (defined in tfe_ntuple.hip)
+void launch_scatter(const Moves& m, const NtDev& dev, bool symmetric, void* stream);
+
 // what pulse_tfe_nt_evaluate and pulse_tfe_nt_evaluate_search refuse, and the game loop's parameters of an evaluation (defined in
 // tfe_ntuple.hip)
 int check_eval(const PulseTfeNtEval* o, const char* name, NtDev* dev, Games* g);
+
+// The four moves of board `key`: the afterstates' keys and the merge scores
+__device__ __forceinline__ void moves4(const uint64_t key, const uint32_t* __restrict__ lut, uint64_t (&ka)[4], int (&sc)[4]) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        PackedBoard m{(uint32_t)key, (uint32_t)(key >> 32)};
+        sc[a] = tfe_move_packed(m, a, lut);
+        ka[a] = (uint64_t)m.hi << 32 | m.lo;
+    }
+}
+
+// the greedy action of pulse_tfe_nt_rollout on these q (-1: no candidate), and the candidates (the moves that change the board) as bit a
+__device__ __forceinline__ int greedy_of(const double (&q)[4], const uint64_t key_b, const uint64_t (&ka)[4], uint64_t tie_seed, uint64_t round,
+                                         uint32_t* bits = nullptr) {
+    pulse_philox::U4 coins{0u, 0u, 0u, 0u};
+    if (any_two_equal(q)) coins = pulse_philox::philox4x32(tie_seed, key_b, round);
+    const bool cand[4] = {ka[0] != key_b, ka[1] != key_b, ka[2] != key_b, ka[3] != key_b};
+    if (bits) *bits = (cand[0] ? 1u : 0u) | (cand[1] ? 2u : 0u) | (cand[2] ? 4u : 0u) | (cand[3] ? 8u : 0u);
+    return greedy_scan<false>(q, coins, cand);
+}
+
+// The game loop of the roll-out (Record) and of the two evaluations: game g of the launch, from its reset to its end, its cap or
+// max_steps.  q_of(key_b, ka, sc, v, q) fills the four q of board key_b from its moves, and where the launch records also V of the
+// four afterstates.  `writer`: this lane writes the game's outputs and counts it (a game that several lanes play alike has one).
+// wg: the workgroup's zeroed LDS words, 2 with Record and kEvalBins without.  Called by every thread of the workgroup, whatever its g.
+template <bool Record, class Q>
+__device__ __forceinline__ void play_game(const Games& o, unsigned long long* wg, const int g, const bool writer, Q&& q_of) {
+    using pulse_philox::philox4x32;
+    using pulse_philox::U4;
+    const size_t B = (size_t)o.n_games;
+    unsigned long long n_moves = 0ull, n_cut = 0ull;
+    if (g < o.n_games) {
+        const uint64_t id = o.board_id0 + (uint64_t)g;
+        PackedBoard p = tfe_reset_packed(o.env_seed, id);
+        int64_t total = 0;
+        int ep_reward = 0, length = 0;
+        bool over = false, capped = false;
+        unsigned long long n_greedy = 0ull;
+        for (int t = 0; t < o.max_steps && !over && !capped; ++t) {
+            const U4 r = philox4x32(o.agent_seed, id, (uint64_t)t);
+            const uint64_t key_b = (uint64_t)p.hi << 32 | p.lo;
+            uint64_t ka[4];
+            int sc[4];
+            moves4(key_b, o.lut, ka, sc);
+            double v[4] = {0.0, 0.0, 0.0, 0.0}, q[4];
+            q_of(key_b, ka, sc, v, q);
+            const bool greedy = (r.x >> 8) >= o.eps_q24;
+            int act = (int)(r.y >> 30);
+            if (greedy) {
+                const int best = greedy_of(q, key_b, ka, o.tie_seed, o.round);
+                act = best < 0 ? act : best;                                            // (a live board has a candidate)
+                n_greedy += 1ull;
+            }
+            uint64_t key = ka[0];
+            double val = v[0];
+            int score = sc[0];
+#pragma unroll
+            for (int a = 1; a < 4; ++a) { key = act == a ? ka[a] : key; val = act == a ? v[a] : val; score = act == a ? sc[a] : score; }
+            p.lo = (uint32_t)key; p.hi = (uint32_t)(key >> 32);                         // the afterstate's key IS the moved board
+            const U4 rnd = philox4x32(o.env_seed, id, (uint64_t)t + 1ull);
+            const int empty_before = tfe_spawn_packed(p, rnd.x, rnd.y);                // TFE.py:182 (always)
+            over = tfe_over_packed(p, empty_before);                                   // TFE.py:48-67
+            capped = has_nibble15(p);
+            const int reward = tfe_reward(score);
+            if constexpr (Record) {
+                if (writer) {
+                    const size_t at = (size_t)t * B + (size_t)g;
+                    o.keys[at] = key;
+                    o.values[at] = val;
+                    o.steps[at] = tfe_step_byte(act, reward, over ? 1u : 0u);
+                }
+            }
+            total += score; ep_reward += reward;
+            length = t + 1;
+        }
+        if (writer) {
+            n_moves = (unsigned long long)length;
+            n_cut = over ? 0ull : 1ull;
+            if constexpr (Record) {
+                o.lengths[g] = length;
+                o.total_score[g] = total;
+                o.episode_reward[g] = ep_reward;
+            } else {
+                if (o.lengths) o.lengths[g] = length;
+                if (o.total_score) o.total_score[g] = total;
+                uint32_t top = 0u;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) top = max(top, max((p.lo >> (4 * i)) & 15u, (p.hi >> (4 * i)) & 15u));
+                const unsigned long long s = (unsigned long long)total;
+                add_game(wg, {1ull, n_moves, s, s * s, s, n_cut, n_greedy, capped ? 1ull : 0ull}, (int)top);
+            }
+        }
+    }
+    if constexpr (Record) add_stats(wg, o.stats, 0, n_moves, 3, n_cut);
+    else flush_bins(wg, o.stats, o.hist);
+}
 
 }  // namespace pulse_tfe

@@ -11,17 +11,13 @@
 // among its own 32 lanes only, which are active together.
 #include <hip/hip_runtime.h>
 
-#include "philox_device.h"
 #include "pulse_internal.h"
-#include "tfe_agent_device.h"
 #include "tfe_device.h"
 #include "tfe_ntuple_device.h"
 
 namespace {
 
 using namespace pulse_tfe;
-using pulse_philox::philox4x32;
-using pulse_philox::U4;
 using pulse::fail_named;
 using pulse::finish_launch;
 
@@ -41,15 +37,6 @@ struct Boards {
     double* q; int8_t* action; uint8_t* candidates;
     const uint32_t* lut;
 };
-
-__device__ __forceinline__ void moves4(const uint64_t key, const uint32_t* __restrict__ lut, uint64_t (&ka)[4], int (&sc)[4]) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        PackedBoard m{(uint32_t)key, (uint32_t)(key >> 32)};
-        sc[a] = tfe_move_packed(m, a, lut);
-        ka[a] = (uint64_t)m.hi << 32 | m.lo;
-    }
-}
 
 __device__ __forceinline__ int count_empty(const uint64_t key) {
     return __popc(tfe_nz_nibbles((uint32_t)key) ^ 0x88888888u) + __popc(tfe_nz_nibbles((uint32_t)(key >> 32)) ^ 0x88888888u);
@@ -101,16 +88,6 @@ __device__ __forceinline__ void search_q(const NtDev& net, const float* __restri
     }
 }
 
-// the greedy action of pulse_tfe_nt_rollout on these q (-1: no candidate), and the candidates as bit a
-__device__ __forceinline__ int greedy_of(const double (&q)[4], const uint64_t key_b, const uint64_t (&ka)[4], uint64_t tie_seed, uint64_t round,
-                                         uint32_t* bits = nullptr) {
-    U4 coins{0u, 0u, 0u, 0u};
-    if (any_two_equal(q)) coins = philox4x32(tie_seed, key_b, round);
-    const bool cand[4] = {ka[0] != key_b, ka[1] != key_b, ka[2] != key_b, ka[3] != key_b};
-    if (bits) *bits = (cand[0] ? 1u : 0u) | (cand[1] ? 2u : 0u) | (cand[2] ? 4u : 0u) | (cand[3] ? 8u : 0u);
-    return greedy_scan<false>(q, coins, cand);
-}
-
 template <int IMG>
 __global__ __launch_bounds__(kBlock) void tfe_nt_search_kernel(const Boards o, const NtDev net) {
     const int g = (int)blockIdx.x * kGroupsPerBlock + ((int)threadIdx.x >> 5), s = (int)threadIdx.x & (kGroup - 1);
@@ -131,58 +108,17 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_search_kernel(const Boards o, c
     }
 }
 
-// pulse_tfe_nt_evaluate's game loop (tfe_ntuple.hip, Record = false) with q from the search; lane 0 of a group writes and counts
+// pulse_tfe_nt_evaluate's game loop with q from the search: the 32 lanes of a group play the game alike, lane 0 writes and counts
 template <int IMG>
 __global__ __launch_bounds__(kBlock) void tfe_nt_search_games_kernel(const Games o, const NtDev net) {
     __shared__ unsigned long long wg[kEvalBins];
     if (threadIdx.x < kEvalBins) wg[threadIdx.x] = 0ull;
     __syncthreads();
     const int g = (int)blockIdx.x * kGroupsPerBlock + ((int)threadIdx.x >> 5), s = (int)threadIdx.x & (kGroup - 1);
-    if (g < o.n_games) {
-        const uint64_t id = o.board_id0 + (uint64_t)g;
-        PackedBoard p = tfe_reset_packed(o.env_seed, id);
-        int64_t total = 0;
-        int length = 0;
-        bool over = false, capped = false;
-        unsigned long long n_greedy = 0ull;
-        for (int t = 0; t < o.max_steps && !over && !capped; ++t) {
-            const U4 r = philox4x32(o.agent_seed, id, (uint64_t)t);
-            const uint64_t key_b = (uint64_t)p.hi << 32 | p.lo;
-            uint64_t ka[4];
-            int sc[4];
-            moves4(key_b, o.lut, ka, sc);
-            double q[4];
-            search_q<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, s, q);
-            const bool greedy = (r.x >> 8) >= o.eps_q24;
-            int act = (int)(r.y >> 30);
-            if (greedy) {
-                const int best = greedy_of(q, key_b, ka, o.tie_seed, o.round);
-                act = best < 0 ? act : best;                                            // (a live board has a candidate)
-                n_greedy += 1ull;
-            }
-            uint64_t key = ka[0];
-            int score = sc[0];
-#pragma unroll
-            for (int a = 1; a < 4; ++a) { key = act == a ? ka[a] : key; score = act == a ? sc[a] : score; }
-            p.lo = (uint32_t)key; p.hi = (uint32_t)(key >> 32);
-            const U4 rnd = philox4x32(o.env_seed, id, (uint64_t)t + 1ull);
-            const int empty_before = tfe_spawn_packed(p, rnd.x, rnd.y);
-            over = tfe_over_packed(p, empty_before);
-            capped = has_nibble15(p);
-            total += score;
-            length = t + 1;
-        }
-        if (s == 0) {
-            if (o.lengths) o.lengths[g] = length;
-            if (o.total_score) o.total_score[g] = total;
-            uint32_t top = 0u;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) top = max(top, max((p.lo >> (4 * i)) & 15u, (p.hi >> (4 * i)) & 15u));
-            const unsigned long long sum = (unsigned long long)total;
-            add_game(wg, {1ull, (unsigned long long)length, sum, sum * sum, sum, over ? 0ull : 1ull, n_greedy, capped ? 1ull : 0ull}, (int)top);
-        }
-    }
-    flush_bins(wg, o.stats, o.hist);
+    play_game<false>(o, wg, g, s == 0,
+                     [&](const uint64_t key_b, const uint64_t (&ka)[4], const int (&sc)[4], double (&)[4], double (&q)[4]) {
+                         search_q<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, s, q);
+                     });
 }
 
 }  // namespace

@@ -4,13 +4,12 @@ checkpoint file, and what the compiler made of the kernels."""
 import ctypes as C
 import math
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from tests.native_args import assert_refusals
+from tests.native_args import PTR, assert_refusals, nt_opts, resource_usage
 
 ROOT = Path(__file__).resolve().parent.parent
 NAMES = ("pulse_tfe_nt_rollout", "pulse_tfe_nt_learn", "pulse_tfe_nt_apply", "pulse_tfe_nt_evaluate")
@@ -32,40 +31,15 @@ def test_library_exports_the_four_entry_points():
 
 # ------------------------------------------------------------------ PULSE_EINVAL before anything is launched
 def _opts(name, **kw):
-    """A struct every check passes (the buffers are host words: nothing is launched on a refusal), then `kw` over it.  net_* go to
-    the network; tuples = a list of cell lists."""
+    """A struct every check passes, then `kw` over it (native_args.nt_opts' keywords)."""
     from pulselib_amd import _native
     struct = dict(zip(NAMES, (_native.TfeNtRollout, _native.TfeNtLearn, _native.TfeNtApply, _native.TfeNtEval)))[name]
-    o = struct()
-    buf = (C.c_int64 * 8)()
-    o._keep = buf
-    ptr = C.addressof(buf)
-    assert ptr % 16 == 0
-    base = dict(tuples=[[0, 1, 2, 3], [4, 5, 6, 8, 9, 10]], net_n=4, net_symmetric=1, net_weights=ptr)
     fields = {f[0] for f in struct._fields_}
-    for f in ("keys", "values", "steps", "lengths", "total_score", "episode_reward", "stats", "acc", "summary", "max_tile_hist"):
-        if f in fields:
-            base[f] = ptr
-    for f, v in (("n_games", 64), ("max_steps", 32), ("gamma", 1.0), ("epsilon", 0.25), ("step", 1.0 / 16)):
-        if f in fields:
-            base[f] = v
-    base.update(kw)
-    tuples = base.pop("tuples")
-    o.net.n_tuples = base.pop("net_n_tuples", len(tuples))
-    for t, cells in enumerate(tuples[:8]):
-        o.net.tuple_len[t] = base.get("net_len%d" % t, len(cells))
-        for i, c in enumerate(cells):
-            o.net.cells[t][i] = c
-    base = {k: v for k, v in base.items() if not k.startswith("net_len")}
-    o.net.n_weights = base.pop("net_n_weights", sum(16 ** len(c) for c in tuples))
-    for k, v in base.items():
-        if k.startswith("net_"):
-            setattr(o.net, k[4:], v)
-        elif k in fields:
-            setattr(o, k, v)
-        else:
-            raise KeyError(k)
-    return o
+    base = dict(tuples=[[0, 1, 2, 3], [4, 5, 6, 8, 9, 10]], net_n=4, net_symmetric=1, net_weights=PTR)
+    base.update((f, PTR) for f in ("keys", "values", "steps", "lengths", "total_score", "episode_reward", "stats", "acc", "summary", "max_tile_hist")
+                if f in fields)
+    base.update((f, v) for f, v in (("n_games", 64), ("max_steps", 32), ("gamma", 1.0), ("epsilon", 0.25), ("step", 1.0 / 16)) if f in fields)
+    return nt_opts(struct, base, **kw)
 
 
 NET_CASES = [(dict(net_n=3), b"board side n must be 4"), (dict(net_n=5), b"board side n must be 4"),
@@ -305,14 +279,9 @@ def test_checkpoint_round_trip(tmp_path):
 
 # ------------------------------------------------------------------ what the compiler made
 def test_kernels_use_no_scratch():
-    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple.hip with the Makefile's flags: seven kernels, none with scratch or a spilled vector
-    register.  VGPRs as built for this change: games 118 (symmetric) / 63, learn 59 / 18, apply 22."""
-    run = subprocess.run(["make", "-s", "-C", str(ROOT / "pulselib_amd" / "csrc"), "ntuple-resource-usage"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", run.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", run.stderr)]
-    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", run.stderr)]
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", run.stderr)]
-    print(dict(zip(names, vgprs)))
-    assert len(names) == 7 and sum("tfe_nt_games_kernel" in n for n in names) == 4 and sum("tfe_nt_learn_kernel" in n for n in names) == 2
-    assert scratch == [0] * 7 and spills == [0] * 7 and len(vgprs) == 7 and max(vgprs) <= 128
+    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple.hip with the Makefile's flags: nine kernels, none with scratch or a spilled vector
+    register.  VGPRs as built: games 118 (symmetric) / 63, scatter 59 / 18 (both learners'), apply 22."""
+    names, vgprs, scratch, spills = resource_usage("ntuple-resource-usage")
+    assert len(names) == 9 and sum("tfe_nt_games_kernel" in n for n in names) == 4 and sum("tfe_nt_scatter_kernel" in n for n in names) == 4
+    assert sum("tfe_nt_apply_kernel" in n for n in names) == 1
+    assert scratch == [0] * 9 and spills == [0] * 9 and len(vgprs) == 9 and max(vgprs) <= 128

@@ -79,6 +79,11 @@ def _rounds():
     return _play_rounds(True, ROUNDS)
 
 
+@functools.lru_cache(maxsize=None)
+def _plain_rounds():
+    return _play_rounds(False, 2)
+
+
 def test_every_round_has_ended_and_cut_games():
     _, rounds = _rounds()
     for r, rec in enumerate(rounds):
@@ -100,11 +105,28 @@ def test_rollout_equals_the_host_word_for_word():
 
 def test_rollout_without_symmetry():
     """symmetric = 0: one feature per tuple; the second round runs on weights the first one learnt"""
-    _, rounds = _play_rounds(False, 2)
+    _, rounds = _plain_rounds()
     for r, rec in enumerate(rounds):
         assert_rollout(rec["got"], rec["want"], r, PER_MOVE)
         assert rec["acc_equal"] and rec["weights_equal"] and rec["acc_zero"] and rec["acc_adds"] == 2 * rec["host"]["learnt"], r
     assert rounds[1]["want"]["values"].any()
+
+
+def test_evaluate_without_symmetry():
+    """symmetric = 0 in the evaluation launch: the per-game arrays and the 24 counters against the host's games under the weights of
+    the two rounds without symmetry.  Rehearsed on the host: 242 games end and 15 are cut at epsilon .25, 203 and 54 at 0, none capped."""
+    from pulselib_amd.agents.tfe_ntuple_td_gpu import EVAL_SUMMARY
+    from tests.tfe_host import eval_words
+    a, _ = _plain_rounds()
+    weights = a.weights()
+    for epsilon in (EPSILON, 0.0):
+        want = _host_rollout(a, weights, epsilon=epsilon)
+        assert want["ended"] >= 8 and want["truncated"] >= 8 and want["capped"] == 0, (epsilon, want["ended"], want["truncated"], want["capped"])
+        ev = a.evaluate(epsilon=epsilon, board_id0=a.round_board_id0(), per_game=True)
+        assert np.array_equal(ev["total_score"], want["total_score"]) and np.array_equal(ev["lengths"], want["lengths"]), epsilon
+        words = eval_words(want["total_score"], want["lengths"], want["final_boards"], want["truncated"], want["greedy"], want["capped"])
+        assert [ev[k] for k in EVAL_SUMMARY] + ev["max_tile_hist"] == words, epsilon
+    guards_intact(a)
 
 
 def test_recorded_actions_replay_through_the_environment():

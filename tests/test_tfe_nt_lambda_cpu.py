@@ -5,13 +5,12 @@ return, the checkpoint's two versions, and what the compiler made of the kernels
 import ctypes as C
 import math
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from tests.native_args import assert_refusals
+from tests.native_args import PTR, assert_refusals, nt_opts, resource_usage
 from tests.test_tfe_nt_cpu import BATCH, NET_CASES, _null_and_odd
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -47,27 +46,10 @@ def test_library_exports_the_entry_point():
 
 # ------------------------------------------------------------------ C2: PULSE_EINVAL before anything is launched
 def _opts(**kw):
-    """a PulseTfeNtLearnLambda every check passes (the buffers are host words: nothing is launched on a refusal), then `kw` over it,
-    with test_tfe_nt_cpu's keywords for the network"""
+    """a PulseTfeNtLearnLambda every check passes, then `kw` over it (native_args.nt_opts' keywords)"""
     from pulselib_amd import _native
-    o = _native.TfeNtLearnLambda()
-    buf = (C.c_int64 * 8)()
-    o._keep = buf
-    ptr = C.addressof(buf)
-    assert ptr % 16 == 0
-    base = dict(tuples=[list(t) for t in TUPLES], net_n=4, net_symmetric=1, net_weights=ptr, n_games=64, max_steps=32, gamma=1.0, lam=0.5,
-                keys=ptr, values=ptr, steps=ptr, lengths=ptr, deltas=ptr, acc=ptr, stats=ptr)
-    base.update(kw)
-    tuples = base.pop("tuples")
-    o.net.n_tuples = base.pop("net_n_tuples", len(tuples))
-    for t, cells in enumerate(tuples[:8]):
-        o.net.tuple_len[t] = base.pop("net_len%d" % t, len(cells))
-        for i, c in enumerate(cells):
-            o.net.cells[t][i] = c
-    o.net.n_weights = base.pop("net_n_weights", sum(16 ** len(c) for c in tuples))
-    for k, v in base.items():
-        setattr(o.net if k.startswith("net_") else o, k[4:] if k.startswith("net_") else k, v)
-    return o
+    return nt_opts(_native.TfeNtLearnLambda, dict(tuples=[list(t) for t in TUPLES], net_n=4, net_symmetric=1, net_weights=PTR, n_games=64, max_steps=32,
+                                                  gamma=1.0, lam=0.5, keys=PTR, values=PTR, steps=PTR, lengths=PTR, deltas=PTR, acc=PTR, stats=PTR), **kw)
 
 
 LAMBDA = [(dict(lam=-0.01), b"lambda must be in [0, 1]"), (dict(lam=1.01), b"lambda must be in [0, 1]"), (dict(lam=math.nan), b"lambda must be in [0, 1]")]
@@ -250,14 +232,8 @@ def test_checkpoint_versions(tmp_path):
 
 # ------------------------------------------------------------------ C7: what the compiler made
 def test_lambda_kernels_use_no_scratch():
-    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_lambda.hip with the Makefile's flags: three kernels (the walk, the scatter with
-    and without symmetry), none with scratch or a spilled vector register.  VGPRs as built for this change: walk 68, scatter 59 / 18."""
-    run = subprocess.run(["make", "-s", "-C", str(ROOT / "pulselib_amd" / "csrc"), "ntuple-lambda-resource-usage"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", run.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", run.stderr)]
-    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", run.stderr)]
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", run.stderr)]
-    print(dict(zip(names, vgprs)))
-    assert len(names) == 3 and sum("tfe_nt_lambda_walk_kernel" in n for n in names) == 1 and sum("tfe_nt_lambda_scatter_kernel" in n for n in names) == 2
-    assert scratch == [0] * 3 and spills == [0] * 3 and len(vgprs) == 3 and max(vgprs) <= 128
+    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_lambda.hip with the Makefile's flags: one kernel, the walk (the scatter is
+    csrc/tfe_ntuple.hip's), without scratch or a spilled vector register.  VGPRs as built: 68."""
+    names, vgprs, scratch, spills = resource_usage("ntuple-lambda-resource-usage")
+    assert len(names) == 1 and "tfe_nt_lambda_walk_kernel" in names[0]
+    assert scratch == [0] and spills == [0] and len(vgprs) == 1 and max(vgprs) <= 128

@@ -4,14 +4,13 @@ from a move written out in plain Python -- and what the compiler made of the ker
 import ctypes as C
 import math
 import re
-import subprocess
 from fractions import Fraction
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from tests.native_args import assert_refusals
+from tests.native_args import PTR, assert_refusals, nt_opts, resource_usage
 from tests.test_tfe_nt_cpu import BATCH, CASES, EPSILON, NET_CASES, WEIGHTS, _opts
 from tests.tfe_search_host import key_of
 
@@ -56,26 +55,10 @@ def test_library_exports_the_two_entry_points():
 
 # ------------------------------------------------------------------ PULSE_EINVAL before anything is launched
 def _search_opts(**kw):
-    """a PulseTfeNtSearch every check passes (the buffers are host words: nothing is launched on a refusal), then `kw` over it, with
-    test_tfe_nt_cpu's keywords for the network"""
+    """a PulseTfeNtSearch every check passes, then `kw` over it (native_args.nt_opts' keywords)"""
     from pulselib_amd import _native
-    o = _native.TfeNtSearch()
-    buf = (C.c_int64 * 8)()
-    o._keep = buf
-    ptr = C.addressof(buf)
-    base = dict(tuples=[list(t) for t in TUPLES], net_n=4, net_symmetric=1, net_weights=ptr, n_boards=73, gamma=1.0, tie_seed=5, round=2,
-                boards=ptr, q=ptr, action=ptr, candidates=ptr)
-    base.update(kw)
-    tuples = base.pop("tuples")
-    o.net.n_tuples = base.pop("net_n_tuples", len(tuples))
-    for t, cells in enumerate(tuples[:8]):
-        o.net.tuple_len[t] = base.pop("net_len%d" % t, len(cells))
-        for i, c in enumerate(cells):
-            o.net.cells[t][i] = c
-    o.net.n_weights = base.pop("net_n_weights", sum(16 ** len(c) for c in tuples))
-    for k, v in base.items():
-        setattr(o.net if k.startswith("net_") else o, k[4:] if k.startswith("net_") else k, v)
-    return o
+    return nt_opts(_native.TfeNtSearch, dict(tuples=[list(t) for t in TUPLES], net_n=4, net_symmetric=1, net_weights=PTR, n_boards=73, gamma=1.0,
+                                             tie_seed=5, round=2, boards=PTR, q=PTR, action=PTR, candidates=PTR), **kw)
 
 
 SEARCH_CASES = NET_CASES + WEIGHTS + [
@@ -266,13 +249,7 @@ def test_the_sum_is_the_tree():
 # ------------------------------------------------------------------ what the compiler made
 def test_search_kernels_use_no_scratch():
     """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search.hip with the Makefile's flags: four kernels, none with scratch or a spilled
-    vector register.  VGPRs as built for this change: search 138 (symmetric) / 112, games 152 / 97."""
-    run = subprocess.run(["make", "-s", "-C", str(ROOT / "pulselib_amd" / "csrc"), "ntuple-search-resource-usage"], capture_output=True, text=True)
-    assert run.returncode == 0, run.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", run.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", run.stderr)]
-    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", run.stderr)]
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", run.stderr)]
-    print(dict(zip(names, vgprs)))
+    vector register.  VGPRs as built: search 138 (symmetric) / 112, games 152 / 97."""
+    names, vgprs, scratch, spills = resource_usage("ntuple-search-resource-usage")
     assert len(names) == 4 and sum("tfe_nt_search_kernel" in n for n in names) == 2 and sum("tfe_nt_search_games_kernel" in n for n in names) == 2
     assert scratch == [0] * 4 and spills == [0] * 4 and len(vgprs) == 4 and max(vgprs) <= 256
