@@ -64,6 +64,7 @@ enum {
 #define PULSE_VIEW_NO_CHUNK       0x2  /* pulse_poker_rollout: one launch per step instead of one launch per chunk     */
 #define PULSE_VIEW_FOUR_LANES     0x4  /* chunk launches: four lanes per table also where two are the default (<= 10 seats) */
 #define PULSE_VIEW_NO_PAIRS       0x8  /* pulse_poker_rollout_until: one check interval per launch instead of two (lag 1)  */
+#define PULSE_VIEW_NO_LONG_LAUNCHES 0x10 /* pulse_poker_rollout_until: at most two check intervals per launch (PULSE_STOPRULE_OPT_LONG_LAUNCHES) */
 typedef struct PulsePokerView {
     int32_t n_games, n_players, active_players, max_players;   /* n_games <= 2^24 per view (shard larger batches) */
     int32_t obs_size, hand_ranks_len;
@@ -264,8 +265,31 @@ int64_t pulse_stoprule_side_launches(void* handle);
 #define PULSE_STOPRULE_OPT_VERDICT_WAIT_TICKS        0
 #define PULSE_STOPRULE_OPT_ALLOW_SHARED_DEVICE_PAIRS 1
 #define PULSE_STOPRULE_OPT_DEBUG_LATE_VERDICTS       2
+/* Long launches (pulse_poker_rollout_until; a lag-1 rule of ONE process whose tables are the whole job): a call that has
+ * more than one pair's worth of full check intervals left enqueues all the intervals its pairs would cover as ONE launch
+ * (the rest of the call, less than two intervals, runs as before: a call returns the same steps and `over` either way).  Its start is the paired launch's (the host's word decides
+ * about the first two chunks); from the third chunk on the launch takes the rule's verdicts itself: at a check point every
+ * wavefront adds its done count to an arrival word, the wavefront that completes the arrivals compares the total with the
+ * rule's threshold and writes the verdict every wavefront reads before the chunk after the next.  Wavefronts wait for each
+ * other there, so the mode is used only where every workgroup of the launch is on the device at once: what
+ * hipOccupancyMaxActiveBlocksPerMultiprocessor answers for the chunk kernel MINUS ONE workgroup (the query can answer one
+ * more than the hardware admits), times the compute units, must cover the grid -- 65,536 tables on an MI355X, not more.  The
+ * wait is bounded by VERDICT_WAIT_TICKS, and by 100 ms where that is longer (wavefronts of one launch are microseconds apart; a
+ * workgroup kept off the device by another stream's or process's kernels is what such a wait would mean): a wavefront whose wait runs out calls the check point off (one compare-and-swap
+ * decides between it and the verdict), the launch ends behind the chunk it is in, exactly as if it had been planned that
+ * long, the episode goes on with paired launches and the handle plans no long launch again.  Same episodes either way.
+ * LONG_LAUNCHES (0 / 1, default 1).  DEBUG_SKIP_DECISION (test hook, one-shot): in the next long launch nobody decides
+ * check point `value` (1 = the launch's first; 0 = none), so its waiters run into the bound and call it off.
+ * DEBUG_RESIDENT_BLOCKS (test hook): the occupancy answer to assume (0: ask the device).
+ * long_stats: out4 = {long launches issued, verdicts taken in-launch, check points called off, 1 if the handle would
+ * still plan long launches (the residency of a grid is only known per call)}; PULSE_EINTERNAL if a launch told the host its
+ * chunk count more than once (it must not: the device counts its writes of that word). */
+#define PULSE_STOPRULE_OPT_LONG_LAUNCHES             3
+#define PULSE_STOPRULE_OPT_DEBUG_SKIP_DECISION       4
+#define PULSE_STOPRULE_OPT_DEBUG_RESIDENT_BLOCKS     5
 int pulse_stoprule_set_option(void* handle, int32_t option, int64_t value);
 int pulse_stoprule_stats(void* handle, int64_t* out4);
+int pulse_stoprule_long_stats(void* handle, int64_t* out4);
 
 /* The shared-memory exchange of the stop rule as an object of its own (host code only; the rule creates one itself when
  * given shm_name).  Every rank maps the POSIX segment `name` (created by whoever comes first; unlink it once all ranks

@@ -25,7 +25,7 @@ PH_FOLDWIN, PH_SHOWDOWN, PH_CLEARDONE, PH_REWARD, PH_OBS = 0x010, 0x020, 0x040, 
 PH_STEP = 0x1FF
 
 # PulsePokerView.flags: kernel variants selectable per view (include/pulse_env.h)
-VIEW_NO_OBS_STAGING, VIEW_NO_CHUNK, VIEW_FOUR_LANES, VIEW_NO_PAIRS = 0x1, 0x2, 0x4, 0x8
+VIEW_NO_OBS_STAGING, VIEW_NO_CHUNK, VIEW_FOUR_LANES, VIEW_NO_PAIRS, VIEW_NO_LONG_LAUNCHES = 0x1, 0x2, 0x4, 0x8, 0x10
 
 AGENT_EXTERNAL, AGENT_RANDOM, AGENT_HEURISTIC_HANDS, AGENT_TIGHT_AGGRESSIVE, AGENT_LOOSE_PASSIVE, AGENT_SMALL_BALL = range(6)
 
@@ -214,6 +214,7 @@ SYMBOLS = {
     "pulse_stoprule_side_launches": (_I64, [_P]),
     "pulse_stoprule_set_option": (C.c_int, [_P, _I32, _I64]),
     "pulse_stoprule_stats": (C.c_int, [_P, _P]),
+    "pulse_stoprule_long_stats": (C.c_int, [_P, _P]),
     "pulse_shm_create": (C.c_int, [C.c_char_p, _I32, _I32, _P]),
     "pulse_shm_all_sum": (C.c_int, [_P, _I64, _I64, _P]),
     "pulse_shm_set_device": (C.c_int, [_P, C.c_char_p]),

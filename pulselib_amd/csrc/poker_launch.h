@@ -18,6 +18,8 @@ struct PolicyArgs {
     const long long* verdict_host = nullptr; long long* verdict_dev = nullptr; long long verdict_id = 0;
     long long* verdict_err = nullptr;      // pinned: set by a launch that gave up waiting for its verdict (the host then runs its steps unpaired)
     long long verdict_ticks = 0;           // ticks of the 100 MHz wall clock thread 0 waits for the word: a launch never waits for a dead host for ever
+    // long launches (pulse_internal.h: StopRuleLong): n_chunks > 2 check intervals, the verdicts from the third chunk on taken in-launch
+    StopRuleLong lng = {};
     PolicyArgs() = default;
     PolicyArgs(uint64_t types, uint64_t seed_, uint64_t step, uint64_t id0) : types_packed(types), seed(seed_), step_counter(step), table_id0(id0) {}
 };
@@ -28,5 +30,9 @@ inline int launch_waves(int n_games, int lpt) { return (int)(((long long)n_games
 // one fused policy + step launch / one chunk of ca.n_steps of them (errors: pulse::finish_launch)
 void launch_policy_step(const PulsePokerView& v, int64_t* actions, float* rewards, const PolicyArgs& pa, ihipStream_t* st);
 void launch_chunk(const PulsePokerView& v, int64_t* actions, float* rewards_even, const PolicyArgs& pa, const ChunkArgs& ca, ihipStream_t* st);
+// what hipOccupancyMaxActiveBlocksPerMultiprocessor answers for the chunk-kernel instantiation launch_chunk would take on this view, with its
+// dynamic LDS size (< 0: the query failed, error recorded); *grid = workgroups of that launch
+int chunk_resident_blocks(const PulsePokerView& v, const float* obs_odd, int* grid);
+int chunk_grid(const PulsePokerView& v);                    // workgroups of a chunk launch on this view
 
 }  // namespace pulse

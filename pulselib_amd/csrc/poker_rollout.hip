@@ -41,12 +41,13 @@ void timer_end(PulseTimer* tm, hipStream_t st) {
 // one chunk launch of a paired sequence (pulse_internal.h: StopRulePair)
 void launch_pair(const PulsePokerView& v_even, const PulsePokerView& v_odd, uint64_t packed, uint64_t seed, uint64_t step_counter0,
                  uint64_t table_id0, int64_t* actions, float* rewards_even, float* rewards_odd, int n_steps, int chunk_steps,
-                 const pulse::StopRulePair& plan, hipStream_t st) {
+                 const pulse::StopRulePair& plan, const pulse::StopRuleLong* lng, hipStream_t st) {
     PolicyArgs pa(packed, seed, step_counter0, table_id0);
+    if (lng) pa.lng = *lng;
     pa.wave_done = plan.wave_done_fin;
     pa.carry[0] = plan.carry[0]; pa.carry[1] = plan.carry[1];
     if (pa.carry[0].n == 0 && pa.carry[1].n > 0) { pa.carry[0] = pa.carry[1]; pa.carry[1].n = 0; }      // (cannot happen: carries are filled in order; kept for safety)
-    pa.wave_done_mid = plan.wave_done_mid; pa.mid_step = plan.n_chunks == 2 ? chunk_steps : 0;
+    pa.wave_done_mid = plan.wave_done_mid; pa.mid_step = plan.n_chunks >= 2 ? chunk_steps : 0;
     pa.verdict_host = plan.verdict_host; pa.verdict_dev = plan.verdict_dev; pa.verdict_id = plan.launch_id; pa.verdict_err = plan.verdict_err;
     pa.verdict_ticks = plan.wait_ticks;
     pulse::launch_chunk(v_even, actions, rewards_even, pa, ChunkArgs{v_odd.obs, rewards_odd, n_steps}, st);
@@ -149,18 +150,36 @@ int pulse_poker_rollout_until(const PulsePokerView* v_even, const PulsePokerView
                        pulse::stoprule_pairs_supported(rule, n_waves_chunk);
     if (pairs) {
         const uint64_t packed = pulse::pack_types(agent_types, v_even->n_players);
+        const int grid = pulse::chunk_grid(*v_even);
         while (done < max_steps && !verdict) {
             const int left = max_steps - done;
-            const int k = left >= 2 * chunk_steps ? 2 : 1;
-            const int n = k == 2 ? 2 * chunk_steps : (left < chunk_steps ? left : chunk_steps);
+            // More than one pair's worth of full check intervals left: ONE launch for all the intervals the pairs would cover,
+            // where the handle and the grid allow it (pulse_internal.h: StopRuleLong); otherwise pairs, exactly as before.
+            // What is then left of the call (less than two intervals) runs with one interval per launch as it always has,
+            // so a call returns the same (steps, over) as with pairs: a launch that runs all its chunks reports `over` with
+            // the NEXT launch, and whether a call's last launch is such a one must not depend on the mode.
+            const int m = 2 * (left / (2 * chunk_steps));
+            bool lng = false;
+            if (m > 2 && m <= pulse::kLongMaxChunks && !(v_even->flags & PULSE_VIEW_NO_LONG_LAUNCHES)) {
+                int resident = 0;
+                if (pulse::stoprule_long_needs_query(rule, grid)) {
+                    resident = pulse::chunk_resident_blocks(*v_even, v_odd->obs, nullptr);
+                    if (resident < 0) return resident;
+                }
+                lng = pulse::stoprule_long_launch_supported(rule, n_waves_chunk, grid, resident);
+            }
+            const int k = lng ? m : left >= 2 * chunk_steps ? 2 : 1;
+            const int n = lng ? m * chunk_steps : k == 2 ? 2 * chunk_steps : (left < chunk_steps ? left : chunk_steps);
             pulse::StopRulePair plan;
             const int c = pulse::stoprule_pair_claim(rule, n_waves_chunk, k, &plan);
             if (c < 0) return c;
             if (c == 1) { verdict = 1; break; }
             if (tm && time_every > 0 && !tm->open && (tm->calls % time_every) == 0) if (int rc = timer_begin(tm, st)) return rc;
             if (tm) ++tm->calls;
+            pulse::StopRuleLong in_launch{};
+            if (lng) if (int rc = pulse::stoprule_long_plan(rule, &plan, n_waves_chunk, chunk_steps, &in_launch)) return rc;
             launch_pair(parity ? *v_odd : *v_even, parity ? *v_even : *v_odd, packed, seed, step_counter0 + (uint64_t)done, table_id0, actions,
-                        parity ? rewards_odd : rewards_even, parity ? rewards_even : rewards_odd, n, chunk_steps, plan, st);
+                        parity ? rewards_odd : rewards_even, parity ? rewards_even : rewards_odd, n, chunk_steps, plan, lng ? &in_launch : nullptr, st);
             if (int rc = pulse::finish_launch("pulse_poker_rollout_until")) return rc;
             if (int rc = pulse::stoprule_pair_commit(rule, &plan, n_waves_chunk, st)) return rc;
             int chunks_run = 0, gave_up = 0;
@@ -169,6 +188,8 @@ int pulse_poker_rollout_until(const PulsePokerView* v_even, const PulsePokerView
                 fell_back = !verdict;       // (unless the episode had ended before it anyway) its steps run below, one check interval per launch
                 break;
             }
+            // a long launch the host's word let run: how far it went is its own news
+            if (lng && chunks_run == k) if (int rc = pulse::stoprule_long_verdict(rule, &plan, &chunks_run, &verdict)) return rc;
             const int ran = chunks_run == k ? n : chunks_run * chunk_steps;
             done += ran; parity ^= ran & 1;
             if (tm && tm->open) {

@@ -57,7 +57,103 @@ static_assert(offsetof(StepKernargs, v) == 0 && offsetof(StepKernargs, actions) 
 static_assert(offsetof(StepKernargs, pa) == sizeof(PulsePokerView) + 24 && offsetof(StepKernargs, ca) == offsetof(StepKernargs, pa) + sizeof(PolicyArgs), "kernel arguments");
 // (PolicyArgs' two carried check points are pulse::StopRuleCarry records: the same words, in the same places, as when they were eight loose fields)
 static_assert(sizeof(pulse::StopRuleCarry) == 32 && offsetof(PolicyArgs, wave_done) == 32 && offsetof(PolicyArgs, carry) == 40 &&
-              offsetof(PolicyArgs, wave_done_mid) == 104 && offsetof(PolicyArgs, verdict_host) == 120 && sizeof(PolicyArgs) == 160, "PolicyArgs layout");
+              offsetof(PolicyArgs, wave_done_mid) == 104 && offsetof(PolicyArgs, verdict_host) == 120 && offsetof(PolicyArgs, lng) == 160 &&
+              sizeof(pulse::StopRuleLong) == 72 && sizeof(PolicyArgs) == 232, "PolicyArgs layout");
+
+// ---- long launches (pulse_internal.h: StopRuleLong): the check points a launch takes itself.
+// The arrival words are agent-scope atomics (performed at the memory side: the per-XCD L2s are not coherent), the verdict
+// words RELAXED system-scope accesses like the relayed word of a paired launch: every word carries its own key {launch
+// id, check point}, and a wavefront's count travels inside its arrival, so no other data needs ordering with them.
+typedef __attribute__((address_space(1))) long long GlobalLL;
+constexpr int kLongSetWords = (1 + pulse::kLongWords) * kVerdictStride;      // long longs of one set of arrival words
+
+// Settles the verdict of check point r with `word` (a decision, or "called off") unless the other word landed first: a
+// compare-and-swap on the slot's first copy from whatever an earlier check point left there (a word with another key:
+// "pending"), then the remaining copies.  Returns the word that stands.  Whoever wrote it tells the host, where it
+// settles the launch's length.  Called by every active lane of the wavefront (the lanes are 0 .. n - 1).
+__device__ __forceinline__ long long long_settle(StepKernargsPtr ka, int r, long long word) {
+    GlobalLL* slot = (GlobalLL*)ka->pa.lng.verdicts + (size_t)(r & (pulse::kLongSlots - 1)) * 64 * kVerdictStride;
+    const int lane = threadIdx.x & 63;
+    long long stands = 0; int won = 0;
+    if (lane == 0) {
+        long long cur = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        for (;;) {
+            if ((cur >> 8) == (word >> 8)) { stands = cur; break; }
+            if (__hip_atomic_compare_exchange_strong(slot, &cur, word, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)) { stands = word; won = 1; break; }
+        }
+    }
+    won = __builtin_amdgcn_readfirstlane(won);
+    stands = ((long long)__builtin_amdgcn_readfirstlane((int)(stands >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)stands);
+    if (won) {
+        const int n_act = __popcll(__ballot(1));
+        for (int k = lane; k < 64; k += n_act)
+            if (k) __hip_atomic_store(slot + k * kVerdictStride, stands, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        const int flags = (int)(stands & 3), m = ka->pa.lng.n_chunks;
+        // (ONE such word per launch: behind an "over" or "called off" nobody arrives at a later check point -- long_check_point.
+        // The host holds it to that: the second word counts the writes.)
+        if (lane == 0 && (flags || r == m - 3)) {
+            __hip_atomic_store((GlobalLL*)ka->pa.lng.host, (ka->pa.verdict_id << 16) | (long long)((flags ? r + 2 : m) << 8) | flags, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_fetch_add((GlobalLL*)ka->pa.lng.host + 1, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    return stands;
+}
+
+// The check point behind the launch's q-th chunk (q >= 1): `c` = this wavefront's done tables, `wid` = its number in the
+// launch.  Stores the count in the ring, reads the verdict of check point q - 2 where another chunk would follow, and --
+// only if that verdict lets the launch go on -- arrives (check points the launch decides: r = q - 1 <= m - 3; the last two
+// are the next launch's carries, as after a pair).  The order matters: every wavefront reads the same verdict word, so behind
+// an "over" or a "called off" NO wavefront arrives again, no later verdict is decided, and the word that told the host how
+// many chunks the launch runs stays the only one (arriving first, the next check point was decided "over" too and its word
+// overwrote the host's a chunk later).  true: the launch ends here.
+__device__ __forceinline__ bool long_check_point(StepKernargsPtr ka, int q, int c, uint32_t wid, bool arrives) {
+    const int m = ka->pa.lng.n_chunks, r = q - 1;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    if (lane0) stg(ka->pa.lng.partials, ((uint32_t)((ka->pa.lng.slot0 + r) & 3) * (uint32_t)ka->pa.lng.max_partials + wid) * 4u, (uint32_t)c);
+    if (q >= 2 && q < m) {
+        const int rv = q - 2;
+        const GlobalLL* copy = (const GlobalLL*)ka->pa.lng.verdicts + ((size_t)(rv & (pulse::kLongSlots - 1)) * 64 + (wid & 63u)) * kVerdictStride;
+        const long long key = (ka->pa.verdict_id << 8) | (long long)rv;
+        const long long t0 = wall_clock64();
+        long long w;
+        for (;;) {
+            w = __hip_atomic_load(copy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if ((w >> 8) == key) break;
+            if (wall_clock64() - t0 > ka->pa.lng.wait_ticks) { w = long_settle(ka, rv, (key << 8) | 2); break; }      // waited long enough: call it off (or read what landed first)
+            __builtin_amdgcn_s_sleep(32);
+        }
+        if ((__builtin_amdgcn_readfirstlane((int)w) & 3) != 0) return true;
+    }
+    if (arrives && r <= m - 3) {
+        long long word = 0;
+        if (lane0) {
+            const int W = ka->pa.lng.n_words, k = (int)(wid % (uint32_t)W);
+            GlobalLL* top = (GlobalLL*)ka->pa.lng.arrive + (r & 1) * kLongSetWords;
+            GlobalLL* mine = top + (1 + k) * kVerdictStride;
+            const long long old = __hip_atomic_fetch_add(mine, (1ll << 32) | (long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((int)(old >> 32) + 1 == (ka->pa.lng.n_waves + W - 1 - k) / W) {        // this word's last arrival: on to the second level
+                const long long sum = (old & 0xFFFFFFFFll) + c;
+                __hip_atomic_store(mine, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the word is zero again before anybody can learn that it is complete
+                const long long old2 = __hip_atomic_fetch_add(top, (1ll << 32) | sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if ((int)(old2 >> 32) + 1 == W) {
+                    const long long total = (old2 & 0xFFFFFFFFll) + sum;
+                    __hip_atomic_store(top, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    if (r != ka->pa.lng.skip_cp)
+                        word = (ka->pa.verdict_id << 16) | (long long)(r << 8) | (total >= (long long)ka->pa.lng.over_from ? 1 : 0);
+                }
+            }
+        }
+        const int has = __builtin_amdgcn_readfirstlane(word != 0 ? 1 : 0);
+        if (has) {
+            word = ((long long)__builtin_amdgcn_readfirstlane((int)(word >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)word);
+            (void)long_settle(ka, r, word);
+        }
+    }
+    return false;
+}
 
 // In-kernel timeline (diagnostic build only, -DPULSE_STAMPS=1 -> libpulse_hip_stamps.so; no stamp executes
 // in the product): lane 0 of every wavefront stores s_memtime at phase boundaries into a buffer of its own.
@@ -378,13 +474,13 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
     // the caller's action word was loaded with the state; pin its arrival to the prologue's waits: left pending, its one
     // use after the loop (the final store of the action) became an s_waitcnt vmcnt(0) behind every store of the last step
     if (MULTI) asm volatile("" : "+v"(act64));
-    const int n_steps = MULTI ? (stop_mid ? pa.mid_step : ca.n_steps) : 1;        // (the verdict is known: no exit from inside the loop)
+    int n_steps = MULTI ? (stop_mid ? pa.mid_step : ca.n_steps) : 1;        // (a long launch cuts it at a check point: long_check_point)
     // output buffers of this step / of the next one: swapped at the end of every step (scalar moves; a select on the
     // step's parity made the compiler keep both sets of per-lane addresses alive across the loop -- and spill them)
     float* obs_dst = v.obs; float* obs_nxt = MULTI ? ca.obs_odd : v.obs;
     uint8_t* done_dst = v.is_done_out; uint8_t* done_nxt = v.is_done;
     float* rew_dst = rewards; float* rew_nxt = MULTI ? ca.rewards_odd : rewards;
-    const int mid_step = MULTI ? pa.mid_step : 0;          // > 0: the launch covers two check intervals, the first one mid_step steps long
+    int cp_at = MULTI ? pa.mid_step : 0;          // > 0: the launch covers several check intervals, the first check point is behind step cp_at
     for (int i = 0; i < n_steps; ++i) {
         // In a chunk, everything derived from the lane's position in its table (seat numbers, `seat < A` masks, ...)
         // is re-derived inside the step: hoisted out of the loop those lane masks filled the scalar registers and were
@@ -733,11 +829,28 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
         }
         STAMP(9);   // observation stores issued
         if ((PH & PULSE_PH_ADVANCE) && j == 0) sto_in_loop(done_dst, ut, (uint8_t)(done ? 1 : 0));      // ping-pong buffer: always written
-        if (MULTI && i + 1 == mid_step) {        // the check point in the middle of a paired launch
+        if (MULTI && i + 1 == cp_at) {        // the check point in the middle of a paired launch / a check point of a long one
             StepKernargsPtr ka = (StepKernargsPtr)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(ka));
             const int c = __popcll(__ballot(done && j == 0));
-            if ((threadIdx.x & 63) == 0) stg(ka->pa.wave_done_mid, (uint32_t)(blockIdx.x * (BLK / 64) + (threadIdx.x >> 6)) * 4u, (uint32_t)c);
+            const uint32_t wid = (uint32_t)(blockIdx.x * (BLK / 64) + (threadIdx.x >> 6));
+            if (ka->pa.lng.n_chunks == 0) {
+                if ((threadIdx.x & 63) == 0) stg(ka->pa.wave_done_mid, wid * 4u, (uint32_t)c);
+            } else {
+                const int cs = ka->pa.lng.chunk_steps;
+#if PULSE_STAMPS
+                const long long cp_t0 = clock64();
+#endif
+                if (long_check_point(ka, cp_at / cs, c, wid, !stop_mid)) n_steps = i + 1;
+#if PULSE_STAMPS
+                if ((threadIdx.x & 63) == 0 && g_stamp_buf) {       // slots 12..14: ticks inside the check points, their number, the longest one
+                    const long long dt = clock64() - cp_t0;
+                    unsigned long long* s = g_stamp_buf + (size_t)wid * 16;
+                    s[12] += (unsigned long long)dt; s[13] += 1; if ((unsigned long long)dt > s[14]) s[14] = (unsigned long long)dt;
+                }
+#endif
+                cp_at += cs;
+            }
         }
         if (MULTI) {
             float* fo = obs_dst; obs_dst = obs_nxt; obs_nxt = fo;
@@ -864,6 +977,21 @@ void launch_one(const PulsePokerView& v, int64_t* actions, const int32_t* actor_
     pulse::launch_lds(fn, step_grid(v, LPT).x, kStepBlock, lds, st, true, v, actions, actor_idx, rewards, pa, ca);
 }
 
+// the occupancy query for exactly the instantiation and LDS size launch_one takes
+template <uint32_t PH, bool POLICY, int LPT, int SPL, int MULTI>
+int resident_one(const PulsePokerView& v, const float* obs_odd) {
+    constexpr int TPW = 64 / LPT;
+    const bool wobs = obs_staging(v, obs_odd, LPT);
+    const size_t lds = sizeof(int32_t) * (size_t)(kStepBlock / 64) * (size_t)chunk_lds_dwords(v.obs_size, LPT * SPL, TPW, MULTI == 2);
+    const auto fn = wobs ? &poker_step_kernel<PH, POLICY, LPT, SPL, true, MULTI> : &poker_step_kernel<PH, POLICY, LPT, SPL, false, MULTI>;
+    int blocks = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(fn), kStepBlock, lds);
+    if (e != hipSuccess) return pulse::fail_hip((int)e, "chunk kernel: occupancy query");
+    return blocks;
+}
+
+inline bool chunk_slim(const PulsePokerView& v) { return v.n_games > 81920; }     // the two-lane chunk's slim LDS image (launch_chunk)
+
 template <uint32_t PH, bool POLICY, int MULTI>
 void launch_any(const PulsePokerView& v, int64_t* actions, const int32_t* actor_idx, float* rewards, const PolicyArgs& pa, const ChunkArgs& ca,
                 hipStream_t st) {
@@ -889,9 +1017,17 @@ void pulse::launch_chunk(const PulsePokerView& v, int64_t* actions, float* rewar
         // MI355X), the slim one 12.  Batches with more wavefronts than that take the slim image -- 67.0 vs 68.9 us per chunk
         // at 131,072 tables, 84.9 vs 91.8 at 196,608, 361 vs 403 at 1,048,576; where every wavefront is resident anyway it
         // only costs the river's divisions (37.7 vs 37.2 us at 65,536 tables).
-        if (v.n_games > 81920) launch_one<PULSE_PH_STEP, true, 2, 5, 2>(v, actions, nullptr, rewards_even, pa, ca, st);
+        if (chunk_slim(v)) launch_one<PULSE_PH_STEP, true, 2, 5, 2>(v, actions, nullptr, rewards_even, pa, ca, st);
         else launch_one<PULSE_PH_STEP, true, 2, 5, 1>(v, actions, nullptr, rewards_even, pa, ca, st);
     } else launch_any<PULSE_PH_STEP, true, 1>(v, actions, nullptr, rewards_even, pa, ca, st);
+}
+
+int pulse::chunk_grid(const PulsePokerView& v) { return (int)step_grid(v, lanes_for(v, true)).x; }
+
+int pulse::chunk_resident_blocks(const PulsePokerView& v, const float* obs_odd, int* grid) {
+    if (grid) *grid = chunk_grid(v);
+    if (lanes_for(v, true) == 2) return chunk_slim(v) ? resident_one<PULSE_PH_STEP, true, 2, 5, 2>(v, obs_odd) : resident_one<PULSE_PH_STEP, true, 2, 5, 1>(v, obs_odd);
+    return v.max_players <= 12 ? resident_one<PULSE_PH_STEP, true, 4, 3, 1>(v, obs_odd) : resident_one<PULSE_PH_STEP, true, 4, 4, 1>(v, obs_odd);
 }
 
 extern "C" {

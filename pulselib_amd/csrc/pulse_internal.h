@@ -80,4 +80,44 @@ int stoprule_pair_commit(PulseStopRule* h, const StopRulePair* plan, int n_parti
 // *gave_up = 1: the host was too late, the launch ran nothing, the handle is back before it and pairs no more (stoprule.hip).
 int stoprule_pair_verdict(PulseStopRule* h, const StopRulePair* plan, int* chunks_run, int* over, int* gave_up);
 
+// Long launches (lag 1, a local rule, every workgroup of the launch resident at once): ONE launch covers the check points
+// [a, a + m), m > 2.  Its start is the pair's protocol (carries of a - 2 and a - 1, the host's verdict word, the give-up path):
+// chunks 0 and 1 run on the host's word.  Chunk r + 2 runs iff check point a + r did not end the episode, and that count
+// is taken INSIDE the launch: at check point r <= m - 3 every wavefront adds {1 << 32 | its done count} to an arrival word
+// (spread over n_words words with a second level; two sets, by the parity of r, zero between launches), the wavefront that
+// completes the arrivals has the total, compares it with over_from and writes the verdict word {launch id << 16 | r << 8 |
+// over | called off << 1} into slot r % kLongSlots of `verdicts` -- a compare-and-swap on the slot's first copy, then the
+// other 63 copies.  A wavefront reads verdict r before chunk r + 2 -- and BEFORE it arrives for check point r + 1: behind an
+// over or called-off word nobody arrives again, so the host is told once --; one that has waited wait_ticks calls the check point
+// off with the same compare-and-swap, so exactly one word lands and every wavefront reads the same one: over or called
+// off, the launch ends behind chunk r + 1, leaving the memory of a launch planned r + 2 chunks long.  Whoever wrote the
+// word that settles the launch's length tells the host: {launch id << 16 | chunks run << 8 | over | called off << 1} -- an
+// over or called-off word at once, a "not over" at check point m - 3 (the launch runs to its cap) otherwise.
+// (In the kernel's argument block as it stands here: poker_step.hip asserts the layout.)
+struct StopRuleLong {
+    long long* arrive;            // device, zero between launches: [2 sets][1 + kLongWords] words, one 128-byte line each
+    long long* verdicts;          // device: [kLongSlots][64 copies], one line each
+    long long* host;              // pinned: what the host learns (one word)
+    uint32_t* partials;           // the ring of per-wavefront counts: check point c at partials + (c % 4) * max_partials
+    uint32_t over_from;           // the smallest count that ends the episode (the host's own float comparison)
+    int max_partials;
+    int n_chunks;                 // m; 0: not a long launch
+    int chunk_steps;
+    int slot0;                    // a % 4
+    int skip_cp;                  // test hook: the completing wavefront of this check point does not decide (-1: none)
+    int n_waves;                  // wavefronts of the launch = arrivals per check point
+    int n_words;                  // first-level arrival words in use (min(kLongWords, n_waves))
+    long long wait_ticks;         // how long a wavefront waits for a verdict of its own launch before it calls the check point off
+};
+constexpr int kLongWords = 32, kLongSlots = 4, kLongMaxChunks = 64;
+// May rollout_until plan long launches of `grid` workgroups on this handle?  `resident_blocks`: the occupancy query's answer
+// for the chunk kernel (asked by the caller once per handle and grid: a negative value = "ask", see stoprule_long_needs_query).
+bool stoprule_long_needs_query(const PulseStopRule* h, int grid);
+bool stoprule_long_launch_supported(PulseStopRule* h, int n_partials, int grid, int resident_blocks);
+// after stoprule_pair_claim(.., n_chunks = m > 2, ..): the in-launch part of the plan
+int stoprule_long_plan(PulseStopRule* h, const StopRulePair* plan, int n_partials, int chunk_steps, StopRuleLong* out);
+// after stoprule_pair_verdict let the launch run (chunks_run == m there): how many chunks it really ran, whether the rule
+// ended the episode; a called-off check point is counted and switches long launches off for the handle's life
+int stoprule_long_verdict(PulseStopRule* h, const StopRulePair* plan, int* chunks_run, int* over);
+
 }  // namespace pulse

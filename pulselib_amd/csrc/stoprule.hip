@@ -111,6 +111,7 @@ int pulse_comm_destroy(void* comm) {
 namespace {
 constexpr int kSlots = 4;                 // check points in flight: lag < kSlots
 constexpr int kMaxPartials = 1024;        // workgroups of the flag-counting kernel
+constexpr long long kLongWaitTicks = 10000000ll;        // 100 ms: the bound of a wait for a verdict taken inside the launch
 constexpr int kVerdictCopies = 64, kVerdictStride = 16;     // a relayed verdict word: 64 copies, one 128-byte line each (poker_step.hip)
 
 // What the host polls, in coherent pinned memory: the counts of one check point, then its sequence number (written
@@ -271,6 +272,16 @@ struct PulseStopRule {
     int device_private;                   // shm exchange: -1 = not asked yet, 0 = another rank shares this GPU (no pairs), 1 = no
     bool allow_shared_device_pairs;
     int debug_late;                       // test hook: that many coming verdicts are treated as "host too late"
+    // long launches (pulse_internal.h: StopRuleLong)
+    long long* long_arrive;               // device [2][1 + kLongWords] lines: the arrival words, zeroed once (whoever completes a word sets it back)
+    long long* long_verdicts;             // device [kLongSlots][kVerdictCopies] lines: the in-launch verdict words
+    long long* long_host;                 // pinned: {launch id << 16 | chunks run << 8 | flags} of the newest long launch
+    bool long_on, long_off;               // the option (default on) / a check point was called off: no long launch for the rest of the handle's life
+    int long_grid, long_grid_ok;          // the residency gate's answer is asked once per handle and grid
+    int debug_resident, debug_skip;       // test hooks: the occupancy answer to assume (0: ask) / the check point (1-based, one-shot) nobody decides
+    long long long_words_read;            // long launches whose word the host has read; long_host[1] counts the launches' writes of it: one each
+    bool shm_asked;                       // created with a shared-memory segment's name (a world of one is local mode all the same)
+    long long long_launches, long_taken, long_called_off;
     std::chrono::steady_clock::time_point pair_enqueued;
 };
 
@@ -381,10 +392,11 @@ int pair_count(PulseStopRule* h, long long c, bool* over) {
 }  // namespace
 
 int stoprule_pair_claim(PulseStopRule* h, int n_partials, int n_chunks, StopRulePair* plan) {
-    if (!plan || n_chunks < 1 || n_chunks > 2 || !stoprule_pairs_supported(h, n_partials)) return fail(PULSE_EINVAL, "stop rule: paired launch not possible with this handle");
+    if (!plan || n_chunks < 1 || n_chunks > kLongMaxChunks || !stoprule_pairs_supported(h, n_partials)) return fail(PULSE_EINVAL, "stop rule: paired launch not possible with this handle");
     if (const long long gave_up = __atomic_load_n(h->verdict_host + kSlots, __ATOMIC_ACQUIRE)) {
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "stop rule: paired launch %lld waited 20 s for its verdict and ran nothing (a rank of the job is gone or stalled)", gave_up);
+        char msg[192];
+        std::snprintf(msg, sizeof msg, "stop rule: paired launch %lld waited %.3g s for its verdict and ran nothing (a rank of the job is gone or stalled)", gave_up,
+                      (double)h->verdict_wait_ticks * 1e-8);
         return fail(PULSE_EINTERNAL, msg);
     }
     if (h->over_known) return 1;                                       // a count read earlier already ended the episode
@@ -398,8 +410,8 @@ int stoprule_pair_claim(PulseStopRule* h, int n_partials, int n_chunks, StopRule
     plan->wait_ticks = h->verdict_wait_ticks;
     uint32_t* first = h->partials_dev + (size_t)(a % kSlots) * h->max_partials;
     uint32_t* second = h->partials_dev + (size_t)((a + 1) % kSlots) * h->max_partials;
-    plan->wave_done_mid = n_chunks == 2 ? first : nullptr;
-    plan->wave_done_fin = n_chunks == 2 ? second : first;
+    plan->wave_done_mid = n_chunks >= 2 ? first : nullptr;
+    plan->wave_done_fin = n_chunks > 2 ? nullptr : n_chunks == 2 ? second : first;      // (a long launch stores every count through the ring: StopRuleLong)
     // carries: this episode's check points a - 2, a - 1 whose publication nobody has enqueued yet
     int k = 0;
     for (long long c = a - 2; c < a; ++c) {
@@ -439,8 +451,12 @@ int stoprule_pair_verdict(PulseStopRule* h, const StopRulePair* plan, int* chunk
     if (h->debug_late > 0) { --h->debug_late; late = true; }
     if (late) {
         const auto t0 = std::chrono::steady_clock::now();
-        while (__atomic_load_n(plan->verdict_err, __ATOMIC_ACQUIRE) != plan->launch_id) {
+        for (long long polls = 1; __atomic_load_n(plan->verdict_err, __ATOMIC_ACQUIRE) != plan->launch_id; ++polls) {
             usleep(100);
+            if ((polls & 0x3FF) == 0) {                         // now and then: is the device still alive?
+                const hipError_t q = hipStreamQuery(h->last_stream);
+                if (q != hipSuccess && q != hipErrorNotReady) return fail_hip((int)q, "stop rule: the stream of a paired launch");
+            }
             if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0 * wait_s + 5.0)
                 return fail(PULSE_EINTERNAL, "stop rule: a paired launch neither took its verdict nor gave up (is the device gone?)");
         }
@@ -451,10 +467,98 @@ int stoprule_pair_verdict(PulseStopRule* h, const StopRulePair* plan, int* chunk
         return 0;
     }
     // (stop_mid only means something to a launch of two chunks; a one-chunk launch whose chunk is the episode's last runs it)
-    const long long word = (plan->launch_id << 8) | (skip ? 1 : 0) | (stop && plan->n_chunks == 2 ? 2 : 0);
+    const long long word = (plan->launch_id << 8) | (skip ? 1 : 0) | (stop && plan->n_chunks >= 2 ? 2 : 0);
     __atomic_store_n(const_cast<long long*>(plan->verdict_host), word, __ATOMIC_RELEASE);
     *chunks_run = skip ? 0 : (stop ? 1 : plan->n_chunks);
     *over = (skip || stop) ? 1 : 0;
+    return 0;
+}
+
+// ---- long launches (pulse_internal.h: StopRuleLong)
+// A long launch tells the host ONCE how many chunks it runs (the device counts its writes of the word in long_host[1]): a second
+// write would be a second, larger chunk count for the same launch, and a host that read it would count steps that never ran.
+int long_word_written_once(const PulseStopRule* h) {
+    const long long writes = __atomic_load_n(h->long_host + 1, __ATOMIC_ACQUIRE);
+    if (writes > h->long_words_read) return fail(PULSE_EINTERNAL, "stop rule: a long launch wrote its chunk count more than once");
+    return 0;
+}
+
+bool stoprule_long_needs_query(const PulseStopRule* h, int grid) { return h && h->long_grid != grid && h->debug_resident == 0; }
+
+bool stoprule_long_launch_supported(PulseStopRule* h, int n_partials, int grid, int resident_blocks) {
+    // a local rule only: with several ranks the count needs the host (n_global == n_local rules out a shard of a larger job)
+    if (!h || !h->long_on || h->long_off || h->mode != kModeLocal || h->shm_asked || h->n_global != (long long)h->n_local) return false;
+    if (!stoprule_pairs_supported(h, n_partials)) return false;            // lag 1, pairs not switched off
+    if (h->long_grid != grid || h->debug_resident != 0) {
+        // Residency: every wavefront of the launch waits for every other one, so all workgroups must be on the device at
+        // once.  The occupancy query can answer one workgroup per compute unit more than the hardware admits (the surplus
+        // workgroup then queues until a resident one exits): one is taken off its answer.
+        const int blocks = h->debug_resident != 0 ? h->debug_resident : resident_blocks;
+        h->long_grid = grid;
+        h->long_grid_ok = blocks > 1 && (long long)(blocks - 1) * device_cus() >= (long long)grid ? 1 : 0;
+        if (h->debug_resident != 0) h->long_grid = -1;                     // (an assumed answer is not remembered)
+    }
+    return h->long_grid_ok != 0;
+}
+
+int stoprule_long_plan(PulseStopRule* h, const StopRulePair* plan, int n_partials, int chunk_steps, StopRuleLong* out) {
+    if (!h || !plan || !out || plan->n_chunks <= 2 || plan->n_chunks > kLongMaxChunks) return fail(PULSE_EINVAL, "stop rule: not a long launch");
+    // the smallest count for which the rule's own comparison, (double)count > threshold * (double)n_global, holds
+    const double limit = h->threshold * (double)h->n_global;
+    long long from = limit < 0.0 ? 0 : limit >= 4294967294.0 ? 4294967295ll : (long long)limit;
+    while (from < 4294967295ll && !((double)from > limit)) ++from;
+    *out = StopRuleLong{};
+    out->arrive = h->long_arrive; out->verdicts = h->long_verdicts; out->host = h->long_host;
+    out->partials = h->partials_dev; out->max_partials = h->max_partials;
+    out->over_from = (uint32_t)from;
+    out->n_chunks = plan->n_chunks; out->chunk_steps = chunk_steps;
+    out->slot0 = (int)(plan->first_check_point % kSlots);
+    out->skip_cp = h->debug_skip > 0 && h->debug_skip - 1 <= plan->n_chunks - 3 ? h->debug_skip - 1 : -1;      // (a check point somebody waits for)
+    h->debug_skip = 0;
+    out->n_waves = n_partials;
+    out->n_words = kLongWords < n_partials ? kLongWords : n_partials;
+    // Wavefronts of one launch are microseconds apart; a verdict that is not there after 100 ms will not come (a workgroup that
+    // is not resident after all: another stream's or another process's kernels on the device).  The wait for the HOST's word
+    // keeps its own, longer bound; an option below 100 ms holds for both.
+    out->wait_ticks = h->verdict_wait_ticks < kLongWaitTicks ? h->verdict_wait_ticks : kLongWaitTicks;
+    if (int rc = long_word_written_once(h)) return rc;
+    ++h->long_launches;
+    return 0;
+}
+
+int stoprule_long_verdict(PulseStopRule* h, const StopRulePair* plan, int* chunks_run, int* over) {
+    volatile long long* word = h->long_host;
+    const auto t0 = std::chrono::steady_clock::now();
+    const double limit_s = 60.0 + 2.0 * (double)plan->wait_ticks * 1e-8 * plan->n_chunks;
+    bool finished = false;
+    for (long long spins = 1; (*word >> 16) != plan->launch_id; ++spins) {
+        __builtin_ia32_pause();
+        if ((spins & 0xFFFFF) == 0) {                       // now and then: is the device still alive?
+            if (finished) return fail(PULSE_EINTERNAL, "stop rule: a long launch ended without telling how many chunks it ran");
+            const hipError_t q = hipStreamQuery(h->last_stream);
+            if (q != hipSuccess && q != hipErrorNotReady) return fail_hip((int)q, "stop rule: the stream of a long launch");
+            finished = q == hipSuccess;                     // (one more look at the word: it was written before the launch ended)
+            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit_s)
+                return fail(PULSE_EINTERNAL, "stop rule: no word from a long launch (is the device gone?)");
+        }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    const long long w = *word;
+    ++h->long_words_read;
+    const int ran = (int)((w >> 8) & 0xFF), flags = (int)(w & 0xFF);
+    if (ran < 2 || ran > plan->n_chunks) return fail(PULSE_EINTERNAL, "stop rule: a long launch reported an impossible chunk count");
+    const long long a = plan->first_check_point;
+    const bool is_over = (flags & 1) != 0, off = (flags & 2) != 0;
+    // Check points below a + ran - 2 did not end the episode.  a + ran - 2 did (over); or it was never decided (called off), or
+    // the launch ran to its cap and did not take it: it is then left, like a + ran - 1, to the next launch, which carries both
+    // counts as after a pair -- and, as after a pair that ran both its chunks, `over` comes with that launch.
+    const long long known = is_over ? a + ran - 1 : a + ran - 2;
+    h->submitted = a + ran;
+    if (h->scheduled < known) h->scheduled = known;
+    h->verdicts_known = known; h->over_known = is_over;
+    h->long_taken += known - a;
+    if (off) { ++h->long_called_off; h->long_off = true; }
+    *chunks_run = ran; *over = is_over ? 1 : 0;
     return 0;
 }
 
@@ -471,11 +575,13 @@ int pulse_stoprule_create(int32_t n_local, int64_t n_global, double threshold, i
     h->n_local = n_local; h->n_global = n_global; h->threshold = threshold; h->lag = lag;
     h->verdict_wait_ticks = 2000000000ll;                   // 20 s
     h->device_private = -1;
+    h->long_on = true; h->long_grid = -1;
     for (int i = 0; i < kSlots; ++i) h->global_known_idx[i] = -1;
     h->comm = static_cast<PulseComm*>(comm); h->rank = rank; h->world = world;
     // a communicator is honoured whatever its size: a world of one is a valid all-reduce, and it is what a one-GPU box
     // can run of the side-stream path (event hand-over, sum, ncclAllReduce, publish)
     h->mode = h->comm ? kModeRccl : (shm_name && world > 1) ? kModeShm : kModeLocal;
+    h->shm_asked = shm_name != nullptr;
     h->max_partials = (int)(((long long)n_local * 4 + 63) / 64) + 4;          // one per wavefront of a step launch (4 lanes per table at most)
     if (h->max_partials < kMaxPartials) h->max_partials = kMaxPartials;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->partials_dev), (size_t)kSlots * h->max_partials * sizeof(uint32_t));
@@ -484,6 +590,14 @@ int pulse_stoprule_create(int32_t n_local, int64_t n_global, double threshold, i
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->verdict_host), (kSlots + 1) * sizeof(long long), hipHostMallocCoherent | hipHostMallocMapped);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->verdict_dev), kSlots * kVerdictCopies * kVerdictStride * sizeof(long long));
     if (e == hipSuccess) e = hipMemset(h->verdict_dev, 0, kSlots * kVerdictCopies * kVerdictStride * sizeof(long long));
+    const size_t arrive_bytes = 2 * (1 + pulse::kLongWords) * kVerdictStride * sizeof(long long);
+    const size_t long_verdict_bytes = (size_t)pulse::kLongSlots * kVerdictCopies * kVerdictStride * sizeof(long long);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->long_arrive), arrive_bytes);
+    if (e == hipSuccess) e = hipMemset(h->long_arrive, 0, arrive_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->long_verdicts), long_verdict_bytes);
+    if (e == hipSuccess) e = hipMemset(h->long_verdicts, 0, long_verdict_bytes);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->long_host), 8 * sizeof(long long), hipHostMallocCoherent | hipHostMallocMapped);
+    if (e == hipSuccess) std::memset(h->long_host, 0, 8 * sizeof(long long));
     if (e == hipSuccess && h->mode == kModeRccl) {
         e = hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking);
         for (int i = 0; i < kSlots && e == hipSuccess; ++i) {
@@ -531,6 +645,9 @@ int pulse_stoprule_destroy(void* handle) {
     if (h->host) (void)hipHostFree(h->host);
     if (h->verdict_host) (void)hipHostFree(h->verdict_host);
     if (h->verdict_dev) (void)hipFree(h->verdict_dev);
+    if (h->long_arrive) (void)hipFree(h->long_arrive);
+    if (h->long_verdicts) (void)hipFree(h->long_verdicts);
+    if (h->long_host) (void)hipHostFree(h->long_host);
     delete h;
     return 0;
 }
@@ -550,6 +667,13 @@ int pulse_stoprule_set_option(void* handle, int32_t option, int64_t value) {
         h->verdict_wait_ticks = value; return 0;
     case PULSE_STOPRULE_OPT_ALLOW_SHARED_DEVICE_PAIRS: h->allow_shared_device_pairs = value != 0; return 0;
     case PULSE_STOPRULE_OPT_DEBUG_LATE_VERDICTS: h->debug_late = (int)value; return 0;
+    case PULSE_STOPRULE_OPT_LONG_LAUNCHES: h->long_on = value != 0; return 0;
+    case PULSE_STOPRULE_OPT_DEBUG_SKIP_DECISION:
+        if (value < 0 || value > pulse::kLongMaxChunks) return pulse::fail(PULSE_EINVAL, "pulse_stoprule_set_option: the check point to skip is 1-based, 0 = none");
+        h->debug_skip = (int)value; return 0;
+    case PULSE_STOPRULE_OPT_DEBUG_RESIDENT_BLOCKS:
+        if (value < 0 || value > 64) return pulse::fail(PULSE_EINVAL, "pulse_stoprule_set_option: resident workgroups per compute unit: 0 (ask the device) .. 64");
+        h->debug_resident = (int)value; h->long_grid = -1; return 0;
     default: return pulse::fail(PULSE_EINVAL, "pulse_stoprule_set_option: unknown option");
     }
 }
@@ -560,6 +684,15 @@ int pulse_stoprule_stats(void* handle, int64_t* out4) {
     out4[0] = h->launches; out4[1] = h->verdict_timeouts;
     out4[2] = pulse::stoprule_pairs_supported(h, 1) ? 1 : 0;
     out4[3] = h->side_launches;
+    return 0;
+}
+
+int pulse_stoprule_long_stats(void* handle, int64_t* out4) {
+    PulseStopRule* h = static_cast<PulseStopRule*>(handle);
+    if (!h || !out4) return pulse::fail(PULSE_EINVAL, "pulse_stoprule_long_stats: null argument");
+    if (int rc = pulse::long_word_written_once(h)) return rc;
+    out4[0] = h->long_launches; out4[1] = h->long_taken; out4[2] = h->long_called_off;
+    out4[3] = h->long_on && !h->long_off && h->mode == kModeLocal && !h->shm_asked && h->n_global == (long long)h->n_local && pulse::stoprule_pairs_supported(h, 1) ? 1 : 0;
     return 0;
 }
 

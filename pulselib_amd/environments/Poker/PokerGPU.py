@@ -51,7 +51,7 @@ _ROWS = ("stacks", "current_round_bet", "total_invested", "status")
 _TRACKED = frozenset(_I32_SCALARS + _BOOL_SCALARS + _ROWS + ("hands", "board", "decks", "equities", "obs",
                                                              "w1", "w2", "K", "alpha", "hand_ranks",
                                                              "active_players", "n_players", "n_games", "max_players",
-                                                             "use_eval_cache", "obs_staging", "chunked_rollout", "chunk_four_lanes", "paired_launches"))
+                                                             "use_eval_cache", "obs_staging", "chunked_rollout", "chunk_four_lanes", "paired_launches", "long_launches"))
 
 
 class PokerGPU(_EnvBase):
@@ -102,6 +102,7 @@ class PokerGPU(_EnvBase):
         self.chunked_rollout = True      # rollout(): one launch per chunk of steps instead of one per step
         self.chunk_four_lanes = False    # chunk launches: four lanes per table also where two are the default (<= 10 seats)
         self.paired_launches = True      # rollout_until(): two check intervals per launch under the lag-1 rule
+        self.long_launches = True        # rollout_until(): all the check intervals a call has left in ONE launch, where the rule and the grid allow it (section 3.5)
         # opt-in: successive steps write their observation into two alternating buffers, so the tensor a step returned
         # stays intact through the NEXT step (a trainer then needs no copy of the pre-step observation).  Off: the
         # reference's single persistent buffer (PokerGPU.py:633).
@@ -234,7 +235,8 @@ class PokerGPU(_EnvBase):
             v.n_games, v.n_players, v.active_players, v.max_players = N, P, A, self.max_players
             v.obs_size, v.hand_ranks_len = self.obs_size, hr.numel()
             v.flags = ((0 if self.obs_staging else _native.VIEW_NO_OBS_STAGING) | (0 if self.chunked_rollout else _native.VIEW_NO_CHUNK)
-                       | (_native.VIEW_FOUR_LANES if self.chunk_four_lanes else 0) | (0 if self.paired_launches else _native.VIEW_NO_PAIRS))
+                       | (_native.VIEW_FOUR_LANES if self.chunk_four_lanes else 0) | (0 if self.paired_launches else _native.VIEW_NO_PAIRS)
+                       | (0 if self.long_launches else _native.VIEW_NO_LONG_LAUNCHES))
             v.hand_ranks = hr.data_ptr()
             for k, p in ptr.items():
                 setattr(v, k, p)
@@ -479,7 +481,9 @@ class PokerGPU(_EnvBase):
         of `chunk_steps` fused policy+step transitions, the stop rule's verdict after each, until it ends the episode
         or `max_steps` steps have run.  Returns (steps_done, over).  `stop_rule` must decide natively
         (stoprule.LaggedDoneCount with exchange "local" or "rccl"); with a host-side exchange call rollout() + over()
-        per chunk instead."""
+        per chunk instead.  With a lag-1 rule one launch runs two chunks (`paired_launches`) or, where the rule is one
+        process's own and the grid fits the device at once, all the chunks the call has left (`long_launches`): a launch
+        that ran all its chunks reports `over` with the next call, which then runs nothing."""
         if stop_rule is None or getattr(stop_rule, "handle", None) is None or stop_rule.exchange == "host":
             raise ValueError("rollout_until needs a stop rule that decides natively (exchange 'local' or 'rccl')")
         actions = self._actions(actions)
