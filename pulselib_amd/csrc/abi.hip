@@ -41,6 +41,29 @@ LdsLaunch launch_lds(const void* fn, unsigned grid, unsigned block, void** param
     return {(int)attr, (int)hipLaunchKernel(fn, dim3(grid), dim3(block), params, lds_bytes, stream)};
 }
 
+int resident_blocks_per_cu(const void* fn, int block, size_t lds_bytes) {
+    // the assumptions of launch_lds's table, except that the device is part of the key (a partition holds fewer)
+    static struct { const void* fn; size_t bytes; int dev, per_cu; } asked[64] = {};
+    int dev = 0, per_cu = 0, i = 0;
+    hipError_t e = hipGetDevice(&dev);
+    while (i < 64 && asked[i].fn && !(asked[i].fn == fn && asked[i].bytes == lds_bytes && asked[i].dev == dev)) ++i;
+    if (e == hipSuccess && i < 64 && asked[i].fn) return asked[i].per_cu;
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, lds_bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail_hip((int)e, "occupancy query"); }
+    if (per_cu < 0) per_cu = 0;
+    if (i < 64) asked[i] = {fn, lds_bytes, dev, per_cu};
+    return per_cu;
+}
+
+long long* CalledOffWord::get() {
+    void* p = nullptr;
+    if (!word && hipHostMalloc(&p, sizeof(long long), hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) (void)hipGetLastError();
+    if (!word && p) { word = static_cast<long long*>(p); *word = 0; }
+    return word;
+}
+long long CalledOffWord::count() const { return word ? __atomic_load_n(word, __ATOMIC_ACQUIRE) : 0; }
+bool CalledOffWord::changed() { const long long was = seen; seen = count(); return seen != was; }
+
 }  // namespace pulse
 
 // ---- the tail of an entry point, one copy for every unit (pulse_internal.h)

@@ -206,26 +206,16 @@ int rollout(const PulseBlackjackMC* o, void* stream, const char* name) {
     if constexpr (CONTROL) {
         // Two workgroups per CU are what the kernel's time per game rests on (one: 1.39 x): a device or a build that cannot hold
         // them is an error, not a slower run.
-        static int resident[64] = {0};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess && (dev < 0 || dev >= 64)) e = hipErrorInvalidDevice;
-        if (e == hipSuccess && resident[dev] == 0) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(blackjack_mc_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)Layout<true>::kLdsBytes);
-            int n = 0;
-            if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, blackjack_mc_kernel<true>, kBlock, Layout<true>::kLdsBytes);
-            if (e == hipSuccess) resident[dev] = n > 0 ? n : -1;
-        }
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            std::snprintf(what, sizeof what, "%s: occupancy query", name);
-            return pulse::fail_hip(e, what);
-        }
-        if (resident[dev] < 2) {
+        const void* fn = reinterpret_cast<const void*>(blackjack_mc_kernel<true>);
+        static bool raised = false;                  // the query counts the LDS only within the function's limit: raise it first, once
+        const hipError_t e = raised ? hipSuccess : hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Layout<true>::kLdsBytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); std::snprintf(what, sizeof what, "%s: LDS size attribute", name); return pulse::fail_hip(e, what); }
+        raised = true;
+        const int resident = pulse::resident_blocks_per_cu(fn, kBlock, Layout<true>::kLdsBytes);
+        if (resident < 0) return resident;
+        if (resident < 2) {
             char text[256];
-            std::snprintf(text, sizeof text, "%s: %d workgroup(s) of %d lanes and %zu bytes of LDS fit on a CU, 2 are needed", name,
-                          resident[dev] < 0 ? 0 : resident[dev], kBlock, Layout<true>::kLdsBytes);
+            std::snprintf(text, sizeof text, "%s: %d workgroup(s) of %d lanes and %zu bytes of LDS fit on a CU, 2 are needed", name, resident, kBlock, Layout<true>::kLdsBytes);
             return pulse::fail(PULSE_ELAUNCH, text);
         }
     }

@@ -984,10 +984,7 @@ int resident_one(const PulsePokerView& v, const float* obs_odd) {
     const bool wobs = obs_staging(v, obs_odd, LPT);
     const size_t lds = sizeof(int32_t) * (size_t)(kStepBlock / 64) * (size_t)chunk_lds_dwords(v.obs_size, LPT * SPL, TPW, MULTI == 2);
     const auto fn = wobs ? &poker_step_kernel<PH, POLICY, LPT, SPL, true, MULTI> : &poker_step_kernel<PH, POLICY, LPT, SPL, false, MULTI>;
-    int blocks = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(fn), kStepBlock, lds);
-    if (e != hipSuccess) return pulse::fail_hip((int)e, "chunk kernel: occupancy query");
-    return blocks;
+    return pulse::resident_blocks_per_cu(reinterpret_cast<const void*>(fn), kStepBlock, lds);
 }
 
 inline bool chunk_slim(const PulsePokerView& v) { return v.n_games > 81920; }     // the two-lane chunk's slim LDS image (launch_chunk)

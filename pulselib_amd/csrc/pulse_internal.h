@@ -36,6 +36,20 @@ LdsLaunch launch_lds(void (*kernel)(P...), unsigned grid, unsigned block, size_t
     return launch_lds(reinterpret_cast<const void*>(kernel), grid, block, params, lds_bytes, stream, launch_if_refused);
 }
 
+// abi.hip: workgroups of `block` threads and `lds_bytes` of dynamic LDS that a CU holds of `fn` at once (the occupancy query, asked
+// once per device, function and LDS size; beyond 48 KiB the caller has raised the function's limit first).  Negative: the query
+// failed, as fail_hip reports it.  What the number permits is the caller's policy.
+int resident_blocks_per_cu(const void* fn, int block, size_t lds_bytes);
+
+// abi.hip: the pinned host word in which one unit's launches count their called-off workgroup meetings (meeting_device.h)
+struct CalledOffWord {
+    long long* get();              // coherent, mapped, portable; allocated and zeroed on first use; nullptr: no such memory (sticky error cleared)
+    long long count() const;       // meetings called off so far
+    bool changed();                // has count() moved since this was last asked?
+    long long* word = nullptr;
+    long long seen = 0;
+};
+
 // envs.hip: the current device's row table of the packed 2048 move (tfe_device.h), built on first use
 int tfe_row_lut(const uint32_t** out);
 

@@ -38,6 +38,7 @@ __device__ unsigned long long* g_qstamp_buf = nullptr;
 #define QSTAMP(i) do { } while (0)
 #endif
 
+#include "meeting_device.h"
 #include "qnet_device.h"
 #include "qnet_rows16.h"
 #include "qnet_train_device.h"
@@ -447,7 +448,6 @@ struct ReduceArgs {
     long long* gave_up;                       // fused form: pinned host word, += 1 by a launch whose meeting was called off
     float* stab;                              // PulseQNetTrain.stability or nullptr; two-launch form: [0..4] = the unnormalised totals
 };
-constexpr unsigned kMeetOff = 0x80000000u;     // an arrival counter with this bit set: the meeting was called off
 
 struct AdamArgs {
     float* params; float* target; const float* grad; float* m; float* v; const long long* step; float* scal; float* report;
@@ -488,10 +488,9 @@ __device__ __forceinline__ void adamw_one(const AdamArgs& a, int i, float g_sum,
 }
 
 // FUSED: the AdamW step rides in the same launch.  Every workgroup needs the squared norm of the WHOLE gradient for the
-// clipping factor, so the workgroups (282 of 256 threads: all resident at once) meet at a counter after publishing their part
-// of it; each then updates the parameters whose gradient sums it holds in registers.  Saves the third launch's dispatch
-// and its 4.7 us for a wait of about one.  Everything a workgroup reads that another wrote in this launch goes through
-// device-scope atomics (the norm, the counter): the per-XCD L2s are not coherent for plain loads.
+// clipping factor, so the workgroups (282 of 256 threads: all resident at once) meet (meeting_device.h) after publishing their
+// part of it -- through agent-scope atomics, like the counters --; each then updates the parameters whose gradient sums it
+// holds in registers.  Saves the third launch's dispatch and its 4.7 us for a wait of about one.
 template <bool FUSED>
 __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(const ReduceArgs a, const AdamArgs w) {
     __shared__ float red[4];
@@ -549,13 +548,12 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(const ReduceArgs 
     if (threadIdx.x == 0) {
         const float part = (red[0] + red[1]) + (red[2] + red[3]);
         if (FUSED) {
-            // this workgroup's part of the norm goes to its own word, then it is counted on one of 8 counters (282 arrivals
-            // on one address serialise at ~60 ns each: 6 us of the first version of this meeting)
+            // this workgroup's part of the norm goes to its own word, then the workgroup arrives at the meeting (meeting_device.h)
             step_old = *a.step;                                    // (workgroup 0 advances it after the meeting)
             __hip_atomic_store(reinterpret_cast<float*>(a.meet + 8 + blockIdx.x), part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the store has left before the arrival is sent after it
             asm volatile("" :: "v"((int)step_old));
-            __hip_atomic_fetch_add(a.meet + (blockIdx.x & 7), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            pulse_meet::arrive(a.meet);
         } else {
             unsafeAtomicAdd(a.scal + 0, part);
         }
@@ -581,30 +579,8 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(const ReduceArgs 
         }
     }
     if (FUSED) {
-        if (threadIdx.x < 64) {                                   // wavefront 0: lanes 0..7 watch one counter each
-            // The meeting is all or nothing.  "Go" = all eight counters read exactly full.  A workgroup whose wait runs out
-            // calls the meeting off by setting kMeetOff in a counter that is still short -- with a compare-and-swap from the
-            // value it read, so the bit lands either before the missing arrival (that counter never reads full again: nobody
-            // goes, before or after) or not at all (the counter moved: look again).  A full counter is never marked, a marked
-            // one never reads full: no workgroup can apply its part of the update while another skips its own.
-            unsigned want = (gridDim.x + 7 - (threadIdx.x & 7)) / 8;            // workgroups b with b % 8 == lane
-            if (threadIdx.x == 0) want += a.extra_arrivals;
-            bool met = false;
-            for (const long long t0 = wall_clock64();;) {
-                const unsigned got = threadIdx.x < 8 ? __hip_atomic_load(a.meet + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : want;
-                if (__ballot((got & kMeetOff) != 0u) != 0ull) break;
-                const unsigned long long short_of = __ballot(got != want);
-                if (short_of == 0ull) { met = true; break; }
-                if (wall_clock64() - t0 > a.wait_ticks) {
-                    const int first = __ffsll((long long)short_of) - 1;
-                    unsigned mine = 0u;
-                    if ((int)threadIdx.x == first)
-                        mine = atomicCAS(a.meet + threadIdx.x, got, got | kMeetOff) == got ? 1u : 0u;
-                    if (__ballot(mine != 0u) != 0ull) break;
-                    continue;                                      // the counter moved under the mark: read it again
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
+        if (threadIdx.x < 64) {                                   // wavefront 0; all or nothing: every workgroup updates its part or none does
+            const bool met = pulse_meet::wait<2>(a.meet, a.extra_arrivals, a.wait_ticks, a.gave_up);
             float tot = 0.0f;                                      // the same order in every workgroup: the update does not depend on timing
             for (unsigned b = threadIdx.x; b < gridDim.x; b += 64)
                 tot += __hip_atomic_load(reinterpret_cast<float*>(a.meet + 8 + b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -612,10 +588,7 @@ __global__ __launch_bounds__(256) void qnet_grad_reduce_kernel(const ReduceArgs 
             for (int off = 32; off >= 1; off >>= 1) tot += __shfl_xor(tot, off);
             if (threadIdx.x == 0) {
                 bc[0] = tot; bc[1] = met ? rows : 0.0f;
-                if (blockIdx.x == 0) {
-                    w.report[3] = met ? 0.0f : -1.0f;
-                    if (!met && a.gave_up) __hip_atomic_fetch_add(a.gave_up, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
+                if (blockIdx.x == 0) w.report[3] = met ? 0.0f : -1.0f;
             }
         }
         __syncthreads();
@@ -665,27 +638,12 @@ using pulse::device_cus;
 constexpr int kActTwoLaunchRows = 262144;       // from here on the masked action selection lists first and runs full tiles second
 
 // The fused reduce + AdamW launch is a meeting of all its workgroups inside one ordinary launch: it is only taken where the
-// device can hold the whole grid at once (asked once per device; a smaller part, e.g. a CPX partition, gets the two-launch
-// form), and a meeting that does not come about -- a co-tenant holding the CUs -- is called off as a whole, counted in
-// this pinned word and reported by the next call (PULSE_EINTERNAL once; nothing was updated, training may go on).
-long long* g_meet_gave_up = nullptr;
-long long g_meet_gave_up_seen = 0;
+// device can hold the whole grid at once (a smaller part, e.g. a CPX partition, or a device that cannot be asked gets the
+// two-launch form), and a meeting that does not come about -- a co-tenant holding the CUs -- is called off as a whole, counted
+// in this pinned word and reported by the next call (PULSE_EINTERNAL once; nothing was updated, training may go on).
+pulse::CalledOffWord g_meet_called_off;
 bool fused_apply_fits(unsigned grid) {
-    static int resident[64] = {0};                                 // per device: 0 = not asked yet, -1 = unknown
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-    if (resident[dev] == 0) {
-        int per_cu = 0; hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, qnet_grad_reduce_kernel<true>, 256, 0) == hipSuccess &&
-            hipGetDeviceProperties(&prop, dev) == hipSuccess) resident[dev] = std::max(per_cu * prop.multiProcessorCount, 1);
-        else { (void)hipGetLastError(); resident[dev] = -1; }
-    }
-    if (!g_meet_gave_up) {
-        void* p = nullptr;
-        if (hipHostMalloc(&p, sizeof(long long), hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); return false; }
-        g_meet_gave_up = static_cast<long long*>(p); *g_meet_gave_up = 0;
-    }
-    return resident[dev] >= (int)grid;
+    return (long long)pulse::resident_blocks_per_cu(reinterpret_cast<const void*>(&qnet_grad_reduce_kernel<true>), 256, 0) * device_cus() >= (long long)grid;
 }
 
 // PulseQNetTrain.select_scratch / pulse_qnet_act_select's select_scratch (int32 words, pulse_env.h), nw = ceil(n_rows / 256):
@@ -796,7 +754,7 @@ struct TrainBatch {
 };
 
 // What every training entry point checks, in one order; `b`: the call's transitions, nullptr for pulse_qnet_train_apply (which
-// has none).  Last, once: the report of an earlier launch whose meeting was called off (see fused_apply_fits).
+// has none).  Last, once: the report of an earlier launch whose meeting was called off (see g_meet_called_off).
 int train_validate(const PulseQNetTrain* t, const TrainBatch* b) {
     if (!t || (b && (!b->states || !b->actions || !b->rewards || !b->next_states || !b->dones)))
         return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: null argument");
@@ -823,15 +781,10 @@ int train_validate(const PulseQNetTrain* t, const TrainBatch* b) {
         return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: flat parameter buffers must be 16-byte aligned");
     if (!(t->dropout_p >= 0.0f && t->dropout_p < 1.0f)) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: dropout_p outside [0, 1)");
     if (b && b->n_rows < 0) return pulse::fail(PULSE_EINVAL, "pulse_qnet_train_step: n_rows < 0");
-    if (g_meet_gave_up) {
-        const long long gave_up = __atomic_load_n(g_meet_gave_up, __ATOMIC_ACQUIRE);
-        if (gave_up != g_meet_gave_up_seen) {
-            g_meet_gave_up_seen = gave_up;
-            return pulse::fail(PULSE_EINTERNAL, "pulse_qnet_train_step: an earlier reduce + AdamW launch could not gather its workgroups within its wait "
-                                                "(another process or stream holds the GPU's compute units?) and applied NO update (report[3] = -1); "
-                                                "set PulseQNetTrain.separate_apply to run AdamW as a launch of its own");
-        }
-    }
+    if (g_meet_called_off.changed())
+        return pulse::fail(PULSE_EINTERNAL, "pulse_qnet_train_step: an earlier reduce + AdamW launch could not gather its workgroups within its wait "
+                                            "(another process or stream holds the GPU's compute units?) and applied NO update (report[3] = -1); "
+                                            "set PulseQNetTrain.separate_apply to run AdamW as a launch of its own");
     return 0;
 }
 
@@ -886,10 +839,10 @@ int train_grads(const PulseQNetTrain* t, const TrainBatch& b, bool apply, bool* 
     r.reward_sum = b.reward_sum; r.win_reward = sc.win_reward(); r.n_windows = n_windows; r.meet = a.meet;
     const AdamArgs w = adam_args(t, np);
     const unsigned rg = (unsigned)((kSliceStats + 127) / 128);
-    *fused = apply && !t->separate_apply && fused_apply_fits(rg);
+    r.gave_up = apply && !t->separate_apply ? g_meet_called_off.get() : nullptr;     // (no word to report in: not fused)
+    *fused = r.gave_up && fused_apply_fits(rg);
     r.wait_ticks = t->meet_wait_ticks > 0 ? (long long)t->meet_wait_ticks : 500000000ll;     // 5 s of the 100 MHz clock
     r.extra_arrivals = t->debug_meet_extra > 0 ? (unsigned)t->debug_meet_extra : 0u;
-    r.gave_up = g_meet_gave_up;
     r.stab = t->stability;
     if (*fused) hipLaunchKernelGGL(qnet_grad_reduce_kernel<true>, dim3(rg), dim3(256), 0, st, r, w);
     else hipLaunchKernelGGL(qnet_grad_reduce_kernel<false>, dim3(rg), dim3(256), 0, st, r, w);
@@ -941,7 +894,7 @@ int pulse_debug_set_qnet_stamp_buffer(unsigned long long* buf) {
 
 int pulse_qnet_slice_floats(void) { return kSlicePitch; }
 
-int64_t pulse_qnet_called_off_meetings(void) { return g_meet_gave_up ? (int64_t)__atomic_load_n(g_meet_gave_up, __ATOMIC_ACQUIRE) : 0; }
+int64_t pulse_qnet_called_off_meetings(void) { return (int64_t)g_meet_called_off.count(); }
 
 int pulse_qnet_param_count(int32_t state_dim, int32_t n_actions) {
     if (state_dim < 1 || n_actions < 1 || n_actions > 32) return pulse::fail(PULSE_EINVAL, "pulse_qnet_param_count: bad dimensions");

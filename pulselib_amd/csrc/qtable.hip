@@ -23,6 +23,7 @@
 // -- the k transitions applied one after another with the mean of their targets (k = 1: the reference's formula itself).
 #include <hip/hip_runtime.h>
 
+#include "meeting_device.h"
 #include "philox_device.h"
 #include "pulse_internal.h"
 #include "tfe_agent_device.h"
@@ -80,7 +81,6 @@ struct Deferred {                 // per-launch scratch, owned by the caller (Pu
     int ablate;                   // timing-only diagnostics (PulseQTableScratch.reserved0; results are then NOT valid updates):
                                   // 1 = no compare-and-swap, every update is deferred; 2 = losers are dropped, not listed; 4 = new states are not inserted
 };
-constexpr unsigned int kDeferOff = 0x80000000u;   // a meeting counter with this bit: called off
 
 // q[s][a] <- q + alpha (target - q): race-free regions write, shared tables try ONE compare-and-swap and defer on a loss.
 // Called by EVERY thread of the workgroup (`live` = this thread has a transition): the losers' list positions come from the
@@ -195,35 +195,13 @@ __global__ __launch_bounds__(kBlock) void qtable_defer_kernel(Entry* table, Defe
     __threadfence();
     __syncthreads();
     if (!solo) {
-        // All or nothing: phase 2 runs iff all eight counters read exactly full.  A workgroup whose wait runs out marks a counter
-        // that is still short (compare-and-swap from the value it read: the mark lands before the missing arrival or not at
-        // all), after which that counter never reads full: no owner applies `sum / k` from accumulators other workgroups are
-        // still adding to.  The accumulators then stay claimed; the host finds the pinned count changed, clears them and
-        // fails its next call.  (Eight counters: arrivals on ONE address cost the meeting ~25 us.)
+        // Phase 2 runs iff the workgroups meet (meeting_device.h): no owner applies `sum / k` from accumulators others still add to.
+        // Called off, the accumulators stay claimed; the host finds the pinned count changed, clears them and fails its next call.
         __shared__ int go_s;
         if (threadIdx.x < 64) {
             unsigned int* meet = d.count + kCountMeet + 8 * d.parity;
-            if (threadIdx.x == 0) atomicAdd(meet + (blockIdx.x & 7), 1u);
-            unsigned int want = (gridDim.x + 7 - (threadIdx.x & 7)) / 8;
-            if (threadIdx.x == 0) want += d.extra_arrivals;
-            int go = 0;
-            for (const long long t0 = wall_clock64();;) {        // (100 MHz)
-                const unsigned int got = threadIdx.x < 8 ? __hip_atomic_load(meet + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : want;
-                if (__ballot((got & kDeferOff) != 0u) != 0ull) break;
-                const unsigned long long short_of = __ballot(got != want);
-                if (short_of == 0ull) { go = 1; break; }
-                if (wall_clock64() - t0 > d.wait_ticks) {
-                    const int first = __ffsll((long long)short_of) - 1;
-                    unsigned int marked = 0u;
-                    if ((int)threadIdx.x == first) marked = atomicCAS(meet + threadIdx.x, got, got | kDeferOff) == got ? 1u : 0u;
-                    if (__ballot(marked != 0u) != 0ull) {
-                        if ((int)threadIdx.x == first && d.gave_up) __hip_atomic_fetch_add(d.gave_up, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                        break;
-                    }
-                    continue;
-                }
-                __builtin_amdgcn_s_sleep(8);
-            }
+            if (threadIdx.x == 0) pulse_meet::arrive(meet);
+            const bool go = pulse_meet::wait<8>(meet, d.extra_arrivals, d.wait_ticks, d.gave_up);
             if (threadIdx.x == 0) go_s = go;
         }
         __syncthreads();
@@ -370,8 +348,7 @@ int check_table(const PulseQTable* q, int32_t n_boards, int32_t n) {
 // A follow-up launch whose workgroups did not gather (a co-tenant on the GPU) drops that launch's combined updates and
 // leaves their accumulators claimed: counted in this pinned word; the next call on a shared table clears the accumulators
 // it is handed and fails once (PULSE_EINTERNAL), after which the table is usable again.
-long long* g_defer_gave_up = nullptr;
-long long g_defer_gave_up_seen = 0;
+pulse::CalledOffWord g_defer_called_off;
 
 // the shared table's scratch, checked and turned into the kernels' view of it
 int deferred_of(const PulseQTable* q, const PulseQTableScratch* sc, int32_t n_boards, uint64_t launch_index, Deferred* d, hipStream_t st) {
@@ -384,15 +361,9 @@ int deferred_of(const PulseQTable* q, const PulseQTableScratch* sc, int32_t n_bo
     const int n_wg = (n_boards + kBlock - 1) / kBlock;
     if (n_wg > 4096) return pulse::fail(PULSE_EINVAL, "PulseQTable: a shared table takes at most 1,048,576 boards per launch");
     if (sc->n % kBlock) return pulse::fail(PULSE_EINVAL, "PulseQTableScratch: n must be a multiple of 256 (the list is kept in segments of 256)");
-    if (!g_defer_gave_up) {
-        void* p = nullptr;
-        if (hipHostMalloc(&p, sizeof(long long), hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable) != hipSuccess)
-            return pulse::fail_hip((int)hipGetLastError(), "PulseQTable: pinned word of the follow-up launch");
-        g_defer_gave_up = static_cast<long long*>(p); *g_defer_gave_up = 0;
-    }
-    const long long gone = __atomic_load_n(g_defer_gave_up, __ATOMIC_ACQUIRE);
-    if (gone != g_defer_gave_up_seen) {
-        g_defer_gave_up_seen = gone;
+    long long* gave_up = g_defer_called_off.get();
+    if (!gave_up) return pulse::fail(PULSE_ELAUNCH, "PulseQTable: pinned word of the follow-up launch: allocation failed");
+    if (g_defer_called_off.changed()) {
         (void)hipMemsetAsync(sc->acc_key, 0, (size_t)sc->acc_slots * sizeof(uint64_t), st);
         (void)hipMemsetAsync(sc->acc_cnt, 0, (size_t)sc->acc_slots * sizeof(uint32_t), st);
         (void)hipMemsetAsync(sc->acc_sum, 0, (size_t)sc->acc_slots * sizeof(double), st);
@@ -403,7 +374,7 @@ int deferred_of(const PulseQTable* q, const PulseQTableScratch* sc, int32_t n_bo
     *d = Deferred{sc->count, reinterpret_cast<unsigned long long*>(sc->cells), sc->targets, sc->owner,
                   reinterpret_cast<unsigned long long*>(sc->acc_key), sc->acc_cnt, sc->acc_sum, sc->acc_slots, (int)(launch_index & 1u), n_wg,
                   sc->wait_ticks > 0 ? (long long)sc->wait_ticks : 300000000ll, sc->debug_meet_extra > 0 ? (unsigned int)sc->debug_meet_extra : 0u,
-                  g_defer_gave_up, sc->reserved0};
+                  gave_up, sc->reserved0};
     return 0;
 }
 void launch_deferred(Entry* table, const Deferred& d, double alpha, hipStream_t st) {

@@ -345,9 +345,12 @@ def test_a_called_off_meeting_updates_nothing_and_fails_the_next_call(g):
     q.meet_wait_ticks = 5_000_000                                   # 50 ms of the 100 MHz clock
     t.debug_meet_extra = 1
     t.meet_wait_ticks = q.meet_wait_ticks
+    called_off = int(_native.lib().pulse_qnet_called_off_meetings())
     t0 = time.perf_counter()
     rep = q.train_step_native(*args).cpu().numpy().copy()
+    torch.cuda.synchronize()
     assert time.perf_counter() - t0 < 5.0                           # it gave up after its 50 ms, not after the default 5 s
+    assert int(_native.lib().pulse_qnet_called_off_meetings()) == called_off + 1      # one add per called-off meeting, not one per workgroup
     assert rep[3] == -1.0 and rep[0] == 0.0
     np.testing.assert_array_equal(_flat(q.network), p0)
     assert torch.equal(q._native["m"], m0) and torch.equal(q._native["v"], v0) and q.native_steps() == s0
@@ -360,6 +363,8 @@ def test_a_called_off_meeting_updates_nothing_and_fails_the_next_call(g):
     assert rep[3] == 0.0 and rep[0] > 0 and q.native_steps() == s0 + 1
     q.check_native_report()
     assert np.abs(_flat(q.network) - p0).max() > 0
+    torch.cuda.synchronize()
+    assert int(_native.lib().pulse_qnet_called_off_meetings()) == called_off + 1      # the two ordinary steps added nothing
 
 
 def test_separate_apply_equals_the_in_launch_adamw(g):
