@@ -180,10 +180,11 @@ int pulse_poker_policy_step(const PulsePokerView* v, const uint8_t* agent_types,
 
 /* Roll-out: n_steps fused policy+step transitions enqueued by ONE native call and, by default, executed by ONE
  * launch: every table's state is loaded once, stepped n_steps times in registers and its changed words stored once,
- * while every step still stores its observation, reward, done flag and action -- step i into the even buffers
- * (v_even->obs, v_even->is_done_out, rewards_even) when i is even, else into the odd ones (v_odd->obs,
- * v_odd->is_done_out, rewards_odd).  Memory after the call is bit-identical to calling pulse_poker_policy_step
- * n_steps times on v_even, v_odd, v_even, ... (PULSE_VIEW_NO_CHUNK in v_even->flags does exactly that instead).
+ * while step i's observation, reward and done flag belong into the even buffers (v_even->obs, v_even->is_done_out,
+ * rewards_even) when i is even, else into the odd ones (v_odd->obs, v_odd->is_done_out, rewards_odd).
+ * The contract (this call and pulse_poker_rollout_until): memory after the call is bit-identical to calling
+ * pulse_poker_policy_step n_steps times on v_even, v_odd, v_even, ... (PULSE_VIEW_NO_CHUNK in v_even->flags does exactly
+ * that instead); outputs that a later step of the same call overwrites are not materialised.
  * v_odd must be v_even with is_done <-> is_done_out swapped (obs may differ: double-buffered observations).
  * Draws of step i: the scripted-opponent stream at step_counter0 + i (pulse_poker_policy).
  * timer (NULL or a pulse_timer_create handle): the call is bracketed by one HIP event pair on `stream`; read the

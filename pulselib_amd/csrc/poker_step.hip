@@ -14,8 +14,10 @@
 //
 // Memory: single step -- state is read once and only the words that changed are written back, in the reference's
 // own SoA tensors, so the drop-in class exposes them unchanged.  Chunk (pulse_poker_rollout) -- state is read once
-// per chunk, every step still stores its observation / reward / done flag / action (ping-pong buffers, exactly what
-// n single launches leave behind), and the changed state words are written once at the end.  The 130 MB hand-rank
+// per chunk, the steps store observation / reward / done flag into ping-pong buffers so that memory is exactly what n
+// single launches leave behind -- only the last two steps before a possible end of the launch are visible there, and only
+// those compute and store them ("live steps", at the step loop) -- and the changed state words and the action are written
+// once at the end.  The 130 MB hand-rank
 // table is only touched when a poked state misses the evaluation cache the reset kernel fills.
 #include <algorithm>
 #include <cstddef>
@@ -458,6 +460,9 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
     // seat-set bitmask of a per-seat predicate / value of one seat, visible to every lane of the table
 #define SEAT_BITS(expr) ([&]() { uint32_t m_ = 0; _Pragma("unroll") for (int k = 0; k < SPL; ++k) m_ |= (uint32_t)((expr) ? 1u : 0u) << SEAT(k); return grp_or<LPT>(m_); }())
 #define SEAT_PICK(arr, seat_) ([&]() { uint32_t r_ = 0; _Pragma("unroll") for (int k = 0; k < SPL; ++k) r_ |= SEAT(k) == (seat_) ? (uint32_t)(arr)[k] : 0u; return (int)grp_or<LPT>(r_); }())
+    // the actor's equity into e_actor (a macro: the single step expands it where it always stood, a chunk inside the reward of a live step)
+#define PICK_E_ACTOR() { uint32_t r_ = 0; _Pragma("unroll") for (int k = 0; k < SPL; ++k) r_ |= SEAT(k) == actor ? __float_as_uint(eq[k]) : 0u; \
+                         e_actor = __uint_as_float(grp_or<LPT>(r_)); if (actor >= LPT * SPL) e_actor = 0.5f; }
 
     STAMP(1);   // loads issued
     // The seat to act, as every lane of the table sees it: status / stack / round bet / hole cards.  Nothing changes
@@ -481,7 +486,17 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
     uint8_t* done_dst = v.is_done_out; uint8_t* done_nxt = v.is_done;
     float* rew_dst = rewards; float* rew_nxt = MULTI ? ca.rewards_odd : rewards;
     int cp_at = MULTI ? pa.mid_step : 0;          // > 0: the launch covers several check intervals, the first check point is behind step cp_at
+    // Live steps.  Step i writes its reward, observation and done flag into buffer set i mod 2, so of a launch that ends
+    // after e steps only steps e - 2 and e - 1 leave outputs anybody can read: a dead step computes and stores none of them.
+    // A launch can end at n_steps and, a long one, behind any of its check points (the middle check point of a pair only
+    // stores a count: its end is known before the loop, stop_mid) -- end_at is the nearest of them, one scalar compare per
+    // step.  The single step and the act + step launch store every step: their predicate is a constant.
+    constexpr bool LIVE_RULE = MULTI != 0 && !ACT;
+    int end_at = n_steps;
+    if (LIVE_RULE && pa.lng.n_chunks != 0 && cp_at > 0) end_at = min(cp_at, n_steps);
+    if (LIVE_RULE) end_at = __builtin_amdgcn_readfirstlane(end_at);      // wave-uniform, and known to be: the compare below is a scalar one
     for (int i = 0; i < n_steps; ++i) {
+        const bool live = !LIVE_RULE || i + 2 >= end_at;
         // In a chunk, everything derived from the lane's position in its table (seat numbers, `seat < A` masks, ...)
         // is re-derived inside the step: hoisted out of the loop those lane masks filled the scalar registers and were
         // spilled (~200 v_readlane per step to fetch them back); a compare is cheaper than its reload.
@@ -566,14 +581,10 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                 dirty = false; street_dirty = true; eq_dirty = true;
             }
         }
+        // the actor's equity: only the reward reads it, and nothing between here and there changes eq[] -- where dead steps
+        // skip the reward it is picked there
         float e_actor;
-        {
-            uint32_t r_ = 0;
-#pragma unroll
-            for (int k = 0; k < SPL; ++k) r_ |= SEAT(k) == actor ? __float_as_uint(eq[k]) : 0u;
-            e_actor = __uint_as_float(grp_or<LPT>(r_));
-            if (actor >= LPT * SPL) e_actor = 0.5f;
-        }
+        if (!LIVE_RULE) PICK_E_ACTOR();
 
         STAMP(4);   // equities done
         // ---- 2) execute the action of the seat to act (PokerGPU.py:230-303)
@@ -750,7 +761,8 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
 
         STAMP(7);   // payouts done
         // ---- 5) shaped reward (PokerGPU.py:305-329, :631-632)
-        if (PH & PULSE_PH_REWARD) {
+        if ((PH & PULSE_PH_REWARD) && live) {
+            if (LIVE_RULE) PICK_E_ACTOR();
             const float cnt = (float)contenders;
             const float fair = __fdiv_rn(1.0f, fmaxf(cnt, 1.0f));
             const int cc = max(0, highest - prev_invested);
@@ -777,58 +789,60 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
             const int seat_i = idx & 15;
             const int n_h0 = MULTI ? next_hand.x : SEAT_PICK(h0, seat_i), n_h1 = MULTI ? next_hand.y : SEAT_PICK(h1, seat_i);
             const int n_stack = SEAT_PICK(stack, seat_i), n_status = SEAT_PICK(status, seat_i), n_bet = SEAT_PICK(bet, seat_i);
-            if (MULTI) { a_status = n_status; a_stack = n_stack; a_bet = n_bet; a_cls = next_cls; }   // the next step's actor
-            const int idxm = mod_near(idx, A);
-            const int pos = mod_near(idx - button, A);
-            // columns 0..12, LPT per pass: lane j writes column LPT*pass + j (an LPT-way select per pass)
-            if (LPT == 4) {
-                const int h0v = j == 0 ? b0 : j == 1 ? b1 : j == 2 ? b2 : b3;
-                const int h1v = j == 0 ? b4 : j == 1 ? n_h0 : j == 2 ? n_h1 : stage;
-                const int h2v = j == 0 ? pos : j == 1 ? pot : j == 2 ? highest - n_bet : n_stack;
-                o[j] = (float)h0v; o[4 + j] = (float)h1v; o[8 + j] = (float)h2v;
-                if (j == 0) o[12] = (float)n_status;
-            } else {
-                o[j] = (float)(j == 0 ? b0 : b1); o[2 + j] = (float)(j == 0 ? b2 : b3); o[4 + j] = (float)(j == 0 ? b4 : n_h0);
-                o[6 + j] = (float)(j == 0 ? n_h1 : stage); o[8 + j] = (float)(j == 0 ? pos : pot);
-                o[10 + j] = (float)(j == 0 ? highest - n_bet : n_stack);
-                if (j == 0) o[12] = (float)n_status;
-            }
-            // opponents: seat (idx+1+k)%A -> columns 13+3k..; seats >= A zero-fill the padding slots
-#pragma unroll
-            for (int k = 0; k < SPL; ++k) {
-                const int seat = SEAT(k);
-                if (seat < v.max_players && seat != idxm) {
-                    int slot; float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;
-                    if (seat < A) { slot = seat - idxm - 1; if (slot < 0) slot += A; f0 = (float)stack[k]; f1 = (float)status[k]; f2 = (float)bet[k]; }
-                    else slot = seat - 1;
-                    float* dst = o + 13 + 3 * slot;
-                    dst[0] = f0; dst[1] = f1; dst[2] = f2;
+            if (MULTI) { a_status = n_status; a_stack = n_stack; a_bet = n_bet; a_cls = next_cls; }   // the next step's actor: carried on every step, live or not
+            if (live) {
+                const int idxm = mod_near(idx, A);
+                const int pos = mod_near(idx - button, A);
+                // columns 0..12, LPT per pass: lane j writes column LPT*pass + j (an LPT-way select per pass)
+                if (LPT == 4) {
+                    const int h0v = j == 0 ? b0 : j == 1 ? b1 : j == 2 ? b2 : b3;
+                    const int h1v = j == 0 ? b4 : j == 1 ? n_h0 : j == 2 ? n_h1 : stage;
+                    const int h2v = j == 0 ? pos : j == 1 ? pot : j == 2 ? highest - n_bet : n_stack;
+                    o[j] = (float)h0v; o[4 + j] = (float)h1v; o[8 + j] = (float)h2v;
+                    if (j == 0) o[12] = (float)n_status;
+                } else {
+                    o[j] = (float)(j == 0 ? b0 : b1); o[2 + j] = (float)(j == 0 ? b2 : b3); o[4 + j] = (float)(j == 0 ? b4 : n_h0);
+                    o[6 + j] = (float)(j == 0 ? n_h1 : stage); o[8 + j] = (float)(j == 0 ? pos : pot);
+                    o[10 + j] = (float)(j == 0 ? highest - n_bet : n_stack);
+                    if (j == 0) o[12] = (float)n_status;
                 }
-            }
-            if (WOBS) {
-                wave_sync();
-                const int n4 = TPW / 4 * v.obs_size;                             // int4 per wavefront block
-                const int tw0 = (int)((blockIdx.x * BLK + threadIdx.x) >> 6) * TPW;  // first table of this wavefront
-                const uint32_t blk0 = __umul24((uint32_t)tw0, (uint32_t)v.obs_size) * 4u;      // byte offset of the wavefront's block
-                const int4* src = reinterpret_cast<const int4*>(l_obs);
-                constexpr int kBursts = 5;          // two-lane chunk, 40 columns: 32 rows x 160 B = five 1-KiB bursts
-                if (n4 == kBursts * 64) {
-                    // all reads first, then all stores: as a loop over e every pass waited for its own LDS read
-                    // (five exposed LDS latencies per step)
-                    int4 x[kBursts];
+                // opponents: seat (idx+1+k)%A -> columns 13+3k..; seats >= A zero-fill the padding slots
 #pragma unroll
-                    for (int u = 0; u < kBursts; ++u) x[u] = src[wlane + 64 * u];
-#pragma unroll
-                    for (int u = 0; u < kBursts; ++u) sto_in_loop(reinterpret_cast<int4*>(obs_dst), blk0 + (uint32_t)(wlane + 64 * u) * 16u, x[u]);
-                } else
-                    for (int e = wlane; e < n4; e += 64) sto_in_loop(reinterpret_cast<int4*>(obs_dst), blk0 + (uint32_t)e * 16u, src[e]);
-                if (MULTI) {       // the next step's values must not overtake these reads of the slice
+                for (int k = 0; k < SPL; ++k) {
+                    const int seat = SEAT(k);
+                    if (seat < v.max_players && seat != idxm) {
+                        int slot; float f0 = 0.0f, f1 = 0.0f, f2 = 0.0f;
+                        if (seat < A) { slot = seat - idxm - 1; if (slot < 0) slot += A; f0 = (float)stack[k]; f1 = (float)status[k]; f2 = (float)bet[k]; }
+                        else slot = seat - 1;
+                        float* dst = o + 13 + 3 * slot;
+                        dst[0] = f0; dst[1] = f1; dst[2] = f2;
+                    }
+                }
+                if (WOBS) {
                     wave_sync();
+                    const int n4 = TPW / 4 * v.obs_size;                             // int4 per wavefront block
+                    const int tw0 = (int)((blockIdx.x * BLK + threadIdx.x) >> 6) * TPW;  // first table of this wavefront
+                    const uint32_t blk0 = __umul24((uint32_t)tw0, (uint32_t)v.obs_size) * 4u;      // byte offset of the wavefront's block
+                    const int4* src = reinterpret_cast<const int4*>(l_obs);
+                    constexpr int kBursts = 5;          // two-lane chunk, 40 columns: 32 rows x 160 B = five 1-KiB bursts
+                    if (n4 == kBursts * 64) {
+                        // all reads first, then all stores: as a loop over e every pass waited for its own LDS read
+                        // (five exposed LDS latencies per step)
+                        int4 x[kBursts];
+#pragma unroll
+                        for (int u = 0; u < kBursts; ++u) x[u] = src[wlane + 64 * u];
+#pragma unroll
+                        for (int u = 0; u < kBursts; ++u) sto_in_loop(reinterpret_cast<int4*>(obs_dst), blk0 + (uint32_t)(wlane + 64 * u) * 16u, x[u]);
+                    } else
+                        for (int e = wlane; e < n4; e += 64) sto_in_loop(reinterpret_cast<int4*>(obs_dst), blk0 + (uint32_t)e * 16u, src[e]);
+                    if (MULTI) {       // the next step's values must not overtake these reads of the slice
+                        wave_sync();
+                    }
                 }
             }
         }
         STAMP(9);   // observation stores issued
-        if ((PH & PULSE_PH_ADVANCE) && j == 0) sto_in_loop(done_dst, ut, (uint8_t)(done ? 1 : 0));      // ping-pong buffer: always written
+        if ((PH & PULSE_PH_ADVANCE) && live && j == 0) sto_in_loop(done_dst, ut, (uint8_t)(done ? 1 : 0));      // ping-pong buffer: written by every live step
         if (MULTI && i + 1 == cp_at) {        // the check point in the middle of a paired launch / a check point of a long one
             StepKernargsPtr ka = (StepKernargsPtr)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(ka));
@@ -850,6 +864,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                 }
 #endif
                 cp_at += cs;
+                if (LIVE_RULE) end_at = __builtin_amdgcn_readfirstlane(min(cp_at, n_steps));
             }
         }
         if (MULTI) {
@@ -923,6 +938,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
 #endif
 #undef SEAT_BITS
 #undef SEAT_PICK
+#undef PICK_E_ACTOR
 #undef ROW_OFF
 #undef SEAT
 #undef VS
