@@ -845,6 +845,60 @@ typedef struct PulseTfeNtLearnLambda {
 } PulseTfeNtLearnLambda;
 int pulse_tfe_nt_learn_lambda(const PulseTfeNtLearnLambda* o, void* stream);
 
+/* ---- the n-tuple network's temporal-coherence (TC) step sizes: every weight moves by step * rho, rho = |E| / A, from the running sums
+ * of its rounds' mean errors (E) and mean absolute errors (A).  A weight whose errors keep their sign keeps the full step; one whose
+ * errors cancel stops moving.  Opt-in: a caller that never calls these two keeps the launches above unchanged.  Everything is
+ * float64, one rounding per operation.
+ * State per weight, caller-owned, zeroed once by the caller: double e[n_weights], double a[n_weights], 8-byte aligned.
+ * A third accumulator beside acc: int64 acc_abs[n_weights], 8-byte aligned, zeroed once by the caller (the apply launch zeroes what
+ * it reads).
+ *
+ * pulse_tfe_nt_learn_tc: pulse_tfe_nt_learn's adds (deltas NULL; needs lambda == 0) or pulse_tfe_nt_learn_lambda's walk and adds (deltas
+ * set, any lambda in [0, 1]), with the same skip rule, clamp and counters stats[1], [2], [4]; wherever those add sum += d, cnt += 1
+ * this also adds acc_abs[index] += |d|, d the clamped fixed-point integer read as signed.  acc is what the other two learners leave.
+ *
+ * pulse_tfe_nt_apply_tc: one lane per weight; where cnt > 0,
+ *   m   = ((double)sum / (double)cnt) * 2^-16            (pulse_tfe_nt_apply's mean)
+ *   ab  = ((double)abs / (double)cnt) * 2^-16
+ *   rho = a[i] > 0 ? |e[i]| / a[i] : 1.0                 (from e and a BEFORE this round's m and ab are added)
+ *   weights[i] = (float)((double)weights[i] + (step * rho) * m)      (step * rho is formed first)
+ *   e[i] = e[i] + m;  a[i] = a[i] + ab;  sum, cnt and abs become 0.
+ * A weight with cnt = 0 keeps its bits, and so do its e and a.  On zeroed e and a (the first apply) rho is 1.0 exactly and the
+ * weights are pulse_tfe_nt_apply's, bit for bit.
+ * tc_stats, device int64[4], 8-byte aligned, ADDED TO: [0] weights moved, [1] the sum over them of llrint(rho * 2^32) (the mean rho
+ * of a round = [1] / [0] * 2^-32); [2], [3] not written.  Summed per workgroup, then one atomic per workgroup and word; integer
+ * adds, so tc_stats does not depend on scheduling.
+ *
+ * PULSE_EINVAL, before anything is launched: pulse_tfe_nt_learn_lambda's refusals, except that deltas may be NULL at lambda == 0;
+ * lambda > 0 with deltas NULL; acc_abs null or not 8-byte aligned; for the apply pulse_tfe_nt_apply's, and acc_abs, e, a or tc_stats
+ * null or not 8-byte aligned. */
+typedef struct PulseTfeNtLearnTc {
+    PulseTfeNtNet net;                  /* weights may be NULL */
+    int32_t n_games, max_steps;
+    double gamma, lambda;
+    const uint64_t* keys;
+    const double* values;
+    const uint8_t* steps;
+    const int32_t* lengths;
+    double* deltas;                     /* float64[max_steps * n_games], or NULL at lambda == 0 */
+    int64_t* acc;                       /* int64[n_weights][2] */
+    int64_t* acc_abs;                   /* int64[n_weights] */
+    int64_t* stats;                     /* int64[8] */
+    int64_t reserved0;
+} PulseTfeNtLearnTc;
+int pulse_tfe_nt_learn_tc(const PulseTfeNtLearnTc* o, void* stream);
+typedef struct PulseTfeNtApplyTc {
+    PulseTfeNtNet net;
+    double step;                        /* alpha / F */
+    int64_t* acc;                       /* int64[n_weights][2] */
+    int64_t* acc_abs;                   /* int64[n_weights] */
+    double* e;                          /* float64[n_weights] */
+    double* a;                          /* float64[n_weights] */
+    int64_t* tc_stats;                  /* int64[4] */
+    int64_t reserved0;
+} PulseTfeNtApplyTc;
+int pulse_tfe_nt_apply_tc(const PulseTfeNtApplyTc* o, void* stream);
+
 /* ---- the n-tuple network under expectimax search, one chance layer deep: the same network asked about the boards AFTER the random
  * tile.  Everything is float64, one rounding per operation.  For a board B and a = 0..3, (B_a, score_a), r_a, V and "candidate"
  * (B_a != B) are pulse_tfe_nt_rollout's.  For a candidate a the CHANCE BOARDS of B_a are C(c, k) = B_a with nibble k at the empty cell

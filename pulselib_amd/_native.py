@@ -175,6 +175,15 @@ class TfeNtApply(C.Structure):
     _fields_ = [("net", TfeNtNet), ("step", C.c_double), ("acc", C.c_void_p), ("reserved0", C.c_int64)]
 
 
+class TfeNtLearnTc(C.Structure):
+    _fields_ = [("net", TfeNtNet), ("n_games", C.c_int32), ("max_steps", C.c_int32), ("gamma", C.c_double), ("lam", C.c_double)] + [
+        (n, C.c_void_p) for n in ("keys", "values", "steps", "lengths", "deltas", "acc", "acc_abs", "stats")] + [("reserved0", C.c_int64)]
+
+
+class TfeNtApplyTc(C.Structure):
+    _fields_ = [("net", TfeNtNet), ("step", C.c_double)] + [(n, C.c_void_p) for n in ("acc", "acc_abs", "e", "a", "tc_stats")] + [("reserved0", C.c_int64)]
+
+
 class TfeNtEval(C.Structure):
     _fields_ = [("net", TfeNtNet), ("n_games", C.c_int32), ("max_steps", C.c_int32), ("gamma", C.c_double), ("epsilon", C.c_double)] + _TFE_NT_SEEDS + [
         (n, C.c_void_p) for n in ("summary", "max_tile_hist", "total_score", "lengths")] + [("reserved0", C.c_int64)]
@@ -251,6 +260,8 @@ SYMBOLS = {
     "pulse_tfe_nt_learn": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_learn_lambda": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_apply": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_learn_tc": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_apply_tc": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_evaluate": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_search": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_evaluate_search": (C.c_int, [_P, _P]),

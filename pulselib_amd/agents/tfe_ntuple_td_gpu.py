@@ -15,7 +15,11 @@ lambda-differences D_t = delta_t + gamma * lam * D_{t+1} in `deltas`, and the sa
 
 The policy of a round is frozen (the weights are only read by the roll-out) and the adds are integers, so a round's result does not
 depend on scheduling: `feature_cells_on_host`, `value_on_host`, `greedy_nt_on_host`, `search_nt_on_host`, `learn_nt_on_host`,
-`lambda_deltas_on_host`, `learn_lambda_nt_on_host` and `apply_nt_on_host` are the host's statement of the same arithmetic in numpy, vectorised over boards, and the device is held to them word for word."""
+`lambda_deltas_on_host`, `learn_lambda_nt_on_host` and `apply_nt_on_host` are the host's statement of the same arithmetic in numpy, vectorised over boards, and the device is held to them word for word.
+
+With `tc=True` (section 13.3; csrc/tfe_ntuple_tc.hip) every weight has a step size of its own, rho = |E| / A, from the running sums of
+its rounds' mean errors and mean absolute errors: `learn` is `pulse_tfe_nt_learn_tc`, which also adds |d| into a third accumulator,
+and `apply` is `pulse_tfe_nt_apply_tc`; `learn_tc_nt_on_host` and `apply_tc_nt_on_host` state them on the host."""
 from __future__ import annotations
 
 import functools
@@ -33,6 +37,8 @@ STATS = ("moves", "learnt", "skipped", "truncated", "clamped")                  
 EVAL_SUMMARY = ("games", "moves", "score_sum", "score_sq_sum", "max_score", "truncated", "moves_greedy", "tile_capped")
 CHECKPOINT_VERSION = 1                                                                        # what an agent with lam == 0 writes
 CHECKPOINT_VERSION_LAMBDA = 2                                                                 # ... and with lam != 0: version 1's arrays and `lam`
+CHECKPOINT_VERSION_TC = 4                                                                     # ... and with tc: version 2's and tc_index / tc_e / tc_a (3 is not a format)
+TC_RHO_BITS = 32                                                                              # rho is summed as llrint(rho * 2^32)
 CHECKPOINT_SCALARS = ("symmetric", "gamma", "epsilon", "alpha", "max_steps", "seed", "board_id0", "round", "n_games")
 _U64 = np.uint64
 
@@ -193,10 +199,11 @@ def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
 
 
 # ------------------------------------------------------------------ the learner and the apply launch
-def _add_moves_on_host(keys, steps, lengths, deltas, tuples, symmetric, acc) -> dict:
+def _add_moves_on_host(keys, steps, lengths, deltas, tuples, symmetric, acc, acc_abs=None) -> dict:
     """The learners' tail.  A game has L = min(lengths[g], T) moves; its last is skipped without its terminal bit; any other move (t, g),
     t < L, has deltas[t, g] clamped to +-DELTA_MAX, d = round-half-even(that * 2^16), and sum += d, cnt += 1 at every feature of
-    keys[t, g] (a weight two images meet gets both).  acc int64[W, 2] = {sum, cnt}, in place.  Returns dict(learnt, skipped, clamped)."""
+    keys[t, g] (a weight two images meet gets both).  acc int64[W, 2] = {sum, cnt}, in place; with acc_abs int64[W] also
+    acc_abs += |d| at the same features.  Returns dict(learnt, skipped, clamped)."""
     L = np.minimum(np.asarray(lengths, dtype=np.int64).reshape(-1), keys.shape[0])
     t = np.arange(keys.shape[0], dtype=np.int64)[:, None]
     played = t < L[None, :]
@@ -208,21 +215,23 @@ def _add_moves_on_host(keys, steps, lengths, deltas, tuples, symmetric, acc) -> 
     idx = feature_indices_on_host(keys[learn], tuples, symmetric)
     np.add.at(acc[:, 0], idx.reshape(-1), np.repeat(d, idx.shape[1]))
     np.add.at(acc[:, 1], idx.reshape(-1), 1)
+    if acc_abs is not None:
+        np.add.at(acc_abs, idx.reshape(-1), np.repeat(np.abs(d), idx.shape[1]))
     return dict(learnt=int(learn.sum()), skipped=int(skipped.sum()), clamped=int(clamped.sum()))
 
 
-def learn_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, acc):
+def learn_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, acc, acc_abs=None):
     """pulse_tfe_nt_learn on the host.  keys uint64[T, B], values float64[T, B], steps uint8[T, B], lengths int[B] (a game has
     min(lengths[g], T) moves); acc int64[W, 2] = {sum, cnt}, added to in place.  The last move of a game has target 0; any other has
-    target = reward(steps[t + 1]) + gamma * values[t + 1]; delta = target - values[t], added by _add_moves_on_host.  Returns
-    dict(learnt, skipped, clamped)."""
+    target = reward(steps[t + 1]) + gamma * values[t + 1]; delta = target - values[t], added by _add_moves_on_host (to acc_abs too,
+    where one is given).  Returns dict(learnt, skipped, clamped)."""
     keys, values, steps = np.asarray(keys, dtype=_U64), np.asarray(values, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
     T = keys.shape[0]
     last = np.arange(T, dtype=np.int64)[:, None] == np.minimum(np.asarray(lengths, dtype=np.int64).reshape(-1), T)[None, :] - 1
     nxt_r, nxt_v = np.zeros_like(values), np.zeros_like(values)
     nxt_r[:-1], nxt_v[:-1] = ((steps[1:] >> 2) & 31).astype(np.float64), values[1:]
     target = np.where(last, 0.0, nxt_r + float(gamma) * nxt_v)
-    return _add_moves_on_host(keys, steps, lengths, target - values, tuples, symmetric, acc)
+    return _add_moves_on_host(keys, steps, lengths, target - values, tuples, symmetric, acc, acc_abs)
 
 
 def lambda_deltas_on_host(values, steps, lengths, gamma: float, lam: float) -> np.ndarray:
@@ -249,13 +258,13 @@ def lambda_deltas_on_host(values, steps, lengths, gamma: float, lam: float) -> n
     return out
 
 
-def learn_lambda_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, lam: float, acc) -> dict:
+def learn_lambda_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, lam: float, acc, acc_abs=None) -> dict:
     """pulse_tfe_nt_learn_lambda on the host: learn_nt_on_host with lambda_deltas_on_host's D_t in place of the one-step difference.
     The skipped moves, the clamp to +-DELTA_MAX (applied to the add only: the recurrence carries the unclamped D), d and the adds are
     _add_moves_on_host's.  Returns dict(learnt, skipped, clamped, deltas float64[T, B])."""
     keys, values, steps = np.asarray(keys, dtype=_U64), np.asarray(values, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
     deltas = lambda_deltas_on_host(values, steps, lengths, gamma, lam)
-    return dict(_add_moves_on_host(keys, steps, lengths, deltas, tuples, symmetric, acc), deltas=deltas)
+    return dict(_add_moves_on_host(keys, steps, lengths, deltas, tuples, symmetric, acc, acc_abs), deltas=deltas)
 
 
 def apply_nt_on_host(weights, acc, step: float) -> int:
@@ -268,17 +277,54 @@ def apply_nt_on_host(weights, acc, step: float) -> int:
     return len(at)
 
 
+def learn_tc_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, lam: float, acc, acc_abs) -> dict:
+    """pulse_tfe_nt_learn_tc on the host: learn_nt_on_host (lam == 0) or learn_lambda_nt_on_host (lam > 0) with the third accumulator,
+    acc_abs int64[W] += |d| wherever those add sum += d, cnt += 1.  Returns what they return."""
+    if float(lam) > 0.0:
+        return learn_lambda_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma, lam, acc, acc_abs)
+    return learn_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma, acc, acc_abs)
+
+
+def apply_tc_nt_on_host(weights, acc, acc_abs, E, A, step: float):
+    """pulse_tfe_nt_apply_tc on the host, in place, float64 with one rounding per operation.  Where cnt > 0: m = (sum / cnt) * 2^-16,
+    a = (abs / cnt) * 2^-16, rho = |E| / A where A > 0 and 1.0 otherwise -- from E and A as they stand, before this round's are added --
+    w = float32(float64(w) + (step * rho) * m), E = E + m, A = A + a, and the three accumulator words become 0.  A weight with
+    cnt == 0 keeps its bits, its E and its A.  Returns (weights moved, the sum over them of round-half-even(rho * 2^32)): what the
+    launch adds to tc_stats."""
+    at = np.flatnonzero(acc[:, 1] > 0)
+    cnt = acc[at, 1].astype(np.float64)
+    m = acc[at, 0].astype(np.float64) / cnt * 2.0 ** -FRAC_BITS
+    a = acc_abs[at].astype(np.float64) / cnt * 2.0 ** -FRAC_BITS
+    e0, a0 = E[at], A[at]
+    rho = np.ones(len(at), dtype=np.float64)
+    pos = a0 > 0.0
+    rho[pos] = np.abs(e0[pos]) / a0[pos]
+    weights[at] = (weights[at].astype(np.float64) + (np.float64(step) * rho) * m).astype(np.float32)
+    E[at], A[at] = e0 + m, a0 + a
+    acc[at] = 0
+    acc_abs[at] = 0
+    return len(at), int(np.rint(np.ldexp(rho, TC_RHO_BITS)).astype(np.int64).sum())
+
+
+def tc_summary_on_host(words) -> dict:
+    """tc_stats' words as {"moved", "mean_rho"}: mean_rho = words[1] / words[0] * 2^-32, 1.0 where nothing moved."""
+    moved, total = int(words[0]), int(words[1])
+    return dict(moved=moved, mean_rho=(total / moved) * 2.0 ** -TC_RHO_BITS if moved else 1.0)
+
+
 def eval_summary_on_host(words) -> dict:
     """pulse_tfe_nt_evaluate's 8 + 16 counters as a dict (tfe_common.eval_summary_on_host with this agent's EVAL_SUMMARY)."""
     return _eval_summary_on_host(words, EVAL_SUMMARY)
 
 
 # ------------------------------------------------------------------ the checkpoint file
-def write_checkpoint(path, weights, tuples, lam=0.0, **scalars) -> None:
+def write_checkpoint(path, weights, tuples, lam=0.0, tc=None, **scalars) -> None:
     """The network as an .npz of plain arrays (np.savez, no pickles): the non-zero weights as index int64[m] (ascending) and value
     float32[m], the tuples as tuple_len int64[n_tuples] and tuple_cells int64[n_tuples, 6] (-1 beyond a tuple's length), the scalars of
     CHECKPOINT_SCALARS as 0-d arrays and `version`.  lam == 0 writes exactly that, as version 1; any other `lam` adds a 0-d float64
-    `lam` and writes version 2.  `path` is written as given."""
+    `lam` and writes version 2.  tc = (E, A), float64[n_weights] each, writes version 4: version 2's arrays with `lam` whatever its
+    value, tc_index int64[m'] (ascending: the weights whose E or A is not +0.0 by bit pattern) and tc_e / tc_a float64[m'].  `path` is
+    written as given."""
     if sorted(scalars) != sorted(CHECKPOINT_SCALARS):
         raise ValueError(f"a checkpoint holds exactly the scalars {CHECKPOINT_SCALARS}")
     weights = np.asarray(weights, dtype=np.float32).reshape(-1)
@@ -289,29 +335,42 @@ def write_checkpoint(path, weights, tuples, lam=0.0, **scalars) -> None:
     dtypes = dict(gamma=np.float64, epsilon=np.float64, alpha=np.float64, seed=np.uint64, board_id0=np.uint64)
     arrays = {k: np.array(scalars[k], dtype=dtypes.get(k, np.int64)) for k in CHECKPOINT_SCALARS}
     version = CHECKPOINT_VERSION
-    if float(lam) != 0.0:
+    if float(lam) != 0.0 or tc is not None:
         arrays["lam"], version = np.array(lam, dtype=np.float64), CHECKPOINT_VERSION_LAMBDA
+    if tc is not None:
+        E, A = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in tc)
+        if E.shape != weights.shape or A.shape != weights.shape:
+            raise ValueError("tc = (E, A), one float64 per weight each")
+        at = np.flatnonzero((E.view(np.uint64) != 0) | (A.view(np.uint64) != 0))
+        arrays.update(tc_index=at.astype(np.int64), tc_e=E[at], tc_a=A[at])
+        version = CHECKPOINT_VERSION_TC
     with open(path, "wb") as fh:
         np.savez(fh, version=np.array(version, dtype=np.int64), index=index.astype(np.int64), value=weights[index],
                  tuple_len=np.array([len(t) for t in tuples], dtype=np.int64), tuple_cells=cells, **arrays)
 
 
 def read_checkpoint(path) -> dict:
-    """What write_checkpoint wrote (np.load with allow_pickle=False), version 1 or 2: `tuples`, `index`, `value`, `n_weights`, the
-    scalars as Python numbers and `lam` (0.0 for version 1).  ValueError for another format version, a missing array, tuples the library would refuse or an index outside
-    the network."""
+    """What write_checkpoint wrote (np.load with allow_pickle=False), version 1, 2 or 4: `tuples`, `index`, `value`, `n_weights`, the
+    scalars as Python numbers, `lam` (0.0 for version 1) and `tc` (False for versions 1 and 2); for version 4 also `tc_index`, `tc_e`
+    and `tc_a`.  ValueError for another format version, a missing array, tuples the library would refuse or an index outside the
+    network."""
     with np.load(path, allow_pickle=False) as f:
         missing = [k for k in ("version", "index", "value", "tuple_len", "tuple_cells") + CHECKPOINT_SCALARS if k not in f.files]
         if missing:
             raise ValueError(f"{path}: not an n-tuple network checkpoint (no {missing})")
         version = int(f["version"])
-        if version not in (CHECKPOINT_VERSION, CHECKPOINT_VERSION_LAMBDA):
-            raise ValueError(f"{path}: format version {version}, this package reads {CHECKPOINT_VERSION} and {CHECKPOINT_VERSION_LAMBDA}")
-        if version == CHECKPOINT_VERSION_LAMBDA and "lam" not in f.files:
-            raise ValueError(f"{path}: not an n-tuple network checkpoint (no ['lam'])")
+        if version not in (CHECKPOINT_VERSION, CHECKPOINT_VERSION_LAMBDA, CHECKPOINT_VERSION_TC):
+            raise ValueError(f"{path}: format version {version}, this package reads {CHECKPOINT_VERSION}, {CHECKPOINT_VERSION_LAMBDA} and "
+                             f"{CHECKPOINT_VERSION_TC}")
+        more = {CHECKPOINT_VERSION: (), CHECKPOINT_VERSION_LAMBDA: ("lam",), CHECKPOINT_VERSION_TC: ("lam", "tc_index", "tc_e", "tc_a")}[version]
+        missing = [k for k in more if k not in f.files]
+        if missing:
+            raise ValueError(f"{path}: not an n-tuple network checkpoint (no {missing})")
         out = {k: (float(f[k]) if k in ("gamma", "epsilon", "alpha") else int(f[k])) for k in CHECKPOINT_SCALARS}
-        out["lam"] = float(f["lam"]) if version == CHECKPOINT_VERSION_LAMBDA else 0.0
+        out["lam"] = float(f["lam"]) if "lam" in more else 0.0
+        out["tc"] = version == CHECKPOINT_VERSION_TC
         index, value, lens, cells = f["index"], f["value"], f["tuple_len"], f["tuple_cells"]
+        tc_arrays = [f[k] for k in more[1:]]
     out["symmetric"] = bool(out["symmetric"])
     out["tuples"] = check_tuples([cells[i, :int(n)].tolist() for i, n in enumerate(lens.tolist())])
     out["n_weights"] = tuple_offsets(out["tuples"])[1]
@@ -320,7 +379,21 @@ def read_checkpoint(path) -> dict:
     if len(index) and (int(index[0]) < 0 or int(index[-1]) >= out["n_weights"] or not bool((index[1:] > index[:-1]).all())):
         raise ValueError(f"{path}: index must be strictly ascending inside the network's {out['n_weights']} weights")
     out["index"], out["value"] = index, value
+    if out["tc"]:
+        at, e, a = tc_arrays
+        if at.dtype != np.int64 or e.dtype != np.float64 or a.dtype != np.float64 or at.ndim != 1 or e.shape != at.shape or a.shape != at.shape:
+            raise ValueError(f"{path}: tc_index must be int64[m] and tc_e / tc_a float64[m]")
+        if len(at) and (int(at[0]) < 0 or int(at[-1]) >= out["n_weights"] or not bool((at[1:] > at[:-1]).all())):
+            raise ValueError(f"{path}: tc_index must be strictly ascending inside the network's {out['n_weights']} weights")
+        out["tc_index"], out["tc_e"], out["tc_a"] = at, e, a
     return out
+
+
+def coherence_of_checkpoint(f: dict):
+    """(E, A), float64[n_weights] each, of a version-4 read_checkpoint dict."""
+    E, A = np.zeros(f["n_weights"], dtype=np.float64), np.zeros(f["n_weights"], dtype=np.float64)
+    E[f["tc_index"]], A[f["tc_index"]] = f["tc_e"], f["tc_a"]
+    return E, A
 
 
 def weights_of_checkpoint(f: dict) -> np.ndarray:
@@ -335,13 +408,15 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     """`learn_batch` = `rollout` + `learn` + `apply` + `round += 1`: three launches and no synchronisation.  Everything that reads
     back (`weights`, `stats`, `trajectory`, `evaluate`, the per-game arrays' `.cpu()`) synchronises.  Round r plays the boards
     board_id0 + r * n_games + g, so no two rounds replay the same spawns.  `lam` > 0: `learn` is the TD(lambda) launch and the agent
-    holds `deltas`, float64 in the shape of `values`; `lam` = 0 (the default) allocates nothing more and learns by TD(0)."""
+    holds `deltas`, float64 in the shape of `values`; `lam` = 0 (the default) allocates nothing more and learns by TD(0).  `tc`:
+    temporal-coherence step sizes (section 13.3): `learn` is pulse_tfe_nt_learn_tc under the agent's `lam`, `apply` is
+    pulse_tfe_nt_apply_tc, and the agent holds `acc_abs`, `E`, `A` and `tc_stats`; without it (the default) none of them exists."""
     STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
 
     def __init__(self, device, n_games, tuples=DEFAULT_TUPLES, symmetric=True, gamma=1.0, epsilon=0.0, alpha=1.0, max_steps=4096, seed=0,
-                 board_id0=0, lam=0.0):
+                 board_id0=0, lam=0.0, tc=False):
         import torch
-        self.lam = check_lam(lam)
+        self.lam, self.tc = check_lam(lam), bool(tc)
         super().__init__(device, n_games, 4, max_steps, gamma, epsilon, seed, board_id0)
         self.tuples, self.symmetric, self.alpha = check_tuples(tuples), bool(symmetric), float(alpha)
         self.n_features = len(self.tuples) * (8 if self.symmetric else 1)
@@ -352,6 +427,9 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         self.acc = torch.zeros((self.n_weights, 2), dtype=torch.int64, device=self.device)            # {sum, cnt}; torch allocations are 16-byte aligned
         self.values = torch.zeros((self.max_steps, self.n_games), dtype=torch.float64, device=self.device)
         self.deltas = torch.zeros_like(self.values) if self.lam > 0.0 else None
+        self.acc_abs = self.E = self.A = self.tc_stats = None
+        if self.tc:
+            self._tc_state()
 
     # ------------------------------------------------------------------ the launches
     def _net(self, net):
@@ -380,9 +458,20 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         o.acc, o.stats = self.acc.data_ptr(), self.counters.data_ptr()
         return o
 
+    def _tc_state(self):
+        """The third accumulator, E, A and tc_stats, zeroed, where the agent has none yet."""
+        import torch
+        if self.acc_abs is None:
+            self.acc_abs = torch.zeros(self.n_weights, dtype=torch.int64, device=self.device)
+            self.E = torch.zeros(self.n_weights, dtype=torch.float64, device=self.device)
+            self.A = torch.zeros(self.n_weights, dtype=torch.float64, device=self.device)
+            self.tc_stats = torch.zeros(4, dtype=torch.int64, device=self.device)
+
     def learn(self):
         """The temporal differences of the games last played, into the accumulators: one launch, or with lam > 0
-        learn_lambda_launch's two."""
+        learn_lambda_launch's two; with tc, learn_tc_launch's."""
+        if self.tc:
+            return self.learn_tc_launch(self.lam)
         if self.lam > 0.0:
             return self.learn_lambda_launch(self.lam)
         return self._launch("pulse_tfe_nt_learn", self._moves(_native.TfeNtLearn()))
@@ -398,8 +487,36 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         o.lam, o.deltas = lam, self.deltas.data_ptr()
         return self._launch("pulse_tfe_nt_learn_lambda", o)
 
+    def learn_tc_launch(self, lam):
+        """pulse_tfe_nt_learn_tc on the games last played, whatever the agent's own `lam` and `tc`: the adds of learn() (lam == 0: one
+        launch, no deltas) or of learn_lambda_launch (lam > 0: the walk into `deltas`, then the adds), with |d| into `acc_abs` as
+        well.  Allocates the TC state, and for lam > 0 `deltas`, if the agent has none."""
+        import torch
+        lam = check_lam(lam)
+        self._tc_state()
+        o = self._moves(_native.TfeNtLearnTc())
+        o.lam, o.acc_abs = lam, self.acc_abs.data_ptr()
+        if lam > 0.0:
+            if self.deltas is None:
+                self.deltas = torch.zeros_like(self.values)
+            o.deltas = self.deltas.data_ptr()
+        return self._launch("pulse_tfe_nt_learn_tc", o)
+
+    def apply_tc_launch(self):
+        """pulse_tfe_nt_apply_tc: every visited weight moves by (alpha / F) * rho of the mean of its adds, rho = |E| / A as they stood;
+        E and A take the round's means, the three accumulator words are zero afterwards and tc_stats has the round added."""
+        self._tc_state()
+        o = _native.TfeNtApplyTc()
+        self._net(o.net)
+        o.step, o.acc, o.acc_abs = self.alpha / self.n_features, self.acc.data_ptr(), self.acc_abs.data_ptr()
+        o.e, o.a, o.tc_stats = self.E.data_ptr(), self.A.data_ptr(), self.tc_stats.data_ptr()
+        return self._launch("pulse_tfe_nt_apply_tc", o)
+
     def apply(self):
-        """One launch: every visited weight moves by alpha / F of the mean of its adds; the accumulators are zero afterwards."""
+        """One launch: every visited weight moves by alpha / F of the mean of its adds; the accumulators are zero afterwards.  With
+        tc, apply_tc_launch."""
+        if self.tc:
+            return self.apply_tc_launch()
         o = _native.TfeNtApply()
         self._net(o.net)
         o.step, o.acc = self.alpha / self.n_features, self.acc.data_ptr()
@@ -480,20 +597,39 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         T, _ = self._played()
         return self.deltas[:T].cpu().numpy()
 
+    def coherence(self):
+        """(E, A), float64[n_weights] each, on the host."""
+        if self.E is None:
+            raise ValueError("no temporal-coherence launch has run: the agent holds no E and A")
+        return self.E.cpu().numpy(), self.A.cpu().numpy()
+
+    def tc_summary(self) -> dict:
+        """{"moved", "mean_rho"} of the apply_tc launches since the last call (tc_summary_on_host; synchronises), and tc_stats zeroed."""
+        if self.tc_stats is None:
+            raise ValueError("no temporal-coherence launch has run: the agent holds no tc_stats")
+        out = tc_summary_on_host(self.tc_stats.cpu().tolist())
+        self.tc_stats.zero_()
+        return out
+
     def save(self, path):
-        """The non-zero weights and what a continued run needs as an .npz (write_checkpoint)."""
+        """The non-zero weights and what a continued run needs as an .npz (write_checkpoint); with tc, E and A too."""
         write_checkpoint(path, self.weights(), self.tuples, symmetric=int(self.symmetric), gamma=self.gamma, epsilon=self.epsilon, alpha=self.alpha,
-                         max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games, lam=self.lam)
+                         max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games, lam=self.lam,
+                         tc=self.coherence() if self.tc else None)
 
     @classmethod
     def load(cls, path, device, n_games=None):
-        """The agent save() wrote: weights, round, seeds and lam restored.  With the saved n_games it continues the run the saved agent would
+        """The agent save() wrote: weights, round, seeds, lam, tc and with it E and A restored.  With the saved n_games it continues the run the saved agent would
         have continued (another n_games plays other boards: round r starts at board_id0 + r * n_games)."""
         import torch
         f = read_checkpoint(path)
         agent = cls(device, f["n_games"] if n_games is None else n_games, tuples=f["tuples"], symmetric=f["symmetric"], gamma=f["gamma"],
-                    epsilon=f["epsilon"], alpha=f["alpha"], max_steps=f["max_steps"], seed=f["seed"], board_id0=f["board_id0"], lam=f["lam"])
+                    epsilon=f["epsilon"], alpha=f["alpha"], max_steps=f["max_steps"], seed=f["seed"], board_id0=f["board_id0"], lam=f["lam"], tc=f["tc"])
         agent.weights_dev.copy_(torch.from_numpy(weights_of_checkpoint(f)))
+        if f["tc"]:
+            E, A = coherence_of_checkpoint(f)
+            agent.E.copy_(torch.from_numpy(E))
+            agent.A.copy_(torch.from_numpy(A))
         agent.round = f["round"]
         return agent
 
@@ -502,5 +638,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         self.weights_dev.zero_()
         self.acc.zero_()
         self.counters.zero_()
+        for t in (self.acc_abs, self.E, self.A, self.tc_stats):
+            if t is not None:
+                t.zero_()
         self.round = 0
         return self

@@ -8,8 +8,9 @@
 // cells and hands the kernels 6 shift counts per feature in one 64-bit word, by value, so a nibble is a shift by a scalar and no lane
 // indexes an array.  The learner runs one lane per recorded move and adds temporal differences as fixed-point integers, so the
 // accumulators do not depend on scheduling; the apply launch moves each weight by step * the mean of its adds.
-// The game loop (play_game) is tfe_ntuple_device.h's, shared with tfe_ntuple_search.hip; the learner's kernel (tfe_nt_scatter_kernel,
-// launch_scatter) also makes the adds of tfe_ntuple_lambda.hip's TD(lambda) learner.
+// The game loop (play_game) is tfe_ntuple_device.h's, shared with tfe_ntuple_search.hip, and so is the learner's kernel
+// (tfe_nt_scatter_kernel), instantiated here by launch_scatter, which also makes the adds of tfe_ntuple_lambda.hip's TD(lambda)
+// learner; tfe_ntuple_tc.hip instantiates the same text with a third accumulator.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -40,46 +41,6 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_games_kernel(const Games o, con
 #pragma unroll
                           for (int a = 0; a < 4; ++a) q[a] = __dadd_rn((double)tfe_reward(sc[a]), __dmul_rn(o.gamma, v[a]));
                       });
-}
-
-// The learners' adds, one lane per recorded move: blockIdx.y = t, blockIdx.x * kBlock + threadIdx.x = g.  Given: the move's difference
-// is o.deltas' (pulse_tfe_nt_learn_lambda, after its walk); otherwise it is the one-step difference, formed here (pulse_tfe_nt_learn).
-template <int IMG, bool Given>
-__global__ __launch_bounds__(kBlock) void tfe_nt_scatter_kernel(const Moves o, const NtDev net) {
-    __shared__ unsigned long long wg[3];
-    if (threadIdx.x < 3) wg[threadIdx.x] = 0ull;
-    __syncthreads();
-    const int g = blockIdx.x * kBlock + threadIdx.x, t = (int)blockIdx.y;
-    const size_t B = (size_t)o.n_games;
-    if (g < o.n_games) {
-        int length = o.lengths[g];
-        length = length > o.max_steps ? o.max_steps : length;                          // (the buffers hold max_steps rows)
-        if (t < length) {
-            const size_t at = (size_t)t * B + (size_t)g;
-            const bool last = t == length - 1;
-            const bool skip = last && (o.steps[at] & 0x80u) == 0u;
-            if (skip) {
-                atomicAdd(&wg[1], 1ull);                                                // LDS
-            } else {
-                double delta;
-                if constexpr (Given) {
-                    delta = o.deltas[at];
-                } else {
-                    double target = 0.0;
-                    if (!last) target = td_target(o.steps[at + B], o.values[at + B], o.gamma);
-                    delta = __dsub_rn(target, o.values[at]);
-                }
-                bool clamp;
-                const unsigned long long d = td_fixed(delta, clamp);
-                add_features<IMG>(net, reinterpret_cast<unsigned long long*>(o.acc), o.keys[at], d);
-                atomicAdd(&wg[0], 1ull);
-                if (clamp) atomicAdd(&wg[2], 1ull);
-            }
-        }
-    }
-    __syncthreads();
-    const int i = (int)threadIdx.x;
-    if (i < 3 && wg[i]) atomicAdd(reinterpret_cast<unsigned long long*>(o.stats) + (i == 0 ? 1 : i == 1 ? 2 : 4), wg[i]);
 }
 
 __global__ __launch_bounds__(kBlock) void tfe_nt_apply_kernel(float* __restrict__ weights, longlong2* __restrict__ acc, uint64_t n_weights, double step) {
@@ -151,14 +112,14 @@ int check_net(const PulseTfeNtNet& n, bool need_weights, const char* name, NtDev
 }
 
 void launch_scatter(const Moves& m, const NtDev& dev, bool symmetric, void* stream) {
-    const dim3 grid((unsigned)((m.n_games + kBlock - 1) / kBlock), (unsigned)m.max_steps), block(kBlock);
+    const dim3 grid((unsigned)((m.n_games + kScatterBlock - 1) / kScatterBlock), (unsigned)m.max_steps), block(kScatterBlock);
     hipStream_t st = (hipStream_t)stream;
     if (m.deltas) {
-        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, true>), grid, block, 0, st, m, dev);
-        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, true>), grid, block, 0, st, m, dev);
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, true, false>), grid, block, 0, st, m, dev);
+        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, true, false>), grid, block, 0, st, m, dev);
     } else {
-        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, false>), grid, block, 0, st, m, dev);
-        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, false>), grid, block, 0, st, m, dev);
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, false, false>), grid, block, 0, st, m, dev);
+        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, false, false>), grid, block, 0, st, m, dev);
     }
 }
 

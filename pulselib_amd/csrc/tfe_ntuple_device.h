@@ -1,7 +1,7 @@
 // tfe_ntuple_device.h -- what the units of the 2048 n-tuple network share (tfe_ntuple.hip: the learner's four launches; tfe_ntuple_search.hip:
-// expectimax play; tfe_ntuple_lambda.hip: the TD(lambda) walk): the network as the kernels take it, a feature's index, V of four
-// afterstates at once, the learners' target, fixed-point difference and adds, their parameters (Moves), shared refusals
-// (check_moves) and scatter launch, the four moves of a board, the greedy action, the game loop (play_game) with its parameters
+// expectimax play; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes): the network as the
+// kernels take it, a feature's index, V of four afterstates at once, the learners' target, fixed-point difference and adds, their
+// parameters (Moves), shared refusals (check_moves), scatter kernel and launches, the four moves of a board, the greedy action, the game loop (play_game) with its parameters
 // (Games) and the host's checks of the network, of the accumulators and of a batch of games.  One copy each.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -77,9 +77,12 @@ __device__ __forceinline__ unsigned long long td_fixed(double delta, bool& clamp
     return (unsigned long long)llrint(ldexp(delta, PULSE_TFE_NT_FRAC_BITS));
 }
 
-// ... and its adds: sum += d, cnt += 1 at every feature of `key`
-template <int IMG>
-__device__ __forceinline__ void add_features(const NtDev& net, unsigned long long* acc, const uint64_t key, const unsigned long long d) {
+// ... and its adds: sum += d, cnt += 1 at every feature of `key`; with Abs (temporal-coherence step sizes, tfe_ntuple_tc.hip) also
+// acc_abs += |d|, d read as signed
+template <int IMG, bool Abs>
+__device__ __forceinline__ void add_features(const NtDev& net, unsigned long long* acc, unsigned long long* acc_abs, const uint64_t key,
+                                             const unsigned long long d) {
+    const unsigned long long mag = (long long)d < 0 ? 0ull - d : d;
 #pragma unroll 1
     for (int tu = 0; tu < net.n_tuples; ++tu) {
         const uint32_t mask = net.mask[tu], offset = net.offset[tu];
@@ -88,6 +91,7 @@ __device__ __forceinline__ void add_features(const NtDev& net, unsigned long lon
             const size_t idx = (size_t)feature_index(key, net.shifts[tu * IMG + j], mask, offset);
             atomicAdd(acc + 2 * idx, d);
             atomicAdd(acc + 2 * idx + 1, 1ull);
+            if constexpr (Abs) atomicAdd(acc_abs + idx, mag);
         }
     }
 }
@@ -139,7 +143,8 @@ inline int check_acc(const int64_t* acc, const char* name) {
     return 0;
 }
 
-// The learners' counterpart of Games: what pulse_tfe_nt_learn and pulse_tfe_nt_learn_lambda hand the scatter (deltas: null for TD(0))
+// The learners' counterpart of Games: what pulse_tfe_nt_learn, pulse_tfe_nt_learn_lambda and pulse_tfe_nt_learn_tc hand the scatter
+// (deltas: null for TD(0); acc_abs: pulse_tfe_nt_learn_tc's third accumulator, null for the other two)
 struct Moves {
     int32_t n_games, max_steps;
     double gamma;
@@ -147,6 +152,7 @@ struct Moves {
     const int32_t* lengths;
     const double* deltas;
     int64_t* acc; int64_t* stats;
+    int64_t* acc_abs;
 };
 
 // ... what both learners refuse, and the scatter's parameters of their struct (deltas left null)
@@ -161,13 +167,61 @@ int check_moves(const O* o, const char* name, NtDev* dev, Moves* m) {
     if (!o->lengths) return fail_named(name, "lengths is null");
     if (int rc = check_acc(o->acc, name)) return rc;
     if (!o->stats) return fail_named(name, "stats is null");
-    *m = Moves{o->n_games, o->max_steps, o->gamma, o->keys, o->values, o->steps, o->lengths, nullptr, o->acc, o->stats};
+    *m = Moves{o->n_games, o->max_steps, o->gamma, o->keys, o->values, o->steps, o->lengths, nullptr, o->acc, o->stats, nullptr};
     return 0;
 }
 
-// ... and their adds, one lane per recorded move: the difference is m.deltas' where it is set and the one-step difference otherwise
-// (defined in tfe_ntuple.hip)
+// The learners' adds, one lane per recorded move: blockIdx.y = t, blockIdx.x * kScatterBlock + threadIdx.x = g.  Given: the move's
+// difference is o.deltas' (after the walk of tfe_ntuple_lambda.hip); otherwise it is the one-step difference, formed here.  Abs: the
+// adds go to o.acc_abs too (add_features).  One text: tfe_ntuple.hip instantiates the four forms without Abs, tfe_ntuple_tc.hip the
+// four with it.
+constexpr int kScatterBlock = 256;
+
+template <int IMG, bool Given, bool Abs>
+__global__ __launch_bounds__(kScatterBlock) void tfe_nt_scatter_kernel(const Moves o, const NtDev net) {
+    __shared__ unsigned long long wg[3];
+    if (threadIdx.x < 3) wg[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int g = blockIdx.x * kScatterBlock + threadIdx.x, t = (int)blockIdx.y;
+    const size_t B = (size_t)o.n_games;
+    if (g < o.n_games) {
+        int length = o.lengths[g];
+        length = length > o.max_steps ? o.max_steps : length;                          // (the buffers hold max_steps rows)
+        if (t < length) {
+            const size_t at = (size_t)t * B + (size_t)g;
+            const bool last = t == length - 1;
+            const bool skip = last && (o.steps[at] & 0x80u) == 0u;
+            if (skip) {
+                atomicAdd(&wg[1], 1ull);                                                // LDS
+            } else {
+                double delta;
+                if constexpr (Given) {
+                    delta = o.deltas[at];
+                } else {
+                    double target = 0.0;
+                    if (!last) target = td_target(o.steps[at + B], o.values[at + B], o.gamma);
+                    delta = __dsub_rn(target, o.values[at]);
+                }
+                bool clamp;
+                const unsigned long long d = td_fixed(delta, clamp);
+                add_features<IMG, Abs>(net, reinterpret_cast<unsigned long long*>(o.acc), reinterpret_cast<unsigned long long*>(o.acc_abs), o.keys[at], d);
+                atomicAdd(&wg[0], 1ull);
+                if (clamp) atomicAdd(&wg[2], 1ull);
+            }
+        }
+    }
+    __syncthreads();
+    const int i = (int)threadIdx.x;
+    if (i < 3 && wg[i]) atomicAdd(reinterpret_cast<unsigned long long*>(o.stats) + (i == 0 ? 1 : i == 1 ? 2 : 4), wg[i]);
+}
+
+// ... its launch without Abs: the difference is m.deltas' where it is set and the one-step difference otherwise (defined in
+// tfe_ntuple.hip)
 void launch_scatter(const Moves& m, const NtDev& dev, bool symmetric, void* stream);
+
+// ... and the launch of the TD(lambda) walk, which leaves D_t in o.deltas (defined in tfe_ntuple_lambda.hip, where the kernel is): of
+// `o` it reads n_games, max_steps, gamma, lambda, values, steps, lengths and deltas
+void launch_lambda_walk(const PulseTfeNtLearnLambda& o, void* stream);
 
 // what pulse_tfe_nt_evaluate and pulse_tfe_nt_evaluate_search refuse, and the game loop's parameters of an evaluation (defined in
 // tfe_ntuple.hip)

@@ -1,5 +1,6 @@
 // tfe_ntuple_lambda.hip -- the 2048 n-tuple network's TD(lambda) learner, one entry point and two launches:
 // pulse_tfe_nt_learn_lambda (include/pulse_env.h).  This unit holds the first launch's kernel; the second is tfe_ntuple.hip's.
+// launch_lambda_walk is that first launch alone, which pulse_tfe_nt_learn_tc (tfe_ntuple_tc.hip) runs too.
 //
 // The roll-out recorded per move the afterstate's key, its V as float64, the reward and the terminal bit, so the lambda-differences
 // are one backward recurrence per game over data already in memory: D_t = delta_t + (gamma * lambda) * D_{t+1}.  The first kernel
@@ -72,6 +73,14 @@ __global__ __launch_bounds__(kWalkBlock) void tfe_nt_lambda_walk_kernel(const Pu
 
 }  // namespace
 
+namespace pulse_tfe {
+
+void launch_lambda_walk(const PulseTfeNtLearnLambda& o, void* stream) {
+    hipLaunchKernelGGL(tfe_nt_lambda_walk_kernel, dim3((unsigned)((o.n_games + kWalkBlock - 1) / kWalkBlock)), dim3(kWalkBlock), 0, (hipStream_t)stream, o);
+}
+
+}  // namespace pulse_tfe
+
 extern "C" int pulse_tfe_nt_learn_lambda(const PulseTfeNtLearnLambda* o, void* stream) {
     const char* name = "pulse_tfe_nt_learn_lambda";
     NtDev dev;
@@ -82,7 +91,7 @@ extern "C" int pulse_tfe_nt_learn_lambda(const PulseTfeNtLearnLambda* o, void* s
     if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->values & 7u) || ((uintptr_t)o->deltas & 7u) || ((uintptr_t)o->stats & 7u))
         return fail_named(name, "keys / values / deltas / stats must be 8-byte aligned");
     if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
-    hipLaunchKernelGGL(tfe_nt_lambda_walk_kernel, dim3((unsigned)((o->n_games + kWalkBlock - 1) / kWalkBlock)), dim3(kWalkBlock), 0, (hipStream_t)stream, *o);
+    launch_lambda_walk(*o, stream);
     m.deltas = o->deltas;
     launch_scatter(m, dev, o->net.symmetric != 0, stream);
     return finish_launch("pulse_tfe_nt_learn_lambda launch");

@@ -7,7 +7,9 @@ score and its standard error, the mean length and the histogram of the largest t
 the run's state at the end, `--resume PATH` continues such a run for `--rounds` more rounds.  `--search`: every evaluation also runs
 under expectimax search one chance layer deep (section 13.1) on the same boards, and both means are printed; `--resume PATH --rounds 0
 --search` plays a saved network.  `--lambda L` (0 < L <= 1) learns by TD(lambda) (section 13.2): the learn launch walks every game
-backwards first and adds lambda-differences; the run's first line names it, and `--resume` takes it from the file."""
+backwards first and adds lambda-differences; the run's first line names it, and `--resume` takes it from the file.  `--tc` learns with temporal-coherence
+step sizes (section 13.3): every weight moves by rho = |E| / A of the step, from the running sums of its errors; the round's mean rho
+is printed beside the round's counters, and `--resume` takes `tc` from the file too."""
 from __future__ import annotations
 
 import argparse
@@ -19,7 +21,7 @@ from ..agents import NTupleTDAfterstateTFEGPU
 
 
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
-        resume=None, out=print, search=False, lam=0.0):
+        resume=None, out=print, search=False, lam=0.0, tc=False):
     if resume:
         agent = NTupleTDAfterstateTFEGPU.load(resume, device)
         want = dict(n_games=tables, alpha=float(alpha), epsilon=float(epsilon), gamma=float(gamma), max_steps=max_steps, seed=seed)
@@ -27,9 +29,9 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
         if differ:
             raise ValueError(f"{resume} continues another run: (saved, asked) {differ}")
     else:
-        agent = NTupleTDAfterstateTFEGPU(device, tables, gamma=gamma, epsilon=epsilon, alpha=alpha, max_steps=max_steps, seed=seed, lam=lam)
+        agent = NTupleTDAfterstateTFEGPU(device, tables, gamma=gamma, epsilon=epsilon, alpha=alpha, max_steps=max_steps, seed=seed, lam=lam, tc=tc)
     out(f"{agent.n_games} games per round from round {agent.round}: alpha {agent.alpha}, epsilon {agent.epsilon}, gamma {agent.gamma}, "
-        f"lambda {agent.lam}, max_steps {agent.max_steps}, seed {agent.seed}")
+        f"lambda {agent.lam}, tc {agent.tc}, max_steps {agent.max_steps}, seed {agent.seed}")
     first, moves_before, t0 = agent.round, agent.stats()["moves"], time.perf_counter()
 
     def under_search():
@@ -51,9 +53,10 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
         if eval_every and ((r + 1) % eval_every == 0 or r + 1 == first + rounds):
             line = evaluation()
             st, now = agent.stats(), time.perf_counter()
+            rho = f", mean rho {agent.tc_summary()['mean_rho']:.4f}" if agent.tc else ""       # (of the applies since the last line)
             out(f"Round {r}: {line}; "
                 f"training: Avg final score {agent.total_score.double().mean().item():.1f}, moves/sec {(st['moves'] - moves_before) / (now - t0):.0f}, "
-                f"skipped {st['skipped']}, clamped {st['clamped']}{under_search()}")
+                f"skipped {st['skipped']}, clamped {st['clamped']}{rho}{under_search()}")
             moves_before, t0 = st["moves"], time.perf_counter()
     if save:
         agent.save(save)
@@ -69,6 +72,7 @@ def main(argv=None):
     ap.add_argument("--gamma", type=float, default=1.0)
     ap.add_argument("--lambda", dest="lam", type=float, default=0.0, metavar="L",
                     help="TD(lambda): credit decays by gamma * L per move back along the game (0: TD(0)); --resume takes it from the file")
+    ap.add_argument("--tc", action="store_true", help="temporal-coherence step sizes: a weight moves by |E| / A of the step; --resume takes it from the file")
     ap.add_argument("--max-steps", type=int, default=4096)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--eval-every", type=int, default=1, help="rounds between evaluations of the greedy policy (0: never)")
@@ -78,7 +82,7 @@ def main(argv=None):
     ap.add_argument("--search", action="store_true", help="every evaluation also under expectimax search, one chance layer deep")
     args = ap.parse_args(argv)
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
-                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam)
+                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc)
     st = agent.stats()
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
           f"{int((agent.weights_dev != 0).sum().item())} of {agent.n_weights} weights are not zero")

@@ -15,7 +15,11 @@ from the default evaluation boards under the one-ply policy and under expectimax
 per move (a move = one move of one game; the launch's time over all the moves it played) and the ratio of the two.  --lambda L: per B one more line, {"lambda": ...}: on the games of the last timed round, in the same
 process and back to back, the TD(0) learn launch (pulse_tfe_nt_learn) and the TD(lambda) launch (pulse_tfe_nt_learn_lambda: the backward
 walk and the adds) each between its own pair of HIP events, --warmup untimed pairs and then --repeats timed ones, alternating; the
-accumulators are zeroed, untimed, before every launch, so both add the same moves into empty cells.  max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes).  Lines are also
+accumulators are zeroed, untimed, before every launch, so both add the same moves into empty cells.  --tc: per B one more line, marked {"tc": true}: on the games of the last timed round, in the same process and alternating, the fixed-step pair
+(pulse_tfe_nt_learn, then pulse_tfe_nt_apply on what it added) and the temporal-coherence pair (pulse_tfe_nt_learn_tc, then
+pulse_tfe_nt_apply_tc), with --lambda L also pulse_tfe_nt_learn_lambda beside pulse_tfe_nt_learn_tc at L; every launch
+between its own pair of HIP events, the accumulators zeroed (untimed) before every learn launch; the weights are put back and E and
+A zeroed afterwards.  max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes).  Lines are also
 appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
 import argparse
 import json
@@ -103,6 +107,47 @@ def lambda_line(agent, torch, lam, warmup, repeats):
                        "atomics": 2 * agent.n_features * moves}}
 
 
+def tc_line(agent, torch, lam, warmup, repeats):
+    """the fixed-step and the temporal-coherence launches on the games the agent last recorded (the agent's own lam is 0 and its tc off:
+    learn() and apply() are the TD(0) launch and the fixed-step apply)"""
+    launches = [("learn", agent.learn, "apply", agent.apply), ("learn_tc", lambda: agent.learn_tc_launch(0.0), "apply_tc", agent.apply_tc_launch)]
+    if lam:
+        launches += [("learn_lambda", lambda: agent.learn_lambda_launch(lam), None, agent.apply),
+                     ("learn_tc_lambda", lambda: agent.learn_tc_launch(lam), None, agent.apply_tc_launch)]
+    agent.learn_tc_launch(0.0)                                              # untimed: allocates acc_abs, E, A and tc_stats
+    weights, before = agent.weights_dev.clone(), agent.stats()
+    seconds = {name: [] for row in launches for name in (row[0], row[2]) if name}
+    for i in range(warmup + repeats):
+        for learn_name, learn, apply_name, apply in launches:
+            agent.acc.zero_()
+            agent.acc_abs.zero_()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record()
+            learn()
+            ev[1].record()
+            apply()
+            ev[2].record()
+            ev[2].synchronize()
+            if i >= warmup:
+                seconds[learn_name].append(ev[0].elapsed_time(ev[1]) * 1e-3)
+                if apply_name:
+                    seconds[apply_name].append(ev[1].elapsed_time(ev[2]) * 1e-3)
+    moves = (agent.stats()["learnt"] - before["learnt"]) // (len(launches) * (warmup + repeats))
+    tc = agent.tc_summary()
+    agent.weights_dev.copy_(weights)
+    for t in (agent.acc, agent.acc_abs, agent.E, agent.A):
+        t.zero_()
+    out = {name + "_s": _spread(xs) for name, xs in seconds.items()}
+    med = lambda name: out[name + "_s"]["median"]
+    out.update(learn_ratio=med("learn_tc") / med("learn"), apply_ratio=med("apply_tc") / med("apply"),
+               round_overhead_s=med("learn_tc") + med("apply_tc") - med("learn") - med("apply"))
+    if lam:
+        out.update(learn_lambda_ratio=med("learn_tc_lambda") / med("learn_lambda"))
+    return {"tc": True, "games": agent.n_games, "lambda": lam or 0.0, "gamma": agent.gamma, "trained_rounds": agent.round, "max_steps": agent.max_steps,
+            "warmup": warmup, "repeats": repeats, "moves_learnt": moves, "weights": agent.n_weights, "weights_moved_per_apply_tc": tc["moved"] // (
+                (2 if lam else 1) * (warmup + repeats)), "atomics": 2 * agent.n_features * moves, "atomics_tc": 3 * agent.n_features * moves, **out}
+
+
 def state_line(agent, torch, state, trained_rounds, warmup, repeats):
     agent.clear()
     for _ in range(trained_rounds if state == "trained" else 0):
@@ -143,6 +188,7 @@ def main(argv=None):
     ap.add_argument("--search", action="store_true", help="one more line per B: the evaluation under search beside the one-ply one")
     ap.add_argument("--search-games", type=int, nargs="+", default=[1024, 65536])
     ap.add_argument("--lambda", dest="lam", type=float, help="one more line per B: the TD(lambda) learn launch beside the TD(0) one, on the same games")
+    ap.add_argument("--tc", action="store_true", help="one more line per B: the temporal-coherence learn and apply launches beside the fixed-step ones")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
     args = ap.parse_args(argv)
     import torch
@@ -153,7 +199,7 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     for games in args.games:
-        need = 20 * tuple_offsets(DEFAULT_TUPLES)[1] + (17 if args.lam is None else 25) * games * args.max_steps + 64 * games
+        need = (48 if args.tc else 20) * tuple_offsets(DEFAULT_TUPLES)[1] + (17 if args.lam is None else 25) * games * args.max_steps + 64 * games
         free = torch.cuda.mem_get_info(dev)[0]
         if need > 0.9 * free:
             lines = [{"games": games, "skipped": f"needs {need} bytes of device memory, {free} are free"}]
@@ -164,6 +210,8 @@ def main(argv=None):
                 lines += [search_line(agent, torch, g, args.repeats) for g in args.search_games]
             if args.lam is not None:                                        # on the games the last timed round recorded
                 lines.append(lambda_line(agent, torch, args.lam, args.warmup, args.repeats))
+            if args.tc:                                                     # likewise
+                lines.append(tc_line(agent, torch, args.lam, args.warmup, args.repeats))
             del agent
             torch.cuda.empty_cache()
         for line in lines:
