@@ -935,6 +935,20 @@ typedef struct PulseTfeNtSearch {
 int pulse_tfe_nt_search(const PulseTfeNtSearch* o, void* stream);
 int pulse_tfe_nt_evaluate_search(const PulseTfeNtEval* o, void* stream);
 
+/* ---- ... two chance layers deep.  The two structs above, with the depth beside them: `layers` = 1 is exactly the two entry points
+ * above (the same kernels); `layers` = 2 replaces m(C) by W2(C), the best q of the one-layer search of C:
+ *   W2(C)  = the best of q_a'(C) over the candidates a' of C, q(C) being the four q of the definition above on board C (its own
+ *            chance boards, terms, tree and division); scanned a' = 0..3, the first candidate starts and a strictly larger q
+ *            replaces it; +0.0 where C has no candidate.  No tie coins are drawn inside the tree;
+ *   term_s = P_k * W2(C(c, k)), +0.0 at a slot whose cell is filled; S, E_a, q_a and the action as above.
+ * One board or game per workgroup of 256 lanes: the live (move, slot) children are dealt to its 8 groups of 32 lanes, each of which
+ * searches its child as the one-layer kernels search a board; the terms meet in LDS and are summed in the order above.
+ *
+ * PULSE_EINVAL, before anything is launched: what pulse_tfe_nt_search / pulse_tfe_nt_evaluate_search refuse, under these names;
+ * `layers` other than 1 or 2 ("layers must be 1 or 2"). */
+int pulse_tfe_nt_search_deep(const PulseTfeNtSearch* o, int32_t layers, void* stream);
+int pulse_tfe_nt_evaluate_search_deep(const PulseTfeNtEval* o, int32_t layers, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

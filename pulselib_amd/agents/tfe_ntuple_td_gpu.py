@@ -9,7 +9,8 @@ moves that change the board, and records per move the afterstate's key, its V an
 recorded move and adds the temporal difference reward' + gamma * V' - V (0 - V at a terminal move) as a fixed-point integer into
 {sum, cnt} of every weight the afterstate reads; `pulse_tfe_nt_apply` moves every visited weight by alpha / F of the MEAN of its
 adds and zeroes the accumulators.  `pulse_tfe_nt_evaluate` plays games without a trajectory and reduces the scores in the launch; `pulse_tfe_nt_search` and
-`pulse_tfe_nt_evaluate_search` play under expectimax search one chance layer deep (section 13.1), 32 lanes per board.  With `lam > 0`
+`pulse_tfe_nt_evaluate_search` play under expectimax search one chance layer deep (section 13.1), 32 lanes per board; with `layers=2`
+`pulse_tfe_nt_search_deep` and `pulse_tfe_nt_evaluate_search_deep` search two (section 13.4), 256 lanes per board.  With `lam > 0`
 the learn launch is `pulse_tfe_nt_learn_lambda` (section 13.2): one lane per game walks the recorded game backwards and leaves the
 lambda-differences D_t = delta_t + gamma * lam * D_{t+1} in `deltas`, and the same one-lane-per-move adds follow with D_t for delta_t.
 
@@ -159,14 +160,27 @@ def greedy_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
 TILE_ODDS = (15099495.0 / 16777216.0, 1677721.0 / 16777216.0)                                 # a 2-tile, a 4-tile (csrc/tfe_device.h: tfe_spawn_packed)
 
 
-def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: int, round: int) -> dict:
+def check_layers(layers) -> int:
+    """The search's depth in chance layers as an int: 1 or 2 (ValueError otherwise), as the library checks it."""
+    if isinstance(layers, bool) or layers not in (1, 2):
+        raise ValueError("layers must be 1 or 2")
+    return int(layers)
+
+
+def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: int, round: int, *, layers: int = 1) -> dict:
     """pulse_tfe_nt_search on the host, word for word.  For a candidate move a of board B (B_a != B) the chance boards of B_a are B_a
     with nibble k = 1, 2 at an empty cell c, slot s = 2 c + (k - 1); m = the best r + gamma * V over the candidate moves of a chance board
     (scanned in the order 0..3, a larger one replaces; 0.0 without a candidate); term_s = P_k * m, +0.0 at a filled cell; S = the pairwise
     tree over the 32 terms (x[0::2] + x[1::2], five times); E_a = S / n_empty(B_a); q_a = r_a + gamma * E_a, +0.0 for a move that is no
     candidate.  The action is greedy_nt_on_host's scan on these q.  Returns q float64[N, 4], action int64[N] (-1: no candidate),
     candidates uint8[N] (bit a), E float64[N, 4] (0.0 for a non-candidate), terms float64[N, 4, 32], and the moves themselves: after
-    uint64[N, 4], rewards int64[N, 4]."""
+    uint64[N, 4], rewards int64[N, 4].
+
+    layers = 2 (pulse_tfe_nt_search_deep): m of a chance board C is W2(C), the best over C's candidate moves
+    of the q this function gives board C at one layer (the same scan: the first candidate starts, a strictly larger q replaces it;
+    +0.0 without a candidate; no tie coins inside the tree); everything else is as above, and `terms` are these outer terms.  The
+    one-layer search runs once per distinct chance board.  ValueError for any other `layers`."""
+    layers = check_layers(layers)
     keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
     gamma = float(gamma)
     after, scores = moves_on_host(keys)
@@ -178,9 +192,14 @@ def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
     chance = (after[:, :, None] | (tile << shift))[live]
     terms = np.zeros(live.shape, dtype=np.float64)
     if len(chance):
-        after2, scores2 = moves_on_host(chance)
-        x = rewards_of_scores(scores2).astype(np.float64) + gamma * value_on_host(after2.reshape(-1), weights, tuples, symmetric).reshape(-1, 4)
-        cand2 = after2 != chance[:, None]
+        if layers == 2:
+            distinct, at = np.unique(chance, return_inverse=True)
+            inner = search_nt_on_host(distinct, weights, tuples, symmetric, gamma, tie_seed, round)
+            x, cand2 = inner["q"][at], (inner["after"] != distinct[:, None])[at]
+        else:
+            after2, scores2 = moves_on_host(chance)
+            x = rewards_of_scores(scores2).astype(np.float64) + gamma * value_on_host(after2.reshape(-1), weights, tuples, symmetric).reshape(-1, 4)
+            cand2 = after2 != chance[:, None]
         m, found = np.zeros(len(chance), dtype=np.float64), np.zeros(len(chance), dtype=bool)
         for a in range(4):
             take = cand2[:, a] & (~found | (x[:, a] > m))
@@ -537,46 +556,61 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         return o
 
     def _eval_launch(self, o):
-        self._launch(self._eval_entry, o)
+        self._launch(self._eval_entry, o, *self._eval_args)
 
-    # ------------------------------------------------------------------ expectimax search
-    _eval_entry = "pulse_tfe_nt_evaluate"
+    # ------------------------------------------------------------------ expectimax search (DESIGN.md sections 13.1 and 13.4)
+    _eval_entry, _eval_args = "pulse_tfe_nt_evaluate", ()
 
-    def _under_search(self, call, *args):
-        self._eval_entry = "pulse_tfe_nt_evaluate_search"
+    def _under_search(self, layers, call, *args):
+        """call(*args) with the evaluation's entry point set to the search's: at one layer pulse_tfe_nt_evaluate_search, at two
+        pulse_tfe_nt_evaluate_search_deep with the depth beside the struct."""
+        if check_layers(layers) == 1:
+            self._eval_entry = "pulse_tfe_nt_evaluate_search"
+        else:
+            self._eval_entry, self._eval_args = "pulse_tfe_nt_evaluate_search_deep", (layers,)
         try:
             return call(*args)
         finally:
-            del self._eval_entry
+            self.__dict__.pop("_eval_entry", None)
+            self.__dict__.pop("_eval_args", None)
 
-    def search_launch(self, boards, q, action, candidates):
-        """The launch of search() alone on device tensors: boards int64[N] (the keys' words), q float64[N, 4], action int8[N],
-        candidates uint8[N]."""
+    def _search_struct(self, boards, q, action, candidates):
         o = _native.TfeNtSearch()
         self._net(o.net)
         o.n_boards, o.gamma, o.tie_seed, o.round = boards.numel(), self.gamma, self.tie_seed, self.round
         o.boards, o.q, o.action, o.candidates = boards.data_ptr(), q.data_ptr(), action.data_ptr(), candidates.data_ptr()
-        return self._launch("pulse_tfe_nt_search", o)
+        return o
 
-    def search(self, keys) -> dict:
-        """One launch and one read-back: q float64[N, 4] of the packed boards `keys` under one chance layer of search, the greedy action
-        int8[N] (-1: the board is over) and the candidates uint8[N] (bit a: move a changes the board); search_nt_on_host on the device."""
+    def search_launch(self, boards, q, action, candidates, layers=1):
+        """The launch of search() alone on device tensors: boards int64[N] (the keys' words), q float64[N, 4], action int8[N],
+        candidates uint8[N].  layers = 1: pulse_tfe_nt_search; layers = 2: pulse_tfe_nt_search_deep (ValueError for any other)."""
+        layers = check_layers(layers)
+        o = self._search_struct(boards, q, action, candidates)
+        if layers == 1:
+            return self._launch("pulse_tfe_nt_search", o)
+        return self._launch("pulse_tfe_nt_search_deep", o, layers)
+
+    def search(self, keys, layers=1) -> dict:
+        """One launch and one read-back: q float64[N, 4] of the packed boards `keys` under `layers` chance layers of search (1 or 2), the
+        greedy action int8[N] (-1: the board is over) and the candidates uint8[N] (bit a: move a changes the board); search_nt_on_host
+        on the device."""
         import torch
+        layers = check_layers(layers)
         keys = np.array(keys, dtype=_U64).reshape(-1)                       # (a copy: torch takes no read-only array)
         boards = torch.from_numpy(keys.view(np.int64)).to(self.device)
         q = torch.zeros((len(keys), 4), dtype=torch.float64, device=self.device)
         action, candidates = torch.zeros(len(keys), dtype=torch.int8, device=self.device), torch.zeros(len(keys), dtype=torch.uint8, device=self.device)
-        self.search_launch(boards, q, action, candidates)
+        self.search_launch(boards, q, action, candidates, layers)
         return dict(q=q.cpu().numpy(), action=action.cpu().numpy(), candidates=candidates.cpu().numpy())
 
-    def evaluate_search_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False):
-        """evaluate_launch() under the search policy."""
-        return self._under_search(self.evaluate_launch, n_games, epsilon, board_id0, per_game)
+    def evaluate_search_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False, layers=1):
+        """evaluate_launch() under the search policy of `layers` chance layers (1 or 2)."""
+        return self._under_search(layers, self.evaluate_launch, n_games, epsilon, board_id0, per_game)
 
-    def evaluate_search(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False) -> dict:
-        """evaluate() under the search policy: the same default boards, so the two policies are paired on the spawns each game starts
-        from."""
-        return self._under_search(self.evaluate, n_games, epsilon, board_id0, per_game)
+    def evaluate_search(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False, layers=1) -> dict:
+        """evaluate() under the search policy of `layers` chance layers (1 or 2): the same default boards, so the policies are paired on
+        the spawns each game starts from."""
+        return self._under_search(layers, self.evaluate, n_games, epsilon, board_id0, per_game)
 
     # ------------------------------------------------------------------ read-back (the only syncs) and the checkpoint
     def weights(self) -> np.ndarray:

@@ -1,5 +1,5 @@
 // tfe_ntuple_device.h -- what the units of the 2048 n-tuple network share (tfe_ntuple.hip: the learner's four launches; tfe_ntuple_search.hip:
-// expectimax play; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes): the network as the
+// expectimax play, and tfe_ntuple_search_deep.hip, two chance layers of it; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes): the network as the
 // kernels take it, a feature's index, V of four afterstates at once, the learners' target, fixed-point difference and adds, their
 // parameters (Moves), shared refusals (check_moves), scatter kernel and launches, the four moves of a board, the greedy action, the game loop (play_game) with its parameters
 // (Games) and the host's checks of the network, of the accumulators and of a batch of games.  One copy each.  Not part of the ABI.

@@ -14,6 +14,7 @@
 #include "pulse_internal.h"
 #include "tfe_device.h"
 #include "tfe_ntuple_device.h"
+#include "tfe_ntuple_search_device.h"
 
 namespace {
 
@@ -21,11 +22,8 @@ using namespace pulse_tfe;
 using pulse::fail_named;
 using pulse::finish_launch;
 
-constexpr int kBlock = 256, kGroup = 32, kGroupsPerBlock = kBlock / kGroup;
+constexpr int kBlock = kSearchBlock;
 static_assert(sizeof(PulseTfeNtSearch) == 176, "struct layouts are part of the ABI");
-
-// the environment's tile odds (tfe_spawn_packed: the nibble is 2 iff r >> 8 > 15099494), exact doubles
-constexpr double kP1 = 15099495.0 / 16777216.0, kP2 = 1677721.0 / 16777216.0;
 
 // pulse_tfe_nt_search's struct as its kernel takes it
 struct Boards {
@@ -37,56 +35,6 @@ struct Boards {
     double* q; int8_t* action; uint8_t* candidates;
     const uint32_t* lut;
 };
-
-__device__ __forceinline__ int count_empty(const uint64_t key) {
-    return __popc(tfe_nz_nibbles((uint32_t)key) ^ 0x88888888u) + __popc(tfe_nz_nibbles((uint32_t)(key >> 32)) ^ 0x88888888u);
-}
-
-// The four q of board `key_b` (its moves ka / sc given), by the 32 lanes of its group together; s = this lane's slot.  Every lane of
-// the group must call it with the same board (the butterfly is among them), and every lane returns the same q.  A move that does
-// not change the board has q = +0.0.  The loop over the moves is kept rolled: one copy of the chance layer in the code.
-template <int IMG>
-__device__ __forceinline__ void search_q(const NtDev& net, const float* __restrict__ w, const uint32_t* __restrict__ lut, const double gamma,
-                                         const uint64_t key_b, const uint64_t (&ka)[4], const int (&sc)[4], const int s, double (&q)[4]) {
-#pragma unroll
-    for (int a = 0; a < 4; ++a) q[a] = 0.0;
-    const int cell4 = 4 * (s >> 1);
-    const uint64_t tile = (uint64_t)((s & 1) + 1) << cell4;
-    const double odds = (s & 1) ? kP2 : kP1;
-#pragma unroll 1
-    for (int a = 0; a < 4; ++a) {
-        uint64_t kb = ka[0];
-        int score = sc[0];
-#pragma unroll
-        for (int i = 1; i < 4; ++i) { kb = a == i ? ka[i] : kb; score = a == i ? sc[i] : score; }
-        const bool candidate = kb != key_b;                                             // (the same in the 32 lanes)
-        double term = 0.0;
-        if (candidate && ((kb >> cell4) & 15ull) == 0ull) {
-            const uint64_t chance = kb | tile;
-            uint64_t kc[4];
-            int scc[4];
-            moves4(chance, lut, kc, scc);
-            double v[4];
-            values4<IMG>(net, w, kc, v);
-            double m = 0.0;
-            bool any = false;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const double x = __dadd_rn((double)tfe_reward(scc[i]), __dmul_rn(gamma, v[i]));
-                const bool cand = kc[i] != chance;
-                m = cand && (!any || x > m) ? x : m;
-                any = any || cand;
-            }
-            term = __dmul_rn(odds, m);
-        }
-#pragma unroll
-        for (int d = 1; d < kGroup; d <<= 1) term = __dadd_rn(term, __shfl_xor(term, d, kGroup));
-        double qa = 0.0;
-        if (candidate) qa = __dadd_rn((double)tfe_reward(score), __dmul_rn(gamma, __ddiv_rn(term, (double)count_empty(kb))));
-#pragma unroll
-        for (int i = 0; i < 4; ++i) q[i] = a == i ? qa : q[i];
-    }
-}
 
 template <int IMG>
 __global__ __launch_bounds__(kBlock) void tfe_nt_search_kernel(const Boards o, const NtDev net) {
@@ -123,24 +71,30 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_search_games_kernel(const Games
 
 }  // namespace
 
-extern "C" int pulse_tfe_nt_search(const PulseTfeNtSearch* o, void* stream) {
-    const char* name = "pulse_tfe_nt_search";
-    if (!o) return fail_named(name, "options are null");
-    NtDev dev;
-    if (int rc = check_net(o->net, true, name, &dev)) return rc;
-    if (o->n_boards < 1) return fail_named(name, "n_boards must be positive");
-    if (!(o->gamma >= 0.0 && o->gamma <= 1.0)) return fail_named(name, "gamma must be in [0, 1]");
-    if (o->reserved0 != 0 || o->reserved1 != 0) return fail_named(name, "reserved0 / reserved1 must be 0 (zero-initialise the struct)");
-    if (!o->boards) return fail_named(name, "boards is null");
-    if (!o->q) return fail_named(name, "q is null");
-    if (!o->action) return fail_named(name, "action is null");
-    if (!o->candidates) return fail_named(name, "candidates is null");
-    if (((uintptr_t)o->boards & 7u) || ((uintptr_t)o->q & 7u)) return fail_named(name, "boards / q must be 8-byte aligned");
-    Boards b{o->net.weights, o->n_boards, o->gamma, o->tie_seed, o->round, o->boards, o->q, o->action, o->candidates, nullptr};
-    if (int rc = pulse::tfe_row_lut(&b.lut)) return rc;
-    const dim3 grid((unsigned)(((int64_t)o->n_boards + kGroupsPerBlock - 1) / kGroupsPerBlock)), block(kBlock);
-    if (o->net.symmetric) hipLaunchKernelGGL(tfe_nt_search_kernel<8>, grid, block, 0, (hipStream_t)stream, b, dev);
+// the launches (tfe_ntuple_search_device.h): pulse_tfe_nt_search_deep and pulse_tfe_nt_evaluate_search_deep take them at one layer
+namespace pulse_tfe {
+
+void launch_search(const PulseTfeNtSearch& o, const NtDev& dev, const uint32_t* lut, void* stream) {
+    const Boards b{o.net.weights, o.n_boards, o.gamma, o.tie_seed, o.round, o.boards, o.q, o.action, o.candidates, lut};
+    const dim3 grid((unsigned)(((int64_t)o.n_boards + kGroupsPerBlock - 1) / kGroupsPerBlock)), block(kBlock);
+    if (o.net.symmetric) hipLaunchKernelGGL(tfe_nt_search_kernel<8>, grid, block, 0, (hipStream_t)stream, b, dev);
     else hipLaunchKernelGGL(tfe_nt_search_kernel<1>, grid, block, 0, (hipStream_t)stream, b, dev);
+}
+
+void launch_search_games(const Games& g, const NtDev& dev, const bool symmetric, void* stream) {
+    const dim3 grid((unsigned)(((int64_t)g.n_games + kGroupsPerBlock - 1) / kGroupsPerBlock)), block(kBlock);
+    if (symmetric) hipLaunchKernelGGL(tfe_nt_search_games_kernel<8>, grid, block, 0, (hipStream_t)stream, g, dev);
+    else hipLaunchKernelGGL(tfe_nt_search_games_kernel<1>, grid, block, 0, (hipStream_t)stream, g, dev);
+}
+
+}  // namespace pulse_tfe
+
+extern "C" int pulse_tfe_nt_search(const PulseTfeNtSearch* o, void* stream) {
+    NtDev dev;
+    const uint32_t* lut = nullptr;
+    if (int rc = check_search(o, "pulse_tfe_nt_search", &dev)) return rc;
+    if (int rc = pulse::tfe_row_lut(&lut)) return rc;
+    launch_search(*o, dev, lut, stream);
     return finish_launch("pulse_tfe_nt_search launch");
 }
 
@@ -149,8 +103,6 @@ extern "C" int pulse_tfe_nt_evaluate_search(const PulseTfeNtEval* o, void* strea
     Games g;
     if (int rc = check_eval(o, "pulse_tfe_nt_evaluate_search", &dev, &g)) return rc;
     if (int rc = pulse::tfe_row_lut(&g.lut)) return rc;
-    const dim3 grid((unsigned)(((int64_t)g.n_games + kGroupsPerBlock - 1) / kGroupsPerBlock)), block(kBlock);
-    if (o->net.symmetric) hipLaunchKernelGGL(tfe_nt_search_games_kernel<8>, grid, block, 0, (hipStream_t)stream, g, dev);
-    else hipLaunchKernelGGL(tfe_nt_search_games_kernel<1>, grid, block, 0, (hipStream_t)stream, g, dev);
+    launch_search_games(g, dev, o->net.symmetric != 0, stream);
     return finish_launch("pulse_tfe_nt_evaluate_search launch");
 }

@@ -6,7 +6,7 @@ prints, from ONE evaluation launch of `--eval-games` games under the greedy poli
 score and its standard error, the mean length and the histogram of the largest tile.  `--save PATH` writes the non-zero weights and
 the run's state at the end, `--resume PATH` continues such a run for `--rounds` more rounds.  `--search`: every evaluation also runs
 under expectimax search one chance layer deep (section 13.1) on the same boards, and both means are printed; `--resume PATH --rounds 0
---search` plays a saved network.  `--lambda L` (0 < L <= 1) learns by TD(lambda) (section 13.2): the learn launch walks every game
+--search` plays a saved network; `--search --layers 2` searches two chance layers deep (section 13.4).  `--lambda L` (0 < L <= 1) learns by TD(lambda) (section 13.2): the learn launch walks every game
 backwards first and adds lambda-differences; the run's first line names it, and `--resume` takes it from the file.  `--tc` learns with temporal-coherence
 step sizes (section 13.3): every weight moves by rho = |E| / A of the step, from the running sums of its errors; the round's mean rho
 is printed beside the round's counters, and `--resume` takes `tc` from the file too."""
@@ -21,7 +21,7 @@ from ..agents import NTupleTDAfterstateTFEGPU
 
 
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
-        resume=None, out=print, search=False, lam=0.0, tc=False):
+        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1):
     if resume:
         agent = NTupleTDAfterstateTFEGPU.load(resume, device)
         want = dict(n_games=tables, alpha=float(alpha), epsilon=float(epsilon), gamma=float(gamma), max_steps=max_steps, seed=seed)
@@ -37,8 +37,8 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
     def under_search():
         if not search:
             return ""
-        e = agent.evaluate_search(n_games=eval_games)
-        return (f"; under search: Avg final score: {e['mean_score']:.1f} +- {e['std_score'] / e['games'] ** .5:.1f}, Highest: {e['max_score']}, "
+        e = agent.evaluate_search(n_games=eval_games, layers=layers)
+        return (f"; under search{'' if layers == 1 else f' of {layers} chance layers'}: Avg final score: {e['mean_score']:.1f} +- {e['std_score'] / e['games'] ** .5:.1f}, Highest: {e['max_score']}, "
                 f"Avg length: {e['mean_length']:.1f}, cut {e['truncated']}, largest tile 2^k: {e['max_tile_hist']}")
 
     def evaluation():
@@ -80,9 +80,10 @@ def main(argv=None):
     ap.add_argument("--save", metavar="PATH", help="write the non-zero weights and the run's state to this .npz at the end")
     ap.add_argument("--resume", metavar="PATH", help="continue the run saved there (the same --tables, --alpha, --epsilon, --gamma, --max-steps, --seed)")
     ap.add_argument("--search", action="store_true", help="every evaluation also under expectimax search, one chance layer deep")
+    ap.add_argument("--layers", type=int, default=1, choices=[1, 2], help="with --search: the chance layers the search looks ahead")
     args = ap.parse_args(argv)
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
-                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc)
+                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers)
     st = agent.stats()
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
           f"{int((agent.weights_dev != 0).sum().item())} of {agent.n_weights} weights are not zero")

@@ -12,7 +12,11 @@ times after one untimed call.  --search: per B and per --search-games G (1,024: 
 line, {"search": ...}: G games on the weights the rounds left
 from the default evaluation boards under the one-ply policy and under expectimax search one chance layer deep (DESIGN.md section
 13.1), each launch between its own HIP events in the same process, --repeats times after one untimed call: seconds, moves, seconds
-per move (a move = one move of one game; the launch's time over all the moves it played) and the ratio of the two.  --lambda L: per B one more line, {"lambda": ...}: on the games of the last timed round, in the same
+per move (a move = one move of one game; the launch's time over all the moves it played) and the ratio of the two.  --search --layers 2:
+the line also holds "search2", the evaluation under search two chance layers deep (section 13.4) on the same boards, its per-move time
+over the one-layer search's, and the yardstick of that ratio: the mean number of child searches a two-layer move makes, counted on the
+host from the candidate and empty-cell masks of the boards of 32 games played under that policy (children_per_move); the ratio over
+the count, and whether it is within the count + 50 %.  --lambda L: per B one more line, {"lambda": ...}: on the games of the last timed round, in the same
 process and back to back, the TD(0) learn launch (pulse_tfe_nt_learn) and the TD(lambda) launch (pulse_tfe_nt_learn_lambda: the backward
 walk and the adds) each between its own pair of HIP events, --warmup untimed pairs and then --repeats timed ones, alternating; the
 accumulators are zeroed, untimed, before every launch, so both add the same moves into empty cells.  --tc: per B one more line, marked {"tc": true}: on the games of the last timed round, in the same process and alternating, the fixed-step pair
@@ -59,10 +63,40 @@ def _timed_evaluate(agent, torch):
     return ev[0].elapsed_time(ev[1]) * 1e-3, agent.eval_counters()
 
 
-def search_line(agent, torch, games, repeats):
-    """the evaluation launch under both policies on the same weights and boards"""
+def children_per_move(agent, torch, sample, max_moves):
+    """The mean number of one-layer searches a two-layer move makes: `sample` games from the default evaluation boards played through
+    the environment's own launches under the two-layer policy (agent.search(layers=2), greedy), and on every board met, counted on the
+    host from the moves' masks, the live children: 2 * n_empty(B_a) summed over the candidate moves a.  Stops after max_moves moves."""
+    import numpy as np
+    from pulselib_amd.agents.tfe_ntuple_td_gpu import moves_on_host
+    from pulselib_amd.environments.TFE.TFE import TFEBatch
+    env = TFEBatch(agent.device, sample, 4, seed=agent.env_seed, board_id0=agent.eval_board_id0())
+    boards, _ = env.reset()
+    live, children, moves = np.ones(sample, dtype=bool), 0, 0
+    shifts = np.uint64(4) * np.arange(16, dtype=np.uint64)
+    for _ in range(max_moves):
+        cells = boards.cpu().numpy().reshape(sample, 16).astype(np.int64)
+        logs = np.where(cells > 0, np.log2(np.maximum(cells, 1)).round().astype(np.int64), 0).astype(np.uint64)
+        keys = (logs << shifts).sum(axis=1, dtype=np.uint64)
+        after, _ = moves_on_host(keys)
+        n_empty = (((after[:, :, None] >> shifts) & np.uint64(15)) == 0).sum(axis=2)
+        per_board = (2 * n_empty * (after != keys[:, None])).sum(axis=1)
+        children, moves = children + int(per_board[live].sum()), moves + int(live.sum())
+        action = agent.search(keys, layers=2)["action"].astype(np.int64)
+        boards, _, dones, _, _ = env.step(torch.from_numpy(np.maximum(action, 0)))
+        live &= ~dones.cpu().numpy() & (action >= 0)
+        if not live.any():
+            break
+    return {"sample_games": sample, "sample_moves": moves, "children_per_move": children / max(moves, 1)}
+
+
+def search_line(agent, torch, games, repeats, layers=1):
+    """the evaluation launch under the policies on the same weights and boards; layers = 2 adds the two-layer search and its yardstick"""
     out = {}
-    for name, launch in (("one_ply", agent.evaluate_launch), ("search", agent.evaluate_search_launch)):
+    policies = [("one_ply", agent.evaluate_launch), ("search", agent.evaluate_search_launch)]
+    if layers == 2:
+        policies.append(("search2", lambda n: agent.evaluate_search_launch(n, layers=2)))
+    for name, launch in policies:
         agent.eval_counters(clear=True)
         launch(games)                                                       # untimed: the kernel's code object
         torch.cuda.synchronize()
@@ -78,9 +112,15 @@ def search_line(agent, torch, games, repeats):
         e, s = agent.eval_counters(), _spread(seconds)
         out[name] = {"seconds": s, "moves": e["moves"], "seconds_per_move": s["median"] / e["moves"], "mean_score": e["mean_score"],
                      "std_score": e["std_score"], "mean_length": e["mean_length"], "truncated": e["truncated"]}
-    return {"search": {"games": games, "trained_rounds": agent.round, "train_games": agent.n_games, "max_steps": agent.max_steps, "repeats": repeats, **out,
-                       "seconds_per_move_ratio": out["search"]["seconds_per_move"] / out["one_ply"]["seconds_per_move"],
-                       "seconds_ratio": out["search"]["seconds"]["median"] / out["one_ply"]["seconds"]["median"]}}
+    line = {"games": games, "trained_rounds": agent.round, "train_games": agent.n_games, "max_steps": agent.max_steps, "repeats": repeats, **out,
+            "seconds_per_move_ratio": out["search"]["seconds_per_move"] / out["one_ply"]["seconds_per_move"],
+            "seconds_ratio": out["search"]["seconds"]["median"] / out["one_ply"]["seconds"]["median"]}
+    if layers == 2:
+        count = children_per_move(agent, torch, 32, agent.max_steps)
+        ratio = out["search2"]["seconds_per_move"] / out["search"]["seconds_per_move"]
+        line.update(layers=2, **count, search2_per_move_ratio=ratio, search2_over_yardstick=ratio / count["children_per_move"],
+                    search2_within_margin=ratio <= 1.5 * count["children_per_move"])
+    return {"search": line}
 
 
 def lambda_line(agent, torch, lam, warmup, repeats):
@@ -187,6 +227,7 @@ def main(argv=None):
     ap.add_argument("--max-steps", type=int, default=4096)
     ap.add_argument("--search", action="store_true", help="one more line per B: the evaluation under search beside the one-ply one")
     ap.add_argument("--search-games", type=int, nargs="+", default=[1024, 65536])
+    ap.add_argument("--layers", type=int, default=1, choices=[1, 2], help="with --search, 2: the two-layer evaluation and its child count beside the other two")
     ap.add_argument("--lambda", dest="lam", type=float, help="one more line per B: the TD(lambda) learn launch beside the TD(0) one, on the same games")
     ap.add_argument("--tc", action="store_true", help="one more line per B: the temporal-coherence learn and apply launches beside the fixed-step ones")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
@@ -207,7 +248,7 @@ def main(argv=None):
             agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=args.max_steps, seed=0)
             lines = [state_line(agent, torch, s, args.trained_rounds, args.warmup, args.repeats) for s in args.states]
             if args.search:                                                 # on the weights the last state left
-                lines += [search_line(agent, torch, g, args.repeats) for g in args.search_games]
+                lines += [search_line(agent, torch, g, args.repeats, args.layers) for g in args.search_games]
             if args.lam is not None:                                        # on the games the last timed round recorded
                 lines.append(lambda_line(agent, torch, args.lam, args.warmup, args.repeats))
             if args.tc:                                                     # likewise
