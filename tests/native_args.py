@@ -2,6 +2,7 @@
 its refusals.  Nothing here launches a kernel: every case fails its check first.  And the compiler's resource remarks of a unit's
 kernels.  A helper, not a test."""
 import ctypes as C
+import functools
 import re
 import subprocess
 from pathlib import Path
@@ -46,15 +47,22 @@ def nt_opts(struct, defaults, **kw):
     return o
 
 
-def resource_usage(target):
-    """(names, vgprs, scratch, spills), one entry per kernel: the compiler's resource remarks of `make <target>` in csrc (one of its
-    *-resource-usage targets), printed as name -> VGPRs"""
+@functools.lru_cache(maxsize=None)
+def remarks(target):
+    """the compiler's resource remarks of `make <target>` in csrc (one of its *-resource-usage targets), as it printed them; one
+    compiler run per target and session"""
     run = subprocess.run(["make", "-s", "-C", str(CSRC), target], capture_output=True, text=True)
     assert run.returncode == 0, run.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", run.stderr)
-    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", run.stderr)]
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", run.stderr)]
-    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", run.stderr)]
+    return run.stderr
+
+
+def resource_usage(target):
+    """(names, vgprs, scratch, spills), one entry per kernel of remarks(target), printed as name -> VGPRs"""
+    text = remarks(target)
+    names = re.findall(r"Function Name: (\S+)", text)
+    vgprs = [int(x) for x in re.findall(r" VGPRs: (\d+)", text)]
+    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", text)]
+    spills = [int(x) for x in re.findall(r"VGPRs Spill: (\d+)", text)]
     print(dict(zip(names, vgprs)))
     return names, vgprs, scratch, spills
 

@@ -2,26 +2,21 @@
 the features, the value, the learner and the apply launch (pulselib_amd/agents/tfe_ntuple_td_gpu.py), that the host mirror learns, the
 checkpoint file, and what the compiler made of the kernels."""
 import ctypes as C
-import math
 import re
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from tests.native_args import PTR, assert_refusals, nt_opts, resource_usage
+from tests.native_args import assert_refusals
+from tests.tfe_nt_support import CASES, assert_exports, assert_no_scratch, opts, worked_games
 
-ROOT = Path(__file__).resolve().parent.parent
 NAMES = ("pulse_tfe_nt_rollout", "pulse_tfe_nt_learn", "pulse_tfe_nt_apply", "pulse_tfe_nt_evaluate")
+STRUCTS = dict(zip(NAMES, ("TfeNtRollout", "TfeNtLearn", "TfeNtApply", "TfeNtEval")))
 
 
 def test_library_exports_the_four_entry_points():
     from pulselib_amd import _native
-    lib = _native.lib()
-    text = (ROOT / "include" / "pulse_env.h").read_text()
-    for name, struct in zip(NAMES, ("PulseTfeNtRollout", "PulseTfeNtLearn", "PulseTfeNtApply", "PulseTfeNtEval")):
-        assert hasattr(lib, name) and _native.SYMBOLS[name] == (C.c_int, [C.c_void_p, C.c_void_p])
-        assert re.search(r"int %s\(const %s\* o, void\* stream\);" % (name, struct), text), name
+    _, text = assert_exports([(name, "Pulse" + STRUCTS[name]) for name in NAMES], [C.c_void_p, C.c_void_p], r"int %s\(const %s\* o, void\* stream\);")
     assert [C.sizeof(s) for s in (_native.TfeNtNet, _native.TfeNtRollout, _native.TfeNtLearn, _native.TfeNtApply, _native.TfeNtEval)] == \
         [104, 232, 176, 128, 208]                                          # the static_assert of csrc/tfe_ntuple.hip
     for macro, value in (("MAX_TUPLES", 8), ("MAX_LEN", 6), ("FRAC_BITS", 16)):
@@ -30,61 +25,16 @@ def test_library_exports_the_four_entry_points():
 
 
 # ------------------------------------------------------------------ PULSE_EINVAL before anything is launched
-def _opts(name, **kw):
-    """A struct every check passes, then `kw` over it (native_args.nt_opts' keywords)."""
-    from pulselib_amd import _native
-    struct = dict(zip(NAMES, (_native.TfeNtRollout, _native.TfeNtLearn, _native.TfeNtApply, _native.TfeNtEval)))[name]
-    fields = {f[0] for f in struct._fields_}
-    base = dict(tuples=[[0, 1, 2, 3], [4, 5, 6, 8, 9, 10]], net_n=4, net_symmetric=1, net_weights=PTR)
-    base.update((f, PTR) for f in ("keys", "values", "steps", "lengths", "total_score", "episode_reward", "stats", "acc", "summary", "max_tile_hist")
-                if f in fields)
-    base.update((f, v) for f, v in (("n_games", 64), ("max_steps", 32), ("gamma", 1.0), ("epsilon", 0.25), ("step", 1.0 / 16)) if f in fields)
-    return nt_opts(struct, base, **kw)
-
-
-NET_CASES = [(dict(net_n=3), b"board side n must be 4"), (dict(net_n=5), b"board side n must be 4"),
-             (dict(tuples=[], net_n_weights=0), b"n_tuples must be in 1..8"), (dict(net_n_tuples=9), b"n_tuples must be in 1..8"),
-             (dict(net_len1=0), b"length must be in 1..6"), (dict(net_len1=7), b"length must be in 1..6"),
-             (dict(tuples=[[0, 1, 2, 16]]), b"cell must be in 0..15"), (dict(tuples=[[0, 1, 2, 3], [4, 5, 4]]), b"repeated within a tuple"),
-             (dict(net_n_weights=16 ** 4 + 16 ** 6 - 1), b"n_weights must be the sum of 16^len"), (dict(net_n_weights=0), b"n_weights must be the sum"),
-             (dict(net_symmetric=2), b"symmetric must be 0 or 1"), (dict(net_symmetric=-1), b"symmetric must be 0 or 1"),
-             (dict(net_reserved0=1), b"net.reserved0 must be 0")]
-WEIGHTS = [(dict(net_weights=None), b"weights is null"), (dict(net_weights=2), b"weights must be 4-byte aligned")]
-BATCH = [(dict(n_games=0), b"n_games must be positive"), (dict(max_steps=0), b"max_steps must be in 1..65535"),
-         (dict(max_steps=65536), b"max_steps must be in 1..65535"), (dict(gamma=-0.01), b"gamma must be in [0, 1]"),
-         (dict(gamma=1.01), b"gamma must be in [0, 1]"), (dict(gamma=math.nan), b"gamma must be in [0, 1]"), (dict(reserved0=1), b"reserved0 must be 0")]
-EPSILON = [(dict(epsilon=-0.01), b"epsilon must be in [0, 1]"), (dict(epsilon=1.01), b"epsilon must be in [0, 1]"),
-           (dict(epsilon=math.nan), b"epsilon must be in [0, 1]")]
-
-
-def _null_and_odd(fields8, fields4=()):
-    return [(dict([(f, None)]), f.encode() + b" is null") for f in fields8 + fields4] + \
-        [(dict([(f, 4)]), b"8-byte aligned") for f in fields8] + [(dict([(f, 2)]), b"4-byte aligned") for f in fields4]
-
-
-CASES = {
-    "pulse_tfe_nt_rollout": NET_CASES + WEIGHTS + BATCH + EPSILON + _null_and_odd(("keys", "values", "total_score", "stats"), ("lengths", "episode_reward"))
-    + [(dict(steps=None), b"steps is null")],
-    "pulse_tfe_nt_learn": NET_CASES + BATCH + _null_and_odd(("keys", "values", "stats"), ("lengths",))
-    + [(dict(steps=None), b"steps is null"), (dict(acc=None), b"acc is null"), (dict(acc=8), b"acc must be 16-byte aligned")],
-    "pulse_tfe_nt_apply": NET_CASES + WEIGHTS + [(dict(step=0.0), b"step must be in (0, 1]"), (dict(step=1.01), b"step must be in (0, 1]"),
-                                                 (dict(step=math.nan), b"step must be in (0, 1]"), (dict(step=-0.5), b"step must be in (0, 1]"),
-                                                 (dict(acc=None), b"acc is null"), (dict(acc=8), b"acc must be 16-byte aligned"),
-                                                 (dict(reserved0=1), b"reserved0 must be 0")],
-    "pulse_tfe_nt_evaluate": NET_CASES + WEIGHTS + BATCH + EPSILON + _null_and_odd(("summary", "max_tile_hist"))
-    + [(dict(total_score=4), b"total_score must be 8-byte aligned"), (dict(lengths=2), b"lengths must be 4-byte aligned")],
-}
-
-
 @pytest.mark.parametrize("name", NAMES)
 def test_argument_checks_without_gpu(name):
     """every refusal comes back as PULSE_EINVAL with its message under the entry point's name; a refusal returns before the row table
     is asked for or anything is launched (there is no device here to ask)"""
     from pulselib_amd import _native
     lib = _native.lib()
-    assert_refusals(lib, name, lambda **kw: _opts(name, **kw), CASES[name])
+    struct = getattr(_native, STRUCTS[name])
+    assert_refusals(lib, name, lambda **kw: opts(struct, **kw), CASES[name])
     if name == "pulse_tfe_nt_learn":                                       # the learner reads no weight
-        o = _opts(name, net_weights=None, n_games=0)
+        o = opts(struct, net_weights=None, n_games=0)
         assert getattr(lib, name)(C.byref(o), None) == -1 and b"n_games must be positive" in lib.pulse_last_error()
 
 
@@ -175,11 +125,10 @@ def test_learn_and_apply_on_a_hand_worked_case():
     tuples, X = ((0, 3),), 0x1
     assert nt.feature_cells_on_host(tuples, True)[0].tolist() == [[0, 3], [3, 15], [15, 12], [12, 0], [0, 12], [12, 15], [15, 3], [3, 0]]
     assert nt.feature_indices_on_host([X], tuples, True)[0].tolist() == [1, 0, 0, 16, 1, 0, 0, 16]
-    keys = np.full((3, 2), X, dtype=np.uint64)
-    values = np.array([[10.0, 1.5], [20000.0, 7.0], [2.0, -99.0]])
-    steps = np.array([[0 | 0 << 2, 1 | 2 << 2], [2 | 1 << 2, 3 | 2 << 2], [1 | 3 << 2 | 0x80, 0xEE]], dtype=np.uint8)
+    keys, values, steps, lengths = worked_games()
+    assert (keys == X).all() and lengths == [3, 2]
     acc = np.zeros((256, 2), dtype=np.int64)
-    st = nt.learn_nt_on_host(keys, values, steps, [3, 2], tuples, True, 1.0, acc)
+    st = nt.learn_nt_on_host(keys, values, steps, lengths, tuples, True, 1.0, acc)
     assert st == dict(learnt=4, skipped=1, clamped=2)
     total = 8192 * 65536 - 8192 * 65536 - 131072 + 491520
     want = np.zeros((256, 2), dtype=np.int64)
@@ -281,7 +230,4 @@ def test_checkpoint_round_trip(tmp_path):
 def test_kernels_use_no_scratch():
     """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple.hip with the Makefile's flags: nine kernels, none with scratch or a spilled vector
     register.  VGPRs as built: games 118 (symmetric) / 63, scatter 59 / 18 (both learners'), apply 22."""
-    names, vgprs, scratch, spills = resource_usage("ntuple-resource-usage")
-    assert len(names) == 9 and sum("tfe_nt_games_kernel" in n for n in names) == 4 and sum("tfe_nt_scatter_kernel" in n for n in names) == 4
-    assert sum("tfe_nt_apply_kernel" in n for n in names) == 1
-    assert scratch == [0] * 9 and spills == [0] * 9 and len(vgprs) == 9 and max(vgprs) <= 128
+    assert_no_scratch("ntuple-resource-usage", {"tfe_nt_games_kernel": 4, "tfe_nt_scatter_kernel": 4, "tfe_nt_apply_kernel": 1}, 128)

@@ -14,25 +14,11 @@ import functools
 import numpy as np
 import pytest
 
-from tests.tfe_gpu_support import PATTERNS, assert_rollout, guard, guards_intact, replay, rollout
+from tests.tfe_gpu_support import assert_rollout, guards_intact, replay, rollout
+from tests.tfe_nt_support import EPSILON_PLAY as EPSILON
+from tests.tfe_nt_support import GAMES, MAX_STEPS, PER_MOVE, ROUNDS, learner_agent, learner_round
 
 pytestmark = pytest.mark.gpu
-
-GAMES, MAX_STEPS, ROUNDS, EPSILON = 257, 256, 3, .25
-TUPLES = ((0, 1, 2, 3), (4, 5, 6, 8, 9, 10))
-SEED, BOARD_ID0 = 457, 3000
-BUFFERS = ("weights_dev", "acc", "keys", "values", "steps", "lengths", "total_score", "episode_reward", "counters", "_eval")
-PER_MOVE = ("keys", "values", "steps")
-
-
-def _agent(n_games=GAMES, **kw):
-    """The agent with every device buffer re-seated between guard words; keys / values / steps pre-filled with a pattern."""
-    import torch
-    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
-    kw = dict(dict(tuples=TUPLES, epsilon=EPSILON, max_steps=MAX_STEPS, seed=SEED, board_id0=BOARD_ID0), **kw)
-    a = guard(NTupleTDAfterstateTFEGPU(torch.device("cuda:0"), n_games, **kw), BUFFERS, **PATTERNS)
-    assert a.acc.data_ptr() % 16 == 0
-    return a
 
 
 def _host_rollout(a, weights, **kw):
@@ -43,33 +29,22 @@ def _host_rollout(a, weights, **kw):
 
 
 def _play_rounds(symmetric, rounds):
-    """`rounds` rounds on the device and on the host: (the agent after them, per round a record).  The big arrays are compared here,
-    where they are, and the records keep the verdicts and the counts."""
-    from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-    a = _agent(symmetric=symmetric)
-    out, moves, learnt, skipped = [], 0, 0, 0
+    """`rounds` rounds on the device and on the host: (the agent after them, per round learner_round's record with this file's own:
+    the roll-out held to the host's, the counters since the first round, and what the apply launch changed)."""
+    a = learner_agent(symmetric=symmetric)
+    out, total = [], dict(moves=0, learnt=0, skipped=0)
+
+    def after_learn(a, h):
+        total.update(moves=total["moves"] + int(h.L.sum()), learnt=total["learnt"] + h.host["learnt"], skipped=total["skipped"] + h.host["skipped"])
+        return dict(total, got=h.got, want=_host_rollout(a, h.policy), acc_cells=int(h.visited.sum()), acc_max_cnt=int(h.acc[:, 1].max()),
+                    stats_learn=a.stats(), board_id0=a.round_board_id0())
+
+    def after_apply(a, h):
+        untouched = ~h.visited
+        return dict(untouched_kept=np.array_equal(h.weights.view(np.uint32)[untouched], h.policy.view(np.uint32)[untouched]),
+                    weights_changed=int((h.weights.view(np.uint32) != h.policy.view(np.uint32)).sum()), max_index=int(np.flatnonzero(~untouched).max()))
     for _ in range(rounds):
-        policy = a.weights()
-        want = _host_rollout(a, policy)
-        got = rollout(a, PER_MOVE)
-        a.learn()
-        acc = a.acc.cpu().numpy()
-        host_acc = np.zeros_like(acc)
-        st = nt.learn_nt_on_host(got["keys"], got["values"].view(np.float64), got["steps"], got["lengths"], a.tuples, a.symmetric, a.gamma, host_acc)
-        moves, learnt, skipped = moves + int(got["lengths"].sum()), learnt + st["learnt"], skipped + st["skipped"]
-        rec = dict(got=got, want=want, acc_equal=np.array_equal(acc, host_acc), acc_cells=int((acc[:, 1] > 0).sum()), acc_adds=int(acc[:, 1].sum()),
-                   acc_max_cnt=int(acc[:, 1].max()), host=st, stats_learn=a.stats(), moves=moves, learnt=learnt, skipped=skipped,
-                   board_id0=a.round_board_id0())
-        a.apply()
-        weights = a.weights()
-        host_w = policy.copy()
-        rec["moved"] = nt.apply_nt_on_host(host_w, host_acc, a.alpha / a.n_features)
-        untouched = acc[:, 1] == 0
-        rec.update(weights_equal=np.array_equal(weights.view(np.uint32), host_w.view(np.uint32)), acc_zero=not bool(a.acc.any().item()),
-                   untouched_kept=np.array_equal(weights.view(np.uint32)[untouched], policy.view(np.uint32)[untouched]),
-                   weights_changed=int((weights.view(np.uint32) != policy.view(np.uint32)).sum()), max_index=int(np.flatnonzero(~untouched).max()))
-        out.append(rec)
-        a.round += 1
+        out.append(learner_round(a, after_learn, after_apply))
     guards_intact(a)
     return a, out
 

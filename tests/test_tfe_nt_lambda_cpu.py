@@ -5,35 +5,21 @@ return, the checkpoint's two versions, and what the compiler made of the kernels
 import ctypes as C
 import math
 import re
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from tests.native_args import PTR, assert_refusals, nt_opts, resource_usage
-from tests.test_tfe_nt_cpu import BATCH, NET_CASES, _null_and_odd
+from tests.native_args import assert_refusals
+from tests.tfe_nt_support import BATCH, CASES, NET_CASES, ROOT, assert_exports, assert_no_scratch, bits, opts, worked_games
+from tests.tfe_nt_support import nt as _nt
 
-ROOT = Path(__file__).resolve().parent.parent
 NAME = "pulse_tfe_nt_learn_lambda"
-TUPLES = ((0, 1, 2, 3), (4, 5, 6, 8, 9, 10))
-
-
-def _nt():
-    from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-    return nt
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
 
 
 # ------------------------------------------------------------------ C1: the export
 def test_library_exports_the_entry_point():
     from pulselib_amd import _native
-    lib = _native.lib()
-    text = (ROOT / "include" / "pulse_env.h").read_text()
-    assert hasattr(lib, NAME) and _native.SYMBOLS[NAME] == (C.c_int, [C.c_void_p, C.c_void_p])
-    assert re.search(r"int %s\(const PulseTfeNtLearnLambda\* o, void\* stream\);" % NAME, text)
+    _, text = assert_exports([(NAME, "PulseTfeNtLearnLambda")], [C.c_void_p, C.c_void_p], r"int %s\(const %s\* o, void\* stream\);")
     assert re.search(r"typedef struct PulseTfeNtLearnLambda \{", text) and re.search(r"double gamma, lambda;", text)
     s = _native.TfeNtLearnLambda
     assert C.sizeof(s) == 192
@@ -45,29 +31,17 @@ def test_library_exports_the_entry_point():
 
 
 # ------------------------------------------------------------------ C2: PULSE_EINVAL before anything is launched
-def _opts(**kw):
-    """a PulseTfeNtLearnLambda every check passes, then `kw` over it (native_args.nt_opts' keywords)"""
-    from pulselib_amd import _native
-    return nt_opts(_native.TfeNtLearnLambda, dict(tuples=[list(t) for t in TUPLES], net_n=4, net_symmetric=1, net_weights=PTR, n_games=64, max_steps=32,
-                                                  gamma=1.0, lam=0.5, keys=PTR, values=PTR, steps=PTR, lengths=PTR, deltas=PTR, acc=PTR, stats=PTR), **kw)
-
-
-LAMBDA = [(dict(lam=-0.01), b"lambda must be in [0, 1]"), (dict(lam=1.01), b"lambda must be in [0, 1]"), (dict(lam=math.nan), b"lambda must be in [0, 1]")]
-CASES = NET_CASES + BATCH + LAMBDA + _null_and_odd(("keys", "values", "deltas", "stats"), ("lengths",)) + [
-    (dict(steps=None), b"steps is null"), (dict(acc=None), b"acc is null"), (dict(acc=8), b"acc must be 16-byte aligned")]
-
-
 def test_argument_checks_without_gpu():
     """every refusal of pulse_tfe_nt_learn and the three of its own (lambda, deltas null, deltas misaligned), under its own name,
     before anything is launched (there is no device here to launch on)"""
     from pulselib_amd import _native
-    lib = _native.lib()
-    errors = assert_refusals(lib, NAME, _opts, CASES)
+    lib, make = _native.lib(), lambda **kw: opts(_native.TfeNtLearnLambda, **kw)
+    errors = assert_refusals(lib, NAME, make, CASES[NAME])
     assert len(errors) == len(NET_CASES) + len(BATCH) + 3 + 5 + 4 + 1 + 3
-    o = _opts(net_weights=None, n_games=0)                                 # the learner reads no weight
+    o = make(net_weights=None, n_games=0)                                  # the learner reads no weight
     assert getattr(lib, NAME)(C.byref(o), None) == -1 and b"n_games must be positive" in lib.pulse_last_error()
     for lam in (0.0, 1.0):                                                 # the ends of the interval are inside: the next check refuses
-        assert getattr(lib, NAME)(C.byref(_opts(lam=lam, keys=None)), None) == -1 and b"keys is null" in lib.pulse_last_error()
+        assert getattr(lib, NAME)(C.byref(make(lam=lam, keys=None)), None) == -1 and b"keys is null" in lib.pulse_last_error()
 
 
 def test_python_layer_refuses():
@@ -87,35 +61,26 @@ def test_python_layer_refuses():
 
 
 # ------------------------------------------------------------------ C3: the hand-worked case
-def _worked():
-    """test_tfe_nt_cpu's games: tuple (0, 3), board X = 0x1 in all five moves.  Game 0 ends at t = 2 (values 10, 20000, 2; rewards
-    0, 1, 3); game 1 is cut at length 2 (values 1.5, 7; rewards 2, 2)."""
-    keys = np.full((3, 2), 0x1, dtype=np.uint64)
-    values = np.array([[10.0, 1.5], [20000.0, 7.0], [2.0, -99.0]])
-    steps = np.array([[0 | 0 << 2, 1 | 2 << 2], [2 | 1 << 2, 3 | 2 << 2], [1 | 3 << 2 | 0x80, 0xEE]], dtype=np.uint8)
-    return keys, values, steps, [3, 2]
-
-
 def test_a_hand_worked_case():
     """gamma 1, lambda .5.  Game 0: D_2 = 0 - 2 = -2; D_1 = (3 + 2 - 20000) + .5 * (-2) = -19,996, which its add clamps to -8,192;
     D_0 = (1 + 20000 - 10) + .5 * (-19,996) = 9,993 -- from the UNCLAMPED D_1 (the clamped one would give 15,895) -- which clamps to
     8,192.  Game 1: its last move is skipped, D_1 = +0.0; D_0 = (2 + 7 - 1.5) + .5 * 0 = 7.5.  Every move records board X: index 0 gets
     4 adds per learnt move, 1 and 16 two each."""
     nt = _nt()
-    keys, values, steps, lengths = _worked()
+    keys, values, steps, lengths = worked_games()
     deltas = nt.lambda_deltas_on_host(values, steps, lengths, 1.0, 0.5)
     assert deltas.dtype == np.float64 and deltas.tolist() == [[9993.0, 7.5], [-19996.0, 0.0], [-2.0, 0.0]]
-    assert _bits(deltas)[1, 1] == 0 and _bits(deltas)[2, 1] == 0            # +0.0: the skipped move, and the row beyond game 1's length
+    assert bits(deltas)[1, 1] == 0 and bits(deltas)[2, 1] == 0            # +0.0: the skipped move, and the row beyond game 1's length
     acc = np.zeros((256, 2), dtype=np.int64)
     st = nt.learn_lambda_nt_on_host(keys, values, steps, lengths, ((0, 3),), True, 1.0, 0.5, acc)
-    assert np.array_equal(_bits(st.pop("deltas")), _bits(deltas)) and st == dict(learnt=4, skipped=1, clamped=2)
+    assert np.array_equal(bits(st.pop("deltas")), bits(deltas)) and st == dict(learnt=4, skipped=1, clamped=2)
     total = 8192 * 65536 - 8192 * 65536 - 2 * 65536 + 491520               # the four d
     want = np.zeros((256, 2), dtype=np.int64)
     want[0], want[1], want[16] = (4 * total, 16), (2 * total, 8), (2 * total, 8)
     assert np.array_equal(acc, want)
     # game 1 alone at gamma .9: gl = .9 * .5 is a rounded product, D_0 = (2 + .9 * 7 - 1.5) + gl * 0
     one = nt.lambda_deltas_on_host(values[:, 1:], steps[:, 1:], [2], 0.9, 0.5)
-    assert _bits(one)[:, 0].tolist() == _bits([(2.0 + 0.9 * 7.0) - 1.5 + (0.9 * 0.5) * 0.0, 0.0, 0.0]).tolist()
+    assert bits(one)[:, 0].tolist() == bits([(2.0 + 0.9 * 7.0) - 1.5 + (0.9 * 0.5) * 0.0, 0.0, 0.0]).tolist()
     acc2 = np.zeros((256, 2), dtype=np.int64)
     st = nt.learn_lambda_nt_on_host(keys[:, 1:], values[:, 1:], steps[:, 1:], [2], ((0, 3),), True, 0.9, 0.5, acc2)
     d = int(np.rint(np.ldexp((2.0 + 0.9 * 7.0) - 1.5, 16)))
@@ -128,13 +93,13 @@ def test_a_hand_worked_case():
     d2 = 0.0 - 7.0
     d1 = ((2.0 + 0.9 * 7.0) - 5.0) + gl * d2
     d0 = ((1.0 + 0.9 * 5.0) - 3.0) + gl * d1
-    assert _bits(got).tolist() == _bits([d0, d1, d2]).tolist()
+    assert bits(got).tolist() == bits([d0, d1, d2]).tolist()
 
 
 def test_lengths_beyond_the_buffers_are_clamped():
     """a game whose length says more than the rows there are has the rows there are, and its last row is its last move"""
     nt = _nt()
-    keys, values, steps, _ = _worked()
+    keys, values, steps, _ = worked_games()
     deltas = nt.lambda_deltas_on_host(values, steps, [9, 2], 1.0, 0.5)
     assert deltas.tolist() == [[9993.0, 7.5], [-19996.0, 0.0], [-2.0, 0.0]]
 
@@ -169,7 +134,7 @@ def test_lambda_zero_is_the_one_step_learner():
         nxt_r[:-1], nxt_v[:-1] = ((out["steps"][1:] >> 2) & 31).astype(np.float64), out["values"][1:]
         one_step = np.where(t == L[None, :] - 1, 0.0, nxt_r + gamma * nxt_v) - out["values"]
         learn = (t < L[None, :]) & ~((t == L[None, :] - 1) & (out["steps"] >> 7 == 0))
-        assert np.array_equal(_bits(deltas)[learn], _bits(one_step)[learn]) and not _bits(deltas)[~learn].any()
+        assert np.array_equal(bits(deltas)[learn], bits(one_step)[learn]) and not bits(deltas)[~learn].any()
     # ... and lambda enters: the same games at lambda .5 (gamma .9 still) leave other sums in the same cells
     acc2 = np.zeros((W, 2), dtype=np.int64)
     nt.learn_lambda_nt_on_host(*args, 0.9, 0.5, acc2)
@@ -234,6 +199,4 @@ def test_checkpoint_versions(tmp_path):
 def test_lambda_kernels_use_no_scratch():
     """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_lambda.hip with the Makefile's flags: one kernel, the walk (the scatter is
     csrc/tfe_ntuple.hip's), without scratch or a spilled vector register.  VGPRs as built: 68."""
-    names, vgprs, scratch, spills = resource_usage("ntuple-lambda-resource-usage")
-    assert len(names) == 1 and "tfe_nt_lambda_walk_kernel" in names[0]
-    assert scratch == [0] and spills == [0] and len(vgprs) == 1 and max(vgprs) <= 128
+    assert_no_scratch("ntuple-lambda-resource-usage", {"tfe_nt_lambda_walk_kernel": 1}, 128)

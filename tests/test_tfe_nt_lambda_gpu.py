@@ -4,7 +4,7 @@ the device's own recorded games.  Every comparison is exact: the lambda-differen
 counters as integers, the weights as float32 bit patterns.  Every buffer a launch is handed sits between guard words; `deltas` holds
 a pattern before the first launch and must keep it at and beyond a game's length.
 
-Shape: test_tfe_nt_gpu.py's -- 257 games (one full workgroup of the adds and one of one lane; five wavefronts of the walk, the last
+Shape: the learners' regime (tests/tfe_nt_support.py) -- 257 games (one full workgroup of the adds and one of one lane; five wavefronts of the walk, the last
 of one lane, with games of mixed lengths in each), max_steps 256, epsilon .25, the tuples (0, 1, 2, 3) and (4, 5, 6, 8, 9, 10), seed
 457, board_id0 3000 -- at lambda .5, gamma 1.  Three rounds, played once and shared; rounds 1 and 2 run on the device's own weights.
 (The roll-out itself is held to the host's in test_tfe_nt_gpu.py; here its records are the input.)"""
@@ -13,65 +13,35 @@ import functools
 import numpy as np
 import pytest
 
-from tests.tfe_gpu_support import PATTERNS, guard, guards_intact, rollout
+from tests.tfe_gpu_support import PATTERNS, guards_intact
+from tests.tfe_nt_support import EPSILON_PLAY as EPSILON
+from tests.tfe_nt_support import BOARD_ID0, GAMES, MAX_STEPS, ROUNDS, SEED, TUPLES, bits, learner_agent, learner_round, nt, worked_games
 
 pytestmark = pytest.mark.gpu
 
-GAMES, MAX_STEPS, ROUNDS, EPSILON, LAM = 257, 256, 3, .25, .5
-TUPLES = ((0, 1, 2, 3), (4, 5, 6, 8, 9, 10))
-SEED, BOARD_ID0 = 457, 3000
-BUFFERS = ("weights_dev", "acc", "keys", "values", "steps", "lengths", "total_score", "episode_reward", "counters", "_eval", "deltas")
-PER_MOVE = ("keys", "values", "steps")
+LAM = .5
 DELTAS_PATTERN = -4321.125
+_agent = functools.partial(learner_agent, extra_buffers=("deltas",), patterns=dict(PATTERNS, deltas=DELTAS_PATTERN), lam=LAM)
 
 
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+def _round(a):
+    """learner_round with this file's verdicts on `deltas`: at t < L the host's lambda-differences, at t >= L what the buffer held
+    before the launch; not the one-step differences; and trajectory_deltas() is the buffer trimmed to the longest game"""
+    deltas_before = bits(a.deltas.cpu().numpy())
 
-
-def _agent(n_games=GAMES, **kw):
-    """The agent with every device buffer re-seated between guard words; keys / values / steps / deltas pre-filled with a pattern."""
-    import torch
-    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
-    kw = dict(dict(tuples=TUPLES, epsilon=EPSILON, max_steps=MAX_STEPS, seed=SEED, board_id0=BOARD_ID0, lam=LAM), **kw)
-    a = guard(NTupleTDAfterstateTFEGPU(torch.device("cuda:0"), n_games, **kw), BUFFERS, deltas=DELTAS_PATTERN, **PATTERNS)
-    assert a.acc.data_ptr() % 16 == 0 and a.deltas.data_ptr() % 8 == 0
-    return a
-
-
-def _one_round(a):
-    """A round on the device -- roll-out, learn (the agent's lam), apply -- with the learn and the apply launch held to the host's on
-    the device's own records.  The big arrays are compared here, where they are; the record keeps the verdicts and the counts."""
-    from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-    policy = a.weights()
-    got = rollout(a, PER_MOVE)
-    before, deltas_before = a.stats(), _bits(a.deltas.cpu().numpy())
-    a.learn()
-    acc, deltas, st = a.acc.cpu().numpy(), _bits(a.deltas.cpu().numpy()), a.stats()
-    L = got["lengths"].astype(np.int64)
-    played = np.arange(a.max_steps)[:, None] < L[None, :]
-    last = got["steps"][np.minimum(L, a.max_steps) - 1, np.arange(a.n_games)]
-    host_acc = np.zeros_like(acc)
-    host = nt.learn_lambda_nt_on_host(got["keys"], got["values"].view(np.float64), got["steps"], L, a.tuples, a.symmetric, a.gamma, a.lam, host_acc)
-    host_deltas = _bits(host.pop("deltas"))
-    rec = dict(ended=int((last >> 7 != 0).sum()), cut=int((last >> 7 == 0).sum()), moves=int(L.sum()), host=host,
-               deltas_equal=np.array_equal(deltas[played], host_deltas[played]), deltas_kept=np.array_equal(deltas[~played], deltas_before[~played]),
-               deltas_differ=int((deltas[played] != _bits(nt.lambda_deltas_on_host(got["values"].view(np.float64), got["steps"], L, a.gamma, 0.0))[played]).sum()),
-               acc_equal=np.array_equal(acc, host_acc), acc_adds=int(acc[:, 1].sum()), values_any=bool(got["values"].view(np.float64)[played].any()),
-               stats={k: st[k] - before[k] for k in ("learnt", "skipped", "clamped")}, lengths=L,
-               trajectory_equal=np.array_equal(_bits(a.trajectory_deltas()), deltas[:int(L.max())]))
-    a.apply()
-    weights, host_w = a.weights(), policy.copy()
-    rec["moved"] = nt.apply_nt_on_host(host_w, host_acc, a.alpha / a.n_features)
-    rec.update(weights_equal=np.array_equal(weights.view(np.uint32), host_w.view(np.uint32)), acc_zero=not bool(a.acc.any().item()))
-    a.round += 1
-    return rec
+    def after_learn(a, h):
+        deltas, steps = bits(a.deltas.cpu().numpy()), h.got["steps"]
+        return dict(deltas_equal=np.array_equal(deltas[h.played], bits(h.host_deltas)[h.played]),
+                    deltas_kept=np.array_equal(deltas[~h.played], deltas_before[~h.played]),
+                    deltas_differ=int((deltas[h.played] != bits(nt().lambda_deltas_on_host(h.values, steps, h.L, a.gamma, 0.0))[h.played]).sum()),
+                    trajectory_equal=np.array_equal(bits(a.trajectory_deltas()), deltas[:int(h.L.max())]))
+    return learner_round(a, after_learn)
 
 
 @functools.lru_cache(maxsize=None)
 def _rounds():
     a = _agent()
-    out = [_one_round(a) for _ in range(ROUNDS)]
+    out = [_round(a) for _ in range(ROUNDS)]
     guards_intact(a)
     return a, out
 
@@ -93,9 +63,9 @@ def test_deltas_equal_the_host_bit_for_bit():
         assert rec["deltas_equal"] and rec["deltas_kept"] and rec["trajectory_equal"], r
         assert rec["deltas_differ"] > 0, r
     assert rounds[1]["values_any"] and rounds[2]["values_any"]
-    deltas, L = _bits(a.deltas.cpu().numpy()), np.maximum.reduce([rec["lengths"] for rec in rounds])
+    deltas, L = bits(a.deltas.cpu().numpy()), np.maximum.reduce([rec["lengths"] for rec in rounds])
     never = np.arange(MAX_STEPS)[:, None] >= L[None, :]                    # rows no round has played
-    assert never.any() and (deltas[never] == _bits([DELTAS_PATTERN])[0]).all()
+    assert never.any() and (deltas[never] == bits([DELTAS_PATTERN])[0]).all()
 
 
 def test_learn_and_apply_equal_the_host():
@@ -134,7 +104,7 @@ def test_other_settings(kw):
     a = _agent(**kw)
     w = (np.random.default_rng(19).standard_normal(a.n_weights) * 3).astype(np.float32)
     a.weights_dev.copy_(torch.from_numpy(w))
-    rec = _one_round(a)
+    rec = _round(a)
     guards_intact(a)
     assert rec["values_any"] and rec["ended"] >= 1 and rec["cut"] >= 1
     assert rec["deltas_equal"] and rec["deltas_kept"] and rec["deltas_differ"] > 0
@@ -143,22 +113,20 @@ def test_other_settings(kw):
 
 
 def test_hand_made_buffers():
-    """G5: test_tfe_nt_lambda_cpu's hand-worked case copied into an agent of 2 games and 3 moves: the clamp of the add (twice), the
+    """G5: the hand-worked games (tests/tfe_nt_support.py: worked_games) copied into an agent of 2 games and 3 moves: the clamp of the add (twice), the
     unclamped carry and the cut game's skipped move, on the device"""
     import torch
-    keys = np.full((3, 2), 0x1, dtype=np.uint64)
-    values = np.array([[10.0, 1.5], [20000.0, 7.0], [2.0, -99.0]])
-    steps = np.array([[0 | 0 << 2, 1 | 2 << 2], [2 | 1 << 2, 3 | 2 << 2], [1 | 3 << 2 | 0x80, 0xEE]], dtype=np.uint8)
+    keys, values, steps, lengths = worked_games()
     a = _agent(2, tuples=((0, 3),), max_steps=3, gamma=1.0)
     a.keys.copy_(torch.from_numpy(keys.view(np.int64)))
     a.values.copy_(torch.from_numpy(values))
     a.steps.copy_(torch.from_numpy(steps))
-    a.lengths.copy_(torch.tensor([3, 2], dtype=torch.int32))
+    a.lengths.copy_(torch.tensor(lengths, dtype=torch.int32))
     a.learn()
     st = a.stats()
     assert (st["learnt"], st["skipped"], st["clamped"]) == (4, 1, 2)
     deltas = a.deltas.cpu().numpy()
-    assert _bits(deltas).tolist() == _bits([[9993.0, 7.5], [-19996.0, 0.0], [-2.0, DELTAS_PATTERN]]).tolist()
+    assert bits(deltas).tolist() == bits([[9993.0, 7.5], [-19996.0, 0.0], [-2.0, DELTAS_PATTERN]]).tolist()
     total = 8192 * 65536 - 8192 * 65536 - 2 * 65536 + 491520
     want = np.zeros((256, 2), dtype=np.int64)
     want[0], want[1], want[16] = (4 * total, 16), (2 * total, 8), (2 * total, 8)

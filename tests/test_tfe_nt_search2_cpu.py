@@ -1,34 +1,21 @@
 """The 2048 n-tuple network's expectimax play two chance layers deep without a GPU: the host mirror
-search_nt_on_host(layers=2) against the definition restated one board at a time in plain Python (tests/tfe_search2_host.py), a
+search_nt_on_host(layers=2) against the definition restated one board at a time in plain Python (tests/tfe_search_host.py), a
 hand-worked board, what does not change at one layer, the library's two new entry points with their refusals, and what the compiler
 made of the kernels."""
 import ctypes as C
 import functools
 import inspect
-import re
-from fractions import Fraction
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from tests.native_args import assert_refusals, resource_usage
-from tests.test_tfe_nt_cpu import CASES, _opts
-from tests.test_tfe_nt_search_cpu import ONE_MERGE, P, SEARCH_CASES, _search_opts
-from tests.test_tfe_nt_search_gpu import CRAFTED
-from tests.tfe_search2_host import TUPLES, key_of, scalar_search_on_host, weights
+from tests.native_args import assert_refusals
+from tests.tfe_nt_support import CASES, CRAFTED, P, SEARCH_CASES, TUPLES, assert_exports, assert_no_scratch, bits, opts, weights
+from tests.tfe_nt_support import nt as _nt
+from tests.tfe_search_host import key_of, scalar_search_on_host
 
-ROOT = Path(__file__).resolve().parent.parent
 NAMES = (("pulse_tfe_nt_search_deep", "PulseTfeNtSearch"), ("pulse_tfe_nt_evaluate_search_deep", "PulseTfeNtEval"))
-
-
-def _nt():
-    from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-    return nt
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+ONE_MERGE = key_of(CRAFTED["one_merge"])
 
 
 @functools.lru_cache(maxsize=None)
@@ -54,9 +41,9 @@ def test_mirror_equals_the_scalar_definition(name, symmetric):
     differs = 0
     for i, key in enumerate(keys.tolist()):
         want = scalar_search_on_host(key, weights(name), TUPLES, symmetric, 1.0, 77, 5, 2)
-        assert np.array_equal(_bits(look["q"][i]), _bits(want["q"])), (i, look["q"][i], want["q"])
+        assert np.array_equal(bits(look["q"][i]), bits(want["q"])), (i, look["q"][i], want["q"])
         assert int(look["action"][i]) == want["action"] and int(look["candidates"][i]) == want["candidates"], i
-        assert np.array_equal(_bits(look["terms"][i]), _bits(want["terms"])), i
+        assert np.array_equal(bits(look["terms"][i]), bits(want["terms"])), i
         differs += int(not np.array_equal(look["q"][i], scalar_search_on_host(key, weights(name), TUPLES, symmetric, 1.0, 77, 5, 1)["q"]))
     assert differs >= len(keys) - 4                                        # (the dead board, the board over after every spawn ...)
     names = list(CRAFTED)
@@ -69,7 +56,7 @@ def test_the_scalar_definition_at_one_layer_is_the_mirror():
     look = nt.search_nt_on_host(keys, weights("seeded"), TUPLES, True, 1.0, 77, 5)
     for i, key in enumerate(keys.tolist()):
         want = scalar_search_on_host(key, weights("seeded"), TUPLES, True, 1.0, 77, 5, 1)
-        assert np.array_equal(_bits(look["q"][i]), _bits(want["q"])) and int(look["action"][i]) == want["action"], i
+        assert np.array_equal(bits(look["q"][i]), bits(want["q"])) and int(look["action"][i]) == want["action"], i
 
 
 def test_a_hand_worked_board_on_zero_weights():
@@ -118,7 +105,7 @@ def test_gamma_zero_is_the_rewards_at_both_depths():
         look = nt.search_nt_on_host(keys, weights("seeded"), TUPLES, True, 0.0, 9, 4, layers=layers)
         cand = look["after"] != keys[:, None]
         assert cand.any() and not cand.all()
-        assert np.array_equal(_bits(look["q"]), _bits(np.where(cand, look["rewards"].astype(np.float64), 0.0)))
+        assert np.array_equal(bits(look["q"]), bits(np.where(cand, look["rewards"].astype(np.float64), 0.0)))
         assert np.array_equal(look["action"], nt.greedy_nt_on_host(keys, weights("seeded"), TUPLES, True, 0.0, 9, 4)["action"])
 
 
@@ -139,18 +126,14 @@ def test_two_layers_add_rewards_on_zero_weights():
 # ------------------------------------------------------------------ the library, without a GPU
 def test_library_exports_the_two_deep_entry_points():
     from pulselib_amd import _native
-    lib = _native.lib()
-    text = (ROOT / "include" / "pulse_env.h").read_text()
-    for name, struct in NAMES:
-        assert hasattr(lib, name) and _native.SYMBOLS[name] == (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p])
-        assert re.search(r"int %s\(const %s\* o, int32_t layers, void\* stream\);" % (name, struct), text), name
+    lib, _ = assert_exports(NAMES, [C.c_void_p, C.c_int32, C.c_void_p], r"int %s\(const %s\* o, int32_t layers, void\* stream\);")
     assert C.sizeof(_native.TfeNtSearch) == 176 and C.sizeof(_native.TfeNtEval) == 208 and lib.pulse_version() == 1
 
 
 @pytest.mark.parametrize("layers", [1, 2])
 def test_search_deep_refuses_what_search_refuses(layers):
     from pulselib_amd import _native
-    errors = assert_refusals(_native.lib(), "pulse_tfe_nt_search_deep", _search_opts, SEARCH_CASES, layers)
+    errors = assert_refusals(_native.lib(), "pulse_tfe_nt_search_deep", functools.partial(opts, _native.TfeNtSearch), SEARCH_CASES, layers)
     assert len(errors) == len(SEARCH_CASES) and all(e.startswith(b"pulse_tfe_nt_search_deep: ") for e in errors)
 
 
@@ -158,7 +141,7 @@ def test_search_deep_refuses_what_search_refuses(layers):
 def test_evaluate_search_deep_refuses_what_evaluate_refuses(layers):
     from pulselib_amd import _native
     cases = CASES["pulse_tfe_nt_evaluate"]
-    errors = assert_refusals(_native.lib(), "pulse_tfe_nt_evaluate_search_deep", lambda **kw: _opts("pulse_tfe_nt_evaluate", **kw), cases, layers)
+    errors = assert_refusals(_native.lib(), "pulse_tfe_nt_evaluate_search_deep", functools.partial(opts, _native.TfeNtEval), cases, layers)
     assert len(errors) == len(cases) and all(e.startswith(b"pulse_tfe_nt_evaluate_search_deep: ") for e in errors)
 
 
@@ -167,7 +150,8 @@ def test_other_depths_are_refused(layers):
     """on structs every other check passes: nothing is launched"""
     from pulselib_amd import _native
     lib = _native.lib()
-    for name, make in (("pulse_tfe_nt_search_deep", _search_opts), ("pulse_tfe_nt_evaluate_search_deep", lambda: _opts("pulse_tfe_nt_evaluate"))):
+    for name, make in (("pulse_tfe_nt_search_deep", functools.partial(opts, _native.TfeNtSearch)),
+                       ("pulse_tfe_nt_evaluate_search_deep", functools.partial(opts, _native.TfeNtEval))):
         rc = getattr(lib, name)(C.byref(make()), layers, None)
         assert rc == -1 and lib.pulse_last_error() == name.encode() + b": layers must be 1 or 2"
         with pytest.raises(ValueError, match="layers must be 1 or 2"):
@@ -190,6 +174,4 @@ def test_python_layer():
 def test_deep_search_kernels_use_no_scratch():
     """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search_deep.hip with the Makefile's flags: four kernels, none with scratch or a
     spilled vector register.  VGPRs as built: boards 157 (symmetric) / 131, games 191 / 165."""
-    names, vgprs, scratch, spills = resource_usage("ntuple-search-deep-resource-usage")
-    assert len(names) == 4 and sum("tfe_nt_search2_kernel" in n for n in names) == 2 and sum("tfe_nt_search2_games_kernel" in n for n in names) == 2
-    assert scratch == [0] * 4 and spills == [0] * 4 and len(vgprs) == 4 and max(vgprs) <= 256
+    assert_no_scratch("ntuple-search-deep-resource-usage", {"tfe_nt_search2_kernel": 2, "tfe_nt_search2_games_kernel": 2}, 256)

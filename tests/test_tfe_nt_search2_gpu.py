@@ -1,6 +1,6 @@
 """The 2048 n-tuple network's expectimax play two chance layers deep on the device (DESIGN.md section 13.4;
 csrc/tfe_ntuple_search_deep.hip: pulse_tfe_nt_search_deep, pulse_tfe_nt_evaluate_search_deep) against the host's statement of it
-(search_nt_on_host(layers=2); tests/tfe_search2_host.py: the oracle's environment under it).  Every comparison is exact: integers word
+(search_nt_on_host(layers=2); tests/tfe_search_host.py: the oracle's environment under it).  Every comparison is exact: integers word
 for word, float64 as bit patterns.  Every buffer a launch is handed sits between guard words.
 
 Shape: the tuples (0, 1, 2, 3) and (4, 5, 6, 8, 9, 10), weights all zero or a seeded normal array of scale 4, gamma 1.  The kernels
@@ -17,23 +17,22 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_tfe_nt_search_gpu import CRAFTED
-from tests.tfe_gpu_support import PATTERNS, guard, guarded, guards_intact
-from tests.tfe_search2_host import TUPLES, key_of, search2_games_on_host, weights
+from tests.tfe_gpu_support import guarded, guards_intact
+from tests.tfe_nt_support import BOARD_ID0, CRAFTED, MORE, TUPLES, search_agent, search_outputs, weights
+from tests.tfe_search_host import key_of, search_games_on_host
 
 pytestmark = pytest.mark.gpu
 GAMES, MAX_STEPS, EPSILON = 7, 160, .25
-SEED, BOARD_ID0, ROUND = 5, 3000, 0
-BUFFERS = ("weights_dev", "acc", "keys", "values", "steps", "lengths", "total_score", "episode_reward", "counters", "_eval")
-MORE = dict(one_empty=[1, 2, 1, 2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 4, 0])   # CRAFTED's one_merge after its move to the left
+SEED, ROUND = 5, 0
 CASES = (("seeded", 0.0, True), ("seeded", EPSILON, True), ("zero", EPSILON, True), ("zero", 0.0, True), ("seeded", EPSILON, False))
+_agent = functools.partial(search_agent, GAMES, MAX_STEPS, SEED)
 
 
 @functools.lru_cache(maxsize=None)
 def _host_games(name, epsilon, symmetric=True):
     from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
-    return search2_games_on_host(GAMES, MAX_STEPS, epsilon, 1.0, weights(name), TUPLES, symmetric, SEED, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, BOARD_ID0,
-                                 ROUND, keep_boards="before")
+    return search_games_on_host(GAMES, MAX_STEPS, epsilon, 1.0, weights(name), TUPLES, symmetric, SEED, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, BOARD_ID0,
+                                ROUND, keep_boards="before", layers=2)
 
 
 @functools.lru_cache(maxsize=None)
@@ -52,25 +51,6 @@ def _boards():
     return keys
 
 
-def _agent(name, symmetric=True, **kw):
-    """the agent with every device buffer re-seated between guard words and the weights `name` uploaded"""
-    import torch
-    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
-    kw = dict(dict(tuples=TUPLES, symmetric=symmetric, max_steps=MAX_STEPS, seed=SEED, board_id0=BOARD_ID0), **kw)
-    a = guard(NTupleTDAfterstateTFEGPU(torch.device("cuda:0"), GAMES, **kw), BUFFERS, **PATTERNS)
-    a.weights_dev.copy_(torch.from_numpy(weights(name).copy()))
-    return a
-
-
-def _outputs(n, dev):
-    """(q, action, candidates) of n boards between guard words, holding patterns, and the guards"""
-    import torch
-    q, gq, nq = guarded(torch.zeros((n, 4), dtype=torch.float64, device=dev), -12345.678)
-    action, ga, na = guarded(torch.zeros(n, dtype=torch.int8, device=dev), 0x55)
-    cand, gc, nc = guarded(torch.zeros(n, dtype=torch.uint8, device=dev), 0x55)
-    return q, action, cand, [("q", gq, nq), ("action", ga, na), ("candidates", gc, nc)]
-
-
 def _n_empty(keys):
     return ((keys[:, None] >> (np.uint64(4) * np.arange(16, dtype=np.uint64))) & np.uint64(15) == 0).sum(axis=1)
 
@@ -85,7 +65,7 @@ def test_search_equals_the_mirror_bit_for_bit(name, symmetric):
     want = nt.search_nt_on_host(keys, weights(name), TUPLES, symmetric, a.gamma, a.tie_seed, a.round, layers=2)
     dev = torch.device("cuda:0")
     boards, gb, nb = guarded(torch.from_numpy(keys.view(np.int64).copy()).to(dev))
-    q, action, cand, guards = _outputs(len(keys), dev)
+    q, action, cand, guards = search_outputs(len(keys), dev)
     a.search_launch(boards, q, action, cand, layers=2)
     got_q = q.cpu().numpy()
     assert np.array_equal(cand.cpu().numpy(), want["candidates"]) and np.array_equal(action.cpu().numpy().astype(np.int64), want["action"])
@@ -119,8 +99,8 @@ def test_one_layer_through_the_deep_entry_point_is_the_search():
     import torch
     a, keys, dev = _agent("seeded"), _boards(), torch.device("cuda:0")
     boards = torch.from_numpy(keys.view(np.int64).copy()).to(dev)
-    q0, action0, cand0, guards0 = _outputs(len(keys), dev)
-    q1, action1, cand1, guards1 = _outputs(len(keys), dev)
+    q0, action0, cand0, guards0 = search_outputs(len(keys), dev)
+    q1, action1, cand1, guards1 = search_outputs(len(keys), dev)
     a.search_launch(boards, q0, action0, cand0)
     a._launch("pulse_tfe_nt_search_deep", a._search_struct(boards, q1, action1, cand1), 1)
     assert torch.equal(q0.view(torch.int64), q1.view(torch.int64)) and torch.equal(action0, action1) and torch.equal(cand0, cand1)

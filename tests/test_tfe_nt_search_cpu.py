@@ -2,50 +2,28 @@
 refusals, the host mirror search_nt_on_host (pulselib_amd/agents/tfe_ntuple_td_gpu.py) on hand-worked boards -- E as exact rationals
 from a move written out in plain Python -- and what the compiler made of the kernels."""
 import ctypes as C
-import math
+import functools
 import re
 from fractions import Fraction
-from pathlib import Path
 
 import numpy as np
-import pytest
 
-from tests.native_args import PTR, assert_refusals, nt_opts, resource_usage
-from tests.test_tfe_nt_cpu import BATCH, CASES, EPSILON, NET_CASES, WEIGHTS, _opts
+from tests.native_args import assert_refusals
+from tests.tfe_nt_support import BATCH, CASES, CRAFTED, EPSILON, NET_CASES, P, ROOT, SEARCH_CASES, TUPLES, WEIGHTS, assert_exports, assert_no_scratch, bits, opts, weights
+from tests.tfe_nt_support import nt as _nt
 from tests.tfe_search_host import key_of
 
-ROOT = Path(__file__).resolve().parent.parent
-TUPLES = ((0, 1, 2, 3), (4, 5, 6, 8, 9, 10))
-P = (Fraction(15099495, 2 ** 24), Fraction(1677721, 2 ** 24))            # a 2-tile, a 4-tile
-#               the row 1 1 . . over a filling no 2- or 4-tile merges with
-WORKED = key_of([1, 1, 0, 0,
-                 3, 4, 3, 4,
-                 4, 3, 4, 3,
-                 3, 4, 3, 4])
-DEAD = key_of([1, 2, 1, 2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 2, 1])
-ONE_MERGE = key_of([1, 2, 1, 2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 3, 3])      # full; only the two 8s of the last row merge
-
-
-def _nt():
-    from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-    return nt
+WORKED, DEAD, ONE_MERGE = key_of(CRAFTED["worked"]), key_of(CRAFTED["dead"]), key_of(CRAFTED["one_merge"])
 
 
 def _zero():
-    return np.zeros(_nt().tuple_offsets(TUPLES)[1], dtype=np.float32)
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+    return weights("zero")
 
 
 def test_library_exports_the_two_entry_points():
     from pulselib_amd import _native
-    lib = _native.lib()
-    text = (ROOT / "include" / "pulse_env.h").read_text()
-    for name, struct in (("pulse_tfe_nt_search", "PulseTfeNtSearch"), ("pulse_tfe_nt_evaluate_search", "PulseTfeNtEval")):
-        assert hasattr(lib, name) and _native.SYMBOLS[name] == (C.c_int, [C.c_void_p, C.c_void_p])
-        assert re.search(r"int %s\(const %s\* o, void\* stream\);" % (name, struct), text), name
+    _, text = assert_exports((("pulse_tfe_nt_search", "PulseTfeNtSearch"), ("pulse_tfe_nt_evaluate_search", "PulseTfeNtEval")), [C.c_void_p, C.c_void_p],
+                             r"int %s\(const %s\* o, void\* stream\);")
     assert C.sizeof(_native.TfeNtSearch) == 176 and C.sizeof(_native.TfeNtEval) == 208         # the static_asserts of csrc/tfe_ntuple*.hip
     assert [f[0] for f in _native.TfeNtSearch._fields_] == ["net", "n_boards", "reserved0", "gamma", "tie_seed", "round", "boards", "q", "action",
                                                             "candidates", "reserved1"]
@@ -54,24 +32,9 @@ def test_library_exports_the_two_entry_points():
 
 
 # ------------------------------------------------------------------ PULSE_EINVAL before anything is launched
-def _search_opts(**kw):
-    """a PulseTfeNtSearch every check passes, then `kw` over it (native_args.nt_opts' keywords)"""
-    from pulselib_amd import _native
-    return nt_opts(_native.TfeNtSearch, dict(tuples=[list(t) for t in TUPLES], net_n=4, net_symmetric=1, net_weights=PTR, n_boards=73, gamma=1.0,
-                                             tie_seed=5, round=2, boards=PTR, q=PTR, action=PTR, candidates=PTR), **kw)
-
-
-SEARCH_CASES = NET_CASES + WEIGHTS + [
-    (dict(n_boards=0), b"n_boards must be positive"), (dict(n_boards=-3), b"n_boards must be positive"),
-    (dict(gamma=-0.01), b"gamma must be in [0, 1]"), (dict(gamma=1.01), b"gamma must be in [0, 1]"), (dict(gamma=math.nan), b"gamma must be in [0, 1]"),
-    (dict(reserved0=1), b"reserved0 / reserved1 must be 0"), (dict(reserved1=1), b"reserved0 / reserved1 must be 0"),
-    (dict(boards=None), b"boards is null"), (dict(q=None), b"q is null"), (dict(action=None), b"action is null"),
-    (dict(candidates=None), b"candidates is null"), (dict(boards=4), b"boards / q must be 8-byte aligned"), (dict(q=4), b"boards / q must be 8-byte aligned")]
-
-
 def test_search_refuses_without_gpu():
     from pulselib_amd import _native
-    assert len(assert_refusals(_native.lib(), "pulse_tfe_nt_search", _search_opts, SEARCH_CASES)) == len(SEARCH_CASES)
+    assert len(assert_refusals(_native.lib(), "pulse_tfe_nt_search", functools.partial(opts, _native.TfeNtSearch), SEARCH_CASES)) == len(SEARCH_CASES)
 
 
 def test_evaluate_search_refuses_what_evaluate_refuses():
@@ -79,7 +42,7 @@ def test_evaluate_search_refuses_what_evaluate_refuses():
     from pulselib_amd import _native
     cases = CASES["pulse_tfe_nt_evaluate"]
     assert len(cases) == len(NET_CASES + WEIGHTS + BATCH + EPSILON) + 6
-    errors = assert_refusals(_native.lib(), "pulse_tfe_nt_evaluate_search", lambda **kw: _opts("pulse_tfe_nt_evaluate", **kw), cases)
+    errors = assert_refusals(_native.lib(), "pulse_tfe_nt_evaluate_search", functools.partial(opts, _native.TfeNtEval), cases)
     assert all(e.startswith(b"pulse_tfe_nt_evaluate_search: ") for e in errors)
 
 
@@ -152,7 +115,7 @@ def test_gamma_zero_is_the_one_ply_policy():
     look, ply = nt.search_nt_on_host(keys, w, TUPLES, True, 0.0, 9, 4), nt.greedy_nt_on_host(keys, w, TUPLES, True, 0.0, 9, 4)
     cand = look["after"] != keys[:, None]
     assert cand.any(axis=1).sum() > 250 and not cand.all()
-    assert np.array_equal(_bits(look["q"]), _bits(np.where(cand, look["rewards"].astype(np.float64), 0.0)))
+    assert np.array_equal(bits(look["q"]), bits(np.where(cand, look["rewards"].astype(np.float64), 0.0)))
     assert np.array_equal(look["action"], ply["action"]) and np.array_equal(look["candidates"], (cand << np.arange(4)).sum(axis=1))
     # ... and gamma enters: the same boards at gamma 1 choose otherwise somewhere
     assert not np.array_equal(nt.search_nt_on_host(keys, w, TUPLES, True, 1.0, 9, 4)["action"], ply["action"])
@@ -217,7 +180,7 @@ def test_q_is_the_same_on_the_eight_images():
     assert len(set(q.ravel().tolist())) > 150
     for j, src in enumerate(transforms_on_host(4)):
         image = nt.search_nt_on_host(pack(nib[:, src]), w, TUPLES, True, 1.0, 1, 0)["q"]
-        assert np.array_equal(_bits(image[:, list(ACTION_MAP[j])]), _bits(q)), j
+        assert np.array_equal(bits(image[:, list(ACTION_MAP[j])]), bits(q)), j
     plain = nt.search_nt_on_host(pack(nib[:, transforms_on_host(4)[1]]), w, TUPLES, False, 1.0, 1, 0)["q"]
     assert not np.array_equal(plain[:, list(ACTION_MAP[1])], nt.search_nt_on_host(pack(nib), w, TUPLES, False, 1.0, 1, 0)["q"])
 
@@ -234,22 +197,20 @@ def test_the_sum_is_the_tree():
     lanes = look["terms"].copy()
     for d in (1, 2, 4, 8, 16):
         lanes = lanes + lanes[..., np.arange(32) ^ d]
-    assert all(np.array_equal(_bits(lanes[..., s]), _bits(lanes[..., 0])) for s in range(32))          # the sum, in every lane
+    assert all(np.array_equal(bits(lanes[..., s]), bits(lanes[..., 0])) for s in range(32))          # the sum, in every lane
     left_to_right = np.zeros(lanes.shape[:2])
     for s in range(32):
         left_to_right = left_to_right + look["terms"][..., s]
     cand = (look["candidates"][:, None] >> np.arange(4) & 1).astype(bool)
     n_empty = ((look["after"][:, :, None] >> (np.uint64(4) * np.arange(16, dtype=np.uint64))) & np.uint64(15) == 0).sum(axis=2)
-    assert np.array_equal(_bits(look["E"][cand]), _bits((lanes[..., 0] / np.maximum(n_empty, 1))[cand]))
-    differ = cand & (_bits(lanes[..., 0]) != _bits(left_to_right))
+    assert np.array_equal(bits(look["E"][cand]), bits((lanes[..., 0] / np.maximum(n_empty, 1))[cand]))
+    differ = cand & (bits(lanes[..., 0]) != bits(left_to_right))
     assert differ.sum() > 20 and np.allclose(lanes[..., 0], left_to_right, rtol=1e-13, atol=0)
-    assert (_bits(look["E"]) != _bits(left_to_right / np.maximum(n_empty, 1)))[differ].any()
+    assert (bits(look["E"]) != bits(left_to_right / np.maximum(n_empty, 1)))[differ].any()
 
 
 # ------------------------------------------------------------------ what the compiler made
 def test_search_kernels_use_no_scratch():
     """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search.hip with the Makefile's flags: four kernels, none with scratch or a spilled
     vector register.  VGPRs as built: search 138 (symmetric) / 112, games 152 / 97."""
-    names, vgprs, scratch, spills = resource_usage("ntuple-search-resource-usage")
-    assert len(names) == 4 and sum("tfe_nt_search_kernel" in n for n in names) == 2 and sum("tfe_nt_search_games_kernel" in n for n in names) == 2
-    assert scratch == [0] * 4 and spills == [0] * 4 and len(vgprs) == 4 and max(vgprs) <= 256
+    assert_no_scratch("ntuple-search-resource-usage", {"tfe_nt_search_kernel": 2, "tfe_nt_search_games_kernel": 2}, 256)

@@ -14,39 +14,21 @@ import functools
 import numpy as np
 import pytest
 
-from tests.tfe_gpu_support import PATTERNS, guard, guarded, guards_intact
+from tests.tfe_gpu_support import guarded, guards_intact
+from tests.tfe_nt_support import BOARD_ID0, CRAFTED, TUPLES, search_agent, search_outputs, weights
 from tests.tfe_search_host import key_of, search_games_on_host
 
 pytestmark = pytest.mark.gpu
 
 GAMES, MAX_STEPS, BOARDS, EPSILON = 17, 192, 73, .25
-TUPLES = ((0, 1, 2, 3), (4, 5, 6, 8, 9, 10))
-SEED, BOARD_ID0, ROUND = 2312, 3000, 0
-BUFFERS = ("weights_dev", "acc", "keys", "values", "steps", "lengths", "total_score", "episode_reward", "counters", "_eval")
-CRAFTED = dict(
-    worked=[1, 1, 0, 0, 3, 4, 3, 4, 4, 3, 4, 3, 3, 4, 3, 4],               # tests/test_tfe_nt_search_cpu.py works these out by hand
-    dead=[1, 2, 1, 2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 2, 1],
-    one_merge=[1, 2, 1, 2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 3, 3],
-    over_after_spawn=[1, 2, 1, 2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 4, 1],
-    corner=[1] + [0] * 15,                                                 # right and down are mirror images: two equal best q on zero weights
-    fourteen_empty=[0, 0, 0, 0, 0, 2, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1],
-    tile_32768=[15, 3, 0, 1, 2, 5, 1, 0, 0, 0, 4, 0, 1, 0, 0, 2],
-    makes_32768=[15, 14, 14, 3, 0, 1, 2, 0, 0, 0, 0, 0, 13, 13, 0, 1])
-
-
-@functools.lru_cache(maxsize=None)
-def _weights(name):
-    from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-    n = nt.tuple_offsets(TUPLES)[1]
-    w = np.zeros(n, dtype=np.float32) if name == "zero" else (np.random.default_rng(7).standard_normal(n) * 4).astype(np.float32)
-    w.setflags(write=False)
-    return w
+SEED, ROUND = 2312, 0
+_agent = functools.partial(search_agent, GAMES, MAX_STEPS, SEED)
 
 
 @functools.lru_cache(maxsize=None)
 def _host_games(name, epsilon, symmetric=True, keep_boards=None):
     from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
-    return search_games_on_host(GAMES, MAX_STEPS, epsilon, 1.0, _weights(name), TUPLES, symmetric, SEED, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, BOARD_ID0, ROUND,
+    return search_games_on_host(GAMES, MAX_STEPS, epsilon, 1.0, weights(name), TUPLES, symmetric, SEED, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, BOARD_ID0, ROUND,
                                 keep_boards=keep_boards)
 
 
@@ -69,34 +51,22 @@ def _boards():
     return keys
 
 
-def _agent(name, symmetric=True, **kw):
-    """the agent with every device buffer re-seated between guard words and the weights `name` uploaded"""
-    import torch
-    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
-    kw = dict(dict(tuples=TUPLES, symmetric=symmetric, max_steps=MAX_STEPS, seed=SEED, board_id0=BOARD_ID0), **kw)
-    a = guard(NTupleTDAfterstateTFEGPU(torch.device("cuda:0"), GAMES, **kw), BUFFERS, **PATTERNS)
-    a.weights_dev.copy_(torch.from_numpy(_weights(name).copy()))
-    return a
-
-
 @pytest.mark.parametrize("name,symmetric", [("zero", True), ("seeded", True), ("seeded", False)])
 def test_search_equals_the_mirror_bit_for_bit(name, symmetric):
     import torch
     from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
     a, keys = _agent(name, symmetric), _boards()
     a.round = 3                                                            # (the coins of another round than the games')
-    want = nt.search_nt_on_host(keys, _weights(name), TUPLES, symmetric, a.gamma, a.tie_seed, a.round)
+    want = nt.search_nt_on_host(keys, weights(name), TUPLES, symmetric, a.gamma, a.tie_seed, a.round)
     dev = torch.device("cuda:0")
     boards, gb, nb = guarded(torch.from_numpy(keys.view(np.int64).copy()).to(dev))
-    q, gq, nq = guarded(torch.zeros((BOARDS, 4), dtype=torch.float64, device=dev), -12345.678)
-    action, ga, na = guarded(torch.zeros(BOARDS, dtype=torch.int8, device=dev), 0x55)
-    cand, gc, nc = guarded(torch.zeros(BOARDS, dtype=torch.uint8, device=dev), 0x55)
+    q, action, cand, guards = search_outputs(BOARDS, dev)
     a.search_launch(boards, q, action, cand)
     got_q = q.cpu().numpy()
     assert np.array_equal(cand.cpu().numpy(), want["candidates"]) and np.array_equal(action.cpu().numpy().astype(np.int64), want["action"])
     assert np.array_equal(got_q.view(np.uint64), want["q"].view(np.uint64))
     assert np.array_equal(boards.cpu().numpy().view(np.uint64), keys)
-    guards_intact(a, [("boards", gb, nb), ("q", gq, nq), ("action", ga, na), ("candidates", gc, nc)])
+    guards_intact(a, [("boards", gb, nb)] + guards)
     # what the comparison exercised
     names = list(CRAFTED)
     assert int(want["action"][names.index("dead")]) == -1 and int(want["candidates"][names.index("over_after_spawn")]) == 0

@@ -3,39 +3,26 @@ their refusals, the host's statement of the learner with its third accumulator a
 (pulselib_amd/agents/tfe_ntuple_td_gpu.py: learn_tc_nt_on_host, apply_tc_nt_on_host) on two hand-worked rounds, the first apply against
 apply_nt_on_host, the checkpoint's version 4, and what the compiler made of the kernels."""
 import ctypes as C
+import functools
 import inspect
-import math
 import re
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-from tests.native_args import PTR, assert_refusals, nt_opts, resource_usage
-from tests.test_tfe_nt_cpu import BATCH, NET_CASES, WEIGHTS, _null_and_odd
+from tests.native_args import assert_refusals, remarks
+from tests.tfe_nt_support import BATCH, CASES, NET_CASES, RHO, ROOT, STEP_SIZE, V, X, Y, assert_exports, assert_no_scratch, bits, opts, tc_worked, tc_worked_state
+from tests.tfe_nt_support import nt as _nt
 
-ROOT = Path(__file__).resolve().parent.parent
 LEARN, APPLY = "pulse_tfe_nt_learn_tc", "pulse_tfe_nt_apply_tc"
-TUPLES = ((0, 1, 2, 3), (4, 5, 6, 8, 9, 10))
-
-
-def _nt():
-    from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-    return nt
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
 
 
 # ------------------------------------------------------------------ the export
 def test_library_exports_the_two_entry_points():
     from pulselib_amd import _native
-    lib = _native.lib()
-    text = (ROOT / "include" / "pulse_env.h").read_text()
-    for name, struct in ((LEARN, "PulseTfeNtLearnTc"), (APPLY, "PulseTfeNtApplyTc")):
-        assert hasattr(lib, name) and _native.SYMBOLS[name] == (C.c_int, [C.c_void_p, C.c_void_p])
-        assert re.search(r"int %s\(const %s\* o, void\* stream\);" % (name, struct), text), name
+    names = ((LEARN, "PulseTfeNtLearnTc"), (APPLY, "PulseTfeNtApplyTc"))
+    lib, text = assert_exports(names, [C.c_void_p, C.c_void_p], r"int %s\(const %s\* o, void\* stream\);")
+    for name, struct in names:
         assert re.search(r"typedef struct %s \{" % struct, text)
     s = _native.TfeNtLearnTc
     assert C.sizeof(s) == 200
@@ -57,39 +44,15 @@ def test_library_exports_the_two_entry_points():
 
 
 # ------------------------------------------------------------------ PULSE_EINVAL before anything is launched
-def _learn_opts(**kw):
-    from pulselib_amd import _native
-    return nt_opts(_native.TfeNtLearnTc, dict(tuples=[list(t) for t in TUPLES], net_n=4, net_symmetric=1, net_weights=PTR, n_games=64, max_steps=32,
-                                              gamma=1.0, lam=0.5, keys=PTR, values=PTR, steps=PTR, lengths=PTR, deltas=PTR, acc=PTR, acc_abs=PTR, stats=PTR),
-                   **kw)
-
-
-def _apply_opts(**kw):
-    from pulselib_amd import _native
-    return nt_opts(_native.TfeNtApplyTc, dict(tuples=[list(t) for t in TUPLES], net_n=4, net_symmetric=1, net_weights=PTR, step=1.0 / 16, acc=PTR,
-                                              acc_abs=PTR, e=PTR, a=PTR, tc_stats=PTR), **kw)
-
-
-LAMBDA = [(dict(lam=-0.01), b"lambda must be in [0, 1]"), (dict(lam=1.01), b"lambda must be in [0, 1]"), (dict(lam=math.nan), b"lambda must be in [0, 1]")]
-ACC = [(dict(acc=None), b"acc is null"), (dict(acc=8), b"acc must be 16-byte aligned")]
-# what pulse_tfe_nt_learn_lambda refuses (tests/test_tfe_nt_lambda_cpu.py: CASES), then its own
-LEARN_CASES = NET_CASES + BATCH + LAMBDA + _null_and_odd(("keys", "values", "deltas", "stats"), ("lengths",)) + [(dict(steps=None), b"steps is null")] + ACC + [
-    (dict(acc_abs=None), b"acc_abs is null"), (dict(acc_abs=4), b"acc_abs must be 8-byte aligned"),
-    (dict(deltas=None, lam=1.0), b"deltas is null"), (dict(deltas=None, lam=5e-324), b"deltas is null")]
-STEP = [(dict(step=0.0), b"step must be in (0, 1]"), (dict(step=1.01), b"step must be in (0, 1]"), (dict(step=math.nan), b"step must be in (0, 1]"),
-        (dict(step=-0.5), b"step must be in (0, 1]")]
-APPLY_CASES = NET_CASES + WEIGHTS + STEP + ACC + [(dict([(f, None)]), f.encode() + b" is null") for f in ("acc_abs", "e", "a", "tc_stats")] + [
-    (dict([(f, 4)]), b"acc_abs / e / a / tc_stats must be 8-byte aligned") for f in ("acc_abs", "e", "a", "tc_stats")] + [(dict(reserved0=1), b"reserved0 must be 0")]
-
-
 def test_argument_checks_without_gpu():
     """every refusal of pulse_tfe_nt_learn_lambda under the new name and the four of its own (acc_abs null, misaligned; lambda > 0
     without deltas, twice), and every refusal of pulse_tfe_nt_apply and the eight of its own, before anything is launched (there is no
     device here to launch on)"""
     from pulselib_amd import _native
     lib = _native.lib()
-    assert len(assert_refusals(lib, LEARN, _learn_opts, LEARN_CASES)) == len(NET_CASES) + len(BATCH) + 3 + 5 + 4 + 1 + 1 + 2 + 4
-    assert len(assert_refusals(lib, APPLY, _apply_opts, APPLY_CASES)) == len(NET_CASES) + 2 + 4 + 2 + 8 + 1
+    _learn_opts, _apply_opts = functools.partial(opts, _native.TfeNtLearnTc), functools.partial(opts, _native.TfeNtApplyTc)
+    assert len(assert_refusals(lib, LEARN, _learn_opts, CASES[LEARN])) == len(NET_CASES) + len(BATCH) + 3 + 5 + 4 + 1 + 1 + 2 + 4
+    assert len(assert_refusals(lib, APPLY, _apply_opts, CASES[APPLY])) == len(NET_CASES) + 2 + 4 + 2 + 8 + 1
     o = _learn_opts(net_weights=None, n_games=0)                            # the learner reads no weight
     assert getattr(lib, LEARN)(C.byref(o), None) == -1 and b"n_games must be positive" in lib.pulse_last_error()
     # lambda == 0 with deltas null is the TD(0) form: it passes that check, and the next one refuses
@@ -116,70 +79,6 @@ def test_python_layer():
 
 
 # ------------------------------------------------------------------ the hand-worked case: two rounds
-X, Y, V = 0x1, 0x2002000000002002, 0x3000000000000001
-STEP_SIZE = 0.125                                                          # alpha 1 over the 8 features of one symmetric tuple
-RHO = 1.375 / 4098.375                                                     # |E| / A of weights 0, 1 and 16 after round 1
-
-
-def tc_worked():
-    """Tuple (0, 3), symmetric (its images read the corner pairs: test_tfe_nt_cpu.py), gamma 1, TD(0), 3 games of up to 3 moves.
-    Boards: X = nibble 1 in cell 0 reads the weights 1, 0, 0, 16, 1, 0, 0, 16 (index = first nibble + 16 * second); Y = nibble 2 in all
-    four corners reads weight 34 eight times; V = nibble 1 in cell 0 and nibble 3 in cell 15 reads 1, 48, 3, 16, 1, 48, 3, 16.
-
-    Round 1.  Games 0 and 1 are test_tfe_nt_lambda_cpu.py's, every move on X: game 0 ends at t = 2 (values 10, 20000, 2; rewards 0, 1,
-    3), game 1 is cut at length 2 (values 1.5, 7; rewards 2, 2).  Their four learnt differences are 19,991 -> 8,192 (clamped), -19,995 ->
-    -8,192 (clamped), -2 and 7.5: as integers d = 536,870,912, -536,870,912, -131,072 and 491,520, so per add sum = 360,448 and
-    |d| = 1,074,364,416.  Game 2 is one move on Y that ends the game with value 0: difference 0 - 0 = 0.
-      weight 0: 16 adds, sum 4 * 360,448, abs 4 * 1,074,364,416: m = 360,448 / 4 / 65,536 = 1.375, a = 1,074,364,416 / 4 / 65,536 = 4,098.375
-      weights 1 and 16: 8 adds each, half those sums: the same m and a
-      weight 34: 8 adds of 0: m = 0, a = 0
-    On zero state rho = 1: weights 0, 1, 16 become 0.125 * 1.375 = 0.171875 with E = 1.375, A = 4,098.375; weight 34 stays 0 with
-    E = A = 0.  Moved 4, rho sum 4 * 2^32.
-
-    Round 2.  Game 0 is one ending move on V with value 2: difference -2, d = -131,072.  Game 1 is one ending move on Y with value -3:
-    difference 3, d = 196,608.  Game 2 has length 0.
-      weights 1 and 16: 2 adds, m = -2, a = 2: the sign of round 1 turned, rho = 1.375 / 4,098.375 = 11 / 32,787 < 1:
-        w = float32(0.171875 + (0.125 * rho) * -2), E = 1.375 - 2 = -0.625, A = 4,100.375
-      weight 0: visited in round 1 only: its bits, E = 1.375 and A = 4,098.375 stay
-      weight 34: every earlier difference was 0, so A = 0 and rho = 1: m = a = 3, w = 0.375, E = A = 3
-      weights 3 and 48: never seen before, rho = 1: m = -2, a = 2, w = -0.25, E = -2, A = 2
-    Moved 5, rho sum 3 * 2^32 + 2 * rint(rho * 2^32).
-    Returns the two rounds as (keys, values, steps, lengths)."""
-    keys = np.full((3, 3), X, dtype=np.uint64)
-    keys[0, 2] = Y
-    values = np.array([[10.0, 1.5, 0.0], [20000.0, 7.0, -55.0], [2.0, -99.0, -55.0]])
-    steps = np.array([[0 | 0 << 2, 1 | 2 << 2, 0x80], [2 | 1 << 2, 3 | 2 << 2, 0xEE], [1 | 3 << 2 | 0x80, 0xEE, 0xEE]], dtype=np.uint8)
-    keys2 = np.full((3, 3), X, dtype=np.uint64)
-    keys2[0, 0], keys2[0, 1] = V, Y
-    values2 = np.full((3, 3), -55.0)
-    values2[0, 0], values2[0, 1] = 2.0, -3.0
-    steps2 = np.full((3, 3), 0xEE, dtype=np.uint8)
-    steps2[0, 0], steps2[0, 1] = 0x80, 0x80 | 1
-    return (keys, values, steps, [3, 2, 1]), (keys2, values2, steps2, [1, 1, 0])
-
-
-def tc_worked_state():
-    """What tc_worked's docstring works out: per round (acc [W, 2], acc_abs [W], stats of the learn launch, weights float32[W] after the
-    apply, E, A, (moved, rho sum)), W = 256"""
-    out = []
-    acc, ab = np.zeros((256, 2), dtype=np.int64), np.zeros(256, dtype=np.int64)
-    acc[0], acc[1], acc[16], acc[34] = (4 * 360448, 16), (2 * 360448, 8), (2 * 360448, 8), (0, 8)
-    ab[0], ab[1], ab[16] = 4 * 1074364416, 2 * 1074364416, 2 * 1074364416
-    w, E, A = np.zeros(256, dtype=np.float32), np.zeros(256), np.zeros(256)
-    w[[0, 1, 16]], E[[0, 1, 16]], A[[0, 1, 16]] = 0.171875, 1.375, 4098.375
-    out.append((acc, ab, dict(learnt=5, skipped=1, clamped=2), w, E, A, (4, 4 << 32)))
-    acc, ab = np.zeros((256, 2), dtype=np.int64), np.zeros(256, dtype=np.int64)
-    for i in (1, 16, 3, 48):
-        acc[i], ab[i] = (2 * -131072, 2), 2 * 131072
-    acc[34], ab[34] = (8 * 196608, 8), 8 * 196608
-    w, E, A = w.copy(), E.copy(), A.copy()
-    w[[1, 16]], E[[1, 16]], A[[1, 16]] = np.float32(0.171875 + (0.125 * RHO) * -2.0), -0.625, 4100.375
-    w[34], E[34], A[34] = 0.375, 3.0, 3.0
-    w[[3, 48]], E[[3, 48]], A[[3, 48]] = -0.25, -2.0, 2.0
-    out.append((acc, ab, dict(learnt=2, skipped=0, clamped=0), w, E, A, (5, (3 << 32) + 2 * int(np.rint(np.ldexp(RHO, 32))))))
-    return out
-
-
 def test_two_hand_worked_rounds():
     nt = _nt()
     tuples = ((0, 3),)
@@ -194,7 +93,7 @@ def test_two_hand_worked_rounds():
         assert nt.apply_tc_nt_on_host(w, acc, ab, E, A, STEP_SIZE) == want_tc, r
         assert not acc.any() and not ab.any(), r
         assert np.array_equal(w.view(np.uint32), want_w.view(np.uint32)), r
-        assert np.array_equal(_bits(E), _bits(want_E)) and np.array_equal(_bits(A), _bits(want_A)), r
+        assert np.array_equal(bits(E), bits(want_E)) and np.array_equal(bits(A), bits(want_A)), r
     assert w[1] < np.float32(0.171875) and w[1] > np.float32(0.171875 - 0.25)      # the turned sign moved it by less than the full step
     # the lambda form of round 1: the same four clamped integers (D_0 = 9,993 and D_1 = -19,996 clamp as the one-step ones do)
     acc2, ab2 = np.zeros((256, 2), dtype=np.int64), np.zeros(256, dtype=np.int64)
@@ -253,7 +152,7 @@ def test_checkpoint_version_4(tmp_path):
         assert f["tc"] is True and f["lam"] == lam and {k: f[k] for k in scalars} == {**scalars, "symmetric": True}
         assert np.array_equal(nt.weights_of_checkpoint(f).view(np.uint32), w.view(np.uint32))
         E2, A2 = nt.coherence_of_checkpoint(f)
-        assert np.array_equal(_bits(E2), _bits(E)) and np.array_equal(_bits(A2), _bits(A))
+        assert np.array_equal(bits(E2), bits(E)) and np.array_equal(bits(A2), bits(A))
     # without tc: today's files, byte for byte (versions 1 and 2), and read back with tc False
     for lam, version in ((0.0, 1), (0.5, 2)):
         nt.write_checkpoint(tmp_path / "a.npz", w, tuples, lam=lam, **scalars)
@@ -299,15 +198,7 @@ def test_checkpoint_version_4(tmp_path):
 def test_tc_kernels_use_no_scratch():
     """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_tc.hip with the Makefile's flags: five kernels -- the scatter text's four forms with
     the third accumulator and the apply -- none with scratch or a spilled vector register.  VGPRs as built: scatter 59 / 20, apply 41."""
-    names, vgprs, scratch, spills = resource_usage("ntuple-tc-resource-usage")
-    assert len(names) == 5 and sum("tfe_nt_scatter_kernel" in n for n in names) == 4 and sum("tfe_nt_tc_apply_kernel" in n for n in names) == 1
+    names = assert_no_scratch("ntuple-tc-resource-usage", {"tfe_nt_scatter_kernel": 4, "tfe_nt_tc_apply_kernel": 1}, 128)
     assert all("Lb1EEE" in n for n in names if "tfe_nt_scatter_kernel" in n)        # every one of the four has Abs = true
-    assert scratch == [0] * 5 and spills == [0] * 5 and len(vgprs) == 5 and max(vgprs) <= 128
-    sgpr_spills = re.findall(r"SGPRs Spill: (\d+)", _remarks("ntuple-tc-resource-usage"))
+    sgpr_spills = re.findall(r"SGPRs Spill: (\d+)", remarks("ntuple-tc-resource-usage"))
     assert sgpr_spills == ["0"] * 5
-
-
-def _remarks(target):
-    import subprocess
-    from tests.native_args import CSRC
-    return subprocess.run(["make", "-s", "-C", str(CSRC), target], capture_output=True, text=True).stderr

@@ -3,7 +3,7 @@ pulse_tfe_nt_learn_tc, pulse_tfe_nt_apply_tc) against the host's statement of th
 device's own recorded games.  Every comparison is exact: the three accumulators, the counters and tc_stats as integers, the weights as
 float32 bit patterns, E and A as float64 bit patterns.  Every buffer a launch is handed sits between guard words.
 
-Shape: test_tfe_nt_lambda_gpu.py's regime -- 257 games (one full workgroup of the adds and one of one lane), max_steps 256, epsilon
+Shape: the learners' regime (tests/tfe_nt_support.py) -- 257 games (one full workgroup of the adds and one of one lane), max_steps 256, epsilon
 .25, seed 457, board_id0 3000 -- on the tuples (0, 1, 2, 3) and (15,): 65,552 weights, so that most visited weights are visited in
 every round and rho leaves 1.  Three rounds per setting, played once and shared; the host's E and A are carried by the host from zero,
 the weights a round starts from are the device's."""
@@ -12,67 +12,30 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_tfe_nt_tc_cpu import STEP_SIZE, tc_worked, tc_worked_state
-from tests.tfe_gpu_support import PATTERNS, guard, guards_intact, rollout
+from tests.tfe_gpu_support import guards_intact
+from tests.tfe_nt_support import GAMES, ROUNDS, STEP_SIZE, bits, learner_agent, learner_round, plain_learner, tc_worked, tc_worked_state
 
 pytestmark = pytest.mark.gpu
 
-GAMES, MAX_STEPS, ROUNDS, EPSILON = 257, 256, 3, .25
 TUPLES = ((0, 1, 2, 3), (15,))
-SEED, BOARD_ID0 = 457, 3000
-BUFFERS = ("weights_dev", "acc", "keys", "values", "steps", "lengths", "total_score", "episode_reward", "counters", "_eval", "acc_abs", "E", "A", "tc_stats")
-PER_MOVE = ("keys", "values", "steps")
 SETTINGS = {"td0": dict(lam=0.0), "lambda": dict(lam=0.5), "td0-plain": dict(lam=0.0, symmetric=False), "lambda-plain": dict(lam=0.5, symmetric=False),
             "td0-gamma": dict(lam=0.0, gamma=0.9), "lambda-gamma": dict(lam=0.5, gamma=0.9)}
+_plain = functools.partial(plain_learner, tuples=TUPLES, tc=True)
+_agent = functools.partial(learner_agent, extra_buffers=("acc_abs", "E", "A", "tc_stats", "deltas"), tuples=TUPLES, tc=True)
 
 
-def _bits(x):
-    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+def _round(a, host_E, host_A):
+    """learner_round with this file's verdicts: the third accumulator, tc_stats' differences against the host's (moved, rho sum), and
+    E and A against host_E / host_A, the host's own, advanced in place"""
+    def after_learn(a, h):
+        h.tc_before = a.tc_stats.cpu().numpy().copy()
+        return dict(abs_equal=np.array_equal(h.acc_abs, h.host_abs), abs_any=bool(h.acc_abs.any()), abs_bounds=bool((h.acc_abs >= np.abs(h.acc[:, 0])).all()))
 
-
-def _plain(n_games=GAMES, **kw):
-    import torch
-    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
-    kw = dict(dict(tuples=TUPLES, epsilon=EPSILON, max_steps=MAX_STEPS, seed=SEED, board_id0=BOARD_ID0, tc=True), **kw)
-    return NTupleTDAfterstateTFEGPU(torch.device("cuda:0"), n_games, **kw)
-
-
-def _agent(n_games=GAMES, **kw):
-    """The tc agent with every device buffer re-seated between guard words; keys / values / steps pre-filled with a pattern."""
-    a = _plain(n_games, **kw)
-    a = guard(a, BUFFERS + (("deltas",) if a.deltas is not None else ()), **PATTERNS)
-    assert a.acc.data_ptr() % 16 == 0 and all(getattr(a, k).data_ptr() % 8 == 0 for k in ("acc_abs", "E", "A", "tc_stats"))
-    return a
-
-
-def _one_round(a, host_E, host_A):
-    """A round on the device -- roll-out, learn, apply -- with the learn and the apply launch held to the host's on the device's own
-    records; host_E / host_A are the host's own, advanced in place."""
-    from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-    policy = a.weights()
-    got = rollout(a, PER_MOVE)
-    before = a.stats()
-    a.learn()
-    acc, acc_abs, st = a.acc.cpu().numpy(), a.acc_abs.cpu().numpy(), a.stats()
-    L = got["lengths"].astype(np.int64)
-    last = got["steps"][np.minimum(L, a.max_steps) - 1, np.arange(a.n_games)]
-    host_acc, host_abs = np.zeros_like(acc), np.zeros_like(acc_abs)
-    host = nt.learn_tc_nt_on_host(got["keys"], got["values"].view(np.float64), got["steps"], L, a.tuples, a.symmetric, a.gamma, a.lam, host_acc, host_abs)
-    host.pop("deltas", None)
-    rec = dict(ended=int((last >> 7 != 0).sum()), cut=int((last >> 7 == 0).sum()), host=host, acc_equal=np.array_equal(acc, host_acc),
-               abs_equal=np.array_equal(acc_abs, host_abs), abs_any=bool(acc_abs.any()), abs_bounds=bool((acc_abs >= np.abs(acc[:, 0])).all()),
-               visited=int((acc[:, 1] > 0).sum()), stats={k: st[k] - before[k] for k in ("learnt", "skipped", "clamped")},
-               values_any=bool(got["values"].view(np.float64)[np.arange(a.max_steps)[:, None] < L[None, :]].any()))
-    tc_before = a.tc_stats.cpu().numpy().copy()
-    a.apply()
-    host_w = policy.copy()
-    rec["host_tc"] = nt.apply_tc_nt_on_host(host_w, host_acc, host_abs, host_E, host_A, a.alpha / a.n_features)
-    E, A = a.coherence()
-    rec.update(tc=tuple((a.tc_stats.cpu().numpy() - tc_before).tolist()), weights_equal=np.array_equal(a.weights().view(np.uint32), host_w.view(np.uint32)),
-               E_equal=np.array_equal(_bits(E), _bits(host_E)), A_equal=np.array_equal(_bits(A), _bits(host_A)),
-               acc_zero=not bool(a.acc.any().item()) and not bool(a.acc_abs.any().item()), coherent=bool((np.abs(E) <= A).all()))
-    a.round += 1
-    return rec
+    def after_apply(a, h):
+        E, A = a.coherence()
+        return dict(host_tc=h.host_tc, tc=tuple((a.tc_stats.cpu().numpy() - h.tc_before).tolist()), E_equal=np.array_equal(bits(E), bits(host_E)),
+                    A_equal=np.array_equal(bits(A), bits(host_A)), coherent=bool((np.abs(E) <= A).all()))
+    return learner_round(a, after_learn, after_apply, coherence=(host_E, host_A))
 
 
 @functools.lru_cache(maxsize=None)
@@ -84,7 +47,7 @@ def _rounds(setting):
         a.weights_dev.copy_(torch.from_numpy((np.random.default_rng(19).standard_normal(a.n_weights) * 3).astype(np.float32)))
     first = a.weights()
     E, A = np.zeros(a.n_weights), np.zeros(a.n_weights)
-    out = [_one_round(a, E, A) for _ in range(ROUNDS)]
+    out = [_round(a, E, A) for _ in range(ROUNDS)]
     guards_intact(a)
     return a, out, first
 
@@ -165,7 +128,7 @@ def test_launches_allocate_on_first_use():
 
 
 def test_hand_made_buffers():
-    """test_tfe_nt_tc_cpu's two hand-worked rounds copied into an agent of 3 games and 3 moves: the clamp, the cut game's skipped move,
+    """the two hand-worked rounds (tests/tfe_nt_support.py: tc_worked) copied into an agent of 3 games and 3 moves: the clamp, the cut game's skipped move,
     a game of length 0, a turned sign (rho = 11 / 32,787), a weight seen in round 1 only and one whose A is still 0"""
     import torch
     a = _agent(3, tuples=((0, 3),), max_steps=3, gamma=1.0, epsilon=0.0)
@@ -186,7 +149,7 @@ def test_hand_made_buffers():
         a.tc_stats.zero_()
         E, A = a.coherence()
         assert np.array_equal(a.weights().view(np.uint32), want_w.view(np.uint32)), r
-        assert np.array_equal(_bits(E), _bits(want_E)) and np.array_equal(_bits(A), _bits(want_A)), r
+        assert np.array_equal(bits(E), bits(want_E)) and np.array_equal(bits(A), bits(want_A)), r
         assert not a.acc.any().item() and not a.acc_abs.any().item(), r
     guards_intact(a)
 
@@ -209,9 +172,9 @@ def test_untouched_weights_keep_their_state():
     moved, rho_sum = nt.apply_tc_nt_on_host(w, acc, acc_abs, E, A, a.alpha / a.n_features)
     assert 100 < moved == a.n_weights - int(rest.sum()) and int(rest.sum()) > 1000
     got_E, got_A = a.coherence()
-    assert (_bits(got_E)[rest] == _bits([-3.5])[0]).all() and (_bits(got_A)[rest] == _bits([7.25])[0]).all()
+    assert (bits(got_E)[rest] == bits([-3.5])[0]).all() and (bits(got_A)[rest] == bits([7.25])[0]).all()
     assert (a.weights().view(np.uint32)[rest] == np.float32(-1.5).view(np.uint32)).all()
-    assert np.array_equal(_bits(got_E), _bits(E)) and np.array_equal(_bits(got_A), _bits(A)) and np.array_equal(a.weights().view(np.uint32), w.view(np.uint32))
+    assert np.array_equal(bits(got_E), bits(E)) and np.array_equal(bits(got_A), bits(A)) and np.array_equal(a.weights().view(np.uint32), w.view(np.uint32))
     assert tuple(a.tc_stats.cpu().tolist()) == (moved, rho_sum, 0, 0) and rho_sum == moved * int(np.rint(np.ldexp(3.5 / 7.25, 32)))
     guards_intact(a)
 
@@ -231,7 +194,7 @@ def test_save_and_load_continue_the_run(tmp_path):
     c.learn_batch()
     assert c.round == a.round == 3 and np.array_equal(c.weights().view(np.uint32), a.weights().view(np.uint32))
     for x, y in zip(c.coherence(), a.coherence()):
-        assert np.array_equal(_bits(x), _bits(y)) and x.any()
+        assert np.array_equal(bits(x), bits(y)) and x.any()
     plain = _plain(tc=False)
     plain.learn_batch().save(tmp_path / "plain.npz")
     f = nt.read_checkpoint(tmp_path / "plain.npz")
