@@ -949,6 +949,22 @@ int pulse_tfe_nt_evaluate_search(const PulseTfeNtEval* o, void* stream);
 int pulse_tfe_nt_search_deep(const PulseTfeNtSearch* o, int32_t layers, void* stream);
 int pulse_tfe_nt_evaluate_search_deep(const PulseTfeNtEval* o, int32_t layers, void* stream);
 
+/* ---- ... and in the training roll-out: pulse_tfe_nt_rollout's games under the search policy.  The roll-out's struct, with the depth
+ * beside it.  Everything is pulse_tfe_nt_rollout's -- the boards board_id0 + g, the three Philox streams, the epsilon branch and its
+ * uniform action, the cap at a 32,768 tile, max_steps, the counters stats[0] (moves) and stats[3] (games cut), the per-game arrays
+ * and the rows at and beyond a game's length, which are not written -- except the q the greedy scan reads: those of the definitions
+ * above at `layers` chance layers, on the same tie coins (tie_seed, the board's key, round).  What a move records is unchanged too:
+ *   keys[t, g]   = the chosen afterstate B_a;
+ *   values[t, g] = V(B_a) of the NETWORK (tuple-major, image-minor, one rounding per add), not the search's q_a or E_a;
+ *   steps[t, g]  = the action, the reward and the game-over bit.
+ * So pulse_tfe_nt_learn, pulse_tfe_nt_learn_lambda and pulse_tfe_nt_learn_tc read the records as they read pulse_tfe_nt_rollout's: the
+ * target of a move is the reward and V of the next move the search chose.  At gamma = 0 the records are pulse_tfe_nt_rollout's.
+ * One game per group of 32 lanes at layers = 1 and per workgroup of 256 at layers = 2, as the evaluations above play theirs.
+ *
+ * PULSE_EINVAL, before anything is launched: what pulse_tfe_nt_rollout refuses, under this name; `layers` other than 1 or 2
+ * ("layers must be 1 or 2"). */
+int pulse_tfe_nt_rollout_search(const PulseTfeNtRollout* o, int32_t layers, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

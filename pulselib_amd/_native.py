@@ -267,6 +267,7 @@ SYMBOLS = {
     "pulse_tfe_nt_evaluate_search": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_search_deep": (C.c_int, [_P, _I32, _P]),
     "pulse_tfe_nt_evaluate_search_deep": (C.c_int, [_P, _I32, _P]),
+    "pulse_tfe_nt_rollout_search": (C.c_int, [_P, _I32, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

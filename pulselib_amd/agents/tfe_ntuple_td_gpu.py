@@ -10,7 +10,8 @@ recorded move and adds the temporal difference reward' + gamma * V' - V (0 - V a
 {sum, cnt} of every weight the afterstate reads; `pulse_tfe_nt_apply` moves every visited weight by alpha / F of the MEAN of its
 adds and zeroes the accumulators.  `pulse_tfe_nt_evaluate` plays games without a trajectory and reduces the scores in the launch; `pulse_tfe_nt_search` and
 `pulse_tfe_nt_evaluate_search` play under expectimax search one chance layer deep (section 13.1), 32 lanes per board; with `layers=2`
-`pulse_tfe_nt_search_deep` and `pulse_tfe_nt_evaluate_search_deep` search two (section 13.4), 256 lanes per board.  With `lam > 0`
+`pulse_tfe_nt_search_deep` and `pulse_tfe_nt_evaluate_search_deep` search two (section 13.4), 256 lanes per board; with the attribute `rollout_layers` = 1 or 2 the
+round's games themselves are played under that search, `pulse_tfe_nt_rollout_search` (section 13.5), and recorded alike.  With `lam > 0`
 the learn launch is `pulse_tfe_nt_learn_lambda` (section 13.2): one lane per game walks the recorded game backwards and leaves the
 lambda-differences D_t = delta_t + gamma * lam * D_{t+1} in `deltas`, and the same one-lane-per-move adds follow with D_t for delta_t.
 
@@ -164,6 +165,14 @@ def check_layers(layers) -> int:
     """The search's depth in chance layers as an int: 1 or 2 (ValueError otherwise), as the library checks it."""
     if isinstance(layers, bool) or layers not in (1, 2):
         raise ValueError("layers must be 1 or 2")
+    return int(layers)
+
+
+def check_rollout_layers(layers) -> int:
+    """The depth of the search a training roll-out plays under, as an int: 0 (none: the one-ply roll-out, pulse_tfe_nt_rollout), 1 or 2
+    chance layers (pulse_tfe_nt_rollout_search).  ValueError otherwise; a bool is no depth."""
+    if isinstance(layers, bool) or layers not in (0, 1, 2):
+        raise ValueError("rollout_layers must be 0, 1 or 2")
     return int(layers)
 
 
@@ -429,8 +438,12 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     board_id0 + r * n_games + g, so no two rounds replay the same spawns.  `lam` > 0: `learn` is the TD(lambda) launch and the agent
     holds `deltas`, float64 in the shape of `values`; `lam` = 0 (the default) allocates nothing more and learns by TD(0).  `tc`:
     temporal-coherence step sizes (section 13.3): `learn` is pulse_tfe_nt_learn_tc under the agent's `lam`, `apply` is
-    pulse_tfe_nt_apply_tc, and the agent holds `acc_abs`, `E`, `A` and `tc_stats`; without it (the default) none of them exists."""
+    pulse_tfe_nt_apply_tc, and the agent holds `acc_abs`, `E`, `A` and `tc_stats`; without it (the default) none of them exists.
+    `rollout_layers` (an attribute, 0 by default; section 13.5): 1 or 2 and `rollout`, so `learn_batch`, plays its games under
+    expectimax search that many chance layers deep and records them as before; it is how rounds are played, not part of the network,
+    so no checkpoint holds it."""
     STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
+    rollout_layers = 0                                                     # set on the agent; checked at the launch (check_rollout_layers)
 
     def __init__(self, device, n_games, tuples=DEFAULT_TUPLES, symmetric=True, gamma=1.0, epsilon=0.0, alpha=1.0, max_steps=4096, seed=0,
                  board_id0=0, lam=0.0, tc=False):
@@ -459,15 +472,29 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
                 net.cells[t][i] = c
         net.n_weights, net.weights = self.n_weights, self.weights_dev.data_ptr()
 
-    def rollout(self):
-        """One launch: n_games games under the weights as they stand (round `self.round`), into keys / values / steps / lengths /
-        scores."""
+    def _rollout_struct(self):
         o = self._draws(_native.TfeNtRollout(), self.round_board_id0())
         self._net(o.net)
         o.n_games, o.max_steps, o.gamma, o.epsilon = self.n_games, self.max_steps, self.gamma, self.epsilon
         o.keys, o.values, o.steps, o.lengths = self.keys.data_ptr(), self.values.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr()
         o.total_score, o.episode_reward, o.stats = self.total_score.data_ptr(), self.episode_reward.data_ptr(), self.counters.data_ptr()
-        return self._launch("pulse_tfe_nt_rollout", o)
+        return o
+
+    def rollout(self, layers=None):
+        """One launch: n_games games under the weights as they stand (round `self.round`), into keys / values / steps / lengths /
+        scores.  layers (None: the agent's `rollout_layers`) = 0: pulse_tfe_nt_rollout, greedy on reward + gamma * V; 1 or 2:
+        rollout_search_launch, greedy on the q of the search that deep.  ValueError for any other."""
+        layers = check_rollout_layers(self.rollout_layers if layers is None else layers)
+        if layers:
+            return self.rollout_search_launch(layers)
+        return self._launch("pulse_tfe_nt_rollout", self._rollout_struct())
+
+    def rollout_search_launch(self, layers):
+        """pulse_tfe_nt_rollout_search alone, whatever the agent's `rollout_layers`: the roll-out's games, draws and records with the
+        greedy action taken on the q of expectimax search `layers` chance layers deep (1 or 2; ValueError for any other).  `values`
+        holds the network's V of the chosen afterstates, so the learners read the records as they read rollout()'s."""
+        layers = check_layers(layers)
+        return self._launch("pulse_tfe_nt_rollout_search", self._rollout_struct(), layers)
 
     def _moves(self, o):
         """The network and the fields the two learners' structs share."""
@@ -646,7 +673,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         return out
 
     def save(self, path):
-        """The non-zero weights and what a continued run needs as an .npz (write_checkpoint); with tc, E and A too."""
+        """The non-zero weights and what a continued run needs as an .npz (write_checkpoint); with tc, E and A too.  `rollout_layers`
+        is not saved: it says how rounds are played, not what the network is."""
         write_checkpoint(path, self.weights(), self.tuples, symmetric=int(self.symmetric), gamma=self.gamma, epsilon=self.epsilon, alpha=self.alpha,
                          max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games, lam=self.lam,
                          tc=self.coherence() if self.tc else None)
@@ -654,7 +682,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     @classmethod
     def load(cls, path, device, n_games=None):
         """The agent save() wrote: weights, round, seeds, lam, tc and with it E and A restored.  With the saved n_games it continues the run the saved agent would
-        have continued (another n_games plays other boards: round r starts at board_id0 + r * n_games)."""
+        have continued (another n_games plays other boards: round r starts at board_id0 + r * n_games).  `rollout_layers` is 0, whatever the saved
+        agent played under: set it again to continue rounds under search."""
         import torch
         f = read_checkpoint(path)
         agent = cls(device, f["n_games"] if n_games is None else n_games, tuples=f["tuples"], symmetric=f["symmetric"], gamma=f["gamma"],

@@ -123,6 +123,27 @@ void launch_scatter(const Moves& m, const NtDev& dev, bool symmetric, void* stre
     }
 }
 
+int check_rollout(const PulseTfeNtRollout* o, const char* name, NtDev* dev, Games* g) {
+    if (!o) return fail_named(name, "options are null");
+    if (int rc = check_net(o->net, true, name, dev)) return rc;
+    if (int rc = check_batch(o, name)) return rc;
+    if (!(o->epsilon >= 0.0 && o->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
+    if (!o->keys) return fail_named(name, "keys is null");
+    if (!o->values) return fail_named(name, "values is null");
+    if (!o->steps) return fail_named(name, "steps is null");
+    if (!o->lengths) return fail_named(name, "lengths is null");
+    if (!o->total_score) return fail_named(name, "total_score is null");
+    if (!o->episode_reward) return fail_named(name, "episode_reward is null");
+    if (!o->stats) return fail_named(name, "stats is null");
+    if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->values & 7u) || ((uintptr_t)o->total_score & 7u) || ((uintptr_t)o->stats & 7u))
+        return fail_named(name, "keys / values / total_score / stats must be 8-byte aligned");
+    if (((uintptr_t)o->lengths & 3u) || ((uintptr_t)o->episode_reward & 3u)) return fail_named(name, "lengths / episode_reward must be 4-byte aligned");
+    *g = games_of(o);
+    g->keys = o->keys; g->values = o->values; g->steps = o->steps; g->lengths = o->lengths; g->total_score = o->total_score;
+    g->episode_reward = o->episode_reward; g->stats = o->stats;
+    return 0;
+}
+
 int check_eval(const PulseTfeNtEval* o, const char* name, NtDev* dev, Games* g) {
     if (!o) return fail_named(name, "options are null");
     if (int rc = check_net(o->net, true, name, dev)) return rc;
@@ -141,25 +162,9 @@ int check_eval(const PulseTfeNtEval* o, const char* name, NtDev* dev, Games* g) 
 }  // namespace pulse_tfe
 
 extern "C" int pulse_tfe_nt_rollout(const PulseTfeNtRollout* o, void* stream) {
-    const char* name = "pulse_tfe_nt_rollout";
-    if (!o) return fail_named(name, "options are null");
     NtDev dev;
-    if (int rc = check_net(o->net, true, name, &dev)) return rc;
-    if (int rc = check_batch(o, name)) return rc;
-    if (!(o->epsilon >= 0.0 && o->epsilon <= 1.0)) return fail_named(name, "epsilon must be in [0, 1]");
-    if (!o->keys) return fail_named(name, "keys is null");
-    if (!o->values) return fail_named(name, "values is null");
-    if (!o->steps) return fail_named(name, "steps is null");
-    if (!o->lengths) return fail_named(name, "lengths is null");
-    if (!o->total_score) return fail_named(name, "total_score is null");
-    if (!o->episode_reward) return fail_named(name, "episode_reward is null");
-    if (!o->stats) return fail_named(name, "stats is null");
-    if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->values & 7u) || ((uintptr_t)o->total_score & 7u) || ((uintptr_t)o->stats & 7u))
-        return fail_named(name, "keys / values / total_score / stats must be 8-byte aligned");
-    if (((uintptr_t)o->lengths & 3u) || ((uintptr_t)o->episode_reward & 3u)) return fail_named(name, "lengths / episode_reward must be 4-byte aligned");
-    Games g = games_of(o);
-    g.keys = o->keys; g.values = o->values; g.steps = o->steps; g.lengths = o->lengths; g.total_score = o->total_score;
-    g.episode_reward = o->episode_reward; g.stats = o->stats;
+    Games g;
+    if (int rc = check_rollout(o, "pulse_tfe_nt_rollout", &dev, &g)) return rc;
     if (int rc = launch_games(g, dev, o->net.symmetric != 0, true, stream)) return rc;
     return finish_launch("pulse_tfe_nt_rollout launch");
 }

@@ -1,5 +1,5 @@
 // tfe_ntuple_device.h -- what the units of the 2048 n-tuple network share (tfe_ntuple.hip: the learner's four launches; tfe_ntuple_search.hip:
-// expectimax play, and tfe_ntuple_search_deep.hip, two chance layers of it; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes): the network as the
+// expectimax play, tfe_ntuple_search_deep.hip, two chance layers of it, and tfe_ntuple_search_rollout.hip, the roll-out under either; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes): the network as the
 // kernels take it, a feature's index, V of four afterstates at once, the learners' target, fixed-point difference and adds, their
 // parameters (Moves), shared refusals (check_moves), scatter kernel and launches, the four moves of a board, the greedy action, the game loop (play_game) with its parameters
 // (Games) and the host's checks of the network, of the accumulators and of a batch of games.  One copy each.  Not part of the ABI.
@@ -222,6 +222,10 @@ void launch_scatter(const Moves& m, const NtDev& dev, bool symmetric, void* stre
 // ... and the launch of the TD(lambda) walk, which leaves D_t in o.deltas (defined in tfe_ntuple_lambda.hip, where the kernel is): of
 // `o` it reads n_games, max_steps, gamma, lambda, values, steps, lengths and deltas
 void launch_lambda_walk(const PulseTfeNtLearnLambda& o, void* stream);
+
+// what pulse_tfe_nt_rollout and pulse_tfe_nt_rollout_search refuse, and the game loop's parameters of a recording launch (defined in
+// tfe_ntuple.hip)
+int check_rollout(const PulseTfeNtRollout* o, const char* name, NtDev* dev, Games* g);
 
 // what pulse_tfe_nt_evaluate and pulse_tfe_nt_evaluate_search refuse, and the game loop's parameters of an evaluation (defined in
 // tfe_ntuple.hip)

@@ -9,7 +9,9 @@ under expectimax search one chance layer deep (section 13.1) on the same boards,
 --search` plays a saved network; `--search --layers 2` searches two chance layers deep (section 13.4).  `--lambda L` (0 < L <= 1) learns by TD(lambda) (section 13.2): the learn launch walks every game
 backwards first and adds lambda-differences; the run's first line names it, and `--resume` takes it from the file.  `--tc` learns with temporal-coherence
 step sizes (section 13.3): every weight moves by rho = |E| / A of the step, from the running sums of its errors; the round's mean rho
-is printed beside the round's counters, and `--resume` takes `tc` from the file too."""
+is printed beside the round's counters, and `--resume` takes `tc` from the file too.  `--train-layers L` (1 or 2; section 13.5) plays the
+rounds' own games under expectimax search L chance layers deep, recorded and learnt from as before; every round's line carries the mean
+score and length of the games it trained on; no checkpoint holds the option, so `--resume` needs it given again."""
 from __future__ import annotations
 
 import argparse
@@ -21,7 +23,7 @@ from ..agents import NTupleTDAfterstateTFEGPU
 
 
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
-        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1):
+        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0):
     if resume:
         agent = NTupleTDAfterstateTFEGPU.load(resume, device)
         want = dict(n_games=tables, alpha=float(alpha), epsilon=float(epsilon), gamma=float(gamma), max_steps=max_steps, seed=seed)
@@ -30,8 +32,9 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
             raise ValueError(f"{resume} continues another run: (saved, asked) {differ}")
     else:
         agent = NTupleTDAfterstateTFEGPU(device, tables, gamma=gamma, epsilon=epsilon, alpha=alpha, max_steps=max_steps, seed=seed, lam=lam, tc=tc)
+    agent.rollout_layers = train_layers                                     # (no checkpoint holds it: given again on --resume)
     out(f"{agent.n_games} games per round from round {agent.round}: alpha {agent.alpha}, epsilon {agent.epsilon}, gamma {agent.gamma}, "
-        f"lambda {agent.lam}, tc {agent.tc}, max_steps {agent.max_steps}, seed {agent.seed}")
+        f"lambda {agent.lam}, tc {agent.tc}, max_steps {agent.max_steps}, seed {agent.seed}, roll-out under {agent.rollout_layers} chance layers of search")
     first, moves_before, t0 = agent.round, agent.stats()["moves"], time.perf_counter()
 
     def under_search():
@@ -55,7 +58,7 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
             st, now = agent.stats(), time.perf_counter()
             rho = f", mean rho {agent.tc_summary()['mean_rho']:.4f}" if agent.tc else ""       # (of the applies since the last line)
             out(f"Round {r}: {line}; "
-                f"training: Avg final score {agent.total_score.double().mean().item():.1f}, moves/sec {(st['moves'] - moves_before) / (now - t0):.0f}, "
+                f"training: Avg final score {agent.total_score.double().mean().item():.1f}, Avg length {agent.lengths.double().mean().item():.1f}, moves/sec {(st['moves'] - moves_before) / (now - t0):.0f}, "
                 f"skipped {st['skipped']}, clamped {st['clamped']}{rho}{under_search()}")
             moves_before, t0 = st["moves"], time.perf_counter()
     if save:
@@ -81,9 +84,11 @@ def main(argv=None):
     ap.add_argument("--resume", metavar="PATH", help="continue the run saved there (the same --tables, --alpha, --epsilon, --gamma, --max-steps, --seed)")
     ap.add_argument("--search", action="store_true", help="every evaluation also under expectimax search, one chance layer deep")
     ap.add_argument("--layers", type=int, default=1, choices=[1, 2], help="with --search: the chance layers the search looks ahead")
+    ap.add_argument("--train-layers", type=int, default=0, choices=[0, 1, 2],
+                    help="the chance layers of search the rounds' own games are played under (0: the one-ply roll-out); not saved: give it again with --resume")
     args = ap.parse_args(argv)
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
-                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers)
+                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers)
     st = agent.stats()
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
           f"{int((agent.weights_dev != 0).sum().item())} of {agent.n_weights} weights are not zero")

@@ -23,7 +23,12 @@ accumulators are zeroed, untimed, before every launch, so both add the same move
 (pulse_tfe_nt_learn, then pulse_tfe_nt_apply on what it added) and the temporal-coherence pair (pulse_tfe_nt_learn_tc, then
 pulse_tfe_nt_apply_tc), with --lambda L also pulse_tfe_nt_learn_lambda beside pulse_tfe_nt_learn_tc at L; every launch
 between its own pair of HIP events, the accumulators zeroed (untimed) before every learn launch; the weights are put back and E and
-A zeroed afterwards.  max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes).  Lines are also
+A zeroed afterwards.  --train-layers L (1 or 2): per B one more line, {"train_rollout": ...}: on the weights the rounds left, the recording
+launch under search L chance layers deep (pulse_tfe_nt_rollout_search) and, alternating with it in the same
+process, the evaluation launch under the same policy on the same boards, weights and epsilon, each between its own pair of HIP events;
+the ratio of the medians, the evaluation's own spread (max / min) beside it, and the yardstick by count: 1 + 1 / (the mean number of
+candidate moves per board), counted on the host over 32 games played under that policy, and whether the ratio is within it + 50 %.
+max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes).  Lines are also
 appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
 import argparse
 import json
@@ -63,16 +68,17 @@ def _timed_evaluate(agent, torch):
     return ev[0].elapsed_time(ev[1]) * 1e-3, agent.eval_counters()
 
 
-def children_per_move(agent, torch, sample, max_moves):
+def children_per_move(agent, torch, sample, max_moves, layers=2):
     """The mean number of one-layer searches a two-layer move makes: `sample` games from the default evaluation boards played through
     the environment's own launches under the two-layer policy (agent.search(layers=2), greedy), and on every board met, counted on the
-    host from the moves' masks, the live children: 2 * n_empty(B_a) summed over the candidate moves a.  Stops after max_moves moves."""
+    host from the moves' masks, the live children: 2 * n_empty(B_a) summed over the candidate moves a.  Stops after max_moves moves.
+    Beside it candidates_per_move, the mean number of candidate moves of those boards; layers = 1: the games of the one-layer policy."""
     import numpy as np
     from pulselib_amd.agents.tfe_ntuple_td_gpu import moves_on_host
     from pulselib_amd.environments.TFE.TFE import TFEBatch
     env = TFEBatch(agent.device, sample, 4, seed=agent.env_seed, board_id0=agent.eval_board_id0())
     boards, _ = env.reset()
-    live, children, moves = np.ones(sample, dtype=bool), 0, 0
+    live, children, candidates, moves = np.ones(sample, dtype=bool), 0, 0, 0
     shifts = np.uint64(4) * np.arange(16, dtype=np.uint64)
     for _ in range(max_moves):
         cells = boards.cpu().numpy().reshape(sample, 16).astype(np.int64)
@@ -82,12 +88,43 @@ def children_per_move(agent, torch, sample, max_moves):
         n_empty = (((after[:, :, None] >> shifts) & np.uint64(15)) == 0).sum(axis=2)
         per_board = (2 * n_empty * (after != keys[:, None])).sum(axis=1)
         children, moves = children + int(per_board[live].sum()), moves + int(live.sum())
-        action = agent.search(keys, layers=2)["action"].astype(np.int64)
+        candidates += int((after != keys[:, None])[live].sum())
+        action = agent.search(keys, layers=layers)["action"].astype(np.int64)
         boards, _, dones, _, _ = env.step(torch.from_numpy(np.maximum(action, 0)))
         live &= ~dones.cpu().numpy() & (action >= 0)
         if not live.any():
             break
-    return {"sample_games": sample, "sample_moves": moves, "children_per_move": children / max(moves, 1)}
+    return {"sample_games": sample, "sample_moves": moves, "children_per_move": children / max(moves, 1),
+            "candidates_per_move": candidates / max(moves, 1)}
+
+
+def train_rollout_line(agent, torch, layers, warmup, repeats):
+    """the recording launch under search and the evaluation launch under the same policy, on the boards of the agent's next round"""
+    board_id0, before = agent.round_board_id0(), agent.stats()
+    launches = (("rollout_search", lambda: agent.rollout_search_launch(layers)),
+                ("evaluate_search", lambda: agent.evaluate_search_launch(epsilon=agent.epsilon, board_id0=board_id0, layers=layers)))
+    seconds = {name: [] for name, _ in launches}
+    for i in range(warmup + repeats):
+        for name, launch in launches:
+            agent.eval_counters(clear=True)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            launch()
+            ev[1].record()
+            ev[1].synchronize()
+            if i >= warmup:
+                seconds[name].append(ev[0].elapsed_time(ev[1]) * 1e-3)
+    e, st = agent.eval_counters(), agent.stats()
+    moves = (st["moves"] - before["moves"]) // (warmup + repeats)
+    ro, ev_s = _spread(seconds["rollout_search"]), _spread(seconds["evaluate_search"])
+    count = children_per_move(agent, torch, 32, agent.max_steps, layers)
+    ratio, yardstick = ro["median"] / ev_s["median"], 1.0 + 1.0 / count["candidates_per_move"]
+    return {"train_rollout": {"games": agent.n_games, "layers": layers, "epsilon": agent.epsilon, "trained_rounds": agent.round, "max_steps": agent.max_steps,
+                              "warmup": warmup, "repeats": repeats, "moves": moves, "evaluate_moves": e["moves"], "rollout_search_s": ro,
+                              "evaluate_search_s": ev_s, "ratio": ratio, "evaluate_spread": ev_s["max"] / ev_s["min"], **count,
+                              "yardstick_by_count": yardstick, "ratio_over_yardstick": ratio / yardstick, "within_margin": ratio <= 1.5 * yardstick,
+                              "mean_length": moves / agent.n_games, "mean_final_score": agent.total_score.double().mean().item(),
+                              "record_bytes": 17 * moves}}
 
 
 def search_line(agent, torch, games, repeats, layers=1):
@@ -230,6 +267,7 @@ def main(argv=None):
     ap.add_argument("--layers", type=int, default=1, choices=[1, 2], help="with --search, 2: the two-layer evaluation and its child count beside the other two")
     ap.add_argument("--lambda", dest="lam", type=float, help="one more line per B: the TD(lambda) learn launch beside the TD(0) one, on the same games")
     ap.add_argument("--tc", action="store_true", help="one more line per B: the temporal-coherence learn and apply launches beside the fixed-step ones")
+    ap.add_argument("--train-layers", type=int, choices=[1, 2], help="one more line per B: the recording launch under search beside the evaluation under it")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
     args = ap.parse_args(argv)
     import torch
@@ -253,6 +291,8 @@ def main(argv=None):
                 lines.append(lambda_line(agent, torch, args.lam, args.warmup, args.repeats))
             if args.tc:                                                     # likewise
                 lines.append(tc_line(agent, torch, args.lam, args.warmup, args.repeats))
+            if args.train_layers:                                           # on the weights the last state left
+                lines.append(train_rollout_line(agent, torch, args.train_layers, args.warmup, args.repeats))
             del agent
             torch.cuda.empty_cache()
         for line in lines:
