@@ -965,6 +965,52 @@ int pulse_tfe_nt_evaluate_search_deep(const PulseTfeNtEval* o, int32_t layers, v
  * ("layers must be 1 or 2"). */
 int pulse_tfe_nt_rollout_search(const PulseTfeNtRollout* o, int32_t layers, void* stream);
 
+/* ---- ... and learning towards the value the search backed up.  Opt-in: a caller that never calls these two keeps every launch above
+ * unchanged.  Everything is float64, one rounding per operation.
+ *
+ * pulse_tfe_nt_rollout_backed: pulse_tfe_nt_rollout_search's games and records, word for word, and one more word per move.  Let
+ * q[0..3] be the search's q of the board before move t (the definitions above at `layers`):
+ *   backed[t, g] = the largest q[a] over the candidate moves (B_a != B), scanned a = 0..3: the first candidate starts, a strictly
+ *                  larger q replaces it.  A maximum: no tie coin enters.  It is formed on every move, the epsilon branch included,
+ *                  and does not depend on the action taken; at epsilon = 0 it is the q of the action taken.
+ * backed: device float64[max_steps * n_games], step-major like values; rows at and beyond a game's length are not written.
+ *
+ * pulse_tfe_nt_learn_backed: pulse_tfe_nt_learn_lambda with another one-step difference.  V_t = values[t, g] estimates the value of
+ * the board after the next spawn; backed[t + 1] is the search's estimate for the spawn that happened, r_{t+1} and its gamma inside.
+ * For game g let L = min(lengths[g], max_steps):
+ *   delta_{L-1} = 0 - V_{L-1} at the last move with its terminal bit; the last move without it is SKIPPED as in pulse_tfe_nt_learn
+ *                 (counted in stats[2]; its difference is +0.0);
+ *   delta_t     = backed[t + 1] - V_t at any other move, one subtract;
+ *   gl = gamma * lambda, formed once;  D_{L-1} = delta_{L-1};  D_t = delta_t + gl * D_{t+1}, the UNCLAMPED D carried; the same
+ *   recurrence at lambda = 0: one path.
+ * The adds are pulse_tfe_nt_learn_lambda's: D_t clamped to +-PULSE_TFE_NT_DELTA_MAX (stats[4]), d = llrint(ldexp(D_t, 16)),
+ * sum += d and cnt += 1 at every feature of keys[t]; with acc_abs set also acc_abs += |d| (pulse_tfe_nt_learn_tc's third
+ * accumulator), with acc_abs NULL the plain accumulators.  pulse_tfe_nt_apply or pulse_tfe_nt_apply_tc follows, unchanged.  Two
+ * launches on the stream: one lane per game walks t downwards and writes deltas[t * n_games + g] = D_t for t < L, reading 25 bytes
+ * per move (backed[t + 1], V_t, the step byte); one lane per recorded move then adds.
+ * The struct is PulseTfeNtLearnTc's fields in order, followed by `backed`.  Zero-initialise it: reserved0 must be 0.
+ *
+ * PULSE_EINVAL, before anything is launched: for the recording what pulse_tfe_nt_rollout refuses, under this name, `layers` other
+ * than 1 or 2, backed null or not 8-byte aligned; for the learner pulse_tfe_nt_learn's refusals, lambda outside [0, 1] (NaN
+ * included), deltas or backed null, keys / values / deltas / stats / backed / acc_abs not 8-byte aligned. */
+int pulse_tfe_nt_rollout_backed(const PulseTfeNtRollout* o, int32_t layers, double* backed, void* stream);
+typedef struct PulseTfeNtLearnBacked {
+    PulseTfeNtNet net;                  /* weights may be NULL */
+    int32_t n_games, max_steps;
+    double gamma, lambda;
+    const uint64_t* keys;
+    const double* values;
+    const uint8_t* steps;
+    const int32_t* lengths;
+    double* deltas;                     /* float64[max_steps * n_games] */
+    int64_t* acc;                       /* int64[n_weights][2] */
+    int64_t* acc_abs;                   /* int64[n_weights], or NULL: the plain accumulators */
+    int64_t* stats;                     /* int64[8] */
+    int64_t reserved0;
+    const double* backed;               /* float64[max_steps * n_games] */
+} PulseTfeNtLearnBacked;
+int pulse_tfe_nt_learn_backed(const PulseTfeNtLearnBacked* o, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

@@ -180,6 +180,10 @@ class TfeNtLearnTc(C.Structure):
         (n, C.c_void_p) for n in ("keys", "values", "steps", "lengths", "deltas", "acc", "acc_abs", "stats")] + [("reserved0", C.c_int64)]
 
 
+class TfeNtLearnBacked(C.Structure):                                        # TfeNtLearnTc's fields in order, then `backed`
+    _fields_ = TfeNtLearnTc._fields_ + [("backed", C.c_void_p)]
+
+
 class TfeNtApplyTc(C.Structure):
     _fields_ = [("net", TfeNtNet), ("step", C.c_double)] + [(n, C.c_void_p) for n in ("acc", "acc_abs", "e", "a", "tc_stats")] + [("reserved0", C.c_int64)]
 
@@ -268,6 +272,8 @@ SYMBOLS = {
     "pulse_tfe_nt_search_deep": (C.c_int, [_P, _I32, _P]),
     "pulse_tfe_nt_evaluate_search_deep": (C.c_int, [_P, _I32, _P]),
     "pulse_tfe_nt_rollout_search": (C.c_int, [_P, _I32, _P]),
+    "pulse_tfe_nt_rollout_backed": (C.c_int, [_P, _I32, _P, _P]),
+    "pulse_tfe_nt_learn_backed": (C.c_int, [_P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

@@ -21,7 +21,12 @@ depend on scheduling: `feature_cells_on_host`, `value_on_host`, `greedy_nt_on_ho
 
 With `tc=True` (section 13.3; csrc/tfe_ntuple_tc.hip) every weight has a step size of its own, rho = |E| / A, from the running sums of
 its rounds' mean errors and mean absolute errors: `learn` is `pulse_tfe_nt_learn_tc`, which also adds |d| into a third accumulator,
-and `apply` is `pulse_tfe_nt_apply_tc`; `learn_tc_nt_on_host` and `apply_tc_nt_on_host` state them on the host."""
+and `apply` is `pulse_tfe_nt_apply_tc`; `learn_tc_nt_on_host` and `apply_tc_nt_on_host` state them on the host.
+
+With the attribute `backed_targets` (section 13.6; csrc/tfe_ntuple_backed.hip) a round under search also records, per move, the value
+the search backed up for the board the move was made on (`pulse_tfe_nt_rollout_backed`), and `learn` is `pulse_tfe_nt_learn_backed`:
+the difference of a move is backed[t + 1] - V_t in place of r' + gamma * V' - V.  `search_backed_on_host`, `backed_deltas_on_host`
+and `learn_backed_nt_on_host` state them on the host."""
 from __future__ import annotations
 
 import functools
@@ -176,6 +181,18 @@ def check_rollout_layers(layers) -> int:
     return int(layers)
 
 
+def search_backed_on_host(q, candidates) -> np.ndarray:
+    """float64[N]: the value the search backs up for a board, from its q float64[N, 4] and candidates bool[N, 4]:
+    the largest q over the candidate moves, scanned in the order a = 0..3 -- the first candidate starts, a strictly larger q replaces
+    it; +0.0 without a candidate (the board is over).  A maximum: no tie coin, and nothing of the action taken."""
+    q, candidates = np.asarray(q, dtype=np.float64).reshape(-1, 4), np.asarray(candidates, dtype=bool).reshape(-1, 4)
+    best, found = np.zeros(len(q), dtype=np.float64), np.zeros(len(q), dtype=bool)
+    for a in range(4):
+        take = candidates[:, a] & (~found | (q[:, a] > best))
+        best, found = np.where(take, q[:, a], best), found | candidates[:, a]
+    return best
+
+
 def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: int, round: int, *, layers: int = 1) -> dict:
     """pulse_tfe_nt_search on the host, word for word.  For a candidate move a of board B (B_a != B) the chance boards of B_a are B_a
     with nibble k = 1, 2 at an empty cell c, slot s = 2 c + (k - 1); m = the best r + gamma * V over the candidate moves of a chance board
@@ -183,7 +200,8 @@ def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
     tree over the 32 terms (x[0::2] + x[1::2], five times); E_a = S / n_empty(B_a); q_a = r_a + gamma * E_a, +0.0 for a move that is no
     candidate.  The action is greedy_nt_on_host's scan on these q.  Returns q float64[N, 4], action int64[N] (-1: no candidate),
     candidates uint8[N] (bit a), E float64[N, 4] (0.0 for a non-candidate), terms float64[N, 4, 32], and the moves themselves: after
-    uint64[N, 4], rewards int64[N, 4].
+    uint64[N, 4], rewards int64[N, 4]; and backed float64[N], search_backed_on_host of these q and candidates (what
+    pulse_tfe_nt_rollout_backed records per move).
 
     layers = 2 (pulse_tfe_nt_search_deep): m of a chance board C is W2(C), the best over C's candidate moves
     of the q this function gives board C at one layer (the same scan: the first candidate starts, a strictly larger q replaces it;
@@ -223,7 +241,7 @@ def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
     q = np.where(cand, rewards.astype(np.float64) + gamma * E, 0.0)
     action = greedy_scan_many_on_host(q, philox_many_on_host(tie_seed, keys, int(round)), cand)
     return dict(q=q, action=action, candidates=(cand << np.arange(4)).sum(axis=1).astype(np.uint8), E=E, terms=terms, after=after,
-                rewards=rewards)
+                rewards=rewards, backed=search_backed_on_host(q, cand))
 
 
 # ------------------------------------------------------------------ the learner and the apply launch
@@ -292,6 +310,38 @@ def learn_lambda_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gam
     _add_moves_on_host's.  Returns dict(learnt, skipped, clamped, deltas float64[T, B])."""
     keys, values, steps = np.asarray(keys, dtype=_U64), np.asarray(values, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
     deltas = lambda_deltas_on_host(values, steps, lengths, gamma, lam)
+    return dict(_add_moves_on_host(keys, steps, lengths, deltas, tuples, symmetric, acc, acc_abs), deltas=deltas)
+
+
+def backed_deltas_on_host(values, backed, steps, lengths, gamma: float, lam: float) -> np.ndarray:
+    """float64[T, B]: the differences pulse_tfe_nt_learn_backed writes, operation for operation.  values and
+    backed float64[T, B], steps uint8[T, B], lengths int[B] (a game has min(lengths[g], T) moves).  gl = gamma * lam (one multiply); at a
+    game's last move D = 0 - values[t] with its terminal bit and +0.0 without (the move is skipped); at any other D_t = (backed[t + 1] -
+    values[t]) + gl * D_{t+1}, unclamped: backed[t + 1] holds the next reward and its own gamma.  Rows at or beyond a game's length are
+    returned as 0 (the device does not write them: they keep what `deltas` held)."""
+    values, backed, steps = np.asarray(values, dtype=np.float64), np.asarray(backed, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
+    T = values.shape[0]
+    L = np.minimum(np.asarray(lengths, dtype=np.int64).reshape(-1), T)
+    gl = np.float64(gamma) * np.float64(lam)
+    out, carried = np.zeros(values.shape, dtype=np.float64), np.zeros(values.shape[1], dtype=np.float64)
+    for t in range(int(L.max()) - 1 if L.size else -1, -1, -1):
+        last, played = t == L - 1, t < L
+        nxt = t + 1 if t + 1 < T else t                                    # (row T does not exist; a move at T - 1 is a last move)
+        with np.errstate(all="ignore"):                                    # (what a lane computes on rows beyond its game is not used)
+            delta = np.where(last, 0.0, backed[nxt]) - values[t]
+            through = delta + gl * carried
+        carried = np.where(last, np.where(steps[t] >> 7 != 0, delta, 0.0), through)
+        carried = np.where(played, carried, 0.0)
+        out[t] = carried
+    return out
+
+
+def learn_backed_nt_on_host(keys, values, backed, steps, lengths, tuples, symmetric, gamma: float, lam: float, acc, acc_abs=None) -> dict:
+    """pulse_tfe_nt_learn_backed on the host: learn_lambda_nt_on_host with backed_deltas_on_host's D_t.  The skipped moves, the clamp
+    to +-DELTA_MAX (applied to the add only), d and the adds -- to acc_abs too, where one is given -- are _add_moves_on_host's.
+    Returns dict(learnt, skipped, clamped, deltas float64[T, B])."""
+    keys, steps = np.asarray(keys, dtype=_U64), np.asarray(steps, dtype=np.uint8)
+    deltas = backed_deltas_on_host(values, backed, steps, lengths, gamma, lam)
     return dict(_add_moves_on_host(keys, steps, lengths, deltas, tuples, symmetric, acc, acc_abs), deltas=deltas)
 
 
@@ -441,9 +491,13 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     pulse_tfe_nt_apply_tc, and the agent holds `acc_abs`, `E`, `A` and `tc_stats`; without it (the default) none of them exists.
     `rollout_layers` (an attribute, 0 by default; section 13.5): 1 or 2 and `rollout`, so `learn_batch`, plays its games under
     expectimax search that many chance layers deep and records them as before; it is how rounds are played, not part of the network,
-    so no checkpoint holds it."""
+    so no checkpoint holds it.  `backed_targets` (an attribute, False by default; section 13.6): with `rollout_layers` 1 or 2, `rollout`
+    also records the search's backed-up value of every move's board in `backed` (float64 in the shape of `values`, allocated at the
+    first such launch) and `learn` is pulse_tfe_nt_learn_backed under the agent's `lam` and `tc`; it says how rounds are learnt, so
+    no checkpoint holds it either."""
     STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
     rollout_layers = 0                                                     # set on the agent; checked at the launch (check_rollout_layers)
+    backed_targets = False                                                 # set on the agent; checked at the launch, with rollout_layers
 
     def __init__(self, device, n_games, tuples=DEFAULT_TUPLES, symmetric=True, gamma=1.0, epsilon=0.0, alpha=1.0, max_steps=4096, seed=0,
                  board_id0=0, lam=0.0, tc=False):
@@ -459,7 +513,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         self.acc = torch.zeros((self.n_weights, 2), dtype=torch.int64, device=self.device)            # {sum, cnt}; torch allocations are 16-byte aligned
         self.values = torch.zeros((self.max_steps, self.n_games), dtype=torch.float64, device=self.device)
         self.deltas = torch.zeros_like(self.values) if self.lam > 0.0 else None
-        self.acc_abs = self.E = self.A = self.tc_stats = None
+        self.acc_abs = self.E = self.A = self.tc_stats = self.backed = None
         if self.tc:
             self._tc_state()
 
@@ -483,8 +537,13 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     def rollout(self, layers=None):
         """One launch: n_games games under the weights as they stand (round `self.round`), into keys / values / steps / lengths /
         scores.  layers (None: the agent's `rollout_layers`) = 0: pulse_tfe_nt_rollout, greedy on reward + gamma * V; 1 or 2:
-        rollout_search_launch, greedy on the q of the search that deep.  ValueError for any other."""
+        rollout_search_launch, greedy on the q of the search that deep.  ValueError for any other.  With `backed_targets` the depth
+        must be 1 or 2 (ValueError otherwise, before anything is touched) and the launch is rollout_backed_launch."""
         layers = check_rollout_layers(self.rollout_layers if layers is None else layers)
+        if self.backed_targets:
+            if not layers:
+                raise ValueError("backed_targets needs rollout_layers in (1, 2): a one-ply roll-out has no search to back a value up")
+            return self.rollout_backed_launch(layers)
         if layers:
             return self.rollout_search_launch(layers)
         return self._launch("pulse_tfe_nt_rollout", self._rollout_struct())
@@ -495,6 +554,16 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         holds the network's V of the chosen afterstates, so the learners read the records as they read rollout()'s."""
         layers = check_layers(layers)
         return self._launch("pulse_tfe_nt_rollout_search", self._rollout_struct(), layers)
+
+    def rollout_backed_launch(self, layers):
+        """pulse_tfe_nt_rollout_backed alone, whatever the agent's `rollout_layers` and `backed_targets`: rollout_search_launch's games
+        and records, and in `backed` (allocated here if the agent has none) per move the largest q of the search over the moves that
+        change the board."""
+        import torch
+        layers = check_layers(layers)
+        if self.backed is None:
+            self.backed = torch.zeros_like(self.values)
+        return self._launch("pulse_tfe_nt_rollout_backed", self._rollout_struct(), layers, self.backed.data_ptr())
 
     def _moves(self, o):
         """The network and the fields the two learners' structs share."""
@@ -515,7 +584,9 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
 
     def learn(self):
         """The temporal differences of the games last played, into the accumulators: one launch, or with lam > 0
-        learn_lambda_launch's two; with tc, learn_tc_launch's."""
+        learn_lambda_launch's two; with tc, learn_tc_launch's; with backed_targets, learn_backed_launch's."""
+        if self.backed_targets:
+            return self.learn_backed_launch(self.lam)
         if self.tc:
             return self.learn_tc_launch(self.lam)
         if self.lam > 0.0:
@@ -547,6 +618,23 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
                 self.deltas = torch.zeros_like(self.values)
             o.deltas = self.deltas.data_ptr()
         return self._launch("pulse_tfe_nt_learn_tc", o)
+
+    def learn_backed_launch(self, lam):
+        """pulse_tfe_nt_learn_backed on the games rollout_backed_launch last recorded, whatever the agent's own `lam` and
+        `backed_targets`: the backward walk of backed[t + 1] - V_t into `deltas` (allocated here if the agent has none) and the adds
+        of what it left -- with the agent's `tc` into `acc_abs` as well.  ValueError if no such roll-out has run."""
+        import torch
+        lam = check_lam(lam)
+        if self.backed is None:
+            raise ValueError("no roll-out with backed values has run: the agent holds no backed")
+        if self.deltas is None:
+            self.deltas = torch.zeros_like(self.values)
+        o = self._moves(_native.TfeNtLearnBacked())
+        o.lam, o.deltas, o.backed = lam, self.deltas.data_ptr(), self.backed.data_ptr()
+        if self.tc:
+            self._tc_state()
+            o.acc_abs = self.acc_abs.data_ptr()
+        return self._launch("pulse_tfe_nt_learn_backed", o)
 
     def apply_tc_launch(self):
         """pulse_tfe_nt_apply_tc: every visited weight moves by (alpha / F) * rho of the mean of its adds, rho = |E| / A as they stood;
@@ -658,6 +746,14 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         T, _ = self._played()
         return self.deltas[:T].cpu().numpy()
 
+    def trajectory_backed(self) -> np.ndarray:
+        """float64[T, B]: the search's backed-up values of the last rollout_backed_launch, T = the longest game; rows at and beyond a
+        game's length hold whatever `backed` held before."""
+        if self.backed is None:
+            raise ValueError("no roll-out with backed values has run: the agent holds no backed")
+        T, _ = self._played()
+        return self.backed[:T].cpu().numpy()
+
     def coherence(self):
         """(E, A), float64[n_weights] each, on the host."""
         if self.E is None:
@@ -674,7 +770,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
 
     def save(self, path):
         """The non-zero weights and what a continued run needs as an .npz (write_checkpoint); with tc, E and A too.  `rollout_layers`
-        is not saved: it says how rounds are played, not what the network is."""
+        and `backed_targets` are not saved: they say how rounds are played and learnt, not what the network is."""
         write_checkpoint(path, self.weights(), self.tuples, symmetric=int(self.symmetric), gamma=self.gamma, epsilon=self.epsilon, alpha=self.alpha,
                          max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games, lam=self.lam,
                          tc=self.coherence() if self.tc else None)
@@ -683,7 +779,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     def load(cls, path, device, n_games=None):
         """The agent save() wrote: weights, round, seeds, lam, tc and with it E and A restored.  With the saved n_games it continues the run the saved agent would
         have continued (another n_games plays other boards: round r starts at board_id0 + r * n_games).  `rollout_layers` is 0, whatever the saved
-        agent played under: set it again to continue rounds under search."""
+        agent played under, and `backed_targets` False: set them again to continue such rounds."""
         import torch
         f = read_checkpoint(path)
         agent = cls(device, f["n_games"] if n_games is None else n_games, tuples=f["tuples"], symmetric=f["symmetric"], gamma=f["gamma"],

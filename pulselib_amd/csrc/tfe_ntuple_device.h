@@ -1,13 +1,15 @@
 // tfe_ntuple_device.h -- what the units of the 2048 n-tuple network share (tfe_ntuple.hip: the learner's four launches; tfe_ntuple_search.hip:
-// expectimax play, tfe_ntuple_search_deep.hip, two chance layers of it, and tfe_ntuple_search_rollout.hip, the roll-out under either; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes): the network as the
+// expectimax play, tfe_ntuple_search_deep.hip, two chance layers of it, and tfe_ntuple_search_rollout.hip, the roll-out under either; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes;
+// tfe_ntuple_backed.hip: search-backed targets): the network as the
 // kernels take it, a feature's index, V of four afterstates at once, the learners' target, fixed-point difference and adds, their
-// parameters (Moves), shared refusals (check_moves), scatter kernel and launches, the four moves of a board, the greedy action, the game loop (play_game) with its parameters
+// parameters (Moves), shared refusals (check_moves), scatter kernel and launches, the backward walk's kernel, the four moves of a board, the greedy action, the game loop (play_game) with its parameters
 // (Games) and the host's checks of the network, of the accumulators and of a batch of games.  One copy each.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "philox_device.h"
 #include "pulse_internal.h"
@@ -112,6 +114,7 @@ struct Games {
     int32_t* lengths; int64_t* total_score; int32_t* episode_reward;
     int64_t* stats; int64_t* hist;
     const uint32_t* lut;
+    double* backed;                                                                     // play_game<true, true> alone (tfe_ntuple_backed.hip): the search's best q per move
 };
 
 template <class O>
@@ -219,8 +222,82 @@ __global__ __launch_bounds__(kScatterBlock) void tfe_nt_scatter_kernel(const Mov
 // tfe_ntuple.hip)
 void launch_scatter(const Moves& m, const NtDev& dev, bool symmetric, void* stream);
 
-// ... and the launch of the TD(lambda) walk, which leaves D_t in o.deltas (defined in tfe_ntuple_lambda.hip, where the kernel is): of
-// `o` it reads n_games, max_steps, gamma, lambda, values, steps, lengths and deltas
+// ... and launch_scatter's counterpart with the third accumulator, m.acc_abs (defined in tfe_ntuple_tc.hip)
+void launch_scatter_tc(const Moves& m, const NtDev& dev, bool symmetric, void* stream);
+
+// The backward walk of the learners that carry credit along a game: D_t = delta_t + (gamma * lambda) * D_{t+1} into o.deltas.  Backed
+// says where delta_t of a move that is not its game's last comes from: without it (tfe_ntuple_lambda.hip) it
+// is the one-step difference (r_{t+1} + gamma * V_{t+1}) - V_t of the records; with it (tfe_ntuple_backed.hip, section 13.6) it is
+// backed[t + 1] - V_t, the search's value of the board the next move was made on.  What the kernel takes: the TD(lambda) learner's
+// struct, of which it reads n_games, max_steps, gamma, lambda, values, steps, lengths and deltas, with `backed` behind it for the
+// second form.
+constexpr int kWalkBlock = 64, kRows = 8;
+
+struct WalkBacked : PulseTfeNtLearnLambda {
+    const double* backed;
+};
+
+// One lane per game, one wavefront per workgroup, t downwards from the wavefront's longest game: every lane of the wavefront is at
+// the same row t, so a row's loads and stores are one 512-byte and one 64-byte segment, and a lane whose game is shorter waits with
+// `t < length` as its predicate.  A lane reads its column of every row from the wavefront's first (what a row at or beyond its own
+// length holds is loaded and not used); rows of kRows are loaded together, the next kRows before the chain of these is run, so the
+// chain is one multiply and one add per move and no memory latency.  V and the byte of row t + 1 (Backed: `backed` of row t + 1) stay
+// in registers for row t.
+template <bool Backed>
+__global__ __launch_bounds__(kWalkBlock) void tfe_nt_lambda_walk_kernel(const std::conditional_t<Backed, WalkBacked, PulseTfeNtLearnLambda> o) {
+    const int g = (int)blockIdx.x * kWalkBlock + (int)threadIdx.x;
+    const size_t B = (size_t)o.n_games;
+    int length = 0;
+    if (g < o.n_games) {
+        length = o.lengths[g];
+        length = length > o.max_steps ? o.max_steps : length;                          // (the buffers hold max_steps rows)
+    }
+    int longest = length;
+#pragma unroll
+    for (int d = 1; d < kWalkBlock; d <<= 1) longest = max(longest, __shfl_xor(longest, d, kWalkBlock));
+    if (longest < 1) return;
+    const size_t col = (size_t)(g < o.n_games ? g : o.n_games - 1);                    // a lane beyond the batch reads the last column, and writes nothing
+    const double gl = __dmul_rn(o.gamma, o.lambda);
+    double v[kRows], nv[kRows], b[Backed ? kRows : 1], nb[Backed ? kRows : 1];
+    uint32_t s[kRows], ns[kRows];
+#pragma unroll
+    for (int j = 0; j < kRows; ++j) {
+        const size_t at = (size_t)max(longest - 1 - j, 0) * B + col;
+        v[j] = o.values[at]; s[j] = o.steps[at];
+        if constexpr (Backed) b[j] = o.backed[at];
+    }
+    double above_v = 0.0, above_b = 0.0, big = 0.0;                                    // row t + 1's V and byte (its `backed`); D_{t+1}
+    uint32_t above_s = 0u;
+    for (int top = longest - 1; top >= 0; top -= kRows) {
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) {
+            const size_t at = (size_t)max(top - kRows - j, 0) * B + col;
+            nv[j] = o.values[at]; ns[j] = o.steps[at];
+            if constexpr (Backed) nb[j] = o.backed[at];
+        }
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) {
+            const int t = top - j;
+            const bool last = t == length - 1;
+            double target;
+            if constexpr (Backed) target = last ? 0.0 : above_b;
+            else target = last ? 0.0 : td_target(above_s, above_v, o.gamma);
+            const double delta = __dsub_rn(target, v[j]);
+            const double carried = __dadd_rn(delta, __dmul_rn(gl, big));
+            big = last ? ((s[j] & 0x80u) != 0u ? delta : 0.0) : carried;              // (a cut game's last move is skipped: +0.0)
+            if (t >= 0 && t < length) o.deltas[(size_t)t * B + col] = big;
+            above_v = v[j]; above_s = s[j];
+            if constexpr (Backed) above_b = b[j];
+        }
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) {
+            v[j] = nv[j]; s[j] = ns[j];
+            if constexpr (Backed) b[j] = nb[j];
+        }
+    }
+}
+
+// ... and the launch of its first form, the TD(lambda) walk (defined in tfe_ntuple_lambda.hip, which instantiates it)
 void launch_lambda_walk(const PulseTfeNtLearnLambda& o, void* stream);
 
 // what pulse_tfe_nt_rollout and pulse_tfe_nt_rollout_search refuse, and the game loop's parameters of a recording launch (defined in
@@ -253,9 +330,10 @@ __device__ __forceinline__ int greedy_of(const double (&q)[4], const uint64_t ke
 
 // The game loop of the roll-out (Record) and of the two evaluations: game g of the launch, from its reset to its end, its cap or
 // max_steps.  q_of(key_b, ka, sc, v, q) fills the four q of board key_b from its moves, and where the launch records also V of the
-// four afterstates.  `writer`: this lane writes the game's outputs and counts it (a game that several lanes play alike has one).
+// four afterstates.  Backed (with Record): a move also records in o.backed the largest q over the moves that
+// change the board -- scanned a = 0..3, the first candidate starts, a strictly larger q replaces it -- whatever the action taken.  `writer`: this lane writes the game's outputs and counts it (a game that several lanes play alike has one).
 // wg: the workgroup's zeroed LDS words, 2 with Record and kEvalBins without.  Called by every thread of the workgroup, whatever its g.
-template <bool Record, class Q>
+template <bool Record, bool Backed = false, class Q>
 __device__ __forceinline__ void play_game(const Games& o, unsigned long long* wg, const int g, const bool writer, Q&& q_of) {
     using pulse_philox::philox4x32;
     using pulse_philox::U4;
@@ -283,6 +361,16 @@ __device__ __forceinline__ void play_game(const Games& o, unsigned long long* wg
                 act = best < 0 ? act : best;                                            // (a live board has a candidate)
                 n_greedy += 1ull;
             }
+            double best_q = 0.0;
+            if constexpr (Backed) {
+                bool any = false;
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    const bool cand = ka[a] != key_b;
+                    best_q = cand && (!any || q[a] > best_q) ? q[a] : best_q;
+                    any = any || cand;
+                }
+            }
             uint64_t key = ka[0];
             double val = v[0];
             int score = sc[0];
@@ -300,6 +388,7 @@ __device__ __forceinline__ void play_game(const Games& o, unsigned long long* wg
                     o.keys[at] = key;
                     o.values[at] = val;
                     o.steps[at] = tfe_step_byte(act, reward, over ? 1u : 0u);
+                    if constexpr (Backed) o.backed[at] = best_q;
                 }
             }
             total += score; ep_reward += reward;

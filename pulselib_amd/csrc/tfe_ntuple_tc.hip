@@ -53,7 +53,11 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_tc_apply_kernel(float* __restri
     if (threadIdx.x < 2 && wg[threadIdx.x]) atomicAdd(tc_stats + threadIdx.x, wg[threadIdx.x]);
 }
 
-// launch_scatter's counterpart with the third accumulator
+}  // namespace
+
+namespace pulse_tfe {
+
+// launch_scatter's counterpart with the third accumulator (declared in tfe_ntuple_device.h: pulse_tfe_nt_learn_backed launches it too)
 void launch_scatter_tc(const Moves& m, const NtDev& dev, bool symmetric, void* stream) {
     const dim3 grid((unsigned)((m.n_games + kScatterBlock - 1) / kScatterBlock), (unsigned)m.max_steps), block(kScatterBlock);
     hipStream_t st = (hipStream_t)stream;
@@ -66,7 +70,7 @@ void launch_scatter_tc(const Moves& m, const NtDev& dev, bool symmetric, void* s
     }
 }
 
-}  // namespace
+}  // namespace pulse_tfe
 
 extern "C" int pulse_tfe_nt_learn_tc(const PulseTfeNtLearnTc* o, void* stream) {
     const char* name = "pulse_tfe_nt_learn_tc";

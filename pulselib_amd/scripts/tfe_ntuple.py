@@ -11,7 +11,9 @@ backwards first and adds lambda-differences; the run's first line names it, and 
 step sizes (section 13.3): every weight moves by rho = |E| / A of the step, from the running sums of its errors; the round's mean rho
 is printed beside the round's counters, and `--resume` takes `tc` from the file too.  `--train-layers L` (1 or 2; section 13.5) plays the
 rounds' own games under expectimax search L chance layers deep, recorded and learnt from as before; every round's line carries the mean
-score and length of the games it trained on; no checkpoint holds the option, so `--resume` needs it given again."""
+score and length of the games it trained on; no checkpoint holds the option, so `--resume` needs it given again.  `--backed` (with
+`--train-layers 1` or `2`; section 13.6) also records the value the search backed up for every move's board and learns towards it:
+a move's difference is backed[t + 1] - V_t, under the run's `--lambda` and `--tc`; not saved either."""
 from __future__ import annotations
 
 import argparse
@@ -23,7 +25,9 @@ from ..agents import NTupleTDAfterstateTFEGPU
 
 
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
-        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0):
+        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False):
+    if backed and train_layers not in (1, 2):
+        raise ValueError("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
     if resume:
         agent = NTupleTDAfterstateTFEGPU.load(resume, device)
         want = dict(n_games=tables, alpha=float(alpha), epsilon=float(epsilon), gamma=float(gamma), max_steps=max_steps, seed=seed)
@@ -32,9 +36,10 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
             raise ValueError(f"{resume} continues another run: (saved, asked) {differ}")
     else:
         agent = NTupleTDAfterstateTFEGPU(device, tables, gamma=gamma, epsilon=epsilon, alpha=alpha, max_steps=max_steps, seed=seed, lam=lam, tc=tc)
-    agent.rollout_layers = train_layers                                     # (no checkpoint holds it: given again on --resume)
+    agent.rollout_layers, agent.backed_targets = train_layers, bool(backed)  # (no checkpoint holds them: given again on --resume)
     out(f"{agent.n_games} games per round from round {agent.round}: alpha {agent.alpha}, epsilon {agent.epsilon}, gamma {agent.gamma}, "
-        f"lambda {agent.lam}, tc {agent.tc}, max_steps {agent.max_steps}, seed {agent.seed}, roll-out under {agent.rollout_layers} chance layers of search")
+        f"lambda {agent.lam}, tc {agent.tc}, max_steps {agent.max_steps}, seed {agent.seed}, roll-out under {agent.rollout_layers} chance layers of search"
+        f"{', learning towards the search-backed values' if agent.backed_targets else ''}")
     first, moves_before, t0 = agent.round, agent.stats()["moves"], time.perf_counter()
 
     def under_search():
@@ -86,9 +91,13 @@ def main(argv=None):
     ap.add_argument("--layers", type=int, default=1, choices=[1, 2], help="with --search: the chance layers the search looks ahead")
     ap.add_argument("--train-layers", type=int, default=0, choices=[0, 1, 2],
                     help="the chance layers of search the rounds' own games are played under (0: the one-ply roll-out); not saved: give it again with --resume")
+    ap.add_argument("--backed", action="store_true",
+                    help="with --train-layers 1 or 2: learn towards the value the search backed up instead of r + gamma * V of the next record; not saved")
     args = ap.parse_args(argv)
+    if args.backed and args.train_layers not in (1, 2):
+        ap.error("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
-                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers)
+                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers, backed=args.backed)
     st = agent.stats()
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
           f"{int((agent.weights_dev != 0).sum().item())} of {agent.n_weights} weights are not zero")

@@ -28,7 +28,17 @@ launch under search L chance layers deep (pulse_tfe_nt_rollout_search; DESIGN.md
 process, the evaluation launch under the same policy on the same boards, weights and epsilon, each between its own pair of HIP events;
 the ratio of the medians, the evaluation's own spread (max / min) beside it, and the yardstick by count: 1 + 1 / (the mean number of
 candidate moves per board), counted on the host over 32 games played under that policy, and whether the ratio is within it + 50 %.
-max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes).  Lines are also
+--backed (with --train-layers L): per B two more lines.  {"backed_rollout": ...}: on the weights the rounds left, the
+recording launch with the search's backed-up values (pulse_tfe_nt_rollout_backed) and, alternating with it in the same process, the
+parent's recording launch (pulse_tfe_nt_rollout_search) on the same boards, weights and epsilon, each between its own pair of HIP
+events; the ratio of the medians beside the parent launch's own spread (max / min) and whether the ratio is inside it; by count the new
+launch adds one 8-byte store per move and three compares.  {"backed_learn": ...}: on the records of the last such launch,
+pulse_tfe_nt_learn_backed and pulse_tfe_nt_learn_lambda at the same lambda (--lambda, 0 if not given), alternating, the accumulators
+zeroed (untimed) before each; the walk reads 25 bytes per move against 17.  --backed-regime: instead of everything above, ONE line,
+{"backed_regime": ...}: section 13.5's regime -- learn_batch --regime-rounds (12) times with the first --games games per round, then
+--regime-eval-games (2,048) games from the default evaluation boards one ply deep and under one-layer search, paired by board -- for
+four agents: rollout_layers = 0, rollout_layers = 1, and rollout_layers = 1 with backed_targets at lambda 0 and at lambda 0.5.
+max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes, 25 with deltas, 33 with backed).  Lines are also
 appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
 import argparse
 import json
@@ -125,6 +135,81 @@ def train_rollout_line(agent, torch, layers, warmup, repeats):
                               "yardstick_by_count": yardstick, "ratio_over_yardstick": ratio / yardstick, "within_margin": ratio <= 1.5 * yardstick,
                               "mean_length": moves / agent.n_games, "mean_final_score": agent.total_score.double().mean().item(),
                               "record_bytes": 17 * moves}}
+
+
+def _alternate(agent, torch, launches, warmup, repeats, before=None):
+    """seconds per name: the launches in turn, each between its own pair of HIP events, `warmup` untimed turns and then `repeats`"""
+    seconds = {name: [] for name, _ in launches}
+    for i in range(warmup + repeats):
+        for name, launch in launches:
+            if before:
+                before()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            launch()
+            ev[1].record()
+            ev[1].synchronize()
+            if i >= warmup:
+                seconds[name].append(ev[0].elapsed_time(ev[1]) * 1e-3)
+    return seconds
+
+
+def backed_lines(agent, torch, layers, lam, warmup, repeats):
+    """the recording launch with backed values beside the parent's, then the backed learner beside the TD(lambda) learner on its records"""
+    before = agent.stats()
+    seconds = _alternate(agent, torch, (("rollout_search", lambda: agent.rollout_search_launch(layers)),
+                                        ("rollout_backed", lambda: agent.rollout_backed_launch(layers))), warmup, repeats)
+    moves = (agent.stats()["moves"] - before["moves"]) // (2 * (warmup + repeats))
+    old, new = _spread(seconds["rollout_search"]), _spread(seconds["rollout_backed"])
+    ratio, spread = new["median"] / old["median"], old["max"] / old["min"]
+    common = {"games": agent.n_games, "layers": layers, "epsilon": agent.epsilon, "trained_rounds": agent.round, "max_steps": agent.max_steps,
+              "warmup": warmup, "repeats": repeats}
+    rollout = {"backed_rollout": {**common, "moves": moves, "rollout_search_s": old, "rollout_backed_s": new, "ratio": ratio, "parent_spread": spread,
+                                  "inside_parent_spread": 1.0 / spread <= ratio <= spread, "more_bytes": 8 * moves,
+                                  "mean_length": moves / agent.n_games}}
+    before = agent.stats()
+    seconds = _alternate(agent, torch, (("learn_lambda", lambda: agent.learn_lambda_launch(lam)), ("learn_backed", lambda: agent.learn_backed_launch(lam))),
+                         warmup, repeats, before=agent.acc.zero_)
+    agent.acc.zero_()
+    learnt = (agent.stats()["learnt"] - before["learnt"]) // (2 * (warmup + repeats))
+    old, new = _spread(seconds["learn_lambda"]), _spread(seconds["learn_backed"])
+    ratio, spread = new["median"] / old["median"], old["max"] / old["min"]
+    learn = {"backed_learn": {**common, "lambda": lam, "gamma": agent.gamma, "moves_learnt": learnt, "learn_lambda_s": old, "learn_backed_s": new,
+                              "ratio": ratio, "parent_spread": spread, "inside_parent_spread": 1.0 / spread <= ratio <= spread,
+                              "walk_bytes": 25 * learnt, "walk_bytes_lambda": 17 * learnt, "atomics": 2 * agent.n_features * learnt}}
+    return [rollout, learn]
+
+
+def backed_regime_line(torch, dev, games, rounds, eval_games, max_steps):
+    """section 13.5's regime for the four agents; the evaluations are paired by board"""
+    import numpy as np
+    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
+    out, ev = {"games": games, "rounds": rounds, "eval_games": eval_games, "seed": 0, "max_steps": max_steps}, {}
+    for name, layers, backed, lam in (("layers_0", 0, False, 0.0), ("layers_1", 1, False, 0.0), ("layers_1_backed", 1, True, 0.0),
+                                      ("layers_1_backed_lambda_0.5", 1, True, 0.5)):
+        agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=max_steps, seed=0, lam=lam)
+        agent.rollout_layers, agent.backed_targets = layers, backed
+        per_round = []
+        for _ in range(rounds):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            e[0].record()
+            agent.learn_batch()
+            e[1].record()
+            e[1].synchronize()
+            per_round.append({"seconds": e[0].elapsed_time(e[1]) * 1e-3, "mean_length": agent.lengths.double().mean().item(),
+                              "mean_score": agent.total_score.double().mean().item()})
+        ev[name] = {"one_ply": agent.evaluate(n_games=eval_games, per_game=True), "search": agent.evaluate_search(n_games=eval_games, per_game=True)}
+        out[name] = {"rollout_layers": layers, "backed_targets": backed, "lambda": lam, "rounds": per_round, "stats": agent.stats(),
+                     **{k: {"mean": e["mean_score"], "se": e["std_score"] / e["games"] ** .5, "mean_length": e["mean_length"], "cut": e["truncated"]}
+                        for k, e in ev[name].items()}}
+        del agent
+        torch.cuda.empty_cache()
+    for name in ("layers_1_backed", "layers_1_backed_lambda_0.5"):
+        for other in ("layers_0", "layers_1"):
+            for k in ("one_ply", "search"):
+                d = (ev[name][k]["total_score"] - ev[other][k]["total_score"]).astype(np.float64)
+                out[f"{k}_eval_{name}_minus_{other}"] = {"mean": d.mean(), "se": d.std(ddof=1) / d.size ** .5}
+    return {"backed_regime": out}
 
 
 def search_line(agent, torch, games, repeats, layers=1):
@@ -268,8 +353,14 @@ def main(argv=None):
     ap.add_argument("--lambda", dest="lam", type=float, help="one more line per B: the TD(lambda) learn launch beside the TD(0) one, on the same games")
     ap.add_argument("--tc", action="store_true", help="one more line per B: the temporal-coherence learn and apply launches beside the fixed-step ones")
     ap.add_argument("--train-layers", type=int, choices=[1, 2], help="one more line per B: the recording launch under search beside the evaluation under it")
+    ap.add_argument("--backed", action="store_true", help="with --train-layers: two more lines per B, the backed recording launch and the backed learner beside the parent's")
+    ap.add_argument("--backed-regime", action="store_true", help="one line instead: twelve rounds and paired evaluations of the four agents of DESIGN.md section 13.6")
+    ap.add_argument("--regime-rounds", type=int, default=12)
+    ap.add_argument("--regime-eval-games", type=int, default=2048)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
     args = ap.parse_args(argv)
+    if args.backed and not args.train_layers:
+        ap.error("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_tfe_ntuple needs the MI355X: no timing is taken on a CPU")
@@ -277,8 +368,15 @@ def main(argv=None):
     from pulselib_amd.agents.tfe_ntuple_td_gpu import DEFAULT_TUPLES, tuple_offsets
     dev = torch.device("cuda:0")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if args.backed_regime:
+        line = backed_regime_line(torch, dev, args.games[0], args.regime_rounds, args.regime_eval_games, args.max_steps)
+        print(json.dumps(line), flush=True)
+        with open(args.out, "a") as fh:
+            fh.write(json.dumps(line) + "\n")
+        return
     for games in args.games:
-        need = (48 if args.tc else 20) * tuple_offsets(DEFAULT_TUPLES)[1] + (17 if args.lam is None else 25) * games * args.max_steps + 64 * games
+        per_move = 33 if args.backed else 17 if args.lam is None else 25
+        need = (48 if args.tc else 20) * tuple_offsets(DEFAULT_TUPLES)[1] + per_move * games * args.max_steps + 64 * games
         free = torch.cuda.mem_get_info(dev)[0]
         if need > 0.9 * free:
             lines = [{"games": games, "skipped": f"needs {need} bytes of device memory, {free} are free"}]
@@ -293,6 +391,8 @@ def main(argv=None):
                 lines.append(tc_line(agent, torch, args.lam, args.warmup, args.repeats))
             if args.train_layers:                                           # on the weights the last state left
                 lines.append(train_rollout_line(agent, torch, args.train_layers, args.warmup, args.repeats))
+            if args.backed:                                                 # likewise, then on the records of its own last launch
+                lines += backed_lines(agent, torch, args.train_layers, args.lam or 0.0, args.warmup, args.repeats)
             del agent
             torch.cuda.empty_cache()
         for line in lines:
