@@ -1011,6 +1011,50 @@ typedef struct PulseTfeNtLearnBacked {
 } PulseTfeNtLearnBacked;
 int pulse_tfe_nt_learn_backed(const PulseTfeNtLearnBacked* o, void* stream);
 
+/* ---- ... and rounds whose games start half-way through the games of the round before (the "restart" strategy of the n-tuple 2048
+ * literature).  Opt-in: a caller that never calls these two keeps every launch above unchanged.
+ *
+ * pulse_tfe_nt_rollout_from: pulse_tfe_nt_rollout (layers = 0), pulse_tfe_nt_rollout_search at one layer (layers = 1, backed NULL) or
+ * pulse_tfe_nt_rollout_backed at one layer (layers = 1, backed set), with one difference: game g begins on the board packed in
+ * start[g] (the state key: 4 bits of log2(tile) per cell) instead of its reset board, where that board is USABLE:
+ *   - it is not 0;
+ *   - at least one of its four moves changes it;
+ *   - it holds no nibble 15 (a 32,768 tile stops a game).
+ * Otherwise the game begins at its reset exactly as in those launches, and 0 is stored into start[g]: after the launch start[g] != 0
+ * says exactly which games began from their start board.  Nothing else differs.  Move t of game g, counted from the start board,
+ * draws Philox4x32-10(agent_seed, board_id0 + g, t), and the spawn after it Philox4x32-10(env_seed, board_id0 + g, t + 1); total_score
+ * and episode_reward count from the start board; max_steps, the 32,768 cap, the terminal bit, stats[0] and stats[3] and the records
+ * (keys, values, steps, backed) are as before, so every learner reads them unchanged.  With start all 0 the launch's outputs are
+ * those of its sibling, byte for byte.
+ * start: device uint64[n_games], read and, where unusable, written.  One lane per game at layers = 0, one group of 32 lanes at 1.
+ *
+ * pulse_tfe_nt_restart_pick: the next round's `start` from the round just recorded.  For game g let L = min(lengths[g], max_steps)
+ * and t* = (int)floor((double)L * fraction), one float64 multiply:
+ *   L >= min_length and 1 <= t* <= L - 1:  start[g] = the board move t* was made on: keys[(t* - 1) * n_games + g] with the spawn of
+ *                                          Philox4x32-10(env_seed, board_id0 + g, t*) words x (cell) and y (tile) put into it;
+ *   otherwise:                             start[g] = 0.
+ * env_seed and board_id0 are those of the launch that RECORDED keys.  The board is one the recorded game stood on and moved on: it
+ * is usable by construction.  picked: device int64[2], added to: [0] the boards picked, [1] the sum of their t*.
+ * Zero-initialise the struct: reserved0 must be 0.
+ *
+ * PULSE_EINVAL, before anything is launched: for the roll-out what pulse_tfe_nt_rollout refuses, under this name; `layers` other
+ * than 0 or 1 ("layers must be 0 or 1": two layers are not built); backed set with layers = 0; backed or start not 8-byte aligned;
+ * start null.  For the pick: null options, n_games < 1, max_steps outside 1..65,535, fraction not in the open interval (0, 1) (NaN
+ * included), min_length outside 2..65,535, reserved0 not 0, a null pointer, keys / start / picked not 8-byte or lengths not 4-byte
+ * aligned. */
+int pulse_tfe_nt_rollout_from(const PulseTfeNtRollout* o, int32_t layers, double* backed, uint64_t* start, void* stream);
+typedef struct PulseTfeNtRestartPick {
+    int32_t n_games, max_steps;
+    uint64_t env_seed, board_id0;       /* of the round that recorded keys */
+    double fraction;                    /* in (0, 1) */
+    int32_t min_length, reserved0;
+    const uint64_t* keys;               /* uint64[max_steps * n_games] */
+    const int32_t* lengths;             /* int32[n_games] */
+    uint64_t* start;                    /* uint64[n_games], written */
+    int64_t* picked;                    /* int64[2], added to */
+} PulseTfeNtRestartPick;
+int pulse_tfe_nt_restart_pick(const PulseTfeNtRestartPick* o, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

@@ -184,6 +184,11 @@ class TfeNtLearnBacked(C.Structure):                                        # Tf
     _fields_ = TfeNtLearnTc._fields_ + [("backed", C.c_void_p)]
 
 
+class TfeNtRestartPick(C.Structure):
+    _fields_ = [("n_games", C.c_int32), ("max_steps", C.c_int32), ("env_seed", C.c_uint64), ("board_id0", C.c_uint64), ("fraction", C.c_double),
+                ("min_length", C.c_int32), ("reserved0", C.c_int32)] + [(n, C.c_void_p) for n in ("keys", "lengths", "start", "picked")]
+
+
 class TfeNtApplyTc(C.Structure):
     _fields_ = [("net", TfeNtNet), ("step", C.c_double)] + [(n, C.c_void_p) for n in ("acc", "acc_abs", "e", "a", "tc_stats")] + [("reserved0", C.c_int64)]
 
@@ -274,6 +279,8 @@ SYMBOLS = {
     "pulse_tfe_nt_rollout_search": (C.c_int, [_P, _I32, _P]),
     "pulse_tfe_nt_rollout_backed": (C.c_int, [_P, _I32, _P, _P]),
     "pulse_tfe_nt_learn_backed": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_rollout_from": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "pulse_tfe_nt_restart_pick": (C.c_int, [_P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

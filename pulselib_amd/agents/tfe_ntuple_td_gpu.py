@@ -26,7 +26,12 @@ and `apply` is `pulse_tfe_nt_apply_tc`; `learn_tc_nt_on_host` and `apply_tc_nt_o
 With the attribute `backed_targets` (section 13.6; csrc/tfe_ntuple_backed.hip) a round under search also records, per move, the value
 the search backed up for the board the move was made on (`pulse_tfe_nt_rollout_backed`), and `learn` is `pulse_tfe_nt_learn_backed`:
 the difference of a move is backed[t + 1] - V_t in place of r' + gamma * V' - V.  `search_backed_on_host`, `backed_deltas_on_host`
-and `learn_backed_nt_on_host` state them on the host."""
+and `learn_backed_nt_on_host` state them on the host.
+
+With the attribute `restart_fraction` > 0 (section 13.7; csrc/tfe_ntuple_restart.hip) `learn_batch` ends with a fourth launch,
+`pulse_tfe_nt_restart_pick`, which writes into `start` the board every long enough game of the round stood on at that fraction of its
+length, and the next round's games begin there (`pulse_tfe_nt_rollout_from`) instead of at their reset boards: the "restart" strategy
+of the n-tuple 2048 literature.  `spawn_on_host` and `restart_pick_on_host` state the pick on the host."""
 from __future__ import annotations
 
 import functools
@@ -242,6 +247,54 @@ def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
     action = greedy_scan_many_on_host(q, philox_many_on_host(tie_seed, keys, int(round)), cand)
     return dict(q=q, action=action, candidates=(cand << np.arange(4)).sum(axis=1).astype(np.uint8), E=E, terms=terms, after=after,
                 rewards=rewards, backed=search_backed_on_host(q, cand))
+
+
+# ------------------------------------------------------------------ restarted roll-outs
+def check_restart_fraction(fraction) -> float:
+    """The fraction of a game's length its successor starts at, as a float: 0 (off) or inside the open interval (0, 1).  ValueError
+    otherwise; NaN is outside."""
+    fraction = float(fraction)
+    if not 0.0 <= fraction < 1.0:
+        raise ValueError("restart_fraction must be 0 (off) or in (0, 1)")
+    return fraction
+
+
+def spawn_on_host(keys, r_cell, r_val) -> np.ndarray:
+    """uint64[N]: the environment's spawn (csrc/tfe_device.h: tfe_spawn_packed) on packed 4 x 4 boards, from the two Philox words it
+    reads: the tile goes to the k-th empty cell in cell order, k = (r_cell * empty) >> 32, and is nibble 2 (a 4-tile) iff
+    (r_val >> 8) > 15099494, else nibble 1.  A full board comes back as it is."""
+    keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
+    r_cell, r_val = np.asarray(r_cell, dtype=_U64).reshape(-1), np.asarray(r_val, dtype=_U64).reshape(-1)
+    free = np.stack([(keys >> _U64(4 * c)) & _U64(15) for c in range(16)], axis=1) == 0
+    empty = free.sum(axis=1).astype(_U64)
+    k = ((r_cell * empty) >> _U64(32)).astype(np.int64)
+    cell = (free & (np.cumsum(free, axis=1) - 1 == k[:, None])).argmax(axis=1).astype(_U64)
+    tile = np.where((r_val >> _U64(8)) > _U64(15099494), _U64(2), _U64(1))
+    return keys | np.where(empty > 0, tile << (_U64(4) * cell), _U64(0))
+
+
+def restart_pick_on_host(keys, lengths, max_steps, env_seed, board_id0, fraction, min_length):
+    """pulse_tfe_nt_restart_pick on the host.  keys uint64[T, B] and lengths int[B] of a recorded round (T at least the longest game),
+    env_seed and board_id0 those it was recorded under.  L = min(lengths[g], max_steps), t* = floor(float64(L) * fraction); where
+    L >= min_length and 1 <= t* <= L - 1, start[g] = the board move t* was made on: spawn_on_host of keys[t* - 1, g] under words x and
+    y of Philox(env_seed, board_id0 + g, t*); 0 elsewhere.  Returns (start uint64[B], picked (the boards picked, the sum of their t*))."""
+    keys = np.asarray(keys, dtype=_U64)
+    L = np.minimum(np.asarray(lengths, dtype=np.int64).reshape(-1), int(max_steps))
+    at = np.floor(L.astype(np.float64) * np.float64(fraction)).astype(np.int64)
+    g = np.flatnonzero((L >= int(min_length)) & (at >= 1) & (at <= L - 1))
+    start = np.zeros(len(L), dtype=_U64)
+    if len(g):
+        ids = np.array([(int(board_id0) + int(i)) & 0xFFFFFFFFFFFFFFFF for i in g], dtype=_U64)
+        draws = philox_many_on_host(int(env_seed), ids, at[g].astype(_U64))
+        start[g] = spawn_on_host(keys[at[g] - 1, g], draws[:, 0], draws[:, 1])
+    return start, (len(g), int(at[g].sum()))
+
+
+def restart_summary_on_host(words, start) -> dict:
+    """restart_stats' two words and `start` as {"picked", "mean_depth", "started"}: mean_depth = words[1] / words[0] (0.0 where nothing
+    was picked), started = the non-zero entries of start."""
+    picked, total = int(words[0]), int(words[1])
+    return dict(picked=picked, mean_depth=total / picked if picked else 0.0, started=int(np.count_nonzero(start)))
 
 
 # ------------------------------------------------------------------ the learner and the apply launch
@@ -494,8 +547,15 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     so no checkpoint holds it.  `backed_targets` (an attribute, False by default; section 13.6): with `rollout_layers` 1 or 2, `rollout`
     also records the search's backed-up value of every move's board in `backed` (float64 in the shape of `values`, allocated at the
     first such launch) and `learn` is pulse_tfe_nt_learn_backed under the agent's `lam` and `tc`; it says how rounds are learnt, so
-    no checkpoint holds it either."""
+    no checkpoint holds it either.  `restart_fraction` (an attribute, 0.0 by default: off; section 13.7): in (0, 1) and `learn_batch`
+    ends with the pick launch, which fills `start` (uint64[n_games], allocated at first use, as `restart_stats` int64[2] is) from the
+    games of at least `restart_min_length` moves (an attribute, 64 by default: a starting point, not tuned), and `rollout` starts the
+    next round's games there; with `rollout_layers` 2 it is refused.  No checkpoint holds either, and `start` is not saved: a loaded
+    agent's next round starts at the reset boards."""
     STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
+    restart_fraction = 0.0                                                 # set on the agent; checked at the launch (check_restart_fraction)
+    restart_min_length = 64                                                # set on the agent; checked by the pick launch
+    start = restart_stats = None                                           # allocated by the first restart launch
     rollout_layers = 0                                                     # set on the agent; checked at the launch (check_rollout_layers)
     backed_targets = False                                                 # set on the agent; checked at the launch, with rollout_layers
 
@@ -538,15 +598,71 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         """One launch: n_games games under the weights as they stand (round `self.round`), into keys / values / steps / lengths /
         scores.  layers (None: the agent's `rollout_layers`) = 0: pulse_tfe_nt_rollout, greedy on reward + gamma * V; 1 or 2:
         rollout_search_launch, greedy on the q of the search that deep.  ValueError for any other.  With `backed_targets` the depth
-        must be 1 or 2 (ValueError otherwise, before anything is touched) and the launch is rollout_backed_launch."""
+        must be 1 or 2 (ValueError otherwise, before anything is touched) and the launch is rollout_backed_launch.  With
+        `restart_fraction` > 0 the depth must be 0 or 1 (ValueError otherwise, before anything is touched), and once a pick has filled
+        `start` the launch is rollout_from_launch at that depth, with the backed values if `backed_targets`."""
         layers = check_rollout_layers(self.rollout_layers if layers is None else layers)
+        restart = check_restart_fraction(self.restart_fraction) > 0.0
+        if restart and layers == 2:
+            raise ValueError("restart_fraction > 0 needs rollout_layers in (0, 1): the restarted roll-out is not built two layers deep")
         if self.backed_targets:
             if not layers:
                 raise ValueError("backed_targets needs rollout_layers in (1, 2): a one-ply roll-out has no search to back a value up")
+            if restart and self.start is not None:
+                return self.rollout_from_launch(layers, backed=True)
             return self.rollout_backed_launch(layers)
+        if restart and self.start is not None:
+            return self.rollout_from_launch(layers)
         if layers:
             return self.rollout_search_launch(layers)
         return self._launch("pulse_tfe_nt_rollout", self._rollout_struct())
+
+    def _restart_state(self):
+        """`start` and `restart_stats`, zeroed, where the agent has none yet."""
+        import torch
+        if self.start is None:
+            self.start = torch.zeros(self.n_games, dtype=torch.int64, device=self.device)             # (uint64 words)
+            self.restart_stats = torch.zeros(2, dtype=torch.int64, device=self.device)
+
+    def rollout_from_launch(self, layers, backed=False):
+        """pulse_tfe_nt_rollout_from alone, whatever the agent's attributes: rollout()'s games at `layers` = 0 (one ply) or 1 (one-layer
+        search; ValueError for any other), each begun on the board in `start` where that board is usable and at its reset otherwise
+        (`start` is 0 there afterwards).  backed: rollout_backed_launch's `backed` too (layers must be 1).  A `start` no pick has
+        filled is all zero: the launch plays its sibling's games."""
+        import torch
+        if isinstance(layers, bool) or layers not in (0, 1):
+            raise ValueError("layers must be 0 or 1")
+        if backed and not layers:
+            raise ValueError("backed needs layers = 1: a one-ply roll-out has no search to back a value up")
+        self._restart_state()
+        if backed and self.backed is None:
+            self.backed = torch.zeros_like(self.values)
+        return self._launch("pulse_tfe_nt_rollout_from", self._rollout_struct(), int(layers), self.backed.data_ptr() if backed else None,
+                            self.start.data_ptr())
+
+    def restart_pick_launch(self, fraction=None, min_length=None):
+        """pulse_tfe_nt_restart_pick alone on the games last recorded (under this round's seed and boards): `start` becomes, per game
+        of at least `min_length` moves, the board it stood on before move floor(L * fraction), and 0 for the others; `restart_stats`
+        has the boards picked and their depths added.  fraction, min_length: None for the agent's attributes."""
+        fraction = check_restart_fraction(self.restart_fraction if fraction is None else fraction)
+        if not fraction > 0.0:
+            raise ValueError("the pick needs a fraction in (0, 1): restart_fraction is 0 (off)")
+        self._restart_state()
+        o = _native.TfeNtRestartPick()
+        o.n_games, o.max_steps, o.env_seed, o.board_id0 = self.n_games, self.max_steps, self.env_seed, self.round_board_id0()
+        o.fraction, o.min_length = fraction, int(self.restart_min_length if min_length is None else min_length)
+        o.keys, o.lengths, o.start, o.picked = self.keys.data_ptr(), self.lengths.data_ptr(), self.start.data_ptr(), self.restart_stats.data_ptr()
+        return self._launch("pulse_tfe_nt_restart_pick", o)
+
+    def restart_summary(self) -> dict:
+        """{"picked", "mean_depth", "started"} (restart_summary_on_host; synchronises): the boards the pick launches since the last call
+        picked and the mean of their t*, and the non-zero entries of `start` as it stands -- after a pick the games that will be
+        restarted, after a roll-out those that were.  `restart_stats` is zeroed."""
+        if self.start is None:
+            raise ValueError("no restart launch has run: the agent holds no start")
+        out = restart_summary_on_host(self.restart_stats.cpu().tolist(), self.start.cpu().numpy())
+        self.restart_stats.zero_()
+        return out
 
     def rollout_search_launch(self, layers):
         """pulse_tfe_nt_rollout_search alone, whatever the agent's `rollout_layers`: the roll-out's games, draws and records with the
@@ -660,6 +776,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         self.rollout()
         self.learn()
         self.apply()
+        if self.restart_fraction > 0.0:                                    # the next round's start boards, from this round's records
+            self.restart_pick_launch()
         self.round += 1
         return self
 
@@ -769,8 +887,9 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         return out
 
     def save(self, path):
-        """The non-zero weights and what a continued run needs as an .npz (write_checkpoint); with tc, E and A too.  `rollout_layers`
-        and `backed_targets` are not saved: they say how rounds are played and learnt, not what the network is."""
+        """The non-zero weights and what a continued run needs as an .npz (write_checkpoint); with tc, E and A too.  `rollout_layers`,
+        `backed_targets`, `restart_fraction` and `restart_min_length` are not saved: they say how rounds are played and learnt, not what
+        the network is."""
         write_checkpoint(path, self.weights(), self.tuples, symmetric=int(self.symmetric), gamma=self.gamma, epsilon=self.epsilon, alpha=self.alpha,
                          max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games, lam=self.lam,
                          tc=self.coherence() if self.tc else None)
@@ -779,7 +898,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     def load(cls, path, device, n_games=None):
         """The agent save() wrote: weights, round, seeds, lam, tc and with it E and A restored.  With the saved n_games it continues the run the saved agent would
         have continued (another n_games plays other boards: round r starts at board_id0 + r * n_games).  `rollout_layers` is 0, whatever the saved
-        agent played under, and `backed_targets` False: set them again to continue such rounds."""
+        agent played under, `backed_targets` False and `restart_fraction` 0.0 with no `start`: set them again to continue such rounds."""
         import torch
         f = read_checkpoint(path)
         agent = cls(device, f["n_games"] if n_games is None else n_games, tuples=f["tuples"], symmetric=f["symmetric"], gamma=f["gamma"],
@@ -797,7 +916,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         self.weights_dev.zero_()
         self.acc.zero_()
         self.counters.zero_()
-        for t in (self.acc_abs, self.E, self.A, self.tc_stats):
+        for t in (self.acc_abs, self.E, self.A, self.tc_stats, self.start, self.restart_stats):
             if t is not None:
                 t.zero_()
         self.round = 0

@@ -37,9 +37,7 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_games_kernel(const Games o, con
     __syncthreads();
     play_game<Record>(o, wg, blockIdx.x * kBlock + threadIdx.x, true,
                       [&](const uint64_t, const uint64_t (&ka)[4], const int (&sc)[4], double (&v)[4], double (&q)[4]) {
-                          values4<IMG>(net, o.weights, ka, v);
-#pragma unroll
-                          for (int a = 0; a < 4; ++a) q[a] = __dadd_rn((double)tfe_reward(sc[a]), __dmul_rn(o.gamma, v[a]));
+                          one_ply_q<IMG>(net, o.weights, o.gamma, ka, sc, v, q);
                       });
 }
 

@@ -1,6 +1,6 @@
 // tfe_ntuple_device.h -- what the units of the 2048 n-tuple network share (tfe_ntuple.hip: the learner's four launches; tfe_ntuple_search.hip:
 // expectimax play, tfe_ntuple_search_deep.hip, two chance layers of it, and tfe_ntuple_search_rollout.hip, the roll-out under either; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes;
-// tfe_ntuple_backed.hip: search-backed targets): the network as the
+// tfe_ntuple_backed.hip: search-backed targets; tfe_ntuple_restart.hip: roll-outs restarted from recorded boards): the network as the
 // kernels take it, a feature's index, V of four afterstates at once, the learners' target, fixed-point difference and adds, their
 // parameters (Moves), shared refusals (check_moves), scatter kernel and launches, the backward walk's kernel, the four moves of a board, the greedy action, the game loop (play_game) with its parameters
 // (Games) and the host's checks of the network, of the accumulators and of a batch of games.  One copy each.  Not part of the ABI.
@@ -115,6 +115,7 @@ struct Games {
     int64_t* stats; int64_t* hist;
     const uint32_t* lut;
     double* backed;                                                                     // play_game<true, true> alone (tfe_ntuple_backed.hip): the search's best q per move
+    uint64_t* start;                                                                    // play_game<true, *, true> alone (tfe_ntuple_restart.hip): the board game g starts from, or 0
 };
 
 template <class O>
@@ -328,12 +329,25 @@ __device__ __forceinline__ int greedy_of(const double (&q)[4], const uint64_t ke
     return greedy_scan<false>(q, coins, cand);
 }
 
+// the one-ply q of a board's four moves, q = r + gamma * V(afterstate), with V of the four afterstates left in v (what
+// pulse_tfe_nt_rollout and pulse_tfe_nt_evaluate play on; tfe_ntuple_restart.hip's one-ply games too)
+template <int IMG>
+__device__ __forceinline__ void one_ply_q(const NtDev& net, const float* __restrict__ w, const double gamma, const uint64_t (&ka)[4], const int (&sc)[4],
+                                          double (&v)[4], double (&q)[4]) {
+    values4<IMG>(net, w, ka, v);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) q[a] = __dadd_rn((double)tfe_reward(sc[a]), __dmul_rn(gamma, v[a]));
+}
+
 // The game loop of the roll-out (Record) and of the two evaluations: game g of the launch, from its reset to its end, its cap or
 // max_steps.  q_of(key_b, ka, sc, v, q) fills the four q of board key_b from its moves, and where the launch records also V of the
 // four afterstates.  Backed (with Record): a move also records in o.backed the largest q over the moves that
-// change the board -- scanned a = 0..3, the first candidate starts, a strictly larger q replaces it -- whatever the action taken.  `writer`: this lane writes the game's outputs and counts it (a game that several lanes play alike has one).
+// change the board -- scanned a = 0..3, the first candidate starts, a strictly larger q replaces it -- whatever the action taken.
+// From (with Record): the game starts on the board packed in o.start[g] instead of its reset board where that
+// board is usable -- not zero, changed by at least one of its four moves, no nibble 15 -- and otherwise at its reset, with 0 stored
+// into o.start[g]; the draws, the counts and the records are those of a game that met this board at its move 0.  `writer`: this lane writes the game's outputs and counts it (a game that several lanes play alike has one).
 // wg: the workgroup's zeroed LDS words, 2 with Record and kEvalBins without.  Called by every thread of the workgroup, whatever its g.
-template <bool Record, bool Backed = false, class Q>
+template <bool Record, bool Backed = false, bool From = false, class Q>
 __device__ __forceinline__ void play_game(const Games& o, unsigned long long* wg, const int g, const bool writer, Q&& q_of) {
     using pulse_philox::philox4x32;
     using pulse_philox::U4;
@@ -342,6 +356,16 @@ __device__ __forceinline__ void play_game(const Games& o, unsigned long long* wg
     if (g < o.n_games) {
         const uint64_t id = o.board_id0 + (uint64_t)g;
         PackedBoard p = tfe_reset_packed(o.env_seed, id);
+        if constexpr (From) {
+            const uint64_t key0 = o.start[g];                                           // (the same word in every lane that plays game g)
+            const PackedBoard p0{(uint32_t)key0, (uint32_t)(key0 >> 32)};
+            // A move changes a board without nibble 15 iff it is not zero and has an empty cell or two equal neighbours: the
+            // environment's own test (a second moves4 here cost tfe_nt_from_games_kernel<1> 30 VGPRs and two waves, section 13.7)
+            const bool full = (tfe_nz_nibbles(p0.lo) & tfe_nz_nibbles(p0.hi)) == 0x88888888u;
+            const bool live = !tfe_over_packed(p0, full ? 0 : 2);
+            if (key0 != 0ull && live && !has_nibble15(p0)) p = p0;
+            else if (writer) o.start[g] = 0ull;
+        }
         int64_t total = 0;
         int ep_reward = 0, length = 0;
         bool over = false, capped = false;

@@ -13,7 +13,11 @@ is printed beside the round's counters, and `--resume` takes `tc` from the file 
 rounds' own games under expectimax search L chance layers deep, recorded and learnt from as before; every round's line carries the mean
 score and length of the games it trained on; no checkpoint holds the option, so `--resume` needs it given again.  `--backed` (with
 `--train-layers 1` or `2`; section 13.6) also records the value the search backed up for every move's board and learns towards it:
-a move's difference is backed[t + 1] - V_t, under the run's `--lambda` and `--tc`; not saved either."""
+a move's difference is backed[t + 1] - V_t, under the run's `--lambda` and `--tc`; not saved either.  `--restart F` (0 < F < 1;
+section 13.7; not with `--train-layers 2`) starts every game of a round on the board its predecessor of the round before stood on at
+the fraction F of its length, where that game had at least `--restart-min-length` moves: every round's line says how many of its games
+were restarted and from what mean depth -- a restarted game's score counts from its start board and is not comparable with a whole
+game's; the evaluations stay from reset.  Not saved either: a resumed run's first round starts at the reset boards."""
 from __future__ import annotations
 
 import argparse
@@ -25,7 +29,9 @@ from ..agents import NTupleTDAfterstateTFEGPU
 
 
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
-        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False):
+        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False, restart=0.0, restart_min_length=64):
+    if restart and train_layers == 2:
+        raise ValueError("--restart does not go with --train-layers 2: the restarted roll-out is one ply or one chance layer deep")
     if backed and train_layers not in (1, 2):
         raise ValueError("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
     if resume:
@@ -37,9 +43,11 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
     else:
         agent = NTupleTDAfterstateTFEGPU(device, tables, gamma=gamma, epsilon=epsilon, alpha=alpha, max_steps=max_steps, seed=seed, lam=lam, tc=tc)
     agent.rollout_layers, agent.backed_targets = train_layers, bool(backed)  # (no checkpoint holds them: given again on --resume)
+    agent.restart_fraction, agent.restart_min_length = float(restart), int(restart_min_length)
     out(f"{agent.n_games} games per round from round {agent.round}: alpha {agent.alpha}, epsilon {agent.epsilon}, gamma {agent.gamma}, "
         f"lambda {agent.lam}, tc {agent.tc}, max_steps {agent.max_steps}, seed {agent.seed}, roll-out under {agent.rollout_layers} chance layers of search"
-        f"{', learning towards the search-backed values' if agent.backed_targets else ''}")
+        f"{', learning towards the search-backed values' if agent.backed_targets else ''}"
+        f"{f', games restarted at {agent.restart_fraction} of games of {agent.restart_min_length} moves or more' if agent.restart_fraction else ''}")
     first, moves_before, t0 = agent.round, agent.stats()["moves"], time.perf_counter()
 
     def under_search():
@@ -56,14 +64,17 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
 
     if not rounds and search:
         out(f"After {agent.round} rounds: {evaluation()}{under_search()}")
+    restarted = dict(picked=0, mean_depth=0.0)                            # of the round being played: what the round before picked
     for r in range(first, first + rounds):
         agent.learn_batch()
+        began, restarted = restarted, (agent.restart_summary() if agent.restart_fraction else restarted)     # (synchronises)
         if eval_every and ((r + 1) % eval_every == 0 or r + 1 == first + rounds):
             line = evaluation()
             st, now = agent.stats(), time.perf_counter()
+            again = f"restarted {began['picked']} games from mean depth {began['mean_depth']:.1f}, " if agent.restart_fraction else ""
             rho = f", mean rho {agent.tc_summary()['mean_rho']:.4f}" if agent.tc else ""       # (of the applies since the last line)
             out(f"Round {r}: {line}; "
-                f"training: Avg final score {agent.total_score.double().mean().item():.1f}, Avg length {agent.lengths.double().mean().item():.1f}, moves/sec {(st['moves'] - moves_before) / (now - t0):.0f}, "
+                f"training: Avg final score {agent.total_score.double().mean().item():.1f}, Avg length {agent.lengths.double().mean().item():.1f}, {again}moves/sec {(st['moves'] - moves_before) / (now - t0):.0f}, "
                 f"skipped {st['skipped']}, clamped {st['clamped']}{rho}{under_search()}")
             moves_before, t0 = st["moves"], time.perf_counter()
     if save:
@@ -93,11 +104,17 @@ def main(argv=None):
                     help="the chance layers of search the rounds' own games are played under (0: the one-ply roll-out); not saved: give it again with --resume")
     ap.add_argument("--backed", action="store_true",
                     help="with --train-layers 1 or 2: learn towards the value the search backed up instead of r + gamma * V of the next record; not saved")
+    ap.add_argument("--restart", type=float, default=0.0, metavar="F",
+                    help="start every game on the board its predecessor stood on at this fraction of its length (0: off; not with --train-layers 2); not saved")
+    ap.add_argument("--restart-min-length", type=int, default=64, metavar="N", help="with --restart: only games of at least N moves are restarted from")
     args = ap.parse_args(argv)
+    if args.restart and args.train_layers == 2:
+        ap.error("--restart does not go with --train-layers 2: the restarted roll-out is one ply or one chance layer deep")
     if args.backed and args.train_layers not in (1, 2):
         ap.error("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
-                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers, backed=args.backed)
+                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers, backed=args.backed,
+                restart=args.restart, restart_min_length=args.restart_min_length)
     st = agent.stats()
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
           f"{int((agent.weights_dev != 0).sum().item())} of {agent.n_weights} weights are not zero")

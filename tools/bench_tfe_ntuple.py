@@ -38,6 +38,15 @@ zeroed (untimed) before each; the walk reads 25 bytes per move against 17.  --ba
 {"backed_regime": ...}: section 13.5's regime -- learn_batch --regime-rounds (12) times with the first --games games per round, then
 --regime-eval-games (2,048) games from the default evaluation boards one ply deep and under one-layer search, paired by board -- for
 four agents: rollout_layers = 0, rollout_layers = 1, and rollout_layers = 1 with backed_targets at lambda 0 and at lambda 0.5.
+--restart F: per B two more lines.  {"restart_rollout": ...}: on the weights the rounds left and with `start` all zero, so that it
+plays the parent's very games, the restarted recording launch (pulse_tfe_nt_rollout_from) beside pulse_tfe_nt_rollout (layers 0),
+pulse_tfe_nt_rollout_search and pulse_tfe_nt_rollout_backed (one layer), each pair alternating in the same process between its own HIP
+events; per pair the ratio of the medians beside the parent launch's own spread (max / min) and whether the ratio is inside it.
+{"restart_pick": ...}: the pick launch (pulse_tfe_nt_restart_pick) at fraction F on the records of the last of those launches, by the
+same events; by count it reads 4 + 8 bytes and writes 8 per game.  --restart-regime: instead of everything above, ONE line,
+{"restart_regime": ...}: section 13.5's regime for four agents: restart_fraction 0 and --restart (0.5 if not given) one ply deep, and the
+same two under rollout_layers = 1 with backed_targets at lambda 0.5; per round the games restarted and their mean depth, per agent
+the moves learnt, and the evaluations' paired differences with and without restart.
 max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes, 25 with deltas, 33 with backed).  Lines are also
 appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
 import argparse
@@ -212,6 +221,69 @@ def backed_regime_line(torch, dev, games, rounds, eval_games, max_steps):
     return {"backed_regime": out}
 
 
+def restart_lines(agent, torch, fraction, min_length, warmup, repeats):
+    """the restarted recording launch with `start` all zero beside each of its three parents, then the pick launch on the last records"""
+    agent._restart_state()
+    agent.start.zero_()
+    common = {"games": agent.n_games, "epsilon": agent.epsilon, "trained_rounds": agent.round, "max_steps": agent.max_steps, "warmup": warmup, "repeats": repeats}
+    pairs = {}
+    for name, parent, new in (("layers_0", lambda: agent._launch("pulse_tfe_nt_rollout", agent._rollout_struct()), lambda: agent.rollout_from_launch(0)),
+                              ("layers_1", lambda: agent.rollout_search_launch(1), lambda: agent.rollout_from_launch(1)),
+                              ("layers_1_backed", lambda: agent.rollout_backed_launch(1), lambda: agent.rollout_from_launch(1, backed=True))):
+        before = agent.stats()
+        seconds = _alternate(agent, torch, (("parent", parent), ("from", new)), warmup, repeats)
+        moves = (agent.stats()["moves"] - before["moves"]) // (2 * (warmup + repeats))
+        old, fresh = _spread(seconds["parent"]), _spread(seconds["from"])
+        ratio, spread = fresh["median"] / old["median"], old["max"] / old["min"]
+        pairs[name] = {"moves": moves, "parent_s": old, "from_s": fresh, "ratio": ratio, "parent_spread": spread,
+                       "inside_parent_spread": 1.0 / spread <= ratio <= spread, "started": int((agent.start != 0).sum().item())}
+    seconds = _alternate(agent, torch, (("pick", lambda: agent.restart_pick_launch(fraction, min_length)),), warmup, repeats)
+    summary = agent.restart_summary()
+    agent.start.zero_()
+    pick = {**common, "fraction": fraction, "min_length": min_length, "pick_s": _spread(seconds["pick"]), "picked": summary["picked"] // (warmup + repeats),
+            "mean_depth": summary["mean_depth"], "bytes_read": 12 * agent.n_games, "bytes_written": 8 * agent.n_games}
+    return [{"restart_rollout": {**common, **pairs}}, {"restart_pick": pick}]
+
+
+def restart_regime_line(torch, dev, games, rounds, eval_games, max_steps, fraction, min_length):
+    """section 13.5's regime with and without restart, one ply deep and under one-layer search with backed targets at lambda 0.5; the
+    evaluations are from reset and paired by board"""
+    import numpy as np
+    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
+    out = {"games": games, "rounds": rounds, "eval_games": eval_games, "seed": 0, "max_steps": max_steps, "fraction": fraction, "min_length": min_length}
+    ev = {}
+    rows = (("layers_0", 0, False, 0.0, 0.0), ("layers_0_restart", 0, False, 0.0, fraction),
+            ("layers_1_backed_lambda_0.5", 1, True, 0.5, 0.0), ("layers_1_backed_lambda_0.5_restart", 1, True, 0.5, fraction))
+    for name, layers, backed, lam, restart in rows:
+        agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=max_steps, seed=0, lam=lam)
+        agent.rollout_layers, agent.backed_targets, agent.restart_fraction, agent.restart_min_length = layers, backed, restart, min_length
+        per_round, began = [], {"picked": 0, "mean_depth": 0.0}
+        for _ in range(rounds):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            e[0].record()
+            agent.learn_batch()
+            e[1].record()
+            e[1].synchronize()
+            per_round.append({"seconds": e[0].elapsed_time(e[1]) * 1e-3, "mean_length": agent.lengths.double().mean().item(),
+                              "mean_score": agent.total_score.double().mean().item(), "restarted": began["picked"],
+                              "restarted_share": began["picked"] / games, "mean_depth": began["mean_depth"]})
+            if restart:
+                began = agent.restart_summary()                             # what this round's pick left for the next
+        ev[name] = {"one_ply": agent.evaluate(n_games=eval_games, per_game=True), "search": agent.evaluate_search(n_games=eval_games, per_game=True)}
+        st = agent.stats()
+        out[name] = {"rollout_layers": layers, "backed_targets": backed, "lambda": lam, "restart_fraction": restart, "rounds": per_round, "stats": st,
+                     "moves_learnt": st["learnt"],
+                     **{k: {"mean": e["mean_score"], "se": e["std_score"] / e["games"] ** .5, "mean_length": e["mean_length"], "cut": e["truncated"]}
+                        for k, e in ev[name].items()}}
+        del agent
+        torch.cuda.empty_cache()
+    for name in ("layers_0", "layers_1_backed_lambda_0.5"):
+        for k in ("one_ply", "search"):
+            d = (ev[name + "_restart"][k]["total_score"] - ev[name][k]["total_score"]).astype(np.float64)
+            out[f"{k}_eval_{name}_restart_minus_{name}"] = {"mean": d.mean(), "se": d.std(ddof=1) / d.size ** .5}
+    return {"restart_regime": out}
+
+
 def search_line(agent, torch, games, repeats, layers=1):
     """the evaluation launch under the policies on the same weights and boards; layers = 2 adds the two-layer search and its yardstick"""
     out = {}
@@ -355,6 +427,9 @@ def main(argv=None):
     ap.add_argument("--train-layers", type=int, choices=[1, 2], help="one more line per B: the recording launch under search beside the evaluation under it")
     ap.add_argument("--backed", action="store_true", help="with --train-layers: two more lines per B, the backed recording launch and the backed learner beside the parent's")
     ap.add_argument("--backed-regime", action="store_true", help="one line instead: twelve rounds and paired evaluations of the four agents of DESIGN.md section 13.6")
+    ap.add_argument("--restart", type=float, metavar="F", help="two more lines per B: the restarted recording launch beside its three parents, and the pick launch at this fraction")
+    ap.add_argument("--restart-min-length", type=int, default=64)
+    ap.add_argument("--restart-regime", action="store_true", help="one line instead: twelve rounds and paired evaluations with and without restart (DESIGN.md section 13.7)")
     ap.add_argument("--regime-rounds", type=int, default=12)
     ap.add_argument("--regime-eval-games", type=int, default=2048)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
@@ -374,8 +449,15 @@ def main(argv=None):
         with open(args.out, "a") as fh:
             fh.write(json.dumps(line) + "\n")
         return
+    if args.restart_regime:
+        line = restart_regime_line(torch, dev, args.games[0], args.regime_rounds, args.regime_eval_games, args.max_steps,
+                                   0.5 if args.restart is None else args.restart, args.restart_min_length)
+        print(json.dumps(line), flush=True)
+        with open(args.out, "a") as fh:
+            fh.write(json.dumps(line) + "\n")
+        return
     for games in args.games:
-        per_move = 33 if args.backed else 17 if args.lam is None else 25
+        per_move = 33 if args.backed or args.restart else 17 if args.lam is None else 25
         need = (48 if args.tc else 20) * tuple_offsets(DEFAULT_TUPLES)[1] + per_move * games * args.max_steps + 64 * games
         free = torch.cuda.mem_get_info(dev)[0]
         if need > 0.9 * free:
@@ -393,6 +475,8 @@ def main(argv=None):
                 lines.append(train_rollout_line(agent, torch, args.train_layers, args.warmup, args.repeats))
             if args.backed:                                                 # likewise, then on the records of its own last launch
                 lines += backed_lines(agent, torch, args.train_layers, args.lam or 0.0, args.warmup, args.repeats)
+            if args.restart:                                                # on the weights the last state left
+                lines += restart_lines(agent, torch, args.restart, args.restart_min_length, args.warmup, args.repeats)
             del agent
             torch.cuda.empty_cache()
         for line in lines:
