@@ -41,7 +41,7 @@ def test_library_exports_the_two_entry_points():
 
 
 # ------------------------------------------------------------------ PULSE_EINVAL before anything is launched
-@pytest.mark.parametrize("layers,backed", [(0, None), (1, None), (1, PTR)])
+@pytest.mark.parametrize("layers,backed", [(0, None), (1, None), pytest.param(1, PTR, id="1-PTR")])     # (PTR is an address: no two runs share it)
 def test_the_rollout_refuses_what_the_rollout_refuses(layers, backed):
     from pulselib_amd import _native
     cases, make = CASES["pulse_tfe_nt_rollout"], functools.partial(opts, _native.TfeNtRollout)

@@ -1,5 +1,5 @@
-"""What the 2048 n-tuple network's tests (tests/test_tfe_nt_*.py) share, once each: the network and weights most of them use, the crafted
-boards, the hand-worked games, the refusal tables with the one struct builder, the export and no-scratch checks of the CPU files, and
+"""What the 2048 n-tuple network's tests (tests/test_tfe_nt_*.py) share, once each: the network and weights most of them use, the networks
+at the ABI's limits and the late boards of the shapes file, the crafted boards, the hand-worked games, the refusal tables with the one struct builder, the export and no-scratch checks of the CPU files, and
 for the GPU files the learner regime, the guarded agents and the one device round held to the host (learner_round).  Each test file
 keeps what only it uses, its caches and its assertions.  A helper, not a test."""
 import ctypes as C
@@ -29,13 +29,45 @@ def bits(x):
 
 
 @functools.lru_cache(maxsize=None)
-def weights(name):
-    """float32[n_weights] of TUPLES, read-only: all zero ("zero"), or a seeded normal array of scale 4 ("seeded": V of the order of
-    the rewards)"""
-    n = nt().tuple_offsets(TUPLES)[1]
+def _weights(name, tuples):
+    n = nt().tuple_offsets(tuples)[1]
     w = np.zeros(n, dtype=np.float32) if name == "zero" else (np.random.default_rng(7).standard_normal(n) * 4).astype(np.float32)
     w.setflags(write=False)
     return w
+
+
+def weights(name, tuples=TUPLES):
+    """float32[n_weights] of `tuples`, read-only and made once per (name, tuples): all zero ("zero"), or a seeded normal array of
+    scale 4 ("seeded": V of the order of the rewards)"""
+    return _weights(name, tuple(tuple(t) for t in tuples))
+
+
+# The networks of tests/test_tfe_nt_shapes_gpu.py.  "eight": the limit of 8 tuples, of lengths 1, 2, 3, 4 and 5, on descending and
+# scattered cells, overlapping, one a diagonal; 1,188,368 weights, no multiple of 256: the apply launch's last workgroup is ragged.
+# "one6": the other limit, one tuple of the greatest length, descending, in the board's upper word; 16,777,216 weights.
+SHAPES = dict(eight=((15,), (3, 0), (5, 10, 6), (12, 8, 4, 0), (1, 2, 5, 6, 9), (0, 5, 10, 15), (7, 11), (13, 14, 9)),
+              one6=((15, 14, 13, 11, 10, 9),),
+              default=nt().DEFAULT_TUPLES)
+
+
+@functools.lru_cache(maxsize=None)
+def late_start(n_games, seed):
+    """uint64[n_games], read-only: a `start` of boards late in a game.  Games with g % 4 == 3 get 0 (they begin at their reset
+    boards); every other game gets nibbles drawn from 6..14 with 5 cells emptied, and games with g % 4 == 1 also two adjacent 14s in
+    a row: one move from the 32,768 tile.  Every board that is not 0 is usable: it has empty cells and no nibble 15."""
+    rng = np.random.default_rng(seed)
+    start = np.zeros(n_games, dtype=np.uint64)
+    for g in range(n_games):
+        if g % 4 == 3:
+            continue
+        nib = rng.integers(6, 15, 16)
+        nib[rng.choice(16, 5, replace=False)] = 0
+        if g % 4 == 1:
+            row, col = int(rng.integers(4)), int(rng.integers(3))
+            nib[4 * row + col] = nib[4 * row + col + 1] = 14
+        start[g] = sum(int(x) << (4 * i) for i, x in enumerate(nib))
+    start.setflags(write=False)
+    return start
 
 
 # ------------------------------------------------------------------ boards and games made by hand
@@ -238,12 +270,13 @@ def learner_agent(n_games=GAMES, extra_buffers=(), patterns=PATTERNS, **kw):
 
 
 def search_agent(games, max_steps, seed, name, symmetric=True, **kw):
-    """the agent of a search file's shape with every device buffer re-seated between guard words and weights(name) uploaded"""
+    """the agent of a search file's shape with every device buffer re-seated between guard words and weights(name) of its tuples
+    uploaded"""
     import torch
     from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
     kw = dict(dict(tuples=TUPLES, symmetric=symmetric, max_steps=max_steps, seed=seed, board_id0=BOARD_ID0), **kw)
     a = guard(NTupleTDAfterstateTFEGPU(torch.device("cuda:0"), games, **kw), BUFFERS, **PATTERNS)
-    a.weights_dev.copy_(torch.from_numpy(weights(name).copy()))
+    a.weights_dev.copy_(torch.from_numpy(weights(name, kw["tuples"]).copy()))
     return a
 
 
