@@ -1055,6 +1055,42 @@ typedef struct PulseTfeNtRestartPick {
 } PulseTfeNtRestartPick;
 int pulse_tfe_nt_restart_pick(const PulseTfeNtRestartPick* o, void* stream);
 
+/* ---- ... and weight sets by tile stage ("multi-stage TD"; promoting a stage's weights into a new one is "weight promotion").
+ * Opt-in: a caller that never calls these four keeps every launch above unchanged.
+ *
+ * A staged network is S = n_stages = 1..4 copies of the tables, chosen per board by how far the game has come.  Let m(B) be the
+ * largest nibble of the packed board B and threshold[0] < ... < threshold[S - 2] nibbles in 1..15:
+ *   stage(B) = the number of s with threshold[s] <= m(B)        (threshold[s - 1] is the nibble at which stage s begins)
+ * Stage s owns the weights [s * W, (s + 1) * W), W = net.n_weights (still the sum of 16^len: ONE stage's size), so net.weights is
+ * float[S * W], acc int64[S * W][2], acc_abs int64[S * W]; S * W <= 2^29 by the network's own limits (8 tuples of length 6).  A feature's index is that of the one-stage network plus
+ * stage * W.  V(B) is read in the stage of B itself, the afterstate whose value it is -- float64, tuple-major, image order, as before;
+ * a recorded move's adds go to the stage of keys[t].  Targets need nothing new: values[t + 1] was recorded in whatever stage that
+ * afterstate was in, so a difference crosses a stage boundary by itself.  The learners still read no weight, and the backward walks
+ * are the launches they were.  With n_stages = 1 every output is the parent entry point's, byte for byte.
+ * Bytes of threshold at and beyond n_stages - 1 must be 0.  Zero-initialise the struct: reserved0 must be 0.
+ *
+ * pulse_tfe_nt_rollout_staged: pulse_tfe_nt_rollout_from's contract word for word -- layers 0 or 1, backed only with layers 1, start
+ *   read and zeroed where unusable (all 0: the games from reset) -- with V read by stage.
+ * pulse_tfe_nt_learn_staged: the four learners through the superset struct.  deltas NULL (needs lambda == 0 and backed NULL):
+ *   pulse_tfe_nt_learn's one-step differences; deltas set and backed NULL: pulse_tfe_nt_learn_lambda's walk; backed set (needs
+ *   deltas): pulse_tfe_nt_learn_backed's walk; acc_abs set: the third accumulator.  The walks are the existing launches; the adds go
+ *   to the stage of keys[t].
+ * pulse_tfe_nt_evaluate_staged: layers 0 pulse_tfe_nt_evaluate, layers 1 pulse_tfe_nt_evaluate_search.
+ * pulse_tfe_nt_search_staged: pulse_tfe_nt_search, one chance layer.
+ * The apply launches need nothing new: pulse_tfe_nt_apply / pulse_tfe_nt_apply_tc once per stage on that stage's slice of weights,
+ * acc, acc_abs, e and a (tc_stats is added to).
+ *
+ * PULSE_EINVAL, before anything is launched: everything the parent entry point refuses, under the new name; null stages; n_stages
+ * outside 1..4; a threshold outside 1..15 or not strictly increasing; a non-zero byte beyond n_stages - 1; reserved0 not 0;
+ * `layers` outside what the entry point takes (two layers are not built on stages). */
+#define PULSE_TFE_NT_MAX_STAGES 4
+typedef struct PulseTfeNtStages { int32_t n_stages; uint8_t threshold[4]; int64_t reserved0; } PulseTfeNtStages;  /* 16 bytes */
+int pulse_tfe_nt_rollout_staged(const PulseTfeNtRollout* o, const PulseTfeNtStages* stages, int32_t layers, double* backed, uint64_t* start,
+                                void* stream);
+int pulse_tfe_nt_learn_staged(const PulseTfeNtLearnBacked* o, const PulseTfeNtStages* stages, void* stream);
+int pulse_tfe_nt_evaluate_staged(const PulseTfeNtEval* o, const PulseTfeNtStages* stages, int32_t layers, void* stream);
+int pulse_tfe_nt_search_staged(const PulseTfeNtSearch* o, const PulseTfeNtStages* stages, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

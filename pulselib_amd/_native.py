@@ -148,6 +148,7 @@ class TfeMCMerge(C.Structure):
 
 # the 2048 n-tuple network (include/pulse_env.h): the network heads the structs
 TFE_NT_MAX_TUPLES, TFE_NT_MAX_LEN, TFE_NT_FRAC_BITS, TFE_NT_DELTA_MAX = 8, 6, 16, 8192.0
+TFE_NT_MAX_STAGES = 4
 _TFE_NT_SEEDS = [(n, C.c_uint64) for n in ("env_seed", "agent_seed", "tie_seed", "board_id0", "round")]
 
 
@@ -187,6 +188,10 @@ class TfeNtLearnBacked(C.Structure):                                        # Tf
 class TfeNtRestartPick(C.Structure):
     _fields_ = [("n_games", C.c_int32), ("max_steps", C.c_int32), ("env_seed", C.c_uint64), ("board_id0", C.c_uint64), ("fraction", C.c_double),
                 ("min_length", C.c_int32), ("reserved0", C.c_int32)] + [(n, C.c_void_p) for n in ("keys", "lengths", "start", "picked")]
+
+
+class TfeNtStages(C.Structure):                                             # weight sets by tile stage: beside the struct of a *_staged entry point
+    _fields_ = [("n_stages", C.c_int32), ("threshold", C.c_uint8 * 4), ("reserved0", C.c_int64)]
 
 
 class TfeNtApplyTc(C.Structure):
@@ -281,6 +286,10 @@ SYMBOLS = {
     "pulse_tfe_nt_learn_backed": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_rollout_from": (C.c_int, [_P, _I32, _P, _P, _P]),
     "pulse_tfe_nt_restart_pick": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_rollout_staged": (C.c_int, [_P, _P, _I32, _P, _P, _P]),
+    "pulse_tfe_nt_learn_staged": (C.c_int, [_P, _P, _P]),
+    "pulse_tfe_nt_evaluate_staged": (C.c_int, [_P, _P, _I32, _P]),
+    "pulse_tfe_nt_search_staged": (C.c_int, [_P, _P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

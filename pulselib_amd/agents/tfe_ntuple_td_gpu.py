@@ -31,9 +31,16 @@ and `learn_backed_nt_on_host` state them on the host.
 With the attribute `restart_fraction` > 0 (section 13.7; csrc/tfe_ntuple_restart.hip) `learn_batch` ends with a fourth launch,
 `pulse_tfe_nt_restart_pick`, which writes into `start` the board every long enough game of the round stood on at that fraction of its
 length, and the next round's games begin there (`pulse_tfe_nt_rollout_from`) instead of at their reset boards: the "restart" strategy
-of the n-tuple 2048 literature.  `spawn_on_host` and `restart_pick_on_host` state the pick on the host."""
+of the n-tuple 2048 literature.  `spawn_on_host` and `restart_pick_on_host` state the pick on the host.
+
+With `stage_tiles` (section 13.9; csrc/tfe_ntuple_staged.hip) the network is S = len(stage_tiles) + 1 copies of its tables, and a board
+reads -- a recorded move adds to -- the copy of its stage, the number of those tiles its largest tile has reached: multi-stage TD.
+Every launch of a round then goes through the four `pulse_tfe_nt_*_staged` entry points and one apply launch per stage; `add_stage`
+splits a stage in two at a tile, the new one starting as a copy (weight promotion).  On the host the stages travel on `tuples`
+(`with_stages`), so every mirror above reads and adds by stage; `stage_of_keys_on_host` states the stage."""
 from __future__ import annotations
 
+import ctypes as C
 import functools
 
 import numpy as np
@@ -44,12 +51,14 @@ from .tfe_common import (AGENT_KEY, EVAL_BINS, TIE_KEY, _TFEGamesGPU, greedy_sca
 from .tfe_common import eval_summary_on_host as _eval_summary_on_host
 
 MAX_TUPLES, MAX_LEN, FRAC_BITS, DELTA_MAX = _native.TFE_NT_MAX_TUPLES, _native.TFE_NT_MAX_LEN, _native.TFE_NT_FRAC_BITS, _native.TFE_NT_DELTA_MAX
+MAX_STAGES = _native.TFE_NT_MAX_STAGES
 DEFAULT_TUPLES = ((0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 2, 4, 5, 6), (4, 5, 6, 8, 9, 10))       # two rows and two 2 x 3 rectangles
 STATS = ("moves", "learnt", "skipped", "truncated", "clamped")                                # words 0..4 of the stats buffer
 EVAL_SUMMARY = ("games", "moves", "score_sum", "score_sq_sum", "max_score", "truncated", "moves_greedy", "tile_capped")
 CHECKPOINT_VERSION = 1                                                                        # what an agent with lam == 0 writes
 CHECKPOINT_VERSION_LAMBDA = 2                                                                 # ... and with lam != 0: version 1's arrays and `lam`
 CHECKPOINT_VERSION_TC = 4                                                                     # ... and with tc: version 2's and tc_index / tc_e / tc_a (3 is not a format)
+CHECKPOINT_VERSION_STAGED = 5                                                                 # ... and with stage_tiles: version 2's or 4's arrays over S * W weights and `stage_tiles`
 TC_RHO_BITS = 32                                                                              # rho is summed as llrint(rho * 2^32)
 CHECKPOINT_SCALARS = ("symmetric", "gamma", "epsilon", "alpha", "max_steps", "seed", "board_id0", "round", "n_games")
 _U64 = np.uint64
@@ -58,6 +67,7 @@ _U64 = np.uint64
 # ------------------------------------------------------------------ the network's shape
 def check_tuples(tuples) -> tuple:
     """The tuples as a tuple of tuples of ints, after the library's own checks (ValueError)."""
+    stage_tiles = stage_tiles_of(tuples)
     tuples = tuple(tuple(int(c) for c in t) for t in tuples)
     if not 1 <= len(tuples) <= MAX_TUPLES:
         raise ValueError(f"n_tuples must be in 1..{MAX_TUPLES}")
@@ -66,7 +76,58 @@ def check_tuples(tuples) -> tuple:
             raise ValueError(f"a tuple's length must be in 1..{MAX_LEN}")
         if any(not 0 <= c <= 15 for c in t) or len(set(t)) != len(t):
             raise ValueError("a tuple's cells must be distinct and in 0..15")
-    return tuples
+    return StagedTuples(tuples, stage_tiles) if stage_tiles else tuples
+
+
+# ------------------------------------------------------------------ weight sets by tile stage
+def check_stage_tiles(stage_tiles) -> tuple:
+    """The tiles at which the stages 1, 2, ... begin, as a tuple of ints: at most MAX_STAGES - 1 powers of two in 2..32,768, strictly
+    increasing (ValueError otherwise; a bool is no tile).  () is the one-stage network."""
+    tiles = tuple(stage_tiles)
+    if any(isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer)) for t in tiles):
+        raise ValueError("a stage tile must be an int")
+    tiles = tuple(int(t) for t in tiles)
+    if len(tiles) > MAX_STAGES - 1:
+        raise ValueError(f"at most {MAX_STAGES - 1} stage tiles ({MAX_STAGES} stages)")
+    if any(not 2 <= t <= 32768 or t & (t - 1) for t in tiles):
+        raise ValueError("a stage tile must be a power of two in 2..32768")
+    if any(b <= a for a, b in zip(tiles, tiles[1:])):
+        raise ValueError("the stage tiles must be strictly increasing")
+    return tiles
+
+
+class StagedTuples(tuple):
+    """The tuples of a network with weight sets by stage: a tuple of tuples like any other, with the tiles at which its stages begin
+    as `stage_tiles`.  Every host mirror takes `tuples`; handed these, it reads and adds by stage."""
+    def __new__(cls, tuples, stage_tiles):
+        self = super().__new__(cls, tuples)
+        self.stage_tiles = check_stage_tiles(stage_tiles)
+        return self
+
+
+def with_stages(tuples, stage_tiles):
+    """`tuples` (checked) carrying `stage_tiles`; with () the plain tuples of the one-stage network."""
+    plain = check_tuples(tuple(tuple(t) for t in tuples))
+    tiles = check_stage_tiles(stage_tiles)
+    return StagedTuples(plain, tiles) if tiles else plain
+
+
+def stage_tiles_of(tuples) -> tuple:
+    """The stage tiles `tuples` carries: () unless they are StagedTuples."""
+    return tuple(getattr(tuples, "stage_tiles", ()))
+
+
+def stage_of_keys_on_host(keys, stage_tiles) -> np.ndarray:
+    """int64[len(keys)]: the stage of packed boards = the number of `stage_tiles` whose nibble (log2 of the tile) is at most the board's
+    largest nibble.  The empty board is in stage 0; () puts every board there."""
+    keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
+    top = np.zeros(len(keys), dtype=np.int64)
+    for c in range(16):
+        top = np.maximum(top, ((keys >> _U64(4 * c)) & _U64(15)).astype(np.int64))
+    stage = np.zeros(len(keys), dtype=np.int64)
+    for tile in check_stage_tiles(stage_tiles):
+        stage += top >= tile.bit_length() - 1
+    return stage
 
 
 def check_lam(lam) -> float:
@@ -78,9 +139,29 @@ def check_lam(lam) -> float:
 
 
 def tuple_offsets(tuples):
-    """(offsets, n_weights): tuple t's table of 16^len weights starts at the sum of the earlier tables' sizes."""
+    """(offsets, n_weights): tuple t's table of 16^len weights starts at the sum of the earlier tables' sizes.  n_weights is ONE stage's."""
     sizes = [16 ** len(t) for t in tuples]
     return [sum(sizes[:i]) for i in range(len(sizes))], sum(sizes)
+
+
+def add_stage_on_host(arrays, tuples, tile, copy=True):
+    """add_stage on the host: (the arrays grown by one stage, `tuples` carrying the stage tiles with `tile` among them).  Every array of
+    `arrays` holds n_stages slices of equal length along its first axis; the stage that holds `tile` is split at it and the new, upper
+    stage's slice is a copy of the slice it is split from (copy: the weights, E and A) or zero (the accumulators).  ValueError if a
+    stage begins at `tile` already or MAX_STAGES stages exist."""
+    (tile,), old = check_stage_tiles((tile,)), stage_tiles_of(tuples)
+    if tile in old:
+        raise ValueError(f"a stage begins at tile {tile} already")
+    if len(old) + 1 >= MAX_STAGES:
+        raise ValueError(f"the network has {MAX_STAGES} stages already")
+    tiles = tuple(sorted(old + (tile,)))
+    new = tiles.index(tile) + 1                                             # the new stage; it is split from stage new - 1
+    grown = []
+    for x in arrays:
+        rows = np.asarray(x).reshape((len(old) + 1, -1) + np.asarray(x).shape[1:])
+        rows = np.insert(rows, new, rows[new - 1] if copy else 0, axis=0)
+        grown.append(np.ascontiguousarray(rows.reshape((-1,) + rows.shape[2:])))
+    return grown, with_stages(tuples, tiles)
 
 
 def feature_cells_on_host(tuples, symmetric=True) -> list:
@@ -91,15 +172,18 @@ def feature_cells_on_host(tuples, symmetric=True) -> list:
 
 
 def feature_indices_on_host(keys, tuples, symmetric=True) -> np.ndarray:
-    """int64[len(keys), F]: the weights an afterstate reads, tuple-major and image j within a tuple (the order V is summed in)."""
+    """int64[len(keys), F]: the weights an afterstate reads, tuple-major and image j within a tuple (the order V is summed in).  Where
+    `tuples` carry stage tiles (with_stages) every index is in the slice of the afterstate's own stage: + stage * n_weights."""
     keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
     nib = np.stack([(keys >> _U64(4 * c)) & _U64(15) for c in range(16)], axis=1).astype(np.int64)
-    offsets, _ = tuple_offsets(tuples)
+    offsets, n_weights = tuple_offsets(tuples)
     cols = []
     for off, cells in zip(offsets, feature_cells_on_host(tuples, symmetric)):
         for image in cells:
             cols.append(off + sum(nib[:, int(c)] << (4 * i) for i, c in enumerate(image)))
-    return np.stack(cols, axis=1)
+    idx = np.stack(cols, axis=1)
+    stage_tiles = stage_tiles_of(tuples)
+    return idx + (stage_of_keys_on_host(keys, stage_tiles) * n_weights)[:, None] if stage_tiles else idx
 
 
 def value_on_host(keys, weights, tuples, symmetric=True) -> np.ndarray:
@@ -449,13 +533,14 @@ def eval_summary_on_host(words) -> dict:
 
 
 # ------------------------------------------------------------------ the checkpoint file
-def write_checkpoint(path, weights, tuples, lam=0.0, tc=None, **scalars) -> None:
+def write_checkpoint(path, weights, tuples, lam=0.0, tc=None, stage_tiles=(), **scalars) -> None:
     """The network as an .npz of plain arrays (np.savez, no pickles): the non-zero weights as index int64[m] (ascending) and value
     float32[m], the tuples as tuple_len int64[n_tuples] and tuple_cells int64[n_tuples, 6] (-1 beyond a tuple's length), the scalars of
     CHECKPOINT_SCALARS as 0-d arrays and `version`.  lam == 0 writes exactly that, as version 1; any other `lam` adds a 0-d float64
     `lam` and writes version 2.  tc = (E, A), float64[n_weights] each, writes version 4: version 2's arrays with `lam` whatever its
-    value, tc_index int64[m'] (ascending: the weights whose E or A is not +0.0 by bit pattern) and tc_e / tc_a float64[m'].  `path` is
-    written as given."""
+    value, tc_index int64[m'] (ascending: the weights whose E or A is not +0.0 by bit pattern) and tc_e / tc_a float64[m'].
+    stage_tiles other than () writes version 5: version 2's arrays (with `lam` whatever its value) or, with tc, version 4's, every index
+    over the S * W weights of the staged network, and stage_tiles int64[S - 1].  `path` is written as given."""
     if sorted(scalars) != sorted(CHECKPOINT_SCALARS):
         raise ValueError(f"a checkpoint holds exactly the scalars {CHECKPOINT_SCALARS}")
     weights = np.asarray(weights, dtype=np.float32).reshape(-1)
@@ -465,8 +550,8 @@ def write_checkpoint(path, weights, tuples, lam=0.0, tc=None, **scalars) -> None
         cells[i, :len(t)] = t
     dtypes = dict(gamma=np.float64, epsilon=np.float64, alpha=np.float64, seed=np.uint64, board_id0=np.uint64)
     arrays = {k: np.array(scalars[k], dtype=dtypes.get(k, np.int64)) for k in CHECKPOINT_SCALARS}
-    version = CHECKPOINT_VERSION
-    if float(lam) != 0.0 or tc is not None:
+    version, stage_tiles = CHECKPOINT_VERSION, check_stage_tiles(stage_tiles)
+    if float(lam) != 0.0 or tc is not None or stage_tiles:
         arrays["lam"], version = np.array(lam, dtype=np.float64), CHECKPOINT_VERSION_LAMBDA
     if tc is not None:
         E, A = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1) for x in tc)
@@ -475,36 +560,48 @@ def write_checkpoint(path, weights, tuples, lam=0.0, tc=None, **scalars) -> None
         at = np.flatnonzero((E.view(np.uint64) != 0) | (A.view(np.uint64) != 0))
         arrays.update(tc_index=at.astype(np.int64), tc_e=E[at], tc_a=A[at])
         version = CHECKPOINT_VERSION_TC
+    if stage_tiles:
+        arrays["stage_tiles"], version = np.array(stage_tiles, dtype=np.int64), CHECKPOINT_VERSION_STAGED
     with open(path, "wb") as fh:
         np.savez(fh, version=np.array(version, dtype=np.int64), index=index.astype(np.int64), value=weights[index],
                  tuple_len=np.array([len(t) for t in tuples], dtype=np.int64), tuple_cells=cells, **arrays)
 
 
 def read_checkpoint(path) -> dict:
-    """What write_checkpoint wrote (np.load with allow_pickle=False), version 1, 2 or 4: `tuples`, `index`, `value`, `n_weights`, the
-    scalars as Python numbers, `lam` (0.0 for version 1) and `tc` (False for versions 1 and 2); for version 4 also `tc_index`, `tc_e`
-    and `tc_a`.  ValueError for another format version, a missing array, tuples the library would refuse or an index outside the
-    network."""
+    """What write_checkpoint wrote (np.load with allow_pickle=False), version 1, 2, 4 or 5: `tuples`, `index`, `value`, `n_weights`, the
+    scalars as Python numbers, `lam` (0.0 for version 1), `tc` (False for versions 1 and 2) and `stage_tiles` (() below version 5); with
+    tc also `tc_index`, `tc_e` and `tc_a`.  For version 5 `n_weights` is S * W, all stages', and `tc` says whether the file holds the tc
+    arrays.  ValueError for another format version, a missing array, tuples or stage tiles the library would refuse or an index outside
+    the network."""
     with np.load(path, allow_pickle=False) as f:
         missing = [k for k in ("version", "index", "value", "tuple_len", "tuple_cells") + CHECKPOINT_SCALARS if k not in f.files]
         if missing:
             raise ValueError(f"{path}: not an n-tuple network checkpoint (no {missing})")
         version = int(f["version"])
-        if version not in (CHECKPOINT_VERSION, CHECKPOINT_VERSION_LAMBDA, CHECKPOINT_VERSION_TC):
-            raise ValueError(f"{path}: format version {version}, this package reads {CHECKPOINT_VERSION}, {CHECKPOINT_VERSION_LAMBDA} and "
-                             f"{CHECKPOINT_VERSION_TC}")
-        more = {CHECKPOINT_VERSION: (), CHECKPOINT_VERSION_LAMBDA: ("lam",), CHECKPOINT_VERSION_TC: ("lam", "tc_index", "tc_e", "tc_a")}[version]
+        if version not in (CHECKPOINT_VERSION, CHECKPOINT_VERSION_LAMBDA, CHECKPOINT_VERSION_TC, CHECKPOINT_VERSION_STAGED):
+            raise ValueError(f"{path}: format version {version}, this package reads {CHECKPOINT_VERSION}, {CHECKPOINT_VERSION_LAMBDA}, "
+                             f"{CHECKPOINT_VERSION_TC} and {CHECKPOINT_VERSION_STAGED}")
+        if version == CHECKPOINT_VERSION_STAGED and "stage_tiles" not in f.files:
+            raise ValueError(f"{path}: format version {version} is a staged network's, and the file holds no stage_tiles")
+        tc_names = ("tc_index", "tc_e", "tc_a")
+        has_tc = version == CHECKPOINT_VERSION_TC or (version == CHECKPOINT_VERSION_STAGED and any(k in f.files for k in tc_names))
+        more = ("lam",) * (version != CHECKPOINT_VERSION) + tc_names * has_tc
+        if version == CHECKPOINT_VERSION_STAGED:
+            more += ("stage_tiles",)
         missing = [k for k in more if k not in f.files]
         if missing:
             raise ValueError(f"{path}: not an n-tuple network checkpoint (no {missing})")
         out = {k: (float(f[k]) if k in ("gamma", "epsilon", "alpha") else int(f[k])) for k in CHECKPOINT_SCALARS}
         out["lam"] = float(f["lam"]) if "lam" in more else 0.0
-        out["tc"] = version == CHECKPOINT_VERSION_TC
+        out["tc"] = has_tc
         index, value, lens, cells = f["index"], f["value"], f["tuple_len"], f["tuple_cells"]
-        tc_arrays = [f[k] for k in more[1:]]
+        tc_arrays = [f[k] for k in tc_names * has_tc]
+        out["stage_tiles"] = check_stage_tiles(f["stage_tiles"].tolist()) if version == CHECKPOINT_VERSION_STAGED else ()
+    if version == CHECKPOINT_VERSION_STAGED and not out["stage_tiles"]:
+        raise ValueError(f"{path}: a version {CHECKPOINT_VERSION_STAGED} checkpoint holds at least one stage tile")
     out["symmetric"] = bool(out["symmetric"])
-    out["tuples"] = check_tuples([cells[i, :int(n)].tolist() for i, n in enumerate(lens.tolist())])
-    out["n_weights"] = tuple_offsets(out["tuples"])[1]
+    out["tuples"] = with_stages([cells[i, :int(n)].tolist() for i, n in enumerate(lens.tolist())], out["stage_tiles"])
+    out["n_weights"] = tuple_offsets(out["tuples"])[1] * (len(out["stage_tiles"]) + 1)
     if index.dtype != np.int64 or value.dtype != np.float32 or index.shape != value.shape or index.ndim != 1:
         raise ValueError(f"{path}: index must be int64[m] and value float32[m]")
     if len(index) and (int(index[0]) < 0 or int(index[-1]) >= out["n_weights"] or not bool((index[1:] > index[:-1]).all())):
@@ -535,7 +632,22 @@ def weights_of_checkpoint(f: dict) -> np.ndarray:
 
 
 # ------------------------------------------------------------------ the device agent
-class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
+class _TakesStageTiles(type):
+    """The agent's call: NTupleTDAfterstateTFEGPU(..., stage_tiles=()) sets the attribute `stage_tiles` (checked) before __init__ runs,
+    which takes the other arguments.  __init__'s own parameters are the agent's as it was without stages -- the tests of sections 13.6
+    and 13.7 hold them to that list -- and the opt-ins since are attributes; this one sizes the allocations, so it has to be known when
+    __init__ makes them.  Two consequences: inspect.signature of the class shows this call's (*args, stage_tiles=(), **kw), not
+    __init__'s parameters (ask inspect.signature(cls.__init__) for those), and a subclass that builds instances another way -- its own
+    __new__, a classmethod that calls __init__ itself -- must set `stage_tiles` on the instance before __init__ runs, or leave the
+    class's default (): the one-stage network."""
+    def __call__(cls, *args, stage_tiles=(), **kw):
+        self = cls.__new__(cls)
+        self.stage_tiles = check_stage_tiles(stage_tiles)
+        self.__init__(*args, **kw)
+        return self
+
+
+class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
     """`learn_batch` = `rollout` + `learn` + `apply` + `round += 1`: three launches and no synchronisation.  Everything that reads
     back (`weights`, `stats`, `trajectory`, `evaluate`, the per-game arrays' `.cpu()`) synchronises.  Round r plays the boards
     board_id0 + r * n_games + g, so no two rounds replay the same spawns.  `lam` > 0: `learn` is the TD(lambda) launch and the agent
@@ -551,31 +663,136 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     ends with the pick launch, which fills `start` (uint64[n_games], allocated at first use, as `restart_stats` int64[2] is) from the
     games of at least `restart_min_length` moves (an attribute, 64 by default: a starting point, not tuned), and `rollout` starts the
     next round's games there; with `rollout_layers` 2 it is refused.  No checkpoint holds either, and `start` is not saved: a loaded
-    agent's next round starts at the reset boards."""
+    agent's next round starts at the reset boards.  `stage_tiles` (section 13.9; () by default: the agent as it was, launches, allocations
+    and checkpoint files): up to three tiles, powers of two, strictly increasing, at which the stages 1, 2, ... begin.  `weights_dev`,
+    `acc` and the TC state then hold S * W words, stage s in [s * W, (s + 1) * W) with W = `n_weights`; rollout, learn, evaluate,
+    evaluate_search and search go through the `pulse_tfe_nt_*_staged` entry points under the agent's `lam`, `tc`, `rollout_layers` 0 or
+    1, `backed_targets` and `restart_fraction`, and apply is one launch per stage; two chance layers are refused (ValueError, before
+    anything is touched).  `tuples` carries the stage tiles (with_stages), so the host mirrors handed `agent.tuples` read by stage."""
     STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
     restart_fraction = 0.0                                                 # set on the agent; checked at the launch (check_restart_fraction)
     restart_min_length = 64                                                # set on the agent; checked by the pick launch
     start = restart_stats = None                                           # allocated by the first restart launch
     rollout_layers = 0                                                     # set on the agent; checked at the launch (check_rollout_layers)
     backed_targets = False                                                 # set on the agent; checked at the launch, with rollout_layers
+    stage_tiles = ()                                                       # set by the call (stage_tiles=...), before __init__ allocates; add_stage grows it
 
     def __init__(self, device, n_games, tuples=DEFAULT_TUPLES, symmetric=True, gamma=1.0, epsilon=0.0, alpha=1.0, max_steps=4096, seed=0,
                  board_id0=0, lam=0.0, tc=False):
         import torch
-        self.lam, self.tc = check_lam(lam), bool(tc)
+        self.lam, self.tc, self.stage_tiles = check_lam(lam), bool(tc), check_stage_tiles(self.stage_tiles or stage_tiles_of(tuples))
         super().__init__(device, n_games, 4, max_steps, gamma, epsilon, seed, board_id0)
-        self.tuples, self.symmetric, self.alpha = check_tuples(tuples), bool(symmetric), float(alpha)
+        self.tuples, self.symmetric, self.alpha = with_stages(tuples, self.stage_tiles), bool(symmetric), float(alpha)
         self.n_features = len(self.tuples) * (8 if self.symmetric else 1)
         if not 0.0 < self.alpha <= self.n_features:
             raise ValueError("alpha must be in (0, F]: the apply launch takes step = alpha / F in (0, 1]")
         self.offsets, self.n_weights = tuple_offsets(self.tuples)
-        self.weights_dev = torch.zeros(self.n_weights, dtype=torch.float32, device=self.device)
-        self.acc = torch.zeros((self.n_weights, 2), dtype=torch.int64, device=self.device)            # {sum, cnt}; torch allocations are 16-byte aligned
+        self.weights_dev = torch.zeros(self.total_weights, dtype=torch.float32, device=self.device)
+        self.acc = torch.zeros((self.total_weights, 2), dtype=torch.int64, device=self.device)        # {sum, cnt}; torch allocations are 16-byte aligned
         self.values = torch.zeros((self.max_steps, self.n_games), dtype=torch.float64, device=self.device)
         self.deltas = torch.zeros_like(self.values) if self.lam > 0.0 else None
         self.acc_abs = self.E = self.A = self.tc_stats = self.backed = None
         if self.tc:
             self._tc_state()
+
+    # ------------------------------------------------------------------ weight sets by tile stage (DESIGN.md section 13.9)
+    @property
+    def n_stages(self) -> int:
+        return len(self.stage_tiles) + 1
+
+    @property
+    def total_weights(self) -> int:
+        """The weights of all stages: n_stages * n_weights (n_weights is one stage's, what the library's network struct holds)."""
+        return self.n_stages * self.n_weights
+
+    def _stages(self):
+        """PulseTfeNtStages of the agent's stage tiles: threshold[s - 1] = log2 of the tile at which stage s begins."""
+        st = _native.TfeNtStages()
+        st.n_stages = self.n_stages
+        for i, tile in enumerate(self.stage_tiles):
+            st.threshold[i] = tile.bit_length() - 1
+        return st
+
+    def _refuse_two_layers(self, layers, what):
+        if self.stage_tiles and layers == 2:
+            raise ValueError(f"{what} = 2 on an agent with stage_tiles: two chance layers are not built on stages")
+
+    def add_stage(self, tile):
+        """Weight promotion: the stage that holds `tile` is split at it.  The new, upper stage's weights -- with tc its E and A too --
+        start as a copy of the stage it is split from, and its accumulators are zero, so V of every board is what it was right after
+        the call; from then on the boards whose largest tile has reached `tile` learn apart.  ValueError if `tile` is no stage tile,
+        begins a stage already, or the agent has MAX_STAGES stages.  Reallocates `weights_dev`, `acc` and the TC state."""
+        import torch
+        (tile,) = check_stage_tiles((tile,))
+        if tile in self.stage_tiles:
+            raise ValueError(f"a stage begins at tile {tile} already")
+        if self.n_stages >= MAX_STAGES:
+            raise ValueError(f"the agent has {MAX_STAGES} stages already")
+        tiles = tuple(sorted(self.stage_tiles + (tile,)))
+        new = tiles.index(tile) + 1                                         # the new stage; it is split from stage new - 1
+        source = [s if s < new else s - 1 for s in range(len(tiles) + 1)]
+        W = self.n_weights
+
+        def grown(t, copy):
+            rows = t.reshape(self.n_stages, -1)
+            out = torch.stack([rows[src] if copy or s != new else torch.zeros_like(rows[src]) for s, src in enumerate(source)])
+            return out.reshape((len(source) * W,) + tuple(t.shape[1:])).contiguous()
+        self.weights_dev, self.acc = grown(self.weights_dev, True), grown(self.acc, False)
+        if self.acc_abs is not None:
+            self.acc_abs, self.E, self.A = grown(self.acc_abs, False), grown(self.E, True), grown(self.A, True)
+        self.stage_tiles = tiles
+        self.tuples = with_stages(self.tuples, tiles)
+        return self
+
+    def rollout_staged_launch(self, layers, backed=False):
+        """pulse_tfe_nt_rollout_staged alone: rollout_from_launch's games (layers 0 or 1, `backed` with 1) with V read by stage, begun
+        on the boards of `start` where usable."""
+        import torch
+        self._refuse_two_layers(layers, "layers")
+        if isinstance(layers, bool) or layers not in (0, 1):
+            raise ValueError("layers must be 0 or 1")
+        if backed and not layers:
+            raise ValueError("backed needs layers = 1: a one-ply roll-out has no search to back a value up")
+        self._restart_state()
+        if backed and self.backed is None:
+            self.backed = torch.zeros_like(self.values)
+        return self._launch("pulse_tfe_nt_rollout_staged", self._rollout_struct(), C.byref(self._stages()), int(layers),
+                            self.backed.data_ptr() if backed else None, self.start.data_ptr())
+
+    def learn_staged_launch(self, lam, backed=False, tc=False):
+        """pulse_tfe_nt_learn_staged alone on the games last played: learn()'s adds (lam == 0 without backed: no deltas), the walk of
+        learn_lambda_launch (lam > 0) or of learn_backed_launch (backed) into `deltas` first, with tc |d| into `acc_abs` as well; every
+        move's adds go to the stage of its afterstate.  Allocates what the agent lacks of `deltas` and the TC state."""
+        import torch
+        lam = check_lam(lam)
+        if backed and self.backed is None:
+            raise ValueError("no roll-out with backed values has run: the agent holds no backed")
+        o = self._moves(_native.TfeNtLearnBacked())
+        o.lam = lam
+        if backed or lam > 0.0:
+            if self.deltas is None:
+                self.deltas = torch.zeros_like(self.values)
+            o.deltas = self.deltas.data_ptr()
+        if backed:
+            o.backed = self.backed.data_ptr()
+        if tc:
+            self._tc_state()
+            o.acc_abs = self.acc_abs.data_ptr()
+        return self._launch("pulse_tfe_nt_learn_staged", o, C.byref(self._stages()))
+
+    def _apply_staged(self):
+        """pulse_tfe_nt_apply, or with tc pulse_tfe_nt_apply_tc, once per stage on that stage's slice of weights, acc, acc_abs, E and A."""
+        W = self.n_weights
+        for s in range(self.n_stages):
+            o = _native.TfeNtApplyTc() if self.tc else _native.TfeNtApply()
+            self._net(o.net)
+            o.net.weights = self.weights_dev[s * W:].data_ptr()
+            o.step, o.acc = self.alpha / self.n_features, self.acc[s * W:].data_ptr()
+            if self.tc:
+                o.acc_abs, o.e, o.a = self.acc_abs[s * W:].data_ptr(), self.E[s * W:].data_ptr(), self.A[s * W:].data_ptr()
+                o.tc_stats = self.tc_stats.data_ptr()
+            self._launch("pulse_tfe_nt_apply_tc" if self.tc else "pulse_tfe_nt_apply", o)
+        return self
 
     # ------------------------------------------------------------------ the launches
     def _net(self, net):
@@ -600,14 +817,21 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         rollout_search_launch, greedy on the q of the search that deep.  ValueError for any other.  With `backed_targets` the depth
         must be 1 or 2 (ValueError otherwise, before anything is touched) and the launch is rollout_backed_launch.  With
         `restart_fraction` > 0 the depth must be 0 or 1 (ValueError otherwise, before anything is touched), and once a pick has filled
-        `start` the launch is rollout_from_launch at that depth, with the backed values if `backed_targets`."""
+        `start` the launch is rollout_from_launch at that depth, with the backed values if `backed_targets`.  With `stage_tiles` the
+        depth must be 0 or 1 and the launch is rollout_staged_launch, from `start` (zeroed here while restart_fraction is 0)."""
         layers = check_rollout_layers(self.rollout_layers if layers is None else layers)
         restart = check_restart_fraction(self.restart_fraction) > 0.0
+        self._refuse_two_layers(layers, "rollout_layers")
         if restart and layers == 2:
             raise ValueError("restart_fraction > 0 needs rollout_layers in (0, 1): the restarted roll-out is not built two layers deep")
+        if self.backed_targets and not layers:
+            raise ValueError("backed_targets needs rollout_layers in (1, 2): a one-ply roll-out has no search to back a value up")
+        if self.stage_tiles:                                                # one entry point: from `start`, all zero while restarts are off
+            self._restart_state()
+            if not restart:
+                self.start.zero_()
+            return self.rollout_staged_launch(layers, backed=bool(self.backed_targets))
         if self.backed_targets:
-            if not layers:
-                raise ValueError("backed_targets needs rollout_layers in (1, 2): a one-ply roll-out has no search to back a value up")
             if restart and self.start is not None:
                 return self.rollout_from_launch(layers, backed=True)
             return self.rollout_backed_launch(layers)
@@ -693,14 +917,17 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         """The third accumulator, E, A and tc_stats, zeroed, where the agent has none yet."""
         import torch
         if self.acc_abs is None:
-            self.acc_abs = torch.zeros(self.n_weights, dtype=torch.int64, device=self.device)
-            self.E = torch.zeros(self.n_weights, dtype=torch.float64, device=self.device)
-            self.A = torch.zeros(self.n_weights, dtype=torch.float64, device=self.device)
+            self.acc_abs = torch.zeros(self.total_weights, dtype=torch.int64, device=self.device)
+            self.E = torch.zeros(self.total_weights, dtype=torch.float64, device=self.device)
+            self.A = torch.zeros(self.total_weights, dtype=torch.float64, device=self.device)
             self.tc_stats = torch.zeros(4, dtype=torch.int64, device=self.device)
 
     def learn(self):
         """The temporal differences of the games last played, into the accumulators: one launch, or with lam > 0
-        learn_lambda_launch's two; with tc, learn_tc_launch's; with backed_targets, learn_backed_launch's."""
+        learn_lambda_launch's two; with tc, learn_tc_launch's; with backed_targets, learn_backed_launch's; with stage_tiles,
+        learn_staged_launch's under the same three."""
+        if self.stage_tiles:
+            return self.learn_staged_launch(self.lam, backed=bool(self.backed_targets), tc=self.tc)
         if self.backed_targets:
             return self.learn_backed_launch(self.lam)
         if self.tc:
@@ -764,7 +991,9 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
 
     def apply(self):
         """One launch: every visited weight moves by alpha / F of the mean of its adds; the accumulators are zero afterwards.  With
-        tc, apply_tc_launch."""
+        tc, apply_tc_launch.  With stage_tiles, either once per stage on that stage's slices."""
+        if self.stage_tiles:
+            return self._apply_staged()
         if self.tc:
             return self.apply_tc_launch()
         o = _native.TfeNtApply()
@@ -789,23 +1018,28 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         return o
 
     def _eval_launch(self, o):
+        if self.stage_tiles:                                                # (_under_search has refused two layers)
+            return self._launch("pulse_tfe_nt_evaluate_staged", o, C.byref(self._stages()), self._eval_layers)
         self._launch(self._eval_entry, o, *self._eval_args)
 
     # ------------------------------------------------------------------ expectimax search (DESIGN.md sections 13.1 and 13.4)
-    _eval_entry, _eval_args = "pulse_tfe_nt_evaluate", ()
+    _eval_entry, _eval_args, _eval_layers = "pulse_tfe_nt_evaluate", (), 0     # the evaluation one ply deep; _under_search sets the three for one call
 
     def _under_search(self, layers, call, *args):
         """call(*args) with the evaluation's entry point set to the search's: at one layer pulse_tfe_nt_evaluate_search, at two
         pulse_tfe_nt_evaluate_search_deep with the depth beside the struct."""
-        if check_layers(layers) == 1:
+        self._refuse_two_layers(check_layers(layers), "layers")
+        if layers == 1:
             self._eval_entry = "pulse_tfe_nt_evaluate_search"
         else:
             self._eval_entry, self._eval_args = "pulse_tfe_nt_evaluate_search_deep", (layers,)
+        self._eval_layers = int(layers)
         try:
             return call(*args)
         finally:
             self.__dict__.pop("_eval_entry", None)
             self.__dict__.pop("_eval_args", None)
+            self.__dict__.pop("_eval_layers", None)
 
     def _search_struct(self, boards, q, action, candidates):
         o = _native.TfeNtSearch()
@@ -818,7 +1052,10 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         """The launch of search() alone on device tensors: boards int64[N] (the keys' words), q float64[N, 4], action int8[N],
         candidates uint8[N].  layers = 1: pulse_tfe_nt_search; layers = 2: pulse_tfe_nt_search_deep (ValueError for any other)."""
         layers = check_layers(layers)
+        self._refuse_two_layers(layers, "layers")
         o = self._search_struct(boards, q, action, candidates)
+        if self.stage_tiles:
+            return self._launch("pulse_tfe_nt_search_staged", o, C.byref(self._stages()))
         if layers == 1:
             return self._launch("pulse_tfe_nt_search", o)
         return self._launch("pulse_tfe_nt_search_deep", o, layers)
@@ -829,6 +1066,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         on the device."""
         import torch
         layers = check_layers(layers)
+        self._refuse_two_layers(layers, "layers")
         keys = np.array(keys, dtype=_U64).reshape(-1)                       # (a copy: torch takes no read-only array)
         boards = torch.from_numpy(keys.view(np.int64)).to(self.device)
         q = torch.zeros((len(keys), 4), dtype=torch.float64, device=self.device)
@@ -847,7 +1085,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
 
     # ------------------------------------------------------------------ read-back (the only syncs) and the checkpoint
     def weights(self) -> np.ndarray:
-        """float32[n_weights] on the host."""
+        """float32[n_weights] on the host; with stage_tiles float32[n_stages * n_weights], stage s at [s * n_weights, (s + 1) * n_weights)."""
         return self.weights_dev.cpu().numpy()
 
     def trajectory(self):
@@ -892,7 +1130,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         the network is."""
         write_checkpoint(path, self.weights(), self.tuples, symmetric=int(self.symmetric), gamma=self.gamma, epsilon=self.epsilon, alpha=self.alpha,
                          max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games, lam=self.lam,
-                         tc=self.coherence() if self.tc else None)
+                         tc=self.coherence() if self.tc else None, stage_tiles=self.stage_tiles)
 
     @classmethod
     def load(cls, path, device, n_games=None):
@@ -902,7 +1140,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         import torch
         f = read_checkpoint(path)
         agent = cls(device, f["n_games"] if n_games is None else n_games, tuples=f["tuples"], symmetric=f["symmetric"], gamma=f["gamma"],
-                    epsilon=f["epsilon"], alpha=f["alpha"], max_steps=f["max_steps"], seed=f["seed"], board_id0=f["board_id0"], lam=f["lam"], tc=f["tc"])
+                    epsilon=f["epsilon"], alpha=f["alpha"], max_steps=f["max_steps"], seed=f["seed"], board_id0=f["board_id0"], lam=f["lam"], tc=f["tc"],
+                    stage_tiles=f["stage_tiles"])
         agent.weights_dev.copy_(torch.from_numpy(weights_of_checkpoint(f)))
         if f["tc"]:
             E, A = coherence_of_checkpoint(f)

@@ -57,6 +57,15 @@ __global__ __launch_bounds__(kSearchBlock) void tfe_nt_backed2_rollout_kernel(co
 
 }  // namespace
 
+namespace pulse_tfe {
+
+// the launch of the walk with Backed set (declared in tfe_ntuple_device.h: pulse_tfe_nt_learn_staged launches it too)
+void launch_backed_walk(const WalkBacked& o, void* stream) {
+    hipLaunchKernelGGL(tfe_nt_lambda_walk_kernel<true>, dim3((unsigned)((o.n_games + kWalkBlock - 1) / kWalkBlock)), dim3(kWalkBlock), 0, (hipStream_t)stream, o);
+}
+
+}  // namespace pulse_tfe
+
 extern "C" int pulse_tfe_nt_rollout_backed(const PulseTfeNtRollout* o, int32_t layers, double* backed, void* stream) {
     const char* name = "pulse_tfe_nt_rollout_backed";
     NtDev dev;
@@ -97,7 +106,7 @@ extern "C" int pulse_tfe_nt_learn_backed(const PulseTfeNtLearnBacked* o, void* s
     WalkBacked w{};                                                                     // the walk, then the adds of what it left
     w.n_games = o->n_games; w.max_steps = o->max_steps; w.gamma = o->gamma; w.lambda = o->lambda;
     w.values = o->values; w.steps = o->steps; w.lengths = o->lengths; w.deltas = o->deltas; w.backed = o->backed;
-    hipLaunchKernelGGL(tfe_nt_lambda_walk_kernel<true>, dim3((unsigned)((o->n_games + kWalkBlock - 1) / kWalkBlock)), dim3(kWalkBlock), 0, (hipStream_t)stream, w);
+    launch_backed_walk(w, stream);
     m.deltas = o->deltas;
     if (o->acc_abs) {
         m.acc_abs = o->acc_abs;

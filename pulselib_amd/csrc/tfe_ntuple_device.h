@@ -1,6 +1,7 @@
 // tfe_ntuple_device.h -- what the units of the 2048 n-tuple network share (tfe_ntuple.hip: the learner's four launches; tfe_ntuple_search.hip:
 // expectimax play, tfe_ntuple_search_deep.hip, two chance layers of it, and tfe_ntuple_search_rollout.hip, the roll-out under either; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes;
-// tfe_ntuple_backed.hip: search-backed targets; tfe_ntuple_restart.hip: roll-outs restarted from recorded boards): the network as the
+// tfe_ntuple_backed.hip: search-backed targets; tfe_ntuple_restart.hip: roll-outs restarted from recorded boards;
+// tfe_ntuple_staged.hip: weight sets by tile stage, with the staged network and the stage of a board): the network as the
 // kernels take it, a feature's index, V of four afterstates at once, the learners' target, fixed-point difference and adds, their
 // parameters (Moves), shared refusals (check_moves), scatter kernel and launches, the backward walk's kernel, the four moves of a board, the greedy action, the game loop (play_game) with its parameters
 // (Games) and the host's checks of the network, of the accumulators and of a batch of games.  One copy each.  Not part of the ABI.
@@ -38,12 +39,52 @@ __device__ __forceinline__ uint32_t feature_index(uint64_t key, uint64_t sh, uin
     return (idx & mask) + offset;
 }
 
+// The network with weight sets by tile stage (tfe_ntuple_staged.hip): stage s owns the weights
+// [s * n_weights, (s + 1) * n_weights), and a board is in stage s = the number of thresholds its largest nibble has reached.
+// reach[i] = 16 - (the nibble at which stage i + 1 begins) in each of its four bytes, 0 where the network has no such stage.
+// Derived, so that NtDev -- a by-value argument of every kernel of the one-stage network -- keeps its size; the words are as
+// wavefront-uniform as NtDev's.
+struct NtStagedDev : NtDev {
+    uint32_t reach[PULSE_TFE_NT_MAX_STAGES - 1];
+    uint32_t n_weights;
+};
+
+template <class Net>
+inline constexpr bool kStaged = std::is_same_v<Net, NtStagedDev>;
+
+// The stage of board `key`: the even and the odd nibbles of its two halves as bytes (each 0..15); adding 16 - threshold to every byte
+// sets bit 4 of a byte iff its nibble has reached the threshold (at most 15 + 15: no carry leaves a byte).  Four adds, an or of the
+// four and one test per threshold, on the two 32-bit halves, with no array indexed by a lane.
+__device__ __forceinline__ uint32_t stage_of(const NtStagedDev& net, const uint64_t key) {
+    const uint32_t lo = (uint32_t)key, hi = (uint32_t)(key >> 32);
+    const uint32_t a = lo & 0x0F0F0F0Fu, b = (lo >> 4) & 0x0F0F0F0Fu, c = hi & 0x0F0F0F0Fu, d = (hi >> 4) & 0x0F0F0F0Fu;
+    uint32_t s = 0u;
+#pragma unroll
+    for (int i = 0; i < PULSE_TFE_NT_MAX_STAGES - 1; ++i) {
+        const uint32_t r = net.reach[i];
+        s += (((a + r) | (b + r) | (c + r) | (d + r)) & 0x10101010u) != 0u ? 1u : 0u;
+    }
+    return s;
+}
+
+// what a feature's index gains in the stage of `key`: 0 for the one-stage network (nothing is computed), stage * n_weights otherwise;
+// stages * n_weights <= 2^29, so the index stays inside 32 bits
+template <class Net>
+__device__ __forceinline__ uint32_t stage_base(const Net& net, const uint64_t key) {
+    if constexpr (kStaged<Net>) return stage_of(net, key) * net.n_weights;
+    else return 0u;
+}
+
 // V of the four afterstates of a move at once: per tuple the 4 * IMG indices are formed first and their loads issued with nothing
 // dependent between them (32 lines in flight per lane), then added in the order of the definition: tuple-major, image j = 0..7.
-template <int IMG>
-__device__ __forceinline__ void values4(const NtDev& net, const float* __restrict__ w, const uint64_t (&ka)[4], double (&v)[4]) {
+// With weight sets by stage every afterstate is read in its own stage.
+template <int IMG, class Net>
+__device__ __forceinline__ void values4(const Net& net, const float* __restrict__ w, const uint64_t (&ka)[4], double (&v)[4]) {
 #pragma unroll
     for (int a = 0; a < 4; ++a) v[a] = 0.0;
+    uint32_t base[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) base[a] = stage_base(net, ka[a]);
 #pragma unroll 1
     for (int t = 0; t < net.n_tuples; ++t) {
         const uint32_t mask = net.mask[t], offset = net.offset[t];
@@ -52,7 +93,10 @@ __device__ __forceinline__ void values4(const NtDev& net, const float* __restric
         for (int j = 0; j < IMG; ++j) {
             const uint64_t sh = net.shifts[t * IMG + j];
 #pragma unroll
-            for (int a = 0; a < 4; ++a) idx[a][j] = feature_index(ka[a], sh, mask, offset);
+            for (int a = 0; a < 4; ++a) {
+                idx[a][j] = feature_index(ka[a], sh, mask, offset);
+                if constexpr (kStaged<Net>) idx[a][j] += base[a];
+            }
         }
         float x[4][IMG];
 #pragma unroll
@@ -80,17 +124,19 @@ __device__ __forceinline__ unsigned long long td_fixed(double delta, bool& clamp
 }
 
 // ... and its adds: sum += d, cnt += 1 at every feature of `key`; with Abs (temporal-coherence step sizes, tfe_ntuple_tc.hip) also
-// acc_abs += |d|, d read as signed
-template <int IMG, bool Abs>
-__device__ __forceinline__ void add_features(const NtDev& net, unsigned long long* acc, unsigned long long* acc_abs, const uint64_t key,
+// acc_abs += |d|, d read as signed; with weight sets by stage, at the features of the stage of `key`
+template <int IMG, bool Abs, class Net>
+__device__ __forceinline__ void add_features(const Net& net, unsigned long long* acc, unsigned long long* acc_abs, const uint64_t key,
                                              const unsigned long long d) {
     const unsigned long long mag = (long long)d < 0 ? 0ull - d : d;
+    const size_t base = (size_t)stage_base(net, key);
 #pragma unroll 1
     for (int tu = 0; tu < net.n_tuples; ++tu) {
         const uint32_t mask = net.mask[tu], offset = net.offset[tu];
 #pragma unroll
         for (int j = 0; j < IMG; ++j) {
-            const size_t idx = (size_t)feature_index(key, net.shifts[tu * IMG + j], mask, offset);
+            size_t idx = (size_t)feature_index(key, net.shifts[tu * IMG + j], mask, offset);
+            if constexpr (kStaged<Net>) idx += base;                                    // (2 * idx below is formed in 64 bits)
             atomicAdd(acc + 2 * idx, d);
             atomicAdd(acc + 2 * idx + 1, 1ull);
             if constexpr (Abs) atomicAdd(acc_abs + idx, mag);
@@ -177,12 +223,12 @@ int check_moves(const O* o, const char* name, NtDev* dev, Moves* m) {
 
 // The learners' adds, one lane per recorded move: blockIdx.y = t, blockIdx.x * kScatterBlock + threadIdx.x = g.  Given: the move's
 // difference is o.deltas' (after the walk of tfe_ntuple_lambda.hip); otherwise it is the one-step difference, formed here.  Abs: the
-// adds go to o.acc_abs too (add_features).  One text: tfe_ntuple.hip instantiates the four forms without Abs, tfe_ntuple_tc.hip the
-// four with it.
+// adds go to o.acc_abs too (add_features).  One text (scatter_moves, which the kernels only call): tfe_ntuple.hip instantiates the
+// four forms without Abs, tfe_ntuple_tc.hip the four with it, tfe_ntuple_staged.hip the eight on the staged network.
 constexpr int kScatterBlock = 256;
 
-template <int IMG, bool Given, bool Abs>
-__global__ __launch_bounds__(kScatterBlock) void tfe_nt_scatter_kernel(const Moves o, const NtDev net) {
+template <int IMG, bool Given, bool Abs, class Net>
+__device__ __forceinline__ void scatter_moves(const Moves& o, const Net& net) {
     __shared__ unsigned long long wg[3];
     if (threadIdx.x < 3) wg[threadIdx.x] = 0ull;
     __syncthreads();
@@ -217,6 +263,11 @@ __global__ __launch_bounds__(kScatterBlock) void tfe_nt_scatter_kernel(const Mov
     __syncthreads();
     const int i = (int)threadIdx.x;
     if (i < 3 && wg[i]) atomicAdd(reinterpret_cast<unsigned long long*>(o.stats) + (i == 0 ? 1 : i == 1 ? 2 : 4), wg[i]);
+}
+
+template <int IMG, bool Given, bool Abs>
+__global__ __launch_bounds__(kScatterBlock) void tfe_nt_scatter_kernel(const Moves o, const NtDev net) {
+    scatter_moves<IMG, Given, Abs>(o, net);
 }
 
 // ... its launch without Abs: the difference is m.deltas' where it is set and the one-step difference otherwise (defined in
@@ -301,6 +352,9 @@ __global__ __launch_bounds__(kWalkBlock) void tfe_nt_lambda_walk_kernel(const st
 // ... and the launch of its first form, the TD(lambda) walk (defined in tfe_ntuple_lambda.hip, which instantiates it)
 void launch_lambda_walk(const PulseTfeNtLearnLambda& o, void* stream);
 
+// ... and of its second, the walk of backed[t + 1] - V_t (defined in tfe_ntuple_backed.hip, which instantiates it)
+void launch_backed_walk(const WalkBacked& o, void* stream);
+
 // what pulse_tfe_nt_rollout and pulse_tfe_nt_rollout_search refuse, and the game loop's parameters of a recording launch (defined in
 // tfe_ntuple.hip)
 int check_rollout(const PulseTfeNtRollout* o, const char* name, NtDev* dev, Games* g);
@@ -331,8 +385,8 @@ __device__ __forceinline__ int greedy_of(const double (&q)[4], const uint64_t ke
 
 // the one-ply q of a board's four moves, q = r + gamma * V(afterstate), with V of the four afterstates left in v (what
 // pulse_tfe_nt_rollout and pulse_tfe_nt_evaluate play on; tfe_ntuple_restart.hip's one-ply games too)
-template <int IMG>
-__device__ __forceinline__ void one_ply_q(const NtDev& net, const float* __restrict__ w, const double gamma, const uint64_t (&ka)[4], const int (&sc)[4],
+template <int IMG, class Net>
+__device__ __forceinline__ void one_ply_q(const Net& net, const float* __restrict__ w, const double gamma, const uint64_t (&ka)[4], const int (&sc)[4],
                                           double (&v)[4], double (&q)[4]) {
     values4<IMG>(net, w, ka, v);
 #pragma unroll

@@ -51,8 +51,8 @@ __device__ __forceinline__ int count_empty(const uint64_t key) {
 // The four q of board `key_b` (its moves ka / sc given), by the 32 lanes of its group together; s = this lane's slot.  Every lane of
 // the group must call it with the same board (the butterfly is among them), and every lane returns the same q.  A move that does
 // not change the board has q = +0.0.  The loop over the moves is kept rolled: one copy of the chance layer in the code.
-template <int IMG>
-__device__ __forceinline__ void search_q(const NtDev& net, const float* __restrict__ w, const uint32_t* __restrict__ lut, const double gamma,
+template <int IMG, class Net>
+__device__ __forceinline__ void search_q(const Net& net, const float* __restrict__ w, const uint32_t* __restrict__ lut, const double gamma,
                                          const uint64_t key_b, const uint64_t (&ka)[4], const int (&sc)[4], const int s, double (&q)[4]) {
 #pragma unroll
     for (int a = 0; a < 4; ++a) q[a] = 0.0;

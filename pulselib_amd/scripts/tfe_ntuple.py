@@ -17,7 +17,10 @@ a move's difference is backed[t + 1] - V_t, under the run's `--lambda` and `--tc
 section 13.7; not with `--train-layers 2`) starts every game of a round on the board its predecessor of the round before stood on at
 the fraction F of its length, where that game had at least `--restart-min-length` moves: every round's line says how many of its games
 were restarted and from what mean depth -- a restarted game's score counts from its start board and is not comparable with a whole
-game's; the evaluations stay from reset.  Not saved either: a resumed run's first round starts at the reset boards."""
+game's; the evaluations stay from reset.  Not saved either: a resumed run's first round starts at the reset boards.  `--stages 512,2048`
+(section 13.9) keeps one weight set per tile stage -- a board reads and learns in the set of the largest of those tiles it has reached --
+and `--add-stage ROUND:TILE` splits a stage at TILE before round ROUND, the new set starting as a copy (weight promotion); not with
+`--train-layers 2` or `--search --layers 2`; the file holds the stages, and `--resume` takes them from it."""
 from __future__ import annotations
 
 import argparse
@@ -28,8 +31,23 @@ import torch
 from ..agents import NTupleTDAfterstateTFEGPU
 
 
+def _promotions(add_stage, first, rounds) -> dict:
+    """{round: the tile a stage is split at before it} of --add-stage's (round, tile) pairs; ValueError for a round named twice or
+    outside the rounds first .. first + rounds - 1 this run plays: neither is passed over in silence."""
+    add_stage = tuple((int(r), int(tile)) for r, tile in add_stage)
+    promotions = dict(add_stage)
+    if len(promotions) != len(add_stage):
+        raise ValueError("--add-stage names a round twice: one stage is split before a round")
+    outside = sorted(r for r in promotions if not first <= r < first + rounds)
+    if outside:
+        raise ValueError(f"--add-stage rounds {outside} are outside the rounds this run plays, {first}..{first + rounds - 1}")
+    return promotions
+
+
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
-        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False, restart=0.0, restart_min_length=64):
+        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False, restart=0.0, restart_min_length=64, stages=(), add_stage=()):
+    if (stages or add_stage) and (train_layers == 2 or (search and layers == 2)):
+        raise ValueError("--stages / --add-stage do not go with two chance layers: the staged launches are one ply or one chance layer deep")
     if restart and train_layers == 2:
         raise ValueError("--restart does not go with --train-layers 2: the restarted roll-out is one ply or one chance layer deep")
     if backed and train_layers not in (1, 2):
@@ -41,13 +59,17 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
         if differ:
             raise ValueError(f"{resume} continues another run: (saved, asked) {differ}")
     else:
-        agent = NTupleTDAfterstateTFEGPU(device, tables, gamma=gamma, epsilon=epsilon, alpha=alpha, max_steps=max_steps, seed=seed, lam=lam, tc=tc)
+        _promotions(add_stage, 0, rounds)                                   # (refused before a device is asked for)
+        agent = NTupleTDAfterstateTFEGPU(device, tables, gamma=gamma, epsilon=epsilon, alpha=alpha, max_steps=max_steps, seed=seed, lam=lam, tc=tc,
+                                         stage_tiles=tuple(stages))
+    promotions = _promotions(add_stage, agent.round, rounds)
     agent.rollout_layers, agent.backed_targets = train_layers, bool(backed)  # (no checkpoint holds them: given again on --resume)
     agent.restart_fraction, agent.restart_min_length = float(restart), int(restart_min_length)
     out(f"{agent.n_games} games per round from round {agent.round}: alpha {agent.alpha}, epsilon {agent.epsilon}, gamma {agent.gamma}, "
         f"lambda {agent.lam}, tc {agent.tc}, max_steps {agent.max_steps}, seed {agent.seed}, roll-out under {agent.rollout_layers} chance layers of search"
         f"{', learning towards the search-backed values' if agent.backed_targets else ''}"
-        f"{f', games restarted at {agent.restart_fraction} of games of {agent.restart_min_length} moves or more' if agent.restart_fraction else ''}")
+        f"{f', games restarted at {agent.restart_fraction} of games of {agent.restart_min_length} moves or more' if agent.restart_fraction else ''}"
+        f"{f', weight sets by stage from tiles {agent.stage_tiles}' if agent.stage_tiles else ''}")
     first, moves_before, t0 = agent.round, agent.stats()["moves"], time.perf_counter()
 
     def under_search():
@@ -66,6 +88,9 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
         out(f"After {agent.round} rounds: {evaluation()}{under_search()}")
     restarted = dict(picked=0, mean_depth=0.0)                            # of the round being played: what the round before picked
     for r in range(first, first + rounds):
+        if r in promotions:
+            agent.add_stage(promotions[r])
+            out(f"Round {r}: a stage split at tile {promotions[r]}: stages from tiles {agent.stage_tiles}")
         agent.learn_batch()
         began, restarted = restarted, (agent.restart_summary() if agent.restart_fraction else restarted)     # (synchronises)
         if eval_every and ((r + 1) % eval_every == 0 or r + 1 == first + rounds):
@@ -107,17 +132,30 @@ def main(argv=None):
     ap.add_argument("--restart", type=float, default=0.0, metavar="F",
                     help="start every game on the board its predecessor stood on at this fraction of its length (0: off; not with --train-layers 2); not saved")
     ap.add_argument("--restart-min-length", type=int, default=64, metavar="N", help="with --restart: only games of at least N moves are restarted from")
+    ap.add_argument("--stages", default="", metavar="TILES", help="weight sets by tile stage: up to three increasing tiles, e.g. 512,2048; --resume takes them from the file")
+    ap.add_argument("--add-stage", action="append", default=[], metavar="ROUND:TILE", help="split a stage at TILE before round ROUND (weight promotion); repeatable")
     args = ap.parse_args(argv)
+    try:
+        stages = tuple(int(t) for t in args.stages.split(",") if t)
+        add_stage = tuple(tuple(int(x) for x in item.split(":")) for item in args.add_stage)
+        if any(len(item) != 2 for item in add_stage):
+            raise ValueError
+    except ValueError:
+        ap.error("--stages takes tiles as 512,2048 and --add-stage ROUND:TILE")
+    if len({r for r, _ in add_stage}) != len(add_stage):
+        ap.error("--add-stage names a round twice: one stage is split before a round")
+    if (stages or add_stage) and (args.train_layers == 2 or (args.search and args.layers == 2)):
+        ap.error("--stages / --add-stage do not go with two chance layers: the staged launches are one ply or one chance layer deep")
     if args.restart and args.train_layers == 2:
         ap.error("--restart does not go with --train-layers 2: the restarted roll-out is one ply or one chance layer deep")
     if args.backed and args.train_layers not in (1, 2):
         ap.error("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
                 args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers, backed=args.backed,
-                restart=args.restart, restart_min_length=args.restart_min_length)
+                restart=args.restart, restart_min_length=args.restart_min_length, stages=stages, add_stage=add_stage)
     st = agent.stats()
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
-          f"{int((agent.weights_dev != 0).sum().item())} of {agent.n_weights} weights are not zero")
+          f"{int((agent.weights_dev != 0).sum().item())} of {agent.total_weights} weights are not zero")
 
 
 if __name__ == "__main__":

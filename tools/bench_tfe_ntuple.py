@@ -47,6 +47,15 @@ same events; by count it reads 4 + 8 bytes and writes 8 per game.  --restart-reg
 {"restart_regime": ...}: section 13.5's regime for four agents: restart_fraction 0 and --restart (0.5 if not given) one ply deep, and the
 same two under rollout_layers = 1 with backed_targets at lambda 0.5; per round the games restarted and their mean depth, per agent
 the moves learnt, and the evaluations' paired differences with and without restart.
+--stages TILES (512,2048): per B one more line, {"staged": ...}: a second agent with those stage tiles and the
+first agent's weights copied into every stage's slice, so that a staged launch plays, records and adds exactly what its unstaged
+sibling does; ten pairs (the recording launch one ply deep and one layer deep with and without backed values, the TD(0), TD(lambda)
+and backed learners, the two evaluations, the board search on the afterstates of move 64, and last the apply launch against the
+apply launches of the three stages, each after an untimed TD(lambda) learn launch), each alternating between its own HIP events, with the ratio of the medians beside the sibling's own
+spread.  --stage-regime: instead of everything above, ONE line, {"stage_regime": ...}: section 13.5's regime for the unstaged agent one
+ply deep, and under one-layer search with backed targets at lambda 0.5 for the unstaged agent, for --stages from round 0 and for one
+stage added half-way by add_stage; the evaluations' largest-tile histograms and paired differences.  Without --stages the two tiles are
+chosen from the baseline's histogram: the largest tile at least half its evaluation games reached, and a quarter of it.
 max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes, 25 with deltas, 33 with backed).  Lines are also
 appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
 import argparse
@@ -284,6 +293,114 @@ def restart_regime_line(torch, dev, games, rounds, eval_games, max_steps, fracti
     return {"restart_regime": out}
 
 
+def staged_lines(agent, torch, dev, stage_tiles, lam, warmup, repeats):
+    """every staged launch beside its unstaged sibling, on `agent`'s weights copied into every stage's slice: the games, the moves and
+    the adds per move are then the same, and a ratio is the stage arithmetic and the wider address range alone.  One line."""
+    from pulselib_amd import _native
+    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
+    staged = NTupleTDAfterstateTFEGPU(dev, agent.n_games, max_steps=agent.max_steps, seed=agent.seed, stage_tiles=stage_tiles)
+    staged.weights_dev.copy_(agent.weights_dev.repeat(staged.n_stages))
+    staged.round = agent.round
+    for a in (agent, staged):
+        a._restart_state()
+        a.start.zero_()
+    common = {"games": agent.n_games, "stage_tiles": list(stage_tiles), "lambda": lam, "epsilon": agent.epsilon, "trained_rounds": agent.round,
+              "max_steps": agent.max_steps, "warmup": warmup, "repeats": repeats, "weights": agent.n_weights, "staged_weights": staged.total_weights}
+    zero = lambda: (agent.acc.zero_(), staged.acc.zero_())
+
+    boards = agent.keys[min(64, agent.max_steps - 1)].clone()               # the afterstates the first agent's games recorded at their move 64
+
+    def search_pair(a):
+        q = torch.zeros((a.n_games, 4), dtype=torch.float64, device=dev)
+        action, cand = torch.zeros(a.n_games, dtype=torch.int8, device=dev), torch.zeros(a.n_games, dtype=torch.uint8, device=dev)
+        return lambda: a.search_launch(boards, q, action, cand)
+
+    def learnt():                                                           # an apply launch moves what a learn launch left: both agents learn, untimed, before each
+        zero()
+        agent.learn_lambda_launch(lam)
+        staged.learn_staged_launch(lam)
+    pairs = (("rollout_layers_0", lambda: agent.rollout_from_launch(0), lambda: staged.rollout_staged_launch(0), None),
+             ("learn", lambda: agent._launch("pulse_tfe_nt_learn", agent._moves(_native.TfeNtLearn())), lambda: staged.learn_staged_launch(0.0), zero),
+             ("learn_lambda", lambda: agent.learn_lambda_launch(lam), lambda: staged.learn_staged_launch(lam), zero),
+             ("evaluate", agent.evaluate_launch, staged.evaluate_launch, None),
+             ("rollout_layers_1_backed", lambda: agent.rollout_from_launch(1, backed=True), lambda: staged.rollout_staged_launch(1, backed=True), None),
+             ("learn_backed", lambda: agent.learn_backed_launch(lam), lambda: staged.learn_staged_launch(lam, backed=True), zero),
+             ("evaluate_search", agent.evaluate_search_launch, staged.evaluate_search_launch, None),
+             ("rollout_layers_1", lambda: agent.rollout_from_launch(1), lambda: staged.rollout_staged_launch(1), None),
+             ("search", search_pair(agent), search_pair(staged), None),
+             ("apply", agent.apply, staged.apply, learnt))                  # last: it moves the weights, and the slices are no longer equal
+    out = {}
+    for name, parent, new, before in pairs:
+        seconds = _alternate(agent, torch, (("parent", parent), ("staged", new)), warmup, repeats, before=before)
+        old, fresh = _spread(seconds["parent"]), _spread(seconds["staged"])
+        ratio, spread = fresh["median"] / old["median"], old["max"] / old["min"]
+        out[name] = {"parent_s": old, "staged_s": fresh, "ratio": ratio, "parent_spread": spread, "inside_parent_spread": 1.0 / spread <= ratio <= spread}
+        if name.startswith("rollout"):                                      # equal slices: the two launches recorded the same games
+            out[name]["same_games"] = bool(torch.equal(agent.lengths, staged.lengths) and torch.equal(agent.total_score, staged.total_score))
+            out[name]["moves"] = int(agent.lengths.sum().item())
+    zero()
+    del staged
+    torch.cuda.empty_cache()
+    return [{"staged": {**common, **out}}]
+
+
+def stage_regime_line(torch, dev, games, rounds, eval_games, max_steps, stage_tiles, lam=0.5):
+    """section 13.5's regime for the unstaged agent one ply deep (the baseline of the sections before) and, under one-layer search with
+    backed targets at lambda, for the unstaged agent, for stages from round 0 and for one stage added half-way by add_stage at the first
+    of the stage tiles; the evaluations are from reset and paired by board.  The baseline's largest-tile histogram is in the line: it
+    is what the thresholds are chosen from.  stage_tiles None: chosen here from that histogram (stage_tiles_from_hist)."""
+    import numpy as np
+    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
+    out = {"games": games, "rounds": rounds, "eval_games": eval_games, "seed": 0, "max_steps": max_steps, "lambda": lam, "stage_tiles_given": stage_tiles is not None}
+    ev = {}
+    rows = (("layers_0", 0, False, 0.0, False, False), ("layers_1_backed_lambda", 1, True, lam, False, False),
+            ("layers_1_backed_lambda_staged", 1, True, lam, True, False), ("layers_1_backed_lambda_promoted", 1, True, lam, False, True))
+    for name, layers, backed, row_lam, from_round_0, promoted in rows:
+        if name != "layers_0" and stage_tiles is None:                     # the baseline has been evaluated
+            stage_tiles = stage_tiles_from_hist(ev["layers_0"]["one_ply"]["max_tile_hist"])
+        tiles, promote = (tuple(stage_tiles) if from_round_0 else ()), (stage_tiles[0] if promoted else None)
+        agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=max_steps, seed=0, lam=row_lam, stage_tiles=tiles)
+        agent.rollout_layers, agent.backed_targets = layers, backed
+        per_round = []
+        for r in range(rounds):
+            if promote is not None and r == rounds // 2:
+                agent.add_stage(promote)
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            e[0].record()
+            agent.learn_batch()
+            e[1].record()
+            e[1].synchronize()
+            per_round.append({"seconds": e[0].elapsed_time(e[1]) * 1e-3, "mean_length": agent.lengths.double().mean().item(),
+                              "mean_score": agent.total_score.double().mean().item(), "stages": agent.n_stages})
+        ev[name] = {"one_ply": agent.evaluate(n_games=eval_games, per_game=True), "search": agent.evaluate_search(n_games=eval_games, per_game=True)}
+        W = agent.n_weights
+        out[name] = {"rollout_layers": layers, "backed_targets": backed, "lambda": row_lam, "stage_tiles": list(agent.stage_tiles), "rounds": per_round,
+                     "stats": agent.stats(), "nonzero_weights_per_stage": [int((agent.weights_dev[s * W:(s + 1) * W] != 0).sum().item()) for s in range(agent.n_stages)],
+                     **{k: {"mean": e["mean_score"], "se": e["std_score"] / e["games"] ** .5, "mean_length": e["mean_length"], "cut": e["truncated"],
+                            "max_tile_hist": e["max_tile_hist"]} for k, e in ev[name].items()}}
+        del agent
+        torch.cuda.empty_cache()
+    for name in ("layers_1_backed_lambda_staged", "layers_1_backed_lambda_promoted"):
+        for other in ("layers_0", "layers_1_backed_lambda"):
+            for k in ("one_ply", "search"):
+                d = (ev[name][k]["total_score"] - ev[other][k]["total_score"]).astype(np.float64)
+                out[f"{k}_eval_{name}_minus_{other}"] = {"mean": d.mean(), "se": d.std(ddof=1) / d.size ** .5}
+    out["stage_tiles"] = list(stage_tiles)
+    return {"stage_regime": out}
+
+
+def stage_tiles_from_hist(hist):
+    """Two stage tiles from an evaluation's largest-tile histogram (hist[k]: the games whose largest tile was 2^k): the upper one is
+    the largest tile at least half the games reached, so that the last stage sees the later part of a typical game and not a few lucky
+    ones; the lower one is a quarter of it, two doublings earlier, where a game is about a quarter as long."""
+    games, reached = sum(hist), 0
+    for k in range(15, 0, -1):
+        reached += hist[k]
+        if 2 * reached >= games:
+            return (1 << max(k - 2, 1), 1 << max(k, 2))
+    return (2, 4)
+
+
 def search_line(agent, torch, games, repeats, layers=1):
     """the evaluation launch under the policies on the same weights and boards; layers = 2 adds the two-layer search and its yardstick"""
     out = {}
@@ -430,6 +547,8 @@ def main(argv=None):
     ap.add_argument("--restart", type=float, metavar="F", help="two more lines per B: the restarted recording launch beside its three parents, and the pick launch at this fraction")
     ap.add_argument("--restart-min-length", type=int, default=64)
     ap.add_argument("--restart-regime", action="store_true", help="one line instead: twelve rounds and paired evaluations with and without restart (DESIGN.md section 13.7)")
+    ap.add_argument("--stages", default="", metavar="TILES", help="one more line per B: every staged launch beside its unstaged sibling, stages at these tiles (512,2048), equal slices")
+    ap.add_argument("--stage-regime", action="store_true", help="one line instead: twelve rounds and paired evaluations without stages, with --stages from round 0 and with one added half-way (DESIGN.md section 13.9)")
     ap.add_argument("--regime-rounds", type=int, default=12)
     ap.add_argument("--regime-eval-games", type=int, default=2048)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
@@ -449,6 +568,13 @@ def main(argv=None):
         with open(args.out, "a") as fh:
             fh.write(json.dumps(line) + "\n")
         return
+    stage_tiles = tuple(int(t) for t in args.stages.split(",") if t)
+    if args.stage_regime:
+        line = stage_regime_line(torch, dev, args.games[0], args.regime_rounds, args.regime_eval_games, args.max_steps, stage_tiles or None)
+        print(json.dumps(line), flush=True)
+        with open(args.out, "a") as fh:
+            fh.write(json.dumps(line) + "\n")
+        return
     if args.restart_regime:
         line = restart_regime_line(torch, dev, args.games[0], args.regime_rounds, args.regime_eval_games, args.max_steps,
                                    0.5 if args.restart is None else args.restart, args.restart_min_length)
@@ -459,6 +585,8 @@ def main(argv=None):
     for games in args.games:
         per_move = 33 if args.backed or args.restart else 17 if args.lam is None else 25
         need = (48 if args.tc else 20) * tuple_offsets(DEFAULT_TUPLES)[1] + per_move * games * args.max_steps + 64 * games
+        if stage_tiles:                                                     # a second agent: the staged weights and records of its own
+            need = 2 * 33 * games * args.max_steps + (48 if args.tc else 20) * (len(stage_tiles) + 2) * tuple_offsets(DEFAULT_TUPLES)[1] + 128 * games
         free = torch.cuda.mem_get_info(dev)[0]
         if need > 0.9 * free:
             lines = [{"games": games, "skipped": f"needs {need} bytes of device memory, {free} are free"}]
@@ -477,6 +605,8 @@ def main(argv=None):
                 lines += backed_lines(agent, torch, args.train_layers, args.lam or 0.0, args.warmup, args.repeats)
             if args.restart:                                                # on the weights the last state left
                 lines += restart_lines(agent, torch, args.restart, args.restart_min_length, args.warmup, args.repeats)
+            if stage_tiles:                                                 # likewise
+                lines += staged_lines(agent, torch, dev, stage_tiles, 0.5 if args.lam is None else args.lam, args.warmup, args.repeats)
             del agent
             torch.cuda.empty_cache()
         for line in lines:
