@@ -453,6 +453,12 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
     // raised wherever a group of words is assigned: bit k of cells_dirty = this lane's seat k (its four row cells),
     // bet_dirty = {pot, highest, agg, acted, last_raise_size, idx}, street_dirty = {stage, deck position, dirty flag},
     // board_dirty = the five board cards.
+    // Where dead steps put work off (LIVE_RULE, at the step loop) the word also carries what is owed -- a bool of its own is a
+    // lane mask, two more scalar registers across the loop: bit 16 = the table finished on a dead step, its payout and the
+    // clearing of its bets are still to come ("unsettled"); bits 17..18 = the stage (1..3) the equity flag was raised at or
+    // loaded with, 0 = a flag loaded outside the streets (every equity 0.5).
+    constexpr uint32_t kUnsettled = 1u << 16;
+    constexpr int kEqStageShift = 17;
     uint32_t cells_dirty = 0;
     bool bet_dirty = false, street_dirty = false, board_dirty = false, eq_dirty = false, act_dirty = false;
     int prev_stack = 0, prev_invested = 0;
@@ -495,6 +501,23 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
     int end_at = n_steps;
     if (LIVE_RULE && pa.lng.n_chunks != 0 && cp_at > 0) end_at = min(cp_at, n_steps);
     if (LIVE_RULE) end_at = __builtin_amdgcn_readfirstlane(end_at);      // wave-uniform, and known to be: the compare below is a scalar one
+    // Lazy steps.  A dead step runs the betting state machine and the deal only.  Three phases whose results nothing reads
+    // before the next live step wait for it -- divergent phases, which a wavefront pays for whenever one of its tables needs one:
+    //  - the equity refresh: eq[] is read by a live step's reward and by the store behind the loop.  It refreshes for the stage
+    //    the flag was raised at (carried in cells_dirty); a later transition overwrites that stage, and the refresh it skips wrote
+    //    values nobody read.
+    //  - the payouts (fold-win, showdown) and the clearing of finished tables: a table that finishes on a dead step is marked
+    //    unsettled and paid on the next live step, cleared behind the payout as ever.  Exact because all the payouts read is frozen
+    //    once a table is done: no action executes (status, inv, bet, stack), stage and dpos advance for running tables only,
+    //    cont_bits is recomputed from status.  A table loaded as done is never unsettled (no payout, as before); its bets are
+    //    cleared on the first live step.
+    // Invariant: every possible end e of the launch (n_steps as called, cut by stop_mid or by a check point; any check point of a
+    // long launch, whatever the cap's remainder) has steps e - 2 and e - 1 live -- end_at is the NEAREST possible end at every
+    // step.  A table becomes unsettled, or keeps a raised flag unrefreshed, on a dead step only, and a dead step is followed by a
+    // live one before any end; so behind the payout phase of step e - 2 nothing is owed, and what the last step's policy reads
+    // (pot, the carried a_*) and what is stored behind the loop (prev_stacks, prev_invested, actions, equities, equity_dirty,
+    // the state words) are what eager steps leave.
+    if (LIVE_RULE && dirty && stage >= 1 && stage <= 3) cells_dirty |= (uint32_t)stage << kEqStageShift;
     for (int i = 0; i < n_steps; ++i) {
         const bool live = !LIVE_RULE || i + 2 >= end_at;
         // In a chunk, everything derived from the lane's position in its table (seat numbers, `seat < A` masks, ...)
@@ -544,10 +567,13 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
         STAMP(3);   // policy done
         // ---- 1) equities of dirty tables (PokerGPU.py:455-525)
         if (PH & PULSE_PH_EQUITY) {
-            if (dirty) {
-                const int c5 = stage >= 2 ? b3 : 0, c6 = stage == 3 ? b4 : 0;
-                const bool street = stage >= 1 && stage <= 3;
-                const bool cached_board = street && board_matches(pre_tag, stage + 2, b0, b1, b2, b3, b4);
+            if (live && dirty) {
+                // the stage the refresh is FOR: where dead steps put it off, the one the flag was raised at or loaded with (0: no
+                // street) -- a table whose river was dealt on a dead step has usually finished (stage 4) by the next live one
+                const int rs = LIVE_RULE ? (int)(cells_dirty >> kEqStageShift) & 3 : stage;
+                const int c5 = rs >= 2 ? b3 : 0, c6 = rs == 3 ? b4 : 0;
+                const bool street = rs >= 1 && rs <= 3;
+                const bool cached_board = street && board_matches(pre_tag, rs + 2, b0, b1, b2, b3, b4);
 #pragma unroll
                 for (int k = 0; k < SPL; ++k) {
                     const int seat = SEAT(k);
@@ -557,13 +583,13 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                         if (cached_board) {       // the cache reads are independent single hops
                             if (MULTI) {
                                 hit = seat_hit[k];
-                                if (SLIM && stage == 3) {      // the river's equity is the 7-card rank normalised (PokerGPU.py:481), as the reset kernel stored it
+                                if (SLIM && rs == 3) {      // the river's equity is the 7-card rank normalised (PokerGPU.py:481), as the reset kernel stored it
                                     e = __fdiv_rn(__fsub_rn((float)(l_prerank[q * P_ + seat] & 0xFFFF), 4109.0f), 32765.0f);
                                     e = fminf(fmaxf(e, 0.0f), 1.0f);
-                                } else e = l_preeq[(q * EQROWS + (stage - 1)) * P_ + seat];
+                                } else e = l_preeq[(q * EQROWS + (rs - 1)) * P_ + seat];
                             } else {
                                 const uint32_t ph = (uint32_t)ldo(v.pre_hands, ROW_OFF(k));
-                                const float pe = ldo(v.pre_eq, (__umul24(ut, 3u * (uint32_t)P) + __umul24((uint32_t)(stage - 1), (uint32_t)P) + (uint32_t)seat) * 4u);
+                                const float pe = ldo(v.pre_eq, (__umul24(ut, 3u * (uint32_t)P) + __umul24((uint32_t)(rs - 1), (uint32_t)P) + (uint32_t)seat) * 4u);
                                 hit = PULSE_CACHE_HIT(ph, h0[k], h1[k]);
                                 e = pe;
                             }
@@ -572,7 +598,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                             int hc0 = h0[k], hc1 = h1[k];
                             if (MULTI) { const int2 h = hand_of_seat(seat); hc0 = h.x; hc1 = h.y; }
                             const float r = (float)walk7(hr, hr_len, hc0, hc1, b0, b1, b2, c5, c6);
-                            e = stage == 1 ? __fdiv_rn(__fsub_rn(r, 74359.0f), 749420.0f) : __fdiv_rn(__fsub_rn(r, 4109.0f), 32765.0f);
+                            e = rs == 1 ? __fdiv_rn(__fsub_rn(r, 74359.0f), 749420.0f) : __fdiv_rn(__fsub_rn(r, 4109.0f), 32765.0f);
                             e = fminf(fmaxf(e, 0.0f), 1.0f);
                         }
                     }
@@ -660,18 +686,25 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                     else if (stage == 2) { b3 = nx0; dpos += 2; }                    // burn + turn (:607-610)
                     else { b4 = nx0; dpos += 2; }                                    // burn + river (:613-616)
                     dirty = true; board_dirty = true;
+                    if (LIVE_RULE) cells_dirty = (cells_dirty & ~(3u << kEqStageShift)) | (uint32_t)stage << kEqStageShift;
                 }
             }
         }
-        // a chunk fetches the next actor's hole cards now; they are first needed by the observation below
+        // a chunk fetches the next actor's hole cards now; they are first needed by the observation below (of a live step: the
+        // hand class is carried on every step)
         int2 next_hand = make_int2(0, 0);
         uint32_t next_cls = 0;
-        if (MULTI) { next_hand = hand_of_seat(idx & 15); next_cls = class_of_seat(idx & 15); }
+        if (MULTI) { if (live) next_hand = hand_of_seat(idx & 15); next_cls = class_of_seat(idx & 15); }
 
         STAMP(6);   // advance / deal done
         // ---- 4) payouts on newly finished tables (PokerGPU.py:619-623)
-        const bool newly_done = (PH & PULSE_PH_CAPTURE) ? (done && !prev_done) : done;
-        if (PH & PULSE_PH_FOLDWIN) {                                            // :331-338
+        bool newly_done = (PH & PULSE_PH_CAPTURE) ? (done && !prev_done) : done;
+        if (LIVE_RULE) {               // a dead step leaves the table unsettled; a live one pays what is owed, this step's finish included
+            cells_dirty |= newly_done ? kUnsettled : 0u;
+            newly_done = live && (cells_dirty & kUnsettled) != 0;
+            if (live) cells_dirty &= ~kUnsettled;
+        }
+        if ((PH & PULSE_PH_FOLDWIN) && live) {                                         // :331-338
             if (newly_done && contenders == 1) {
                 const int survivor = __ffs((int)cont_bits) - 1;
 #pragma unroll
@@ -679,7 +712,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                 pot = 0; bet_dirty = true;
             }
         }
-        if (PH & PULSE_PH_SHOWDOWN) {                                           // :380-453
+        if ((PH & PULSE_PH_SHOWDOWN) && live) {                                 // :380-453
             if (newly_done && stage < 5 && contenders > 1) {
                 if (stage == 0) {
                     b0 = deck_card(dpos + 1); b1 = deck_card(dpos + 2); b2 = deck_card(dpos + 3);
@@ -750,7 +783,7 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
                 bet_dirty = true; street_dirty = true; board_dirty = true;
             }
         }
-        if (PH & PULSE_PH_CLEARDONE) {                                          // :625-628
+        if ((PH & PULSE_PH_CLEARDONE) && live) {                                // :625-628 (idempotent: a dead step leaves it to the next live one)
             if (done) {
                 bet_dirty = bet_dirty || highest != 0;
                 highest = 0;
@@ -944,8 +977,10 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
 #undef VS
 }
 
+// (two lanes per table -- chunks only: three wavefronts per SIMD, the 168 VGPRs the residency of the long launches counts on.  With
+// two asked for, the lazy steps' bookkeeping came out at 169 / 170 by the compiler's choice alone.)
 template <uint32_t PH, bool POLICY, int LPT, int SPL, bool WOBS, int MULTI>
-__global__ __launch_bounds__(kStepBlock, LPT == 4 ? 4 : 2) void poker_step_kernel(const PulsePokerView v, int64_t* __restrict__ actions,
+__global__ __launch_bounds__(kStepBlock, LPT == 4 ? 4 : 3) void poker_step_kernel(const PulsePokerView v, int64_t* __restrict__ actions,
                                                            const int32_t* __restrict__ actor_idx_in,
                                                            float* __restrict__ rewards, const PolicyArgs pa, const ChunkArgs ca) {
     poker_step_body<PH, POLICY, LPT, SPL, WOBS, MULTI, false>(v, actions, actor_idx_in, rewards, pa, ca, nullptr);
