@@ -171,11 +171,16 @@ def feature_cells_on_host(tuples, symmetric=True) -> list:
     return [tf[:, list(t)] for t in tuples]
 
 
+def _nibbles(keys) -> np.ndarray:
+    """int64[len(keys), 16]: the nibbles of packed boards uint64[N], cell c in column c."""
+    return np.stack([(keys >> _U64(4 * c)) & _U64(15) for c in range(16)], axis=1).astype(np.int64)
+
+
 def feature_indices_on_host(keys, tuples, symmetric=True) -> np.ndarray:
     """int64[len(keys), F]: the weights an afterstate reads, tuple-major and image j within a tuple (the order V is summed in).  Where
     `tuples` carry stage tiles (with_stages) every index is in the slice of the afterstate's own stage: + stage * n_weights."""
     keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
-    nib = np.stack([(keys >> _U64(4 * c)) & _U64(15) for c in range(16)], axis=1).astype(np.int64)
+    nib = _nibbles(keys)
     offsets, n_weights = tuple_offsets(tuples)
     cols = []
     for off, cells in zip(offsets, feature_cells_on_host(tuples, symmetric)):
@@ -224,7 +229,7 @@ def moves_on_host(keys):
     """(afterstate keys uint64[N, 4], merge scores int64[N, 4]) of the four moves of packed 4 x 4 boards, without the spawn
     (TFE.py:154-178: the board rotated `a` times, every row squashed to the left, rotated back)."""
     keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
-    nib = np.stack([(keys >> _U64(4 * c)) & _U64(15) for c in range(16)], axis=1).astype(np.int64)
+    nib = _nibbles(keys)
     table, table_score = row_table_on_host()
     after, score = np.zeros((len(keys), 4), dtype=_U64), np.zeros((len(keys), 4), dtype=np.int64)
     for a, src in enumerate(transforms_on_host(4)[:4].tolist()):
@@ -316,11 +321,7 @@ def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
             after2, scores2 = moves_on_host(chance)
             x = rewards_of_scores(scores2).astype(np.float64) + gamma * value_on_host(after2.reshape(-1), weights, tuples, symmetric).reshape(-1, 4)
             cand2 = after2 != chance[:, None]
-        m, found = np.zeros(len(chance), dtype=np.float64), np.zeros(len(chance), dtype=bool)
-        for a in range(4):
-            take = cand2[:, a] & (~found | (x[:, a] > m))
-            m, found = np.where(take, x[:, a], m), found | cand2[:, a]
-        terms[live] = np.broadcast_to(np.array(TILE_ODDS, dtype=np.float64)[slot & 1], live.shape)[live] * m
+        terms[live] = np.broadcast_to(np.array(TILE_ODDS, dtype=np.float64)[slot & 1], live.shape)[live] * search_backed_on_host(x, cand2)
     total = terms
     for _ in range(5):
         total = total[..., 0::2] + total[..., 1::2]
@@ -349,7 +350,7 @@ def spawn_on_host(keys, r_cell, r_val) -> np.ndarray:
     (r_val >> 8) > 15099494, else nibble 1.  A full board comes back as it is."""
     keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
     r_cell, r_val = np.asarray(r_cell, dtype=_U64).reshape(-1), np.asarray(r_val, dtype=_U64).reshape(-1)
-    free = np.stack([(keys >> _U64(4 * c)) & _U64(15) for c in range(16)], axis=1) == 0
+    free = _nibbles(keys) == 0
     empty = free.sum(axis=1).astype(_U64)
     k = ((r_cell * empty) >> _U64(32)).astype(np.int64)
     cell = (free & (np.cumsum(free, axis=1) - 1 == k[:, None])).argmax(axis=1).astype(_U64)
@@ -417,12 +418,10 @@ def learn_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: flo
     return _add_moves_on_host(keys, steps, lengths, target - values, tuples, symmetric, acc, acc_abs)
 
 
-def lambda_deltas_on_host(values, steps, lengths, gamma: float, lam: float) -> np.ndarray:
-    """float64[T, B]: the lambda-differences pulse_tfe_nt_learn_lambda writes, operation for operation.  values float64[T, B], steps
-    uint8[T, B], lengths int[B] (a game has min(lengths[g], T) moves).  gl = gamma * lam (one multiply); at a game's last move
-    D = 0 - values[t] with its terminal bit and +0.0 without (the move is skipped); at any other D_t = ((reward(steps[t + 1]) + gamma *
-    values[t + 1]) - values[t]) + gl * D_{t+1}, unclamped.  Rows at or beyond a game's length are returned as 0 (the device does
-    not write them: they keep what `deltas` held)."""
+def _walk_deltas_on_host(values, steps, lengths, gamma, lam, backed=None) -> np.ndarray:
+    """The learners' backward walk, operation for operation: gl = gamma * lam (one multiply); at a game's last move D = 0 - values[t] with
+    its terminal bit and +0.0 without (the move is skipped); at any other D_t = (target - values[t]) + gl * D_{t+1}, unclamped, where
+    target = reward(steps[t + 1]) + gamma * values[t + 1], or with `backed` backed[t + 1].  Rows at or beyond a game's length are 0."""
     values, steps = np.asarray(values, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
     T = values.shape[0]
     L = np.minimum(np.asarray(lengths, dtype=np.int64).reshape(-1), T)
@@ -431,14 +430,23 @@ def lambda_deltas_on_host(values, steps, lengths, gamma: float, lam: float) -> n
     for t in range(int(L.max()) - 1 if L.size else -1, -1, -1):
         last, played = t == L - 1, t < L
         nxt = t + 1 if t + 1 < T else t                                    # (row T does not exist; a move at T - 1 is a last move)
-        target = np.where(last, 0.0, ((steps[nxt] >> 2) & 31).astype(np.float64) + gamma * values[nxt])
-        delta = target - values[t]
         with np.errstate(all="ignore"):                                    # (what a lane computes on rows beyond its game is not used)
+            target = backed[nxt] if backed is not None else ((steps[nxt] >> 2) & 31).astype(np.float64) + gamma * values[nxt]
+            delta = np.where(last, 0.0, target) - values[t]
             through = delta + gl * carried
         carried = np.where(last, np.where(steps[t] >> 7 != 0, delta, 0.0), through)
         carried = np.where(played, carried, 0.0)
         out[t] = carried
     return out
+
+
+def lambda_deltas_on_host(values, steps, lengths, gamma: float, lam: float) -> np.ndarray:
+    """float64[T, B]: the lambda-differences pulse_tfe_nt_learn_lambda writes, operation for operation.  values float64[T, B], steps
+    uint8[T, B], lengths int[B] (a game has min(lengths[g], T) moves).  gl = gamma * lam (one multiply); at a game's last move
+    D = 0 - values[t] with its terminal bit and +0.0 without (the move is skipped); at any other D_t = ((reward(steps[t + 1]) + gamma *
+    values[t + 1]) - values[t]) + gl * D_{t+1}, unclamped.  Rows at or beyond a game's length are returned as 0 (the device does
+    not write them: they keep what `deltas` held)."""
+    return _walk_deltas_on_host(values, steps, lengths, gamma, lam)
 
 
 def learn_lambda_nt_on_host(keys, values, steps, lengths, tuples, symmetric, gamma: float, lam: float, acc, acc_abs=None) -> dict:
@@ -456,21 +464,7 @@ def backed_deltas_on_host(values, backed, steps, lengths, gamma: float, lam: flo
     game's last move D = 0 - values[t] with its terminal bit and +0.0 without (the move is skipped); at any other D_t = (backed[t + 1] -
     values[t]) + gl * D_{t+1}, unclamped: backed[t + 1] holds the next reward and its own gamma.  Rows at or beyond a game's length are
     returned as 0 (the device does not write them: they keep what `deltas` held)."""
-    values, backed, steps = np.asarray(values, dtype=np.float64), np.asarray(backed, dtype=np.float64), np.asarray(steps, dtype=np.uint8)
-    T = values.shape[0]
-    L = np.minimum(np.asarray(lengths, dtype=np.int64).reshape(-1), T)
-    gl = np.float64(gamma) * np.float64(lam)
-    out, carried = np.zeros(values.shape, dtype=np.float64), np.zeros(values.shape[1], dtype=np.float64)
-    for t in range(int(L.max()) - 1 if L.size else -1, -1, -1):
-        last, played = t == L - 1, t < L
-        nxt = t + 1 if t + 1 < T else t                                    # (row T does not exist; a move at T - 1 is a last move)
-        with np.errstate(all="ignore"):                                    # (what a lane computes on rows beyond its game is not used)
-            delta = np.where(last, 0.0, backed[nxt]) - values[t]
-            through = delta + gl * carried
-        carried = np.where(last, np.where(steps[t] >> 7 != 0, delta, 0.0), through)
-        carried = np.where(played, carried, 0.0)
-        out[t] = carried
-    return out
+    return _walk_deltas_on_host(values, steps, lengths, gamma, lam, np.asarray(backed, dtype=np.float64))
 
 
 def learn_backed_nt_on_host(keys, values, backed, steps, lengths, tuples, symmetric, gamma: float, lam: float, acc, acc_abs=None) -> dict:
@@ -602,18 +596,17 @@ def read_checkpoint(path) -> dict:
     out["symmetric"] = bool(out["symmetric"])
     out["tuples"] = with_stages([cells[i, :int(n)].tolist() for i, n in enumerate(lens.tolist())], out["stage_tiles"])
     out["n_weights"] = tuple_offsets(out["tuples"])[1] * (len(out["stage_tiles"]) + 1)
-    if index.dtype != np.int64 or value.dtype != np.float32 or index.shape != value.shape or index.ndim != 1:
-        raise ValueError(f"{path}: index must be int64[m] and value float32[m]")
-    if len(index) and (int(index[0]) < 0 or int(index[-1]) >= out["n_weights"] or not bool((index[1:] > index[:-1]).all())):
-        raise ValueError(f"{path}: index must be strictly ascending inside the network's {out['n_weights']} weights")
+    def check_sparse(name, index, others, dtype, shapes):
+        """index int64[m], strictly ascending inside the network, and `others` of `dtype` in its shape (ValueError)"""
+        if index.dtype != np.int64 or index.ndim != 1 or any(x.dtype != dtype or x.shape != index.shape for x in others):
+            raise ValueError(f"{path}: {shapes}")
+        if len(index) and (int(index[0]) < 0 or int(index[-1]) >= out["n_weights"] or not bool((index[1:] > index[:-1]).all())):
+            raise ValueError(f"{path}: {name} must be strictly ascending inside the network's {out['n_weights']} weights")
+    check_sparse("index", index, [value], np.float32, "index must be int64[m] and value float32[m]")
     out["index"], out["value"] = index, value
     if out["tc"]:
-        at, e, a = tc_arrays
-        if at.dtype != np.int64 or e.dtype != np.float64 or a.dtype != np.float64 or at.ndim != 1 or e.shape != at.shape or a.shape != at.shape:
-            raise ValueError(f"{path}: tc_index must be int64[m] and tc_e / tc_a float64[m]")
-        if len(at) and (int(at[0]) < 0 or int(at[-1]) >= out["n_weights"] or not bool((at[1:] > at[:-1]).all())):
-            raise ValueError(f"{path}: tc_index must be strictly ascending inside the network's {out['n_weights']} weights")
-        out["tc_index"], out["tc_e"], out["tc_a"] = at, e, a
+        check_sparse("tc_index", tc_arrays[0], tc_arrays[1:], np.float64, "tc_index must be int64[m] and tc_e / tc_a float64[m]")
+        out["tc_index"], out["tc_e"], out["tc_a"] = tc_arrays
     return out
 
 
@@ -747,32 +740,21 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
     def rollout_staged_launch(self, layers, backed=False):
         """pulse_tfe_nt_rollout_staged alone: rollout_from_launch's games (layers 0 or 1, `backed` with 1) with V read by stage, begun
         on the boards of `start` where usable."""
-        import torch
         self._refuse_two_layers(layers, "layers")
-        if isinstance(layers, bool) or layers not in (0, 1):
-            raise ValueError("layers must be 0 or 1")
-        if backed and not layers:
-            raise ValueError("backed needs layers = 1: a one-ply roll-out has no search to back a value up")
-        self._restart_state()
-        if backed and self.backed is None:
-            self.backed = torch.zeros_like(self.values)
-        return self._launch("pulse_tfe_nt_rollout_staged", self._rollout_struct(), C.byref(self._stages()), int(layers),
-                            self.backed.data_ptr() if backed else None, self.start.data_ptr())
+        args = self._from_args(layers, backed)
+        return self._launch("pulse_tfe_nt_rollout_staged", self._rollout_struct(), C.byref(self._stages()), *args)
 
     def learn_staged_launch(self, lam, backed=False, tc=False):
         """pulse_tfe_nt_learn_staged alone on the games last played: learn()'s adds (lam == 0 without backed: no deltas), the walk of
         learn_lambda_launch (lam > 0) or of learn_backed_launch (backed) into `deltas` first, with tc |d| into `acc_abs` as well; every
         move's adds go to the stage of its afterstate.  Allocates what the agent lacks of `deltas` and the TC state."""
-        import torch
         lam = check_lam(lam)
         if backed and self.backed is None:
             raise ValueError("no roll-out with backed values has run: the agent holds no backed")
         o = self._moves(_native.TfeNtLearnBacked())
         o.lam = lam
         if backed or lam > 0.0:
-            if self.deltas is None:
-                self.deltas = torch.zeros_like(self.values)
-            o.deltas = self.deltas.data_ptr()
+            o.deltas = self._per_move("deltas").data_ptr()
         if backed:
             o.backed = self.backed.data_ptr()
         if tc:
@@ -782,17 +764,20 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
 
     def _apply_staged(self):
         """pulse_tfe_nt_apply, or with tc pulse_tfe_nt_apply_tc, once per stage on that stage's slice of weights, acc, acc_abs, E and A."""
-        W = self.n_weights
         for s in range(self.n_stages):
-            o = _native.TfeNtApplyTc() if self.tc else _native.TfeNtApply()
-            self._net(o.net)
-            o.net.weights = self.weights_dev[s * W:].data_ptr()
-            o.step, o.acc = self.alpha / self.n_features, self.acc[s * W:].data_ptr()
-            if self.tc:
-                o.acc_abs, o.e, o.a = self.acc_abs[s * W:].data_ptr(), self.E[s * W:].data_ptr(), self.A[s * W:].data_ptr()
-                o.tc_stats = self.tc_stats.data_ptr()
-            self._launch("pulse_tfe_nt_apply_tc" if self.tc else "pulse_tfe_nt_apply", o)
+            self._launch(*self._apply_struct(s, self.tc))
         return self
+
+    def _apply_struct(self, stage, tc):
+        """(entry point, its struct): pulse_tfe_nt_apply, or with tc pulse_tfe_nt_apply_tc, on stage `stage`'s slices."""
+        at = stage * self.n_weights
+        o = _native.TfeNtApplyTc() if tc else _native.TfeNtApply()
+        self._net(o.net)
+        o.net.weights = self.weights_dev[at:].data_ptr()
+        o.step, o.acc = self.alpha / self.n_features, self.acc[at:].data_ptr()
+        if tc:
+            o.acc_abs, o.e, o.a, o.tc_stats = self.acc_abs[at:].data_ptr(), self.E[at:].data_ptr(), self.A[at:].data_ptr(), self.tc_stats.data_ptr()
+        return "pulse_tfe_nt_apply_tc" if tc else "pulse_tfe_nt_apply", o
 
     # ------------------------------------------------------------------ the launches
     def _net(self, net):
@@ -848,21 +833,30 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
             self.start = torch.zeros(self.n_games, dtype=torch.int64, device=self.device)             # (uint64 words)
             self.restart_stats = torch.zeros(2, dtype=torch.int64, device=self.device)
 
-    def rollout_from_launch(self, layers, backed=False):
-        """pulse_tfe_nt_rollout_from alone, whatever the agent's attributes: rollout()'s games at `layers` = 0 (one ply) or 1 (one-layer
-        search; ValueError for any other), each begun on the board in `start` where that board is usable and at its reset otherwise
-        (`start` is 0 there afterwards).  backed: rollout_backed_launch's `backed` too (layers must be 1).  A `start` no pick has
-        filled is all zero: the launch plays its sibling's games."""
+    def _per_move(self, name):
+        """The agent's `deltas` or `backed` (`name`): float64 in the shape of `values`, allocated zeroed where the agent has none yet."""
         import torch
+        if getattr(self, name) is None:
+            setattr(self, name, torch.zeros_like(self.values))
+        return getattr(self, name)
+
+    def _from_args(self, layers, backed):
+        """What rollout_from_launch and rollout_staged_launch check and pass beside the struct: (layers, `backed` or None, `start`),
+        `start` and `backed` allocated where the agent has none."""
         if isinstance(layers, bool) or layers not in (0, 1):
             raise ValueError("layers must be 0 or 1")
         if backed and not layers:
             raise ValueError("backed needs layers = 1: a one-ply roll-out has no search to back a value up")
         self._restart_state()
-        if backed and self.backed is None:
-            self.backed = torch.zeros_like(self.values)
-        return self._launch("pulse_tfe_nt_rollout_from", self._rollout_struct(), int(layers), self.backed.data_ptr() if backed else None,
-                            self.start.data_ptr())
+        return int(layers), self._per_move("backed").data_ptr() if backed else None, self.start.data_ptr()
+
+    def rollout_from_launch(self, layers, backed=False):
+        """pulse_tfe_nt_rollout_from alone, whatever the agent's attributes: rollout()'s games at `layers` = 0 (one ply) or 1 (one-layer
+        search; ValueError for any other), each begun on the board in `start` where that board is usable and at its reset otherwise
+        (`start` is 0 there afterwards).  backed: rollout_backed_launch's `backed` too (layers must be 1).  A `start` no pick has
+        filled is all zero: the launch plays its sibling's games."""
+        args = self._from_args(layers, backed)
+        return self._launch("pulse_tfe_nt_rollout_from", self._rollout_struct(), *args)
 
     def restart_pick_launch(self, fraction=None, min_length=None):
         """pulse_tfe_nt_restart_pick alone on the games last recorded (under this round's seed and boards): `start` becomes, per game
@@ -899,11 +893,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
         """pulse_tfe_nt_rollout_backed alone, whatever the agent's `rollout_layers` and `backed_targets`: rollout_search_launch's games
         and records, and in `backed` (allocated here if the agent has none) per move the largest q of the search over the moves that
         change the board."""
-        import torch
         layers = check_layers(layers)
-        if self.backed is None:
-            self.backed = torch.zeros_like(self.values)
-        return self._launch("pulse_tfe_nt_rollout_backed", self._rollout_struct(), layers, self.backed.data_ptr())
+        return self._launch("pulse_tfe_nt_rollout_backed", self._rollout_struct(), layers, self._per_move("backed").data_ptr())
 
     def _moves(self, o):
         """The network and the fields the two learners' structs share."""
@@ -939,41 +930,32 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
     def learn_lambda_launch(self, lam):
         """pulse_tfe_nt_learn_lambda on the games last played, whatever the agent's own `lam`: the backward walk into `deltas`
         (allocated here if the agent has none) and the adds of the lambda-differences into the accumulators."""
-        import torch
         lam = check_lam(lam)
-        if self.deltas is None:
-            self.deltas = torch.zeros_like(self.values)
         o = self._moves(_native.TfeNtLearnLambda())
-        o.lam, o.deltas = lam, self.deltas.data_ptr()
+        o.lam, o.deltas = lam, self._per_move("deltas").data_ptr()
         return self._launch("pulse_tfe_nt_learn_lambda", o)
 
     def learn_tc_launch(self, lam):
         """pulse_tfe_nt_learn_tc on the games last played, whatever the agent's own `lam` and `tc`: the adds of learn() (lam == 0: one
         launch, no deltas) or of learn_lambda_launch (lam > 0: the walk into `deltas`, then the adds), with |d| into `acc_abs` as
         well.  Allocates the TC state, and for lam > 0 `deltas`, if the agent has none."""
-        import torch
         lam = check_lam(lam)
         self._tc_state()
         o = self._moves(_native.TfeNtLearnTc())
         o.lam, o.acc_abs = lam, self.acc_abs.data_ptr()
         if lam > 0.0:
-            if self.deltas is None:
-                self.deltas = torch.zeros_like(self.values)
-            o.deltas = self.deltas.data_ptr()
+            o.deltas = self._per_move("deltas").data_ptr()
         return self._launch("pulse_tfe_nt_learn_tc", o)
 
     def learn_backed_launch(self, lam):
         """pulse_tfe_nt_learn_backed on the games rollout_backed_launch last recorded, whatever the agent's own `lam` and
         `backed_targets`: the backward walk of backed[t + 1] - V_t into `deltas` (allocated here if the agent has none) and the adds
         of what it left -- with the agent's `tc` into `acc_abs` as well.  ValueError if no such roll-out has run."""
-        import torch
         lam = check_lam(lam)
         if self.backed is None:
             raise ValueError("no roll-out with backed values has run: the agent holds no backed")
-        if self.deltas is None:
-            self.deltas = torch.zeros_like(self.values)
         o = self._moves(_native.TfeNtLearnBacked())
-        o.lam, o.deltas, o.backed = lam, self.deltas.data_ptr(), self.backed.data_ptr()
+        o.lam, o.deltas, o.backed = lam, self._per_move("deltas").data_ptr(), self.backed.data_ptr()
         if self.tc:
             self._tc_state()
             o.acc_abs = self.acc_abs.data_ptr()
@@ -983,11 +965,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
         """pulse_tfe_nt_apply_tc: every visited weight moves by (alpha / F) * rho of the mean of its adds, rho = |E| / A as they stood;
         E and A take the round's means, the three accumulator words are zero afterwards and tc_stats has the round added."""
         self._tc_state()
-        o = _native.TfeNtApplyTc()
-        self._net(o.net)
-        o.step, o.acc, o.acc_abs = self.alpha / self.n_features, self.acc.data_ptr(), self.acc_abs.data_ptr()
-        o.e, o.a, o.tc_stats = self.E.data_ptr(), self.A.data_ptr(), self.tc_stats.data_ptr()
-        return self._launch("pulse_tfe_nt_apply_tc", o)
+        return self._launch(*self._apply_struct(0, True))
 
     def apply(self):
         """One launch: every visited weight moves by alpha / F of the mean of its adds; the accumulators are zero afterwards.  With
@@ -996,10 +974,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
             return self._apply_staged()
         if self.tc:
             return self.apply_tc_launch()
-        o = _native.TfeNtApply()
-        self._net(o.net)
-        o.step, o.acc = self.alpha / self.n_features, self.acc.data_ptr()
-        return self._launch("pulse_tfe_nt_apply", o)
+        return self._launch(*self._apply_struct(0, False))
 
     def learn_batch(self):
         self.rollout()

@@ -8,9 +8,9 @@
 // cells and hands the kernels 6 shift counts per feature in one 64-bit word, by value, so a nibble is a shift by a scalar and no lane
 // indexes an array.  The learner runs one lane per recorded move and adds temporal differences as fixed-point integers, so the
 // accumulators do not depend on scheduling; the apply launch moves each weight by step * the mean of its adds.
-// The game loop (play_game) is tfe_ntuple_device.h's, shared with tfe_ntuple_search.hip, and so is the learner's kernel
-// (tfe_nt_scatter_kernel), instantiated here by launch_scatter, which also makes the adds of tfe_ntuple_lambda.hip's TD(lambda)
-// learner; tfe_ntuple_tc.hip instantiates the same text with a third accumulator.
+// The game loop (play_game) and the learner's kernel (tfe_nt_scatter_kernel) are tfe_ntuple_device.h's, the game kernel
+// (tfe_nt_play_kernel, here at one lane per game) tfe_ntuple_search_device.h's.  launch_scatter instantiates the scatter without its
+// third accumulator, and makes the adds of tfe_ntuple_lambda.hip's and tfe_ntuple_backed.hip's learners too.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -18,6 +18,7 @@
 #include "pulse_internal.h"
 #include "tfe_device.h"
 #include "tfe_ntuple_device.h"
+#include "tfe_ntuple_search_device.h"
 
 namespace {
 
@@ -29,18 +30,6 @@ constexpr int kBlock = 256;
 static_assert(sizeof(PulseTfeNtNet) == 104 && sizeof(PulseTfeNtRollout) == 232 && sizeof(PulseTfeNtLearn) == 176 && sizeof(PulseTfeNtApply) == 128 &&
               sizeof(PulseTfeNtEval) == 208, "struct layouts are part of the ABI");
 
-// IMG = 8 (symmetric) or 1.  Record: pulse_tfe_nt_rollout; otherwise pulse_tfe_nt_evaluate.  One lane plays one game: q = r + gamma * V.
-template <int IMG, bool Record>
-__global__ __launch_bounds__(kBlock) void tfe_nt_games_kernel(const Games o, const NtDev net) {
-    __shared__ unsigned long long wg[Record ? 2 : kEvalBins];
-    if (threadIdx.x < (Record ? 2 : kEvalBins)) wg[threadIdx.x] = 0ull;
-    __syncthreads();
-    play_game<Record>(o, wg, blockIdx.x * kBlock + threadIdx.x, true,
-                      [&](const uint64_t, const uint64_t (&ka)[4], const int (&sc)[4], double (&v)[4], double (&q)[4]) {
-                          one_ply_q<IMG>(net, o.weights, o.gamma, ka, sc, v, q);
-                      });
-}
-
 __global__ __launch_bounds__(kBlock) void tfe_nt_apply_kernel(float* __restrict__ weights, longlong2* __restrict__ acc, uint64_t n_weights, double step) {
     const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n_weights) return;
@@ -50,20 +39,6 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_apply_kernel(float* __restrict_
         weights[i] = (float)__dadd_rn((double)weights[i], __dmul_rn(step, mean));
         acc[i] = make_longlong2(0, 0);
     }
-}
-
-int launch_games(Games& g, const NtDev& dev, bool symmetric, bool record, void* stream) {
-    if (int rc = pulse::tfe_row_lut(&g.lut)) return rc;
-    const dim3 grid((unsigned)((g.n_games + kBlock - 1) / kBlock)), block(kBlock);
-    hipStream_t st = (hipStream_t)stream;
-    if (record) {
-        if (symmetric) hipLaunchKernelGGL((tfe_nt_games_kernel<8, true>), grid, block, 0, st, g, dev);
-        else hipLaunchKernelGGL((tfe_nt_games_kernel<1, true>), grid, block, 0, st, g, dev);
-    } else {
-        if (symmetric) hipLaunchKernelGGL((tfe_nt_games_kernel<8, false>), grid, block, 0, st, g, dev);
-        else hipLaunchKernelGGL((tfe_nt_games_kernel<1, false>), grid, block, 0, st, g, dev);
-    }
-    return 0;
 }
 
 }  // namespace
@@ -109,17 +84,7 @@ int check_net(const PulseTfeNtNet& n, bool need_weights, const char* name, NtDev
     return 0;
 }
 
-void launch_scatter(const Moves& m, const NtDev& dev, bool symmetric, void* stream) {
-    const dim3 grid((unsigned)((m.n_games + kScatterBlock - 1) / kScatterBlock), (unsigned)m.max_steps), block(kScatterBlock);
-    hipStream_t st = (hipStream_t)stream;
-    if (m.deltas) {
-        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, true, false>), grid, block, 0, st, m, dev);
-        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, true, false>), grid, block, 0, st, m, dev);
-    } else {
-        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, false, false>), grid, block, 0, st, m, dev);
-        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, false, false>), grid, block, 0, st, m, dev);
-    }
-}
+void launch_scatter(const Moves& m, const NtDev& dev, bool symmetric, void* stream) { launch_scatter_as<false>(m, dev, symmetric, stream); }
 
 int check_rollout(const PulseTfeNtRollout* o, const char* name, NtDev* dev, Games* g) {
     if (!o) return fail_named(name, "options are null");
@@ -163,7 +128,7 @@ extern "C" int pulse_tfe_nt_rollout(const PulseTfeNtRollout* o, void* stream) {
     NtDev dev;
     Games g;
     if (int rc = check_rollout(o, "pulse_tfe_nt_rollout", &dev, &g)) return rc;
-    if (int rc = launch_games(g, dev, o->net.symmetric != 0, true, stream)) return rc;
+    if (int rc = launch_play<true, 0, 0>(0, g, dev, o->net.symmetric != 0, stream)) return rc;
     return finish_launch("pulse_tfe_nt_rollout launch");
 }
 
@@ -171,7 +136,7 @@ extern "C" int pulse_tfe_nt_evaluate(const PulseTfeNtEval* o, void* stream) {
     NtDev dev;
     Games g;
     if (int rc = check_eval(o, "pulse_tfe_nt_evaluate", &dev, &g)) return rc;
-    if (int rc = launch_games(g, dev, o->net.symmetric != 0, false, stream)) return rc;
+    if (int rc = launch_play<false, 0, 0>(0, g, dev, o->net.symmetric != 0, stream)) return rc;
     return finish_launch("pulse_tfe_nt_evaluate launch");
 }
 

@@ -3,7 +3,7 @@
 // tfe_ntuple_backed.hip: search-backed targets; tfe_ntuple_restart.hip: roll-outs restarted from recorded boards;
 // tfe_ntuple_staged.hip: weight sets by tile stage, with the staged network and the stage of a board): the network as the
 // kernels take it, a feature's index, V of four afterstates at once, the learners' target, fixed-point difference and adds, their
-// parameters (Moves), shared refusals (check_moves), scatter kernel and launches, the backward walk's kernel, the four moves of a board, the greedy action, the game loop (play_game) with its parameters
+// parameters (Moves), shared refusals (check_moves, check_learner), scatter kernel and launch ladder, the backward walk's kernel and hand-off (launch_walk), the four moves of a board, the greedy action, the game loop (play_game) with its parameters
 // (Games) and the host's checks of the network, of the accumulators and of a batch of games.  One copy each.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -223,8 +223,8 @@ int check_moves(const O* o, const char* name, NtDev* dev, Moves* m) {
 
 // The learners' adds, one lane per recorded move: blockIdx.y = t, blockIdx.x * kScatterBlock + threadIdx.x = g.  Given: the move's
 // difference is o.deltas' (after the walk of tfe_ntuple_lambda.hip); otherwise it is the one-step difference, formed here.  Abs: the
-// adds go to o.acc_abs too (add_features).  One text (scatter_moves, which the kernels only call): tfe_ntuple.hip instantiates the
-// four forms without Abs, tfe_ntuple_tc.hip the four with it, tfe_ntuple_staged.hip the eight on the staged network.
+// adds go to o.acc_abs too (add_features).  One text (scatter_moves, which the kernel only calls): tfe_ntuple.hip instantiates the four forms without Abs (launch_scatter),
+// tfe_ntuple_tc.hip the four with it (launch_scatter_tc), tfe_ntuple_staged.hip the eight on the staged network.
 constexpr int kScatterBlock = 256;
 
 template <int IMG, bool Given, bool Abs, class Net>
@@ -265,16 +265,29 @@ __device__ __forceinline__ void scatter_moves(const Moves& o, const Net& net) {
     if (i < 3 && wg[i]) atomicAdd(reinterpret_cast<unsigned long long*>(o.stats) + (i == 0 ? 1 : i == 1 ? 2 : 4), wg[i]);
 }
 
-template <int IMG, bool Given, bool Abs>
-__global__ __launch_bounds__(kScatterBlock) void tfe_nt_scatter_kernel(const Moves o, const NtDev net) {
+template <int IMG, bool Given, bool Abs, class Net>
+__global__ __launch_bounds__(kScatterBlock) void tfe_nt_scatter_kernel(const Moves o, const Net net) {
     scatter_moves<IMG, Given, Abs>(o, net);
 }
 
-// ... its launch without Abs: the difference is m.deltas' where it is set and the one-step difference otherwise (defined in
-// tfe_ntuple.hip)
+// ... and its one launch ladder: the difference is m.deltas' where it is set and the one-step difference otherwise
+template <bool Abs, class Net>
+void launch_scatter_as(const Moves& m, const Net& net, const bool symmetric, void* stream) {
+    const dim3 grid((unsigned)((m.n_games + kScatterBlock - 1) / kScatterBlock), (unsigned)m.max_steps), block(kScatterBlock);
+    hipStream_t st = (hipStream_t)stream;
+    if (m.deltas) {
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, true, Abs, Net>), grid, block, 0, st, m, net);
+        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, true, Abs, Net>), grid, block, 0, st, m, net);
+    } else {
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, false, Abs, Net>), grid, block, 0, st, m, net);
+        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, false, Abs, Net>), grid, block, 0, st, m, net);
+    }
+}
+
+// ... instantiated on the one-stage network without Abs (defined in tfe_ntuple.hip)
 void launch_scatter(const Moves& m, const NtDev& dev, bool symmetric, void* stream);
 
-// ... and launch_scatter's counterpart with the third accumulator, m.acc_abs (defined in tfe_ntuple_tc.hip)
+// ... and with the third accumulator, m.acc_abs (defined in tfe_ntuple_tc.hip)
 void launch_scatter_tc(const Moves& m, const NtDev& dev, bool symmetric, void* stream);
 
 // The backward walk of the learners that carry credit along a game: D_t = delta_t + (gamma * lambda) * D_{t+1} into o.deltas.  Backed
@@ -355,6 +368,52 @@ void launch_lambda_walk(const PulseTfeNtLearnLambda& o, void* stream);
 // ... and of its second, the walk of backed[t + 1] - V_t (defined in tfe_ntuple_backed.hip, which instantiates it)
 void launch_backed_walk(const WalkBacked& o, void* stream);
 
+// `backed` and acc_abs of a learner's struct, null where the struct has no such field
+inline const double* backed_of(const PulseTfeNtLearnBacked& o) { return o.backed; }
+template <class O> const double* backed_of(const O&) { return nullptr; }
+inline int64_t* acc_abs_of(const PulseTfeNtLearnLambda&) { return nullptr; }
+template <class O> int64_t* acc_abs_of(const O& o) { return o.acc_abs; }
+
+// What the learners with a lambda refuse after check_moves (pulse_tfe_nt_learn_lambda, _learn_tc, _learn_backed, _learn_staged).
+// `need`: which of deltas, backed and acc_abs the entry point requires; one it does not require may be null, and deltas then only
+// where neither `backed` nor a lambda above 0 asks for them.
+enum : unsigned { kNeedDeltas = 1u, kNeedBacked = 2u, kNeedAccAbs = 4u };
+
+template <class O>
+int check_learner(const O* o, const char* name, const unsigned need) {
+    const double* backed = backed_of(*o);
+    const int64_t* acc_abs = acc_abs_of(*o);
+    if (!(o->lambda >= 0.0 && o->lambda <= 1.0)) return fail_named(name, "lambda must be in [0, 1]");
+    if (need & kNeedAccAbs) {                                                           // (who requires acc_abs refuses all of it first)
+        if (!acc_abs) return fail_named(name, "acc_abs is null");
+        if ((uintptr_t)acc_abs & 7u) return fail_named(name, "acc_abs must be 8-byte aligned");
+    }
+    if ((need & kNeedDeltas) && !o->deltas) return fail_named(name, "deltas is null");
+    if ((need & kNeedBacked) && !backed) return fail_named(name, "backed is null");
+    if (backed && !o->deltas) return fail_named(name, "deltas is null (backed needs them)");
+    if (o->lambda > 0.0 && !o->deltas) return fail_named(name, "deltas is null (lambda > 0 needs them)");
+    if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->values & 7u) || ((uintptr_t)o->deltas & 7u) || ((uintptr_t)o->stats & 7u))
+        return fail_named(name, "keys / values / deltas / stats must be 8-byte aligned");
+    if ((uintptr_t)backed & 7u) return fail_named(name, "backed must be 8-byte aligned");
+    if ((uintptr_t)acc_abs & 7u) return fail_named(name, "acc_abs must be 8-byte aligned");
+    if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
+    return 0;
+}
+
+// ... and their hand-off after the checks: where the struct has deltas, the walk (Backed where it has `backed`), then the adds of
+// what it left; m->acc_abs is the struct's
+template <class O>
+void launch_walk(const O* o, Moves* m, void* stream) {
+    m->acc_abs = acc_abs_of(*o);
+    if (!o->deltas) return;
+    WalkBacked w{};
+    w.n_games = o->n_games; w.max_steps = o->max_steps; w.gamma = o->gamma; w.lambda = o->lambda;
+    w.values = o->values; w.steps = o->steps; w.lengths = o->lengths; w.deltas = o->deltas; w.backed = backed_of(*o);
+    if (w.backed) launch_backed_walk(w, stream);
+    else launch_lambda_walk(w, stream);
+    m->deltas = o->deltas;
+}
+
 // what pulse_tfe_nt_rollout and pulse_tfe_nt_rollout_search refuse, and the game loop's parameters of a recording launch (defined in
 // tfe_ntuple.hip)
 int check_rollout(const PulseTfeNtRollout* o, const char* name, NtDev* dev, Games* g);
@@ -414,7 +473,7 @@ __device__ __forceinline__ void play_game(const Games& o, unsigned long long* wg
             const uint64_t key0 = o.start[g];                                           // (the same word in every lane that plays game g)
             const PackedBoard p0{(uint32_t)key0, (uint32_t)(key0 >> 32)};
             // A move changes a board without nibble 15 iff it is not zero and has an empty cell or two equal neighbours: the
-            // environment's own test (a second moves4 here cost tfe_nt_from_games_kernel<1> 30 VGPRs and two waves, section 13.7)
+            // environment's own test (a second moves4 here cost the one-lane kernel at IMG = 1 30 VGPRs and two waves, section 13.7)
             const bool full = (tfe_nz_nibbles(p0.lo) & tfe_nz_nibbles(p0.hi)) == 0x88888888u;
             const bool live = !tfe_over_packed(p0, full ? 0 : 2);
             if (key0 != 0ull && live && !has_nibble15(p0)) p = p0;

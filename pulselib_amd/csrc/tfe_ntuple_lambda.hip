@@ -36,13 +36,8 @@ extern "C" int pulse_tfe_nt_learn_lambda(const PulseTfeNtLearnLambda* o, void* s
     NtDev dev;
     Moves m;
     if (int rc = check_moves(o, name, &dev, &m)) return rc;
-    if (!(o->lambda >= 0.0 && o->lambda <= 1.0)) return fail_named(name, "lambda must be in [0, 1]");
-    if (!o->deltas) return fail_named(name, "deltas is null");
-    if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->values & 7u) || ((uintptr_t)o->deltas & 7u) || ((uintptr_t)o->stats & 7u))
-        return fail_named(name, "keys / values / deltas / stats must be 8-byte aligned");
-    if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
-    launch_lambda_walk(*o, stream);
-    m.deltas = o->deltas;
+    if (int rc = check_learner(o, name, kNeedDeltas)) return rc;
+    launch_walk(o, &m, stream);
     launch_scatter(m, dev, o->net.symmetric != 0, stream);
     return finish_launch("pulse_tfe_nt_learn_lambda launch");
 }

@@ -7,10 +7,10 @@
 // only difference), and the pick launch fills `start` for the next round from the round just recorded: the board the game stood on
 // at a fraction of its length.
 //
-// The six game kernels are their siblings' few wrapper lines: one lane per game on q = r + gamma * V (tfe_ntuple.hip's mapping), 32
-// lanes per game on search_q without and with the backed value (tfe_ntuple_search_rollout.hip's and tfe_ntuple_backed.hip's).  At 32
-// lanes per game every lane of a group reads the same start[g] and decides alike; `writer` guards the store of the 0.  The pick is
-// one lane per game: 4 + 8 bytes read and 8 written, one Philox block and one spawn.
+// The six game kernels are tfe_nt_play_kernel (tfe_ntuple_search_device.h) with From set: one lane per game on q = r + gamma * V, 32
+// lanes per game on search_q without and with the backed value.  At 32 lanes per game every lane of a group reads the same start[g]
+// and decides alike; `writer` guards the store of the 0.  The pick is one lane per game: 4 + 8 bytes read and 8 written, one Philox
+// block and one spawn.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -29,32 +29,6 @@ using pulse::finish_launch;
 
 constexpr int kBlock = 256;
 static_assert(sizeof(PulseTfeNtRestartPick) == 72 && sizeof(PulseTfeNtRollout) == 232, "struct layouts are part of the ABI");
-
-// one lane plays one game: q = r + gamma * V
-template <int IMG>
-__global__ __launch_bounds__(kBlock) void tfe_nt_from_games_kernel(const Games o, const NtDev net) {
-    __shared__ unsigned long long wg[2];
-    if (threadIdx.x < 2) wg[threadIdx.x] = 0ull;
-    __syncthreads();
-    play_game<true, false, true>(o, wg, blockIdx.x * kBlock + threadIdx.x, true,
-                                 [&](const uint64_t, const uint64_t (&ka)[4], const int (&sc)[4], double (&v)[4], double (&q)[4]) {
-                                     one_ply_q<IMG>(net, o.weights, o.gamma, ka, sc, v, q);
-                                 });
-}
-
-// one game per group of 32 lanes: g < n_games is the same in the 32, and a group beyond the batch only meets the barrier of the counts
-template <int IMG, bool Backed>
-__global__ __launch_bounds__(kSearchBlock) void tfe_nt_from_search_kernel(const Games o, const NtDev net) {
-    __shared__ unsigned long long wg[2];
-    if (threadIdx.x < 2) wg[threadIdx.x] = 0ull;
-    __syncthreads();
-    const int g = (int)blockIdx.x * kGroupsPerBlock + ((int)threadIdx.x >> 5), s = (int)threadIdx.x & (kGroup - 1);
-    play_game<true, Backed, true>(o, wg, g, s == 0,
-                                  [&](const uint64_t key_b, const uint64_t (&ka)[4], const int (&sc)[4], double (&v)[4], double (&q)[4]) {
-                                      values4<IMG>(net, o.weights, ka, v);
-                                      search_q<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, s, q);
-                                  });
-}
 
 // One lane per game: the board game g of the recorded round stood on before its move t*, t* = floor(L * fraction) -- the afterstate
 // of move t* - 1 with the environment's spawn of draw t* put into it, as the game loop did -- or 0.  t* - 1 <= L - 2 < max_steps:
@@ -91,30 +65,11 @@ extern "C" int pulse_tfe_nt_rollout_from(const PulseTfeNtRollout* o, int32_t lay
     NtDev dev;
     Games g;
     if (int rc = check_rollout(o, name, &dev, &g)) return rc;
-    if (layers != 0 && layers != 1) return fail_named(name, "layers must be 0 or 1");
-    if (backed && layers == 0) return fail_named(name, "backed needs layers = 1: a one-ply roll-out has no search to back a value up");
-    if ((uintptr_t)backed & 7u) return fail_named(name, "backed must be 8-byte aligned");
-    if (!start) return fail_named(name, "start is null");
-    if ((uintptr_t)start & 7u) return fail_named(name, "start must be 8-byte aligned");
-    if (int rc = pulse::tfe_row_lut(&g.lut)) return rc;
+    if (int rc = check_start(layers, backed, start, name, "layers must be 0 or 1")) return rc;
     g.backed = backed;
     g.start = start;
-    const bool sym = o->net.symmetric != 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (layers == 0) {
-        const dim3 grid((unsigned)(((int64_t)g.n_games + kBlock - 1) / kBlock)), block(kBlock);
-        if (sym) hipLaunchKernelGGL(tfe_nt_from_games_kernel<8>, grid, block, 0, st, g, dev);
-        else hipLaunchKernelGGL(tfe_nt_from_games_kernel<1>, grid, block, 0, st, g, dev);
-    } else {
-        const dim3 grid((unsigned)(((int64_t)g.n_games + kGroupsPerBlock - 1) / kGroupsPerBlock)), block(kSearchBlock);
-        if (backed) {
-            if (sym) hipLaunchKernelGGL((tfe_nt_from_search_kernel<8, true>), grid, block, 0, st, g, dev);
-            else hipLaunchKernelGGL((tfe_nt_from_search_kernel<1, true>), grid, block, 0, st, g, dev);
-        } else {
-            if (sym) hipLaunchKernelGGL((tfe_nt_from_search_kernel<8, false>), grid, block, 0, st, g, dev);
-            else hipLaunchKernelGGL((tfe_nt_from_search_kernel<1, false>), grid, block, 0, st, g, dev);
-        }
-    }
+    if (int rc = backed ? launch_play<true, 0, 1, true, true>(layers, g, dev, o->net.symmetric != 0, stream)
+                        : launch_play<true, 0, 1, false, true>(layers, g, dev, o->net.symmetric != 0, stream)) return rc;
     return finish_launch("pulse_tfe_nt_rollout_from launch");
 }
 

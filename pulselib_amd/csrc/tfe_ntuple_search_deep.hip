@@ -1,6 +1,7 @@
 // tfe_ntuple_search_deep.hip -- the 2048 n-tuple network under expectimax search two chance layers deep, two
 // launches: pulse_tfe_nt_search_deep and pulse_tfe_nt_evaluate_search_deep (include/pulse_env.h).  At layers = 1 they launch the
-// kernels of tfe_ntuple_search.hip; the kernels here are those of layers = 2.
+// kernels of tfe_ntuple_search.hip; the kernels here are those of layers = 2: the board kernel below and tfe_nt_play_kernel
+// (tfe_ntuple_search_device.h) at 256 lanes per game.
 //
 // q_a = r_a + gamma * E_a as in section 13.1, with the best q of the ONE-LAYER search of the board after the spawn where that section
 // has its best one-ply value.  One board or game per workgroup of 256 lanes = 8 groups of 32.  The live children (a, slot) of the
@@ -45,20 +46,6 @@ __global__ __launch_bounds__(kSearchBlock) void tfe_nt_search2_kernel(const Puls
     }
 }
 
-// pulse_tfe_nt_evaluate's game loop with q from the two-layer search, one game per workgroup: g is blockIdx.x, so the 256 lanes play
-// the game alike -- the same boards, draws and length -- and reach search_q2's barriers together; lane 0 writes and counts
-template <int IMG>
-__global__ __launch_bounds__(kSearchBlock) void tfe_nt_search2_games_kernel(const Games o, const NtDev net) {
-    __shared__ unsigned long long wg[kEvalBins];
-    __shared__ double terms[4 * kGroup];
-    if (threadIdx.x < kEvalBins) wg[threadIdx.x] = 0ull;
-    __syncthreads();
-    play_game<false>(o, wg, (int)blockIdx.x, threadIdx.x == 0,
-                     [&](const uint64_t key_b, const uint64_t (&ka)[4], const int (&sc)[4], double (&)[4], double (&q)[4]) {
-                         search_q2<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, terms, q);
-                     });
-}
-
 }  // namespace
 
 extern "C" int pulse_tfe_nt_search_deep(const PulseTfeNtSearch* o, int32_t layers, void* stream) {
@@ -84,13 +71,6 @@ extern "C" int pulse_tfe_nt_evaluate_search_deep(const PulseTfeNtEval* o, int32_
     Games g;
     if (int rc = check_eval(o, name, &dev, &g)) return rc;
     if (int rc = check_layers(layers, name)) return rc;
-    if (int rc = pulse::tfe_row_lut(&g.lut)) return rc;
-    if (layers == 1) {
-        launch_search_games(g, dev, o->net.symmetric != 0, stream);
-    } else {
-        const dim3 grid((unsigned)g.n_games), block(kSearchBlock);
-        if (o->net.symmetric) hipLaunchKernelGGL(tfe_nt_search2_games_kernel<8>, grid, block, 0, (hipStream_t)stream, g, dev);
-        else hipLaunchKernelGGL(tfe_nt_search2_games_kernel<1>, grid, block, 0, (hipStream_t)stream, g, dev);
-    }
+    if (int rc = layers == 1 ? launch_search_games(g, dev, o->net.symmetric != 0, stream) : launch_play<false, 2, 2>(2, g, dev, o->net.symmetric != 0, stream)) return rc;
     return finish_launch("pulse_tfe_nt_evaluate_search_deep launch");
 }

@@ -1,12 +1,14 @@
-// tfe_ntuple_search_device.h -- what the units of the n-tuple network's expectimax play share (tfe_ntuple_search.hip: one chance
-// layer; tfe_ntuple_search_deep.hip: two, section 13.4; tfe_ntuple_search_rollout.hip: the recording games
-// under either, section 13.5): the group of 32 lanes, the tile odds, the board launch's refusals (check_search), the chance layer
-// itself (search_q), the two-layer deal over a workgroup (search_q2 with live_slots and nth_set_bit) and the launches of the
-// one-layer kernels.  One copy each.  Not part of the ABI.
+// tfe_ntuple_search_device.h -- what the units of the n-tuple network's play share (tfe_ntuple.hip: one ply; tfe_ntuple_search.hip: one
+// chance layer; tfe_ntuple_search_deep.hip: two, section 13.4; tfe_ntuple_search_rollout.hip, _backed.hip,
+// _restart.hip and _staged.hip: the recording games, sections 13.5 to 13.9): the group of 32 lanes, the tile odds, the board
+// launch's refusals (check_search), the chance layer itself (search_q), the two-layer deal over a workgroup (search_q2 with
+// live_slots and nth_set_bit), the one game kernel (tfe_nt_play_kernel) with its launch ladder (launch_play) and the one-layer board
+// kernel with its launch (launch_boards).  One copy each.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "pulse_internal.h"
 #include "tfe_device.h"
@@ -39,10 +41,20 @@ inline int check_layers(const int32_t layers, const char* name) {
     return layers == 1 || layers == 2 ? 0 : fail_named(name, "layers must be 1 or 2");
 }
 
-// The launches of the one-layer kernels (defined in tfe_ntuple_search.hip, where the kernels are), after the checks: of the boards
-// of `o` with the row table `lut`, and of the games `g` (g.lut set)
+// ... and what pulse_tfe_nt_rollout_from and pulse_tfe_nt_rollout_staged refuse of theirs, of `backed` and of `start`
+inline int check_start(const int32_t layers, const double* backed, const uint64_t* start, const char* name, const char* layers_message) {
+    if (layers != 0 && layers != 1) return fail_named(name, layers_message);
+    if (backed && layers == 0) return fail_named(name, "backed needs layers = 1: a one-ply roll-out has no search to back a value up");
+    if ((uintptr_t)backed & 7u) return fail_named(name, "backed must be 8-byte aligned");
+    if (!start) return fail_named(name, "start is null");
+    if ((uintptr_t)start & 7u) return fail_named(name, "start must be 8-byte aligned");
+    return 0;
+}
+
+// The launches of the one-layer kernels on the one-stage network (defined in tfe_ntuple_search.hip, which instantiates them), after
+// the checks: of the boards of `o` with the row table `lut`, and of the evaluation's games `g`
 void launch_search(const PulseTfeNtSearch& o, const NtDev& dev, const uint32_t* lut, void* stream);
-void launch_search_games(const Games& g, const NtDev& dev, bool symmetric, void* stream);
+int launch_search_games(Games& g, const NtDev& dev, bool symmetric, void* stream);
 
 __device__ __forceinline__ int count_empty(const uint64_t key) {
     return __popc(tfe_nz_nibbles((uint32_t)key) ^ 0x88888888u) + __popc(tfe_nz_nibbles((uint32_t)(key >> 32)) ^ 0x88888888u);
@@ -166,6 +178,113 @@ __device__ __forceinline__ void search_q2(const NtDev& net, const float* __restr
         q[a] = 0.0;
         if (ka[a] != key_b) q[a] = __dadd_rn((double)tfe_reward(sc[a]), __dmul_rn(gamma, __ddiv_rn(term, (double)count_empty(ka[a]))));
     }
+}
+
+// pulse_tfe_nt_search's struct as its one-layer kernel takes it
+struct Boards {
+    const float* weights;
+    int32_t n_boards;
+    double gamma;
+    uint64_t tie_seed, round;
+    const uint64_t* boards;
+    double* q; int8_t* action; uint8_t* candidates;
+    const uint32_t* lut;
+};
+
+// 32 lanes per board (pulse_tfe_nt_search, pulse_tfe_nt_search_staged): lane 0 of the group writes
+template <int IMG, class Net>
+__global__ __launch_bounds__(kSearchBlock) void tfe_nt_search_kernel(const Boards o, const Net net) {
+    const int g = (int)blockIdx.x * kGroupsPerBlock + ((int)threadIdx.x >> 5), s = (int)threadIdx.x & (kGroup - 1);
+    if (g >= o.n_boards) return;
+    const uint64_t key_b = o.boards[g];
+    uint64_t ka[4];
+    int sc[4];
+    moves4(key_b, o.lut, ka, sc);
+    double q[4];
+    search_q<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, s, q);
+    uint32_t bits;
+    const int best = greedy_of(q, key_b, ka, o.tie_seed, o.round, &bits);
+    if (s == 0) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) o.q[(size_t)g * 4 + a] = q[a];
+        o.action[g] = (int8_t)best;
+        o.candidates[g] = (uint8_t)bits;
+    }
+}
+
+template <class Net>
+void launch_boards(const PulseTfeNtSearch& o, const Net& net, const uint32_t* lut, void* stream) {
+    const Boards b{o.net.weights, o.n_boards, o.gamma, o.tie_seed, o.round, o.boards, o.q, o.action, o.candidates, lut};
+    const dim3 grid((unsigned)(((int64_t)o.n_boards + kGroupsPerBlock - 1) / kGroupsPerBlock)), block(kSearchBlock);
+    if (o.net.symmetric) hipLaunchKernelGGL((tfe_nt_search_kernel<8, Net>), grid, block, 0, (hipStream_t)stream, b, net);
+    else hipLaunchKernelGGL((tfe_nt_search_kernel<1, Net>), grid, block, 0, (hipStream_t)stream, b, net);
+}
+
+// The one game kernel: play_game<Record, Backed, From> on one of three mappings of a game to lanes, each with the q its policy plays on.
+template <int LANES /* 1, 32 (kGroup) or 256 (kSearchBlock) per game */, int IMG, bool Record, bool Backed, bool From, class Net>
+__global__ __launch_bounds__(kSearchBlock) void tfe_nt_play_kernel(const Games o, const Net net) {
+    constexpr int kCounters = Record ? 2 : kEvalBins;
+    __shared__ unsigned long long wg[kCounters];
+    if (threadIdx.x < kCounters) wg[threadIdx.x] = 0ull;
+    if constexpr (LANES == 1) {
+        // one lane plays one game: q = r + gamma * V
+        static_assert(kSearchBlock == 256, "the one-lane mapping's workgroup is the 256 lanes (kBlock) of its units' other kernels");
+        __syncthreads();
+        play_game<Record, Backed, From>(o, wg, blockIdx.x * kSearchBlock + threadIdx.x, true,
+                                        [&](const uint64_t, const uint64_t (&ka)[4], const int (&sc)[4], double (&v)[4], double (&q)[4]) {
+                                            one_ply_q<IMG>(net, o.weights, o.gamma, ka, sc, v, q);
+                                        });
+    } else if constexpr (LANES == kGroup) {
+        // One game per group of 32 lanes, which play it alike -- the same start[g], boards, draws and four afterstates, so the gathers
+        // are uniform -- and lane 0 of the group writes and counts.  g < n_games is the same in the 32, and a group beyond the batch
+        // only meets the barrier of the counts.  A recording launch records the NETWORK's V of the chosen afterstate, not the search's
+        // backed-up value: values4 runs before the search starts, so that its indices and loaded words are dead by then and eight
+        // registers (the four doubles) live across the search.
+        __syncthreads();
+        const int g = (int)blockIdx.x * kGroupsPerBlock + ((int)threadIdx.x >> 5), s = (int)threadIdx.x & (kGroup - 1);
+        play_game<Record, Backed, From>(o, wg, g, s == 0,
+                                        [&](const uint64_t key_b, const uint64_t (&ka)[4], const int (&sc)[4], double (&v)[4], double (&q)[4]) {
+                                            if constexpr (Record) values4<IMG>(net, o.weights, ka, v);
+                                            search_q<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, s, q);
+                                        });
+    } else {
+        // One game per workgroup: g is blockIdx.x (grid = n_games), so the 256 lanes play the game alike -- the same boards, draws and
+        // length -- and thread 0 writes and counts.  Nothing lane-dependent encloses q_of: search_q2's two barriers per move are
+        // reached by the 256 lanes together, which leave the loop at the same move, and `writer` guards stores only.
+        static_assert(LANES == kSearchBlock, "a game is played by 1, 32 or 256 lanes");
+        __shared__ double terms[4 * kGroup];
+        __syncthreads();
+        play_game<Record, Backed, From>(o, wg, (int)blockIdx.x, threadIdx.x == 0,
+                                        [&](const uint64_t key_b, const uint64_t (&ka)[4], const int (&sc)[4], double (&v)[4], double (&q)[4]) {
+                                            if constexpr (Record) values4<IMG>(net, o.weights, ka, v);
+                                            search_q2<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, terms, q);
+                                        });
+    }
+}
+
+// The one launch ladder of the games, after the checks: fetches the row table, and launches the mapping of `layers` (0: one lane
+// per game, 1: 32, 2: 256), which the caller has checked to be in MinLayers..MaxLayers -- the depths its unit builds, so a unit
+// instantiates the kernels it can launch and no others.  A backed value needs a search: Backed builds no one-ply form.
+template <bool Record, int MinLayers, int MaxLayers, bool Backed = false, bool From = false, class Net>
+int launch_play(const int layers, Games& g, const Net& net, const bool symmetric, void* stream) {
+    static_assert(0 <= MinLayers && MinLayers <= MaxLayers && MaxLayers <= (kStaged<Net> ? 1 : 2), "search_q2 takes the one-stage network only");
+    if (int rc = pulse::tfe_row_lut(&g.lut)) return rc;
+    const auto launch = [&](auto lanes) {
+        constexpr int LANES = decltype(lanes)::value;
+        const dim3 grid((unsigned)(((int64_t)g.n_games * LANES + kSearchBlock - 1) / kSearchBlock)), block(kSearchBlock);
+        if (symmetric) hipLaunchKernelGGL((tfe_nt_play_kernel<LANES, 8, Record, Backed, From, Net>), grid, block, 0, (hipStream_t)stream, g, net);
+        else hipLaunchKernelGGL((tfe_nt_play_kernel<LANES, 1, Record, Backed, From, Net>), grid, block, 0, (hipStream_t)stream, g, net);
+    };
+    if constexpr (MinLayers == 0 && !Backed) {
+        if (layers == 0) launch(std::integral_constant<int, 1>{});
+    }
+    if constexpr (MinLayers <= 1 && MaxLayers >= 1) {
+        if (layers == 1) launch(std::integral_constant<int, kGroup>{});
+    }
+    if constexpr (MaxLayers == 2) {
+        if (layers == 2) launch(std::integral_constant<int, kSearchBlock>{});
+    }
+    return 0;
 }
 
 }  // namespace pulse_tfe

@@ -58,17 +58,7 @@ __global__ __launch_bounds__(kBlock) void tfe_nt_tc_apply_kernel(float* __restri
 namespace pulse_tfe {
 
 // launch_scatter's counterpart with the third accumulator (declared in tfe_ntuple_device.h: pulse_tfe_nt_learn_backed launches it too)
-void launch_scatter_tc(const Moves& m, const NtDev& dev, bool symmetric, void* stream) {
-    const dim3 grid((unsigned)((m.n_games + kScatterBlock - 1) / kScatterBlock), (unsigned)m.max_steps), block(kScatterBlock);
-    hipStream_t st = (hipStream_t)stream;
-    if (m.deltas) {
-        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, true, true>), grid, block, 0, st, m, dev);
-        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, true, true>), grid, block, 0, st, m, dev);
-    } else {
-        if (symmetric) hipLaunchKernelGGL((tfe_nt_scatter_kernel<8, false, true>), grid, block, 0, st, m, dev);
-        else hipLaunchKernelGGL((tfe_nt_scatter_kernel<1, false, true>), grid, block, 0, st, m, dev);
-    }
-}
+void launch_scatter_tc(const Moves& m, const NtDev& dev, bool symmetric, void* stream) { launch_scatter_as<true>(m, dev, symmetric, stream); }
 
 }  // namespace pulse_tfe
 
@@ -77,21 +67,8 @@ extern "C" int pulse_tfe_nt_learn_tc(const PulseTfeNtLearnTc* o, void* stream) {
     NtDev dev;
     Moves m;
     if (int rc = check_moves(o, name, &dev, &m)) return rc;
-    if (!(o->lambda >= 0.0 && o->lambda <= 1.0)) return fail_named(name, "lambda must be in [0, 1]");
-    if (!o->acc_abs) return fail_named(name, "acc_abs is null");
-    if ((uintptr_t)o->acc_abs & 7u) return fail_named(name, "acc_abs must be 8-byte aligned");
-    if (o->lambda > 0.0 && !o->deltas) return fail_named(name, "deltas is null (lambda > 0 needs them)");
-    if (((uintptr_t)o->keys & 7u) || ((uintptr_t)o->values & 7u) || ((uintptr_t)o->deltas & 7u) || ((uintptr_t)o->stats & 7u))
-        return fail_named(name, "keys / values / deltas / stats must be 8-byte aligned");
-    if ((uintptr_t)o->lengths & 3u) return fail_named(name, "lengths must be 4-byte aligned");
-    m.acc_abs = o->acc_abs;
-    if (o->deltas) {                                                                    // the walk, then the adds of what it left
-        PulseTfeNtLearnLambda w{};
-        w.n_games = o->n_games; w.max_steps = o->max_steps; w.gamma = o->gamma; w.lambda = o->lambda;
-        w.values = o->values; w.steps = o->steps; w.lengths = o->lengths; w.deltas = o->deltas;
-        launch_lambda_walk(w, stream);
-        m.deltas = o->deltas;
-    }
+    if (int rc = check_learner(o, name, kNeedAccAbs)) return rc;
+    launch_walk(o, &m, stream);
     launch_scatter_tc(m, dev, o->net.symmetric != 0, stream);
     return finish_launch("pulse_tfe_nt_learn_tc launch");
 }

@@ -13,7 +13,7 @@ import pytest
 
 from tests.native_args import PTR, assert_refusals, remarks
 from tests.tfe_backed_host import backed_rollout_on_host
-from tests.tfe_nt_support import BOARD_ID0, CASES, CRAFTED, MORE, P, ROOT, TUPLES, assert_exports, assert_no_scratch, bits, opts, weights
+from tests.tfe_nt_support import BOARD_ID0, CASES, CRAFTED, MORE, P, ROOT, TUPLES, assert_exports, assert_no_scratch, play_kernels, bits, opts, weights
 from tests.tfe_nt_support import nt as _nt
 from tests.tfe_search_host import key_of, scalar_search_on_host
 
@@ -260,6 +260,6 @@ def test_backed_kernels_use_no_scratch():
     Backed set, none with scratch or a spilled vector register.  VGPRs as built: one layer 160 (symmetric) / 135, two layers 204 / 177,
     the walk 98."""
     names = assert_no_scratch("ntuple-backed-resource-usage",
-                              {"tfe_nt_backed_rollout_kernel": 2, "tfe_nt_backed2_rollout_kernel": 2, "tfe_nt_lambda_walk_kernel": 1}, 256)
+                              {**play_kernels(32, True, backed=True), **play_kernels(256, True, backed=True), "tfe_nt_lambda_walk_kernel": 1}, 256)
     assert all("ILb1E" in n for n in names if "tfe_nt_lambda_walk_kernel" in n)      # the walk here is the Backed one
     assert "scatter" not in " ".join(names) and len(re.findall(r"Function Name:", remarks("ntuple-backed-resource-usage"))) == 5

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests.native_args import assert_refusals
-from tests.tfe_nt_support import CASES, assert_exports, assert_no_scratch, opts, worked_games
+from tests.tfe_nt_support import CASES, assert_exports, assert_no_scratch, play_kernels, opts, worked_games
 
 NAMES = ("pulse_tfe_nt_rollout", "pulse_tfe_nt_learn", "pulse_tfe_nt_apply", "pulse_tfe_nt_evaluate")
 STRUCTS = dict(zip(NAMES, ("TfeNtRollout", "TfeNtLearn", "TfeNtApply", "TfeNtEval")))
@@ -230,4 +230,4 @@ def test_checkpoint_round_trip(tmp_path):
 def test_kernels_use_no_scratch():
     """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple.hip with the Makefile's flags: nine kernels, none with scratch or a spilled vector
     register.  VGPRs as built: games 118 (symmetric) / 63, scatter 59 / 18 (both learners'), apply 22."""
-    assert_no_scratch("ntuple-resource-usage", {"tfe_nt_games_kernel": 4, "tfe_nt_scatter_kernel": 4, "tfe_nt_apply_kernel": 1}, 128)
+    assert_no_scratch("ntuple-resource-usage", {**play_kernels(1, True), **play_kernels(1, False), "tfe_nt_scatter_kernel": 4, "tfe_nt_apply_kernel": 1}, 128)

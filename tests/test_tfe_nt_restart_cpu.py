@@ -14,7 +14,7 @@ import pytest
 from tests import tfe_host
 from tests.native_args import PTR, assert_refusals, remarks, resource_usage
 from tests.native_args import opts as plain_opts
-from tests.tfe_nt_support import BOARD_ID0, CASES, CRAFTED, ROOT, TUPLES, assert_exports, assert_no_scratch, bits, opts, weights
+from tests.tfe_nt_support import BOARD_ID0, CASES, CRAFTED, ROOT, TUPLES, assert_exports, assert_no_scratch, play_kernel, play_kernels, bits, opts, weights
 from tests.tfe_nt_support import nt as _nt
 from tests.tfe_restart_host import boards_of_keys, rollout_from_on_host, usable_on_host
 from tests.tfe_search_host import key_of
@@ -269,10 +269,12 @@ def test_restart_kernels_use_no_scratch():
     (one ply 117 symmetric / 61; one layer 158 / 133; one layer with the backed value 160 / 135) plus four: the start word and its
     address, two registers each.  VGPRs as built: one ply 117 / 61, one layer 159 / 133, with the backed value 161 / 135, the pick 16."""
     names = assert_no_scratch("ntuple-restart-resource-usage",
-                              {"tfe_nt_from_games_kernel": 2, "tfe_nt_from_search_kernel": 4, "tfe_nt_restart_pick_kernel": 1}, 160 + 4)
+                              {**play_kernels(1, True, start=True), **play_kernels(32, True, start=True), **play_kernels(32, True, backed=True, start=True),
+                               "tfe_nt_restart_pick_kernel": 1}, 160 + 4)
     assert len(re.findall(r"Function Name:", remarks("ntuple-restart-resource-usage"))) == 7
-    ceiling = {"from_games_kernelILi8E": 117, "from_games_kernelILi1E": 61, "from_search_kernelILi8ELb0E": 158, "from_search_kernelILi1ELb0E": 133,
-               "from_search_kernelILi8ELb1E": 160, "from_search_kernelILi1ELb1E": 135, "restart_pick_kernel": 32 - 4}
+    ceiling = {play_kernel(1, 8, True, start=True): 117, play_kernel(1, 1, True, start=True): 61,
+               play_kernel(32, 8, True, start=True): 158, play_kernel(32, 1, True, start=True): 133,
+               play_kernel(32, 8, True, backed=True, start=True): 160, play_kernel(32, 1, True, backed=True, start=True): 135, "restart_pick_kernel": 32 - 4}
     _, vgprs, _, _ = resource_usage("ntuple-restart-resource-usage")
     for name, v in zip(names, vgprs):
         key = [k for k in ceiling if k in name]

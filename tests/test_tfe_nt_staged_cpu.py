@@ -14,7 +14,7 @@ import pytest
 from tests import tfe_host
 from tests.native_args import PTR, assert_refusals, resource_usage
 from tests.tfe_nt_staged_support import STAGE_TILES, adds_per_stage, staged, stages_struct
-from tests.tfe_nt_support import (BOARD_ID0, CASES, LAMBDA, ROOT, SEARCH_CASES, STEP_SIZE, V, X, Y, assert_no_scratch, bits, opts)
+from tests.tfe_nt_support import (BOARD_ID0, CASES, LAMBDA, ROOT, SEARCH_CASES, STEP_SIZE, V, X, Y, assert_no_scratch, play_kernels, bits, opts)
 from tests.tfe_nt_support import nt as _nt
 from tests.tfe_search_host import key_of
 
@@ -396,11 +396,12 @@ def test_the_checkpoint(tmp_path):
 def test_staged_kernels_use_no_scratch_and_stay_within_the_recorded_registers():
     """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_staged.hip with the Makefile's flags: twenty kernels, none with scratch or a spilled
     vector register, each within the VGPR count of its line in profiles/tfe_mc/kernel_resource_usage.txt."""
-    counts = {"tfe_nt_staged_games_kernel": 2, "tfe_nt_staged_search_rollout_kernel": 4, "tfe_nt_staged_eval_kernel": 2, "tfe_nt_staged_search_eval_kernel": 2,
-              "tfe_nt_staged_search_kernel": 2, "tfe_nt_staged_scatter_kernel": 8}
+    staged = dict(net="NtStagedDev")
+    counts = {**play_kernels(1, True, start=True, **staged), **play_kernels(32, True, start=True, **staged), **play_kernels(32, True, backed=True, start=True, **staged),
+              **play_kernels(1, False, **staged), **play_kernels(32, False, **staged), "tfe_nt_search_kernel": 2, "tfe_nt_scatter_kernel": 8}
     names = assert_no_scratch("ntuple-staged-resource-usage", counts, 165 + 4)
     text = (ROOT / "profiles" / "tfe_mc" / "kernel_resource_usage.txt").read_text()
-    recorded = dict(re.findall(r"^tfe_ntuple_staged\.hip:\d+:\d+: Function Name: (\S+)\n.*\n.*VGPRs: (\d+)$", text, flags=re.M))
+    recorded = dict(re.findall(r"^tfe_ntuple\w*\.h:\d+:\d+: Function Name: (\S+NtStagedDev\S+)\n.*\n.*VGPRs: (\d+)$", text, flags=re.M))
     _, vgprs, _, _ = resource_usage("ntuple-staged-resource-usage")
     assert sorted(recorded) == sorted(names) and len(names) == 20
     for name, v in zip(names, vgprs):

@@ -199,6 +199,6 @@ def test_tc_kernels_use_no_scratch():
     """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_tc.hip with the Makefile's flags: five kernels -- the scatter text's four forms with
     the third accumulator and the apply -- none with scratch or a spilled vector register.  VGPRs as built: scatter 59 / 20, apply 41."""
     names = assert_no_scratch("ntuple-tc-resource-usage", {"tfe_nt_scatter_kernel": 4, "tfe_nt_tc_apply_kernel": 1}, 128)
-    assert all("Lb1EEE" in n for n in names if "tfe_nt_scatter_kernel" in n)        # every one of the four has Abs = true
+    assert all("Lb1ENS_5NtDevEEE" in n for n in names if "tfe_nt_scatter_kernel" in n)  # every one of the four has Abs = true
     sgpr_spills = re.findall(r"SGPRs Spill: (\d+)", remarks("ntuple-tc-resource-usage"))
     assert sgpr_spills == ["0"] * 5

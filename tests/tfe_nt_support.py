@@ -232,6 +232,16 @@ def assert_exports(names_and_structs, argtypes, header_pattern):
     return lib, text
 
 
+def play_kernel(lanes, img, record, backed=False, start=False, net="NtDev"):
+    """What names one instance of csrc's tfe_nt_play_kernel<LANES, IMG, Record, Backed, From, Net> in a kernel's mangled name."""
+    return "tfe_nt_play_kernelILi%dELi%dELb%dELb%dELb%dENS_%d%sEEE" % (lanes, img, record, backed, start, len(net), net)
+
+
+def play_kernels(lanes, record, backed=False, start=False, net="NtDev"):
+    """assert_no_scratch's counts of the symmetric and the plain instance of play_kernel(lanes, IMG, ...): one each"""
+    return {play_kernel(lanes, img, record, backed, start, net): 1 for img in (8, 1)}
+
+
 def assert_no_scratch(target, counts, max_vgprs):
     """The kernels of csrc's `make <target>` are those of `counts` {a substring of the name: how many}, none with scratch or a spilled
     vector register, none above max_vgprs.  Returns their names."""
