@@ -1091,6 +1091,44 @@ int pulse_tfe_nt_learn_staged(const PulseTfeNtLearnBacked* o, const PulseTfeNtSt
 int pulse_tfe_nt_evaluate_staged(const PulseTfeNtEval* o, const PulseTfeNtStages* stages, int32_t layers, void* stream);
 int pulse_tfe_nt_search_staged(const PulseTfeNtSearch* o, const PulseTfeNtStages* stages, void* stream);
 
+/* ---- ... and games continued across rounds: a round of a small max_steps = K plays K moves of every game, and the next round takes
+ * the cut games up again under the new weights.  Opt-in: a caller that never calls this keeps every launch above unchanged.
+ *
+ * pulse_tfe_nt_continue_pick: from the round just recorded, the next round's `start` (pulse_tfe_nt_rollout_from, _rollout_staged), the
+ * score and moves of every game so far, and the whole games that finished.  For game g let L = min(lengths[g], max_steps) (at least
+ * 1), b = steps[(L - 1) * n_games + g], A = keys[(L - 1) * n_games + g] (the last afterstate) and id = board_id0 + g.
+ *   CUT -- b has no terminal bit, A holds no nibble 15 and L == max_steps.  The learners skipped move L - 1 (it has no successor), so
+ *     the game is taken up on the board that move was made on and the move is decided again:
+ *       start[g]        = keys[(L - 2) * n_games + g] with the spawn of Philox4x32-10(env_seed, id, L - 1) words x (cell) and y (tile);
+ *       carry_score[g] += total_score[g] - sc, sc the merge score of moving that board by the action b & 3;
+ *       carry_moves[g] += L - 1;                finished[5] += 1.
+ *     The launch does not check that the move gives A again.
+ *   FINISHED -- every other game: it is over, or it stopped at the 32,768 tile.  The whole game has the score
+ *     s = carry_score[g] + total_score[g] and carry_moves[g] + L moves, and its largest tile is that of A with the spawn of
+ *     Philox4x32-10(env_seed, id, L): the board pulse_tfe_nt_evaluate's game ends on.  Added to `finished`:
+ *       [0] games  [1] moves  [2] sum of s  [3] sum of s * s  [4] max of s  [6] games with carry_moves[g] > 0 (continued at least
+ *       once)  [7] games whose A holds a nibble 15;  [8 + k] games whose largest tile is 2^k (k = 15: 32,768).
+ *     start[g] = 0, carry_score[g] = 0, carry_moves[g] = 0: the next round's game g begins at its reset.
+ * env_seed and board_id0 are those of the launch that RECORDED the round.  One lane per game; no other launch need have finished
+ * but the recording one.  Zero-initialise the struct: reserved0 must be 0.  sizeof == 96.
+ *
+ * PULSE_EINVAL, before anything is launched: null options, n_games < 1, max_steps outside 2..65,535, reserved0 not 0, a null
+ * pointer, keys / total_score / start / carry_score / finished not 8-byte or lengths / carry_moves not 4-byte aligned. */
+typedef struct PulseTfeNtContinuePick {
+    int32_t n_games, max_steps;         /* max_steps: the segment length K of the round that recorded */
+    uint64_t env_seed, board_id0;       /* of the round that recorded */
+    int64_t reserved0;
+    const uint64_t* keys;               /* uint64[max_steps * n_games] */
+    const uint8_t* steps;               /* uint8[max_steps * n_games] */
+    const int32_t* lengths;             /* int32[n_games] */
+    const int64_t* total_score;         /* int64[n_games] */
+    uint64_t* start;                    /* uint64[n_games], written */
+    int64_t* carry_score;               /* int64[n_games], read and written */
+    int32_t* carry_moves;               /* int32[n_games], read and written */
+    int64_t* finished;                  /* int64[24], added to (word 4: a maximum) */
+} PulseTfeNtContinuePick;
+int pulse_tfe_nt_continue_pick(const PulseTfeNtContinuePick* o, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

@@ -190,7 +190,12 @@ class TfeNtRestartPick(C.Structure):
                 ("min_length", C.c_int32), ("reserved0", C.c_int32)] + [(n, C.c_void_p) for n in ("keys", "lengths", "start", "picked")]
 
 
-class TfeNtStages(C.Structure):                                             # weight sets by tile stage: beside the struct of a *_staged entry point
+class TfeNtContinuePick(C.Structure):                                       # games continued across rounds
+    _fields_ = [("n_games", C.c_int32), ("max_steps", C.c_int32), ("env_seed", C.c_uint64), ("board_id0", C.c_uint64), ("reserved0", C.c_int64)] + [
+        (n, C.c_void_p) for n in ("keys", "steps", "lengths", "total_score", "start", "carry_score", "carry_moves", "finished")]
+
+
+class TfeNtStages(C.Structure):                                           # weight sets by tile stage: beside the struct of a *_staged entry point
     _fields_ = [("n_stages", C.c_int32), ("threshold", C.c_uint8 * 4), ("reserved0", C.c_int64)]
 
 
@@ -290,6 +295,7 @@ SYMBOLS = {
     "pulse_tfe_nt_learn_staged": (C.c_int, [_P, _P, _P]),
     "pulse_tfe_nt_evaluate_staged": (C.c_int, [_P, _P, _I32, _P]),
     "pulse_tfe_nt_search_staged": (C.c_int, [_P, _P, _P]),
+    "pulse_tfe_nt_continue_pick": (C.c_int, [_P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

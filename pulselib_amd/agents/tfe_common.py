@@ -184,7 +184,7 @@ class _TFEGamesGPU:
         import torch
         B = self.n_games if n_games is None else int(n_games)
         o = self._draws(self._eval_struct(), self.eval_board_id0() if board_id0 is None else int(board_id0))
-        o.n_games, o.max_steps, o.epsilon = B, self.max_steps, float(epsilon)
+        o.n_games, o.max_steps, o.epsilon = B, self._eval_cap(), float(epsilon)
         o.summary, o.max_tile_hist = self._eval.data_ptr(), self._eval[len(self.EVAL_SUMMARY):].data_ptr()
         arrays = None
         if per_game:
@@ -192,6 +192,16 @@ class _TFEGamesGPU:
             o.total_score, o.lengths = arrays[0].data_ptr(), arrays[1].data_ptr()
         self._eval_launch(o)
         return arrays
+
+    def _eval_cap(self) -> int:
+        """The cap of an evaluation's games: the attribute `eval_max_steps` where the agent has one that is not None (1..65,535;
+        ValueError otherwise), else the agent's max_steps.  The evaluation launches hold no per-move buffers: any cap is free."""
+        cap = getattr(self, "eval_max_steps", None)
+        if cap is None:
+            return self.max_steps
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= int(cap) <= 65535:
+            raise ValueError("eval_max_steps must be None or an int in 1..65535")
+        return int(cap)
 
     def eval_counters(self, clear=False) -> dict:
         """What the evaluation launches since the last clear added up to (eval_summary_on_host; synchronises), or, with clear, nothing:

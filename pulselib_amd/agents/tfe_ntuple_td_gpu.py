@@ -37,7 +37,13 @@ With `stage_tiles` (section 13.9; csrc/tfe_ntuple_staged.hip) the network is S =
 reads -- a recorded move adds to -- the copy of its stage, the number of those tiles its largest tile has reached: multi-stage TD.
 Every launch of a round then goes through the four `pulse_tfe_nt_*_staged` entry points and one apply launch per stage; `add_stage`
 splits a stage in two at a tile, the new one starting as a copy (weight promotion).  On the host the stages travel on `tuples`
-(`with_stages`), so every mirror above reads and adds by stage; `stage_of_keys_on_host` states the stage."""
+(`with_stages`), so every mirror above reads and adds by stage; `stage_of_keys_on_host` states the stage.
+
+With the attribute `continue_games` (section 13.10; csrc/tfe_ntuple_continue.hip) an agent built with a small `max_steps` = K plays K
+moves of every game per round: `learn_batch` ends with `pulse_tfe_nt_continue_pick`, which puts into `start` the board the last move
+of every cut game was made on -- the next round decides that move again under the new weights, so every transition is learnt once --
+keeps the score and moves of the game so far in `carry_score` / `carry_moves` and adds the games that ended, whole, to `finished`.
+`continue_pick_on_host` states the pick on the host; `eval_max_steps` gives the evaluations a cap of their own."""
 from __future__ import annotations
 
 import ctypes as C
@@ -382,6 +388,68 @@ def restart_summary_on_host(words, start) -> dict:
     return dict(picked=picked, mean_depth=total / picked if picked else 0.0, started=int(np.count_nonzero(start)))
 
 
+# ------------------------------------------------------------------ games continued across rounds
+FINISHED_SUMMARY = ("games", "moves", "score_sum", "score_sq_sum", "max_score", "continued", "resumed", "tile_capped")     # words 0..7 of `finished`
+
+
+def continue_pick_on_host(keys, steps, lengths, total_score, max_steps, env_seed, board_id0, carry_score, carry_moves):
+    """pulse_tfe_nt_continue_pick on the host.  keys uint64[T, B], steps uint8[T, B], lengths int[B] and total_score int64[B] of a
+    recorded round (T at least the longest game), env_seed and board_id0 those it was recorded under, carry_score int64[B] and
+    carry_moves int[B] as the launch finds them (not written).  L = min(lengths[g], max_steps), b = steps[L - 1, g], A = keys[L - 1, g].
+    A game is CUT where b has no terminal bit, A holds no nibble 15 and L == max_steps: start[g] = spawn_on_host of keys[L - 2, g] under
+    words x and y of Philox(env_seed, board_id0 + g, L - 1), the board move L - 1 was made on; carry_score[g] += total_score[g] - sc, sc
+    the merge score of that board's move b & 3 (moves_on_host), carry_moves[g] += L - 1.  AssertionError if that move does not give A:
+    the device does not check it.  Every other game is FINISHED: its score carry_score[g] + total_score[g], its length carry_moves[g] +
+    L and the largest tile of A with the spawn of Philox(env_seed, board_id0 + g, L) go into the 24 words (FINISHED_SUMMARY, then the
+    histogram), and start[g] and both carries are 0.  Returns (start uint64[B], carry_score int64[B], carry_moves int32[B], the 24 words
+    this launch adds as Python ints; word 4 is a maximum)."""
+    keys, steps = np.asarray(keys, dtype=_U64), np.asarray(steps, dtype=np.uint8)
+    max_steps = int(max_steps)
+    if not 2 <= max_steps <= 65535:
+        raise ValueError("max_steps must be in 2..65535")
+    L = np.minimum(np.asarray(lengths, dtype=np.int64).reshape(-1), max_steps)
+    assert (L >= 1).all(), "a recorded game has a move"
+    B = len(L)
+    g = np.arange(B)
+    total = np.asarray(total_score, dtype=np.int64).reshape(-1)
+    score, moves = np.array(carry_score, dtype=np.int64).reshape(-1), np.array(carry_moves, dtype=np.int64).reshape(-1)
+    b, A = steps[L - 1, g], keys[L - 1, g]
+    capped = (_nibbles(A) == 15).any(axis=1)
+    cut = (b >> 7 == 0) & ~capped & (L == max_steps)
+    ids = np.array([(int(board_id0) + int(i)) & 0xFFFFFFFFFFFFFFFF for i in g], dtype=_U64)
+    draws = philox_many_on_host(int(env_seed), ids, np.where(cut, L - 1, L).astype(_U64))
+    start, words = np.zeros(B, dtype=_U64), [0] * (len(FINISHED_SUMMARY) + EVAL_BINS)
+    c, f = np.flatnonzero(cut), np.flatnonzero(~cut)
+    if len(c):
+        start[c] = spawn_on_host(keys[L[c] - 2, c], draws[c, 0], draws[c, 1])
+        after, scores = moves_on_host(start[c])
+        a = (b[c] & 3).astype(np.int64)
+        assert np.array_equal(after[np.arange(len(c)), a], A[c]), "the cut move made again does not give the recorded afterstate"
+        score[c] += total[c] - scores[np.arange(len(c)), a]
+        moves[c] += L[c] - 1
+        words[5] = len(c)
+    if len(f):
+        s = (score[f] + total[f]).astype(object)                           # (Python ints: the sum of squares is exact)
+        top = _nibbles(spawn_on_host(A[f], draws[f, 0], draws[f, 1])).max(axis=1)
+        words[:5] = [len(f), int((moves[f] + L[f]).sum()), int(s.sum()), int((s * s).sum()), int(s.max())]
+        words[6], words[7] = int((moves[f] > 0).sum()), int(capped[f].sum())
+        words[len(FINISHED_SUMMARY):] = np.bincount(top, minlength=EVAL_BINS).tolist()
+        score[f], moves[f] = 0, 0
+    return start, score, moves.astype(np.int32), words
+
+
+def add_finished_on_host(words, more) -> list:
+    """`finished` after a launch that adds `more` to `words`: every word a sum but word 4, the largest score."""
+    return [max(int(x), int(y)) if i == 4 else int(x) + int(y) for i, (x, y) in enumerate(zip(words, more))]
+
+
+def finished_summary_on_host(words) -> dict:
+    """`finished`'s 8 + 16 words as a dict (tfe_common.eval_summary_on_host with FINISHED_SUMMARY): the whole games that ended since the
+    words were zeroed -- mean_score, std_score and mean_length are theirs -- `continued` the games the pick launches took on into
+    another round, `resumed` the finished games that had been continued at least once."""
+    return _eval_summary_on_host(words, FINISHED_SUMMARY)
+
+
 # ------------------------------------------------------------------ the learner and the apply launch
 def _add_moves_on_host(keys, steps, lengths, deltas, tuples, symmetric, acc, acc_abs=None) -> dict:
     """The learners' tail.  A game has L = min(lengths[g], T) moves; its last is skipped without its terminal bit; any other move (t, g),
@@ -661,8 +729,21 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
     `acc` and the TC state then hold S * W words, stage s in [s * W, (s + 1) * W) with W = `n_weights`; rollout, learn, evaluate,
     evaluate_search and search go through the `pulse_tfe_nt_*_staged` entry points under the agent's `lam`, `tc`, `rollout_layers` 0 or
     1, `backed_targets` and `restart_fraction`, and apply is one launch per stage; two chance layers are refused (ValueError, before
-    anything is touched).  `tuples` carries the stage tiles (with_stages), so the host mirrors handed `agent.tuples` read by stage."""
+    anything is touched).  `tuples` carries the stage tiles (with_stages), so the host mirrors handed `agent.tuples` read by stage.
+    `continue_games` (an attribute, False by default: the agent as it was; section 13.10): on an agent built with a small `max_steps`
+    = K >= 2, a game a round cuts at K moves is taken up again by the next round instead of being reset: `learn_batch` ends with the
+    continue pick, a fourth launch, which fills `start` with the board the cut move was made on, and `rollout` plays from `start`
+    (rollout_from_launch, or the staged launch) at `rollout_layers` 0 or 1 with `backed_targets`, `lam`, `tc` and `stage_tiles` as
+    they are; not with `restart_fraction` > 0 nor two layers (ValueError before anything is touched).  `carry_score` int64[n_games]
+    and `carry_moves` int32[n_games] hold the games so far, `finished` int64[24] the whole games that ended (`finished_summary`);
+    the three are allocated by the first continue launch.  `total_score`, `lengths` and stats() stay per segment.  A lambda-walk ends
+    at the segment's cut.  No checkpoint holds any of it: a loaded agent's games begin at their resets.  `eval_max_steps` (an
+    attribute, None by default: the agent's `max_steps`): the cap of evaluate_launch's games, so of evaluate and evaluate_search, any
+    value in 1..65,535 -- the evaluation launches hold no per-move buffers."""
     STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
+    continue_games = False                                                 # set on the agent; checked at the launch
+    eval_max_steps = None                                                  # set on the agent; None: the agent's max_steps
+    carry_score = carry_moves = finished = None                            # allocated by the first continue launch
     restart_fraction = 0.0                                                 # set on the agent; checked at the launch (check_restart_fraction)
     restart_min_length = 64                                                # set on the agent; checked by the pick launch
     start = restart_stats = None                                           # allocated by the first restart launch
@@ -803,9 +884,20 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
         must be 1 or 2 (ValueError otherwise, before anything is touched) and the launch is rollout_backed_launch.  With
         `restart_fraction` > 0 the depth must be 0 or 1 (ValueError otherwise, before anything is touched), and once a pick has filled
         `start` the launch is rollout_from_launch at that depth, with the backed values if `backed_targets`.  With `stage_tiles` the
-        depth must be 0 or 1 and the launch is rollout_staged_launch, from `start` (zeroed here while restart_fraction is 0)."""
+        depth must be 0 or 1 and the launch is rollout_staged_launch, from `start` (zeroed here while restart_fraction is 0 and
+        `continue_games` is off).  With `continue_games` the depth must be 0 or 1, restart_fraction 0 and max_steps at least 2
+        (ValueError otherwise, before anything is touched), and once a continue pick has filled `start` the launch is
+        rollout_from_launch at that depth, with the backed values if `backed_targets`."""
         layers = check_rollout_layers(self.rollout_layers if layers is None else layers)
         restart = check_restart_fraction(self.restart_fraction) > 0.0
+        if self.continue_games:
+            if restart:
+                raise ValueError("continue_games does not go with restart_fraction > 0: both fill start for the next round")
+            if layers == 2:
+                raise ValueError("continue_games needs rollout_layers in (0, 1): the roll-out from start is not built two layers deep")
+            if self.max_steps < 2:
+                raise ValueError("continue_games needs max_steps >= 2: a segment of K moves gives K - 1 learnt ones")
+            restart = True                                                  # from here on the launches are the restarted rounds': from `start`
         self._refuse_two_layers(layers, "rollout_layers")
         if restart and layers == 2:
             raise ValueError("restart_fraction > 0 needs rollout_layers in (0, 1): the restarted roll-out is not built two layers deep")
@@ -832,6 +924,40 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
         if self.start is None:
             self.start = torch.zeros(self.n_games, dtype=torch.int64, device=self.device)             # (uint64 words)
             self.restart_stats = torch.zeros(2, dtype=torch.int64, device=self.device)
+
+    # ------------------------------------------------------------------ games continued across rounds
+    def _continue_state(self):
+        """`carry_score`, `carry_moves` and `finished`, zeroed, where the agent has none yet; `start` too (_restart_state)."""
+        import torch
+        self._restart_state()
+        if self.carry_score is None:
+            self.carry_score = torch.zeros(self.n_games, dtype=torch.int64, device=self.device)
+            self.carry_moves = torch.zeros(self.n_games, dtype=torch.int32, device=self.device)
+            self.finished = torch.zeros(len(FINISHED_SUMMARY) + EVAL_BINS, dtype=torch.int64, device=self.device)
+
+    def continue_pick_launch(self):
+        """pulse_tfe_nt_continue_pick alone on the games last recorded (under this round's seed and boards), whatever the agent's
+        `continue_games`: per game cut at `max_steps`, `start` becomes the board its last move was made on and the carries take the
+        segment without that move; every other game is added whole to `finished`, and its `start` and carries become 0.  ValueError
+        if max_steps < 2."""
+        if self.max_steps < 2:
+            raise ValueError("continue_games needs max_steps >= 2: a segment of K moves gives K - 1 learnt ones")
+        self._continue_state()
+        o = _native.TfeNtContinuePick()
+        o.n_games, o.max_steps, o.env_seed, o.board_id0 = self.n_games, self.max_steps, self.env_seed, self.round_board_id0()
+        o.keys, o.steps, o.lengths, o.total_score = self.keys.data_ptr(), self.steps.data_ptr(), self.lengths.data_ptr(), self.total_score.data_ptr()
+        o.start, o.carry_score, o.carry_moves, o.finished = self.start.data_ptr(), self.carry_score.data_ptr(), self.carry_moves.data_ptr(), self.finished.data_ptr()
+        return self._launch("pulse_tfe_nt_continue_pick", o)
+
+    def finished_summary(self, clear=True) -> dict:
+        """finished_summary_on_host of `finished` (synchronises): the whole games that ended since the words were last zeroed, the
+        games continued by the pick launches since and the finished games that had been continued.  clear: `finished` is zeroed."""
+        if self.finished is None:
+            raise ValueError("no continue launch has run: the agent holds no finished")
+        out = finished_summary_on_host(self.finished.cpu().tolist())
+        if clear:
+            self.finished.zero_()
+        return out
 
     def _per_move(self, name):
         """The agent's `deltas` or `backed` (`name`): float64 in the shape of `values`, allocated zeroed where the agent has none yet."""
@@ -980,7 +1106,9 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
         self.rollout()
         self.learn()
         self.apply()
-        if self.restart_fraction > 0.0:                                    # the next round's start boards, from this round's records
+        if self.continue_games:                                             # the cut games' boards for the next round, the ended games into `finished`
+            self.continue_pick_launch()
+        elif self.restart_fraction > 0.0:                                  # the next round's start boards, from this round's records
             self.restart_pick_launch()
         self.round += 1
         return self
@@ -1101,8 +1229,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
 
     def save(self, path):
         """The non-zero weights and what a continued run needs as an .npz (write_checkpoint); with tc, E and A too.  `rollout_layers`,
-        `backed_targets`, `restart_fraction` and `restart_min_length` are not saved: they say how rounds are played and learnt, not what
-        the network is."""
+        `backed_targets`, `restart_fraction`, `restart_min_length`, `continue_games` and `eval_max_steps` are not saved: they say how
+        rounds are played, learnt and evaluated, not what the network is; nor are `start` and the carries of continued games."""
         write_checkpoint(path, self.weights(), self.tuples, symmetric=int(self.symmetric), gamma=self.gamma, epsilon=self.epsilon, alpha=self.alpha,
                          max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games, lam=self.lam,
                          tc=self.coherence() if self.tc else None, stage_tiles=self.stage_tiles)
@@ -1111,7 +1239,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
     def load(cls, path, device, n_games=None):
         """The agent save() wrote: weights, round, seeds, lam, tc and with it E and A restored.  With the saved n_games it continues the run the saved agent would
         have continued (another n_games plays other boards: round r starts at board_id0 + r * n_games).  `rollout_layers` is 0, whatever the saved
-        agent played under, `backed_targets` False and `restart_fraction` 0.0 with no `start`: set them again to continue such rounds."""
+        agent played under, `backed_targets` False, `restart_fraction` 0.0 and `continue_games` False with no `start` and no carries:
+        set them again to continue such rounds; a loaded agent's games begin at their resets."""
         import torch
         f = read_checkpoint(path)
         agent = cls(device, f["n_games"] if n_games is None else n_games, tuples=f["tuples"], symmetric=f["symmetric"], gamma=f["gamma"],
@@ -1130,7 +1259,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
         self.weights_dev.zero_()
         self.acc.zero_()
         self.counters.zero_()
-        for t in (self.acc_abs, self.E, self.A, self.tc_stats, self.start, self.restart_stats):
+        for t in (self.acc_abs, self.E, self.A, self.tc_stats, self.start, self.restart_stats, self.carry_score, self.carry_moves, self.finished):
             if t is not None:
                 t.zero_()
         self.round = 0

@@ -20,7 +20,12 @@ were restarted and from what mean depth -- a restarted game's score counts from 
 game's; the evaluations stay from reset.  Not saved either: a resumed run's first round starts at the reset boards.  `--stages 512,2048`
 (section 13.9) keeps one weight set per tile stage -- a board reads and learns in the set of the largest of those tiles it has reached --
 and `--add-stage ROUND:TILE` splits a stage at TILE before round ROUND, the new set starting as a copy (weight promotion); not with
-`--train-layers 2` or `--search --layers 2`; the file holds the stages, and `--resume` takes them from it."""
+`--train-layers 2` or `--search --layers 2`; the file holds the stages, and `--resume` takes them from it.  `--continue-games` with
+`--max-steps K` (K >= 2, small: 64; section 13.10; not with `--restart` nor `--train-layers 2`) plays K moves of every game per round
+and takes the cut games up again in the next round under the new weights, so the weights move every K moves of a game instead of once
+per generation of games; the evaluations are capped at 4,096 moves, not at K, and every round's line says how many whole games
+finished since the last line, their mean score and length, and how many games the round's pick continued: the training curve of
+complete games.  Not saved either: a resumed run's games begin at their resets."""
 from __future__ import annotations
 
 import argparse
@@ -29,6 +34,8 @@ import time
 import torch
 
 from ..agents import NTupleTDAfterstateTFEGPU
+
+CONTINUE_EVAL_MAX_STEPS = 4096                                             # --continue-games: the evaluations' cap (max_steps is the segment's length)
 
 
 def _promotions(add_stage, first, rounds) -> dict:
@@ -45,9 +52,16 @@ def _promotions(add_stage, first, rounds) -> dict:
 
 
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
-        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False, restart=0.0, restart_min_length=64, stages=(), add_stage=()):
+        resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False, restart=0.0, restart_min_length=64, stages=(), add_stage=(),
+        continue_games=False):
     if (stages or add_stage) and (train_layers == 2 or (search and layers == 2)):
         raise ValueError("--stages / --add-stage do not go with two chance layers: the staged launches are one ply or one chance layer deep")
+    if continue_games and restart:
+        raise ValueError("--continue-games does not go with --restart: both choose the boards the next round's games begin on")
+    if continue_games and train_layers == 2:
+        raise ValueError("--continue-games does not go with --train-layers 2: the roll-out from given boards is one ply or one chance layer deep")
+    if continue_games and max_steps < 2:
+        raise ValueError("--continue-games needs --max-steps 2 or more: a segment of K moves gives K - 1 learnt ones")
     if restart and train_layers == 2:
         raise ValueError("--restart does not go with --train-layers 2: the restarted roll-out is one ply or one chance layer deep")
     if backed and train_layers not in (1, 2):
@@ -65,11 +79,14 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
     promotions = _promotions(add_stage, agent.round, rounds)
     agent.rollout_layers, agent.backed_targets = train_layers, bool(backed)  # (no checkpoint holds them: given again on --resume)
     agent.restart_fraction, agent.restart_min_length = float(restart), int(restart_min_length)
+    if continue_games:                                                      # (not saved: given again on --resume; the games begin at their resets)
+        agent.continue_games, agent.eval_max_steps = True, CONTINUE_EVAL_MAX_STEPS
     out(f"{agent.n_games} games per round from round {agent.round}: alpha {agent.alpha}, epsilon {agent.epsilon}, gamma {agent.gamma}, "
         f"lambda {agent.lam}, tc {agent.tc}, max_steps {agent.max_steps}, seed {agent.seed}, roll-out under {agent.rollout_layers} chance layers of search"
         f"{', learning towards the search-backed values' if agent.backed_targets else ''}"
         f"{f', games restarted at {agent.restart_fraction} of games of {agent.restart_min_length} moves or more' if agent.restart_fraction else ''}"
-        f"{f', weight sets by stage from tiles {agent.stage_tiles}' if agent.stage_tiles else ''}")
+        f"{f', weight sets by stage from tiles {agent.stage_tiles}' if agent.stage_tiles else ''}"
+        f"{f', games continued across rounds in segments of {agent.max_steps} moves, evaluations capped at {agent.eval_max_steps}' if agent.continue_games else ''}")
     first, moves_before, t0 = agent.round, agent.stats()["moves"], time.perf_counter()
 
     def under_search():
@@ -98,8 +115,12 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
             st, now = agent.stats(), time.perf_counter()
             again = f"restarted {began['picked']} games from mean depth {began['mean_depth']:.1f}, " if agent.restart_fraction else ""
             rho = f", mean rho {agent.tc_summary()['mean_rho']:.4f}" if agent.tc else ""       # (of the applies since the last line)
+            if agent.continue_games:                                        # (the whole games that ended since the last line; synchronises)
+                done = agent.finished_summary()
+                again = (f"whole games finished {done['games']}: Avg final score {done['mean_score']:.1f}, Avg length {done['mean_length']:.1f}, "
+                         f"games continued {done['continued']}; per segment: ")
             out(f"Round {r}: {line}; "
-                f"training: Avg final score {agent.total_score.double().mean().item():.1f}, Avg length {agent.lengths.double().mean().item():.1f}, {again}moves/sec {(st['moves'] - moves_before) / (now - t0):.0f}, "
+                f"training: {again if agent.continue_games else ''}Avg final score {agent.total_score.double().mean().item():.1f}, Avg length {agent.lengths.double().mean().item():.1f}, {'' if agent.continue_games else again}moves/sec {(st['moves'] - moves_before) / (now - t0):.0f}, "
                 f"skipped {st['skipped']}, clamped {st['clamped']}{rho}{under_search()}")
             moves_before, t0 = st["moves"], time.perf_counter()
     if save:
@@ -132,6 +153,9 @@ def main(argv=None):
     ap.add_argument("--restart", type=float, default=0.0, metavar="F",
                     help="start every game on the board its predecessor stood on at this fraction of its length (0: off; not with --train-layers 2); not saved")
     ap.add_argument("--restart-min-length", type=int, default=64, metavar="N", help="with --restart: only games of at least N moves are restarted from")
+    ap.add_argument("--continue-games", action="store_true",
+                    help="with a small --max-steps K: a game cut after K moves is taken up again by the next round under the new weights "
+                         "(not with --restart nor --train-layers 2); evaluations are capped at 4096 moves; not saved")
     ap.add_argument("--stages", default="", metavar="TILES", help="weight sets by tile stage: up to three increasing tiles, e.g. 512,2048; --resume takes them from the file")
     ap.add_argument("--add-stage", action="append", default=[], metavar="ROUND:TILE", help="split a stage at TILE before round ROUND (weight promotion); repeatable")
     args = ap.parse_args(argv)
@@ -148,11 +172,18 @@ def main(argv=None):
         ap.error("--stages / --add-stage do not go with two chance layers: the staged launches are one ply or one chance layer deep")
     if args.restart and args.train_layers == 2:
         ap.error("--restart does not go with --train-layers 2: the restarted roll-out is one ply or one chance layer deep")
+    if args.continue_games and args.restart:
+        ap.error("--continue-games does not go with --restart: both choose the boards the next round's games begin on")
+    if args.continue_games and args.train_layers == 2:
+        ap.error("--continue-games does not go with --train-layers 2: the roll-out from given boards is one ply or one chance layer deep")
+    if args.continue_games and args.max_steps < 2:
+        ap.error("--continue-games needs --max-steps 2 or more: a segment of K moves gives K - 1 learnt ones")
     if args.backed and args.train_layers not in (1, 2):
         ap.error("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
                 args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers, backed=args.backed,
-                restart=args.restart, restart_min_length=args.restart_min_length, stages=stages, add_stage=add_stage)
+                restart=args.restart, restart_min_length=args.restart_min_length, stages=stages, add_stage=add_stage,
+                continue_games=args.continue_games)
     st = agent.stats()
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
           f"{int((agent.weights_dev != 0).sum().item())} of {agent.total_weights} weights are not zero")

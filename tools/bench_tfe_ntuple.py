@@ -56,6 +56,13 @@ spread.  --stage-regime: instead of everything above, ONE line, {"stage_regime":
 ply deep, and under one-layer search with backed targets at lambda 0.5 for the unstaged agent, for --stages from round 0 and for one
 stage added half-way by add_stage; the evaluations' largest-tile histograms and paired differences.  Without --stages the two tiles are
 chosen from the baseline's histogram: the largest tile at least half its evaluation games reached, and a quarter of it.
+--continue-games: instead of everything above, per B ONE line, {"continue_pick": ...}: an agent with
+max_steps = --continue-max-steps (64) and continue_games plays --continue-rounds (16) rounds and one more recording launch; on those
+records the continue pick (pulse_tfe_nt_continue_pick) and the restart pick (pulse_tfe_nt_restart_pick, fraction 0.5) alternate, each
+between its own pair of HIP events, --warmup untimed turns and then --repeats; the games continued and finished per launch beside them.
+--continue-regime: instead, ONE line, {"continue_regime": ...}: section 13.5's regime one ply deep (--regime-rounds whole-game rounds)
+and a continue_games agent of --continue-max-steps moves a segment trained until it has learnt at least as many moves: the rounds, their
+summed launch time and the wall time, the whole games that finished, and both evaluations (capped at --max-steps) paired by board.
 max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes, 25 with deltas, 33 with backed).  Lines are also
 appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
 import argparse
@@ -291,6 +298,75 @@ def restart_regime_line(torch, dev, games, rounds, eval_games, max_steps, fracti
             d = (ev[name + "_restart"][k]["total_score"] - ev[name][k]["total_score"]).astype(np.float64)
             out[f"{k}_eval_{name}_restart_minus_{name}"] = {"mean": d.mean(), "se": d.std(ddof=1) / d.size ** .5}
     return {"restart_regime": out}
+
+
+def continue_pick_line(torch, dev, games, segment, rounds, warmup, repeats):
+    """the continue pick beside the restart pick on the records of an agent that has played `rounds` continued rounds of `segment` moves:
+    the two launches alternate, each between its own pair of HIP events"""
+    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
+    agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=segment, seed=0)
+    agent.continue_games = True
+    for _ in range(rounds):
+        agent.learn_batch()
+    agent.rollout()                                                         # the records the picks read: the next round's, under this round's ids
+    agent.finished_summary()
+    seconds = _alternate(agent, torch, (("restart_pick", lambda: agent.restart_pick_launch(0.5, 2)), ("continue_pick", agent.continue_pick_launch)),
+                         warmup, repeats)
+    done, turns = agent.finished_summary(), warmup + repeats
+    restart = agent.restart_summary()
+    old, new = _spread(seconds["restart_pick"]), _spread(seconds["continue_pick"])
+    line = {"games": games, "max_steps": segment, "continued_rounds": rounds, "warmup": warmup, "repeats": repeats, "restart_pick_s": old, "continue_pick_s": new,
+            "ratio": new["median"] / old["median"], "continued": done["continued"] // turns, "finished": done["games"] // turns,
+            "restart_picked": restart["picked"] // turns, "bytes_read": (4 + 1 + 8 + 8 + 8 + 4) * games + 8 * (done["continued"] // turns),
+            "bytes_written": (8 + 8 + 4) * games}
+    del agent
+    torch.cuda.empty_cache()
+    return {"continue_pick": line}
+
+
+def continue_regime_line(torch, dev, games, rounds, eval_games, max_steps, segment):
+    """section 13.5's regime one ply deep -- `rounds` whole-game rounds -- beside a continue_games agent with max_steps = `segment`
+    trained until it has learnt at least as many moves; the evaluations are from reset, capped at `max_steps`, and paired by board"""
+    import time
+    import numpy as np
+    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
+    out, ev = {"games": games, "rounds": rounds, "eval_games": eval_games, "seed": 0, "max_steps": max_steps, "segment": segment}, {}
+
+    def timed_batch(agent):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        e[0].record()
+        agent.learn_batch()
+        e[1].record()
+        e[1].synchronize()
+        return e[0].elapsed_time(e[1]) * 1e-3
+
+    def row(agent, seconds, wall, more):
+        name = "continued" if agent.continue_games else "whole_games"
+        ev[name] = {"one_ply": agent.evaluate(n_games=eval_games, per_game=True), "search": agent.evaluate_search(n_games=eval_games, per_game=True)}
+        st = agent.stats()
+        out[name] = {"max_steps": agent.max_steps, "rounds": agent.round, "round_seconds_sum": sum(seconds), "round_seconds": _spread(seconds),
+                     "wall_seconds": wall, "stats": st, "moves_learnt": st["learnt"], **more,
+                     **{k: {"mean": e["mean_score"], "se": e["std_score"] / e["games"] ** .5, "mean_length": e["mean_length"], "cut": e["truncated"]}
+                        for k, e in ev[name].items()}}
+        return st["learnt"]
+
+    agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=max_steps, seed=0)
+    t0 = time.perf_counter()
+    seconds = [timed_batch(agent) for _ in range(rounds)]
+    target = row(agent, seconds, time.perf_counter() - t0, {})
+    del agent
+    torch.cuda.empty_cache()
+    agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=segment, seed=0)
+    agent.continue_games, agent.eval_max_steps = True, max_steps
+    seconds, t0 = [], time.perf_counter()
+    while agent.stats()["learnt"] < target:                                 # (synchronises once a round: inside the wall time, outside the events)
+        seconds.append(timed_batch(agent))
+    wall, done = time.perf_counter() - t0, agent.finished_summary()
+    row(agent, seconds, wall, {"finished": {k: done[k] for k in ("games", "mean_score", "mean_length", "continued", "resumed", "tile_capped")}})
+    for k in ("one_ply", "search"):
+        d = (ev["continued"][k]["total_score"] - ev["whole_games"][k]["total_score"]).astype(np.float64)
+        out[f"{k}_eval_continued_minus_whole_games"] = {"mean": d.mean(), "se": d.std(ddof=1) / d.size ** .5}
+    return {"continue_regime": out}
 
 
 def staged_lines(agent, torch, dev, stage_tiles, lam, warmup, repeats):
@@ -549,6 +625,10 @@ def main(argv=None):
     ap.add_argument("--restart-regime", action="store_true", help="one line instead: twelve rounds and paired evaluations with and without restart (DESIGN.md section 13.7)")
     ap.add_argument("--stages", default="", metavar="TILES", help="one more line per B: every staged launch beside its unstaged sibling, stages at these tiles (512,2048), equal slices")
     ap.add_argument("--stage-regime", action="store_true", help="one line instead: twelve rounds and paired evaluations without stages, with --stages from round 0 and with one added half-way (DESIGN.md section 13.9)")
+    ap.add_argument("--continue-games", action="store_true", help="one line per B instead: the continue pick launch beside the restart pick (DESIGN.md section 13.10)")
+    ap.add_argument("--continue-regime", action="store_true", help="one line instead: twelve whole-game rounds beside continued rounds of --continue-max-steps moves to the same moves learnt")
+    ap.add_argument("--continue-max-steps", type=int, default=64, metavar="K", help="with --continue-games / --continue-regime: the segment length")
+    ap.add_argument("--continue-rounds", type=int, default=16, help="with --continue-games: the continued rounds played before the picks are timed")
     ap.add_argument("--regime-rounds", type=int, default=12)
     ap.add_argument("--regime-eval-games", type=int, default=2048)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
@@ -581,6 +661,14 @@ def main(argv=None):
         print(json.dumps(line), flush=True)
         with open(args.out, "a") as fh:
             fh.write(json.dumps(line) + "\n")
+        return
+    if args.continue_regime or args.continue_games:
+        lines = [continue_regime_line(torch, dev, args.games[0], args.regime_rounds, args.regime_eval_games, args.max_steps, args.continue_max_steps)] \
+            if args.continue_regime else [continue_pick_line(torch, dev, g, args.continue_max_steps, args.continue_rounds, args.warmup, args.repeats) for g in args.games]
+        for line in lines:
+            print(json.dumps(line), flush=True)
+            with open(args.out, "a") as fh:
+                fh.write(json.dumps(line) + "\n")
         return
     for games in args.games:
         per_move = 33 if args.backed or args.restart else 17 if args.lam is None else 25
