@@ -949,6 +949,23 @@ int pulse_tfe_nt_evaluate_search(const PulseTfeNtEval* o, void* stream);
 int pulse_tfe_nt_search_deep(const PulseTfeNtSearch* o, int32_t layers, void* stream);
 int pulse_tfe_nt_evaluate_search_deep(const PulseTfeNtEval* o, int32_t layers, void* stream);
 
+/* ---- ... at a depth the board chooses, per move.  The two structs above, with the threshold beside them: `deep_empty_max` = E in
+ * 0..16.  For a board B to decide, n = the number of empty cells of B, the board the move is made from (not its afterstates):
+ *   n <= E:    q(B) is the four q of the two-layer search (pulse_tfe_nt_search_deep at layers = 2);
+ *   otherwise: q(B) is the four q of the one-layer search (pulse_tfe_nt_search), bit for bit.
+ * Nothing else changes: the candidates, the greedy scan with its tie coins Philox(tie_seed, key of B, round), the epsilon branch,
+ * the 32,768 cut, the counters.  E = 16 is the two-layer search on every board; E = 0 searches two layers on full boards only.
+ * One board or game per workgroup of 256 lanes; n is the same in every lane that plays the board, so the choice is the workgroup's.
+ * On a shallow move groups 0..3 of 32 lanes search one candidate move each and the four q meet in LDS.
+ *
+ * depth_stats: device int64[2], or NULL: [0] += the moves whose q came from two layers, [1] += those from one layer; every move of
+ * every game counts, the epsilon branch's too (q is formed before the branch); added once per game, at its end.
+ *
+ * PULSE_EINVAL, before anything is launched: what pulse_tfe_nt_search_deep / pulse_tfe_nt_evaluate_search_deep refuse of their
+ * structs, under these names; `deep_empty_max` outside 0..16 ("deep_empty_max must be in 0..16"); depth_stats not 8-byte aligned. */
+int pulse_tfe_nt_search_adaptive(const PulseTfeNtSearch* o, int32_t deep_empty_max, void* stream);
+int pulse_tfe_nt_evaluate_search_adaptive(const PulseTfeNtEval* o, int32_t deep_empty_max, int64_t* depth_stats, void* stream);
+
 /* ---- ... and in the training roll-out: pulse_tfe_nt_rollout's games under the search policy.  The roll-out's struct, with the depth
  * beside it.  Everything is pulse_tfe_nt_rollout's -- the boards board_id0 + g, the three Philox streams, the epsilon branch and its
  * uniform action, the cap at a 32,768 tile, max_steps, the counters stats[0] (moves) and stats[3] (games cut), the per-game arrays

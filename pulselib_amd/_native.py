@@ -286,6 +286,8 @@ SYMBOLS = {
     "pulse_tfe_nt_evaluate_search": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_search_deep": (C.c_int, [_P, _I32, _P]),
     "pulse_tfe_nt_evaluate_search_deep": (C.c_int, [_P, _I32, _P]),
+    "pulse_tfe_nt_search_adaptive": (C.c_int, [_P, _I32, _P]),
+    "pulse_tfe_nt_evaluate_search_adaptive": (C.c_int, [_P, _I32, _P, _P]),
     "pulse_tfe_nt_rollout_search": (C.c_int, [_P, _I32, _P]),
     "pulse_tfe_nt_rollout_backed": (C.c_int, [_P, _I32, _P, _P]),
     "pulse_tfe_nt_learn_backed": (C.c_int, [_P, _P]),

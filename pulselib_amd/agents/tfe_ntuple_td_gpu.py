@@ -10,7 +10,8 @@ recorded move and adds the temporal difference reward' + gamma * V' - V (0 - V a
 {sum, cnt} of every weight the afterstate reads; `pulse_tfe_nt_apply` moves every visited weight by alpha / F of the MEAN of its
 adds and zeroes the accumulators.  `pulse_tfe_nt_evaluate` plays games without a trajectory and reduces the scores in the launch; `pulse_tfe_nt_search` and
 `pulse_tfe_nt_evaluate_search` play under expectimax search one chance layer deep (section 13.1), 32 lanes per board; with `layers=2`
-`pulse_tfe_nt_search_deep` and `pulse_tfe_nt_evaluate_search_deep` search two (section 13.4), 256 lanes per board; with the attribute `rollout_layers` = 1 or 2 the
+`pulse_tfe_nt_search_deep` and `pulse_tfe_nt_evaluate_search_deep` search two (section 13.4), 256 lanes per board; with `layers=2, deep_empty_max=E`
+`pulse_tfe_nt_search_adaptive` and `pulse_tfe_nt_evaluate_search_adaptive` search two on the boards with at most E empty cells and one on the others (section 13.11); with the attribute `rollout_layers` = 1 or 2 the
 round's games themselves are played under that search, `pulse_tfe_nt_rollout_search` (section 13.5), and recorded alike.  With `lam > 0`
 the learn launch is `pulse_tfe_nt_learn_lambda` (section 13.2): one lane per game walks the recorded game backwards and leaves the
 lambda-differences D_t = delta_t + gamma * lam * D_{t+1} in `deltas`, and the same one-lane-per-move adds follow with D_t for delta_t.
@@ -338,6 +339,41 @@ def search_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: 
     action = greedy_scan_many_on_host(q, philox_many_on_host(tie_seed, keys, int(round)), cand)
     return dict(q=q, action=action, candidates=(cand << np.arange(4)).sum(axis=1).astype(np.uint8), E=E, terms=terms, after=after,
                 rewards=rewards, backed=search_backed_on_host(q, cand))
+
+
+# ------------------------------------------------------------------ search depth chosen by the board's empty cells
+def check_deep_empty_max(x):
+    """The threshold of the adaptive search: None (no adaptive search: the call is what it was) or an int in 0..16, returned as it is
+    meant.  ValueError otherwise; a bool is no threshold."""
+    if x is None:
+        return None
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) <= 16:
+        raise ValueError("deep_empty_max must be None or an int in 0..16")
+    return int(x)
+
+
+def count_empty_on_host(keys) -> np.ndarray:
+    """int64[N]: the empty cells (nibbles 0) of packed 4 x 4 boards"""
+    return (_nibbles(np.ascontiguousarray(keys, dtype=_U64).reshape(-1)) == 0).sum(axis=1).astype(np.int64)
+
+
+def search_adaptive_nt_on_host(keys, weights, tuples, symmetric, gamma: float, tie_seed: int, round: int, deep_empty_max: int) -> dict:
+    """pulse_tfe_nt_search_adaptive on the host, word for word: a board with at most `deep_empty_max` empty cells gets every row of
+    search_nt_on_host(layers=2), every other board those of search_nt_on_host(layers=1); the boards of a depth are searched in one
+    call.  Returns search_nt_on_host's dict and deep bool[N]: the board was searched two layers deep."""
+    E = check_deep_empty_max(deep_empty_max)
+    if E is None:
+        raise ValueError("deep_empty_max must be None or an int in 0..16")
+    keys = np.ascontiguousarray(keys, dtype=_U64).reshape(-1)
+    deep = count_empty_on_host(keys) <= E
+    out = search_nt_on_host(keys[:0], weights, tuples, symmetric, gamma, tie_seed, round)       # (the rows' shapes and types)
+    out = {k: np.zeros((len(keys),) + v.shape[1:], dtype=v.dtype) for k, v in out.items()}
+    for rows, layers in ((~deep, 1), (deep, 2)):
+        if rows.any():
+            look = search_nt_on_host(keys[rows], weights, tuples, symmetric, gamma, tie_seed, round, layers=layers)
+            for k, v in look.items():
+                out[k][rows] = v
+    return dict(out, deep=deep)
 
 
 # ------------------------------------------------------------------ restarted roll-outs (DESIGN.md section 13.7)
@@ -1125,17 +1161,36 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
             return self._launch("pulse_tfe_nt_evaluate_staged", o, C.byref(self._stages()), self._eval_layers)
         self._launch(self._eval_entry, o, *self._eval_args)
 
-    # ------------------------------------------------------------------ expectimax search (DESIGN.md sections 13.1 and 13.4)
+    # ------------------------------------------------------------------ expectimax search (DESIGN.md sections 13.1, 13.4 and 13.11)
     _eval_entry, _eval_args, _eval_layers = "pulse_tfe_nt_evaluate", (), 0     # the evaluation one ply deep; _under_search sets the three for one call
+    depth_stats = None                                                     # int64[2] on the device, from the first adaptive evaluation: moves two layers deep, one layer deep
 
-    def _under_search(self, layers, call, *args):
+    def _check_depth(self, layers, deep_empty_max):
+        """(layers, deep_empty_max) as ints (deep_empty_max: or None), or the ValueError of what the search refuses: a depth other than 1
+        or 2, a threshold other than None or 0..16, a threshold without two layers, two layers on an agent with stage_tiles"""
+        layers, deep_empty_max = check_layers(layers), check_deep_empty_max(deep_empty_max)
+        if deep_empty_max is not None and layers != 2:
+            raise ValueError("deep_empty_max needs layers = 2: it says where the two-layer search is used; layers = 1 searches no board deeper")
+        self._refuse_two_layers(layers, "layers")
+        return layers, deep_empty_max
+
+    def _depth_words(self):
+        import torch
+        if self.depth_stats is None:
+            self.depth_stats = torch.zeros(2, dtype=torch.int64, device=self.device)
+        return self.depth_stats
+
+    def _under_search(self, layers, call, *args, deep_empty_max=None):
         """call(*args) with the evaluation's entry point set to the search's: at one layer pulse_tfe_nt_evaluate_search, at two
-        pulse_tfe_nt_evaluate_search_deep with the depth beside the struct."""
-        self._refuse_two_layers(check_layers(layers), "layers")
+        pulse_tfe_nt_evaluate_search_deep with the depth beside the struct; with deep_empty_max (and two layers)
+        pulse_tfe_nt_evaluate_search_adaptive with the threshold and the agent's `depth_stats` beside it."""
+        layers, deep_empty_max = self._check_depth(layers, deep_empty_max)
         if layers == 1:
             self._eval_entry = "pulse_tfe_nt_evaluate_search"
-        else:
+        elif deep_empty_max is None:
             self._eval_entry, self._eval_args = "pulse_tfe_nt_evaluate_search_deep", (layers,)
+        else:
+            self._eval_entry, self._eval_args = "pulse_tfe_nt_evaluate_search_adaptive", (deep_empty_max, self._depth_words().data_ptr())
         self._eval_layers = int(layers)
         try:
             return call(*args)
@@ -1151,40 +1206,50 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU, metaclass=_TakesStageTiles):
         o.boards, o.q, o.action, o.candidates = boards.data_ptr(), q.data_ptr(), action.data_ptr(), candidates.data_ptr()
         return o
 
-    def search_launch(self, boards, q, action, candidates, layers=1):
+    def search_launch(self, boards, q, action, candidates, layers=1, deep_empty_max=None):
         """The launch of search() alone on device tensors: boards int64[N] (the keys' words), q float64[N, 4], action int8[N],
-        candidates uint8[N].  layers = 1: pulse_tfe_nt_search; layers = 2: pulse_tfe_nt_search_deep (ValueError for any other)."""
-        layers = check_layers(layers)
-        self._refuse_two_layers(layers, "layers")
+        candidates uint8[N].  layers = 1: pulse_tfe_nt_search; layers = 2: pulse_tfe_nt_search_deep (ValueError for any other); with
+        layers = 2 and deep_empty_max = 0..16: pulse_tfe_nt_search_adaptive, two layers on the boards with at most that many empty
+        cells and one layer on the others."""
+        layers, deep_empty_max = self._check_depth(layers, deep_empty_max)
         o = self._search_struct(boards, q, action, candidates)
         if self.stage_tiles:
             return self._launch("pulse_tfe_nt_search_staged", o, C.byref(self._stages()))
         if layers == 1:
             return self._launch("pulse_tfe_nt_search", o)
+        if deep_empty_max is not None:
+            return self._launch("pulse_tfe_nt_search_adaptive", o, deep_empty_max)
         return self._launch("pulse_tfe_nt_search_deep", o, layers)
 
-    def search(self, keys, layers=1) -> dict:
+    def search(self, keys, layers=1, deep_empty_max=None) -> dict:
         """One launch and one read-back: q float64[N, 4] of the packed boards `keys` under `layers` chance layers of search (1 or 2), the
         greedy action int8[N] (-1: the board is over) and the candidates uint8[N] (bit a: move a changes the board); search_nt_on_host
-        on the device."""
+        on the device, with deep_empty_max search_adaptive_nt_on_host."""
         import torch
-        layers = check_layers(layers)
-        self._refuse_two_layers(layers, "layers")
+        layers, deep_empty_max = self._check_depth(layers, deep_empty_max)
         keys = np.array(keys, dtype=_U64).reshape(-1)                       # (a copy: torch takes no read-only array)
         boards = torch.from_numpy(keys.view(np.int64)).to(self.device)
         q = torch.zeros((len(keys), 4), dtype=torch.float64, device=self.device)
         action, candidates = torch.zeros(len(keys), dtype=torch.int8, device=self.device), torch.zeros(len(keys), dtype=torch.uint8, device=self.device)
-        self.search_launch(boards, q, action, candidates, layers)
+        self.search_launch(boards, q, action, candidates, layers, deep_empty_max)
         return dict(q=q.cpu().numpy(), action=action.cpu().numpy(), candidates=candidates.cpu().numpy())
 
-    def evaluate_search_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False, layers=1):
-        """evaluate_launch() under the search policy of `layers` chance layers (1 or 2)."""
-        return self._under_search(layers, self.evaluate_launch, n_games, epsilon, board_id0, per_game)
+    def evaluate_search_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False, layers=1, deep_empty_max=None):
+        """evaluate_launch() under the search policy of `layers` chance layers (1 or 2); with layers = 2 and deep_empty_max = 0..16 under
+        the adaptive search, which also ADDS the moves at each depth to `depth_stats` (int64[2]: two layers, one layer)."""
+        return self._under_search(layers, self.evaluate_launch, n_games, epsilon, board_id0, per_game, deep_empty_max=deep_empty_max)
 
-    def evaluate_search(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False, layers=1) -> dict:
+    def evaluate_search(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False, layers=1, deep_empty_max=None) -> dict:
         """evaluate() under the search policy of `layers` chance layers (1 or 2): the same default boards, so the policies are paired on
-        the spawns each game starts from."""
-        return self._under_search(layers, self.evaluate, n_games, epsilon, board_id0, per_game)
+        the spawns each game starts from.  With layers = 2 and deep_empty_max = 0..16 the search is two layers deep on the boards with at
+        most that many empty cells and one layer deep on the others (section 13.11), and the dict also has moves_deep / moves_shallow."""
+        layers, deep_empty_max = self._check_depth(layers, deep_empty_max)
+        if deep_empty_max is not None:
+            self._depth_words().zero_()
+        out = self._under_search(layers, self.evaluate, n_games, epsilon, board_id0, per_game, deep_empty_max=deep_empty_max)
+        if deep_empty_max is not None:
+            out["moves_deep"], out["moves_shallow"] = self.depth_stats.cpu().tolist()
+        return out
 
     # ------------------------------------------------------------------ read-back (the only syncs) and the checkpoint
     def weights(self) -> np.ndarray:

@@ -1,8 +1,9 @@
 // tfe_ntuple_search_device.h -- what the units of the n-tuple network's play share (tfe_ntuple.hip: one ply; tfe_ntuple_search.hip: one
-// chance layer; tfe_ntuple_search_deep.hip: two, section 13.4; tfe_ntuple_search_rollout.hip, _backed.hip,
+// chance layer; tfe_ntuple_search_deep.hip: two, section 13.4; tfe_ntuple_search_adaptive.hip: one or two by
+// the board's empty cells, section 13.11; tfe_ntuple_search_rollout.hip, _backed.hip,
 // _restart.hip and _staged.hip: the recording games, sections 13.5 to 13.9): the group of 32 lanes, the tile odds, the board
-// launch's refusals (check_search), the chance layer itself (search_q), the two-layer deal over a workgroup (search_q2 with
-// live_slots and nth_set_bit), the one game kernel (tfe_nt_play_kernel) with its launch ladder (launch_play) and the one-layer board
+// launch's refusals (check_search), the chance layer itself (search_q_move, one move; search_q, the four in turn), the two-layer deal
+// over a workgroup (search_q2 with live_slots and nth_set_bit), the choice between the two per board (search_q_adaptive), the one game kernel (tfe_nt_play_kernel) with its launch ladder (launch_play) and the one-layer board
 // kernel with its launch (launch_boards).  One copy each.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -60,6 +61,43 @@ __device__ __forceinline__ int count_empty(const uint64_t key) {
     return __popc(tfe_nz_nibbles((uint32_t)key) ^ 0x88888888u) + __popc(tfe_nz_nibbles((uint32_t)(key >> 32)) ^ 0x88888888u);
 }
 
+// q of ONE move of board `key_b` -- kb its afterstate, score its merge score -- by the 32 lanes of a group together; s = this lane's
+// slot of kb: cell s / 2 with the tile 2 (s even) or 4 (s odd).  The chance layer, one copy: the lane's chance board, its four moves,
+// values4, the term, the xor butterfly among the 32, the division.  Every lane of the group must call it with the same move, and
+// every lane returns the same q; +0.0 for a move that does not change the board.
+template <int IMG, class Net>
+__device__ __forceinline__ double search_q_move(const Net& net, const float* __restrict__ w, const uint32_t* __restrict__ lut, const double gamma,
+                                                const uint64_t key_b, const uint64_t kb, const int score, const int s) {
+    const int cell4 = 4 * (s >> 1);
+    const uint64_t tile = (uint64_t)((s & 1) + 1) << cell4;
+    const double odds = (s & 1) ? kP2 : kP1;
+    const bool candidate = kb != key_b;                                                 // (the same in the 32 lanes)
+    double term = 0.0;
+    if (candidate && ((kb >> cell4) & 15ull) == 0ull) {
+        const uint64_t chance = kb | tile;
+        uint64_t kc[4];
+        int scc[4];
+        moves4(chance, lut, kc, scc);
+        double v[4];
+        values4<IMG>(net, w, kc, v);
+        double m = 0.0;
+        bool any = false;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const double x = __dadd_rn((double)tfe_reward(scc[i]), __dmul_rn(gamma, v[i]));
+            const bool cand = kc[i] != chance;
+            m = cand && (!any || x > m) ? x : m;
+            any = any || cand;
+        }
+        term = __dmul_rn(odds, m);
+    }
+#pragma unroll
+    for (int d = 1; d < kGroup; d <<= 1) term = __dadd_rn(term, __shfl_xor(term, d, kGroup));
+    double qa = 0.0;
+    if (candidate) qa = __dadd_rn((double)tfe_reward(score), __dmul_rn(gamma, __ddiv_rn(term, (double)count_empty(kb))));
+    return qa;
+}
+
 // The four q of board `key_b` (its moves ka / sc given), by the 32 lanes of its group together; s = this lane's slot.  Every lane of
 // the group must call it with the same board (the butterfly is among them), and every lane returns the same q.  A move that does
 // not change the board has q = +0.0.  The loop over the moves is kept rolled: one copy of the chance layer in the code.
@@ -68,39 +106,13 @@ __device__ __forceinline__ void search_q(const Net& net, const float* __restrict
                                          const uint64_t key_b, const uint64_t (&ka)[4], const int (&sc)[4], const int s, double (&q)[4]) {
 #pragma unroll
     for (int a = 0; a < 4; ++a) q[a] = 0.0;
-    const int cell4 = 4 * (s >> 1);
-    const uint64_t tile = (uint64_t)((s & 1) + 1) << cell4;
-    const double odds = (s & 1) ? kP2 : kP1;
 #pragma unroll 1
     for (int a = 0; a < 4; ++a) {
         uint64_t kb = ka[0];
         int score = sc[0];
 #pragma unroll
         for (int i = 1; i < 4; ++i) { kb = a == i ? ka[i] : kb; score = a == i ? sc[i] : score; }
-        const bool candidate = kb != key_b;                                             // (the same in the 32 lanes)
-        double term = 0.0;
-        if (candidate && ((kb >> cell4) & 15ull) == 0ull) {
-            const uint64_t chance = kb | tile;
-            uint64_t kc[4];
-            int scc[4];
-            moves4(chance, lut, kc, scc);
-            double v[4];
-            values4<IMG>(net, w, kc, v);
-            double m = 0.0;
-            bool any = false;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const double x = __dadd_rn((double)tfe_reward(scc[i]), __dmul_rn(gamma, v[i]));
-                const bool cand = kc[i] != chance;
-                m = cand && (!any || x > m) ? x : m;
-                any = any || cand;
-            }
-            term = __dmul_rn(odds, m);
-        }
-#pragma unroll
-        for (int d = 1; d < kGroup; d <<= 1) term = __dadd_rn(term, __shfl_xor(term, d, kGroup));
-        double qa = 0.0;
-        if (candidate) qa = __dadd_rn((double)tfe_reward(score), __dmul_rn(gamma, __ddiv_rn(term, (double)count_empty(kb))));
+        const double qa = search_q_move<IMG>(net, w, lut, gamma, key_b, kb, score, s);
 #pragma unroll
         for (int i = 0; i < 4; ++i) q[i] = a == i ? qa : q[i];
     }
@@ -178,6 +190,38 @@ __device__ __forceinline__ void search_q2(const NtDev& net, const float* __restr
         q[a] = 0.0;
         if (ka[a] != key_b) q[a] = __dadd_rn((double)tfe_reward(sc[a]), __dmul_rn(gamma, __ddiv_rn(term, (double)count_empty(ka[a]))));
     }
+}
+
+// The four q of board `key_b` at the depth its empty cells choose, by the 256 lanes of the workgroup
+// together: with count_empty(key_b) <= deep_empty_max search_q2, two chance layers; otherwise the one-layer q of search_q, the four
+// moves side by side: group a < 4 runs search_q_move on move a and its lane 0 stores q_a into qs[a], groups 4..7 only meet the
+// barriers.  Every lane of the workgroup must call it, with the same board, the same number of times; every lane returns the same q
+// and the same `deep`.  The branch depends on the board alone, so the 256 lanes take it alike and meet the same two barriers a
+// call on either side.  terms: search_q2's rows; qs: 4 doubles of LDS of their own, which need no initial value.
+template <int IMG>
+__device__ __forceinline__ bool search_q_adaptive(const NtDev& net, const float* __restrict__ w, const uint32_t* __restrict__ lut, const double gamma,
+                                                  const uint64_t key_b, const uint64_t (&ka)[4], const int (&sc)[4], const int deep_empty_max,
+                                                  double* terms, double* qs, double (&q)[4]) {
+    // (the same in the 256 lanes; read from the first, so that the compiler knows it too and the branch is a scalar one)
+    const bool deep = __builtin_amdgcn_readfirstlane(count_empty(key_b)) <= deep_empty_max;
+    if (deep) {
+        search_q2<IMG>(net, w, lut, gamma, key_b, ka, sc, terms, q);
+    } else {
+        const int group = (int)threadIdx.x >> 5, s = (int)threadIdx.x & (kGroup - 1);
+        __syncthreads();                                                                // the four q of the shallow call before have been read
+        if (group < 4) {                                                                // (the same in the 32 lanes of a group; no barrier inside)
+            uint64_t kb = ka[0];
+            int score = sc[0];
+#pragma unroll
+            for (int i = 1; i < 4; ++i) { kb = group == i ? ka[i] : kb; score = group == i ? sc[i] : score; }
+            const double qa = search_q_move<IMG>(net, w, lut, gamma, key_b, kb, score, s);
+            if (s == 0) qs[group] = qa;                                                 // group < 4: inside the four words
+        }
+        __syncthreads();
+#pragma unroll
+        for (int a = 0; a < 4; ++a) q[a] = qs[a];
+    }
+    return deep;
 }
 
 // pulse_tfe_nt_search's struct as its one-layer kernel takes it

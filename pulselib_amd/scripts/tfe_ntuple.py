@@ -6,7 +6,7 @@ prints, from ONE evaluation launch of `--eval-games` games under the greedy poli
 score and its standard error, the mean length and the histogram of the largest tile.  `--save PATH` writes the non-zero weights and
 the run's state at the end, `--resume PATH` continues such a run for `--rounds` more rounds.  `--search`: every evaluation also runs
 under expectimax search one chance layer deep (section 13.1) on the same boards, and both means are printed; `--resume PATH --rounds 0
---search` plays a saved network; `--search --layers 2` searches two chance layers deep (section 13.4).  `--lambda L` (0 < L <= 1) learns by TD(lambda) (section 13.2): the learn launch walks every game
+--search` plays a saved network; `--search --layers 2` searches two chance layers deep (section 13.4), with `--deep-empty-max E` only on the boards with at most E empty cells and one layer on the others (section 13.11; the line says what share of the moves went deep; not with `--stages`).  `--lambda L` (0 < L <= 1) learns by TD(lambda) (section 13.2): the learn launch walks every game
 backwards first and adds lambda-differences; the run's first line names it, and `--resume` takes it from the file.  `--tc` learns with temporal-coherence
 step sizes (section 13.3): every weight moves by rho = |E| / A of the step, from the running sums of its errors; the round's mean rho
 is printed beside the round's counters, and `--resume` takes `tc` from the file too.  `--train-layers L` (1 or 2; section 13.5) plays the
@@ -34,6 +34,7 @@ import time
 import torch
 
 from ..agents import NTupleTDAfterstateTFEGPU
+from ..agents.tfe_ntuple_td_gpu import check_deep_empty_max
 
 CONTINUE_EVAL_MAX_STEPS = 4096                                             # --continue-games: the evaluations' cap (max_steps is the segment's length)
 
@@ -53,7 +54,13 @@ def _promotions(add_stage, first, rounds) -> dict:
 
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
         resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False, restart=0.0, restart_min_length=64, stages=(), add_stage=(),
-        continue_games=False):
+        continue_games=False, deep_empty_max=None):
+    if deep_empty_max is not None:
+        check_deep_empty_max(deep_empty_max)
+        if not (search and layers == 2):
+            raise ValueError("--deep-empty-max needs --search --layers 2: it says on which boards the evaluation's search looks two chance layers ahead")
+        if stages or add_stage:
+            raise ValueError("--deep-empty-max does not go with --stages / --add-stage: two chance layers are not built on stages")
     if (stages or add_stage) and (train_layers == 2 or (search and layers == 2)):
         raise ValueError("--stages / --add-stage do not go with two chance layers: the staged launches are one ply or one chance layer deep")
     if continue_games and restart:
@@ -92,8 +99,10 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
     def under_search():
         if not search:
             return ""
-        e = agent.evaluate_search(n_games=eval_games, layers=layers)
-        return (f"; under search{'' if layers == 1 else f' of {layers} chance layers'}: Avg final score: {e['mean_score']:.1f} +- {e['std_score'] / e['games'] ** .5:.1f}, Highest: {e['max_score']}, "
+        e = agent.evaluate_search(n_games=eval_games, layers=layers, deep_empty_max=deep_empty_max)
+        depth = "" if deep_empty_max is None else (f" on boards with at most {deep_empty_max} empty cells and one on the others "
+                                                   f"(deep share {e['moves_deep'] / max(e['moves'], 1):.4f} of {e['moves']} moves)")
+        return (f"; under search{'' if layers == 1 else f' of {layers} chance layers'}{depth}: Avg final score: {e['mean_score']:.1f} +- {e['std_score'] / e['games'] ** .5:.1f}, Highest: {e['max_score']}, "
                 f"Avg length: {e['mean_length']:.1f}, cut {e['truncated']}, largest tile 2^k: {e['max_tile_hist']}")
 
     def evaluation():
@@ -146,6 +155,8 @@ def main(argv=None):
     ap.add_argument("--resume", metavar="PATH", help="continue the run saved there (the same --tables, --alpha, --epsilon, --gamma, --max-steps, --seed)")
     ap.add_argument("--search", action="store_true", help="every evaluation also under expectimax search, one chance layer deep")
     ap.add_argument("--layers", type=int, default=1, choices=[1, 2], help="with --search: the chance layers the search looks ahead")
+    ap.add_argument("--deep-empty-max", type=int, metavar="E",
+                    help="with --search --layers 2: two chance layers only on boards with at most E empty cells (0..16), one on the others; not with --stages")
     ap.add_argument("--train-layers", type=int, default=0, choices=[0, 1, 2],
                     help="the chance layers of search the rounds' own games are played under (0: the one-ply roll-out); not saved: give it again with --resume")
     ap.add_argument("--backed", action="store_true",
@@ -168,6 +179,13 @@ def main(argv=None):
         ap.error("--stages takes tiles as 512,2048 and --add-stage ROUND:TILE")
     if len({r for r, _ in add_stage}) != len(add_stage):
         ap.error("--add-stage names a round twice: one stage is split before a round")
+    if args.deep_empty_max is not None:
+        if not 0 <= args.deep_empty_max <= 16:
+            ap.error("--deep-empty-max must be in 0..16")
+        if not (args.search and args.layers == 2):
+            ap.error("--deep-empty-max needs --search --layers 2: it says on which boards the evaluation's search looks two chance layers ahead")
+        if stages or add_stage:
+            ap.error("--deep-empty-max does not go with --stages / --add-stage: two chance layers are not built on stages")
     if (stages or add_stage) and (args.train_layers == 2 or (args.search and args.layers == 2)):
         ap.error("--stages / --add-stage do not go with two chance layers: the staged launches are one ply or one chance layer deep")
     if args.restart and args.train_layers == 2:
@@ -183,7 +201,7 @@ def main(argv=None):
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
                 args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers, backed=args.backed,
                 restart=args.restart, restart_min_length=args.restart_min_length, stages=stages, add_stage=add_stage,
-                continue_games=args.continue_games)
+                continue_games=args.continue_games, deep_empty_max=args.deep_empty_max)
     st = agent.stats()
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
           f"{int((agent.weights_dev != 0).sum().item())} of {agent.total_weights} weights are not zero")

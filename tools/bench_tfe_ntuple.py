@@ -16,7 +16,12 @@ per move (a move = one move of one game; the launch's time over all the moves it
 the line also holds "search2", the evaluation under search two chance layers deep (section 13.4) on the same boards, its per-move time
 over the one-layer search's, and the yardstick of that ratio: the mean number of child searches a two-layer move makes, counted on the
 host from the candidate and empty-cell masks of the boards of 32 games played under that policy (children_per_move); the ratio over
-the count, and whether it is within the count + 50 %.  --lambda L: per B one more line, {"lambda": ...}: on the games of the last timed round, in the same
+the count, and whether it is within the count + 50 %.  --search --layers 2 --deep-empty-max E [E ...]: per G and E
+one more line, {"adaptive_search": ...}: the evaluation launches under one layer, under the search two layers deep on the boards with
+at most E empty cells, and under two layers on every board, same weights and boards, alternating in turn in the same process, each
+between its own HIP events, one untimed pass and then --repeats: the three launch times, the moves and the share of them searched two
+layers deep, the mean scores with their standard errors, and the differences E - one layer and E - two layers paired by board.
+--lambda L: per B one more line, {"lambda": ...}: on the games of the last timed round, in the same
 process and back to back, the TD(0) learn launch (pulse_tfe_nt_learn) and the TD(lambda) launch (pulse_tfe_nt_learn_lambda: the backward
 walk and the adds) each between its own pair of HIP events, --warmup untimed pairs and then --repeats timed ones, alternating; the
 accumulators are zeroed, untimed, before every launch, so both add the same moves into empty cells.  --tc: per B one more line, marked {"tc": true}: on the games of the last timed round, in the same process and alternating, the fixed-step pair
@@ -510,6 +515,40 @@ def search_line(agent, torch, games, repeats, layers=1):
     return {"search": line}
 
 
+def adaptive_lines(agent, torch, games, thresholds, repeats):
+    """One {"adaptive_search": ...} line per threshold E: the evaluation launch under one layer of search, under
+    the adaptive search at every E and under two layers, on the same weights and boards, alternating in turn, each between its own pair
+    of HIP events: one untimed pass (with its read-back: the scores per game, the counters, the moves at each depth), then `repeats`."""
+    import numpy as np
+    how = {"one": dict(layers=1), **{E: dict(layers=2, deep_empty_max=E) for E in thresholds}, "two": dict(layers=2)}
+    scores, counters = {}, {}
+    for name, kw in how.items():
+        e = agent.evaluate_search(n_games=games, per_game=True, **kw)
+        scores[name], counters[name] = e.pop("total_score").astype(np.float64), e
+    launches = [(name, lambda kw=kw: agent.evaluate_search_launch(games, **kw)) for name, kw in how.items()]
+    seconds = _alternate(agent, torch, launches, 0, repeats, before=lambda: agent.eval_counters(clear=True))
+
+    def policy(name):
+        e, t = counters[name], _spread(seconds[name])
+        return {"seconds": t, "moves": e["moves"], "seconds_per_move": t["median"] / e["moves"], "mean_score": e["mean_score"],
+                "se_score": e["std_score"] / e["games"] ** .5, "mean_length": e["mean_length"], "truncated": e["truncated"]}
+
+    def paired(a, b):
+        d = scores[a] - scores[b]
+        return {"mean": float(d.mean()), "se": float(d.std(ddof=1) / np.sqrt(d.size))}
+
+    lines = []
+    for E in thresholds:
+        e, mine, one, two = counters[E], policy(E), policy("one"), policy("two")
+        mine.update(moves_deep=e["moves_deep"], moves_shallow=e["moves_shallow"], deep_share=e["moves_deep"] / max(e["moves"], 1))
+        lines.append({"adaptive_search": {"games": games, "deep_empty_max": E, "trained_rounds": agent.round, "train_games": agent.n_games,
+                                          "max_steps": agent.max_steps, "repeats": repeats, "one_layer": one, "adaptive": mine, "two_layers": two,
+                                          "adaptive_minus_one": paired(E, "one"), "adaptive_minus_two": paired(E, "two"),
+                                          "seconds_over_one": mine["seconds"]["median"] / one["seconds"]["median"],
+                                          "seconds_over_two": mine["seconds"]["median"] / two["seconds"]["median"]}})
+    return lines
+
+
 def lambda_line(agent, torch, lam, warmup, repeats):
     """the two learn launches on the games the agent last recorded (the agent's own lam is 0: learn() is the TD(0) launch)"""
     launches = (("learn", agent.learn), ("learn_lambda", lambda: agent.learn_lambda_launch(lam)))
@@ -615,6 +654,8 @@ def main(argv=None):
     ap.add_argument("--search", action="store_true", help="one more line per B: the evaluation under search beside the one-ply one")
     ap.add_argument("--search-games", type=int, nargs="+", default=[1024, 65536])
     ap.add_argument("--layers", type=int, default=1, choices=[1, 2], help="with --search, 2: the two-layer evaluation and its child count beside the other two")
+    ap.add_argument("--deep-empty-max", type=int, nargs="+", metavar="E",
+                    help="with --search --layers 2: one more line per B and E, the evaluation under the search two layers deep on boards with at most E empty cells beside one and two layers")
     ap.add_argument("--lambda", dest="lam", type=float, help="one more line per B: the TD(lambda) learn launch beside the TD(0) one, on the same games")
     ap.add_argument("--tc", action="store_true", help="one more line per B: the temporal-coherence learn and apply launches beside the fixed-step ones")
     ap.add_argument("--train-layers", type=int, choices=[1, 2], help="one more line per B: the recording launch under search beside the evaluation under it")
@@ -635,6 +676,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.backed and not args.train_layers:
         ap.error("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
+    if args.deep_empty_max and not (args.search and args.layers == 2):
+        ap.error("--deep-empty-max needs --search --layers 2: it says on which boards the search looks two chance layers ahead")
+    if args.deep_empty_max and not all(0 <= E <= 16 for E in args.deep_empty_max):
+        ap.error("--deep-empty-max takes thresholds in 0..16")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_tfe_ntuple needs the MI355X: no timing is taken on a CPU")
@@ -683,6 +728,8 @@ def main(argv=None):
             lines = [state_line(agent, torch, s, args.trained_rounds, args.warmup, args.repeats) for s in args.states]
             if args.search:                                                 # on the weights the last state left
                 lines += [search_line(agent, torch, g, args.repeats, args.layers) for g in args.search_games]
+            if args.deep_empty_max:                                         # likewise
+                lines += [line for g in args.search_games for line in adaptive_lines(agent, torch, g, args.deep_empty_max, args.repeats)]
             if args.lam is not None:                                        # on the games the last timed round recorded
                 lines.append(lambda_line(agent, torch, args.lam, args.warmup, args.repeats))
             if args.tc:                                                     # likewise
