@@ -181,6 +181,11 @@ class _TFEGamesGPU:
     def evaluate_launch(self, n_games=None, epsilon=0.0, board_id0=None, per_game=False):
         """The launch of evaluate() alone: ADDS to the counters of `eval_counters` and reads nothing back.  Returns the per-game device
         tensors (total_score int64[B], lengths int32[B]) with per_game, else None."""
+        return self._evaluate_launch_with(self._eval_launch, n_games, epsilon, board_id0, per_game)
+
+    def _evaluate_launch_with(self, launch, n_games, epsilon, board_id0, per_game):
+        """evaluate_launch's body: the evaluation's struct filled, then launch(struct) -- the agent's `_eval_launch`, or the entry point
+        of another policy on the same struct."""
         import torch
         B = self.n_games if n_games is None else int(n_games)
         o = self._draws(self._eval_struct(), self.eval_board_id0() if board_id0 is None else int(board_id0))
@@ -190,7 +195,7 @@ class _TFEGamesGPU:
         if per_game:
             arrays = (torch.zeros(B, dtype=torch.int64, device=self.device), torch.zeros(B, dtype=torch.int32, device=self.device))
             o.total_score, o.lengths = arrays[0].data_ptr(), arrays[1].data_ptr()
-        self._eval_launch(o)
+        launch(o)
         return arrays
 
     def _eval_cap(self) -> int:
@@ -215,8 +220,12 @@ class _TFEGamesGPU:
         """One launch and one read-back: `n_games` games (default: the agent's) under the policy as it stands and `epsilon` (default 0:
         the greedy policy), no trajectory.  With equal seeds, round, epsilon and board_id0 they are the games rollout() plays.  Returns
         what eval_summary_on_host makes of the agent's counters; per_game adds the arrays total_score / lengths."""
+        return self._evaluate_with(self._eval_launch, n_games, epsilon, board_id0, per_game)
+
+    def _evaluate_with(self, launch, n_games, epsilon, board_id0, per_game) -> dict:
+        """evaluate's body: the counters cleared, _evaluate_launch_with(launch, ...) and the read-back."""
         self.eval_counters(clear=True)
-        arrays = self.evaluate_launch(n_games, epsilon, board_id0, per_game)
+        arrays = self._evaluate_launch_with(launch, n_games, epsilon, board_id0, per_game)
         out = self.eval_counters()
         if per_game:
             out["total_score"], out["lengths"] = arrays[0].cpu().numpy(), arrays[1].cpu().numpy()

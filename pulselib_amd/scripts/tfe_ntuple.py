@@ -1,5 +1,5 @@
 """An n-tuple network for 2048 on the 4 x 4 board, trained by batch TD(0) on afterstates with the whole loop on the device
-(agents/tfe_ntuple_td_gpu.py): every round is a roll-out launch of `--tables` whole games under the network,
+(agents/tfe_ntuple_td_gpu.py; which flags go together: check_options of agents/tfe_ntuple_host.py, section 13.12): every round is a roll-out launch of `--tables` whole games under the network,
 a learn launch of one lane per recorded move and an apply launch over the weights.  Defaults: the network of two rows and two 2 x 3
 rectangles over the board's eight images, gamma 1, epsilon 0, alpha 1.  Every `--eval-every` rounds (default: every round) it
 prints, from ONE evaluation launch of `--eval-games` games under the greedy policy on the same boards every time: the mean final
@@ -34,7 +34,7 @@ import time
 import torch
 
 from ..agents import NTupleTDAfterstateTFEGPU
-from ..agents.tfe_ntuple_td_gpu import check_deep_empty_max
+from ..agents.tfe_ntuple_host import check_options
 
 CONTINUE_EVAL_MAX_STEPS = 4096                                             # --continue-games: the evaluations' cap (max_steps is the segment's length)
 
@@ -55,24 +55,8 @@ def _promotions(add_stage, first, rounds) -> dict:
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
         resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False, restart=0.0, restart_min_length=64, stages=(), add_stage=(),
         continue_games=False, deep_empty_max=None):
-    if deep_empty_max is not None:
-        check_deep_empty_max(deep_empty_max)
-        if not (search and layers == 2):
-            raise ValueError("--deep-empty-max needs --search --layers 2: it says on which boards the evaluation's search looks two chance layers ahead")
-        if stages or add_stage:
-            raise ValueError("--deep-empty-max does not go with --stages / --add-stage: two chance layers are not built on stages")
-    if (stages or add_stage) and (train_layers == 2 or (search and layers == 2)):
-        raise ValueError("--stages / --add-stage do not go with two chance layers: the staged launches are one ply or one chance layer deep")
-    if continue_games and restart:
-        raise ValueError("--continue-games does not go with --restart: both choose the boards the next round's games begin on")
-    if continue_games and train_layers == 2:
-        raise ValueError("--continue-games does not go with --train-layers 2: the roll-out from given boards is one ply or one chance layer deep")
-    if continue_games and max_steps < 2:
-        raise ValueError("--continue-games needs --max-steps 2 or more: a segment of K moves gives K - 1 learnt ones")
-    if restart and train_layers == 2:
-        raise ValueError("--restart does not go with --train-layers 2: the restarted roll-out is one ply or one chance layer deep")
-    if backed and train_layers not in (1, 2):
-        raise ValueError("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
+    check_options(train_layers, backed, restart, continue_games, max_steps, bool(stages or add_stage), search=search, layers=layers,
+                  deep_empty_max=deep_empty_max, script=True)        # (refused before a device is asked for)
     if resume:
         agent = NTupleTDAfterstateTFEGPU.load(resume, device)
         want = dict(n_games=tables, alpha=float(alpha), epsilon=float(epsilon), gamma=float(gamma), max_steps=max_steps, seed=seed)
@@ -182,22 +166,11 @@ def main(argv=None):
     if args.deep_empty_max is not None:
         if not 0 <= args.deep_empty_max <= 16:
             ap.error("--deep-empty-max must be in 0..16")
-        if not (args.search and args.layers == 2):
-            ap.error("--deep-empty-max needs --search --layers 2: it says on which boards the evaluation's search looks two chance layers ahead")
-        if stages or add_stage:
-            ap.error("--deep-empty-max does not go with --stages / --add-stage: two chance layers are not built on stages")
-    if (stages or add_stage) and (args.train_layers == 2 or (args.search and args.layers == 2)):
-        ap.error("--stages / --add-stage do not go with two chance layers: the staged launches are one ply or one chance layer deep")
-    if args.restart and args.train_layers == 2:
-        ap.error("--restart does not go with --train-layers 2: the restarted roll-out is one ply or one chance layer deep")
-    if args.continue_games and args.restart:
-        ap.error("--continue-games does not go with --restart: both choose the boards the next round's games begin on")
-    if args.continue_games and args.train_layers == 2:
-        ap.error("--continue-games does not go with --train-layers 2: the roll-out from given boards is one ply or one chance layer deep")
-    if args.continue_games and args.max_steps < 2:
-        ap.error("--continue-games needs --max-steps 2 or more: a segment of K moves gives K - 1 learnt ones")
-    if args.backed and args.train_layers not in (1, 2):
-        ap.error("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
+    try:                                                                    # (run()'s refusals, as the command line's)
+        check_options(args.train_layers, args.backed, args.restart, args.continue_games, args.max_steps, bool(stages or add_stage),
+                      search=args.search, layers=args.layers, deep_empty_max=args.deep_empty_max, script=True)
+    except ValueError as refused:
+        ap.error(str(refused))
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
                 args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers, backed=args.backed,
                 restart=args.restart, restart_min_length=args.restart_min_length, stages=stages, add_stage=add_stage,

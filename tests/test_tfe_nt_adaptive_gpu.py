@@ -132,9 +132,7 @@ def test_a_null_depth_stats_leaves_everything_else_equal():
     a = _agent("seeded")
     mine = a.evaluate_search(epsilon=EPSILON, board_id0=BOARD_ID0, per_game=True, layers=2, deep_empty_max=E)
     counted = a.depth_stats.cpu().tolist()
-    a._eval_entry, a._eval_args = EVALUATE, (E, None)
-    null = a.evaluate(epsilon=EPSILON, board_id0=BOARD_ID0, per_game=True)
-    del a._eval_entry, a._eval_args
+    null = a._evaluate_with(a._entry(EVALUATE, E, None), None, EPSILON, BOARD_ID0, True)
     _same(null, mine, skip=DEPTHS)
     assert a.depth_stats.cpu().tolist() == counted == [mine[k] for k in DEPTHS] and mine["moves"] > GAMES and not set(DEPTHS) & set(null)
     # the launch alone only adds

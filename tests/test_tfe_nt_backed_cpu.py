@@ -212,8 +212,8 @@ def test_python_layer(tmp_path):
     from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
     nt = _nt()
     assert NTupleTDAfterstateTFEGPU.backed_targets is False
-    p = inspect.signature(NTupleTDAfterstateTFEGPU.__init__).parameters
-    assert list(p) == ["self", "device", "n_games", "tuples", "symmetric", "gamma", "epsilon", "alpha", "max_steps", "seed", "board_id0", "lam", "tc"]
+    from tests.tfe_nt_support import assert_init_parameters
+    assert_init_parameters(NTupleTDAfterstateTFEGPU)
     assert list(inspect.signature(NTupleTDAfterstateTFEGPU.rollout).parameters) == ["self", "layers"]
     assert inspect.signature(NTupleTDAfterstateTFEGPU.rollout).parameters["layers"].default is None
     assert list(inspect.signature(NTupleTDAfterstateTFEGPU.learn_batch).parameters) == ["self"]

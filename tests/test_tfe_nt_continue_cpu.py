@@ -152,8 +152,8 @@ def test_python_layer(tmp_path):
     assert Agent.continue_games is False and Agent.eval_max_steps is None
     assert Agent.carry_score is None and Agent.carry_moves is None and Agent.finished is None
     assert Agent.restart_fraction == 0.0 and Agent.start is None            # (what was there stays)
-    p = inspect.signature(Agent.__init__).parameters
-    assert list(p) == ["self", "device", "n_games", "tuples", "symmetric", "gamma", "epsilon", "alpha", "max_steps", "seed", "board_id0", "lam", "tc"]
+    from tests.tfe_nt_support import assert_init_parameters
+    assert_init_parameters(Agent)
     assert list(inspect.signature(Agent.rollout).parameters) == ["self", "layers"] and inspect.signature(Agent.rollout).parameters["layers"].default is None
     assert list(inspect.signature(Agent.learn_batch).parameters) == ["self"]
     assert list(inspect.signature(Agent.restart_pick_launch).parameters) == ["self", "fraction", "min_length"]

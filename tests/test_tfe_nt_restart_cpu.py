@@ -208,8 +208,8 @@ def test_python_layer(tmp_path):
     from pulselib_amd.agents import NTupleTDAfterstateTFEGPU as Agent
     nt = _nt()
     assert Agent.restart_fraction == 0.0 and Agent.restart_min_length == 64 and Agent.start is None and Agent.restart_stats is None
-    p = inspect.signature(Agent.__init__).parameters
-    assert list(p) == ["self", "device", "n_games", "tuples", "symmetric", "gamma", "epsilon", "alpha", "max_steps", "seed", "board_id0", "lam", "tc"]
+    from tests.tfe_nt_support import assert_init_parameters
+    assert_init_parameters(Agent)
     assert list(inspect.signature(Agent.rollout).parameters) == ["self", "layers"] and inspect.signature(Agent.rollout).parameters["layers"].default is None
     assert list(inspect.signature(Agent.learn_batch).parameters) == ["self"]
     assert list(inspect.signature(Agent.restart_pick_launch).parameters) == ["self", "fraction", "min_length"]

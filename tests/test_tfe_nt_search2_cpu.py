@@ -168,7 +168,8 @@ def test_python_layer():
                      lambda: agent.evaluate_search(layers=layers), lambda: agent.evaluate_search_launch(layers=layers)):
             with pytest.raises(ValueError, match="layers must be 1 or 2"):
                 call()
-    assert list(inspect.signature(NTupleTDAfterstateTFEGPU.__init__).parameters)[-1] == "tc"
+    from tests.tfe_nt_support import assert_init_parameters
+    assert_init_parameters(NTupleTDAfterstateTFEGPU)
 
 
 def test_deep_search_kernels_use_no_scratch():

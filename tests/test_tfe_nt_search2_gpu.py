@@ -139,9 +139,7 @@ def test_one_layer_through_the_deep_entry_point_is_the_search_evaluation():
     """the same board_id0, every key: pulse_tfe_nt_evaluate_search_deep at layers = 1 and pulse_tfe_nt_evaluate_search"""
     a = _agent("seeded")
     one = a.evaluate_search(epsilon=EPSILON, board_id0=BOARD_ID0, per_game=True)
-    a._eval_entry, a._eval_args = "pulse_tfe_nt_evaluate_search_deep", (1,)
-    deep = a.evaluate(epsilon=EPSILON, board_id0=BOARD_ID0, per_game=True)
-    del a._eval_entry, a._eval_args
+    deep = a._evaluate_with(a._entry("pulse_tfe_nt_evaluate_search_deep", 1), None, EPSILON, BOARD_ID0, True)
     assert sorted(one) == sorted(deep) and one["moves"] > GAMES
     for k in one:
         assert np.array_equal(one[k], deep[k]) if k in ("total_score", "lengths") else one[k] == deep[k], k

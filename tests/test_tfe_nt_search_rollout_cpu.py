@@ -62,7 +62,8 @@ def test_python_layer():
     assert inspect.signature(NTupleTDAfterstateTFEGPU.rollout).parameters["layers"].default is None
     assert list(inspect.signature(NTupleTDAfterstateTFEGPU.rollout_search_launch).parameters) == ["self", "layers"]
     assert list(inspect.signature(NTupleTDAfterstateTFEGPU.learn_batch).parameters) == ["self"]
-    assert list(inspect.signature(NTupleTDAfterstateTFEGPU.__init__).parameters)[-1] == "tc"
+    from tests.tfe_nt_support import assert_init_parameters
+    assert_init_parameters(NTupleTDAfterstateTFEGPU)
     agent = NTupleTDAfterstateTFEGPU.__new__(NTupleTDAfterstateTFEGPU)        # (no device: the depth is refused before anything is touched)
     assert agent.rollout_layers == 0
     for bad in (3, True, -1):

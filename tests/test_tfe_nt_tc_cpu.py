@@ -66,8 +66,9 @@ def test_python_layer():
     import torch
     from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
     nt = _nt()
-    p = inspect.signature(NTupleTDAfterstateTFEGPU.__init__).parameters
-    assert p["tc"].default is False and p["lam"].default == 0.0 and list(p)[-1] == "tc"
+    from tests.tfe_nt_support import assert_init_parameters
+    p = assert_init_parameters(NTupleTDAfterstateTFEGPU)
+    assert p["tc"].default is False and p["lam"].default == 0.0
     for name in ("learn_tc_launch", "apply_tc_launch", "coherence", "tc_summary", "clear", "learn_lambda_launch"):
         assert callable(getattr(NTupleTDAfterstateTFEGPU, name)), name
     for name in ("learn_tc_nt_on_host", "apply_tc_nt_on_host", "tc_summary_on_host", "coherence_of_checkpoint"):

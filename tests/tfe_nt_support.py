@@ -24,6 +24,19 @@ def nt():
     return tfe_ntuple_td_gpu
 
 
+def assert_init_parameters(Agent):
+    """The agent's __init__ takes, by position, exactly the parameters it took before the opt-ins that are attributes, ending in `tc`;
+    `stage_tiles` is keyword-only with default (); and inspect.signature of the class is __init__'s without `self`: nothing stands
+    between the call and __init__.  Returns __init__'s parameters."""
+    import inspect
+    p = inspect.signature(Agent.__init__).parameters
+    positional = [k for k, v in p.items() if v.kind is inspect.Parameter.POSITIONAL_OR_KEYWORD]
+    assert positional == ["self", "device", "n_games", "tuples", "symmetric", "gamma", "epsilon", "alpha", "max_steps", "seed", "board_id0", "lam", "tc"]
+    assert list(p) == positional + ["stage_tiles"] and p["stage_tiles"].kind is inspect.Parameter.KEYWORD_ONLY and p["stage_tiles"].default == ()
+    assert type(Agent) is type and list(inspect.signature(Agent).parameters.values()) == list(p.values())[1:]
+    return p
+
+
 def bits(x):
     return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
 
