@@ -1072,6 +1072,24 @@ typedef struct PulseTfeNtRestartPick {
 } PulseTfeNtRestartPick;
 int pulse_tfe_nt_restart_pick(const PulseTfeNtRestartPick* o, void* stream);
 
+/* ---- ... and the training roll-out at the depth the board chooses, per move.  Opt-in: a caller that never calls it keeps every launch
+ * above unchanged.  pulse_tfe_nt_rollout_search's games and records under pulse_tfe_nt_evaluate_search_adaptive's policy: for the
+ * board B a move is made from, n = its empty cells, the q the greedy scan reads are those of the two-layer search with
+ * n <= deep_empty_max and those of the one-layer search otherwise, bit for bit.  What a move records is unchanged: keys[t, g] the
+ * chosen afterstate, values[t, g] the NETWORK's V of it, steps[t, g] the action, the reward and the game-over bit.
+ *   backed:      device float64[max_steps * n_games], or NULL: pulse_tfe_nt_rollout_backed's word per move, the largest q over the
+ *                candidate moves, of the q at the depth the board chose; NULL records none.
+ *   start:       device uint64[n_games], or NULL: pulse_tfe_nt_rollout_from's start boards -- game g begins on start[g] where that
+ *                board is usable and at its reset otherwise, with 0 stored into start[g]; NULL begins every game at its reset.
+ *   depth_stats: device int64[2], or NULL: [0] += the moves whose q came from two layers, [1] += those from one layer; every move of
+ *                every game counts, the epsilon branch's too; added once per game, at its end, and never zeroed by the launch.
+ * deep_empty_max = 16 is pulse_tfe_nt_rollout_search / _backed at layers = 2, record for record.  One game per workgroup of 256 lanes.
+ *
+ * PULSE_EINVAL, before anything is launched, in this order: null options; `deep_empty_max` outside 0..16 ("deep_empty_max must be in
+ * 0..16"); depth_stats, backed or start not 8-byte aligned; what pulse_tfe_nt_rollout refuses of the struct, under this name. */
+int pulse_tfe_nt_rollout_adaptive(const PulseTfeNtRollout* o, int32_t deep_empty_max, double* backed, uint64_t* start,
+                                  int64_t* depth_stats, void* stream);
+
 /* ---- ... and weight sets by tile stage ("multi-stage TD"; promoting a stage's weights into a new one is "weight promotion").
  * Opt-in: a caller that never calls these four keeps every launch above unchanged.
  *

@@ -292,6 +292,7 @@ SYMBOLS = {
     "pulse_tfe_nt_rollout_backed": (C.c_int, [_P, _I32, _P, _P]),
     "pulse_tfe_nt_learn_backed": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_rollout_from": (C.c_int, [_P, _I32, _P, _P, _P]),
+    "pulse_tfe_nt_rollout_adaptive": (C.c_int, [_P, _I32, _P, _P, _P, _P]),
     "pulse_tfe_nt_restart_pick": (C.c_int, [_P, _P]),
     "pulse_tfe_nt_rollout_staged": (C.c_int, [_P, _P, _I32, _P, _P, _P]),
     "pulse_tfe_nt_learn_staged": (C.c_int, [_P, _P, _P]),

@@ -15,7 +15,8 @@ below, vectorised over boards, state it exactly:
   restarted roll-outs (13.7): `spawn_on_host`, `restart_pick_on_host`;
   weight sets by tile stage (13.9): the stages travel on `tuples` (`with_stages`), so every mirror reads and adds by stage;
     `stage_of_keys_on_host` states the stage, `split_stage_tiles` and `add_stage_on_host` the promotion;
-  games continued across rounds (13.10): `continue_pick_on_host`.
+  games continued across rounds (13.10): `continue_pick_on_host`;
+  the roll-out at the adaptive depth (13.13): `search_adaptive_nt_on_host`'s q with `search_backed_on_host` of them; no mirror of its own.
 Which of a round's options go together is stated once, in `check_options` (13.12), in the agent's words and in the script's."""
 from __future__ import annotations
 
@@ -471,16 +472,19 @@ def finished_summary_on_host(words) -> dict:
 
 # ------------------------------------------------------------------ which options go together
 def check_options(depth=0, backed_targets=False, restart_fraction=0.0, continue_games=False, max_steps=None, staged=False, *,
-                  search=False, layers=1, deep_empty_max=None, script=False):
+                  search=False, layers=1, deep_empty_max=None, rollout_deep_empty_max=None, script=False):
     """The one statement of which options of a round and of an evaluation go together.  Of the round: `depth`, the chance layers its
     games are played under (check_rollout_layers), `backed_targets`, `restart_fraction` (check_restart_fraction), `continue_games`,
     `max_steps` (None: not asked about) and `staged`, whether the network has weight sets by stage.  Of the evaluation or the search,
-    where there is one (`search`): its `layers` (check_layers) and `deep_empty_max` (check_deep_empty_max).  ValueError at the first
+    where there is one (`search`): its `layers` (check_layers) and `deep_empty_max` (check_deep_empty_max).  Of the round again:
+    `rollout_deep_empty_max` (check_deep_empty_max; None: off), the threshold of a roll-out at the adaptive depth (section 13.13), which
+    is built from `start` too: with it two layers go with restarts and with continuation.  ValueError at the first
     rule of the table below that is broken, in the agent's words (attributes and arguments) or, with `script`, in those of
     scripts/tfe_ntuple.py (flags).  Returns (depth, from_start, layers, deep_empty_max) as they are meant: from_start, the round's
     games begin on the boards of `start` (restarts or continuation); layers 0 without `search`.  A new option's rules are added here."""
     depth, restart = check_rollout_layers(depth), check_restart_fraction(restart_fraction) > 0.0
     layers, deep_empty_max = check_layers(layers) if search else 0, check_deep_empty_max(deep_empty_max)
+    adaptive = check_deep_empty_max(rollout_deep_empty_max) is not None
     two_on_stages = "layers = 2 on an agent with stage_tiles: two chance layers are not built on stages"
     stages_two = "--stages / --add-stage do not go with two chance layers: the staged launches are one ply or one chance layer deep"
     rules = (                                                               # (broken, the agent's words, the script's), in the order they are tested
@@ -489,10 +493,15 @@ def check_options(depth=0, backed_targets=False, restart_fraction=0.0, continue_
          "--deep-empty-max needs --search --layers 2: it says on which boards the evaluation's search looks two chance layers ahead"),
         (deep_empty_max is not None and staged, two_on_stages,
          "--deep-empty-max does not go with --stages / --add-stage: two chance layers are not built on stages"),
+        (adaptive and depth != 2,
+         "rollout_deep_empty_max needs rollout_layers = 2: it says on which boards the roll-out's search looks two chance layers ahead",
+         "--train-deep-empty-max needs --train-layers 2: it says on which boards the roll-out's search looks two chance layers ahead"),
+        (adaptive and staged, "rollout_deep_empty_max on an agent with stage_tiles: two chance layers are not built on stages",
+         "--train-deep-empty-max does not go with --stages / --add-stage: two chance layers are not built on stages"),
         (continue_games and restart,
          "continue_games does not go with restart_fraction > 0: both fill start for the next round",
          "--continue-games does not go with --restart: both choose the boards the next round's games begin on"),
-        (continue_games and depth == 2,
+        (continue_games and depth == 2 and not adaptive,
          "continue_games needs rollout_layers in (0, 1): the roll-out from start is not built two layers deep",
          "--continue-games does not go with --train-layers 2: the roll-out from given boards is one ply or one chance layer deep"),
         (continue_games and max_steps is not None and max_steps < 2,
@@ -500,7 +509,7 @@ def check_options(depth=0, backed_targets=False, restart_fraction=0.0, continue_
          "--continue-games needs --max-steps 2 or more: a segment of K moves gives K - 1 learnt ones"),
         (staged and depth == 2, "rollout_" + two_on_stages, stages_two),
         (staged and layers == 2, two_on_stages, stages_two),
-        (restart and depth == 2,
+        (restart and depth == 2 and not adaptive,
          "restart_fraction > 0 needs rollout_layers in (0, 1): the restarted roll-out is not built two layers deep",
          "--restart does not go with --train-layers 2: the restarted roll-out is one ply or one chance layer deep"),
         (backed_targets and not depth,

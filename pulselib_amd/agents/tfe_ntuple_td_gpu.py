@@ -25,7 +25,10 @@ agent as it was while it is off:
     copy of its stage, through the four `pulse_tfe_nt_*_staged` entry points and one apply launch per stage; `add_stage` splits one;
   `continue_games` (13.10; csrc/tfe_ntuple_continue.hip): with a small `max_steps` = K a round plays K moves of every game, and
     `pulse_tfe_nt_continue_pick` puts the cut games' boards into `start`, their scores so far into the carries and the ended games
-    into `finished`; `eval_max_steps` gives the evaluations a cap of their own.
+    into `finished`; `eval_max_steps` gives the evaluations a cap of their own;
+  `rollout_deep_empty_max` = E (13.13; csrc/tfe_ntuple_adaptive_rollout.hip): with `rollout_layers` 2 the round's games are played and
+    recorded by `pulse_tfe_nt_rollout_adaptive`, two layers deep on the boards with at most E empty cells and one on the others, with
+    the backed values and from `start` where those are on.
 Which of them go together is `check_options`' to say (13.12), and the agent asks it before it touches anything."""
 from __future__ import annotations
 
@@ -71,7 +74,14 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     the three are allocated by the first continue launch.  `total_score`, `lengths` and stats() stay per segment.  A lambda-walk ends
     at the segment's cut.  No checkpoint holds any of it: a loaded agent's games begin at their resets.  `eval_max_steps` (an
     attribute, None by default: the agent's `max_steps`): the cap of evaluate_launch's games, so of evaluate and evaluate_search, any
-    value in 1..65,535 -- the evaluation launches hold no per-move buffers."""
+    value in 1..65,535 -- the evaluation launches hold no per-move buffers.
+    `rollout_deep_empty_max` (an attribute, None by default: the agent as it was; section 13.13): an int E in 0..16 and, with
+    `rollout_layers` 2, `rollout` plays the round's games under the search whose depth the board chooses -- two chance layers where
+    the board a move is made from has at most E empty cells, one elsewhere (rollout_adaptive_launch) -- and records them as before,
+    with `backed` if `backed_targets` and from `start` once a restart or continue pick has filled it: with E set, two layers go with
+    `restart_fraction` > 0 and with `continue_games`.  Any other `rollout_layers` and `stage_tiles` are refused (ValueError before
+    anything is touched).  The launch adds the moves at each depth to `depth_stats` (rollout_depth_summary).  The learners, the apply
+    and the pick launches read the records as they are.  It says how rounds are played, so no checkpoint holds it."""
     STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
     continue_games = False                                                 # set on the agent; checked at the launch
     eval_max_steps = None                                                  # set on the agent; None: the agent's max_steps
@@ -80,6 +90,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     restart_min_length = 64                                                # set on the agent; checked by the pick launch
     start = restart_stats = None                                           # allocated by the first restart launch
     rollout_layers = 0                                                     # set on the agent; checked at the launch (check_rollout_layers)
+    rollout_deep_empty_max = None                                          # set on the agent; checked at the launch, with rollout_layers
     backed_targets = False                                                 # set on the agent; checked at the launch, with rollout_layers
     stage_tiles = ()                                                       # __init__'s stage_tiles, or those `tuples` carry; add_stage grows it
 
@@ -200,9 +211,15 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         depth must be 0 or 1 and the launch is rollout_staged_launch, from `start` (zeroed here while restart_fraction is 0 and
         `continue_games` is off).  With `continue_games` the depth must be 0 or 1, restart_fraction 0 and max_steps at least 2
         (ValueError otherwise, before anything is touched), and once a continue pick has filled `start` the launch is
-        rollout_from_launch at that depth, with the backed values if `backed_targets`."""
+        rollout_from_launch at that depth, with the backed values if `backed_targets`.  With `rollout_deep_empty_max` the depth
+        must be 2 and the agent without stages (ValueError otherwise, before anything is touched), and the launch is
+        rollout_adaptive_launch at that threshold, with the backed values if `backed_targets` and from `start` once a pick has filled it."""
         layers, from_start, _, _ = check_options(self.rollout_layers if layers is None else layers, self.backed_targets, self.restart_fraction,
-                                                 self.continue_games, self.max_steps if self.continue_games else None, bool(self.stage_tiles))
+                                                 self.continue_games, self.max_steps if self.continue_games else None, bool(self.stage_tiles),
+                                                 rollout_deep_empty_max=self.rollout_deep_empty_max)
+        if self.rollout_deep_empty_max is not None:                         # (two layers, no stages: check_options has seen to it)
+            return self.rollout_adaptive_launch(self.rollout_deep_empty_max, backed=bool(self.backed_targets),
+                                                from_start=from_start and self.start is not None)
         if self.stage_tiles:                                                # one entry point: from `start`, all zero while restarts are off
             self._restart_state()
             if not from_start:
@@ -308,6 +325,32 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         holds the network's V of the chosen afterstates, so the learners read the records as they read rollout()'s."""
         layers = check_layers(layers)
         return self._launch("pulse_tfe_nt_rollout_search", self._rollout_struct(), layers)
+
+    def rollout_adaptive_launch(self, deep_empty_max, backed=False, from_start=False):
+        """pulse_tfe_nt_rollout_adaptive alone, whatever the agent's attributes: rollout_search_launch's games and records at two
+        layers on the boards with at most `deep_empty_max` (0..16; ValueError otherwise) empty cells and at one layer on the others.
+        backed: rollout_backed_launch's `backed` too, of the q at the depth the board chose.  from_start: the games begin on the
+        boards of `start` where usable, as rollout_from_launch's do.  The moves at each depth are ADDED to `depth_stats`.  Allocates
+        `backed`, `start` and `depth_stats` where the agent has none, and zeroes nothing."""
+        deep_empty_max = check_deep_empty_max(deep_empty_max)
+        if deep_empty_max is None:
+            raise ValueError("deep_empty_max must be None or an int in 0..16")
+        if from_start:
+            self._restart_state()
+        return self._launch("pulse_tfe_nt_rollout_adaptive", self._rollout_struct(), deep_empty_max,
+                            self._per_move("backed").data_ptr() if backed else None, self.start.data_ptr() if from_start else None,
+                            self._depth_words().data_ptr())
+
+    def rollout_depth_summary(self, clear=True) -> dict:
+        """{"moves_deep", "moves_shallow"} (synchronises): the moves the adaptive launches since the words were last zeroed searched
+        two layers and one layer deep -- rollout_adaptive_launch's and the adaptive evaluations' alike.  clear: `depth_stats` is zeroed.
+        ValueError if no adaptive launch has run."""
+        if self.depth_stats is None:
+            raise ValueError("no adaptive launch has run: the agent holds no depth_stats")
+        deep, shallow = self.depth_stats.cpu().tolist()
+        if clear:
+            self.depth_stats.zero_()
+        return dict(moves_deep=deep, moves_shallow=shallow)
 
     def rollout_backed_launch(self, layers):
         """pulse_tfe_nt_rollout_backed alone, whatever the agent's `rollout_layers` and `backed_targets`: rollout_search_launch's games
@@ -426,7 +469,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         return self._search_eval_launch(0, None)(o)
 
     # ------------------------------------------------------------------ expectimax search (DESIGN.md sections 13.1, 13.4 and 13.11)
-    depth_stats = None                                                     # int64[2] on the device, from the first adaptive evaluation: moves two layers deep, one layer deep
+    depth_stats = None                                                     # int64[2] on the device, from the first adaptive launch: moves two layers deep, one layer deep
 
     def _search_options(self, layers, deep_empty_max=None):
         """(layers, deep_empty_max) as ints (deep_empty_max: or None), or check_options' ValueError of what the search refuses: a depth
@@ -548,7 +591,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
 
     def save(self, path):
         """The non-zero weights and what a continued run needs as an .npz (write_checkpoint); with tc, E and A too.  `rollout_layers`,
-        `backed_targets`, `restart_fraction`, `restart_min_length`, `continue_games` and `eval_max_steps` are not saved: they say how
+        `backed_targets`, `restart_fraction`, `restart_min_length`, `continue_games`, `eval_max_steps` and `rollout_deep_empty_max` are not saved: they say how
         rounds are played, learnt and evaluated, not what the network is; nor are `start` and the carries of continued games."""
         write_checkpoint(path, self.weights(), self.tuples, symmetric=int(self.symmetric), gamma=self.gamma, epsilon=self.epsilon, alpha=self.alpha,
                          max_steps=self.max_steps, seed=self.seed, board_id0=self.board_id0, round=self.round, n_games=self.n_games, lam=self.lam,

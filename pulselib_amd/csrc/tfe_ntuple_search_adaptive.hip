@@ -68,10 +68,6 @@ __global__ __launch_bounds__(kSearchBlock) void tfe_nt_play_adaptive_kernel(cons
     }
 }
 
-int check_deep_empty_max(const int32_t deep_empty_max, const char* name) {
-    return deep_empty_max >= 0 && deep_empty_max <= 16 ? 0 : fail_named(name, "deep_empty_max must be in 0..16");
-}
-
 }  // namespace
 
 extern "C" int pulse_tfe_nt_search_adaptive(const PulseTfeNtSearch* o, int32_t deep_empty_max, void* stream) {

@@ -42,6 +42,11 @@ inline int check_layers(const int32_t layers, const char* name) {
     return layers == 1 || layers == 2 ? 0 : fail_named(name, "layers must be 1 or 2");
 }
 
+// ... and the threshold beside it, as the adaptive launches take it (tfe_ntuple_search_adaptive.hip, tfe_ntuple_adaptive_rollout.hip)
+inline int check_deep_empty_max(const int32_t deep_empty_max, const char* name) {
+    return deep_empty_max >= 0 && deep_empty_max <= 16 ? 0 : fail_named(name, "deep_empty_max must be in 0..16");
+}
+
 // ... and what pulse_tfe_nt_rollout_from and pulse_tfe_nt_rollout_staged refuse of theirs, of `backed` and of `start`
 inline int check_start(const int32_t layers, const double* backed, const uint64_t* start, const char* name, const char* layers_message) {
     if (layers != 0 && layers != 1) return fail_named(name, layers_message);

@@ -25,7 +25,11 @@ and `--add-stage ROUND:TILE` splits a stage at TILE before round ROUND, the new 
 and takes the cut games up again in the next round under the new weights, so the weights move every K moves of a game instead of once
 per generation of games; the evaluations are capped at 4,096 moves, not at K, and every round's line says how many whole games
 finished since the last line, their mean score and length, and how many games the round's pick continued: the training curve of
-complete games.  Not saved either: a resumed run's games begin at their resets."""
+complete games.  Not saved either: a resumed run's games begin at their resets.  `--train-layers 2 --train-deep-empty-max E` (E in
+0..16; section 13.13; not with `--stages`) plays the rounds' own games under the search whose depth the board chooses: two chance
+layers where the board a move is made from has at most E empty cells and one elsewhere, recorded and learnt from as before; it goes
+with `--backed`, with `--continue-games --max-steps K` and with `--restart F`, which `--train-layers 2` alone does not; every round's
+line says what share of the training moves since the last line went deep.  Not saved either."""
 from __future__ import annotations
 
 import argparse
@@ -54,9 +58,9 @@ def _promotions(add_stage, first, rounds) -> dict:
 
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
         resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False, restart=0.0, restart_min_length=64, stages=(), add_stage=(),
-        continue_games=False, deep_empty_max=None):
+        continue_games=False, deep_empty_max=None, train_deep_empty_max=None):
     check_options(train_layers, backed, restart, continue_games, max_steps, bool(stages or add_stage), search=search, layers=layers,
-                  deep_empty_max=deep_empty_max, script=True)        # (refused before a device is asked for)
+                  deep_empty_max=deep_empty_max, rollout_deep_empty_max=train_deep_empty_max, script=True)     # (refused before a device is asked for)
     if resume:
         agent = NTupleTDAfterstateTFEGPU.load(resume, device)
         want = dict(n_games=tables, alpha=float(alpha), epsilon=float(epsilon), gamma=float(gamma), max_steps=max_steps, seed=seed)
@@ -69,11 +73,13 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
                                          stage_tiles=tuple(stages))
     promotions = _promotions(add_stage, agent.round, rounds)
     agent.rollout_layers, agent.backed_targets = train_layers, bool(backed)  # (no checkpoint holds them: given again on --resume)
+    agent.rollout_deep_empty_max = train_deep_empty_max
     agent.restart_fraction, agent.restart_min_length = float(restart), int(restart_min_length)
     if continue_games:                                                      # (not saved: given again on --resume; the games begin at their resets)
         agent.continue_games, agent.eval_max_steps = True, CONTINUE_EVAL_MAX_STEPS
     out(f"{agent.n_games} games per round from round {agent.round}: alpha {agent.alpha}, epsilon {agent.epsilon}, gamma {agent.gamma}, "
         f"lambda {agent.lam}, tc {agent.tc}, max_steps {agent.max_steps}, seed {agent.seed}, roll-out under {agent.rollout_layers} chance layers of search"
+        f"{'' if train_deep_empty_max is None else f' on boards with at most {train_deep_empty_max} empty cells and one on the others'}"
         f"{', learning towards the search-backed values' if agent.backed_targets else ''}"
         f"{f', games restarted at {agent.restart_fraction} of games of {agent.restart_min_length} moves or more' if agent.restart_fraction else ''}"
         f"{f', weight sets by stage from tiles {agent.stage_tiles}' if agent.stage_tiles else ''}"
@@ -108,6 +114,9 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
             st, now = agent.stats(), time.perf_counter()
             again = f"restarted {began['picked']} games from mean depth {began['mean_depth']:.1f}, " if agent.restart_fraction else ""
             rho = f", mean rho {agent.tc_summary()['mean_rho']:.4f}" if agent.tc else ""       # (of the applies since the last line)
+            if train_deep_empty_max is not None:                            # (of the roll-outs since the last line; synchronises)
+                d = agent.rollout_depth_summary()
+                rho += f", deep share {d['moves_deep'] / max(d['moves_deep'] + d['moves_shallow'], 1):.4f} of {d['moves_deep'] + d['moves_shallow']} training moves"
             if agent.continue_games:                                        # (the whole games that ended since the last line; synchronises)
                 done = agent.finished_summary()
                 again = (f"whole games finished {done['games']}: Avg final score {done['mean_score']:.1f}, Avg length {done['mean_length']:.1f}, "
@@ -115,6 +124,8 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
             out(f"Round {r}: {line}; "
                 f"training: {again if agent.continue_games else ''}Avg final score {agent.total_score.double().mean().item():.1f}, Avg length {agent.lengths.double().mean().item():.1f}, {'' if agent.continue_games else again}moves/sec {(st['moves'] - moves_before) / (now - t0):.0f}, "
                 f"skipped {st['skipped']}, clamped {st['clamped']}{rho}{under_search()}")
+            if train_deep_empty_max is not None:
+                agent.depth_stats.zero_()                                   # (an adaptive evaluation leaves its own moves there)
             moves_before, t0 = st["moves"], time.perf_counter()
     if save:
         agent.save(save)
@@ -143,6 +154,9 @@ def main(argv=None):
                     help="with --search --layers 2: two chance layers only on boards with at most E empty cells (0..16), one on the others; not with --stages")
     ap.add_argument("--train-layers", type=int, default=0, choices=[0, 1, 2],
                     help="the chance layers of search the rounds' own games are played under (0: the one-ply roll-out); not saved: give it again with --resume")
+    ap.add_argument("--train-deep-empty-max", type=int, metavar="E",
+                    help="with --train-layers 2: the rounds' games search two chance layers only on boards with at most E empty cells (0..16), one on the "
+                         "others; goes with --backed, --continue-games and --restart; not with --stages; not saved")
     ap.add_argument("--backed", action="store_true",
                     help="with --train-layers 1 or 2: learn towards the value the search backed up instead of r + gamma * V of the next record; not saved")
     ap.add_argument("--restart", type=float, default=0.0, metavar="F",
@@ -166,15 +180,19 @@ def main(argv=None):
     if args.deep_empty_max is not None:
         if not 0 <= args.deep_empty_max <= 16:
             ap.error("--deep-empty-max must be in 0..16")
+    if args.train_deep_empty_max is not None:
+        if not 0 <= args.train_deep_empty_max <= 16:
+            ap.error("--train-deep-empty-max must be in 0..16")
     try:                                                                    # (run()'s refusals, as the command line's)
         check_options(args.train_layers, args.backed, args.restart, args.continue_games, args.max_steps, bool(stages or add_stage),
-                      search=args.search, layers=args.layers, deep_empty_max=args.deep_empty_max, script=True)
+                      search=args.search, layers=args.layers, deep_empty_max=args.deep_empty_max, rollout_deep_empty_max=args.train_deep_empty_max,
+                      script=True)
     except ValueError as refused:
         ap.error(str(refused))
     agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
                 args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers, backed=args.backed,
                 restart=args.restart, restart_min_length=args.restart_min_length, stages=stages, add_stage=add_stage,
-                continue_games=args.continue_games, deep_empty_max=args.deep_empty_max)
+                continue_games=args.continue_games, deep_empty_max=args.deep_empty_max, train_deep_empty_max=args.train_deep_empty_max)
     st = agent.stats()
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
           f"{int((agent.weights_dev != 0).sum().item())} of {agent.total_weights} weights are not zero")

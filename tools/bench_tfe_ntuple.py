@@ -68,6 +68,20 @@ between its own pair of HIP events, --warmup untimed turns and then --repeats; t
 --continue-regime: instead, ONE line, {"continue_regime": ...}: section 13.5's regime one ply deep (--regime-rounds whole-game rounds)
 and a continue_games agent of --continue-max-steps moves a segment trained until it has learnt at least as many moves: the rounds, their
 summed launch time and the wall time, the whole games that finished, and both evaluations (capped at --max-steps) paired by board.
+--train-layers 2 --train-deep-empty-max E [E ...]: per B and E one more line, {"adaptive_rollout": ...}, on the
+weights the rounds left.  At E = 16 the recording launch at the adaptive depth (pulse_tfe_nt_rollout_adaptive) without and with backed
+values beside the two-layer recording launches (pulse_tfe_nt_rollout_search, pulse_tfe_nt_rollout_backed at layers = 2), the four
+alternating in the same process, each between its own pair of HIP events: medians with min and max, the ratios, and whether the new
+launch's median is inside its parent's min .. max widened by 2 %.  At any other E the recording launch without and with backed values
+beside the evaluation launch at the same E (pulse_tfe_nt_evaluate_search_adaptive) on the same boards, weights and epsilon: the ratios,
+the moves and the deep share.  Then one {"adaptive_round": ...} line per B at the first E below 16: roll-out + learn + apply with backed
+targets under one layer, under two layers and under two layers at E, each from the same weights and boards (put back, untimed, before
+every round), and the continue pick and the restart pick on the records of the last.  --adaptive-regime: instead of everything above,
+ONE line, {"adaptive_regime": ...}: section 13.5's regime with backed targets at lambda 0.5 under rollout_layers = 1 and under
+rollout_layers = 2 with rollout_deep_empty_max = 3 (--train-deep-empty-max's first value if given), with rollout_layers = 2 on every
+board between them (the two-layer backed round no regime had recorded), and the first pair again with continue_games
+in segments of --continue-max-steps moves trained until each has learnt as many moves as its whole-game twin; per regime the wall time,
+the deep share of its training moves and both evaluations, and the differences adaptive - one layer paired by board.
 max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes, 25 with deltas, 33 with backed).  Lines are also
 appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
 import argparse
@@ -549,6 +563,100 @@ def adaptive_lines(agent, torch, games, thresholds, repeats):
     return lines
 
 
+def adaptive_rollout_lines(agent, torch, thresholds, warmup, repeats):
+    """One {"adaptive_rollout": ...} line per threshold on the boards of the agent's next round, then one
+    {"adaptive_round": ...} line at the first threshold below 16"""
+    board_id0 = agent.round_board_id0()
+    common = {"games": agent.n_games, "epsilon": agent.epsilon, "trained_rounds": agent.round, "max_steps": agent.max_steps, "warmup": warmup, "repeats": repeats}
+    lines = []
+    for E in thresholds:
+        mine = (("adaptive", lambda E=E: agent.rollout_adaptive_launch(E)), ("adaptive_backed", lambda E=E: agent.rollout_adaptive_launch(E, backed=True)))
+        if E == 16:
+            parents = (("rollout_search", lambda: agent.rollout_search_launch(2)), ("rollout_backed", lambda: agent.rollout_backed_launch(2)))
+        else:
+            parents = (("evaluate_adaptive", lambda E=E: agent.evaluate_search_launch(epsilon=agent.epsilon, board_id0=board_id0, layers=2, deep_empty_max=E)),)
+        agent._depth_words().zero_()
+        seconds = _alternate(agent, torch, parents + mine, warmup, repeats, before=lambda: agent.eval_counters(clear=True))
+        deep, shallow = (x // ((warmup + repeats) * (2 if E == 16 else 3)) for x in agent.rollout_depth_summary().values())
+        t = {name: _spread(xs) for name, xs in seconds.items()}
+        line = {**common, "deep_empty_max": E, "moves": deep + shallow, "deep_share": deep / max(deep + shallow, 1), **{k + "_s": v for k, v in t.items()}}
+        if E == 16:
+            for new, old in (("adaptive", "rollout_search"), ("adaptive_backed", "rollout_backed")):
+                line[new + "_over_" + old] = t[new]["median"] / t[old]["median"]
+                line[new + "_inside_parent_min_max_plus_2_percent"] = t[old]["min"] / 1.02 <= t[new]["median"] <= t[old]["max"] * 1.02
+        else:
+            for new in ("adaptive", "adaptive_backed"):
+                line[new + "_over_evaluate"] = t[new]["median"] / t["evaluate_adaptive"]["median"]
+        lines.append({"adaptive_rollout": line})
+    below = [E for E in thresholds if E < 16]
+    if below:
+        lines.append(adaptive_round_line(agent, torch, below[0], common))
+    return lines
+
+
+def adaptive_round_line(agent, torch, E, common):
+    """roll-out + learn + apply with backed targets under one layer, two layers and two layers at E, from the same weights and boards"""
+    weights, round0, saved = agent.weights_dev.clone(), agent.round, (agent.rollout_layers, agent.backed_targets, agent.rollout_deep_empty_max)
+    rows, out = (("layers_1_backed", 1, None), ("layers_2_backed", 2, None), ("layers_2_adaptive_backed", 2, E)), {}
+    for name, layers, threshold in rows:
+        agent.rollout_layers, agent.backed_targets, agent.rollout_deep_empty_max = layers, True, threshold
+        times = []
+        for i in range(common["warmup"] + common["repeats"]):
+            agent.weights_dev.copy_(weights)
+            agent.round = round0
+            t = _timed_round(agent, torch)
+            if i >= common["warmup"]:
+                times.append(t)
+        ro, le, ap = (_spread([t[i] for t in times]) for i in range(3))
+        out[name] = {"rollout_s": ro, "learn_s": le, "apply_s": ap, "round_s": _spread([sum(t) for t in times]), "moves": int(agent.lengths.sum().item())}
+    agent.round = round0                                                    # the picks read the last records under their round's ids
+    picks = _alternate(agent, torch, (("continue_pick", agent.continue_pick_launch), ("restart_pick", lambda: agent.restart_pick_launch(0.5, 64))),
+                       common["warmup"], common["repeats"])
+    agent.weights_dev.copy_(weights)
+    agent.rollout_layers, agent.backed_targets, agent.rollout_deep_empty_max = saved
+    agent._depth_words().zero_()
+    return {"adaptive_round": {**common, "deep_empty_max": E, **out, **{k + "_s": _spread(v) for k, v in picks.items()},
+                               "adaptive_over_one_layer": out["layers_2_adaptive_backed"]["round_s"]["median"] / out["layers_1_backed"]["round_s"]["median"],
+                               "adaptive_over_two_layers": out["layers_2_adaptive_backed"]["round_s"]["median"] / out["layers_2_backed"]["round_s"]["median"]}}
+
+
+def adaptive_regime_line(torch, dev, games, rounds, eval_games, max_steps, segment, E, lam=0.5):
+    """section 13.5's regime with backed targets at lambda under one layer, under two layers and under two layers at E, the first and the last
+    also continued in segments;
+    a continued agent trains until it has learnt as many moves as its whole-game twin; the evaluations are from reset and paired by board"""
+    import time
+    import numpy as np
+    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
+    out, ev = {"games": games, "rounds": rounds, "eval_games": eval_games, "seed": 0, "max_steps": max_steps, "segment": segment, "deep_empty_max": E, "lambda": lam}, {}
+    for name, layers, threshold, continued in (("layers_1", 1, None, False), ("layers_2", 2, None, False), ("adaptive", 2, E, False),
+                                               ("layers_1_continued", 1, None, True), ("adaptive_continued", 2, E, True)):
+        agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=segment if continued else max_steps, seed=0, lam=lam)
+        agent.rollout_layers, agent.backed_targets, agent.rollout_deep_empty_max = layers, True, threshold
+        if continued:
+            agent.continue_games, agent.eval_max_steps = True, max_steps
+        target, t0 = out[name[:-len("_continued")]]["moves_learnt"] if continued else None, time.perf_counter()
+        while (agent.stats()["learnt"] < target) if continued else (agent.round < rounds):       # (synchronises once a round)
+            agent.learn_batch()
+        torch.cuda.synchronize(dev)
+        wall, st = time.perf_counter() - t0, agent.stats()
+        depth = agent.rollout_depth_summary() if threshold is not None else None
+        ev[name] = {"one_ply": agent.evaluate(n_games=eval_games, per_game=True), "search": agent.evaluate_search(n_games=eval_games, per_game=True)}
+        out[name] = {"rollout_layers": layers, "rollout_deep_empty_max": threshold, "continue_games": continued, "max_steps": agent.max_steps, "rounds": agent.round,
+                     "wall_seconds": wall, "stats": st, "moves_learnt": st["learnt"],
+                     "deep_share": None if depth is None else depth["moves_deep"] / max(depth["moves_deep"] + depth["moves_shallow"], 1),
+                     "finished": agent.finished_summary()["games"] if continued else None,
+                     **{k: {"mean": e["mean_score"], "se": e["std_score"] / e["games"] ** .5, "mean_length": e["mean_length"], "cut": e["truncated"]}
+                        for k, e in ev[name].items()}}
+        del agent
+        torch.cuda.empty_cache()
+    for mine, other in (("adaptive", "layers_1"), ("adaptive", "layers_2"), ("layers_2", "layers_1"), ("adaptive_continued", "layers_1_continued"),
+                        ("adaptive_continued", "adaptive")):
+        for k in ("one_ply", "search"):
+            d = (ev[mine][k]["total_score"] - ev[other][k]["total_score"]).astype(np.float64)
+            out[f"{k}_eval_{mine}_minus_{other}"] = {"mean": d.mean(), "se": d.std(ddof=1) / d.size ** .5}
+    return {"adaptive_regime": out}
+
+
 def lambda_line(agent, torch, lam, warmup, repeats):
     """the two learn launches on the games the agent last recorded (the agent's own lam is 0: learn() is the TD(0) launch)"""
     launches = (("learn", agent.learn), ("learn_lambda", lambda: agent.learn_lambda_launch(lam)))
@@ -659,6 +767,9 @@ def main(argv=None):
     ap.add_argument("--lambda", dest="lam", type=float, help="one more line per B: the TD(lambda) learn launch beside the TD(0) one, on the same games")
     ap.add_argument("--tc", action="store_true", help="one more line per B: the temporal-coherence learn and apply launches beside the fixed-step ones")
     ap.add_argument("--train-layers", type=int, choices=[1, 2], help="one more line per B: the recording launch under search beside the evaluation under it")
+    ap.add_argument("--train-deep-empty-max", type=int, nargs="+", metavar="E",
+                    help="with --train-layers 2: one more line per B and E, the recording launch at the adaptive depth beside its parents (E = 16) or the evaluation at E")
+    ap.add_argument("--adaptive-regime", action="store_true", help="one line instead: backed rounds under one layer and at the adaptive depth, whole games and continued (DESIGN.md section 13.13)")
     ap.add_argument("--backed", action="store_true", help="with --train-layers: two more lines per B, the backed recording launch and the backed learner beside the parent's")
     ap.add_argument("--backed-regime", action="store_true", help="one line instead: twelve rounds and paired evaluations of the four agents of DESIGN.md section 13.6")
     ap.add_argument("--restart", type=float, metavar="F", help="two more lines per B: the restarted recording launch beside its three parents, and the pick launch at this fraction")
@@ -676,6 +787,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.backed and not args.train_layers:
         ap.error("--backed needs --train-layers 1 or 2: the backed-up values are the search's")
+    if args.train_deep_empty_max and args.train_layers != 2 and not args.adaptive_regime:
+        ap.error("--train-deep-empty-max needs --train-layers 2: it says on which boards the roll-out's search looks two chance layers ahead")
+    if args.train_deep_empty_max and not all(0 <= E <= 16 for E in args.train_deep_empty_max):
+        ap.error("--train-deep-empty-max takes thresholds in 0..16")
     if args.deep_empty_max and not (args.search and args.layers == 2):
         ap.error("--deep-empty-max needs --search --layers 2: it says on which boards the search looks two chance layers ahead")
     if args.deep_empty_max and not all(0 <= E <= 16 for E in args.deep_empty_max):
@@ -687,6 +802,13 @@ def main(argv=None):
     from pulselib_amd.agents.tfe_ntuple_td_gpu import DEFAULT_TUPLES, tuple_offsets
     dev = torch.device("cuda:0")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if args.adaptive_regime:
+        line = adaptive_regime_line(torch, dev, args.games[0], args.regime_rounds, args.regime_eval_games, args.max_steps, args.continue_max_steps,
+                                    (args.train_deep_empty_max or [3])[0])
+        print(json.dumps(line), flush=True)
+        with open(args.out, "a") as fh:
+            fh.write(json.dumps(line) + "\n")
+        return
     if args.backed_regime:
         line = backed_regime_line(torch, dev, args.games[0], args.regime_rounds, args.regime_eval_games, args.max_steps)
         print(json.dumps(line), flush=True)
@@ -716,7 +838,7 @@ def main(argv=None):
                 fh.write(json.dumps(line) + "\n")
         return
     for games in args.games:
-        per_move = 33 if args.backed or args.restart else 17 if args.lam is None else 25
+        per_move = 33 if args.backed or args.restart or args.train_deep_empty_max else 17 if args.lam is None else 25
         need = (48 if args.tc else 20) * tuple_offsets(DEFAULT_TUPLES)[1] + per_move * games * args.max_steps + 64 * games
         if stage_tiles:                                                     # a second agent: the staged weights and records of its own
             need = 2 * 33 * games * args.max_steps + (48 if args.tc else 20) * (len(stage_tiles) + 2) * tuple_offsets(DEFAULT_TUPLES)[1] + 128 * games
@@ -734,7 +856,9 @@ def main(argv=None):
                 lines.append(lambda_line(agent, torch, args.lam, args.warmup, args.repeats))
             if args.tc:                                                     # likewise
                 lines.append(tc_line(agent, torch, args.lam, args.warmup, args.repeats))
-            if args.train_layers:                                           # on the weights the last state left
+            if args.train_deep_empty_max:                                   # on the weights the last state left; instead of the line of section 13.5
+                lines += adaptive_rollout_lines(agent, torch, args.train_deep_empty_max, args.warmup, args.repeats)
+            elif args.train_layers:                                         # on the weights the last state left
                 lines.append(train_rollout_line(agent, torch, args.train_layers, args.warmup, args.repeats))
             if args.backed:                                                 # likewise, then on the records of its own last launch
                 lines += backed_lines(agent, torch, args.train_layers, args.lam or 0.0, args.warmup, args.repeats)
