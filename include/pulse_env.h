@@ -1164,6 +1164,42 @@ typedef struct PulseTfeNtContinuePick {
 } PulseTfeNtContinuePick;
 int pulse_tfe_nt_continue_pick(const PulseTfeNtContinuePick* o, void* stream);
 
+/* ---- ... and rank-parallel rounds: R ranks play disjoint games of one round, each learns into its own accumulators, and the
+ * accumulators are summed before the apply launch runs, replicated, on every rank.  The learners' adds are integers, so the sum is
+ * bit for bit the accumulator of one process that played all the games.  A round touches few of the cells, so what travels is a
+ * list of the touched cells.  Opt-in: a caller that never calls these keeps every launch above unchanged.
+ *
+ * The list: int64[4 + 4 * capacity], a header {found, written, 0, 0} and then 32-byte entries {index, sum, cnt, abs}.
+ *
+ * pulse_tfe_nt_acc_pack: the header is zeroed on the stream; then every cell i < n_entries with acc[i].cnt > 0 -- cnt, not sum: a
+ * cell whose differences cancel was visited all the same -- becomes the entry {i, acc[i].sum, acc[i].cnt, acc_abs ? acc_abs[i] : 0}
+ * at a slot of its own.  found = the number of such cells; an entry whose slot is >= capacity is not written; written =
+ * min(found, capacity), set by a one-lane launch behind the first.  Nothing is written outside list[0, 4 + 4 * capacity); acc and
+ * acc_abs are only read; `stats` is not used.  The ORDER of the entries follows the order of the launch's atomics and is not
+ * defined; with found <= capacity the SET of entries is.  One returning atomic per workgroup and pass that found a live cell.
+ *
+ * pulse_tfe_nt_acc_unpack: the header's `written` is read on the device.  written > capacity: nothing is added and stats[1] +=
+ * capacity.  Otherwise, for every slot below written: an entry with index < n_entries and cnt > 0 is added -- acc[index].sum +=
+ * sum, acc[index].cnt += cnt, and with acc_abs, acc_abs[index] += abs -- by 64-bit atomics, so the lists of several ranks may be
+ * added by launches that run together; any other entry adds nothing.  stats[0] += entries added, stats[1] += entries refused.  The
+ * list is only read.
+ *
+ * n_entries covers all stages of a network with weight sets by stage.  Zero-initialise the struct: reserved0 must be 0.  sizeof == 56.
+ *
+ * PULSE_EINVAL, before anything is launched: null options, n_entries outside 1..2^32, acc null or not 16-byte aligned, acc_abs not
+ * 8-byte aligned, capacity 0, list null or not 32-byte aligned, stats null (unpack) or not 8-byte aligned, reserved0 not 0. */
+typedef struct PulseTfeNtAccList {
+    uint64_t n_entries;                 /* accumulator cells covered: total weights, all stages */
+    int64_t* acc;                       /* int64[n_entries][2] = {sum, cnt}, 16-byte aligned; pack: read, unpack: added to */
+    int64_t* acc_abs;                   /* int64[n_entries] or NULL; pack: read, unpack: added to */
+    uint64_t capacity;                  /* entries the list has room for, >= 1 */
+    int64_t* list;                      /* int64[4 + 4 * capacity], 32-byte aligned; pack: written, unpack: read */
+    int64_t* stats;                     /* unpack only, int64[2], ADDED TO: [0] entries added, [1] entries refused */
+    int64_t reserved0;
+} PulseTfeNtAccList;
+int pulse_tfe_nt_acc_pack(const PulseTfeNtAccList* o, void* stream);
+int pulse_tfe_nt_acc_unpack(const PulseTfeNtAccList* o, void* stream);
+
 /* ---- the learner's action selection (environments/Poker/Player.py:178-253) ---------------------
  * PokerQNetwork.network in eval mode: Linear(state_dim,128) GELU Linear(128,128) GELU [Dropout] Linear(128,64)
  * GELU [Dropout] Linear(64,32) GELU Linear(32,n_actions) (:189-201).  Weights are the module's own tensors:

@@ -195,6 +195,11 @@ class TfeNtContinuePick(C.Structure):                                       # ga
         (n, C.c_void_p) for n in ("keys", "steps", "lengths", "total_score", "start", "carry_score", "carry_moves", "finished")]
 
 
+class TfeNtAccList(C.Structure):                                            # rank-parallel rounds: the sparse accumulator exchange
+    _fields_ = [("n_entries", C.c_uint64), ("acc", C.c_void_p), ("acc_abs", C.c_void_p), ("capacity", C.c_uint64), ("list", C.c_void_p),
+                ("stats", C.c_void_p), ("reserved0", C.c_int64)]
+
+
 class TfeNtStages(C.Structure):                                           # weight sets by tile stage: beside the struct of a *_staged entry point
     _fields_ = [("n_stages", C.c_int32), ("threshold", C.c_uint8 * 4), ("reserved0", C.c_int64)]
 
@@ -299,6 +304,8 @@ SYMBOLS = {
     "pulse_tfe_nt_evaluate_staged": (C.c_int, [_P, _P, _I32, _P]),
     "pulse_tfe_nt_search_staged": (C.c_int, [_P, _P, _P]),
     "pulse_tfe_nt_continue_pick": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_acc_pack": (C.c_int, [_P, _P]),
+    "pulse_tfe_nt_acc_unpack": (C.c_int, [_P, _P]),
     "pulse_qtable_select": (C.c_int, [_P, _P, _I32, _I32, C.c_double, _U64, _U64, _U64, _P, _P, _P]),
     "pulse_qtable_update": (C.c_int, [_P, _P, _U64, _P, _P, _P, _P, _P, _I32, _I32, C.c_double, C.c_double, _P]),
     "pulse_qtable_rollout_step": (C.c_int, [_P, _P, _U64, _P, _P, _I32, _I32, C.c_double, C.c_double, C.c_double, _U64, _U64, _U64, _U64, _U64,

@@ -16,7 +16,8 @@ below, vectorised over boards, state it exactly:
   weight sets by tile stage (13.9): the stages travel on `tuples` (`with_stages`), so every mirror reads and adds by stage;
     `stage_of_keys_on_host` states the stage, `split_stage_tiles` and `add_stage_on_host` the promotion;
   games continued across rounds (13.10): `continue_pick_on_host`;
-  the roll-out at the adaptive depth (13.13): `search_adaptive_nt_on_host`'s q with `search_backed_on_host` of them; no mirror of its own.
+  the roll-out at the adaptive depth (13.13): `search_adaptive_nt_on_host`'s q with `search_backed_on_host` of them; no mirror of its own;
+  rank-parallel rounds (13.14): `pack_acc_on_host`, `unpack_acc_on_host`, `shard_round_board_id0`.
 Which of a round's options go together is stated once, in `check_options` (13.12), in the agent's words and in the script's."""
 from __future__ import annotations
 
@@ -472,19 +473,24 @@ def finished_summary_on_host(words) -> dict:
 
 # ------------------------------------------------------------------ which options go together
 def check_options(depth=0, backed_targets=False, restart_fraction=0.0, continue_games=False, max_steps=None, staged=False, *,
-                  search=False, layers=1, deep_empty_max=None, rollout_deep_empty_max=None, script=False):
+                  search=False, layers=1, deep_empty_max=None, rollout_deep_empty_max=None, shard=None, script=False):
     """The one statement of which options of a round and of an evaluation go together.  Of the round: `depth`, the chance layers its
     games are played under (check_rollout_layers), `backed_targets`, `restart_fraction` (check_restart_fraction), `continue_games`,
     `max_steps` (None: not asked about) and `staged`, whether the network has weight sets by stage.  Of the evaluation or the search,
     where there is one (`search`): its `layers` (check_layers) and `deep_empty_max` (check_deep_empty_max).  Of the round again:
     `rollout_deep_empty_max` (check_deep_empty_max; None: off), the threshold of a roll-out at the adaptive depth (section 13.13), which
-    is built from `start` too: with it two layers go with restarts and with continuation.  ValueError at the first
+    is built from `start` too: with it two layers go with restarts and with continuation.  `shard` (section 13.14; None: one process
+    plays the round): (n_games_total, game0, n_games), the job's games, the rank's first and how many it plays (check_shard).  A
+    sharded round goes with every learner, `tc`, stages, restarts, continuation and the search roll-outs: the exchange sits between the
+    learn and the apply launch and knows none of them, so the shard adds no row to the table.  ValueError at the first
     rule of the table below that is broken, in the agent's words (attributes and arguments) or, with `script`, in those of
     scripts/tfe_ntuple.py (flags).  Returns (depth, from_start, layers, deep_empty_max) as they are meant: from_start, the round's
     games begin on the boards of `start` (restarts or continuation); layers 0 without `search`.  A new option's rules are added here."""
     depth, restart = check_rollout_layers(depth), check_restart_fraction(restart_fraction) > 0.0
     layers, deep_empty_max = check_layers(layers) if search else 0, check_deep_empty_max(deep_empty_max)
     adaptive = check_deep_empty_max(rollout_deep_empty_max) is not None
+    if shard is not None:
+        check_shard(*shard)
     two_on_stages = "layers = 2 on an agent with stage_tiles: two chance layers are not built on stages"
     stages_two = "--stages / --add-stage do not go with two chance layers: the staged launches are one ply or one chance layer deep"
     rules = (                                                               # (broken, the agent's words, the script's), in the order they are tested
@@ -519,6 +525,54 @@ def check_options(depth=0, backed_targets=False, restart_fraction=0.0, continue_
         if broken:
             raise ValueError(words[bool(script)])
     return depth, restart or bool(continue_games), layers, deep_empty_max
+
+
+# ------------------------------------------------------------------ rank-parallel rounds
+ACC_LIST_HEADER, ACC_LIST_ENTRY = 4, 4                                                         # int64 words: {found, written, 0, 0}; {index, sum, cnt, abs}
+
+
+def check_shard(n_games_total, game0, n_games) -> tuple:
+    """A rank's share of a round as ints (n_games_total, game0, n_games): the games game0 .. game0 + n_games - 1 of the job's
+    n_games_total.  ValueError unless 0 <= game0, 1 <= n_games and game0 + n_games <= n_games_total; a bool is no count."""
+    if any(isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) for x in (n_games_total, game0, n_games)):
+        raise ValueError("a shard's n_games_total, game0 and n_games must be ints")
+    n_games_total, game0, n_games = int(n_games_total), int(game0), int(n_games)
+    if game0 < 0 or n_games < 1 or game0 + n_games > n_games_total:
+        raise ValueError("a shard must lie inside the job's games: 0 <= game0, 1 <= n_games, game0 + n_games <= n_games_total")
+    return n_games_total, game0, n_games
+
+
+def shard_round_board_id0(board_id0, round, n_games_total, game0) -> int:
+    """The id of the first board a rank plays in round `round`: board_id0 + round * n_games_total + game0.  The single process plays
+    board_id0 + round * n_games_total + g for g < n_games_total, so the rank whose games begin at game0 plays exactly its games."""
+    return int(board_id0) + int(round) * int(n_games_total) + int(game0)
+
+
+def pack_acc_on_host(acc, acc_abs=None) -> np.ndarray:
+    """pulse_tfe_nt_acc_pack's entries on the host, int64[k, 4] = {index, sum, cnt, abs} in ascending index order (the device's order
+    is not defined: compare after sorting by index): one per cell with cnt > 0 -- cnt, not sum: a cell whose differences cancel is
+    still a visit -- abs from acc_abs, 0 without one.  acc int64[W, 2], acc_abs int64[W] or None; neither is written."""
+    acc = np.asarray(acc, dtype=np.int64).reshape(-1, 2)
+    at = np.flatnonzero(acc[:, 1] > 0)
+    out = np.zeros((len(at), ACC_LIST_ENTRY), dtype=np.int64)
+    out[:, 0], out[:, 1:3] = at, acc[at]
+    if acc_abs is not None:
+        out[:, 3] = np.asarray(acc_abs, dtype=np.int64).reshape(-1)[at]
+    return out
+
+
+def unpack_acc_on_host(acc, acc_abs, entries):
+    """pulse_tfe_nt_acc_unpack's adds on the host, in place: for every entry {index, sum, cnt, abs} of int64[k, 4] with 0 <= index <
+    len(acc) (the index read as unsigned: a negative one is outside) and cnt > 0, acc[index] += {sum, cnt} and, with acc_abs,
+    acc_abs[index] += abs; any other entry adds nothing.  Entries may repeat an index.  Returns (added, refused)."""
+    entries = np.asarray(entries, dtype=np.int64).reshape(-1, ACC_LIST_ENTRY)
+    good = (entries[:, 0] >= 0) & (entries[:, 0] < len(acc)) & (entries[:, 2] > 0)
+    e = entries[good]
+    np.add.at(acc[:, 0], e[:, 0], e[:, 1])
+    np.add.at(acc[:, 1], e[:, 0], e[:, 2])
+    if acc_abs is not None:
+        np.add.at(acc_abs, e[:, 0], e[:, 3])
+    return int(good.sum()), int(len(entries) - good.sum())
 
 
 # ------------------------------------------------------------------ the learner and the apply launch

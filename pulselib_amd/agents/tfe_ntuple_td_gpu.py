@@ -28,7 +28,10 @@ agent as it was while it is off:
     into `finished`; `eval_max_steps` gives the evaluations a cap of their own;
   `rollout_deep_empty_max` = E (13.13; csrc/tfe_ntuple_adaptive_rollout.hip): with `rollout_layers` 2 the round's games are played and
     recorded by `pulse_tfe_nt_rollout_adaptive`, two layers deep on the boards with at most E empty cells and one on the others, with
-    the backed values and from `start` where those are on.
+    the backed values and from `start` where those are on;
+  `set_shard` (13.14; csrc/tfe_ntuple_exchange.hip, tfe_ntuple_ranks.py): the agent plays a rank's share of the job's games, and
+    `learn_batch` sums the ranks' accumulators between learn and apply (`exchange`: `pulse_tfe_nt_acc_pack`, an all-gather of the
+    lists, `pulse_tfe_nt_acc_unpack`), so every rank applies what one process would have applied.
 Which of them go together is `check_options`' to say (13.12), and the agent asks it before it touches anything."""
 from __future__ import annotations
 
@@ -81,8 +84,16 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     with `backed` if `backed_targets` and from `start` once a restart or continue pick has filled it: with E set, two layers go with
     `restart_fraction` > 0 and with `continue_games`.  Any other `rollout_layers` and `stage_tiles` are refused (ValueError before
     anything is touched).  The launch adds the moves at each depth to `depth_stats` (rollout_depth_summary).  The learners, the apply
-    and the pick launches read the records as they are.  It says how rounds are played, so no checkpoint holds it."""
+    and the pick launches read the records as they are.  It says how rounds are played, so no checkpoint holds it.
+    `set_shard` (a method; no shard by default: the agent as it was; section 13.14): the agent's `n_games` games are the games game0 ..
+    game0 + n_games - 1 of a job of n_games_total, played by the ranks of a torch.distributed group; `learn_batch` calls `exchange`
+    between learn() and apply(), after which `acc` (and `acc_abs`) hold the sum over the ranks, and the apply launch runs replicated:
+    weights, E, A and tc_stats are identical on all ranks and equal, bit for bit, those of one process on n_games_total games.  It
+    goes with every other option.  stats(), finished_summary(), restart_summary()'s counters, evaluate and evaluate_search are
+    job-wide then.  It says how rounds are played, so no checkpoint holds it: save() is valid from any rank, and load() followed by
+    set_shard resumes."""
     STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
+    _shard = None                                                          # set_shard's; None: one process plays the rounds
     continue_games = False                                                 # set on the agent; checked at the launch
     eval_max_steps = None                                                  # set on the agent; None: the agent's max_steps
     carry_score = carry_moves = finished = None                            # allocated by the first continue launch
@@ -265,10 +276,12 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
 
     def finished_summary(self, clear=True) -> dict:
         """finished_summary_on_host of `finished` (synchronises): the whole games that ended since the words were last zeroed, the
-        games continued by the pick launches since and the finished games that had been continued.  clear: `finished` is zeroed."""
+        games continued by the pick launches since and the finished games that had been continued.  clear: `finished` is zeroed.
+        With a shard the words are reduced over the ranks (sums, word 4 a maximum): the job's games."""
         if self.finished is None:
             raise ValueError("no continue launch has run: the agent holds no finished")
-        out = finished_summary_on_host(self.finished.cpu().tolist())
+        words = self.finished.cpu().tolist()
+        out = finished_summary_on_host(words if self._shard is None else self._shard.reduce(words, max_at=(4,)))        # (with a shard: job-wide)
         if clear:
             self.finished.zero_()
         return out
@@ -316,6 +329,9 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
         if self.start is None:
             raise ValueError("no restart launch has run: the agent holds no start")
         out = restart_summary_on_host(self.restart_stats.cpu().tolist(), self.start.cpu().numpy())
+        if self._shard is not None:                                         # job-wide: the three counters summed over the ranks
+            picked, total, started = self._shard.reduce([out["picked"], self.restart_stats[1].item(), out["started"]])
+            out = dict(picked=picked, mean_depth=total / picked if picked else 0.0, started=started)
         self.restart_stats.zero_()
         return out
 
@@ -445,6 +461,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     def learn_batch(self):
         self.rollout()
         self.learn()
+        if self._shard is not None:                                         # the ranks' accumulators summed: apply runs replicated
+            self.exchange()
         self.apply()
         if self.continue_games:                                             # the cut games' boards for the next round, the ended games into `finished`
             self.continue_pick_launch()
@@ -452,6 +470,62 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
             self.restart_pick_launch()
         self.round += 1
         return self
+
+    # ------------------------------------------------------------------ rank-parallel rounds (tfe_ntuple_ranks.py)
+    def set_shard(self, n_games_total, game0, group=None, exchange_capacity=None):
+        """The agent's games become the games game0 .. game0 + n_games - 1 of a job of `n_games_total` (its own `n_games` is its local
+        count; tfe_ntuple_ranks.shard_of gives the split of sharding.shard_tables, so uneven splits work).  group: the
+        torch.distributed group of the job's ranks (None: the default group, or without torch.distributed a world of one).
+        exchange_capacity: the entries the rank's list has room for (None: min(total_weights, n_games * max_steps * F), which a round
+        cannot overflow; a round that finds more on any rank is exchanged by a dense all-reduce, as exactly).  ValueError if the
+        games do not lie inside the job's."""
+        from .tfe_ntuple_ranks import Shard
+        self._shard = Shard(self, n_games_total, game0, group, exchange_capacity)
+        return self
+
+    def round_board_id0(self, round=None) -> int:
+        if self._shard is None:
+            return super().round_board_id0(round)
+        return self._shard.round_board_id0(self.board_id0, self.round if round is None else round)
+
+    def exchange(self) -> dict:
+        """Between learn() and apply(): `acc` (and `acc_abs`) become the sum over the ranks (tfe_ntuple_ranks.exchange_round): the
+        pack launch, an all-gather of the 4-word headers READ ON THE HOST -- the one host read per round this mode costs -- and then
+        the lists all-gathered and every other rank's added by the unpack launch, or, where a rank found more than its list holds, a
+        dense all-reduce.  Returns the round's record (exchange_summary)."""
+        if self._shard is None:
+            raise ValueError("no shard is set: the agent holds no exchange (set_shard)")
+        return self._shard.exchange(self.round)
+
+    def exchange_summary(self, clear=True) -> dict:
+        """{"rounds", "added", "refused"} (synchronises): per exchange since the last clear {"round", "path" ("sparse" or "dense"),
+        "entries" (found, per rank), "bytes" (what this rank's collectives gathered or reduced)}, and the entries the unpack launches
+        added and refused."""
+        if self._shard is None:
+            raise ValueError("no shard is set: the agent holds no exchange (set_shard)")
+        return self._shard.summary(clear)
+
+    def stats(self) -> dict:
+        """The counters by name; with a shard summed over the ranks (job-wide)."""
+        if self._shard is None:
+            return super().stats()
+        return dict(zip(self.STATS, self._shard.reduce(self.counters.cpu().tolist())))
+
+    def _evaluate_with(self, launch, n_games, epsilon, board_id0, per_game) -> dict:
+        """With a shard `n_games` (default: the job's) is the job-wide count: the rank plays its share of the boards board_id0 + g
+        (sharding.shard_tables) and the counters are reduced over the ranks -- sums, word 4 (max_score) a maximum -- so mean and
+        standard error are the single process's.  per_game: the arrays are those of the rank's OWN share."""
+        if self._shard is None:
+            return super()._evaluate_with(launch, n_games, epsilon, board_id0, per_game)
+        total = self._shard.n_games_total if n_games is None else int(n_games)
+        n, first = self._shard.eval_shard(total, self.eval_board_id0() if board_id0 is None else int(board_id0))
+        self.eval_counters(clear=True)
+        arrays = self._evaluate_launch_with(launch, n, epsilon, first, per_game) if n else None
+        out = eval_summary_on_host(self._shard.reduce(self._eval.cpu().tolist(), max_at=(4,)))
+        if per_game:
+            out["total_score"] = arrays[0].cpu().numpy() if n else np.zeros(0, dtype=np.int64)
+            out["lengths"] = arrays[1].cpu().numpy() if n else np.zeros(0, dtype=np.int32)
+        return out
 
     # ------------------------------------------------------------------ evaluation
     def _eval_struct(self):

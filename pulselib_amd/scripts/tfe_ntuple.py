@@ -29,10 +29,19 @@ complete games.  Not saved either: a resumed run's games begin at their resets. 
 0..16; section 13.13; not with `--stages`) plays the rounds' own games under the search whose depth the board chooses: two chance
 layers where the board a move is made from has at most E empty cells and one elsewhere, recorded and learnt from as before; it goes
 with `--backed`, with `--continue-games --max-steps K` and with `--restart F`, which `--train-layers 2` alone does not; every round's
-line says what share of the training moves since the last line went deep.  Not saved either."""
+line says what share of the training moves since the last line went deep.  Not saved either.  `--ranks R` (section 13.14) plays
+every round on R ranks, one fresh process and one device each (or run the module under torch.distributed.run, which sets RANK and
+WORLD_SIZE): `--tables` and `--eval-games` are the job's counts, every rank plays its share of the same boards, the ranks' accumulators
+are summed between the learn and the apply launch (a sparse list of the touched cells; one host read per round), and the weights
+stay identical on all ranks and equal to those of one process -- exactly.  Rank 0 prints and saves; the training scores of a line are
+rank 0's share, every other number is the job's.  `--ranks-one-device` puts all ranks on device 0 over gloo: a rehearsal of the
+protocol, not of its speed.  `--resume` with `--ranks` takes the file's weights and round; the file's n_games is the saving rank's share."""
 from __future__ import annotations
 
 import argparse
+import os
+import subprocess
+import sys
 import time
 
 import torch
@@ -58,11 +67,15 @@ def _promotions(add_stage, first, rounds) -> dict:
 
 def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0, max_steps=4096, eval_every=1, eval_games=None, save=None,
         resume=None, out=print, search=False, lam=0.0, tc=False, layers=1, train_layers=0, backed=False, restart=0.0, restart_min_length=64, stages=(), add_stage=(),
-        continue_games=False, deep_empty_max=None, train_deep_empty_max=None):
+        continue_games=False, deep_empty_max=None, train_deep_empty_max=None, shard=False):
     check_options(train_layers, backed, restart, continue_games, max_steps, bool(stages or add_stage), search=search, layers=layers,
                   deep_empty_max=deep_empty_max, rollout_deep_empty_max=train_deep_empty_max, script=True)     # (refused before a device is asked for)
+    job_tables, game0 = tables, 0
+    if shard:                                                               # (torch.distributed is initialised: main's _join_ranks)
+        from ..agents.tfe_ntuple_ranks import shard_of
+        tables, game0 = shard_of(job_tables)
     if resume:
-        agent = NTupleTDAfterstateTFEGPU.load(resume, device)
+        agent = NTupleTDAfterstateTFEGPU.load(resume, device, n_games=tables if shard else None)
         want = dict(n_games=tables, alpha=float(alpha), epsilon=float(epsilon), gamma=float(gamma), max_steps=max_steps, seed=seed)
         differ = {k: (getattr(agent, k), v) for k, v in want.items() if getattr(agent, k) != v}
         if differ:
@@ -71,13 +84,15 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
         _promotions(add_stage, 0, rounds)                                   # (refused before a device is asked for)
         agent = NTupleTDAfterstateTFEGPU(device, tables, gamma=gamma, epsilon=epsilon, alpha=alpha, max_steps=max_steps, seed=seed, lam=lam, tc=tc,
                                          stage_tiles=tuple(stages))
+    if shard:
+        agent.set_shard(job_tables, game0)
     promotions = _promotions(add_stage, agent.round, rounds)
     agent.rollout_layers, agent.backed_targets = train_layers, bool(backed)  # (no checkpoint holds them: given again on --resume)
     agent.rollout_deep_empty_max = train_deep_empty_max
     agent.restart_fraction, agent.restart_min_length = float(restart), int(restart_min_length)
     if continue_games:                                                      # (not saved: given again on --resume; the games begin at their resets)
         agent.continue_games, agent.eval_max_steps = True, CONTINUE_EVAL_MAX_STEPS
-    out(f"{agent.n_games} games per round from round {agent.round}: alpha {agent.alpha}, epsilon {agent.epsilon}, gamma {agent.gamma}, "
+    out(f"{f'rank 0 of a job of {job_tables} games per round: ' if shard else ''}{agent.n_games} games per round from round {agent.round}: alpha {agent.alpha}, epsilon {agent.epsilon}, gamma {agent.gamma}, "
         f"lambda {agent.lam}, tc {agent.tc}, max_steps {agent.max_steps}, seed {agent.seed}, roll-out under {agent.rollout_layers} chance layers of search"
         f"{'' if train_deep_empty_max is None else f' on boards with at most {train_deep_empty_max} empty cells and one on the others'}"
         f"{', learning towards the search-backed values' if agent.backed_targets else ''}"
@@ -132,8 +147,33 @@ def run(device, rounds, tables=65536, alpha=1.0, epsilon=0.0, gamma=1.0, seed=0,
     return agent
 
 
+def _spawn_ranks(argv, ranks) -> int:
+    """`ranks` fresh processes of this module with `argv`, rank r with RANK = LOCAL_RANK = r; the largest exit status."""
+    import socket
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env = dict(os.environ, WORLD_SIZE=str(ranks), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    children = [subprocess.Popen([sys.executable, "-m", "pulselib_amd.scripts.tfe_ntuple"] + list(argv), env=dict(env, RANK=str(r), LOCAL_RANK=str(r)))
+                for r in range(ranks)]
+    return max(abs(c.wait()) for c in children)
+
+
+def _join_ranks(one_device):
+    """This process as the rank RANK of WORLD_SIZE (set by _spawn_ranks or torch.distributed.run): the group initialised -- gloo with
+    all ranks on device 0, else nccl (RCCL) with rank r on device LOCAL_RANK -- and (the device, the rank)."""
+    from ..agents.tfe_ntuple_ranks import init_ranks
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    device = torch.device("cuda", 0 if one_device else int(os.environ.get("LOCAL_RANK", rank)))
+    torch.cuda.set_device(device)
+    init_ranks("gloo" if one_device else "nccl", rank, world)
+    return device, rank
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--ranks", type=int, default=1, metavar="R", help="play every round on R ranks, one process and one device each; --tables is the job's count")
+    ap.add_argument("--ranks-one-device", action="store_true", help="with --ranks: all ranks on device 0 over gloo (a rehearsal of the protocol)")
     ap.add_argument("--tables", type=int, default=65536, help="games per round (one update of the weights per round)")
     ap.add_argument("--rounds", type=int, default=16)
     ap.add_argument("--alpha", type=float, default=1.0, help="a weight moves by alpha / F of the mean temporal difference of its visits")
@@ -189,11 +229,23 @@ def main(argv=None):
                       script=True)
     except ValueError as refused:
         ap.error(str(refused))
-    agent = run(torch.device("cuda"), args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
-                args.eval_games, args.save, args.resume, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers, backed=args.backed,
+    device, rank, sharded = torch.device("cuda"), 0, "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1
+    if args.ranks < 1 or (args.ranks_one_device and args.ranks < 2 and not sharded):
+        ap.error("--ranks must be positive, and --ranks-one-device needs --ranks 2 or more")
+    if args.ranks > 1 and not sharded:                                      # the parent: one fresh process per rank, and nothing else
+        sys.exit(_spawn_ranks(sys.argv[1:] if argv is None else argv, args.ranks))
+    if sharded:
+        device, rank = _join_ranks(args.ranks_one_device)
+    quiet = (lambda *a: None) if rank else print                            # rank 0 prints and saves
+    agent = run(device, args.rounds, args.tables, args.alpha, args.epsilon, args.gamma, args.seed, args.max_steps, args.eval_every,
+                args.eval_games, None if rank else args.save, args.resume, out=quiet, shard=sharded, search=args.search, lam=args.lam, tc=args.tc, layers=args.layers, train_layers=args.train_layers, backed=args.backed,
                 restart=args.restart, restart_min_length=args.restart_min_length, stages=stages, add_stage=add_stage,
                 continue_games=args.continue_games, deep_empty_max=args.deep_empty_max, train_deep_empty_max=args.train_deep_empty_max)
     st = agent.stats()
+    if sharded:
+        torch.distributed.destroy_process_group()
+    if rank:
+        return
     print(f"{agent.round * args.tables} games in {agent.round} rounds, {st['moves']} moves, alpha {args.alpha}, epsilon {args.epsilon}: "
           f"{int((agent.weights_dev != 0).sum().item())} of {agent.total_weights} weights are not zero")
 

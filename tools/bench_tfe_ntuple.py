@@ -82,6 +82,15 @@ rollout_layers = 2 with rollout_deep_empty_max = 3 (--train-deep-empty-max's fir
 board between them (the two-layer backed round no regime had recorded), and the first pair again with continue_games
 in segments of --continue-max-steps moves trained until each has learnt as many moves as its whole-game twin; per regime the wall time,
 the deep share of its training moves and both evaluations, and the differences adaptive - one layer paired by board.
+--exchange: instead of everything above, two lines, {"exchange": ...}, in a single process on the default
+network with 4,096 games (--games' first value if given): at max_steps 64 and at whole games (--max-steps).  Per turn a real roll-out
+and learn launch (untimed), then, each between its own pair of HIP events: the pack launch (pulse_tfe_nt_acc_pack, the list at its
+default capacity) twice -- pack_first is the first reader of the accumulators after the learn launch's adds, pack reads them as the apply
+launch does, behind a launch that has just read them --, the unpack launch of that list into a second, zeroed accumulator (pulse_tfe_nt_acc_unpack), and the apply launch, the
+yardstick: the pack reads the bytes the apply launch reads.  The entries found, the medians with min and max, and the ratios to the
+apply launch measured in the same run.  --exchange-ranks 2 adds one line, {"exchange_ranks": ...}: the wall time of --regime-rounds
+rounds at max_steps 64 in one process beside the same rounds on two gloo ranks that share device 0 -- a REHEARSAL of the protocol: two
+ranks on one device say nothing about scaling -- with the paths taken, the entries per rank and the bytes moved per round.
 max_steps is --max-steps (4,096; the per-move buffers are B x max_steps x 17 bytes, 25 with deltas, 33 with backed).  Lines are also
 appended to profiles/tfe_mc/bench_tfe_ntuple.jsonl.  Nothing is asserted about the rates."""
 import argparse
@@ -657,6 +666,103 @@ def adaptive_regime_line(torch, dev, games, rounds, eval_games, max_steps, segme
     return {"adaptive_regime": out}
 
 
+def exchange_line(torch, dev, games, max_steps, warmup, repeats):
+    """the pack launch, the unpack launch into a second, zeroed accumulator and the apply launch on the accumulators a real learn launch
+    left, each between its own pair of HIP events, in the same run"""
+    from pulselib_amd import _native
+    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
+    agent = NTupleTDAfterstateTFEGPU(dev, games, max_steps=max_steps, seed=0).set_shard(games, 0)
+    side = agent._shard.side
+    second, stats = torch.zeros_like(agent.acc), torch.zeros(2, dtype=torch.int64, device=dev)
+    seconds, found, packed = {"pack_first": [], "pack": [], "unpack": [], "apply": []}, [], 0
+    for turn in range(warmup + repeats):
+        agent.rollout()
+        agent.learn()
+        second.zero_()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        ev[4].record()
+        side.pack()                                                         # the first reader of acc after the learn launch's scattered adds ...
+        ev[0].record()
+        words = side.pack()                                                 # ... and the same launch again, as the apply launch finds acc: just read
+        ev[1].record()
+        o = _native.TfeNtAccList()
+        o.n_entries, o.acc, o.capacity, o.list, o.stats = agent.total_weights, second.data_ptr(), side.capacity, words.data_ptr(), stats.data_ptr()
+        agent._launch("pulse_tfe_nt_acc_unpack", o)
+        ev[2].record()
+        agent.apply()
+        ev[3].record()
+        agent.round += 1
+        ev[3].synchronize()
+        packed += int(words[0].item())
+        if turn >= warmup:
+            for i, k in enumerate(("pack", "unpack", "apply")):
+                seconds[k].append(ev[i].elapsed_time(ev[i + 1]) * 1e-3)
+            seconds["pack_first"].append(ev[4].elapsed_time(ev[0]) * 1e-3)
+            found.append(int(words[0].item()))
+    assert stats.tolist() == [packed, 0], (stats.tolist(), packed)         # every entry of a packed list is a good one, and all were added
+    spread = {k + "_s": _spread(v) for k, v in seconds.items()}
+    line = {"games": games, "max_steps": max_steps, "weights": agent.total_weights, "capacity": side.capacity, "warmup": warmup, "repeats": repeats,
+            "entries_found": _spread(found), "list_bytes": 32 * (1 + max(found)), "acc_bytes": 16 * agent.total_weights, **spread,
+            "pack_first_over_apply": spread["pack_first_s"]["median"] / spread["apply_s"]["median"],
+            "pack_over_apply": spread["pack_s"]["median"] / spread["apply_s"]["median"],
+            "unpack_over_apply": spread["unpack_s"]["median"] / spread["apply_s"]["median"], "refused": stats.tolist()[1]}
+    del agent, second, side
+    torch.cuda.empty_cache()
+    return {"exchange": line}
+
+
+def _exchange_rounds(torch, dev, n_games, games, game0, max_steps, rounds):
+    """(wall seconds of `rounds` rounds after one untimed, the agent): `n_games` games of a job of `games`, sharded where they are fewer"""
+    import time
+    from pulselib_amd.agents import NTupleTDAfterstateTFEGPU
+    agent = NTupleTDAfterstateTFEGPU(dev, n_games, max_steps=max_steps, seed=0)
+    if n_games != games:
+        agent.set_shard(games, game0)
+    agent.learn_batch()
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    for _ in range(rounds):
+        agent.learn_batch()
+    torch.cuda.synchronize(dev)
+    return time.perf_counter() - t0, agent
+
+
+def _exchange_rank(rank, world, port, games, max_steps, rounds, out):
+    import torch
+    import torch.distributed as dist
+    from pulselib_amd.agents import tfe_ntuple_ranks as ranks
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    ranks.init_ranks("gloo", rank, world)
+    try:
+        n_games, game0 = ranks.shard_of(games)
+        wall, agent = _exchange_rounds(torch, torch.device("cuda:0"), n_games, games, game0, max_steps, rounds)
+        out[rank] = {"wall_s": wall, "rounds": agent.exchange_summary()["rounds"][1:], "weights_nonzero": int((agent.weights_dev != 0).sum().item()),
+                     "weights_sum": float(agent.weights_dev.double().sum().item())}
+    finally:
+        dist.destroy_process_group()
+
+
+def exchange_ranks_line(torch, dev, games, max_steps, rounds, world):
+    """one process on `games` games beside `world` gloo ranks on the same device and the same games: a rehearsal, not a scaling number"""
+    import socket
+    import torch.multiprocessing as mp
+    wall, agent = _exchange_rounds(torch, dev, games, games, 0, max_steps, rounds)
+    single = {"wall_s": wall, "weights_nonzero": int((agent.weights_dev != 0).sum().item()), "weights_sum": float(agent.weights_dev.double().sum().item())}
+    del agent
+    torch.cuda.empty_cache()
+    with socket.socket() as sock:
+        sock.bind(("127.0.0.1", 0))
+        port = sock.getsockname()[1]
+    out = mp.Manager().dict()
+    mp.spawn(_exchange_rank, args=(world, port, games, max_steps, rounds, out), nprocs=world, join=True)
+    got = [out[r] for r in range(world)]
+    same = all(g["weights_nonzero"] == single["weights_nonzero"] and g["weights_sum"] == single["weights_sum"] for g in got)
+    return {"exchange_ranks": {"rehearsal": "all ranks share device 0 over gloo (host tensors): says nothing about scaling", "games": games, "max_steps": max_steps,
+                               "rounds": rounds, "world": world, "single_process": single, "ranks_wall_s": [g["wall_s"] for g in got],
+                               "paths": [r["path"] for r in got[0]["rounds"]], "entries_per_rank": [r["entries"] for r in got[0]["rounds"]],
+                               "bytes_per_round": [r["bytes"] for r in got[0]["rounds"]], "weights_equal_single_process": same}}
+
+
 def lambda_line(agent, torch, lam, warmup, repeats):
     """the two learn launches on the games the agent last recorded (the agent's own lam is 0: learn() is the TD(0) launch)"""
     launches = (("learn", agent.learn), ("learn_lambda", lambda: agent.learn_lambda_launch(lam)))
@@ -781,6 +887,8 @@ def main(argv=None):
     ap.add_argument("--continue-regime", action="store_true", help="one line instead: twelve whole-game rounds beside continued rounds of --continue-max-steps moves to the same moves learnt")
     ap.add_argument("--continue-max-steps", type=int, default=64, metavar="K", help="with --continue-games / --continue-regime: the segment length")
     ap.add_argument("--continue-rounds", type=int, default=16, help="with --continue-games: the continued rounds played before the picks are timed")
+    ap.add_argument("--exchange", action="store_true", help="two lines instead: the pack and unpack launches of the accumulator exchange beside the apply launch (DESIGN.md section 13.14)")
+    ap.add_argument("--exchange-ranks", type=int, default=0, metavar="R", help="with --exchange: one more line, rounds on R gloo ranks sharing device 0 beside one process (a rehearsal)")
     ap.add_argument("--regime-rounds", type=int, default=12)
     ap.add_argument("--regime-eval-games", type=int, default=2048)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tfe_mc", "bench_tfe_ntuple.jsonl"))
@@ -802,6 +910,16 @@ def main(argv=None):
     from pulselib_amd.agents.tfe_ntuple_td_gpu import DEFAULT_TUPLES, tuple_offsets
     dev = torch.device("cuda:0")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    if args.exchange:
+        games = args.games[0] if "--games" in (sys.argv if argv is None else argv) else 4096
+        lines = [exchange_line(torch, dev, games, ms, args.warmup, args.repeats) for ms in (64, args.max_steps)]
+        if args.exchange_ranks > 1:
+            lines.append(exchange_ranks_line(torch, dev, games, 64, args.regime_rounds, args.exchange_ranks))
+        for line in lines:
+            print(json.dumps(line), flush=True)
+            with open(args.out, "a") as fh:
+                fh.write(json.dumps(line) + "\n")
+        return
     if args.adaptive_regime:
         line = adaptive_regime_line(torch, dev, args.games[0], args.regime_rounds, args.regime_eval_games, args.max_steps, args.continue_max_steps,
                                     (args.train_deep_empty_max or [3])[0])
