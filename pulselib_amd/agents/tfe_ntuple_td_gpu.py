@@ -89,8 +89,8 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     game0 + n_games - 1 of a job of n_games_total, played by the ranks of a torch.distributed group; `learn_batch` calls `exchange`
     between learn() and apply(), after which `acc` (and `acc_abs`) hold the sum over the ranks, and the apply launch runs replicated:
     weights, E, A and tc_stats are identical on all ranks and equal, bit for bit, those of one process on n_games_total games.  It
-    goes with every other option.  stats(), finished_summary(), restart_summary()'s counters, evaluate and evaluate_search are
-    job-wide then.  It says how rounds are played, so no checkpoint holds it: save() is valid from any rank, and load() followed by
+    goes with every other option.  stats(), finished_summary(), restart_summary()'s counters, rollout_depth_summary(), evaluate and
+    evaluate_search -- its moves_deep / moves_shallow too -- are job-wide then: summed over the ranks (Shard.reduce).  It says how rounds are played, so no checkpoint holds it: save() is valid from any rank, and load() followed by
     set_shard resumes."""
     STATS, EVAL_SUMMARY = STATS, EVAL_SUMMARY
     _shard = None                                                          # set_shard's; None: one process plays the rounds
@@ -360,13 +360,18 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
     def rollout_depth_summary(self, clear=True) -> dict:
         """{"moves_deep", "moves_shallow"} (synchronises): the moves the adaptive launches since the words were last zeroed searched
         two layers and one layer deep -- rollout_adaptive_launch's and the adaptive evaluations' alike.  clear: `depth_stats` is zeroed.
-        ValueError if no adaptive launch has run."""
+        With a shard the two words are summed over the ranks: the job's moves.  ValueError if no adaptive launch has run."""
         if self.depth_stats is None:
             raise ValueError("no adaptive launch has run: the agent holds no depth_stats")
-        deep, shallow = self.depth_stats.cpu().tolist()
+        deep, shallow = self._depth_read()
         if clear:
             self.depth_stats.zero_()
         return dict(moves_deep=deep, moves_shallow=shallow)
+
+    def _depth_read(self) -> list:
+        """`depth_stats` on the host (synchronises); with a shard summed over the ranks, as stats() is (job-wide)."""
+        words = self.depth_stats.cpu().tolist()
+        return words if self._shard is None else self._shard.reduce(words)
 
     def rollout_backed_launch(self, layers):
         """pulse_tfe_nt_rollout_backed alone, whatever the agent's `rollout_layers` and `backed_targets`: rollout_search_launch's games
@@ -619,7 +624,7 @@ class NTupleTDAfterstateTFEGPU(_TFEGamesGPU):
             self._depth_words().zero_()
         out = self._evaluate_with(self._search_eval_launch(layers, deep_empty_max), n_games, epsilon, board_id0, per_game)
         if deep_empty_max is not None:
-            out["moves_deep"], out["moves_shallow"] = self.depth_stats.cpu().tolist()
+            out["moves_deep"], out["moves_shallow"] = self._depth_read()   # (with a shard: job-wide, as the summary is)
         return out
 
     # ------------------------------------------------------------------ read-back (the only syncs) and the checkpoint

@@ -15,8 +15,8 @@ import pytest
 from pulselib_amd.sharding import shard_tables
 from tests.native_args import remarks
 from tests.tfe_host import rollout_nt_on_host
-from tests.tfe_nt_ranks_support import (EPSILON, FIELDS, GAMES, GAMMA, LAM, MAX_STEPS, PACK, ROUNDS, SPLITS, STRUCT, TUPLES, UNPACK, assert_list_refusals, by_index,
-                                        list_words)
+from tests.tfe_nt_ranks_support import (ADAPTIVE_REHEARSED, DEEP_EMPTY_MAX, EPSILON, EVAL_GAMES, FIELDS, GAMES, GAMMA, GROWN_FROM, GROWN_TILE, LAM, MAX_STEPS, PACK,
+                                        RESTART, ROUNDS, SPLITS, STAGE_TILES, STRUCT, TUPLES, UNPACK, assert_list_refusals, by_index, list_words)
 from tests.tfe_nt_support import BOARD_ID0, ROOT, SEED, assert_exports, assert_no_scratch
 from tests.tfe_nt_support import nt as _nt
 
@@ -52,6 +52,32 @@ def test_pack_and_unpack_round_trip_on_the_host():
     assert nt.unpack_acc_on_host(acc2, ab2, bad) == (0, 5) and np.array_equal(acc2, kept[0]) and np.array_equal(ab2, kept[1])
     assert nt.unpack_acc_on_host(acc2, ab2, np.vstack([bad, [[3999, -4, 1, 4]]])) == (1, 5) and acc2[3999].tolist() == [kept[0][3999, 0] - 4, kept[0][3999, 1] + 1]
     assert nt.unpack_acc_on_host(acc2, ab2, np.zeros((0, 4), dtype=np.int64)) == (0, 0)
+
+
+def test_the_synthetic_buffers_of_the_device_tests():
+    """tests/tfe_nt_ranks_support.py's buffers for the kernels' loops, at a cap of 24 workgroups: the tiles hold what their docstring
+    says, the mirrors round-trip them, and the contended list's refusals are counted"""
+    from tests.tfe_nt_ranks_support import BLOCK, DEAD, TILE, TINY, TINY_PATTERNS, contended_entries, multi_pass_accumulators, passes, tiny_accumulators
+    nt, cap = _nt(), 24
+    acc, ab, tiles = multi_pass_accumulators(cap)
+    n = len(acc)
+    assert n == (2 * cap + 1) * TILE + 517 and passes(n, TILE, cap) == 3 and [len(range(b, 2 * cap + 2, cap)) for b in (0, 1, 2, cap - 1)] == [3, 3, 2, 2]
+    e = nt.pack_acc_on_host(acc, ab)
+    per_tile = np.bincount(e[:, 0] // TILE, minlength=2 * cap + 2)
+    assert {t: int(per_tile[t]) for t in tiles} == tiles and {0, n - 1} <= set(e[:, 0].tolist()) and (e[:, 1] < 0).any() and (e[:, 2] > 0).all()
+    dead = np.flatnonzero((acc[:, 1] <= 0) & (acc[:, 0] != 0))
+    assert len(dead) > 500 and sorted(set(map(tuple, acc[dead].tolist()))) == sorted(DEAD) and np.isin(dead // TILE, [cap, 1, 2 * cap + 1]).sum() >= 4
+    acc2, ab2 = np.zeros_like(acc), np.zeros_like(ab)
+    assert nt.unpack_acc_on_host(acc2, ab2, e) == (len(e), 0) and np.array_equal(nt.pack_acc_on_host(acc2, ab2), e)
+    for n in TINY:
+        for which in TINY_PATTERNS:
+            acc, ab = tiny_accumulators(n, which, 3 * TILE)
+            assert len(nt.pack_acc_on_host(acc[:n], ab[:n])) == dict(all=n, last=1, first=1, none=0)[which] and (acc[n:, 1] > 0).all()
+    k = 2 * cap * BLOCK + 77
+    entries, n_bad = contended_entries(k, 5000, np.random.default_rng(8))
+    assert passes(k, BLOCK, cap) == 3 and nt.unpack_acc_on_host(np.zeros((5000, 2), dtype=np.int64), None, entries) == (k - n_bad, n_bad)
+    hot = np.bincount(entries[:, 0][(entries[:, 0] >= 0) & (entries[:, 0] < 5000)], minlength=5000)[[0, 1234, 2500, 4999]]
+    assert (hot > k // 40).all() and (entries[:, 0] == 5000).any() and (entries[:, 0] > 5000).any() and (entries[:, 0] < 0).any() and (entries[:, 2] == 0).any() and (entries[:, 2] < 0).any()
 
 
 def test_the_shards_board_ids_are_the_single_process_s():
@@ -116,6 +142,90 @@ def test_the_shards_accumulators_sum_to_the_single_run_s():
             assert all(len(s) for s in shards)
             assert sum(len(s) for s in shards) > len(rec["single"]), (r, split)       # some cell is met by two shards: the adds overlap
     assert rounds[1]["moved"] > rounds[0]["moved"]                                  # (round 1 played on round 0's weights)
+
+
+# ------------------------------------------------------------------ the regimes of the device's sharded cases, on the host
+# tests/test_tfe_nt_ranks_gpu.py asserts "> 0" of what a case is there for -- boards picked and started, moves at both depths, weights in
+# two stages.  The host mirrors play the same 13 games here, so those hold by the constants of tests/tfe_nt_ranks_support.py and are not
+# tuned on the device.
+def _seeds():
+    nt = _nt()
+    return SEED, SEED ^ nt.AGENT_KEY, SEED ^ nt.TIE_KEY
+
+
+def test_the_restart_case_picks_and_starts_boards():
+    """TD(0) from zero weights, restart_fraction .5, restart_min_length 8: rounds 0 and 1 on the host.  Both pick boards, and round 1
+    begins games on the boards round 0 picked."""
+    from tests.tfe_restart_host import rollout_from_on_host, usable_on_host
+    nt = _nt()
+    W, F = nt.tuple_offsets(TUPLES)[1], 8 * len(TUPLES)
+    w, start = np.zeros(W, dtype=np.float32), np.zeros(GAMES, dtype=np.uint64)
+    for r in range(2):
+        id0 = BOARD_ID0 + r * GAMES
+        g, left = rollout_from_on_host(start, GAMES, MAX_STEPS, EPSILON, GAMMA, w, TUPLES, True, *_seeds(), id0, r)
+        assert int(np.count_nonzero(left)) == (0 if r == 0 else picked) and (r == 0 or picked > 0)    # started: the games begun on a picked board
+        acc = np.zeros((W, 2), dtype=np.int64)
+        assert nt.learn_nt_on_host(g["keys"], g["values"], g["steps"], g["lengths"], TUPLES, True, GAMMA, acc)["learnt"] > 100
+        assert nt.apply_nt_on_host(w, acc, 1.0 / F) > 100
+        start, (picked, depth) = nt.restart_pick_on_host(g["keys"], g["lengths"], MAX_STEPS, SEED, id0, RESTART["restart_fraction"], RESTART["restart_min_length"])
+        print("round", r, "lengths", g["lengths"].tolist(), "picked", picked, "depth", depth)
+        assert picked > 0 and depth > 0 and int(usable_on_host(start).sum()) == picked == int(np.count_nonzero(start))
+        assert (g["lengths"] >= RESTART["restart_min_length"]).sum() == picked
+
+
+def test_the_staged_case_reaches_two_stages():
+    """stage_tiles (8, 16), TD(.5) with temporal coherence, round 0 from zero weights on the host: within 24 moves games reach the 8
+    and some the 16, moves are learnt in at least two stages and their adds are not all zero.  The stage tiles (16,) of the grown
+    case, split at 8, are the same three stages."""
+    from tests.tfe_nt_staged_support import adds_per_stage
+    nt = _nt()
+    tuples = nt.with_stages(TUPLES, STAGE_TILES)
+    W, S = nt.tuple_offsets(TUPLES)[1], len(STAGE_TILES) + 1
+    g = rollout_nt_on_host(GAMES, MAX_STEPS, EPSILON, GAMMA, np.zeros(S * W, dtype=np.float32), tuples, True, *_seeds(), BOARD_ID0, 0)
+    top = g["final_boards"].reshape(GAMES, -1).max(axis=1)
+    print("largest tiles", top.tolist())
+    assert (top >= 8).sum() >= GAMES - 2 and (top >= 16).sum() >= 2
+    acc, ab = np.zeros((S * W, 2), dtype=np.int64), np.zeros(S * W, dtype=np.int64)
+    nt.learn_tc_nt_on_host(g["keys"], g["values"], g["steps"], g["lengths"], tuples, True, GAMMA, LAM, acc, ab)
+    adds = adds_per_stage(acc, S)
+    print("adds per stage", adds)
+    assert sum(a > 0 for a in adds) >= 2 and sum(bool(x[:, 0].any()) for x in acc.reshape(S, -1, 2)) >= 2
+    assert nt.split_stage_tiles(GROWN_FROM, GROWN_TILE)[0] == STAGE_TILES
+
+
+def adaptive_case_on_host(rounds, evaluate=False):
+    """The adaptive case on the host: `rounds` rounds of 13 games at E = DEEP_EMPTY_MAX with backed targets (TD(0)) and restarts, from
+    zero weights; per round (moves two layers deep, one layer deep, boards picked); with `evaluate` also the depth words of the 11
+    evaluation games on the weights as they stand.  adaptive_case_on_host(ROUNDS, True) is what ADAPTIVE_REHEARSED records."""
+    from tests.tfe_adaptive_host import adaptive_games_on_host
+    from tests.tfe_adaptive_rollout_host import adaptive_rollout_from_on_host
+    nt = _nt()
+    W, F = nt.tuple_offsets(TUPLES)[1], 8 * len(TUPLES)
+    w, start, out = np.zeros(W, dtype=np.float32), np.zeros(GAMES, dtype=np.uint64), []
+    for r in range(rounds):
+        id0 = BOARD_ID0 + r * GAMES
+        g, _ = adaptive_rollout_from_on_host(start, GAMES, MAX_STEPS, EPSILON, GAMMA, w, TUPLES, True, *_seeds(), id0, r, DEEP_EMPTY_MAX, backed=True)
+        acc = np.zeros((W, 2), dtype=np.int64)
+        nt.learn_backed_nt_on_host(g["keys"], g["values"], g["backed"], g["steps"], g["lengths"], TUPLES, True, GAMMA, 0.0, acc)
+        nt.apply_nt_on_host(w, acc, 1.0 / F)
+        start, (picked, _) = nt.restart_pick_on_host(g["keys"], g["lengths"], MAX_STEPS, SEED, id0, RESTART["restart_fraction"], RESTART["restart_min_length"])
+        out.append((g["deep"], g["shallow"], picked))
+    if evaluate:
+        ev = adaptive_games_on_host(EVAL_GAMES, MAX_STEPS, 0.0, GAMMA, w, TUPLES, True, *_seeds(), BOARD_ID0 + (1 << 62), rounds, DEEP_EMPTY_MAX)
+        out.append((ev["deep"], ev["shallow"]))
+    return out
+
+
+def test_the_adaptive_case_moves_at_both_depths():
+    """Round 0 of the adaptive case on the host (the later rounds and the evaluation are recorded in ADAPTIVE_REHEARSED, which the
+    device test holds the device to): moves at both depths, every one of them counted, boards picked.  The depth words only grow, so
+    round 0 alone puts both above 0.  Whatever the weights, a game's first move is one layer deep at any E below 14: a reset board
+    has 14 empty cells."""
+    (deep, shallow, picked), = adaptive_case_on_host(1)
+    print("E", DEEP_EMPTY_MAX, "deep", deep, "shallow", shallow, "picked", picked)
+    assert (deep, shallow) == ADAPTIVE_REHEARSED["per_round"][0] and deep > 0 and shallow >= GAMES and picked > 0 and DEEP_EMPTY_MAX < 14
+    assert tuple(map(sum, zip(*ADAPTIVE_REHEARSED["per_round"]))) == tuple(ADAPTIVE_REHEARSED["rounds"].values())
+    assert all(x > 0 for x in ADAPTIVE_REHEARSED["evaluation"])
 
 
 # ------------------------------------------------------------------ two gloo ranks on CPU tensors
@@ -241,6 +351,22 @@ def test_python_layer():
     agent.n_weights = 100
     assert agent.set_shard(13, 0)._shard.side.capacity == 100 and agent.set_shard(13, 0, exchange_capacity=3)._shard.side.capacity == 3
     assert agent._shard.eval_shard(11, (1 << 62) + 5) == (11, (1 << 62) + 5)                    # (a world of one plays them all)
+    # the depth words are read through the shard's reduce, as stats() is: a world of one reduces to itself; without a shard as it was
+    import torch
+    seen = []
+    agent._shard.reduce = lambda words, max_at=(): seen.append(list(words)) or ranks.reduce_words(words, None, None, max_at)
+    agent.depth_stats = torch.tensor([5, 7], dtype=torch.int64)
+    assert agent._depth_read() == [5, 7] and agent.rollout_depth_summary(clear=False) == dict(moves_deep=5, moves_shallow=7)
+    assert agent.rollout_depth_summary() == dict(moves_deep=5, moves_shallow=7) and agent.depth_stats.tolist() == [0, 0]
+    assert seen == [[5, 7]] * 3
+    sharded, agent._shard = agent._shard, None
+    agent.depth_stats = torch.tensor([2, 3], dtype=torch.int64)
+    assert agent.rollout_depth_summary() == dict(moves_deep=2, moves_shallow=3) and seen == [[5, 7]] * 3
+    agent._shard, agent.depth_stats = sharded, None
+    with pytest.raises(ValueError, match="no adaptive launch has run"):
+        agent.rollout_depth_summary()
+    assert "_depth_read" in inspect.getsource(Agent.evaluate_search) and "job-wide" in Agent._depth_read.__doc__
+    assert "rollout_depth_summary()" in Agent.__doc__.split("job-wide")[0].rsplit("stats()", 1)[1]       # named in the list of job-wide read-backs
     # check_options takes the shard, and the shard goes with everything
     assert nt.check_options(shard=(13, 7, 6)) == (0, False, 0, None)
     assert nt.check_options(1, True, 0.5, False, 64, True, shard=(13, 0, 13)) == (1, True, 0, None)

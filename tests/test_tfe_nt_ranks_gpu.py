@@ -5,7 +5,10 @@ launch is handed sits between guard words.
 
 Shapes: the network "eight" of tests/tfe_nt_support.py, 1,188,368 cells -- no multiple of the pack's 1,024-cell tile nor of 256, so
 the last workgroup is ragged and the launch takes 1,161 tiles --; the accumulators of a real learn launch on 8 games of 16 moves
-with cells set by hand on top; for the ranks 13 games (7 + 6) of at most 24 moves, 3 rounds, epsilon .25."""
+with cells set by hand on top; synthetic int64 buffers, no agent, where the kernels' grid-stride loops turn three times under the cap
+of eight workgroups per compute unit ((2 cap + 1) * 1,024 + 517 cells, 2 cap * 256 + 77 entries: about 4.2 M cells and 1 M entries at
+256 compute units), n_entries from 1 to 2,049, and one entry in eight on four cells; for the ranks 13 games (7 + 6) of at most 24
+moves, 3 rounds, epsilon .25, under every option that goes with a shard."""
 import os
 import socket
 
@@ -13,7 +16,9 @@ import numpy as np
 import pytest
 
 from tests.tfe_gpu_support import guarded, guards_intact
-from tests.tfe_nt_ranks_support import GAMES, LAM, MAX_STEPS, PACK, ROUNDS, TUPLES, UNPACK, assert_list_refusals, by_index, list_words
+from tests.tfe_nt_ranks_support import (ADAPTIVE_REHEARSED, BLOCK, DEAD, DEEP_EMPTY_MAX, EVAL_GAMES, GAMES, GROWN_FROM, GROWN_TILE, LAM, MAX_STEPS, PACK, RESTART, ROUNDS,
+                                        STAGE_TILES, TILE, TINY, TINY_PATTERNS, TUPLES, UNPACK, assert_list_refusals, by_index, contended_entries, device_launcher,
+                                        list_words, multi_pass_accumulators, passes, tiny_accumulators)
 from tests.tfe_nt_support import learner_agent, nt, plain_learner
 
 pytestmark = pytest.mark.gpu
@@ -190,16 +195,168 @@ def test_pack_then_unpack_into_zeroed_accumulators_round_trips(learnt):
     guards_intact([("list", flat, g), ("acc2", f2, g2), ("abs2", f3, g3)], a)
 
 
+# ------------------------------------------------------------------ synthetic buffers: the grid-stride loops turn, tiny counts, contended adds
+# Both entry points take a raw pointer and n_entries, so these need no agent.  Both grids are capped at eight workgroups per compute unit.
+def _cap():
+    import torch
+    return 8 * torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _on_device(x):
+    """a host array on the device between guard words: (the tensor, its guards)"""
+    import torch
+    dev, flat, g = guarded(torch.from_numpy(x).to("cuda:0"))
+    return dev, [("buffer", flat, g)]
+
+
+def _pack_into(a, acc, ab, capacity, n_entries=None, words=None):
+    """one pack launch of the device tensors acc (and ab, or None) into a list of `capacity` entries full of PATTERN between guard
+    words (or into `words`, refilled): (the list's words on the host, its guards, the device tensor)"""
+    import torch
+    guards = []
+    if words is None:
+        words, flat, g = guarded(torch.zeros(4 + 4 * capacity, dtype=torch.int64, device=a.device), PATTERN)
+        guards = [("list", flat, g)]
+    else:
+        words.fill_(PATTERN)
+    _launch_list(a, PACK, acc, ab, words, capacity, n_entries=n_entries)
+    return words.cpu().numpy(), guards, words
+
+
+@pytest.fixture(scope="module")
+def multi_pass():
+    """(the launcher, the cap, acc and acc_abs on the host and on the device between guard words, their guards, the mirror's entries with
+    and without acc_abs) of multi_pass_accumulators: about 4.2 M cells at a cap of 2,048, 67 MB + 34 MB.  The pass counts the size is
+    chosen for are asserted, so a device with another count of compute units turns the loops as often or fails here."""
+    a, cap = device_launcher(), _cap()
+    acc, ab, tiles = multi_pass_accumulators(cap)
+    n = len(acc)
+    n_tiles = -(-n // TILE)
+    print("compute units", cap // 8, "cap", cap, "cells", n, "tiles", n_tiles)
+    assert n == (2 * cap + 1) * TILE + 517 and n_tiles == 2 * cap + 2 and passes(n, TILE, cap) == 3
+    assert [len(range(b, n_tiles, cap)) for b in (0, 1, 2, cap - 1)] == [3, 3, 2, 2]                 # workgroups 0 and 1 go round three times, every other twice
+    with_abs, without = nt().pack_acc_on_host(acc, ab), nt().pack_acc_on_host(acc)
+    per_tile = np.bincount(with_abs[:, 0] // TILE, minlength=n_tiles)
+    assert {t: int(per_tile[t]) for t in tiles} == tiles and len(with_abs) > 3 * TILE + 5000
+    assert {0, n - 1} <= set(with_abs[:, 0].tolist()) and (with_abs[:, 1] < 0).sum() > 1000 and (with_abs[:, 1] > 0).sum() > 1000
+    dead = np.flatnonzero((acc[:, 1] <= 0) & (acc[:, 0] != 0))
+    assert len(dead) > 500 and sorted(set(map(tuple, acc[dead].tolist()))) == sorted(DEAD) and not np.isin(dead, with_abs[:, 0]).any()
+    assert np.isin(dead // TILE, [cap, 1, 2 * cap + 1]).sum() >= 4                                   # some of them where a tile has no live cell, and in the ragged one
+    (dacc, g1), (dab, g2) = _on_device(acc), _on_device(ab)
+    return a, cap, acc, ab, dacc, dab, g1 + g2, with_abs, without
+
+
+@pytest.mark.parametrize("with_abs", (True, False))
+def test_pack_goes_round_its_grid_three_times(multi_pass, with_abs):
+    """2 cap + 2 tiles under a grid of cap workgroups: the LDS words of either parity are written a second time, a workgroup skips its
+    atomic in one pass and takes 1,024 slots in the next.  capacity == found: the mirror's set; 1,000 short: 1,000 entries are counted
+    and not written, and every written one is the mirror's.  (Tried once on an MI355X: the kernel without its second barrier fails here,
+    slots taken from a wg_base not yet written.  Without `parity ^= 1u` it passes: that only opens a race -- a wavefront a pass ahead
+    would overwrite wave_total while a slower one still sums it for its slot0, but it first waits for its four loads from memory, far
+    longer than the few LDS reads it would have to overtake -- so the double buffer rests on the argument in the kernel, not on a test.)"""
+    a, cap, acc, ab, dacc, dab, guards, *mirrors = multi_pass
+    want = mirrors[0] if with_abs else mirrors[1]
+    found = len(want)
+    print("found", found)
+    words, lg, _ = _pack_into(a, dacc, dab if with_abs else None, found)
+    assert words[:4].tolist() == [found, found, 0, 0]
+    assert np.array_equal(by_index(words[4:]), want)
+    guards_intact(lg, guards)
+    assert found > 2000
+    short, lg, _ = _pack_into(a, dacc, dab if with_abs else None, found - 1000)
+    assert short[:4].tolist() == [found, found - 1000, 0, 0]
+    got = by_index(short[4:])
+    assert len(got) == found - 1000 and len(np.unique(got[:, 0])) == found - 1000                     # distinct indices
+    at = np.searchsorted(want[:, 0], got[:, 0])
+    assert (at < found).all() and np.array_equal(want[np.minimum(at, found - 1)], got)              # each is the mirror's entry of its index
+    guards_intact(lg, guards)                                                                        # nothing lies beyond the list
+    assert np.array_equal(dacc.cpu().numpy(), acc) and np.array_equal(dab.cpu().numpy(), ab)         # the accumulators are only read
+
+
+def test_pack_at_tiny_and_boundary_counts():
+    """n_entries of TINY under TINY_PATTERNS, one pair of buffers of three tiles for all of them: whole wavefronts -- at n_entries 1, all
+    but one lane -- read only the clamped last cell, which must not be counted again; the cells from n_entries on are live decoys."""
+    import torch
+    a, cells = device_launcher(), -(-max(TINY) // TILE) * TILE
+    dacc, g1 = _on_device(np.zeros((cells, 2), dtype=np.int64))
+    dab, g2 = _on_device(np.zeros(cells, dtype=np.int64))
+    words, flat, g = guarded(torch.zeros(4 + 4 * cells, dtype=torch.int64, device=a.device), PATTERN)
+    for n in TINY:
+        for which in TINY_PATTERNS:
+            acc, ab = tiny_accumulators(n, which, cells)
+            dacc.copy_(torch.from_numpy(acc))
+            dab.copy_(torch.from_numpy(ab))
+            want = nt().pack_acc_on_host(acc[:n], ab[:n])
+            assert len(want) == dict(all=n, last=1, first=1, none=0)[which]
+            got, _, _ = _pack_into(a, dacc, dab, cells, n_entries=n, words=words)
+            assert got[:4].tolist() == [len(want), len(want), 0, 0], (n, which, got[:4].tolist())
+            assert np.array_equal(by_index(got[4:4 + 4 * len(want)]), want), (n, which)
+            assert (got[4 + 4 * len(want):] == PATTERN).all(), (n, which)                            # (no cell live: the whole body)
+            assert np.array_equal(dacc.cpu().numpy(), acc), (n, which)
+    guards_intact(g1, g2, [("list", flat, g)])
+
+
+@pytest.mark.parametrize("with_abs", (True, False))
+def test_unpack_goes_round_its_grid_on_contended_cells(with_abs):
+    """2 cap * 256 + 77 entries under a grid of cap workgroups: every lane adds two entries, the first 77 three; one entry in eight adds
+    into one of four cells, 300 are refused in place.  acc, acc_abs and the two counters equal numpy's add.at and its count."""
+    a, cap, rng = device_launcher(), _cap(), np.random.default_rng(8)
+    k = 2 * cap * BLOCK + 77
+    assert -(-k // BLOCK) == 2 * cap + 1 > cap and passes(k, BLOCK, cap) == 3 and len(range(77, k, cap * BLOCK)) == 2
+    print("cap", cap, "entries", k)
+    entries, n_bad = contended_entries(k, N_CELLS, rng)
+    assert (np.bincount(entries[:, 0][(entries[:, 0] >= 0) & (entries[:, 0] < N_CELLS)], minlength=N_CELLS)[[0, 1234, 2500, N_CELLS - 1]] > k // 40).all()
+    acc, ab, dacc, dab, stats, guards = _cells(a, 4)
+    before_abs = ab.copy()
+    host_words = list_words(entries, k)
+    words, lg = _list_on_device(a, host_words)
+    _launch_list(a, UNPACK, dacc, dab if with_abs else None, words, k, stats)
+    assert nt().unpack_acc_on_host(acc, ab if with_abs else None, entries) == (k - n_bad, n_bad)
+    assert stats.cpu().tolist() == [k - n_bad, n_bad]
+    assert np.array_equal(dacc.cpu().numpy(), acc) and np.array_equal(dab.cpu().numpy(), ab)
+    assert with_abs or np.array_equal(ab, before_abs)
+    assert np.array_equal(words.cpu().numpy(), host_words)                                           # the list is only read
+    guards_intact(guards, lg)
+
+
+def test_multi_pass_pack_then_unpack_round_trips(multi_pass):
+    """the list of the multi-pass buffer, added into zeroed accumulators of its size: the live cells again, zeros elsewhere"""
+    import torch
+    a, cap, acc, ab, dacc, dab, guards, want, _ = multi_pass
+    found = len(want)
+    _, lg, words = _pack_into(a, dacc, dab, found)
+    acc2, f2, g2 = guarded(torch.zeros_like(dacc))
+    ab2, f3, g3 = guarded(torch.zeros_like(dab))
+    stats = torch.zeros(2, dtype=torch.int64, device=a.device)
+    _launch_list(a, UNPACK, acc2, ab2, words, found, stats)
+    live = acc[:, 1] > 0
+    got, got_abs = acc2.cpu().numpy(), ab2.cpu().numpy()
+    assert stats.cpu().tolist() == [found, 0] and live.sum() == found
+    assert np.array_equal(got[live], acc[live]) and np.array_equal(got_abs[live], ab[live]) and not got[~live].any() and not got_abs[~live].any()
+    guards_intact(lg, guards, [("acc2", f2, g2), ("abs2", f3, g3)])
+
+
 def test_the_entry_points_refuse():
     assert_list_refusals()
+
+
 
 
 # ------------------------------------------------------------------ rounds: a world of one, and two ranks on one device
 CASES = (("td0", dict(), dict(), None),                                    # (name, the agent's keywords, its attributes, exchange_capacity)
          ("tc", dict(lam=LAM, tc=True), dict(), None),
          ("continue", dict(max_steps=8), dict(continue_games=True), None),
-         ("dense", dict(lam=LAM, tc=True), dict(), 3))
-EVAL_GAMES = 11
+         ("dense", dict(lam=LAM, tc=True), dict(), 3),
+         # every other option the docstrings name beside a shard; tests/test_tfe_nt_ranks_cpu.py plays their regimes on the host
+         ("lambda", dict(lam=LAM), dict(), None),
+         ("staged", dict(stage_tiles=STAGE_TILES, lam=LAM, tc=True), dict(), None),
+         ("staged-grown", dict(stage_tiles=GROWN_FROM), dict(), None),             # add_stage(GROWN_TILE) behind round 1: acc is reallocated under the shard
+         ("restart", dict(), dict(RESTART), None),
+         ("backed", dict(lam=LAM), dict(rollout_layers=1, backed_targets=True), None),
+         ("search2", dict(), dict(rollout_layers=2), None),
+         ("adaptive", dict(), dict(RESTART, rollout_layers=2, rollout_deep_empty_max=DEEP_EMPTY_MAX, backed_targets=True), None),
+         ("resume", dict(lam=LAM, tc=True), dict(), None))                           # save() behind round 1, load() + set_shard, round 2
+GROW_BEHIND = 1
 
 
 def _sparse(x):
@@ -213,30 +370,64 @@ def _same(x, y):
     return np.array_equal(x[0], y[0]) and np.array_equal(x[1], y[1])
 
 
-def _rounds(n_games, game0, kw, attrs, capacity, sharded):
+def _file_words(path):
+    """an .npz as {name: (dtype, shape, bytes)}"""
+    with np.load(path) as f:
+        return {k: (str(f[k].dtype), f[k].shape, f[k].tobytes()) for k in f.files}
+
+
+def _resumed(a, attrs, capacity, tmp, rank):
+    """every rank saves; every rank loads RANK 0's file with its own share of the games and sets the shard again: (the loaded agent,
+    the exchange summary of the agent it replaces, this rank's file)"""
+    import torch.distributed as dist
+    a.save(os.path.join(tmp, "rank%d.npz" % rank))
+    dist.barrier()
+    b = type(a).load(os.path.join(tmp, "rank0.npz"), a.device, n_games=a.n_games)
+    for k, v in attrs.items():
+        setattr(b, k, v)
+    b.set_shard(a._shard.n_games_total, a._shard.game0, exchange_capacity=capacity)
+    return b, a.exchange_summary(), _file_words(os.path.join(tmp, "rank%d.npz" % rank))
+
+
+def _rounds(case, n_games, game0, sharded, tmp=None, rank=0):
     """three rounds of the case on `n_games` games that begin at game `game0` of the job's 13: (the agent, what it read back)"""
+    name, kw, attrs, capacity = case
     a = plain_learner(n_games, **dict(dict(tuples=TUPLES, max_steps=MAX_STEPS), **kw))
     for k, v in attrs.items():
         setattr(a, k, v)
     if sharded:
         a.set_shard(GAMES, game0, exchange_capacity=capacity)
-    for _ in range(ROUNDS):
+    out, before = dict(restarts=[]), None
+    for r in range(ROUNDS):
+        if name == "resume" and sharded and tmp is not None and r == ROUNDS - 1:
+            a, before, out["file"] = _resumed(a, attrs, capacity, tmp, rank)
+            assert a.round == ROUNDS - 1 and a.n_games == n_games
         a.learn_batch()
-    out = dict(weights=_sparse(a.weights()), stats=a.stats(), round=a.round)
+        if a.restart_fraction > 0.0:
+            out["restarts"].append(a.restart_summary())                    # (with a shard: job-wide)
+        if name == "staged-grown" and r == GROW_BEHIND:
+            a.add_stage(GROWN_TILE)
+    out.update(weights=_sparse(a.weights()), stats=a.stats(), round=a.round, stages=(a.n_stages, a.n_weights))
     if a.tc:
         E, A = a.coherence()
         out.update(E=_sparse(E), A=_sparse(A), tc=a.tc_summary())
     if a.continue_games:
         out["finished"] = a.finished_summary()
+    if a.rollout_deep_empty_max is not None:                                # the rounds' depth words, then the evaluation's: job-wide with a shard
+        out["depth"] = a.rollout_depth_summary()
+        out["evaluate_adaptive"] = a.evaluate_search(n_games=EVAL_GAMES, layers=2, deep_empty_max=DEEP_EMPTY_MAX)
     if sharded:
         out["exchange"] = a.exchange_summary()
+        if before is not None:                                              # the rounds of the agent that was saved, then the loaded one's
+            out["exchange"] = {k: before[k] + out["exchange"][k] for k in ("rounds", "added", "refused")}
     return a, out
 
 
-def _all_cases(n_games, game0, sharded):
+def _all_cases(n_games, game0, sharded, tmp=None, rank=0):
     out = {}
-    for name, kw, attrs, capacity in CASES:
-        a, out[name] = _rounds(n_games, game0, kw, attrs, capacity, sharded)
+    for case in CASES:
+        name = case[0]
+        a, out[name] = _rounds(case, n_games, game0, sharded, tmp, rank)
         if name == "tc":                                                    # the trained network's evaluations: 11 games, job-wide
             out["evaluate"] = a.evaluate(n_games=EVAL_GAMES)
             out["evaluate_search"] = a.evaluate_search(n_games=EVAL_GAMES)
@@ -257,9 +448,8 @@ def _assert_case(got, want, where):
 def test_a_world_of_one_is_the_agent_without_the_shard():
     """set_shard(n, 0) and no group: three rounds of TD(.5) with temporal coherence; weights, E and A bit for bit those of the agent
     without the shard; the summary names the sparse path, counts the entries and moves no byte"""
-    name, kw, attrs, capacity = CASES[1]
-    _, want = _rounds(GAMES, 0, kw, attrs, capacity, False)
-    _, got = _rounds(GAMES, 0, kw, attrs, capacity, True)
+    _, want = _rounds(CASES[1], GAMES, 0, False)
+    _, got = _rounds(CASES[1], GAMES, 0, True)
     _assert_case(got, want, "world of one")
     rounds = got["exchange"]["rounds"]
     assert [r["round"] for r in rounds] == [0, 1, 2] and all(r["path"] == "sparse" and r["bytes"] == 0 and r["entries"][0] > 100 for r in rounds)
@@ -272,33 +462,42 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _worker(rank, world, port, out):
+def _worker(rank, world, port, tmp, out):
     import torch.distributed as dist
     from pulselib_amd.agents import tfe_ntuple_ranks as ranks
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     ranks.init_ranks("gloo", rank, world)
     try:
         n_games, game0 = ranks.shard_of(GAMES)
-        out[rank] = dict(_all_cases(n_games, game0, True), shard=(n_games, game0))
+        out[rank] = dict(_all_cases(n_games, game0, True, tmp, rank), shard=(n_games, game0))
     finally:
         dist.destroy_process_group()
 
 
-def test_two_ranks_on_one_device_equal_one_process():
-    """One spawn of two fresh processes (three with this one) for all four cases: each rank's weights -- and E, A, the job-wide stats(),
+def test_two_ranks_on_one_device_equal_one_process(tmp_path):
+    """One spawn of two fresh processes (three with this one) for all the cases: each rank's weights -- and E, A, the job-wide stats(),
     finished_summary() and tc_summary() where the case has them -- equal one process's on 13 games exactly, the ranks equal each
-    other, and the summary names the path: sparse in the first three cases, dense with room for 3 entries.  evaluate(n_games=11) and
-    evaluate_search on the two ranks give the single process's summary and histogram word for word."""
+    other, and the summary names the path: dense with room for 3 entries, sparse in every other case.  evaluate(n_games=11) and
+    evaluate_search on the two ranks give the single process's summary and histogram word for word.  Beyond the first four cases:
+    TD(.5) without tc; stages (two of them learnt in); a stage added between two rounds, so that the exchange meets a reallocated acc;
+    restarts, with restart_summary() after every round; search-backed targets under one chance layer; roll-outs two layers deep; the
+    adaptive depth with backed targets and restarts, with rollout_depth_summary() and the adaptive evaluate_search, whose depth words
+    are the job's; and a run saved by both ranks behind round 1 and taken up from rank 0's file."""
     import torch.multiprocessing as mp
     want = _all_cases(GAMES, 0, False)
     out = mp.Manager().dict()
-    mp.spawn(_worker, args=(2, _free_port(), out), nprocs=2, join=True)
+    mp.spawn(_worker, args=(2, _free_port(), str(tmp_path), out), nprocs=2, join=True)
     got = [out[0], out[1]]
     assert [g["shard"] for g in got] == [(7, 0), (6, 7)]
     for name, *_ in CASES:
         for rank in range(2):
-            _assert_case(got[rank][name], want[name], (name, rank))
+            if name == "resume":                                            # (stats() and tc_summary() are the agent's, not the file's: a loaded agent counts from 0)
+                assert got[rank][name]["round"] == want[name]["round"] == ROUNDS and all(_same(got[rank][name][k], want[name][k]) for k in ("weights", "E", "A")), rank
+                assert len(got[rank][name]["weights"][0]) >= len(TUPLES) and want[name]["stats"]["learnt"] > 100
+            else:
+                _assert_case(got[rank][name], want[name], (name, rank))
             rounds = got[rank][name]["exchange"]["rounds"]
+            assert [r["round"] for r in rounds] == list(range(ROUNDS)), (name, rank)
             assert [r["path"] for r in rounds] == ["dense" if name == "dense" else "sparse"] * ROUNDS, (name, rank)
             assert all(len(r["entries"]) == 2 and min(r["entries"]) >= len(TUPLES) for r in rounds) and got[rank][name]["exchange"]["refused"] == 0
             added = sum(r["entries"][1 - rank] for r in rounds)
@@ -311,3 +510,24 @@ def test_two_ranks_on_one_device_equal_one_process():
     assert [len(g["per_game"][0]) for g in got] == [6, 5]
     for i in range(2):
         assert np.array_equal(np.concatenate([g["per_game"][i] for g in got]), want["per_game"][i])
+    # stages: weights that are not zero in at least two of the three, and after the split in the stage that was added
+    for name, n_stages in (("staged", 3), ("staged-grown", 3)):
+        assert want[name]["stages"] == got[0][name]["stages"] == got[1][name]["stages"] == (n_stages, 1188368)
+        assert len(np.unique(want[name]["weights"][0] // 1188368)) >= 2, name
+    # restarts: the job's picks and started games after every round
+    for name in ("restart", "adaptive"):
+        assert got[0][name]["restarts"] == got[1][name]["restarts"] == want[name]["restarts"] and len(want[name]["restarts"]) == ROUNDS, name
+        assert all(s["picked"] > 0 and s["mean_depth"] > 0 for s in want[name]["restarts"][:2]) and all(s["started"] > 0 for s in want[name]["restarts"][1:]), name
+    # the adaptive depth: both words move, and they are the job's on either rank, the evaluation's too
+    depth, ev = want["adaptive"]["depth"], want["adaptive"]["evaluate_adaptive"]
+    assert got[0]["adaptive"]["depth"] == got[1]["adaptive"]["depth"] == depth and depth["moves_deep"] > 0 and depth["moves_shallow"] > 0
+    assert depth["moves_deep"] + depth["moves_shallow"] == want["adaptive"]["stats"]["moves"]
+    assert got[0]["adaptive"]["evaluate_adaptive"] == got[1]["adaptive"]["evaluate_adaptive"] == ev
+    assert ev["games"] == EVAL_GAMES and ev["moves_deep"] > 0 and ev["moves_shallow"] > 0 and ev["moves_deep"] + ev["moves_shallow"] == ev["moves"]
+    assert (depth, (ev["moves_deep"], ev["moves_shallow"])) == (ADAPTIVE_REHEARSED["rounds"], ADAPTIVE_REHEARSED["evaluation"])      # the host's, played ahead
+    # resume: the two files differ in n_games alone
+    files = [g["resume"]["file"] for g in got]
+    assert sorted(files[0]) == sorted(files[1]) and {"n_games", "round", "index", "value"} <= set(files[0])
+    assert [k for k in files[0] if files[0][k] != files[1][k]] == ["n_games"]
+    assert [np.frombuffer(f["n_games"][2], dtype=f["n_games"][0]).tolist() for f in files] == [[7], [6]]
+    assert np.frombuffer(files[0]["round"][2], dtype=files[0]["round"][0]).tolist() == [ROUNDS - 1] and len(files[0]["index"][2]) > 8 * len(TUPLES)
