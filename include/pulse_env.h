@@ -282,15 +282,26 @@ int64_t pulse_stoprule_side_launches(void* handle);
  * LONG_LAUNCHES (0 / 1, default 1).  DEBUG_SKIP_DECISION (test hook, one-shot): in the next long launch nobody decides
  * check point `value` (1 = the launch's first; 0 = none), so its waiters run into the bound and call it off.
  * DEBUG_RESIDENT_BLOCKS (test hook): the occupancy answer to assume (0: ask the device).
- * long_stats: out4 = {long launches issued, verdicts taken in-launch, check points called off, 1 if the handle would
- * still plan long launches (the residency of a grid is only known per call)}; PULSE_EINTERNAL if a launch told the host its
- * chunk count more than once (it must not: the device counts its writes of that word). */
+ * EARLY_VERDICTS (0 .. 3, default 1): of a long launch only the two steps in front of an end it can still take compute and
+ * store rewards, observations and done flags.  On, the launch's first check point (which reads no verdict and so ends nothing)
+ * is no such end, and before the two steps in front of every later check point a wavefront looks -- one load, no loop -- whether
+ * the verdict that check point will read is settled already: "go on" makes the check point no end either (the two steps run
+ * without outputs, the check point reads nothing and arrives), "over" or "called off" ends the launch there as the check
+ * point's own read would, and a pending word leaves everything to that read.  Memory behind a call is the same in every case.
+ * 0: no look, every check point a possible end (the A/B twin).  2: as 1, and the launches count the looks that found their
+ * word settled / pending (long_stats; test use: two atomic adds per wavefront and check point).  3: as 2, but odd-numbered
+ * wavefronts treat every look as pending: both paths inside one launch.
+ * long_stats: out6 = {long launches issued, verdicts taken in-launch, check points called off, 1 if the handle would
+ * still plan long launches (the residency of a grid is only known per call), early looks that found the verdict settled, early
+ * looks that found it pending (both 0 unless EARLY_VERDICTS has been 2 or 3; reading them waits for the launches' stream)};
+ * PULSE_EINTERNAL if a launch told the host its chunk count more than once (it must not: the device counts its writes of that word). */
 #define PULSE_STOPRULE_OPT_LONG_LAUNCHES             3
 #define PULSE_STOPRULE_OPT_DEBUG_SKIP_DECISION       4
 #define PULSE_STOPRULE_OPT_DEBUG_RESIDENT_BLOCKS     5
+#define PULSE_STOPRULE_OPT_EARLY_VERDICTS            6
 int pulse_stoprule_set_option(void* handle, int32_t option, int64_t value);
 int pulse_stoprule_stats(void* handle, int64_t* out4);
-int pulse_stoprule_long_stats(void* handle, int64_t* out4);
+int pulse_stoprule_long_stats(void* handle, int64_t* out6);
 
 /* The shared-memory exchange of the stop rule as an object of its own (host code only; the rule creates one itself when
  * given shm_name).  Every rank maps the POSIX segment `name` (created by whoever comes first; unlink it once all ranks

@@ -109,11 +109,16 @@ __device__ __forceinline__ long long long_settle(StepKernargsPtr ka, int r, long
 // an "over" or a "called off" NO wavefront arrives again, no later verdict is decided, and the word that told the host how
 // many chunks the launch runs stays the only one (arriving first, the next check point was decided "over" too and its word
 // overwrote the host's a chunk later).  true: the launch ends here.
-__device__ __forceinline__ bool long_check_point(StepKernargsPtr ka, int q, int c, uint32_t wid, bool arrives) {
+// `taken`: the wavefront has that verdict from its early look (long_peek below; 0: it has not) -- 1 = "go on", 2 = "over" or
+// "called off".  It is the word the read here would find (a settled word stays until its slot's next check point, four later,
+// which nobody decides before this wavefront has arrived three more times), so the read is skipped and the rest is the same:
+// behind a 2 the wavefront does not arrive.
+__device__ __forceinline__ bool long_check_point(StepKernargsPtr ka, int q, int c, uint32_t wid, bool arrives, int taken) {
     const int m = ka->pa.lng.n_chunks, r = q - 1;
     const bool lane0 = (threadIdx.x & 63) == 0;
     if (lane0) stg(ka->pa.lng.partials, ((uint32_t)((ka->pa.lng.slot0 + r) & 3) * (uint32_t)ka->pa.lng.max_partials + wid) * 4u, (uint32_t)c);
-    if (q >= 2 && q < m) {
+    if (q >= 2 && q < m && taken == 2) return true;
+    if (q >= 2 && q < m && taken == 0) {
         const int rv = q - 2;
         const GlobalLL* copy = (const GlobalLL*)ka->pa.lng.verdicts + ((size_t)(rv & (pulse::kLongSlots - 1)) * 64 + (wid & 63u)) * kVerdictStride;
         const long long key = (ka->pa.verdict_id << 8) | (long long)rv;
@@ -155,6 +160,29 @@ __device__ __forceinline__ bool long_check_point(StepKernargsPtr ka, int q, int 
         }
     }
     return false;
+}
+
+// The early look at the verdict of check point rv = q - 2, at the bottom of step cp_at - 3, two steps before check point q reads
+// it (the step loop): ONE relaxed system-scope load of this wavefront's copy of the slot, compared with the key long_check_point
+// compares; no loop, no time-out, no store.  0 = pending (another key), 1 = "go on", 2 = "over" or "called off", wave-uniform
+// (scalar: what it decides, end_at and n_steps, stays scalar).  `early` >= 2 counts the outcome (lane 0, one non-returning
+// agent-scope add into the kLongWords lines behind the arrival words, {settled, pending} in line wavefront mod kLongWords -- on one
+// line the adds of 2,048 wavefronts, performed at the memory side, queued for longer than a check interval and the count changed
+// what it counted; a wave-uniform branch, the product executes none); 3 makes odd wavefronts find nothing.
+__device__ __forceinline__ int long_peek(StepKernargsPtr ka, int rv, uint32_t wid, int early) {
+    const GlobalLL* copy = (const GlobalLL*)ka->pa.lng.verdicts + ((size_t)(rv & (pulse::kLongSlots - 1)) * 64 + (wid & 63u)) * kVerdictStride;
+    const long long w = __hip_atomic_load(copy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    const int lo = __builtin_amdgcn_readfirstlane((int)w), hi = __builtin_amdgcn_readfirstlane((int)(w >> 32));
+    const long long word = ((long long)hi << 32) | (unsigned)lo, key = (ka->pa.verdict_id << 8) | (long long)rv;
+    int taken = (word >> 8) != key ? 0 : (lo & 3) != 0 ? 2 : 1;
+    if (early >= 2) {
+        const int w_ = __builtin_amdgcn_readfirstlane((int)wid);      // (as a lane's value the wavefront number made everything behind it a vector)
+        if (early == 3 && (w_ & 1)) taken = 0;
+        if ((threadIdx.x & 63) == 0)
+            (void)__hip_atomic_fetch_add((GlobalLL*)ka->pa.lng.arrive + 2 * kLongSetWords + (w_ & (pulse::kLongWords - 1)) * kVerdictStride + (taken ? 0 : 1), 1ll,
+                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return taken;
 }
 
 // In-kernel timeline (diagnostic build only, -DPULSE_STAMPS=1 -> libpulse_hip_stamps.so; no stamp executes
@@ -494,12 +522,25 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
     int cp_at = MULTI ? pa.mid_step : 0;          // > 0: the launch covers several check intervals, the first check point is behind step cp_at
     // Live steps.  Step i writes its reward, observation and done flag into buffer set i mod 2, so of a launch that ends
     // after e steps only steps e - 2 and e - 1 leave outputs anybody can read: a dead step computes and stores none of them.
-    // A launch can end at n_steps and, a long one, behind any of its check points (the middle check point of a pair only
-    // stores a count: its end is known before the loop, stop_mid) -- end_at is the nearest of them, one scalar compare per
-    // step.  The single step and the act + step launch store every step: their predicate is a constant.
+    // A launch can end at n_steps and, a long one, behind its check points (the middle check point of a pair only
+    // stores a count: its end is known before the loop, stop_mid) -- end_at is the nearest end the wavefront cannot yet rule
+    // out, one scalar compare per step.  The single step and the act + step launch store every step: their predicate is a constant.
+    // Which check points a wavefront can rule out (early verdicts, pa.lng.early; off, every check point is a possible end):
+    //  - the launch's first, q = 1 (cp_at starts at chunk_steps in every long launch, wherever in the episode the call began):
+    //    long_check_point reads a verdict for q >= 2 only, so nothing can end the launch there;
+    //  - check point q, 2 <= q < m, once the verdict it will read (that of q - 2, settled by the last arrival at q - 1) is known
+    //    to be "go on": the wavefront looks for it at the bottom of step cp_at - 3 -- one load, waited for there behind dead steps
+    //    that left no store for the wait to count -- and, where it is settled, moves end_at on to the next check point ("go on")
+    //    or cuts n_steps here ("over", "called off").  A pending word changes nothing: the two steps in front of q run live and
+    //    q reads the word with its bounded wait, as without the look.  (The look is as late as it can be.  Issued at the top of
+    //    that step, its latency hidden under the step, it found the word pending too often -- wavefronts of one launch run
+    //    steps apart, and the last arrival at q - 1 is the slowest one's: the headline launch 141 -> 136 us, against 124 us with
+    //    the look a step later and its latency exposed.  DESIGN.md section 6.0r8.)
+    // The look adds no wait and no decision: every wavefront acts on the one settled word, at the look or at the check point.
+    // Which steps run live may differ from wavefront to wavefront and from run to run; what a launch leaves in memory does not.
     constexpr bool LIVE_RULE = MULTI != 0 && !ACT;
     int end_at = n_steps;
-    if (LIVE_RULE && pa.lng.n_chunks != 0 && cp_at > 0) end_at = min(cp_at, n_steps);
+    if (LIVE_RULE && pa.lng.n_chunks != 0 && cp_at > 0) end_at = min(pa.lng.early ? cp_at + pa.lng.chunk_steps : cp_at, n_steps);
     if (LIVE_RULE) end_at = __builtin_amdgcn_readfirstlane(end_at);      // wave-uniform, and known to be: the compare below is a scalar one
     // Lazy steps.  A dead step runs the betting state machine and the deal only.  Three phases whose results nothing reads
     // before the next live step wait for it -- divergent phases, which a wavefront pays for whenever one of its tables needs one:
@@ -511,10 +552,11 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
     //    once a table is done: no action executes (status, inv, bet, stack), stage and dpos advance for running tables only,
     //    cont_bits is recomputed from status.  A table loaded as done is never unsettled (no payout, as before); its bets are
     //    cleared on the first live step.
-    // Invariant: every possible end e of the launch (n_steps as called, cut by stop_mid or by a check point; any check point of a
-    // long launch, whatever the cap's remainder) has steps e - 2 and e - 1 live -- end_at is the NEAREST possible end at every
-    // step.  A table becomes unsettled, or keeps a raised flag unrefreshed, on a dead step only, and a dead step is followed by a
-    // live one before any end; so behind the payout phase of step e - 2 nothing is owed, and what the last step's policy reads
+    // Invariant: every end e the launch can take (n_steps as called, cut by stop_mid, by a check point or by an early look; a check
+    // point of a long launch whose verdict this wavefront does not know to be "go on", whatever the cap's remainder) has steps
+    // e - 2 and e - 1 live -- end_at is the NEAREST end the wavefront cannot rule out at every step, and it only moves away at the
+    // bottom of step e - 3, before either of them.  A table becomes unsettled, or keeps a raised flag unrefreshed, on a dead step
+    // only, and a dead step is followed by a live one before any end; so behind the payout phase of step e - 2 nothing is owed, and what the last step's policy reads
     // (pot, the carried a_*) and what is stored behind the loop (prev_stacks, prev_invested, actions, equities, equity_dirty,
     // the state words) are what eager steps leave.
     if (LIVE_RULE && dirty && stage >= 1 && stage <= 3) cells_dirty |= (uint32_t)stage << kEqStageShift;
@@ -876,6 +918,20 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
         }
         STAMP(9);   // observation stores issued
         if ((PH & PULSE_PH_ADVANCE) && live && j == 0) sto_in_loop(done_dst, ut, (uint8_t)(done ? 1 : 0));      // ping-pong buffer: written by every live step
+        // the early look at the verdict the coming check point will read.  (Not in the slim image: it is taken above 81,920 tables,
+        // where no long launch passes the residency gate, and the pairs it runs there paid 1.2 % for the look's mere presence.
+        // A long launch forced onto it looks at nothing and reads every verdict at its check point.)
+        if (LIVE_RULE && !SLIM && i + 3 == cp_at) {
+            StepKernargsPtr ka = (StepKernargsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(ka));
+            const int early = ka->pa.lng.early;
+            if (early != 0 && cp_at > ka->pa.mid_step && cp_at < ka->ca.n_steps) {      // a long launch's check point q, 2 <= q < m
+                const int cs = ka->pa.lng.chunk_steps;
+                const int taken = long_peek(ka, cp_at / cs - 2, (uint32_t)(blockIdx.x * (BLK / 64) + (threadIdx.x >> 6)), early);
+                if (taken == 2) n_steps = cp_at;                                                        // end_at == cp_at already
+                if (taken == 1) end_at = __builtin_amdgcn_readfirstlane(min(cp_at + cs, n_steps));
+            }
+        }
         if (MULTI && i + 1 == cp_at) {        // the check point in the middle of a paired launch / a check point of a long one
             StepKernargsPtr ka = (StepKernargsPtr)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(ka));
@@ -888,7 +944,10 @@ __device__ __forceinline__ void poker_step_body(const PulsePokerView& v, int64_t
 #if PULSE_STAMPS
                 const long long cp_t0 = clock64();
 #endif
-                if (long_check_point(ka, cp_at / cs, c, wid, !stop_mid)) n_steps = i + 1;
+                // (what an early look took: it moved end_at past this check point, or cut n_steps to it -- a launch's last check
+                // point, where n_steps is cp_at as called, reads no verdict)
+                const int taken = !LIVE_RULE ? 0 : end_at > cp_at ? 1 : n_steps == cp_at ? 2 : 0;
+                if (long_check_point(ka, cp_at / cs, c, wid, !stop_mid, taken)) n_steps = i + 1;
 #if PULSE_STAMPS
                 if ((threadIdx.x & 63) == 0 && g_stamp_buf) {       // slots 12..14: ticks inside the check points, their number, the longest one
                     const long long dt = clock64() - cp_t0;

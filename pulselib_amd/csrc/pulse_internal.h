@@ -107,17 +107,22 @@ int stoprule_pair_verdict(PulseStopRule* h, const StopRulePair* plan, int* chunk
 // off, the launch ends behind chunk r + 1, leaving the memory of a launch planned r + 2 chunks long.  Whoever wrote the
 // word that settles the launch's length tells the host: {launch id << 16 | chunks run << 8 | over | called off << 1} -- an
 // over or called-off word at once, a "not over" at check point m - 3 (the launch runs to its cap) otherwise.
+// Early verdicts (`early`): a wavefront also LOOKS at verdict r two steps before the check point that reads it -- one load, no
+// loop; a settled word is acted upon there, a pending one leaves everything to the blocking read above -- same word, same order
+// of read and arrival, fewer steps that compute outputs nobody reads (poker_step.hip).
 // (In the kernel's argument block as it stands here: poker_step.hip asserts the layout.)
 struct StopRuleLong {
-    long long* arrive;            // device, zero between launches: [2 sets][1 + kLongWords] words, one 128-byte line each
-    long long* verdicts;          // device: [kLongSlots][64 copies], one line each
+    long long* arrive;            // device, zero between launches: [2 sets][1 + kLongWords] words, one 128-byte line each; kLongWords more lines
+                                  // behind them: {early looks that found their verdict settled, that found it pending} (early >= 2 only)
+    long long* verdicts;         // device: [kLongSlots][64 copies], one line each
     long long* host;              // pinned: what the host learns (one word)
     uint32_t* partials;           // the ring of per-wavefront counts: check point c at partials + (c % 4) * max_partials
     uint32_t over_from;           // the smallest count that ends the episode (the host's own float comparison)
     int max_partials;
     int n_chunks;                 // m; 0: not a long launch
     int chunk_steps;
-    int slot0;                    // a % 4
+    int16_t slot0;                // a % 4
+    int16_t early;                // PULSE_STOPRULE_OPT_EARLY_VERDICTS: 0 off, 1 on, 2 on + counted, 3 as 2 with every peek of an odd wavefront pending
     int skip_cp;                  // test hook: the completing wavefront of this check point does not decide (-1: none)
     int n_waves;                  // wavefronts of the launch = arrivals per check point
     int n_words;                  // first-level arrival words in use (min(kLongWords, n_waves))

@@ -282,6 +282,8 @@ struct PulseStopRule {
     long long long_words_read;            // long launches whose word the host has read; long_host[1] counts the launches' writes of it: one each
     bool shm_asked;                       // created with a shared-memory segment's name (a world of one is local mode all the same)
     long long long_launches, long_taken, long_called_off;
+    int early;                            // PULSE_STOPRULE_OPT_EARLY_VERDICTS (default 1); early_counted: it has been 2 or 3, the two counters behind long_arrive may hold something
+    bool early_counted;
     std::chrono::steady_clock::time_point pair_enqueued;
 };
 
@@ -512,7 +514,8 @@ int stoprule_long_plan(PulseStopRule* h, const StopRulePair* plan, int n_partial
     out->partials = h->partials_dev; out->max_partials = h->max_partials;
     out->over_from = (uint32_t)from;
     out->n_chunks = plan->n_chunks; out->chunk_steps = chunk_steps;
-    out->slot0 = (int)(plan->first_check_point % kSlots);
+    out->slot0 = (int16_t)(plan->first_check_point % kSlots);
+    out->early = (int16_t)h->early;
     out->skip_cp = h->debug_skip > 0 && h->debug_skip - 1 <= plan->n_chunks - 3 ? h->debug_skip - 1 : -1;      // (a check point somebody waits for)
     h->debug_skip = 0;
     out->n_waves = n_partials;
@@ -576,6 +579,7 @@ int pulse_stoprule_create(int32_t n_local, int64_t n_global, double threshold, i
     h->verdict_wait_ticks = 2000000000ll;                   // 20 s
     h->device_private = -1;
     h->long_on = true; h->long_grid = -1;
+    h->early = 1;
     for (int i = 0; i < kSlots; ++i) h->global_known_idx[i] = -1;
     h->comm = static_cast<PulseComm*>(comm); h->rank = rank; h->world = world;
     // a communicator is honoured whatever its size: a world of one is a valid all-reduce, and it is what a one-GPU box
@@ -590,7 +594,7 @@ int pulse_stoprule_create(int32_t n_local, int64_t n_global, double threshold, i
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->verdict_host), (kSlots + 1) * sizeof(long long), hipHostMallocCoherent | hipHostMallocMapped);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->verdict_dev), kSlots * kVerdictCopies * kVerdictStride * sizeof(long long));
     if (e == hipSuccess) e = hipMemset(h->verdict_dev, 0, kSlots * kVerdictCopies * kVerdictStride * sizeof(long long));
-    const size_t arrive_bytes = 2 * (1 + pulse::kLongWords) * kVerdictStride * sizeof(long long);
+    const size_t arrive_bytes = (2 * (1 + pulse::kLongWords) + pulse::kLongWords) * kVerdictStride * sizeof(long long);      // (the last kLongWords lines: the early verdicts' counters)
     const size_t long_verdict_bytes = (size_t)pulse::kLongSlots * kVerdictCopies * kVerdictStride * sizeof(long long);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->long_arrive), arrive_bytes);
     if (e == hipSuccess) e = hipMemset(h->long_arrive, 0, arrive_bytes);
@@ -674,6 +678,9 @@ int pulse_stoprule_set_option(void* handle, int32_t option, int64_t value) {
     case PULSE_STOPRULE_OPT_DEBUG_RESIDENT_BLOCKS:
         if (value < 0 || value > 64) return pulse::fail(PULSE_EINVAL, "pulse_stoprule_set_option: resident workgroups per compute unit: 0 (ask the device) .. 64");
         h->debug_resident = (int)value; h->long_grid = -1; return 0;
+    case PULSE_STOPRULE_OPT_EARLY_VERDICTS:
+        if (value < 0 || value > 3) return pulse::fail(PULSE_EINVAL, "pulse_stoprule_set_option: early verdicts: 0 (off), 1 (on), 2 (on, counted), 3 (counted, odd wavefronts never find one)");
+        h->early = (int)value; h->early_counted = h->early_counted || value >= 2; return 0;
     default: return pulse::fail(PULSE_EINVAL, "pulse_stoprule_set_option: unknown option");
     }
 }
@@ -687,9 +694,18 @@ int pulse_stoprule_stats(void* handle, int64_t* out4) {
     return 0;
 }
 
-int pulse_stoprule_long_stats(void* handle, int64_t* out4) {
+int pulse_stoprule_long_stats(void* handle, int64_t* out6) {
     PulseStopRule* h = static_cast<PulseStopRule*>(handle);
-    if (!h || !out4) return pulse::fail(PULSE_EINVAL, "pulse_stoprule_long_stats: null argument");
+    int64_t* const out4 = out6;
+    if (!h || !out6) return pulse::fail(PULSE_EINVAL, "pulse_stoprule_long_stats: null argument");
+    out6[4] = 0; out6[5] = 0;
+    if (h->early_counted) {                // (test use: the launches' stream is waited for, so that every peek of the newest launch is in)
+        long long counts[pulse::kLongWords * kVerdictStride];      // {settled, pending} at the head of each line
+        hipError_t e = h->last_stream || h->submitted ? hipStreamSynchronize(h->last_stream) : hipSuccess;
+        if (e == hipSuccess) e = hipMemcpy(counts, h->long_arrive + 2 * (1 + pulse::kLongWords) * kVerdictStride, sizeof counts, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return pulse::fail_hip((int)e, "pulse_stoprule_long_stats: the early verdicts' counters");
+        for (int k = 0; k < pulse::kLongWords; ++k) { out6[4] += counts[k * kVerdictStride]; out6[5] += counts[k * kVerdictStride + 1]; }
+    }
     if (int rc = pulse::long_word_written_once(h)) return rc;
     out4[0] = h->long_launches; out4[1] = h->long_taken; out4[2] = h->long_called_off;
     out4[3] = h->long_on && !h->long_off && h->mode == kModeLocal && !h->shm_asked && h->n_global == (long long)h->n_local && pulse::stoprule_pairs_supported(h, 1) ? 1 : 0;

@@ -267,7 +267,7 @@ class LaggedDoneCount:
         return int(self._lib.pulse_stoprule_side_launches(self.handle)) if self.handle is not None else 0
 
     OPT_VERDICT_WAIT_TICKS, OPT_ALLOW_SHARED_DEVICE_PAIRS, OPT_DEBUG_LATE_VERDICTS = 0, 1, 2     # pulse_env.h: PULSE_STOPRULE_OPT_*
-    OPT_LONG_LAUNCHES, OPT_DEBUG_SKIP_DECISION, OPT_DEBUG_RESIDENT_BLOCKS = 3, 4, 5
+    OPT_LONG_LAUNCHES, OPT_DEBUG_SKIP_DECISION, OPT_DEBUG_RESIDENT_BLOCKS, OPT_EARLY_VERDICTS = 3, 4, 5, 6
 
     def set_option(self, option: int, value: int) -> None:
         """Options of the native handle (pulse_stoprule_set_option): how long a paired launch waits for its verdict, whether
@@ -281,15 +281,17 @@ class LaggedDoneCount:
         the handle fall back to one check interval per launch), 'pairs': whether the handle would still pair,
         'side_stream_check_points'} -- bench.py reports the first three -- and, of the long launches (pulse_stoprule_long_stats;
         they count among the paired ones too): 'long_launches' issued, 'in_launch_verdicts' taken, check points 'called_off'
-        (the first one switches them off), 'long': whether the handle would still plan them."""
+        (the first one switches them off), 'long': whether the handle would still plan them, 'early_hits' / 'early_misses':
+        early looks at a verdict that found it settled / pending (counted under OPT_EARLY_VERDICTS 2 or 3 only)."""
         if self.handle is None:
             return {"paired_launches": 0, "verdict_timeouts": 0, "pairs": False, "side_stream_check_points": 0,
-                    "long_launches": 0, "in_launch_verdicts": 0, "called_off": 0, "long": False}
-        out, lng = (C.c_int64 * 4)(), (C.c_int64 * 4)()
+                    "long_launches": 0, "in_launch_verdicts": 0, "called_off": 0, "long": False, "early_hits": 0, "early_misses": 0}
+        out, lng = (C.c_int64 * 4)(), (C.c_int64 * 6)()
         _native.check(self._lib.pulse_stoprule_stats(self.handle, out), "pulse_stoprule_stats")
         _native.check(self._lib.pulse_stoprule_long_stats(self.handle, lng), "pulse_stoprule_long_stats")
         return {"paired_launches": int(out[0]), "verdict_timeouts": int(out[1]), "pairs": bool(out[2]), "side_stream_check_points": int(out[3]),
-                "long_launches": int(lng[0]), "in_launch_verdicts": int(lng[1]), "called_off": int(lng[2]), "long": bool(lng[3])}
+                "long_launches": int(lng[0]), "in_launch_verdicts": int(lng[1]), "called_off": int(lng[2]), "long": bool(lng[3]),
+                "early_hits": int(lng[4]), "early_misses": int(lng[5])}
 
     def publish(self) -> None:
         """Publish the newest check point's count now (pulse_stoprule_publish) instead of with the next launch that carries
