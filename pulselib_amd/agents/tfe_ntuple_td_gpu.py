@@ -26,7 +26,7 @@ agent as it was while it is off:
   `continue_games` (13.10; csrc/tfe_ntuple_continue.hip): with a small `max_steps` = K a round plays K moves of every game, and
     `pulse_tfe_nt_continue_pick` puts the cut games' boards into `start`, their scores so far into the carries and the ended games
     into `finished`; `eval_max_steps` gives the evaluations a cap of their own;
-  `rollout_deep_empty_max` = E (13.13; csrc/tfe_ntuple_adaptive_rollout.hip): with `rollout_layers` 2 the round's games are played and
+  `rollout_deep_empty_max` = E (13.13; csrc/tfe_ntuple_search_rollout.hip): with `rollout_layers` 2 the round's games are played and
     recorded by `pulse_tfe_nt_rollout_adaptive`, two layers deep on the boards with at most E empty cells and one on the others, with
     the backed values and from `start` where those are on;
   `set_shard` (13.14; csrc/tfe_ntuple_exchange.hip, tfe_ntuple_ranks.py): the agent plays a rank's share of the job's games, and

@@ -1,5 +1,5 @@
 // tfe_ntuple_device.h -- what the units of the 2048 n-tuple network share (tfe_ntuple.hip: the learner's four launches; tfe_ntuple_search.hip:
-// expectimax play, tfe_ntuple_search_deep.hip, two chance layers of it, and tfe_ntuple_search_rollout.hip, the roll-out under either; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes;
+// expectimax play, one or two chance layers deep, and tfe_ntuple_search_rollout.hip, the roll-out under either; tfe_ntuple_lambda.hip: the TD(lambda) walk; tfe_ntuple_tc.hip: temporal-coherence step sizes;
 // tfe_ntuple_backed.hip: search-backed targets; tfe_ntuple_restart.hip: roll-outs restarted from recorded boards;
 // tfe_ntuple_staged.hip: weight sets by tile stage, with the staged network and the stage of a board): the network as the
 // kernels take it, a feature's index, V of four afterstates at once, the learners' target, fixed-point difference and adds, their

@@ -66,10 +66,7 @@ extern "C" int pulse_tfe_nt_rollout_from(const PulseTfeNtRollout* o, int32_t lay
     Games g;
     if (int rc = check_rollout(o, name, &dev, &g)) return rc;
     if (int rc = check_start(layers, backed, start, name, "layers must be 0 or 1")) return rc;
-    g.backed = backed;
-    g.start = start;
-    if (int rc = backed ? launch_play<true, 0, 1, true, true>(layers, g, dev, o->net.symmetric != 0, stream)
-                        : launch_play<true, 0, 1, false, true>(layers, g, dev, o->net.symmetric != 0, stream)) return rc;
+    if (int rc = launch_play_from<0, 1, true>(layers, g, backed, start, dev, o->net.symmetric != 0, stream)) return rc;
     return finish_launch("pulse_tfe_nt_rollout_from launch");
 }
 

@@ -1,10 +1,11 @@
 // tfe_ntuple_search_device.h -- what the units of the n-tuple network's play share (tfe_ntuple.hip: one ply; tfe_ntuple_search.hip: one
-// chance layer; tfe_ntuple_search_deep.hip: two, section 13.4; tfe_ntuple_search_adaptive.hip: one or two by
-// the board's empty cells, section 13.11; tfe_ntuple_search_rollout.hip, _backed.hip,
-// _restart.hip and _staged.hip: the recording games, sections 13.5 to 13.9): the group of 32 lanes, the tile odds, the board
-// launch's refusals (check_search), the chance layer itself (search_q_move, one move; search_q, the four in turn), the two-layer deal
-// over a workgroup (search_q2 with live_slots and nth_set_bit), the choice between the two per board (search_q_adaptive), the one game kernel (tfe_nt_play_kernel) with its launch ladder (launch_play) and the one-layer board
-// kernel with its launch (launch_boards).  One copy each.  Not part of the ABI.
+// chance layer, DESIGN.md section 13.1, two, section 13.4, and one or two by the board's empty cells, section 13.11;
+// tfe_ntuple_search_rollout.hip, _backed.hip, _restart.hip and _staged.hip: the recording games, sections 13.5 to 13.13): the group of
+// 32 lanes, the tile odds, the board launch's refusals (check_search), the chance layer itself (search_q_move, one move; search_q, the
+// four in turn), the two-layer deal over a workgroup (search_q2 with live_slots and nth_set_bit), the choice between the two per board
+// (search_q_adaptive, on the network as NtAdaptiveDev), the one board kernel (tfe_nt_search_kernel) with its launch ladder
+// (launch_boards), and the one game kernel (tfe_nt_play_kernel) with its launch ladder (launch_play) and the step to it from an entry
+// point's `backed` / `start` (launch_play_from).  One copy each.  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,7 +43,7 @@ inline int check_layers(const int32_t layers, const char* name) {
     return layers == 1 || layers == 2 ? 0 : fail_named(name, "layers must be 1 or 2");
 }
 
-// ... and the threshold beside it, as the adaptive launches take it (tfe_ntuple_search_adaptive.hip, tfe_ntuple_adaptive_rollout.hip)
+// ... and the threshold beside it, as the adaptive launches take it (tfe_ntuple_search.hip, tfe_ntuple_search_rollout.hip)
 inline int check_deep_empty_max(const int32_t deep_empty_max, const char* name) {
     return deep_empty_max >= 0 && deep_empty_max <= 16 ? 0 : fail_named(name, "deep_empty_max must be in 0..16");
 }
@@ -56,11 +57,6 @@ inline int check_start(const int32_t layers, const double* backed, const uint64_
     if ((uintptr_t)start & 7u) return fail_named(name, "start must be 8-byte aligned");
     return 0;
 }
-
-// The launches of the one-layer kernels on the one-stage network (defined in tfe_ntuple_search.hip, which instantiates them), after
-// the checks: of the boards of `o` with the row table `lut`, and of the evaluation's games `g`
-void launch_search(const PulseTfeNtSearch& o, const NtDev& dev, const uint32_t* lut, void* stream);
-int launch_search_games(Games& g, const NtDev& dev, bool symmetric, void* stream);
 
 __device__ __forceinline__ int count_empty(const uint64_t key) {
     return __popc(tfe_nz_nibbles((uint32_t)key) ^ 0x88888888u) + __popc(tfe_nz_nibbles((uint32_t)(key >> 32)) ^ 0x88888888u);
@@ -229,7 +225,22 @@ __device__ __forceinline__ bool search_q_adaptive(const NtDev& net, const float*
     return deep;
 }
 
-// pulse_tfe_nt_search's struct as its one-layer kernel takes it
+// The one-stage network under that choice, as the adaptive launches hand it to the board and the game kernel: the threshold, and
+// where a game adds its moves at each depth -- [0] += those whose q came from two layers, [1] += those from one; null for boards, and
+// for games nobody counts.  Derived, as NtStagedDev is, so that the kernels of the fixed depths keep their arguments and their names.
+struct NtAdaptiveDev : NtDev {
+    int32_t deep_empty_max;
+    unsigned long long* depth_stats;
+};
+
+template <class Net>
+inline constexpr bool kAdaptive = std::is_same_v<Net, NtAdaptiveDev>;
+
+inline NtAdaptiveDev adaptive_of(const NtDev& dev, const int32_t deep_empty_max, int64_t* depth_stats) {
+    return NtAdaptiveDev{dev, deep_empty_max, reinterpret_cast<unsigned long long*>(depth_stats)};
+}
+
+// pulse_tfe_nt_search's struct as the board kernel takes it
 struct Boards {
     const float* weights;
     int32_t n_boards;
@@ -240,20 +251,38 @@ struct Boards {
     const uint32_t* lut;
 };
 
-// 32 lanes per board (pulse_tfe_nt_search, pulse_tfe_nt_search_staged): lane 0 of the group writes
-template <int IMG, class Net>
+// The one board kernel: the four q of board g, its greedy action and its candidates, on one of two mappings of a board to lanes, each
+// with its q.  32 lanes per board: search_q, and a group beyond the batch leaves at once (nothing below meets the workgroup).  A
+// workgroup per board: g is blockIdx.x (grid = n_boards), so the 256 lanes carry the board alike and meet the two barriers of
+// search_q2 -- of search_q_adaptive on NtAdaptiveDev, on either side of the branch the board alone decides -- together.  The first lane
+// of the board's lanes writes.
+template <int LANES /* 32 (kGroup) or 256 (kSearchBlock) per board */, int IMG, class Net>
 __global__ __launch_bounds__(kSearchBlock) void tfe_nt_search_kernel(const Boards o, const Net net) {
-    const int g = (int)blockIdx.x * kGroupsPerBlock + ((int)threadIdx.x >> 5), s = (int)threadIdx.x & (kGroup - 1);
-    if (g >= o.n_boards) return;
+    static_assert(LANES == kGroup || (LANES == kSearchBlock && !kStaged<Net>), "search_q2 takes the one-stage network only");
+    static_assert(!kAdaptive<Net> || LANES == kSearchBlock, "search_q_adaptive is a workgroup's");
+    const int g = LANES == kGroup ? (int)blockIdx.x * kGroupsPerBlock + ((int)threadIdx.x >> 5) : (int)blockIdx.x;
+    if constexpr (LANES == kGroup) {
+        if (g >= o.n_boards) return;
+    }
     const uint64_t key_b = o.boards[g];
     uint64_t ka[4];
     int sc[4];
     moves4(key_b, o.lut, ka, sc);
     double q[4];
-    search_q<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, s, q);
+    if constexpr (LANES == kGroup) {
+        search_q<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, (int)threadIdx.x & (kGroup - 1), q);
+    } else {
+        __shared__ double terms[4 * kGroup];
+        if constexpr (kAdaptive<Net>) {
+            __shared__ double qs[4];
+            search_q_adaptive<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, net.deep_empty_max, terms, qs, q);
+        } else {
+            search_q2<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, terms, q);
+        }
+    }
     uint32_t bits;
     const int best = greedy_of(q, key_b, ka, o.tie_seed, o.round, &bits);
-    if (s == 0) {
+    if (((int)threadIdx.x & (LANES - 1)) == 0) {
 #pragma unroll
         for (int a = 0; a < 4; ++a) o.q[(size_t)g * 4 + a] = q[a];
         o.action[g] = (int8_t)best;
@@ -261,17 +290,29 @@ __global__ __launch_bounds__(kSearchBlock) void tfe_nt_search_kernel(const Board
     }
 }
 
+// The one launch ladder of the boards, after the checks: the mapping of `layers` (1: 32 lanes per board, 2: 256), which the caller has
+// checked to be one its network has -- the staged network one layer, the adaptive network (the threshold in it) the workgroup alone.
 template <class Net>
-void launch_boards(const PulseTfeNtSearch& o, const Net& net, const uint32_t* lut, void* stream) {
+void launch_boards(const int layers, const PulseTfeNtSearch& o, const Net& net, const uint32_t* lut, void* stream) {
     const Boards b{o.net.weights, o.n_boards, o.gamma, o.tie_seed, o.round, o.boards, o.q, o.action, o.candidates, lut};
-    const dim3 grid((unsigned)(((int64_t)o.n_boards + kGroupsPerBlock - 1) / kGroupsPerBlock)), block(kSearchBlock);
-    if (o.net.symmetric) hipLaunchKernelGGL((tfe_nt_search_kernel<8, Net>), grid, block, 0, (hipStream_t)stream, b, net);
-    else hipLaunchKernelGGL((tfe_nt_search_kernel<1, Net>), grid, block, 0, (hipStream_t)stream, b, net);
+    const auto launch = [&](auto lanes) {
+        constexpr int LANES = decltype(lanes)::value;
+        const dim3 grid((unsigned)(((int64_t)o.n_boards * LANES + kSearchBlock - 1) / kSearchBlock)), block(kSearchBlock);
+        if (o.net.symmetric) hipLaunchKernelGGL((tfe_nt_search_kernel<LANES, 8, Net>), grid, block, 0, (hipStream_t)stream, b, net);
+        else hipLaunchKernelGGL((tfe_nt_search_kernel<LANES, 1, Net>), grid, block, 0, (hipStream_t)stream, b, net);
+    };
+    if constexpr (!kAdaptive<Net>) {
+        if (layers == 1) launch(std::integral_constant<int, kGroup>{});
+    }
+    if constexpr (!kStaged<Net>) {
+        if (layers == 2) launch(std::integral_constant<int, kSearchBlock>{});
+    }
 }
 
 // The one game kernel: play_game<Record, Backed, From> on one of three mappings of a game to lanes, each with the q its policy plays on.
 template <int LANES /* 1, 32 (kGroup) or 256 (kSearchBlock) per game */, int IMG, bool Record, bool Backed, bool From, class Net>
 __global__ __launch_bounds__(kSearchBlock) void tfe_nt_play_kernel(const Games o, const Net net) {
+    static_assert(!kAdaptive<Net> || (LANES == kSearchBlock && !kStaged<Net>), "search_q_adaptive is a workgroup's, on the one-stage network");
     constexpr int kCounters = Record ? 2 : kEvalBins;
     __shared__ unsigned long long wg[kCounters];
     if (threadIdx.x < kCounters) wg[threadIdx.x] = 0ull;
@@ -298,25 +339,47 @@ __global__ __launch_bounds__(kSearchBlock) void tfe_nt_play_kernel(const Games o
                                         });
     } else {
         // One game per workgroup: g is blockIdx.x (grid = n_games), so the 256 lanes play the game alike -- the same boards, draws and
-        // length -- and thread 0 writes and counts.  Nothing lane-dependent encloses q_of: search_q2's two barriers per move are
-        // reached by the 256 lanes together, which leave the loop at the same move, and `writer` guards stores only.
+        // length -- and thread 0 writes and counts.  Nothing lane-dependent encloses q_of: search_q2's two barriers per move --
+        // search_q_adaptive's, on either side of a branch the board alone decides -- are reached by the 256 lanes together, which
+        // leave the loop at the same move, and `writer` guards stores only, with Record, Backed and From alike.
+        // From: thread 0 stores 0 into an unusable start[g] while a slower wavefront may not have read the word yet.  The word is
+        // 8-byte aligned (the entry points check it) and read and written as one 64-bit access, so such a lane reads either the
+        // unusable word as it was or 0; 0 is itself unusable (play_game tests key0 != 0 first), so every lane falls back to the reset
+        // board: the four wavefronts decide alike whichever they read.  A usable word is never written.
+        // On NtAdaptiveDev (DESIGN.md sections 13.11 and 13.13) the q is search_q_adaptive's, with four LDS words of its own, and the
+        // closure counts the moves at each depth; thread 0 adds the two counts once, after the game.
         static_assert(LANES == kSearchBlock, "a game is played by 1, 32 or 256 lanes");
         __shared__ double terms[4 * kGroup];
         __syncthreads();
+        [[maybe_unused]] uint32_t depths = 0u;                                         // deep moves + 65,536 * shallow moves: a game has at most 65,535
         play_game<Record, Backed, From>(o, wg, (int)blockIdx.x, threadIdx.x == 0,
                                         [&](const uint64_t key_b, const uint64_t (&ka)[4], const int (&sc)[4], double (&v)[4], double (&q)[4]) {
                                             if constexpr (Record) values4<IMG>(net, o.weights, ka, v);
-                                            search_q2<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, terms, q);
+                                            if constexpr (kAdaptive<Net>) {
+                                                __shared__ double qs[4];
+                                                const bool deep = search_q_adaptive<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, net.deep_empty_max, terms, qs, q);
+                                                depths += deep ? 1u : 65536u;
+                                            } else {
+                                                search_q2<IMG>(net, o.weights, o.lut, o.gamma, key_b, ka, sc, terms, q);
+                                            }
                                         });
+        if constexpr (kAdaptive<Net>) {
+            if (threadIdx.x == 0 && net.depth_stats) {
+                atomicAdd(net.depth_stats, (unsigned long long)(depths & 65535u));
+                atomicAdd(net.depth_stats + 1, (unsigned long long)(depths >> 16));
+            }
+        }
     }
 }
 
 // The one launch ladder of the games, after the checks: fetches the row table, and launches the mapping of `layers` (0: one lane
 // per game, 1: 32, 2: 256), which the caller has checked to be in MinLayers..MaxLayers -- the depths its unit builds, so a unit
-// instantiates the kernels it can launch and no others.  A backed value needs a search: Backed builds no one-ply form.
+// instantiates the kernels it can launch and no others.  A backed value needs a search: Backed builds no one-ply form.  The adaptive
+// network (the threshold and the counts' address in it) has the 256-lane mapping alone: its launches say 2 .. 2.
 template <bool Record, int MinLayers, int MaxLayers, bool Backed = false, bool From = false, class Net>
 int launch_play(const int layers, Games& g, const Net& net, const bool symmetric, void* stream) {
     static_assert(0 <= MinLayers && MinLayers <= MaxLayers && MaxLayers <= (kStaged<Net> ? 1 : 2), "search_q2 takes the one-stage network only");
+    static_assert(!kAdaptive<Net> || MinLayers == 2, "search_q_adaptive is a workgroup's");
     if (int rc = pulse::tfe_row_lut(&g.lut)) return rc;
     const auto launch = [&](auto lanes) {
         constexpr int LANES = decltype(lanes)::value;
@@ -334,6 +397,21 @@ int launch_play(const int layers, Games& g, const Net& net, const bool symmetric
         if (layers == 2) launch(std::integral_constant<int, kSearchBlock>{});
     }
     return 0;
+}
+
+// The one step from `backed` / `start` as a recording entry point got them (either may be null) to launch_play's Backed / From, with
+// g.backed / g.start set.  NeedStart: the entry point has refused a null `start`, so its unit builds no form without From.
+template <int MinLayers, int MaxLayers, bool NeedStart, class Net>
+int launch_play_from(const int layers, Games& g, double* backed, uint64_t* start, const Net& net, const bool symmetric, void* stream) {
+    g.backed = backed;
+    g.start = start;
+    const auto launch = [&](auto with_backed, auto from) {
+        return launch_play<true, MinLayers, MaxLayers, decltype(with_backed)::value, decltype(from)::value>(layers, g, net, symmetric, stream);
+    };
+    if constexpr (!NeedStart) {
+        if (!start) return backed ? launch(std::true_type{}, std::false_type{}) : launch(std::false_type{}, std::false_type{});
+    }
+    return backed ? launch(std::true_type{}, std::true_type{}) : launch(std::false_type{}, std::true_type{});
 }
 
 }  // namespace pulse_tfe

@@ -66,10 +66,7 @@ extern "C" int pulse_tfe_nt_rollout_staged(const PulseTfeNtRollout* o, const Pul
     if (int rc = check_rollout(o, name, &dev, &g)) return rc;
     if (int rc = check_stages(stages, o->net, dev, name, &net)) return rc;
     if (int rc = check_start(layers, backed, start, name, kStagedLayers)) return rc;
-    g.backed = backed;
-    g.start = start;
-    if (int rc = backed ? launch_play<true, 0, 1, true, true>(layers, g, net, o->net.symmetric != 0, stream)
-                        : launch_play<true, 0, 1, false, true>(layers, g, net, o->net.symmetric != 0, stream)) return rc;
+    if (int rc = launch_play_from<0, 1, true>(layers, g, backed, start, net, o->net.symmetric != 0, stream)) return rc;
     return finish_launch("pulse_tfe_nt_rollout_staged launch");
 }
 
@@ -107,6 +104,6 @@ extern "C" int pulse_tfe_nt_search_staged(const PulseTfeNtSearch* o, const Pulse
     if (int rc = check_search(o, name, &dev)) return rc;
     if (int rc = check_stages(stages, o->net, dev, name, &net)) return rc;
     if (int rc = pulse::tfe_row_lut(&lut)) return rc;
-    launch_boards(*o, net, lut, stream);
+    launch_boards(1, *o, net, lut, stream);
     return finish_launch("pulse_tfe_nt_search_staged launch");
 }

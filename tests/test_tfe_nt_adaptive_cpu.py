@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from tests.native_args import assert_refusals, remarks
-from tests.tfe_nt_support import CASES, CRAFTED, MORE, ROOT, SEARCH_CASES, TUPLES, assert_exports, assert_no_scratch, bits, opts, play_kernel, weights
+from tests.tfe_nt_support import CASES, CRAFTED, MORE, ROOT, SEARCH_CASES, SEARCH_UNIT, TUPLES, assert_exports, assert_no_scratch, bits, listed, opts, play_kernel, weights
 from tests.tfe_nt_support import nt as _nt
 from tests.tfe_search_host import key_of, scalar_search_on_host
 
@@ -189,22 +189,15 @@ def test_the_hosts_games_end_are_cut_and_move_at_both_depths(name, epsilon, symm
 
 
 # ------------------------------------------------------------------ the compiler's remarks
-def _occupancy(text, kernel):
-    """waves per SIMD of the LAST block of remarks in `text` whose kernel's name holds `kernel`"""
-    found = re.findall(r"Function Name: \S*" + re.escape(kernel) + r"\S*.*?Occupancy \[waves/SIMD\]: (\d+)", text, flags=re.S)
-    assert found, kernel
-    return int(found[-1])
-
-
 def test_adaptive_search_kernels_use_no_scratch_and_keep_their_siblings_occupancy():
-    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search_adaptive.hip with the Makefile's flags: four kernels, none with scratch or a
-    spilled vector register, each with at least the waves per SIMD of its two-layer sibling as profiles/tfe_mc/kernel_resource_usage.txt
-    last lists it.  VGPRs as built: boards 157 (symmetric) / 130, games 194 / 167."""
-    target = "ntuple-search-adaptive-resource-usage"
-    assert_no_scratch(target, {"tfe_nt_search_adaptive_kernel": 2, "tfe_nt_play_adaptive_kernel": 2}, 256)
-    listed = (ROOT / "profiles" / "tfe_mc" / "kernel_resource_usage.txt").read_text()
-    listed = listed[:listed.index("tfe_ntuple_search_adaptive.hip")]        # (the siblings, not this unit's own lines)
+    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search.hip with the Makefile's flags: twelve kernels, none with scratch or a
+    spilled vector register, each of the four on NtAdaptiveDev with at least the waves per SIMD of its two-layer sibling as
+    profiles/tfe_mc/kernel_resource_usage.txt lists it ahead of the merged unit.  VGPRs as built: boards 157 (symmetric) / 130, games 192 / 165."""
+    target, waves = "ntuple-search-resource-usage", "Occupancy [waves/SIMD]"
+    assert_no_scratch(target, SEARCH_UNIT, 256)
+    older = (ROOT / "profiles" / "tfe_mc" / "kernel_resource_usage.txt").read_text()
+    older = older[:older.index("tfe_ntuple_search.hip (merged)")]          # (the siblings, not this unit's own lines)
     for img in (8, 1):
-        for mine, sibling in (("tfe_nt_search_adaptive_kernelILi%dE" % img, "tfe_nt_search2_kernelILi%dE" % img),
-                              ("tfe_nt_play_adaptive_kernelILi%dE" % img, play_kernel(256, img, False))):
-            assert _occupancy(remarks(target), mine) >= _occupancy(listed, sibling) >= 2, (mine, sibling)
+        for mine, sibling in (("tfe_nt_search_kernelILi256ELi%dENS_13NtAdaptiveDevE" % img, "tfe_nt_search2_kernelILi%dE" % img),
+                              (play_kernel(256, img, False, net="NtAdaptiveDev"), play_kernel(256, img, False))):
+            assert listed(remarks(target), mine, waves) >= listed(older, sibling, waves) >= 2, (mine, sibling)

@@ -1,5 +1,5 @@
 """The 2048 n-tuple network's expectimax play at a depth the board's empty cells choose, on the device (DESIGN.md section 13.11;
-csrc/tfe_ntuple_search_adaptive.hip: pulse_tfe_nt_search_adaptive, pulse_tfe_nt_evaluate_search_adaptive) against the host's statement
+csrc/tfe_ntuple_search.hip: pulse_tfe_nt_search_adaptive, pulse_tfe_nt_evaluate_search_adaptive) against the host's statement
 of it (search_adaptive_nt_on_host; tests/tfe_adaptive_host.py: the oracle's environment under it) and against the two searches it
 chooses between.  Every comparison is exact: integers word for word, float64 as bit patterns.  Every buffer a launch is handed sits
 between guard words, the two depth counters too.

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from tests.native_args import PTR, assert_refusals, resource_usage
-from tests.tfe_nt_support import CASES, ROOT, TUPLES, assert_exports, assert_no_scratch, bits, opts, play_kernel, weights
+from tests.tfe_nt_support import CASES, ROLLOUT_UNIT, ROOT, TUPLES, assert_exports, assert_no_scratch, bits, listed, opts, play_kernel, weights
 from tests.tfe_nt_support import nt as _nt
 
 ENTRY = "pulse_tfe_nt_rollout_adaptive"
@@ -53,8 +53,9 @@ def test_library_exports_the_entry_point():
     comment = text[text.rindex("/* ----", 0, at):at]
     for words in ("n <= deep_empty_max", "NETWORK's V", "never zeroed", "deep_empty_max must be in", "in this order", "backed:", "start:", "depth_stats:"):
         assert words in comment, words
-    unit = (ROOT / "pulselib_amd" / "csrc" / "tfe_ntuple_adaptive_rollout.hip").read_text()
-    assert "play_game<true, Backed, From>" in unit and "search_q_adaptive<IMG>" in unit and "values4<IMG>" in unit
+    unit = (ROOT / "pulselib_amd" / "csrc" / "tfe_ntuple_search_device.h").read_text()          # ... of which the one game kernel's 256-lane branch:
+    unit = unit[unit.index("static_assert(LANES == kSearchBlock"):unit.index("int launch_play(")]
+    assert "play_game<Record, Backed, From>" in unit and "search_q_adaptive<IMG>" in unit and "values4<IMG>" in unit
     assert unit.index("values4<IMG>") < unit.index("search_q_adaptive<IMG>(net")         # V of the afterstates before the search starts
 
 
@@ -245,31 +246,23 @@ def test_the_games_from_start_are_those_of_the_header():
 
 
 # ------------------------------------------------------------------ what the compiler made of the kernels
-def _listed(text, kernel, field):
-    """`field` of the LAST block of remarks in `text` whose kernel's name holds `kernel`"""
-    found = re.findall(r"Function Name: \S*" + re.escape(kernel) + r"\S*.*?" + re.escape(field) + r": (\d+)", text, flags=re.S)
-    assert found, kernel
-    return int(found[-1])
-
-
 def test_the_kernels_use_no_scratch_and_keep_their_siblings_occupancy():
-    """profiles/tfe_mc/kernel_resource_usage.txt's section of csrc/tfe_ntuple_adaptive_rollout.hip: eight kernels, none with scratch or a
-    spilled vector register, each with the waves per SIMD of its two-layer recording sibling tfe_nt_play_kernel<256, IMG, true, Backed,
-    false, NtDev> as the file lists it (2); and hipcc --offload-arch=gfx950 on the unit with the Makefile's flags gives the section's
-    figures.  VGPRs as built: 204 (symmetric) / 177, with the backed value 206 / 179, with or without From."""
+    """profiles/tfe_mc/kernel_resource_usage.txt's section of the merged csrc/tfe_ntuple_search_rollout.hip: twelve kernels, none with
+    scratch or a spilled vector register, each of the eight on NtAdaptiveDev with the waves per SIMD of its two-layer recording sibling
+    tfe_nt_play_kernel<256, IMG, true, Backed, false, NtDev> as the file lists it ahead of the section (2); and hipcc --offload-arch=gfx950 on the unit with the Makefile's
+    flags gives the section's figures.  VGPRs as built: the sibling's, 202 (symmetric) / 175 and with the backed value 204 / 177; 178 with the backed value and From, not symmetric."""
     text = (ROOT / "profiles" / "tfe_mc" / "kernel_resource_usage.txt").read_text()
-    at = text.index("tfe_ntuple_adaptive_rollout.hip (new)")
-    older, mine = text[:at], text[at:]
-    assert len(re.findall(r"Function Name:", mine)) == 8
-    target = "ntuple-adaptive-rollout-resource-usage"
-    names = assert_no_scratch(target, {"tfe_nt_record_adaptive_kernelILi%dELb%dELb%dE" % (img, b, f): 1 for img in (8, 1) for b in (0, 1) for f in (0, 1)}, 256)
+    older, _, mine = text.partition("tfe_ntuple_search_rollout.hip (merged)")
+    assert len(re.findall(r"Function Name:", mine)) == 12
+    target = "ntuple-search-rollout-resource-usage"
+    names = assert_no_scratch(target, ROLLOUT_UNIT, 256)
     _, vgprs, _, _ = resource_usage(target)
     for img in (8, 1):
         for backed in (0, 1):
             sibling = play_kernel(256, img, True, bool(backed))
             for start in (0, 1):
-                kernel = "tfe_nt_record_adaptive_kernelILi%dELb%dELb%dE" % (img, backed, start)
-                assert _listed(mine, kernel, "ScratchSize [bytes/lane]") == 0 and _listed(mine, kernel, "VGPRs Spill") == 0, kernel
-                assert _listed(mine, kernel, "Occupancy [waves/SIMD]") >= _listed(older, sibling, "Occupancy [waves/SIMD]") == 2, kernel
+                kernel = play_kernel(256, img, True, bool(backed), bool(start), net="NtAdaptiveDev")
+                assert listed(mine, kernel, "ScratchSize [bytes/lane]") == 0 and listed(mine, kernel, "VGPRs Spill") == 0, kernel
+                assert listed(mine, kernel, "Occupancy [waves/SIMD]") >= listed(older, sibling, "Occupancy [waves/SIMD]") == 2, kernel
                 built = vgprs[next(i for i, name in enumerate(names) if kernel in name)]
-                assert built == _listed(mine, kernel, " VGPRs") <= _listed(older, sibling, " VGPRs") + 2, (kernel, built)
+                assert built == listed(mine, kernel, " VGPRs") <= listed(older, sibling, " VGPRs") + 2, (kernel, built)

@@ -1,5 +1,5 @@
 """The 2048 n-tuple network's training roll-out at the adaptive search depth, on the device (DESIGN.md section 13.13;
-csrc/tfe_ntuple_adaptive_rollout.hip: pulse_tfe_nt_rollout_adaptive) against the host's statement of it
+csrc/tfe_ntuple_search_rollout.hip: pulse_tfe_nt_rollout_adaptive) against the host's statement of it
 (tests/tfe_adaptive_rollout_host.py: the oracle's environment under search_adaptive_nt_on_host, recording V of the chosen afterstate
 and search_backed_on_host of the q), against the two-layer recording launches at E = 16, and through the agent: whole rounds with
 backed targets, games continued across rounds and restarted rounds.  Every comparison is exact: integers word for word, float64 and

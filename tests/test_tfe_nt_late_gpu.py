@@ -1,6 +1,6 @@
 """The 2048 n-tuple network's three newest units on the device, at the limits and on late boards: weight sets
 by tile stage (section 13.9; csrc/tfe_ntuple_staged.hip), games continued across rounds (section 13.10; csrc/tfe_ntuple_continue.hip)
-and the search whose depth the empty cells choose (section 13.11; csrc/tfe_ntuple_search_adaptive.hip), against the host's statement of
+and the search whose depth the empty cells choose (section 13.11; csrc/tfe_ntuple_search.hip), against the host's statement of
 them.  Every comparison is exact: integers word for word, float64 and float32 as bit patterns.  Every buffer a launch is handed sits
 between guard words, and the rows of keys / values / steps / backed at and beyond a game's length must keep what they held.  The
 premises a case rests on -- stages reached, games capped, dead and cut, boards deep and shallow -- are the HOST's counts, asserted

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests.native_args import assert_refusals
-from tests.tfe_nt_support import CASES, CRAFTED, P, SEARCH_CASES, TUPLES, assert_exports, assert_no_scratch, play_kernels, bits, opts, weights
+from tests.tfe_nt_support import CASES, CRAFTED, P, SEARCH_CASES, SEARCH_UNIT, TUPLES, assert_exports, assert_no_scratch, bits, opts, weights
 from tests.tfe_nt_support import nt as _nt
 from tests.tfe_search_host import key_of, scalar_search_on_host
 
@@ -173,6 +173,6 @@ def test_python_layer():
 
 
 def test_deep_search_kernels_use_no_scratch():
-    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search_deep.hip with the Makefile's flags: four kernels, none with scratch or a
-    spilled vector register.  VGPRs as built: boards 157 (symmetric) / 131, games 191 / 165."""
-    assert_no_scratch("ntuple-search-deep-resource-usage", {"tfe_nt_search2_kernel": 2, **play_kernels(256, False)}, 256)
+    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search.hip with the Makefile's flags: twelve kernels, the four of two layers among
+    them, none with scratch or a spilled vector register.  VGPRs as built: boards 157 (symmetric) / 131, games 191 / 165."""
+    assert_no_scratch("ntuple-search-resource-usage", SEARCH_UNIT, 256)

@@ -1,5 +1,5 @@
 """The 2048 n-tuple network's expectimax play two chance layers deep on the device (DESIGN.md section 13.4;
-csrc/tfe_ntuple_search_deep.hip: pulse_tfe_nt_search_deep, pulse_tfe_nt_evaluate_search_deep) against the host's statement of it
+csrc/tfe_ntuple_search.hip: pulse_tfe_nt_search_deep, pulse_tfe_nt_evaluate_search_deep) against the host's statement of it
 (search_nt_on_host(layers=2); tests/tfe_search_host.py: the oracle's environment under it).  Every comparison is exact: integers word
 for word, float64 as bit patterns.  Every buffer a launch is handed sits between guard words.
 

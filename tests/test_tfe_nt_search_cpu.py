@@ -9,7 +9,7 @@ from fractions import Fraction
 import numpy as np
 
 from tests.native_args import assert_refusals
-from tests.tfe_nt_support import BATCH, CASES, CRAFTED, EPSILON, NET_CASES, P, ROOT, SEARCH_CASES, TUPLES, WEIGHTS, assert_exports, assert_no_scratch, play_kernels, bits, opts, weights
+from tests.tfe_nt_support import BATCH, CASES, CRAFTED, EPSILON, NET_CASES, P, ROOT, SEARCH_CASES, SEARCH_UNIT, TUPLES, WEIGHTS, assert_exports, assert_no_scratch, bits, opts, weights
 from tests.tfe_nt_support import nt as _nt
 from tests.tfe_search_host import key_of
 
@@ -211,6 +211,6 @@ def test_the_sum_is_the_tree():
 
 # ------------------------------------------------------------------ what the compiler made
 def test_search_kernels_use_no_scratch():
-    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search.hip with the Makefile's flags: four kernels, none with scratch or a spilled
-    vector register.  VGPRs as built: search 138 (symmetric) / 112, games 152 / 97."""
-    assert_no_scratch("ntuple-search-resource-usage", {"tfe_nt_search_kernel": 2, **play_kernels(32, False)}, 256)
+    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search.hip with the Makefile's flags: twelve kernels, this file's four at 32 lanes among
+    them, none with scratch or a spilled vector register.  VGPRs as built: search 138 (symmetric) / 112, games 152 / 97."""
+    assert_no_scratch("ntuple-search-resource-usage", SEARCH_UNIT, 256)

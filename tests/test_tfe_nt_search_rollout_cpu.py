@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests.native_args import assert_refusals
-from tests.tfe_nt_support import BOARD_ID0, CASES, CRAFTED, P, TUPLES, assert_exports, assert_no_scratch, play_kernels, bits, opts, weights
+from tests.tfe_nt_support import BOARD_ID0, CASES, CRAFTED, P, ROLLOUT_UNIT, TUPLES, assert_exports, assert_no_scratch, bits, opts, weights
 from tests.tfe_nt_support import nt as _nt
 from tests.tfe_search_host import key_of, search_games_on_host
 from tests.tfe_search_rollout_host import search_rollout_on_host
@@ -152,6 +152,6 @@ def test_one_board_worked_by_hand():
 
 # ------------------------------------------------------------------ what the compiler made of the kernels
 def test_search_rollout_kernels_use_no_scratch():
-    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search_rollout.hip with the Makefile's flags: four kernels, none with scratch or
-    a spilled vector register.  VGPRs as built: one layer 158 (symmetric) / 133, two layers 202 / 175."""
-    assert_no_scratch("ntuple-search-rollout-resource-usage", {**play_kernels(32, True), **play_kernels(256, True)}, 256)
+    """hipcc --offload-arch=gfx950 on csrc/tfe_ntuple_search_rollout.hip with the Makefile's flags: twelve kernels, this file's four among
+    them, none with scratch or a spilled vector register.  VGPRs as built: one layer 158 (symmetric) / 133, two layers 202 / 175."""
+    assert_no_scratch("ntuple-search-rollout-resource-usage", ROLLOUT_UNIT, 256)

@@ -1,4 +1,4 @@
-"""The host's side of the n-tuple network's play under the search whose depth the board chooses (csrc/tfe_ntuple_search_adaptive.hip;
+"""The host's side of the n-tuple network's play under the search whose depth the board chooses (csrc/tfe_ntuple_search.hip;
 DESIGN.md section 13.11), for the tests: tests/tfe_host.py's game loop on the oracle's environment, the live boards of a move split by
 their empty cells and searched by search_nt_on_host once per depth.  A helper, not a test."""
 import functools

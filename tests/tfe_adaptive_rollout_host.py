@@ -1,4 +1,4 @@
-"""The host's side of the n-tuple network's training roll-out at the adaptive search depth (csrc/tfe_ntuple_adaptive_rollout.hip;
+"""The host's side of the n-tuple network's training roll-out at the adaptive search depth (csrc/tfe_ntuple_search_rollout.hip;
 DESIGN.md section 13.13), for the tests: tests/tfe_adaptive_host.py's policy -- the live boards of a move searched at the depth their
 empty cells choose -- which also hands the game loop the value a move records, the NETWORK's V of the chosen afterstate, and keeps per
 move the value the search backed up at that depth.  One search per move (search_adaptive_nt_on_host gives the q, the action and

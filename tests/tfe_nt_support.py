@@ -255,6 +255,20 @@ def play_kernels(lanes, record, backed=False, start=False, net="NtDev"):
     return {play_kernel(lanes, img, record, backed, start, net): 1 for img in (8, 1)}
 
 
+# The twelve kernels each of csrc/tfe_ntuple_search.hip -- tfe_nt_search_kernel<LANES, IMG, Net> and the evaluations' games at one layer, at two
+# and at the adaptive depth -- and of csrc/tfe_ntuple_search_rollout.hip: the recording games at one layer, at two and, Backed x From, at the adaptive depth
+SEARCH_UNIT = {**{"tfe_nt_search_kernelILi%dELi%dENS_%sEEE" % (lanes, img, net): 1 for lanes, net in ((32, "5NtDev"), (256, "5NtDev"), (256, "13NtAdaptiveDev")) for img in (8, 1)},
+               **play_kernels(32, False), **play_kernels(256, False), **play_kernels(256, False, net="NtAdaptiveDev")}
+ROLLOUT_UNIT = {**play_kernels(32, True), **play_kernels(256, True), **{k: 1 for b in (False, True) for f in (False, True) for k in play_kernels(256, True, b, f, "NtAdaptiveDev")}}
+
+
+def listed(text, kernel, field):
+    """`field` of the LAST block of the compiler's remarks in `text` whose kernel's name holds `kernel`"""
+    found = re.findall(r"Function Name: \S*" + re.escape(kernel) + r"\S*.*?" + re.escape(field) + r": (\d+)", text, flags=re.S)
+    assert found, kernel
+    return int(found[-1])
+
+
 def assert_no_scratch(target, counts, max_vgprs):
     """The kernels of csrc's `make <target>` are those of `counts` {a substring of the name: how many}, none with scratch or a spilled
     vector register, none above max_vgprs.  Returns their names."""

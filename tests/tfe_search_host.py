@@ -1,5 +1,5 @@
 """The host's side of the n-tuple network's expectimax play, one or two chance layers deep (csrc/tfe_ntuple_search.hip,
-csrc/tfe_ntuple_search_deep.hip), for the tests: tests/tfe_host.py's game loop on the oracle's environment under search_nt_on_host,
+csrc/tfe_ntuple_search.hip), for the tests: tests/tfe_host.py's game loop on the oracle's environment under search_nt_on_host,
 packed boards from lists of nibbles, and the definition once more as plain recursive Python over one board.  A helper, not a test."""
 import numpy as np
 
