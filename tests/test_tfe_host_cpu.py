@@ -1,4 +1,4 @@
-"""The unified host roll-out (tests/tfe_host.py) held to what the four roll-outs it replaced returned, as recorded from them: a digest
+"""The unified host roll-out (tests/tfe_host.py, and under the n-tuple network's policy tests/tfe_nt_host.py) held to what the four roll-outs it replaced returned, as recorded from them: a digest
 of the arrays a device roll-out is compared with, and the counts.  The digest: the first 16 hex digits of SHA-256 over the C-contiguous
 bytes of keys, (values,) steps, lengths, total_score, episode_reward (, final_boards)."""
 import hashlib
@@ -58,6 +58,6 @@ NT_PINS = [(lambda: np.zeros(16 ** 4 + 16 ** 6, dtype=np.float32), True, 48, 0, 
 def test_ntuple_rollouts_are_the_recorded_ones(weights, symmetric, max_steps, round, want):
     """16 games, the tuples (0, 1, 2, 3) and (4, 5, 6, 8, 9, 10), epsilon .25, gamma 1, seed 8, board_id0 3"""
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import AGENT_KEY, TIE_KEY
-    from tests.tfe_host import rollout_nt_on_host
-    o = rollout_nt_on_host(16, max_steps, 0.25, 1.0, weights(), ((0, 1, 2, 3), (4, 5, 6, 8, 9, 10)), symmetric, 8, 8 ^ AGENT_KEY, 8 ^ TIE_KEY, 3, round)
+    from tests.tfe_nt_host import nt_games_on_host
+    o = nt_games_on_host(16, max_steps, 0.25, 1.0, weights(), ((0, 1, 2, 3), (4, 5, 6, 8, 9, 10)), symmetric, 8, 8 ^ AGENT_KEY, 8 ^ TIE_KEY, 3, round)
     assert (_digest(o, NT), int(o["lengths"].sum()), int(o["total_score"].sum()), o["greedy"], o["ended"], o["truncated"], o["capped"]) == want

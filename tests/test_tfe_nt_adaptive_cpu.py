@@ -174,10 +174,10 @@ def test_script_refuses_the_option_where_it_does_not_apply(capsys):
     ("seeded", 0.0, True, [213, 244], 5, 1043, 694), ("seeded", .25, True, [101, 132, 178, 209], 3, 762, 626),
     ("seeded", .25, False, [143, 155, 157, 244], 3, 593, 874), ("zero", .25, True, [], 7, 330, 1462)])
 def test_the_hosts_games_end_are_cut_and_move_at_both_depths(name, epsilon, symmetric, ended, cut, deep, shallow):
-    """tests/tfe_adaptive_host.py's games, as tests/test_tfe_nt_adaptive_gpu.py holds the device to them (about 2 s per case): on the seeded
+    """tests/tfe_nt_adaptive_support.py's games, as tests/test_tfe_nt_adaptive_gpu.py holds the device to them (about 2 s per case): on the seeded
     weights at least two games end, no two of them equally long; in every case at least two are cut, none is capped and each depth
     decides at least 200 moves.  The counts are those of the rehearsal, so that a change of the host's games is seen here."""
-    from tests.tfe_adaptive_host import CASES as PLAYED, GAMES, MAX_STEPS, host_games
+    from tests.tfe_nt_adaptive_support import CASES as PLAYED, GAMES, MAX_STEPS, host_games
     assert (name, epsilon, symmetric) in PLAYED
     want = host_games(name, epsilon, symmetric)
     L = want["lengths"]

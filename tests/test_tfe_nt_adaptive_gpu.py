@@ -1,10 +1,10 @@
 """The 2048 n-tuple network's expectimax play at a depth the board's empty cells choose, on the device (DESIGN.md section 13.11;
 csrc/tfe_ntuple_search.hip: pulse_tfe_nt_search_adaptive, pulse_tfe_nt_evaluate_search_adaptive) against the host's statement
-of it (search_adaptive_nt_on_host; tests/tfe_adaptive_host.py: the oracle's environment under it) and against the two searches it
+of it (search_adaptive_nt_on_host; tests/tfe_nt_host.py: the oracle's environment under it) and against the two searches it
 chooses between.  Every comparison is exact: integers word for word, float64 as bit patterns.  Every buffer a launch is handed sits
 between guard words, the two depth counters too.
 
-Shape (tests/tfe_adaptive_host.py, where the rehearsal is written down): the tuples (0, 1, 2, 3) and (4, 5, 6, 8, 9, 10), weights all
+Shape (tests/tfe_nt_adaptive_support.py, where the rehearsal is written down): the tuples (0, 1, 2, 3) and (4, 5, 6, 8, 9, 10), weights all
 zero or a seeded normal array of scale 4, gamma 1, 7 games of at most 256 moves, E = 3.  The kernels take one board or game per
 workgroup, so no batch size leaves a workgroup partly filled.  The host's games are played once per case and shared (about 2 s per
 case: most moves are one layer deep)."""
@@ -13,8 +13,8 @@ import functools
 import numpy as np
 import pytest
 
-from tests.tfe_adaptive_host import CASES, DEEP_EMPTY_MAX, EPSILON, GAMES, MAX_STEPS, SEED, host_games
 from tests.tfe_gpu_support import guard, guarded, guards_intact
+from tests.tfe_nt_adaptive_support import CASES, DEEP_EMPTY_MAX, EPSILON, GAMES, MAX_STEPS, SEED, host_games
 from tests.tfe_nt_support import BOARD_ID0, CRAFTED, MORE, TUPLES, search_agent, search_outputs, weights
 from tests.tfe_search_host import key_of
 

@@ -1,8 +1,8 @@
 """The 2048 n-tuple network's training roll-out at the adaptive search depth, without a GPU: the library's new
 entry point with its refusals in their order, check_options' new rows in the agent's words and in the script's with the two relaxed rows
 still firing while the threshold is off, the agent's and the script's refusals on an object without a device, the host's policy of
-tests/tfe_adaptive_rollout_host.py against the policies it composes and against the two-layer roll-out at E = 16, the games from
-`start` as that file's header lists them, and what the compiler made of the kernels as profiles/tfe_mc/kernel_resource_usage.txt lists it."""
+tests/tfe_nt_host.py with and without its records, against the searches it composes and against the two-layer roll-out at E = 16, the
+games from `start` as the header of tests/tfe_nt_adaptive_support.py lists them, and what the compiler made of the kernels as profiles/tfe_mc/kernel_resource_usage.txt lists it."""
 import ctypes as C
 import functools
 import inspect
@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from tests.native_args import PTR, assert_refusals, resource_usage
-from tests.tfe_nt_support import CASES, ROLLOUT_UNIT, ROOT, TUPLES, assert_exports, assert_no_scratch, bits, listed, opts, play_kernel, weights
+from tests.tfe_nt_support import CASES, ROLLOUT_UNIT, ROOT, TUPLES, assert_exports, assert_no_scratch, bits, listed, opts, play_kernel, seeds, weights
 from tests.tfe_nt_support import nt as _nt
 
 ENTRY = "pulse_tfe_nt_rollout_adaptive"
@@ -191,40 +191,41 @@ def test_the_script_says_the_functions_words(capsys):
 
 
 # ------------------------------------------------------------------ the host's policy
-def _seeds(seed=7):
-    from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
-    return seed, seed ^ AGENT_KEY, seed ^ TIE_KEY, 3000, 0
-
-
 def test_recording_does_not_change_the_games_the_policy_plays():
-    """the recording policy against tests/tfe_adaptive_host.py's, which it restates in one search per move: 3 games of 48 moves at E = 5
-    (both depths within the opening), every record the two share and the counters; and the recorded values and backed values are the
-    mirrors' of the boards before the moves"""
-    from tests import tfe_host
-    from tests.tfe_adaptive_host import adaptive_games_on_host
-    from tests.tfe_adaptive_rollout_host import adaptive_rollout_on_host
+    """the policy with its records against the policy without them: 3 games of 48 moves at E = 5 (both depths within the opening),
+    every record the two share and the counters; the recorded values and backed values are the mirrors' of the boards before the
+    moves; and on those boards the one search per move (search_adaptive_nt_on_host) is, row for row, the split by empty cells
+    written out by hand: search_nt_on_host one layer deep on the boards with more than 5 empty cells, two layers deep on the others"""
+    from tests.tfe_host import pack_boards
+    from tests.tfe_nt_host import nt_games_on_host
     nt, w = _nt(), weights("seeded")
-    args = (3, 48, .25, 1.0, w, TUPLES, True, *_seeds(), 5)
-    played, recorded = adaptive_games_on_host(*args, keep_boards="before"), adaptive_rollout_on_host(*args, backed=True)
+    args = (3, 48, .25, 1.0, w, TUPLES, True, *seeds(7))
+    played, recorded = nt_games_on_host(*args, deep_empty_max=5, record=False, keep_boards="before"), nt_games_on_host(*args, deep_empty_max=5, backed=True)
     for k in ("keys", "steps", "moved", "lengths", "total_score", "episode_reward", "final_boards"):
         assert np.array_equal(played[k], recorded[k]), k
     assert all(played[k] == recorded[k] for k in ("ended", "truncated", "capped", "greedy", "deep", "shallow"))
-    assert played["deep"] >= 5 and played["shallow"] >= 5 and "values" not in played and "backed" not in adaptive_rollout_on_host(*args)
+    assert played["deep"] >= 5 and played["shallow"] >= 5 and "values" not in played and "backed" not in nt_games_on_host(*args, deep_empty_max=5)
     for t in (0, 20, 47):
         live = np.flatnonzero(recorded["lengths"] > t)
-        look = nt.search_adaptive_nt_on_host(tfe_host.pack_boards(played["boards"][t][live]), w, TUPLES, True, 1.0, _seeds()[2], 0, 5)
+        keys = pack_boards(played["boards"][t][live])
+        look = nt.search_adaptive_nt_on_host(keys, w, TUPLES, True, 1.0, seeds(7)[2], 0, 5)
         assert np.array_equal(bits(recorded["backed"][t, live]), bits(look["backed"])) and look["deep"].dtype == np.bool_
         assert np.array_equal(bits(recorded["values"][t, live]), bits(nt.value_on_host(recorded["keys"][t, live], w, TUPLES, True)))
+        deep = nt.count_empty_on_host(keys) <= 5
+        assert np.array_equal(deep, look["deep"]), t
+        for rows, layers in ((~deep, 1), (deep, 2)):
+            split = nt.search_nt_on_host(keys[rows], w, TUPLES, True, 1.0, seeds(7)[2], 0, layers=layers)
+            for k in ("action", "after", "rewards"):
+                assert split[k].dtype == look[k].dtype and np.array_equal(split[k], look[k][rows]), (t, layers, k)
+            assert np.array_equal(bits(split["backed"]), bits(look["backed"][rows])), (t, layers)
 
 
 def test_sixteen_is_the_two_layer_rollout_on_the_host():
-    """3 games of 24 moves: the mirror at E = 16 equals search_rollout_on_host(layers=2), with search_backed_on_host of its q
-    (backed_rollout_on_host(layers=2) keeps it)"""
-    from tests.tfe_adaptive_rollout_host import adaptive_rollout_on_host
-    from tests.tfe_backed_host import backed_rollout_on_host
-    from tests.tfe_search_rollout_host import search_rollout_on_host
-    args = (3, 24, .25, 1.0, weights("seeded"), TUPLES, True, *_seeds())
-    mine, two, backed = adaptive_rollout_on_host(*args, 16, backed=True), search_rollout_on_host(*args, layers=2), backed_rollout_on_host(*args, layers=2)
+    """3 games of 24 moves: the roll-out at E = 16 (search_adaptive_nt_on_host) equals the one at depth 2 (search_nt_on_host(layers=2)),
+    with search_backed_on_host of its q (the roll-out at depth 2 with `backed` keeps it)"""
+    from tests.tfe_nt_host import nt_games_on_host
+    args = (3, 24, .25, 1.0, weights("seeded"), TUPLES, True, *seeds(7))
+    mine, two, backed = nt_games_on_host(*args, deep_empty_max=16, backed=True), nt_games_on_host(*args, depth=2), nt_games_on_host(*args, depth=2, backed=True)
     for k in ("keys", "steps", "lengths", "total_score", "episode_reward"):
         assert np.array_equal(mine[k], two[k]) and np.array_equal(mine[k], backed[k]), k
     assert np.array_equal(bits(mine["values"]), bits(two["values"])) and np.array_equal(bits(mine["backed"]), bits(backed["backed"]))
@@ -232,17 +233,17 @@ def test_sixteen_is_the_two_layer_rollout_on_the_host():
 
 
 def test_the_games_from_start_are_those_of_the_header():
-    """tests/tfe_adaptive_rollout_host.py's start boards and the games from them (about 4 s with the case they are taken from)"""
-    from tests.tfe_adaptive_rollout_host import FROM_REHEARSED, GAMES, UNUSABLE, host_rollout_from, start_boards
-    from tests.tfe_restart_host import usable_on_host
+    """tests/tfe_nt_adaptive_support.py's start boards and the games from them (about 4 s with the case they are taken from)"""
+    from tests.tfe_nt_adaptive_support import FROM_REHEARSED, GAMES, UNUSABLE, host_rollout_from, start_boards
+    from tests.tfe_nt_host import usable_on_host
     nt, start = _nt(), start_boards()
     usable = usable_on_host(start)
     assert sorted(np.flatnonzero(~usable).tolist()) == sorted(UNUSABLE) and len(start) == GAMES and start[0] == 0
     assert nt.count_empty_on_host(start[usable]).tolist() == [3, 5, 2, 1] and nt.count_empty_on_host(start[[2]]).tolist() == [0]
     assert ((start[5] >> np.uint64(4 * np.arange(16))) & np.uint64(15) == 15).any()
-    want, left = host_rollout_from()
+    want = host_rollout_from()
     assert {k: (want[k].tolist() if k == "lengths" else want[k]) for k in FROM_REHEARSED} == FROM_REHEARSED
-    assert np.array_equal(left, np.where(usable, start, np.uint64(0))) and want["backed"].any()
+    assert np.array_equal(want["start_left"], np.where(usable, start, np.uint64(0))) and want["backed"].any()
 
 
 # ------------------------------------------------------------------ what the compiler made of the kernels

@@ -1,21 +1,22 @@
 """The 2048 n-tuple network's training roll-out at the adaptive search depth, on the device (DESIGN.md section 13.13;
 csrc/tfe_ntuple_search_rollout.hip: pulse_tfe_nt_rollout_adaptive) against the host's statement of it
-(tests/tfe_adaptive_rollout_host.py: the oracle's environment under search_adaptive_nt_on_host, recording V of the chosen afterstate
+(tests/tfe_nt_host.py: the oracle's environment under search_adaptive_nt_on_host, recording V of the chosen afterstate
 and search_backed_on_host of the q), against the two-layer recording launches at E = 16, and through the agent: whole rounds with
 backed targets, games continued across rounds and restarted rounds.  Every comparison is exact: integers word for word, float64 and
 float32 as bit patterns.  Every buffer a launch is handed sits between guard words -- `backed`, `start` and `depth_stats` too -- and
 the rows of keys / values / steps / backed at and beyond a game's length must keep what they held.
 
-Shape (tests/tfe_adaptive_host.py and tests/tfe_adaptive_rollout_host.py, where the rehearsals are written down): the tuples (0, 1, 2,
+Shape (tests/tfe_nt_adaptive_support.py, where the rehearsals are written down): the tuples (0, 1, 2,
 3) and (4, 5, 6, 8, 9, 10), weights all zero or a seeded normal array of scale 4, gamma 1, 7 games of at most 256 moves, one workgroup
 each, E = 3.  The host's games are played once per case and shared (about 2 s per case)."""
 import numpy as np
 import pytest
 
-from tests.tfe_adaptive_rollout_host import (CASES, DEEP_EMPTY_MAX, EPSILON, FROM_CASE, FROM_REHEARSED, GAMES, MAX_STEPS, SEED, UNUSABLE,
-                                             adaptive_rollout_from_on_host, adaptive_rollout_on_host, host_rollout, host_rollout_from, start_boards)
 from tests.tfe_continue_host import Carried, pick_on_host
 from tests.tfe_gpu_support import assert_rollout, guard, guards_intact, read
+from tests.tfe_nt_adaptive_support import (CASES, DEEP_EMPTY_MAX, EPSILON, FROM_CASE, FROM_REHEARSED, GAMES, MAX_STEPS, SEED, UNUSABLE, host_rollout, host_rollout_from,
+                                           start_boards)
+from tests.tfe_nt_host import nt_games_on_host
 from tests.tfe_nt_support import PER_MOVE, TUPLES, bits, nt, search_agent
 
 pytestmark = pytest.mark.gpu
@@ -119,10 +120,11 @@ def test_sixteen_is_the_two_layer_recording_launches():
 
 # ------------------------------------------------------------------ from `start`
 def test_the_games_from_start_are_the_mirrors():
-    """four late boards and the three kinds of unusable entry (tests/tfe_adaptive_rollout_host.py): the unusable ones fall back to the
+    """four late boards and the three kinds of unusable entry (tests/tfe_nt_adaptive_support.py): the unusable ones fall back to the
     reset and read 0 afterwards, the usable ones are unchanged"""
     name, epsilon, symmetric = FROM_CASE
-    start, (want, left) = start_boards(), host_rollout_from()
+    start, want = start_boards(), host_rollout_from()
+    left = want["start_left"]
     assert {k: (want[k].tolist() if k == "lengths" else want[k]) for k in FROM_REHEARSED} == FROM_REHEARSED
     assert want["deep"] >= 5 and want["shallow"] >= 5 and want["ended"] >= 1 and want["truncated"] >= 1
     unusable = np.isin(np.arange(GAMES), list(UNUSABLE))
@@ -196,8 +198,8 @@ def test_two_rounds_with_backed_targets_are_the_hosts(tc):
     coherence = (np.zeros(a.n_weights), np.zeros(a.n_weights)) if tc else None
     for r in range(2):
         policy = a.weights()
-        want = host_rollout(*FROM_CASE) if r == 0 else adaptive_rollout_on_host(
-            GAMES, MAX_STEPS, a.epsilon, a.gamma, policy, TUPLES, True, a.env_seed, a.agent_seed, a.tie_seed, a.round_board_id0(), a.round, E, backed=True)
+        want = host_rollout(*FROM_CASE) if r == 0 else nt_games_on_host(
+            GAMES, MAX_STEPS, a.epsilon, a.gamma, policy, TUPLES, True, a.env_seed, a.agent_seed, a.tie_seed, a.round_board_id0(), a.round, deep_empty_max=E, backed=True)
         got, st0 = _launched(a, a.rollout), a.stats()
         _assert_games(a, got, want, ("round", r), True)
         a.learn()
@@ -259,9 +261,9 @@ def test_three_continued_rounds_with_backed_targets_are_the_hosts():
     round_ = [("rollout_adaptive", E), ("learn_backed",), ("apply",), ("continue_pick",)]
     for r in range(3):
         policy, board_id0 = a.weights(), a.round_board_id0()
-        want, left = adaptive_rollout_from_on_host(c.start, games, segment, a.epsilon, a.gamma, policy, TUPLES, True, a.env_seed, a.agent_seed, a.tie_seed,
-                                                   board_id0, a.round, E, backed=True)
-        assert np.array_equal(left, c.start)                                # boards a game moved on: none is zeroed
+        want = nt_games_on_host(games, segment, a.epsilon, a.gamma, policy, TUPLES, True, a.env_seed, a.agent_seed, a.tie_seed, board_id0, a.round,
+                                deep_empty_max=E, backed=True, start=c.start)
+        assert np.array_equal(want["start_left"], c.start)                  # boards a game moved on: none is zeroed
         _, _, host, host_w = _host_learn(n, a, want, policy, None)
         words, cut = pick_on_host(c, want, segment, a.env_seed, board_id0)
         before = _read(a)
@@ -303,8 +305,9 @@ def test_a_restarted_round_is_the_hosts():
     assert np.array_equal(_start_of(a), start) and tuple(a.restart_stats.cpu().tolist()) == picked and picked[0] >= 3
     assert np.array_equal(a.weights().view(np.uint32), host_w.view(np.uint32))
     assert calls == [("rollout_adaptive", E), ("learn",), ("apply",), ("restart_pick",)]
-    want, left = adaptive_rollout_from_on_host(start, GAMES, MAX_STEPS, a.epsilon, a.gamma, host_w, TUPLES, True, a.env_seed, a.agent_seed, a.tie_seed,
-                                               a.round_board_id0(), a.round, E)
+    want = nt_games_on_host(GAMES, MAX_STEPS, a.epsilon, a.gamma, host_w, TUPLES, True, a.env_seed, a.agent_seed, a.tie_seed, a.round_board_id0(), a.round,
+                            deep_empty_max=E, start=start)
+    left = want["start_left"]
     assert np.array_equal(left, start) and want["deep"] >= 5 and want["shallow"] >= 5
     got = _launched(a, a.rollout)
     _assert_games(a, got, want, "round 1", False)

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from tests.native_args import PTR, assert_refusals, remarks
-from tests.tfe_backed_host import backed_rollout_on_host
+from tests.tfe_nt_host import nt_games_on_host
 from tests.tfe_nt_support import BOARD_ID0, CASES, CRAFTED, MORE, P, ROOT, TUPLES, assert_exports, assert_no_scratch, play_kernels, bits, opts, weights
 from tests.tfe_nt_support import nt as _nt
 from tests.tfe_search_host import key_of, scalar_search_on_host
@@ -124,22 +124,33 @@ def test_one_board_worked_by_hand():
     assert look["backed"].tolist() == [q_right] and look["q"][0, 2] == q_right and look["q"][0, 0] < q_right
     boards0 = (1 << np.array(CRAFTED["one_merge"], dtype=np.int32)).reshape(1, 4, 4)
     for epsilon in (0.0, 1.0):                                             # whatever the action taken
-        got = backed_rollout_on_host(1, 1, epsilon, 1.0, w, tuples, False, 11, 12, 1, 500, 0, boards0=boards0)
+        got = nt_games_on_host(1, 1, epsilon, 1.0, w, tuples, False, 11, 12, 1, 500, 0, depth=1, backed=True, boards0=boards0)
         assert got["backed"].shape == (1, 1) and got["backed"][0, 0] == q_right and got["lengths"].tolist() == [1]
-    got = backed_rollout_on_host(1, 1, 0.0, 1.0, w, tuples, False, 11, 12, 1, 500, 0, boards0=boards0)
+    got = nt_games_on_host(1, 1, 0.0, 1.0, w, tuples, False, 11, 12, 1, 500, 0, depth=1, backed=True, boards0=boards0)
     assert got["values"][0, 0] == 2.5 and int(got["steps"][0, 0]) == 18
 
 
 def test_recording_the_backed_value_does_not_change_play():
+    """the roll-out one layer deep with and without `backed`; the records the two share come from one policy, so the values and the
+    backed values are also held to the package's mirrors: value_on_host of the recorded afterstates, and search_backed_on_host of
+    the search's q on the boards before the moves 0, 10 and 23"""
     from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
-    from tests.tfe_search_rollout_host import search_rollout_on_host
+    from tests.tfe_host import pack_boards
+    nt = _nt()
     args = (5, 24, .25, 1.0, weights("seeded"), TUPLES, True, 2312, 2312 ^ AGENT_KEY, 2312 ^ TIE_KEY, BOARD_ID0, 0)
-    got, want = backed_rollout_on_host(*args), search_rollout_on_host(*args)
+    got, want = nt_games_on_host(*args, depth=1, backed=True), nt_games_on_host(*args, depth=1, keep_boards="before")
+    assert "backed" not in want
     for k in ("keys", "steps", "moved", "lengths", "total_score", "episode_reward", "final_boards"):
         assert np.array_equal(got[k], want[k]), k
     assert np.array_equal(bits(got["values"]), bits(want["values"])) and got["greedy"] == want["greedy"] < int(want["lengths"].sum())
     played = np.arange(24)[:, None] < got["lengths"][None, :]
     assert got["backed"][played].all() and not got["backed"][~played].any()
+    assert np.array_equal(bits(got["values"][played]), bits(nt.value_on_host(got["keys"][played], weights("seeded"), TUPLES, True)))
+    for t in (0, 10, 23):
+        live = np.flatnonzero(got["lengths"] > t)
+        keys = pack_boards(want["boards"][t][live])
+        look = nt.search_nt_on_host(keys, weights("seeded"), TUPLES, True, 1.0, 2312 ^ TIE_KEY, 0)
+        assert live.size and np.array_equal(bits(got["backed"][t, live]), bits(nt.search_backed_on_host(look["q"], look["after"] != keys[:, None]))), t
 
 
 # ------------------------------------------------------------------ the learner's mirror, worked by hand

@@ -1,5 +1,5 @@
 """The 2048 n-tuple network's search-backed TD targets on the device (csrc/tfe_ntuple_backed.hip:
-pulse_tfe_nt_rollout_backed, pulse_tfe_nt_learn_backed) against the host's statement of them (tests/tfe_backed_host.py: the oracle's
+pulse_tfe_nt_rollout_backed, pulse_tfe_nt_learn_backed) against the host's statement of them (tests/tfe_nt_host.py: the oracle's
 environment under search_nt_on_host, recording its `backed`; backed_deltas_on_host, learn_backed_nt_on_host).  Every comparison is
 exact: integers word for word, float64 and float32 as bit patterns.  Every buffer a launch is handed sits between guard words, and the
 rows of keys / values / steps / backed / deltas at and beyond a game's length must keep what they held.
@@ -46,10 +46,10 @@ def _agent(layers, name, epsilon, symmetric=True, **kw):
 @functools.lru_cache(maxsize=None)
 def _host_games(layers, name, epsilon, symmetric=True):
     from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
-    from tests.tfe_backed_host import backed_rollout_on_host
+    from tests.tfe_nt_host import nt_games_on_host
     games, max_steps, seed = SHAPE[layers]
-    want = backed_rollout_on_host(games, max_steps, epsilon, 1.0, weights(name), TUPLES, symmetric, seed, seed ^ AGENT_KEY, seed ^ TIE_KEY, BOARD_ID0, ROUND,
-                                  layers=layers)
+    want = nt_games_on_host(games, max_steps, epsilon, 1.0, weights(name), TUPLES, symmetric, seed, seed ^ AGENT_KEY, seed ^ TIE_KEY, BOARD_ID0, ROUND,
+                            depth=layers, backed=True)
     assert want["ended"] >= 1 and want["truncated"] >= 1 and want["ended"] + want["truncated"] == games, (layers, name, epsilon, want["ended"])
     return want
 

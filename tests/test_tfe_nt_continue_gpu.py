@@ -12,8 +12,8 @@ import pytest
 
 from tests.tfe_continue_host import WORDS, Carried, pick_on_host
 from tests.tfe_gpu_support import PATTERNS, assert_rollout, guard, guards_intact, read
+from tests.tfe_nt_host import nt_games_on_host
 from tests.tfe_nt_support import BOARD_ID0, BUFFERS, GAMES, PER_MOVE, TUPLES, bits, learner_agent, learner_round, nt, plain_learner, weights
-from tests.tfe_restart_host import rollout_from_on_host
 
 pytestmark = pytest.mark.gpu
 
@@ -89,8 +89,9 @@ def _continued_round(a, c, coherence, where):
     """learner_round with the games held to the host's from the `start` the pick of the round before left and, after the apply, the
     pick launch held to the host's"""
     def games(a, h):
-        want, kept = rollout_from_on_host(c.start, a.n_games, a.max_steps, a.epsilon, a.gamma, h.policy, a.tuples, a.symmetric, a.env_seed, a.agent_seed,
-                                          a.tie_seed, a.round_board_id0(), a.round, layers=0)
+        want = nt_games_on_host(a.n_games, a.max_steps, a.epsilon, a.gamma, h.policy, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
+                                a.round_board_id0(), a.round, start=c.start)
+        kept = want["start_left"]
         assert_rollout(h.got, want, where, PER_MOVE)
         assert np.array_equal(_start_of(a), kept) and np.array_equal(kept, c.start), where
         return dict(continued=int(np.count_nonzero(kept)))
@@ -165,8 +166,9 @@ def test_three_continued_rounds_under_search_with_backed_targets_are_the_hosts()
         before = read(a, PER_MOVE)
         a.rollout()
         got = dict(read(a, PER_MOVE), **{k + "_before": v for k, v in before.items() if k in PER_MOVE})
-        want, kept = rollout_from_on_host(c.start, games, max_steps, a.epsilon, a.gamma, policy, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
-                                          a.round_board_id0(), a.round, layers=1, backed=True)
+        want = nt_games_on_host(games, max_steps, a.epsilon, a.gamma, policy, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
+                                a.round_board_id0(), a.round, depth=1, backed=True, start=c.start)
+        kept = want["start_left"]
         assert_rollout(got, want, ("round", r), PER_MOVE)
         L = got["lengths"].astype(np.int64)
         played, backed = np.arange(max_steps)[:, None] < L[None, :], bits(a.backed.cpu().numpy())
@@ -239,9 +241,8 @@ def test_without_the_attribute_three_rounds_are_todays():
 
 # ------------------------------------------------------------------ the evaluations' own cap
 def _host_whole_games(a, max_steps):
-    from tests import tfe_host
-    return tfe_host.rollout_nt_on_host(a.n_games, max_steps, 0.0, a.gamma, a.weights(), a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
-                                       a.eval_board_id0(), a.round)
+    return nt_games_on_host(a.n_games, max_steps, 0.0, a.gamma, a.weights(), a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
+                            a.eval_board_id0(), a.round)
 
 
 @pytest.mark.parametrize("cap", [None, 4096], ids=["agents_max_steps", "4096"])

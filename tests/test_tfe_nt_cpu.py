@@ -157,8 +157,8 @@ def test_learn_and_apply_on_a_hand_worked_case():
 # ------------------------------------------------------------------ games on the host
 def _round(weights, tuples, r, n_games=256, epsilon=0.0, max_steps=4096, seed=0, **kw):
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import AGENT_KEY, TIE_KEY
-    from tests.tfe_host import rollout_nt_on_host
-    return rollout_nt_on_host(n_games, max_steps, epsilon, 1.0, weights, tuples, True, seed, seed ^ AGENT_KEY, seed ^ TIE_KEY, r * n_games, r, **kw)
+    from tests.tfe_nt_host import nt_games_on_host
+    return nt_games_on_host(n_games, max_steps, epsilon, 1.0, weights, tuples, True, seed, seed ^ AGENT_KEY, seed ^ TIE_KEY, r * n_games, r, **kw)
 
 
 def test_the_host_mirror_learns():

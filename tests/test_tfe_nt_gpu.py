@@ -1,5 +1,5 @@
 """The 2048 n-tuple network on the device (csrc/tfe_ntuple.hip: pulse_tfe_nt_rollout, pulse_tfe_nt_learn,
-pulse_tfe_nt_apply, pulse_tfe_nt_evaluate) against the host's statement of it (tests/tfe_host.py: the oracle's environment under
+pulse_tfe_nt_apply, pulse_tfe_nt_evaluate) against the host's statement of it (tests/tfe_nt_host.py: the oracle's environment under
 greedy_nt_on_host; learn_nt_on_host, apply_nt_on_host) and the environment's own kernels.  Every comparison is exact: keys, bytes and
 integers word for word, values and weights as bit patterns.  Every buffer a launch is handed sits between guard words, and the rows of
 keys / values / steps at and beyond a game's length must keep what they held.
@@ -22,10 +22,10 @@ pytestmark = pytest.mark.gpu
 
 
 def _host_rollout(a, weights, **kw):
-    from tests.tfe_host import rollout_nt_on_host
+    from tests.tfe_nt_host import nt_games_on_host
     kw = dict(dict(epsilon=a.epsilon, board_id0=a.round_board_id0()), **kw)
-    return rollout_nt_on_host(a.n_games, a.max_steps, kw["epsilon"], a.gamma, weights, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
-                              kw["board_id0"], a.round)
+    return nt_games_on_host(a.n_games, a.max_steps, kw["epsilon"], a.gamma, weights, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
+                            kw["board_id0"], a.round)
 
 
 def _play_rounds(symmetric, rounds):

@@ -108,11 +108,11 @@ def test_lengths_beyond_the_buffers_are_clamped():
 def _recorded_round():
     """64 games of 64 moves at epsilon .25 under random weights on a small network: games that end and games that are cut"""
     from pulselib_amd.agents.tfe_on_policy_mc_gpu import AGENT_KEY, TIE_KEY
-    from tests.tfe_host import rollout_nt_on_host
+    from tests.tfe_nt_host import nt_games_on_host
     nt = _nt()
     tuples = ((0, 1, 2, 3), (4, 5, 6, 7), (0, 1, 4, 5))
     w = (np.random.default_rng(6).standard_normal(nt.tuple_offsets(tuples)[1]) * 4).astype(np.float32)
-    out = rollout_nt_on_host(64, 64, 0.25, 1.0, w, tuples, True, 5, 5 ^ AGENT_KEY, 5 ^ TIE_KEY, 100, 0)
+    out = nt_games_on_host(64, 64, 0.25, 1.0, w, tuples, True, 5, 5 ^ AGENT_KEY, 5 ^ TIE_KEY, 100, 0)
     return tuples, len(w), out
 
 

@@ -14,10 +14,10 @@ import pytest
 
 from pulselib_amd.sharding import shard_tables
 from tests.native_args import remarks
-from tests.tfe_host import rollout_nt_on_host
+from tests.tfe_nt_host import nt_games_on_host, usable_on_host
 from tests.tfe_nt_ranks_support import (ADAPTIVE_REHEARSED, DEEP_EMPTY_MAX, EPSILON, EVAL_GAMES, FIELDS, GAMES, GAMMA, GROWN_FROM, GROWN_TILE, LAM, MAX_STEPS, PACK,
                                         RESTART, ROUNDS, SPLITS, STAGE_TILES, STRUCT, TUPLES, UNPACK, assert_list_refusals, by_index, list_words)
-from tests.tfe_nt_support import BOARD_ID0, ROOT, SEED, assert_exports, assert_no_scratch
+from tests.tfe_nt_support import BOARD_ID0, ROOT, SEED, assert_exports, assert_no_scratch, seeds
 from tests.tfe_nt_support import nt as _nt
 
 
@@ -94,7 +94,7 @@ def test_the_shards_board_ids_are_the_single_process_s():
 # ------------------------------------------------------------------ exactness on the host
 def _learn(nt, weights, n_games, board_id0, r):
     """one shard's (or the single run's) round r on the host: its accumulators from zero"""
-    g = rollout_nt_on_host(n_games, MAX_STEPS, EPSILON, GAMMA, weights, TUPLES, True, SEED, SEED ^ nt.AGENT_KEY, SEED ^ nt.TIE_KEY, board_id0, r)
+    g = nt_games_on_host(n_games, MAX_STEPS, EPSILON, GAMMA, weights, TUPLES, True, *seeds(SEED, board_id0, r))
     W = nt.tuple_offsets(TUPLES)[1]
     acc, ab = np.zeros((W, 2), dtype=np.int64), np.zeros(W, dtype=np.int64)
     counts = nt.learn_tc_nt_on_host(g["keys"], g["values"], g["steps"], g["lengths"], TUPLES, True, GAMMA, LAM, acc, ab)
@@ -148,22 +148,16 @@ def test_the_shards_accumulators_sum_to_the_single_run_s():
 # tests/test_tfe_nt_ranks_gpu.py asserts "> 0" of what a case is there for -- boards picked and started, moves at both depths, weights in
 # two stages.  The host mirrors play the same 13 games here, so those hold by the constants of tests/tfe_nt_ranks_support.py and are not
 # tuned on the device.
-def _seeds():
-    nt = _nt()
-    return SEED, SEED ^ nt.AGENT_KEY, SEED ^ nt.TIE_KEY
-
-
 def test_the_restart_case_picks_and_starts_boards():
     """TD(0) from zero weights, restart_fraction .5, restart_min_length 8: rounds 0 and 1 on the host.  Both pick boards, and round 1
     begins games on the boards round 0 picked."""
-    from tests.tfe_restart_host import rollout_from_on_host, usable_on_host
     nt = _nt()
     W, F = nt.tuple_offsets(TUPLES)[1], 8 * len(TUPLES)
     w, start = np.zeros(W, dtype=np.float32), np.zeros(GAMES, dtype=np.uint64)
     for r in range(2):
         id0 = BOARD_ID0 + r * GAMES
-        g, left = rollout_from_on_host(start, GAMES, MAX_STEPS, EPSILON, GAMMA, w, TUPLES, True, *_seeds(), id0, r)
-        assert int(np.count_nonzero(left)) == (0 if r == 0 else picked) and (r == 0 or picked > 0)    # started: the games begun on a picked board
+        g = nt_games_on_host(GAMES, MAX_STEPS, EPSILON, GAMMA, w, TUPLES, True, *seeds(SEED, id0, r), start=start)
+        assert int(np.count_nonzero(g["start_left"])) == (0 if r == 0 else picked) and (r == 0 or picked > 0)    # started: the games begun on a picked board
         acc = np.zeros((W, 2), dtype=np.int64)
         assert nt.learn_nt_on_host(g["keys"], g["values"], g["steps"], g["lengths"], TUPLES, True, GAMMA, acc)["learnt"] > 100
         assert nt.apply_nt_on_host(w, acc, 1.0 / F) > 100
@@ -181,7 +175,7 @@ def test_the_staged_case_reaches_two_stages():
     nt = _nt()
     tuples = nt.with_stages(TUPLES, STAGE_TILES)
     W, S = nt.tuple_offsets(TUPLES)[1], len(STAGE_TILES) + 1
-    g = rollout_nt_on_host(GAMES, MAX_STEPS, EPSILON, GAMMA, np.zeros(S * W, dtype=np.float32), tuples, True, *_seeds(), BOARD_ID0, 0)
+    g = nt_games_on_host(GAMES, MAX_STEPS, EPSILON, GAMMA, np.zeros(S * W, dtype=np.float32), tuples, True, *seeds(SEED))
     top = g["final_boards"].reshape(GAMES, -1).max(axis=1)
     print("largest tiles", top.tolist())
     assert (top >= 8).sum() >= GAMES - 2 and (top >= 16).sum() >= 2
@@ -197,21 +191,19 @@ def adaptive_case_on_host(rounds, evaluate=False):
     """The adaptive case on the host: `rounds` rounds of 13 games at E = DEEP_EMPTY_MAX with backed targets (TD(0)) and restarts, from
     zero weights; per round (moves two layers deep, one layer deep, boards picked); with `evaluate` also the depth words of the 11
     evaluation games on the weights as they stand.  adaptive_case_on_host(ROUNDS, True) is what ADAPTIVE_REHEARSED records."""
-    from tests.tfe_adaptive_host import adaptive_games_on_host
-    from tests.tfe_adaptive_rollout_host import adaptive_rollout_from_on_host
     nt = _nt()
     W, F = nt.tuple_offsets(TUPLES)[1], 8 * len(TUPLES)
     w, start, out = np.zeros(W, dtype=np.float32), np.zeros(GAMES, dtype=np.uint64), []
     for r in range(rounds):
         id0 = BOARD_ID0 + r * GAMES
-        g, _ = adaptive_rollout_from_on_host(start, GAMES, MAX_STEPS, EPSILON, GAMMA, w, TUPLES, True, *_seeds(), id0, r, DEEP_EMPTY_MAX, backed=True)
+        g = nt_games_on_host(GAMES, MAX_STEPS, EPSILON, GAMMA, w, TUPLES, True, *seeds(SEED, id0, r), deep_empty_max=DEEP_EMPTY_MAX, backed=True, start=start)
         acc = np.zeros((W, 2), dtype=np.int64)
         nt.learn_backed_nt_on_host(g["keys"], g["values"], g["backed"], g["steps"], g["lengths"], TUPLES, True, GAMMA, 0.0, acc)
         nt.apply_nt_on_host(w, acc, 1.0 / F)
         start, (picked, _) = nt.restart_pick_on_host(g["keys"], g["lengths"], MAX_STEPS, SEED, id0, RESTART["restart_fraction"], RESTART["restart_min_length"])
         out.append((g["deep"], g["shallow"], picked))
     if evaluate:
-        ev = adaptive_games_on_host(EVAL_GAMES, MAX_STEPS, 0.0, GAMMA, w, TUPLES, True, *_seeds(), BOARD_ID0 + (1 << 62), rounds, DEEP_EMPTY_MAX)
+        ev = nt_games_on_host(EVAL_GAMES, MAX_STEPS, 0.0, GAMMA, w, TUPLES, True, *seeds(SEED, BOARD_ID0 + (1 << 62), rounds), deep_empty_max=DEEP_EMPTY_MAX, record=False)
         out.append((ev["deep"], ev["shallow"]))
     return out
 

@@ -1,6 +1,6 @@
 """The 2048 n-tuple network's restarted roll-outs without a GPU: the library's two entry points with their
 refusals, the pick struct's layout, the host's statement of the spawn and of the pick (spawn_on_host, restart_pick_on_host) against the
-oracle's environment and on three games worked by hand, the host's restarted game loop (tests/tfe_restart_host.py), the Python layer's
+oracle's environment and on three games worked by hand, the host's restarted game loop (tests/tfe_nt_host.py), the Python layer's
 attributes, and what the compiler made of the kernels."""
 import ctypes as C
 import functools
@@ -11,12 +11,12 @@ import re
 import numpy as np
 import pytest
 
-from tests import tfe_host
+from tests import tfe_host, tfe_nt_host
 from tests.native_args import PTR, assert_refusals, remarks, resource_usage
 from tests.native_args import opts as plain_opts
+from tests.tfe_nt_host import boards_of_keys, nt_games_on_host, usable_on_host
 from tests.tfe_nt_support import BOARD_ID0, CASES, CRAFTED, ROOT, TUPLES, assert_exports, assert_no_scratch, play_kernel, play_kernels, bits, opts, weights
 from tests.tfe_nt_support import nt as _nt
-from tests.tfe_restart_host import boards_of_keys, rollout_from_on_host, usable_on_host
 from tests.tfe_search_host import key_of
 
 FROM, PICK = "pulse_tfe_nt_rollout_from", "pulse_tfe_nt_restart_pick"
@@ -95,7 +95,7 @@ def test_the_pick_refuses():
 def _recorded():
     """a host roll-out of 257 games of at most 256 moves on zero weights at epsilon .25, with the boards before every move kept"""
     from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
-    policy = tfe_host._NTuple(GAMES, .25, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, 0, weights=weights("zero"), tuples=TUPLES, symmetric=True, gamma=1.0)
+    policy = tfe_nt_host._NTuple(GAMES, .25, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, 0, weights=weights("zero"), tuples=TUPLES, symmetric=True, gamma=1.0)
     return tfe_host._play(policy, GAMES, 4, MAX_STEPS, SEED, BOARD_ID0, keep_boards="before", tile_cap=32768)
 
 
@@ -173,8 +173,8 @@ def _args(n_games, max_steps, epsilon=.25, name="seeded"):
 
 def test_a_start_of_zeros_gives_the_plain_games():
     args = _args(5, 24)
-    got, start = rollout_from_on_host(np.zeros(5, dtype=np.uint64), *args)
-    want = tfe_host.rollout_nt_on_host(*args)
+    got = nt_games_on_host(*args, start=np.zeros(5, dtype=np.uint64))
+    want, start = nt_games_on_host(*args), got["start_left"]
     for k in ("keys", "steps", "moved", "lengths", "total_score", "episode_reward", "final_boards"):
         assert np.array_equal(got[k], want[k]), k
     assert np.array_equal(bits(got["values"]), bits(want["values"])) and not start.any()
@@ -189,8 +189,8 @@ def test_only_a_usable_board_starts_a_game():
     assert usable_on_host([key_of(CRAFTED["makes_32768"]), key_of(CRAFTED["corner"]), key_of(CRAFTED["over_after_spawn"])]).tolist() == [False, True, False]
     assert boards_of_keys([LIVE])[0].ravel().tolist() == [2, 4, 2, 4, 4, 2, 4, 2, 2, 4, 2, 4, 4, 2, 8, 8]
     args = _args(4, 24, epsilon=0.0)                                       # greedy: the live board's first move is one that changes it
-    got, start = rollout_from_on_host(given, *args)
-    want = tfe_host.rollout_nt_on_host(*args)
+    got = nt_games_on_host(*args, start=given)
+    want, start = nt_games_on_host(*args), got["start_left"]
     assert start.tolist() == [0, 0, 0, LIVE] and np.count_nonzero(start) == 1
     for k in ("keys", "steps", "lengths", "total_score", "episode_reward"):
         assert np.array_equal(got[k][..., :3], want[k][..., :3]), k     # the three reset games
@@ -199,8 +199,8 @@ def test_only_a_usable_board_starts_a_game():
     assert int(got["total_score"][3]) >= 16 and int(got["lengths"][3]) >= 1
     # under the search, with and without the backed value, the same rule
     for backed in (False, True):
-        searched, left = rollout_from_on_host(given, *_args(4, 6, epsilon=0.0), layers=1, backed=backed)
-        assert left.tolist() == [0, 0, 0, LIVE] and ("backed" in searched) == backed and (int(searched["steps"][0, 3]) >> 2) & 31 == 4
+        searched = nt_games_on_host(*_args(4, 6, epsilon=0.0), depth=1, backed=backed, start=given)
+        assert searched["start_left"].tolist() == [0, 0, 0, LIVE] and ("backed" in searched) == backed and (int(searched["steps"][0, 3]) >> 2) & 31 == 4
 
 
 # ------------------------------------------------------------------ the Python layer

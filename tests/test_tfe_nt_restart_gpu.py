@@ -1,5 +1,5 @@
 """The 2048 n-tuple network's restarted roll-outs on the device (csrc/tfe_ntuple_restart.hip:
-pulse_tfe_nt_rollout_from, pulse_tfe_nt_restart_pick) against the host's statement of them (restart_pick_on_host; tests/tfe_restart_host.py:
+pulse_tfe_nt_rollout_from, pulse_tfe_nt_restart_pick) against the host's statement of them (restart_pick_on_host; tests/tfe_nt_host.py:
 the oracle's environment begun on the usable boards of `start`).  Every comparison but the last is exact: integers word for word,
 float64 and float32 as bit patterns.  Every buffer a launch is handed sits between guard words, and the rows of keys / values / steps /
 backed at and beyond a game's length must keep what they held.
@@ -17,9 +17,9 @@ import numpy as np
 import pytest
 
 from tests.tfe_gpu_support import PATTERNS, assert_rollout, guard, guards_intact, read
+from tests.tfe_nt_host import nt_games_on_host, usable_on_host
 from tests.tfe_nt_support import (BOARD_ID0, BUFFERS, CRAFTED, GAMES, MAX_STEPS, PER_MOVE, SEED, TUPLES, bits, learner_agent, learner_round, nt, plain_learner,
                                   search_agent, weights)
-from tests.tfe_restart_host import rollout_from_on_host, usable_on_host
 from tests.tfe_search_host import key_of
 
 pytestmark = pytest.mark.gpu
@@ -103,9 +103,8 @@ def test_the_pick_takes_the_hosts_boards():
 def _mixed_start(layers):
     """boards the host's pick takes from a host round of the shape (zero weights, one ply), every third of them zeroed, and three made by
     hand: a dead board, a board with a 32,768 tile and a live one"""
-    from tests import tfe_host
     games, max_steps, seed = SHAPE[layers]
-    rec = tfe_host.rollout_nt_on_host(games, max_steps, .25, 1.0, weights("zero"), TUPLES, True, *_seeds(seed), BOARD_ID0, ROUND)
+    rec = nt_games_on_host(games, max_steps, .25, 1.0, weights("zero"), TUPLES, True, *_seeds(seed), BOARD_ID0, ROUND)
     start, picked = nt().restart_pick_on_host(rec["keys"], rec["lengths"], max_steps, seed, BOARD_ID0, 0.5, 2)
     assert picked[0] == games
     start[::3] = 0
@@ -120,8 +119,9 @@ def _host_games(layers, symmetric):
     tests/test_tfe_nt_backed_cpu.py), and the `start` the launch is to leave"""
     games, max_steps, seed = SHAPE[layers]
     start = _mixed_start(layers)
-    want, left = rollout_from_on_host(start, games, max_steps, EPSILON[layers], 1.0, _weights(layers), TUPLES, symmetric, *_seeds(seed), BOARD_ID0, ROUND,
-                                      layers=layers, backed=bool(layers))
+    want = nt_games_on_host(games, max_steps, EPSILON[layers], 1.0, _weights(layers), TUPLES, symmetric, *_seeds(seed), BOARD_ID0, ROUND,
+                            depth=layers, backed=bool(layers), start=start)
+    left = want["start_left"]
     assert want["ended"] >= 1 and want["truncated"] >= 1 and want["ended"] + want["truncated"] == games, (layers, symmetric, want["ended"])
     kept = left != 0
     assert not kept[[DEAD, CAPPED]].any() and kept[LIVE] and not kept[::3].any() and int(kept.sum()) == games - len(start[::3]) - 2
@@ -173,8 +173,8 @@ def test_the_games_from_given_boards_are_the_hosts(mode, symmetric):
 def _plain_first_keys(layers, symmetric):
     """the first afterstates of the same launch from reset: one move of every game on the host"""
     games, _, seed = SHAPE[layers]
-    want, _ = rollout_from_on_host(np.zeros(games, dtype=np.uint64), games, 1, EPSILON[layers], 1.0, _weights(layers), TUPLES, symmetric, *_seeds(seed), BOARD_ID0,
-                                   ROUND, layers=layers, backed=False)
+    want = nt_games_on_host(games, 1, EPSILON[layers], 1.0, _weights(layers), TUPLES, symmetric, *_seeds(seed), BOARD_ID0, ROUND, depth=layers,
+                            start=np.zeros(games, dtype=np.uint64))
     return want["keys"][0]
 
 
@@ -207,8 +207,9 @@ def _restarted_round(a, left, coherence, where):
 
     def games(a, h):
         given = np.zeros(a.n_games, dtype=np.uint64) if left is None else left
-        want, kept = rollout_from_on_host(given, a.n_games, a.max_steps, a.epsilon, a.gamma, h.policy, a.tuples, a.symmetric, a.env_seed, a.agent_seed,
-                                          a.tie_seed, a.round_board_id0(), a.round, layers=0)
+        want = nt_games_on_host(a.n_games, a.max_steps, a.epsilon, a.gamma, h.policy, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
+                                a.round_board_id0(), a.round, start=given)
+        kept = want["start_left"]
         assert_rollout(h.got, want, where, PER_MOVE)
         assert np.array_equal(_start_of(a), kept) and np.array_equal(kept, given), where      # picked boards are usable: none is zeroed
         return dict(restarted=int(np.count_nonzero(kept)))
@@ -286,8 +287,9 @@ def test_three_restarted_rounds_under_search_with_backed_targets_are_the_hosts()
     for r in range(3):
         policy = a.weights()
         got = _launched(a, a.rollout)
-        want, kept = rollout_from_on_host(left, games, max_steps, a.epsilon, a.gamma, policy, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
-                                          a.round_board_id0(), a.round, layers=1, backed=True)
+        want = nt_games_on_host(games, max_steps, a.epsilon, a.gamma, policy, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
+                                a.round_board_id0(), a.round, depth=1, backed=True, start=left)
+        kept = want["start_left"]
         assert_rollout(got, want, ("round", r), PER_MOVE)
         L = got["lengths"].astype(np.int64)
         played = np.arange(max_steps)[:, None] < L[None, :]

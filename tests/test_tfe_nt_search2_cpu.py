@@ -23,8 +23,8 @@ def _boards():
     """uint64[18]: the crafted boards, then moves 6 and 40 of five one-layer host games on the seeded weights"""
     from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
     from tests.tfe_host import pack_boards
-    from tests.tfe_search_host import search_games_on_host
-    games = search_games_on_host(5, 41, .25, 1.0, weights("seeded"), TUPLES, True, 11, 11 ^ AGENT_KEY, 11 ^ TIE_KEY, 500, 0, keep_boards="before")
+    from tests.tfe_nt_host import nt_games_on_host
+    games = nt_games_on_host(5, 41, .25, 1.0, weights("seeded"), TUPLES, True, 11, 11 ^ AGENT_KEY, 11 ^ TIE_KEY, 500, 0, depth=1, record=False, keep_boards="before")
     assert games["lengths"].min() == 41
     keys = np.concatenate([np.array([key_of(c) for c in CRAFTED.values()], dtype=np.uint64), pack_boards(games["boards"][6]),
                            pack_boards(games["boards"][40])])

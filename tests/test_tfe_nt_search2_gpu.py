@@ -1,6 +1,6 @@
 """The 2048 n-tuple network's expectimax play two chance layers deep on the device (DESIGN.md section 13.4;
 csrc/tfe_ntuple_search.hip: pulse_tfe_nt_search_deep, pulse_tfe_nt_evaluate_search_deep) against the host's statement of it
-(search_nt_on_host(layers=2); tests/tfe_search_host.py: the oracle's environment under it).  Every comparison is exact: integers word
+(search_nt_on_host(layers=2); tests/tfe_nt_host.py: the oracle's environment under it).  Every comparison is exact: integers word
 for word, float64 as bit patterns.  Every buffer a launch is handed sits between guard words.
 
 Shape: the tuples (0, 1, 2, 3) and (4, 5, 6, 8, 9, 10), weights all zero or a seeded normal array of scale 4, gamma 1.  The kernels
@@ -19,7 +19,8 @@ import pytest
 
 from tests.tfe_gpu_support import guarded, guards_intact
 from tests.tfe_nt_support import BOARD_ID0, CRAFTED, MORE, TUPLES, search_agent, search_outputs, weights
-from tests.tfe_search_host import key_of, search_games_on_host
+from tests.tfe_nt_host import nt_games_on_host
+from tests.tfe_search_host import key_of
 
 pytestmark = pytest.mark.gpu
 GAMES, MAX_STEPS, EPSILON = 7, 160, .25
@@ -31,8 +32,8 @@ _agent = functools.partial(search_agent, GAMES, MAX_STEPS, SEED)
 @functools.lru_cache(maxsize=None)
 def _host_games(name, epsilon, symmetric=True):
     from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
-    return search_games_on_host(GAMES, MAX_STEPS, epsilon, 1.0, weights(name), TUPLES, symmetric, SEED, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, BOARD_ID0,
-                                ROUND, keep_boards="before", layers=2)
+    return nt_games_on_host(GAMES, MAX_STEPS, epsilon, 1.0, weights(name), TUPLES, symmetric, SEED, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, BOARD_ID0,
+                            ROUND, depth=2, record=False, keep_boards="before")
 
 
 @functools.lru_cache(maxsize=None)

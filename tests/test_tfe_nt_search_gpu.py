@@ -1,5 +1,5 @@
 """The 2048 n-tuple network's expectimax play on the device (csrc/tfe_ntuple_search.hip: pulse_tfe_nt_search,
-pulse_tfe_nt_evaluate_search) against the host's statement of it (search_nt_on_host; tests/tfe_search_host.py: the oracle's environment
+pulse_tfe_nt_evaluate_search) against the host's statement of it (search_nt_on_host; tests/tfe_nt_host.py: the oracle's environment
 under it).  Every comparison is exact: integers word for word, float64 as bit patterns.  Every buffer a launch is handed sits between
 guard words.
 
@@ -16,7 +16,8 @@ import pytest
 
 from tests.tfe_gpu_support import guarded, guards_intact
 from tests.tfe_nt_support import BOARD_ID0, CRAFTED, TUPLES, search_agent, search_outputs, weights
-from tests.tfe_search_host import key_of, search_games_on_host
+from tests.tfe_nt_host import nt_games_on_host
+from tests.tfe_search_host import key_of
 
 pytestmark = pytest.mark.gpu
 
@@ -28,8 +29,8 @@ _agent = functools.partial(search_agent, GAMES, MAX_STEPS, SEED)
 @functools.lru_cache(maxsize=None)
 def _host_games(name, epsilon, symmetric=True, keep_boards=None):
     from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
-    return search_games_on_host(GAMES, MAX_STEPS, epsilon, 1.0, weights(name), TUPLES, symmetric, SEED, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, BOARD_ID0, ROUND,
-                                keep_boards=keep_boards)
+    return nt_games_on_host(GAMES, MAX_STEPS, epsilon, 1.0, weights(name), TUPLES, symmetric, SEED, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, BOARD_ID0, ROUND,
+                            depth=1, record=False, keep_boards=keep_boards)
 
 
 @functools.lru_cache(maxsize=None)

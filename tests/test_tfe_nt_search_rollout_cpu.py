@@ -1,5 +1,5 @@
 """The 2048 n-tuple network's training roll-out under expectimax search without a GPU: the library's new entry
-point with its refusals, the Python layer's depth check, the host's statement of the recording games (tests/tfe_search_rollout_host.py)
+point with its refusals, the Python layer's depth check, the host's statement of the recording games (tests/tfe_nt_host.py)
 against the evaluation's games and against the one-ply roll-out, one board worked by hand, and what the compiler made of the kernels."""
 import ctypes as C
 import functools
@@ -10,10 +10,10 @@ import numpy as np
 import pytest
 
 from tests.native_args import assert_refusals
+from tests.tfe_nt_host import nt_games_on_host
 from tests.tfe_nt_support import BOARD_ID0, CASES, CRAFTED, P, ROLLOUT_UNIT, TUPLES, assert_exports, assert_no_scratch, bits, opts, weights
 from tests.tfe_nt_support import nt as _nt
-from tests.tfe_search_host import key_of, search_games_on_host
-from tests.tfe_search_rollout_host import search_rollout_on_host
+from tests.tfe_search_host import key_of
 
 NAME = "pulse_tfe_nt_rollout_search"
 GAMES, MAX_STEPS, EPSILON, SEED, ROUND = 17, 192, .25, 2312, 0           # the shape of tests/test_tfe_nt_search_gpu.py
@@ -81,12 +81,12 @@ def test_python_layer():
 # ------------------------------------------------------------------ the host's statement of the recording games
 @functools.lru_cache(maxsize=None)
 def _recorded(gamma=1.0):
-    return search_rollout_on_host(GAMES, MAX_STEPS, EPSILON, gamma, weights("seeded"), TUPLES, True, *_seeds())
+    return nt_games_on_host(GAMES, MAX_STEPS, EPSILON, gamma, weights("seeded"), TUPLES, True, *_seeds(), depth=1)
 
 
 def test_recording_does_not_change_play():
     got = _recorded()
-    want = search_games_on_host(GAMES, MAX_STEPS, EPSILON, 1.0, weights("seeded"), TUPLES, True, *_seeds())
+    want = nt_games_on_host(GAMES, MAX_STEPS, EPSILON, 1.0, weights("seeded"), TUPLES, True, *_seeds(), depth=1, record=False)
     for k in ("keys", "steps", "moved", "lengths", "total_score", "episode_reward", "final_boards"):
         assert np.array_equal(got[k], want[k]), k
     assert all(got[k] == want[k] for k in ("ended", "truncated", "capped", "greedy")) and "values" not in want
@@ -101,7 +101,7 @@ def test_the_recorded_values_are_the_networks():
     assert np.unique(want).size > played.sum() // 2 and not got["values"][~played].any()
     # ... and not the search's: on the first boards, q of the chosen move is another number
     from tests.tfe_host import pack_boards
-    first = search_games_on_host(GAMES, 1, 0.0, 1.0, weights("seeded"), TUPLES, True, *_seeds(), keep_boards="before")
+    first = nt_games_on_host(GAMES, 1, 0.0, 1.0, weights("seeded"), TUPLES, True, *_seeds(), depth=1, record=False, keep_boards="before")
     look = nt.search_nt_on_host(pack_boards(first["boards"][0]), weights("seeded"), TUPLES, True, 1.0, _seeds()[2], ROUND)
     q = look["q"][np.arange(GAMES), look["action"]]
     v = nt.value_on_host(look["after"][np.arange(GAMES), look["action"]], weights("seeded"), TUPLES, True)
@@ -109,9 +109,8 @@ def test_the_recorded_values_are_the_networks():
 
 
 def test_gamma_zero_is_the_one_ply_rollout():
-    from tests.tfe_host import rollout_nt_on_host
     got = _recorded(0.0)
-    want = rollout_nt_on_host(GAMES, MAX_STEPS, EPSILON, 0.0, weights("seeded"), TUPLES, True, *_seeds())
+    want = nt_games_on_host(GAMES, MAX_STEPS, EPSILON, 0.0, weights("seeded"), TUPLES, True, *_seeds())
     for k in ("keys", "steps", "moved", "lengths", "total_score", "episode_reward"):
         assert np.array_equal(got[k], want[k]), k
     assert np.array_equal(bits(got["values"]), bits(want["values"])) and want["values"].any() and int(want["lengths"].sum()) > GAMES
@@ -145,7 +144,7 @@ def test_one_board_worked_by_hand():
     assert int(look["action"][0]) == 2
     assert nt.value_on_host(look["after"][0, [0, 2]], w, tuples, False).tolist() == [2.5, 2.5]
     boards0 = (1 << np.array(CRAFTED["one_merge"], dtype=np.int32)).reshape(1, 4, 4)
-    got = search_rollout_on_host(1, 1, 0.0, 1.0, w, tuples, False, 11, 12, 1, 500, 0, boards0=boards0)
+    got = nt_games_on_host(1, 1, 0.0, 1.0, w, tuples, False, 11, 12, 1, 500, 0, depth=1, boards0=boards0)
     assert got["lengths"].tolist() == [1] and int(got["keys"][0, 0]) == right and got["total_score"].tolist() == [16]
     assert got["values"][0, 0] == 2.5 and int(got["steps"][0, 0]) == 18 and got["ended"] == 0 and got["greedy"] == 1
 

@@ -1,5 +1,5 @@
 """The 2048 n-tuple network's training roll-out under expectimax search on the device (DESIGN.md section 13.5;
-csrc/tfe_ntuple_search_rollout.hip: pulse_tfe_nt_rollout_search) against the host's statement of it (tests/tfe_search_rollout_host.py:
+csrc/tfe_ntuple_search_rollout.hip: pulse_tfe_nt_rollout_search) against the host's statement of it (tests/tfe_nt_host.py:
 the oracle's environment under search_nt_on_host, recording value_on_host of the chosen afterstates).  Every comparison is exact:
 integers word for word, float64 as bit patterns.  Every buffer a launch is handed sits between guard words, and the rows of keys /
 values / steps at and beyond a game's length must keep what they held.
@@ -35,11 +35,10 @@ def _agent(layers, name, epsilon, symmetric=True, **kw):
 @functools.lru_cache(maxsize=None)
 def _host_games(layers, name, epsilon, symmetric=True, gamma=1.0):
     from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
-    from tests.tfe_host import rollout_nt_on_host
-    from tests.tfe_search_rollout_host import search_rollout_on_host
+    from tests.tfe_nt_host import nt_games_on_host
     games, max_steps, seed = SHAPE[layers or 1]
     args = (games, max_steps, epsilon, gamma, weights(name), TUPLES, symmetric, seed, seed ^ AGENT_KEY, seed ^ TIE_KEY, BOARD_ID0, ROUND)
-    return search_rollout_on_host(*args, layers=layers) if layers else rollout_nt_on_host(*args)
+    return nt_games_on_host(*args, depth=layers)
 
 
 def _launched(a, launch):

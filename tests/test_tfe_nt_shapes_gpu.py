@@ -15,7 +15,7 @@ pulse_tfe_nt_rollout_from, so that nibbles up to 15 enter feature indices in pla
 
 Out of scope: the evaluation launches take no `start`, so the cap inside pulse_tfe_nt_evaluate* is reachable only through play_game's
 one shared text, which the restarted roll-outs below run with Record; two-layer roll-outs from late boards have no host statement
-(rollout_from_on_host: layers in (0, 1)); no test here reads kernel assembly."""
+(nt_games_on_host: `start` needs depth in (0, 1)); no test here reads kernel assembly."""
 import functools
 import time
 
@@ -24,6 +24,8 @@ import pytest
 
 from tests.test_tfe_nt_restart_gpu import MODES, START_PATTERN, _assert_games, _launched, _set_start, _start_of, _with_restart
 from tests.tfe_gpu_support import PER_GAME, assert_rollout, guard, guarded, guards_intact, read
+from tests.tfe_nt_host import nibbles as _nibbles
+from tests.tfe_nt_host import nt_games_on_host
 from tests.tfe_nt_support import (BOARD_ID0, CRAFTED, MORE, PER_MOVE, ROUNDS, SEED, SHAPES, bits, late_start, learner_agent, learner_round, nt,
                                   search_agent, search_outputs, weights)
 
@@ -42,11 +44,6 @@ LATE_EPSILON, ROUND = {0: .05, 1: .25}, 0                                  # by 
 def _seeds(seed):
     from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
     return seed, seed ^ AGENT_KEY, seed ^ TIE_KEY
-
-
-def _nibbles(keys):
-    """the 16 nibbles of packed boards, on a new last axis"""
-    return (np.asarray(keys, dtype=np.uint64)[..., None] >> (np.uint64(4) * np.arange(16, dtype=np.uint64))) & np.uint64(15)
 
 
 @functools.lru_cache(maxsize=None)
@@ -98,14 +95,12 @@ def test_search_equals_the_mirror_at_every_shape(shape, symmetric):
 
 # ------------------------------------------------------------------ 2. three learner rounds at every shape
 def _round(a, coherence, where, least=8):
-    """learner_round with the roll-out held to rollout_nt_on_host on the weights the round played on -- the host's counts asserted
+    """learner_round with the roll-out held to nt_games_on_host on the weights the round played on -- the host's counts asserted
     before the device's records are compared: at least `least` games end and as many are cut -- and, with tc, the third accumulator,
     tc_stats' differences, E and A"""
-    from tests.tfe_host import rollout_nt_on_host
-
     def after_learn(a, h):
-        want = rollout_nt_on_host(a.n_games, a.max_steps, a.epsilon, a.gamma, h.policy, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
-                                  a.round_board_id0(), a.round)
+        want = nt_games_on_host(a.n_games, a.max_steps, a.epsilon, a.gamma, h.policy, a.tuples, a.symmetric, a.env_seed, a.agent_seed, a.tie_seed,
+                                a.round_board_id0(), a.round)
         out = dict(want_ended=want["ended"], want_cut=want["truncated"], want_capped=want["capped"])
         assert want["ended"] >= least and want["truncated"] >= least and want["ended"] + want["truncated"] == a.n_games, (where, out)
         assert_rollout(h.got, want, where, PER_MOVE)
@@ -190,15 +185,14 @@ def test_the_evaluations_play_the_hosts_games_at_every_shape(shape, epsilon):
       default, epsilon 0: one ply 4/61 (6,184), search 0/65 (6,240); epsilon .25: 8/57 (6,152) and 0/65 (6,240)"""
     import torch
     from pulselib_amd.agents.tfe_ntuple_td_gpu import EVAL_SUMMARY
-    from tests.tfe_host import eval_words, rollout_nt_on_host
-    from tests.tfe_search_host import search_games_on_host
+    from tests.tfe_host import eval_words
     (games, max_steps, seed), tuples = LATE, SHAPES[shape]
     w = _rounds("eight", True, "td0")[0].weights() if shape == "eight" else _small_weights(shape)
     assert w.any()
     args = (games, max_steps, epsilon, 1.0, w, tuples, True, *_seeds(seed), BOARD_ID0, ROUND)
     a = _late_agent(shape, True, epsilon)
     a.weights_dev.copy_(torch.from_numpy(w.copy()))
-    for name, want, play in (("one ply", rollout_nt_on_host(*args), a.evaluate), ("search", search_games_on_host(*args), a.evaluate_search)):
+    for name, want, play in (("one ply", nt_games_on_host(*args), a.evaluate), ("search", nt_games_on_host(*args, depth=1, record=False), a.evaluate_search)):
         assert want["ended"] + want["truncated"] == games and int(want["lengths"].sum()) > 32 * games, name
         ev = play(epsilon=epsilon, board_id0=BOARD_ID0, per_game=True)
         assert np.array_equal(ev["total_score"], want["total_score"]) and np.array_equal(ev["lengths"], want["lengths"]), name
@@ -218,11 +212,11 @@ def _late_games(shape, mode, symmetric):
     """The host's games from late_start(65, 3), with what they are asserted to hold: at least 8 capped games, 8 ended ones and 8 cut at
     max_steps without a 32,768 tile; nibble 15 in recorded afterstates; a capped game whose last byte has no terminal bit.  Returns
     (the games, the `start` the launch is to leave, bool[B]: the capped games)."""
-    from tests.tfe_restart_host import rollout_from_on_host
     (games, max_steps, seed), (layers, backed) = LATE, MODES[mode]
     start = late_start(games, 3)
-    want, left = rollout_from_on_host(start, games, max_steps, LATE_EPSILON[layers], 1.0, _small_weights(shape), SHAPES[shape], symmetric, *_seeds(seed),
-                                      BOARD_ID0, ROUND, layers=layers, backed=backed)
+    want = nt_games_on_host(games, max_steps, LATE_EPSILON[layers], 1.0, _small_weights(shape), SHAPES[shape], symmetric, *_seeds(seed), BOARD_ID0, ROUND,
+                            depth=layers, backed=backed, start=start)
+    left = want["start_left"]
     L, rows = want["lengths"].astype(np.int64), np.arange(games)
     played = np.arange(max_steps)[:, None] < L[None, :]
     fifteen = (_nibbles(want["keys"]) == 15).any(axis=2) & played

@@ -13,6 +13,7 @@ import pytest
 
 from tests import tfe_host
 from tests.native_args import PTR, assert_refusals, resource_usage
+from tests.tfe_nt_host import nt_games_on_host
 from tests.tfe_nt_staged_support import STAGE_TILES, adds_per_stage, staged, stages_struct
 from tests.tfe_nt_support import (BOARD_ID0, CASES, LAMBDA, ROOT, SEARCH_CASES, STEP_SIZE, V, X, Y, assert_no_scratch, play_kernels, bits, opts)
 from tests.tfe_nt_support import nt as _nt
@@ -202,7 +203,7 @@ def _host_round(staged_tuples):
     one = (np.random.default_rng(5).standard_normal(131072) * 4).astype(np.float32)
     tuples = staged(SMALL) if staged_tuples else SMALL
     w = np.tile(one, 3) if staged_tuples else one
-    rec = tfe_host.rollout_nt_on_host(GAMES, MAX_STEPS, .25, 1.0, w, tuples, True, SEED, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, BOARD_ID0, 0)
+    rec = nt_games_on_host(GAMES, MAX_STEPS, .25, 1.0, w, tuples, True, SEED, SEED ^ AGENT_KEY, SEED ^ TIE_KEY, BOARD_ID0, 0)
     acc = np.zeros((len(w), 2), dtype=np.int64)
     counts = nt.learn_nt_on_host(rec["keys"], rec["values"], rec["steps"], rec["lengths"], tuples, True, 1.0, acc)
     return rec, acc, counts, w

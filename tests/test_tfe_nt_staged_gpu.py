@@ -18,10 +18,10 @@ import numpy as np
 import pytest
 
 from tests.tfe_gpu_support import PATTERNS, assert_rollout, guard, guarded, guards_intact, read
+from tests.tfe_nt_host import nt_games_on_host
 from tests.tfe_nt_staged_support import STAGE_TILES, UNREACHED, adds_per_stage, boards, staged, staged_weights, stages_struct
 from tests.tfe_nt_support import (BOARD_ID0, BUFFERS, GAMES, MAX_STEPS, PER_MOVE, SEED, TUPLES, bits, learner_agent, learner_round, nt, plain_learner,
                                   search_outputs, weights)
-from tests.tfe_restart_host import rollout_from_on_host
 
 pytestmark = pytest.mark.gpu
 
@@ -81,13 +81,13 @@ def _host_games(layers, symmetric):
     """the host's games of the shape from reset on the staged weights (at one layer with the backed values: recording them does not
     change play), once per session"""
     w = staged_weights(TUPLES, S, DIVISOR[layers])
-    want, left = rollout_from_on_host(np.zeros(GAMES, dtype=np.uint64), GAMES, MAX_STEPS, EPSILON, 1.0, w, staged(), symmetric, *_seeds(), BOARD_ID0, ROUND,
-                                      layers=layers, backed=bool(layers))
+    zeros = np.zeros(GAMES, dtype=np.uint64)
+    want = nt_games_on_host(GAMES, MAX_STEPS, EPSILON, 1.0, w, staged(), symmetric, *_seeds(), BOARD_ID0, ROUND, depth=layers, backed=bool(layers), start=zeros)
     played = np.arange(MAX_STEPS)[:, None] < want["lengths"][None, :]
     per_stage = np.bincount(nt().stage_of_keys_on_host(want["keys"][played], STAGE_TILES), minlength=S)
     print("layers", layers, "symmetric", symmetric, "ended", want["ended"], "cut", want["truncated"], "afterstates per stage", per_stage.tolist())
-    assert (per_stage > 0).all() and want["ended"] >= 1 and want["truncated"] >= 1 and not left.any()
-    plain = rollout_from_on_host(np.zeros(GAMES, dtype=np.uint64), GAMES, 32, EPSILON, 1.0, w[:W], TUPLES, symmetric, *_seeds(), BOARD_ID0, ROUND, layers=layers)[0]
+    assert (per_stage > 0).all() and want["ended"] >= 1 and want["truncated"] >= 1 and not want["start_left"].any()
+    plain = nt_games_on_host(GAMES, 32, EPSILON, 1.0, w[:W], TUPLES, symmetric, *_seeds(), BOARD_ID0, ROUND, depth=layers, start=zeros)
     assert not np.array_equal(plain["keys"][:32], want["keys"][:32])         # the stages change play: slice 0 alone plays other games
     return want
 
@@ -391,7 +391,8 @@ def test_a_restarted_staged_round_is_the_hosts():
     assert 8 <= picked[0] <= GAMES - 8 and np.array_equal(_start_of(a), left) and a.round == 1
     policy = a.weights()
     got = _launched(a, a.rollout)
-    want, kept = rollout_from_on_host(left, GAMES, MAX_STEPS, EPSILON, 1.0, policy, a.tuples, True, *_seeds(), a.round_board_id0(), a.round, layers=0)
+    want = nt_games_on_host(GAMES, MAX_STEPS, EPSILON, 1.0, policy, a.tuples, True, *_seeds(), a.round_board_id0(), a.round, start=left)
+    kept = want["start_left"]
     assert_rollout(got, want, "round 1", PER_MOVE)
     assert np.array_equal(_start_of(a), kept) and np.array_equal(kept, left) and got["moves"] == int(want["lengths"].sum())
     first = n.stage_of_keys_on_host(want["keys"][0], STAGE_TILES)

@@ -1,11 +1,11 @@
 """The host's side of the n-tuple network's games continued across rounds (csrc/tfe_ntuple_continue.hip), for
-the tests: one round of continued games on the host -- the host's roll-out from `start` (tests/tfe_restart_host.py), then
+the tests: one round of continued games on the host -- the host's roll-out from `start` (tests/tfe_nt_host.py), then
 continue_pick_on_host on its records -- with the bookkeeping a test keeps on its own beside the carries, and the chain of such rounds
 under fixed weights.  A helper, not a test."""
 import numpy as np
 
 from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
-from tests.tfe_restart_host import rollout_from_on_host, usable_on_host
+from tests.tfe_nt_host import nt_games_on_host, usable_on_host
 
 WORDS = len(nt.FINISHED_SUMMARY) + nt.EVAL_BINS
 
@@ -41,11 +41,12 @@ def pick_on_host(c, games, max_steps, env_seed, board_id0):
     return words, cut
 
 
-def round_on_host(c, n_games, max_steps, epsilon, gamma, weights, tuples, symmetric, env_seed, agent_seed, tie_seed, board_id0, round, layers=0, backed=False):
-    """One round of continued games: the host's roll-out from c.start (board_id0: the round's first board), then pick_on_host.  Every
-    board of c.start is usable, so the roll-out leaves `start` as it was.  Returns (the games, the words the pick adds, cut)."""
-    games, left = rollout_from_on_host(c.start, n_games, max_steps, epsilon, gamma, weights, tuples, symmetric, env_seed, agent_seed, tie_seed, board_id0, round,
-                                       layers=layers, backed=backed)
-    assert np.array_equal(left, c.start)
+def round_on_host(c, n_games, max_steps, epsilon, gamma, weights, tuples, symmetric, env_seed, agent_seed, tie_seed, board_id0, round, **options):
+    """One round of continued games: the host's roll-out from c.start (board_id0: the round's first board; `options`:
+    nt_games_on_host's depth and backed), then pick_on_host.  Every board of c.start is usable, so the roll-out leaves `start` as it
+    was.  Returns (the games, the words the pick adds, cut)."""
+    games = nt_games_on_host(n_games, max_steps, epsilon, gamma, weights, tuples, symmetric, env_seed, agent_seed, tie_seed, board_id0, round, start=c.start,
+                             **options)
+    assert np.array_equal(games["start_left"], c.start)
     words, cut = pick_on_host(c, games, max_steps, env_seed, board_id0)
     return games, words, cut

@@ -1,14 +1,13 @@
 """The host's side of the 2048 agents (csrc/tfe_mc.hip, csrc/tfe_ntuple.hip), for the tests: ONE game loop on the oracle's environment
-(oracle.tfe_reset / oracle.tfe_step) and a policy per roll-out kernel -- the Q table plain or canonical, the afterstate table, the
-n-tuple network -- each under the kernel's rule as the agent modules state it, so that a device roll-out can be compared word for word;
-the keys of many boards at once, the oracle's move without its spawn, and an evaluation's 24 counters as numpy reductions.
-A helper, not a test."""
+(oracle.tfe_reset / oracle.tfe_step) and a policy per roll-out kernel -- the Q table plain or canonical and the afterstate table here,
+the n-tuple network's in tests/tfe_nt_host.py -- each under the kernel's rule as the agent modules state it, so that a device roll-out
+can be compared word for word; the keys of many boards at once, the oracle's move without its spawn, and an evaluation's 24 counters
+as numpy reductions.  A helper, not a test."""
 import functools
 
 import numpy as np
 
 from oracle import oracle as orc
-from pulselib_amd.agents import tfe_ntuple_td_gpu as nt
 from pulselib_amd.agents import tfe_on_policy_mc_gpu as mc
 
 MOVE_SEED = 0x5EED
@@ -152,21 +151,6 @@ class _AfterTable(_Policy):
         return first
 
 
-class _NTuple(_Policy):
-    """pulse_tfe_nt_rollout: greedy_nt_on_host over all live games at once, draws from the package's vectorised Philox; bit 7 is game over"""
-    philox_many, counters = staticmethod(nt.philox_many_on_host), ("greedy",)
-
-    def choose(self, t, ids, live, boards):
-        choice = nt.greedy_nt_on_host(pack_boards(boards), self.weights, self.tuples, self.symmetric, self.gamma, self.tie_seed, self.round)
-        assert (choice["action"] >= 0).all()                               # a board that is not over has a candidate
-        greedy, uniform = self.branch(t, ids)
-        a, rows = np.where(greedy, choice["action"], uniform), np.arange(live.size)
-        return choice["after"][rows, a], a, a, choice["rewards"][rows, a], choice["values"][rows, a]
-
-    def flag(self, live, keys, actions, over):
-        return over
-
-
 # ------------------------------------------------------------------ the game loop
 def _play(policy, n_games, n, max_steps, env_seed, board_id0, boards0=None, keep_boards=None, tile_cap=None):
     """The games of one roll-out launch under `policy`.  Returns a dict: keys uint64[max_steps, B], steps uint8[max_steps, B] and moved
@@ -228,14 +212,6 @@ def rollout_after_on_host(n_games, n, max_steps, epsilon, gamma, frac_bits, tabl
     `present` counts the moves where one of the four afterstates had an entry."""
     policy = _AfterTable(n_games, epsilon, agent_seed, tie_seed, round, table=table, canonical=canonical, gamma=gamma, frac_bits=frac_bits)
     return _play(policy, n_games, n, max_steps, env_seed, board_id0, keep_boards=keep_boards)
-
-
-def rollout_nt_on_host(n_games, max_steps, epsilon, gamma, weights, tuples, symmetric, env_seed, agent_seed, tie_seed, board_id0, round,
-                       boards0=None):
-    """pulse_tfe_nt_rollout on the host: 4 x 4, a game stops where it is over or holds a 32,768 tile; `greedy` counts the moves not
-    decided by the epsilon branch."""
-    policy = _NTuple(n_games, epsilon, agent_seed, tie_seed, round, weights=weights, tuples=tuples, symmetric=symmetric, gamma=gamma)
-    return _play(policy, n_games, 4, max_steps, env_seed, board_id0, boards0=boards0, tile_cap=32768)
 
 
 def values_of(table):

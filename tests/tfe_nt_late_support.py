@@ -11,9 +11,9 @@ from types import SimpleNamespace
 import numpy as np
 
 from tests.tfe_continue_host import Carried, round_on_host
+from tests.tfe_nt_host import nibbles, nt_games_on_host
 from tests.tfe_nt_staged_support import staged, staged_weights
-from tests.tfe_nt_support import BOARD_ID0, CRAFTED, MORE, SEED, SHAPES, late_start, nt, weights
-from tests.tfe_restart_host import rollout_from_on_host
+from tests.tfe_nt_support import BOARD_ID0, CRAFTED, MORE, SEED, SHAPES, late_start, nt, seeds, weights
 from tests.tfe_search_host import key_of
 
 # Four stages, the ABI's limit.  Stage 0: boards below the 8 tile (late_start's games with g % 4 == 3 begin at reset); stage 1: nibbles
@@ -42,16 +42,6 @@ ADAPTIVE_FLOOR = dict(deep=25, shallow=25, q_differs=20, action_differs=3)
 SEARCH_ROUND = 3                                                           # the coins of another round than the games'
 
 
-def seeds(seed):
-    from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
-    return seed, seed ^ AGENT_KEY, seed ^ TIE_KEY
-
-
-def nibbles(keys):
-    """the 16 nibbles of packed boards, on a new last axis"""
-    return (np.asarray(keys, dtype=np.uint64)[..., None] >> (np.uint64(4) * np.arange(16, dtype=np.uint64))) & np.uint64(15)
-
-
 def late_weights(shape, layers):
     """float32[4 W] of the shape, read-only: a slice of its own per stage, / 64 one ply deep so that play is led by the rewards"""
     return staged_weights(SHAPES[shape], S, DIVISOR[layers])
@@ -72,8 +62,9 @@ def late_games(shape, symmetric, layers, tiles=LATE_TILES):
     capped / dead / cut bool[B], seed."""
     seed = late_seed(shape, symmetric, layers)
     start = late_start(GAMES, 3)
-    want, left = rollout_from_on_host(start, GAMES, MAX_STEPS, EPSILON, 1.0, late_weights(shape, layers), staged(SHAPES[shape], tiles), symmetric, *seeds(seed),
-                                      BOARD_ID0, ROUND, layers=layers, backed=bool(layers))
+    want = nt_games_on_host(GAMES, MAX_STEPS, EPSILON, 1.0, late_weights(shape, layers), staged(SHAPES[shape], tiles), symmetric, *seeds(seed, BOARD_ID0, ROUND),
+                            depth=layers, backed=bool(layers), start=start)
+    left = want["start_left"]
     L, rows = want["lengths"].astype(np.int64), np.arange(GAMES)
     played = np.arange(MAX_STEPS)[:, None] < L[None, :]
     stage = nt().stage_of_keys_on_host(want["keys"].reshape(-1), tiles).reshape(MAX_STEPS, GAMES)
@@ -177,7 +168,7 @@ def continued_rounds(case):
     counts = dict(capped=0, capped_at_k=0, dead_at_k=0, resumed=0, finished=0, continued=[])
     for r in range(CONTINUE_ROUNDS):
         start = c.start.copy()
-        g, words, cut = round_on_host(c, games, K, EPSILON, 1.0, w, tuples, True, *seeds(seed), BOARD_ID0 + games * r, r, layers=layers, backed=bool(layers))
+        g, words, cut = round_on_host(c, games, K, EPSILON, 1.0, w, tuples, True, *seeds(seed, BOARD_ID0 + games * r, r), depth=layers, backed=bool(layers))
         L, rows = g["lengths"].astype(np.int64), np.arange(games)
         capped, dead = (nibbles(g["keys"][L - 1, rows]) == 15).any(axis=1), g["steps"][L - 1, rows] >> 7 != 0
         assert words[7] == int(capped.sum()) and not (cut & (capped | dead)).any()

@@ -1,7 +1,7 @@
 """What the two test files of the 2048 n-tuple network's weight sets by tile stage share (tests/test_tfe_nt_staged_*.py; DESIGN.md
 section 13.9): the stage tiles of the tests, the stages struct, weights with a slice of its own per stage, boards on either side of
 every threshold, and the count of adds per stage.  The stages travel to the host mirrors on `tuples` (with_stages), so
-tests/tfe_host.py, tests/tfe_search_host.py, tests/tfe_restart_host.py and tests/tfe_nt_support.py serve staged networks as they are.
+tests/tfe_host.py, tests/tfe_nt_host.py, tests/tfe_search_host.py and tests/tfe_nt_support.py serve staged networks as they are.
 A helper, not a test."""
 import functools
 

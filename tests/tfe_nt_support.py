@@ -288,6 +288,13 @@ BUFFERS = ("weights_dev", "acc", "keys", "values", "steps", "lengths", "total_sc
 PER_MOVE = ("keys", "values", "steps")
 
 
+def seeds(seed, board_id0=BOARD_ID0, round=0):
+    """(env_seed, agent_seed, tie_seed, board_id0, round) as the agent derives them from its `seed`: the tail of the host roll-out's
+    positional arguments"""
+    from pulselib_amd.agents.tfe_common import AGENT_KEY, TIE_KEY
+    return seed, seed ^ AGENT_KEY, seed ^ TIE_KEY, board_id0, round
+
+
 def plain_learner(n_games=GAMES, **kw):
     """the agent of the regime, `kw` over it, on buffers of its own"""
     import torch
